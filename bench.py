@@ -9,11 +9,15 @@ resident in HBM.  Default workload at every N: BASELINE.json configs[2] -- MW-SI
 (80 x 800 mels) per GPU, the largest single-GPU configuration; utterances are independent, so N ranks run N such
 batches (weak scaling, no data-path collective; RCCL only carries the barrier and the max-over-ranks of the timing).
 Started without a launcher and with --gpus N > 1 the script starts the N ranks itself (one process per GPU, RCCL).
-Rank 0 prints ONE JSON line: the default workload's throughput, max|delta| against the float64 oracle, the roofline
-of the dominant kernel and of the bandwidth-type stages, the CPU baseline (best leg of a thread sweep), and as secondary
-fields the other four BASELINE configurations: configs[0]'s 3 s utterance and configs[1] (1 x 10 s) on the GPU,
-configs[3] (256 utterances sharded over the ranks, strong scaling, with its own max|delta|) and configs[4] (64 streams).
+Rank 0 prints ONE JSON line: the default workload's throughput and ms per timed step.  A plain run does nothing else:
+set-up, warm-up, the K timed steps, the outputs (--dump-outputs DIR) and the line.
+With --full the line also holds max|delta| against the float64 oracle, the roofline of the dominant kernel and of the
+bandwidth-type stages, the CPU baseline (best leg of a thread sweep), and as secondary fields the other four BASELINE
+configurations: configs[0]'s 3 s utterance and configs[1] (1 x 10 s) on the GPU, configs[3] (256 utterances sharded over
+the ranks, strong scaling, with its own max|delta|) and configs[4] (64 streams).
 max|delta| is computed from the output buffer the timed steps wrote (prefix property), not from a separate forward.
+--dump-outputs DIR writes what the last timed step of the main workload computed as DIR/<name>.npy (float32; inputs and
+weights are seeded, so two builds can be compared output for output).
 """
 import argparse
 import json
@@ -81,6 +85,7 @@ DELTA_MARGIN = 12                 # frames at the end of a prefix that reach int
 DELTA_TOL = 1e-4                  # tolerance of max|delta|, relative to max(1, max|oracle audio|) (tests/test_gpu_parity.py)
 PORT_IN_USE_EXIT = 98             # exit status of a rank that found the rendezvous port taken (EADDRINUSE)
 REJECTED_ENV = ("MBX_WG_ABLATE",)  # switches of timing experiments that produce wrong audio: never measured
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: at most this many bytes in all
 
 
 def mbx_env():
@@ -106,6 +111,16 @@ def build_engine(voice, overrides=None, **engine_kw):
         wt = WaveTables(sample_rate=dims.pulse_rate, **cfg["mbexwn_config"]["wavetable_config"])
         _ENGINES[key] = (cfg, raw, wt, dims, MBExWNEngine(cfg, raw, wt, **engine_kw))
     return _ENGINES[key]
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as <outdir>/<name>.npy in float32.  Past DUMP_BUDGET_BYTES in all, a fixed sample stands
+    in for each array: every k-th element of its flat data, k the same for all of them."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {kk: np.ascontiguousarray(vv, dtype=np.float32) for kk, vv in arrays.items()}
+    stride = -(-sum(vv.nbytes for vv in arrays.values()) // DUMP_BUDGET_BYTES)
+    for name, vv in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), vv if stride <= 1 else vv.reshape(-1)[::stride])
 
 
 def synthetic_batch(rng, batch, frames, steps_per_frame):
@@ -249,10 +264,12 @@ def delta_vs_reference_f32(torch):
     the golden cases speech800 / speech240 (tests/golden/make_reference_long.py: the reference's own MBExWN.call executed in
     float32).  The float32 phase integrator of the reference makes this distance grow with the utterance (DESIGN.md
     section 5), so it is stated per length; tolerance 1e-4 max(1, |audio|)."""
-    path = os.path.join(ROOT, "tests", "golden", "reference_long_f32.npz")
-    if not os.path.exists(path):
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import golden_npz                                   # the archive is committed in parts of <= 1 MiB
+    try:
+        gold = golden_npz.load(os.path.join(ROOT, "tests", "golden", "reference_long_f32.npz"))
+    except FileNotFoundError:
         return {}
-    gold = np.load(path)
     # the golden cases' own variables (tests/helpers.py::build_case: seed 1234 with bias and PReLU jitter), not the bench's
     from mbexwn_vocoder_amd.config import ModelDims, canonical_config
     from mbexwn_vocoder_amd.engine import MBExWNEngine
@@ -305,8 +322,9 @@ def time_steps(step, steps, warmup, fence):
     return fence.max_over_ranks(time.perf_counter() - t0)
 
 
-def run_batch(args, name, rank, world, fence, torch, profile, steps=None, warmup=None):
-    """configs[0..2]: one padded batch per GPU.  Returns (result dict, context for the roofline / delta legs)."""
+def run_batch(args, name, rank, world, fence, torch, profile, steps=None, warmup=None, keep_output=False):
+    """configs[0..2]: one padded batch per GPU.  Returns (result dict, context for the roofline / delta legs); with
+    keep_output the result's "_outputs" holds the audio of the last timed step."""
     voice, batch, frames = WORKLOADS[name]
     cfg, raw, wt, dims, eng = build_engine(voice, WORKLOAD_OVERRIDES.get(name), **ENGINE_KW.get(name, {}))
     rng = np.random.default_rng(42 + rank)
@@ -329,6 +347,8 @@ def run_batch(args, name, rank, world, fence, torch, profile, steps=None, warmup
            "batch_per_gpu": batch, "frames": frames, "value": samples / elapsed, "x_realtime": samples / elapsed / 24000.0,
            "ms_per_step": elapsed / steps * 1e3, "steps": steps, "scaling": "weak",
            "gate_form": eng.gate_form(batch, frames), "conv_form": eng.conv_form_info()}
+    if keep_output:
+        res["_outputs"] = {"audio": out.cpu().numpy()}
     ctx = {"cfg": cfg, "raw": raw, "wt": wt, "dims": dims, "eng": eng, "mel_h": mel_h, "noise_h": noise_h, "batch": batch,
            "frames": frames, "timed_out": timed_out, "timed_full": timed_full, "delta_items": delta_items, "stages": None}
     if profile:
@@ -581,7 +601,7 @@ def roofline(ctx, workload):
             "stages": stage_list}
 
 
-def run_sharded(args, name, rank, world, dist, fence, torch, steps=None, warmup=None, check_delta=False):
+def run_sharded(args, name, rank, world, dist, fence, torch, steps=None, warmup=None, check_delta=False, keep_output=False):
     """configs[3]: every rank sees the same seeded list of utterance lengths, ShardedSynthesizer takes its LPT shard,
     stages the padded micro-batches in HBM once, and every step runs them and gathers the audio on rank 0 (RCCL, device
     tensors: no host copy between the forward pass and the collective; chunks of the shard are handed to the collective
@@ -637,6 +657,9 @@ def run_sharded(args, name, rank, world, dist, fence, torch, steps=None, warmup=
         delta = {"_delta_later": lambda: max_abs_delta_timed(
             [(f"utterance {pick} ({lengths[pick]} frames)", got, mels[pick], noises[pick])],
             cfg, raw, wt, f"forward + gather ({args.gather}) of the sharded run")}
+    if keep_output:
+        # the utterances this rank holds after the gather, in input order, back to back
+        delta["_outputs"] = {"audio": np.concatenate([aa for aa in last["res"].to_list() if aa is not None])}
     return {**delta, "workload": f"{name}: MW-{voice[:2]}-FD canonical (C={dims.wn_channels}), {n_utt} utterances U[2 s,15 s] = "
                         f"{sum(lengths) / 80:.0f} s of audio, LPT-sharded over {world} ranks (ShardedSynthesizer), padded "
                         f"micro-batches <= 16 items, device-resident chunked asynchronous gather ({args.gather}) of the audio each step",
@@ -654,7 +677,7 @@ def run_sharded(args, name, rank, world, dist, fence, torch, steps=None, warmup=
                           for nn, st in ((nn, plan_stats(lengths, nn, dims.hop_size, 16, 16 * 1200)) for nn in (1, 2, 4, 8))}}
 
 
-def run_streaming(args, name, rank, world, fence, torch, steps=None, warmup=None):
+def run_streaming(args, name, rank, world, fence, torch, steps=None, warmup=None, keep_output=False):
     """configs[4]: steady-state tick of the streaming driver -- every stream advances by `chunk` frames.  `value`
     counts the emitted audio only, inputs resident in HBM; the tick is timed on the device with HIP events (events on
     the launch stream around each tick) and, separately, host-inclusive through the Python driver."""
@@ -713,7 +736,10 @@ def run_streaming(args, name, rank, world, fence, torch, steps=None, warmup=None
             "tick_ms_host_inclusive_p99": float(np.percentile(host_ms, 99)),
             # window frames (mel-rate stages, phase) and frames of the active region (WaveNet ... overlap-add) per emitted frame
             "frames_computed_per_emitted_frame": float(np.mean(frames)) / (n_streams * chunk),
-            "wavenet_frames_per_emitted_frame": float(np.mean(act_frames)) / (n_streams * chunk)}
+            "wavenet_frames_per_emitted_frame": float(np.mean(act_frames)) / (n_streams * chunk),
+            # the audio every stream received from the last timed tick (streams in id order)
+            **({"_outputs": {"audio": np.stack([np.asarray(res[sid].cpu() if hasattr(res[sid], "cpu") else res[sid])
+                                                for sid in sorted(res)])}} if keep_output else {})}
 
 
 def visible_gpu_count():
@@ -785,9 +811,15 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: max|delta| vs the oracle, roofline and stage times, the secondary "
+                         "workloads (default workload) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary workloads (the other four configs) and the max|delta| legs: profiling runs")
+                    help="with --full: skip the secondary workloads (the other four configs) and the max|delta| legs: "
+                         "profiling runs")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-spawned ranks (default: probe a free one)")
     ap.add_argument("--gather", default="rank0", choices=["rank0", "all", "none"],
                     help="result gather of the sharded workload: on rank 0 (default), on every rank, or none (local shards)")
@@ -797,6 +829,8 @@ def main():
     args.gather = None if args.gather == "none" else args.gather
     if args.gpus < 1 or args.steps < 1:
         raise SystemExit("--gpus and --steps must be >= 1")
+    if args.dump_outputs and args.workload == "geometry_sweep":
+        raise SystemExit("--dump-outputs: the geometry sweep has no single output; pick another workload")
     for kk in REJECTED_ENV:
         if kk in os.environ:
             raise SystemExit(f"{kk} is set: it selects a timing experiment that produces wrong audio; refusing to measure")
@@ -847,18 +881,23 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
+    keep = bool(args.dump_outputs) and rank == 0
     if frames is None:
-        main_res = run_sharded(args, args.workload, rank, world, dist, fence, torch, check_delta=not args.no_secondary)
-        later = main_res.pop("_delta_later", None)
-        if later is not None:
-            main_res.update(later())
+        main_res = run_sharded(args, args.workload, rank, world, dist, fence, torch,
+                               check_delta=args.full and not args.no_secondary, keep_output=keep)
     elif isinstance(frames, tuple) or frames < 0:
-        main_res = run_streaming(args, args.workload, rank, world, fence, torch)
+        main_res = run_streaming(args, args.workload, rank, world, fence, torch, keep_output=keep)
     else:
-        main_res, ctx = run_batch(args, args.workload, rank, world, fence, torch, profile=True)
+        main_res, ctx = run_batch(args, args.workload, rank, world, fence, torch, profile=args.full, keep_output=keep)
+    outputs = main_res.pop("_outputs", None)
+    if keep:
+        dump_outputs(args.dump_outputs, outputs)
+    later = main_res.pop("_delta_later", None)
+    if later is not None:
+        main_res.update(later())
 
     secondary = {}
-    if args.workload == DEFAULT_WORKLOAD and not args.no_secondary:
+    if args.workload == DEFAULT_WORKLOAD and args.full and not args.no_secondary:
         # the other four BASELINE configurations with bounded step counts (the whole default run stays within a minute or
         # two): configs[1] at the same step count; configs[0]'s utterance size on the GPU; configs[3] (one step = 2 181 s of
         # audio) with its own max|delta| on a C = 340 utterance of the timed, gathered output; configs[4] streaming ticks
@@ -918,7 +957,7 @@ def main():
                        if kk not in ("value", "x_realtime", "ms_per_step", "steps", "scaling") and not kk.startswith("_")},
             "env": mbx_env()})
         line["config"]["parallelism"] = main_res.get("parallelism", f"utterance-sharded x{world}")
-        if ctx is not None:
+        if ctx is not None and ctx["stages"] is not None:
             if args.workload in ENGINE_KW:                  # the opt-in split precision as the main workload (profiling runs)
                 main_res_extra = {}
                 split_report(main_res_extra, ctx)
@@ -938,7 +977,7 @@ def main():
             summary = compact_summary(line, main_res, secondary)
             line["config"].update(summary)
             line["config"]["all"] = dict(summary)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cfg, raw, wt = build_engine(voice)[:3]
             line["cpu_baseline"] = cpu_baseline(cfg, raw, wt)
         print(json.dumps(line))

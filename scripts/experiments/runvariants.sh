@@ -4,7 +4,7 @@
 # per-kernel times.  The product library is never overwritten: a killed run cannot leave a wrong-output build in the tree.
 cd $GRAFT_REPO_ROOT
 for lib in "$@"; do
-  MBX_LIB_PATH=$PWD/scripts/experiments/libs/lib_$lib.so timeout -k 5 120 python bench.py --no-cpu-baseline --no-secondary $BENCH_ARGS > /tmp/b.json 2>/tmp/b.err || { echo "$lib FAILED"; tail -3 /tmp/b.err; }
+  MBX_LIB_PATH=$PWD/scripts/experiments/libs/lib_$lib.so timeout -k 5 120 python bench.py --full --no-cpu-baseline --no-secondary $BENCH_ARGS > /tmp/b.json 2>/tmp/b.err || { echo "$lib FAILED"; tail -3 /tmp/b.err; }
   python - "$lib" <<'PY'
 import json,sys
 try:

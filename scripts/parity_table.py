@@ -17,8 +17,9 @@ def main():
     import numpy as np
     import torch
     import test_gpu_long as tl
-    g32 = np.load(os.path.join(ROOT, "tests", "golden", "reference_long_f32.npz"))
-    g64 = np.load(os.path.join(ROOT, "tests", "golden", "reference_long_f64.npz"))
+    from helpers import load_golden
+    g32 = load_golden(os.path.join(ROOT, "tests", "golden", "reference_long_f32.npz"))
+    g64 = load_golden(os.path.join(ROOT, "tests", "golden", "reference_long_f64.npz"))
     table = {}
     for case in tl.LONG_CASES:
         eng = tl.get_engine(case)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condense the rocprofv3 output of scripts/profile_round.sh (gpurun_out/<tag>_*) into the files committed under
+"""Condense the rocprofv3 output of scripts/profile_round.sh ($PROFILE_OUT/<tag>_*) into the files committed under
 profiles/:
 
   <tag>_kernel_stats_<workload>.csv   rocprofv3's own --stats table of the traced run (every launch of the process)
@@ -23,7 +23,7 @@ import sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(root, "gpurun_out")
+src = os.environ.get("PROFILE_OUT") or os.path.join(root, "profile_out")
 dst = os.path.join(root, "profiles")
 os.makedirs(dst, exist_ok=True)
 summary = {}

@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
+import golden_npz  # noqa: E402
 import tf_numpy_shim as shim  # noqa: E402
 
 CASES = {
@@ -245,8 +246,8 @@ def main():
                 bundle[f"{name}/{kk}"] = arr
             print(tag, name, "audio", res["audio"].shape, float(np.abs(res["audio"]).max()))
         path = os.path.join(HERE, f"reference_forward_{tag}.npz")
-        np.savez_compressed(path, **bundle)
-        print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+        for written in golden_npz.save(path, bundle):          # parts of <= 1 MiB when the archive is larger
+            print("wrote", written, os.path.getsize(written) // 1024, "KiB")
 
 
 if __name__ == "__main__":

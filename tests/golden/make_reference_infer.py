@@ -20,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
+import golden_npz  # noqa: E402
 import tf_numpy_shim as shim  # noqa: E402
 from make_reference_forward import load_into_reference  # noqa: E402
 
@@ -89,8 +90,8 @@ def main():
         out[f"{name}/ext/env_abs"] = np.abs(np.asarray(envb))[:, :, ::8]
         print(name, "components", np.asarray(f0).shape, np.asarray(exc).shape, np.asarray(env).shape, None if gain is None else np.asarray(gain).shape)
     path = os.path.join(HERE, "reference_infer.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+    for written in golden_npz.save(path, out):                 # parts of <= 1 MiB when the archive is larger
+        print("wrote", written, os.path.getsize(written) // 1024, "KiB")
 
 
 if __name__ == "__main__":

@@ -1,11 +1,16 @@
 """Shared builders for the tests (CPU side)."""
 import functools
+import os
+import sys
 
 import numpy as np
 
 from mbexwn_vocoder_amd.config import ModelDims, canonical_config
 from mbexwn_vocoder_amd.tables import WaveTables
 from mbexwn_vocoder_amd.weights import synthetic_weights
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+from golden_npz import load as load_golden  # noqa: E402,F401 -- golden archives, whole or in parts of <= 1 MiB
 
 # the golden cases of tests/golden/make_reference_forward.py
 GOLDEN_CASES = {

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import mbexwn_oracle as orc
-from helpers import form_kwargs, GOLDEN_CASES, build_case, synthetic_inputs
+from helpers import form_kwargs, GOLDEN_CASES, build_case, load_golden, synthetic_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -147,7 +147,7 @@ def test_canon_ragged_batch_of_16(torch, monkeypatch, canon_case):
 def test_voice_reference_golden(torch, golden_dir):
     """C = 340, 2 x 41 frames, against the float32 run of the reference's own MBExWN.call."""
     from mbexwn_vocoder_amd.engine import MBExWNEngine
-    gold = np.load(os.path.join(golden_dir, "reference_forward_f32.npz"))
+    gold = load_golden(os.path.join(golden_dir, "reference_forward_f32.npz"))
     voice, overrides, batch, frames = GOLDEN_CASES["voice"]
     eng = MBExWNEngine(*build_case(voice, overrides))
     got = eng.forward(dev(torch, gold["voice/mell"]), noise=dev(torch, gold["voice/noise"])).cpu().numpy()
@@ -273,7 +273,7 @@ def test_subnet_grammar_variants_end_to_end(torch, golden_dir):
     for ii, ll in enumerate(lengths):
         single = eng.forward(dev(torch, mel[ii:ii + 1, :ll]), noise=dev(torch, noise[ii:ii + 1, :ll * 20])).cpu().numpy()[0]
         assert np.array_equal(rag[ii, :ll * 300], single)
-    gold = np.load(os.path.join(golden_dir, "reference_forward_f32.npz"))
+    gold = load_golden(os.path.join(golden_dir, "reference_forward_f32.npz"))
     out = eng.forward(dev(torch, gold["grammar/mell"]), noise=dev(torch, gold["grammar/noise"])).cpu().numpy()
     assert _maxdiff(eng.stage("f0").cpu().numpy(), gold["grammar/f0"]) <= 1e-3
     assert _maxdiff(out, gold["grammar/audio"]) <= _tol(gold["grammar/audio"])
@@ -283,7 +283,7 @@ def test_long_canonical_reference_golden(torch, golden_dir):
     """60 frames of the canonical model against the float32 run of the reference: six 1000-sample phase chunks (bit
     exact phase from the reference's own F0), the chunk-offset chain, F0-dependent lifter rows."""
     from mbexwn_vocoder_amd.engine import MBExWNEngine
-    gold = np.load(os.path.join(golden_dir, "reference_forward_f32.npz"))
+    gold = load_golden(os.path.join(golden_dir, "reference_forward_f32.npz"))
     voice, overrides, batch, frames = GOLDEN_CASES["canon60"]
     eng = MBExWNEngine(*build_case(voice, overrides))
     got = eng.forward(dev(torch, gold["canon60/mell"]), noise=dev(torch, gold["canon60/noise"])).cpu().numpy()
@@ -399,7 +399,7 @@ def test_gate_variants_and_equalized_lr_vs_reference_goldens(torch, golden_dir, 
     (:203-204,293-294) and spect_filters_preserve_energy (custom_pulsed_generator.py:817-849), against the float32 run of
     the reference's own MBExWN.call and the oracle."""
     from mbexwn_vocoder_amd.engine import MBExWNEngine
-    gold = np.load(os.path.join(golden_dir, "reference_forward_f32.npz"))
+    gold = load_golden(os.path.join(golden_dir, "reference_forward_f32.npz"))
     voice, overrides, batch, frames = GOLDEN_CASES[case]
     cfg, raw, wt = build_case(voice, overrides)
     eng = MBExWNEngine(cfg, raw, wt)
@@ -441,7 +441,7 @@ def test_subband_gain_model(torch, golden_dir, case):
     """ps_use_stft: false -- sub-band gains, interpolated and indexed exactly as the reference does it (by hop_size, first
     rows), against the reference's own run and the oracle; a ragged batch; only ["F0", .] among the parameters."""
     from mbexwn_vocoder_amd.engine import MBExWNEngine
-    gold = np.load(os.path.join(golden_dir, "reference_forward_f32.npz"))
+    gold = load_golden(os.path.join(golden_dir, "reference_forward_f32.npz"))
     voice, overrides, batch, frames = GOLDEN_CASES[case]
     cfg, raw, wt = build_case(voice, overrides)
     eng, om = MBExWNEngine(cfg, raw, wt), orc.OracleModel(cfg, raw, wt)

@@ -305,7 +305,7 @@ def test_rccl_single_rank_collectives(tmp_path):
     env = {kk: vv for kk, vv in os.environ.items() if kk not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--workload",
-                          "config4_vo_256utt", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], env=env,
+                          "config4_vo_256utt", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"], env=env,
                          capture_output=True, text=True, timeout=840)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
@@ -408,9 +408,9 @@ def test_infer_and_infer_components_against_the_reference_methods(case):
     mel (the last frame is repeated once), the parameter list of return_F0 with the reference's slices, a transposition
     factor, an external F0 contour, with and without the RMS normalisation."""
     import torch
-    from helpers import build_case
+    from helpers import build_case, load_golden
     from mbexwn_vocoder_amd.engine import MBExWNEngine
-    gold = np.load(os.path.join(ROOT, "tests", "golden", "reference_infer.npz"))
+    gold = load_golden(os.path.join(ROOT, "tests", "golden", "reference_infer.npz"))
     over = dict(SMALL)
     if case == "rmsnorm":
         over.update({"mbexwn_config:normalize_rms_from_mell": True, "mbexwn_config:normalize_rms_num_smooth_iters": 1})

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import build_case
+from helpers import build_case, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +46,7 @@ def torch():
 
 @pytest.fixture(scope="module")
 def gold(golden_dir):
-    return (np.load(os.path.join(golden_dir, "reference_long_f32.npz")), np.load(os.path.join(golden_dir, "reference_long_f64.npz")))
+    return (load_golden(os.path.join(golden_dir, "reference_long_f32.npz")), load_golden(os.path.join(golden_dir, "reference_long_f64.npz")))
 
 
 _ENGINES = {}

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import mbexwn_oracle as orc
-from helpers import form_kwargs, GOLDEN_CASES, build_case, synthetic_inputs
+from helpers import form_kwargs, GOLDEN_CASES, build_case, load_golden, synthetic_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -397,7 +397,7 @@ def test_f0_contour_in_float64_keeps_the_error_from_growing_with_the_length(torc
 @pytest.mark.parametrize("case", sorted(GOLDEN_CASES))
 def test_forward_matches_reference_goldens(torch, golden_dir, case):
     """HIP path vs the output of the reference's own model code (float32 emulation run)."""
-    gold = np.load(os.path.join(golden_dir, "reference_forward_f32.npz"))
+    gold = load_golden(os.path.join(golden_dir, "reference_forward_f32.npz"))
     voice, overrides, batch, frames = GOLDEN_CASES[case]
     eng = get_engine("gold_" + case, voice, overrides)[0]
     mel, noise = gold[f"{case}/mell"], gold[f"{case}/noise"]

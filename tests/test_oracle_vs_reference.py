@@ -6,11 +6,11 @@ import numpy as np
 import pytest
 
 from oracle.mbexwn_oracle import OracleModel
-from helpers import GOLDEN_CASES, LEAN_GOLDEN_CASES, build_case
+from helpers import GOLDEN_CASES, LEAN_GOLDEN_CASES, build_case, load_golden
 
 
 def _load(golden_dir, tag):
-    return np.load(os.path.join(golden_dir, f"reference_forward_{tag}.npz"))
+    return load_golden(os.path.join(golden_dir, f"reference_forward_{tag}.npz"))
 
 
 def _maxdiff(a, b):
@@ -113,8 +113,8 @@ def test_long_cases_structural_float64_and_float32_phase(golden_dir, case):
     """The oracle at 3 s / 10 s / 5 s (C = 340) and with 12 layers (dilations to 2048, and in cycles of four): float64 mode
     against the float64 run of the reference graph to rounding noise; the float32-faithful phase integrator against the
     float32 run's phase, bit for bit, over every 1000-sample chunk of the utterance."""
-    g32 = np.load(os.path.join(golden_dir, "reference_long_f32.npz"))
-    g64 = np.load(os.path.join(golden_dir, "reference_long_f64.npz"))
+    g32 = load_golden(os.path.join(golden_dir, "reference_long_f32.npz"))
+    g64 = load_golden(os.path.join(golden_dir, "reference_long_f64.npz"))
     voice, overrides, batch, frames = LONG_CASES[case]
     cfg, raw, wt = build_case(voice, overrides)
     mel, noise = g32[f"{case}/mell"], g32[f"{case}/noise"]

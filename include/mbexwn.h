@@ -451,7 +451,10 @@ mbx_status mbx_emit_rows(mbx_handle *handle, const float *audio, int64_t row_flo
  * tests.  Names: "f0" "pulse" "cond" "wn_hidden" "wn_skip" "wn_out" "subbands" "excitation" "cepstrum"
  * "ceps_index" "frames".  `count` = floats (int32 for ceps_index) per batch item, `stride` = item stride.
  * "wn_skip" (the C-wide skip sum) only exists when the skip path is not folded into the end convolution
- * (mbx_config.wn_keep_skip, or a handle created without the *.fold tensors). */
+ * (mbx_config.wn_keep_skip, or a handle created without the *.fold tensors).  A forward in split half precision whose
+ * every consumer of the hidden state takes it as fp16 planes does not write the float32 hidden state: there "wn_hidden"
+ * is unknown and "wn_hidden_planes" holds it instead, per row ceil(C/8)*8 hi halves then as many lo' halves (h = hi +
+ * 2^-11 lo'; count and stride in float32 words). */
 mbx_status mbx_stage(const mbx_handle *handle, const char *name, const void **device_ptr, int64_t *count,
                      int64_t *stride);
 

@@ -300,7 +300,10 @@ def make_config(config, wavetables, conv_form=None, batch_invariant=None, keep_s
                 calib_fraction=None, tune=None, precision="f32", f0_accumulate="f64"):
     """mbx_config of a model.  Policy arguments (None = default, or the experiment variable if one is set):
     conv_form "auto" | "direct" | "f23" | "f43" (mbx_config.wn_conv_form), batch_invariant, keep_skip, keep_start,
-    calib_fraction, tune = {"gate_shape": 0|1|2, "resskip_wave_tiles": n, "resskip_split": 0..3}."""
+    calib_fraction, tune = {"gate_shape": 0|1|2|3, "resskip_wave_tiles": n, "resskip_split": 0..3}.  gate_shape 0 keeps the
+    launch-size rule; 1 | 2 | 3 pin the F(4,3) block shape (256-row | product-split | product-split of half a column tile) of
+    launches of fewer than 4 * 768 256-row blocks (csrc/mbx_api.hip).  resskip_wave_tiles -1: never the wave-tiled res/skip
+    kernel."""
     dims = ModelDims(config)
     mb = config["mbexwn_config"]
     cc = mbx_config()

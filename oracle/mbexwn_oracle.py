@@ -377,9 +377,11 @@ class OracleModel:
         c = depth_to_time(self.wn_conv(x, w, b), conv_up)
         return lin_interp(c, lin_up, self.f32)
 
-    def wavenet(self, x, mel, return_layers=False, prefix="wn.", channels=None, rate_factor=1):
+    def wavenet(self, x, mel, return_layers=False, prefix="wn.", channels=None, rate_factor=1, hook=None):
         """custom_AE_layers.py:273-346 (WaveNetAE.call), activation gtu / gfu / gsu / glu; n_ch_groups independent channel groups between
-        the shared start and end convolutions (:303-340; layers of group g > 0 are named "<layer>g<g>", :249,260)."""
+        the shared start and end convolutions (:303-340; layers of group g > 0 are named "<layer>g<g>", :249,260).
+        ``hook`` (test instrument, default None: no effect): called as hook(layer, hidden) after the residual update of every layer
+        but the last, with the whole hidden state (B, T, C; the groups side by side); what it returns replaces the hidden state."""
         C = self.wn["n_channels"] if channels is None else channels
         L = self.wn.get("n_layers", 12)
         G = int(self.wn.get("n_ch_groups", 1))
@@ -421,6 +423,9 @@ class OracleModel:
                 output[gg] = s if output[gg] is None else output[gg] + s          # :332-335
                 if return_layers:
                     acts.append(a)
+            if hook is not None and ll < L - 1:
+                hidden = hook(ll, np.concatenate(started, axis=-1) if G > 1 else started[0])
+                started = [np.array(ss) for ss in np.split(hidden, G, axis=-1)] if G > 1 else [hidden]
         skip = np.concatenate(output, axis=-1) if G > 1 else output[0]            # :337-340
         w, b = self.weight(prefix + "end")
         out = conv1d_valid(skip, w, b)

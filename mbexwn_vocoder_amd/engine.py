@@ -821,9 +821,13 @@ class MBExWNEngine:
         return ff.value, rr.value, mm.value
 
     def forward(self, mel, n_frames=None, noise=None, out=None, stream_state=None, active=None, wavenet=None, carry=None,
-                layers=None, state_out=None, frontend=None):
+                layers=None, state_out=None, frontend=None, f0=None, transposition=1.0):
         """mel (B,T,80) float32 cuda tensor; n_frames int32 cuda tensor (B,) or None;
         noise (B, T*steps_per_frame) float32 cuda tensor (N(0,1) draw) -> audio (B, T*hop) cuda tensor.
+
+        f0: optional external F0 contour, float32 cuda tensor (B, T*pulse_per_frame) in Hz at the pulse rate, used instead
+        of the F0-net's (``mbx_forward_options.f0``, reference wavegen_1d.py:546-550); transposition scales the contour, the
+        F0-net's or the given one (``mbx_forward_options.transposition``).  Both apply to whole items (no stream_state).
 
         stream_state: optional int32 cuda tensor (B, 6) holding one ``mbx_stream_state`` per item (see
         streaming.pack_state); the call then returns (audio, state_out) with the carried phase state.
@@ -863,6 +867,8 @@ class MBExWNEngine:
         ws, need = self._get_workspace(B, T)
         if stream_state is None and (active is not None or wavenet is not None or carry is not None or layers is not None):
             raise ValueError("active / wavenet / carry / layers describe a streaming window: pass stream_state as well")
+        if stream_state is not None and (f0 is not None or transposition != 1.0):
+            raise ValueError("f0 / transposition apply to whole items: not with stream_state")
         if stream_state is not None:
             if stream_state.dtype != torch.int32 or tuple(stream_state.shape) != (B, 6) or stream_state.device != self.device:
                 raise ValueError("stream_state must be an int32 tensor of shape (batch, 6) on the engine's device")
@@ -943,6 +949,25 @@ class MBExWNEngine:
                                                 self._stream()))
             self._last_shape = (B, T)
             return out, state_out
+        if f0 is not None or transposition != 1.0:
+            if not transposition > 0.0:
+                raise ValueError("transposition must be positive")
+            opt = mbx_forward_options()
+            opt.struct_size = ctypes.sizeof(mbx_forward_options)
+            opt.transposition = float(transposition)
+            if f0 is not None:
+                if (f0.dtype != torch.float32 or tuple(f0.shape) != (B, T * self.dims.pulse_per_frame) or
+                        f0.device != self.device):
+                    raise ValueError(f"f0 must be a float32 tensor of shape ({B}, {T * self.dims.pulse_per_frame}) on the "
+                                     "engine's device")
+                f0 = f0.contiguous()
+                opt.f0 = f0.data_ptr()
+            _check(self._lib.mbx_forward_ex(self._handle, mel.data_ptr(),
+                                            n_frames.data_ptr() if n_frames is not None else None, B, T,
+                                            noise.data_ptr() if noise is not None else None, out.data_ptr(),
+                                            ws.data_ptr(), need, ctypes.byref(opt), self._stream()))
+            self._last_shape = (B, T)
+            return out
         _check(self._lib.mbx_forward(self._handle, mel.data_ptr(),
                                      n_frames.data_ptr() if n_frames is not None else None, B, T,
                                      noise.data_ptr() if noise is not None else None, out.data_ptr(),

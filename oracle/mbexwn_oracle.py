@@ -160,11 +160,12 @@ class OracleModel:
         rng_db = mb.get("filter_max_db_range", None)
         self.max_log_range = rng_db / LOG_TO_DB if rng_db is not None else None      # :371
         self.preserve_energy = bool(mb.get("spect_filters_preserve_energy", False))     # :817-849
-        self.stft_win = 4 * self.hop                                                # :396
+        win_s = mb.get("internal_win_size_s", None)
+        self.stft_win = int(win_s * self.sample_rate) if win_s else 4 * self.hop    # :391-396
         fft_size = 16
         while fft_size < self.stft_win:
             fft_size *= 2
-        self.fft_size = fft_size                                                    # :397-400
+        self.fft_size = fft_size * (2 ** int(mb.get("internal_fft_over", 0)))      # :397-400
         self.wt = wavetables
         self.raw = raw_weights
         self.use_prelu = mb.get("use_prelu", True)
@@ -197,8 +198,9 @@ class OracleModel:
         n = self.stft_win
         hann = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(n) / n))
         self.hann = hann.astype(self.f32).astype(dt)
-        den = np.square(self.hann).reshape(n // self.hop, self.hop).sum(axis=0)
-        self.inv_win = (self.hann / np.tile(den, n // self.hop)).astype(dt)
+        overlaps = -(-n // self.hop)            # inverse_stft_window_fn: the squared window zero-padded to whole hops
+        den = np.pad(np.square(self.hann), (0, overlaps * self.hop - n)).reshape(overlaps, self.hop).sum(axis=0)
+        self.inv_win = (self.hann / np.tile(den, overlaps)[:n]).astype(dt)
         # cepstral lifter table -- custom_pulsed_generator.py:434-450
         if self.env_scale:
             rows, logs = [], []

@@ -279,7 +279,10 @@ typedef struct {
                                * accumulation) or MBX_F0_ACC_F32 -- see f0_accumulate */
     int32_t n_gate_layers;    /* entries of gate_kernel that the most recent forward filled (0 before the first one) */
     int32_t gate_kernel[MBX_MAX_WN_LAYERS];   /* MBX_GATE_K_*: what ran the dilated convolution + gate of layer l in the most
-                                               * recent forward (first WaveNet block) */
+                                               * recent forward.  A handle with several WaveNet blocks (n_wn_blocks >= 1)
+                                               * fills it block-major: entry b * wn_layers + l is layer l of block b, and
+                                               * n_gate_layers = n_blocks * wn_layers, capped at MBX_MAX_WN_LAYERS (its
+                                               * blocks run MBX_GATE_K_F43, _F43_STRIDED or _DIRECT) */
 } mbx_conv_form_info;
 #define MBX_GATE_K_NONE 0
 #define MBX_GATE_K_DIRECT 1          /* conv1d_mfma_dma_kernel<EPI_GATE> */
@@ -454,7 +457,12 @@ mbx_status mbx_emit_rows(mbx_handle *handle, const float *audio, int64_t row_flo
  * (mbx_config.wn_keep_skip, or a handle created without the *.fold tensors).  A forward in split half precision whose
  * every consumer of the hidden state takes it as fp16 planes does not write the float32 hidden state: there "wn_hidden"
  * is unknown and "wn_hidden_planes" holds it instead, per row ceil(C/8)*8 hi halves then as many lo' halves (h = hi +
- * 2^-11 lo'; count and stride in float32 words). */
+ * 2^-11 lo'; count and stride in float32 words).
+ * Several WaveNet blocks (mbx_config.n_wn_blocks >= 1): "wn_hidden" and "wn_skip" are the LAST block's hidden state and
+ * skip sum, max_frames * rows_per_frame * C floats per item at that block's own rate and channels; "cond" is block 0's
+ * conditioning rows and "cond1" .. "cond3" those of blocks 1 .. 3, laid out like "cond" (max_frames * cond rows per frame
+ * * 2 C of the block; zeros with disable_conditioning).  "pulse_ana" (pulse_pqmf_taps > 0 only): the PQMF analysis of
+ * "pulse", the rows the WaveNet reads (max_frames * pulse_per_frame floats per item, pulse_channels per row). */
 mbx_status mbx_stage(const mbx_handle *handle, const char *name, const void **device_ptr, int64_t *count,
                      int64_t *stride);
 

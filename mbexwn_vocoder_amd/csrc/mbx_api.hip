@@ -1003,6 +1003,8 @@ static mbx_status run_wavenet_blocks(mbx_handle *hd, const Workspace &w, int B, 
     const int nsub1 = 1 + c.wt_subharm_channels;
     auto lerp = hd->lerp[cond_up];
     const float *x_in = nullptr;                 // output of the previous block (B, rows, n_out)
+    // mbx_conv_form_info.gate_kernel: block-major, entry b * L + l (as many as MBX_MAX_WN_LAYERS holds)
+    hd->last_gate_layers = std::min<int>((int)hd->blocks.size() * L, MBX_MAX_WN_LAYERS);
     for (size_t b = 0; b < hd->blocks.size(); ++b) {
         const auto &blk = hd->blocks[b];
         const int C = blk.C, spf = blk.spf;
@@ -1047,6 +1049,9 @@ static mbx_status run_wavenet_blocks(mbx_handle *hd, const Workspace &w, int B, 
                     done = mbx::launch_wn_gate_winograd4w(gw, 0, stream);
                 }
                 if (!done) mbx::launch_conv1d(g, mbx::EPI_GATE, stream);
+                const size_t slot = b * L + l;
+                if (slot < MBX_MAX_WN_LAYERS)
+                    hd->last_gate_kernel[slot] = !done ? MBX_GATE_K_DIRECT : d > 16 ? MBX_GATE_K_F43_STRIDED : MBX_GATE_K_F43;
             }
             const bool last = l == L - 1;
             mbx::ConvArgs r = conv_args(w.mb_a, rows * C, C, n_frames, spf, (int)rows, B, find(hd, blk.prefix + "res_skip_" + ls + ".w"),
@@ -1753,6 +1758,25 @@ static mbx_status forward_impl(mbx_handle *hd, const float *mel, const int32_t *
     }
     if (!hd->fold_skip) sg["wn_skip"] = {w_base.skip, nsteps * C, nsteps * C};
     else sg.erase("wn_skip");
+    if (!hd->blocks.empty()) {
+        // several blocks (run_wavenet_blocks): the hidden state and the skip sum of the last block, at its own rate
+        const auto &lb = hd->blocks.back();
+        const long long hc = (long long)T * lb.spf * lb.C;
+        sg["wn_hidden"] = {w_base.mb_h, hc, hc};
+        sg["wn_skip"] = {w_base.mb_skip, hc, hc};
+    }
+    for (int b = 1; b < MBX_MAX_WN_BLOCKS; ++b) {
+        // the conditioning rows of block b >= 1, laid out like "cond" (zeros with disable_conditioning)
+        const std::string nm = "cond" + std::to_string(b);
+        if (b < (int)hd->blocks.size()) {
+            const long long cc = (long long)T * hd->blocks[b].ccu * 2 * hd->blocks[b].C;
+            sg[nm] = {w_base.mb_cond[b], cc, cc};
+        } else {
+            sg.erase(nm);
+        }
+    }
+    if (c.pulse_pqmf_taps > 0) sg["pulse_ana"] = {w_base.pulse_ana, npulse, npulse};
+    else sg.erase("pulse_ana");
     sg["wn_out"] = {w_base.wn_out, nsteps * c.wn_out_channels, nsteps * c.wn_out_channels};
     sg["subbands"] = {w_base.sub, nsteps * M, nsteps * M};
     sg["excitation"] = {w_base.exc, (long long)T * c.hop_size, (long long)T * c.hop_size};

@@ -1067,7 +1067,9 @@ class MBExWNEngine:
         ``err_f43`` / ``err_f23`` (max |audio(form) - audio(direct)|, None: form not available), ``ref_max``,
         ``threshold``; with ``precision="split_f16"`` also ``err_split`` (max |audio(this handle in split precision) -
         audio(float32 direct form)| of the calibration run at creation) and ``split_rejected`` (True: that error was above the
-        threshold or not finite, the handle runs float32 after all: ``split_f16_layers`` is 0 then)."""
+        threshold or not finite, the handle runs float32 after all: ``split_f16_layers`` is 0 then).  ``gate_kernels``: the
+        gate kernel of every layer of the last forward, block-major (block b, layer l at b * n_layers + l) on a model with
+        several WaveNet blocks."""
         info = mbx_conv_form_info()
         info.struct_size = ctypes.sizeof(mbx_conv_form_info)
         _check(self._lib.mbx_conv_form(self._handle, ctypes.byref(info)))
@@ -1129,7 +1131,9 @@ class MBExWNEngine:
         return self.conv_form_info()["fold_start"]
 
     def stage(self, name):
-        """Intermediate tensor of the last forward (copy), shaped (B, count); see mbx_stage."""
+        """Intermediate tensor of the last forward (copy), shaped (B, count); see mbx_stage.  On a model with several WaveNet
+        blocks "wn_hidden" / "wn_skip" are the last block's (its rows and channels), "cond1" .. "cond3" the conditioning rows
+        of blocks 1 .. 3; a pulse-PQMF model also has "pulse_ana", the rows its WaveNet reads."""
         torch = self._torch
         ptr, cnt, stride = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
         status = self._lib.mbx_stage(self._handle, name.encode(), ctypes.byref(ptr), ctypes.byref(cnt), ctypes.byref(stride))

@@ -366,18 +366,24 @@ class OracleModel:
             return conv1d_causal(x, w, b, dilation)
         return conv1d_same_zero(x, w, b, dilation)
 
-    def conditioning(self, mel, prefix="wn.", rate_factor=1):
-        """custom_AE_layers.py:214-227,287-289: sub-pixel conv (factor cond_conv_upsampling) then LinInterp.  ``prefix`` /
-        ``rate_factor``: the block's tensors and its rate relative to the first block (custom_pulsed_generator.py:484,488)."""
+    def cond_conv_upsampling(self, rate_factor=1):
         lin_up = self.wn.get("cond_lin_upsampling", 16)
-        conv_up = int((self.pulse_rate / self.pulse_channels * rate_factor) // ((self.sample_rate / self.hop) * lin_up))
+        return int((self.pulse_rate / self.pulse_channels * rate_factor) // ((self.sample_rate / self.hop) * lin_up))
+
+    def conditioning_rows(self, mel, prefix="wn.", rate_factor=1):
+        """The conditioning rows before the linear interpolation (custom_AE_layers.py:214-227,287-289): pre-conditioning
+        convolutions, then the sub-pixel conv of factor cond_conv_upsampling -> (B, T * conv_up, 2C)."""
         x = mel
         for ii in range(len(self.wn.get("pre_cond_layer_channels", None) or [])):    # :192-201, 283-285: plain convolutions
             w, b = self.weight(f"{prefix}precond_{ii}")
             x = self.wn_conv(x, w, b)
         w, b = self.weight(prefix + "cond")
-        c = depth_to_time(self.wn_conv(x, w, b), conv_up)
-        return lin_interp(c, lin_up, self.f32)
+        return depth_to_time(self.wn_conv(x, w, b), self.cond_conv_upsampling(rate_factor))
+
+    def conditioning(self, mel, prefix="wn.", rate_factor=1):
+        """custom_AE_layers.py:214-227,287-289: sub-pixel conv (factor cond_conv_upsampling) then LinInterp.  ``prefix`` /
+        ``rate_factor``: the block's tensors and its rate relative to the first block (custom_pulsed_generator.py:484,488)."""
+        return lin_interp(self.conditioning_rows(mel, prefix, rate_factor), self.wn.get("cond_lin_upsampling", 16), self.f32)
 
     def wavenet(self, x, mel, return_layers=False, prefix="wn.", channels=None, rate_factor=1, hook=None):
         """custom_AE_layers.py:273-346 (WaveNetAE.call), activation gtu / gfu / gsu / glu; n_ch_groups independent channel groups between
@@ -439,6 +445,51 @@ class OracleModel:
             return out, h, skip, acts, cond[0]
         return out
 
+    def up_conv(self, block, y, factor):
+        """The up-sampling convolution behind WaveNet block ``block`` (k = 3, SAME, depth -> time; custom_AE_layers.py:519-524,
+        574-582)."""
+        w, b = self.weight(f"up{block}")
+        return depth_to_time(self.wn_conv(y, w, b), factor)
+
+    def wavenet_blocks(self, x, mel, hook=None, return_blocks=False):
+        """custom_pulsed_generator.py:456-488, 908-910: one WaveNet block per up-sampling factor; block b has n_channels *
+        channel_factors[b] channels and an up-sampling convolution behind it.  x (B, rows, cin): the excitation rows with
+        the noise channel.  ``hook`` (test instrument): hook(block, layer, hidden), see :meth:`wavenet`.  return_blocks: also
+        a list with one dict per block: "cond" its conditioning rows before the interpolation (zeros with
+        disable_conditioning), "hidden" and "skip" its last hidden state and skip sum, "out" its output (behind "up<b>")."""
+        ups = [int(uu) for uu in self.mb.get("pp_mod_subnet_upsampling_factors", [1])]
+        chf = list(self.mb.get("pp_mod_subnet_channel_factors", [1]))
+        y, rate, blocks = x, 1, []
+        for bb, (uu, ff) in enumerate(zip(ups, chf)):
+            prefix = "wn." if bb == 0 else f"wn{bb}."
+            C = int(self.wn["n_channels"] * ff)
+            kw = {} if hook is None else {"hook": lambda ll, h, bb=bb: hook(bb, ll, h)}
+            if return_blocks:
+                y, h, skip, _, _ = self.wavenet(y, mel, return_layers=True, prefix=prefix, channels=C, rate_factor=rate, **kw)
+                if self.wn.get("disable_conditioning", False):
+                    cond = np.zeros((mel.shape[0], mel.shape[1] * self.cond_conv_upsampling(rate), 2 * C), dtype=self.dtype)
+                else:
+                    cond = self.conditioning_rows(mel, prefix, rate)
+            else:
+                y = self.wavenet(y, mel, prefix=prefix, channels=C, rate_factor=rate, **kw)
+            if uu > 1:
+                y = self.up_conv(bb, y, uu)
+            if return_blocks:
+                blocks.append({"cond": cond, "hidden": h, "skip": skip, "out": y})
+            rate *= uu
+        return (y, blocks) if return_blocks else y
+
+    def pulse_analysis(self, pulse):
+        """PQMF analysis of the pulse signal (B, N) -> (B, N / K, K), the WaveNet's excitation rows of a pulse_channels_use_pqmf
+        model (custom_pulsed_generator.py:894-895, tf_preprocess.py:188-200): zero-pad taps/2 on both sides, cross-correlate
+        with the K analysis filters, keep every K-th sample."""
+        pq = self.mb["pulse_channels_multi_band_config"]
+        ana = pqmf_analysis_bank(pq["subbands"], pq["taps"], pq["cutoff_ratio"], pq["beta"]).astype(self.dtype)
+        K, taps = ana.shape[1], ana.shape[0] - 1
+        padded = np.pad(np.asarray(pulse).astype(self.dtype), ((0, 0), (taps // 2, taps // 2)))
+        return np.stack([np.stack([np.correlate(padded[bb], ana[:, kk], mode="valid")[::K] for kk in range(K)], axis=-1)
+                         for bb in range(padded.shape[0])], axis=0)
+
     # ------------------------------------------------------------------ PQMF (A10)
     def pqmf_synthesis(self, x):
         """tf_preprocess.py:208-226: zero-stuff by M with gain M, zero-pad taps/2, cross-correlate."""
@@ -458,12 +509,7 @@ class OracleModel:
         pulse = self.wavetable(f0)                                                # :889
         n_sub = int(self.wt_cfg.get("add_subharm_chans", 0) or 0)
         if self.mb.get("pulse_channels_use_pqmf", False):                         # :894-895, tf_preprocess.py:188-200
-            pq = self.mb["pulse_channels_multi_band_config"]
-            ana = pqmf_analysis_bank(pq["subbands"], pq["taps"], pq["cutoff_ratio"], pq["beta"]).astype(self.dtype)
-            K, taps = ana.shape[1], ana.shape[0] - 1
-            padded = np.pad(pulse.astype(self.dtype), ((0, 0), (taps // 2, taps // 2)))
-            x = np.stack([np.stack([np.correlate(padded[bb], ana[:, kk], mode="valid")[::K] for kk in range(K)], axis=-1)
-                          for bb in range(pulse.shape[0])], axis=0)
+            x = self.pulse_analysis(pulse)
         else:
             x = pulse.reshape(pulse.shape[0], -1, self.pulse_channels * (1 + n_sub)).astype(self.dtype)   # :893
         if self.sigma:
@@ -471,18 +517,7 @@ class OracleModel:
                 raise ValueError("noise must be given when pp_mod_subnet_noise_channel_sigma != 0")
             nz = np.asarray(noise).astype(self.dtype)[:, :x.shape[1], None]
             x = np.concatenate((x, self.sigma * nz), axis=-1)                     # :905-906
-        # :908-910, 456-488: one WaveNet block per up-sampling factor; block b has n_channels * channel_factors[b] channels
-        # and an up-sampling convolution (k = 3, SAME, depth -> time; custom_AE_layers.py:519-524, 574-582) behind it
-        ups = [int(uu) for uu in self.mb.get("pp_mod_subnet_upsampling_factors", [1])]
-        chf = list(self.mb.get("pp_mod_subnet_channel_factors", [1]))
-        y, rate = x, 1
-        for bb, (uu, ff) in enumerate(zip(ups, chf)):
-            prefix = "wn." if bb == 0 else f"wn{bb}."
-            y = self.wavenet(y, mel, prefix=prefix, channels=int(self.wn["n_channels"] * ff), rate_factor=rate)
-            if uu > 1:
-                w, b = self.weight(f"up{bb}")
-                y = depth_to_time(self.wn_conv(y, w, b), uu)
-            rate *= uu
+        y = self.wavenet_blocks(x, mel)                                           # :908-910, 456-488
         w, b = self.weight("post")
         y = conv1d_valid(y, w, b)                                                 # :913-914
         if not self.mb.get("ps_use_stft", True) and not self.mb.get("ps_off", False):

@@ -539,6 +539,26 @@ mbx_status mbx_mel_analysis(const float *audio, const int32_t *n_samples, int32_
                             const float *twiddle, const float *basis, const int32_t *bin_lo, const int32_t *bin_hi,
                             float eps, float *out, int32_t max_frames, void *hip_stream);
 
+/* FLAC frames of a ragged batch of mono audio, the hot path of the CLI's default output format (csrc/flac_frames.hip): for
+ * every item, everything that follows the 42-byte "fLaC" + STREAMINFO header of mbexwn_vocoder_amd/flac.py::encode, byte
+ * for byte -- 16-bit samples clip(rint(x * 32767)) (in float64, ties to even), blocks of 4096 samples (the last one
+ * shorter), VERBATIM sub-frames, "UTF-8" frame numbers, CRC-8 and CRC-16.  The STREAMINFO header (it holds the MD5 of the
+ * samples) stays with the caller.  Needs no handle: runs on the current device.
+ *   audio        device (batch, stride) float32; item b is audio[b][0 .. n_samples[b])
+ *   n_samples    HOST int64 (batch), 0 <= n_samples[b] <= min(stride, MBX_FLAC_MAX_SAMPLES)
+ *   sample_rate  Hz, 0 < rate < 2^20: the rate code of the frame headers (0 = "see STREAMINFO" outside FLAC's table)
+ *   crc_tables   device uint16 (MBX_FLAC_CRC_TABLE_WORDS): the CRC-16 byte table (poly 0x8005, init 0), then for
+ *                k = 0 .. 15 the 16 columns of M_{2^k}, which advances the register over 2^k zero bytes (column j: the
+ *                register 1 << j advanced); mbexwn_vocoder_amd/flac.py builds them
+ *   out          device bytes (out_bytes): item b's frames start behind the frames of the items in front of it
+ *   max_abs      device float32 (batch): max |x| of every item; not finite when the item holds a NaN or an infinity (the
+ *                caller then writes that item with the host writer) */
+#define MBX_FLAC_MAX_SAMPLES 268435456    /* 2^28: frame numbers of at most 3 bytes (the forward: < 2^24 sub-band rows) */
+#define MBX_FLAC_CRC_TABLE_WORDS 512
+mbx_status mbx_encode_flac16(const float *audio, int64_t stride, int32_t batch, const int64_t *n_samples,
+                             int32_t sample_rate, const uint16_t *crc_tables, uint8_t *out, int64_t out_bytes,
+                             float *max_abs, void *hip_stream);
+
 /* NormMelComponents.normalize_inputs_by_rms(None, mell, synth_length) (reference wavegen_1d.py:638-769), only for
  * models with nm_iters > 0: mel (batch, frames, mel_channels) -> mel_out (same shape) and, if gain != NULL,
  * gain (batch, frames*hop) = upsampled_rms (what mbx_forward multiplies onto the audio).  n_frames: device int32

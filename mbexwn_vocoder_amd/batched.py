@@ -1,0 +1,302 @@
+"""Batched synthesis behind the drop-in surface: ``MELInverter.synth_from_mels`` and ``resynth_mel.py --batch N --gpus N``.
+
+The reference's CLI synthesises one file at a time (reference bin/resynth_mel.py:74-104).  Here the files of a job go
+through padded micro-batches of whole utterances (``sharding.plan_batches``; every boundary op of the engine honours the
+item's own length), the FLAC frames are encoded on the device (``MBExWNEngine.encode_flac16``) and copied into pinned host
+memory while the next micro-batch runs, and host thread pools read the ``.mell`` files and write the results.  A
+``--gpus N`` job partitions the files by frames (``sharding.lpt_partition``) over N fresh child processes, each of which
+writes its own files: no gather, no process group.
+
+Noise: after ``torch.manual_seed(seed)`` the one-at-a-time loop draws ``torch.randn((1, T_i * wn_in_rows_per_frame))`` on
+the device once per file, in file order (``engine._prepare``), and nothing else takes numbers from the device generator in
+between (``MELInverter.calibrate`` draws from numpy).  :func:`replay_noise` makes the same draws in the same order and keeps
+those of the files a process owns.  With ``batch_invariant`` on both sides (include/mbexwn.h) batched files are then
+bit-identical to one-at-a-time files.
+"""
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import threading
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from .fileio import load_var
+from .sharding import lpt_partition, plan_batches, visible_gpu_count
+
+
+def output_path(mell_file, output_dir, fmt):
+    """syn_<basename>.<format> in ``output_dir`` (reference bin/resynth_mel.py)."""
+    return os.path.join(output_dir or "", "syn_" + os.path.splitext(os.path.basename(mell_file))[0] + "." + fmt)
+
+
+def have_soundfile():
+    try:
+        import soundfile  # noqa: F401
+    except ImportError:
+        return False
+    return True
+
+
+def write_audio(outfile, data, rate, format):
+    """reference bin/resynth_mel.py:104-105 (sndio.write): libsndfile through soundfile where it is installed, else the
+    built-in writers -- flac (mbexwn_vocoder_amd/flac.py: 16-bit, uncompressed sub-frames) and wav (float32)."""
+    try:
+        import soundfile
+        soundfile.write(outfile, data, rate, format=format.upper())
+        return outfile
+    except ImportError:
+        pass
+    if format.lower() == "flac":
+        from . import flac
+        return flac.write(outfile, data, rate)
+    if format.lower() == "wav":
+        from scipy.io import wavfile
+        wavfile.write(outfile, rate, np.asarray(data, dtype=np.float32))
+        return outfile
+    raise RuntimeError(f"cannot write format {format}: soundfile is not installed, only flac and wav are built in")
+
+
+def replay_noise(frames, rows_per_frame, keep=None, device=None, generator=None):
+    """The N(0,1) draws of the one-at-a-time loop over files of ``frames`` frames (after scale_mel), in file order: returns
+    {i: (frames[i] * rows_per_frame,) tensor} for the files in ``keep`` (default: all); the others are drawn and dropped."""
+    import torch
+    keep = set(range(len(frames))) if keep is None else set(keep)
+    draws = {}
+    for ii, tt in enumerate(frames):
+        zz = torch.randn((1, int(tt) * rows_per_frame), device=device, dtype=torch.float32, generator=generator)
+        if ii in keep:
+            draws[ii] = zz[0]
+    return draws
+
+
+def stage_micro_batch(mels, noises, rows_per_frame, device=None):
+    """Padded inputs of one micro-batch: ``mels`` (list of (T_j, C) float32 arrays), ``noises`` (list of (T_j *
+    rows_per_frame,) tensors, or None) -> mel (B, Tmax, C), n_frames int32 (B,), noise (B, Tmax * rows_per_frame) or None,
+    on ``device``; item j's draw at the front of row j, zeros behind it."""
+    import torch
+    lengths = [int(mm.shape[0]) for mm in mels]
+    tmax = max(lengths)
+    mel = np.zeros((len(mels), tmax, mels[0].shape[1]), dtype=np.float32)
+    for jj, mm in enumerate(mels):
+        mel[jj, :lengths[jj]] = mm
+    noise = None
+    if noises is not None:
+        noise = torch.zeros((len(mels), tmax * rows_per_frame), dtype=torch.float32, device=device)
+        for jj, zz in enumerate(noises):
+            noise[jj, :lengths[jj] * rows_per_frame] = zz
+    return (torch.as_tensor(mel, device=device), torch.as_tensor(np.asarray(lengths, dtype=np.int32), device=device),
+            noise)
+
+
+class SynthBatch:
+    """One micro-batch in flight: ``indices`` into the caller's list, the samples of every item, the device audio (B, stride)
+    and what was enqueued behind the forward -- the FLAC frames (``engine.EncodedFlac``) and / or the audio in pinned host
+    memory.  :meth:`wait` before reading; ``device_ms`` / ``copy_ms`` are then the forward's and the encode + copies' time."""
+
+    def __init__(self, indices, n_samples, audio, flac, host_audio, events):
+        self.indices, self.n_samples, self.device_audio = list(indices), list(n_samples), audio
+        self.flac, self.host_audio, self._events = flac, host_audio, events
+        self.device_ms = self.copy_ms = 0.0
+
+    def wait(self):
+        if self._events is not None:
+            ev0, ev1, ev2 = self._events
+            ev2.synchronize()
+            self.device_ms, self.copy_ms = ev0.elapsed_time(ev1), ev1.elapsed_time(ev2)
+            if self.flac is not None:
+                self.flac.wait()
+            self._events = None
+        return self
+
+    def audio(self, jj):
+        """float32 audio of item jj (numpy)."""
+        nn = self.n_samples[jj]
+        if self.host_audio is not None:
+            return self.host_audio[jj, :nn].numpy()
+        return self.device_audio[jj, :nn].cpu().numpy()
+
+    def max_abs(self, jj):
+        if self.flac is not None:
+            return float(self.flac.max_abs[jj])
+        return float(np.max(np.abs(self.audio(jj)))) if self.n_samples[jj] else 0.0
+
+
+def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False, host_audio=True):
+    """Generator over the padded micro-batches of ``mels`` (list of (T_i, C) float32 arrays) on ``engine``: each is staged
+    and run (engine.forward with the items' lengths), its FLAC frames encoded (``flac``) and / or its audio copied to pinned
+    host memory (``host_audio``), all enqueued on the current stream; the SynthBatch is yielded without waiting, so that a
+    writer can take it while the next one runs.  ``noises``: per-item device tensors (T_i * wn_in_rows_per_frame,), or
+    None for a model without noise channel."""
+    import torch
+    dims = engine.dims
+    lengths = [int(mm.shape[0]) for mm in mels]
+    stream = torch.cuda.current_stream(engine.device)
+    for group in plan_batches(range(len(mels)), lengths, max_batch, max_padded_frames):
+        mel, n_frames, noise = stage_micro_batch([mels[ii] for ii in group],
+                                                 None if noises is None else [noises[ii] for ii in group],
+                                                 dims.wn_in_rows_per_frame, engine.device)
+        events = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        events[0].record(stream)
+        audio = engine.forward(mel, n_frames=n_frames, noise=noise)
+        events[1].record(stream)
+        n_samples = [lengths[ii] * dims.hop_size for ii in group]
+        enc = engine.encode_flac16(audio, n_samples, wait=False) if flac else None
+        host = None
+        if host_audio:
+            host = torch.empty(tuple(audio.shape), dtype=torch.float32, pin_memory=True)
+            host.copy_(audio, non_blocking=True)
+        events[2].record(stream)
+        yield SynthBatch(group, n_samples, audio, enc, host, events)
+
+
+class _Clock:
+    """Seconds per stage, summed over the threads of a pool."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+        self.seconds = {}
+
+    def add(self, key, seconds):
+        with self._lock:
+            self.seconds[key] = self.seconds.get(key, 0.0) + seconds
+
+
+def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threads=2, verbose=False, quiet=False):
+    """The batched CLI on this process's GPU: ``files[mine]`` -> syn_<basename>.<fmt> in ``output_dir``.
+
+    ``frames``: the frame count after scale_mel of EVERY file of the job, in file order (the noise replay needs all of
+    them; default: read here, which needs ``mine`` = all files).  Reader pool (load_var + scale_mel; a missing or bad file
+    fails before anything runs), device (forward, FLAC frames, asynchronous copies into pinned memory), writer pool (MD5,
+    header, file write); both pools have ``threads`` threads."""
+    t_start = time.perf_counter()
+    mine = list(range(len(files))) if mine is None else list(mine)
+    clock, log_lock = _Clock(), threading.Lock()
+
+    def log(lines):
+        with log_lock:
+            for line in lines:
+                print(line, file=sys.stderr)
+
+    def read(ii):
+        t0 = time.perf_counter()
+        if verbose:
+            log([f"load mell  from {files[ii]}"])
+        mel = inv.scale_mel(load_var(files[ii]), verbose=verbose)
+        clock.add("read", time.perf_counter() - t0)
+        return mel
+
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+        scaled = dict(zip(mine, pool.map(read, mine)))
+    if frames is None:
+        if sorted(mine) != list(range(len(files))):
+            raise ValueError("run_job: the frames of every file are needed when this process writes only some of them")
+        frames = [int(scaled[ii].shape[1]) for ii in range(len(files))]
+    for ii in mine:
+        if int(scaled[ii].shape[1]) != int(frames[ii]):
+            raise RuntimeError(f"{files[ii]}: {scaled[ii].shape[1]} frames after scale_mel, the job plan says {frames[ii]}")
+    dims = inv.model.dims
+    draws = (replay_noise(frames, dims.wn_in_rows_per_frame, keep=mine, device=inv.model.device)
+             if dims.noise_sigma else None)
+    device_flac = fmt.lower() == "flac" and not have_soundfile()
+    rate = inv.srate
+    from . import flac
+    from .mel_inverter import log_to_db
+
+    def write(sb):
+        sb.wait()
+        t0 = time.perf_counter()
+        for jj, local in enumerate(sb.indices):
+            ii = mine[local]
+            outfile = output_path(files[ii], output_dir, fmt)
+            lines = [] if quiet else [f"synthesize {files[ii]} into {outfile}"]
+            audio = sb.audio(jj) if (verbose or not device_flac) else None
+            if verbose:                                  # as the one-at-a-time loop (reference :90-96)
+                resyn = inv.generate_mel_from_snd(audio, srate=rate)['mell'].T[np.newaxis]
+                err = log_to_db * np.mean(np.abs(scaled[ii] - resyn[:, :scaled[ii].shape[1]]))
+                lines.append(f"    synthesized audio with {audio.size} samples in a micro-batch of {len(sb.indices)} "
+                             f"({sb.device_ms:.1f} ms on the device), mel_error: {err:.3f}dB")
+            peak = sb.max_abs(jj)
+            if peak > 1:
+                lines.append(f'    to prevent clipping you would need to normalize {outfile} by {0.99 / peak:.3f}')
+            if verbose:
+                lines.append(f"    save audio under {outfile}")
+            if device_flac and np.isfinite(peak):
+                flac.write_frames(outfile, sb.flac.frames(jj), sb.n_samples[jj], rate)
+            else:                                        # soundfile, wav, or an item the host writer must take
+                write_audio(outfile, audio if audio is not None else sb.audio(jj), rate, fmt)
+            log(lines)
+        clock.add("write", time.perf_counter() - t0)
+        clock.add("device_ms", sb.device_ms)
+        clock.add("copy_ms", sb.copy_ms)
+
+    mels = [scaled[ii][0] for ii in mine]
+    noises = None if draws is None else [draws[ii] for ii in mine]
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as writers:
+        pending = [writers.submit(write, sb) for sb in run_micro_batches(inv.model, mels, noises, max(1, batch),
+                                                                         flac=device_flac, host_audio=verbose or not device_flac)]
+        for fu in pending:
+            fu.result()
+    if verbose:
+        wall = time.perf_counter() - t_start
+        sec = clock.seconds
+        audio_s = sum(int(frames[ii]) for ii in mine) * inv.hop_size / rate
+        print(f"resynth_mel: {len(mine)} files, {audio_s:.1f} s of audio in {wall:.2f} s wall ({audio_s / max(wall, 1e-9):.1f} x "
+              f"real time); read+scale {sec.get('read', 0.0):.2f} s, device {sec.get('device_ms', 0.0) / 1e3:.3f} s, "
+              f"encode+D2H {sec.get('copy_ms', 0.0) / 1e3:.3f} s, MD5+write {sec.get('write', 0.0):.2f} s "
+              f"(pool stages summed over {max(1, threads)} threads each)", file=sys.stderr)
+
+
+def plan_ranks(model_id_or_path, files, ranks, threads=2):
+    """What the parent of a ``--gpus N`` job decides before it starts its ranks, without importing torch: the number of
+    visible GPUs (sharding.visible_gpu_count), the frames after scale_mel of every file (a missing or bad file fails here,
+    before any rank starts) and the LPT partition of the files by frames."""
+    from .mel_inverter import MELInverter
+    inv = MELInverter.host_only(model_id_or_path)
+
+    def frames_of(path):
+        return int(inv.scale_mel(load_var(path)).shape[1])
+
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+        frames = list(pool.map(frames_of, files))
+    return {"devices": visible_gpu_count(), "frames": frames, "shards": lpt_partition(frames, ranks)}
+
+
+def run_ranks(script, child_argv, model_id_or_path, files, ranks, threads=2, quiet=False, poll_s=0.05):
+    """``resynth_mel.py --gpus N``: plan the job (:func:`plan_ranks`), start N fresh child processes ``script child_argv
+    --rank r --job <plan>`` (rank r on visible device r % count), poll them; when one fails, end the others.  Returns the
+    exit status of the job."""
+    plan = plan_ranks(model_id_or_path, files, ranks, threads)
+    if plan["devices"] < 1:
+        print("resynth_mel::error:: no GPU visible", file=sys.stderr)
+        return 1
+    if ranks > plan["devices"] and not quiet:
+        print(f"resynth_mel::note:: {ranks} ranks on {plan['devices']} visible GPU(s): rank r runs on device r % "
+              f"{plan['devices']}, ranks share a GPU", file=sys.stderr)
+    with tempfile.TemporaryDirectory() as tmp:
+        job = os.path.join(tmp, "job.json")
+        with open(job, "w") as fo:
+            json.dump(plan, fo)
+        procs = [subprocess.Popen([sys.executable, script, *child_argv, "--rank", str(rr), "--job", job])
+                 for rr in range(ranks)]
+        try:
+            while True:
+                codes = [pp.poll() for pp in procs]
+                if any(cc not in (None, 0) for cc in codes):
+                    return 1
+                if all(cc == 0 for cc in codes):
+                    return 0
+                time.sleep(poll_s)
+        finally:
+            for pp in procs:
+                if pp.poll() is None:
+                    pp.terminate()
+            for pp in procs:
+                try:
+                    pp.wait(timeout=30)
+                except subprocess.TimeoutExpired:
+                    pp.kill()
+                    pp.wait()

@@ -5,9 +5,12 @@
 Deviations (documented in INTEGRATION.md):
   * this build has only the GPU path: ``-g`` is accepted and implied; without a GPU the script fails loudly
   * ``-nt`` (TensorFlow CPU threads) is accepted and ignored
-  * audio files are written with ``soundfile`` if it is installed, otherwise as float32 ``.wav`` through scipy
-    (the reference uses pysndfile, default format flac)
+  * audio files are written with ``soundfile`` if it is installed, otherwise through the built-in writers (flac: 16-bit
+    VERBATIM frames, wav: float32 through scipy; the reference uses pysndfile, default format flac)
+  * additionally ``--batch N`` (padded micro-batches, FLAC frames encoded on the GPU, reader / writer pools of -nt
+    threads), ``--gpus N`` (the files sharded over N child processes by frames) and ``--batch-invariant``
 """
+import json
 import os
 import sys
 import time
@@ -19,30 +22,22 @@ if os.path.exists(test_path):
     sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
 
 from mbexwn_vocoder_amd import list_models, mel_inverter  # noqa: E402
+from mbexwn_vocoder_amd.batched import write_audio  # noqa: E402,F401 -- the writer of the one-at-a-time loop
 from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 
 
-def write_audio(outfile, data, rate, format):
-    """reference bin/resynth_mel.py:104-105 (sndio.write): libsndfile through soundfile where it is installed, else the
-    built-in writers -- flac (mbexwn_vocoder_amd/flac.py: 16-bit, uncompressed sub-frames) and wav (float32)."""
-    try:
-        import soundfile
-        soundfile.write(outfile, data, rate, format=format.upper())
-        return outfile
-    except ImportError:
-        pass
-    if format.lower() == "flac":
-        from mbexwn_vocoder_amd import flac
-        return flac.write(outfile, data, rate)
-    if format.lower() == "wav":
-        from scipy.io import wavfile
-        wavfile.write(outfile, rate, np.asarray(data, dtype=np.float32))
-        return outfile
-    raise RuntimeError(f"cannot write format {format}: soundfile is not installed, only flac and wav are built in")
-
-
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
-         num_threads=2, quiet=False, calibrate=0):
+         num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, rank=None, job=None):
+    format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
+    if gpus > 1 and rank is None:
+        # --gpus N: this parent never initialises HIP; N fresh child processes write their share of the files each
+        from mbexwn_vocoder_amd.batched import run_ranks
+        argv = [model_id, "-i", *input_mell_files, "--format", format, "-nt", str(num_threads), "--batch", str(batch),
+                "--calibrate", str(calibrate)] + (["-o", output_dir] if output_dir else [])
+        argv += [flag for flag, on in (("-g", use_gpu), ("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant))
+                 if on]
+        sys.exit(run_ranks(os.path.abspath(__file__), argv, model_id, input_mell_files, gpus, threads=num_threads,
+                           quiet=quiet))
     import torch
     if not torch.cuda.is_available():
         print("resynth_mel::error:: no GPU available; this build has no CPU path", file=sys.stderr)
@@ -50,7 +45,11 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
     if not use_gpu and not quiet:
         print("resynth_mel::note:: running on the MI355X HIP path (this build has no CPU path, -g is implied)",
               file=sys.stderr)
-    format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
+    plan = None
+    if job is not None:                                       # a rank of a --gpus job: its device and its files
+        with open(job) as fo:
+            plan = json.load(fo)
+        torch.cuda.set_device(rank % plan["devices"])
     if num_threads:                                           # -nt: host threads (numpy / torch CPU work around the HIP path)
         torch.set_num_threads(max(1, int(num_threads)))
         try:
@@ -62,9 +61,10 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         np.random.seed(seed)
         torch.manual_seed(seed)
 
-    MelInv = mel_inverter.MELInverter(model_id_or_path=model_id, verbose=verbose)
-    if output_dir and not os.path.exists(output_dir):
-        os.makedirs(output_dir)
+    MelInv = mel_inverter.MELInverter(model_id_or_path=model_id, verbose=verbose,
+                                      batch_invariant=True if batch_invariant else None)
+    if output_dir:
+        os.makedirs(output_dir, exist_ok=True)
     if calibrate and input_mell_files:
         # --calibrate N (this build): the form of the WaveNet's convolution is decided on the first N mels of the job
         # (MELInverter.calibrate -> mbx_calibrate) instead of on the synthetic mel of the engine's creation
@@ -72,6 +72,12 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         info = MelInv.calibrate(first, verbose=verbose)
         if not quiet and not verbose:
             print(f"calibrated on {len(first)} file(s): convolution form {info['form']}", file=sys.stderr)
+
+    if batch > 1 or plan is not None:
+        from mbexwn_vocoder_amd.batched import run_job
+        run_job(MelInv, input_mell_files, output_dir, format, frames=plan["frames"] if plan else None,
+                mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose, quiet=quiet)
+        return
 
     for mell_file in input_mell_files:
         outfile = os.path.join(output_dir or "", "syn_" + os.path.splitext(os.path.basename(mell_file))[0] + "." + format)
@@ -101,7 +107,7 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
 
 
 if __name__ == "__main__":
-    from argparse import ArgumentParser
+    from argparse import SUPPRESS, ArgumentParser
     parser = ArgumentParser(description="invert mel spectrograms into audio with an MBExWN model (MI355X HIP path)")
     parser.add_argument("model_id", default=None, nargs="?", const=None,
                         help="model identifier or path to a model directory. If not given the script lists all known "
@@ -118,6 +124,17 @@ if __name__ == "__main__":
                         help="decide the form of the WaveNet's convolution on the first N input files before synthesis "
                              "(Def: %(default)s = keep the decision made at model load on a synthetic mel); the decision then "
                              "binds every file of the job, so the output depends on which N files come first")
+    parser.add_argument("--batch", default=1, type=int, metavar="N",
+                        help="synthesise up to N files per launch in padded micro-batches, with the FLAC frames encoded on "
+                             "the GPU and reader / writer pools of -nt threads (Def: %(default)s = one file at a time)")
+    parser.add_argument("--gpus", default=1, type=int, metavar="N",
+                        help="shard the files by frames over N child processes, rank r on visible GPU r %% count, each "
+                             "writing its own files (Def: %(default)s)")
+    parser.add_argument("--batch-invariant", action="store_true",
+                        help="pin the engine's kernels so that a file's audio does not depend on the batch it ran in: with "
+                             "this flag on both sides, batched files are bit-identical to one-at-a-time files")
+    parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
+    parser.add_argument("--job", default=None, help=SUPPRESS)
     args = parser.parse_args()
 
     if not args.model_id:

@@ -2125,6 +2125,20 @@ mbx_status mbx_mel_analysis(const float *audio, const int32_t *n_samples, int32_
     return MBX_OK;
 }
 
+mbx_status mbx_encode_flac16(const float *audio, int64_t stride, int32_t batch, const int64_t *n_samples, int32_t sample_rate,
+                             const uint16_t *crc_tables, uint8_t *out, int64_t out_bytes, float *max_abs, void *hip_stream) {
+    if (const char *why = mbx::check_flac_frames(audio, stride, batch, n_samples, sample_rate, crc_tables, out, out_bytes,
+                                                 max_abs))
+        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("encode flac16: ") + why);
+    if (batch == 0) return MBX_OK;
+    const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipMemsetAsync(max_abs, 0, (size_t)batch * sizeof(float), stream));
+    mbx::launch_flac_frames(audio, stride, batch, n_samples, sample_rate, crc_tables, out, max_abs, stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
 mbx_status mbx_profile_enable(mbx_handle *handle, int32_t enabled) {
     if (!handle) return fail(MBX_ERR_INVALID_ARGUMENT, "null argument");
     handle->profiling = enabled != 0;

@@ -316,6 +316,30 @@ struct MelAnalysisArgs {
 };
 bool launch_mel_analysis(const MelAnalysisArgs &a, hipStream_t stream);
 
+// FLAC frames of 16-bit mono audio (flac_frames.hip): flac.py::encode's stream behind its 42-byte header
+constexpr int FLAC_BLOCK = 4096;                // samples per frame (the last one may be shorter)
+constexpr int FLAC_THREADS = 256;
+constexpr int FLAC_ITEMS_PER_LAUNCH = 32;       // the items' lengths and offsets travel in the kernel arguments
+constexpr int FLAC_CRC_SHIFTS = 16;             // operators M_{2^k}, k < 16, of the CRC-16 combine (frames are < 2^14 bytes)
+constexpr long long FLAC_MAX_SAMPLES = 65536LL * FLAC_BLOCK;   // frame numbers of at most 3 bytes
+struct FlacFramesArgs {
+    const float *audio;          // item i of the launch at audio + i * stride
+    long long stride;
+    const uint16_t *crc_tables;  // CRC-16 byte table (256), then FLAC_CRC_SHIFTS x 16 operator columns
+    uint8_t *out;                // item i's frames at out + offset[i]
+    float *max_abs;              // (items) max |x| of every item, as the maximum of the bit patterns; zeroed before the launch
+    int items, rate_code;
+    long long n_samples[FLAC_ITEMS_PER_LAUNCH];
+    long long offset[FLAC_ITEMS_PER_LAUNCH];
+};
+long long flac_frames_bytes(long long n);       // bytes of the frames of an n-sample item
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_flac_frames(const float *audio, long long stride, int batch, const int64_t *n_samples, int sample_rate,
+                              const uint16_t *crc_tables, const uint8_t *out, long long out_bytes, const float *max_abs);
+// items packed back to back in `out` (item b behind the frames of the items in front of it); max_abs must be zeroed
+void launch_flac_frames(const float *audio, long long stride, int batch, const int64_t *n_samples, int sample_rate,
+                        const uint16_t *crc_tables, uint8_t *out, float *max_abs, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // optional RMS normalisation of the mel input / de-normalisation of the audio (norm_mel.hip)
 // ---------------------------------------------------------------------------------------------

@@ -190,13 +190,16 @@ def load_library():
     lib.mbx_norm_mel.argtypes = [vp, fp, vp, i32, i32, fp, fp, fp, vp]
     lib.mbx_mel_analysis.restype = i32
     lib.mbx_mel_analysis.argtypes = [fp, vp, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp, vp, ctypes.c_float, fp, i32, vp]
+    lib.mbx_encode_flac16.restype = i32
+    lib.mbx_encode_flac16.argtypes = [fp, ctypes.c_int64, i32, i64p, i32, vp, vp, ctypes.c_int64, fp, vp]
     _lib = lib
     return lib
 
 
 EXPORTED_SYMBOLS = ["mbx_last_error", "mbx_create", "mbx_destroy", "mbx_conv_form", "mbx_calibrate", "mbx_workspace_size", "mbx_forward",
                     "mbx_forward_stream", "mbx_forward_ex", "mbx_layer_state_info", "mbx_window_advance", "mbx_window_update", "mbx_emit_rows", "mbx_stage",
-                    "mbx_profile_enable", "mbx_profile_read", "mbx_profile_read_launches", "mbx_clock_probe", "mbx_pqmf_synthesis", "mbx_conv1d", "mbx_conv1d_f64acc", "mbx_lin_interp", "mbx_wavetable", "mbx_stft_filter", "mbx_norm_mel", "mbx_mel_analysis"]
+                    "mbx_profile_enable", "mbx_profile_read", "mbx_profile_read_launches", "mbx_clock_probe", "mbx_pqmf_synthesis", "mbx_conv1d", "mbx_conv1d_f64acc", "mbx_lin_interp", "mbx_wavetable", "mbx_stft_filter", "mbx_norm_mel", "mbx_mel_analysis",
+                    "mbx_encode_flac16"]
 
 
 def _check(status):
@@ -776,6 +779,7 @@ class MBExWNEngine:
         self._handle = handle
         self._workspace = None
         self._last_shape = None
+        self._flac_tables = None
 
     def close(self):
         if getattr(self, "_handle", None):
@@ -974,6 +978,41 @@ class MBExWNEngine:
                                      ws.data_ptr(), need, self._stream()))
         self._last_shape = (B, T)
         return out
+
+    def encode_flac16(self, audio, n_samples, sample_rate=None, wait=True):
+        """mbx_encode_flac16: the FLAC frames (``flac.encode`` of the item without its 42-byte header) and max |x| of every
+        item audio[b, :n_samples[b]] of a device batch (B, stride) float32, encoded on the engine's stream and copied into
+        pinned host memory asynchronously.  ``n_samples``: host integers; ``sample_rate`` defaults to the model's.  Returns an
+        :class:`EncodedFlac`; with ``wait=False`` the copies may still be in flight (``EncodedFlac.wait()`` before reading)."""
+        from . import flac
+        torch = self._torch
+        if audio.dim() != 2 or audio.dtype != torch.float32 or audio.device != self.device:
+            raise ValueError("audio must be a float32 tensor (batch, stride) on the engine's device")
+        audio = audio.contiguous()
+        B, stride = int(audio.shape[0]), int(audio.shape[1])
+        counts = [int(nn) for nn in n_samples]
+        if len(counts) != B:
+            raise ValueError(f"n_samples must hold one count per item ({B})")
+        rate = int(self.dims.sample_rate if sample_rate is None else sample_rate)
+        offsets = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum([flac.frames_bytes(nn) for nn in counts], out=offsets[1:])
+        total = int(offsets[-1])
+        if self._flac_tables is None:
+            self._flac_tables = torch.as_tensor(flac.crc16_device_tables().view(np.int16)).to(self.device)
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
+        max_abs = torch.empty(max(B, 1), dtype=torch.float32, device=self.device)
+        counts_c = (ctypes.c_int64 * max(B, 1))(*counts)
+        with torch.cuda.device(self.device):
+            _check(self._lib.mbx_encode_flac16(audio.data_ptr(), stride, B, counts_c, rate, self._flac_tables.data_ptr(),
+                                               out.data_ptr(), total, max_abs.data_ptr(), self._stream()))
+            host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(out, non_blocking=True)
+            host_max = torch.empty(max_abs.shape, dtype=torch.float32, pin_memory=True)
+            host_max.copy_(max_abs, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(self.device))
+        res = EncodedFlac(host, offsets, host_max, counts, rate, event)
+        return res.wait() if wait else res
 
     def window_advance(self, mel_window, mel_new, noise_window=None, noise_new=None):
         """mbx_window_advance: shift the device-resident windows (B, T, mel_channels) / (B, T*steps_per_frame) left by the
@@ -1324,6 +1363,34 @@ class MBExWNEngine:
                                          ceps_index.contiguous().data_ptr() if ceps_index is not None else None,
                                          B, T, audio.data_ptr(), scratch.data_ptr(), self._stream()))
         return audio
+
+
+class EncodedFlac:
+    """What :meth:`MBExWNEngine.encode_flac16` returns: the frames of every item in one pinned host buffer (item b at
+    ``offsets[b]:offsets[b + 1]``) and max |x| per item, behind the event of their device-to-host copies."""
+
+    def __init__(self, host, offsets, max_abs, n_samples, rate, event):
+        self._host, self._host_max, self._event = host, max_abs, event
+        self.offsets, self.n_samples, self.rate = offsets, list(n_samples), rate
+        self.max_abs = None
+
+    def wait(self):
+        if self._event is not None:
+            self._event.synchronize()
+            self._event = None
+            self.max_abs = self._host_max.numpy()[:len(self.n_samples)]
+        return self
+
+    def frames(self, b):
+        """The frames of item b (a numpy view of the pinned buffer)."""
+        self.wait()
+        return self._host.numpy()[self.offsets[b]:self.offsets[b + 1]]
+
+    def stream(self, b):
+        """The whole FLAC stream of item b (``flac.assemble``); only for an item whose max |x| is finite -- any other goes
+        through the host writer, ``flac.encode``."""
+        from . import flac
+        return flac.assemble(self.frames(b), self.n_samples[b], self.rate)
 
 
 class _HostTensor:

@@ -6,6 +6,10 @@ VERBATIM sub-frame stores the samples as they are, and with 16-bit samples every
 aligned, so a valid stream (magic, STREAMINFO with the MD5 of the samples, frames with CRC-8 / CRC-16) can be assembled
 with numpy alone.  Any FLAC decoder reads the result; the files are the size of a wav.
 
+The layout of the frames and the headers are defined here once (frame_layout, frame_header, stream_header): ``encode``
+builds a stream from them, and the device encoder (csrc/flac_frames.hip through ``MBExWNEngine.encode_flac16``) writes the
+same frames, in front of which ``write_frames`` / ``assemble`` put the header with the MD5 of the samples.
+
 Format: https://xiph.org/flac/format.html (STREAMINFO, FRAME_HEADER, SUBFRAME_VERBATIM, FRAME_FOOTER).
 """
 import hashlib
@@ -14,7 +18,9 @@ import struct
 import numpy as np
 
 BLOCK = 4096                                # samples per channel of every frame but the last
+HEADER_BYTES = 42                           # "fLaC" + STREAMINFO in front of the frames
 _RATE_CODES = {88200: 1, 176400: 2, 192000: 3, 8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 44100: 9, 48000: 10, 96000: 11}
+_NUMBER_LIMITS = (0x80, 0x800, 0x10000, 0x200000, 0x4000000)   # a "UTF-8" frame number takes one more byte at each
 
 
 def _crc_table(poly, bits):
@@ -47,6 +53,47 @@ def crc16(data):
     return crc
 
 
+def _gf2_apply(columns, value):
+    out = 0
+    for jj in range(16):
+        if value >> jj & 1:
+            out ^= columns[jj]
+    return out
+
+
+_SHIFT_OPS = []
+CRC16_DEVICE_SHIFTS = 16                    # operators the device encoder takes (its frames are shorter than 2^14 bytes)
+
+
+def crc16_shift_operators(count):
+    """The operators M_{2^k}, k < count, of the CRC-16: M_n advances the register over n zero bytes.  With init 0 and no
+    final XOR the CRC is linear over GF(2), so crc16(a + b) = M_len(b) crc16(a) ^ crc16(b).  An operator is its 16 columns:
+    column j is the register 1 << j advanced."""
+    if not _SHIFT_OPS:
+        _SHIFT_OPS.append([((1 << jj << 8) & 0xFFFF) ^ _CRC16[(1 << jj) >> 8] for jj in range(16)])
+    while len(_SHIFT_OPS) < count:
+        prev = _SHIFT_OPS[-1]
+        _SHIFT_OPS.append([_gf2_apply(prev, _gf2_apply(prev, 1 << jj)) for jj in range(16)])
+    return _SHIFT_OPS[:count]
+
+
+def crc16_combine(crc_a, crc_b, len_b):
+    """crc16(a + b) from crc16(a), crc16(b) and len(b): M_len(b) is the product of the operators of the set bits of len(b)."""
+    nn = int(len_b)
+    ops = crc16_shift_operators(max(1, nn.bit_length()))
+    for kk in range(nn.bit_length()):
+        if nn >> kk & 1:
+            crc_a = _gf2_apply(ops[kk], crc_a)
+    return crc_a ^ crc_b
+
+
+def crc16_device_tables():
+    """What mbx_encode_flac16 takes as ``crc_tables``: uint16 (256 + 16 * CRC16_DEVICE_SHIFTS), the byte table of crc16, then
+    the columns of M_1, M_2, M_4, ... (include/mbexwn.h)."""
+    ops = crc16_shift_operators(CRC16_DEVICE_SHIFTS)
+    return np.asarray(_CRC16 + [cc for op in ops for cc in op], dtype=np.uint16)
+
+
 def _utf8_number(value):
     """The "UTF-8" coding of a frame number (up to 31 bits)."""
     if value < 0x80:
@@ -74,6 +121,47 @@ def to_pcm16(data):
     return np.clip(np.rint(data.astype(np.float64) * 32767.0), -32768, 32767).astype(np.int16)
 
 
+def frame_layout(n, channels=1):
+    """Where the frames of an n-sample stream lie behind its header: int64 arrays ``offsets`` (frames + 1: frame f spans
+    bytes offsets[f]:offsets[f + 1]), ``sizes`` (samples per channel of every frame) and ``heads`` (bytes of every frame's
+    header, CRC-8 included; the sub-frames follow it, each a 0x02 byte and 2 * size bytes)."""
+    index = np.arange(-(-int(n) // BLOCK), dtype=np.int64)
+    sizes = np.minimum(BLOCK, int(n) - index * BLOCK)
+    number = 1 + sum((index >= lim).astype(np.int64) for lim in _NUMBER_LIMITS)
+    heads = 4 + number + 2 * (sizes != BLOCK) + 1
+    offsets = np.zeros(index.size + 1, dtype=np.int64)
+    np.cumsum(heads + channels * (1 + 2 * sizes) + 2, out=offsets[1:])
+    return offsets, sizes, heads
+
+
+def frames_bytes(n, channels=1):
+    """Bytes of the frames of an n-sample stream (the stream without its 42-byte header)."""
+    return int(frame_layout(n, channels)[0][-1])
+
+
+def frame_header(index, size, rate, channels=1):
+    """Header of frame ``index`` holding ``size`` samples per channel of a ``rate`` Hz stream, CRC-8 included."""
+    size_code = 12 if size == BLOCK else 7                       # 1100: 4096; 0111: 16-bit (blocksize - 1) follows
+    rate_code = _RATE_CODES.get(int(rate), 0)                    # 0000: take the rate from STREAMINFO
+    head = bytes([0xFF, 0xF8, (size_code << 4) | rate_code, ((channels - 1) << 4) | (4 << 1)])     # 100: 16 bits
+    head += _utf8_number(index)
+    if size_code == 7:
+        head += struct.pack(">H", size - 1)
+    return head + bytes([crc8(head)])
+
+
+def stream_header(n, rate, md5, channels=1):
+    """The 42 bytes in front of the frames: "fLaC" and STREAMINFO (block sizes, the smallest and largest frame of
+    frame_layout, rate, channels, 16 bits, sample count, ``md5`` = MD5 digest of the little-endian int16 samples)."""
+    lengths = np.diff(frame_layout(n, channels)[0])
+    min_frame, max_frame = (int(lengths.min()), int(lengths.max())) if lengths.size else (0, 0)
+    info = struct.pack(">HH", BLOCK, BLOCK) + min_frame.to_bytes(3, "big") + max_frame.to_bytes(3, "big")
+    packed = (int(rate) << 44) | ((channels - 1) << 41) | ((16 - 1) << 36) | int(n)          # 20 + 3 + 5 + 36 bits
+    info += packed.to_bytes(8, "big") + md5
+    assert len(info) == 34
+    return b"fLaC" + bytes([0x80]) + len(info).to_bytes(3, "big") + info         # last-block flag | STREAMINFO
+
+
 def encode(data, rate):
     """bytes of a FLAC stream holding ``data`` (float or int16; (frames,) or (frames, channels <= 8)) at ``rate`` Hz."""
     pcm = to_pcm16(data)
@@ -84,34 +172,43 @@ def encode(data, rate):
         raise ValueError("FLAC: 1..8 channels and a sample rate below 2^20 Hz")
     rate = int(rate)
     frames = []
-    min_frame = max_frame = 0
     for index, start in enumerate(range(0, n, BLOCK)):
         block = pcm[start:start + BLOCK]
-        size = block.shape[0]
-        size_code = 12 if size == BLOCK else 7                       # 1100: 4096; 0111: 16-bit (blocksize - 1) follows
-        rate_code = _RATE_CODES.get(rate, 0)                         # 0000: take the rate from STREAMINFO
-        head = bytes([0xFF, 0xF8, (size_code << 4) | rate_code, ((channels - 1) << 4) | (4 << 1)])     # 100: 16 bits
-        head += _utf8_number(index)
-        if size_code == 7:
-            head += struct.pack(">H", size - 1)
-        head += bytes([crc8(head)])
+        frame = frame_header(index, block.shape[0], rate, channels)
         # one VERBATIM sub-frame per channel: 0 | 000001 | 0, then the samples big-endian
-        body = b"".join(b"\x02" + block[:, ch].astype(">i2").tobytes() for ch in range(channels))
-        frame = head + body
+        frame += b"".join(b"\x02" + block[:, ch].astype(">i2").tobytes() for ch in range(channels))
         frame += struct.pack(">H", crc16(frame))
         frames.append(frame)
-        min_frame = len(frame) if min_frame == 0 else min(min_frame, len(frame))
-        max_frame = max(max_frame, len(frame))
     md5 = hashlib.md5(pcm.astype("<i2").tobytes()).digest()
-    info = struct.pack(">HH", BLOCK, BLOCK) + min_frame.to_bytes(3, "big") + max_frame.to_bytes(3, "big")
-    packed = (rate << 44) | ((channels - 1) << 41) | ((16 - 1) << 36) | n          # 20 + 3 + 5 + 36 bits
-    info += packed.to_bytes(8, "big") + md5
-    assert len(info) == 34
-    header = b"fLaC" + bytes([0x80]) + len(info).to_bytes(3, "big") + info         # last-block flag | STREAMINFO
-    return header + b"".join(frames)
+    return stream_header(n, rate, md5, channels) + b"".join(frames)
+
+
+def pcm16_from_frames(frames, n):
+    """The int16 samples of the mono frames of an n-sample stream (frame_layout): their big-endian sub-frame bodies,
+    byte-swapped into a little-endian array (what the MD5 of STREAMINFO is taken over)."""
+    offsets, sizes, heads = frame_layout(n)
+    pcm = np.empty(int(n), dtype="<i2")
+    for ff in range(sizes.size):
+        pcm[ff * BLOCK:ff * BLOCK + sizes[ff]] = np.frombuffer(frames, dtype=">i2", count=int(sizes[ff]),
+                                                               offset=int(offsets[ff] + heads[ff] + 1))
+    return pcm
+
+
+def assemble(frames, n, rate):
+    """The whole mono stream from frames encoded elsewhere (the device encoder): header with the MD5 of their samples, frames."""
+    return stream_header(n, rate, hashlib.md5(pcm16_from_frames(frames, n)).digest()) + bytes(frames)
 
 
 def write(path, data, rate):
     with open(path, "wb") as fo:
         fo.write(encode(data, rate))
+    return path
+
+
+def write_frames(path, frames, n, rate):
+    """``assemble`` into a file, the frames written as they are (no copy)."""
+    md5 = hashlib.md5(pcm16_from_frames(frames, n)).digest()
+    with open(path, "wb") as fo:
+        fo.write(stream_header(n, rate, md5))
+        fo.write(frames)
     return path

@@ -15,9 +15,10 @@ log_to_db = 20 * np.log10(np.exp(1))   # reference vocoder/model/preprocess.py:7
 
 
 class MELInverter(object):
-    def __init__(self, model_id_or_path: Union[str, None] = None, verbose: bool = False, calibrate: bool = False):
-        """As the reference's constructor (mel_inverter.py:22-41); ``calibrate`` (this build) is handed to
-        :meth:`load_model`."""
+    def __init__(self, model_id_or_path: Union[str, None] = None, verbose: bool = False, calibrate: bool = False,
+                 batch_invariant: Union[bool, None] = None):
+        """As the reference's constructor (mel_inverter.py:22-41); ``calibrate`` and ``batch_invariant`` (this build) are
+        handed to :meth:`load_model`."""
         self.model = None
         self._calibrate_pending = False
         self._verbose = verbose
@@ -38,7 +39,20 @@ class MELInverter(object):
         self.use_max_limit = False
 
         if model_id_or_path:
-            self.load_model(model_id_or_path=model_id_or_path, verbose=verbose, calibrate=calibrate)
+            self.load_model(model_id_or_path=model_id_or_path, verbose=verbose, calibrate=calibrate,
+                            batch_invariant=batch_invariant)
+
+    @classmethod
+    def host_only(cls, model_id_or_path):
+        """An instance with a model's pre-processing parameters and no engine: :meth:`scale_mel` in a process that must not
+        initialise HIP (the parent of a multi-GPU job, batched.plan_ranks)."""
+        from . import get_config_file
+        from .config import read_config
+        inv = cls()
+        inv.model_id_or_path = model_id_or_path
+        inv.config_file = get_config_file(model_id_or_path=model_id_or_path)
+        inv._set_preprocess_config(read_config(config_file=inv.config_file)["preprocess_config"])
+        return inv
 
     @property
     def srate(self):
@@ -124,6 +138,12 @@ class MELInverter(object):
 
         ``noise`` optionally injects the N(0,1) draw of the noise channel (shape (B, T*steps_per_frame));
         by default it is drawn on the device, as the reference draws tf.random.normal."""
+        self._calibrate_if_pending(scaled_mell)
+        syn_audio = self.model.infer(scaled_mell, sigma=None, synth_length=scaled_mell.shape[1] * self.hop_size,
+                                     noise=noise).numpy()
+        return syn_audio.ravel()
+
+    def _calibrate_if_pending(self, scaled_mell):
         if self._calibrate_pending:
             # load_model(..., calibrate=True): the FIRST mel synthesised decides the form for every later call (at most 400 of
             # its frames are used) -- results therefore depend on which utterance came first; calibrate([...]) on a fixed set
@@ -136,9 +156,40 @@ class MELInverter(object):
                 import warnings
                 warnings.warn(f"MELInverter: calibration on the first mel failed ({exc}); keeping the convolution form "
                               f"chosen at creation ({self.model.conv_form_info()['form']})", RuntimeWarning)
-        syn_audio = self.model.infer(scaled_mell, sigma=None, synth_length=scaled_mell.shape[1] * self.hop_size,
-                                     noise=noise).numpy()
-        return syn_audio.ravel()
+
+    def synth_from_mels(self, scaled_mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False):
+        """Batched :meth:`synth_from_mel` (this build): a list of ``scale_mel`` outputs (1, T_i, mel_channels) -> a list of
+        float32 audio (T_i * hop_size,), or with ``flac=True`` of complete FLAC files (bytes; frames encoded on the device).
+
+        The mels run in padded micro-batches (sharding.plan_batches, at most ``max_batch`` items and ``max_padded_frames``
+        padded frames each) through the engine's forward with per-item lengths.  ``noises``: per-item N(0,1) draws
+        (T_i * wn_in_rows_per_frame,), default: the draws :meth:`synth_from_mel` would make called on the list one by one
+        (batched.replay_noise) -- with a ``batch_invariant`` engine the results are then bit-identical to those calls."""
+        import torch
+        from .batched import replay_noise, run_micro_batches
+        if len(scaled_mels):
+            self._calibrate_if_pending(scaled_mels[0])
+        mels =[np.asarray(mm, dtype=np.float32).reshape(-1, mm.shape[-2], mm.shape[-1])[0] for mm in scaled_mels]
+        dims = self.model.dims
+        if not dims.noise_sigma:
+            noises = None
+        elif noises is None:
+            noises = replay_noise([mm.shape[0] for mm in mels], dims.wn_in_rows_per_frame, device=self.model.device)
+        else:
+            noises = [torch.as_tensor(np.asarray(zz) if not torch.is_tensor(zz) else zz).to(self.model.device, torch.float32)
+                      .reshape(-1) for zz in noises]
+        out = [None] * len(mels)
+        for batch in run_micro_batches(self.model, mels, noises, max_batch, max_padded_frames, flac=flac, host_audio=not flac):
+            batch.wait()
+            for jj, ii in enumerate(batch.indices):
+                if not flac:
+                    out[ii] = batch.audio(jj)
+                elif np.isfinite(batch.flac.max_abs[jj]):
+                    out[ii] = batch.flac.stream(jj)
+                else:
+                    from . import flac as flac_writer
+                    out[ii] = flac_writer.encode(batch.audio(jj), self.srate)
+        return out
 
     def calibrate(self, scaled_mells, verbose=False, max_frames=400, seed=42):
         """Decide the form of the WaveNet's dilated convolution on REAL data (this build; C ABI mbx_calibrate).
@@ -214,9 +265,12 @@ class MELInverter(object):
         return data_dict
 
     # ------------------------------------------------------------------------------------------
-    def load_model(self, model_id_or_path, verbose=False, calibrate=False):
+    def load_model(self, model_id_or_path, verbose=False, calibrate=False, batch_invariant=None):
         """reference mel_inverter.py:184-239: resolve the model directory, read ``config.yaml``, build the
         generator, restore the weights and copy the pre-processing parameters onto the instance.
+
+        ``batch_invariant`` (this build; ``mbx_config.batch_invariant``, None = the engine's default): True pins the engine's
+        kernels so that an utterance's bits do not depend on the batch it runs in (:meth:`synth_from_mels`).
 
         ``calibrate=True`` (this build; ORDER DEPENDENT: the decision is taken on at most 400 frames of the first utterance and
         binds every later one, a failing calibration keeps the creation-time form with a warning): the first mel handed to
@@ -251,14 +305,17 @@ class MELInverter(object):
             raw = load_reference_checkpoint(weights_tf, hparams)
         else:
             raise FileNotFoundError(f"error::no weights found under {model_dir} (expected weights.npz or weights.tf.index)")
-        self.model = MBExWNEngine(hparams, raw)
+        self.model = MBExWNEngine(hparams, raw, batch_invariant=batch_invariant)
         self._calibrate_pending = bool(calibrate)
         self._verbose = bool(verbose)
         if verbose:
             info = self.model.conv_form_info()
             print(f"convolution form {info['form']} (requested {info['requested']}, calibrated at creation on a synthetic mel: "
                   f"{'yes' if info['calibrated'] == 1 else 'no'})", file=sys.stderr)
+        self._set_preprocess_config(self.preprocess_config)
 
+    def _set_preprocess_config(self, preprocess_config):
+        self.preprocess_config = preprocess_config
         self.mel_channels = self.preprocess_config["mel_channels"]
         self.hop_size = self.preprocess_config["hop_size"]
         self.fft_size = self.preprocess_config["fft_size"]
@@ -280,7 +337,6 @@ class MELInverter(object):
         self.use_max_limit = False
         if self.preprocess_config.get("use_max_limit", False):
             self.use_max_limit = self.preprocess_config["use_max_limit"]
-        return
 
 
 def create_synthetic_model_dir(path, voice_type="SPEECH", seed=1234, weights_format="npz", **config_overrides):

@@ -9,7 +9,30 @@ Partitioning: longest-processing-time-first greedy assignment (cost = frames), t
 micro-batches of similar length; every boundary op of the engine honours the item's own length, so padded
 batches give exactly the one-at-a-time results.
 """
+import os
+import subprocess
+import sys
+
 import numpy as np
+
+
+def visible_gpu_count():
+    """GPUs this process may use, WITHOUT initialising HIP in this process (the parent of the ranks of a multi-GPU job must
+    never touch the GPU): the visibility variables when they are set, else torch.cuda.device_count() evaluated in a child
+    process."""
+    counts = []
+    for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
+        val = os.environ.get(var)
+        if val is not None:
+            counts.append(len([tok for tok in val.split(",") if tok.strip() != ""]))
+    if counts:
+        return min(counts)
+    res = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True,
+                         text=True, timeout=600)
+    try:
+        return int(res.stdout.strip().splitlines()[-1])
+    except (ValueError, IndexError):
+        raise RuntimeError(f"cannot count the GPUs: {res.stderr[-400:]}")
 
 
 def lpt_partition(lengths, world_size):

@@ -304,7 +304,14 @@ mbx_status mbx_calibrate(mbx_handle *handle, const float *mel, const int32_t *n_
                          int32_t max_frames, const float *noise, void *workspace, size_t workspace_bytes,
                          void *hip_stream);
 
-/* Bytes of device workspace mbx_forward needs for `batch` items of at most `max_frames` mel frames. */
+/* Bytes of device workspace mbx_forward needs for `batch` items of at most `max_frames` mel frames.
+ * The memory contract of every forward (mbx_forward, mbx_forward_stream, mbx_forward_ex, mbx_calibrate), held by
+ * tests/test_gpu_memory_contract.py: the workspace need not be initialised -- no result depends on what it held before, so
+ * one buffer may serve forwards of any batch shape and of any handle, one after the other; nothing outside
+ * [workspace, workspace + mbx_workspace_size(handle, batch, max_frames)) and the stated extent of each output (audio,
+ * state_out, the caller's stores) is written; no input is read outside its stated extent.  A workspace_bytes below
+ * mbx_workspace_size returns MBX_ERR_WORKSPACE and a workspace that is not 256-byte aligned MBX_ERR_INVALID_ARGUMENT, both
+ * before anything is enqueued. */
 size_t mbx_workspace_size(const mbx_handle *handle, int32_t batch, int32_t max_frames);
 
 /* Replaces: model.infer(mell, synth_length=T*hop) (reference mel_inverter.py:152, wavegen_1d.py:483-526,
@@ -489,6 +496,8 @@ mbx_status mbx_profile_read_launches(mbx_handle *handle, const char *kernel, flo
 mbx_status mbx_clock_probe(mbx_handle *handle, uint64_t *device_out4, int64_t real_ticks, void *hip_stream);
 
 /* ---- stage entry points (unit parity; all pointers device memory) ------------------------------- */
+/* The same memory contract as the forward: an entry point writes nothing outside the stated extent of its outputs and its
+ * scratch, reads no input outside its stated extent, and no result depends on what the outputs or the scratch held before. */
 
 /* TFPQMF.synthesis (reference tf_preprocess.py:204-226): x (batch, n_steps, subbands) -> y (batch, n_steps*subbands) */
 mbx_status mbx_pqmf_synthesis(mbx_handle *handle, const float *x, int32_t batch, int32_t n_steps, float *y,

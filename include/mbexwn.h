@@ -184,8 +184,10 @@ typedef struct {
      * only. */
     int32_t ps_subband_gain;
     /* pp_mod_subnet.padding: CAUSAL (Keras "causal"): the dilated, pre-conditioning, conditioning and up-sampling
-     * convolutions of the WaveNet blocks pad dilation * (kernel size - 1) zeros in front and none behind.  Generic
-     * kernels, whole items only. */
+     * convolutions of the WaveNet blocks pad dilation * (kernel size - 1) zeros in front and none behind.  Several
+     * blocks: generic kernels, whole items only.  One block: the direct form under MBX_CONV_AUTO / _DIRECT; a pinned
+     * MBX_CONV_F23 / _F43 runs the Winograd gate kernels on windows shifted by d rows (dilations up to 16; above: the
+     * direct form, per layer) with the start convolution folded into layer 0, and streams (layer state below). */
     int32_t wn_causal;
     /* ---- ABI 7: numerics / kernel policy (all zero = the defaults) ------------------------------------------------ */
     int32_t wn_conv_form;        /* MBX_CONV_* */
@@ -387,7 +389,12 @@ typedef struct {
      * tick runs every layer only on the rows that are new.  Layer l is exact up to its own reach in front of the rows
      * layer l-1 is exact for (a staircase that ends mbx_layer_state_info().reach_rows in front of the end of the WaveNet
      * region); a slot of the store keeps, per layer, the rows of the layer's input and of the output accumulator the next
-     * tick reads from in front of its own rows.
+     * tick reads from in front of its own rows.  Slot layout, per layer l = 1 .. L-1 in order (r = d_l (k - 1) / 2,
+     * step = r rounded up to even): SAME padding -- the rows [e_l - r, e_l + step) of h_l (C floats each), then the rows
+     * [e_l, e_l + step) of the accumulator (wn_out_channels floats each), e_l = E - reach_rows + (steps of the layers
+     * behind l); CAUSAL padding -- no error spreads backwards, e_l = E - reach_rows for every layer (reach_rows = the
+     * clamped conditioning tail cond_lin_upsampling - 1, rounded up to a frame) and the slot keeps the rows
+     * [e_l - 2 r, e_l) of h_l only (min_rows = 2 r of the widest layer).
      *   layer_store         device (slots, layer_store_floats) persistent buffer of the caller
      *   layer_store_floats  floats per slot (mbx_layer_state_info)
      *   layer_carry         device (batch, 3) int32: slot of the item; window row (WaveNet rate) the stored state ends at =

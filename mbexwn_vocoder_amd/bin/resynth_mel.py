@@ -27,13 +27,13 @@ from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 
 
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
-         num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, rank=None, job=None):
+         num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None):
     format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
     if gpus > 1 and rank is None:
         # --gpus N: this parent never initialises HIP; N fresh child processes write their share of the files each
         from mbexwn_vocoder_amd.batched import run_ranks
         argv = [model_id, "-i", *input_mell_files, "--format", format, "-nt", str(num_threads), "--batch", str(batch),
-                "--calibrate", str(calibrate)] + (["-o", output_dir] if output_dir else [])
+                "--calibrate", str(calibrate), "--conv-form", conv_form] + (["-o", output_dir] if output_dir else [])
         argv += [flag for flag, on in (("-g", use_gpu), ("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant))
                  if on]
         sys.exit(run_ranks(os.path.abspath(__file__), argv, model_id, input_mell_files, gpus, threads=num_threads,
@@ -62,7 +62,8 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         torch.manual_seed(seed)
 
     MelInv = mel_inverter.MELInverter(model_id_or_path=model_id, verbose=verbose,
-                                      batch_invariant=True if batch_invariant else None)
+                                      batch_invariant=True if batch_invariant else None,
+                                      conv_form=None if conv_form == "auto" else conv_form)
     if output_dir:
         os.makedirs(output_dir, exist_ok=True)
     if calibrate and input_mell_files:
@@ -133,6 +134,9 @@ if __name__ == "__main__":
     parser.add_argument("--batch-invariant", action="store_true",
                         help="pin the engine's kernels so that a file's audio does not depend on the batch it ran in: with "
                              "this flag on both sides, batched files are bit-identical to one-at-a-time files")
+    parser.add_argument("--conv-form", default="auto", choices=["auto", "direct", "f23", "f43"],
+                        help="form of the WaveNet's dilated convolution: auto = calibrated at model load; a causal model "
+                             "(force_causal) runs its Winograd kernels only when f23 / f43 is pinned (Def: %(default)s)")
     parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
     parser.add_argument("--job", default=None, help=SUPPRESS)
     args = parser.parse_args()

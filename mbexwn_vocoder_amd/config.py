@@ -281,6 +281,11 @@ class ModelDims:
         self.wn_padding = str(wn.get("padding", "SAME")).upper()
         if self.wn_padding not in ("SAME", "CAUSAL"):
             raise NotImplementedError(f"pp_mod_subnet.padding {self.wn_padding}: SAME and CAUSAL are supported")
+        # force_causal: every convolution of the model pads in front only, the WaveNet's whatever pp_mod_subnet.padding says
+        # (reference custom_pulsed_generator.py:474-475); the sub-nets get their causal pads in subnet.build_subnet
+        self.force_causal = bool(mb.get("force_causal", False))
+        if self.force_causal:
+            self.wn_padding = "CAUSAL"
         self.wn_use_weight_norm = bool(wn.get("use_weight_norm", False))
         self.cond_lin_upsampling = int(wn.get("cond_lin_upsampling", 16))
         self.cond_kernel_size = int(wn.get("cond_kernel_size", 3))

@@ -842,10 +842,12 @@ mbx_status mbx_create(const mbx_config *config, const mbx_tensor *tensors, int32
                    expect("wn.res_skip_" + std::to_string(l) + ".fold_b", C + c.wn_out_channels);
         have = have && expect("wn.tail.fold", (long long)((C + 7) / 8) * 256) && expect("wn.tail.fold_b", c.wn_out_channels);
         if (c.n_wn_blocks >= 1) have = false;      // several blocks: generic kernels (run_wavenet_blocks)
-        const bool sym = !c.wn_causal;              // the folded first layer and the Winograd forms assume SAME padding
+        // causal padding folds the start only under a pinned Winograd form: MBX_CONV_AUTO keeps the kernels it always ran
+        const bool pinned = c.wn_conv_form == MBX_CONV_F23 || c.wn_conv_form == MBX_CONV_F43;
+        const bool fold_pad = !c.wn_causal || pinned;
         hd->fold_skip = have;
         // start convolution folded into layer 0 (wn_gate0.hip); wn_keep_start keeps the h0 tensor and the full layer
-        bool have0 = have && sym && !c.wn_keep_start && c.wn_kernel_size == 3 &&
+        bool have0 = have && fold_pad && !c.wn_keep_start && c.wn_kernel_size == 3 &&
                      mbx::wn_gate0_fits(C, c.pulse_channels * (1 + c.wt_subharm_channels), c.wn_dilations[0], c.cond_lin_upsampling) &&
                      expect("wn.conv1D_0.start_fold", (long long)((C + 31) / 32) * 1536);
         if (have0 && c.wn_layers > 1)
@@ -916,9 +918,13 @@ size_t mbx_workspace_size(const mbx_handle *handle, int32_t batch, int32_t max_f
 // e_l = e_{l-1} - step[l] (step = the reach rounded up to even rows: the rows of the n_out-wide accumulator stay 8-byte
 // aligned).  A slot keeps per layer l >= 1 the rows [e_l - r[l], e_l + step[l]) of h_l and [e_l, e_l + step[l]) of the
 // accumulator.
+// CAUSAL padding: layer l reads r[l] = 2 d rows in front of an output and none behind (ahead[l] = 0), so no layer's
+// error at a region end spreads backwards: every layer is exact up to the same row e = E - reach_rows (the clamped
+// conditioning tail only), c[l] = step[l] = 0, and a slot keeps per layer l >= 1 the rows [e - 2 d, e) of h_l (no
+// accumulator rows: every layer adds to the same new rows).
 struct LayerGeom {
     int floats, reach_rows, min_rows;
-    int r[MBX_MAX_WN_LAYERS], step[MBX_MAX_WN_LAYERS], c[MBX_MAX_WN_LAYERS];
+    int r[MBX_MAX_WN_LAYERS], ahead[MBX_MAX_WN_LAYERS], step[MBX_MAX_WN_LAYERS], c[MBX_MAX_WN_LAYERS];
     long long off[MBX_MAX_WN_LAYERS];
 };
 
@@ -934,16 +940,20 @@ static LayerGeom layer_geom(const mbx_handle *hd) {
         const int d = c.wn_dilations[l];
         if (!wino || d > 16 || (d & (d - 1)) != 0) return g;
     }
+    const bool causal = c.wn_causal != 0;
     for (int l = 0; l < L; ++l) {
-        g.r[l] = c.wn_dilations[l] * (c.wn_kernel_size - 1) / 2;
-        g.step[l] = (g.r[l] + 1) & ~1;
+        g.r[l] = c.wn_dilations[l] * (c.wn_kernel_size - 1) / (causal ? 1 : 2);
+        g.ahead[l] = causal ? 0 : g.r[l];
+        g.step[l] = causal ? 0 : (g.r[l] + 1) & ~1;
     }
     g.c[L - 1] = 0;
     for (int l = L - 2; l >= 0; --l) g.c[l] = g.c[l + 1] + g.step[l + 1];
     const int spf = c.steps_per_frame;
     // (+ cond_lin_upsampling - 1: a whole-region run interpolates the conditioning of its last rows towards the clamped
-    // last conditioning row; that error spreads backwards through the layers behind, streaming.py::stream_margins)
-    g.reach_rows = (g.c[0] + g.r[0] + c.cond_lin_upsampling - 1 + spf - 1) / spf * spf;
+    // last conditioning row; that error spreads backwards through the layers behind, streaming.py::stream_margins --
+    // under CAUSAL padding it stays where it is)
+    const int spread = causal ? 0 : g.c[0] + g.r[0];
+    g.reach_rows = (spread + c.cond_lin_upsampling - 1 + spf - 1) / spf * spf;
     long long off = 0;
     for (int l = 1; l < L; ++l) {
         g.off[l] = off;
@@ -1137,8 +1147,8 @@ static mbx_status forward_impl(mbx_handle *hd, const float *mel, const int32_t *
     // rows per item = 2.9 h of audio at the canonical 1.6 kHz is the tested side of that
     if ((long long)max_frames * hd->cfg.steps_per_frame >= (1LL << 24))
         return fail(MBX_ERR_UNSUPPORTED, "an item may have at most 2^24 - 1 sub-band rows (split longer recordings)");
-    if ((!hd->blocks.empty() || hd->cfg.wn_causal) && (active_frames || st_in || st_out || sub_carry || ex.lay || fe_on))
-        return fail(MBX_ERR_UNSUPPORTED, "a model with several WaveNet blocks or causal padding runs whole items only (no stream windows / state)");
+    if (!hd->blocks.empty() && (active_frames || st_in || st_out || sub_carry || ex.lay || fe_on))
+        return fail(MBX_ERR_UNSUPPORTED, "a model with several WaveNet blocks runs whole items only (no stream windows / state)");
     DeviceGuard guard(hd->device);
     if (!guard.ok) return fail(MBX_ERR_HIP, "cannot select the handle's device");
     const mbx_config &c = hd->cfg;
@@ -1345,7 +1355,7 @@ static mbx_status forward_impl(mbx_handle *hd, const float *mel, const int32_t *
             const int phase = (int)(A % cond_up);
             // rows of the launch: up to the layer's reach behind the last new row, and far enough that the conditioning
             // row behind the last new row is not the item's last one (which is where the interpolation clamps)
-            const long long n1 = e + geo.r[l] - A;
+            const long long n1 = e + geo.ahead[l] - A;
             const long long n2 = (long long)cond_up * ((e - 1 - A + phase) / cond_up + 2) - phase;
             const long long need = std::max(n1, n2);
             if (A + need > nsteps) return fail(MBX_ERR_INVALID_ARGUMENT, "layer_rows: the region ends too close to the window end");
@@ -1416,6 +1426,7 @@ static mbx_status forward_impl(mbx_handle *hd, const float *mel, const int32_t *
             g0.channels = C;
             g0.gate_act = c.wn_gate_activation;
             g0.dil = d;
+            g0.causal = c.wn_causal;
             g0.cond = g.cond;
             g0.cond_bstride = g.cond_bstride;
             g0.cond_up = g.cond_up;
@@ -1787,13 +1798,16 @@ static mbx_status forward_impl(mbx_handle *hd, const float *mel, const int32_t *
 }
 
 // ---- form of the dilated convolution -----------------------------------------------------------------------------------
-// A Winograd form is available when the host supplied its weight images for every layer that runs a gate kernel, the
-// padding is SAME and the kernel size 3 (layers whose dilation does not fit the kernels fall back per layer).
+// A Winograd form is available when the host supplied its weight images for every layer that runs a gate kernel and the
+// kernel size is 3 (layers whose dilation does not fit the kernels fall back per layer).  CAUSAL padding runs the same
+// kernels on a window shifted by d rows, on a single block whose configuration pins a Winograd form: MBX_CONV_AUTO and the
+// block runner keep the direct form there.
 static bool form_available(const mbx_handle *hd, int form) {
     const mbx_config &c = hd->cfg;
     if (form == MBX_CONV_DIRECT) return true;
     if (form != MBX_CONV_F23 && form != MBX_CONV_F43) return false;
-    if (c.wn_causal || c.wn_kernel_size != 3) return false;
+    if (c.wn_kernel_size != 3) return false;
+    if (c.wn_causal && (!hd->blocks.empty() || (c.wn_conv_form != MBX_CONV_F23 && c.wn_conv_form != MBX_CONV_F43))) return false;
     const bool f43 = form == MBX_CONV_F43;
     auto images = [&](const std::string &prefix, int C, int l0) {
         if (l0 >= c.wn_layers) return false;
@@ -1815,7 +1829,8 @@ static bool form_available(const mbx_handle *hd, int form) {
 
 static void set_form(mbx_handle *hd, int form) {
     hd->winograd = form == MBX_CONV_F43 ? 4 : form == MBX_CONV_F23 ? 2 : 0;
-    if (hd->cfg.wn_causal) hd->winograd = 0;  // causal padding: the direct form (generic kernel)
+    // causal padding without a pinned Winograd form, or in the block runner: the direct form (generic kernel)
+    if (hd->cfg.wn_causal && !form_available(hd, form)) hd->winograd = 0;
     hd->winograd4_always = hd->winograd == 4 && hd->cfg.batch_invariant != 0;
 }
 

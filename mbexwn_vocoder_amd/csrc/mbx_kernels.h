@@ -134,6 +134,7 @@ struct Gate0Args {
     const float *w;           // image of engine.fold_start_weights (ceil(C/32), 3, 2, 64, 4)
     const float *bias;        // (2C) gate bias or null
     int channels, dil;
+    int causal;               // 0: SAME (taps t - d, t, t + d), 1: CAUSAL (taps t - 2d, t - d, t)
     const float *cond;        // (batch, rows/cond_up, 2C)
     long long cond_bstride;
     int cond_up;

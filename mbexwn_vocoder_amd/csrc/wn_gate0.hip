@@ -21,8 +21,8 @@
 // channels {2 kq + m} of tap tau.  The weights of a column tile are 24 registers per lane (loaded once per wave).  The
 // 24 MFMAs of tile i + 1 are issued between the activation arithmetic of tile i, three per output channel (two
 // accumulator sets).  Everything the block needs from global memory is requested up front (one round trip instead of a
-// chain of them), then staged in LDS: the rows x'[m0 - d, m0 + 256 + d) (32 bytes each, 16-byte chunk c at 2*row +
-// (c ^ ((row>>3)&1)): bank-conflict free 8-byte operand reads), the conditioning rows of the block (<= 32 x (32 tanh |
+// chain of them), then staged in LDS: the rows x'[m0 - d, m0 + 256 + d) (CAUSAL padding: [m0 - 2d, m0 + 256)) (32 bytes
+// each, 16-byte chunk c at 2*row + (c ^ ((row>>3)&1)): bank-conflict free 8-byte operand reads), the conditioning rows of the block (<= 32 x (32 tanh |
 // 32 sigmoid), row pitch 68 floats) and the per-row interpolation tables.
 //
 // What bounds it (16 x 10 s, round 3, ablations scripts/experiments/mkexp.py g0n_*): 158 us = prologue 49 + arithmetic of
@@ -46,7 +46,7 @@ constexpr int G0_CS = 68;                               // floats between condit
 
 template <int KIND>
 __global__ __launch_bounds__(256) void wn_gate0_kernel(Gate0Args p) {
-    __shared__ __attribute__((aligned(16))) float xs[G0_XROWS * 8];        // x' rows m0 - d .. (staged row i = m0 - d + i)
+    __shared__ __attribute__((aligned(16))) float xs[G0_XROWS * 8];        // x' rows m0 - pad .. (staged row i = m0 - pad + i)
     __shared__ __attribute__((aligned(16))) float cs[G0_COND_ROWS * G0_CS];   // conditioning rows t2base ..
     __shared__ float2 tabw[G0_ROWS];                                        // (w0, w1) of block row lr
     __shared__ int tabo[G0_ROWS];                                           // float offset of its conditioning row in cs
@@ -60,6 +60,7 @@ __global__ __launch_bounds__(256) void wn_gate0_kernel(Gate0Args p) {
     if (m0 >= rows) return;
     const int C = p.channels;
     const int d = p.dil;
+    const int pad = p.causal ? 2 * d : d;                // rows staged in front of the block (CAUSAL: the same taps d rows earlier)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = tid >> 6;
     const int r16 = lane & 15, kq = lane >> 4;
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void wn_gate0_kernel(Gate0Args p) {
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
         const int i = tid + 256 * it;
-        const int srow = m0 - d + i;
+        const int srow = m0 - pad + i;
         xok[it] = i < G0_ROWS + 2 * d && srow >= 0 && srow < rows;
         const long long sr = xok[it] ? srow : 0;
 #pragma unroll
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(256) void wn_gate0_kernel(Gate0Args p) {
             const int l0 = 64 * wave + 16 * i;           // first row of the tile, relative to m0
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                const int si = l0 + r16 + t * d;         // staged row of tap t: m0 + l0 + r16 + (t - 1) d
+                const int si = l0 + r16 + t * d;         // staged row of tap t: m0 + l0 + r16 + t d - pad
                 xv[t] = *reinterpret_cast<const float2 *>(xs + 8 * si + 4 * ((kq >> 1) ^ ((si >> 3) & 1)) + 2 * (kq & 1));
             }
 #pragma unroll
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(256) void wn_gate0_kernel(Gate0Args p) {
             // x' (8 channels, padded to 16) behind the C gate channels of the rows of this tile: lane -> row lane / 4, 4 floats
             if (p.write_inputs && nt == 0) {
                 const int lx = l0 + (lane >> 2), q = lane & 3;
-                const int xrow = m0 + lx, si = lx + d;
+                const int xrow = m0 + lx, si = lx + pad;
                 if (xrow < rows) {
                     float4 ox = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (q < 2) ox = *reinterpret_cast<const float4 *>(xs + 8 * si + 4 * (q ^ ((si >> 3) & 1)));

@@ -28,9 +28,10 @@
 // Pair P of a wave tile: q = P / d, r = P % d, t = m0 + 2 d q + r (d a power of two <= 16).
 // Per 8-channel slice a wave stages, through LDS-DMA, its rows [m0 - d, m0 + 32 + d) x 8 channels in read order: row
 // m0 - d + d m + b (b < d) lives in 32-byte cell p = (m & 1) * 32 + (m >> 1) * d + b, its 16-byte chunk c at
-// 2 p + (c ^ ((p >> 3) & 1)); lane (r = lane & 15, kq = lane >> 4) reads the 8 bytes of channels 2 kq, 2 kq + 1 of cell
-// (i & 1) * 32 + P + (i >> 1) * d for its four rows i -- consecutive lanes, consecutive cells, conflict free with the
-// chunk swizzle.  The block stages the weights of the slice: 4 products x 8 channels x 64 columns in MFMA operand order
+// 2 p + (c ^ ((p >> 3) & 1)) (CAUSAL padding, pad_l = 2 d: the same window d rows earlier, [m0 - 2 d, m0 + 32); the
+// outputs and their conditioning rows stay where they are); lane (r = lane & 15, kq = lane >> 4) reads the 8 bytes of
+// channels 2 kq, 2 kq + 1 of cell (i & 1) * 32 + P + (i >> 1) * d for its four rows i -- consecutive lanes, consecutive
+// cells, conflict free with the chunk swizzle.  The block stages the weights of the slice: 4 products x 8 channels x 64 columns in MFMA operand order
 // [product j][channel parity e][lane][tanh step 0, tanh step 1, sigmoid step 0, sigmoid step 1] (one ds_read_b128 = the
 // weight operands of four MFMAs).  LDS: two stages x (4 x 2 KB + 8 KB) + the four conditioning tiles (8 rows x 64 floats
 // each): 40 KB -> 4 blocks per CU = 4 waves per SIMD, which is what hides the LDS-DMA latency and the
@@ -116,8 +117,11 @@ __global__ __launch_bounds__(256, 4) void wn_gate_winograd2w_kernel(ConvArgs p, 
     const int n0 = nt * 32;
     const int d = 1 << log2d;
     const int r16 = lane & 15, kq = lane >> 4;
-    // rows are addressed relative to the tile's first staged row: 32-bit byte offsets stay small for any item length
-    const int xrow0 = max(m0 - d, 0);
+    // rows are addressed relative to the tile's first staged row: 32-bit byte offsets stay small for any item length.
+    // The staged window starts pad_l rows in front of the tile: d (SAME) or 2 d (CAUSAL -- the same arithmetic on the
+    // input shifted by d rows; the launcher admits nothing else)
+    const int pad_l = p.pad_l;
+    const int xrow0 = max(m0 - pad_l, 0);
     const float *xb = p.x + (long long)b * p.x_bstride + (long long)xrow0 * p.ldx;
     const int nk8 = (p.cin + W2_BK - 1) / W2_BK;         // 8-channel slices of the weight image = stage fills
 
@@ -131,14 +135,14 @@ __global__ __launch_bounds__(256, 4) void wn_gate_winograd2w_kernel(ConvArgs p, 
         const int cell = pos >> 1;
         const int phase = cell / W2_PHASE, sidx = cell - phase * W2_PHASE;
         const int m = 2 * (sidx >> log2d) + phase;
-        const int src = m0 - d + (m << log2d) + (sidx & (d - 1));
+        const int src = m0 - pad_l + (m << log2d) + (sidx & (d - 1));
         const int hi = (pos & 1) ^ ((cell >> 3) & 1);
         if (active && sidx < W2_TROWS / 2 + d && src >= 0 && src < rows) a_bits |= 1u << i;
         a_bits |= (unsigned)hi << (4 + i);
         a_voff[i] = 4u * (unsigned)((min(max(src, 0), rows - 1) - xrow0) * p.ldx + 4 * hi);
     }
     // interior tiles (every staged row exists, whole slices): uniform base + per-lane byte offset, no selects
-    const bool fast_rows = active && p.fast_dma && m0 >= d && m0 + W2_TROWS + d <= rows;
+    const bool fast_rows = active && p.fast_dma && m0 >= pad_l && m0 + W2_TROWS + 2 * d - pad_l <= rows;
     const int whole_fills = p.cin / W2_BK;
     const float *wtile = p.w + (long long)nt * nk8 * W2_B_FLOATS;
     const unsigned b_voff = 16u * (unsigned)lane;
@@ -372,7 +376,8 @@ bool launch_wn_gate_winograd2w(const ConvArgs &a, hipStream_t stream) {
     int log2d = 0;
     while ((1 << log2d) < a.dil) ++log2d;
     const int nk8 = (a.cin + W2_BK - 1) / W2_BK;
-    const bool ok = a.ks == 3 && (1 << log2d) == a.dil && a.dil <= W2_HALO && nk8 >= 3 && a.pad_l == a.dil && a.pad_mode == 0 &&
+    const bool ok = a.ks == 3 && (1 << log2d) == a.dil && a.dil <= W2_HALO && nk8 >= 3 && a.pad_mode == 0 &&
+                    (a.pad_l == a.dil || a.pad_l == 2 * a.dil) &&
                     a.cin % 4 == 0 && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 && a.channels % 4 == 0 &&
                     a.cout == 2 * a.channels && (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && a.zeros &&
                     a.cond && (uintptr_t)a.cond % 16 == 0 && a.cond_bstride % 4 == 0 && a.cond_up >= 1 &&

@@ -153,7 +153,9 @@ __global__ __launch_bounds__(256, CR <= 28 ? 3 : 2) void wn_gate_winograd4w_kern
     const int r16 = lane & 15, kq = lane >> 4;
     // rows are addressed relative to the block's first staged row: 32-bit byte offsets never leave the block's window,
     // however long the item is
-    const int xrow0 = max(m0 - WW_HALO, 0);
+    // CAUSAL padding (pad_l = 2 d, d <= 16): the staged rows start sh = d rows earlier, the outputs stay where they are
+    const int sh = VS ? 0 : p.pad_l - d;
+    const int xrow0 = max(m0 - WW_HALO - sh, 0);
     const int ldxv = VS ? p.ldx * vs : p.ldx;               // floats between (virtual) rows
     const float *xb = p.x + (long long)b * p.x_bstride + (long long)strip * p.ldx + (long long)xrow0 * ldxv;
     const int nk8 = (p.cin + WW_BK - 1) / WW_BK;            // 8-channel slices of the weight image = stage fills
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(256, CR <= 28 ? 3 : 2) void wn_gate_winograd4w_kern
             a_voff[i] = 4u * (unsigned)(min(max(src, 0), max(rs - 1, 0)) * ldxv + sub * p.ldx + 4 * hi);
         } else {
             const int row = (m << log2d) + (sidx & (d - 1)) + WW_HALO - d;       // staged row index, m0 - 16 + row = source
-            const int src = m0 - WW_HALO + row;
+            const int src = m0 - WW_HALO - sh + row;
             if (row < SH::AROWS && src >= 0 && src < rows) a_bits |= 1u << i;
             a_bits |= (unsigned)hi << (4 + i);
             a_voff[i] = 4u * (unsigned)((min(max(src, 0), rows - 1) - xrow0) * ldxv + 4 * hi);
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(256, CR <= 28 ? 3 : 2) void wn_gate_winograd4w_kern
     }
     // interior blocks (every staged row exists, whole stage fills): uniform base + per-lane byte offset, no selects
     // (C = 340: every stage fill but the last one is whole, so only that one takes the masked path)
-    const bool fast_rows = p.fast_dma && m0 >= WW_HALO && m0 + ROWS + WW_HALO <= rows;
+    const bool fast_rows = p.fast_dma && m0 - sh >= WW_HALO && m0 + ROWS + WW_HALO - sh <= rows;
     const int whole_fills = p.cin / WW_BK;
     const float *wtile = p.w + (long long)nt * nk8 * WW_B_FLOATS;
     const unsigned b_voff = 16u * (unsigned)lane;
@@ -543,7 +545,9 @@ __global__ __launch_bounds__(256, 3) void wn_gate_winograd4p_kernel(ConvArgs p, 
     const int r16 = lane & 15, kq = lane >> 4;
     // rows are addressed relative to the block's first staged row: 32-bit byte offsets never leave the block's window,
     // however long the item is
-    const int xrow0 = max(m0 - WW_HALO, 0);
+    // CAUSAL padding (pad_l = 2 d, d <= 16): the staged rows start sh = d rows earlier, the outputs stay where they are
+    const int sh = VS ? 0 : p.pad_l - d;
+    const int xrow0 = max(m0 - WW_HALO - sh, 0);
     const int ldxv = VS ? p.ldx * vs : p.ldx;
     const float *xb = p.x + (long long)b * p.x_bstride + (long long)strip * p.ldx + (long long)xrow0 * ldxv;
     const int nk8 = (p.cin + WW_BK - 1) / WW_BK;
@@ -560,13 +564,13 @@ __global__ __launch_bounds__(256, 3) void wn_gate_winograd4p_kernel(ConvArgs p, 
         const int phase = cell / PHASE, sidx = cell - phase * PHASE;
         const int m = 4 * (sidx >> log2d) + phase;
         const int row = (m << log2d) + (sidx & (d - 1)) + WW_HALO - d;
-        const int src = m0 - WW_HALO + row;
+        const int src = m0 - WW_HALO - sh + row;
         const int hi = (pos & 1) ^ ((cell >> 3) & 1);
         if (row < SH::AROWS && src >= 0 && src < rows) a_bits |= 1u << i;
         a_bits |= (unsigned)hi << (4 + i);
         a_voff[i] = 4u * (unsigned)((min(max(src, 0), rows - 1) - xrow0) * ldxv + 4 * hi);
     }
-    const bool fast_rows = p.fast_dma && m0 >= WW_HALO && m0 + ROWS + WW_HALO <= rows;
+    const bool fast_rows = p.fast_dma && m0 - sh >= WW_HALO && m0 + ROWS + WW_HALO - sh <= rows;
     const int whole_fills = p.cin / WW_BK;
     const float *wtile = p.w + (long long)nt * nk8 * WW_B_FLOATS;
     const unsigned b_voff = 16u * (unsigned)lane;
@@ -854,7 +858,8 @@ __global__ __launch_bounds__(256, 4) void wn_gate_winograd4h_kernel(ConvArgs p, 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rw = wave >> 1, ph = wave & 1;                // row half and product half of this wave
     const int r16 = lane & 15, kq = lane >> 4;
-    const int xrow0 = max(m0 - WW_HALO, 0);
+    const int sh = p.pad_l - d;                             // CAUSAL padding: d (see wn_gate_winograd4w_kernel)
+    const int xrow0 = max(m0 - WW_HALO - sh, 0);
     const float *xb = p.x + (long long)b * p.x_bstride + (long long)xrow0 * p.ldx;
     const int nk8 = (p.cin + WW_BK - 1) / WW_BK;
 
@@ -870,13 +875,13 @@ __global__ __launch_bounds__(256, 4) void wn_gate_winograd4h_kernel(ConvArgs p, 
         const int phase = cell / PHASE, sidx = cell - phase * PHASE;
         const int m = 4 * (sidx >> log2d) + phase;
         const int row = (m << log2d) + (sidx & (d - 1)) + WW_HALO - d;
-        const int src = m0 - WW_HALO + row;
+        const int src = m0 - WW_HALO - sh + row;
         const int hi = (pos & 1) ^ ((cell >> 3) & 1);
         if (row < ROWS + 2 * WW_HALO && src >= 0 && src < rows) a_bits |= 1u << i;
         a_bits |= (unsigned)hi << (4 + i);
         a_voff[i] = 4u * (unsigned)((min(max(src, 0), rows - 1) - xrow0) * p.ldx + 4 * hi);
     }
-    const bool fast_rows = p.fast_dma && m0 >= WW_HALO && m0 + ROWS + WW_HALO <= rows;
+    const bool fast_rows = p.fast_dma && m0 - sh >= WW_HALO && m0 + ROWS + WW_HALO - sh <= rows;
     const int whole_fills = p.cin / WW_BK;
     const float *wtile = p.w + (long long)nt * nk8 * WW_B_FLOATS + eh * 256;      // product j of this parity: + 512 j
     const unsigned b_voff = 16u * (unsigned)lane;
@@ -1100,7 +1105,8 @@ bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream)
     const int rows_blk = split ? 128 : 256;
     const int nk8 = (a.cin + WW_BK - 1) / WW_BK;
     const int cond_rows = vs > 1 ? 1 : a.cond_up >= 1 ? (rows_blk + a.cond_up - 2) / a.cond_up + 2 : 1 << 30;   // conditioning rows a block's tile holds
-    const bool ok = a.ks == 3 && (1 << log2d) == dil_v && dil_v * vs == a.dil && nk8 >= 4 && a.pad_l == a.dil && a.pad_mode == 0 &&
+    const bool ok = a.ks == 3 && (1 << log2d) == dil_v && dil_v * vs == a.dil && nk8 >= 4 && a.pad_mode == 0 &&
+                    (a.pad_l == a.dil || (vs == 1 && a.pad_l == 2 * a.dil)) &&
                     a.cin % 4 == 0 && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 && a.channels % 4 == 0 &&
                     a.cout == 2 * a.channels && (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && a.zeros &&
                     a.cond && (uintptr_t)a.cond % 16 == 0 && a.cond_bstride % 4 == 0 && a.cond_up >= 1 &&

@@ -16,9 +16,9 @@ log_to_db = 20 * np.log10(np.exp(1))   # reference vocoder/model/preprocess.py:7
 
 class MELInverter(object):
     def __init__(self, model_id_or_path: Union[str, None] = None, verbose: bool = False, calibrate: bool = False,
-                 batch_invariant: Union[bool, None] = None):
-        """As the reference's constructor (mel_inverter.py:22-41); ``calibrate`` and ``batch_invariant`` (this build) are
-        handed to :meth:`load_model`."""
+                 batch_invariant: Union[bool, None] = None, conv_form: Union[str, None] = None):
+        """As the reference's constructor (mel_inverter.py:22-41); ``calibrate``, ``batch_invariant`` and ``conv_form`` (this
+        build) are handed to :meth:`load_model`."""
         self.model = None
         self._calibrate_pending = False
         self._verbose = verbose
@@ -40,7 +40,7 @@ class MELInverter(object):
 
         if model_id_or_path:
             self.load_model(model_id_or_path=model_id_or_path, verbose=verbose, calibrate=calibrate,
-                            batch_invariant=batch_invariant)
+                            batch_invariant=batch_invariant, conv_form=conv_form)
 
     @classmethod
     def host_only(cls, model_id_or_path):
@@ -265,12 +265,16 @@ class MELInverter(object):
         return data_dict
 
     # ------------------------------------------------------------------------------------------
-    def load_model(self, model_id_or_path, verbose=False, calibrate=False, batch_invariant=None):
+    def load_model(self, model_id_or_path, verbose=False, calibrate=False, batch_invariant=None, conv_form=None):
         """reference mel_inverter.py:184-239: resolve the model directory, read ``config.yaml``, build the
         generator, restore the weights and copy the pre-processing parameters onto the instance.
 
         ``batch_invariant`` (this build; ``mbx_config.batch_invariant``, None = the engine's default): True pins the engine's
         kernels so that an utterance's bits do not depend on the batch it runs in (:meth:`synth_from_mels`).
+
+        ``conv_form`` (this build; ``mbx_config.wn_conv_form``, None = "auto"): "auto" | "direct" | "f23" | "f43" pins the form
+        of the WaveNet's dilated convolution.  A force_causal / CAUSAL-padded model runs its Winograd kernels only when a form
+        is pinned ("f23" / "f43"); under "auto" it keeps the direct form.
 
         ``calibrate=True`` (this build; ORDER DEPENDENT: the decision is taken on at most 400 frames of the first utterance and
         binds every later one, a failing calibration keeps the creation-time form with a warning): the first mel handed to
@@ -305,7 +309,7 @@ class MELInverter(object):
             raw = load_reference_checkpoint(weights_tf, hparams)
         else:
             raise FileNotFoundError(f"error::no weights found under {model_dir} (expected weights.npz or weights.tf.index)")
-        self.model = MBExWNEngine(hparams, raw, batch_invariant=batch_invariant)
+        self.model = MBExWNEngine(hparams, raw, batch_invariant=batch_invariant, conv_form=conv_form)
         self._calibrate_pending = bool(calibrate)
         self._verbose = bool(verbose)
         if verbose:

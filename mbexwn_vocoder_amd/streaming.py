@@ -17,7 +17,8 @@ Receptive field in mel frames (canonical model): F0-net 3 convs k=3 (+-3) and th
 valid F0, so pulses are valid from window frame 4; WaveNet (dilations 1..16, k=3: +-31 steps, + 9 steps of conditioning
 interpolation towards a row that a region's end clamps = 2 frames) -> 6;
 PQMF (+-4 steps) -> 7; STFT frame + overlap-add (-3 / +4 frames) -> LEFT = 10, RIGHT = 11 (look-ahead 137.5 ms).
-``StreamingSynthesizer`` derives the margins from the model configuration.
+``StreamingSynthesizer`` derives the margins from the model configuration.  A force_causal model (every convolution
+padded in front only) needs no look-ahead in its sub-nets and WaveNet: 87.5 ms of the same model (stream_margins).
 """
 import numpy as np
 
@@ -43,47 +44,77 @@ def cond_chain_reach(dims):
     """(left, right) reach in mel frames of the conditioning chain -- the conditioning layer and the pre-conditioning
     convolutions in front of it, all with kernel size cond_kernel_size and zero SAME padding, which the library pads
     (k - 1) // 2 frames in front and k // 2 behind (csrc/mbx_api.hip, cond_chain): an even kernel size reaches one frame
-    further to the right than to the left, per convolution."""
+    further to the right than to the left, per convolution.  CAUSAL WaveNet padding: k - 1 frames in front, none behind."""
     n_cond = 0 if dims.wn_disable_conditioning else 1 + len(dims.wn_pre_cond_channels)
+    if dims.wn_padding == "CAUSAL":
+        return n_cond * (dims.cond_kernel_size - 1), 0
     return n_cond * ((dims.cond_kernel_size - 1) // 2), n_cond * (dims.cond_kernel_size // 2)
 
 
+def subnet_reach(specs, causal=False):
+    """(left, right) reach in mel frames of an F0- / VTF-net: per convolution its pads (subnet.build_subnet), counted in
+    frames whatever the rate the layer runs at -- the larger half in front, or everything in front under force_causal."""
+    left = right = 0
+    for spec in specs:
+        if spec[0] == "L":
+            continue
+        ks = int(spec[0])
+        left += ks - 1 if causal else (ks - 1) // 2 + ((ks - 1) % 2)
+        right += 0 if causal else (ks - 1) // 2
+    return left, right
+
+
+def wavenet_reach(dims):
+    """(left, right) reach in mel frames of the WaveNet: the rows at the start / end of a region that are not those of a
+    whole-utterance run.  SAME padding: the receptive field (k - 1) / 2 * d per layer, plus the cond_lin_upsampling - 1 last
+    rows of every layer, which interpolate the conditioning towards a clamped row -- an error that spreads backwards
+    through the layers behind -- on both sides.  CAUSAL padding: (k - 1) d per layer to the left; to the right only the
+    clamped conditioning tail, which no layer carries backwards."""
+    spf = dims.steps_per_frame
+    tail = dims.cond_lin_upsampling - 1
+    if dims.wn_padding == "CAUSAL":
+        left = sum(dims.wn_dilation(ll) * (dims.wn_kernel_size - 1) for ll in range(dims.wn_layers))
+        return -(-left // spf), -(-tail // spf)
+    steps = sum(dims.wn_dilation(ll) * (dims.wn_kernel_size - 1) // 2 for ll in range(dims.wn_layers)) + tail
+    return -(-steps // spf), -(-steps // spf)
+
+
 def stream_margins(dims, config):
-    """(left, right, pulse_lead, act_left, act_right, wn_reach) in mel frames, from the layer geometry of the model."""
+    """(left, right, pulse_lead, act_left, act_right, wn_reach) in mel frames, from the layer geometry of the model;
+    wn_reach = the WaveNet's reach behind a region's end (wavenet_reach; SAME padding: the same in front).
+
+    Every reach follows the model's padding.  force_causal sub-nets reach ks - 1 frames to the left and none to the right,
+    a CAUSAL WaveNet 2 sum(d) steps to the left and its conditioning tail to the right.  The SMALL model of
+    tests/test_gpu_streaming.py (C = 32, 5 layers, d = 1 .. 16, PQMF 1 frame, STFT 3 / 4 frames):
+
+        model                 lead       WaveNet (l, r)   left   right   look-ahead
+        SAME                  3 + 1 = 4  (2, 2)           10     11      137.5 ms
+        force_causal          6 + 1 = 7  (4, 1)           15      7       87.5 ms
+        WaveNet CAUSAL only   3 + 1 = 4  (4, 1)           12     10      125.0 ms
+
+    (force_causal: left = lead 7 + WaveNet 4 + PQMF 1 + STFT 3 = 15; right = max(F0-net 0 + interpolation 1, conditioning
+    chain 0 + 1) + 1 + 1 + 4 = 7.  WaveNet CAUSAL only: the SAME sub-nets keep right = max(3 + 1, 1 + 1) + 1 + 1 + 4 = 10.
+    What is left of the look-ahead is the non-causal back end: PQMF, the STFT frame / overlap-add and the F0 smoother.)"""
     mb = config["mbexwn_config"]
     nr = norm_reach(dims, config)      # the normalised mel of a window is reproducible nr frames inside its edges only
-
-    def subnet_reach(specs):
-        left = right = 0
-        for spec in specs:
-            if spec[0] == "L":
-                continue
-            ks = int(spec[0])
-            left += (ks - 1) // 2 + ((ks - 1) % 2)
-            right += (ks - 1) // 2
-        return left, right
-
-    f0_l, f0_r = subnet_reach(mb["pp_subnet"])
+    causal = dims.force_causal
+    f0_l, f0_r = subnet_reach(mb["pp_subnet"], causal)
     f0_r += 1                                             # interpolation towards the next frame
-    spf = dims.steps_per_frame
-    wn_steps = sum(dims.wn_dilation(ll) * (dims.wn_kernel_size - 1) // 2 for ll in range(dims.wn_layers))
     # the conditioning is interpolated towards the next conditioning row, which at the end of a region is the clamped
-    # last one: the last cond_lin_upsampling - 1 rows of every layer's gate are off, and that spreads backwards by the
-    # reach of the layers behind
-    wn_steps += dims.cond_lin_upsampling - 1
-    wn_frames = -(-wn_steps // spf)
+    # last one: the last cond_lin_upsampling - 1 rows of every layer's gate are off (wavenet_reach)
+    wn_left, wn_right = wavenet_reach(dims)
     pqmf_frames = -(-(int(mb["multi_band_config"]["taps"]) // 2) // dims.hop_size)
     # conditioning chain: the conditioning layer and the pre-conditioning convolutions in front of it (same kernel size,
     # zero SAME padding: (k - 1) // 2 frames to the left, k // 2 to the right, per convolution); + 1: the interpolation
     # towards the next conditioning row
     cond_l, cond_r = cond_chain_reach(dims)
     cond_r += 1
-    vt_l, vt_r = (0, 0) if dims.no_envelope else subnet_reach(mb["ps_subnet"])     # cepstrum of a frame <- mel frames around it
+    vt_l, vt_r = (0, 0) if dims.no_envelope else subnet_reach(mb["ps_subnet"], causal)     # cepstrum of a frame <- mel frames around it
     stft_l, stft_r = 3, 4                                  # frame t reaches excitation frames t-3 .. t+4
     # first window frame whose mel-rate inputs of the WaveNet -- F0 / phase and the conditioning rows -- are reproducible
     pulse_lead = nr + max(f0_l + 1, cond_l)
-    left = pulse_lead + wn_frames + pqmf_frames + stft_l
-    right = nr + max(f0_r, cond_r) + wn_frames + pqmf_frames + stft_r
+    left = pulse_lead + wn_left + pqmf_frames + stft_l
+    right = nr + max(f0_r, cond_r) + wn_right + pqmf_frames + stft_r
     # the envelope filter of the frames around the emitted ones needs their cepstra
     left = max(left, nr + vt_l + stft_l)
     right = max(right, nr + vt_r + stft_r)
@@ -91,29 +122,18 @@ def stream_margins(dims, config):
     left = max(left, pulse_lead + smooth + 1)
     right = max(right, nr + f0_r + smooth + 2)
     # margins of the stages from the WaveNet on (the active region of a window, mbx_forward_options.active_begin)
-    act_left = wn_frames + pqmf_frames + stft_l
-    act_right = wn_frames + pqmf_frames + stft_r
-    return left, right, pulse_lead, act_left, act_right, wn_frames
+    act_left = wn_left + pqmf_frames + stft_l
+    act_right = wn_right + pqmf_frames + stft_r
+    return left, right, pulse_lead, act_left, act_right, wn_right
 
 
 def frontend_reach(dims, config):
     """(left, right) reach in mel frames of the mel-rate front end (F0-net, VTF-net, conditioning convolution): the output
     of frame t depends on the mel frames [t - left, t + right]."""
     mb = config["mbexwn_config"]
-
-    def reach(specs):
-        left = right = 0
-        for spec in specs:
-            if spec[0] == "L" or (isinstance(spec[0], str) and spec[0].startswith("L")):
-                continue
-            ks = int(spec[0])
-            left += (ks - 1) // 2 + ((ks - 1) % 2)
-            right += (ks - 1) // 2
-        return left, right
-
-    f0_l, f0_r = reach(mb["pp_subnet"])
-    vt_l, vt_r = reach(mb["ps_subnet"])
-    # the conditioning layer and the pre-conditioning convolutions in front of it (same kernel size, zero SAME padding)
+    f0_l, f0_r = subnet_reach(mb["pp_subnet"], dims.force_causal)
+    vt_l, vt_r = subnet_reach(mb["ps_subnet"], dims.force_causal)
+    # the conditioning layer and the pre-conditioning convolutions in front of it (same kernel size and padding)
     ck_l, ck_r = cond_chain_reach(dims)
     # + 1: the interpolators (F0 contour, conditioning rows) reach the next frame
     return max(f0_l, vt_l, ck_l), max(f0_r, vt_r, ck_r) + 1
@@ -167,10 +187,12 @@ class StreamingSynthesizer:
         self.chunk = self.schedule[0] if self.uniform else min(self.schedule)
         (self.left, self.right, self.lead, self.act_left, self.act_right,
          self.wn_reach) = stream_margins(engine.dims, engine.config)
+        # the WaveNet's reach in front of a region (wn_left) and behind it (wn_reach); equal under SAME padding
+        self.wn_left = wavenet_reach(engine.dims)[0]
         # sub-band rows carried from tick to tick: the stages behind the WaveNet reach sr_left frames in front of the
         # emitted ones and sr_right behind them; these frames were computed exactly by the previous tick, so the WaveNet
         # of a tick only runs on the frames behind them (plus its own reach)
-        self.sr_left = self.act_left - self.wn_reach
+        self.sr_left = self.act_left - self.wn_left
         self.sr_right = self.act_right - self.wn_reach
         self.carry = True
         self._store = None            # (slots, (sr_left + sr_right) * steps_per_frame, subbands) on the device
@@ -201,6 +223,11 @@ class StreamingSynthesizer:
         import math
         d_max = max(engine.dims.wn_dilation(ll) for ll in range(engine.dims.wn_layers))
         self.align = (2 * d_max) // math.gcd(2 * d_max, engine.dims.steps_per_frame)
+        if engine.dims.wn_padding == "CAUSAL":
+            # a causal WaveNet reaches further left than right: the carried sub-bands start far enough in front of the
+            # emitted frames that the aligned start of a tick's WaveNet region never lies in front of them (the region
+            # stays inside the active one), whatever the phase of the tick schedule
+            self.sr_left = max(self.sr_left, self.align - 1 + self.wn_left - self.sr_right)
         self.streams = {}
         # ticks of a schedule whose period is a whole number of alignment steps have a geometry that repeats per phase
         self.periodic = sum(self.schedule) % self.align == 0
@@ -358,7 +385,7 @@ class StreamingSynthesizer:
             ends.append(a1)
             act[bb] = a1 - ws - a0
         # carried sub-bands: usable when every item of the tick has a valid store and the same geometry
-        sl, sr, wr = self.sr_left, self.sr_right, self.wn_reach
+        sl, sr, wr, wl = self.sr_left, self.sr_right, self.wn_reach, self.wn_left
         wn = None
         desc = np.zeros((B, 5), dtype=np.int32)
         use_carry = self.carry
@@ -368,7 +395,7 @@ class StreamingSynthesizer:
                 break
             ok = st.carry_pos == st.emitted and st.emitted - sl >= ws
             sab = st.emitted - sl - ws
-            wab = ((st.emitted + min(sr, st.carry_frames - sl) - wr) // self.align) * self.align - ws
+            wab = ((st.emitted + min(sr, st.carry_frames - sl) - wl) // self.align) * self.align - ws
             ok = ok and wab >= sab and (ws == 0 or wab >= self.lead) and st.carry_frames > sl
             ok = ok and (sa is None or (sab == sa and wab == wa))
             sa, wa = sab, wab
@@ -386,7 +413,7 @@ class StreamingSynthesizer:
         for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
             e1 = st.emitted + nn
             lo, hi = e1 - sl, min(e1 + sr, ends[bb] if ends[bb] == we and st.closed else ends[bb] - wr)
-            region_lo = ws + a0 if use_carry else ws + a0 + (wr if ws + a0 > 0 else 0)
+            region_lo = ws + a0 if use_carry else ws + a0 + (wl if ws + a0 > 0 else 0)
             good = self.carry and lo >= region_lo and hi > lo + sl and lo >= ws
             desc[bb, 0] = st.slot
             if good:
@@ -415,7 +442,8 @@ class StreamingSynthesizer:
             for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
                 final = st.closed and ends[bb] >= we
                 # state of this tick's region: exact if the region starts the utterance or reaches 2 * reach + 1 frames back
-                long_enough = ws + region0 == 0 or ends[bb] - ws - region0 >= 3 * wr + 1
+                # in front of its last exact row (SAME: 3 * reach + 1 frames in all)
+                long_enough = ws + region0 == 0 or ends[bb] - ws - region0 >= 2 * wl + wr + 1
                 if not final and (steady or long_enough):
                     ldesc[bb, 2] = (ends[bb] - ws) * spf
                     next_layer_end[bb] = ends[bb]

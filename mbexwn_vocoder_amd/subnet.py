@@ -21,13 +21,27 @@ def _same_pad(ks):
     return total // 2, total - total // 2
 
 
+def _keras_pad(ks, causal):
+    # Keras "CAUSAL": all ks-1 zeros in front
+    return (ks - 1, 0) if causal else _same_pad(ks)
+
+
+def _explicit_pad(ks, causal):
+    # TFPad1d sizes of the reference: the larger half in front, or everything in front under force_causal
+    if causal:
+        return (ks - 1) // 2 + ((ks - 1) % 2) + (ks - 1) // 2, 0
+    return (ks - 1) // 2 + ((ks - 1) % 2), (ks - 1) // 2
+
+
 def build_subnet(specs, base_name, in_channels, final_n_channels, final_nks, final_activation,
                  target_ups=None, pad_to_valid=False, remove_inactive_pad_layers=False,
                  use_prelu=True, alpha=0.2, force_causal=False):
-    """Return (ops, total_ups, out_channels). See module docstring."""
-    if force_causal:
-        # reference custom_pulsed_generator.py:213-217: "would require a dedicated implementation"
-        raise NotImplementedError("force_causal is not supported")
+    """Return (ops, total_ups, out_channels). See module docstring.
+
+    force_causal (reference :53,76-79,93-95,111-113,128-130): every explicit pad becomes (ks-1, 0) of the same type, and
+    the convolutions that pad themselves (sub-pixel layers, the final layer, without pad_to_valid) use Keras "CAUSAL":
+    ks-1 zeros in front, none behind.
+    """
     ops = []
     total_ups = 1
     cin = in_channels
@@ -54,8 +68,7 @@ def build_subnet(specs, base_name, in_channels, final_n_channels, final_nks, fin
                 up = int(spec[2][1:])
             else:
                 up = int(spec[2])
-        pad_l = (ks - 1) // 2 + ((ks - 1) % 2)
-        pad_r = (ks - 1) // 2
+        pad_l, pad_r = _explicit_pad(ks, force_causal)
         explicit_mode = PAD_EDGE if pad_to_valid else PAD_SYMMETRIC
         name = f"{base_name}_Layer_{ii}"
         if linear_up:
@@ -69,7 +82,7 @@ def build_subnet(specs, base_name, in_channels, final_n_channels, final_nks, fin
             if pad_to_valid:
                 pl, pr, mode = pad_l, pad_r, PAD_EDGE
             else:
-                pl, pr = _same_pad(ks)
+                pl, pr = _keras_pad(ks, force_causal)
                 mode = PAD_ZERO
             ops.append({"kind": "conv", "name": name, "ks": ks, "cin": cin, "cout": nf * up,
                         "pad_l": pl, "pad_r": pr, "pad_mode": mode, "up": up})
@@ -86,11 +99,10 @@ def build_subnet(specs, base_name, in_channels, final_n_channels, final_nks, fin
         # reference :126-138
         fks = int(final_nks)
         if pad_to_valid:
-            pl = (fks - 1) // 2 + ((fks - 1) % 2)
-            pr = (fks - 1) // 2
+            pl, pr = _explicit_pad(fks, force_causal)
             mode = PAD_EDGE
         else:
-            pl, pr = _same_pad(fks)
+            pl, pr = _keras_pad(fks, force_causal)
             mode = PAD_ZERO
         ops.append({"kind": "conv", "name": f"{base_name}_Layer_final", "ks": fks, "cin": cin,
                     "cout": int(final_n_channels), "pad_l": pl, "pad_r": pr, "pad_mode": mode, "up": 1})

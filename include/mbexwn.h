@@ -549,7 +549,11 @@ mbx_status mbx_stft_filter(mbx_handle *handle, const float *excitation, const fl
  *   audio      device (batch, max_samples) float32; n_samples device int32 (batch) or NULL
  *   window     device (win) analysis window; twiddle device (fft_size/2, 2) = exp(-2 pi i m / fft_size)
  *   basis      device (n_mels, fft_size/2+1) mel filters, bin_lo / bin_hi device int32 (n_mels): non-zero range of a row
- *   out        device (batch, max_frames, n_mels): log(max(|STFT| . basis^T, eps)); item b has n_samples[b]/hop + 1 frames */
+ *   out        device (batch, max_frames, n_mels): log(max(|STFT| . basis^T, eps)); item b has n_samples[b]/hop + 1 frames
+ * Every item is padded as numpy's "reflect" pads it, at the item's own length n = n_samples[b]: the padded signal has
+ * period 2 (n - 1), so an item shorter than half a window is reflected as often as the frame needs (max_samples >=
+ * win/2 + 1 bounds the launch, not the items).  n = 1 repeats its one sample; n = 0 gives one frame of log(eps).  A
+ * channel at or below eps is the float32 nearest to log(eps), whatever the device's logf makes of eps. */
 mbx_status mbx_mel_analysis(const float *audio, const int32_t *n_samples, int32_t batch, int32_t max_samples,
                             int32_t win, int32_t hop, int32_t fft_size, int32_t n_mels, const float *window,
                             const float *twiddle, const float *basis, const int32_t *bin_lo, const int32_t *bin_hi,

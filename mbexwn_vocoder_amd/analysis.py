@@ -94,6 +94,22 @@ def compute_log_mel(sound, preprocess_config, dtype=np.float32):
     return mell, preprocess_config["sample_rate"] / preprocess_config["hop_size"]
 
 
+def mel_analysis_tables(preprocess_config):
+    """The tables :func:`compute_log_mel_device` uploads, as numpy arrays: the float32 analysis window (win,), the twiddles
+    exp(-2 pi i m / fft_size) as (fft_size / 2, 2) float32, the float32 mel basis (mel_channels, fft_size / 2 + 1) and the
+    first / last non-zero bin of every basis row as int32 (an all-zero row: lo = 1, hi = 0)."""
+    cfg = preprocess_config
+    win_len = int(cfg.get("win_size", cfg["fft_size"]))
+    fft_size, n_mels = int(cfg["fft_size"]), int(cfg["mel_channels"])
+    basis = mel_basis_slaney(cfg["sample_rate"], fft_size, n_mels, cfg["fmin"], cfg["fmax"], dtype=np.float32)
+    nz = basis != 0
+    lo = np.where(nz.any(axis=1), nz.argmax(axis=1), 1).astype(np.int32)
+    hi = np.where(nz.any(axis=1), basis.shape[1] - 1 - nz[:, ::-1].argmax(axis=1), 0).astype(np.int32)
+    ang = -2.0 * np.pi * np.arange(fft_size // 2) / fft_size
+    return (hann_symmetric(win_len).astype(np.float32), np.stack((np.cos(ang), np.sin(ang)), axis=1).astype(np.float32),
+            basis, lo, hi)
+
+
 def compute_log_mel_device(sound, preprocess_config, n_samples=None):
     """:func:`compute_log_mel` on the GPU (csrc/mel_analysis.hip through ``mbx_mel_analysis``): sound is a float32 cuda
     tensor (batch, time), ``n_samples`` an optional int32 cuda tensor (batch,) of item lengths.  Returns a cuda tensor
@@ -109,14 +125,7 @@ def compute_log_mel_device(sound, preprocess_config, n_samples=None):
     win_len = int(cfg.get("win_size", cfg["fft_size"]))
     hop, fft_size, n_mels = int(cfg["hop_size"]), int(cfg["fft_size"]), int(cfg["mel_channels"])
     dev = sound.device
-    basis = mel_basis_slaney(cfg["sample_rate"], fft_size, n_mels, cfg["fmin"], cfg["fmax"], dtype=np.float32)
-    nz = basis != 0
-    lo = np.where(nz.any(axis=1), nz.argmax(axis=1), 1).astype(np.int32)
-    hi = np.where(nz.any(axis=1), basis.shape[1] - 1 - nz[:, ::-1].argmax(axis=1), 0).astype(np.int32)
-    ang = -2.0 * np.pi * np.arange(fft_size // 2) / fft_size
-    tables = [torch.as_tensor(np.ascontiguousarray(tt), device=dev) for tt in
-              (hann_symmetric(win_len).astype(np.float32), np.stack((np.cos(ang), np.sin(ang)), axis=1).astype(np.float32),
-               basis, lo, hi)]
+    tables = [torch.as_tensor(np.ascontiguousarray(tt), device=dev) for tt in mel_analysis_tables(cfg)]
     sound = sound.contiguous()
     B, N = int(sound.shape[0]), int(sound.shape[1])
     frames = N // hop + 1

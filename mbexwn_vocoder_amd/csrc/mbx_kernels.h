@@ -312,6 +312,7 @@ struct MelAnalysisArgs {
     const float *basis;       // (n_mels, fft_size/2 + 1) dense rows
     const int *bin_lo, *bin_hi;   // (n_mels) first / last non-zero bin of a row
     float eps;
+    float log_eps;            // float32 nearest to log(eps); launch_mel_analysis fills it in
     float *out;               // (batch, max_frames, n_mels), frames of item b: n_samples[b] / hop + 1
     int max_frames;
 };

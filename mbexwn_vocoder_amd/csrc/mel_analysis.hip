@@ -11,6 +11,8 @@
 // One 256-thread block per (item, frame): windowed frame -> real FFT (complex Stockham FFT of fft_size/2 points in LDS,
 // fft_lds.h) -> magnitudes in LDS -> one wavefront per mel channel sums its triangle (bins [lo, hi] of the dense basis
 // row) -> log.  Bandwidth-type: reads hop samples and writes mel_channels floats per frame.
+#include <cmath>
+
 #include "fft_lds.h"
 #include "mbx_kernels.h"
 
@@ -37,10 +39,17 @@ __global__ __launch_bounds__(FFT_THREADS) void mel_analysis_kernel(MelAnalysisAr
             const int j = 2 * m + q;
             float val = 0.f;
             if (j < p.win) {
+                // numpy "reflect" of any depth: the padded signal has period 2 (n - 1), so an item shorter than half a
+                // window folds as often as it needs (closed form, no data-dependent loop); n = 1 repeats its one sample
                 int s = t * p.hop + j - p.win / 2;
-                if (s < 0) s = -s;
-                if (s >= n) s = 2 * (n - 1) - s;
-                s = min(max(s, 0), n - 1);
+                const int period = 2 * (n - 1);
+                if (period > 0) {
+                    s %= period;
+                    if (s < 0) s += period;
+                    if (s >= n) s = period - s;
+                } else {
+                    s = 0;
+                }
                 if (n >= 1) val = p.window[j] * xb[s];      // an empty item is one frame of silence: log(eps) rows
             }
             v[q] = val;
@@ -61,7 +70,8 @@ __global__ __launch_bounds__(FFT_THREADS) void mel_analysis_kernel(MelAnalysisAr
         float acc = 0.f;
         for (int k = p.bin_lo[m] + lane; k <= p.bin_hi[m]; k += 64) acc = fmaf(mag[k], row[k], acc);
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-        if (lane == 0) ob[m] = logf(fmaxf(acc, p.eps));
+        // the floor is the float32 NEAREST to log(eps) (logf(eps) of the device library is its other neighbour)
+        if (lane == 0) ob[m] = acc > p.eps ? logf(acc) : p.log_eps;
     }
 }
 
@@ -73,7 +83,9 @@ bool launch_mel_analysis(const MelAnalysisArgs &a, hipStream_t stream) {
     if (a.batch <= 0) return true;
     const int nc = a.fft_size / 2;
     const size_t smem = sizeof(float2) * (size_t)(3 * nc) + sizeof(float) * (size_t)(nc + 1);
-    hipLaunchKernelGGL(mel_analysis_kernel, dim3(a.max_samples / a.hop + 1, a.batch), dim3(FFT_THREADS), smem, stream, a);
+    MelAnalysisArgs k = a;
+    k.log_eps = (float)log((double)a.eps);
+    hipLaunchKernelGGL(mel_analysis_kernel, dim3(a.max_samples / a.hop + 1, a.batch), dim3(FFT_THREADS), smem, stream, k);
     return true;
 }
 

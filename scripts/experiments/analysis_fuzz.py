@@ -24,8 +24,8 @@ for case in range(int(sys.argv[1])):
     dev = dev.cpu().numpy()
     worst = 0.0
     for ii, ll in enumerate(lens):
-        if ll < win // 2 + 1:
-            continue                                       # shorter than the reflect padding: numpy cannot pad it either
+        if ll == 0:
+            continue                                       # an empty item: one frame of log(eps), nothing to pad
         ref, _ = analysis.compute_log_mel(snd[ii:ii + 1, :ll], cfg)
         nfr = ll // hop + 1
         worst = max(worst, float(np.abs(dev[ii, :nfr] - ref[0, :nfr]).max()))

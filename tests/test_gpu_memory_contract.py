@@ -141,7 +141,7 @@ STANDALONE = {
     "mbx_wavetable": [(f"n{nn}", (nn,)) for nn in (1, 999, 1000, 1001, 12345)],
     "mbx_pqmf_synthesis": [(f"steps{nn}", (nn,)) for nn in (1, 63, 64, 65, 333)],
     "mbx_stft_filter": [(f"frames{nn}", (nn,)) for nn in (1, 3, 4, 5, 11)],
-    "mbx_mel_analysis": [("ragged-exact", ([3001, 900, 5000],))],
+    "mbx_mel_analysis": [("ragged-exact", ([3001, 900, 5000, 301],))],     # 301 < win / 2: reflected three times
     "mbx_norm_mel": [("ragged-one-frame", ([13, 1, 26, 7],))],
     "mbx_encode_flac16": [("boundaries", (FLAC_ORDER,))],
     "mbx_window_advance": [("step8", (35, 8)), ("step-is-window", (35, 35))],

@@ -816,7 +816,7 @@ __global__ __launch_bounds__(256, 3) void wn_gate_winograd4p_kernel(ConvArgs p, 
 // products, same sums in the same order as the other two shapes: the SAME bits.  LDS 29.5 KB, 4+ blocks per CU.
 // Measured (profiles/r05_gate_shapes.txt): 54.0 against 48.8 us at 3 s -- a block of half the matrix work lasts almost as long
 // (its 40 barrier-separated slices set its time, not its MFMAs) -- and 43.8 against 48.5 us at 2 s, where the product-split
-// blocks leave CUs empty: the launcher takes this shape there only (mbx_api.hip).
+// blocks leave CUs empty: the launcher takes this shape there only (mbx_forward.hip, gate_shape_policy).
 struct WhShape {
     static constexpr int ROWS = 128;
     static constexpr int PHASE = ROWS / 4 + WW_HALO;            // 48

@@ -305,7 +305,7 @@ def make_config(config, wavetables, conv_form=None, batch_invariant=None, keep_s
     conv_form "auto" | "direct" | "f23" | "f43" (mbx_config.wn_conv_form), batch_invariant, keep_skip, keep_start,
     calib_fraction, tune = {"gate_shape": 0|1|2|3, "resskip_wave_tiles": n, "resskip_split": 0..3}.  gate_shape 0 keeps the
     launch-size rule; 1 | 2 | 3 pin the F(4,3) block shape (256-row | product-split | product-split of half a column tile) of
-    launches of fewer than 4 * 768 256-row blocks (csrc/mbx_api.hip).  resskip_wave_tiles -1: never the wave-tiled res/skip
+    launches of fewer than 4 * 768 256-row blocks (csrc/mbx_forward.hip, gate_shape_policy).  resskip_wave_tiles -1: never the wave-tiled res/skip
     kernel."""
     dims = ModelDims(config)
     mb = config["mbexwn_config"]
@@ -1142,7 +1142,7 @@ class MBExWNEngine:
 
     def gate_form(self, batch, max_frames):
         """Which implementation of the dilated convolution a forward of this size runs: the handle's form
-        (mbx_conv_form) and, for F(4,3), the block shape the library's launch-size rule picks (csrc/mbx_api.hip: 256-row
+        (mbx_conv_form) and, for F(4,3), the block shape the library's launch-size rule picks (csrc/mbx_forward.hip, gate_shape_policy: 256-row
         blocks, or 128-row blocks whose waves split the six products where those spread the work clearly more evenly over
         the SIMDs, or product-split blocks of half a column tile where even those load the CUs unevenly; all three give the same
         bits): "direct", "winograd_f23", "winograd_f43", "winograd_f43_psplit" or "winograd_f43_hsplit"."""
@@ -1177,7 +1177,7 @@ class MBExWNEngine:
         ptr, cnt, stride = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
         status = self._lib.mbx_stage(self._handle, name.encode(), ctypes.byref(ptr), ctypes.byref(cnt), ctypes.byref(stride))
         if status != 0 and name == "wn_hidden":
-            # split precision with the fp16 planes as the hidden state (csrc/mbx_api.hip: planes_only): the float32 tensor was
+            # split precision with the fp16 planes as the hidden state (csrc/mbx_forward.hip: ForwardCtx::planes_only): the float32 tensor was
             # not written; rebuild hi + 2^-11 lo' from the planes -- per row [C8 hi halves | C8 lo' halves]
             planes = self.stage("wn_hidden_planes")
             C, c8 = self.dims.wn_channels, (self.dims.wn_channels + 7) // 8 * 8

@@ -43,7 +43,7 @@ def norm_reach(dims, config):
 def cond_chain_reach(dims):
     """(left, right) reach in mel frames of the conditioning chain -- the conditioning layer and the pre-conditioning
     convolutions in front of it, all with kernel size cond_kernel_size and zero SAME padding, which the library pads
-    (k - 1) // 2 frames in front and k // 2 behind (csrc/mbx_api.hip, cond_chain): an even kernel size reaches one frame
+    (k - 1) // 2 frames in front and k // 2 behind (csrc/mbx_create.hip, cond_chain): an even kernel size reaches one frame
     further to the right than to the left, per convolution.  CAUSAL WaveNet padding: k - 1 frames in front, none behind."""
     n_cond = 0 if dims.wn_disable_conditioning else 1 + len(dims.wn_pre_cond_channels)
     if dims.wn_padding == "CAUSAL":

@@ -483,39 +483,10 @@ PATCHES = {
         ('    __shared__ __attribute__((aligned(16))) float lds[SH::LDS_FLOATS];\n',
          '    __shared__ __attribute__((aligned(16))) float lds[SH::LDS_FLOATS];\n    __shared__ float lds_pad_[7168];\n    if (p.max_rows == -12345) lds_pad_[threadIdx.x] = 1.f;\n'),
     ],
-    # mbx_api.hip (EXP_FILE=mbx_api.hip), round 6, VERDICT round 5 item 4 -- the ceiling of cross-layer overlap for single
-    # utterances: the res/skip launch of layer l goes to a SECOND stream behind the gate of layer l (that dependency kept),
-    # and the gate of layer l+1 is issued WITHOUT waiting for it (that dependency dropped: wrong audio, timing only).  The
-    # two streams join in front of the tail kernel.
-    'overlap': [
-        ('static mbx_status forward_impl(mbx_handle *hd, const float *mel,',
-         'static hipStream_t exp_side_ = nullptr;\nstatic hipEvent_t exp_ev_[128];\nstatic int exp_ev_i_ = 0;\n'
-         'static hipStream_t exp_side_after(hipStream_t main_) {\n'
-         '    if (!exp_side_) {\n        (void)hipStreamCreateWithFlags(&exp_side_, hipStreamNonBlocking);\n'
-         '        for (auto &e : exp_ev_) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);\n    }\n'
-         '    hipEvent_t e = exp_ev_[exp_ev_i_++ & 127];\n    (void)hipEventRecord(e, main_);\n    (void)hipStreamWaitEvent(exp_side_, e, 0);\n'
-         '    return exp_side_;\n}\n'
-         'static void exp_join(hipStream_t main_) {\n    if (!exp_side_) return;\n    hipEvent_t e = exp_ev_[exp_ev_i_++ & 127];\n'
-         '    (void)hipEventRecord(e, exp_side_);\n    (void)hipStreamWaitEvent(main_, e, 0);\n}\n'
-         'static mbx_status forward_impl(mbx_handle *hd, const float *mel,'),
-        ('                    done = mbx::launch_wn_resskip_wide(rw, stream);',
-         '                    done = mbx::launch_wn_resskip_wide(rw, exp_side_after(stream));'),
-        ('                    done = mbx::launch_wn_resskip_wave(rw, stream);',
-         '                    done = mbx::launch_wn_resskip_wave(rw, exp_side_after(stream));'),
-        ('                if (!done && !mbx::launch_wn_resskip(r, stream)) return fail(',
-         '                if (!done && !mbx::launch_wn_resskip(r, exp_side_after(stream))) return fail('),
-        ('    {\n        ScopedEvents ev(hd, PROF_TAIL, stream);\n        const DevTensor *we = find(hd, "wn.end.w")',
-         '    exp_join(stream);\n    {\n        ScopedEvents ev(hd, PROF_TAIL, stream);\n        const DevTensor *we = find(hd, "wn.end.w")'),
-    ],
-    # the same without the per-layer events: the side stream waits for the main stream ONCE per forward (at the first res/skip
-    # launch) and then runs its res/skip launches back to back beside the gate launches -- no dependency between the two
-    # kernel families at all (apply on top of 'overlap': ovl2:overlap+overlap2)
-    'overlap2': [
-        ('    hipEvent_t e = exp_ev_[exp_ev_i_++ & 127];\n    (void)hipEventRecord(e, main_);\n    (void)hipStreamWaitEvent(exp_side_, e, 0);\n    return exp_side_;',
-         '    static int first_ = 1;\n    if (main_ == nullptr) { first_ = 1; return exp_side_; }\n    if (first_) {\n        first_ = 0;\n        hipEvent_t e = exp_ev_[exp_ev_i_++ & 127];\n        (void)hipEventRecord(e, main_);\n        (void)hipStreamWaitEvent(exp_side_, e, 0);\n    }\n    return exp_side_;'),
-        ('    (void)hipEventRecord(e, exp_side_);\n    (void)hipStreamWaitEvent(main_, e, 0);\n}',
-         '    (void)hipEventRecord(e, exp_side_);\n    (void)hipStreamWaitEvent(main_, e, 0);\n    (void)exp_side_after(nullptr);\n}'),
-    ],
+    # (the round-6 'overlap' / 'overlap2' bound of cross-layer overlap -- res/skip of layer l on a second stream, the gate of
+    # layer l+1 without the dependency; result: profiles/r06_overlap_bound.txt, negative -- patched lines of the single-file
+    # forward_impl, which was split into the stage functions of mbx_forward.hip; the bound is reproduced from commit 9df235e:
+    # git checkout 9df235e -- mbexwn_vocoder_amd/csrc scripts/experiments/mkexp.py, see scripts/experiments/overlap_bound.py)
     'nocomb': [
         ('        constexpr int J = decltype(jc)::value;\n        if (J == 0) u[0] = ww_fma(4.f, x[0]',
          '        constexpr int J = decltype(jc)::value;\n        u[J & 1] = x[J];\n        return;\n        if (J == 0) u[0] = ww_fma(4.f, x[0]'),

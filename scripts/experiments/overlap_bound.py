@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Round 6: what overlap across the layer boundary could buy a single utterance, at most.
 
-Alternates, on ONE box, the product library and `mkexp.py ovl:overlap` (EXP_FILE=mbx_api.hip: res/skip of layer l on a second
-stream, the gate of layer l+1 issued without waiting for it -- wrong audio, timing only) in fresh processes and prints the
-forward time of one utterance of 3 s and 10 s (and 16 x 10 s for scale):
+Alternates, on ONE box, the product library and the libraries given as arguments in fresh processes and prints the forward
+time of one utterance of 3 s and 10 s (and 16 x 10 s for scale):
 
-    EXP_FILE=mbx_api.hip python scripts/experiments/mkexp.py ovl:overlap ovl2:overlap+overlap2      (ovl2: no events per layer)
-    gpurun -- 'python scripts/experiments/overlap_bound.py > gpurun_out/overlap_bound.txt'
+    python scripts/experiments/overlap_bound.py [library.so ...] > overlap_bound.txt
+
+The recorded result (profiles/r06_overlap_bound.txt: the overlap is slower at every size, nothing to build) compared the
+product with `mkexp.py ovl:overlap` (res/skip of layer l on a second stream, the gate of layer l+1 issued without waiting
+for it -- wrong audio, timing only) and `ovl2:overlap+overlap2`.  Those two patches were anchored on lines of the
+single-file launch sequence and went when it was split into stage functions; commit 9df235e still builds them:
+    git worktree add ../ovl 9df235e && cd ../ovl && python -m mbexwn_vocoder_amd.build &&
+    EXP_FILE=mbx_api.hip python scripts/experiments/mkexp.py ovl:overlap ovl2:overlap+overlap2
 """
 import os
 import subprocess
@@ -35,9 +40,9 @@ for batch, frames, reps in ((1, 240, 400), (1, 800, 300), (16, 800, 20)):
 
 
 def main():
-    libs = [os.path.join(ROOT, "scripts", "experiments", "libs", nn) for nn in ("lib_ovl.so", "lib_ovl2.so")]
+    libs = [os.path.abspath(pp) for pp in sys.argv[1:]]
     for rnd in range(2):
-        for path in [None] + [pp for pp in libs if os.path.exists(pp)]:
+        for path in [None] + libs:
             env = dict(os.environ)
             env.pop("MBX_LIB_PATH", None)
             if path:

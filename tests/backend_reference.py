@@ -63,7 +63,7 @@ N_LIFTER_ROWS = 30
 # model kind (what the engine runs behind the WaveNet)
 # ------------------------------------------------------------------------------------------------------------------------
 def backend_kind(dims, cfg):
-    """The back-end branches a model takes, from ModelDims / config with the conditions of csrc/mbx_api.hip,
+    """The back-end branches a model takes, from ModelDims / config with the conditions of csrc/mbx_forward.hip (run_backend),
     csrc/stft_filter.hip::launch_stft_filter and csrc/pqmf.hip::launch_pqmf:
     {"envelope": STFT-domain filter, "lifter": lifter row selected in the kernel, "stft": "wave10_2" | "wave16_16" | "generic" |
      None, "pqmf": "mfma" | "generic" | "reshape", "gain": sub-band gains, "norm": RMS normalisation, "tail": "fused" |
@@ -81,7 +81,7 @@ def backend_kind(dims, cfg):
     if dims.no_pqmf:
         pqmf = "reshape"
     else:
-        # polyphase taps per phase (csrc/mbx_api.hip, tables.pqmf_polyphase): n_dm = 2 ceil((taps / 2) / M) + 1
+        # polyphase taps per phase (csrc/mbx_create.hip, tables.pqmf_polyphase): n_dm = 2 ceil((taps / 2) / M) + 1
         half = int(mb["multi_band_config"]["taps"]) // 2
         n_dm = 2 * ((half + M - 1) // M) + 1
         pqmf = "generic" if M > 16 or n_dm * M > 4 * 48 else "mfma"

@@ -80,8 +80,11 @@ def test_policy_fields_and_experiment_variables(monkeypatch, capsys):
     assert cc.wn_conv_form == 1
     with pytest.raises(ValueError):
         engine.make_config(cfg, wt, conv_form="f63")
-    src = open(os.path.join(ROOT, "mbexwn_vocoder_amd", "csrc", "mbx_api.hip")).read()
-    assert "getenv" not in src
+    csrc = os.path.join(ROOT, "mbexwn_vocoder_amd", "csrc")
+    sources = sorted(os.listdir(csrc))
+    assert {"mbx_api.hip", "mbx_create.hip", "mbx_forward.hip", "mbx_handle.h"} <= set(sources)
+    for name in sources:
+        assert "getenv" not in open(os.path.join(csrc, name)).read(), name
 
 
 def test_make_config_and_tensor_table():

@@ -105,7 +105,7 @@ def test_gpu_cases_cover_every_backend_branch():
     wide one through both of its conditions), the three PQMF forms, the fused and the unfused tail (at that level: "fused"
     covers wn_tail2_kernel, wn_tail_kernel and the folded tail alike), the sub-band gains (with and without the
     energy-preserving mean), no envelope at all, no lifter row, the RMS-normalisation gain -- derived from ModelDims /
-    config by the conditions of launch_stft_filter, launch_pqmf, launch_wn_tail and mbx_api.hip.  The overlap-add loop for
+    config by the conditions of launch_stft_filter, launch_pqmf, launch_wn_tail and mbx_forward.hip (run_tail, run_backend).  The overlap-add loop for
     windows longer than 4 hop is not reachable: mbx_create refuses such a model (test_wide_window_is_refused)."""
     kinds = {}
     for geom in GEOMETRIES:

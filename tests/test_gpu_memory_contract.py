@@ -808,7 +808,7 @@ def test_the_detector_reports_a_row_it_is_told_is_guard(torch):
 @pytest.mark.parametrize("fill", FILLS)
 def test_short_or_misaligned_workspace_is_refused_before_any_launch(torch, fill, entry):
     """workspace_bytes one less than mbx_workspace_size -> MBX_ERR_WORKSPACE; a workspace pointer at +128 bytes ->
-    MBX_ERR_INVALID_ARGUMENT (forward_impl of csrc/mbx_api.hip checks both in front of its first launch, and mbx_calibrate's
+    MBX_ERR_INVALID_ARGUMENT (check_forward_args of csrc/mbx_forward.hip checks both in front of the first launch, and mbx_calibrate's
     first forward is refused the same way); every byte of audio, workspace and guards is still the fill."""
     from mbexwn_vocoder_amd.engine import mbx_forward_options
     eng = _small_engine()

@@ -86,7 +86,7 @@ _MAX_LAYERS = 64                     # MBX_MAX_WN_LAYERS
 
 
 def expected_gate_kernels(dims, kwargs, fold_start):
-    """The gate kernel of every layer (block-major) that csrc/mbx_api.hip picks.  Several blocks (run_wavenet_blocks): F(4,3)
+    """The gate kernel of every layer (block-major) that csrc/mbx_forward.hip (run_gate_layer) picks.  Several blocks (run_wavenet_blocks): F(4,3)
     (launch_wn_gate_winograd4w, 256-row blocks; d > 16 as d / 16 interleaved sub-sequences) where the form is F(4,3), the
     padding SAME, C % 4 == 0, C >= 25 and a 256-row tile holds at most 56 conditioning rows; the direct form otherwise.  One
     block: these cases pin the direct form or hand over no weight images, so layer 0 is the folded first layer or direct."""

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MBX_ABI_VERSION 10
+#define MBX_ABI_VERSION 11
 #define MBX_MAX_SUBNET_OPS 32
 #define MBX_MAX_WN_LAYERS 64
 #define MBX_MAX_PRECOND 8
@@ -297,6 +297,38 @@ typedef struct {
 #define MBX_GATE_K_FOLDED_START 8    /* wn_gate0_kernel: layer 0 with the start convolution folded in */
 #define MBX_GATE_K_SPLIT_F16 9       /* wn_gate_f16_kernel (opt-in split half precision) */
 mbx_status mbx_conv_form(const mbx_handle *handle, mbx_conv_form_info *info);
+
+/* ABI 11: which residual/skip and tail kernels the most recent forward ran (the gate kernels: mbx_conv_form_info.gate_kernel). */
+typedef struct {
+    int32_t struct_size;        /* sizeof(mbx_kernel_report_info), set by the caller */
+    int32_t n_resskip_layers;   /* entries of resskip_kernel that the most recent forward filled (0 before the first one) */
+    int32_t resskip_kernel[MBX_MAX_WN_LAYERS];   /* MBX_RESSKIP_K_*: what ran the residual/skip convolution of layer l; block-major
+                                                  * as gate_kernel is.  MBX_RESSKIP_K_NONE: the layer has no launch of its own (the
+                                                  * last layer of a handle with fold_skip: the tail kernel takes its share) */
+    int32_t tail_kernel;        /* MBX_TAIL_K_*: what ran the end convolution and the post-net */
+    int32_t tail_folded;        /* 1: that kernel was the folded tail (fold_skip: the last layer's gate output x "wn.tail.fold") */
+} mbx_kernel_report_info;
+#define MBX_RESSKIP_K_NONE 0
+#define MBX_RESSKIP_K_CONV1D 1       /* conv1d_mfma_kernel<EPI_RESSKIP> (launch_conv1d): no packed image, or the layer does not fit */
+#define MBX_RESSKIP_K_PACKED64 2     /* wn_resskip_kernel<1,2>: 64-row blocks, 128-column tiles */
+#define MBX_RESSKIP_K_PACKED128 3    /* wn_resskip_kernel<2,3>: 128-row blocks, from 2 304 of them up */
+#define MBX_RESSKIP_K_WIDE11_RES10 4 /* wn_resskip_wide_kernel<11,1,10>: 11 column pairs, C >= 320 (the first 10 pairs are residual) */
+#define MBX_RESSKIP_K_WIDE11 5       /* wn_resskip_wide_kernel<11,1,0>: 11 column pairs, C < 320 */
+#define MBX_RESSKIP_K_WIDE6X2 6      /* wn_resskip_wide_kernel<6,2,0>: 12 column pairs, two blocks of 6 per row tile */
+#define MBX_RESSKIP_K_WAVE11 7       /* wn_resskip_wave_kernel<11,3>: all 11 pairs per wave */
+#define MBX_RESSKIP_K_WAVE12 8       /* wn_resskip_wave_kernel<12,3>: all 12 pairs per wave */
+#define MBX_RESSKIP_K_WAVE6X2 9      /* wn_resskip_wave_kernel<6,4>: two column splits of 6 pairs */
+#define MBX_RESSKIP_K_WAVE4X3 10     /* wn_resskip_wave_kernel<4,4>: three column splits of 4 pairs */
+#define MBX_RESSKIP_K_SPLIT_F16 11   /* wn_resskip_f16_kernel (opt-in split half precision) */
+#define MBX_TAIL_K_NONE 0
+#define MBX_TAIL_K_UNFUSED 1         /* two generic convolutions (conv1d_mfma_kernel<EPI_LINEAR>): end convolution, post-net */
+#define MBX_TAIL_K_TAIL2_NJ4 2       /* wn_tail2_kernel<4>: C <= 64 */
+#define MBX_TAIL_K_TAIL2_NJ8 3       /* wn_tail2_kernel<8>: C <= 128 */
+#define MBX_TAIL_K_TAIL2_NJ12 4      /* wn_tail2_kernel<12>: C <= 192 */
+#define MBX_TAIL_K_TAIL2_NJ20 5      /* wn_tail2_kernel<20>: C <= 320 */
+#define MBX_TAIL_K_TAIL2_NJ22 6      /* wn_tail2_kernel<22>: C <= 352 */
+#define MBX_TAIL_K_TAIL 7            /* wn_tail_kernel: C < 16 or C > 352 */
+mbx_status mbx_kernel_report(const mbx_handle *handle, mbx_kernel_report_info *info);
 
 /* Re-runs the calibration of MBX_CONV_AUTO on the caller's own input (same argument meaning as mbx_forward) and adopts
  * its decision for the forwards that follow -- for a handle created with any wn_conv_form (a pinned form becomes the

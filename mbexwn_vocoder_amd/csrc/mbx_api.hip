@@ -196,6 +196,17 @@ mbx_status mbx_conv_form(const mbx_handle *hd, mbx_conv_form_info *info) {
     return MBX_OK;
 }
 
+mbx_status mbx_kernel_report(const mbx_handle *hd, mbx_kernel_report_info *info) {
+    if (!hd || !info || info->struct_size != (int32_t)sizeof(mbx_kernel_report_info))
+        return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_kernel_report_info ABI mismatch (struct_size)");
+    info->n_resskip_layers = hd->last_gate_layers;
+    for (int l = 0; l < MBX_MAX_WN_LAYERS; ++l)
+        info->resskip_kernel[l] = l < hd->last_gate_layers ? hd->last_resskip_kernel[l] : MBX_RESSKIP_K_NONE;
+    info->tail_kernel = hd->last_gate_layers ? hd->last_tail_kernel : MBX_TAIL_K_NONE;
+    info->tail_folded = hd->last_gate_layers ? hd->last_tail_folded : 0;
+    return MBX_OK;
+}
+
 mbx_status mbx_forward(mbx_handle *hd, const float *mel, const int32_t *n_frames, int32_t batch, int32_t max_frames,
                        const float *noise, float *audio, void *workspace, size_t workspace_bytes, void *hip_stream) {
     return forward_impl(hd, mel, n_frames, batch, max_frames, noise, audio, workspace, workspace_bytes, hip_stream);

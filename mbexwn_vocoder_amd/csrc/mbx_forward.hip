@@ -726,13 +726,13 @@ mbx_status run_gate_layer(ForwardCtx &cx, const mbx::ConvArgs &g, const WnLayerT
 
 // res/skip of one layer: split half precision, then the wide, then the wave-tiled kernel (folded layers: im is the layer's
 // image set, rows of C + 16 channels under ext), then the packed LDS-DMA kernel, then the generic one (layers with a skip
-// tensor only: im null, r.w the plain weights)
-mbx_status run_resskip_layer(ForwardCtx &cx, const mbx::ConvArgs &r, const WnLayerTensors &t, const FoldImages *im, bool ext) {
+// tensor only: im null, r.w the plain weights).  kernel: where the MBX_RESSKIP_K_* that ran is reported (null: not).
+mbx_status run_resskip_layer(ForwardCtx &cx, const mbx::ConvArgs &r, const WnLayerTensors &t, const FoldImages *im, bool ext, int *kernel) {
     mbx_handle *hd = cx.hd;
     hipStream_t stream = cx.stream;
     const int C = r.channels;
     ScopedEvents ev(hd, (hd->split_f16 && (!ext || im->f16)) ? PROF_RES_SKIP_F16 : PROF_RES_SKIP, stream);
-    bool done = false;
+    int done = MBX_RESSKIP_K_NONE;
     if (im) {
         // opt-in split half precision (mbx_config.wn_precision): every launch size, every layer whose split image the
         // host supplied (layer 0 with the folded start convolution too: its rows [a0 | x'] have the image *.fold_start_f16)
@@ -747,7 +747,7 @@ mbx_status run_resskip_layer(ForwardCtx &cx, const mbx::ConvArgs &r, const WnLay
                 rh.h_planes_only = cx.planes_only ? 1 : 0;
             }
             done = mbx::launch_wn_resskip_f16(rh, stream);
-            cx.planes_valid = done && rh.h_split != nullptr;
+            cx.planes_valid = done != MBX_RESSKIP_K_NONE && rh.h_split != nullptr;
             if (cx.planes_only && !cx.planes_valid)
                 return fail(MBX_ERR_INVALID_ARGUMENT, "split precision: a res/skip layer did not take the plane-only hidden state");
         } else {
@@ -775,7 +775,11 @@ mbx_status run_resskip_layer(ForwardCtx &cx, const mbx::ConvArgs &r, const WnLay
         done = mbx::launch_wn_resskip(rp, stream);
     }
     if (!done && im) return fail(MBX_ERR_INVALID_ARGUMENT, "folded res/skip layer does not fit its kernel");
-    if (!done) mbx::launch_conv1d(r, mbx::EPI_RESSKIP, stream);
+    if (!done) {
+        mbx::launch_conv1d(r, mbx::EPI_RESSKIP, stream);
+        done = MBX_RESSKIP_K_CONV1D;
+    }
+    if (kernel) *kernel = done;
     return MBX_OK;
 }
 
@@ -793,17 +797,20 @@ mbx_status run_tail(ForwardCtx &cx) {
     const DevTensor *wpn = hd->tab.post_w, *bpn = hd->tab.post_b, *be = bt.end_b;
     const Span &ts = cx.tail_sp;
     float *acc_t = w.wn_out + ts.row0 * n_out, *sub_t = w.sub + ts.row0 * M, *skip_t = w.skip + ts.row0 * C;
+    int ran = MBX_TAIL_K_NONE;
     if (hd->fold_skip) {
-        if (!mbx::launch_wn_tail(w.a + ts.row0 * C, nsteps * C, ts.nf, ts.rpf, ts.max_rows, B, C, bt.tail_fold->ptr, bt.tail_fold_b->ptr,
-                                 n_out, wpn->ptr, bpn ? bpn->ptr : nullptr, M, L > 1 ? acc_t : nullptr,
-                                 acc_t, nsteps * n_out, sub_t, nsteps * M, stream))
-            return fail(MBX_ERR_INVALID_ARGUMENT, "folded WaveNet tail does not fit its kernel");
+        ran = mbx::launch_wn_tail(w.a + ts.row0 * C, nsteps * C, ts.nf, ts.rpf, ts.max_rows, B, C, bt.tail_fold->ptr, bt.tail_fold_b->ptr,
+                                  n_out, wpn->ptr, bpn ? bpn->ptr : nullptr, M, L > 1 ? acc_t : nullptr,
+                                  acc_t, nsteps * n_out, sub_t, nsteps * M, stream);
+        if (!ran) return fail(MBX_ERR_INVALID_ARGUMENT, "folded WaveNet tail does not fit its kernel");
     }
-    const bool fused = hd->fold_skip || (bt.end_packed &&
-        mbx::launch_wn_tail(skip_t, nsteps * C, ts.nf, ts.rpf, ts.max_rows, B, C, bt.end_packed->ptr,
-                            be ? be->ptr : nullptr, n_out, wpn->ptr, bpn ? bpn->ptr : nullptr, M, nullptr,
-                            acc_t, nsteps * n_out, sub_t, nsteps * M, stream));
-    if (!fused) {
+    if (!hd->fold_skip && bt.end_packed)
+        ran = mbx::launch_wn_tail(skip_t, nsteps * C, ts.nf, ts.rpf, ts.max_rows, B, C, bt.end_packed->ptr,
+                                  be ? be->ptr : nullptr, n_out, wpn->ptr, bpn ? bpn->ptr : nullptr, M, nullptr,
+                                  acc_t, nsteps * n_out, sub_t, nsteps * M, stream);
+    hd->last_tail_kernel = ran ? ran : MBX_TAIL_K_UNFUSED;
+    hd->last_tail_folded = hd->fold_skip ? 1 : 0;
+    if (!ran) {
         mbx::ConvArgs a = conv_args(skip_t, nsteps * C, C, ts.nf, ts.rpf, ts.max_rows, B, bt.end_w, be, 1, C,
                                     n_out, 1, 0, MBX_PAD_ZERO, acc_t, nsteps * n_out, n_out);
         mbx::launch_conv1d(a, mbx::EPI_LINEAR, stream);
@@ -864,7 +871,8 @@ mbx_status run_wavenet(ForwardCtx &cx) {
         }
         mbx_status st = MBX_OK;
         if (!fold) {
-            st = run_resskip_layer(cx, resskip_args(hd, t, C, l, w.a, w.h, w.skip, nsteps * C, rs, B), t, nullptr, false);
+            st = run_resskip_layer(cx, resskip_args(hd, t, C, l, w.a, w.h, w.skip, nsteps * C, rs, B), t, nullptr, false,
+                                   &hd->last_resskip_kernel[l]);
         } else if (l < L - 1) {
             // skip path folded into the end convolution: layers 0..L-2 update h and add a W_skip W_end to the n_out-wide
             // output accumulator; the last layer's contribution is added by the tail kernel.
@@ -882,7 +890,9 @@ mbx_status run_wavenet(ForwardCtx &cx) {
             r.skip_bstride = nsteps * n_out;
             r.hs_bstride = nsteps * C;
             r.skip_init = (l == 0);
-            st = run_resskip_layer(cx, r, t, &t.run, ext);
+            st = run_resskip_layer(cx, r, t, &t.run, ext, &hd->last_resskip_kernel[l]);
+        } else {
+            hd->last_resskip_kernel[l] = MBX_RESSKIP_K_NONE;       // the tail kernel adds the last layer's share
         }
         if (st != MBX_OK) return st;
     }
@@ -904,7 +914,8 @@ mbx_status run_wavenet_blocks(ForwardCtx &cx) {
     const int L = c.wn_layers, n_out = c.wn_out_channels, M = c.subbands;
     const int nsub1 = 1 + c.wt_subharm_channels;
     const float *x_in = nullptr;                 // output of the previous block (B, rows, n_out)
-    // mbx_conv_form_info.gate_kernel: block-major, entry b * L + l (as many as MBX_MAX_WN_LAYERS holds)
+    // mbx_conv_form_info.gate_kernel and mbx_kernel_report_info.resskip_kernel: block-major, entry b * L + l (as many as
+    // MBX_MAX_WN_LAYERS holds)
     hd->last_gate_layers = std::min<int>((int)hd->blocks.size() * L, MBX_MAX_WN_LAYERS);
     for (size_t b = 0; b < hd->blocks.size(); ++b) {
         const auto &blk = hd->blocks[b];
@@ -931,7 +942,8 @@ mbx_status run_wavenet_blocks(ForwardCtx &cx) {
             const mbx::ConvArgs g = gate_args(hd, t, C, c.wn_dilations[l], w.mb_h, w.mb_a, rows * C, sp, B, cond, (long long)T * blk.ccu * 2 * C);
             mbx_status st = run_gate_layer(cx, g, t, nullptr, true, slot < MBX_MAX_WN_LAYERS ? &hd->last_gate_kernel[slot] : nullptr);
             if (st != MBX_OK) return st;
-            st = run_resskip_layer(cx, resskip_args(hd, t, C, l, w.mb_a, w.mb_h, w.mb_skip, rows * C, sp, B), t, nullptr, false);
+            st = run_resskip_layer(cx, resskip_args(hd, t, C, l, w.mb_a, w.mb_h, w.mb_skip, rows * C, sp, B), t, nullptr, false,
+                                   slot < MBX_MAX_WN_LAYERS ? &hd->last_resskip_kernel[slot] : nullptr);
             if (st != MBX_OK) return st;
         }
         // end convolution (reference custom_AE_layers.py:337-340); the last block's output is the stage "wn_out" unless an
@@ -956,6 +968,8 @@ mbx_status run_wavenet_blocks(ForwardCtx &cx) {
     mbx::ConvArgs pn = conv_args(x_in, cx.nsteps * n_out, n_out, n_frames, c.steps_per_frame, (int)cx.nsteps, B, hd->tab.post_w,
                                  hd->tab.post_b, 1, n_out, M, 1, 0, MBX_PAD_ZERO, w.sub, cx.nsteps * M, M);
     mbx::launch_conv1d(pn, mbx::EPI_LINEAR, stream);
+    hd->last_tail_kernel = MBX_TAIL_K_UNFUSED;      // every block's end convolution and the post-net are generic convolutions
+    hd->last_tail_folded = 0;
     return MBX_OK;
 }
 

@@ -131,6 +131,8 @@ struct mbx_handle {
     long long subnet_buf_per_frame = 0;   // floats per frame of one ping-pong buffer
     int last_gate_kernel[MBX_MAX_WN_LAYERS] = {};   // MBX_GATE_K_* of the most recent forward (mbx_conv_form_info.gate_kernel)
     int last_gate_layers = 0;
+    int last_resskip_kernel[MBX_MAX_WN_LAYERS] = {};   // MBX_RESSKIP_K_* per layer, indexed as last_gate_kernel (mbx_kernel_report)
+    int last_tail_kernel = 0, last_tail_folded = 0;    // MBX_TAIL_K_* of the most recent forward; 1: it ran as the folded tail
     bool f0_full64 = false;               // mbx_config.f0_accumulate == MBX_F0_ACC_F64 and the F0-net has the shape (conv [prelu | leaky])* head
                                           // with its "<layer>.w64" tensors: float64 weights and hidden layers (f0_chain_is_full64)
     std::vector<mbx_subnet_op> cond_ops;  // pre-conditioning convolutions + the conditioning layer (empty: conditioning disabled)

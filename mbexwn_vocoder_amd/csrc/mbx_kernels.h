@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/mbexwn.h"   // MBX_RESSKIP_K_* / MBX_TAIL_K_*: what the res/skip and tail launchers return
 
 namespace mbx {
 
@@ -147,23 +148,25 @@ struct Gate0Args {
 };
 bool launch_wn_gate0(const Gate0Args &a, hipStream_t stream);
 bool wn_gate0_fits(int channels, int pulse_channels, int dil, int cond_up);
+// The res/skip launchers return the MBX_RESSKIP_K_* of the instantiation they launched, MBX_RESSKIP_K_NONE (0): the layer does
+// not fit, nothing was launched.
 // WaveNet residual/skip layer for large row counts (wn_resskip.hip); a.w = host-packed weights (ceil(cout/128), ceil(C/16), 2048)
-bool launch_wn_resskip(const ConvArgs &a, hipStream_t stream);
+int launch_wn_resskip(const ConvArgs &a, hipStream_t stream);
 // the same layer for large launches, one block owning all columns of its rows (wn_resskip_wide.hip); a.w = image of
 // engine.pack_resskip_wide_weights (ceil(cin/8), ceil(cout/32), 256)
-bool launch_wn_resskip_wide(const ConvArgs &a, hipStream_t stream);
+int launch_wn_resskip_wide(const ConvArgs &a, hipStream_t stream);
 // the same layer for small launches (one utterance, streaming ticks), tiled at wave granularity (wn_resskip_wave.hip);
 // a.w = image of engine.pack_resskip_wave_weights (ceil(cin/16), 12, 512)
-bool launch_wn_resskip_wave(const ConvArgs &a, hipStream_t stream);
+int launch_wn_resskip_wave(const ConvArgs &a, hipStream_t stream);
 // the same layer in split half precision (wn_resskip_f16.hip; opt-in, mbx_config.wn_precision); a.w = image of
 // engine.pack_resskip_f16_weights (ceil(cin/32), 12, 1024); a.gate_act must be set (glu is refused)
-bool launch_wn_resskip_f16(const ConvArgs &a, hipStream_t stream);
+int launch_wn_resskip_f16(const ConvArgs &a, hipStream_t stream);
 // WaveNet end convolution + post-net in one pass over the skip tensor (wn_tail.hip); w_end_packed = host-packed
-// weights (ceil(C/8), 2, 32, 4); false: shapes do not fit
-bool launch_wn_tail(const float *skip, long long skip_bstride, const int *n_frames, int rows_per_frame, int max_rows,
-                    int batch, int C, const float *w_end_packed, const float *b_end, int n_out, const float *w_post,
-                    const float *b_post, int M, const float *y_acc, float *y, long long y_bstride, float *sub,
-                    long long sub_bstride, hipStream_t stream);
+// weights (ceil(C/8), 2, 32, 4); returns the MBX_TAIL_K_* of the kernel it chose, MBX_TAIL_K_NONE (0): shapes do not fit
+int launch_wn_tail(const float *skip, long long skip_bstride, const int *n_frames, int rows_per_frame, int max_rows,
+                   int batch, int C, const float *w_end_packed, const float *b_end, int n_out, const float *w_post,
+                   const float *b_post, int M, const float *y_acc, float *y, long long y_bstride, float *sub,
+                   long long sub_bstride, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // element-wise / bandwidth-type stages (elementwise.hip)

@@ -293,10 +293,10 @@ __global__ __launch_bounds__(256, (RvShape<NPW, NSTAGE>::WAVES_PER_SIMD)) void w
     }
 }
 
-// a.w must point at the image of engine.pack_resskip_wave_weights (ceil(cin/16), 12, 512); returns false if the layer
+// a.w must point at the image of engine.pack_resskip_wave_weights (ceil(cin/16), 12, 512); returns MBX_RESSKIP_K_NONE if the layer
 // does not fit (the caller then uses launch_wn_resskip).  The cut (pairs per wave) follows the number of wave tiles:
 // all columns per wave while the tiles alone give every SIMD about one wave, column splits below that.
-bool launch_wn_resskip_wave(const ConvArgs &a, hipStream_t stream) {
+int launch_wn_resskip_wave(const ConvArgs &a, hipStream_t stream) {
     const int np = (a.cout + 31) / 32;
     const int nk = (a.cin + RV_BK - 1) / RV_BK;
     const bool ok = a.ks == 1 && (a.h_init ? a.cin >= a.channels : a.cin == a.channels) && !a.last_layer && a.skip_ld > 0 &&
@@ -305,7 +305,7 @@ bool launch_wn_resskip_wave(const ConvArgs &a, hipStream_t stream) {
                     (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && (uintptr_t)a.h % 8 == 0 &&
                     (uintptr_t)a.skip % 8 == 0 && (!a.bias || (uintptr_t)a.bias % 8 == 0) && a.hs_bstride % 2 == 0 && a.zeros &&
                     a.h && a.skip;
-    if (!ok) return false;
+    if (!ok) return MBX_RESSKIP_K_NONE;
     ConvArgs r = a;
     r.fast_dma = 1;                 // byte offsets are relative to the tile's first row
     r.m_tiles_per_item = (a.max_rows + 15) / 16;
@@ -334,7 +334,7 @@ bool launch_wn_resskip_wave(const ConvArgs &a, hipStream_t stream) {
     } else {
         hipLaunchKernelGGL((wn_resskip_wave_kernel<4, 4>), dim3(groups, 3), dim3(256), 0, stream, r);
     }
-    return true;
+    return split == 1 ? (np == 11 ? MBX_RESSKIP_K_WAVE11 : MBX_RESSKIP_K_WAVE12) : split == 2 ? MBX_RESSKIP_K_WAVE6X2 : MBX_RESSKIP_K_WAVE4X3;
 }
 
 }  // namespace mbx

@@ -294,8 +294,8 @@ __global__ __launch_bounds__(512, 4) void wn_resskip_wide_kernel(ConvArgs p) {
 }
 
 // a.w must point at the image of engine.pack_resskip_wide_weights (ceil(cin/8), np, 256) with np = ceil(cout/32) in
-// {11, 12}; returns false if the layer does not fit (the caller then uses launch_wn_resskip)
-bool launch_wn_resskip_wide(const ConvArgs &a, hipStream_t stream) {
+// {11, 12}; returns MBX_RESSKIP_K_NONE if the layer does not fit (the caller then uses launch_wn_resskip)
+int launch_wn_resskip_wide(const ConvArgs &a, hipStream_t stream) {
     const int np = (a.cout + 31) / 32;
     const bool ok = a.ks == 1 && (a.h_init ? a.cin >= a.channels : a.cin == a.channels) && !a.last_layer && a.skip_ld > 0 &&
                     (np == 11 || np == 12) && a.cin % 4 == 0 && a.cin >= 3 * RW_BK && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 &&
@@ -303,7 +303,7 @@ bool launch_wn_resskip_wide(const ConvArgs &a, hipStream_t stream) {
                     (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && (uintptr_t)a.h % 8 == 0 &&
                     (uintptr_t)a.skip % 8 == 0 && (!a.bias || (uintptr_t)a.bias % 8 == 0) && a.hs_bstride % 2 == 0 && a.zeros &&
                     a.h && a.skip;
-    if (!ok) return false;
+    if (!ok) return MBX_RESSKIP_K_NONE;
     ConvArgs r = a;
     r.fast_dma = 1;                 // byte offsets are relative to the block's first row
     r.m_tiles_per_item = (a.max_rows + RW_ROWS - 1) / RW_ROWS;
@@ -314,7 +314,7 @@ bool launch_wn_resskip_wide(const ConvArgs &a, hipStream_t stream) {
     if (np == 11 && a.channels >= 320) hipLaunchKernelGGL((wn_resskip_wide_kernel<11, 1, 10>), dim3((unsigned)blocks), dim3(512), 0, stream, r);
     else if (np == 11) hipLaunchKernelGGL((wn_resskip_wide_kernel<11, 1, 0>), dim3((unsigned)blocks), dim3(512), 0, stream, r);
     else hipLaunchKernelGGL((wn_resskip_wide_kernel<6, 2, 0>), dim3((unsigned)(2 * blocks)), dim3(512), 0, stream, r);
-    return true;
+    return np == 12 ? MBX_RESSKIP_K_WIDE6X2 : a.channels >= 320 ? MBX_RESSKIP_K_WIDE11_RES10 : MBX_RESSKIP_K_WIDE11;
 }
 
 }  // namespace mbx

@@ -19,7 +19,7 @@ from .config import ModelDims
 from .subnet import build_subnet
 from .weights import fold_weights, merge_channel_groups
 
-MBX_ABI_VERSION = 10
+MBX_ABI_VERSION = 11
 MBX_MAX_SUBNET_OPS = 32
 MBX_MAX_WN_LAYERS = 64
 MBX_MAX_PRECOND = 8
@@ -91,6 +91,19 @@ GATE_KERNEL_NAMES = {0: "none", 1: "direct", 2: "f23", 3: "f43", 4: "f43_psplit"
                      7: "f43_strided_psplit", 8: "folded_start", 9: "split_f16"}
 
 
+class mbx_kernel_report_info(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("n_resskip_layers", ctypes.c_int32),
+                ("resskip_kernel", ctypes.c_int32 * MBX_MAX_WN_LAYERS), ("tail_kernel", ctypes.c_int32),
+                ("tail_folded", ctypes.c_int32)]
+
+
+# MBX_RESSKIP_K_* / MBX_TAIL_K_* of include/mbexwn.h (mbx_kernel_report)
+RESSKIP_KERNEL_NAMES = {0: "none", 1: "conv1d", 2: "packed64", 3: "packed128", 4: "wide11_res10", 5: "wide11", 6: "wide6x2",
+                        7: "wave11", 8: "wave12", 9: "wave6x2", 10: "wave4x3", 11: "split_f16"}
+TAIL_KERNEL_NAMES = {0: "none", 1: "unfused", 2: "tail2_nj4", 3: "tail2_nj8", 4: "tail2_nj12", 5: "tail2_nj20", 6: "tail2_nj22",
+                     7: "tail"}
+
+
 CONV_FORMS = {"auto": 0, "direct": 1, "f23": 2, "f43": 3}
 _CONV_FORM_NAMES = {vv: kk for kk, vv in CONV_FORMS.items()}
 
@@ -145,6 +158,8 @@ def load_library():
     lib.mbx_destroy.argtypes = [vp]
     lib.mbx_conv_form.restype = i32
     lib.mbx_conv_form.argtypes = [vp, ctypes.POINTER(mbx_conv_form_info)]
+    lib.mbx_kernel_report.restype = i32
+    lib.mbx_kernel_report.argtypes = [vp, ctypes.POINTER(mbx_kernel_report_info)]
     lib.mbx_calibrate.restype = i32
     lib.mbx_calibrate.argtypes = [vp, fp, vp, i32, i32, fp, vp, ctypes.c_size_t, vp]
     lib.mbx_workspace_size.restype = ctypes.c_size_t
@@ -196,7 +211,7 @@ def load_library():
     return lib
 
 
-EXPORTED_SYMBOLS = ["mbx_last_error", "mbx_create", "mbx_destroy", "mbx_conv_form", "mbx_calibrate", "mbx_workspace_size", "mbx_forward",
+EXPORTED_SYMBOLS = ["mbx_last_error", "mbx_create", "mbx_destroy", "mbx_conv_form", "mbx_kernel_report", "mbx_calibrate", "mbx_workspace_size", "mbx_forward",
                     "mbx_forward_stream", "mbx_forward_ex", "mbx_layer_state_info", "mbx_window_advance", "mbx_window_update", "mbx_emit_rows", "mbx_stage",
                     "mbx_profile_enable", "mbx_profile_read", "mbx_profile_read_launches", "mbx_clock_probe", "mbx_pqmf_synthesis", "mbx_conv1d", "mbx_conv1d_f64acc", "mbx_lin_interp", "mbx_wavetable", "mbx_stft_filter", "mbx_norm_mel", "mbx_mel_analysis",
                     "mbx_encode_flac16"]
@@ -1108,10 +1123,16 @@ class MBExWNEngine:
         audio(float32 direct form)| of the calibration run at creation) and ``split_rejected`` (True: that error was above the
         threshold or not finite, the handle runs float32 after all: ``split_f16_layers`` is 0 then).  ``gate_kernels``: the
         gate kernel of every layer of the last forward, block-major (block b, layer l at b * n_layers + l) on a model with
-        several WaveNet blocks."""
+        several WaveNet blocks.  From mbx_kernel_report: ``resskip_kernels``, one entry (RESSKIP_KERNEL_NAMES) per layer whose
+        res/skip launch ran, in the same order (the last layer of a handle with ``fold_skip`` has none: the tail takes its
+        share), ``tail_kernel`` (TAIL_KERNEL_NAMES) and ``tail_folded``."""
         info = mbx_conv_form_info()
         info.struct_size = ctypes.sizeof(mbx_conv_form_info)
         _check(self._lib.mbx_conv_form(self._handle, ctypes.byref(info)))
+        rep = mbx_kernel_report_info()
+        rep.struct_size = ctypes.sizeof(mbx_kernel_report_info)
+        _check(self._lib.mbx_kernel_report(self._handle, ctypes.byref(rep)))
+        resskip = [RESSKIP_KERNEL_NAMES[rep.resskip_kernel[ll]] for ll in range(rep.n_resskip_layers)]
         return {"requested": _CONV_FORM_NAMES[info.requested], "form": _CONV_FORM_NAMES[info.form],
                 "stream_form": _CONV_FORM_NAMES[info.stream_form], "calibrated": info.calibrated,
                 "batch_invariant": bool(info.batch_invariant), "fold_skip": bool(info.fold_skip),
@@ -1122,7 +1143,9 @@ class MBExWNEngine:
                 "ref_max": float(info.ref_max), "threshold": float(info.threshold),
                 "err_split": None if info.err_split < 0 else float(info.err_split),
                 "split_rejected": bool(info.split_rejected), "f0_float64_chain": bool(info.f0_float64_chain),
-                "gate_kernels": [GATE_KERNEL_NAMES[info.gate_kernel[ll]] for ll in range(info.n_gate_layers)]}
+                "gate_kernels": [GATE_KERNEL_NAMES[info.gate_kernel[ll]] for ll in range(info.n_gate_layers)],
+                "resskip_kernels": [kk for kk in resskip if kk != "none"],
+                "tail_kernel": TAIL_KERNEL_NAMES[rep.tail_kernel], "tail_folded": bool(rep.tail_folded)}
 
     def calibrate(self, mel, n_frames=None, noise=None):
         """mbx_calibrate: repeat the form calibration on the caller's own mel batch (device tensors as for

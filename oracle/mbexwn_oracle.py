@@ -385,11 +385,17 @@ class OracleModel:
         ``rate_factor``: the block's tensors and its rate relative to the first block (custom_pulsed_generator.py:484,488)."""
         return lin_interp(self.conditioning_rows(mel, prefix, rate_factor), self.wn.get("cond_lin_upsampling", 16), self.f32)
 
-    def wavenet(self, x, mel, return_layers=False, prefix="wn.", channels=None, rate_factor=1, hook=None):
+    def wavenet(self, x, mel, return_layers=False, prefix="wn.", channels=None, rate_factor=1, hook=None, taps=None):
         """custom_AE_layers.py:273-346 (WaveNetAE.call), activation gtu / gfu / gsu / glu; n_ch_groups independent channel groups between
         the shared start and end convolutions (:303-340; layers of group g > 0 are named "<layer>g<g>", :249,260).
         ``hook`` (test instrument, default None: no effect): called as hook(layer, hidden) after the residual update of every layer
-        but the last, with the whole hidden state (B, T, C; the groups side by side); what it returns replaces the hidden state."""
+        but the last, with the whole hidden state (B, T, C; the groups side by side); what it returns replaces the hidden state.
+        ``taps`` (test instrument, one channel group only): {"gate_out": f, "res_skip": f}, each called as f(layer, array) with the
+        gate output that the layer's res/skip convolution is about to read (B, T, C) -- for the last layer that is the input of
+        the end convolution's last share, the tail's input where the skip path is folded -- or with the res/skip convolution's
+        output (B, T, 2 C: residual columns, then skip columns; the last layer: C skip columns); what it returns replaces it."""
+        taps = taps or {}
+        assert not taps or int(self.wn.get("n_ch_groups", 1)) == 1
         C = self.wn["n_channels"] if channels is None else channels
         L = self.wn.get("n_layers", 12)
         G = int(self.wn.get("n_ch_groups", 1))
@@ -421,8 +427,12 @@ class OracleModel:
                 else:
                     raise NotImplementedError(f"WaveNetAE activation {act}")
                 a = half * (1 / (1 + np.exp(-z[..., Cg:])))                       # :320-321
+                if "gate_out" in taps:
+                    a = taps["gate_out"](ll, a)
                 w, b = self.weight(f"{prefix}res_skip_{ll}{sfx}")
                 r = conv1d_valid(a, w, b)                                         # :324
+                if "res_skip" in taps:
+                    r = taps["res_skip"](ll, r)
                 if ll < L - 1:
                     started[gg] = started[gg] + r[..., :Cg]                       # :326-328
                     s = r[..., Cg:]

@@ -34,12 +34,13 @@ def test_library_exports_every_declared_symbol():
 def test_struct_layout_matches_c(tmp_path):
     src = tmp_path / "sizes.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mbexwn.h"\n'
-                   'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mbx_config), sizeof(mbx_subnet_op),'
+                   'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mbx_config), sizeof(mbx_subnet_op),'
                    ' sizeof(mbx_tensor), offsetof(mbx_config, n_f0_ops), offsetof(mbx_config, vtf_ops),'
                    ' offsetof(mbx_config, wt_nominal_f0), sizeof(mbx_forward_options), offsetof(mbx_forward_options, wn_frames),'
                    ' offsetof(mbx_forward_options, sub_carry), offsetof(mbx_forward_options, layer_rows),'
                    ' offsetof(mbx_config, wn_conv_form), offsetof(mbx_config, tune_resskip_split), sizeof(mbx_conv_form_info),'
-                   ' offsetof(mbx_conv_form_info, err_f23)); return 0;}\n')
+                   ' offsetof(mbx_conv_form_info, err_f23), sizeof(mbx_kernel_report_info), offsetof(mbx_kernel_report_info, tail_kernel));'
+                   ' return 0;}\n')
     exe = tmp_path / "sizes"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
@@ -50,7 +51,8 @@ def test_struct_layout_matches_c(tmp_path):
                    ctypes.sizeof(engine.mbx_forward_options), engine.mbx_forward_options.wn_frames.offset,
                    engine.mbx_forward_options.sub_carry.offset, engine.mbx_forward_options.layer_rows.offset,
                    cc.wn_conv_form.offset, cc.tune_resskip_split.offset, ctypes.sizeof(engine.mbx_conv_form_info),
-                   engine.mbx_conv_form_info.err_f23.offset]
+                   engine.mbx_conv_form_info.err_f23.offset, ctypes.sizeof(engine.mbx_kernel_report_info),
+                   engine.mbx_kernel_report_info.tail_kernel.offset]
 
 
 def test_policy_fields_and_experiment_variables(monkeypatch, capsys):
@@ -112,7 +114,7 @@ def test_engine_refuses_to_run_without_gpu():
 
 
 def test_gate_kernel_codes_match_the_header():
-    """mbx_conv_form_info.gate_kernel[] (ABI 10): the MBX_GATE_K_* codes of include/mbexwn.h and the names engine.py reports."""
+    """mbx_conv_form_info.gate_kernel[] (ABI 10; the version literal follows MBX_ABI_VERSION): the MBX_GATE_K_* codes of include/mbexwn.h and the names engine.py reports."""
     import re
     from mbexwn_vocoder_amd import engine
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mbexwn.h")).read()
@@ -122,7 +124,35 @@ def test_gate_kernel_codes_match_the_header():
             "F43_STRIDED": "f43_strided", "F43_STRIDED_PSPLIT": "f43_strided_psplit", "FOLDED_START": "folded_start",
             "SPLIT_F16": "split_f16"}
     assert {engine.GATE_KERNEL_NAMES[vv]: kk for kk, vv in codes.items()} == {vv: kk for kk, vv in want.items()}
-    assert int(re.search(r"#define MBX_ABI_VERSION (\d+)", header).group(1)) == engine.MBX_ABI_VERSION == 10
+    assert int(re.search(r"#define MBX_ABI_VERSION (\d+)", header).group(1)) == engine.MBX_ABI_VERSION == 11
     # bench.py's executed-FLOP factors know every kernel that multiplies
     import bench
     assert set(bench.GATE_EXECUTED) == set(engine.GATE_KERNEL_NAMES.values()) - {"none", "folded_start", "split_f16"}
+
+
+def test_resskip_and_tail_kernel_codes_match_the_header():
+    """mbx_kernel_report (ABI 11): the MBX_RESSKIP_K_* and MBX_TAIL_K_* codes of include/mbexwn.h and the names engine.py reports;
+    every code's comment names its kernel."""
+    header = open(HEADER).read()
+    for prefix, names, want in (
+            ("RESSKIP", engine.RESSKIP_KERNEL_NAMES,
+             {"NONE": "none", "CONV1D": "conv1d", "PACKED64": "packed64", "PACKED128": "packed128", "WIDE11_RES10": "wide11_res10",
+              "WIDE11": "wide11", "WIDE6X2": "wide6x2", "WAVE11": "wave11", "WAVE12": "wave12", "WAVE6X2": "wave6x2",
+              "WAVE4X3": "wave4x3", "SPLIT_F16": "split_f16"}),
+            ("TAIL", engine.TAIL_KERNEL_NAMES,
+             {"NONE": "none", "UNFUSED": "unfused", "TAIL2_NJ4": "tail2_nj4", "TAIL2_NJ8": "tail2_nj8", "TAIL2_NJ12": "tail2_nj12",
+              "TAIL2_NJ20": "tail2_nj20", "TAIL2_NJ22": "tail2_nj22", "TAIL": "tail"})):
+        defs = re.findall(rf"#define MBX_{prefix}_K_(\w+) (\d+)[ \t]*(/\*.*?\*/)?", header)
+        codes = {name: int(val) for name, val, _ in defs}
+        assert sorted(codes.values()) == sorted(names) == list(range(len(names)))
+        assert {names[vv]: kk for kk, vv in codes.items()} == {vv: kk for kk, vv in want.items()}
+        for name, _, comment in defs:
+            assert name == "NONE" or "kernel" in comment or "conv" in comment, f"MBX_{prefix}_K_{name}: no kernel named"
+    templ = dict(re.findall(r"#define MBX_RESSKIP_K_(\w+) \d+\s*/\* (\w+(?:<[\d,]+>)?)", header))
+    assert templ["PACKED64"] == "wn_resskip_kernel<1,2>" and templ["PACKED128"] == "wn_resskip_kernel<2,3>"
+    assert templ["WIDE11_RES10"] == "wn_resskip_wide_kernel<11,1,10>" and templ["WIDE11"] == "wn_resskip_wide_kernel<11,1,0>"
+    assert templ["WIDE6X2"] == "wn_resskip_wide_kernel<6,2,0>" and templ["WAVE11"] == "wn_resskip_wave_kernel<11,3>"
+    assert templ["WAVE12"] == "wn_resskip_wave_kernel<12,3>" and templ["WAVE6X2"] == "wn_resskip_wave_kernel<6,4>"
+    assert templ["WAVE4X3"] == "wn_resskip_wave_kernel<4,4>"
+    info = engine.mbx_kernel_report_info()
+    assert len(info.resskip_kernel) == engine.MBX_MAX_WN_LAYERS

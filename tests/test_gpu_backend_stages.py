@@ -93,6 +93,8 @@ EXPECTED = {
     "psoff": {"envelope": False, "gain": False},
     "normmel": {"norm": True},
 }
+# the tail kernel the library must report (mbx_kernel_report): 60 output channels do not fit wn_tail2_kernel / wn_tail_kernel
+TAIL_KERNELS = {"speech": "tail2_nj20", "voice": "tail2_nj22", "bands30_out60": "unfused"}
 
 
 def _model(geom):
@@ -193,8 +195,11 @@ def test_backend_stages_match_the_oracle(torch, cid, geom, lengths, kwargs):
         audio = _forward(torch, eng, mel, noise, lengths, **fw)
         got = engine_backend_stages(eng, B, T)
         got["audio"] = audio
+        tail = eng.conv_form_info()["tail_kernel"]
     finally:
         eng.close()
+    if geom in TAIL_KERNELS:
+        assert tail == TAIL_KERNELS[geom], f"{cid}: tail kernel {tail}, expected {TAIL_KERNELS[geom]}"
     items = LARGE_CHECK if lengths is LARGE else None
     om64, om32 = oracle_models(cfg, raw, wt)
     ref = BackendReference(om64, om32, dims, cfg, got, mel, lengths, items=items)

@@ -47,7 +47,9 @@ E2E_TOL = parity.E2E_TOL
 # ------------------------------------------------------------------------------------------------------------------------
 WN_IDS = ["c12-f43", "c36-f43", "speech-direct", "speech-f23", "speech-f43", "speech-f43-invariant", "speech-f43-hsplit",
           "speech-rs-nowave", "speech-rs-split2", "lin5-f43", "groups2-f43", "causal-auto", "speech-keep-skip", "speech-split",
-          "voice-f43", "deep12-f43", "deep12-f43-invariant", "deep12-split", "large-f43", "large-split"]
+          "voice-f43", "deep12-f43", "deep12-f43-invariant", "deep12-split", "large-f43", "large-split",
+          # C + n_out one column pair past a multiple of 32: a last pair of two valid columns under the wide and the wave kernel
+          "c292-invariant", "c324-rs-split2"]
 # every multi-block geometry once (the mb_* regions are the last ones carved, next to the end of the workspace), the handle
 # without weight images (res/skip through conv1d), and the pulse-PQMF and sub-harmonic inputs
 BLOCK_IDS = ["blocks-f43", "blocks-noimages", "up2-f43", "three-precond-gfu", "nocond", "c64-f43", "deep6-f43", "lin2-f43",
@@ -157,6 +159,7 @@ EXEMPT = {
     "mbx_calibrate": "runs mbx_forward on its workspace argument and allocates its own audio; the refusals are held here",
     "mbx_create": "writes a host handle pointer only",
     "mbx_conv_form": "fills a host struct",
+    "mbx_kernel_report": "fills a host struct",
     "mbx_layer_state_info": "writes three host integers",
     "mbx_stage": "hands out pointers into the workspace of the last forward, writes no device memory",
     "mbx_profile_read": "host scalars",

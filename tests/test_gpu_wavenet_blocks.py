@@ -2,7 +2,8 @@
 sub-harmonic inputs, stage by stage against the float64 oracle at float32-rounding tolerance (tests/wn_blocks_reference.py).
 
 Every case runs one ragged batch, asserts the gate kernel of every layer of every block (mbx_conv_form_info.gate_kernel,
-block-major) and holds "pulse_ana", "cond" / "cond<b>", the last block's "wn_hidden" and "wn_skip", and "wn_out" to the
+block-major), on the block runner and on handles without weight images the res/skip kernel of every layer and the tail kernel
+too (mbx_kernel_report), and holds "pulse_ana", "cond" / "cond<b>", the last block's "wn_hidden" and "wn_skip", and "wn_out" to the
 oracle fed the engine's own WaveNet input, over every item's valid rows, at tol = max(8 * float32-port error, 5e-7 *
 max(1, |ref|)).  The lengths straddle the 128- and 256-row tiles at 5, 10 and 20 rows per frame (the rates of the blocks)
 and put a 1-frame item next to long ones.  Each case prints one JSON line with the worst error and the bar per tensor.
@@ -81,6 +82,8 @@ CASES = [
     ("subharm-folded", "subharm_fold", "ragged", DIRECT),
     ("large-c64-f43", "c64", "large", F43),
 ]
+# a handle without weight images runs every res/skip layer through conv1d (mbx_kernel_report), and the tail unfused
+NOIMG_RESSKIP = {"conv1d"}
 MUST_FOLD = {"subharm-folded"}       # the sub-harmonic channels go through the folded layer 0 (wn_gate0.hip)
 _MAX_LAYERS = 64                     # MBX_MAX_WN_LAYERS
 
@@ -216,6 +219,23 @@ def test_wavenet_block_stages_match_the_oracle(torch, cid, geom, lkey, kwargs):
     assert ran == expected, f"{cid}: gate kernels {ran}, expected {expected}"
     if cid in MUST_FOLD:
         assert info["fold_start"], f"{cid}: layer 0 not folded"
+    if kwargs == NOIMG:
+        assert len(info["resskip_kernels"]) == len(ran) and set(info["resskip_kernels"]) == NOIMG_RESSKIP, \
+            f"{cid}: res/skip kernels {info['resskip_kernels']}"
+        assert (info["tail_kernel"], info["tail_folded"]) == ("unfused", False), f"{cid}: tail kernel {info['tail_kernel']}"
+    if dims.wn_multi:
+        # the block runner: the packed kernel where the block has its image and C % 4 == 0, conv1d otherwise; generic tail
+        # (launch_wn_resskip: 128-row blocks from 3 x 768 of them up, counted as row tiles x items x 128-column tiles of the
+        # layer's 2 C output columns, C for the last layer)
+        want = []
+        for g in block_geometry(dims):
+            for ll in range(dims.wn_layers):
+                cout = g["C"] * (1 if ll == dims.wn_layers - 1 else 2)
+                blocks = (max(lengths) * g["spf"] + 127) // 128 * B * ((cout + 127) // 128)
+                packed = "packed64" if blocks < 3 * 768 else "packed128"
+                want.append(packed if kwargs.get("weight_images", True) and g["C"] % 4 == 0 else "conv1d")
+        assert info["resskip_kernels"] == want[:_MAX_LAYERS], f"{cid}: res/skip kernels {info['resskip_kernels']}, expected {want}"
+        assert info["tail_kernel"] == "unfused", f"{cid}: tail kernel {info['tail_kernel']}"
     layout = stage_layout(dims)
     names = _stage_names(eng, dims)
     got = engine_stages(eng, layout, names, B, items)
@@ -227,7 +247,8 @@ def test_wavenet_block_stages_match_the_oracle(torch, cid, geom, lkey, kwargs):
     om64, om32 = oracle_models(cfg, raw, wt)
     ref = BlocksReference(om64, om32, dims, pulse, noise, mel, lengths, items=items, pulse_ana=pulse_ana)
     rep = ref.compare(got, names=names)
-    record = {"kernels": sorted(set(ran)), "n_gate_layers": len(ran),
+    record = {"kernels": sorted(set(ran)), "n_gate_layers": len(ran), "resskip_kernels": sorted(set(info["resskip_kernels"])),
+              "tail_kernel": info["tail_kernel"],
               **{kk: {"err": vv["err"], "tol": vv["tol"], "ratio": vv["err"] / vv["tol"], "port_err": vv["port_err"],
                       "ref_max": vv["ref_max"]} for kk, vv in rep.items()}}
     print(f"\nwavenet blocks {cid}: {summary(rep)}  kernels {sorted(set(ran))}")

@@ -1,12 +1,20 @@
 """The WaveNet kernels stage by stage against the float64 oracle at float32-rounding tolerance (tests/wn_reference.py).
 
-Every case runs a ragged batch through the engine, asserts which gate kernels ran (mbx_conv_form_info.gate_kernel) and holds
+Every case runs a ragged batch through the engine, asserts which gate, residual/skip and tail kernels ran
+(mbx_conv_form_info.gate_kernel, mbx_kernel_report) and holds
 "wn_out", "wn_hidden" and (with keep_skip) "wn_skip" to the oracle's WaveNet fed the engine's own excitation rows, over every
 item's valid rows, at tol = max(K * float32-port error, F * max(1, |ref|)).  The lengths straddle the 128- and 256-row tiles
 (20 rows per frame) and an item of one frame is shorter than every dilation >= 32; the ragged order puts short items next
 to long ones, so that one item leaking into its neighbour shows.  The end-to-end tests hold the audio to 1e-4: a lost low
 half of one channel tile, a row off at a tile seam or a leak between items passes that bar (test_wn_reference.py) and not
 this one.  A failure names the worst item, row and channel and the row's place in its 256- and 128-row tiles.
+
+The res/skip convolution runs one of eleven kernel instantiations (or conv1d) and the tail one of six (or two generic
+convolutions); which one follows from C + n_out, C, the launch size and the policy (resskip_shape_policy and the launchers).
+The 3-layer geometries "c<C>" put every instantiation at the channel counts where its tiles are ragged: C + 30 one column
+pair past a multiple of 32 (C = 292, 324: the last pair holds two valid columns), the residual/skip seam inside a pair
+(C = 324, 340) and on a pair boundary (C = 352), a last 16-channel block of 4 channels in the tail (C = 68, 132, 196, 324), the
+first C behind the wave, wide and wn_tail2 kernels (C = 356) and five 128-column tiles (C = 512).
 
 The padding contract of include/mbexwn.h ("every boundary op honours the item's own length") is held bit for bit: the same
 ragged batch with its padding frames of mel and noise at 0, 1e30 and NaN."""
@@ -26,7 +34,11 @@ DEEP = [13, 110, 1, 52, 7]
 # the oracle checks the longest, the shortest and one in the middle
 LARGE = [560, 400, 700, 420, 640, 460, 520, 680, 440, 600, 480, 620, 500, 660, 540, 580]
 LARGE_CHECK = [LARGE.index(max(LARGE)), LARGE.index(min(LARGE)), LARGE.index(560)]
-LENGTHS = {"ragged": (RAGGED, None), "deep": (DEEP, None), "large": (LARGE, LARGE_CHECK)}
+# C = 512, one launch of 77 row tiles x 6 items x 5 column tiles = 2 310 128-row blocks: the packed res/skip kernel's 128-row
+# shape starts at 2 304
+LARGE6 = [490, 3, 260, 77, 411, 128]
+LARGE6_CHECK = [LARGE6.index(max(LARGE6)), LARGE6.index(min(LARGE6)), LARGE6.index(260)]
+LENGTHS = {"ragged": (RAGGED, None), "deep": (DEEP, None), "large": (LARGE, LARGE_CHECK), "large6": (LARGE6, LARGE6_CHECK)}
 
 _WN = "mbexwn_config:pp_mod_subnet:"
 GEOMETRIES = {
@@ -43,10 +55,20 @@ GEOMETRIES = {
     "glu": ("SPEECH", {_WN + "activation": "glu"}),
     "groups2": ("SPEECH", {_WN + "n_ch_groups": 2}),
     "causal": ("SPEECH", {_WN + "padding": "CAUSAL"}),
+    # the channel counts of the res/skip and tail instantiations, 3 layers each
+    **{f"c{C}": ("SPEECH", {_WN + "n_channels": C, _WN + "n_layers": 3})
+       for C in (64, 68, 128, 132, 192, 196, 292, 300, 316, 324, 340, 352, 356, 512)},
 }
 
 F43 = {"conv_form": "f43"}
-FS, PS = "folded_start", "f43_psplit"
+INVARIANT = {"conv_form": "f43", "batch_invariant": True}
+FS, PS, HS = "folded_start", "f43_psplit", "f43_hsplit"
+
+
+def _split(ss):
+    return dict(F43, tune={"resskip_split": ss})
+
+
 # (id, geometry, lengths, engine arguments, the gate kernels the forward must run)
 CASES = [
     # the forms on SPEECH (9 items, 1040 rows: 450 256-row blocks -> the product-split shape under the default policy)
@@ -91,8 +113,60 @@ CASES = [
     # large launches
     ("large-f43", "speech", "large", F43, {FS, "f43"}),
     ("large-split", "speech", "large", dict(F43, precision="split_f16"), {FS, "split_f16"}),
+    # ---- the res/skip and tail instantiations (3 layers) ----
+    # wide kernel (batch_invariant): 11 pairs with C < 320 -> <11,1,0>; 12 pairs -> <6,2,0>
+    *[(f"c{C}-invariant", f"c{C}", "ragged", INVARIANT, {FS, "f43"}) for C in (292, 300, 316, 324, 340, 352)],
+    # wave kernel, its column split pinned: 12 pairs -> <12,3>, <6,4>, <4,4>; 11 pairs cut unevenly (6 + 5, 4 + 4 + 3)
+    *[(f"c{C}-rs-split{ss}", f"c{C}", "ragged", _split(ss), {FS, PS}) for C in (340, 324) for ss in (1, 2, 3)],
+    *[(f"c300-rs-split{ss}", "c300", "ragged", _split(ss), {FS, PS}) for ss in (2, 3)],
+    # packed kernel, 64-row shape: one, two, four and five 128-column tiles
+    ("c64-f43", "c64", "ragged", F43, {FS, HS}),
+    ("c128-f43", "c128", "ragged", F43, {FS, PS}),
+    ("c356-f43", "c356", "ragged", F43, {FS, PS}),
+    ("c512-f43", "c512", "ragged", F43, {FS, PS}),
+    # ... and its 128-row shape
+    ("large6-c512-f43", "c512", "large6", F43, {FS, "f43"}),
+    # tail: a last 16-channel block of 4 channels under NJ = 8, 12 and 20, and NJ = 12 filled
+    ("c68-f43", "c68", "ragged", F43, {FS, HS}),
+    ("c132-f43", "c132", "ragged", F43, {FS, PS}),
+    ("c192-f43", "c192", "ragged", F43, {FS, PS}),
+    ("c196-f43", "c196", "ragged", F43, {FS, PS}),
 ]
 PLANES_ONLY = {"speech-split", "l3-split", "large-split"}
+
+# {case id: (the res/skip kernels its forward must run, its tail kernel)} (engine.RESSKIP_KERNEL_NAMES / TAIL_KERNEL_NAMES).  A
+# model with the skip path folded launches L - 1 res/skip layers; the tail kernel takes the last layer's share.
+W43, P64 = "wave4x3", "packed64"
+NJ4, NJ8, NJ12, NJ20, NJ22 = "tail2_nj4", "tail2_nj8", "tail2_nj12", "tail2_nj20", "tail2_nj22"
+KERNELS = {
+    # SPEECH, 9 ragged items: 585 wave tiles, the fill score picks three column splits; a pinned direct form and the wave
+    # tiles switched off leave the packed kernel; batch_invariant and large launches take the wide one
+    "speech-direct": ({P64}, NJ20), "speech-f23": ({W43}, NJ20), "speech-f43": ({W43}, NJ20),
+    "speech-f43-invariant": ({"wide11_res10"}, NJ20), "speech-auto": ({W43}, NJ20),
+    "speech-f43-256row": ({W43}, NJ20), "speech-f43-psplit": ({W43}, NJ20), "speech-f43-hsplit": ({W43}, NJ20),
+    "speech-rs-split1": ({"wave11"}, NJ20), "speech-rs-split2": ({"wave6x2"}, NJ20), "speech-rs-split3": ({W43}, NJ20),
+    "speech-rs-nowave": ({P64}, NJ20),
+    "voice-f43": ({W43}, NJ22), "voice-f43-256row": ({W43}, NJ22),
+    # 5 items of up to 2 200 rows: 690 wave tiles, all columns per wave
+    "deep12-f43": ({"wave11"}, NJ20), "deep12-f43-invariant": ({"wide11_res10"}, NJ20),
+    "c36-f43": ({P64}, NJ4), "c12-f43": ({P64}, "tail"),
+    "lin5-f43": ({W43}, NJ20), "lin20-f43": ({W43}, NJ20), "gfu-f43": ({W43}, NJ20), "gsu-f43": ({W43}, NJ20),
+    "glu-f43": ({W43}, NJ20), "groups2-f43": ({W43}, NJ20), "causal-auto": ({P64}, NJ20),
+    "speech-keep-skip": ({P64}, NJ20), "speech-keep-start": ({W43}, NJ20),
+    "speech-split": ({"split_f16"}, NJ20), "l3-split": ({"split_f16"}, NJ20), "deep12-split": ({"split_f16"}, NJ20),
+    "large-f43": ({"wide11_res10"}, NJ20), "large-split": ({"split_f16"}, NJ20),
+    "c292-invariant": ({"wide11"}, NJ20), "c300-invariant": ({"wide11"}, NJ20), "c316-invariant": ({"wide11"}, NJ20),
+    "c324-invariant": ({"wide6x2"}, NJ22), "c340-invariant": ({"wide6x2"}, NJ22), "c352-invariant": ({"wide6x2"}, NJ22),
+    "c340-rs-split1": ({"wave12"}, NJ22), "c340-rs-split2": ({"wave6x2"}, NJ22), "c340-rs-split3": ({W43}, NJ22),
+    "c324-rs-split1": ({"wave12"}, NJ22), "c324-rs-split2": ({"wave6x2"}, NJ22), "c324-rs-split3": ({W43}, NJ22),
+    "c300-rs-split2": ({"wave6x2"}, NJ20), "c300-rs-split3": ({W43}, NJ20),
+    "c64-f43": ({P64}, NJ4), "c128-f43": ({P64}, NJ8), "c356-f43": ({P64}, "tail"), "c512-f43": ({P64}, "tail"),
+    "large6-c512-f43": ({"packed128"}, "tail"),
+    "c68-f43": ({P64}, NJ8), "c132-f43": ({P64}, NJ12), "c192-f43": ({P64}, NJ12), "c196-f43": ({P64}, NJ20),
+}
+# the cases whose skip path is not folded (a skip tensor is kept): every layer launches a res/skip convolution, the tail reads
+# the skip tensor
+UNFOLDED = {"speech-keep-skip"}
 _REFS = {}
 
 
@@ -106,6 +180,30 @@ def test_gpu_cases_cover_every_gate_kernel():
     assert len({case[0] for case in CASES}) == len(CASES)
     for case in CASES:
         assert case[1] in GEOMETRIES and case[2] in LENGTHS
+
+
+def test_gpu_cases_cover_every_resskip_and_tail_kernel():
+    """(CPU) Every res/skip and tail kernel the library reports is expected by a stage case here, but for the two generic
+    fall-backs, which the cases without weight images (test_gpu_wavenet_blocks.py: conv1d) and with 60 output channels
+    (test_gpu_backend_stages.py: the unfused tail) expect: a new instantiation without a case fails the suite."""
+    import test_gpu_backend_stages as tbe
+    import test_gpu_wavenet_blocks as tblk
+    from mbexwn_vocoder_amd.engine import RESSKIP_KERNEL_NAMES, TAIL_KERNEL_NAMES
+    assert set(KERNELS) == {case[0] for case in CASES}
+    resskip = set().union(*(kk[0] for kk in KERNELS.values()))
+    tails = {kk[1] for kk in KERNELS.values()}
+    assert any(case[3] == tblk.NOIMG for case in tblk.CASES) and tblk.NOIMG_RESSKIP == {"conv1d"}
+    assert tbe.TAIL_KERNELS["bands30_out60"] == "unfused" and any(case[1] == "bands30_out60" for case in tbe.CASES)
+    assert resskip | tblk.NOIMG_RESSKIP == set(RESSKIP_KERNEL_NAMES.values()) - {"none"}
+    assert tails | {tbe.TAIL_KERNELS["bands30_out60"]} == set(TAIL_KERNEL_NAMES.values()) - {"none"}
+    assert UNFOLDED <= set(KERNELS)
+    # the edges the channel counts are there for
+    chans = {int(case[1][1:]): case[0] for case in CASES if case[1][1:].isdigit()}
+    assert {C for C in chans if (C + 30) % 32 == 2} >= {292, 324} and {C for C in chans if C % 16 == 4} >= {68, 132, 196, 324}
+    lengths, items = LENGTHS["large6"]
+    # launch_wn_resskip: 128-row blocks from three rounds of 768 resident blocks up (row tiles x items x 128-column tiles)
+    assert ((max(lengths) * 20 + 127) // 128) * len(lengths) * ((512 + 30 + 127) // 128) >= 3 * 768
+    assert sorted(lengths[ii] for ii in items) == [min(lengths), 260, max(lengths)]
 
 
 @pytest.fixture(scope="module")
@@ -151,6 +249,12 @@ def test_wavenet_stages_match_the_oracle(torch, cid, geom, lkey, kwargs, kernels
     info = eng.conv_form_info()
     ran = info["gate_kernels"]
     assert len(ran) == eng.dims.wn_layers and set(ran) == kernels, f"{cid}: gate kernels {ran}, expected {sorted(kernels)}"
+    resskip, tail = KERNELS[cid]
+    ran_rs, ran_tail = info["resskip_kernels"], info["tail_kernel"]
+    assert info["fold_skip"] == (cid not in UNFOLDED), f"{cid}: fold_skip {info['fold_skip']}"
+    assert len(ran_rs) == eng.dims.wn_layers - (1 if info["fold_skip"] else 0) and set(ran_rs) == resskip, \
+        f"{cid}: res/skip kernels {ran_rs}, expected {sorted(resskip)}"
+    assert (ran_tail, info["tail_folded"]) == (tail, info["fold_skip"]), f"{cid}: tail kernel {ran_tail}, expected {tail}"
     if kwargs.get("precision") == "split_f16":
         assert not info["split_rejected"] and info["split_f16_layers"] == eng.dims.wn_layers - 1, info
     names = ["wn_out", "wn_hidden"] + (["wn_skip"] if kwargs.get("keep_skip") else [])
@@ -167,9 +271,10 @@ def test_wavenet_stages_match_the_oracle(torch, cid, geom, lkey, kwargs, kernels
         assert np.all(np.isfinite(audio[ii, :ll * 300])) and np.all(audio[ii, ll * 300:] == 0.0), f"{cid}: audio of item {ii}"
     ref = _reference(geom, lkey, cfg, raw, wt, mel, noise, pulse)
     rep = ref.compare(got, names=names)
-    record = {"kernels": ran, **{kk: {"err": vv["err"], "tol": vv["tol"], "port_err": vv["port_err"],
-                                      "ref_max": vv["ref_max"]} for kk, vv in rep.items()}}
-    print(f"\nwavenet stages {cid}: {summary(rep)}  kernels {ran}")
+    record = {"kernels": ran, "resskip_kernels": ran_rs, "tail_kernel": ran_tail,
+              **{kk: {"err": vv["err"], "tol": vv["tol"], "port_err": vv["port_err"],
+                      "ref_max": vv["ref_max"]} for kk, vv in rep.items()}}
+    print(f"\nwavenet stages {cid}: {summary(rep)}  kernels {ran}  res/skip {ran_rs}  tail {ran_tail}")
     print("wavenet stages record " + json.dumps({cid: record}))       # with -s: one JSON line per case
     assert_matches(rep)
 

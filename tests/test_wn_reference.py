@@ -2,7 +2,13 @@
 the graph and rejects each planted defect of the kind Winograd transforms, LDS staging and ragged-batch tile decoding produce
 -- a lost low half of one channel tile, a row at a 256-row tile seam, the conditioning of one row read from its neighbour, one
 item leaking into the next.  Two ragged items of 13 and 26 frames (260 / 520 rows: both cross the 256-row seam), SPEECH
-(5 layers, C = 320) and the 12-layer model with dilations up to 2048."""
+(5 layers, C = 320) and the 12-layer model with dilations up to 2048.
+
+The second half plants what the residual/skip and tail kernels can get wrong at the channel counts of
+test_gpu_wavenet_stages.py (3 layers; C + n_out one column pair past a multiple of 32, the residual/skip seam inside a pair, a
+last 16-channel block of 4 channels): a lost last column pair, two residual columns filled from the skip side of the seam, a
+16-row tile written with its neighbour's rows, a tail without its last channel block.  The skip path is planted as the engine
+holds it, folded into the end convolution: a layer's skip columns are its n_out-wide share of "wn_out"."""
 import numpy as np
 import pytest
 
@@ -150,3 +156,112 @@ def test_rejects_a_leak_between_items(case):
     rep, _, msg = _report_defect(name, "(d) 1e-4 of item 1's row 0 into item 0's last row", ref, ref.port_result(hooks={0: leak}))
     w = rep["wn_hidden"]["where"]
     assert (w["item"], w["rows_to_end"]) == (0, 1), msg
+
+
+# ---- what the residual/skip and tail kernels can get wrong ---------------------------------------------------------------
+_RS_REFS = {}
+N_OUT = 30
+
+
+def _rs_case(C):
+    """The two ragged items on SPEECH with 3 layers and C channels (cached)."""
+    if C not in _RS_REFS:
+        wn = "mbexwn_config:pp_mod_subnet:"
+        cfg, raw, wt = build_case("SPEECH", {wn + "n_channels": C, wn + "n_layers": 3})
+        om64, om32 = oracle_models(cfg, raw, wt)
+        rng = np.random.default_rng(31)
+        T = max(LENGTHS)
+        mel = orc.synthetic_mel(rng, len(LENGTHS), T)
+        noise = rng.normal(size=(len(LENGTHS), T * 20)).astype(np.float32)
+        pulse = _cpu_excitation(om64, mel).astype(np.float32)
+        xs = wavenet_inputs(om64, pulse, noise, LENGTHS, 20)
+        ref = WaveNetReference(om64, om32, xs, mel, LENGTHS, 20)
+        w_end = ref.om32.weight("wn.end")[0]
+        w_end = np.asarray(w_end).reshape(-1, np.asarray(w_end).shape[-1])
+        assert w_end.shape == (C, N_OUT) and w_end.dtype == np.float32
+        _RS_REFS[C] = (ref, w_end)
+    return _RS_REFS[C]
+
+
+@pytest.mark.parametrize("C", [292, 324, 340, 68])
+def test_accepts_the_float32_port_at_the_resskip_geometries(C):
+    ref, _ = _rs_case(C)
+    rep = ref.compare(ref.port_result(), names=("wn_out", "wn_hidden", "wn_skip"))
+    assert not failures(rep), failures(rep)
+
+
+@pytest.mark.parametrize("C", [292, 324])
+def test_rejects_a_lost_last_column_pair(C):
+    """(e) Layer 1's res/skip launch loses its last column pair, the columns >= 32 (np - 1) of its C + 30: at C = 292 (322
+    columns, np = 11) and C = 324 (354, np = 12) that pair holds the last two of the layer's 30 skip columns and nothing else,
+    so "wn_out" lacks the layer's share in its columns 28 and 29."""
+    ref, w_end = _rs_case(C)
+    assert (C + N_OUT) % 32 == 2
+    skip1 = {}
+
+    def taps(ii):
+        def record(ll, r):
+            if ll == 1:
+                skip1[ii] = np.array(r[0, :, C:])
+            return r
+        return {"res_skip": record}
+
+    ref.port_result(taps={ii: taps(ii) for ii in ref.items})
+    got = {kk: np.array(vv) for kk, vv in ref.port_result().items()}
+    for ii in ref.items:
+        got["wn_out"][ii, :ref.rows(ii), 28:30] -= skip1[ii] @ w_end[:, 28:30]
+    rep, _, msg = _report_defect(f"C{C}", "(e) layer 1 loses its last column pair", ref, got)
+    assert not rep["wn_out"]["ok"] and rep["wn_hidden"]["ok"], msg
+    assert rep["wn_out"]["where"]["channel"] in (28, 29), msg
+
+
+def test_rejects_residual_columns_from_behind_the_seam():
+    """(f) C = 340: the residual/skip seam lies inside column pair 10 (columns 320 .. 351).  Layer 1's last two residual columns
+    take the values of its first two skip columns."""
+    C = 340
+    ref, w_end = _rs_case(C)
+
+    def seam(ll, r):
+        if ll == 1:
+            r = r.copy()
+            r[..., C - 2:C] = r[..., C:] @ w_end[:, :2]
+        return r
+
+    rep, _, msg = _report_defect(f"C{C}", "(f) residual columns 338, 339 from skip columns 0, 1", ref,
+                                 ref.port_result(taps={ii: {"res_skip": seam} for ii in ref.items}))
+    assert not rep["wn_hidden"]["ok"] and rep["wn_hidden"]["where"]["channel"] in (C - 2, C - 1), msg
+
+
+def test_rejects_a_row_tile_from_the_tile_before():
+    """(g) C = 324: layer 1's res/skip output of item 1 has the rows of the 16-row tile 240 .. 255 in its tile 256 .. 271 too."""
+    ref, _ = _rs_case(324)
+
+    def tile(ll, r):
+        if ll == 1:
+            r = r.copy()
+            r[:, 256:272] = r[:, 240:256]
+        return r
+
+    rep, _, msg = _report_defect("C324", "(g) rows 256 .. 271 take the rows 240 .. 255", ref,
+                                 ref.port_result(taps={1: {"res_skip": tile}}))
+    w = rep["wn_hidden"]["where"]
+    assert not rep["wn_hidden"]["ok"] and w["item"] == 1 and 256 <= w["row"] < 272, msg
+    assert not rep["wn_out"]["ok"], msg
+
+
+@pytest.mark.parametrize("C", [324, 68])
+def test_rejects_a_tail_without_its_last_channel_block(C):
+    """(h) The tail drops the last 16-channel block of its input, the last layer's gate output: 4 channels at C = 324 and C = 68."""
+    ref, _ = _rs_case(C)
+    first = (C - 1) // 16 * 16
+    assert C - first == 4
+
+    def drop(ll, a):
+        if ll == 2:
+            a = a.copy()
+            a[..., first:] = 0
+        return a
+
+    rep, _, msg = _report_defect(f"C{C}", f"(h) the tail without channels {first} .. {C - 1}", ref,
+                                 ref.port_result(taps={ii: {"gate_out": drop} for ii in ref.items}))
+    assert not rep["wn_out"]["ok"] and rep["wn_hidden"]["ok"], msg

@@ -22,11 +22,11 @@ F_FLOOR = 5e-7
 STAGES = ("wn_out", "wn_hidden", "wn_skip")
 
 
-def oracle_stages(om, x, mel, hook=None):
+def oracle_stages(om, x, mel, hook=None, taps=None):
     """The WaveNet stages of one item (x (1, rows, cin), mel (1, frames, 80)) in the oracle's dtype:
     {"wn_out": (rows, n_out), "wn_hidden": (rows, C), "wn_skip": (rows, C)}."""
     out, h, skip, _, _ = om.wavenet(np.asarray(x).astype(om.dtype), np.asarray(mel).astype(om.dtype), return_layers=True,
-                                    hook=hook)
+                                    hook=hook, taps=taps)
     return {"wn_out": out[0], "wn_hidden": h[0], "wn_skip": skip[0]}
 
 
@@ -63,18 +63,19 @@ class WaveNetReference:
     def rows(self, ii):
         return self.lengths[ii] * self.rpf
 
-    def port_result(self, hook=None, hooks=None, model=None):
+    def port_result(self, hook=None, hooks=None, model=None, taps=None):
         """The float32 port's stages as a batch {name: (B, max rows, channels)} (rows behind an item's end are NaN), with an
         optional planted defect: ``hook`` for every item, or ``hooks`` {item: hook} (see OracleModel.wavenet), or ``model``: a
-        float32 OracleModel to run instead of the port (one whose conditioning was altered, say)."""
-        hooks = dict(hooks or {})
+        float32 OracleModel to run instead of the port (one whose conditioning was altered, say), or ``taps`` {item: taps of
+        OracleModel.wavenet} on a layer's gate output or res/skip output."""
+        hooks, taps = dict(hooks or {}), dict(taps or {})
         per = {}
         for ii in self.items:
             hk = hooks.get(ii, hook)
-            if hk is None and model is None:
+            if hk is None and model is None and ii not in taps:
                 per[ii] = self.port[ii]
             else:
-                per[ii] = oracle_stages(self.om32 if model is None else model, self.xs[ii], self.mels[ii], hook=hk)
+                per[ii] = oracle_stages(self.om32 if model is None else model, self.xs[ii], self.mels[ii], hook=hk, taps=taps.get(ii))
         B, R = len(self.lengths), max(self.lengths) * self.rpf
         out = {}
         for name in STAGES:

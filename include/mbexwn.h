@@ -463,6 +463,29 @@ typedef struct {
      * tick uses (one buffer for the phases of a tick schedule, n_frames masks the rest) computes the last fe_new_frames +
      * fe_margin_frames frames IN FRONT OF fe_end_frames */
     int32_t fe_end_frames;
+    /* Per-frame pitch control (an extension inside ABI 11: see the two struct sizes below).  An F0 tracker's output and a
+     * transposition that varies over the utterance are given at the MEL-FRAME rate and brought to the pulse rate by the
+     * model's own linear interpolator, so that a stream window can reproduce them (reach: one frame ahead).
+     *   f0_frames     device (batch, max_frames) Hz, one value per mel frame; NULL: none
+     *   f0_scale      device (batch, max_frames) transposition factor per mel frame; NULL: none
+     *   f0_item_mask  device (batch) int32: 1 = item takes f0_frames, 0 = item keeps the F0-net; NULL with
+     *                 f0_frames != NULL: every item takes f0_frames (the F0-net is then not run at all)
+     * For pulse sample p = t * pulse_per_frame + u of item b, t < n_frames[b]:
+     *   base[p] = the F0-net's contour, or LI(f0_frames[b])[p] for an item that takes the frames
+     *   f0[p]   = base[p] * LI(f0_scale[b])[p]   (one float32 multiply; base[p] without f0_scale)
+     * LI = TF2C_LinInterpLayer as mbx_lin_interp computes it at the item's own length: frame t towards frame
+     * min(t + 1, n_frames[b] - 1) with the float32 weight vectors, bit-equal to mbx_lin_interp of the same values.  Samples
+     * behind an item's end are left as the other contour paths leave them.  The contour is written in place behind the
+     * front end's ring (fe_store), which therefore keeps the F0-net's own contour whatever the control was: the control is
+     * applied to the whole window in every call, and is legal with every streaming field above.
+     * Refused (MBX_ERR_INVALID_ARGUMENT): f0_frames together with f0; f0_frames or f0_scale together with
+     * transposition != 1; f0_item_mask without f0_frames.  The values must be finite and positive (not checked).
+     * struct_size may be sizeof(mbx_forward_options) or the offset of f0_frames -- the size the struct had when ABI 11 was
+     * fixed, which means "all three NULL".  Callers built against that layout keep working unchanged, and with all three
+     * NULL the launches and the bits are those of that layout: this is why MBX_ABI_VERSION stays 11. */
+    const float *f0_frames;
+    const float *f0_scale;
+    const int32_t *f0_item_mask;
 } mbx_forward_options;
 
 /* Geometry of the per-layer state (mbx_forward_options.layer_store): floats per slot (0: the handle cannot carry layer

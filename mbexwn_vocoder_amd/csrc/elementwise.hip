@@ -376,7 +376,7 @@ __global__ void frontend_carry_kernel(FrontendCarryArgs a) {
     const bool restore = f < a.first_new;
     float *bufs[3] = {a.cond + ((long long)b * a.frames + f) * a.cond_floats, a.ceps + ((long long)b * a.frames + f) * a.ceps_floats,
                       a.f0 + ((long long)b * a.frames + f) * a.f0_floats};
-    const int sizes[3] = {a.cond_floats, a.ceps_floats, a.f0_floats};
+    const int sizes[3] = {a.cond_floats, a.ceps_floats, a.skip_f0 ? 0 : a.f0_floats};
     int off = 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -393,6 +393,47 @@ __global__ void frontend_carry_kernel(FrontendCarryArgs a) {
 void launch_frontend_carry(const FrontendCarryArgs &a, int batch, hipStream_t stream) {
     if (batch <= 0 || a.frames <= 0) return;
     hipLaunchKernelGGL(frontend_carry_kernel, dim3(a.frames, batch), dim3(128), 0, stream, a);
+}
+
+// Per-frame pitch control (launch_f0_control): one thread per pulse sample of the item's own frames, in place on the
+// contour.  The two interpolations are lin_interp_kernel's on one channel (frame t towards min(t + 1, rows - 1), weights
+// w0[u] / w1[u]) and must round as mbx_lin_interp does.  The compiler contracts lin_interp_kernel's x[t] * w0[u] + x[tn] * w1[u]
+// into fma(x[t], w0[u], round(x[tn] * w1[u])); next to a second interpolation it would pair the products into packed
+// multiplies and add them unfused instead, so the contraction is written out here
+// (tests/test_gpu_pitch_control.py::test_contour holds the two kernels bit-equal).  The product of base and factor is
+// one float32 multiply.
+__device__ __forceinline__ float lerp_like_lin_interp(float xt, float xn, float w0u, float w1u) {
+    return __fmaf_rn(xt, w0u, __fmul_rn(xn, w1u));
+}
+
+__global__ void f0_control_kernel(const float *frames, const float *scale, const int *mask, const int *n_frames, int max_frames,
+                                  int up, const float *w0, const float *w1, float *f0) {
+    const int b = blockIdx.y;
+    const int rows = item_rows(n_frames, b, 1, max_frames);
+    const long long total = (long long)rows * up;
+    const bool take = frames && (!mask || mask[b] != 0);
+    if (!take && !scale) return;
+    const float *fb = frames ? frames + (long long)b * max_frames : nullptr;
+    const float *sb = scale ? scale + (long long)b * max_frames : nullptr;
+    float *yb = f0 + (long long)b * max_frames * up;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int t = (int)(i / up), u = (int)(i - (long long)t * up);
+        const int tn = min(t + 1, rows - 1);
+        float v;
+        if (take) v = lerp_like_lin_interp(fb[t], fb[tn], w0[u], w1[u]);
+        else v = yb[i];
+        if (sb) v = __fmul_rn(v, lerp_like_lin_interp(sb[t], sb[tn], w0[u], w1[u]));
+        yb[i] = v;
+    }
+}
+
+void launch_f0_control(const float *frames, const float *scale, const int *mask, const int *n_frames, int max_frames, int batch,
+                       int up, const float *w0, const float *w1, float *f0, hipStream_t stream) {
+    if (max_frames <= 0 || batch <= 0 || (!frames && !scale)) return;
+    const long long total = (long long)max_frames * up;
+    const int blocks = (int)min((total + 255) / 256, (long long)2048);
+    hipLaunchKernelGGL(f0_control_kernel, dim3(blocks, batch), dim3(256), 0, stream, frames, scale, mask, n_frames, max_frames, up,
+                       w0, w1, f0);
 }
 
 // Streaming windows kept on the device (mbx_window_advance): every row of `win` (batch, frames * row_floats) moves

@@ -227,9 +227,19 @@ mbx_status mbx_forward_stream(mbx_handle *hd, const float *mel, const int32_t *n
 mbx_status mbx_forward_ex(mbx_handle *hd, const float *mel, const int32_t *n_frames, int32_t batch, int32_t max_frames,
                           const float *noise, float *audio, void *workspace, size_t workspace_bytes,
                           const mbx_forward_options *options, void *hip_stream) {
-    if (!options || options->struct_size != (int32_t)sizeof(mbx_forward_options))
+    // two sizes: the whole struct, or the struct as it was before the per-frame pitch control (f0_frames, f0_scale,
+    // f0_item_mask are then not read: all NULL)
+    const bool has_control = options && options->struct_size == (int32_t)sizeof(mbx_forward_options);
+    if (!options || (!has_control && options->struct_size != (int32_t)offsetof(mbx_forward_options, f0_frames)))
         return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_forward_options ABI mismatch (struct_size)");
     if (!(options->transposition > 0.f)) return fail(MBX_ERR_INVALID_ARGUMENT, "transposition must be positive");
+    const float *f0_frames = has_control ? options->f0_frames : nullptr, *f0_scale = has_control ? options->f0_scale : nullptr;
+    const int32_t *f0_item_mask = has_control ? options->f0_item_mask : nullptr;
+    if (f0_frames && options->f0)
+        return fail(MBX_ERR_INVALID_ARGUMENT, "f0_frames (per mel frame) and f0 (per pulse sample) exclude each other");
+    if ((f0_frames || f0_scale) && options->transposition != 1.f)
+        return fail(MBX_ERR_INVALID_ARGUMENT, "f0_frames / f0_scale need transposition == 1 (put the factor into f0_scale)");
+    if (f0_item_mask && !f0_frames) return fail(MBX_ERR_INVALID_ARGUMENT, "f0_item_mask needs f0_frames");
     if ((!options->layer_carry && options->layer_rows != 0) || options->layer_rows < 0)
         return fail(MBX_ERR_INVALID_ARGUMENT, "layer_rows must be >= 0 and needs layer_carry");
     const LayerOpts lay{options->layer_store, options->layer_store_floats, options->layer_carry, options->layer_rows};
@@ -238,6 +248,9 @@ mbx_status mbx_forward_ex(mbx_handle *hd, const float *mel, const int32_t *n_fra
     ex.st_out = reinterpret_cast<mbx::StreamState *>(options->state_out);
     ex.f0_in = options->f0;
     ex.transposition = options->transposition;
+    ex.f0_frames = f0_frames;
+    ex.f0_scale = f0_scale;
+    ex.f0_item_mask = f0_item_mask;
     ex.active_begin = options->active_begin;
     ex.active_frames = options->active_frames;
     ex.wn_begin = options->wn_begin;

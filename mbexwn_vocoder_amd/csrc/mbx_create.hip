@@ -258,6 +258,7 @@ mbx_status mbx_create(const mbx_config *config, const mbx_tensor *tensors, int32
     // interpolation factors in use
     std::vector<int> ups = {c.cond_lin_upsampling};
     if (c.ps_subband_gain) ups.push_back(c.hop_size);     // the sub-band gains are interpolated by hop_size
+    ups.push_back(c.pulse_per_frame);                     // per-frame pitch control (mbx_forward_options.f0_frames / f0_scale)
     for (int i = 0; i < c.n_f0_ops; ++i)
         if (c.f0_ops[i].kind == MBX_OP_LIN) ups.push_back(c.f0_ops[i].up);
     for (int i = 0; i < c.n_vtf_ops; ++i)

@@ -542,7 +542,7 @@ mbx_status run_norm_mel(ForwardCtx &cx) {
 // custom_pulsed_generator.py:793-800) and F0-net (reference :773-791) are independent chains on the mel input:
 // the n-th convolution of each goes into one launch (launch_conv1d_group; matters at small batch, where the
 // mel-rate convolutions are latency-bound).  Then the extra blocks' conditioning chains, the external F0 contour or the
-// transposition, and the front end's ring.
+// transposition, the front end's ring, and behind it the per-frame pitch control (f0_control_kernel).
 mbx_status run_frontend(ForwardCtx &cx) {
     mbx_handle *hd = cx.hd;
     const mbx_config &c = cx.c;
@@ -551,6 +551,8 @@ mbx_status run_frontend(ForwardCtx &cx) {
     const int B = cx.B, T = cx.T, fe_frames = cx.fe_frames, fe_end = cx.fe_end, cond_cout = cx.cond_cout;
     const long long npulse = cx.npulse;
     const float *mel = cx.mel, *f0_in = ex.f0_in;
+    // per-frame pitch control: every item takes its contour from f0_frames (no mask) = the F0-net does not run
+    const bool no_f0_net = ex.f0_frames && !ex.f0_item_mask;
     hipStream_t stream = cx.stream;
     {
         ScopedEvents ev(hd, PROF_FRONTEND, stream);
@@ -584,7 +586,7 @@ mbx_status run_frontend(ForwardCtx &cx) {
             f0.window_stride(T, c.mel_channels);
             cond.window_stride(T, c.mel_channels);
         }
-        if (f0_in) f0.finished = true;
+        if (f0_in || no_f0_net) f0.finished = true;
         for (;;) {
             mbx::ConvArgs group[3];
             int n = 0;
@@ -612,7 +614,7 @@ mbx_status run_frontend(ForwardCtx &cx) {
             while (cb.next_conv(one)) mbx::launch_conv1d_group(&one, 1, stream);
             if (cb.status != MBX_OK) return cb.status;
         }
-        if (f0_wide && !f0_in)   // pulse_frequency[:, :T * pulse_per_frame] (reference custom_pulsed_generator.py:787)
+        if (f0_wide && !f0_in && !no_f0_net)   // pulse_frequency[:, :T * pulse_per_frame] (reference custom_pulsed_generator.py:787)
             mbx::launch_activation(w.f0_wide, (long long)T * hd->f0_time_factor, cx.n_frames, c.pulse_per_frame, (int)npulse,
                                    B, 1, MBX_ACT_LINEAR, 1.f, 0.f, w.f0, npulse, stream);
     }
@@ -640,7 +642,17 @@ mbx_status run_frontend(ForwardCtx &cx) {
         fc.pos = ex.fe_pos;
         fc.slot_desc = ex.sub_carry;
         fc.first_new = fe_frames ? fe_end - ex.fe_new_frames : 0;
+        fc.skip_f0 = no_f0_net ? 1 : 0;
         mbx::launch_frontend_carry(fc, B, stream);
+    }
+    if (ex.f0_frames || ex.f0_scale) {
+        // per-frame pitch control, in place and behind the ring: the ring keeps the F0-net's own contour, and the control
+        // rows of the whole window are applied in every call, so a frame's ring entry never depends on a control value
+        auto it = hd->lerp.find(c.pulse_per_frame);
+        if (it == hd->lerp.end()) return fail(MBX_ERR_INVALID_ARGUMENT, "interpolation table missing (pulse_per_frame)");
+        ScopedEvents ev(hd, PROF_FRONTEND, stream);
+        mbx::launch_f0_control(ex.f0_frames, ex.f0_scale, ex.f0_item_mask, cx.n_frames, T, B, c.pulse_per_frame, it->second.first,
+                               it->second.second, w.f0, stream);
     }
     return MBX_OK;
 }

@@ -381,6 +381,9 @@ struct ForwardExtras {
     mbx::StreamState *st_out = nullptr;
     const float *f0_in = nullptr;
     float transposition = 1.f;
+    // per-frame pitch control (mbx_forward_options.f0_frames / f0_scale / f0_item_mask): device (batch, max_frames) rows
+    const float *f0_frames = nullptr, *f0_scale = nullptr;
+    const int32_t *f0_item_mask = nullptr;
     int active_begin = 0;
     const int32_t *active_frames = nullptr;
     int wn_begin = 0;

@@ -217,8 +217,17 @@ struct FrontendCarryArgs {
     const int *pos;                   // (batch) ring frame of window frame 0
     const int *slot_desc;             // (batch, 5): [0] = slot of the item (the sub-band carry descriptors)
     int first_new;
+    int skip_f0;                      // 1: the F0 lane is neither read nor written (no F0-net ran: the window's contour is
+                                      // not this call's to copy, and every item takes its contour from f0_frames)
 };
 void launch_frontend_carry(const FrontendCarryArgs &a, int batch, hipStream_t stream);
+// per-frame pitch control (mbx_forward_options.f0_frames / f0_scale / f0_item_mask) in place on the pulse-rate contour
+// f0 (batch, max_frames * up): for the pulse samples of item b's own frames, base = LI(frames[b]) where the item takes
+// the frames (frames given and mask null or mask[b] != 0), the contour as it stands otherwise; f0 = base * LI(scale[b])
+// with scale given.  LI = lin_interp_kernel's arithmetic with the weight vectors w0 / w1 of `up`.  frames, scale:
+// (batch, max_frames) or null; mask: (batch) or null
+void launch_f0_control(const float *frames, const float *scale, const int *mask, const int *n_frames, int max_frames, int batch,
+                       int up, const float *w0, const float *w1, float *f0, hipStream_t stream);
 // device-resident streaming windows: shift every item's window left by step_frames and append the new frames
 void launch_clock_probe(unsigned long long *out, unsigned long long real_ticks, hipStream_t stream);
 bool launch_window_update(float *mel, const float *mel_new, float *noise, const float *noise_new, int batch, int win_frames,

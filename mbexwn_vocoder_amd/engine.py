@@ -116,7 +116,9 @@ class mbx_forward_options(ctypes.Structure):
                 ("layer_store", ctypes.c_void_p), ("layer_store_floats", ctypes.c_int32), ("layer_carry", ctypes.c_void_p),
                 ("layer_rows", ctypes.c_int32), ("fe_store", ctypes.c_void_p), ("fe_ring_frames", ctypes.c_int32),
                 ("fe_pos", ctypes.c_void_p), ("fe_new_frames", ctypes.c_int32), ("fe_margin_frames", ctypes.c_int32),
-                ("fe_end_frames", ctypes.c_int32)]
+                ("fe_end_frames", ctypes.c_int32),
+                # per-frame pitch control; struct_size may also be the offset of f0_frames (all three NULL)
+                ("f0_frames", ctypes.c_void_p), ("f0_scale", ctypes.c_void_p), ("f0_item_mask", ctypes.c_void_p)]
 
 
 class mbx_tensor(ctypes.Structure):
@@ -840,13 +842,20 @@ class MBExWNEngine:
         return ff.value, rr.value, mm.value
 
     def forward(self, mel, n_frames=None, noise=None, out=None, stream_state=None, active=None, wavenet=None, carry=None,
-                layers=None, state_out=None, frontend=None, f0=None, transposition=1.0):
+                layers=None, state_out=None, frontend=None, f0=None, transposition=1.0, f0_frames=None, f0_scale=None,
+                f0_item_mask=None):
         """mel (B,T,80) float32 cuda tensor; n_frames int32 cuda tensor (B,) or None;
         noise (B, T*steps_per_frame) float32 cuda tensor (N(0,1) draw) -> audio (B, T*hop) cuda tensor.
 
         f0: optional external F0 contour, float32 cuda tensor (B, T*pulse_per_frame) in Hz at the pulse rate, used instead
         of the F0-net's (``mbx_forward_options.f0``, reference wavegen_1d.py:546-550); transposition scales the contour, the
         F0-net's or the given one (``mbx_forward_options.transposition``).  Both apply to whole items (no stream_state).
+
+        f0_frames / f0_scale: optional per-frame pitch control, float32 cuda tensors (B, T): Hz and transposition factor, one
+        value per mel frame, brought to the pulse rate by the model's linear interpolator (``mbx_forward_options.f0_frames /
+        f0_scale``); f0_item_mask: optional int32 cuda tensor (B,), 1 = the item takes f0_frames, 0 = it keeps the F0-net
+        (None: every item takes them).  Legal with and without stream_state and the window arguments; not together with f0 /
+        a transposition other than 1.
 
         stream_state: optional int32 cuda tensor (B, 6) holding one ``mbx_stream_state`` per item (see
         streaming.pack_state); the call then returns (audio, state_out) with the carried phase state.
@@ -888,6 +897,7 @@ class MBExWNEngine:
             raise ValueError("active / wavenet / carry / layers describe a streaming window: pass stream_state as well")
         if stream_state is not None and (f0 is not None or transposition != 1.0):
             raise ValueError("f0 / transposition apply to whole items: not with stream_state")
+        control = self._pitch_control(B, T, f0, transposition, f0_frames, f0_scale, f0_item_mask)
         if stream_state is not None:
             if stream_state.dtype != torch.int32 or tuple(stream_state.shape) != (B, 6) or stream_state.device != self.device:
                 raise ValueError("stream_state must be an int32 tensor of shape (batch, 6) on the engine's device")
@@ -955,6 +965,19 @@ class MBExWNEngine:
                     keep.append(fpos)
                     opt.fe_store, opt.fe_ring_frames, opt.fe_pos = ring.data_ptr(), int(ring.shape[1]), fpos.data_ptr()
                     opt.fe_new_frames, opt.fe_margin_frames = int(fnew), int(fmargin)
+                opt.f0_frames, opt.f0_scale, opt.f0_item_mask = (None if cc is None else cc.data_ptr() for cc in control)
+                _check(self._lib.mbx_forward_ex(self._handle, mel.data_ptr(),
+                                                n_frames.data_ptr() if n_frames is not None else None, B, T,
+                                                noise.data_ptr() if noise is not None else None, out.data_ptr(),
+                                                ws.data_ptr(), need, ctypes.byref(opt), self._stream()))
+                self._last_shape = (B, T)
+                return out, state_out
+            if any(cc is not None for cc in control):
+                opt = mbx_forward_options()
+                opt.struct_size = ctypes.sizeof(mbx_forward_options)
+                opt.transposition = 1.0
+                opt.state_in, opt.state_out = stream_state.data_ptr(), state_out.data_ptr()
+                opt.f0_frames, opt.f0_scale, opt.f0_item_mask = (None if cc is None else cc.data_ptr() for cc in control)
                 _check(self._lib.mbx_forward_ex(self._handle, mel.data_ptr(),
                                                 n_frames.data_ptr() if n_frames is not None else None, B, T,
                                                 noise.data_ptr() if noise is not None else None, out.data_ptr(),
@@ -968,12 +991,13 @@ class MBExWNEngine:
                                                 self._stream()))
             self._last_shape = (B, T)
             return out, state_out
-        if f0 is not None or transposition != 1.0:
+        if f0 is not None or transposition != 1.0 or any(cc is not None for cc in control):
             if not transposition > 0.0:
                 raise ValueError("transposition must be positive")
             opt = mbx_forward_options()
             opt.struct_size = ctypes.sizeof(mbx_forward_options)
             opt.transposition = float(transposition)
+            opt.f0_frames, opt.f0_scale, opt.f0_item_mask = (None if cc is None else cc.data_ptr() for cc in control)
             if f0 is not None:
                 if (f0.dtype != torch.float32 or tuple(f0.shape) != (B, T * self.dims.pulse_per_frame) or
                         f0.device != self.device):
@@ -993,6 +1017,25 @@ class MBExWNEngine:
                                      ws.data_ptr(), need, self._stream()))
         self._last_shape = (B, T)
         return out
+
+    def _pitch_control(self, B, T, f0, transposition, f0_frames, f0_scale, f0_item_mask):
+        """The per-frame pitch control of a forward, checked: (f0_frames, f0_scale, f0_item_mask) as contiguous tensors or
+        None.  The combinations mbx_forward_ex refuses raise ValueError here, before the call."""
+        torch = self._torch
+        if f0_frames is not None and f0 is not None:
+            raise ValueError("f0_frames (per mel frame) and f0 (per pulse sample) exclude each other")
+        if (f0_frames is not None or f0_scale is not None) and transposition != 1.0:
+            raise ValueError("f0_frames / f0_scale need transposition == 1: put the factor into f0_scale")
+        if f0_item_mask is not None and f0_frames is None:
+            raise ValueError("f0_item_mask needs f0_frames")
+        for name, rows in (("f0_frames", f0_frames), ("f0_scale", f0_scale)):
+            if rows is not None and (not torch.is_tensor(rows) or rows.dtype != torch.float32 or tuple(rows.shape) != (B, T) or
+                                     rows.device != self.device):
+                raise ValueError(f"{name} must be a float32 tensor of shape ({B}, {T}) on the engine's device")
+        if f0_item_mask is not None and (not torch.is_tensor(f0_item_mask) or f0_item_mask.dtype != torch.int32 or
+                                         tuple(f0_item_mask.shape) != (B,) or f0_item_mask.device != self.device):
+            raise ValueError(f"f0_item_mask must be an int32 tensor of shape ({B},) on the engine's device")
+        return tuple(None if cc is None else cc.contiguous() for cc in (f0_frames, f0_scale, f0_item_mask))
 
     def encode_flac16(self, audio, n_samples, sample_rate=None, wait=True):
         """mbx_encode_flac16: the FLAC frames (``flac.encode`` of the item without its 42-byte header) and max |x| of every

@@ -132,16 +132,54 @@ class MELInverter(object):
         return mell * self.mel_amp_scale
 
     # ------------------------------------------------------------------------------------------
-    def synth_from_mel(self, scaled_mell, noise=None):
+    def synth_from_mel(self, scaled_mell, noise=None, f0=None, transposition=None):
         """(1, T, mel_channels) log-mel -> float32 audio of T*hop_size samples
         (reference mel_inverter.py:151-154; like there, a batch is flattened by ``ravel``).
 
         ``noise`` optionally injects the N(0,1) draw of the noise channel (shape (B, T*steps_per_frame));
-        by default it is drawn on the device, as the reference draws tf.random.normal."""
+        by default it is drawn on the device, as the reference draws tf.random.normal.
+
+        Pitch control (this build): ``f0`` -- (T,) or (B, T) Hz, one value per mel frame, replaces the F0-net's contour;
+        ``transposition`` -- a factor on the contour, a scalar (the ``transposition_factor`` of ``infer_components``, same
+        bits) or one value per mel frame.  Per-frame values are brought to the pulse rate by the model's linear
+        interpolator (``mbx_forward_options.f0_frames / f0_scale``); they must be finite and positive."""
         self._calibrate_if_pending(scaled_mell)
+        if f0 is not None or transposition is not None:
+            return self._synth_with_pitch(scaled_mell, noise, f0, transposition)
         syn_audio = self.model.infer(scaled_mell, sigma=None, synth_length=scaled_mell.shape[1] * self.hop_size,
                                      noise=noise).numpy()
         return syn_audio.ravel()
+
+    def _synth_with_pitch(self, scaled_mell, noise, f0, transposition):
+        import torch
+        model = self.model
+        n_frames = int(scaled_mell.shape[1])
+        mel, noise = model._prepare(scaled_mell, n_frames * self.hop_size, noise)
+        B, T = int(mel.shape[0]), int(mel.shape[1])
+
+        def rows(values, name):
+            values = np.asarray(values, dtype=np.float32)
+            if not (np.all(np.isfinite(values)) and np.all(values > 0)):
+                raise ValueError(f"{name} must be finite and positive")
+            if values.ndim == 0:
+                return values
+            values = values.reshape(-1, values.shape[-1])
+            if values.shape[1] != T or values.shape[0] not in (1, B):
+                raise ValueError(f"{name} must hold one value per mel frame ({T})")
+            return torch.as_tensor(np.array(np.broadcast_to(values, (B, T))), device=model.device)
+
+        f0_rows = None if f0 is None else rows(f0, "f0")
+        if f0_rows is not None and not torch.is_tensor(f0_rows):
+            raise ValueError(f"f0 must hold one value per mel frame ({T})")
+        scale = None if transposition is None else rows(transposition, "transposition")
+        if scale is None or torch.is_tensor(scale):
+            audio = model.forward(mel, noise=noise, f0_frames=f0_rows, f0_scale=scale)
+        elif f0_rows is None:                                # a scalar: the whole-item option, as infer_components applies it
+            audio = model.forward(mel, noise=noise, transposition=float(scale))
+        else:
+            audio = model.forward(mel, noise=noise, f0_frames=f0_rows,
+                                  f0_scale=torch.full((B, T), float(scale), dtype=torch.float32, device=model.device))
+        return audio[:, :n_frames * self.hop_size].cpu().numpy().ravel()
 
     def _calibrate_if_pending(self, scaled_mell):
         if self._calibrate_pending:

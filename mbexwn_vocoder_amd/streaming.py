@@ -155,6 +155,7 @@ class _Stream:
         self.state = (0.0, 0.0, 0)
         self.state_frame = 0
         self.ticks = 0            # chunks emitted so far: position in the synthesizer's tick schedule
+        self.f0_mode = "net"      # "frames": the contour comes from push(f0=...) instead of the F0-net
 
 
 class StreamingSynthesizer:
@@ -217,6 +218,15 @@ class StreamingSynthesizer:
         self._in_cap = 256            # frames per row (grows on demand)
         self._in_mel = np.zeros((0, self._in_cap, self.dims.mel_channels), dtype=np.float32)
         self._in_noise = np.zeros((0, self._in_cap, self.dims.steps_per_frame), dtype=np.float32)
+        # per-frame pitch control of every stream, next to its frames: F0 in Hz ("frames" streams; 1 where none was given --
+        # never read there) and the transposition factor (1 where none was given)
+        self._in_f0 = np.ones((0, self._in_cap), dtype=np.float32)
+        self._in_scale = np.ones((0, self._in_cap), dtype=np.float32)
+        # Sticky: set by the first "frames" stream or the first transposition other than 1.  Until then a tick passes none
+        # of the control arguments (the launch sequence and the captured graphs of a synthesizer that only resynthesises are
+        # unchanged); from then on every tick passes the control rows of its whole windows -- factor 1 and mask 0 for the
+        # streams without control, which changes no bit of theirs (the interpolated factor is exactly 1).
+        self._control = False
         # The Winograd form of the dilated convolution pairs outputs t and t+d inside blocks of 2d steps counted from
         # the first row of the item; a window that starts on a multiple of 2*d_max steps pairs exactly like the offline
         # run, which keeps the streamed audio bit-identical (any other start is equal up to float32 rounding only).
@@ -255,19 +265,28 @@ class StreamingSynthesizer:
 
     def _grow_inputs(self, slots, cap):
         """Make the shared input buffers at least (slots, cap frames) large, keeping their contents."""
-        old_mel, old_noise = self._in_mel, self._in_noise
+        old_mel, old_noise, old_f0, old_scale = self._in_mel, self._in_noise, self._in_f0, self._in_scale
         if slots <= old_mel.shape[0] and cap <= self._in_cap:
             return
         slots, cap = max(slots, old_mel.shape[0]), max(cap, self._in_cap)
         self._in_mel = np.zeros((slots, cap, self.dims.mel_channels), dtype=np.float32)
         self._in_noise = np.zeros((slots, cap, self.dims.steps_per_frame), dtype=np.float32)
+        self._in_f0 = np.ones((slots, cap), dtype=np.float32)
+        self._in_scale = np.ones((slots, cap), dtype=np.float32)
         self._in_mel[:old_mel.shape[0], :self._in_cap] = old_mel
         self._in_noise[:old_noise.shape[0], :self._in_cap] = old_noise
+        self._in_f0[:old_f0.shape[0], :self._in_cap] = old_f0
+        self._in_scale[:old_scale.shape[0], :self._in_cap] = old_scale
         self._in_cap = cap
 
-    def open(self, stream_id):
+    def open(self, stream_id, f0="net"):
+        """``f0``: "net" -- the stream's contour is the F0-net's; "frames" -- it is given from outside, one value in Hz per
+        mel frame with every ``push`` (an F0 tracker's output)."""
+        if f0 not in ("net", "frames"):
+            raise ValueError('f0 must be "net" or "frames"')
         self._leave_steady()
         st = _Stream()
+        st.f0_mode = f0
         import torch
         rows = (self.sr_left + self.sr_right) * self.dims.steps_per_frame
         if not self._free_slots:
@@ -293,6 +312,8 @@ class StreamingSynthesizer:
             self._grow_inputs(n_new, self._in_cap)
         st.slot = self._free_slots.pop()
         self.streams[stream_id] = st
+        if f0 == "frames":
+            self._control = True
 
     def close(self, stream_id):
         """Forget a finished stream (its slot of the sub-band store is reused)."""
@@ -300,12 +321,33 @@ class StreamingSynthesizer:
         st = self.streams.pop(stream_id)
         self._free_slots.append(st.slot)
 
-    def push(self, stream_id, mel_frames, noise=None, last=False):
-        """Append mel frames (n, mel_channels) and the matching N(0,1) draw (n*steps_per_frame,) to a stream."""
+    def push(self, stream_id, mel_frames, noise=None, last=False, f0=None, transposition=None):
+        """Append mel frames (n, mel_channels) and the matching N(0,1) draw (n*steps_per_frame,) to a stream.
+
+        ``f0``: (n,) Hz, one value per pushed frame -- required for a stream opened with ``f0="frames"``, refused for any
+        other.  ``transposition``: factor on the stream's contour, a scalar or (n,) values (default 1).  Both are brought to
+        the pulse rate by the model's linear interpolator, towards the next frame's value; they must be finite and
+        positive."""
         st = self.streams[stream_id]
         mel_frames = np.asarray(mel_frames, dtype=np.float32).reshape(-1, self.dims.mel_channels)
         n = mel_frames.shape[0]
         spf = self.dims.steps_per_frame
+        if (f0 is not None) != (st.f0_mode == "frames"):
+            raise ValueError('f0 goes with every push of a stream opened with f0="frames", and with no other stream')
+        if f0 is not None:
+            f0 = np.asarray(f0, dtype=np.float32).reshape(-1)
+            if f0.shape[0] != n:
+                raise ValueError("f0 must hold one value per pushed mel frame")
+            if not (np.all(np.isfinite(f0)) and np.all(f0 > 0)):
+                raise ValueError("f0 must be finite and positive")
+        if transposition is not None:
+            transposition = np.asarray(transposition, dtype=np.float32)
+            if transposition.ndim > 0:
+                transposition = transposition.reshape(-1)
+                if transposition.shape[0] != n:
+                    raise ValueError("transposition must be a scalar or hold one value per pushed mel frame")
+            if not (np.all(np.isfinite(transposition)) and np.all(transposition > 0)):
+                raise ValueError("transposition must be finite and positive")
         if self.dims.noise_sigma:
             if noise is None:
                 raise ValueError("noise is required (explicit input of the path)")
@@ -320,6 +362,8 @@ class StreamingSynthesizer:
             if drop > 0:
                 self._in_mel[st.slot, :live] = self._in_mel[st.slot, drop:drop + live]
                 self._in_noise[st.slot, :live] = self._in_noise[st.slot, drop:drop + live]
+                self._in_f0[st.slot, :live] = self._in_f0[st.slot, drop:drop + live]
+                self._in_scale[st.slot, :live] = self._in_scale[st.slot, drop:drop + live]
                 st.base = keep_from
             if st.have - st.base + n > self._in_cap:
                 self._grow_inputs(self._in_mel.shape[0], max(2 * self._in_cap, st.have - st.base + n))
@@ -327,6 +371,13 @@ class StreamingSynthesizer:
         self._in_mel[st.slot, col:col + n] = mel_frames
         if self.dims.noise_sigma:
             self._in_noise[st.slot, col:col + n] = noise
+        self._in_f0[st.slot, col:col + n] = 1.0 if f0 is None else f0
+        self._in_scale[st.slot, col:col + n] = 1.0 if transposition is None else transposition
+        if not self._control and transposition is not None and np.any(transposition != 1.0):
+            # the first control this synthesizer sees: a steady run recorded without the control arguments is left and
+            # captured anew
+            self._leave_steady()
+            self._control = True
         st.have += n
         st.closed = st.closed or last
         self._inputs_changed = True       # cached per-stream vectors of a run of replayed ticks are stale
@@ -473,6 +524,15 @@ class StreamingSynthesizer:
             states[bb, 2:5] = st.state[2], (st.state_frame - ws) * ppf, (nxt - ws) * ppf if nxt < we else -1
             next_state_frame.append(nxt)
         states[:, :2] = st_f.view(np.int32)                   # one mbx_stream_state per item (pack_state)
+        control = self._control
+        if control:
+            # the control rows of the whole windows (the frames behind an item's end are not read)
+            f0w = np.ones((B, tpad), dtype=np.float32)
+            scw = np.ones((B, tpad), dtype=np.float32)
+            for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
+                f0w[bb, :we - ws] = self._in_f0[st.slot, ws - st.base:we - st.base]
+                scw[bb, :we - ws] = self._in_scale[st.slot, ws - st.base:we - st.base]
+            f0_mask = np.asarray([st.f0_mode == "frames" for _, st, _ in todo], dtype=np.int32)
         dev = self.engine.device
         mel_d = torch.as_tensor(mel, device=dev)
         noise_d = torch.as_tensor(noise, device=dev) if self.dims.noise_sigma else None
@@ -480,10 +540,17 @@ class StreamingSynthesizer:
         use_fe = self.fe_carry and self.carry and tpad <= self._fe_ring
         fpos = np.asarray([ws % self._fe_ring for ws, _ in windows], dtype=np.int32)
         parts = [states.ravel(), desc.ravel(), ldesc.ravel(), nfr, act, wn if wn is not None else act, fpos]
+        if control:                                           # ... and the control rows with them (floats bit-cast)
+            parts += [f0_mask, f0w.ravel().view(np.int32), scw.ravel().view(np.int32)]
         ints_d = torch.as_tensor(np.concatenate(parts), device=dev)
         cuts = np.cumsum([0] + [pp.size for pp in parts])
         states_d, desc_d, ldesc_d, nfr_d, act_d, wn_d, fpos_d = (ints_d[cuts[ii]:cuts[ii + 1]] for ii in range(7))
         states_d, desc_d, ldesc_d = states_d.view(B, 6), desc_d.view(B, 5), ldesc_d.view(B, 3)
+        pitch = {}
+        if control:
+            pitch = {"f0_item_mask": ints_d[cuts[7]:cuts[8]],
+                     "f0_frames": ints_d[cuts[8]:cuts[9]].view(torch.float32).view(B, tpad),
+                     "f0_scale": ints_d[cuts[9]:cuts[10]].view(torch.float32).view(B, tpad)}
         self.last_tick_frames = int(nfr.sum())
         if self.time_device:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -499,7 +566,8 @@ class StreamingSynthesizer:
             wavenet=(wa, wn_d, int(wn.max())) if wn is not None else None,
             carry=(self._store, desc_d) if self.carry else None,
             layers=(self._layer_store, ldesc_d, layer_rows) if self.layer_carry else None,
-            frontend=(self._fe_store, fpos_d, 0, 0) if use_fe else None)      # whole window computed, every frame kept
+            frontend=(self._fe_store, fpos_d, 0, 0) if use_fe else None,      # whole window computed, every frame kept
+            **pitch)
         if self.time_device:
             ev1.record()
             ev1.synchronize()
@@ -526,7 +594,9 @@ class StreamingSynthesizer:
                 "layer_rows": layer_rows, "act": act.copy(), "wn": wn.copy(), "nfr": nfr.copy(), "desc": desc.copy(),
                 "ldesc": ldesc.copy(), "state_consts": states[:, 3:5].copy(), "rel0": st0.emitted - ws0, "use_fe": use_fe,
                 "frames": self.last_tick_frames, "active_frames": self.last_tick_active_frames,
-                "wavenet_frames": self.last_tick_wavenet_frames, "ws0": ws0}
+                "wavenet_frames": self.last_tick_wavenet_frames, "ws0": ws0, "control": control}
+            if control:
+                steady_ctx["f0_mask"] = f0_mask.copy()
         result = {}
         for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
             a0 = (st.emitted - ws) * hop - lo
@@ -651,13 +721,23 @@ class StreamingSynthesizer:
         mel_win, noise_win = run["win"]
         shared = run["shared"]
         n_mel, n_noise = B * chunk * dims.mel_channels, (B * chunk * spf if use_noise else 0)
-        # one pinned host buffer / one device buffer for everything a tick uploads: new mel frames, new noise, phase states
-        stage_host = torch.empty(n_mel + n_noise + B * 7, dtype=torch.float32).pin_memory()
+        # one pinned host buffer / one device buffer for everything a tick uploads: new mel frames, new noise, phase states,
+        # ring positions and -- once the synthesizer has seen pitch control -- the control rows of the whole windows
+        # (B, tpad) each: small next to the mel frames, and the window they belong to is known to the host anyway, so they
+        # need no device-resident window and no second move launch
+        n_ctl = B * tpad if ctx["control"] else 0
+        stage_host = torch.ones(n_mel + n_noise + B * 7 + 2 * n_ctl, dtype=torch.float32).pin_memory()
         stage_dev = torch.empty_like(stage_host, device=dev)
         mel_new = stage_dev[:n_mel].view(B, chunk, dims.mel_channels)
         noise_new = stage_dev[n_mel:n_mel + n_noise].view(B, chunk * spf) if use_noise else None
         states_d = stage_dev[n_mel + n_noise:n_mel + n_noise + B * 6].view(torch.int32).view(B, 6)
-        fpos_d = stage_dev[n_mel + n_noise + B * 6:].view(torch.int32)
+        fpos_d = stage_dev[n_mel + n_noise + B * 6:n_mel + n_noise + B * 7].view(torch.int32)
+        pitch = {}
+        if ctx["control"]:
+            n_ints = n_mel + n_noise + B * 7
+            pitch = {"f0_frames": stage_dev[n_ints:n_ints + n_ctl].view(B, tpad),
+                     "f0_scale": stage_dev[n_ints + n_ctl:].view(B, tpad),
+                     "f0_item_mask": torch.as_tensor(ctx["f0_mask"], device=dev)}
         # front end: the window gained `chunk` frames and the last fe_right frames of the window before were inexact: the
         # sub-nets run on the last chunk + fe_right (+ their reach) frames in front of the window's end (frame ctx["T"] of the
         # buffer: fe_end_frames), everything in front of that comes from the ring
@@ -681,7 +761,7 @@ class StreamingSynthesizer:
                         layers=(self._layer_store, ints["ldesc"].view(B, 3), ctx["layer_rows"]),
                         frontend=(self._fe_store, fpos_d, fe_new if use_fe else 0, fe_margin if use_fe else 0, ctx["T"])
                         if ctx["use_fe"] else None,
-                        out=audio_buf, state_out=state_out)
+                        out=audio_buf, state_out=state_out, **pitch)
             # the emitted samples of every stream: one strided device-to-host copy (no device-side gather in between)
             eng.emit_rows(audio_buf, ctx["lo"], ctx["hi"] - ctx["lo"], audio_host)
             state_host.copy_(state_out, non_blocking=True)
@@ -689,7 +769,8 @@ class StreamingSynthesizer:
         return {"graph": graph, "stage_host": stage_host, "stage_np": stage_host.numpy(), "n_mel": n_mel,
                 "arange": np.arange(chunk, dtype=np.int64), "n_noise": n_noise, "n_state": n_state,
                 "audio_host": audio_host, "state_host": state_host, "shift": shift, "keep": keep,
-                "keep_alive": (stage_dev, ints)}
+                "n_ints": n_state + B * 7, "n_ctl": n_ctl, "arange_win": np.arange(ctx["T"], dtype=np.int64),
+                "keep_alive": (stage_dev, ints, pitch)}
 
     def _graph_tick(self):
         """A steady tick as one graph launch: gather and upload the new frames and the phase states, replay, read the
@@ -733,9 +814,15 @@ class StreamingSynthesizer:
         if gg["n_noise"]:
             np.copyto(stage[gg["n_mel"]:gg["n_state"]].reshape(B, chunk, dims.steps_per_frame),
                       self._in_noise[slots[:, None], cols])
-        ints = stage[gg["n_state"]:].view(np.int32)
+        ints = stage[gg["n_state"]:gg["n_ints"]].view(np.int32)
         states = ints[:B * 6].reshape(B, 6)
         ints[B * 6:] = (emitted - ctx["rel0"]) % self._fe_ring              # ring frame of each window's first frame
+        if gg["n_ctl"]:
+            # the control rows of the whole windows [emitted - rel0, + T): one gather per row
+            wcols = (emitted - ctx["rel0"] - base)[:, None] + gg["arange_win"]
+            n_ints, n_ctl, tpad, T = gg["n_ints"], gg["n_ctl"], run["tpad"], ctx["T"]
+            stage[n_ints:n_ints + n_ctl].reshape(B, tpad)[:, :T] = self._in_f0[slots[:, None], wcols]
+            stage[n_ints + n_ctl:].reshape(B, tpad)[:, :T] = self._in_scale[slots[:, None], wcols]
         states[:, :3] = run["state_v"][:, :3]
         states[:, 3:5] = ctx["state_consts"]
         states[:, 5] = 0

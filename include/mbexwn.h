@@ -295,7 +295,9 @@ typedef struct {
 #define MBX_GATE_K_F43_STRIDED 6     /* F(4,3) over d / 16 interleaved sub-sequences (d > 16), 256-row blocks */
 #define MBX_GATE_K_F43_STRIDED_PSPLIT 7
 #define MBX_GATE_K_FOLDED_START 8    /* wn_gate0_kernel: layer 0 with the start convolution folded in */
-#define MBX_GATE_K_SPLIT_F16 9       /* wn_gate_f16_kernel (opt-in split half precision) */
+#define MBX_GATE_K_SPLIT_F16 9       /* wn_gate_f16_kernel<true> (opt-in split half precision): hidden state read as fp16 planes, 256 x 64 */
+#define MBX_GATE_K_SPLIT_F16_WIDE 10 /* wn_gate_f16w_kernel: the planes kernel of large launches, 256 rows x pairs of column tiles */
+#define MBX_GATE_K_SPLIT_F16_F32H 11 /* wn_gate_f16_kernel<false>: float32 hidden state split in the kernel (no planes in front) */
 mbx_status mbx_conv_form(const mbx_handle *handle, mbx_conv_form_info *info);
 
 /* ABI 11: which residual/skip and tail kernels the most recent forward ran (the gate kernels: mbx_conv_form_info.gate_kernel). */

@@ -700,8 +700,8 @@ mbx_status run_gate_layer(ForwardCtx &cx, const mbx::ConvArgs &g, const WnLayerT
             gh.h_split_ld = (C + 7) / 8 * 8;
             gh.h_split_bstride = cx.nsteps * (long long)gh.h_split_ld;
         }
-        done = mbx::launch_wn_gate_f16(gh, stream);
-        if (done) ran_kernel = MBX_GATE_K_SPLIT_F16;
+        ran_kernel = mbx::launch_wn_gate_f16(gh, stream);       // which of the three split kernels ran (0: the layer does not fit)
+        done = ran_kernel != MBX_GATE_K_NONE;
         if (cx.planes_only && !(done && cx.planes_valid))
             return fail(MBX_ERR_INVALID_ARGUMENT, "split precision: a gate layer did not take the plane-only hidden state");
     }

@@ -121,7 +121,7 @@ bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream)
 bool launch_wn_gate_winograd2w(const ConvArgs &a, hipStream_t stream);
 // the dilated convolution + gate in split half precision, direct form (wn_gate_f16.hip; opt-in, mbx_config.wn_precision);
 // a.w = image of engine.pack_gate_f16_weights (ceil(C/32), ceil(C/32), 6144)
-bool launch_wn_gate_f16(const ConvArgs &a, hipStream_t stream);
+int launch_wn_gate_f16(const ConvArgs &a, hipStream_t stream);   // MBX_GATE_K_SPLIT_F16* of the kernel launched, 0: does not fit
 // First WaveNet layer with the start convolution folded into it (wn_gate0.hip)
 struct Gate0Args {
     const float *pulse;       // (batch, rows * pulse_channels): the excitation, folded to pulse_channels per row

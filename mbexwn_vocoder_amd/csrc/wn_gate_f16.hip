@@ -508,8 +508,12 @@ __global__ __launch_bounds__(512, 1) void wn_gate_f16w_kernel(ConvArgs p, int lo
 }
 
 // a.w must point at the image of engine.pack_gate_f16_weights (ceil(C/32) column tiles, ceil(C/32) steps, 6144 floats);
-// returns false if the layer does not fit (the caller then runs the float32 kernels)
-bool launch_wn_gate_f16(const ConvArgs &a, hipStream_t stream) {
+// returns the MBX_GATE_K_* of the instantiation it launched -- MBX_GATE_K_SPLIT_F16_WIDE: wn_gate_f16w_kernel, MBX_GATE_K_SPLIT_F16:
+// wn_gate_f16_kernel<true>, MBX_GATE_K_SPLIT_F16_F32H: wn_gate_f16_kernel<false> -- or MBX_GATE_K_NONE (0) if the layer does not
+// fit (the caller then runs the float32 kernels).  wn_gate_f16_kernel<false> reads the float32 hidden state: it runs where the
+// res/skip layer in front left no planes, which a legal tensor table reaches -- one without wn.res_skip_0.fold_start_f16 runs
+// layer 0's res/skip in float32 and layer 1's gate here (tests/test_gpu_wavenet_stages.py: speech-split-f32h).
+int launch_wn_gate_f16(const ConvArgs &a, hipStream_t stream) {
     int log2d = 0;
     while ((1 << log2d) < a.dil) ++log2d;
     const bool ok = a.ks == 3 && (1 << log2d) == a.dil && a.dil <= GH_HALO && a.pad_l == a.dil && a.pad_mode == 0 &&
@@ -520,11 +524,11 @@ bool launch_wn_gate_f16(const ConvArgs &a, hipStream_t stream) {
                     a.cond_phase == 0 && a.out_rows == 0 && a.max_rows < (1 << 24) &&
                     (!a.h_split || (a.h_split_ld % 8 == 0 && a.h_split_ld >= a.channels && a.h_split_bstride % 4 == 0 &&
                                     (uintptr_t)a.h_split % 16 == 0));
-    if (!ok) return false;
+    if (!ok) return MBX_GATE_K_NONE;
     // the attribute belongs to the (function, device) pair: a process may hold handles on several devices
     static unsigned long long attr_devices = 0;       // bit d: set for device d (devices >= 64: set at every launch)
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
+    if (hipGetDevice(&dev) != hipSuccess) return MBX_GATE_K_NONE;
     const bool attr_set = dev >= 0 && dev < 64 && ((attr_devices >> dev) & 1ull);
     static bool gw_ok = false;
     if (!attr_set) {
@@ -534,7 +538,7 @@ bool launch_wn_gate_f16(const ConvArgs &a, hipStream_t stream) {
                                 GH_LDS_FLOATS * (int)sizeof(float)) != hipSuccess ||
             hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_f16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 GH_LDS_FLOATS * (int)sizeof(float)) != hipSuccess)
-            return false;
+            return MBX_GATE_K_NONE;
         if (dev >= 0 && dev < 64) attr_devices |= 1ull << dev;
     }
     ConvArgs r = a;
@@ -548,11 +552,14 @@ bool launch_wn_gate_f16(const ConvArgs &a, hipStream_t stream) {
     if (a.h_split && gw_ok && (a.cin + GH_BK - 1) / GH_BK >= 2 && blocks2 >= 4 * 256) {
         r.n_tiles = (r.n_tiles + 1) / 2;
         hipLaunchKernelGGL(wn_gate_f16w_kernel, dim3((unsigned)blocks2), dim3(512), GW_LDS_FLOATS * sizeof(float), stream, r, log2d);
-    } else if (a.h_split)
+        return MBX_GATE_K_SPLIT_F16_WIDE;
+    }
+    if (a.h_split) {
         hipLaunchKernelGGL(wn_gate_f16_kernel<true>, dim3((unsigned)blocks), dim3(512), GH_LDS_FLOATS * sizeof(float), stream, r, log2d);
-    else
-        hipLaunchKernelGGL(wn_gate_f16_kernel<false>, dim3((unsigned)blocks), dim3(512), GH_LDS_FLOATS * sizeof(float), stream, r, log2d);
-    return true;
+        return MBX_GATE_K_SPLIT_F16;
+    }
+    hipLaunchKernelGGL(wn_gate_f16_kernel<false>, dim3((unsigned)blocks), dim3(512), GH_LDS_FLOATS * sizeof(float), stream, r, log2d);
+    return MBX_GATE_K_SPLIT_F16_F32H;
 }
 
 }  // namespace mbx

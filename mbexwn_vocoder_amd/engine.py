@@ -88,7 +88,8 @@ class mbx_conv_form_info(ctypes.Structure):
 
 
 GATE_KERNEL_NAMES = {0: "none", 1: "direct", 2: "f23", 3: "f43", 4: "f43_psplit", 5: "f43_hsplit", 6: "f43_strided",
-                     7: "f43_strided_psplit", 8: "folded_start", 9: "split_f16"}
+                     7: "f43_strided_psplit", 8: "folded_start", 9: "split_f16", 10: "split_f16_wide",
+                     11: "split_f16_f32h"}
 
 
 class mbx_kernel_report_info(ctypes.Structure):

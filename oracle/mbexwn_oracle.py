@@ -393,7 +393,10 @@ class OracleModel:
         ``taps`` (test instrument, one channel group only): {"gate_out": f, "res_skip": f}, each called as f(layer, array) with the
         gate output that the layer's res/skip convolution is about to read (B, T, C) -- for the last layer that is the input of
         the end convolution's last share, the tail's input where the skip path is folded -- or with the res/skip convolution's
-        output (B, T, 2 C: residual columns, then skip columns; the last layer: C skip columns); what it returns replaces it."""
+        output (B, T, 2 C: residual columns, then skip columns; the last layer: C skip columns); what it returns replaces it.
+        "gate_z": called as f(layer, hidden, cond, z) with the inputs of the layer's dilated convolution -- the hidden state
+        (B, T, C) and the interpolated conditioning (B, T, 2 C) -- and the pre-activation z = conv(hidden) + cond they gave; what it
+        returns replaces z (an emulation of another arithmetic for the K = 3 C contraction plugs in here)."""
         taps = taps or {}
         assert not taps or int(self.wn.get("n_ch_groups", 1)) == 1
         C = self.wn["n_channels"] if channels is None else channels
@@ -414,6 +417,8 @@ class OracleModel:
                 sfx = f"g{gg}" if gg else ""
                 w, b = self.weight(f"{prefix}conv1D_{ll}{sfx}")
                 z = self.wn_conv(started[gg], w, b, dilation=self.dilation(ll)) + cond[gg]   # :307-309
+                if "gate_z" in taps:
+                    z = taps["gate_z"](ll, started[gg], cond[gg], z)
                 zt = z[..., :Cg]
                 act = self.wn.get("activation", "gtu")
                 if act == "gtu":                                                  # :312-318

@@ -122,12 +122,13 @@ def test_gate_kernel_codes_match_the_header():
     assert sorted(codes.values()) == sorted(engine.GATE_KERNEL_NAMES)
     want = {"NONE": "none", "DIRECT": "direct", "F23": "f23", "F43": "f43", "F43_PSPLIT": "f43_psplit", "F43_HSPLIT": "f43_hsplit",
             "F43_STRIDED": "f43_strided", "F43_STRIDED_PSPLIT": "f43_strided_psplit", "FOLDED_START": "folded_start",
-            "SPLIT_F16": "split_f16"}
+            "SPLIT_F16": "split_f16", "SPLIT_F16_WIDE": "split_f16_wide", "SPLIT_F16_F32H": "split_f16_f32h"}
     assert {engine.GATE_KERNEL_NAMES[vv]: kk for kk, vv in codes.items()} == {vv: kk for kk, vv in want.items()}
     assert int(re.search(r"#define MBX_ABI_VERSION (\d+)", header).group(1)) == engine.MBX_ABI_VERSION == 11
     # bench.py's executed-FLOP factors know every kernel that multiplies
     import bench
-    assert set(bench.GATE_EXECUTED) == set(engine.GATE_KERNEL_NAMES.values()) - {"none", "folded_start", "split_f16"}
+    assert set(bench.GATE_EXECUTED) == set(engine.GATE_KERNEL_NAMES.values()) - {"none", "folded_start", "split_f16", "split_f16_wide",
+                                                                                     "split_f16_f32h"}
 
 
 def test_resskip_and_tail_kernel_codes_match_the_header():

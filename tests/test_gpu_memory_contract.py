@@ -47,6 +47,7 @@ E2E_TOL = parity.E2E_TOL
 # ------------------------------------------------------------------------------------------------------------------------
 WN_IDS = ["c12-f43", "c36-f43", "speech-direct", "speech-f23", "speech-f43", "speech-f43-invariant", "speech-f43-hsplit",
           "speech-rs-nowave", "speech-rs-split2", "lin5-f43", "groups2-f43", "causal-auto", "speech-keep-skip", "speech-split",
+          "speech-split-f32h",
           "voice-f43", "deep12-f43", "deep12-f43-invariant", "deep12-split", "large-f43", "large-split",
           # C + n_out one column pair past a multiple of 32: a last pair of two valid columns under the wide and the wave kernel
           "c292-invariant", "c324-rs-split2"]
@@ -249,7 +250,8 @@ def _engine(key, model, kwargs):
     from mbexwn_vocoder_amd.engine import MBExWNEngine
     if key not in _ENGINES:
         cfg, raw, wt = build_case(*model)
-        _ENGINES[key] = (MBExWNEngine(cfg, raw, wt, **kwargs), cfg, raw, wt)
+        with twn.tensor_table_of(key):
+            _ENGINES[key] = (MBExWNEngine(cfg, raw, wt, **kwargs), cfg, raw, wt)
     return _ENGINES[key]
 
 

@@ -16,8 +16,16 @@ pair past a multiple of 32 (C = 292, 324: the last pair holds two valid columns)
 (C = 324, 340) and on a pair boundary (C = 352), a last 16-channel block of 4 channels in the tail (C = 68, 132, 196, 324), the
 first C behind the wave, wide and wn_tail2 kernels (C = 356) and five 128-column tiles (C = 512).
 
+The split-half-precision path (precision="split_f16": wn_gate_f16.hip, wn_resskip_f16.hip) is a second implementation of both
+contractions with three gate kernels (the planes kernel, the large-launch kernel over pairs of column tiles, the kernel that
+splits a float32 hidden state itself) and a res/skip kernel; the "*-split" cases put each at the channel counts where ITS tiles
+are ragged (C % 32 != 0 under an odd tile count, C % 8 == 4: plane padding, C + 30 = 382, C <= 162), on the model variants, in
+the mixed mode under float32 gates, and hold it to the same bar; what the mode's arithmetic alone costs is in
+test_split_reference.py.
+
 The padding contract of include/mbexwn.h ("every boundary op honours the item's own length") is held bit for bit: the same
 ragged batch with its padding frames of mel and noise at 0, 1e30 and NaN."""
+import contextlib
 import json
 
 import numpy as np
@@ -38,7 +46,22 @@ LARGE_CHECK = [LARGE.index(max(LARGE)), LARGE.index(min(LARGE)), LARGE.index(560
 # shape starts at 2 304
 LARGE6 = [490, 3, 260, 77, 411, 128]
 LARGE6_CHECK = [LARGE6.index(max(LARGE6)), LARGE6.index(min(LARGE6)), LARGE6.index(260)]
-LENGTHS = {"ragged": (RAGGED, None), "deep": (DEEP, None), "large": (LARGE, LARGE_CHECK), "large6": (LARGE6, LARGE6_CHECK)}
+# C = 68 under the large-launch split gate kernel (wn_gate_f16w_kernel: 4 x 256 blocks of 256 rows x a PAIR of column tiles): 3
+# column tiles = 2 pairs, so 512 row tiles: 8 items x 65 (the oracle at C = 68 is cheap: three items, about a second)
+LARGE8 = [820, 3, 411, 77, 640, 128, 260, 700]
+LARGE8_CHECK = [0, 1, 2]
+# the shortest set that takes wn_gate_f16w_kernel at C = 340 (6 pairs): 8 items x 22 row tiles = 176 -> 1056 blocks >= 1024
+WIDE8 = [280, 1, 52, 7, 13, 201, 6, 25]
+LENGTHS = {"ragged": (RAGGED, None), "deep": (DEEP, None), "large": (LARGE, LARGE_CHECK), "large6": (LARGE6, LARGE6_CHECK),
+           "large8": (LARGE8, LARGE8_CHECK)}
+
+
+def split_gate_blocks(C, lengths, wide=True):
+    """Blocks of a split gate launch as launch_wn_gate_f16 counts them (row tiles of 256 rows rounded up to the 8 XCDs x column
+    tiles, or pairs of them): the wide kernel runs from 4 * 256 pair blocks."""
+    tiles = ((max(lengths) * 20 + 255) // 256) * len(lengths)
+    nt = (C + 31) // 32
+    return 8 * ((tiles + 7) // 8) * ((nt + 1) // 2 if wide else nt)
 
 _WN = "mbexwn_config:pp_mod_subnet:"
 GEOMETRIES = {
@@ -63,6 +86,8 @@ GEOMETRIES = {
 F43 = {"conv_form": "f43"}
 INVARIANT = {"conv_form": "f43", "batch_invariant": True}
 FS, PS, HS = "folded_start", "f43_psplit", "f43_hsplit"
+SP, SPW, SPF = "split_f16", "split_f16_wide", "split_f16_f32h"
+SPLIT = dict(F43, precision="split_f16")
 
 
 def _split(ss):
@@ -112,7 +137,29 @@ CASES = [
     ("deep12-split", "deep12", "deep", dict(F43, precision="split_f16"), {FS, "split_f16", "f43_strided_psplit", "direct"}),
     # large launches
     ("large-f43", "speech", "large", F43, {FS, "f43"}),
-    ("large-split", "speech", "large", dict(F43, precision="split_f16"), {FS, "split_f16"}),
+    ("large-split", "speech", "large", dict(F43, precision="split_f16"), {FS, SPW}),
+    # ---- split half precision at every channel edge (3 layers) and model variant; small launches: the planes kernel ----
+    # C % 32 != 0 (a partial last column tile and K step), C % 8 == 4 (plane padding), C + 30 = 382 (the largest res/skip
+    # launch), C <= 162 (the second column-half block of the res/skip kernel stores little or nothing)
+    *[(f"c{C}-split", f"c{C}", "ragged", SPLIT, {FS, SP}) for C in (340, 324, 292, 352, 68, 132, 36)],
+    ("voice-split", "voice", "ragged", SPLIT, {FS, SP}),
+    ("gfu-split", "gfu", "ragged", SPLIT, {FS, SP}),
+    ("gsu-split", "gsu", "ragged", SPLIT, {FS, SP}),
+    ("groups2-split", "groups2", "ragged", SPLIT, {FS, SP}),
+    ("lin20-split", "lin20", "ragged", SPLIT, {FS, SP}),
+    # a tensor table without wn.res_skip_0.fold_start_f16: layer 0's res/skip runs in float32 and leaves no planes, layer 1's
+    # gate splits the float32 hidden state itself (wn_gate_f16_kernel<false>)
+    ("speech-split-f32h", "speech", "ragged", SPLIT, {FS, SPF, SP}),
+    # mixed mode: split res/skip layers under float32 gates, no planes.  A kept start convolution leaves layer 0's res/skip to
+    # the float32 policy (L - 2 split layers); causal padding under a pinned form folds the start, so layer 0 takes its split
+    # image as well (L - 1), and only the gates stay float32
+    ("speech-keep-start-split", "speech", "ragged", dict(SPLIT, keep_start=True), {PS}),
+    ("causal-f43-split", "causal", "ragged", SPLIT, {FS, PS}),
+    # large launches: wn_gate_f16w_kernel with an odd number of column tiles (the last pair's second tile does not exist)
+    ("large6-c340-split", "c340", "large6", SPLIT, {FS, SPW}),
+    ("large6-c324-split", "c324", "large6", SPLIT, {FS, SPW}),
+    ("large6-speech-split", "speech", "large6", SPLIT, {FS, SPW}),
+    ("large8-c68-split", "c68", "large8", SPLIT, {FS, SPW}),
     # ---- the res/skip and tail instantiations (3 layers) ----
     # wide kernel (batch_invariant): 11 pairs with C < 320 -> <11,1,0>; 12 pairs -> <6,2,0>
     *[(f"c{C}-invariant", f"c{C}", "ragged", INVARIANT, {FS, "f43"}) for C in (292, 300, 316, 324, 340, 352)],
@@ -132,7 +179,13 @@ CASES = [
     ("c192-f43", "c192", "ragged", F43, {FS, PS}),
     ("c196-f43", "c196", "ragged", F43, {FS, PS}),
 ]
-PLANES_ONLY = {"speech-split", "l3-split", "large-split"}
+PLANES_ONLY = {"speech-split", "l3-split", "large-split", "voice-split", "gfu-split", "gsu-split", "groups2-split", "lin20-split",
+               "large6-c340-split", "large6-c324-split", "large6-speech-split", "large8-c68-split",
+               *(f"c{C}-split" for C in (340, 324, 292, 352, 68, 132, 36))}
+# the cases built from a tensor table without layer 0's split res/skip image
+NO_START_F16 = {"speech-split-f32h"}
+# split res/skip layers whose layer 0 runs a float32 kernel: {case id: that kernel}; split_f16_layers is L - 2 there, L - 1 elsewhere
+F32_LAYER0 = {"speech-split-f32h": "wave4x3", "speech-keep-start-split": "wave4x3"}
 
 # {case id: (the res/skip kernels its forward must run, its tail kernel)} (engine.RESSKIP_KERNEL_NAMES / TAIL_KERNEL_NAMES).  A
 # model with the skip path folded launches L - 1 res/skip layers; the tail kernel takes the last layer's share.
@@ -155,6 +208,12 @@ KERNELS = {
     "speech-keep-skip": ({P64}, NJ20), "speech-keep-start": ({W43}, NJ20),
     "speech-split": ({"split_f16"}, NJ20), "l3-split": ({"split_f16"}, NJ20), "deep12-split": ({"split_f16"}, NJ20),
     "large-f43": ({"wide11_res10"}, NJ20), "large-split": ({"split_f16"}, NJ20),
+    "c340-split": ({SP}, NJ22), "c324-split": ({SP}, NJ22), "c292-split": ({SP}, NJ20), "c352-split": ({SP}, NJ22),
+    "c68-split": ({SP}, NJ8), "c132-split": ({SP}, NJ12), "c36-split": ({SP}, NJ4), "voice-split": ({SP}, NJ22),
+    "gfu-split": ({SP}, NJ20), "gsu-split": ({SP}, NJ20), "groups2-split": ({SP}, NJ20), "lin20-split": ({SP}, NJ20),
+    "speech-split-f32h": ({W43, SP}, NJ20), "speech-keep-start-split": ({W43, SP}, NJ20), "causal-f43-split": ({SP}, NJ20),
+    "large6-c340-split": ({SP}, NJ22), "large6-c324-split": ({SP}, NJ22), "large6-speech-split": ({SP}, NJ20),
+    "large8-c68-split": ({SP}, NJ8),
     "c292-invariant": ({"wide11"}, NJ20), "c300-invariant": ({"wide11"}, NJ20), "c316-invariant": ({"wide11"}, NJ20),
     "c324-invariant": ({"wide6x2"}, NJ22), "c340-invariant": ({"wide6x2"}, NJ22), "c352-invariant": ({"wide6x2"}, NJ22),
     "c340-rs-split1": ({"wave12"}, NJ22), "c340-rs-split2": ({"wave6x2"}, NJ22), "c340-rs-split3": ({W43}, NJ22),
@@ -168,6 +227,26 @@ KERNELS = {
 # the skip tensor
 UNFOLDED = {"speech-keep-skip"}
 _REFS = {}
+
+
+@contextlib.contextmanager
+def tensor_table_of(cid):
+    """The tensor table a case's engine is created from: for the cases of NO_START_F16 the host leaves out layer 0's split
+    res/skip image (a legal table: the C ABI runs that layer in float32), for every other case the engine's own."""
+    from mbexwn_vocoder_amd import engine as engine_module
+    fold_start = engine_module.fold_start_weights
+
+    def without_the_split_image(*args, **kw):
+        out = fold_start(*args, **kw)
+        assert out.pop("wn.res_skip_0.fold_start_f16", None) is not None
+        return out
+
+    if cid in NO_START_F16:
+        engine_module.fold_start_weights = without_the_split_image
+    try:
+        yield
+    finally:
+        engine_module.fold_start_weights = fold_start
 
 
 def test_gpu_cases_cover_every_gate_kernel():
@@ -206,6 +285,41 @@ def test_gpu_cases_cover_every_resskip_and_tail_kernel():
     assert sorted(lengths[ii] for ii in items) == [min(lengths), 260, max(lengths)]
 
 
+def test_gpu_split_cases_cover_the_channel_edges_and_launch_sizes():
+    """(CPU) The split-precision cases stand at the channel counts where wn_gate_f16.hip and wn_resskip_f16.hip take another
+    branch, and the launch arithmetic of launch_wn_gate_f16 puts each case on the kernel it expects."""
+    split = {case[0]: case for case in CASES if case[3].get("precision") == "split_f16"}
+    chan = {"speech": 320, "l3": 320, "deep12": 320, "voice": 340, "gfu": 320, "gsu": 320, "groups2": 320, "lin20": 320, "causal": 320}
+    chan.update({gg: int(gg[1:]) for gg in GEOMETRIES if gg[1:].isdigit()})
+    small = {chan[case[1]] for case in split.values() if SP in case[4] and SPW not in case[4]}
+    wide = {chan[case[1]] for case in split.values() if SPW in case[4]}
+    # a partial last column tile under an odd tile count, in the wide kernel: its last pair has one tile only
+    assert {C for C in wide if C % 32 and ((C + 31) // 32) % 2} >= {340, 324, 68}
+    assert {C for C in small if C % 32} >= {340, 324, 292, 68, 132, 36}
+    # plane padding between C and ceil8(C), read by the next gate as 8-channel chunks
+    assert {C for C in small if C % 8 == 4} >= {292, 324, 340, 68, 132, 36} and {C for C in wide if C % 8 == 4} >= {340, 324, 68}
+    # the widest res/skip launch the kernel accepts (C + 30 = 382: the clamp of the last column pair), two valid columns in it
+    assert {C for C in small if C + 30 == 382} == {352} and {C for C in small if (C + 30) % 32 == 2} >= {292, 324}
+    # the second column-half block (pairs 6 .. 11) lies behind cout: nothing, or plane padding only, to store
+    assert {C for C in small | wide if C <= 162} >= {36, 68, 132}
+    # cond_up: 10 sits exactly at the gate kernels' 28 conditioning rows; 20 is the other value a model can have
+    assert "lin20-split" in split and GEOMETRIES["lin20"][1][_WN + "cond_lin_upsampling"] == 20
+    # launch_wn_gate_f16: the wide kernel from 4 * 256 blocks of column-tile PAIRS, the planes kernel below
+    for cid, case in split.items():
+        lengths = LENGTHS[case[2]][0]
+        if SPW in case[4]:
+            assert SP not in case[4] and split_gate_blocks(chan[case[1]], lengths) >= 4 * 256, cid
+        elif SP in case[4]:
+            assert split_gate_blocks(chan[case[1]], lengths) < 4 * 256, cid
+    assert split_gate_blocks(340, LARGE6) == 1440 and split_gate_blocks(324, LARGE6) == 1440 and split_gate_blocks(320, LARGE6) == 1200
+    assert split_gate_blocks(68, LARGE8) == 1040
+    assert split_gate_blocks(340, WIDE8) == 1056 and split_gate_blocks(340, [ll if ll != max(WIDE8) else ll - 26 for ll in WIDE8]) < 1024
+    assert split_gate_blocks(340, RAGGED) < 1024
+    # every split case that leaves planes is a plane-only one unless a layer is out of the split gate's reach; the mixed mode has none
+    assert PLANES_ONLY <= set(split) and NO_START_F16 <= set(split) and set(F32_LAYER0) <= set(split)
+    assert not PLANES_ONLY & (set(F32_LAYER0) | {"causal-f43-split", "deep12-split"})
+
+
 @pytest.fixture(scope="module")
 def torch():
     import torch as _torch
@@ -241,7 +355,8 @@ def test_wavenet_stages_match_the_oracle(torch, cid, geom, lkey, kwargs, kernels
     lengths, items = LENGTHS[lkey]
     B, T = len(lengths), max(lengths)
     mel, noise = _inputs(lengths)
-    eng = MBExWNEngine(cfg, raw, wt, **kwargs)
+    with tensor_table_of(cid):
+        eng = MBExWNEngine(cfg, raw, wt, **kwargs)
     rpf = eng.dims.wn_in_rows_per_frame
     assert rpf == 20
     nf = torch.as_tensor(lengths, dtype=torch.int32).cuda()
@@ -256,7 +371,14 @@ def test_wavenet_stages_match_the_oracle(torch, cid, geom, lkey, kwargs, kernels
         f"{cid}: res/skip kernels {ran_rs}, expected {sorted(resskip)}"
     assert (ran_tail, info["tail_folded"]) == (tail, info["fold_skip"]), f"{cid}: tail kernel {ran_tail}, expected {tail}"
     if kwargs.get("precision") == "split_f16":
-        assert not info["split_rejected"] and info["split_f16_layers"] == eng.dims.wn_layers - 1, info
+        # layers 0 .. L - 2 run the split res/skip kernel; layer 0 runs a float32 one where its rows have no split image
+        assert not info["split_rejected"] and info["split_f16_layers"] == eng.dims.wn_layers - (2 if cid in F32_LAYER0 else 1), info
+        assert ran_rs[1:] == [SP] * (len(ran_rs) - 1) and ran_rs[0] == F32_LAYER0.get(cid, SP), f"{cid}: res/skip kernels {ran_rs}"
+        assert ran[0] in (FS, PS) and SP not in ran[:1], f"{cid}: gate kernels {ran}"
+        if SPF in kernels:
+            assert ran[1] == SPF and set(ran[2:]) == {SP}, f"{cid}: gate kernels {ran}"
+        if SPW in kernels:
+            assert set(ran[1:]) == {SPW}, f"{cid}: gate kernels {ran}"
     names = ["wn_out", "wn_hidden"] + (["wn_skip"] if kwargs.get("keep_skip") else [])
     got = engine_stages(eng, names, B, T, items=items)
     planes = True
@@ -280,15 +402,18 @@ def test_wavenet_stages_match_the_oracle(torch, cid, geom, lkey, kwargs, kernels
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("form", ["f43", "direct", "split_f16"])
+@pytest.mark.parametrize("form", ["f43", "direct", "split_f16", "split_f16-c340", "split_f16-c340-wide"])
 def test_padding_frames_are_never_read(torch, form):
     """The same ragged batch three times, its padding frames of mel and noise at 0, 1e30 and NaN: the audio and every WaveNet
-    stage of the items' valid rows are bit-identical across the three, and the audio behind each item's end is exactly 0."""
+    stage of the items' valid rows are bit-identical across the three, and the audio behind each item's end is exactly 0.
+    split_f16-c340: a partial last column tile, K step and plane chunk under the planes kernel and, with the shortest batch that
+    reaches it (WIDE8), under wn_gate_f16w_kernel, whose halo rows and missing twelfth column tile are clamped sources: a
+    clamped source that is not masked shows as the neighbour's NaN."""
     from mbexwn_vocoder_amd.engine import MBExWNEngine
-    cfg, raw, wt = build_case("SPEECH", {})
-    kwargs = {"conv_form": "f43", "precision": "split_f16"} if form == "split_f16" else {"conv_form": form}
+    cfg, raw, wt = build_case(*GEOMETRIES["c340" if "c340" in form else "speech"])
+    kwargs = {"conv_form": "f43", "precision": "split_f16"} if form.startswith("split_f16") else {"conv_form": form}
     eng = MBExWNEngine(cfg, raw, wt, **kwargs)
-    lengths = RAGGED
+    lengths = WIDE8 if form.endswith("-wide") else RAGGED
     B, T = len(lengths), max(lengths)
     mel, noise = _inputs(lengths, seed=911)
     nf = torch.as_tensor(lengths, dtype=torch.int32).cuda()
@@ -302,6 +427,9 @@ def test_padding_frames_are_never_read(torch, form):
         st = engine_stages(eng, ["wn_out", "wn_hidden"], B, T)
         st["pulse"] = eng.stage("pulse").cpu().numpy().reshape(B, T * 20, -1)
         runs[fill] = (audio, st)
+        if form.startswith("split_f16"):
+            ran = eng.conv_form_info()["gate_kernels"]
+            assert set(ran[1:]) == {SPW if form.endswith("-wide") else SP}, f"{form}: gate kernels {ran}"
     eng.close()
     base_audio, base_st = runs[0.0]
     for fill in (1e30, np.nan):
@@ -316,3 +444,24 @@ def test_padding_frames_are_never_read(torch, form):
                                       f"{bad[0][0]} channel {bad[0][1]}"
     for ii, ll in enumerate(lengths):
         assert np.all(np.isfinite(base_audio[ii, :ll * 300]))
+
+
+_BLOCKS2 = {"mbexwn_config:pp_mod_subnet_upsampling_factors": [2, 1], "mbexwn_config:pp_mod_subnet_channel_factors": [1, 0.5],
+            "mbexwn_config:pulse_channels": 10, _WN + "cond_lin_upsampling": 5, _WN + "n_channels": 32, _WN + "n_layers": 3}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("what,over,kwargs", [
+    ("several WaveNet blocks", _BLOCKS2, {}),
+    ("keep_skip", {_WN + "n_channels": 36, _WN + "n_layers": 3}, {"keep_skip": True}),
+    ("C + n_out > 384", {_WN + "n_channels": 356, _WN + "n_layers": 3}, {}),
+    ("two layers", {_WN + "n_channels": 36, _WN + "n_layers": 2}, {}),
+], ids=["blocks", "keep-skip", "c356", "two-layers"])
+def test_split_f16_refusals(torch, what, over, kwargs):
+    """What the split precision does not cover is refused at creation with the C ABI's argument error and its message (no
+    forward): a model of several WaveNet blocks, a kept skip tensor, C + n_out > 384 and fewer than three layers.  (glu:
+    test_gpu_forms.py.)"""
+    from mbexwn_vocoder_amd.engine import MBExWNEngine
+    cfg, raw, wt = build_case("SPEECH", over)
+    with pytest.raises(ValueError, match="wn_precision = split f16 needs the folded skip path, >= 3 layers, C \\+ n_out <= 384"):
+        MBExWNEngine(cfg, raw, wt, conv_form="f43", precision="split_f16", **kwargs)

@@ -746,6 +746,15 @@ def tensor_table(config, raw_weights, wavetables, split_f16=False):
 # ------------------------------------------------------------------------------------------------
 # the engine
 # ------------------------------------------------------------------------------------------------
+def forward_entry_point(state, active, control, f0, transposed):
+    """The library entry point of a forward, from which of its arguments are present: stream_state, active, any of the
+    per-frame pitch control (f0_frames / f0_scale / f0_item_mask), an f0 contour, a transposition other than 1.  The plain
+    entry points serve the calls that need no mbx_forward_options."""
+    if state:
+        return "mbx_forward_ex" if active or control else "mbx_forward_stream"
+    return "mbx_forward_ex" if f0 or transposed or control else "mbx_forward"
+
+
 class MBExWNEngine:
     """Device-resident MBExWN generator. One instance per GPU (one process per GPU)."""
 
@@ -894,11 +903,40 @@ class MBExWNEngine:
         if out is None:
             out = torch.empty((B, T * self.dims.hop_size), dtype=torch.float32, device=self.device)
         ws, need = self._get_workspace(B, T)
+        # (alive: the tensors opt points at, up to the call)
+        entry, opt, alive, stream_state, state_out = self._forward_options(
+            B, T, stream_state, state_out, active, wavenet, carry, layers, frontend, f0, transposition, f0_frames, f0_scale,
+            f0_item_mask)
+        common = (self._handle, mel.data_ptr(), n_frames.data_ptr() if n_frames is not None else None, B, T,
+                  noise.data_ptr() if noise is not None else None, out.data_ptr(), ws.data_ptr(), need)
+        if entry == "mbx_forward":
+            _check(self._lib.mbx_forward(*common, self._stream()))
+        elif entry == "mbx_forward_stream":
+            _check(self._lib.mbx_forward_stream(*common, stream_state.data_ptr(), state_out.data_ptr(), self._stream()))
+        else:
+            _check(self._lib.mbx_forward_ex(*common, ctypes.byref(opt), self._stream()))
+        self._last_shape = (B, T)
+        return out if stream_state is None else (out, state_out)
+
+    def _forward_options(self, B, T, stream_state, state_out, active, wavenet, carry, layers, frontend, f0, transposition,
+                         f0_frames, f0_scale, f0_item_mask):
+        """The arguments of a forward behind mel / n_frames / noise, checked: (library entry point (forward_entry_point), its
+        mbx_forward_options or None, the tensors the options point at -- to be kept alive up to the call --, stream_state
+        made contiguous, state_out allocated if none was given)."""
+        torch = self._torch
         if stream_state is None and (active is not None or wavenet is not None or carry is not None or layers is not None):
             raise ValueError("active / wavenet / carry / layers describe a streaming window: pass stream_state as well")
         if stream_state is not None and (f0 is not None or transposition != 1.0):
             raise ValueError("f0 / transposition apply to whole items: not with stream_state")
         control = self._pitch_control(B, T, f0, transposition, f0_frames, f0_scale, f0_item_mask)
+        entry = forward_entry_point(stream_state is not None, active is not None, any(cc is not None for cc in control),
+                                    f0 is not None, transposition != 1.0)
+        opt, keep = None, list(control)
+        if entry == "mbx_forward_ex":
+            opt = mbx_forward_options()
+            opt.struct_size = ctypes.sizeof(mbx_forward_options)
+            opt.transposition = 1.0
+            opt.f0_frames, opt.f0_scale, opt.f0_item_mask = (None if cc is None else cc.data_ptr() for cc in control)
         if stream_state is not None:
             if stream_state.dtype != torch.int32 or tuple(stream_state.shape) != (B, 6) or stream_state.device != self.device:
                 raise ValueError("stream_state must be an int32 tensor of shape (batch, 6) on the engine's device")
@@ -910,114 +948,78 @@ class MBExWNEngine:
                 raise ValueError("state_out must be a contiguous int32 tensor of shape (batch, 6) on the engine's device")
             if active is None and (wavenet is not None or carry is not None or layers is not None or frontend is not None):
                 raise ValueError("wavenet / carry / layers describe regions inside the active one: pass active as well")
+            if opt is not None:
+                opt.state_in, opt.state_out = stream_state.data_ptr(), state_out.data_ptr()
             if active is not None:
-                a0, act = int(active[0]), active[1]
-                if act.dtype != torch.int32 or tuple(act.shape) != (B,) or act.device != self.device or not 0 <= a0 < T:
-                    raise ValueError("active = (begin frame inside the window, int32 tensor of shape (batch,) on the device)")
-                act = act.contiguous()
-                opt = mbx_forward_options()
-                opt.struct_size = ctypes.sizeof(mbx_forward_options)
-                opt.transposition = 1.0
-                opt.state_in, opt.state_out = stream_state.data_ptr(), state_out.data_ptr()
-                opt.active_begin, opt.active_frames = a0, act.data_ptr()
-                if len(active) > 2:
-                    opt.active_max_frames = int(active[2])
-                keep = [act]
-                if wavenet is not None:
-                    w0, wfr = int(wavenet[0]), wavenet[1]
-                    if wfr.dtype != torch.int32 or tuple(wfr.shape) != (B,) or wfr.device != self.device or not a0 <= w0 < T:
-                        raise ValueError("wavenet = (begin frame inside the active region, int32 tensor (batch,) on the device)")
-                    wfr = wfr.contiguous()
-                    keep.append(wfr)
-                    opt.wn_begin, opt.wn_frames = w0, wfr.data_ptr()
-                    if len(wavenet) > 2:
-                        opt.wn_max_frames = int(wavenet[2])
-                if carry is not None:
-                    store, desc = carry
-                    if (store.dtype != torch.float32 or store.dim() != 3 or store.shape[2] != self.dims.subbands or
-                            store.device != self.device or not store.is_contiguous()):
-                        raise ValueError("carry store must be a contiguous float32 tensor (slots, rows, subbands) on the device")
-                    if desc.dtype != torch.int32 or tuple(desc.shape) != (B, 5) or desc.device != self.device:
-                        raise ValueError("carry descriptors must be an int32 tensor of shape (batch, 5) on the device")
-                    desc = desc.contiguous()
-                    keep.append(desc)
-                    opt.sub_store, opt.sub_store_rows, opt.sub_carry = store.data_ptr(), int(store.shape[1]), desc.data_ptr()
-                if layers is not None:
-                    lstore, ldesc, lrows = layers
-                    if (lstore.dtype != torch.float32 or lstore.dim() != 2 or lstore.device != self.device or
-                            not lstore.is_contiguous()):
-                        raise ValueError("layer store must be a contiguous float32 tensor (slots, floats) on the device")
-                    if ldesc.dtype != torch.int32 or tuple(ldesc.shape) != (B, 3) or ldesc.device != self.device:
-                        raise ValueError("layer descriptors must be an int32 tensor of shape (batch, 3) on the device")
-                    ldesc = ldesc.contiguous()
-                    keep.append(ldesc)
-                    opt.layer_store, opt.layer_store_floats = lstore.data_ptr(), int(lstore.shape[1])
-                    opt.layer_carry, opt.layer_rows = ldesc.data_ptr(), int(lrows)
-                if frontend is not None:
-                    ring, fpos, fnew, fmargin = frontend[:4]
-                    opt.fe_end_frames = int(frontend[4]) if len(frontend) > 4 else 0
-                    if (ring.dtype != torch.float32 or ring.dim() != 3 or ring.device != self.device or not ring.is_contiguous() or
-                            ring.shape[2] != self.frontend_frame_floats):
-                        raise ValueError("front-end ring must be a contiguous float32 tensor (slots, ring frames, "
-                                         f"{self.frontend_frame_floats}) on the device")
-                    if fpos.dtype != torch.int32 or tuple(fpos.shape) != (B,) or fpos.device != self.device or carry is None:
-                        raise ValueError("front-end positions must be an int32 tensor (batch,) on the device; carry is required")
-                    fpos = fpos.contiguous()
-                    keep.append(fpos)
-                    opt.fe_store, opt.fe_ring_frames, opt.fe_pos = ring.data_ptr(), int(ring.shape[1]), fpos.data_ptr()
-                    opt.fe_new_frames, opt.fe_margin_frames = int(fnew), int(fmargin)
-                opt.f0_frames, opt.f0_scale, opt.f0_item_mask = (None if cc is None else cc.data_ptr() for cc in control)
-                _check(self._lib.mbx_forward_ex(self._handle, mel.data_ptr(),
-                                                n_frames.data_ptr() if n_frames is not None else None, B, T,
-                                                noise.data_ptr() if noise is not None else None, out.data_ptr(),
-                                                ws.data_ptr(), need, ctypes.byref(opt), self._stream()))
-                self._last_shape = (B, T)
-                return out, state_out
-            if any(cc is not None for cc in control):
-                opt = mbx_forward_options()
-                opt.struct_size = ctypes.sizeof(mbx_forward_options)
-                opt.transposition = 1.0
-                opt.state_in, opt.state_out = stream_state.data_ptr(), state_out.data_ptr()
-                opt.f0_frames, opt.f0_scale, opt.f0_item_mask = (None if cc is None else cc.data_ptr() for cc in control)
-                _check(self._lib.mbx_forward_ex(self._handle, mel.data_ptr(),
-                                                n_frames.data_ptr() if n_frames is not None else None, B, T,
-                                                noise.data_ptr() if noise is not None else None, out.data_ptr(),
-                                                ws.data_ptr(), need, ctypes.byref(opt), self._stream()))
-                self._last_shape = (B, T)
-                return out, state_out
-            _check(self._lib.mbx_forward_stream(self._handle, mel.data_ptr(),
-                                                n_frames.data_ptr() if n_frames is not None else None, B, T,
-                                                noise.data_ptr() if noise is not None else None, out.data_ptr(),
-                                                ws.data_ptr(), need, stream_state.data_ptr(), state_out.data_ptr(),
-                                                self._stream()))
-            self._last_shape = (B, T)
-            return out, state_out
-        if f0 is not None or transposition != 1.0 or any(cc is not None for cc in control):
+                self._window_options(opt, keep, B, T, active, wavenet, carry, layers, frontend)
+        elif opt is not None:
             if not transposition > 0.0:
                 raise ValueError("transposition must be positive")
-            opt = mbx_forward_options()
-            opt.struct_size = ctypes.sizeof(mbx_forward_options)
             opt.transposition = float(transposition)
-            opt.f0_frames, opt.f0_scale, opt.f0_item_mask = (None if cc is None else cc.data_ptr() for cc in control)
             if f0 is not None:
                 if (f0.dtype != torch.float32 or tuple(f0.shape) != (B, T * self.dims.pulse_per_frame) or
                         f0.device != self.device):
                     raise ValueError(f"f0 must be a float32 tensor of shape ({B}, {T * self.dims.pulse_per_frame}) on the "
                                      "engine's device")
                 f0 = f0.contiguous()
+                keep.append(f0)
                 opt.f0 = f0.data_ptr()
-            _check(self._lib.mbx_forward_ex(self._handle, mel.data_ptr(),
-                                            n_frames.data_ptr() if n_frames is not None else None, B, T,
-                                            noise.data_ptr() if noise is not None else None, out.data_ptr(),
-                                            ws.data_ptr(), need, ctypes.byref(opt), self._stream()))
-            self._last_shape = (B, T)
-            return out
-        _check(self._lib.mbx_forward(self._handle, mel.data_ptr(),
-                                     n_frames.data_ptr() if n_frames is not None else None, B, T,
-                                     noise.data_ptr() if noise is not None else None, out.data_ptr(),
-                                     ws.data_ptr(), need, self._stream()))
-        self._last_shape = (B, T)
-        return out
+        return entry, opt, keep, stream_state, state_out
+
+    def _window_options(self, opt, keep, B, T, active, wavenet, carry, layers, frontend):
+        """The streaming-window arguments of a forward, checked and written into opt (the tensors they point at: keep)."""
+        torch = self._torch
+        a0, act = int(active[0]), active[1]
+        if act.dtype != torch.int32 or tuple(act.shape) != (B,) or act.device != self.device or not 0 <= a0 < T:
+            raise ValueError("active = (begin frame inside the window, int32 tensor of shape (batch,) on the device)")
+        act = act.contiguous()
+        keep.append(act)
+        opt.active_begin, opt.active_frames = a0, act.data_ptr()
+        if len(active) > 2:
+            opt.active_max_frames = int(active[2])
+        if wavenet is not None:
+            w0, wfr = int(wavenet[0]), wavenet[1]
+            if wfr.dtype != torch.int32 or tuple(wfr.shape) != (B,) or wfr.device != self.device or not a0 <= w0 < T:
+                raise ValueError("wavenet = (begin frame inside the active region, int32 tensor (batch,) on the device)")
+            wfr = wfr.contiguous()
+            keep.append(wfr)
+            opt.wn_begin, opt.wn_frames = w0, wfr.data_ptr()
+            if len(wavenet) > 2:
+                opt.wn_max_frames = int(wavenet[2])
+        if carry is not None:
+            store, desc = carry
+            if (store.dtype != torch.float32 or store.dim() != 3 or store.shape[2] != self.dims.subbands or
+                    store.device != self.device or not store.is_contiguous()):
+                raise ValueError("carry store must be a contiguous float32 tensor (slots, rows, subbands) on the device")
+            if desc.dtype != torch.int32 or tuple(desc.shape) != (B, 5) or desc.device != self.device:
+                raise ValueError("carry descriptors must be an int32 tensor of shape (batch, 5) on the device")
+            desc = desc.contiguous()
+            keep.append(desc)
+            opt.sub_store, opt.sub_store_rows, opt.sub_carry = store.data_ptr(), int(store.shape[1]), desc.data_ptr()
+        if layers is not None:
+            lstore, ldesc, lrows = layers
+            if (lstore.dtype != torch.float32 or lstore.dim() != 2 or lstore.device != self.device or
+                    not lstore.is_contiguous()):
+                raise ValueError("layer store must be a contiguous float32 tensor (slots, floats) on the device")
+            if ldesc.dtype != torch.int32 or tuple(ldesc.shape) != (B, 3) or ldesc.device != self.device:
+                raise ValueError("layer descriptors must be an int32 tensor of shape (batch, 3) on the device")
+            ldesc = ldesc.contiguous()
+            keep.append(ldesc)
+            opt.layer_store, opt.layer_store_floats = lstore.data_ptr(), int(lstore.shape[1])
+            opt.layer_carry, opt.layer_rows = ldesc.data_ptr(), int(lrows)
+        if frontend is not None:
+            ring, fpos, fnew, fmargin = frontend[:4]
+            opt.fe_end_frames = int(frontend[4]) if len(frontend) > 4 else 0
+            if (ring.dtype != torch.float32 or ring.dim() != 3 or ring.device != self.device or not ring.is_contiguous() or
+                    ring.shape[2] != self.frontend_frame_floats):
+                raise ValueError("front-end ring must be a contiguous float32 tensor (slots, ring frames, "
+                                 f"{self.frontend_frame_floats}) on the device")
+            if fpos.dtype != torch.int32 or tuple(fpos.shape) != (B,) or fpos.device != self.device or carry is None:
+                raise ValueError("front-end positions must be an int32 tensor (batch,) on the device; carry is required")
+            fpos = fpos.contiguous()
+            keep.append(fpos)
+            opt.fe_store, opt.fe_ring_frames, opt.fe_pos = ring.data_ptr(), int(ring.shape[1]), fpos.data_ptr()
+            opt.fe_new_frames, opt.fe_margin_frames = int(fnew), int(fmargin)
 
     def _pitch_control(self, B, T, f0, transposition, f0_frames, f0_scale, f0_item_mask):
         """The per-frame pitch control of a forward, checked: (f0_frames, f0_scale, f0_item_mask) as contiguous tensors or

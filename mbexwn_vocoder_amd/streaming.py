@@ -20,7 +20,12 @@ PQMF (+-4 steps) -> 7; STFT frame + overlap-add (-3 / +4 frames) -> LEFT = 10, R
 ``StreamingSynthesizer`` derives the margins from the model configuration.  A force_causal model (every convolution
 padded in front only) needs no look-ahead in its sub-nets and WaveNet: 87.5 ms of the same model (stream_margins).
 """
+from dataclasses import dataclass, field, fields
+from types import SimpleNamespace
+
 import numpy as np
+
+from .stream_plan import StreamGeometry, plan_tick
 
 
 def pack_state(cum=0.0, offset_sum=0.0, pos_in_chunk=0, start_sample=0, save_sample=-1):
@@ -158,6 +163,183 @@ class _Stream:
         self.f0_mode = "net"      # "frames": the contour comes from push(f0=...) instead of the F0-net
 
 
+class _InputRows:
+    """Input frames of every stream, one row per slot (shared so that a tick gathers its frames with one indexed copy): mel
+    and noise, and next to them the per-frame pitch control -- F0 in Hz ("frames" streams; 1 where none was given, never
+    read there) and the transposition factor (1 where none was given)."""
+
+    def __init__(self, mel_channels, steps_per_frame, cap=256):
+        self._widths = (mel_channels, steps_per_frame)
+        self.cap = cap            # frames per row (grows on demand)
+        self.mel, self.noise, self.f0, self.scale = self._alloc(0, cap)
+
+    def _alloc(self, slots, cap):
+        return (np.zeros((slots, cap, self._widths[0]), dtype=np.float32),
+                np.zeros((slots, cap, self._widths[1]), dtype=np.float32),
+                np.ones((slots, cap), dtype=np.float32), np.ones((slots, cap), dtype=np.float32))
+
+    def _arrays(self):
+        return self.mel, self.noise, self.f0, self.scale
+
+    @property
+    def slots(self):
+        return self.mel.shape[0]
+
+    def grow(self, slots, cap):
+        """Make the rows at least (slots, cap frames) large, keeping their contents."""
+        if slots <= self.slots and cap <= self.cap:
+            return
+        old = self._arrays()
+        self.mel, self.noise, self.f0, self.scale = self._alloc(max(slots, self.slots), max(cap, self.cap))
+        for new, was in zip(self._arrays(), old):
+            new[:was.shape[0], :was.shape[1]] = was
+        self.cap = self.mel.shape[1]
+
+    def drop_front(self, slot, n, live):
+        """Move the `live` frames behind the first n of a row to its front."""
+        for arr in self._arrays():
+            arr[slot, :live] = arr[slot, n:n + live]
+
+    def append(self, slot, col, mel, noise=None, f0=None, scale=None):
+        n = mel.shape[0]
+        self.mel[slot, col:col + n] = mel
+        if noise is not None:
+            self.noise[slot, col:col + n] = noise
+        self.f0[slot, col:col + n] = 1.0 if f0 is None else f0
+        self.scale[slot, col:col + n] = 1.0 if scale is None else scale
+
+    def window(self, slot, lo, hi):
+        """(mel, noise, f0, scale) of the columns [lo, hi) of a row (views)."""
+        return tuple(arr[slot, lo:hi] for arr in self._arrays())
+
+    def gather(self, slots, cols, **into):
+        """Copy the columns cols (n, k) of the rows slots (n,) of the named arrays into the given destinations, e.g.
+        ``gather(slots, cols, mel=dst)``: one indexed copy per array."""
+        for name, dst in into.items():
+            np.copyto(dst, getattr(self, name)[slots[:, None], cols])
+
+
+class _Layout:
+    """Named fields packed back to back into one flat 4-byte buffer (what a tick uploads in one copy).  ``fields``: (name,
+    shape, "int32" / "float32"); ``views`` cuts any such buffer -- host or device, numpy or torch -- into its fields,
+    bit-casting those whose type is not the buffer's.  An empty field is None.  The only place that knows an offset."""
+
+    def __init__(self, fields):
+        self.fields, self.size = [], 0
+        for name, shape, dtype in fields:
+            count = int(np.prod(shape))
+            self.fields.append((name, slice(self.size, self.size + count), tuple(shape), dtype))
+            self.size += count
+
+    def views(self, buf):
+        if isinstance(buf, np.ndarray):
+            ns = np
+        else:
+            import torch as ns
+        out = SimpleNamespace()
+        for name, where, shape, dtype in self.fields:
+            part = buf[where] if where.stop > where.start else None
+            if part is not None and part.dtype != getattr(ns, dtype):
+                part = part.view(getattr(ns, dtype))
+            setattr(out, name, None if part is None else part.reshape(shape))
+        return out
+
+
+def _stage_layout(B, chunk, tpad, mel_channels, spf, use_noise, control):
+    """The (float32) stage buffer of a replayed tick: new mel frames, new noise, phase states, ring positions and -- once
+    the synthesizer has seen pitch control -- the control rows of the whole windows (what a tick does not upload is empty)."""
+    return _Layout([("mel", (B, chunk, mel_channels), "float32"), ("noise", (B, chunk * spf * use_noise), "float32"),
+                    ("states", (B, 6), "int32"), ("fpos", (B,), "int32"),
+                    ("f0_frames", (B, tpad * control), "float32"), ("f0_scale", (B, tpad * control), "float32")])
+
+
+@dataclass
+class _TickInputs:
+    """What a launch-by-launch tick uploaded: the windows and every int32 argument of the call (one buffer, cut)."""
+    mel: object
+    noise: object
+    tpad: int
+    args: object              # device views: states, desc, ldesc, nfr, act, wn, fpos, f0_item_mask, f0_frames, f0_scale
+    use_fe: bool
+    control: bool
+    f0_mask: object           # host copy of f0_item_mask, or None without control
+
+
+@dataclass
+class _Phase:
+    """A recorded steady tick of one phase of the schedule: the window-relative constants of its engine call."""
+    phase: int
+    chunk: int
+    T: int
+    tpad: int
+    a0: int
+    wa: int
+    lo: int                   # the emitted samples are the columns [lo, hi) of the audio
+    hi: int
+    layer_rows: int
+    act: np.ndarray
+    wn: np.ndarray
+    nfr: np.ndarray
+    desc: np.ndarray
+    ldesc: np.ndarray
+    state_consts: np.ndarray
+    rel0: int                 # frame of the window at which the emitted frames start
+    use_fe: bool
+    frames: int
+    active_frames: int
+    wavenet_frames: int
+    control: bool
+    f0_mask: object
+
+    def same_geometry(self, other):
+        for ff in fields(self):
+            mine, theirs = getattr(self, ff.name), getattr(other, ff.name)
+            same = np.array_equal(mine, theirs) if isinstance(mine, np.ndarray) else mine == theirs
+            if not same:
+                return False
+        return True
+
+
+@dataclass
+class _CapturedTick:
+    """The captured launch sequence of one phase and the fixed buffers it works on."""
+    graph: object
+    stage_host: object        # pinned; `host` are its fields as numpy views (_stage_layout)
+    host: object
+    arange: np.ndarray
+    arange_win: np.ndarray
+    audio_host: object
+    state_host: object
+    shift: int
+    keep: int
+    keep_alive: tuple
+
+
+@dataclass
+class _SteadyRun:
+    """A run of steady ticks: its streams, the recorded phases and their graphs, and where it stands -- the streams'
+    progress and phase states as vectors (replayed ticks keep them there, _sync_streams writes them back)."""
+    sids: list
+    streams: list
+    B: int
+    tpad: int
+    slots: np.ndarray
+    phases: dict = field(default_factory=dict)        # phase of the schedule -> _Phase
+    graphs: dict = field(default_factory=dict)        # phase of the schedule -> _CapturedTick
+    win: object = None        # the device-resident windows (mel, noise) all captured phases work on
+    audio_buf: object = None  # ... and their shared outputs
+    state_out: object = None
+    state_host: object = None
+    win_src: object = None    # the tensors that hold the windows of the last tick: `win`, or what that tick uploaded
+    state_v: object = None
+    emitted_v: object = None
+    next_phase: int = 0
+    pending: int = 0          # replayed ticks (and their frames) not yet written back to the streams
+    pending_frames: int = 0
+    need_v: object = None     # cached per-stream vectors; only push() changes them
+    base_v: object = None
+
+
 class StreamingSynthesizer:
     """Serves any number of concurrent streams with one batched engine call per tick."""
 
@@ -202,7 +384,7 @@ class StreamingSynthesizer:
         # region [emitted, emitted + chunk + act_right) with the WaveNet's reach recomputed on both sides
         ff, reach, min_rows = engine.layer_state_info()
         self.layer_carry = ff > 0 and reach == self.wn_reach * engine.dims.steps_per_frame
-        self._layer_floats, self._layer_min_rows = ff, min_rows
+        self._layer_floats = ff
         self._layer_store = None      # (slots, floats per slot) on the device
         # mel-rate front end (conditioning rows, cepstrum, F0 contour) carried from tick to tick in a ring per stream: a
         # replayed steady tick runs the sub-nets only on the frames its new mel frames can reach
@@ -214,14 +396,7 @@ class StreamingSynthesizer:
         self._fe_ring = ring
         self._fe_store = None         # (slots, ring frames, floats per frame) on the device
         self._free_slots = []
-        # input frames of every stream, one row per slot (shared so that a tick gathers its frames with one indexed copy)
-        self._in_cap = 256            # frames per row (grows on demand)
-        self._in_mel = np.zeros((0, self._in_cap, self.dims.mel_channels), dtype=np.float32)
-        self._in_noise = np.zeros((0, self._in_cap, self.dims.steps_per_frame), dtype=np.float32)
-        # per-frame pitch control of every stream, next to its frames: F0 in Hz ("frames" streams; 1 where none was given --
-        # never read there) and the transposition factor (1 where none was given)
-        self._in_f0 = np.ones((0, self._in_cap), dtype=np.float32)
-        self._in_scale = np.ones((0, self._in_cap), dtype=np.float32)
+        self._rows = _InputRows(self.dims.mel_channels, self.dims.steps_per_frame)
         # Sticky: set by the first "frames" stream or the first transposition other than 1.  Until then a tick passes none
         # of the control arguments (the launch sequence and the captured graphs of a synthesizer that only resynthesises are
         # unchanged); from then on every tick passes the control rows of its whole windows -- factor 1 and mask 0 for the
@@ -238,6 +413,13 @@ class StreamingSynthesizer:
             # emitted frames that the aligned start of a tick's WaveNet region never lies in front of them (the region
             # stays inside the active one), whatever the phase of the tick schedule
             self.sr_left = max(self.sr_left, self.align - 1 + self.wn_left - self.sr_right)
+        # everything plan_tick needs to lay a tick out
+        self.geometry = StreamGeometry(
+            left=self.left, right=self.right, lead=self.lead, act_left=self.act_left, act_right=self.act_right,
+            wn_left=self.wn_left, wn_reach=self.wn_reach, sr_left=self.sr_left, sr_right=self.sr_right, align=self.align,
+            steps_per_frame=self.dims.steps_per_frame, pulse_per_frame=self.dims.pulse_per_frame,
+            hop_size=self.dims.hop_size, carry=self.carry, layer_carry=self.layer_carry, layer_min_rows=min_rows,
+            fe_ring=self._fe_ring)
         self.streams = {}
         # ticks of a schedule whose period is a whole number of alignment steps have a geometry that repeats per phase
         self.periodic = sum(self.schedule) % self.align == 0
@@ -249,7 +431,7 @@ class StreamingSynthesizer:
         # practical form of BASELINE config 5's "persistent-kernel path": the launch sequence persists, not a kernel.
         self.use_graph = True
         self._inputs_changed = True
-        self._steady = None               # the steady run in progress: its streams, the recorded phases and their graphs
+        self._steady = None               # the steady run in progress (_SteadyRun)
         self.graph_ticks = 0              # ticks served by a graph replay
         self.last_tick_replayed = False
         self.time_device = False          # bench: bracket the engine call of a tick with events on its stream
@@ -263,21 +445,20 @@ class StreamingSynthesizer:
     def lookahead_ms(self):
         return 1000.0 * self.right * self.dims.hop_size / self.dims.sample_rate
 
-    def _grow_inputs(self, slots, cap):
-        """Make the shared input buffers at least (slots, cap frames) large, keeping their contents."""
-        old_mel, old_noise, old_f0, old_scale = self._in_mel, self._in_noise, self._in_f0, self._in_scale
-        if slots <= old_mel.shape[0] and cap <= self._in_cap:
-            return
-        slots, cap = max(slots, old_mel.shape[0]), max(cap, self._in_cap)
-        self._in_mel = np.zeros((slots, cap, self.dims.mel_channels), dtype=np.float32)
-        self._in_noise = np.zeros((slots, cap, self.dims.steps_per_frame), dtype=np.float32)
-        self._in_f0 = np.ones((slots, cap), dtype=np.float32)
-        self._in_scale = np.ones((slots, cap), dtype=np.float32)
-        self._in_mel[:old_mel.shape[0], :self._in_cap] = old_mel
-        self._in_noise[:old_noise.shape[0], :self._in_cap] = old_noise
-        self._in_f0[:old_f0.shape[0], :self._in_cap] = old_f0
-        self._in_scale[:old_scale.shape[0], :self._in_cap] = old_scale
-        self._in_cap = cap
+    # the shared input rows under the names they had before _InputRows owned them (read by the host tests)
+    _in_cap = property(lambda self: self._rows.cap)
+    _in_mel = property(lambda self: self._rows.mel)
+    _in_noise = property(lambda self: self._rows.noise)
+    _in_f0 = property(lambda self: self._rows.f0)
+    _in_scale = property(lambda self: self._rows.scale)
+
+    def _grown(self, old, slots, *shape):
+        """A zeroed device store of `slots` slots that starts with the contents of the old one."""
+        import torch
+        new = torch.zeros((slots,) + shape, dtype=torch.float32, device=self.engine.device)
+        if old is not None:
+            new[:old.shape[0]] = old
+        return new
 
     def open(self, stream_id, f0="net"):
         """``f0``: "net" -- the stream's contour is the F0-net's; "frames" -- it is given from outside, one value in Hz per
@@ -287,29 +468,18 @@ class StreamingSynthesizer:
         self._leave_steady()
         st = _Stream()
         st.f0_mode = f0
-        import torch
-        rows = (self.sr_left + self.sr_right) * self.dims.steps_per_frame
         if not self._free_slots:
-            old = self._store
-            n_old = 0 if old is None else int(old.shape[0])
+            n_old = 0 if self._store is None else int(self._store.shape[0])
             n_new = max(16, 2 * n_old)
-            self._store = torch.zeros((n_new, rows, self.dims.subbands), dtype=torch.float32, device=self.engine.device)
-            if old is not None:
-                self._store[:n_old] = old
+            rows = (self.sr_left + self.sr_right) * self.dims.steps_per_frame
+            self._store = self._grown(self._store, n_new, rows, self.dims.subbands)
             if self.layer_carry:
-                old_l = self._layer_store
-                self._layer_store = torch.zeros((n_new, self._layer_floats), dtype=torch.float32, device=self.engine.device)
-                if old_l is not None:
-                    self._layer_store[:n_old] = old_l
+                self._layer_store = self._grown(self._layer_store, n_new, self._layer_floats)
             if self.fe_carry:
-                old_f = self._fe_store
-                self._fe_store = torch.zeros((n_new, self._fe_ring, self.engine.frontend_frame_floats), dtype=torch.float32,
-                                             device=self.engine.device)
-                if old_f is not None:
-                    self._fe_store[:n_old] = old_f
+                self._fe_store = self._grown(self._fe_store, n_new, self._fe_ring, self.engine.frontend_frame_floats)
             self._free_slots = list(range(n_new - 1, n_old - 1, -1))
             # (the stores moved: captured ticks point at the old ones -- open() has left the steady run above)
-            self._grow_inputs(n_new, self._in_cap)
+            self._rows.grow(n_new, self._rows.cap)
         st.slot = self._free_slots.pop()
         self.streams[stream_id] = st
         if f0 == "frames":
@@ -354,25 +524,17 @@ class StreamingSynthesizer:
             noise = np.asarray(noise, dtype=np.float32).reshape(-1, spf)
             if noise.shape[0] != n:
                 raise ValueError("noise must hold steps_per_frame values per pushed mel frame")
-        if st.have - st.base + n > self._in_cap:
+        rows = self._rows
+        if st.have - st.base + n > rows.cap:
             # drop the frames no later window can reach (windows start at aligned(emitted - left); a stale `emitted` of a
             # stream inside a run of replayed ticks only keeps more than necessary), then grow the rows if that is not enough
             keep_from = max(st.base, ((st.emitted - self.left) // self.align) * self.align)
-            drop, live = keep_from - st.base, st.have - keep_from
-            if drop > 0:
-                self._in_mel[st.slot, :live] = self._in_mel[st.slot, drop:drop + live]
-                self._in_noise[st.slot, :live] = self._in_noise[st.slot, drop:drop + live]
-                self._in_f0[st.slot, :live] = self._in_f0[st.slot, drop:drop + live]
-                self._in_scale[st.slot, :live] = self._in_scale[st.slot, drop:drop + live]
+            if keep_from > st.base:
+                rows.drop_front(st.slot, keep_from - st.base, st.have - keep_from)
                 st.base = keep_from
-            if st.have - st.base + n > self._in_cap:
-                self._grow_inputs(self._in_mel.shape[0], max(2 * self._in_cap, st.have - st.base + n))
-        col = st.have - st.base
-        self._in_mel[st.slot, col:col + n] = mel_frames
-        if self.dims.noise_sigma:
-            self._in_noise[st.slot, col:col + n] = noise
-        self._in_f0[st.slot, col:col + n] = 1.0 if f0 is None else f0
-        self._in_scale[st.slot, col:col + n] = 1.0 if transposition is None else transposition
+            if st.have - st.base + n > rows.cap:
+                rows.grow(rows.slots, max(2 * rows.cap, st.have - st.base + n))
+        rows.append(st.slot, st.have - st.base, mel_frames, noise if self.dims.noise_sigma else None, f0, transposition)
         if not self._control and transposition is not None and np.any(transposition != 1.0):
             # the first control this synthesizer sees: a steady run recorded without the control arguments is left and
             # captured anew
@@ -391,6 +553,9 @@ class StreamingSynthesizer:
             return min(chunk, have - st.emitted)
         return chunk if have >= st.emitted + chunk + self.right else 0
 
+    # ------------------------------------------------------------------------------------------------------------------
+    # a tick launch by launch: plan (stream_plan.plan_tick), upload, engine call, commit, record
+    # ------------------------------------------------------------------------------------------------------------------
     def tick(self):
         """One batched engine call over every stream that can emit. Returns {stream_id: audio ndarray}."""
         import torch
@@ -407,233 +572,129 @@ class StreamingSynthesizer:
         todo = [(sid, st, nn) for sid, st, nn in todo if nn > 0]
         if not todo:
             return {}
-        ppf, spf, hop = self.dims.pulse_per_frame, self.dims.steps_per_frame, self.dims.hop_size
-        windows = []
-        for sid, st, nn in todo:
-            have = st.have
-            ws = max(0, ((st.emitted - self.left) // self.align) * self.align)
-            we = have if st.closed and st.emitted + nn + self.right >= have else st.emitted + nn + self.right
-            we = min(we, have)
-            windows.append((ws, we))
-        tmax = max(we - ws for ws, we in windows)
-        B = len(todo)
-        # active region: the mel-rate stages and the phase need the whole window (their receptive fields are long: F0-net,
-        # smoother of the lifter selection), the stages from the WaveNet on only the frames around what is emitted.
-        # It starts on an aligned frame (same Winograd pairing as offline), at least `lead` frames inside a window that
-        # does not start the utterance (pulses are reproducible from there), and is the same offset for every item.
-        a0 = None
-        for (sid, st, nn), (ws, we) in zip(todo, windows):
-            ab = max(0, ((st.emitted - self.act_left) // self.align) * self.align) - ws
-            if ws > 0 and ab < self.lead:
-                ab = 0
-            a0 = ab if a0 is None else min(a0, ab)
-        if any(ws > 0 for ws, _ in windows) and 0 < a0 < self.lead:
-            a0 = 0
-        act = np.zeros((B,), dtype=np.int32)
-        ends = []
-        for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
-            a1 = we if we - (st.emitted + nn) <= self.act_right else st.emitted + nn + self.act_right
-            ends.append(a1)
-            act[bb] = a1 - ws - a0
-        # carried sub-bands: usable when every item of the tick has a valid store and the same geometry
-        sl, sr, wr, wl = self.sr_left, self.sr_right, self.wn_reach, self.wn_left
-        wn = None
-        desc = np.zeros((B, 5), dtype=np.int32)
-        use_carry = self.carry
-        sa = wa = None
-        for (sid, st, nn), (ws, we) in zip(todo, windows):
-            if not use_carry:
-                break
-            ok = st.carry_pos == st.emitted and st.emitted - sl >= ws
-            sab = st.emitted - sl - ws
-            wab = ((st.emitted + min(sr, st.carry_frames - sl) - wl) // self.align) * self.align - ws
-            ok = ok and wab >= sab and (ws == 0 or wab >= self.lead) and st.carry_frames > sl
-            ok = ok and (sa is None or (sab == sa and wab == wa))
-            sa, wa = sab, wab
-            use_carry = ok
-        if use_carry and todo:
-            a0 = sa
-            wn = np.zeros((B,), dtype=np.int32)
-            for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
-                act[bb] = ends[bb] - ws - sa
-                wn[bb] = ends[bb] - ws - wa
-                desc[bb, 1:3] = sa * spf, st.carry_frames * spf
-        # rows the next tick will need: frames [e' - sr_left, e' + sr_right) around the next emit position e', if this tick
-        # computes them exactly (its region reaches wn_reach frames beyond them, or to the end of the utterance)
-        next_carry = []
-        for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
-            e1 = st.emitted + nn
-            lo, hi = e1 - sl, min(e1 + sr, ends[bb] if ends[bb] == we and st.closed else ends[bb] - wr)
-            region_lo = ws + a0 if use_carry else ws + a0 + (wl if ws + a0 > 0 else 0)
-            good = self.carry and lo >= region_lo and hi > lo + sl and lo >= ws
-            desc[bb, 0] = st.slot
-            if good:
-                desc[bb, 3:5] = (lo - ws) * spf, (hi - lo) * spf
-            next_carry.append((e1, hi - lo) if good else (None, 0))
-        # per-layer WaveNet state.  Steady tick: every item has the state of a region that ended layer_rows rows in front
-        # of this tick's region end, the sub-bands up to the WaveNet's reach in front of that, the same geometry inside
-        # its window, and does not end its utterance here.  Any other tick runs the whole region and stores the state.
-        ldesc = np.full((B, 3), -1, dtype=np.int32)
-        layer_rows = 0
-        next_layer_end = [None] * B
-        if self.layer_carry:
-            steady = bool(use_carry)
-            geom = None
-            for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
-                final = st.closed and ends[bb] >= we
-                ldesc[bb, 0] = st.slot
-                if st.layer_end is None or final or st.layer_end >= ends[bb]:
-                    steady = False
-                elif steady:
-                    gg = ((ends[bb] - st.layer_end) * spf, ends[bb] - ws)
-                    steady = (gg[0] >= self._layer_min_rows and (geom is None or gg == geom) and st.layer_end - wr >= ws + sa and
-                              st.emitted - sl + st.carry_frames == st.layer_end - wr)
-                    geom = gg
-            region0 = (wa if use_carry else a0)
-            for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
-                final = st.closed and ends[bb] >= we
-                # state of this tick's region: exact if the region starts the utterance or reaches 2 * reach + 1 frames back
-                # in front of its last exact row (SAME: 3 * reach + 1 frames in all)
-                long_enough = ws + region0 == 0 or ends[bb] - ws - region0 >= 2 * wl + wr + 1
-                if not final and (steady or long_enough):
-                    ldesc[bb, 2] = (ends[bb] - ws) * spf
-                    next_layer_end[bb] = ends[bb]
-            if steady:
-                layer_rows = geom[0]
-                wa = geom[1] - layer_rows // spf - wr                 # frame of the first new sub-band row
-                for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
-                    ldesc[bb, 1] = (st.layer_end - ws) * spf
-                    wn[bb] = ends[bb] - ws - wa
-        tpad = max(tmax, self._tcap)              # periodic schedules keep one window size for all phases (n_frames masks)
-        mel = np.zeros((B, tpad, self.dims.mel_channels), dtype=np.float32)
-        noise = np.zeros((B, tpad * spf), dtype=np.float32)
-        nfr = np.zeros((B,), dtype=np.int32)
-        states = np.zeros((B, 6), dtype=np.int32)
-        st_f = np.zeros((B, 2), dtype=np.float32)
-        next_state_frame = []
-        for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
-            mel[bb, :we - ws] = self._in_mel[st.slot, ws - st.base:we - st.base]
-            if self.dims.noise_sigma:
-                noise[bb, :(we - ws) * spf] = self._in_noise[st.slot, ws - st.base:we - st.base].reshape(-1)
-            nfr[bb] = we - ws
-            # the carried state sits at frame st.state_frame (>= ws + lead, or 0 at the utterance start): pulses are
-            # reproducible from there on.  The next state is captured where the NEXT window's reproducible region
-            # starts: `lag` = left - lead frames in front of the next emit position.
-            nxt = max(st.state_frame, st.emitted + nn - (self.left - self.lead))
-            st_f[bb, 0], st_f[bb, 1] = st.state[0], st.state[1]
-            states[bb, 2:5] = st.state[2], (st.state_frame - ws) * ppf, (nxt - ws) * ppf if nxt < we else -1
-            next_state_frame.append(nxt)
-        states[:, :2] = st_f.view(np.int32)                   # one mbx_stream_state per item (pack_state)
-        control = self._control
-        if control:
-            # the control rows of the whole windows (the frames behind an item's end are not read)
-            f0w = np.ones((B, tpad), dtype=np.float32)
-            scw = np.ones((B, tpad), dtype=np.float32)
-            for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
-                f0w[bb, :we - ws] = self._in_f0[st.slot, ws - st.base:we - st.base]
-                scw[bb, :we - ws] = self._in_scale[st.slot, ws - st.base:we - st.base]
-            f0_mask = np.asarray([st.f0_mode == "frames" for _, st, _ in todo], dtype=np.int32)
-        dev = self.engine.device
-        mel_d = torch.as_tensor(mel, device=dev)
-        noise_d = torch.as_tensor(noise, device=dev) if self.dims.noise_sigma else None
-        # every int32 argument of the call in one upload
-        use_fe = self.fe_carry and self.carry and tpad <= self._fe_ring
-        fpos = np.asarray([ws % self._fe_ring for ws, _ in windows], dtype=np.int32)
-        parts = [states.ravel(), desc.ravel(), ldesc.ravel(), nfr, act, wn if wn is not None else act, fpos]
-        if control:                                           # ... and the control rows with them (floats bit-cast)
-            parts += [f0_mask, f0w.ravel().view(np.int32), scw.ravel().view(np.int32)]
-        ints_d = torch.as_tensor(np.concatenate(parts), device=dev)
-        cuts = np.cumsum([0] + [pp.size for pp in parts])
-        states_d, desc_d, ldesc_d, nfr_d, act_d, wn_d, fpos_d = (ints_d[cuts[ii]:cuts[ii + 1]] for ii in range(7))
-        states_d, desc_d, ldesc_d = states_d.view(B, 6), desc_d.view(B, 5), ldesc_d.view(B, 3)
-        pitch = {}
-        if control:
-            pitch = {"f0_item_mask": ints_d[cuts[7]:cuts[8]],
-                     "f0_frames": ints_d[cuts[8]:cuts[9]].view(torch.float32).view(B, tpad),
-                     "f0_scale": ints_d[cuts[9]:cuts[10]].view(torch.float32).view(B, tpad)}
-        self.last_tick_frames = int(nfr.sum())
+        plan = plan_tick(self.geometry, [(st, nn) for _, st, nn in todo])
+        up = self._upload(plan, [st for _, st, _ in todo])
+        args, B = up.args, len(todo)
+        self.last_tick_frames = int(plan.nfr.sum())
+        self.last_tick_active_frames = int(plan.act.sum())
+        self.last_tick_wavenet_frames = int(plan.act.sum()) if plan.wn is None else int(plan.wn.sum())
+        self.last_tick_layer_rows = plan.layer_rows
+        if plan.layer_rows:
+            self.last_tick_wavenet_frames = B * plan.layer_rows // self.dims.steps_per_frame
         if self.time_device:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        self.last_tick_active_frames = int(act.sum())
-        self.last_tick_wavenet_frames = int(wn.sum()) if wn is not None else int(act.sum())
-        self.last_tick_layer_rows = layer_rows
-        if layer_rows:
-            self.last_tick_wavenet_frames = B * layer_rows // spf
+        pitch = {}
+        if up.control:
+            pitch = {"f0_item_mask": args.f0_item_mask, "f0_frames": args.f0_frames, "f0_scale": args.f0_scale}
         audio, state_out = self.engine.forward(
-            mel_d, n_frames=nfr_d, noise=noise_d, stream_state=states_d,
-            active=(a0, act_d, int(act.max())),
-            wavenet=(wa, wn_d, int(wn.max())) if wn is not None else None,
-            carry=(self._store, desc_d) if self.carry else None,
-            layers=(self._layer_store, ldesc_d, layer_rows) if self.layer_carry else None,
-            frontend=(self._fe_store, fpos_d, 0, 0) if use_fe else None,      # whole window computed, every frame kept
+            up.mel, n_frames=args.nfr, noise=up.noise, stream_state=args.states,
+            active=(plan.a0, args.act, int(plan.act.max())),
+            wavenet=(plan.wa, args.wn, int(plan.wn.max())) if plan.wn is not None else None,
+            carry=(self._store, args.desc) if self.carry else None,
+            layers=(self._layer_store, args.ldesc, plan.layer_rows) if self.layer_carry else None,
+            frontend=(self._fe_store, args.fpos, 0, 0) if up.use_fe else None,    # whole window computed, every frame kept
             **pitch)
         if self.time_device:
             ev1.record()
             ev1.synchronize()
             self.last_tick_device_ms = ev0.elapsed_time(ev1)
         # only the emitted samples come back: the columns [lo, hi) of the window that hold some item's chunk
-        lo = min((st.emitted - ws) * hop for (sid, st, nn), (ws, we) in zip(todo, windows))
-        hi = max((st.emitted - ws + nn) * hop for (sid, st, nn), (ws, we) in zip(todo, windows))
-        audio = audio[:, lo:hi].cpu().numpy()
-        state_out = state_out.cpu().numpy()
-        steady_ctx = None
-        # (mbx_window_advance keeps the part of a window that stays in LDS: at most 64 KB per item -- wide windows, e.g. the
-        # RMS normalisation with several smoothing iterations or deep pre-conditioning chains, run launch by launch)
-        window_fits = tpad * max(self.dims.mel_channels, spf) * 4 <= 64 * 1024
-        phases = {st.ticks % len(self.schedule) for _, st, _ in todo}
-        if (layer_rows and self.use_graph and self.periodic and window_fits and len(phases) == 1 and
-                len({nn for _, _, nn in todo}) == 1 and len(set(windows)) >= 1 and
-                len({(st.emitted - ws, we - ws) for (_, st, _), (ws, we) in zip(todo, windows)}) == 1):
-            # a steady tick: when this phase of the schedule comes round again with every stream continuing the same way,
-            # it is this launch sequence on windows that moved on by one period -- every window-relative argument is the
-            # same (_steady_status checks it)
-            (sid0, st0, nn0), (ws0, we0) = todo[0], windows[0]
-            steady_ctx = {
-                "phase": phases.pop(), "chunk": nn0, "T": we0 - ws0, "tpad": tpad, "a0": a0, "wa": wa, "lo": lo, "hi": hi,
-                "layer_rows": layer_rows, "act": act.copy(), "wn": wn.copy(), "nfr": nfr.copy(), "desc": desc.copy(),
-                "ldesc": ldesc.copy(), "state_consts": states[:, 3:5].copy(), "rel0": st0.emitted - ws0, "use_fe": use_fe,
-                "frames": self.last_tick_frames, "active_frames": self.last_tick_active_frames,
-                "wavenet_frames": self.last_tick_wavenet_frames, "ws0": ws0, "control": control}
+        hop = self.dims.hop_size
+        lo = min(rel * hop for rel in plan.rel)
+        hi = max((rel + nn) * hop for rel, nn in zip(plan.rel, plan.emit))
+        audio, state_out = audio[:, lo:hi].cpu().numpy(), state_out.cpu().numpy()
+        result = self._commit(plan, todo, audio, lo, state_out)
+        self._record_steady(plan, todo, up, lo, hi, state_out)
+        return result
+
+    def _upload(self, plan, streams):
+        """The windows of a plan, gathered from the shared input rows, and every int32 argument of the call in one upload
+        (with the control rows, floats bit-cast, once the synthesizer has seen pitch control)."""
+        import torch
+        B, spf, control = len(streams), self.dims.steps_per_frame, self._control
+        tpad = max(plan.tmax, self._tcap)         # periodic schedules keep one window size for all phases (n_frames masks)
+        mel = np.zeros((B, tpad, self.dims.mel_channels), dtype=np.float32)
+        noise = np.zeros((B, tpad * spf), dtype=np.float32)
+        # the control rows of the whole windows (the frames behind an item's end are not read)
+        f0_rows = np.ones((B, tpad * control), dtype=np.float32)
+        scale_rows = np.ones((B, tpad * control), dtype=np.float32)
+        for item, (st, (first, end)) in enumerate(zip(streams, plan.windows)):
+            w_mel, w_noise, w_f0, w_scale = self._rows.window(st.slot, first - st.base, end - st.base)
+            mel[item, :end - first] = w_mel
+            if self.dims.noise_sigma:
+                noise[item, :(end - first) * spf] = w_noise.reshape(-1)
             if control:
-                steady_ctx["f0_mask"] = f0_mask.copy()
+                f0_rows[item, :end - first], scale_rows[item, :end - first] = w_f0, w_scale
+        f0_mask = np.asarray([st.f0_mode == "frames" for st in streams], dtype=np.int32) if control else None
+        parts = [("states", plan.states, "int32"), ("desc", plan.desc, "int32"), ("ldesc", plan.ldesc, "int32"),
+                 ("nfr", plan.nfr, "int32"), ("act", plan.act, "int32"),
+                 ("wn", plan.wn if plan.wn is not None else plan.act, "int32"), ("fpos", plan.fpos, "int32"),
+                 ("f0_item_mask", f0_mask if control else np.zeros(0, np.int32), "int32"),
+                 ("f0_frames", f0_rows, "float32"), ("f0_scale", scale_rows, "float32")]
+        dev = self.engine.device
+        flat = np.concatenate([arr.ravel().view(np.int32) for _, arr, _ in parts])
+        args = _Layout([(name, arr.shape, dtype) for name, arr, dtype in parts]).views(torch.as_tensor(flat, device=dev))
+        return _TickInputs(mel=torch.as_tensor(mel, device=dev),
+                           noise=torch.as_tensor(noise, device=dev) if self.dims.noise_sigma else None, tpad=tpad, args=args,
+                           use_fe=self.fe_carry and self.carry and tpad <= self._fe_ring, control=control, f0_mask=f0_mask)
+
+    def _commit(self, plan, todo, audio, lo, state_out):
+        """Cut every stream's chunk out of the audio (whose column 0 is sample `lo` of the windows) and move the streams on
+        to what the plan says they carry from this tick."""
+        hop = self.dims.hop_size
         result = {}
-        for bb, ((sid, st, nn), (ws, we)) in enumerate(zip(todo, windows)):
-            a0 = (st.emitted - ws) * hop - lo
-            result[sid] = audio[bb, a0:a0 + nn * hop].copy()
+        for item, (sid, st, nn) in enumerate(todo):
+            at = plan.rel[item] * hop - lo
+            result[sid] = audio[item, at:at + nn * hop].copy()
             st.emitted += nn
             st.ticks += 1
-            st.carry_pos, st.carry_frames = next_carry[bb]
-            st.layer_end = next_layer_end[bb]
-            if next_state_frame[bb] < we:
-                ff = state_out[bb, :2].copy().view(np.float32)
-                st.state = (float(ff[0]), float(ff[1]), int(state_out[bb, 2]))
-                st.state_frame = next_state_frame[bb]
-        sids = [sid for sid, _, _ in todo]
-        if steady_ctx is None:
-            self._steady = None                   # not a steady tick: whatever run was being recorded is over
-        else:
-            run = self._steady
-            if run is None or run["sids"] != sids or run["tpad"] != tpad:
-                run = {"sids": sids, "streams": [st for _, st, _ in todo], "B": B, "tpad": tpad, "phases": {}, "graphs": {},
-                       "slots": np.asarray([st.slot for _, st, _ in todo], dtype=np.int64), "win": None, "shared": None}
-                self._steady = run
-            old = run["phases"].get(steady_ctx["phase"])
-            if old is not None and any(not np.array_equal(old[kk], steady_ctx[kk]) if isinstance(old[kk], np.ndarray)
-                                       else old[kk] != steady_ctx[kk] for kk in steady_ctx if kk != "ws0"):
-                run["graphs"].pop(steady_ctx["phase"], None)          # the geometry of this phase changed: capture it anew
-            run["phases"][steady_ctx["phase"]] = steady_ctx
-            # where the run stands: the windows this tick worked on (device tensors) and their first frame, the streams'
-            # progress and phase states as vectors (replayed ticks keep them there, _sync_streams writes them back)
-            run["win_src"] = (mel_d, noise_d)
-            run["win_ws0"] = steady_ctx["ws0"]
-            run["win_T"] = steady_ctx["T"]
-            run["state_v"] = state_out.copy()
-            run["emitted_v"] = np.asarray([st.emitted for _, st, _ in todo], dtype=np.int64)
-            run["next_phase"] = todo[0][1].ticks % len(self.schedule)
-            run["pending"], run["pending_frames"] = 0, 0
-            run.pop("need_v", None)
+            st.carry_pos, st.carry_frames = plan.next_carry[item]
+            st.layer_end = plan.next_layer_end[item]
+            if plan.next_state_frame[item] < plan.windows[item][1]:
+                sums = state_out[item, :2].copy().view(np.float32)
+                st.state = (float(sums[0]), float(sums[1]), int(state_out[item, 2]))
+                st.state_frame = plan.next_state_frame[item]
         return result
+
+    def _record_steady(self, plan, todo, up, lo, hi, state_out):
+        """After a committed tick: if it was a steady tick that a graph could stand for, record it as its phase of the
+        steady run (starting a new run if the streams or the window size changed); any other tick ends the run."""
+        n_ph, spf = len(self.schedule), self.dims.steps_per_frame
+        streams = [st for _, st, _ in todo]
+        # (mbx_window_advance keeps the part of a window that stays in LDS: at most 64 KB per item -- wide windows, e.g. the
+        # RMS normalisation with several smoothing iterations or deep pre-conditioning chains, run launch by launch)
+        window_fits = up.tpad * max(self.dims.mel_channels, spf) * 4 <= 64 * 1024
+        phases = {(st.ticks - 1) % n_ph for st in streams}
+        if not (plan.layer_rows and self.use_graph and self.periodic and window_fits and len(phases) == 1 and
+                len(set(plan.emit)) == 1 and len(set(zip(plan.rel, plan.nfr.tolist()))) == 1):
+            self._steady = None                   # not a steady tick: whatever run was being recorded is over
+            return
+        # a steady tick: when this phase of the schedule comes round again with every stream continuing the same way,
+        # it is this launch sequence on windows that moved on by one period -- every window-relative argument is the
+        # same (_steady_status checks it)
+        new = _Phase(
+            phase=phases.pop(), chunk=plan.emit[0], T=int(plan.nfr[0]), tpad=up.tpad, a0=plan.a0, wa=plan.wa, lo=lo, hi=hi,
+            layer_rows=plan.layer_rows, act=plan.act.copy(), wn=plan.wn.copy(), nfr=plan.nfr.copy(), desc=plan.desc.copy(),
+            ldesc=plan.ldesc.copy(), state_consts=plan.states[:, 3:5].copy(), rel0=plan.rel[0], use_fe=up.use_fe,
+            frames=self.last_tick_frames, active_frames=self.last_tick_active_frames,
+            wavenet_frames=self.last_tick_wavenet_frames, control=up.control, f0_mask=up.f0_mask)
+        sids = [sid for sid, _, _ in todo]
+        run = self._steady
+        if run is None or run.sids != sids or run.tpad != up.tpad:
+            run = self._steady = _SteadyRun(sids=sids, streams=streams, B=len(todo), tpad=up.tpad,
+                                            slots=np.asarray([st.slot for st in streams], dtype=np.int64))
+        old = run.phases.get(new.phase)
+        if old is not None and not old.same_geometry(new):
+            run.graphs.pop(new.phase, None)               # the geometry of this phase changed: capture it anew
+        run.phases[new.phase] = new
+        # where the run stands: the windows this tick worked on (device tensors), the streams' progress and phase states
+        run.win_src = (up.mel, up.noise)
+        run.state_v = state_out.copy()
+        run.emitted_v = np.asarray([st.emitted for st in streams], dtype=np.int64)
+        run.next_phase = streams[0].ticks % n_ph
+        run.pending, run.pending_frames = 0, 0
+        run.need_v = None
 
     # ------------------------------------------------------------------------------------------------------------------
     # steady ticks as replayed hipGraphs (one per phase of the tick schedule)
@@ -642,18 +703,18 @@ class StreamingSynthesizer:
         """Write the progress of the replayed ticks back to the stream objects (inside a run of replayed ticks it is kept
         in vectors: emitted frames, carried phase states)."""
         run = self._steady
-        if run is None or not run["pending"]:
+        if run is None or not run.pending:
             return
-        adv = run["pending_frames"]
-        sf = run["state_v"][:, :2].copy().view(np.float32)
-        for bb, st in enumerate(run["streams"]):
-            st.ticks += run["pending"]
+        adv = run.pending_frames
+        sf = run.state_v[:, :2].copy().view(np.float32)
+        for bb, st in enumerate(run.streams):
+            st.ticks += run.pending
             st.emitted += adv
             st.carry_pos = st.emitted
             st.layer_end += adv
             st.state_frame += adv
-            st.state = (float(sf[bb, 0]), float(sf[bb, 1]), int(run["state_v"][bb, 2]))
-        run["pending"], run["pending_frames"] = 0, 0
+            st.state = (float(sf[bb, 0]), float(sf[bb, 1]), int(run.state_v[bb, 2]))
+        run.pending, run.pending_frames = 0, 0
 
     def _leave_steady(self):
         self._sync_streams()
@@ -667,85 +728,77 @@ class StreamingSynthesizer:
         the streams continue but this phase has no recorded tick yet (it runs launch by launch and is recorded);
         "broken" -- anything else."""
         run = self._steady
-        streams, B = run["streams"], run["B"]
-        if self._inputs_changed or "need_v" not in run:
+        streams, B = run.streams, run.B
+        if self._inputs_changed or run.need_v is None:
             # frames received (+ whether the stream is closed: its last frame must then lie behind the window) and the
             # column of absolute frame 0 in the shared input rows; only push() changes them
-            run["need_v"] = np.fromiter((st.have - st.closed for st in streams), np.int64, B)
-            run["base_v"] = np.fromiter((st.base for st in streams), np.int64, B)
+            run.need_v = np.fromiter((st.have - st.closed for st in streams), np.int64, B)
+            run.base_v = np.fromiter((st.base for st in streams), np.int64, B)
             self._inputs_changed = False
-        phase = run["next_phase"]
+        phase = run.next_phase
         chunk = self.schedule[phase]
-        emitted = run["emitted_v"]
-        if int((run["need_v"] - emitted).min()) < chunk + self.right:
+        emitted = run.emitted_v
+        if int((run.need_v - emitted).min()) < chunk + self.right:
             return "broken"
         if len(self.streams) != B:                        # a stream outside the recorded set must not be ready
-            inside = set(run["sids"])
+            inside = set(run.sids)
             if any(self._ready(st) > 0 for sid, st in self.streams.items() if sid not in inside):
                 return "broken"
-        ctx = run["phases"].get(phase)
-        if ctx is None or (phase - 1) % len(self.schedule) not in run["phases"]:
+        rec = run.phases.get(phase)
+        if rec is None or (phase - 1) % len(self.schedule) not in run.phases:
             return "record"                               # (a phase's graph shifts the window of the phase before it)
         ws = np.maximum(0, ((emitted - self.left) // self.align) * self.align)
-        if np.any(emitted - ws != ctx["rel0"]) or ctx["chunk"] != chunk:
+        if np.any(emitted - ws != rec.rel0) or rec.chunk != chunk:
             return "broken"
         return "replay"
 
     def _capture(self, run, phase):
         """Fixed buffers + the captured launch sequence of the steady tick of one phase of the schedule.  All phases of a
-        run work on ONE pair of device-resident windows (run["win"]: mel (B, tpad, channels), noise (B, tpad * spf)); a
+        run work on ONE pair of device-resident windows (run.win: mel (B, tpad, channels), noise (B, tpad * spf)); a
         tick moves them on -- shift by the frames the aligned window start advanced since the tick before, append the
         tick's new frames -- and runs the forward pass with the phase's constant arguments."""
         import torch
-        ctx = run["phases"][phase]
+        rec = run.phases[phase]
         n_ph = len(self.schedule)
-        prev = run["phases"][(phase - 1) % n_ph]
+        prev = run.phases[(phase - 1) % n_ph]
         eng, dims, dev = self.engine, self.dims, self.engine.device
-        B, tpad, chunk, spf, hop = run["B"], run["tpad"], ctx["chunk"], dims.steps_per_frame, dims.hop_size
+        B, tpad, chunk, spf, hop = run.B, run.tpad, rec.chunk, dims.steps_per_frame, dims.hop_size
         # the window of the tick before held T_prev frames from ws_prev on; this one T frames from ws on: the start moved
         # by `shift` = (emitted - rel0) - (emitted_prev - rel0_prev) frames, `chunk` frames are new at the end
-        shift = prev["chunk"] - (ctx["rel0"] - prev["rel0"])
-        keep = prev["T"] - shift
-        if shift < 0 or keep < 0 or keep + chunk != ctx["T"] or ctx["T"] > tpad:
+        shift = prev.chunk - (rec.rel0 - prev.rel0)
+        keep = prev.T - shift
+        if shift < 0 or keep < 0 or keep + chunk != rec.T or rec.T > tpad:
             raise RuntimeError(f"steady ticks of phases {(phase - 1) % n_ph} and {phase} do not chain: shift {shift}, "
-                               f"windows {prev['T']} -> {ctx['T']} frames, chunk {chunk}")
+                               f"windows {prev.T} -> {rec.T} frames, chunk {chunk}")
         use_noise = bool(dims.noise_sigma)
-        if run["win"] is None:
+        if run.win is None:
             mel_win = torch.zeros((B, tpad, dims.mel_channels), dtype=torch.float32, device=dev)
             noise_win = torch.zeros((B, tpad * spf), dtype=torch.float32, device=dev) if use_noise else None
-            run["win"] = (mel_win, noise_win)
-            run["shared"] = {
-                "audio_buf": torch.empty((B, tpad * hop), dtype=torch.float32, device=dev),
-                "state_out": torch.empty((B, 6), dtype=torch.int32, device=dev),
-                "state_host": torch.empty((B, 6), dtype=torch.int32).pin_memory()}
-        mel_win, noise_win = run["win"]
-        shared = run["shared"]
-        n_mel, n_noise = B * chunk * dims.mel_channels, (B * chunk * spf if use_noise else 0)
+            run.win = (mel_win, noise_win)
+            run.audio_buf = torch.empty((B, tpad * hop), dtype=torch.float32, device=dev)
+            run.state_out = torch.empty((B, 6), dtype=torch.int32, device=dev)
+            run.state_host = torch.empty((B, 6), dtype=torch.int32).pin_memory()
+        mel_win, noise_win = run.win
         # one pinned host buffer / one device buffer for everything a tick uploads: new mel frames, new noise, phase states,
         # ring positions and -- once the synthesizer has seen pitch control -- the control rows of the whole windows
         # (B, tpad) each: small next to the mel frames, and the window they belong to is known to the host anyway, so they
         # need no device-resident window and no second move launch
-        n_ctl = B * tpad if ctx["control"] else 0
-        stage_host = torch.ones(n_mel + n_noise + B * 7 + 2 * n_ctl, dtype=torch.float32).pin_memory()
+        layout = _stage_layout(B, chunk, tpad, dims.mel_channels, spf, use_noise, rec.control)
+        stage_host = torch.ones(layout.size, dtype=torch.float32).pin_memory()
         stage_dev = torch.empty_like(stage_host, device=dev)
-        mel_new = stage_dev[:n_mel].view(B, chunk, dims.mel_channels)
-        noise_new = stage_dev[n_mel:n_mel + n_noise].view(B, chunk * spf) if use_noise else None
-        states_d = stage_dev[n_mel + n_noise:n_mel + n_noise + B * 6].view(torch.int32).view(B, 6)
-        fpos_d = stage_dev[n_mel + n_noise + B * 6:n_mel + n_noise + B * 7].view(torch.int32)
+        new = layout.views(stage_dev)
         pitch = {}
-        if ctx["control"]:
-            n_ints = n_mel + n_noise + B * 7
-            pitch = {"f0_frames": stage_dev[n_ints:n_ints + n_ctl].view(B, tpad),
-                     "f0_scale": stage_dev[n_ints + n_ctl:].view(B, tpad),
-                     "f0_item_mask": torch.as_tensor(ctx["f0_mask"], device=dev)}
+        if rec.control:
+            pitch = {"f0_frames": new.f0_frames, "f0_scale": new.f0_scale,
+                     "f0_item_mask": torch.as_tensor(rec.f0_mask, device=dev)}
         # front end: the window gained `chunk` frames and the last fe_right frames of the window before were inexact: the
-        # sub-nets run on the last chunk + fe_right (+ their reach) frames in front of the window's end (frame ctx["T"] of the
+        # sub-nets run on the last chunk + fe_right (+ their reach) frames in front of the window's end (frame rec.T of the
         # buffer: fe_end_frames), everything in front of that comes from the ring
         fe_new, fe_margin = chunk + self.fe_right, self.fe_left
-        use_fe = ctx["use_fe"] and fe_new + fe_margin <= ctx["T"]
-        ints = {kk: torch.as_tensor(ctx[kk], device=dev) for kk in ("act", "wn", "nfr", "desc", "ldesc")}
-        audio_buf, state_out, state_host = shared["audio_buf"], shared["state_out"], shared["state_host"]
-        audio_host = torch.empty((B, ctx["hi"] - ctx["lo"]), dtype=torch.float32).pin_memory()
+        use_fe = rec.use_fe and fe_new + fe_margin <= rec.T
+        ints = {kk: torch.as_tensor(getattr(rec, kk), device=dev) for kk in ("act", "wn", "nfr", "desc", "ldesc")}
+        audio_buf, state_out, state_host = run.audio_buf, run.state_out, run.state_host
+        audio_host = torch.empty((B, rec.hi - rec.lo), dtype=torch.float32).pin_memory()
         graph = torch.cuda.CUDAGraph()
         torch.cuda.synchronize(dev)
         # thread_local: another thread of the process (the RCCL watchdog of a multi-rank job) may touch the runtime while
@@ -753,39 +806,37 @@ class StreamingSynthesizer:
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             stage_dev.copy_(stage_host, non_blocking=True)
             # shift the kept frames to the front and append the tick's new ones: one launch whatever the schedule
-            eng.window_update(mel_win, mel_new, noise_win, noise_new, shift, keep)
-            eng.forward(mel_win, n_frames=ints["nfr"], noise=noise_win, stream_state=states_d,
-                        active=(ctx["a0"], ints["act"], int(ctx["act"].max())),
-                        wavenet=(ctx["wa"], ints["wn"], int(ctx["wn"].max())),
+            eng.window_update(mel_win, new.mel, noise_win, new.noise, shift, keep)
+            eng.forward(mel_win, n_frames=ints["nfr"], noise=noise_win, stream_state=new.states,
+                        active=(rec.a0, ints["act"], int(rec.act.max())),
+                        wavenet=(rec.wa, ints["wn"], int(rec.wn.max())),
                         carry=(self._store, ints["desc"].view(B, 5)) if self.carry else None,
-                        layers=(self._layer_store, ints["ldesc"].view(B, 3), ctx["layer_rows"]),
-                        frontend=(self._fe_store, fpos_d, fe_new if use_fe else 0, fe_margin if use_fe else 0, ctx["T"])
-                        if ctx["use_fe"] else None,
+                        layers=(self._layer_store, ints["ldesc"].view(B, 3), rec.layer_rows),
+                        frontend=(self._fe_store, new.fpos, fe_new if use_fe else 0, fe_margin if use_fe else 0, rec.T)
+                        if rec.use_fe else None,
                         out=audio_buf, state_out=state_out, **pitch)
             # the emitted samples of every stream: one strided device-to-host copy (no device-side gather in between)
-            eng.emit_rows(audio_buf, ctx["lo"], ctx["hi"] - ctx["lo"], audio_host)
+            eng.emit_rows(audio_buf, rec.lo, rec.hi - rec.lo, audio_host)
             state_host.copy_(state_out, non_blocking=True)
-        n_state = n_mel + n_noise
-        return {"graph": graph, "stage_host": stage_host, "stage_np": stage_host.numpy(), "n_mel": n_mel,
-                "arange": np.arange(chunk, dtype=np.int64), "n_noise": n_noise, "n_state": n_state,
-                "audio_host": audio_host, "state_host": state_host, "shift": shift, "keep": keep,
-                "n_ints": n_state + B * 7, "n_ctl": n_ctl, "arange_win": np.arange(ctx["T"], dtype=np.int64),
-                "keep_alive": (stage_dev, ints, pitch)}
+        return _CapturedTick(graph=graph, stage_host=stage_host, host=layout.views(stage_host.numpy()),
+                             arange=np.arange(chunk, dtype=np.int64), arange_win=np.arange(rec.T, dtype=np.int64),
+                             audio_host=audio_host, state_host=state_host, shift=shift, keep=keep,
+                             keep_alive=(stage_dev, ints, pitch))
 
     def _graph_tick(self):
         """A steady tick as one graph launch: gather and upload the new frames and the phase states, replay, read the
         chunk back.  Nothing here loops over the streams."""
         import torch
         run = self._steady
-        phase = run["next_phase"]
-        ctx = run["phases"][phase]
+        phase = run.next_phase
+        rec = run.phases[phase]
         n_ph = len(self.schedule)
-        gg = run["graphs"].get(phase)
-        if gg is None:
+        cap = run.graphs.get(phase)
+        if cap is None:
             try:
-                if (phase - 1) % n_ph not in run["phases"]:
+                if (phase - 1) % n_ph not in run.phases:
                     raise RuntimeError("the phase in front of this one has no recorded tick")
-                gg = run["graphs"][phase] = self._capture(run, phase)
+                cap = run.graphs[phase] = self._capture(run, phase)
             except Exception as exc:                          # noqa: BLE001 -- whatever made the capture fail
                 # the streams must not get stuck retrying a capture that cannot succeed: from here on every tick runs
                 # launch by launch (bit-identical results, more host time)
@@ -795,56 +846,48 @@ class StreamingSynthesizer:
                 self.use_graph = False
                 self._leave_steady()
                 return self.tick()
-        dims, chunk = self.dims, ctx["chunk"]
-        hop, B = dims.hop_size, run["B"]
+        chunk, hop = rec.chunk, self.dims.hop_size
         # the device windows hold the window of the tick before: written there by a replayed tick, or still in the tensors a
         # launch-by-launch tick uploaded
-        if run["win_src"] is not run["win"]:
-            src_mel, src_noise = run["win_src"]
-            run["win"][0].copy_(src_mel)
-            if run["win"][1] is not None:
-                run["win"][1].copy_(src_noise)
-            run["win_src"] = run["win"]
-        stage = gg["stage_np"]
-        emitted, slots = run["emitted_v"], run["slots"]
-        base = run["base_v"]
+        if run.win_src is not run.win:
+            src_mel, src_noise = run.win_src
+            run.win[0].copy_(src_mel)
+            if run.win[1] is not None:
+                run.win[1].copy_(src_noise)
+            run.win_src = run.win
+        host, emitted, slots, base = cap.host, run.emitted_v, run.slots, run.base_v
         # the frames the windows gain: [emitted + right, emitted + right + chunk) of every stream
-        cols = (emitted + self.right - base)[:, None] + gg["arange"]
-        np.copyto(stage[:gg["n_mel"]].reshape(B, chunk, dims.mel_channels), self._in_mel[slots[:, None], cols])
-        if gg["n_noise"]:
-            np.copyto(stage[gg["n_mel"]:gg["n_state"]].reshape(B, chunk, dims.steps_per_frame),
-                      self._in_noise[slots[:, None], cols])
-        ints = stage[gg["n_state"]:gg["n_ints"]].view(np.int32)
-        states = ints[:B * 6].reshape(B, 6)
-        ints[B * 6:] = (emitted - ctx["rel0"]) % self._fe_ring              # ring frame of each window's first frame
-        if gg["n_ctl"]:
+        cols = (emitted + self.right - base)[:, None] + cap.arange
+        self._rows.gather(slots, cols, mel=host.mel)
+        if host.noise is not None:
+            self._rows.gather(slots, cols, noise=host.noise.reshape(run.B, chunk, -1))
+        host.fpos[:] = (emitted - rec.rel0) % self._fe_ring                   # ring frame of each window's first frame
+        if host.f0_frames is not None:
             # the control rows of the whole windows [emitted - rel0, + T): one gather per row
-            wcols = (emitted - ctx["rel0"] - base)[:, None] + gg["arange_win"]
-            n_ints, n_ctl, tpad, T = gg["n_ints"], gg["n_ctl"], run["tpad"], ctx["T"]
-            stage[n_ints:n_ints + n_ctl].reshape(B, tpad)[:, :T] = self._in_f0[slots[:, None], wcols]
-            stage[n_ints + n_ctl:].reshape(B, tpad)[:, :T] = self._in_scale[slots[:, None], wcols]
-        states[:, :3] = run["state_v"][:, :3]
-        states[:, 3:5] = ctx["state_consts"]
-        states[:, 5] = 0
+            wcols = (emitted - rec.rel0 - base)[:, None] + cap.arange_win
+            self._rows.gather(slots, wcols, f0=host.f0_frames[:, :rec.T], scale=host.f0_scale[:, :rec.T])
+        host.states[:, :3] = run.state_v[:, :3]
+        host.states[:, 3:5] = rec.state_consts
+        host.states[:, 5] = 0
         if self.time_device:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        gg["graph"].replay()
+        cap.graph.replay()
         if self.time_device:
             ev1.record()
         torch.cuda.current_stream(self.engine.device).synchronize()
         if self.time_device:
             self.last_tick_device_ms = ev0.elapsed_time(ev1)
-        audio = gg["audio_host"].numpy().copy()
-        run["state_v"] = gg["state_host"].numpy().copy()
-        a0 = ctx["rel0"] * hop - ctx["lo"]
-        result = dict(zip(run["sids"], audio[:, a0:a0 + chunk * hop]))
+        audio = cap.audio_host.numpy().copy()
+        run.state_v = cap.state_host.numpy().copy()
+        at = rec.rel0 * hop - rec.lo
+        result = dict(zip(run.sids, audio[:, at:at + chunk * hop]))
         emitted += chunk
-        run["pending"] += 1
-        run["pending_frames"] += chunk
-        run["next_phase"] = (phase + 1) % n_ph
-        self.last_tick_frames, self.last_tick_active_frames = ctx["frames"], ctx["active_frames"]
-        self.last_tick_wavenet_frames, self.last_tick_layer_rows = ctx["wavenet_frames"], ctx["layer_rows"]
+        run.pending += 1
+        run.pending_frames += chunk
+        run.next_phase = (phase + 1) % n_ph
+        self.last_tick_frames, self.last_tick_active_frames = rec.frames, rec.active_frames
+        self.last_tick_wavenet_frames, self.last_tick_layer_rows = rec.wavenet_frames, rec.layer_rows
         self.last_tick_replayed = True
         self.graph_ticks += 1
         return result

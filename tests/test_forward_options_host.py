@@ -1,0 +1,136 @@
+"""MBExWNEngine.forward on the host (no GPU, no library): which library entry point a combination of arguments takes
+(engine.forward_entry_point) and which combinations are refused, against a table written out from the forward that had
+one copy of the call per branch."""
+import itertools
+
+import pytest
+import torch
+
+from mbexwn_vocoder_amd import engine
+from mbexwn_vocoder_amd.config import ModelDims, canonical_config
+
+B, T = 2, 12
+
+
+class _HostEngine(engine.MBExWNEngine):
+    """The engine without a library handle: enough for the argument checks of forward, on CPU tensors."""
+
+    def __init__(self):
+        self.config = canonical_config("SPEECH")
+        self.dims, self.device, self._torch = ModelDims(self.config), torch.device("cpu"), torch
+
+
+def _arguments(eng, state=False, active=False, control=None, f0=False, transposition=1.0, wavenet=False, carry=False,
+               layers=False, frontend=False):
+    """The arguments of _forward_options with well-formed tensors for everything that is asked for."""
+    ints = lambda *shape: torch.zeros(shape, dtype=torch.int32)                                     # noqa: E731
+    floats = lambda *shape: torch.ones(shape, dtype=torch.float32)                                  # noqa: E731
+    control = control or ()
+    return dict(
+        B=B, T=T, stream_state=ints(B, 6) if state else None, state_out=None,
+        active=(2, ints(B), 8) if active else None, wavenet=(4, ints(B), 6) if wavenet else None,
+        carry=(floats(4, 180, eng.dims.subbands), ints(B, 5)) if carry else None,
+        layers=(floats(4, 64), ints(B, 3), 0) if layers else None,
+        frontend=(floats(4, 64, eng.frontend_frame_floats), ints(B), 0, 0) if frontend else None,
+        f0=floats(B, T * eng.dims.pulse_per_frame) if f0 else None, transposition=transposition,
+        f0_frames=floats(B, T) if "f0_frames" in control else None, f0_scale=floats(B, T) if "f0_scale" in control else None,
+        f0_item_mask=ints(B) if "f0_item_mask" in control else None)
+
+
+# (state, active, control, f0, transposition other than 1) -> entry point; the combinations that are missing are refused
+ENTRY = {
+    (False, False, False, False, False): "mbx_forward",
+    (False, False, False, True, False): "mbx_forward_ex",
+    (False, False, False, False, True): "mbx_forward_ex",
+    (False, False, False, True, True): "mbx_forward_ex",
+    (False, False, True, False, False): "mbx_forward_ex",
+    (False, False, True, True, False): "mbx_forward_ex",          # f0 next to f0_scale; next to f0_frames it is refused
+    (True, False, False, False, False): "mbx_forward_stream",
+    (True, False, True, False, False): "mbx_forward_ex",
+    (True, True, False, False, False): "mbx_forward_ex",
+    (True, True, True, False, False): "mbx_forward_ex",
+}
+CONTROLS = (("f0_frames",), ("f0_scale",), ("f0_frames", "f0_scale"), ("f0_frames", "f0_item_mask"),
+            ("f0_frames", "f0_scale", "f0_item_mask"))
+
+
+def test_entry_point_table():
+    """Every combination of the five flags: the pure chooser on the legal ones, and the checked path -- entry point, the
+    options' transposition (1 in a stream, the given factor for whole items), the state tensors -- on all 32."""
+    eng = _HostEngine()
+    for flags in itertools.product((False, True), repeat=5):
+        state, active, control, f0, transposed = flags
+        factor = 1.5 if transposed else 1.0
+        for rows in (CONTROLS if control else ((),)):
+            args = _arguments(eng, state=state, active=active, control=rows, f0=f0, transposition=factor)
+            if flags not in ENTRY or (f0 and "f0_frames" in rows):
+                with pytest.raises(ValueError):
+                    eng._forward_options(**args)
+                continue
+            assert engine.forward_entry_point(*flags) == ENTRY[flags], flags
+            entry, opt, alive, state_in, state_out = eng._forward_options(**args)
+            assert entry == ENTRY[flags], (flags, rows)
+            assert (opt is not None) == (entry == "mbx_forward_ex")
+            assert (state_in is not None) == (state_out is not None) == state
+            if opt is not None:
+                assert opt.struct_size == engine.ctypes.sizeof(engine.mbx_forward_options)
+                assert opt.transposition == (1.0 if state else factor)
+                assert (opt.state_in, opt.state_out) == ((state_in.data_ptr(), state_out.data_ptr()) if state else (None, None))
+                assert bool(opt.f0) == f0 and bool(opt.active_frames) == active
+                for name in ("f0_frames", "f0_scale", "f0_item_mask"):
+                    assert bool(getattr(opt, name)) == (name in rows), (flags, rows, name)
+                # whatever the options point at stays alive with them
+                held = {tt.data_ptr() for tt in alive if tt is not None}
+                assert {pp for pp in (opt.f0, opt.active_frames, opt.f0_frames, opt.f0_scale, opt.f0_item_mask) if pp} <= held
+
+
+REFUSED = [
+    ("active without state", dict(active=True), "pass stream_state as well"),
+    ("wavenet without state", dict(wavenet=True), "pass stream_state as well"),
+    ("carry without state", dict(carry=True), "pass stream_state as well"),
+    ("layers without state", dict(layers=True), "pass stream_state as well"),
+    ("wavenet without active", dict(state=True, wavenet=True), "pass active as well"),
+    ("carry without active", dict(state=True, carry=True), "pass active as well"),
+    ("layers without active", dict(state=True, layers=True), "pass active as well"),
+    ("frontend without active", dict(state=True, frontend=True), "pass active as well"),
+    ("f0 with state", dict(state=True, f0=True), "apply to whole items: not with stream_state"),
+    ("transposition with state", dict(state=True, active=True, transposition=2.0), "apply to whole items: not with stream_state"),
+    ("f0_frames with f0", dict(f0=True, control=("f0_frames",)), "exclude each other"),
+    ("f0_item_mask without f0_frames", dict(control=("f0_scale", "f0_item_mask")), "f0_item_mask needs f0_frames"),
+    ("control with transposition", dict(control=("f0_scale",), transposition=2.0), "need transposition == 1"),
+    ("control with transposition in a stream", dict(state=True, control=("f0_frames",), transposition=0.5),
+     "apply to whole items: not with stream_state"),               # the first of the two checks that both hold
+    ("transposition not positive", dict(transposition=-1.0), "transposition must be positive"),
+    ("frontend without carry", dict(state=True, active=True, frontend=True), "carry is required"),
+]
+
+
+@pytest.mark.parametrize("case", REFUSED, ids=[cc[0] for cc in REFUSED])
+def test_refused_combinations(case):
+    _, asked, text = case
+    eng = _HostEngine()
+    with pytest.raises(ValueError, match=text):
+        eng._forward_options(**_arguments(eng, **asked))
+
+
+def test_window_arguments_reach_the_options():
+    """A whole streaming window: every field of the options its arguments set, and the shapes that are refused."""
+    eng = _HostEngine()
+    args = _arguments(eng, state=True, active=True, wavenet=True, carry=True, layers=True, frontend=True,
+                      control=("f0_frames", "f0_scale", "f0_item_mask"))
+    args["layers"] = args["layers"][:2] + (160,)
+    args["frontend"] = args["frontend"][:2] + (9, 3, 11)
+    entry, opt, alive, _, _ = eng._forward_options(**args)
+    assert entry == "mbx_forward_ex"
+    assert (opt.active_begin, opt.active_max_frames, opt.wn_begin, opt.wn_max_frames) == (2, 8, 4, 6)
+    assert (opt.sub_store, opt.sub_store_rows, opt.sub_carry) == (args["carry"][0].data_ptr(), 180, args["carry"][1].data_ptr())
+    assert (opt.layer_store, opt.layer_store_floats, opt.layer_rows) == (args["layers"][0].data_ptr(), 64, 160)
+    assert (opt.fe_store, opt.fe_ring_frames, opt.fe_new_frames, opt.fe_margin_frames, opt.fe_end_frames) == (
+        args["frontend"][0].data_ptr(), 64, 9, 3, 11)
+    assert {opt.active_frames, opt.wn_frames, opt.sub_carry, opt.layer_carry, opt.fe_pos} <= {tt.data_ptr() for tt in alive}
+    for name, bad in (("active", (T, args["active"][1])), ("wavenet", (1, args["wavenet"][1])),
+                      ("carry", (args["carry"][0], torch.zeros((B, 4), dtype=torch.int32))),
+                      ("layers", (args["layers"][0], torch.zeros((B, 3), dtype=torch.int64), 0)),
+                      ("stream_state", torch.zeros((B, 5), dtype=torch.int32))):
+        with pytest.raises(ValueError):
+            eng._forward_options(**dict(args, **{name: bad}))

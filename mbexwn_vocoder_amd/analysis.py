@@ -143,3 +143,104 @@ def compute_log_mel_device(sound, preprocess_config, n_samples=None):
                                                ctypes.c_float(float(np.finfo(np.float32).eps)), out.data_ptr(), frames,
                                                torch.cuda.current_stream(dev).cuda_stream))
     return out, cfg["sample_rate"] / hop
+
+
+def mell_header(preprocess_config):
+    """The entries of a ``.mell`` dictionary apart from ``mell`` itself (reference bin/generate_mel.py:41-52)."""
+    cfg = preprocess_config
+    return {'nfft': cfg["fft_size"],
+            'hoplen': cfg["hop_size"],
+            'winlen': cfg.get("win_size", cfg["fft_size"]),
+            'nmels': cfg["mel_channels"],
+            'sr': cfg['sample_rate'],
+            'fmin': cfg['fmin'],
+            'fmax': cfg['fmax'],
+            'lin_spec_offset': cfg['lin_amp_off'],
+            'lin_spec_scale': cfg['lin_amp_scale'],
+            'log_spec_offset': 0.,
+            'log_spec_scale': cfg['mel_amp_scale'],
+            "time_axis": 1}
+
+
+def _add(stats, key, seconds):
+    if stats is not None:
+        stats[key] = stats.get(key, 0.0) + seconds
+
+
+def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None):
+    """Sounds -> ``.mell`` dictionaries (reference bin/generate_mel.py:54-64 for a list of files): ``sounds`` is a list of 1-D
+    float32 arrays, ``rates`` their sample rates.  A sound that is not at the model rate goes through the reference's resampler
+    (resample.py); one already at it skips that step.  Needs the ``preprocess_config`` alone: no engine, no weights.
+
+    ``on_device``: the items are grouped by rate and run in padded micro-batches of at most ``batch`` items through
+    ``resample_device`` straight into ``compute_log_mel_device`` (the lengths stay on the device), with one copy back per
+    micro-batch; an item's bits do not depend on the batch it ran in.  Otherwise numpy, one item at a time (``resample_host``,
+    ``compute_log_mel``).  ``stats``: a dict that collects seconds per step (resample, analysis, upload, copy_back); on the
+    device that costs one wait per micro-batch."""
+    import time
+    from . import resample
+    cfg = preprocess_config
+    target, hop = int(cfg["sample_rate"]), int(cfg["hop_size"])
+    win_len = int(cfg.get("win_size", cfg["fft_size"]))
+    sounds = [np.ascontiguousarray(ss, dtype=np.float32) for ss in sounds]
+    rates = [int(round(rr)) for rr in rates]
+    if len(sounds) != len(rates):
+        raise ValueError("generate_mels: one rate per sound")
+    for ii, ss in enumerate(sounds):
+        if ss.ndim != 1 or ss.size == 0:
+            raise ValueError(f"generate_mels: sound {ii} must be a non-empty 1-D array, got shape {ss.shape}")
+    out = [None] * len(sounds)
+    if not on_device:
+        for ii, (ss, rr) in enumerate(zip(sounds, rates)):
+            t0 = time.perf_counter()
+            if rr != target:
+                ss = resample.resample_host(ss, rr, target)
+            t1 = time.perf_counter()
+            mel, _ = compute_log_mel(ss[np.newaxis], cfg, dtype=np.float32)
+            _add(stats, "resample", t1 - t0)
+            _add(stats, "analysis", time.perf_counter() - t1)
+            out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[0].T))
+        return out
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("generate_mels(on_device=True): no GPU available (on_device=False is the host path)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    by_rate = {}
+    for ii, rr in enumerate(rates):
+        by_rate.setdefault(rr, []).append(ii)
+    for rr, members in by_rate.items():
+        members = sorted(members, key=lambda ii: -sounds[ii].size)         # neighbours in length share a launch: less padding
+        for start in range(0, len(members), max(1, int(batch))):
+            group = members[start:start + max(1, int(batch))]
+            lengths = [sounds[ii].size for ii in group]
+            host = np.zeros((len(group), max(lengths)), dtype=np.float32)
+            for bb, ii in enumerate(group):
+                host[bb, :lengths[bb]] = sounds[ii]
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if stats is not None else None
+            if marks:
+                marks[0].record()
+            snd = torch.as_tensor(host).to(dev)
+            n_dev = torch.as_tensor(np.asarray(lengths, dtype=np.int32)).to(dev)
+            if marks:
+                marks[1].record()
+            if rr != target:
+                _, up, down = resample.device_taps(rr, target, dev)
+                snd, n_dev = resample.resample_device(snd, n_dev, rr, target)
+                lengths = [-(-nn * up // down) for nn in lengths]
+            if snd.shape[1] < win_len // 2 + 1:                # the analysis kernel wants rows of at least half a window
+                snd = torch.nn.functional.pad(snd, (0, win_len // 2 + 1 - snd.shape[1]))
+            if marks:
+                marks[2].record()
+            mel_dev, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
+            if marks:
+                marks[3].record()
+                marks[3].synchronize()
+                t0 = time.perf_counter()
+            mel = mel_dev.cpu().numpy()
+            if marks:
+                _add(stats, "copy_back", time.perf_counter() - t0)
+                for key, first in (("upload", 0), ("resample", 1), ("analysis", 2)):
+                    _add(stats, key, marks[first].elapsed_time(marks[first + 1]) * 1e-3)
+            for bb, ii in enumerate(group):
+                out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[bb, :lengths[bb] // hop + 1].T))
+    return out

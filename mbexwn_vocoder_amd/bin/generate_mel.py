@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Mel analysis CLI: sound files -> ``.mell`` files, the inputs of resynth_mel.py -- same flags, file naming and dictionary
+as the reference's bin/generate_mel.py (reference bin/generate_mel.py:27-94), with the reference's resampler
+(sig_proc/resample.py) and the mel analysis running on the MI355X HIP path.
+
+Deviations (documented in INTEGRATION.md):
+  * sound files are read with ``soundfile`` if it is installed, otherwise through the built-in readers (wav through scipy,
+    flac as this package writes it; the reference uses pysndfile)
+  * a file with more than one channel is refused by name (the reference raises there too)
+  * additionally ``--batch N`` (padded micro-batches per input rate through the device resampler and the device analysis),
+    ``-nt`` (reader / writer threads), ``--host`` (numpy analysis and host resampler, no GPU needed), ``-v``, ``-q``
+  * without ``--host`` and without a GPU the script fails loudly; there is no ``--gpus``
+"""
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+test_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'mbexwn_vocoder_amd')
+if os.path.exists(test_path):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
+
+from mbexwn_vocoder_amd import get_config_file, list_models  # noqa: E402
+from mbexwn_vocoder_amd.analysis import generate_mels  # noqa: E402
+from mbexwn_vocoder_amd.audioio import read_audio  # noqa: E402
+from mbexwn_vocoder_amd.config import read_config  # noqa: E402
+from mbexwn_vocoder_amd.fileio import save_var  # noqa: E402
+
+
+def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2, host=False, verbose=False, quiet=False):
+    config_file = get_config_file(model_id_or_path=model_id)
+    preprocess_config = read_config(config_file=config_file)['preprocess_config']
+    missing = [ff for ff in input_audio_files if not os.path.isfile(ff)]
+    if missing:
+        print(f"generate_mel::error:: no such file: {', '.join(missing)}", file=sys.stderr)
+        sys.exit(1)
+    if not host:
+        import torch
+        if not torch.cuda.is_available():
+            print("generate_mel::error:: no GPU available; --host runs the numpy analysis", file=sys.stderr)
+            sys.exit(1)
+    if output_dir and not os.path.exists(output_dir):
+        os.makedirs(output_dir)
+    batch, threads = max(1, int(batch)), max(1, int(num_threads))
+    seconds = {"read": 0.0, "write": 0.0}
+    stats = {} if verbose else None
+
+    def read(path):
+        t0 = time.perf_counter()
+        snd, rate = read_audio(path)
+        if snd.size == 0:
+            raise ValueError(f"{path}: no samples")
+        return snd, rate, time.perf_counter() - t0
+
+    def write(path, data):
+        t0 = time.perf_counter()
+        save_var(path, data)
+        return time.perf_counter() - t0
+
+    t_start = time.perf_counter()
+    samples = 0
+    windows = [input_audio_files[ii:ii + batch] for ii in range(0, len(input_audio_files), batch)]
+    with ThreadPoolExecutor(max_workers=threads) as readers, ThreadPoolExecutor(max_workers=threads) as writers:
+        pending = [readers.submit(read, ff) for ff in windows[0]] if windows else []
+        written = []
+        for wi, files in enumerate(windows):
+            loaded = [fu.result() for fu in pending]
+            # the next window is read while this one is analysed
+            pending = [readers.submit(read, ff) for ff in windows[wi + 1]] if wi + 1 < len(windows) else []
+            seconds["read"] += sum(ll[2] for ll in loaded)
+            if not quiet:
+                for ff in files:
+                    print(f"process {ff}", file=sys.stderr)
+            mells = generate_mels([ll[0] for ll in loaded], [ll[1] for ll in loaded], preprocess_config, on_device=not host,
+                                  batch=batch, stats=stats)
+            for ff, ll, dd in zip(files, loaded, mells):
+                outfile = os.path.join(output_dir, os.path.splitext(os.path.basename(ff))[0] + ".mell")
+                samples += ll[0].size / ll[1]
+                if verbose:
+                    print(f"    {ll[0].size} samples at {ll[1]} Hz -> {dd['mell'].shape[1]} frames, save under {outfile}",
+                          file=sys.stderr)
+                written.append(writers.submit(write, outfile, dd))
+        seconds["write"] = sum(fu.result() for fu in written)
+    if verbose:
+        wall = time.perf_counter() - t_start
+        where = "host" if host else "device"
+        print(f"generate_mel: {len(input_audio_files)} files, {samples:.1f} s of audio in {wall:.2f} s wall "
+              f"({samples / max(wall, 1e-9):.1f} x real time); read {seconds['read']:.2f} s, "
+              + (f"upload {stats.get('upload', 0.0):.3f} s, " if not host else "")
+              + f"{where} resample {stats.get('resample', 0.0):.3f} s, {where} analysis {stats.get('analysis', 0.0):.3f} s, "
+              + (f"copy-back {stats.get('copy_back', 0.0):.3f} s, " if not host else "")
+              + f"write {seconds['write']:.2f} s (read and write summed over {threads} threads each)", file=sys.stderr)
+
+
+if __name__ == "__main__":
+    from argparse import ArgumentParser
+    parser = ArgumentParser(description="create mel analysis from sound files using the analysis configuration of a model")
+    parser.add_argument("input_audio_files", nargs="+", help="input files to process")
+    parser.add_argument("-o", "--output_dir", required=True, help="output directory where the .mell files will be stored")
+    parser.add_argument("--model_id", default="VOICE", nargs="?", const="",
+                        help="model identifier or path to a model directory whose config.yaml holds the analysis "
+                             "configuration; all models share it, so the default is fine. Given without a value the script "
+                             "lists all known models. (Def: %(default)s)")
+    parser.add_argument("--batch", default=1, type=int, metavar="N",
+                        help="analyse up to N files per launch, grouped by input rate, in padded micro-batches "
+                             "(Def: %(default)s = one file at a time)")
+    parser.add_argument("-nt", "--num_threads", default=2, type=int, help="reader and writer threads (Def: %(default)s)")
+    parser.add_argument("--host", action="store_true", help="numpy analysis and host resampler; needs no GPU")
+    parser.add_argument("-v", "--verbose", action="store_true", help="display verbose progress info")
+    parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")
+    args = parser.parse_args()
+
+    if not args.model_id:
+        print("Please select one of the following models.\nYou don't need to select with a full ID. "
+              "The first model containing the model_id you provide will be selected.")
+        for kk, ll in list_models().items():
+            for md in ll:
+                print(f" - {kk}/{md}")
+    else:
+        main(**vars(args))

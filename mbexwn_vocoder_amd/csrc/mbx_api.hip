@@ -4,6 +4,9 @@
 // Nothing in here allocates, frees or synchronises after mbx_create apart from the calibration: every call only enqueues
 // kernels on the caller's stream, so a forward pass can be captured into a hipGraph by the caller.
 #include "mbx_handle.h"
+#include "../../include/mbexwn_audio.h"
+
+static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
 
 using namespace mbx_host;
 
@@ -344,6 +347,26 @@ mbx_status mbx_mel_analysis(const float *audio, const int32_t *n_samples, int32_
     if (!mbx::launch_mel_analysis(a, static_cast<hipStream_t>(hip_stream)))
         return fail(MBX_ERR_INVALID_ARGUMENT, "mel analysis: sizes do not fit the kernel (fft_size a power of two <= 2048, "
                                               "win <= fft_size, max_samples > win/2, max_frames >= max_samples/hop + 1)");
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxa_resample_poly(const float *audio, const int32_t *n_samples, int32_t batch, int32_t max_samples, int32_t up,
+                              int32_t down, const float *taps, int32_t n_taps, float *out, int32_t max_out, void *hip_stream) {
+    mbx::ResampleArgs a{};
+    a.audio = audio;
+    a.n_samples = n_samples;
+    a.batch = batch;
+    a.max_samples = max_samples;
+    a.up = up;
+    a.down = down;
+    a.taps = taps;
+    a.n_taps = n_taps;
+    a.out = out;
+    a.max_out = max_out;
+    if (const char *why = mbx::check_resample_poly(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("resample poly: ") + why);
+    mbx::launch_resample_poly(a, static_cast<hipStream_t>(hip_stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

@@ -330,6 +330,23 @@ struct MelAnalysisArgs {
 };
 bool launch_mel_analysis(const MelAnalysisArgs &a, hipStream_t stream);
 
+// polyphase FIR resampler of a ragged batch (resample_poly.hip; include/mbexwn_audio.h: mbxa_resample_poly)
+constexpr int RS_TILE = 1024;                   // outputs per block; MBXA_RESAMPLE_TILE of the header
+struct ResampleArgs {
+    const float *audio;       // (batch, max_samples)
+    const int *n_samples;     // (batch) or null
+    int batch, max_samples;
+    int up, down;
+    const float *taps;        // (n_taps), natural order, gain included
+    int n_taps;
+    float *out;               // (batch, max_out); item b writes ceil(n_b * up / down) samples
+    int max_out;
+    int tiles, span_cap;      // launch_resample_poly fills these in: tiles per item, floats of the staged input span
+};
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_resample_poly(const ResampleArgs &a);
+void launch_resample_poly(const ResampleArgs &a, hipStream_t stream);
+
 // FLAC frames of 16-bit mono audio (flac_frames.hip): flac.py::encode's stream behind its 42-byte header
 constexpr int FLAC_BLOCK = 4096;                // samples per frame (the last one may be shorter)
 constexpr int FLAC_THREADS = 256;

@@ -210,6 +210,9 @@ def load_library():
     lib.mbx_mel_analysis.argtypes = [fp, vp, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp, vp, ctypes.c_float, fp, i32, vp]
     lib.mbx_encode_flac16.restype = i32
     lib.mbx_encode_flac16.argtypes = [fp, ctypes.c_int64, i32, i64p, i32, vp, vp, ctypes.c_int64, fp, vp]
+    # include/mbexwn_audio.h (AUDIO_SYMBOLS)
+    lib.mbxa_resample_poly.restype = i32
+    lib.mbxa_resample_poly.argtypes = [fp, vp, i32, i32, i32, i32, fp, i32, fp, i32, vp]
     _lib = lib
     return lib
 
@@ -218,6 +221,10 @@ EXPORTED_SYMBOLS = ["mbx_last_error", "mbx_create", "mbx_destroy", "mbx_conv_for
                     "mbx_forward_stream", "mbx_forward_ex", "mbx_layer_state_info", "mbx_window_advance", "mbx_window_update", "mbx_emit_rows", "mbx_stage",
                     "mbx_profile_enable", "mbx_profile_read", "mbx_profile_read_launches", "mbx_clock_probe", "mbx_pqmf_synthesis", "mbx_conv1d", "mbx_conv1d_f64acc", "mbx_lin_interp", "mbx_wavetable", "mbx_stft_filter", "mbx_norm_mel", "mbx_mel_analysis",
                     "mbx_encode_flac16"]
+
+
+# include/mbexwn_audio.h: the audio-side entry points of the same library (prefix mbxa_; mbexwn.h's list stays as it is)
+AUDIO_SYMBOLS = ["mbxa_resample_poly"]
 
 
 def _check(status):

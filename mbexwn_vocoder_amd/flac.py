@@ -1,4 +1,5 @@
-"""Minimal FLAC writer (mono / multi-channel 16-bit PCM, VERBATIM sub-frames) for the CLI's default output format.
+"""Minimal FLAC writer (mono / multi-channel 16-bit PCM, VERBATIM sub-frames) for the CLI's default output format, and a
+reader of what it writes (``decode``).
 
 The reference CLI writes ``--format flac`` through its ``sndio`` module on top of libsndfile (reference
 bin/resynth_mel.py:104-105), which is not part of this image.  A FLAC stream does not have to be compressed: a
@@ -197,6 +198,87 @@ def pcm16_from_frames(frames, n):
 def assemble(frames, n, rate):
     """The whole mono stream from frames encoded elsewhere (the device encoder): header with the MD5 of their samples, frames."""
     return stream_header(n, rate, hashlib.md5(pcm16_from_frames(frames, n)).digest()) + bytes(frames)
+
+
+_BLOCK_SIZES = {1: 192, **{cc: 576 << (cc - 2) for cc in range(2, 6)}, **{cc: 256 << (cc - 8) for cc in range(8, 16)}}
+
+
+def decode(stream):
+    """``(int16 samples, rate)`` of a FLAC stream of the kind this module's writers produce: mono, 16 bits, VERBATIM or
+    CONSTANT sub-frames.  Every frame's CRC-8 and CRC-16 and the MD5 of STREAMINFO are checked (an all-zero MD5 means "not
+    computed" and is accepted).  Anything else -- more channels, another sample size, a predicted (FIXED / LPC) sub-frame,
+    as a compressing encoder writes them -- raises ``ValueError`` that says to install ``soundfile``."""
+    data = bytes(stream)
+
+    def refuse(what):
+        return ValueError(f"FLAC reader: {what}; only mono 16-bit streams with VERBATIM / CONSTANT sub-frames are built "
+                          "in -- install soundfile to read other FLAC files")
+
+    if len(data) < HEADER_BYTES or data[:4] != b"fLaC":
+        raise ValueError("FLAC reader: not a FLAC stream (no fLaC marker)")
+    pos, info = 4, None
+    while True:
+        if pos + 4 > len(data):
+            raise ValueError("FLAC reader: truncated metadata")
+        last, kind, size = data[pos] >> 7, data[pos] & 0x7F, int.from_bytes(data[pos + 1:pos + 4], "big")
+        if kind == 0:
+            info = data[pos + 4:pos + 4 + size]
+        pos += 4 + size
+        if last:
+            break
+    if info is None or len(info) != 34 or pos > len(data):
+        raise ValueError("FLAC reader: no STREAMINFO block")
+    packed = int.from_bytes(info[10:18], "big")
+    rate, channels, bits, total = packed >> 44, ((packed >> 41) & 7) + 1, ((packed >> 36) & 31) + 1, packed & ((1 << 36) - 1)
+    if channels != 1:
+        raise refuse(f"{channels} channels")
+    if bits != 16:
+        raise refuse(f"{bits}-bit samples")
+    blocks = []
+    while pos < len(data):
+        start = pos
+        if pos + 5 > len(data) or data[pos] != 0xFF or data[pos + 1] & 0xFE != 0xF8:
+            raise ValueError(f"FLAC reader: no frame sync at byte {pos}")
+        size_code, rate_code = data[pos + 2] >> 4, data[pos + 2] & 15
+        if data[pos + 3] >> 4 != 0 or (data[pos + 3] >> 1) & 7 not in (0, 4) or data[pos + 3] & 1:
+            raise refuse("a frame with more than one channel or a sample size other than 16 bits")
+        pos += 4
+        lead = data[pos]                                     # the "UTF-8" coded frame / sample number: skipped
+        pos += 1 if lead < 0x80 else max(2, 8 - (lead ^ 0xFF).bit_length())
+        if size_code in (6, 7):
+            width = size_code - 5
+            size = int.from_bytes(data[pos:pos + width], "big") + 1
+            pos += width
+        elif size_code in _BLOCK_SIZES:
+            size = _BLOCK_SIZES[size_code]
+        else:
+            raise ValueError("FLAC reader: reserved block size code")
+        pos += {12: 1, 13: 2, 14: 2}.get(rate_code, 0)
+        if pos + 2 > len(data) or crc8(data[start:pos]) != data[pos]:
+            raise ValueError(f"FLAC reader: CRC-8 mismatch in the header of the frame at byte {start}")
+        pos += 1
+        sub = data[pos]
+        pos += 1
+        if sub == 0x02:                                      # VERBATIM, no wasted bits
+            block = np.frombuffer(data[pos:pos + 2 * size], dtype=">i2")
+            pos += 2 * size
+        elif sub == 0x00:                                    # CONSTANT
+            block = np.full(size, np.frombuffer(data[pos:pos + 2], dtype=">i2")[0] if pos + 2 <= len(data) else 0, dtype=">i2")
+            pos += 2
+        else:
+            raise refuse(f"sub-frame type byte 0x{sub:02x}")
+        if block.size != size or pos + 2 > len(data):
+            raise ValueError("FLAC reader: truncated frame")
+        if crc16(data[start:pos]) != int.from_bytes(data[pos:pos + 2], "big"):
+            raise ValueError(f"FLAC reader: CRC-16 mismatch in the frame at byte {start}")
+        pos += 2
+        blocks.append(block)
+    pcm = np.concatenate(blocks).astype("<i2") if blocks else np.zeros(0, dtype="<i2")
+    if total and pcm.size != total:
+        raise ValueError(f"FLAC reader: {pcm.size} samples decoded, STREAMINFO states {total}")
+    if info[18:34] != bytes(16) and hashlib.md5(pcm.tobytes()).digest() != info[18:34]:
+        raise ValueError("FLAC reader: MD5 mismatch")
+    return pcm.astype(np.int16), int(rate)
 
 
 def write(path, data, rate):

@@ -261,13 +261,25 @@ class MELInverter(object):
                   f"{info['ref_max']:.2f})", file=sys.stderr)
         return info
 
-    def generate_mel_from_snd(self, snd, srate, on_device=False):
+    def generate_mel_from_snd(self, snd, srate, on_device=False, resampler="scipy"):
         """Audio -> ``.mell`` dictionary (reference mel_inverter.py:156-182); host side (analysis.py) or, with
         ``on_device=True``, the HIP kernel of csrc/mel_analysis.hip (same tables, float32 transform).
         The reference resamples when ``srate`` differs from the model rate through a function it never imports
         (mel_inverter.py:173, a NameError there); here the sound is resampled with a polyphase FIR
-        (scipy.signal.resample_poly, Kaiser window) along the last axis."""
+        (scipy.signal.resample_poly, Kaiser window) along the last axis.
+
+        ``resampler="reference"`` (this build) resamples as the reference's TOOL does instead (bin/generate_mel.py:58-59,
+        sig_proc/resample.py): resample.py::resample_host, or resample_device when ``on_device`` is set; a 1-D sound
+        (or one row), as the tool reads them.  The result equals the file bin/generate_mel.py of this package writes."""
         from .analysis import compute_log_mel
+        if resampler not in ("scipy", "reference"):
+            raise ValueError(f"generate_mel_from_snd: resampler must be 'scipy' or 'reference', got {resampler!r}")
+        if resampler == "reference":
+            from .analysis import generate_mels
+            snd = np.asarray(snd)
+            if snd.ndim == 2 and snd.shape[0] == 1:
+                snd = snd[0]
+            return generate_mels([snd], [srate], self.preprocess_config, on_device=on_device, batch=1)[0]
         if srate != self.srate:
             from math import gcd
             from scipy.signal import resample_poly

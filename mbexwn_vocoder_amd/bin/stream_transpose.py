@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Transpose a running voice: feeds a sound file through a ``LiveResynthesizer`` (mbexwn_vocoder_amd/live.py) in tick-sized
+pushes, as a live source would deliver it, and writes what the stream gives back.
+
+    stream_transpose.py in.wav -o out.wav --model_id VOICE --transposition 1.5 [--tick-ms 80]
+
+The demonstration of the live path (streaming mel analysis -> scale_mel -> streaming synthesis with per-frame pitch control).
+The input must be at the model's sample rate: there is no streaming resampler.  A ``.wav`` output holds the float32 samples
+as they are; any other extension goes through the writers of resynth_mel.py.
+"""
+import os
+import sys
+
+import numpy as np
+
+test_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'mbexwn_vocoder_amd')
+if os.path.exists(test_path):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
+
+from mbexwn_vocoder_amd import get_config_file, list_models  # noqa: E402
+from mbexwn_vocoder_amd.audioio import read_audio  # noqa: E402
+from mbexwn_vocoder_amd.config import read_config  # noqa: E402
+from mbexwn_vocoder_amd.live import check_rate  # noqa: E402
+
+
+def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0):
+    """Push `samples` in pieces of tick_samples, one tick per push, until the stream is finished; returns its audio."""
+    live.open(stream_id, seed=seed)
+    out = []
+    for start in range(0, samples.size, tick_samples):
+        end = min(start + tick_samples, samples.size)
+        live.push_audio(stream_id, samples[start:end], last=end == samples.size, transposition=transposition)
+        out += [audio for audio in [live.tick().get(stream_id)] if audio is not None]
+    while not live.finished(stream_id):
+        audio = live.tick().get(stream_id)
+        if audio is None:                                     # a closed stream emits with every tick until it is finished
+            raise RuntimeError("the closed stream did not advance")
+        out.append(audio)
+    live.close(stream_id)
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.float32)
+
+
+def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tick_ms=80.0, seed=0, quiet=False):
+    preprocess_config = read_config(config_file=get_config_file(model_id_or_path=model_id))['preprocess_config']
+    if not os.path.isfile(input_audio_file):
+        print(f"stream_transpose::error:: no such file: {input_audio_file}", file=sys.stderr)
+        sys.exit(1)
+    samples, rate = read_audio(input_audio_file)
+    try:
+        check_rate(rate, preprocess_config["sample_rate"], what=input_audio_file)
+        if samples.size == 0:
+            raise ValueError(f"{input_audio_file}: no samples")
+        if not (np.isfinite(transposition) and transposition > 0):
+            raise ValueError("--transposition must be finite and positive")
+    except ValueError as err:
+        print(f"stream_transpose::error:: {err}", file=sys.stderr)
+        sys.exit(1)
+    import torch
+    if not torch.cuda.is_available():
+        print("stream_transpose::error:: no GPU available; this build has no CPU path", file=sys.stderr)
+        sys.exit(1)
+    from mbexwn_vocoder_amd.batched import write_audio
+    from mbexwn_vocoder_amd.live import LiveResynthesizer
+    from mbexwn_vocoder_amd.mel_inverter import MELInverter
+    live = LiveResynthesizer(MELInverter(model_id_or_path=model_id))
+    tick_samples = max(1, int(round(tick_ms * 1e-3 * rate)))
+    audio = stream_file(live, samples, tick_samples, transposition, seed=seed)
+    out_dir = os.path.dirname(os.path.abspath(output_file))
+    os.makedirs(out_dir, exist_ok=True)
+    ext = os.path.splitext(output_file)[1].lower().lstrip(".") or "wav"
+    if ext == "wav":
+        from scipy.io import wavfile
+        wavfile.write(output_file, rate, audio.astype(np.float32, copy=False))
+    else:
+        write_audio(output_file, audio, rate, ext)
+    if not quiet:
+        print(f"{input_audio_file}: {samples.size} samples in pushes of {tick_samples} -> {audio.size} samples, transposed by "
+              f"{transposition}, look-ahead {live.lookahead_ms:.1f} ms, saved under {output_file}", file=sys.stderr)
+
+
+if __name__ == "__main__":
+    from argparse import ArgumentParser
+    parser = ArgumentParser(description="transpose a sound file through the live path: streaming analysis and synthesis")
+    parser.add_argument("input_audio_file", help="mono sound file at the model's sample rate")
+    parser.add_argument("-o", "--output_file", required=True, help="sound file to write (.wav: float32 samples)")
+    parser.add_argument("--model_id", default="VOICE", nargs="?", const="",
+                        help="model identifier or path to a model directory. Given without a value the script lists all known "
+                             "models. (Def: %(default)s)")
+    parser.add_argument("--transposition", default=1.0, type=float, metavar="F", help="factor on the pitch (Def: %(default)s)")
+    parser.add_argument("--tick-ms", dest="tick_ms", default=80.0, type=float,
+                        help="milliseconds of audio per push and tick (Def: %(default)s)")
+    parser.add_argument("--seed", default=0, type=int, help="seed of the stream's noise generator (Def: %(default)s)")
+    parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")
+    args = parser.parse_args()
+
+    if not args.model_id:
+        print("Please select one of the following models.\nYou don't need to select with a full ID. "
+              "The first model containing the model_id you provide will be selected.")
+        for kk, ll in list_models().items():
+            for md in ll:
+                print(f" - {kk}/{md}")
+    else:
+        main(**vars(args))

@@ -5,6 +5,7 @@
 // kernels on the caller's stream, so a forward pass can be captured into a hipGraph by the caller.
 #include "mbx_handle.h"
 #include "../../include/mbexwn_audio.h"
+#include "../../include/mbexwn_live.h"
 
 static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
 
@@ -367,6 +368,53 @@ mbx_status mbxa_resample_poly(const float *audio, const int32_t *n_samples, int3
     a.max_out = max_out;
     if (const char *why = mbx::check_resample_poly(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("resample poly: ") + why);
     mbx::launch_resample_poly(a, static_cast<hipStream_t>(hip_stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxl_ring_append(const float *packed, int64_t packed_samples, const int64_t *desc, int32_t n_streams,
+                            int32_t max_count, float *rings, int32_t n_slots, int32_t ring_samples, void *hip_stream) {
+    mbx::RingAppendArgs a{};
+    a.packed = packed;
+    a.packed_samples = packed_samples;
+    a.desc = reinterpret_cast<const long long *>(desc);
+    a.n_streams = n_streams;
+    a.max_count = max_count;
+    a.rings = rings;
+    a.n_slots = n_slots;
+    a.ring_samples = ring_samples;
+    if (const char *why = mbx::check_ring_append(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("ring append: ") + why);
+    mbx::launch_ring_append(a, static_cast<hipStream_t>(hip_stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxl_mel_frames(const float *rings, int32_t n_slots, int32_t ring_samples, const int64_t *desc, int32_t n_streams,
+                           int32_t max_new_frames, int32_t win, int32_t hop, int32_t fft_size, int32_t n_mels,
+                           const float *window, const float *twiddle, const float *basis, const int32_t *bin_lo,
+                           const int32_t *bin_hi, float eps, float *out, void *hip_stream) {
+    mbx::MelStreamArgs a{};
+    a.rings = rings;
+    a.n_slots = n_slots;
+    a.ring_samples = ring_samples;
+    a.desc = reinterpret_cast<const long long *>(desc);
+    a.n_streams = n_streams;
+    a.max_new_frames = max_new_frames;
+    a.win = win;
+    a.hop = hop;
+    a.fft_size = fft_size;
+    a.n_mels = n_mels;
+    a.window = window;
+    a.twiddle = twiddle;
+    a.basis = basis;
+    a.bin_lo = bin_lo;
+    a.bin_hi = bin_hi;
+    a.eps = eps;
+    a.out = out;
+    if (const char *why = mbx::check_mel_stream(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("mel frames: ") + why);
+    mbx::launch_mel_stream(a, static_cast<hipStream_t>(hip_stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

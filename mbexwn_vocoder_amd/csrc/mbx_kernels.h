@@ -330,6 +330,33 @@ struct MelAnalysisArgs {
 };
 bool launch_mel_analysis(const MelAnalysisArgs &a, hipStream_t stream);
 
+// streaming mel analysis (mel_stream.hip; include/mbexwn_live.h: mbxl_ring_append, mbxl_mel_frames): a ring of the last
+// ring_samples samples per stream slot, frames computed from it by absolute sample index with mel_frame.h's body
+struct RingAppendArgs {
+    const float *packed;          // (packed_samples) the new samples of every stream of the tick, back to back
+    long long packed_samples;
+    const long long *desc;        // (n_streams, 4): slot, abs_start, count, offset into packed
+    int n_streams, max_count;     // max_count sizes the grid only: a larger count is still appended whole
+    float *rings;                 // (n_slots, ring_samples)
+    int n_slots, ring_samples;    // ring_samples a power of two
+};
+struct MelStreamArgs {
+    const float *rings;
+    int n_slots, ring_samples;
+    const long long *desc;        // (n_streams, 4): slot, first_frame, n_frames, n_total (< 0: the stream is still open)
+    int n_streams, max_new_frames;
+    int win, hop, fft_size, n_mels;
+    const float *window, *twiddle, *basis;
+    const int *bin_lo, *bin_hi;
+    float eps;
+    float *out;                   // (n_streams, max_new_frames, n_mels); rows beyond a stream's n_frames are not written
+};
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_ring_append(const RingAppendArgs &a);
+void launch_ring_append(const RingAppendArgs &a, hipStream_t stream);
+const char *check_mel_stream(const MelStreamArgs &a);
+void launch_mel_stream(const MelStreamArgs &a, hipStream_t stream);
+
 // polyphase FIR resampler of a ragged batch (resample_poly.hip; include/mbexwn_audio.h: mbxa_resample_poly)
 constexpr int RS_TILE = 1024;                   // outputs per block; MBXA_RESAMPLE_TILE of the header
 struct ResampleArgs {

@@ -213,6 +213,11 @@ def load_library():
     # include/mbexwn_audio.h (AUDIO_SYMBOLS)
     lib.mbxa_resample_poly.restype = i32
     lib.mbxa_resample_poly.argtypes = [fp, vp, i32, i32, i32, i32, fp, i32, fp, i32, vp]
+    # include/mbexwn_live.h (LIVE_SYMBOLS)
+    lib.mbxl_ring_append.restype = i32
+    lib.mbxl_ring_append.argtypes = [fp, ctypes.c_int64, vp, i32, i32, fp, i32, i32, vp]
+    lib.mbxl_mel_frames.restype = i32
+    lib.mbxl_mel_frames.argtypes = [fp, i32, i32, vp, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp, vp, ctypes.c_float, fp, vp]
     _lib = lib
     return lib
 
@@ -225,6 +230,9 @@ EXPORTED_SYMBOLS = ["mbx_last_error", "mbx_create", "mbx_destroy", "mbx_conv_for
 
 # include/mbexwn_audio.h: the audio-side entry points of the same library (prefix mbxa_; mbexwn.h's list stays as it is)
 AUDIO_SYMBOLS = ["mbxa_resample_poly"]
+
+# include/mbexwn_live.h: the streaming analysis (prefix mbxl_; the two lists above stay as they are)
+LIVE_SYMBOLS = ["mbxl_ring_append", "mbxl_mel_frames"]
 
 
 def _check(status):

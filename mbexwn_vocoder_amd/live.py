@@ -1,0 +1,387 @@
+"""Live streams: audio in, audio out.
+
+``StreamingAnalyzer`` is the mel analysis of ``analysis.compute_log_mel_device`` for sounds that are still arriving: every
+stream keeps its recent samples in a ring on the device (csrc/mel_stream.hip, include/mbexwn_live.h) and a frame is computed
+as soon as the samples of its window are there -- with exactly the bits the offline analysis gives that frame on the whole
+sound, however the sound was cut into pushes.  ``LiveResynthesizer`` joins it to ``MELInverter.scale_mel`` and a
+``StreamingSynthesizer``: the promise of the synthesis streams, "a stream equals the offline run, bit for bit", reaches back
+to the microphone.
+
+The readiness rule and the mapping of per-push transposition factors to mel frames are pure host logic (``frames_ready``,
+``FrameFactors``) and run without a device.
+"""
+import ctypes
+
+import numpy as np
+
+from .analysis import mel_analysis_tables, mell_header
+
+
+def check_rate(sample_rate, model_rate, what="samples"):
+    """Live streams take input at the model's rate only (there is no streaming resampler)."""
+    if int(round(sample_rate)) != int(round(model_rate)):
+        raise ValueError(f"{what} at {sample_rate} Hz: live streams take audio at the model rate {model_rate} Hz only; resample "
+                         "first (bin/generate_mel.py does it for files, resample.resample_host for arrays)")
+
+
+def frames_total(n_samples, hop):
+    """Rows of the offline analysis of a sound of n_samples samples."""
+    return n_samples // hop + 1
+
+
+def frames_ready(have, hop, win, closed=False):
+    """Frames of a stream that can be computed once ``have`` samples have arrived: frame t needs the samples in front of
+    t * hop - win // 2 + win while the stream is open; a closed stream has all frames_total(have) frames (the end is
+    reflected)."""
+    if closed:
+        return frames_total(have, hop)
+    need = win - win // 2
+    return 0 if have < need else (have - need) // hop + 1
+
+
+class FrameFactors:
+    """Per-push transposition factors as per-frame factors: a factor given with a push applies to the mel frames whose
+    centre sample t * hop lies in that push's sample range [start, start + count).  A sound whose length is a multiple of
+    hop has one last frame centred on the sample behind its end: it takes the factor of the last non-empty push."""
+
+    def __init__(self, hop):
+        self.hop, self.samples = int(hop), 0
+        self._base, self._values, self._last = 0, [], 1.0
+
+    @property
+    def frames(self):
+        """Frames whose factor is decided."""
+        return self._base + len(self._values)
+
+    def add(self, count, factor=None):
+        factor = 1.0 if factor is None else float(factor)
+        if count > 0:
+            end = self.samples + int(count)
+            self._values += [factor] * ((end - 1) // self.hop + 1 - self.frames)
+            self.samples, self._last = end, factor
+
+    def close(self):
+        if self.samples % self.hop == 0:
+            self._values.append(self._last)
+
+    def take(self, first, end):
+        """Factors of the frames [first, end) as float32; frames in front of ``first`` are forgotten."""
+        if first < self._base or end > self.frames:
+            raise IndexError(f"frames [{first}, {end}) are not the decided frames [{self._base}, {self.frames})")
+        out = np.asarray(self._values[first - self._base:end - self._base], dtype=np.float32)
+        del self._values[:first - self._base]
+        self._base = first
+        return out
+
+
+def frame_factors(pushes, hop):
+    """``pushes``: (count, factor or None) per push of one whole stream -> the factor of each of its frames."""
+    ff = FrameFactors(hop)
+    for count, factor in pushes:
+        ff.add(count, factor)
+    ff.close()
+    return ff.take(0, frames_total(ff.samples, hop))
+
+
+def _pow2_at_least(n):
+    out = 1
+    while out < n:
+        out *= 2
+    return out
+
+
+class _AStream:
+    def __init__(self, slot):
+        self.slot = slot
+        self.have = 0             # samples pushed so far
+        self.on_device = 0        # ... of which the ring holds [max(0, on_device - ring), on_device)
+        self.emitted = 0          # frames handed out
+        self.closed = False
+        self.queue = []           # pushed since the last tick
+        self.fresh = True         # the slot's ring still holds another stream's samples
+
+
+class StreamingAnalyzer:
+    """Log-mel analysis of any number of concurrent streams, a tick at a time.
+
+    The concatenated rows ``tick`` hands out for a stream are the rows [0, n // hop + 1) of ``compute_log_mel_device`` on the
+    stream's whole sound (n samples), bit for bit, however the sound was cut into pushes.  Frame t is handed out by the
+    first tick after t * hop - win // 2 + win samples have arrived; after ``push(..., last=True)`` the remaining frames
+    follow, with the reflection at the end (as often as a stream shorter than half a window needs it).
+
+    Samples must be at ``preprocess_config["sample_rate"]``.  A steady tick costs one host-to-device copy (descriptors and
+    samples packed in one pinned buffer), two launches and one copy back, and allocates no device memory: the stores grow by
+    doubling when more streams are open than slots exist, when a tick carries more than any before it, and -- the rings --
+    when a stream's pushes would overwrite samples a pending frame still needs.  ``ring_samples`` (default 4 windows) and
+    ``slots`` are the sizes the stores start from."""
+
+    def __init__(self, preprocess_config, device=None, ring_samples=None, slots=16):
+        cfg = preprocess_config
+        self.config = cfg
+        self.sample_rate = cfg["sample_rate"]
+        self.win = int(cfg.get("win_size", cfg["fft_size"]))
+        self.hop, self.fft_size, self.n_mels = int(cfg["hop_size"]), int(cfg["fft_size"]), int(cfg["mel_channels"])
+        self._tables_host = mel_analysis_tables(cfg)
+        # Frame 0 of an even window reads sample win / 2 (the fold of index -win / 2), which the readiness rule does not wait
+        # for.  The symmetric Hann window is exactly 0 there, the product is a zero whatever finite value the ring holds, and
+        # a zero's sign does not survive the magnitudes: same bits.  A window that is not 0 there waits for that sample.
+        self._hold_first = self.win % 2 == 0 and float(self._tables_host[0][0]) != 0.0
+        self.ring_samples = _pow2_at_least(max(self.win, int(ring_samples or 4 * self.win)))
+        self.device = device
+        self.streams = {}
+        self._slots = 0               # slots of the ring store: `slots` at first, then doubling
+        self._first_slots = max(1, int(slots))
+        self._free_slots = []
+        self._rings = None            # (slots, ring_samples) float32 on the device
+        self._tables = None
+        self._stage_host = self._stage_dev = None     # one tick's descriptors and samples: pinned, and its device twin
+        self._out_dev = self._out_host = None         # one tick's frames
+        self.ticks = 0
+        self.device_allocations = 0   # how often a device store was (re)allocated: constant over steady ticks
+        self.time_device = False      # probe: bracket the two launches of a tick with events
+        self.last_tick_device_ms = None
+
+    # -- host side ----------------------------------------------------------------------------------------------------
+    def open(self, stream_id):
+        if stream_id in self.streams:
+            raise ValueError(f"stream {stream_id!r} is open already")
+        if not self._free_slots:
+            n_new = max(self._first_slots, 2 * self._slots)
+            self._free_slots = list(range(n_new - 1, self._slots - 1, -1))
+            self._slots = n_new       # the device store follows at the next tick (_ensure_device)
+        self.streams[stream_id] = _AStream(self._free_slots.pop())
+
+    def close(self, stream_id):
+        """Forget a stream (its slot is reused)."""
+        self._free_slots.append(self.streams.pop(stream_id).slot)
+
+    def push(self, stream_id, samples, last=False, sample_rate=None):
+        """Append mono float32 samples to a stream; ``last`` closes it.  ``sample_rate``, when given, must be the model's."""
+        if sample_rate is not None:
+            check_rate(sample_rate, self.sample_rate)
+        st = self.streams[stream_id]
+        if st.closed:
+            raise ValueError(f"stream {stream_id!r} is closed")
+        samples = np.asarray(samples, dtype=np.float32)
+        if samples.ndim != 1:
+            raise ValueError(f"samples must be 1-D (mono), got shape {samples.shape}")
+        if last and st.have + samples.size == 0:
+            raise ValueError(f"stream {stream_id!r} is closed with no samples at all: there is nothing to analyse")
+        if samples.size:
+            st.queue.append(samples.copy())
+            st.have += samples.size
+        st.closed = bool(last)
+
+    def _ready(self, st):
+        if self._hold_first and not st.closed and st.have < self.win // 2 + 1:
+            return 0
+        return frames_ready(st.have, self.hop, self.win, st.closed)
+
+    def finished(self, stream_id):
+        st = self.streams[stream_id]
+        return st.closed and st.emitted >= frames_total(st.have, self.hop)
+
+    def _keep_from(self, st):
+        """First sample a pending frame of the stream may still read: the start of the window of the next frame to hand
+        out, less the two samples the reflection at the end can reach in front of it."""
+        return max(0, st.emitted * self.hop - self.win // 2 - 2)
+
+    # -- device side --------------------------------------------------------------------------------------------------
+    def _ensure_device(self, ring_needed):
+        import torch
+        if self.device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("StreamingAnalyzer: no GPU available (there is no host path)")
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        dev = self.device = torch.device(self.device)
+        if self._tables is None:
+            self._tables = [torch.as_tensor(np.ascontiguousarray(tt), device=dev) for tt in self._tables_host]
+        ring = self.ring_samples
+        while ring < ring_needed:
+            ring *= 2
+        old = self._rings
+        if old is None or old.shape[0] < self._slots or ring > self.ring_samples:
+            new = torch.zeros((self._slots, ring), dtype=torch.float32, device=dev)
+            self.device_allocations += 1
+            if old is not None and ring == self.ring_samples:
+                new[:old.shape[0]] = old
+            elif old is not None:
+                # a longer ring: every sample a ring holds moves to its place in the longer one
+                for st in self.streams.values():
+                    lo, hi = max(0, st.on_device - self.ring_samples), st.on_device
+                    if hi > lo and not st.fresh:
+                        idx = torch.arange(lo, hi, device=dev)
+                        new[st.slot, idx & (ring - 1)] = old[st.slot, idx & (self.ring_samples - 1)]
+            self._rings, self.ring_samples = new, ring
+
+    def _grown_pair(self, host, dev_buf, floats):
+        """A pinned host buffer and its device twin of at least `floats` float32 words (doubling)."""
+        import torch
+        if host is not None and host.numel() >= floats:
+            return host, dev_buf
+        size = _pow2_at_least(max(floats, 1024))
+        self.device_allocations += 1
+        return torch.zeros(size, dtype=torch.float32).pin_memory(), torch.zeros(size, dtype=torch.float32, device=self.device)
+
+    def tick(self):
+        """Append what was pushed to the rings and compute every frame that became ready.
+        Returns {stream_id: ndarray (n, mel_channels) float32} for the streams with new frames."""
+        work = [(sid, st, self._ready(st) - st.emitted) for sid, st in self.streams.items()]
+        work = [(sid, st, max(0, nn)) for sid, st, nn in work if nn > 0 or st.queue]
+        if not work:
+            return {}
+        import torch
+        from .engine import _check, load_library
+        # the rings hold every sample from the first one a pending frame reads to the newest one pushed
+        self._ensure_device(max(st.have - self._keep_from(st) for _, st, _ in work))
+        lib, dev = load_library(), self.device
+        S, max_new = len(work), max(nn for _, _, nn in work)
+        counts = [st.have - st.on_device for _, st, _ in work]
+        head = 16 * S                                         # two (S, 4) int64 descriptor tables, in float32 words
+        self._stage_host, self._stage_dev = self._grown_pair(self._stage_host, self._stage_dev, head + sum(counts))
+        self._out_host, self._out_dev = self._grown_pair(self._out_host, self._out_dev, S * max_new * self.n_mels)
+        stage = self._stage_host.numpy()
+        desc = stage[:head].view(np.int64).reshape(2, S, 4)
+        offset = 0
+        for row, ((_, st, nn), count) in enumerate(zip(work, counts)):
+            desc[0, row] = (st.slot, st.on_device, count, offset)
+            desc[1, row] = (st.slot, st.emitted, nn, st.have if st.closed else -1)
+            for part in st.queue:
+                stage[head + offset:head + offset + part.size] = part
+                offset += part.size
+        used = head + offset
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            for _, st, _ in work:
+                if st.fresh:                                  # a reused slot starts from silence (first tick of a stream)
+                    self._rings[st.slot].zero_()
+                    st.fresh = False
+            self._stage_dev[:used].copy_(self._stage_host[:used], non_blocking=True)
+            base = self._stage_dev.data_ptr()
+            if self.time_device:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            _check(lib.mbxl_ring_append(base + 4 * head, offset, base, S, max(counts), self._rings.data_ptr(),
+                                        int(self._rings.shape[0]), self.ring_samples, stream.cuda_stream))
+            tabs = self._tables
+            _check(lib.mbxl_mel_frames(self._rings.data_ptr(), int(self._rings.shape[0]), self.ring_samples, base + 32 * S, S,
+                                       max_new, self.win, self.hop, self.fft_size, self.n_mels, tabs[0].data_ptr(),
+                                       tabs[1].data_ptr(), tabs[2].data_ptr(), tabs[3].data_ptr(), tabs[4].data_ptr(),
+                                       ctypes.c_float(float(np.finfo(np.float32).eps)), self._out_dev.data_ptr(),
+                                       stream.cuda_stream))
+            if self.time_device:
+                ev1.record()
+            floats = S * max_new * self.n_mels
+            if floats:
+                self._out_host[:floats].copy_(self._out_dev[:floats], non_blocking=True)
+            stream.synchronize()
+            if self.time_device:
+                self.last_tick_device_ms = ev0.elapsed_time(ev1)
+        rows = self._out_host.numpy()[:S * max_new * self.n_mels].reshape(S, max_new, self.n_mels)
+        result = {}
+        for row, (sid, st, nn) in enumerate(work):
+            st.on_device, st.queue = st.have, []
+            if nn:
+                result[sid] = rows[row, :nn].copy()
+                st.emitted += nn
+        self.ticks += 1
+        return result
+
+
+class _LStream:
+    def __init__(self, hop, rng, noise_fn):
+        self.factors = FrameFactors(hop)
+        self.frames = 0               # mel frames handed to the synthesizer
+        self.rng, self.noise_fn = rng, noise_fn
+        self.flushed = False          # the synthesizer has been told that the stream is over
+
+
+class LiveResynthesizer:
+    """Audio in, audio out: a ``StreamingAnalyzer``, ``MELInverter.scale_mel`` (on the host: it is elementwise, so a chunk
+    of frames scales to the bits the whole file scales to) and a ``StreamingSynthesizer``, a tick at a time.
+
+    Transposition rule: a ``transposition`` factor given with ``push_audio`` applies to the mel frames whose centre sample
+    t * hop lies in that push's sample range (``FrameFactors``); a push without one has factor 1.
+
+    Noise: the N(0,1) draw of the frames [a, b) of a stream is ``noise_fn(stream_id, a, b)`` ((b - a) * steps_per_frame
+    float32 values); by default consecutive draws of a per-stream ``numpy.random.Generator`` seeded with ``seed``.
+
+    A stream's output then equals ``mel_inverter.synth_from_mel(scale_mel(mell dictionary of the whole sound), noise=the
+    same draw, transposition=the per-frame factors)`` bit for bit, when the engine is pinned to ``conv_form="f23"`` (the
+    form the streams run) and the mel is the device analysis of the sound (``compute_log_mel_device``)."""
+
+    def __init__(self, mel_inverter, chunk_frames=(6, 6, 7, 6, 7)):
+        from .streaming import StreamingSynthesizer
+        engine = mel_inverter.model
+        info = engine.conv_form_info()
+        if info.get("split_f16_layers", 0) > 0 or info.get("split_f16_gate_layers", 0) > 0:
+            raise ValueError("LiveResynthesizer needs a float32 engine: this one runs its whole-item forwards in split half "
+                             "precision (precision='split_f16'), streams would not be bit-equal to its offline synthesis")
+        self.mel_inverter = mel_inverter
+        self.synthesizer = StreamingSynthesizer(engine, chunk_frames=chunk_frames)
+        self.analyzer = StreamingAnalyzer(mel_inverter.preprocess_config, device=engine.device)
+        self.dims = engine.dims
+        self._header = mell_header(mel_inverter.preprocess_config)
+        self.streams = {}
+
+    @property
+    def lookahead_ms(self):
+        """The analysis look-ahead -- half a window, rounded up to the next frame -- plus the synthesizer's own."""
+        an = self.analyzer
+        frames = -(-(an.win - an.win // 2) // an.hop)
+        return 1000.0 * frames * an.hop / an.sample_rate + self.synthesizer.lookahead_ms
+
+    def open(self, stream_id, seed=None, noise_fn=None):
+        self.analyzer.open(stream_id)
+        self.synthesizer.open(stream_id)
+        self.streams[stream_id] = _LStream(self.analyzer.hop, None if noise_fn else np.random.default_rng(seed), noise_fn)
+
+    def close(self, stream_id):
+        self.analyzer.close(stream_id)
+        self.synthesizer.close(stream_id)
+        del self.streams[stream_id]
+
+    def push_audio(self, stream_id, samples, last=False, transposition=None, sample_rate=None):
+        """Append samples at the model rate; ``transposition``: one finite positive factor for the frames centred in this
+        push (see the class docstring)."""
+        if transposition is not None:
+            transposition = float(transposition)
+            if not (np.isfinite(transposition) and transposition > 0):
+                raise ValueError("transposition must be finite and positive")
+        st = self.streams[stream_id]
+        before = self.analyzer.streams[stream_id].have
+        self.analyzer.push(stream_id, samples, last=last, sample_rate=sample_rate)
+        st.factors.add(self.analyzer.streams[stream_id].have - before, transposition)
+        if last:
+            st.factors.close()
+
+    def _noise(self, stream_id, st, first, end):
+        spf = self.dims.steps_per_frame
+        if st.noise_fn is not None:
+            noise = np.asarray(st.noise_fn(stream_id, first, end), dtype=np.float32).reshape(-1)
+            if noise.size != (end - first) * spf:
+                raise ValueError(f"noise_fn must return {(end - first) * spf} values for frames [{first}, {end})")
+            return noise
+        return st.rng.standard_normal((end - first) * spf).astype(np.float32)
+
+    def tick(self):
+        """One analysis tick, then one synthesis tick.  Returns {stream_id: audio ndarray} of the streams that emitted."""
+        mels = self.analyzer.tick()
+        for sid, st in self.streams.items():
+            rows = mels.get(sid)
+            done = self.analyzer.finished(sid)
+            if rows is None and not (done and not st.flushed):
+                continue
+            n = 0 if rows is None else rows.shape[0]
+            first, end = st.frames, st.frames + n
+            if n:
+                scaled = self.mel_inverter.scale_mel(dict(self._header, mell=rows.T))[0]
+            else:
+                scaled = np.zeros((0, self.dims.mel_channels), dtype=np.float32)
+            noise = self._noise(sid, st, first, end) if self.dims.noise_sigma else None
+            self.synthesizer.push(sid, scaled, noise, last=done, transposition=st.factors.take(first, end))
+            st.frames, st.flushed = end, done
+        return self.synthesizer.tick()
+
+    def finished(self, stream_id):
+        return self.streams[stream_id].flushed and self.synthesizer.finished(stream_id)

@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""What the live path costs per tick: 64 streams of the canonical SPEECH model at the 80 ms schedule.
+
+Two legs in one process, each after a time-based warm-up:
+
+  synthesis  a StreamingSynthesizer alone, its mel frames resident on the host (bench.py's config 5): host-inclusive time of a
+             steady tick and the device time of its launches
+  live       a LiveResynthesizer fed 80 ms of audio per stream and tick: device time of the two analysis launches
+             (mbxl_ring_append + mbxl_mel_frames, HIP events around them), host-inclusive time of the whole live tick
+             (analysis tick, scale_mel, hand-over, synthesis tick), and the time of the 64 push_audio calls in front of it
+
+Prints one JSON line.  ``--synthesis-only`` runs the first leg alone; with ``--root DIR`` the package is imported from another
+checkout (the parent commit, for the comparison of the synthesis tick), which needs nothing of the live path.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+SCHEDULE = (6, 6, 7, 6, 7)
+
+
+def percentiles(values):
+    return {"p50": float(np.percentile(values, 50)), "p10": float(np.percentile(values, 10)),
+            "p90": float(np.percentile(values, 90)), "p99": float(np.percentile(values, 99)), "n": len(values)}
+
+
+def synthetic_mel(rng, frames, channels, spf):
+    mell = np.log(np.exp(rng.normal(-5.0, 2.0, size=(frames, channels))) + 1e-5)
+    return np.clip(mell, -11.5, 2.0).astype(np.float32), rng.normal(size=frames * spf).astype(np.float32)
+
+
+def synthesis_leg(torch, inv, streams, warm_seconds, ticks):
+    from mbexwn_vocoder_amd.streaming import StreamingSynthesizer
+    dims = inv.model.dims
+    syn = StreamingSynthesizer(inv.model, chunk_frames=SCHEDULE)
+    syn.time_device = True
+    lead = 6 * len(SCHEDULE)
+    # the frames arrive in blocks of 100 ticks' worth, pushed outside the timed section (the same block again and again: what
+    # the frames hold does not change what a tick costs)
+    block_ticks = 100
+    block_frames = block_ticks * sum(SCHEDULE) // len(SCHEDULE) + sum(SCHEDULE)
+    blocks = [synthetic_mel(np.random.default_rng(sid), block_frames, dims.mel_channels, dims.steps_per_frame)
+              for sid in range(streams)]
+    for sid in range(streams):
+        syn.open(sid)
+
+    def feed():
+        for sid in range(streams):
+            syn.push(sid, *blocks[sid])
+
+    feed()
+    feed()
+    host_ms, dev_ms, done, warm_ticks = [], [], 0, 0
+    t_start = time.perf_counter()
+    while len(host_ms) < ticks:
+        if done % block_ticks == 0:
+            feed()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = syn.tick()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        assert len(res) == streams
+        done += 1
+        if done > lead and t1 - t_start >= warm_seconds and syn.last_tick_replayed:
+            host_ms.append((t1 - t0) * 1e3)
+            dev_ms.append(syn.last_tick_device_ms)
+        else:
+            warm_ticks += 1
+            assert warm_ticks < 50000, "the ticks never became steady"
+    return {"tick_ms_host_inclusive": percentiles(host_ms), "tick_ms_device": percentiles(dev_ms), "warmup_ticks": warm_ticks,
+            "graph_ticks": int(syn.graph_ticks)}
+
+
+def live_leg(torch, inv, streams, warm_seconds, ticks):
+    from mbexwn_vocoder_amd.live import LiveResynthesizer
+    live = LiveResynthesizer(inv, chunk_frames=SCHEDULE)
+    live.analyzer.time_device = True
+    live.synthesizer.time_device = True
+    rate = int(inv.srate)
+    per_tick = int(round(0.080 * rate))
+    rng = np.random.default_rng(99)
+    tt = np.arange(50 * per_tick) / rate
+    sounds = [(0.3 * np.sin(2 * np.pi * (90.0 + 3 * sid) * tt) + 0.05 * rng.normal(size=tt.size)).astype(np.float32)
+              for sid in range(streams)]
+    for sid in range(streams):
+        live.open(sid, seed=sid)
+    allocations = None
+    tick_ms, push_ms, analysis_ms, syn_dev_ms, replayed, pos, warm_ticks = [], [], [], [], 0, 0, 0
+    t_start = time.perf_counter()
+    while len(tick_ms) < ticks:
+        t0 = time.perf_counter()
+        for sid in range(streams):                                   # the sounds repeat: the streams never end
+            live.push_audio(sid, sounds[sid][pos:pos + per_tick])
+        pos = (pos + per_tick) % sounds[0].size
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        res = live.tick()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        steady = len(res) == streams and live.synthesizer.last_tick_replayed
+        if steady and t2 - t_start >= warm_seconds:
+            if allocations is None:
+                allocations = live.analyzer.device_allocations
+            tick_ms.append((t2 - t1) * 1e3)
+            push_ms.append((t1 - t0) * 1e3)
+            analysis_ms.append(live.analyzer.last_tick_device_ms)
+            syn_dev_ms.append(live.synthesizer.last_tick_device_ms)
+            replayed += 1
+        else:
+            warm_ticks += 1
+            assert warm_ticks < 20000, "the live ticks never became steady"
+    return {"live_tick_ms_host_inclusive": percentiles(tick_ms), "push_audio_ms_all_streams": percentiles(push_ms),
+            "analysis_launches_ms_device": percentiles(analysis_ms), "synthesis_ms_device_inside": percentiles(syn_dev_ms),
+            "warmup_ticks": warm_ticks, "lookahead_ms": live.lookahead_ms,
+            "analyzer_device_allocations_during_timed_ticks": live.analyzer.device_allocations - allocations,
+            "ring_samples": live.analyzer.ring_samples}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--streams", type=int, default=64)
+    ap.add_argument("--warm-seconds", type=float, default=3.0, help="each leg warms up at least this long before it is timed")
+    ap.add_argument("--ticks", type=int, default=300, help="timed steady ticks per leg")
+    ap.add_argument("--synthesis-only", action="store_true")
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                    help="checkout to import mbexwn_vocoder_amd from (default: this one)")
+    ap.add_argument("--label", default="")
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("live_probe.py: no GPU available; a timing taken without one says nothing")
+    from mbexwn_vocoder_amd.mel_inverter import MELInverter, create_synthetic_model_dir
+    with tempfile.TemporaryDirectory() as tmp:
+        inv = MELInverter(create_synthetic_model_dir(os.path.join(tmp, "speech"), "SPEECH"))
+    out = {"label": args.label, "root": os.path.abspath(args.root), "streams": args.streams, "schedule": list(SCHEDULE),
+           "device": torch.cuda.get_device_name(0)}
+    out["synthesis"] = synthesis_leg(torch, inv, args.streams, args.warm_seconds, args.ticks)
+    if not args.synthesis_only:
+        out["live"] = live_leg(torch, inv, args.streams, args.warm_seconds, args.ticks)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

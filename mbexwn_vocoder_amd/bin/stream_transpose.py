@@ -2,11 +2,13 @@
 """Transpose a running voice: feeds a sound file through a ``LiveResynthesizer`` (mbexwn_vocoder_amd/live.py) in tick-sized
 pushes, as a live source would deliver it, and writes what the stream gives back.
 
-    stream_transpose.py in.wav -o out.wav --model_id VOICE --transposition 1.5 [--tick-ms 80]
+    stream_transpose.py in.wav -o out.wav --model_id VOICE --transposition 1.5 [--tick-ms 80] [--resample]
 
 The demonstration of the live path (streaming mel analysis -> scale_mel -> streaming synthesis with per-frame pitch control).
-The input must be at the model's sample rate: there is no streaming resampler.  A ``.wav`` output holds the float32 samples
-as they are; any other extension goes through the writers of resynth_mel.py.
+The input must be at the model's sample rate, unless ``--resample`` is given: then a file at another rate streams at its own
+rate (``--tick-ms`` of its own samples per push), is resampled on the device by the stream, and the output is written at the
+model rate.  A ``.wav`` output holds the float32 samples as they are; any other extension goes through the writers of
+resynth_mel.py.
 """
 import os
 import sys
@@ -23,9 +25,13 @@ from mbexwn_vocoder_amd.config import read_config  # noqa: E402
 from mbexwn_vocoder_amd.live import check_rate  # noqa: E402
 
 
-def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0):
-    """Push `samples` in pieces of tick_samples, one tick per push, until the stream is finished; returns its audio."""
-    live.open(stream_id, seed=seed)
+def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0, sample_rate=None):
+    """Push `samples` in pieces of tick_samples, one tick per push, until the stream is finished; returns its audio.
+    ``sample_rate``: the rate of `samples` when it is not the model's (the stream resamples)."""
+    if sample_rate is None:
+        live.open(stream_id, seed=seed)
+    else:
+        live.open(stream_id, seed=seed, sample_rate=sample_rate)
     out = []
     for start in range(0, samples.size, tick_samples):
         end = min(start + tick_samples, samples.size)
@@ -40,14 +46,18 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0)
     return np.concatenate(out) if out else np.zeros(0, dtype=np.float32)
 
 
-def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tick_ms=80.0, seed=0, quiet=False):
+def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tick_ms=80.0, seed=0, quiet=False,
+         resample=False):
     preprocess_config = read_config(config_file=get_config_file(model_id_or_path=model_id))['preprocess_config']
     if not os.path.isfile(input_audio_file):
         print(f"stream_transpose::error:: no such file: {input_audio_file}", file=sys.stderr)
         sys.exit(1)
     samples, rate = read_audio(input_audio_file)
     try:
-        check_rate(rate, preprocess_config["sample_rate"], what=input_audio_file)
+        if not resample:
+            check_rate(rate, preprocess_config["sample_rate"], what=input_audio_file)
+        elif int(round(rate)) <= 0:
+            raise ValueError(f"{input_audio_file}: invalid sample rate {rate}")
         if samples.size == 0:
             raise ValueError(f"{input_audio_file}: no samples")
         if not (np.isfinite(transposition) and transposition > 0):
@@ -64,24 +74,26 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
     from mbexwn_vocoder_amd.mel_inverter import MELInverter
     live = LiveResynthesizer(MELInverter(model_id_or_path=model_id))
     tick_samples = max(1, int(round(tick_ms * 1e-3 * rate)))
-    audio = stream_file(live, samples, tick_samples, transposition, seed=seed)
+    model_rate = int(round(preprocess_config["sample_rate"]))
+    own_rate = int(round(rate)) if int(round(rate)) != model_rate else None
+    audio = stream_file(live, samples, tick_samples, transposition, seed=seed, sample_rate=own_rate)
     out_dir = os.path.dirname(os.path.abspath(output_file))
     os.makedirs(out_dir, exist_ok=True)
     ext = os.path.splitext(output_file)[1].lower().lstrip(".") or "wav"
     if ext == "wav":
         from scipy.io import wavfile
-        wavfile.write(output_file, rate, audio.astype(np.float32, copy=False))
+        wavfile.write(output_file, model_rate, audio.astype(np.float32, copy=False))
     else:
-        write_audio(output_file, audio, rate, ext)
+        write_audio(output_file, audio, model_rate, ext)
     if not quiet:
         print(f"{input_audio_file}: {samples.size} samples in pushes of {tick_samples} -> {audio.size} samples, transposed by "
-              f"{transposition}, look-ahead {live.lookahead_ms:.1f} ms, saved under {output_file}", file=sys.stderr)
+              f"{transposition}, look-ahead {live.lookahead_ms_for(own_rate):.1f} ms, saved under {output_file}", file=sys.stderr)
 
 
 if __name__ == "__main__":
     from argparse import ArgumentParser
     parser = ArgumentParser(description="transpose a sound file through the live path: streaming analysis and synthesis")
-    parser.add_argument("input_audio_file", help="mono sound file at the model's sample rate")
+    parser.add_argument("input_audio_file", help="mono sound file at the model's sample rate (any rate with --resample)")
     parser.add_argument("-o", "--output_file", required=True, help="sound file to write (.wav: float32 samples)")
     parser.add_argument("--model_id", default="VOICE", nargs="?", const="",
                         help="model identifier or path to a model directory. Given without a value the script lists all known "
@@ -89,6 +101,9 @@ if __name__ == "__main__":
     parser.add_argument("--transposition", default=1.0, type=float, metavar="F", help="factor on the pitch (Def: %(default)s)")
     parser.add_argument("--tick-ms", dest="tick_ms", default=80.0, type=float,
                         help="milliseconds of audio per push and tick (Def: %(default)s)")
+    parser.add_argument("--resample", action="store_true",
+                        help="stream a file at another rate at its own rate: the stream resamples on the device, the output "
+                             "is at the model rate")
     parser.add_argument("--seed", default=0, type=int, help="seed of the stream's noise generator (Def: %(default)s)")
     parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")
     args = parser.parse_args()

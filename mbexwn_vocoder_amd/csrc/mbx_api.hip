@@ -6,6 +6,7 @@
 #include "mbx_handle.h"
 #include "../../include/mbexwn_audio.h"
 #include "../../include/mbexwn_live.h"
+#include "../../include/mbexwn_live_resample.h"
 
 static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
 
@@ -415,6 +416,31 @@ mbx_status mbxl_mel_frames(const float *rings, int32_t n_slots, int32_t ring_sam
     a.out = out;
     if (const char *why = mbx::check_mel_stream(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("mel frames: ") + why);
     mbx::launch_mel_stream(a, static_cast<hipStream_t>(hip_stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxr_resample_rings(const float *in_rings, int32_t n_in_slots, int32_t in_ring_samples, const int64_t *desc,
+                               int32_t n_rows, int32_t max_new_out, int32_t up, int32_t down, const float *taps, int32_t n_taps,
+                               float *out_rings, int32_t n_out_slots, int32_t out_ring_samples, void *hip_stream) {
+    mbx::ResampleStreamArgs a{};
+    a.in_rings = in_rings;
+    a.n_in_slots = n_in_slots;
+    a.in_ring_samples = in_ring_samples;
+    a.desc = reinterpret_cast<const long long *>(desc);
+    a.n_rows = n_rows;
+    a.max_new_out = max_new_out;
+    a.up = up;
+    a.down = down;
+    a.taps = taps;
+    a.n_taps = n_taps;
+    a.out_rings = out_rings;
+    a.n_out_slots = n_out_slots;
+    a.out_ring_samples = out_ring_samples;
+    if (const char *why = mbx::check_resample_stream(a))
+        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("resample rings: ") + why);
+    mbx::launch_resample_stream(a, static_cast<hipStream_t>(hip_stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

@@ -374,6 +374,23 @@ struct ResampleArgs {
 const char *check_resample_poly(const ResampleArgs &a);
 void launch_resample_poly(const ResampleArgs &a, hipStream_t stream);
 
+// streaming resampler (resample_stream.hip; include/mbexwn_live_resample.h: mbxr_resample_rings): from a ring store at the
+// input rate into the model-rate ring store of the streaming analysis, with resample_chain.h's chain
+struct ResampleStreamArgs {
+    const float *in_rings;        // (n_in_slots, in_ring_samples)
+    int n_in_slots, in_ring_samples;
+    const long long *desc;        // (n_rows, 6): in_slot, out_slot, first_out, n_out_new, n_total_in (< 0: still open), 0
+    int n_rows, max_new_out;      // max_new_out sizes the grid only: a larger n_out_new is still produced whole
+    int up, down;
+    const float *taps;            // (n_taps), natural order, gain included
+    int n_taps;
+    float *out_rings;             // (n_out_slots, out_ring_samples)
+    int n_out_slots, out_ring_samples;
+};
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_resample_stream(const ResampleStreamArgs &a);
+void launch_resample_stream(const ResampleStreamArgs &a, hipStream_t stream);
+
 // FLAC frames of 16-bit mono audio (flac_frames.hip): flac.py::encode's stream behind its 42-byte header
 constexpr int FLAC_BLOCK = 4096;                // samples per frame (the last one may be shorter)
 constexpr int FLAC_THREADS = 256;

@@ -15,6 +15,7 @@
 // Every output is one fmaf chain over ascending j whose bounds follow from k and the item's own length, so its bits do
 // not depend on the batch, on max_samples or on the tile it falls in -- nor on where the operands are read from.
 #include "mbx_kernels.h"
+#include "resample_chain.h"
 
 namespace mbx {
 
@@ -49,19 +50,10 @@ __global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(ResampleArgs 
     if (X_LDS || T_LDS) __syncthreads();
     const float *tsrc = T_LDS ? ts : p.taps;
     float *ob = p.out + (long long)b * p.max_out;
-    for (long long k = k0 + tid; k <= k_last; k += RS_THREADS) {
-        const long long c = k * p.down + half;
-        const long long jh = c / p.up;
-        const int ph = (int)(c - jh * p.up);
-        float acc = 0.f;
-        if (ph < p.n_taps) {
-            const long long i_hi = min((long long)((p.n_taps - 1 - ph) / p.up), jh);      // tap index < n_taps, j >= 0
-            const long long i_lo = max(0LL, jh - (n - 1));                                  // j <= n - 1
-            for (long long i = i_hi; i >= i_lo; --i)                                        // ascending j
-                acc = fmaf(tsrc[ph + (int)i * p.up], X_LDS ? xs[(int)(jh - i - j_lo)] : xb[jh - i], acc);   // j in [j_lo, j_hi]
-        }
-        ob[k] = acc;
-    }
+    // the chain is resample_chain.h's, shared with the streaming kernel; here j lies in [j_lo, j_hi]
+    for (long long k = k0 + tid; k <= k_last; k += RS_THREADS)
+        ob[k] = resample_chain(k * p.down + half, n, p.up, p.n_taps, [=](int idx) { return tsrc[idx]; },
+                               [=](long long j) { return X_LDS ? xs[(int)(j - j_lo)] : xb[j]; });
 }
 
 const char *check_resample_poly(const ResampleArgs &a) {

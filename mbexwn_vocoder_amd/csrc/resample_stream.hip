@@ -1,0 +1,85 @@
+// Streaming polyphase FIR resampler (include/mbexwn_live_resample.h): the resampler of resample_poly.hip for sounds that are
+// still arriving, from a ring at the input rate straight into the model-rate ring the streaming analysis reads.
+//
+// Output k of a stream is resample_chain.h's chain, the one function the offline kernel calls too: only the fetch differs
+// (sample j of the stream at in_rings[in_slot][j & (in_ring_samples - 1)] instead of the item's row).  While a stream is
+// open its length is unknown (n_total_in < 0): there is no clip at the end, and the host asks for no output whose newest
+// sample, jh = (k * down + half) / up, has not arrived.  Once the length is known the trailing clip is the offline one.
+//
+// One 256-thread block per (descriptor row, tile of RSS_TILE outputs), thread t takes output first_out + tile * RSS_TILE + t;
+// a row with more tiles than the launch has blocks is finished by striding.  RSS_TILE is 256, not the 1024 of the offline
+// kernel: a live tick is 64 streams x 1920 outputs, which is 128 blocks at 1024 and 512 at 256 on 256 CUs.  The tap table is
+// staged in LDS when it fits the default 64 KB (6 480 taps at 44.1 kHz, 14 400 at 11.025 kHz), else read from global memory
+// (72 000 taps at 12 345 Hz); the input span is read from the ring as it is (neighbouring outputs read neighbouring
+// samples, and the ring of a tick is cache-resident).  Neither choice, nor the tile, moves a bit: the chain of an output
+// depends on k, the filter and the stream's length alone.  Plain vector code, 45 to 180 multiply-adds per output, no MFMA.
+//
+// A wrong descriptor row must not address outside the caller's buffers: a row that names a slot outside a store, a negative
+// first_out or one so large that k * down + half would leave 62 bits is skipped; n_out_new is clipped to the ring; every
+// ring access is masked; the chain's trip count is bounded by n_taps / up + 1.
+#include <algorithm>
+
+#include "mbx_kernels.h"
+#include "resample_chain.h"
+
+namespace mbx {
+
+constexpr int RSS_THREADS = 256;
+constexpr int RSS_TILE = RSS_THREADS;             // outputs per block and pass
+constexpr int RSS_MAX_TILES = 4096;               // blocks per row; the kernel strides over what is left
+constexpr int RSS_LDS_BYTES = 64 * 1024;          // the default dynamic LDS limit: no function attribute needed
+
+template <bool T_LDS>
+__global__ __launch_bounds__(RSS_THREADS) void resample_stream_kernel(ResampleStreamArgs p) {
+    extern __shared__ float rss_smem[];
+    const long long *d = p.desc + 6LL * blockIdx.y;
+    const long long in_slot = d[0], out_slot = d[1], first_out = d[2], n_total = d[4];
+    const long long n_new = min(d[3], (long long)p.out_ring_samples);     // one call never writes more than the ring holds
+    const int half = (p.n_taps - 1) / 2;
+    // uniform over the block: before any barrier
+    if (in_slot < 0 || in_slot >= p.n_in_slots || out_slot < 0 || out_slot >= p.n_out_slots || first_out < 0) return;
+    if ((long long)blockIdx.x * RSS_TILE >= n_new) return;
+    if (first_out > (0x3FFFFFFFFFFFFFFFLL - half) / p.down - n_new) return;
+    const int tid = threadIdx.x;
+    if (T_LDS) {
+        for (int i = tid; i < p.n_taps; i += RSS_THREADS) rss_smem[i] = p.taps[i];
+        __syncthreads();
+    }
+    const float *tsrc = T_LDS ? rss_smem : p.taps;
+    const float *ring = p.in_rings + in_slot * p.in_ring_samples;
+    float *out = p.out_rings + out_slot * p.out_ring_samples;
+    const long long in_mask = p.in_ring_samples - 1, out_mask = p.out_ring_samples - 1;
+    const long long n = n_total < 0 ? RESAMPLE_OPEN : n_total;
+    for (long long o = (long long)blockIdx.x * RSS_TILE + tid; o < n_new; o += (long long)gridDim.x * RSS_TILE) {
+        const long long k = first_out + o;
+        out[k & out_mask] = resample_chain(k * p.down + half, n, p.up, p.n_taps, [=](int idx) { return tsrc[idx]; },
+                                           [=](long long j) { return ring[j & in_mask]; });
+    }
+}
+
+static bool rss_power_of_two(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+const char *check_resample_stream(const ResampleStreamArgs &a) {
+    if (!a.in_rings || !a.desc || !a.taps || !a.out_rings) return "NULL pointer";
+    if (a.n_rows < 0 || a.n_rows > 65535) return "n_rows must lie in [0, 65535]";
+    if (a.max_new_out < 0) return "max_new_out must not be negative";
+    if (a.up < 1 || a.down < 1 || a.n_taps < 1) return "up, down and n_taps must be at least 1";
+    if (a.n_in_slots < 1 || a.n_out_slots < 1) return "n_in_slots and n_out_slots must be at least 1";
+    if (!rss_power_of_two(a.in_ring_samples) || !rss_power_of_two(a.out_ring_samples))
+        return "in_ring_samples and out_ring_samples must be powers of two";
+    return nullptr;
+}
+
+void launch_resample_stream(const ResampleStreamArgs &a, hipStream_t stream) {
+    if (a.n_rows == 0 || a.max_new_out == 0) return;
+    const long long want = ((long long)std::min(a.max_new_out, a.out_ring_samples) + RSS_TILE - 1) / RSS_TILE;
+    const int tiles = (int)std::min<long long>(std::max<long long>(want, 1), RSS_MAX_TILES);
+    const dim3 grid(tiles, a.n_rows), block(RSS_THREADS);
+    const size_t tap_bytes = (size_t)a.n_taps * sizeof(float);
+    if (tap_bytes <= (size_t)RSS_LDS_BYTES)
+        hipLaunchKernelGGL((resample_stream_kernel<true>), grid, block, tap_bytes, stream, a);
+    else
+        hipLaunchKernelGGL((resample_stream_kernel<false>), grid, block, 0, stream, a);
+}
+
+}  // namespace mbx

@@ -218,6 +218,9 @@ def load_library():
     lib.mbxl_ring_append.argtypes = [fp, ctypes.c_int64, vp, i32, i32, fp, i32, i32, vp]
     lib.mbxl_mel_frames.restype = i32
     lib.mbxl_mel_frames.argtypes = [fp, i32, i32, vp, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp, vp, ctypes.c_float, fp, vp]
+    # include/mbexwn_live_resample.h (LIVE_RESAMPLE_SYMBOLS)
+    lib.mbxr_resample_rings.restype = i32
+    lib.mbxr_resample_rings.argtypes = [fp, i32, i32, vp, i32, i32, i32, i32, fp, i32, fp, i32, i32, vp]
     _lib = lib
     return lib
 
@@ -233,6 +236,9 @@ AUDIO_SYMBOLS = ["mbxa_resample_poly"]
 
 # include/mbexwn_live.h: the streaming analysis (prefix mbxl_; the two lists above stay as they are)
 LIVE_SYMBOLS = ["mbxl_ring_append", "mbxl_mel_frames"]
+
+# include/mbexwn_live_resample.h: the streaming resampler (prefix mbxr_; the three lists above stay as they are)
+LIVE_RESAMPLE_SYMBOLS = ["mbxr_resample_rings"]
 
 
 def _check(status):

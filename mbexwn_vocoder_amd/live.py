@@ -7,8 +7,13 @@ sound, however the sound was cut into pushes.  ``LiveResynthesizer`` joins it to
 ``StreamingSynthesizer``: the promise of the synthesis streams, "a stream equals the offline run, bit for bit", reaches back
 to the microphone.
 
-The readiness rule and the mapping of per-push transposition factors to mel frames are pure host logic (``frames_ready``,
-``FrameFactors``) and run without a device.
+A stream opened with ``sample_rate=R`` takes its pushes at R Hz: a streaming form of the reference's resampler
+(csrc/resample_stream.hip, include/mbexwn_live_resample.h) writes the model-rate samples straight into the ring the analysis
+reads, with the bits ``resample.resample_device`` gives on the whole sound, so the promise does not end at a resampler of
+the caller's.  Streams opened without a rate run exactly what they ran before.
+
+The readiness rules (``frames_ready``, ``outputs_ready``, ``input_keep_from``) and the mapping of per-push transposition
+factors to mel frames (``FrameFactors``) are pure host logic and run without a device.
 """
 import ctypes
 
@@ -18,7 +23,7 @@ from .analysis import mel_analysis_tables, mell_header
 
 
 def check_rate(sample_rate, model_rate, what="samples"):
-    """Live streams take input at the model's rate only (there is no streaming resampler)."""
+    """A stream opened without a rate of its own, and a tool run without --resample, take input at the model's rate only."""
     if int(round(sample_rate)) != int(round(model_rate)):
         raise ValueError(f"{what} at {sample_rate} Hz: live streams take audio at the model rate {model_rate} Hz only; resample "
                          "first (bin/generate_mel.py does it for files, resample.resample_host for arrays)")
@@ -39,13 +44,36 @@ def frames_ready(have, hop, win, closed=False):
     return 0 if have < need else (have - need) // hop + 1
 
 
+def outputs_ready(have, up, down, half, closed=False):
+    """Model-rate samples of a resampled stream that are final once ``have`` input samples have arrived: output k reads the
+    input up to sample (k * down + half) // up, so while the stream is open it is final when k * down + half <=
+    have * up - 1; a closed stream of ``have`` samples has all ceil(have * up / down) outputs (the tail of the filter is
+    clipped at the end, as offline).  ``half`` is (n_taps - 1) // 2 of the stream's filter."""
+    if closed:
+        return -(-have * up // down)
+    top = have * up - 1 - half
+    return 0 if top < 0 else top // down + 1
+
+
+def input_keep_from(k, up, down, half, n_taps):
+    """First input sample output ``k`` of a resampled stream reads: with k the next output not yet produced, everything in
+    front of it may leave the input ring."""
+    return max(0, -(-(k * down + half - (n_taps - 1)) // up))
+
+
 class FrameFactors:
     """Per-push transposition factors as per-frame factors: a factor given with a push applies to the mel frames whose
     centre sample t * hop lies in that push's sample range [start, start + count).  A sound whose length is a multiple of
-    hop has one last frame centred on the sample behind its end: it takes the factor of the last non-empty push."""
+    hop has one last frame centred on the sample behind its end: it takes the factor of the last non-empty push.
 
-    def __init__(self, hop):
+    ``up`` / ``down``: the pushes are counted at an input rate of down / up times the model rate (a resampled stream); the
+    centre of frame t is then input sample (t * hop * down) // up, a push that ends after ``end`` input samples decides
+    the frames in front of (end * up - 1) // (hop * down) + 1, and at the end the frames up to
+    ceil(n * up / down) // hop + 1 that are still undecided (at most one) take the last push's factor."""
+
+    def __init__(self, hop, up=1, down=1):
         self.hop, self.samples = int(hop), 0
+        self.up, self.down = int(up), int(down)
         self._base, self._values, self._last = 0, [], 1.0
 
     @property
@@ -57,12 +85,12 @@ class FrameFactors:
         factor = 1.0 if factor is None else float(factor)
         if count > 0:
             end = self.samples + int(count)
-            self._values += [factor] * ((end - 1) // self.hop + 1 - self.frames)
+            self._values += [factor] * ((end * self.up - 1) // (self.hop * self.down) + 1 - self.frames)
             self.samples, self._last = end, factor
 
     def close(self):
-        if self.samples % self.hop == 0:
-            self._values.append(self._last)
+        total = frames_total(-(-self.samples * self.up // self.down), self.hop)
+        self._values += [self._last] * max(0, total - self.frames)
 
     def take(self, first, end):
         """Factors of the frames [first, end) as float32; frames in front of ``first`` are forgotten."""
@@ -74,13 +102,14 @@ class FrameFactors:
         return out
 
 
-def frame_factors(pushes, hop):
-    """``pushes``: (count, factor or None) per push of one whole stream -> the factor of each of its frames."""
-    ff = FrameFactors(hop)
+def frame_factors(pushes, hop, up=1, down=1):
+    """``pushes``: (count, factor or None) per push of one whole stream -> the factor of each of its frames; with ``up`` /
+    ``down`` the counts are input samples of a resampled stream."""
+    ff = FrameFactors(hop, up, down)
     for count, factor in pushes:
         ff.add(count, factor)
     ff.close()
-    return ff.take(0, frames_total(ff.samples, hop))
+    return ff.take(0, frames_total(-(-ff.samples * ff.up // ff.down), hop))
 
 
 def _pow2_at_least(n):
@@ -91,9 +120,14 @@ def _pow2_at_least(n):
 
 
 class _AStream:
-    def __init__(self, slot):
+    def __init__(self, slot, rate=None, in_slot=None, filt=None):
         self.slot = slot
-        self.have = 0             # samples pushed so far
+        self.rate = rate          # None: pushes at the model rate; else the stream's own input rate
+        self.in_slot = in_slot    # ... its slot in the input-rate ring store
+        self.filt = filt          # ... and its filter: (up, down, half, n_taps)
+        self.in_have = 0          # samples pushed at the stream's own rate (== have for a stream at the model rate)
+        self.in_on_device = 0     # ... of which the input ring holds the newest (resampled streams only)
+        self.have = 0             # model-rate samples so far: pushed, or final outputs of the resampler (outputs_ready)
         self.on_device = 0        # ... of which the ring holds [max(0, on_device - ring), on_device)
         self.emitted = 0          # frames handed out
         self.closed = False
@@ -109,13 +143,22 @@ class StreamingAnalyzer:
     first tick after t * hop - win // 2 + win samples have arrived; after ``push(..., last=True)`` the remaining frames
     follow, with the reflection at the end (as often as a stream shorter than half a window needs it).
 
-    Samples must be at ``preprocess_config["sample_rate"]``.  A steady tick costs one host-to-device copy (descriptors and
-    samples packed in one pinned buffer), two launches and one copy back, and allocates no device memory: the stores grow by
-    doubling when more streams are open than slots exist, when a tick carries more than any before it, and -- the rings --
-    when a stream's pushes would overwrite samples a pending frame still needs.  ``ring_samples`` (default 4 windows) and
-    ``slots`` are the sizes the stores start from."""
+    Samples must be at ``preprocess_config["sample_rate"]``, unless the stream was opened with a ``sample_rate`` of its own
+    (below).  A steady tick costs one host-to-device copy (descriptors and samples packed in one pinned buffer), two
+    launches and one copy back, and allocates no device memory: the stores grow by doubling when more streams are open than
+    slots exist, when a tick carries more than any before it, and -- the rings -- when a stream's pushes would overwrite
+    samples a pending frame still needs.  ``ring_samples`` (default 4 windows) and ``slots`` are the sizes the stores start
+    from.
 
-    def __init__(self, preprocess_config, device=None, ring_samples=None, slots=16):
+    ``open(stream_id, sample_rate=R)`` with R another rate than the model's gives a resampled stream: its pushes are at R
+    and go to a slot of a second ring store, (slots, ``input_ring_samples``) at the input rate, from where the tick's
+    ``mbxr_resample_rings`` launches (one per distinct rate among the streams with work) write every output that became
+    final -- ``outputs_ready`` -- into the stream's model-rate ring.  Behind that ring nothing differs: the stream's
+    model-rate length is the count of outputs produced, and the rows are those of ``generate_mels`` on the whole sound at R,
+    bit for bit.  The input store grows as the other does; its rule is ``input_keep_from``.  A tick without resampled
+    streams is the tick described above, launch for launch."""
+
+    def __init__(self, preprocess_config, device=None, ring_samples=None, slots=16, input_ring_samples=None):
         cfg = preprocess_config
         self.config = cfg
         self.sample_rate = cfg["sample_rate"]
@@ -133,6 +176,9 @@ class StreamingAnalyzer:
         self._first_slots = max(1, int(slots))
         self._free_slots = []
         self._rings = None            # (slots, ring_samples) float32 on the device
+        self.input_ring_samples = _pow2_at_least(int(input_ring_samples or 4096))
+        self._in_slots, self._in_free, self._in_rings = 0, [], None     # the input-rate store of the resampled streams
+        self._taps = {}               # input rate -> (taps on the device, up, down)
         self._tables = None
         self._stage_host = self._stage_dev = None     # one tick's descriptors and samples: pinned, and its device twin
         self._out_dev = self._out_host = None         # one tick's frames
@@ -142,35 +188,63 @@ class StreamingAnalyzer:
         self.last_tick_device_ms = None
 
     # -- host side ----------------------------------------------------------------------------------------------------
-    def open(self, stream_id):
+    def open(self, stream_id, sample_rate=None):
+        """Open a stream; ``sample_rate``: the rate its pushes will be at (None or the model's: no resampling)."""
         if stream_id in self.streams:
             raise ValueError(f"stream {stream_id!r} is open already")
+        rate, filt = None, None
+        if sample_rate is not None:
+            if not np.isfinite(sample_rate) or int(round(sample_rate)) <= 0:
+                raise ValueError(f"stream {stream_id!r}: sample_rate must be a positive rate in Hz, got {sample_rate!r}")
+            if int(round(sample_rate)) != int(round(self.sample_rate)):
+                from .resample import _host_taps
+                rate = int(round(sample_rate))
+                taps, up, down = _host_taps(rate, int(round(self.sample_rate)))
+                filt = (up, down, (taps.size - 1) // 2, int(taps.size))
         if not self._free_slots:
             n_new = max(self._first_slots, 2 * self._slots)
             self._free_slots = list(range(n_new - 1, self._slots - 1, -1))
             self._slots = n_new       # the device store follows at the next tick (_ensure_device)
-        self.streams[stream_id] = _AStream(self._free_slots.pop())
+        if rate is None:
+            self.streams[stream_id] = _AStream(self._free_slots.pop())
+            return
+        if not self._in_free:
+            n_new = max(self._first_slots, 2 * self._in_slots)
+            self._in_free = list(range(n_new - 1, self._in_slots - 1, -1))
+            self._in_slots = n_new    # the device store follows at the next tick (_ensure_input)
+        self.streams[stream_id] = _AStream(self._free_slots.pop(), rate, self._in_free.pop(), filt)
 
     def close(self, stream_id):
-        """Forget a stream (its slot is reused)."""
-        self._free_slots.append(self.streams.pop(stream_id).slot)
+        """Forget a stream (its slots are reused)."""
+        st = self.streams.pop(stream_id)
+        self._free_slots.append(st.slot)
+        if st.rate is not None:
+            self._in_free.append(st.in_slot)
 
     def push(self, stream_id, samples, last=False, sample_rate=None):
-        """Append mono float32 samples to a stream; ``last`` closes it.  ``sample_rate``, when given, must be the model's."""
+        """Append mono float32 samples to a stream; ``last`` closes it.  ``sample_rate``, when given, must be the stream's
+        own: the model's, unless the stream was opened at another."""
         if sample_rate is not None:
-            check_rate(sample_rate, self.sample_rate)
+            own = getattr(self.streams.get(stream_id), "rate", None)
+            if own is None:
+                check_rate(sample_rate, self.sample_rate)
+            elif int(round(sample_rate)) != own:
+                raise ValueError(f"samples at {sample_rate} Hz: stream {stream_id!r} was opened at {own} Hz and takes every "
+                                 "push at that rate")
         st = self.streams[stream_id]
         if st.closed:
             raise ValueError(f"stream {stream_id!r} is closed")
         samples = np.asarray(samples, dtype=np.float32)
         if samples.ndim != 1:
             raise ValueError(f"samples must be 1-D (mono), got shape {samples.shape}")
-        if last and st.have + samples.size == 0:
+        if last and st.in_have + samples.size == 0:
             raise ValueError(f"stream {stream_id!r} is closed with no samples at all: there is nothing to analyse")
         if samples.size:
             st.queue.append(samples.copy())
-            st.have += samples.size
+            st.in_have += samples.size
         st.closed = bool(last)
+        # the model-rate length: what was pushed, or the resampler's outputs that no later sample can change
+        st.have = st.in_have if st.rate is None else outputs_ready(st.in_have, *st.filt[:3], closed=st.closed)
 
     def _ready(self, st):
         if self._hold_first and not st.closed and st.have < self.win // 2 + 1:
@@ -185,6 +259,11 @@ class StreamingAnalyzer:
         """First sample a pending frame of the stream may still read: the start of the window of the next frame to hand
         out, less the two samples the reflection at the end can reach in front of it."""
         return max(0, st.emitted * self.hop - self.win // 2 - 2)
+
+    @staticmethod
+    def _in_keep_from(st):
+        """First input sample a pending output of a resampled stream may still read (never behind what is to be appended)."""
+        return min(input_keep_from(st.on_device, *st.filt), st.in_on_device)
 
     # -- device side --------------------------------------------------------------------------------------------------
     def _ensure_device(self, ring_needed):
@@ -214,6 +293,36 @@ class StreamingAnalyzer:
                         new[st.slot, idx & (ring - 1)] = old[st.slot, idx & (self.ring_samples - 1)]
             self._rings, self.ring_samples = new, ring
 
+    def _ensure_input(self, ring_needed):
+        """The input-rate store of the resampled streams: grows as the model-rate store does."""
+        import torch
+        dev = self.device
+        ring = self.input_ring_samples
+        while ring < ring_needed:
+            ring *= 2
+        old = self._in_rings
+        if old is None or old.shape[0] < self._in_slots or ring > self.input_ring_samples:
+            new = torch.zeros((self._in_slots, ring), dtype=torch.float32, device=dev)
+            self.device_allocations += 1
+            if old is not None and ring == self.input_ring_samples:
+                new[:old.shape[0]] = old
+            elif old is not None:
+                for st in self.streams.values():
+                    if st.rate is None:
+                        continue
+                    lo, hi = max(0, st.in_on_device - self.input_ring_samples), st.in_on_device
+                    if hi > lo:
+                        idx = torch.arange(lo, hi, device=dev)
+                        new[st.in_slot, idx & (ring - 1)] = old[st.in_slot, idx & (self.input_ring_samples - 1)]
+            self._in_rings, self.input_ring_samples = new, ring
+
+    def _device_taps(self, rate):
+        if rate not in self._taps:
+            from .resample import device_taps
+            self._taps[rate] = device_taps(rate, int(round(self.sample_rate)), self.device)
+            self.device_allocations += 1
+        return self._taps[rate]
+
     def _grown_pair(self, host, dev_buf, floats):
         """A pinned host buffer and its device twin of at least `floats` float32 words (doubling)."""
         import torch
@@ -227,7 +336,7 @@ class StreamingAnalyzer:
         """Append what was pushed to the rings and compute every frame that became ready.
         Returns {stream_id: ndarray (n, mel_channels) float32} for the streams with new frames."""
         work = [(sid, st, self._ready(st) - st.emitted) for sid, st in self.streams.items()]
-        work = [(sid, st, max(0, nn)) for sid, st, nn in work if nn > 0 or st.queue]
+        work = [(sid, st, max(0, nn)) for sid, st, nn in work if nn > 0 or st.queue or st.have > st.on_device]
         if not work:
             return {}
         import torch
@@ -236,20 +345,38 @@ class StreamingAnalyzer:
         self._ensure_device(max(st.have - self._keep_from(st) for _, st, _ in work))
         lib, dev = load_library(), self.device
         S, max_new = len(work), max(nn for _, _, nn in work)
-        counts = [st.have - st.on_device for _, st, _ in work]
+        # resampled streams, grouped by rate: their samples go to the input-rate store, their model-rate samples are made
+        # on the device.  Without any, everything below is the tick of the model-rate streams, word for word.
+        rs = sorted((row for row, (_, st, _) in enumerate(work) if st.rate is not None), key=lambda row: work[row][1].rate)
+        R = len(rs)
+        if R:
+            self._ensure_input(max(work[row][1].in_have - self._in_keep_from(work[row][1]) for row in rs))
+            for row in rs:
+                self._device_taps(work[row][1].rate)
+        counts = [st.in_have - st.in_on_device if st.rate is not None else st.have - st.on_device for _, st, _ in work]
+        max_model = max((cc for (_, st, _), cc in zip(work, counts) if st.rate is None), default=0)
         head = 16 * S                                         # two (S, 4) int64 descriptor tables, in float32 words
-        self._stage_host, self._stage_dev = self._grown_pair(self._stage_host, self._stage_dev, head + sum(counts))
+        body = head + 20 * R                                  # ... an (R, 4) and an (R, 6) one for the resampled streams
+        self._stage_host, self._stage_dev = self._grown_pair(self._stage_host, self._stage_dev, body + sum(counts))
         self._out_host, self._out_dev = self._grown_pair(self._out_host, self._out_dev, S * max_new * self.n_mels)
         stage = self._stage_host.numpy()
         desc = stage[:head].view(np.int64).reshape(2, S, 4)
-        offset = 0
+        in_append = stage[head:head + 8 * R].view(np.int64).reshape(R, 4)
+        in_resample = stage[head + 8 * R:body].view(np.int64).reshape(R, 6)
+        offset, offsets = 0, []
         for row, ((_, st, nn), count) in enumerate(zip(work, counts)):
-            desc[0, row] = (st.slot, st.on_device, count, offset)
+            # a resampled stream appends nothing to its model-rate ring: mbxr_resample_rings writes it
+            desc[0, row] = (st.slot, st.on_device, count if st.rate is None else 0, offset)
             desc[1, row] = (st.slot, st.emitted, nn, st.have if st.closed else -1)
+            offsets.append(offset)
             for part in st.queue:
-                stage[head + offset:head + offset + part.size] = part
+                stage[body + offset:body + offset + part.size] = part
                 offset += part.size
-        used = head + offset
+        for ii, row in enumerate(rs):
+            st = work[row][1]
+            in_append[ii] = (st.in_slot, st.in_on_device, counts[row], offsets[row])
+            in_resample[ii] = (st.in_slot, st.slot, st.on_device, st.have - st.on_device, st.in_have if st.closed else -1, 0)
+        used = body + offset
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             for _, st, _ in work:
@@ -261,8 +388,25 @@ class StreamingAnalyzer:
             if self.time_device:
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev0.record()
-            _check(lib.mbxl_ring_append(base + 4 * head, offset, base, S, max(counts), self._rings.data_ptr(),
+            _check(lib.mbxl_ring_append(base + 4 * body, offset, base, S, max_model, self._rings.data_ptr(),
                                         int(self._rings.shape[0]), self.ring_samples, stream.cuda_stream))
+            if R:
+                _check(lib.mbxl_ring_append(base + 4 * body, offset, base + 4 * head, R, max(counts[row] for row in rs),
+                                            self._in_rings.data_ptr(), int(self._in_rings.shape[0]),
+                                            self.input_ring_samples, stream.cuda_stream))
+            first = 0
+            while first < R:                                  # one launch per distinct input rate
+                rate = work[rs[first]][1].rate
+                end = first
+                while end < R and work[rs[end]][1].rate == rate:
+                    end += 1
+                taps, up, down = self._taps[rate]
+                _check(lib.mbxr_resample_rings(self._in_rings.data_ptr(), int(self._in_rings.shape[0]),
+                                               self.input_ring_samples, base + 4 * (head + 8 * R) + 48 * first, end - first,
+                                               int(max(in_resample[first:end, 3].max(), 0)), up, down, taps.data_ptr(),
+                                               int(taps.numel()), self._rings.data_ptr(), int(self._rings.shape[0]),
+                                               self.ring_samples, stream.cuda_stream))
+                first = end
             tabs = self._tables
             _check(lib.mbxl_mel_frames(self._rings.data_ptr(), int(self._rings.shape[0]), self.ring_samples, base + 32 * S, S,
                                        max_new, self.win, self.hop, self.fft_size, self.n_mels, tabs[0].data_ptr(),
@@ -280,7 +424,7 @@ class StreamingAnalyzer:
         rows = self._out_host.numpy()[:S * max_new * self.n_mels].reshape(S, max_new, self.n_mels)
         result = {}
         for row, (sid, st, nn) in enumerate(work):
-            st.on_device, st.queue = st.have, []
+            st.on_device, st.in_on_device, st.queue = st.have, st.in_have, []
             if nn:
                 result[sid] = rows[row, :nn].copy()
                 st.emitted += nn
@@ -289,8 +433,8 @@ class StreamingAnalyzer:
 
 
 class _LStream:
-    def __init__(self, hop, rng, noise_fn):
-        self.factors = FrameFactors(hop)
+    def __init__(self, hop, rng, noise_fn, up=1, down=1):
+        self.factors = FrameFactors(hop, up, down)
         self.frames = 0               # mel frames handed to the synthesizer
         self.rng, self.noise_fn = rng, noise_fn
         self.flushed = False          # the synthesizer has been told that the stream is over
@@ -301,7 +445,9 @@ class LiveResynthesizer:
     of frames scales to the bits the whole file scales to) and a ``StreamingSynthesizer``, a tick at a time.
 
     Transposition rule: a ``transposition`` factor given with ``push_audio`` applies to the mel frames whose centre sample
-    t * hop lies in that push's sample range (``FrameFactors``); a push without one has factor 1.
+    t * hop lies in that push's sample range (``FrameFactors``); a push without one has factor 1.  For a stream opened at a
+    ``sample_rate`` of its own (resampled on the device, see ``StreamingAnalyzer``) the centre of frame t is input sample
+    (t * hop * down) // up.
 
     Noise: the N(0,1) draw of the frames [a, b) of a stream is ``noise_fn(stream_id, a, b)`` ((b - a) * steps_per_frame
     float32 values); by default consecutive draws of a per-stream ``numpy.random.Generator`` seeded with ``seed``.
@@ -331,10 +477,22 @@ class LiveResynthesizer:
         frames = -(-(an.win - an.win // 2) // an.hop)
         return 1000.0 * frames * an.hop / an.sample_rate + self.synthesizer.lookahead_ms
 
-    def open(self, stream_id, seed=None, noise_fn=None):
-        self.analyzer.open(stream_id)
+    def lookahead_ms_for(self, sample_rate=None):
+        """``lookahead_ms`` of a stream opened at ``sample_rate``: a resampled stream waits for half its filter as well,
+        half / up input samples (0.92 ms at 44.1 and 48 kHz, 1.4 ms at 16 kHz for a 24 kHz model)."""
+        model = int(round(self.analyzer.sample_rate))
+        if sample_rate is None or int(round(sample_rate)) == model:
+            return self.lookahead_ms
+        from .resample import _host_taps
+        taps, up, _ = _host_taps(int(round(sample_rate)), model)
+        return self.lookahead_ms + 1000.0 * ((taps.size - 1) // 2) / up / int(round(sample_rate))
+
+    def open(self, stream_id, seed=None, noise_fn=None, sample_rate=None):
+        self.analyzer.open(stream_id, sample_rate=sample_rate)
         self.synthesizer.open(stream_id)
-        self.streams[stream_id] = _LStream(self.analyzer.hop, None if noise_fn else np.random.default_rng(seed), noise_fn)
+        up, down = (self.analyzer.streams[stream_id].filt or (1, 1))[:2]
+        self.streams[stream_id] = _LStream(self.analyzer.hop, None if noise_fn else np.random.default_rng(seed), noise_fn,
+                                           up, down)
 
     def close(self, stream_id):
         self.analyzer.close(stream_id)
@@ -342,16 +500,16 @@ class LiveResynthesizer:
         del self.streams[stream_id]
 
     def push_audio(self, stream_id, samples, last=False, transposition=None, sample_rate=None):
-        """Append samples at the model rate; ``transposition``: one finite positive factor for the frames centred in this
-        push (see the class docstring)."""
+        """Append samples at the stream's rate (the model's, unless it was opened at another); ``transposition``: one finite
+        positive factor for the frames centred in this push (see the class docstring)."""
         if transposition is not None:
             transposition = float(transposition)
             if not (np.isfinite(transposition) and transposition > 0):
                 raise ValueError("transposition must be finite and positive")
         st = self.streams[stream_id]
-        before = self.analyzer.streams[stream_id].have
+        before = self.analyzer.streams[stream_id].in_have
         self.analyzer.push(stream_id, samples, last=last, sample_rate=sample_rate)
-        st.factors.add(self.analyzer.streams[stream_id].have - before, transposition)
+        st.factors.add(self.analyzer.streams[stream_id].in_have - before, transposition)
         if last:
             st.factors.close()
 

@@ -12,6 +12,10 @@ The definition everything here is tested against.  With ``taps, up, down = refer
 over 0 <= j < n with the tap index inside [0, n_taps).  ``half + pre`` is a multiple of ``down``, so the tap index is
 ``k * down + half - j * up``: that is what the device kernel (csrc/resample_poly.hip) evaluates, one float32 fmaf chain
 per output over ascending j.  ``resample_host`` evaluates the same taps in float64 and rounds once.
+
+Live streams at another rate than the model's (live.py, csrc/resample_stream.hip) evaluate the same chain from a ring as
+the samples arrive -- output k once sample (k * down + half) // up is there -- through the one device function both kernels
+share (csrc/resample_chain.h): ``resample_device`` on the whole sound is what a stream's outputs are tested against.
 """
 from functools import lru_cache
 from math import ceil, gcd, pi

@@ -9,6 +9,10 @@ Two legs in one process, each after a time-based warm-up:
              (mbxl_ring_append + mbxl_mel_frames, HIP events around them), host-inclusive time of the whole live tick
              (analysis tick, scale_mel, hand-over, synthesis tick), and the time of the 64 push_audio calls in front of it
 
+With ``--input-rate R`` a third leg follows in the same process: the live leg again with every stream opened at R Hz (80 ms of
+audio at R per push), so that the device time of the analysis launches -- now mbxl_ring_append into the input store,
+mbxr_resample_rings, mbxl_mel_frames -- and the host-inclusive live tick stand next to the figures without resampling.
+
 Prints one JSON line.  ``--synthesis-only`` runs the first leg alone; with ``--root DIR`` the package is imported from another
 checkout (the parent commit, for the comparison of the synthesis tick), which needs nothing of the live path.
 """
@@ -77,19 +81,22 @@ def synthesis_leg(torch, inv, streams, warm_seconds, ticks):
             "graph_ticks": int(syn.graph_ticks)}
 
 
-def live_leg(torch, inv, streams, warm_seconds, ticks):
+def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None):
     from mbexwn_vocoder_amd.live import LiveResynthesizer
     live = LiveResynthesizer(inv, chunk_frames=SCHEDULE)
     live.analyzer.time_device = True
     live.synthesizer.time_device = True
-    rate = int(inv.srate)
+    rate = int(input_rate or inv.srate)
     per_tick = int(round(0.080 * rate))
     rng = np.random.default_rng(99)
     tt = np.arange(50 * per_tick) / rate
     sounds = [(0.3 * np.sin(2 * np.pi * (90.0 + 3 * sid) * tt) + 0.05 * rng.normal(size=tt.size)).astype(np.float32)
               for sid in range(streams)]
     for sid in range(streams):
-        live.open(sid, seed=sid)
+        if input_rate:
+            live.open(sid, seed=sid, sample_rate=input_rate)
+        else:
+            live.open(sid, seed=sid)
     allocations = None
     tick_ms, push_ms, analysis_ms, syn_dev_ms, replayed, pos, warm_ticks = [], [], [], [], 0, 0, 0
     t_start = time.perf_counter()
@@ -117,9 +124,11 @@ def live_leg(torch, inv, streams, warm_seconds, ticks):
             assert warm_ticks < 20000, "the live ticks never became steady"
     return {"live_tick_ms_host_inclusive": percentiles(tick_ms), "push_audio_ms_all_streams": percentiles(push_ms),
             "analysis_launches_ms_device": percentiles(analysis_ms), "synthesis_ms_device_inside": percentiles(syn_dev_ms),
-            "warmup_ticks": warm_ticks, "lookahead_ms": live.lookahead_ms,
+            "warmup_ticks": warm_ticks,
+            "lookahead_ms": live.lookahead_ms_for(input_rate) if input_rate else live.lookahead_ms,
             "analyzer_device_allocations_during_timed_ticks": live.analyzer.device_allocations - allocations,
-            "ring_samples": live.analyzer.ring_samples}
+            "ring_samples": live.analyzer.ring_samples,
+            **({"input_rate": input_rate, "input_ring_samples": live.analyzer.input_ring_samples} if input_rate else {})}
 
 
 def main():
@@ -128,6 +137,8 @@ def main():
     ap.add_argument("--warm-seconds", type=float, default=3.0, help="each leg warms up at least this long before it is timed")
     ap.add_argument("--ticks", type=int, default=300, help="timed steady ticks per leg")
     ap.add_argument("--synthesis-only", action="store_true")
+    ap.add_argument("--input-rate", type=int, default=0, metavar="R",
+                    help="also run the live leg with every stream opened at R Hz (resampled on the device)")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="checkout to import mbexwn_vocoder_amd from (default: this one)")
     ap.add_argument("--label", default="")
@@ -144,6 +155,8 @@ def main():
     out["synthesis"] = synthesis_leg(torch, inv, args.streams, args.warm_seconds, args.ticks)
     if not args.synthesis_only:
         out["live"] = live_leg(torch, inv, args.streams, args.warm_seconds, args.ticks)
+        if args.input_rate and args.input_rate != int(inv.srate):
+            out["live_resampled"] = live_leg(torch, inv, args.streams, args.warm_seconds, args.ticks, args.input_rate)
     print(json.dumps(out))
 
 

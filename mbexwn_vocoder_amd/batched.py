@@ -41,9 +41,11 @@ def have_soundfile():
     return True
 
 
-def write_audio(outfile, data, rate, format):
+def write_audio(outfile, data, rate, format, flac_compression="verbatim"):
     """reference bin/resynth_mel.py:104-105 (sndio.write): libsndfile through soundfile where it is installed, else the
-    built-in writers -- flac (mbexwn_vocoder_amd/flac.py: 16-bit, uncompressed sub-frames) and wav (float32)."""
+    built-in writers -- flac (mbexwn_vocoder_amd/flac.py: 16-bit; uncompressed sub-frames, or with
+    ``flac_compression="fixed"`` fixed predictors and Rice codes) and wav (float32).  soundfile compresses FLAC by itself
+    and ignores ``flac_compression``."""
     try:
         import soundfile
         soundfile.write(outfile, data, rate, format=format.upper())
@@ -52,7 +54,7 @@ def write_audio(outfile, data, rate, format):
         pass
     if format.lower() == "flac":
         from . import flac
-        return flac.write(outfile, data, rate)
+        return flac.write(outfile, data, rate, flac_compression)
     if format.lower() == "wav":
         from scipy.io import wavfile
         wavfile.write(outfile, rate, np.asarray(data, dtype=np.float32))
@@ -125,11 +127,13 @@ class SynthBatch:
         return float(np.max(np.abs(self.audio(jj)))) if self.n_samples[jj] else 0.0
 
 
-def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False, host_audio=True):
+def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False, host_audio=True,
+                      flac_compression="verbatim"):
     """Generator over the padded micro-batches of ``mels`` (list of (T_i, C) float32 arrays) on ``engine``: each is staged
     and run (engine.forward with the items' lengths), its FLAC frames encoded (``flac``) and / or its audio copied to pinned
     host memory (``host_audio``), all enqueued on the current stream; the SynthBatch is yielded without waiting, so that a
-    writer can take it while the next one runs.  ``noises``: per-item device tensors (T_i * wn_in_rows_per_frame,), or
+    writer can take it while the next one runs.  ``flac_compression``: "verbatim" or "fixed" (engine.encode_flac16; the
+    compressed encoder waits for its frame lengths before the batch is yielded).  ``noises``: per-item device tensors (T_i * wn_in_rows_per_frame,), or
     None for a model without noise channel."""
     import torch
     dims = engine.dims
@@ -144,7 +148,7 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
         audio = engine.forward(mel, n_frames=n_frames, noise=noise)
         events[1].record(stream)
         n_samples = [lengths[ii] * dims.hop_size for ii in group]
-        enc = engine.encode_flac16(audio, n_samples, wait=False) if flac else None
+        enc = engine.encode_flac16(audio, n_samples, wait=False, compression=flac_compression) if flac else None
         host = None
         if host_audio:
             host = torch.empty(tuple(audio.shape), dtype=torch.float32, pin_memory=True)
@@ -165,13 +169,15 @@ class _Clock:
             self.seconds[key] = self.seconds.get(key, 0.0) + seconds
 
 
-def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threads=2, verbose=False, quiet=False):
+def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threads=2, verbose=False, quiet=False,
+            flac_compression="verbatim"):
     """The batched CLI on this process's GPU: ``files[mine]`` -> syn_<basename>.<fmt> in ``output_dir``.
 
     ``frames``: the frame count after scale_mel of EVERY file of the job, in file order (the noise replay needs all of
     them; default: read here, which needs ``mine`` = all files).  Reader pool (load_var + scale_mel; a missing or bad file
     fails before anything runs), device (forward, FLAC frames, asynchronous copies into pinned memory), writer pool (MD5,
-    header, file write); both pools have ``threads`` threads."""
+    header, file write); both pools have ``threads`` threads.  ``flac_compression``: what the built-in FLAC writers emit,
+    on the device and on the host ("verbatim" or "fixed")."""
     t_start = time.perf_counter()
     mine = list(range(len(files))) if mine is None else list(mine)
     clock, log_lock = _Clock(), threading.Lock()
@@ -225,9 +231,9 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
             if verbose:
                 lines.append(f"    save audio under {outfile}")
             if device_flac and np.isfinite(peak):
-                flac.write_frames(outfile, sb.flac.frames(jj), sb.n_samples[jj], rate)
+                sb.flac.write(outfile, jj)
             else:                                        # soundfile, wav, or an item the host writer must take
-                write_audio(outfile, audio if audio is not None else sb.audio(jj), rate, fmt)
+                write_audio(outfile, audio if audio is not None else sb.audio(jj), rate, fmt, flac_compression)
             log(lines)
         clock.add("write", time.perf_counter() - t0)
         clock.add("device_ms", sb.device_ms)
@@ -237,7 +243,8 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
     noises = None if draws is None else [draws[ii] for ii in mine]
     with ThreadPoolExecutor(max_workers=max(1, threads)) as writers:
         pending = [writers.submit(write, sb) for sb in run_micro_batches(inv.model, mels, noises, max(1, batch),
-                                                                         flac=device_flac, host_audio=verbose or not device_flac)]
+                                                                         flac=device_flac, host_audio=verbose or not device_flac,
+                                                                         flac_compression=flac_compression)]
         for fu in pending:
             fu.result()
     if verbose:

@@ -6,7 +6,8 @@ Deviations (documented in INTEGRATION.md):
   * this build has only the GPU path: ``-g`` is accepted and implied; without a GPU the script fails loudly
   * ``-nt`` (TensorFlow CPU threads) is accepted and ignored
   * audio files are written with ``soundfile`` if it is installed, otherwise through the built-in writers (flac: 16-bit
-    VERBATIM frames, wav: float32 through scipy; the reference uses pysndfile, default format flac)
+    VERBATIM frames, or with ``--flac-compression fixed`` fixed predictors and Rice codes, about half the size on speech;
+    wav: float32 through scipy; the reference uses pysndfile, default format flac)
   * additionally ``--batch N`` (padded micro-batches, FLAC frames encoded on the GPU, reader / writer pools of -nt
     threads), ``--gpus N`` (the files sharded over N child processes by frames) and ``--batch-invariant``
 """
@@ -27,13 +28,20 @@ from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 
 
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
-         num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None):
+         num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None,
+         flac_compression="verbatim"):
     format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
+    if flac_compression != "verbatim" and rank is None and not quiet:
+        from mbexwn_vocoder_amd.batched import have_soundfile
+        if format.lower() != "flac" or have_soundfile():
+            print("resynth_mel::note:: --flac-compression is ignored: " + ("soundfile writes the files and compresses FLAC "
+                  "by itself" if format.lower() == "flac" else f"the format is {format}"), file=sys.stderr)
     if gpus > 1 and rank is None:
         # --gpus N: this parent never initialises HIP; N fresh child processes write their share of the files each
         from mbexwn_vocoder_amd.batched import run_ranks
         argv = [model_id, "-i", *input_mell_files, "--format", format, "-nt", str(num_threads), "--batch", str(batch),
-                "--calibrate", str(calibrate), "--conv-form", conv_form] + (["-o", output_dir] if output_dir else [])
+                "--calibrate", str(calibrate), "--conv-form", conv_form, "--flac-compression", flac_compression]
+        argv += ["-o", output_dir] if output_dir else []
         argv += [flag for flag, on in (("-g", use_gpu), ("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant))
                  if on]
         sys.exit(run_ranks(os.path.abspath(__file__), argv, model_id, input_mell_files, gpus, threads=num_threads,
@@ -77,7 +85,8 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
     if batch > 1 or plan is not None:
         from mbexwn_vocoder_amd.batched import run_job
         run_job(MelInv, input_mell_files, output_dir, format, frames=plan["frames"] if plan else None,
-                mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose, quiet=quiet)
+                mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose, quiet=quiet,
+                flac_compression=flac_compression)
         return
 
     for mell_file in input_mell_files:
@@ -104,7 +113,7 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
             print(f'    to prevent clipping you would need to normalize {outfile} by {norm:.3f}', file=sys.stderr)
         if verbose:
             print(f"    save audio under {outfile}", file=sys.stderr)
-        write_audio(outfile, syn_audio, MelInv.srate, format)
+        write_audio(outfile, syn_audio, MelInv.srate, format, flac_compression)
 
 
 if __name__ == "__main__":
@@ -137,6 +146,10 @@ if __name__ == "__main__":
     parser.add_argument("--conv-form", default="auto", choices=["auto", "direct", "f23", "f43"],
                         help="form of the WaveNet's dilated convolution: auto = calibrated at model load; a causal model "
                              "(force_causal) runs its Winograd kernels only when f23 / f43 is pinned (Def: %(default)s)")
+    parser.add_argument("--flac-compression", default="verbatim", choices=["verbatim", "fixed"],
+                        help="what the built-in FLAC writer emits: verbatim = uncompressed sub-frames, the size of a wav; fixed "
+                             "= fixed predictors of orders 0-4 with Rice codes, on the GPU with --batch / --gpus; ignored when "
+                             "soundfile writes the files (Def: %(default)s)")
     parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
     parser.add_argument("--job", default=None, help=SUPPRESS)
     args = parser.parse_args()

@@ -7,6 +7,7 @@
 #include "../../include/mbexwn_audio.h"
 #include "../../include/mbexwn_live.h"
 #include "../../include/mbexwn_live_resample.h"
+#include "../../include/mbexwn_flac.h"
 
 static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
 
@@ -455,6 +456,22 @@ mbx_status mbx_encode_flac16(const float *audio, int64_t stride, int32_t batch, 
     const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     HIP_TRY(hipMemsetAsync(max_abs, 0, (size_t)batch * sizeof(float), stream));
     mbx::launch_flac_frames(audio, stride, batch, n_samples, sample_rate, crc_tables, out, max_abs, stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxf_encode_flac16_fixed(const float *audio, int64_t stride, int32_t batch, const int64_t *n_samples,
+                                    int32_t sample_rate, const uint16_t *crc_tables, uint8_t *out, int64_t out_bytes,
+                                    int32_t *frame_bytes, int64_t *workspace, int16_t *pcm_out, float *max_abs, void *hip_stream) {
+    if (const char *why = mbx::check_flac_fixed(audio, stride, batch, n_samples, sample_rate, crc_tables, out, out_bytes,
+                                                frame_bytes, workspace, max_abs))
+        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("encode flac16 fixed: ") + why);
+    if (batch == 0) return MBX_OK;
+    const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipMemsetAsync(max_abs, 0, (size_t)batch * sizeof(float), stream));
+    mbx::launch_flac_fixed(audio, stride, batch, n_samples, sample_rate, crc_tables, out, frame_bytes, workspace, pcm_out,
+                           max_abs, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

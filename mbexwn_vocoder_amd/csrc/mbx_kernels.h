@@ -415,6 +415,19 @@ const char *check_flac_frames(const float *audio, long long stride, int batch, c
 void launch_flac_frames(const float *audio, long long stride, int batch, const int64_t *n_samples, int sample_rate,
                         const uint16_t *crc_tables, uint8_t *out, float *max_abs, hipStream_t stream);
 
+// compressed FLAC frames (flac_fixed.hip; include/mbexwn_flac.h: mbxf_encode_flac16_fixed): flac.py::encode(...,
+// compression="fixed") behind its header -- fixed predictors of orders 0-4 and partitioned Rice codes
+long long flac_fixed_frames(int batch, const int64_t *n_samples);      // frames of the batch
+int flac_rate_code(int rate);                   // the frame header's 4-bit code of a sample rate (flac_frames.hip)
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_flac_fixed(const float *audio, long long stride, int batch, const int64_t *n_samples, int sample_rate,
+                             const uint16_t *crc_tables, const uint8_t *out, long long out_bytes, const int32_t *frame_bytes,
+                             const int64_t *workspace, const float *max_abs);
+// plan, scan and encode passes; frames packed densely from out[0]; max_abs must be zeroed
+void launch_flac_fixed(const float *audio, long long stride, int batch, const int64_t *n_samples, int sample_rate,
+                       const uint16_t *crc_tables, uint8_t *out, int32_t *frame_bytes, int64_t *workspace, int16_t *pcm_out,
+                       float *max_abs, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // optional RMS normalisation of the mel input / de-normalisation of the audio (norm_mel.hip)
 // ---------------------------------------------------------------------------------------------

@@ -221,6 +221,9 @@ def load_library():
     # include/mbexwn_live_resample.h (LIVE_RESAMPLE_SYMBOLS)
     lib.mbxr_resample_rings.restype = i32
     lib.mbxr_resample_rings.argtypes = [fp, i32, i32, vp, i32, i32, i32, i32, fp, i32, fp, i32, i32, vp]
+    # include/mbexwn_flac.h (FLAC_SYMBOLS)
+    lib.mbxf_encode_flac16_fixed.restype = i32
+    lib.mbxf_encode_flac16_fixed.argtypes = [fp, ctypes.c_int64, i32, i64p, i32, vp, vp, ctypes.c_int64, vp, vp, vp, fp, vp]
     _lib = lib
     return lib
 
@@ -239,6 +242,9 @@ LIVE_SYMBOLS = ["mbxl_ring_append", "mbxl_mel_frames"]
 
 # include/mbexwn_live_resample.h: the streaming resampler (prefix mbxr_; the three lists above stay as they are)
 LIVE_RESAMPLE_SYMBOLS = ["mbxr_resample_rings"]
+
+# include/mbexwn_flac.h: the compressing FLAC encoder (prefix mbxf_; the four lists above stay as they are)
+FLAC_SYMBOLS = ["mbxf_encode_flac16_fixed"]
 
 
 def _check(status):
@@ -1061,13 +1067,18 @@ class MBExWNEngine:
             raise ValueError(f"f0_item_mask must be an int32 tensor of shape ({B},) on the engine's device")
         return tuple(None if cc is None else cc.contiguous() for cc in (f0_frames, f0_scale, f0_item_mask))
 
-    def encode_flac16(self, audio, n_samples, sample_rate=None, wait=True):
-        """mbx_encode_flac16: the FLAC frames (``flac.encode`` of the item without its 42-byte header) and max |x| of every
-        item audio[b, :n_samples[b]] of a device batch (B, stride) float32, encoded on the engine's stream and copied into
-        pinned host memory asynchronously.  ``n_samples``: host integers; ``sample_rate`` defaults to the model's.  Returns an
+    def encode_flac16(self, audio, n_samples, sample_rate=None, wait=True, compression="verbatim"):
+        """The FLAC frames (``flac.encode`` of the item without its 42-byte header) and max |x| of every item
+        audio[b, :n_samples[b]] of a device batch (B, stride) float32, encoded on the engine's stream and copied into pinned
+        host memory asynchronously.  ``n_samples``: host integers; ``sample_rate`` defaults to the model's.
+        ``compression="verbatim"`` is mbx_encode_flac16; ``"fixed"`` is mbxf_encode_flac16_fixed (fixed predictors and Rice
+        codes, the bytes of ``flac.encode(..., compression="fixed")``): the frame lengths come back first (the call waits
+        for them), then only the bytes the frames take, and the int16 samples for the MD5.  Returns an
         :class:`EncodedFlac`; with ``wait=False`` the copies may still be in flight (``EncodedFlac.wait()`` before reading)."""
         from . import flac
         torch = self._torch
+        if compression not in flac.COMPRESSIONS:
+            raise ValueError(f"compression must be one of {flac.COMPRESSIONS}, got {compression!r}")
         if audio.dim() != 2 or audio.dtype != torch.float32 or audio.device != self.device:
             raise ValueError("audio must be a float32 tensor (batch, stride) on the engine's device")
         audio = audio.contiguous()
@@ -1084,6 +1095,8 @@ class MBExWNEngine:
         out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
         max_abs = torch.empty(max(B, 1), dtype=torch.float32, device=self.device)
         counts_c = (ctypes.c_int64 * max(B, 1))(*counts)
+        if compression == "fixed":
+            return self._encode_flac16_fixed(audio, counts, counts_c, rate, out, total, max_abs, wait)
         with torch.cuda.device(self.device):
             _check(self._lib.mbx_encode_flac16(audio.data_ptr(), stride, B, counts_c, rate, self._flac_tables.data_ptr(),
                                                out.data_ptr(), total, max_abs.data_ptr(), self._stream()))
@@ -1094,6 +1107,44 @@ class MBExWNEngine:
             event = torch.cuda.Event()
             event.record(torch.cuda.current_stream(self.device))
         res = EncodedFlac(host, offsets, host_max, counts, rate, event)
+        return res.wait() if wait else res
+
+    def _encode_flac16_fixed(self, audio, counts, counts_c, rate, out, capacity, max_abs, wait):
+        """The compressed half of :meth:`encode_flac16`: frames packed densely, so the lengths are copied back first and
+        say how many bytes of ``out`` to copy."""
+        from . import flac
+        torch = self._torch
+        B, stride = int(audio.shape[0]), int(audio.shape[1])
+        frame_counts = [-(-nn // flac.BLOCK) for nn in counts]
+        frames = sum(frame_counts)
+        frame_bytes = torch.empty(max(frames, 1), dtype=torch.int32, device=self.device)
+        workspace = torch.empty(3 * frames + 1, dtype=torch.int64, device=self.device)
+        pcm = torch.empty((max(B, 1), max(stride, 1)), dtype=torch.int16, device=self.device)
+        with torch.cuda.device(self.device):
+            _check(self._lib.mbxf_encode_flac16_fixed(audio.data_ptr(), stride, B, counts_c, rate, self._flac_tables.data_ptr(),
+                                                      out.data_ptr(), capacity, frame_bytes.data_ptr(), workspace.data_ptr(),
+                                                      pcm.data_ptr(), max_abs.data_ptr(), self._stream()))
+            host_lengths = torch.empty(frame_bytes.shape, dtype=torch.int32, pin_memory=True)
+            host_lengths.copy_(frame_bytes, non_blocking=True)
+            first = torch.cuda.Event()
+            first.record(torch.cuda.current_stream(self.device))
+            host_pcm = torch.empty(pcm.shape, dtype=torch.int16, pin_memory=True)
+            host_pcm.copy_(pcm, non_blocking=True)
+            host_max = torch.empty(max_abs.shape, dtype=torch.float32, pin_memory=True)
+            host_max.copy_(max_abs, non_blocking=True)
+            first.synchronize()                              # the lengths say how many bytes the frames take
+            lengths = host_lengths.numpy()[:frames].astype(np.int64)
+            used = int(lengths.sum())
+            if used > capacity:
+                raise RuntimeError("mbexwn_hip: the frame lengths exceed the output buffer")
+            host = torch.empty(max(used, 1), dtype=torch.uint8, pin_memory=True)
+            host.copy_(out[:max(used, 1)], non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(self.device))
+        bounds = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(frame_counts, out=bounds[1:])
+        offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)[bounds]
+        res = EncodedFlac(host, offsets, host_max, counts, rate, event, frame_lengths=lengths, frame_bounds=bounds, pcm=host_pcm)
         return res.wait() if wait else res
 
     def window_advance(self, mel_window, mel_new, noise_window=None, noise_new=None):
@@ -1457,11 +1508,14 @@ class MBExWNEngine:
 
 class EncodedFlac:
     """What :meth:`MBExWNEngine.encode_flac16` returns: the frames of every item in one pinned host buffer (item b at
-    ``offsets[b]:offsets[b + 1]``) and max |x| per item, behind the event of their device-to-host copies."""
+    ``offsets[b]:offsets[b + 1]``) and max |x| per item, behind the event of their device-to-host copies.  Compressed frames
+    (``compression="fixed"``) come with their lengths (``frame_lengths(b)``) and the int16 samples they hold (``pcm(b)``)."""
 
-    def __init__(self, host, offsets, max_abs, n_samples, rate, event):
+    def __init__(self, host, offsets, max_abs, n_samples, rate, event, frame_lengths=None, frame_bounds=None, pcm=None):
         self._host, self._host_max, self._event = host, max_abs, event
         self.offsets, self.n_samples, self.rate = offsets, list(n_samples), rate
+        self._lengths, self._bounds, self._pcm = frame_lengths, frame_bounds, pcm
+        self.compression = "verbatim" if frame_lengths is None else "fixed"
         self.max_abs = None
 
     def wait(self):
@@ -1476,11 +1530,30 @@ class EncodedFlac:
         self.wait()
         return self._host.numpy()[self.offsets[b]:self.offsets[b + 1]]
 
+    def frame_lengths(self, b):
+        """The lengths of the compressed frames of item b; None for uncompressed frames (``flac.frame_layout`` has those)."""
+        if self._lengths is None:
+            return None
+        return self._lengths[self._bounds[b]:self._bounds[b + 1]]
+
+    def pcm(self, b):
+        """The int16 samples the compressed frames of item b hold; None for uncompressed frames (they hold them as they are)."""
+        if self._pcm is None:
+            return None
+        self.wait()
+        return self._pcm.numpy()[b, :self.n_samples[b]]
+
     def stream(self, b):
         """The whole FLAC stream of item b (``flac.assemble``); only for an item whose max |x| is finite -- any other goes
         through the host writer, ``flac.encode``."""
         from . import flac
-        return flac.assemble(self.frames(b), self.n_samples[b], self.rate)
+        return flac.assemble(self.frames(b), self.n_samples[b], self.rate, frame_lengths=self.frame_lengths(b), pcm=self.pcm(b))
+
+    def write(self, path, b):
+        """``stream(b)`` into a file (``flac.write_frames``: the frames are written as they are)."""
+        from . import flac
+        return flac.write_frames(path, self.frames(b), self.n_samples[b], self.rate, frame_lengths=self.frame_lengths(b),
+                                 pcm=self.pcm(b))
 
 
 class _HostTensor:

@@ -1,5 +1,5 @@
-"""Minimal FLAC writer (mono / multi-channel 16-bit PCM, VERBATIM sub-frames) for the CLI's default output format, and a
-reader of what it writes (``decode``).
+"""Minimal FLAC writer (mono / multi-channel 16-bit PCM, VERBATIM sub-frames; mono with FIXED predictors and Rice codes on
+request) for the CLI's default output format, and a reader of what it writes (``decode``).
 
 The reference CLI writes ``--format flac`` through its ``sndio`` module on top of libsndfile (reference
 bin/resynth_mel.py:104-105), which is not part of this image.  A FLAC stream does not have to be compressed: a
@@ -11,7 +11,14 @@ The layout of the frames and the headers are defined here once (frame_layout, fr
 builds a stream from them, and the device encoder (csrc/flac_frames.hip through ``MBExWNEngine.encode_flac16``) writes the
 same frames, in front of which ``write_frames`` / ``assemble`` put the header with the MD5 of the samples.
 
-Format: https://xiph.org/flac/format.html (STREAMINFO, FRAME_HEADER, SUBFRAME_VERBATIM, FRAME_FOOTER).
+``compression="fixed"`` compresses: every frame takes the cheapest of FLAC's fixed predictors of orders 0-4 with
+partitioned Rice codes (``plan_fixed_frame`` makes the choices, DESIGN.md defines them), a CONSTANT sub-frame where all
+samples are equal, and stays VERBATIM where no predictor saves a bit.  The device encoder of csrc/flac_fixed.hip
+(``MBExWNEngine.encode_flac16(..., compression="fixed")``) writes the same bytes.  Frame lengths then come from the data:
+``stream_header`` / ``assemble`` / ``write_frames`` take them as a list.
+
+Format: https://xiph.org/flac/format.html (STREAMINFO, FRAME_HEADER, SUBFRAME_VERBATIM / _CONSTANT / _FIXED, RESIDUAL,
+FRAME_FOOTER).
 """
 import hashlib
 import struct
@@ -151,10 +158,11 @@ def frame_header(index, size, rate, channels=1):
     return head + bytes([crc8(head)])
 
 
-def stream_header(n, rate, md5, channels=1):
-    """The 42 bytes in front of the frames: "fLaC" and STREAMINFO (block sizes, the smallest and largest frame of
-    frame_layout, rate, channels, 16 bits, sample count, ``md5`` = MD5 digest of the little-endian int16 samples)."""
-    lengths = np.diff(frame_layout(n, channels)[0])
+def stream_header(n, rate, md5, channels=1, frame_lengths=None):
+    """The 42 bytes in front of the frames: "fLaC" and STREAMINFO (block sizes, the smallest and largest frame -- of
+    ``frame_lengths`` where the frames are compressed, else of frame_layout --, rate, channels, 16 bits, sample count,
+    ``md5`` = MD5 digest of the little-endian int16 samples)."""
+    lengths = np.diff(frame_layout(n, channels)[0]) if frame_lengths is None else np.asarray(frame_lengths, dtype=np.int64)
     min_frame, max_frame = (int(lengths.min()), int(lengths.max())) if lengths.size else (0, 0)
     info = struct.pack(">HH", BLOCK, BLOCK) + min_frame.to_bytes(3, "big") + max_frame.to_bytes(3, "big")
     packed = (int(rate) << 44) | ((channels - 1) << 41) | ((16 - 1) << 36) | int(n)          # 20 + 3 + 5 + 36 bits
@@ -163,8 +171,104 @@ def stream_header(n, rate, md5, channels=1):
     return b"fLaC" + bytes([0x80]) + len(info).to_bytes(3, "big") + info         # last-block flag | STREAMINFO
 
 
-def encode(data, rate):
-    """bytes of a FLAC stream holding ``data`` (float or int16; (frames,) or (frames, channels <= 8)) at ``rate`` Hz."""
+MAX_FIXED_ORDER = 4
+MAX_RICE = 14                               # Rice parameters 0..14 in 4 bits; 15 would mark an escape partition, never written
+COMPRESSIONS = ("verbatim", "fixed")
+
+
+def partition_order(size):
+    """Partition order of a ``size``-sample frame: min(4, trailing zero bits of size), lowered while the partitions would
+    hold 4 samples or fewer."""
+    size = int(size)
+    order = min(4, (size & -size).bit_length() - 1)
+    while order > 0 and (size >> order) <= 4:
+        order -= 1
+    return order
+
+
+def _fixed_costs(block):
+    """Per fixed order o = 0 .. min(4, size - 1) of one frame: (T(o), Rice parameter per partition, zigzag residuals u of
+    n >= o, first residual of every partition, residuals per partition)."""
+    size = block.size
+    parts = 1 << partition_order(size)
+    plen = size // parts
+    shifts = np.arange(MAX_RICE + 1, dtype=np.int64)[:, None]
+    res = block.astype(np.int64)
+    out = []
+    for order in range(min(MAX_FIXED_ORDER, size - 1) + 1):
+        if order:
+            res = np.diff(res)
+        zig = np.where(res >= 0, 2 * res, -2 * res - 1)
+        starts = np.maximum(np.arange(parts, dtype=np.int64) * plen - order, 0)
+        counts = np.diff(np.append(starts, size - order))
+        cost = np.add.reduceat(zig[None, :] >> shifts, starts, axis=1) + (shifts + 1) * counts[None, :]
+        rice = np.argmin(cost, axis=0)                        # the first minimum: ties go to the smaller parameter
+        out.append((16 * order + 6 + int((4 + cost.min(axis=0)).sum()), rice, zig, starts, counts))
+    return out
+
+
+def plan_fixed_frame(block):
+    """The choices ``compression="fixed"`` makes for one frame of int16 samples: ``(kind, order, partition order, Rice
+    parameters)`` with kind "constant" (all samples equal), "fixed" (the smallest T(o) is below 16 * size bits; ties go to
+    the smaller order) or "verbatim"; order and the rest are None unless the kind is "fixed"."""
+    block = np.asarray(block)
+    if np.all(block == block[0]):
+        return "constant", None, None, None
+    costs = _fixed_costs(block)
+    order = min(range(len(costs)), key=lambda oo: (costs[oo][0], oo))
+    if costs[order][0] >= 16 * block.size:
+        return "verbatim", None, None, None
+    return "fixed", order, partition_order(block.size), [int(kk) for kk in costs[order][1]]
+
+
+def _pack_fields(zeros, widths, values):
+    """Bit fields, most significant bit first, into bytes: field i is zeros[i] zero bits, then the widths[i] (<= 16) low
+    bits of values[i]; zero bits up to the byte boundary."""
+    ends = np.cumsum(zeros + widths)
+    bits = np.zeros(-(-int(ends[-1]) // 8) * 8, dtype=np.uint8)
+    for jj in range(int(widths.max())):
+        sel = widths > jj
+        bits[ends[sel] - 1 - jj] = (values[sel] >> jj) & 1
+    return np.packbits(bits).tobytes()
+
+
+def _fixed_subframe(block):
+    """The sub-frame of one mono frame under ``compression="fixed"``: the type byte and what follows it, byte padded."""
+    kind, order, part_order, _ = plan_fixed_frame(block)
+    if kind == "constant":
+        return b"\x00" + block[:1].astype(">i2").tobytes()
+    if kind == "verbatim":
+        return b"\x02" + block.astype(">i2").tobytes()
+    total, rice, zig, starts, counts = _fixed_costs(block)[order]
+    par = np.repeat(rice, counts)
+    # the residual codes: u >> k zero bits, a one bit, the k low bits of u; in front of every partition its parameter in 4
+    # bits; in front of all that the type byte, the warm-up samples, 00 (4-bit parameters) and the partition order
+    zeros = np.insert(zig >> par, starts, 0)
+    widths = np.insert(par + 1, starts, 4)
+    values = np.insert((1 << par) | (zig & ((1 << par) - 1)), starts, rice)
+    warm = block[:order].astype(np.int64) & 0xFFFF
+    zeros = np.concatenate([np.zeros(order + 3, dtype=np.int64), zeros])
+    widths = np.concatenate([[8], np.full(order, 16, dtype=np.int64), [2, 4], widths])
+    values = np.concatenate([[0x10 + 2 * order], warm, [0, part_order], values])
+    assert int((zeros + widths).sum()) == 8 + total
+    return _pack_fields(zeros, widths, values)
+
+
+def fixed_frames(pcm, rate):
+    """The frames of the mono int16 samples ``pcm`` under ``compression="fixed"``: a list of bytes, one per frame."""
+    frames = []
+    for index, start in enumerate(range(0, pcm.size, BLOCK)):
+        block = pcm[start:start + BLOCK]
+        frame = frame_header(index, block.size, rate) + _fixed_subframe(block)
+        frames.append(frame + struct.pack(">H", crc16(frame)))
+    return frames
+
+
+def encode(data, rate, compression="verbatim"):
+    """bytes of a FLAC stream holding ``data`` (float or int16; (frames,) or (frames, channels <= 8)) at ``rate`` Hz.
+    ``compression``: "verbatim" (uncompressed sub-frames) or "fixed" (mono only: fixed predictors and Rice codes)."""
+    if compression not in COMPRESSIONS:
+        raise ValueError(f"FLAC: compression must be one of {COMPRESSIONS}, got {compression!r}")
     pcm = to_pcm16(data)
     if pcm.ndim == 1:
         pcm = pcm[:, None]
@@ -172,6 +276,12 @@ def encode(data, rate):
     if not 1 <= channels <= 8 or not 0 < rate < (1 << 20):
         raise ValueError("FLAC: 1..8 channels and a sample rate below 2^20 Hz")
     rate = int(rate)
+    if compression == "fixed":
+        if channels != 1:
+            raise ValueError("FLAC: compression=\"fixed\" writes mono streams only")
+        frames = fixed_frames(np.ascontiguousarray(pcm[:, 0]), rate)
+        md5 = hashlib.md5(pcm.astype("<i2").tobytes()).digest()
+        return stream_header(n, rate, md5, frame_lengths=[len(ff) for ff in frames]) + b"".join(frames)
     frames = []
     for index, start in enumerate(range(0, n, BLOCK)):
         block = pcm[start:start + BLOCK]
@@ -195,24 +305,148 @@ def pcm16_from_frames(frames, n):
     return pcm
 
 
-def assemble(frames, n, rate):
-    """The whole mono stream from frames encoded elsewhere (the device encoder): header with the MD5 of their samples, frames."""
-    return stream_header(n, rate, hashlib.md5(pcm16_from_frames(frames, n)).digest()) + bytes(frames)
+def _frames_md5(frames, n, pcm):
+    """MD5 of the samples of mono frames: of ``pcm`` (int16, what compressed frames hold) if given, else read out of the
+    VERBATIM frames themselves."""
+    if pcm is None:
+        return hashlib.md5(pcm16_from_frames(frames, n)).digest()
+    pcm = np.asarray(pcm)
+    if pcm.dtype != np.int16 or pcm.shape != (int(n),):
+        raise ValueError("FLAC: pcm must hold the stream's n int16 samples")
+    return hashlib.md5(pcm.astype("<i2").tobytes()).digest()
+
+
+def assemble(frames, n, rate, frame_lengths=None, pcm=None):
+    """The whole mono stream from frames encoded elsewhere (the device encoder): header with the MD5 of their samples, frames.
+    Compressed frames come with the list of their lengths and the int16 samples they hold."""
+    if (frame_lengths is None) != (pcm is None):
+        raise ValueError("FLAC: compressed frames need both their lengths and their samples")
+    return stream_header(n, rate, _frames_md5(frames, n, pcm), frame_lengths=frame_lengths) + bytes(frames)
 
 
 _BLOCK_SIZES = {1: 192, **{cc: 576 << (cc - 2) for cc in range(2, 6)}, **{cc: 256 << (cc - 8) for cc in range(8, 16)}}
 
 
+class _ShortWindow(Exception):
+    """The bits of a sub-frame run past the window they are read from."""
+
+
+def _parse_subframe_bits(bits, size, sub):
+    """One mono 16-bit sub-frame from the 0/1 array ``bits`` that starts behind its type byte ``sub``: (int64 samples, bits
+    read).  CONSTANT, VERBATIM and FIXED, each with or without wasted bits."""
+    total = bits.size
+    cursor = 0
+
+    def read(width, signed=False):
+        nonlocal cursor
+        if cursor + width > total:
+            raise _ShortWindow
+        value = 0
+        for bit in bits[cursor:cursor + width].tolist():
+            value = (value << 1) | bit
+        cursor += width
+        return value - (1 << width) if signed and width and value >> (width - 1) else value
+
+    def read_block(count, width):
+        """count signed width-bit numbers"""
+        nonlocal cursor
+        if width == 0:
+            return np.zeros(count, dtype=np.int64)
+        if cursor + count * width > total:
+            raise _ShortWindow
+        field = bits[cursor:cursor + count * width].reshape(count, width).astype(np.int64)
+        cursor += count * width
+        value = field @ (1 << np.arange(width - 1, -1, -1, dtype=np.int64))
+        return value - ((value >> (width - 1)) << width)
+
+    wasted = 0
+    if sub & 1:                                              # wasted bits: their number minus one in unary
+        while read(1) == 0:
+            wasted += 1
+        wasted += 1
+    depth = 16 - wasted
+    if depth < 1:
+        raise ValueError("FLAC reader: more wasted bits than bits per sample")
+    kind = sub >> 1
+    if kind == 0:
+        block = np.full(size, read(depth, signed=True), dtype=np.int64)
+    elif kind == 1:
+        block = read_block(size, depth)
+    else:
+        order = kind - 8
+        if order > size:
+            raise ValueError("FLAC reader: a FIXED sub-frame with more warm-up samples than the frame holds")
+        warm = read_block(order, depth)
+        method = read(2)
+        if method > 1:
+            raise ValueError("FLAC reader: reserved residual coding method")
+        par_bits = 4 + method
+        part_order = read(4)
+        parts = 1 << part_order
+        if size % parts or (size >> part_order) < order:
+            raise ValueError("FLAC reader: partition order does not fit the block size")
+        nxt = None
+        residual = []
+        for part in range(parts):
+            count = (size >> part_order) - (order if part == 0 else 0)
+            par = read(par_bits)
+            if par == (1 << par_bits) - 1:                   # escape: raw numbers
+                residual.append(read_block(count, read(5)))
+                continue
+            if nxt is None:                                  # position of the first one bit at or behind every position
+                idx = np.where(bits != 0, np.arange(total, dtype=np.int64), total)
+                nxt = np.minimum.accumulate(idx[::-1])[::-1].tolist()
+            ones = []
+            for _ in range(count):
+                if cursor >= total or nxt[cursor] + par >= total:
+                    raise _ShortWindow
+                one = nxt[cursor]
+                ones.append(one - cursor)
+                cursor = one + 1 + par
+            quot = np.asarray(ones, dtype=np.int64)
+            low = np.zeros(count, dtype=np.int64)
+            if par and count:
+                first = np.cumsum(quot + 1 + par) - par + (cursor - int((quot + 1 + par).sum()))
+                for jj in range(par):
+                    low = (low << 1) | bits[first + jj]
+            zig = (quot << par) | low
+            residual.append((zig >> 1) ^ -(zig & 1))
+        seq = np.concatenate(residual) if residual else np.zeros(0, dtype=np.int64)
+        for level in range(order - 1, -1, -1):               # undo one difference at a time
+            seq = np.diff(warm, n=level)[-1] + np.cumsum(seq)
+        block = np.concatenate([warm, seq])
+    return block << wasted, cursor
+
+
+def _decode_subframe_bits(data, pos, size, sub):
+    """A sub-frame that is not byte aligned, from byte ``pos`` of ``data`` (behind the type byte): (big-endian int16 block,
+    position of the byte behind its padding).  The bits are unpacked from a window that grows when the codes run past it."""
+    window = 2 * size + 64
+    while True:
+        chunk = np.frombuffer(data, dtype=np.uint8, count=min(window, len(data) - pos), offset=pos)
+        try:
+            block, used = _parse_subframe_bits(np.unpackbits(chunk), size, sub)
+            break
+        except _ShortWindow:
+            if pos + window >= len(data):
+                raise ValueError("FLAC reader: truncated frame") from None
+            window *= 4
+    if block.size and (block.min() < -32768 or block.max() > 32767):
+        raise ValueError("FLAC reader: a decoded sample does not fit 16 bits")
+    return block.astype(">i2"), pos + -(-used // 8)
+
+
 def decode(stream):
-    """``(int16 samples, rate)`` of a FLAC stream of the kind this module's writers produce: mono, 16 bits, VERBATIM or
-    CONSTANT sub-frames.  Every frame's CRC-8 and CRC-16 and the MD5 of STREAMINFO are checked (an all-zero MD5 means "not
-    computed" and is accepted).  Anything else -- more channels, another sample size, a predicted (FIXED / LPC) sub-frame,
-    as a compressing encoder writes them -- raises ``ValueError`` that says to install ``soundfile``."""
+    """``(int16 samples, rate)`` of a mono 16-bit FLAC stream with VERBATIM, CONSTANT or FIXED sub-frames: what this module's
+    writers produce, and what other encoders make of the same kinds (partitioned Rice residuals with 4- or 5-bit parameters,
+    escape partitions, wasted bits, any partition order).  Every frame's CRC-8 and CRC-16 and the MD5 of STREAMINFO are
+    checked (an all-zero MD5 means "not computed" and is accepted).  Anything else -- more channels, another sample size,
+    an LPC sub-frame -- raises ``ValueError`` that says to install ``soundfile``."""
     data = bytes(stream)
 
     def refuse(what):
-        return ValueError(f"FLAC reader: {what}; only mono 16-bit streams with VERBATIM / CONSTANT sub-frames are built "
-                          "in -- install soundfile to read other FLAC files")
+        return ValueError(f"FLAC reader: {what}; only mono 16-bit streams with VERBATIM / CONSTANT / FIXED sub-frames are "
+                          "built in -- install soundfile to read other FLAC files")
 
     if len(data) < HEADER_BYTES or data[:4] != b"fLaC":
         raise ValueError("FLAC reader: not a FLAC stream (no fLaC marker)")
@@ -265,8 +499,14 @@ def decode(stream):
         elif sub == 0x00:                                    # CONSTANT
             block = np.full(size, np.frombuffer(data[pos:pos + 2], dtype=">i2")[0] if pos + 2 <= len(data) else 0, dtype=">i2")
             pos += 2
-        else:
-            raise refuse(f"sub-frame type byte 0x{sub:02x}")
+        elif sub & 0x80:
+            raise ValueError(f"FLAC reader: sub-frame type byte 0x{sub:02x} with its padding bit set")
+        elif sub & 0x40:
+            raise refuse("an LPC sub-frame")
+        elif sub >> 1 > 1 and not 8 <= sub >> 1 <= 8 + MAX_FIXED_ORDER:
+            raise ValueError(f"FLAC reader: reserved sub-frame type byte 0x{sub:02x}")
+        else:                                                # FIXED, or wasted bits: not byte aligned
+            block, pos = _decode_subframe_bits(data, pos, size, sub)
         if block.size != size or pos + 2 > len(data):
             raise ValueError("FLAC reader: truncated frame")
         if crc16(data[start:pos]) != int.from_bytes(data[pos:pos + 2], "big"):
@@ -281,16 +521,18 @@ def decode(stream):
     return pcm.astype(np.int16), int(rate)
 
 
-def write(path, data, rate):
+def write(path, data, rate, compression="verbatim"):
     with open(path, "wb") as fo:
-        fo.write(encode(data, rate))
+        fo.write(encode(data, rate, compression))
     return path
 
 
-def write_frames(path, frames, n, rate):
+def write_frames(path, frames, n, rate, frame_lengths=None, pcm=None):
     """``assemble`` into a file, the frames written as they are (no copy)."""
-    md5 = hashlib.md5(pcm16_from_frames(frames, n)).digest()
+    if (frame_lengths is None) != (pcm is None):
+        raise ValueError("FLAC: compressed frames need both their lengths and their samples")
+    md5 = _frames_md5(frames, n, pcm)
     with open(path, "wb") as fo:
-        fo.write(stream_header(n, rate, md5))
+        fo.write(stream_header(n, rate, md5, frame_lengths=frame_lengths))
         fo.write(frames)
     return path

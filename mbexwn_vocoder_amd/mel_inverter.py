@@ -195,7 +195,8 @@ class MELInverter(object):
                 warnings.warn(f"MELInverter: calibration on the first mel failed ({exc}); keeping the convolution form "
                               f"chosen at creation ({self.model.conv_form_info()['form']})", RuntimeWarning)
 
-    def synth_from_mels(self, scaled_mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False):
+    def synth_from_mels(self, scaled_mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False,
+                        flac_compression="verbatim"):
         """Batched :meth:`synth_from_mel` (this build): a list of ``scale_mel`` outputs (1, T_i, mel_channels) -> a list of
         float32 audio (T_i * hop_size,), or with ``flac=True`` of complete FLAC files (bytes; frames encoded on the device).
 
@@ -217,7 +218,8 @@ class MELInverter(object):
             noises = [torch.as_tensor(np.asarray(zz) if not torch.is_tensor(zz) else zz).to(self.model.device, torch.float32)
                       .reshape(-1) for zz in noises]
         out = [None] * len(mels)
-        for batch in run_micro_batches(self.model, mels, noises, max_batch, max_padded_frames, flac=flac, host_audio=not flac):
+        for batch in run_micro_batches(self.model, mels, noises, max_batch, max_padded_frames, flac=flac, host_audio=not flac,
+                                       flac_compression=flac_compression):
             batch.wait()
             for jj, ii in enumerate(batch.indices):
                 if not flac:
@@ -226,7 +228,7 @@ class MELInverter(object):
                     out[ii] = batch.flac.stream(jj)
                 else:
                     from . import flac as flac_writer
-                    out[ii] = flac_writer.encode(batch.audio(jj), self.srate)
+                    out[ii] = flac_writer.encode(batch.audio(jj), self.srate, flac_compression)
         return out
 
     def calibrate(self, scaled_mells, verbose=False, max_frames=400, seed=42):

@@ -12,26 +12,21 @@
 //   encode  one block per (frame, item) again: quantise again (cheaper than staging the samples through memory), every
 //           thread the lengths of the codes of its 16 samples, a block-wide prefix sum for their bit positions, the bits
 //           OR-ed into a zeroed frame image in LDS (neighbouring threads share words: LDS atomics, one per 32-bit word a
-//           thread touches), CRC-16 by the log-depth combine of flac_frames.hip over a now variable byte count, write-out to
-//           the unaligned destination as flac_frames_kernel does.
+//           thread touches), CRC-16 by flac_frame.h's log-depth combine over a now variable byte count, write-out to the
+//           unaligned destination by flac_frame.h's write_frame.
 // A VERBATIM or CONSTANT frame runs through the same encode path: its "codes" are the samples in 16 bits each.
-#include "mbx_kernels.h"
+// What a frame is -- quantisation, header, CRC-16, write-out -- is flac_frame.h's, shared with flac_frames.hip.
+#include "flac_frame.h"
 
 namespace mbx {
 
 namespace {
 
-constexpr int FT = FLAC_THREADS;
-constexpr int PER = FLAC_BLOCK / FT;                        // consecutive samples per thread
 constexpr int MAX_ORDER = 4, RICE_PARAMS = 15, MAX_PARTS = 16;
-// longest frame: 4 sync/code bytes + 3-byte frame number + 16-bit block size + CRC-8 + sub-frame byte + 2 * 4096 + CRC-16
-constexpr int MAX_FRAME_BYTES = 4 + 3 + 2 + 1 + 1 + 2 * FLAC_BLOCK + 2;
-constexpr int FRAME_WORDS = (15 + MAX_FRAME_BYTES + 15) / 16;   // LDS frame image, shifted by the frame's address mod 16
 constexpr int CRC_RUN = 36;                                 // bytes per thread in the CRC stage
 constexpr int SCAN_THREADS = 1024;
 enum { KIND_CONSTANT = 0, KIND_VERBATIM = 1, KIND_FIXED = 2 };
 
-static_assert(PER == 16, "16 consecutive samples per thread");
 static_assert(CRC_RUN * FT >= MAX_FRAME_BYTES - 2, "the CRC runs cover the longest frame");
 
 struct FlacFixedArgs {
@@ -49,16 +44,10 @@ struct FlacFixedArgs {
     long long frame_base[FLAC_ITEMS_PER_LAUNCH];    // index in the batch of the item's first frame
 };
 
-__host__ __device__ inline int frame_number_bytes(long long f) { return f < 128 ? 1 : (f < 2048 ? 2 : 3); }
-
 __device__ inline int partition_order(int size) {
     int p = min(4, __ffs(size) - 1);
     while (p > 0 && (size >> p) <= 4) --p;
     return p;
-}
-
-__device__ inline int quantise(float v) {
-    return (int)fmin(fmax(rint((double)v * 32767.0), -32768.0), 32767.0);
 }
 
 // zigzag of the o-th finite difference at n >= o
@@ -72,38 +61,6 @@ __device__ inline uint32_t zigzag_residual(const int16_t *x, int n, int o) {
         default: break;
     }
     return r >= 0 ? 2u * (uint32_t)r : 2u * (uint32_t)(-r) - 1u;
-}
-
-__device__ inline uint32_t crc16_byte(uint32_t crc, uint32_t byte, const uint16_t *table) {
-    return ((crc << 8) & 0xFFFFu) ^ table[(crc >> 8) ^ byte];
-}
-
-// M_n crc: the operators of the set bits of n (powers of one matrix: they commute)
-__device__ inline uint32_t crc16_shift(uint32_t crc, uint32_t n, const uint16_t *ops) {
-    for (int k = 0; n != 0u && k < FLAC_CRC_SHIFTS; ++k, n >>= 1) {
-        if (!(n & 1u)) continue;
-        const uint16_t *col = ops + 16 * k;
-        uint32_t r = 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) r ^= (0u - ((crc >> j) & 1u)) & col[j];
-        crc = r;
-    }
-    return crc;
-}
-
-// the frame's samples into LDS; max |x| on the bit pattern of |x|
-__device__ inline uint32_t load_pcm(const FlacFixedArgs &p, int item, long long f, int size, int16_t *pcm, bool store) {
-    const float *x = p.audio + (long long)item * p.stride + f * FLAC_BLOCK;
-    int16_t *keep = store && p.pcm_out ? p.pcm_out + (long long)item * p.stride + f * FLAC_BLOCK : nullptr;
-    uint32_t mx = 0;
-    for (int i = threadIdx.x; i < size; i += FT) {
-        const float v = x[i];
-        mx = max(mx, __float_as_uint(v) & 0x7FFFFFFFu);
-        const int16_t q = (int16_t)quantise(v);
-        pcm[i] = q;
-        if (keep) keep[i] = q;
-    }
-    return mx;
 }
 
 __global__ __launch_bounds__(FLAC_THREADS) void flac_fixed_plan_kernel(FlacFixedArgs p) {
@@ -123,7 +80,8 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_fixed_plan_kernel(FlacFixed
     const int po = partition_order(size), parts = 1 << po, plen = size >> po;
     const int max_o = min(MAX_ORDER, size - 1);
 
-    uint32_t mx = load_pcm(p, item, f, size, pcm, true);
+    const long long at = (long long)item * p.stride + f * FLAC_BLOCK;
+    uint32_t mx = load_pcm(p.audio + at, size, pcm, p.pcm_out ? p.pcm_out + at : nullptr);
     for (int i = tid; i < (MAX_ORDER + 1) * MAX_PARTS * RICE_PARAMS; i += FT) (&sums[0][0][0])[i] = 0ull;
     for (int off = 1; off < 64; off <<= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off));
     if ((tid & 63) == 0) part_max[tid >> 6] = mx;
@@ -196,8 +154,7 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_fixed_plan_kernel(FlacFixed
         int order = 0;
         for (int o = 1; o <= max_o; ++o)
             if (order_cost[o] < order_cost[order]) order = o;   // ties go to the smaller order
-        const int nb = frame_number_bytes(f);
-        const int head = 4 + nb + (size != FLAC_BLOCK ? 2 : 0) + 1;
+        const int head = frame_header_bytes(f, size);
         int kind, body;
         unsigned long long ks = 0ull;
         if (!any_differs) {
@@ -323,9 +280,7 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_fixed_encode_kernel(FlacFix
     if (f * FLAC_BLOCK >= n) return;                        // behind this item's last frame
     const long long rest = n - f * FLAC_BLOCK;
     const int size = rest < FLAC_BLOCK ? (int)rest : FLAC_BLOCK;
-    const bool short_block = size != FLAC_BLOCK;
-    const int nb = frame_number_bytes(f);
-    const int head = 4 + nb + (short_block ? 2 : 0) + 1;   // frame header with its CRC-8
+    const int head = frame_header_bytes(f, size);
     const long long fidx = p.frame_base[item] + f;
     const int flen = min(max(p.frame_bytes[fidx], head + 3), head + 1 + 2 * size + 2);   // what the plan pass wrote
     const unsigned long long ks = p.plan[2 * fidx];
@@ -337,10 +292,9 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_fixed_encode_kernel(FlacFix
     uint8_t *img = reinterpret_cast<uint8_t *>(frame_words);      // img[lead + k] = byte k of the frame
     const int lane = tid & 63, wave = tid >> 6;
 
-    for (int i = tid; i < 256; i += FT) table[i] = p.crc_tables[i];
-    for (int i = tid; i < 16 * FLAC_CRC_SHIFTS; i += FT) ops[i] = p.crc_tables[256 + i];
+    stage_crc_tables(p.crc_tables, table, ops);
     for (int i = tid; i < FRAME_WORDS; i += FT) frame_words[i] = make_uint4(0u, 0u, 0u, 0u);
-    load_pcm(p, item, f, size, pcm, false);
+    load_pcm(p.audio + (long long)item * p.stride + f * FLAC_BLOCK, size, pcm, nullptr);
     __syncthreads();
 
     // the bits of this thread's samples, and where they start
@@ -365,32 +319,7 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_fixed_encode_kernel(FlacFix
     BitWriter bw{reinterpret_cast<uint32_t *>(frame_words), -1, 0u};
     if (tid == 0) {
         uint8_t h[11];
-        int k = 0;
-        h[k++] = 0xFF;
-        h[k++] = 0xF8;                                      // sync, fixed block size
-        h[k++] = (uint8_t)(((short_block ? 7 : 12) << 4) | p.rate_code);
-        h[k++] = 0x08;                                      // one channel, 16 bits per sample
-        const int fi = (int)f;
-        if (nb == 1) {
-            h[k++] = (uint8_t)fi;
-        } else if (nb == 2) {
-            h[k++] = (uint8_t)(0xC0 | (fi >> 6));
-            h[k++] = (uint8_t)(0x80 | (fi & 63));
-        } else {
-            h[k++] = (uint8_t)(0xE0 | (fi >> 12));
-            h[k++] = (uint8_t)(0x80 | ((fi >> 6) & 63));
-            h[k++] = (uint8_t)(0x80 | (fi & 63));
-        }
-        if (short_block) {
-            h[k++] = (uint8_t)((size - 1) >> 8);
-            h[k++] = (uint8_t)((size - 1) & 255);
-        }
-        uint32_t c8 = 0;                                    // CRC-8, poly 0x07, init 0
-        for (int i = 0; i < k; ++i) {
-            c8 ^= h[i];
-            for (int b = 0; b < 8; ++b) c8 = (c8 & 0x80u) ? ((c8 << 1) ^ 0x07u) & 0xFFu : (c8 << 1) & 0xFFu;
-        }
-        h[k++] = (uint8_t)c8;
+        int k = frame_header(h, f, size, p.rate_code);
         // sub-frame byte: CONSTANT 0x00, VERBATIM 0x02, FIXED 0x10 + 2 * order; no wasted bits
         h[k++] = kind == KIND_CONSTANT ? 0x00 : (kind == KIND_VERBATIM ? 0x02 : (uint8_t)(0x10 + 2 * order));
         for (int i = 0; i < k; ++i)
@@ -414,36 +343,9 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_fixed_encode_kernel(FlacFix
         for (int b = b0; b < b1; ++b) crc = crc16_byte(crc, img[lead + b], table);
         len = (uint32_t)max(0, b1 - b0);
     }
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t cr = __shfl_down(crc, off), lr = __shfl_down(len, off);
-        if ((lane & (2 * off - 1)) == 0) {
-            crc = crc16_shift(crc, lr, ops) ^ cr;
-            len += lr;
-        }
-    }
-    if (lane == 0) {
-        part_crc[wave] = crc;
-        part_len[wave] = len;
-    }
+    crc16_join(crc, len, 0u, ops, part_crc, part_len, img + lead + flen - 2);
     __syncthreads();
-    if (tid == 0) {
-        uint32_t total = 0;
-        for (int wv = 0; wv < FT / 64; ++wv) total = crc16_shift(total, part_len[wv], ops) ^ part_crc[wv];
-        img[lead + flen - 2] = (uint8_t)(total >> 8);
-        img[lead + flen - 1] = (uint8_t)(total & 255u);
-    }
-    __syncthreads();
-    // write-out: the 16-byte words that lie inside the frame whole, the two edge words byte by byte
-    const int span = lead + flen, words = (span + 15) / 16;
-    uint8_t *base = dst - lead;
-    for (int wd = tid; wd < words; wd += FT) {
-        const int lo = 16 * wd, hi = lo + 16;
-        if (lo >= lead && hi <= span) {
-            reinterpret_cast<uint4 *>(base)[wd] = frame_words[wd];
-        } else {
-            for (int k = max(lo, lead); k < min(hi, span); ++k) base[k] = img[k];
-        }
-    }
+    write_frame(dst, lead, flen, frame_words);
 }
 
 }  // namespace

@@ -135,6 +135,49 @@ class _AStream:
         self.fresh = True         # the slot's ring still holds another stream's samples
 
 
+class _RingStore:
+    """One ring store of include/mbexwn_live.h: ``slots`` rings of ``ring_samples`` samples, a power of two.  It hands out
+    slots -- ``first_slots`` at first, then doubling; the lowest new slot first, a released slot before any other -- and
+    keeps the device tensor ``rings``, which follows lazily: ``ensure`` brings it up to date at the next tick."""
+
+    def __init__(self, ring_samples, first_slots):
+        self.ring_samples = _pow2_at_least(ring_samples)
+        self.slots, self._first_slots, self._free = 0, max(1, int(first_slots)), []
+        self.rings = None             # (slots, ring_samples) float32 on the device
+
+    def take(self):
+        if not self._free:
+            n_new = max(self._first_slots, 2 * self.slots)
+            self._free = list(range(n_new - 1, self.slots - 1, -1))
+            self.slots = n_new
+        return self._free.pop()
+
+    def release(self, slot):
+        self._free.append(slot)
+
+    def ensure(self, device, ring_needed, held_spans):
+        """``rings`` on ``device`` with a row per slot and rings of at least ``ring_needed`` samples (doubling).  When only the
+        slot count grew the rows are copied over; when the ring lengthened, every (slot, hi) of ``held_spans`` -- the slot
+        holds its stream's samples [max(0, hi - ring_samples), hi) -- moves to its place in the longer ring.
+        -> whether it allocated."""
+        import torch
+        ring = self.ring_samples
+        while ring < ring_needed:
+            ring *= 2
+        old = self.rings
+        if old is not None and old.shape[0] >= self.slots and ring == self.ring_samples:
+            return False
+        new = torch.zeros((self.slots, ring), dtype=torch.float32, device=device)
+        if old is not None and ring == self.ring_samples:
+            new[:old.shape[0]] = old
+        elif old is not None:
+            for slot, hi in held_spans:
+                idx = torch.arange(max(0, hi - self.ring_samples), hi, device=device)
+                new[slot, idx & (ring - 1)] = old[slot, idx & (self.ring_samples - 1)]
+        self.rings, self.ring_samples = new, ring
+        return True
+
+
 class StreamingAnalyzer:
     """Log-mel analysis of any number of concurrent streams, a tick at a time.
 
@@ -169,15 +212,10 @@ class StreamingAnalyzer:
         # for.  The symmetric Hann window is exactly 0 there, the product is a zero whatever finite value the ring holds, and
         # a zero's sign does not survive the magnitudes: same bits.  A window that is not 0 there waits for that sample.
         self._hold_first = self.win % 2 == 0 and float(self._tables_host[0][0]) != 0.0
-        self.ring_samples = _pow2_at_least(max(self.win, int(ring_samples or 4 * self.win)))
         self.device = device
         self.streams = {}
-        self._slots = 0               # slots of the ring store: `slots` at first, then doubling
-        self._first_slots = max(1, int(slots))
-        self._free_slots = []
-        self._rings = None            # (slots, ring_samples) float32 on the device
-        self.input_ring_samples = _pow2_at_least(int(input_ring_samples or 4096))
-        self._in_slots, self._in_free, self._in_rings = 0, [], None     # the input-rate store of the resampled streams
+        self._store = _RingStore(max(self.win, int(ring_samples or 4 * self.win)), slots)      # at the model rate
+        self._in_store = _RingStore(int(input_ring_samples or 4096), slots)     # the input-rate store of the resampled streams
         self._taps = {}               # input rate -> (taps on the device, up, down)
         self._tables = None
         self._stage_host = self._stage_dev = None     # one tick's descriptors and samples: pinned, and its device twin
@@ -186,6 +224,11 @@ class StreamingAnalyzer:
         self.device_allocations = 0   # how often a device store was (re)allocated: constant over steady ticks
         self.time_device = False      # probe: bracket the two launches of a tick with events
         self.last_tick_device_ms = None
+
+    ring_samples = property(lambda self: self._store.ring_samples)
+    input_ring_samples = property(lambda self: self._in_store.ring_samples)
+    _rings = property(lambda self: self._store.rings)          # the stores' tensors, under the names they have had
+    _in_rings = property(lambda self: self._in_store.rings)
 
     # -- host side ----------------------------------------------------------------------------------------------------
     def open(self, stream_id, sample_rate=None):
@@ -201,25 +244,15 @@ class StreamingAnalyzer:
                 rate = int(round(sample_rate))
                 taps, up, down = _host_taps(rate, int(round(self.sample_rate)))
                 filt = (up, down, (taps.size - 1) // 2, int(taps.size))
-        if not self._free_slots:
-            n_new = max(self._first_slots, 2 * self._slots)
-            self._free_slots = list(range(n_new - 1, self._slots - 1, -1))
-            self._slots = n_new       # the device store follows at the next tick (_ensure_device)
-        if rate is None:
-            self.streams[stream_id] = _AStream(self._free_slots.pop())
-            return
-        if not self._in_free:
-            n_new = max(self._first_slots, 2 * self._in_slots)
-            self._in_free = list(range(n_new - 1, self._in_slots - 1, -1))
-            self._in_slots = n_new    # the device store follows at the next tick (_ensure_input)
-        self.streams[stream_id] = _AStream(self._free_slots.pop(), rate, self._in_free.pop(), filt)
+        slot = self._store.take()       # the device stores follow at the next tick (_RingStore.ensure)
+        self.streams[stream_id] = _AStream(slot) if rate is None else _AStream(slot, rate, self._in_store.take(), filt)
 
     def close(self, stream_id):
         """Forget a stream (its slots are reused)."""
         st = self.streams.pop(stream_id)
-        self._free_slots.append(st.slot)
+        self._store.release(st.slot)
         if st.rate is not None:
-            self._in_free.append(st.in_slot)
+            self._in_store.release(st.in_slot)
 
     def push(self, stream_id, samples, last=False, sample_rate=None):
         """Append mono float32 samples to a stream; ``last`` closes it.  ``sample_rate``, when given, must be the stream's
@@ -275,46 +308,9 @@ class StreamingAnalyzer:
         dev = self.device = torch.device(self.device)
         if self._tables is None:
             self._tables = [torch.as_tensor(np.ascontiguousarray(tt), device=dev) for tt in self._tables_host]
-        ring = self.ring_samples
-        while ring < ring_needed:
-            ring *= 2
-        old = self._rings
-        if old is None or old.shape[0] < self._slots or ring > self.ring_samples:
-            new = torch.zeros((self._slots, ring), dtype=torch.float32, device=dev)
-            self.device_allocations += 1
-            if old is not None and ring == self.ring_samples:
-                new[:old.shape[0]] = old
-            elif old is not None:
-                # a longer ring: every sample a ring holds moves to its place in the longer one
-                for st in self.streams.values():
-                    lo, hi = max(0, st.on_device - self.ring_samples), st.on_device
-                    if hi > lo and not st.fresh:
-                        idx = torch.arange(lo, hi, device=dev)
-                        new[st.slot, idx & (ring - 1)] = old[st.slot, idx & (self.ring_samples - 1)]
-            self._rings, self.ring_samples = new, ring
-
-    def _ensure_input(self, ring_needed):
-        """The input-rate store of the resampled streams: grows as the model-rate store does."""
-        import torch
-        dev = self.device
-        ring = self.input_ring_samples
-        while ring < ring_needed:
-            ring *= 2
-        old = self._in_rings
-        if old is None or old.shape[0] < self._in_slots or ring > self.input_ring_samples:
-            new = torch.zeros((self._in_slots, ring), dtype=torch.float32, device=dev)
-            self.device_allocations += 1
-            if old is not None and ring == self.input_ring_samples:
-                new[:old.shape[0]] = old
-            elif old is not None:
-                for st in self.streams.values():
-                    if st.rate is None:
-                        continue
-                    lo, hi = max(0, st.in_on_device - self.input_ring_samples), st.in_on_device
-                    if hi > lo:
-                        idx = torch.arange(lo, hi, device=dev)
-                        new[st.in_slot, idx & (ring - 1)] = old[st.in_slot, idx & (self.input_ring_samples - 1)]
-            self._in_rings, self.input_ring_samples = new, ring
+        # a fresh stream's slot still holds another stream's samples: nothing of it moves to a longer ring
+        held = ((st.slot, st.on_device) for st in self.streams.values() if st.on_device and not st.fresh)
+        self.device_allocations += self._store.ensure(dev, ring_needed, held)
 
     def _device_taps(self, rate):
         if rate not in self._taps:
@@ -350,7 +346,9 @@ class StreamingAnalyzer:
         rs = sorted((row for row, (_, st, _) in enumerate(work) if st.rate is not None), key=lambda row: work[row][1].rate)
         R = len(rs)
         if R:
-            self._ensure_input(max(work[row][1].in_have - self._in_keep_from(work[row][1]) for row in rs))
+            held = ((st.in_slot, st.in_on_device) for st in self.streams.values() if st.rate is not None and st.in_on_device)
+            self.device_allocations += self._in_store.ensure(
+                dev, max(work[row][1].in_have - self._in_keep_from(work[row][1]) for row in rs), held)
             for row in rs:
                 self._device_taps(work[row][1].rate)
         counts = [st.in_have - st.in_on_device if st.rate is not None else st.have - st.on_device for _, st, _ in work]

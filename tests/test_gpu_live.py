@@ -117,7 +117,8 @@ def test_analyzer_equals_the_offline_analysis(case):
     """Five streams (1 sample; win / 2 - 1: folded more than once at the end; win / 2 + 1; exactly 3 hops; 40 hops + 7) in
     pushes cut at random from a fixed seed -- among them pushes of 1 sample and one longer than the ring the analyzer starts
     with (the rings grow) -- with the fifth stream opened after the others have started, into a store of 4 slots (the slots
-    grow): every stream's rows are the offline rows, bit for bit."""
+    grow): every stream's rows are the offline rows, bit for bit.  Then both kinds of growth in one tick: a fifth stream's
+    first push and six windows for a stream that has samples on the device."""
     from mbexwn_vocoder_amd.live import StreamingAnalyzer
     cfg, sounds, want = case
     win, hop = geometry(cfg)
@@ -143,6 +144,33 @@ def test_analyzer_equals_the_offline_analysis(case):
     assert an.device_allocations == before
     for pos, ii in enumerate(order):
         assert np.array_equal(again[pos].view(np.int32), want[ii].view(np.int32)), f"reused slot, {sounds[ii].size} samples"
+    # one tick in which the store both gains slots and lengthens its rings: four streams have samples on the device (the
+    # long one a hop of them, which has to move), then a fifth opens and the long one gets six windows at once
+    an = StreamingAnalyzer(cfg, ring_samples=win, slots=4)
+    got = {sid: [] for sid in range(5)}
+
+    def tick():
+        for sid, rows in an.tick().items():
+            got[sid].append(rows)
+
+    long_one = sounds[4]
+    assert long_one.size > hop + 6 * win > ring0
+    for sid, ii in enumerate(order[:4]):
+        an.open(sid)
+        an.push(sid, sounds[ii][:hop] if ii == 4 else sounds[ii], last=ii != 4)
+    tick()
+    assert tuple(an._rings.shape) == (4, ring0) and an.streams[0].on_device == hop
+    an.open(4)
+    an.push(4, sounds[order[4]], last=True)
+    an.push(0, long_one[hop:hop + 6 * win])
+    tick()
+    assert an._rings.shape[0] == 8 and an.ring_samples > ring0 and an._rings.shape[1] == an.ring_samples
+    an.push(0, long_one[hop + 6 * win:], last=True)
+    tick()
+    assert all(an.finished(sid) for sid in range(5))
+    for sid, ii in enumerate(order):
+        rows = np.concatenate(got[sid])
+        assert np.array_equal(rows.view(np.int32), want[ii].view(np.int32)), f"slots and rings grow at once, {sounds[ii].size} samples"
 
 
 def test_push_cuts_do_not_change_a_bit(case):

@@ -99,9 +99,11 @@ class SynthBatch:
     and what was enqueued behind the forward -- the FLAC frames (``engine.EncodedFlac``) and / or the audio in pinned host
     memory.  :meth:`wait` before reading; ``device_ms`` / ``copy_ms`` are then the forward's and the encode + copies' time."""
 
-    def __init__(self, indices, n_samples, audio, flac, host_audio, events):
+    def __init__(self, indices, n_samples, audio, flac, host_audio, events, model_audio=None):
         self.indices, self.n_samples, self.device_audio = list(indices), list(n_samples), audio
         self.flac, self.host_audio, self._events = flac, host_audio, events
+        # with an output rate: (device audio at the model rate, its lengths) -- everything above is at the output rate
+        self._model_audio = model_audio
         self.device_ms = self.copy_ms = 0.0
 
     def wait(self):
@@ -121,6 +123,13 @@ class SynthBatch:
             return self.host_audio[jj, :nn].numpy()
         return self.device_audio[jj, :nn].cpu().numpy()
 
+    def model_audio(self, jj):
+        """float32 audio of item jj at the model rate (numpy): ``audio(jj)`` unless the batch has an output rate."""
+        if self._model_audio is None:
+            return self.audio(jj)
+        audio, n_samples = self._model_audio
+        return audio[jj, :n_samples[jj]].cpu().numpy()
+
     def max_abs(self, jj):
         if self.flac is not None:
             return float(self.flac.max_abs[jj])
@@ -128,15 +137,20 @@ class SynthBatch:
 
 
 def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False, host_audio=True,
-                      flac_compression="verbatim"):
+                      flac_compression="verbatim", out_rate=None):
     """Generator over the padded micro-batches of ``mels`` (list of (T_i, C) float32 arrays) on ``engine``: each is staged
     and run (engine.forward with the items' lengths), its FLAC frames encoded (``flac``) and / or its audio copied to pinned
     host memory (``host_audio``), all enqueued on the current stream; the SynthBatch is yielded without waiting, so that a
     writer can take it while the next one runs.  ``flac_compression``: "verbatim" or "fixed" (engine.encode_flac16; the
     compressed encoder waits for its frame lengths before the batch is yielded).  ``noises``: per-item device tensors (T_i * wn_in_rows_per_frame,), or
-    None for a model without noise channel."""
+    None for a model without noise channel.  ``out_rate`` (None or the model's rate: nothing changes): the micro-batch is
+    resampled on the device behind the forward (``resample.resample_device`` with the items' own lengths), and the FLAC
+    frames, the host audio and ``n_samples`` of the SynthBatch are at that rate; ``SynthBatch.model_audio`` keeps the
+    model-rate audio."""
     import torch
     dims = engine.dims
+    if out_rate is not None and int(round(out_rate)) == int(round(dims.sample_rate)):
+        out_rate = None
     lengths = [int(mm.shape[0]) for mm in mels]
     stream = torch.cuda.current_stream(engine.device)
     for group in plan_batches(range(len(mels)), lengths, max_batch, max_padded_frames):
@@ -148,13 +162,23 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
         audio = engine.forward(mel, n_frames=n_frames, noise=noise)
         events[1].record(stream)
         n_samples = [lengths[ii] * dims.hop_size for ii in group]
-        enc = engine.encode_flac16(audio, n_samples, wait=False, compression=flac_compression) if flac else None
+        model_audio = None
+        if out_rate is not None:
+            from .resample import device_taps, resample_device
+            _, up, down = device_taps(int(round(dims.sample_rate)), int(round(out_rate)), engine.device)
+            model_audio = (audio, n_samples)
+            audio, _ = resample_device(audio, n_frames * dims.hop_size, int(round(dims.sample_rate)), int(round(out_rate)))
+            n_samples = [-(-nn * up // down) for nn in n_samples]
+        enc = None
+        if flac:
+            enc = engine.encode_flac16(audio, n_samples, sample_rate=None if out_rate is None else int(round(out_rate)),
+                                       wait=False, compression=flac_compression)
         host = None
         if host_audio:
             host = torch.empty(tuple(audio.shape), dtype=torch.float32, pin_memory=True)
             host.copy_(audio, non_blocking=True)
         events[2].record(stream)
-        yield SynthBatch(group, n_samples, audio, enc, host, events)
+        yield SynthBatch(group, n_samples, audio, enc, host, events, model_audio)
 
 
 class _Clock:
@@ -170,14 +194,16 @@ class _Clock:
 
 
 def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threads=2, verbose=False, quiet=False,
-            flac_compression="verbatim"):
+            flac_compression="verbatim", out_rate=None):
     """The batched CLI on this process's GPU: ``files[mine]`` -> syn_<basename>.<fmt> in ``output_dir``.
 
     ``frames``: the frame count after scale_mel of EVERY file of the job, in file order (the noise replay needs all of
     them; default: read here, which needs ``mine`` = all files).  Reader pool (load_var + scale_mel; a missing or bad file
     fails before anything runs), device (forward, FLAC frames, asynchronous copies into pinned memory), writer pool (MD5,
     header, file write); both pools have ``threads`` threads.  ``flac_compression``: what the built-in FLAC writers emit,
-    on the device and on the host ("verbatim" or "fixed")."""
+    on the device and on the host ("verbatim" or "fixed").  ``out_rate``: the files are written at that rate (resampled on
+    the device, ``run_micro_batches``); the verbose ``mel_error`` stays computed on the model-rate audio, the clipping note
+    is about what is written."""
     t_start = time.perf_counter()
     mine = list(range(len(files))) if mine is None else list(mine)
     clock, log_lock = _Clock(), threading.Lock()
@@ -209,6 +235,8 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
              if dims.noise_sigma else None)
     device_flac = fmt.lower() == "flac" and not have_soundfile()
     rate = inv.srate
+    out_rate = inv._output_rate(out_rate)
+    file_rate = rate if out_rate is None else out_rate
     from . import flac
     from .mel_inverter import log_to_db
 
@@ -221,7 +249,7 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
             lines = [] if quiet else [f"synthesize {files[ii]} into {outfile}"]
             audio = sb.audio(jj) if (verbose or not device_flac) else None
             if verbose:                                  # as the one-at-a-time loop (reference :90-96)
-                resyn = inv.generate_mel_from_snd(audio, srate=rate)['mell'].T[np.newaxis]
+                resyn = inv.generate_mel_from_snd(sb.model_audio(jj), srate=rate)['mell'].T[np.newaxis]
                 err = log_to_db * np.mean(np.abs(scaled[ii] - resyn[:, :scaled[ii].shape[1]]))
                 lines.append(f"    synthesized audio with {audio.size} samples in a micro-batch of {len(sb.indices)} "
                              f"({sb.device_ms:.1f} ms on the device), mel_error: {err:.3f}dB")
@@ -233,7 +261,7 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
             if device_flac and np.isfinite(peak):
                 sb.flac.write(outfile, jj)
             else:                                        # soundfile, wav, or an item the host writer must take
-                write_audio(outfile, audio if audio is not None else sb.audio(jj), rate, fmt, flac_compression)
+                write_audio(outfile, audio if audio is not None else sb.audio(jj), file_rate, fmt, flac_compression)
             log(lines)
         clock.add("write", time.perf_counter() - t0)
         clock.add("device_ms", sb.device_ms)
@@ -244,7 +272,7 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
     with ThreadPoolExecutor(max_workers=max(1, threads)) as writers:
         pending = [writers.submit(write, sb) for sb in run_micro_batches(inv.model, mels, noises, max(1, batch),
                                                                          flac=device_flac, host_audio=verbose or not device_flac,
-                                                                         flac_compression=flac_compression)]
+                                                                         flac_compression=flac_compression, out_rate=out_rate)]
         for fu in pending:
             fu.result()
     if verbose:

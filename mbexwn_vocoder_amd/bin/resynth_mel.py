@@ -10,6 +10,8 @@ Deviations (documented in INTEGRATION.md):
     wav: float32 through scipy; the reference uses pysndfile, default format flac)
   * additionally ``--batch N`` (padded micro-batches, FLAC frames encoded on the GPU, reader / writer pools of -nt
     threads), ``--gpus N`` (the files sharded over N child processes by frames) and ``--batch-invariant``
+  * additionally ``--out-rate R``: the files are written at R Hz, resampled on the GPU from the model rate with the
+    reference's resampler (mbexwn_vocoder_amd/resample.py)
 """
 import json
 import os
@@ -29,7 +31,7 @@ from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
          num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None,
-         flac_compression="verbatim"):
+         flac_compression="verbatim", out_rate=None):
     format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
     if flac_compression != "verbatim" and rank is None and not quiet:
         from mbexwn_vocoder_amd.batched import have_soundfile
@@ -42,6 +44,7 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         argv = [model_id, "-i", *input_mell_files, "--format", format, "-nt", str(num_threads), "--batch", str(batch),
                 "--calibrate", str(calibrate), "--conv-form", conv_form, "--flac-compression", flac_compression]
         argv += ["-o", output_dir] if output_dir else []
+        argv += ["--out-rate", str(out_rate)] if out_rate else []
         argv += [flag for flag, on in (("-g", use_gpu), ("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant))
                  if on]
         sys.exit(run_ranks(os.path.abspath(__file__), argv, model_id, input_mell_files, gpus, threads=num_threads,
@@ -86,8 +89,9 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         from mbexwn_vocoder_amd.batched import run_job
         run_job(MelInv, input_mell_files, output_dir, format, frames=plan["frames"] if plan else None,
                 mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose, quiet=quiet,
-                flac_compression=flac_compression)
+                flac_compression=flac_compression, out_rate=out_rate)
         return
+    out_rate = MelInv._output_rate(out_rate)
 
     for mell_file in input_mell_files:
         outfile = os.path.join(output_dir or "", "syn_" + os.path.splitext(os.path.basename(mell_file))[0] + "." + format)
@@ -108,12 +112,26 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
                                                                - mel_resyn[:, :log_mel_spectrogram.shape[1]]))
             print(f"    synthesized audio with {syn_audio.size} samples in {end_time - start_time:.3f}s "
                   f"({syn_audio.size / (end_time - start_time):.2f}Hz), mel_error: {mell_err:.3f}dB", file=sys.stderr)
+        if out_rate is not None:                     # --out-rate: what is written is the resampled audio (mel_error above is not)
+            syn_audio = MelInv._to_rate(torch.as_tensor(syn_audio[np.newaxis]).to(MelInv.model.device), out_rate)[0].cpu().numpy()
         if np.max(np.abs(syn_audio)) > 1:
             norm = 0.99 / np.max(np.abs(syn_audio))
             print(f'    to prevent clipping you would need to normalize {outfile} by {norm:.3f}', file=sys.stderr)
         if verbose:
             print(f"    save audio under {outfile}", file=sys.stderr)
-        write_audio(outfile, syn_audio, MelInv.srate, format, flac_compression)
+        write_audio(outfile, syn_audio, MelInv.srate if out_rate is None else out_rate, format, flac_compression)
+
+
+def positive_rate(text):
+    """argparse type of --out-rate: a positive whole number of Hz."""
+    from argparse import ArgumentTypeError
+    try:
+        rate = int(text)
+    except ValueError:
+        raise ArgumentTypeError(f"a sample rate in Hz is expected, got {text!r}") from None
+    if rate <= 0:
+        raise ArgumentTypeError(f"a sample rate must be positive, got {rate}")
+    return rate
 
 
 if __name__ == "__main__":
@@ -150,6 +168,10 @@ if __name__ == "__main__":
                         help="what the built-in FLAC writer emits: verbatim = uncompressed sub-frames, the size of a wav; fixed "
                              "= fixed predictors of orders 0-4 with Rice codes, on the GPU with --batch / --gpus; ignored when "
                              "soundfile writes the files (Def: %(default)s)")
+    parser.add_argument("--out-rate", dest="out_rate", default=None, type=positive_rate, metavar="R",
+                        help="write the files at R Hz: the audio is resampled on the GPU from the model rate with the "
+                             "reference's resampler; with -v, mel_error stays computed on the model-rate audio, the clipping "
+                             "note is about what is written (Def: the model rate)")
     parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
     parser.add_argument("--job", default=None, help=SUPPRESS)
     args = parser.parse_args()

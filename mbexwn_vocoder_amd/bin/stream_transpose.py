@@ -3,11 +3,13 @@
 pushes, as a live source would deliver it, and writes what the stream gives back.
 
     stream_transpose.py in.wav -o out.wav --model_id VOICE --transposition 1.5 [--tick-ms 80] [--resample]
+                        [--output-rate R|input]
 
 The demonstration of the live path (streaming mel analysis -> scale_mel -> streaming synthesis with per-frame pitch control).
 The input must be at the model's sample rate, unless ``--resample`` is given: then a file at another rate streams at its own
 rate (``--tick-ms`` of its own samples per push), is resampled on the device by the stream, and the output is written at the
-model rate.  A ``.wav`` output holds the float32 samples as they are; any other extension goes through the writers of
+model rate -- or, with ``--output-rate R``, at R Hz (``input``: the file's own rate): the stream resamples its output on the
+device too.  A ``.wav`` output holds the float32 samples as they are; any other extension goes through the writers of
 resynth_mel.py.
 """
 import os
@@ -25,13 +27,14 @@ from mbexwn_vocoder_amd.config import read_config  # noqa: E402
 from mbexwn_vocoder_amd.live import check_rate  # noqa: E402
 
 
-def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0, sample_rate=None):
+def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0, sample_rate=None, output_rate=None):
     """Push `samples` in pieces of tick_samples, one tick per push, until the stream is finished; returns its audio.
-    ``sample_rate``: the rate of `samples` when it is not the model's (the stream resamples)."""
-    if sample_rate is None:
-        live.open(stream_id, seed=seed)
-    else:
-        live.open(stream_id, seed=seed, sample_rate=sample_rate)
+    ``sample_rate``: the rate of `samples` when it is not the model's (the stream resamples); ``output_rate``: the rate the
+    audio comes back at when it is not the model's (a rate in Hz, or "input")."""
+    rates = {} if sample_rate is None else {"sample_rate": sample_rate}
+    if output_rate is not None:
+        rates["output_rate"] = output_rate
+    live.open(stream_id, seed=seed, **rates)
     out = []
     for start in range(0, samples.size, tick_samples):
         end = min(start + tick_samples, samples.size)
@@ -47,13 +50,17 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0,
 
 
 def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tick_ms=80.0, seed=0, quiet=False,
-         resample=False):
+         resample=False, output_rate=None):
     preprocess_config = read_config(config_file=get_config_file(model_id_or_path=model_id))['preprocess_config']
     if not os.path.isfile(input_audio_file):
         print(f"stream_transpose::error:: no such file: {input_audio_file}", file=sys.stderr)
         sys.exit(1)
     samples, rate = read_audio(input_audio_file)
+    model_rate = int(round(preprocess_config["sample_rate"]))
     try:
+        if output_rate == "input" and not resample and int(round(rate)) != model_rate:
+            raise ValueError(f"--output-rate input: {input_audio_file} is at {rate} Hz, not the model rate {model_rate} Hz; "
+                             "stream it at its own rate with --resample")
         if not resample:
             check_rate(rate, preprocess_config["sample_rate"], what=input_audio_file)
         elif int(round(rate)) <= 0:
@@ -74,20 +81,36 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
     from mbexwn_vocoder_amd.mel_inverter import MELInverter
     live = LiveResynthesizer(MELInverter(model_id_or_path=model_id))
     tick_samples = max(1, int(round(tick_ms * 1e-3 * rate)))
-    model_rate = int(round(preprocess_config["sample_rate"]))
     own_rate = int(round(rate)) if int(round(rate)) != model_rate else None
-    audio = stream_file(live, samples, tick_samples, transposition, seed=seed, sample_rate=own_rate)
+    out_rate = (own_rate or model_rate) if output_rate == "input" else int(output_rate or model_rate)
+    audio = stream_file(live, samples, tick_samples, transposition, seed=seed, sample_rate=own_rate,
+                        output_rate=out_rate if out_rate != model_rate else None)
     out_dir = os.path.dirname(os.path.abspath(output_file))
     os.makedirs(out_dir, exist_ok=True)
     ext = os.path.splitext(output_file)[1].lower().lstrip(".") or "wav"
     if ext == "wav":
         from scipy.io import wavfile
-        wavfile.write(output_file, model_rate, audio.astype(np.float32, copy=False))
+        wavfile.write(output_file, out_rate, audio.astype(np.float32, copy=False))
     else:
-        write_audio(output_file, audio, model_rate, ext)
+        write_audio(output_file, audio, out_rate, ext)
     if not quiet:
         print(f"{input_audio_file}: {samples.size} samples in pushes of {tick_samples} -> {audio.size} samples, transposed by "
-              f"{transposition}, look-ahead {live.lookahead_ms_for(own_rate):.1f} ms, saved under {output_file}", file=sys.stderr)
+              f"{transposition}, look-ahead {live.lookahead_ms_for(own_rate, out_rate):.1f} ms, saved at {out_rate} Hz under {output_file}",
+              file=sys.stderr)
+
+
+def output_rate_arg(text):
+    """argparse type of --output-rate: "input", or a positive whole number of Hz."""
+    from argparse import ArgumentTypeError
+    if text == "input":
+        return text
+    try:
+        rate = int(text)
+    except ValueError:
+        raise ArgumentTypeError(f"a sample rate in Hz or 'input' is expected, got {text!r}") from None
+    if rate <= 0:
+        raise ArgumentTypeError(f"a sample rate must be positive, got {rate}")
+    return rate
 
 
 if __name__ == "__main__":
@@ -104,6 +127,9 @@ if __name__ == "__main__":
     parser.add_argument("--resample", action="store_true",
                         help="stream a file at another rate at its own rate: the stream resamples on the device, the output "
                              "is at the model rate")
+    parser.add_argument("--output-rate", dest="output_rate", default=None, type=output_rate_arg, metavar="R|input",
+                        help="write the output at R Hz, resampled on the device by the stream; input = the file's own rate, "
+                             "which needs --resample when that is not the model's (Def: the model rate)")
     parser.add_argument("--seed", default=0, type=int, help="seed of the stream's noise generator (Def: %(default)s)")
     parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")
     args = parser.parse_args()

@@ -7,6 +7,7 @@
 #include "../../include/mbexwn_audio.h"
 #include "../../include/mbexwn_live.h"
 #include "../../include/mbexwn_live_resample.h"
+#include "../../include/mbexwn_live_out.h"
 #include "../../include/mbexwn_flac.h"
 
 static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
@@ -442,6 +443,30 @@ mbx_status mbxr_resample_rings(const float *in_rings, int32_t n_in_slots, int32_
     if (const char *why = mbx::check_resample_stream(a))
         return fail(MBX_ERR_INVALID_ARGUMENT, std::string("resample rings: ") + why);
     mbx::launch_resample_stream(a, static_cast<hipStream_t>(hip_stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxo_resample_emit(const float *in_rings, int32_t n_in_slots, int32_t in_ring_samples, const int64_t *desc,
+                              int32_t n_rows, int32_t max_new_out, int32_t up, int32_t down, const float *taps, int32_t n_taps,
+                              float *out, int64_t out_floats, void *hip_stream) {
+    mbx::ResampleEmitArgs a{};
+    a.in_rings = in_rings;
+    a.n_in_slots = n_in_slots;
+    a.in_ring_samples = in_ring_samples;
+    a.desc = reinterpret_cast<const long long *>(desc);
+    a.n_rows = n_rows;
+    a.max_new_out = max_new_out;
+    a.up = up;
+    a.down = down;
+    a.taps = taps;
+    a.n_taps = n_taps;
+    a.out = out;
+    a.out_floats = out_floats;
+    if (const char *why = mbx::check_resample_emit(a))
+        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("resample emit: ") + why);
+    mbx::launch_resample_emit(a, static_cast<hipStream_t>(hip_stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

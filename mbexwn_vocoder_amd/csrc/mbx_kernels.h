@@ -391,6 +391,22 @@ struct ResampleStreamArgs {
 const char *check_resample_stream(const ResampleStreamArgs &a);
 void launch_resample_stream(const ResampleStreamArgs &a, hipStream_t stream);
 
+// the same resampler on the way out (resample_stream.hip; include/mbexwn_live_out.h: mbxo_resample_emit): from a model-rate
+// ring store into packed rows at the output rate
+struct ResampleEmitArgs {
+    const float *in_rings;        // (n_in_slots, in_ring_samples)
+    int n_in_slots, in_ring_samples;
+    const long long *desc;        // (n_rows, 6): in_slot, first_out, n_out_new, n_total_in (< 0: still open), out_offset, 0
+    int n_rows, max_new_out;      // max_new_out sizes the grid only: a larger n_out_new is still produced whole
+    int up, down;
+    const float *taps;            // (n_taps), natural order, gain included
+    int n_taps;
+    float *out;                   // output first_out + i of a row at out[out_offset + i]
+    long long out_floats;         // a row that does not fit is skipped
+};
+const char *check_resample_emit(const ResampleEmitArgs &a);
+void launch_resample_emit(const ResampleEmitArgs &a, hipStream_t stream);
+
 // FLAC frames of 16-bit mono audio (flac_frames.hip): flac.py::encode's stream behind its 42-byte header
 constexpr int FLAC_BLOCK = 4096;                // samples per frame (the last one may be shorter)
 constexpr int FLAC_THREADS = 256;

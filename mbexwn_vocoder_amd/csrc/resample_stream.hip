@@ -1,5 +1,7 @@
 // Streaming polyphase FIR resampler (include/mbexwn_live_resample.h): the resampler of resample_poly.hip for sounds that are
-// still arriving, from a ring at the input rate straight into the model-rate ring the streaming analysis reads.
+// still arriving, from a ring at the input rate straight into the model-rate ring the streaming analysis reads -- and, on the
+// way out (include/mbexwn_live_out.h), from a ring of model-rate samples that are still being produced into packed rows at
+// the output rate, ready for one copy back.  Both are one body, resample_stream_row; only where an output is stored differs.
 //
 // Output k of a stream is resample_chain.h's chain, the one function the offline kernel calls too: only the fetch differs
 // (sample j of the stream at in_rings[in_slot][j & (in_ring_samples - 1)] instead of the item's row).  While a stream is
@@ -15,8 +17,9 @@
 // depends on k, the filter and the stream's length alone.  Plain vector code, 45 to 180 multiply-adds per output, no MFMA.
 //
 // A wrong descriptor row must not address outside the caller's buffers: a row that names a slot outside a store, a negative
-// first_out or one so large that k * down + half would leave 62 bits is skipped; n_out_new is clipped to the ring; every
-// ring access is masked; the chain's trip count is bounded by n_taps / up + 1.
+// first_out or one so large that k * down + half would leave 62 bits is skipped; n_out_new is clipped to the ring (into
+// rings) or the row is skipped when it does not fit `out` (packed rows); every ring access is masked; the chain's trip count
+// is bounded by n_taps / up + 1.
 #include <algorithm>
 
 #include "mbx_kernels.h"
@@ -29,32 +32,56 @@ constexpr int RSS_TILE = RSS_THREADS;             // outputs per block and pass
 constexpr int RSS_MAX_TILES = 4096;               // blocks per row; the kernel strides over what is left
 constexpr int RSS_LDS_BYTES = 64 * 1024;          // the default dynamic LDS limit: no function attribute needed
 
-template <bool T_LDS>
-__global__ __launch_bounds__(RSS_THREADS) void resample_stream_kernel(ResampleStreamArgs p) {
+// The rows of one block: stage the taps, then one chain per output of the block's tiles.  `store(k, value)` is where output k of
+// the stream goes -- the one thing the two kernels below differ in, as the fetches are the one thing resample_chain's callers
+// differ in.  Every return is uniform over the block and in front of the barrier.
+template <bool T_LDS, class Store>
+__device__ __forceinline__ void resample_stream_row(const float *in_rings, int n_in_slots, int in_ring_samples, int up, int down,
+                                                    const float *taps, int n_taps, long long in_slot, long long first_out,
+                                                    long long n_new, long long n_total, Store store) {
     extern __shared__ float rss_smem[];
-    const long long *d = p.desc + 6LL * blockIdx.y;
-    const long long in_slot = d[0], out_slot = d[1], first_out = d[2], n_total = d[4];
-    const long long n_new = min(d[3], (long long)p.out_ring_samples);     // one call never writes more than the ring holds
-    const int half = (p.n_taps - 1) / 2;
-    // uniform over the block: before any barrier
-    if (in_slot < 0 || in_slot >= p.n_in_slots || out_slot < 0 || out_slot >= p.n_out_slots || first_out < 0) return;
+    const int half = (n_taps - 1) / 2;
+    if (in_slot < 0 || in_slot >= n_in_slots || first_out < 0) return;
     if ((long long)blockIdx.x * RSS_TILE >= n_new) return;
-    if (first_out > (0x3FFFFFFFFFFFFFFFLL - half) / p.down - n_new) return;
+    if (first_out > (0x3FFFFFFFFFFFFFFFLL - half) / down - n_new) return;
     const int tid = threadIdx.x;
     if (T_LDS) {
-        for (int i = tid; i < p.n_taps; i += RSS_THREADS) rss_smem[i] = p.taps[i];
+        for (int i = tid; i < n_taps; i += RSS_THREADS) rss_smem[i] = taps[i];
         __syncthreads();
     }
-    const float *tsrc = T_LDS ? rss_smem : p.taps;
-    const float *ring = p.in_rings + in_slot * p.in_ring_samples;
-    float *out = p.out_rings + out_slot * p.out_ring_samples;
-    const long long in_mask = p.in_ring_samples - 1, out_mask = p.out_ring_samples - 1;
+    const float *tsrc = T_LDS ? rss_smem : taps;
+    const float *ring = in_rings + in_slot * in_ring_samples;
+    const long long in_mask = in_ring_samples - 1;
     const long long n = n_total < 0 ? RESAMPLE_OPEN : n_total;
     for (long long o = (long long)blockIdx.x * RSS_TILE + tid; o < n_new; o += (long long)gridDim.x * RSS_TILE) {
         const long long k = first_out + o;
-        out[k & out_mask] = resample_chain(k * p.down + half, n, p.up, p.n_taps, [=](int idx) { return tsrc[idx]; },
-                                           [=](long long j) { return ring[j & in_mask]; });
+        store(k, resample_chain(k * down + half, n, up, n_taps, [=](int idx) { return tsrc[idx]; },
+                                [=](long long j) { return ring[j & in_mask]; }));
     }
+}
+
+// into the model-rate ring store (mbxr_resample_rings): output k at out_rings[out_slot][k & (out_ring_samples - 1)]
+template <bool T_LDS>
+__global__ __launch_bounds__(RSS_THREADS) void resample_stream_kernel(ResampleStreamArgs p) {
+    const long long *d = p.desc + 6LL * blockIdx.y;
+    const long long in_slot = d[0], out_slot = d[1], first_out = d[2], n_total = d[4];
+    const long long n_new = min(d[3], (long long)p.out_ring_samples);     // one call never writes more than the ring holds
+    if (out_slot < 0 || out_slot >= p.n_out_slots) return;
+    float *out = p.out_rings + out_slot * p.out_ring_samples;
+    const long long out_mask = p.out_ring_samples - 1;
+    resample_stream_row<T_LDS>(p.in_rings, p.n_in_slots, p.in_ring_samples, p.up, p.down, p.taps, p.n_taps, in_slot, first_out,
+                               n_new, n_total, [=](long long k, float v) { out[k & out_mask] = v; });
+}
+
+// into packed rows (mbxo_resample_emit, include/mbexwn_live_out.h): output first_out + i at out[out_offset + i]
+template <bool T_LDS>
+__global__ __launch_bounds__(RSS_THREADS) void resample_emit_kernel(ResampleEmitArgs p) {
+    const long long *d = p.desc + 6LL * blockIdx.y;
+    const long long in_slot = d[0], first_out = d[1], n_new = d[2], n_total = d[3], out_offset = d[4];
+    if (out_offset < 0 || out_offset > p.out_floats || n_new > p.out_floats - out_offset) return;   // the row must fit `out`
+    float *out = p.out + out_offset;
+    resample_stream_row<T_LDS>(p.in_rings, p.n_in_slots, p.in_ring_samples, p.up, p.down, p.taps, p.n_taps, in_slot, first_out,
+                               n_new, n_total, [=](long long k, float v) { out[k - first_out] = v; });
 }
 
 static bool rss_power_of_two(int v) { return v > 0 && (v & (v - 1)) == 0; }
@@ -70,16 +97,39 @@ const char *check_resample_stream(const ResampleStreamArgs &a) {
     return nullptr;
 }
 
-void launch_resample_stream(const ResampleStreamArgs &a, hipStream_t stream) {
-    if (a.n_rows == 0 || a.max_new_out == 0) return;
-    const long long want = ((long long)std::min(a.max_new_out, a.out_ring_samples) + RSS_TILE - 1) / RSS_TILE;
+const char *check_resample_emit(const ResampleEmitArgs &a) {
+    if (!a.in_rings || !a.desc || !a.taps || !a.out) return "NULL pointer";
+    if (a.n_rows < 0 || a.n_rows > 65535) return "n_rows must lie in [0, 65535]";
+    if (a.max_new_out < 0) return "max_new_out must not be negative";
+    if (a.up < 1 || a.down < 1 || a.n_taps < 1) return "up, down and n_taps must be at least 1";
+    if (a.n_in_slots < 1) return "n_in_slots must be at least 1";
+    if (!rss_power_of_two(a.in_ring_samples)) return "in_ring_samples must be a power of two";
+    if (a.out_floats < 0) return "out_floats must not be negative";
+    return nullptr;
+}
+
+// one block per (row, tile of the longest row), at most RSS_MAX_TILES tiles; the taps in LDS when they fit
+template <class Args>
+static void rss_launch(void (*taps_in_lds)(Args), void (*taps_in_global)(Args), const Args &a, long long max_new,
+                       hipStream_t stream) {
+    const long long want = (max_new + RSS_TILE - 1) / RSS_TILE;
     const int tiles = (int)std::min<long long>(std::max<long long>(want, 1), RSS_MAX_TILES);
     const dim3 grid(tiles, a.n_rows), block(RSS_THREADS);
     const size_t tap_bytes = (size_t)a.n_taps * sizeof(float);
     if (tap_bytes <= (size_t)RSS_LDS_BYTES)
-        hipLaunchKernelGGL((resample_stream_kernel<true>), grid, block, tap_bytes, stream, a);
+        hipLaunchKernelGGL(taps_in_lds, grid, block, tap_bytes, stream, a);
     else
-        hipLaunchKernelGGL((resample_stream_kernel<false>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL(taps_in_global, grid, block, 0, stream, a);
+}
+
+void launch_resample_stream(const ResampleStreamArgs &a, hipStream_t stream) {
+    if (a.n_rows == 0 || a.max_new_out == 0) return;
+    rss_launch(resample_stream_kernel<true>, resample_stream_kernel<false>, a, std::min(a.max_new_out, a.out_ring_samples), stream);
+}
+
+void launch_resample_emit(const ResampleEmitArgs &a, hipStream_t stream) {
+    if (a.n_rows == 0 || a.max_new_out == 0) return;
+    rss_launch(resample_emit_kernel<true>, resample_emit_kernel<false>, a, a.max_new_out, stream);
 }
 
 }  // namespace mbx

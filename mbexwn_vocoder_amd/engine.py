@@ -221,6 +221,9 @@ def load_library():
     # include/mbexwn_live_resample.h (LIVE_RESAMPLE_SYMBOLS)
     lib.mbxr_resample_rings.restype = i32
     lib.mbxr_resample_rings.argtypes = [fp, i32, i32, vp, i32, i32, i32, i32, fp, i32, fp, i32, i32, vp]
+    # include/mbexwn_live_out.h (LIVE_OUT_SYMBOLS)
+    lib.mbxo_resample_emit.restype = i32
+    lib.mbxo_resample_emit.argtypes = [fp, i32, i32, vp, i32, i32, i32, i32, fp, i32, fp, ctypes.c_int64, vp]
     # include/mbexwn_flac.h (FLAC_SYMBOLS)
     lib.mbxf_encode_flac16_fixed.restype = i32
     lib.mbxf_encode_flac16_fixed.argtypes = [fp, ctypes.c_int64, i32, i64p, i32, vp, vp, ctypes.c_int64, vp, vp, vp, fp, vp]
@@ -245,6 +248,9 @@ LIVE_RESAMPLE_SYMBOLS = ["mbxr_resample_rings"]
 
 # include/mbexwn_flac.h: the compressing FLAC encoder (prefix mbxf_; the four lists above stay as they are)
 FLAC_SYMBOLS = ["mbxf_encode_flac16_fixed"]
+
+# include/mbexwn_live_out.h: the streaming output resampler (prefix mbxo_; the five lists above stay as they are)
+LIVE_OUT_SYMBOLS = ["mbxo_resample_emit"]
 
 
 def _check(status):

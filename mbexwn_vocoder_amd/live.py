@@ -12,6 +12,10 @@ A stream opened with ``sample_rate=R`` takes its pushes at R Hz: a streaming for
 reads, with the bits ``resample.resample_device`` gives on the whole sound, so the promise does not end at a resampler of
 the caller's.  Streams opened without a rate run exactly what they ran before.
 
+On the way out, a stream opened with ``output_rate=R`` gets its audio at R Hz: ``StreamingOutputResampler`` runs the same
+chain from a ring of the synthesizer's model-rate samples into packed rows (include/mbexwn_live_out.h), with the bits
+``resample.resample_device`` gives on the stream's whole synthesis.  Streams without an output rate get what they got.
+
 The readiness rules (``frames_ready``, ``outputs_ready``, ``input_keep_from``) and the mapping of per-push transposition
 factors to mel frames (``FrameFactors``) are pure host logic and run without a device.
 """
@@ -430,12 +434,257 @@ class StreamingAnalyzer:
         return result
 
 
+def output_filter(model_rate, output_rate):
+    """``(up, down, half, n_taps)`` of the reference's filter for model rate -> output rate (``resample.reference_filter``)."""
+    from .resample import _host_taps
+    taps, up, down = _host_taps(int(round(model_rate)), int(round(output_rate)))
+    return up, down, (taps.size - 1) // 2, int(taps.size)
+
+
+def resolve_output_rate(output_rate, sample_rate, model_rate):
+    """The rate an output stage works at for a stream opened with ``output_rate`` and ``sample_rate``, or None when the
+    stream needs none: ``"input"`` is the stream's own ``sample_rate`` (the model's for a stream without one), and the
+    model's rate needs no stage."""
+    if output_rate is None:
+        return None
+    if isinstance(output_rate, str):
+        if output_rate != "input":
+            raise ValueError(f"output_rate must be a rate in Hz or 'input', got {output_rate!r}")
+        if sample_rate is None:
+            return None
+        output_rate = sample_rate
+    from .resample import positive_rate
+    rate = positive_rate(output_rate, "output_rate")
+    return None if rate == int(round(model_rate)) else rate
+
+
+def output_lookahead_ms(model_rate, output_rate):
+    """What the output stage adds to a stream's look-ahead: half the output filter, half / up model-rate samples."""
+    up, _, half, _ = output_filter(model_rate, output_rate)
+    return 1000.0 * half / (up * int(round(model_rate)))
+
+
+class _OStream:
+    def __init__(self, slot, rate, filt):
+        self.slot, self.rate, self.filt = slot, rate, filt     # filt: (up, down, half, n_taps), model rate -> rate
+        self.have = 0             # model-rate samples pushed
+        self.on_device = 0        # ... of which the ring holds the newest
+        self.emitted = 0          # outputs handed out
+        self.closed = False
+        self.queue = []           # (source, offset, count) pushed since the last tick
+
+    def keep_from(self):
+        """First model-rate sample a pending output may still read (never behind what is to be appended)."""
+        return min(input_keep_from(self.emitted, *self.filt), self.on_device)
+
+    def total(self):
+        return outputs_ready(self.have, *self.filt[:3], closed=True)
+
+
+class OutputPlan:
+    """One tick of the output stage, planned on the host: ``rows`` -- (stream_id, first_out, n_out_new, n_total_in) per
+    stream with work, grouped by output rate -- and ``ring_needed``, the samples the longest-held stream's ring must hold."""
+
+    def __init__(self, rows, ring_needed):
+        self.rows, self.ring_needed = rows, ring_needed
+
+
+class StreamingOutputResampler:
+    """The way out of a live stream: model-rate audio that is still being produced, resampled on the device to each
+    stream's own output rate, a tick at a time (csrc/resample_stream.hip through include/mbexwn_live_out.h).
+
+    The concatenated arrays ``tick`` hands out for a stream opened at rate R are ``resample.resample_device(the stream's
+    whole model-rate sound, None, model_rate, R)`` bit for bit, ceil(n * up / down) samples, however the sound was cut into
+    pushes.  The rules are those of the resampled input streams read in the other direction: with ``have`` model-rate
+    samples appended, ``outputs_ready(have, up, down, half, closed)`` outputs are final; the ring (a third ``_RingStore``,
+    at the model rate) holds every sample from ``input_keep_from(next output, ...)`` on and grows by doubling before it
+    would not; after ``push(..., last=True)`` the remaining outputs follow with the filter's tail clipped at the end.
+
+    A push names where the samples ARE on the device -- ``source``, a contiguous float32 tensor, ``count`` samples from flat
+    element ``offset`` -- and the tick's ``mbxl_ring_append`` reads them from there: the audio never visits the host on its
+    way in.  A steady tick is one small pinned upload (the descriptor tables), one append per distinct source tensor, one
+    ``mbxo_resample_emit`` per distinct output rate into one packed buffer, and one copy back; it allocates no device
+    memory (``device_allocations`` counts every (re)allocation)."""
+
+    def __init__(self, model_rate, device=None, ring_samples=None, slots=16):
+        from .resample import positive_rate
+        self.model_rate = positive_rate(model_rate, "model_rate")
+        self.device = device
+        self.streams = {}
+        # 4096: a synthesis tick of the 80 ms schedule hands over up to 7 frames = 2100 samples at once, behind the 44 to 130
+        # samples (48 kHz to 8 kHz) a pending output still reads
+        self._store = _RingStore(int(ring_samples or 4096), slots)
+        self._taps = {}               # output rate -> (taps on the device, up, down)
+        self._desc_host = self._desc_dev = None       # one tick's descriptor tables (int64): pinned, and its device twin
+        self._out_dev = self._out_host = None         # one tick's outputs, packed
+        self.ticks = 0
+        self.device_allocations = 0   # how often a device store was (re)allocated: constant over steady ticks
+        self.time_device = False      # probe: bracket the launches of a tick with events
+        self.last_tick_device_ms = None
+
+    ring_samples = property(lambda self: self._store.ring_samples)
+    rings = property(lambda self: self._store.rings)     # None until the first tick with work: nothing is allocated before
+
+    # -- host side ----------------------------------------------------------------------------------------------------
+    def open(self, stream_id, output_rate):
+        if stream_id in self.streams:
+            raise ValueError(f"stream {stream_id!r} is open already")
+        from .resample import positive_rate
+        rate = positive_rate(output_rate, f"stream {stream_id!r}: output_rate")
+        filt = output_filter(self.model_rate, rate)
+        self.streams[stream_id] = _OStream(self._store.take(), rate, filt)
+
+    def close(self, stream_id):
+        """Forget a stream (its slot is reused)."""
+        self._store.release(self.streams.pop(stream_id).slot)
+
+    def push(self, stream_id, source, offset, count, last=False):
+        """The stream's next ``count`` model-rate samples are the flat elements [offset, offset + count) of ``source``, a
+        contiguous float32 tensor on the stage's device that stays valid until the next ``tick``; ``last`` closes the
+        stream.  ``count`` 0 needs no source."""
+        st = self.streams[stream_id]
+        if st.closed:
+            raise ValueError(f"stream {stream_id!r} is closed")
+        offset, count = int(offset), int(count)
+        if count < 0 or offset < 0:
+            raise ValueError("offset and count must not be negative")
+        if count:
+            import torch
+            if not isinstance(source, torch.Tensor) or source.dtype != torch.float32 or not source.is_contiguous():
+                raise ValueError("source must be a contiguous float32 tensor")
+            if offset + count > source.numel():
+                raise ValueError(f"samples [{offset}, {offset + count}) lie outside a source of {source.numel()} elements")
+            st.queue.append((source, offset, count))
+            st.have += count
+        st.closed = bool(last)
+
+    def finished(self, stream_id):
+        st = self.streams[stream_id]
+        return st.closed and st.emitted >= st.total()
+
+    def plan(self):
+        """What the next tick does, from the host state alone (no device): the streams with samples to append or outputs
+        that became final, grouped by output rate."""
+        rows, ring_needed = [], 0
+        for sid, st in sorted(self.streams.items(), key=lambda kv: kv[1].rate):
+            n_new = outputs_ready(st.have, *st.filt[:3], closed=st.closed) - st.emitted
+            if n_new > 0 or st.queue:
+                rows.append((sid, st.emitted, n_new, st.have if st.closed else -1))
+                ring_needed = max(ring_needed, st.have - st.keep_from())
+        return OutputPlan(rows, ring_needed)
+
+    def commit(self, plan):
+        """Move the streams on to behind the planned tick."""
+        for sid, _, n_new, _ in plan.rows:
+            st = self.streams[sid]
+            st.on_device, st.queue = st.have, []
+            st.emitted += n_new
+
+    # -- device side --------------------------------------------------------------------------------------------------
+    def _device_taps(self, rate):
+        if rate not in self._taps:
+            from .resample import device_taps
+            self._taps[rate] = device_taps(self.model_rate, rate, self.device)
+            self.device_allocations += 1
+        return self._taps[rate]
+
+    def _grown_pair(self, host, dev_buf, size, dtype):
+        """A pinned host buffer and its device twin of at least `size` elements (doubling)."""
+        import torch
+        if host is not None and host.numel() >= size:
+            return host, dev_buf
+        size = _pow2_at_least(max(size, 1024))
+        self.device_allocations += 1
+        return torch.zeros(size, dtype=dtype).pin_memory(), torch.zeros(size, dtype=dtype, device=self.device)
+
+    def tick(self):
+        """Append what was pushed to the rings and resample every output that became final.
+        Returns {stream_id: float32 ndarray at the stream's output rate} for the streams with new output."""
+        plan = self.plan()
+        if not plan.rows:
+            return {}
+        import torch
+        from .engine import _check, load_library
+        if self.device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("StreamingOutputResampler: no GPU available (there is no host path)")
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        lib, dev = load_library(), torch.device(self.device)
+        self.device = dev
+        held = ((st.slot, st.on_device) for st in self.streams.values() if st.on_device)
+        self.device_allocations += self._store.ensure(dev, plan.ring_needed, held)
+        rings, ring = self._store.rings, self._store.ring_samples
+        # the append rows: one call per distinct source tensor (and per place in its stream's queue: two rows of one call
+        # never name the same slot)
+        calls, total = {}, 0
+        for sid, _, _, _ in plan.rows:
+            st, at = self.streams[sid], self.streams[sid].on_device
+            for turn, (source, offset, count) in enumerate(st.queue):
+                if source.device != dev:
+                    raise ValueError(f"stream {sid!r}: source is on {source.device}, the stage on {dev}")
+                calls.setdefault((turn, source.data_ptr(), source.numel()), []).append((st.slot, at, count, offset))
+                at += count
+        n_app, S = sum(len(rr) for rr in calls.values()), len(plan.rows)
+        self._desc_host, self._desc_dev = self._grown_pair(self._desc_host, self._desc_dev, 4 * n_app + 6 * S, torch.int64)
+        table = self._desc_host.numpy()
+        app, emit = table[:4 * n_app].reshape(n_app, 4), table[4 * n_app:4 * n_app + 6 * S].reshape(S, 6)
+        first = 0
+        for rows in calls.values():
+            app[first:first + len(rows)] = rows
+            first += len(rows)
+        for row, (sid, first_out, n_new, n_total) in enumerate(plan.rows):
+            emit[row] = (self.streams[sid].slot, first_out, n_new, n_total, total, 0)
+            total += max(n_new, 0)
+        self._out_host, self._out_dev = self._grown_pair(self._out_host, self._out_dev, total, torch.float32)
+        for sid, _, _, _ in plan.rows:
+            self._device_taps(self.streams[sid].rate)
+        used = 4 * n_app + 6 * S
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            self._desc_dev[:used].copy_(self._desc_host[:used], non_blocking=True)
+            base = self._desc_dev.data_ptr()
+            if self.time_device:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            first = 0
+            for (_, ptr, numel), rows in calls.items():
+                _check(lib.mbxl_ring_append(ptr, numel, base + 32 * first, len(rows), max(rr[2] for rr in rows),
+                                            rings.data_ptr(), int(rings.shape[0]), ring, stream.cuda_stream))
+                first += len(rows)
+            first = 0
+            while first < S:                                  # one launch per distinct output rate
+                rate = self.streams[plan.rows[first][0]].rate
+                end = first
+                while end < S and self.streams[plan.rows[end][0]].rate == rate:
+                    end += 1
+                taps, up, down = self._taps[rate]
+                _check(lib.mbxo_resample_emit(rings.data_ptr(), int(rings.shape[0]), ring, base + 32 * n_app + 48 * first,
+                                              end - first, int(max(emit[first:end, 2].max(), 0)), up, down, taps.data_ptr(),
+                                              int(taps.numel()), self._out_dev.data_ptr(), int(self._out_dev.numel()),
+                                              stream.cuda_stream))
+                first = end
+            if self.time_device:
+                ev1.record()
+            if total:
+                self._out_host[:total].copy_(self._out_dev[:total], non_blocking=True)
+            stream.synchronize()
+            if self.time_device:
+                self.last_tick_device_ms = ev0.elapsed_time(ev1)
+        packed = self._out_host.numpy()
+        result = {sid: packed[int(emit[row, 4]):int(emit[row, 4]) + n_new].copy()
+                  for row, (sid, _, n_new, _) in enumerate(plan.rows) if n_new > 0}
+        self.commit(plan)
+        self.ticks += 1
+        return result
+
+
 class _LStream:
     def __init__(self, hop, rng, noise_fn, up=1, down=1):
         self.factors = FrameFactors(hop, up, down)
         self.frames = 0               # mel frames handed to the synthesizer
         self.rng, self.noise_fn = rng, noise_fn
         self.flushed = False          # the synthesizer has been told that the stream is over
+        self.out_rate = None          # the stream's output rate when it is not the model's: it goes through the output stage
 
 
 class LiveResynthesizer:
@@ -467,6 +716,9 @@ class LiveResynthesizer:
         self.dims = engine.dims
         self._header = mell_header(mel_inverter.preprocess_config)
         self.streams = {}
+        # streams with an output rate of their own leave through this stage; its store is allocated by its first tick
+        self.output = StreamingOutputResampler(self.analyzer.sample_rate, device=engine.device)
+        self._out_streams = 0
 
     @property
     def lookahead_ms(self):
@@ -475,27 +727,42 @@ class LiveResynthesizer:
         frames = -(-(an.win - an.win // 2) // an.hop)
         return 1000.0 * frames * an.hop / an.sample_rate + self.synthesizer.lookahead_ms
 
-    def lookahead_ms_for(self, sample_rate=None):
-        """``lookahead_ms`` of a stream opened at ``sample_rate``: a resampled stream waits for half its filter as well,
-        half / up input samples (0.92 ms at 44.1 and 48 kHz, 1.4 ms at 16 kHz for a 24 kHz model)."""
+    def lookahead_ms_for(self, sample_rate=None, output_rate=None):
+        """``lookahead_ms`` of a stream opened at ``sample_rate`` and ``output_rate``: a resampled stream waits for half
+        its filter as well, half / up input samples (0.92 ms at 44.1 and 48 kHz, 1.4 ms at 16 kHz for a 24 kHz model); a
+        stream with an output rate waits for half the output filter, half / up model-rate samples (0.92 ms to 48 kHz,
+        0.94 ms to 44.1 kHz, 1.4 ms to 16 kHz)."""
         model = int(round(self.analyzer.sample_rate))
-        if sample_rate is None or int(round(sample_rate)) == model:
-            return self.lookahead_ms
-        from .resample import _host_taps
-        taps, up, _ = _host_taps(int(round(sample_rate)), model)
-        return self.lookahead_ms + 1000.0 * ((taps.size - 1) // 2) / up / int(round(sample_rate))
+        ms = self.lookahead_ms
+        if sample_rate is not None and int(round(sample_rate)) != model:
+            from .resample import _host_taps
+            taps, up, _ = _host_taps(int(round(sample_rate)), model)
+            ms += 1000.0 * ((taps.size - 1) // 2) / up / int(round(sample_rate))
+        out_rate = resolve_output_rate(output_rate, sample_rate, model)
+        if out_rate is not None:
+            ms += output_lookahead_ms(model, out_rate)
+        return ms
 
-    def open(self, stream_id, seed=None, noise_fn=None, sample_rate=None):
+    def open(self, stream_id, seed=None, noise_fn=None, sample_rate=None, output_rate=None):
+        """``output_rate``: the rate the stream's audio comes back at -- a rate in Hz, or ``"input"`` for the stream's own
+        ``sample_rate``; None or the model's rate: the model-rate audio, as the synthesizer emits it."""
+        out_rate = resolve_output_rate(output_rate, sample_rate, self.analyzer.sample_rate)
         self.analyzer.open(stream_id, sample_rate=sample_rate)
         self.synthesizer.open(stream_id)
         up, down = (self.analyzer.streams[stream_id].filt or (1, 1))[:2]
-        self.streams[stream_id] = _LStream(self.analyzer.hop, None if noise_fn else np.random.default_rng(seed), noise_fn,
-                                           up, down)
+        st = self.streams[stream_id] = _LStream(self.analyzer.hop, None if noise_fn else np.random.default_rng(seed),
+                                                noise_fn, up, down)
+        if out_rate is not None:
+            self.output.open(stream_id, out_rate)
+            st.out_rate = out_rate
+            self._out_streams += 1
 
     def close(self, stream_id):
         self.analyzer.close(stream_id)
         self.synthesizer.close(stream_id)
-        del self.streams[stream_id]
+        if self.streams.pop(stream_id).out_rate is not None:
+            self.output.close(stream_id)
+            self._out_streams -= 1
 
     def push_audio(self, stream_id, samples, last=False, transposition=None, sample_rate=None):
         """Append samples at the stream's rate (the model's, unless it was opened at another); ``transposition``: one finite
@@ -537,7 +804,25 @@ class LiveResynthesizer:
             noise = self._noise(sid, st, first, end) if self.dims.noise_sigma else None
             self.synthesizer.push(sid, scaled, noise, last=done, transposition=st.factors.take(first, end))
             st.frames, st.flushed = end, done
-        return self.synthesizer.tick()
+        audio = self.synthesizer.tick()
+        if not self._out_streams:
+            return audio
+        # the streams with an output rate: their chunks go on, from where the synthesizer left them on the device, to the
+        # output stage, and what that stage has final comes back in their place
+        source, spans = self.synthesizer.last_emit_device or (None, {})
+        for sid, st in self.streams.items():
+            if st.out_rate is None or self.output.streams[sid].closed:
+                continue
+            offset, count = spans.get(sid, (0, 0))
+            last = st.flushed and self.synthesizer.finished(sid)
+            if count or last:
+                self.output.push(sid, source, offset, count, last=last)
+            audio.pop(sid, None)
+        audio.update(self.output.tick())
+        return audio
 
     def finished(self, stream_id):
-        return self.streams[stream_id].flushed and self.synthesizer.finished(stream_id)
+        st = self.streams[stream_id]
+        if st.out_rate is not None:
+            return self.output.finished(stream_id)
+        return st.flushed and self.synthesizer.finished(stream_id)

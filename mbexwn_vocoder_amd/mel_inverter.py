@@ -132,7 +132,20 @@ class MELInverter(object):
         return mell * self.mel_amp_scale
 
     # ------------------------------------------------------------------------------------------
-    def synth_from_mel(self, scaled_mell, noise=None, f0=None, transposition=None):
+    def _output_rate(self, out_rate):
+        """``out_rate`` as an int, or None when it is the model's rate (or None): today's path, launch for launch."""
+        if out_rate is None:
+            return None
+        from .resample import positive_rate
+        rate = positive_rate(out_rate, "out_rate")
+        return None if rate == int(round(self.srate)) else rate
+
+    def _to_rate(self, audio, out_rate):
+        """Device audio (B, N) at the model rate -> (B, ceil(N * up / down)) at ``out_rate`` (resample.resample_device)."""
+        from .resample import resample_device
+        return resample_device(audio.contiguous(), None, int(round(self.srate)), out_rate)[0]
+
+    def synth_from_mel(self, scaled_mell, noise=None, f0=None, transposition=None, out_rate=None):
         """(1, T, mel_channels) log-mel -> float32 audio of T*hop_size samples
         (reference mel_inverter.py:151-154; like there, a batch is flattened by ``ravel``).
 
@@ -142,15 +155,22 @@ class MELInverter(object):
         Pitch control (this build): ``f0`` -- (T,) or (B, T) Hz, one value per mel frame, replaces the F0-net's contour;
         ``transposition`` -- a factor on the contour, a scalar (the ``transposition_factor`` of ``infer_components``, same
         bits) or one value per mel frame.  Per-frame values are brought to the pulse rate by the model's linear
-        interpolator (``mbx_forward_options.f0_frames / f0_scale``); they must be finite and positive."""
+        interpolator (``mbx_forward_options.f0_frames / f0_scale``); they must be finite and positive.
+
+        ``out_rate`` (this build): the audio comes back at that rate, ceil(T * hop_size * up / down) samples --
+        ``resample.resample_device`` (the reference's resampler, model rate -> ``out_rate``) on the device audio before it
+        is copied back.  None or the model's rate: the audio as the model makes it."""
+        out_rate = self._output_rate(out_rate)
         self._calibrate_if_pending(scaled_mell)
         if f0 is not None or transposition is not None:
-            return self._synth_with_pitch(scaled_mell, noise, f0, transposition)
+            return self._synth_with_pitch(scaled_mell, noise, f0, transposition, out_rate)
         syn_audio = self.model.infer(scaled_mell, sigma=None, synth_length=scaled_mell.shape[1] * self.hop_size,
-                                     noise=noise).numpy()
-        return syn_audio.ravel()
+                                     noise=noise)
+        if out_rate is not None:
+            return self._to_rate(syn_audio.tensor, out_rate).cpu().numpy().ravel()
+        return syn_audio.numpy().ravel()
 
-    def _synth_with_pitch(self, scaled_mell, noise, f0, transposition):
+    def _synth_with_pitch(self, scaled_mell, noise, f0, transposition, out_rate=None):
         import torch
         model = self.model
         n_frames = int(scaled_mell.shape[1])
@@ -179,6 +199,8 @@ class MELInverter(object):
         else:
             audio = model.forward(mel, noise=noise, f0_frames=f0_rows,
                                   f0_scale=torch.full((B, T), float(scale), dtype=torch.float32, device=model.device))
+        if out_rate is not None:
+            return self._to_rate(audio[:, :n_frames * self.hop_size], out_rate).cpu().numpy().ravel()
         return audio[:, :n_frames * self.hop_size].cpu().numpy().ravel()
 
     def _calibrate_if_pending(self, scaled_mell):
@@ -196,16 +218,23 @@ class MELInverter(object):
                               f"chosen at creation ({self.model.conv_form_info()['form']})", RuntimeWarning)
 
     def synth_from_mels(self, scaled_mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False,
-                        flac_compression="verbatim"):
+                        flac_compression="verbatim", out_rate=None):
         """Batched :meth:`synth_from_mel` (this build): a list of ``scale_mel`` outputs (1, T_i, mel_channels) -> a list of
         float32 audio (T_i * hop_size,), or with ``flac=True`` of complete FLAC files (bytes; frames encoded on the device).
 
         The mels run in padded micro-batches (sharding.plan_batches, at most ``max_batch`` items and ``max_padded_frames``
         padded frames each) through the engine's forward with per-item lengths.  ``noises``: per-item N(0,1) draws
         (T_i * wn_in_rows_per_frame,), default: the draws :meth:`synth_from_mel` would make called on the list one by one
-        (batched.replay_noise) -- with a ``batch_invariant`` engine the results are then bit-identical to those calls."""
+        (batched.replay_noise) -- with a ``batch_invariant`` engine the results are then bit-identical to those calls.
+
+        ``out_rate``: every item comes back at that rate (audio, or FLAC files whose header, frames and MD5 are at that
+        rate and length): the micro-batch is resampled on the device (``resample.resample_device`` with the items' own
+        lengths, so each tail is clipped at its item's end), and item b equals ``resample_device`` of its own model-rate
+        audio alone.  None or the model's rate: today's path."""
         import torch
         from .batched import replay_noise, run_micro_batches
+        out_rate = self._output_rate(out_rate)
+        rate = self.srate if out_rate is None else out_rate
         if len(scaled_mels):
             self._calibrate_if_pending(scaled_mels[0])
         mels =[np.asarray(mm, dtype=np.float32).reshape(-1, mm.shape[-2], mm.shape[-1])[0] for mm in scaled_mels]
@@ -219,7 +248,7 @@ class MELInverter(object):
                       .reshape(-1) for zz in noises]
         out = [None] * len(mels)
         for batch in run_micro_batches(self.model, mels, noises, max_batch, max_padded_frames, flac=flac, host_audio=not flac,
-                                       flac_compression=flac_compression):
+                                       flac_compression=flac_compression, out_rate=out_rate):
             batch.wait()
             for jj, ii in enumerate(batch.indices):
                 if not flac:
@@ -228,7 +257,7 @@ class MELInverter(object):
                     out[ii] = batch.flac.stream(jj)
                 else:
                     from . import flac as flac_writer
-                    out[ii] = flac_writer.encode(batch.audio(jj), self.srate, flac_compression)
+                    out[ii] = flac_writer.encode(batch.audio(jj), rate, flac_compression)
         return out
 
     def calibrate(self, scaled_mells, verbose=False, max_frames=400, seed=42):

@@ -25,6 +25,13 @@ import numpy as np
 DEVICE_TILE = 1024          # outputs per block of the device kernel (MBXA_RESAMPLE_TILE of include/mbexwn_audio.h)
 
 
+def positive_rate(rate, what="rate"):
+    """A sample rate a caller handed in, as an int of Hz; anything that is not a finite positive number is refused."""
+    if rate is None or isinstance(rate, (str, bytes)) or not np.isfinite(rate) or int(round(rate)) <= 0:
+        raise ValueError(f"{what} must be a positive rate in Hz, got {rate!r}")
+    return int(round(rate))
+
+
 def reference_filter(in_sr, out_sr, stop_att=70, trans_width_normed=0.1, dtype=np.float32):
     """The reference's anti-aliasing FIR for in_sr -> out_sr: ``(taps, up, down)`` with integer up / down.
 

@@ -434,6 +434,7 @@ class StreamingSynthesizer:
         self._steady = None               # the steady run in progress (_SteadyRun)
         self.graph_ticks = 0              # ticks served by a graph replay
         self.last_tick_replayed = False
+        self._last_emit = None            # what last_emit_device is made from, on demand: a tick pays nothing for it
         self.time_device = False          # bench: bracket the engine call of a tick with events on its stream
         self.last_tick_device_ms = None
         self.last_tick_frames = 0         # window frames of the last tick (all streams): mel-rate stages
@@ -444,6 +445,20 @@ class StreamingSynthesizer:
     @property
     def lookahead_ms(self):
         return 1000.0 * self.right * self.dims.hop_size / self.dims.sample_rate
+
+    @property
+    def last_emit_device(self):
+        """Where the last tick left its audio on the device: ``(tensor, {stream_id: (flat offset, count)})`` -- stream_id's
+        chunk is the ``count`` elements from flat element ``offset`` of the contiguous float32 ``tensor`` (the forward's
+        output of a launch-by-launch tick, the shared buffer of a replayed graph), valid until the next tick.  None after
+        a tick that emitted nothing."""
+        if self._last_emit is None:
+            return None
+        tensor, sids, spans = self._last_emit
+        if isinstance(spans, tuple):                      # a replayed tick: every stream's chunk at the same place of its row
+            row, at, count = spans
+            spans = [(bb * row + at, count) for bb in range(len(sids))]
+        return tensor, dict(zip(sids, spans))
 
     # the shared input rows under the names they had before _InputRows owned them (read by the host tests)
     _in_cap = property(lambda self: self._rows.cap)
@@ -560,6 +575,7 @@ class StreamingSynthesizer:
         """One batched engine call over every stream that can emit. Returns {stream_id: audio ndarray}."""
         import torch
         self.last_tick_replayed = False
+        self._last_emit = None
         if self._steady is not None:
             status = self._steady_status()
             if status == "replay" and self.use_graph:
@@ -603,6 +619,9 @@ class StreamingSynthesizer:
         hop = self.dims.hop_size
         lo = min(rel * hop for rel in plan.rel)
         hi = max((rel + nn) * hop for rel, nn in zip(plan.rel, plan.emit))
+        # where this tick left its chunks on the device, for a stage behind the synthesizer (live.StreamingOutputResampler)
+        self._last_emit = (audio, [sid for sid, _, _ in todo],
+                           [(item * audio.stride(0) + plan.rel[item] * hop, nn * hop) for item, (_, _, nn) in enumerate(todo)])
         audio, state_out = audio[:, lo:hi].cpu().numpy(), state_out.cpu().numpy()
         result = self._commit(plan, todo, audio, lo, state_out)
         self._record_steady(plan, todo, up, lo, hi, state_out)
@@ -882,6 +901,7 @@ class StreamingSynthesizer:
         run.state_v = cap.state_host.numpy().copy()
         at = rec.rel0 * hop - rec.lo
         result = dict(zip(run.sids, audio[:, at:at + chunk * hop]))
+        self._last_emit = (run.audio_buf, run.sids, (run.audio_buf.stride(0), rec.rel0 * hop, chunk * hop))
         emitted += chunk
         run.pending += 1
         run.pending_frames += chunk

@@ -13,6 +13,10 @@ With ``--input-rate R`` a third leg follows in the same process: the live leg ag
 audio at R per push), so that the device time of the analysis launches -- now mbxl_ring_append into the input store,
 mbxr_resample_rings, mbxl_mel_frames -- and the host-inclusive live tick stand next to the figures without resampling.
 
+With ``--output-rate R`` a further leg follows: the live leg with every stream opened with ``output_rate=R`` (at the input rate
+of ``--input-rate``, when given), so that the device time of the output stage's launches -- mbxl_ring_append from the
+synthesizer's buffer, mbxo_resample_emit -- and the host-inclusive live tick stand next to the tick without an output rate.
+
 Prints one JSON line.  ``--synthesis-only`` runs the first leg alone; with ``--root DIR`` the package is imported from another
 checkout (the parent commit, for the comparison of the synthesis tick), which needs nothing of the live path.
 """
@@ -81,24 +85,26 @@ def synthesis_leg(torch, inv, streams, warm_seconds, ticks):
             "graph_ticks": int(syn.graph_ticks)}
 
 
-def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None):
+def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None, output_rate=None):
     from mbexwn_vocoder_amd.live import LiveResynthesizer
     live = LiveResynthesizer(inv, chunk_frames=SCHEDULE)
     live.analyzer.time_device = True
     live.synthesizer.time_device = True
+    if output_rate:
+        live.output.time_device = True
     rate = int(input_rate or inv.srate)
     per_tick = int(round(0.080 * rate))
     rng = np.random.default_rng(99)
     tt = np.arange(50 * per_tick) / rate
     sounds = [(0.3 * np.sin(2 * np.pi * (90.0 + 3 * sid) * tt) + 0.05 * rng.normal(size=tt.size)).astype(np.float32)
               for sid in range(streams)]
+    rates = {"sample_rate": input_rate} if input_rate else {}
+    if output_rate:
+        rates["output_rate"] = output_rate
     for sid in range(streams):
-        if input_rate:
-            live.open(sid, seed=sid, sample_rate=input_rate)
-        else:
-            live.open(sid, seed=sid)
-    allocations = None
-    tick_ms, push_ms, analysis_ms, syn_dev_ms, replayed, pos, warm_ticks = [], [], [], [], 0, 0, 0
+        live.open(sid, seed=sid, **rates)
+    allocations = out_allocations = None
+    tick_ms, push_ms, analysis_ms, syn_dev_ms, output_ms, replayed, pos, warm_ticks = [], [], [], [], [], 0, 0, 0
     t_start = time.perf_counter()
     while len(tick_ms) < ticks:
         t0 = time.perf_counter()
@@ -114,6 +120,9 @@ def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None):
         if steady and t2 - t_start >= warm_seconds:
             if allocations is None:
                 allocations = live.analyzer.device_allocations
+                out_allocations = live.output.device_allocations if output_rate else 0
+            if output_rate:
+                output_ms.append(live.output.last_tick_device_ms)
             tick_ms.append((t2 - t1) * 1e3)
             push_ms.append((t1 - t0) * 1e3)
             analysis_ms.append(live.analyzer.last_tick_device_ms)
@@ -128,7 +137,12 @@ def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None):
             "lookahead_ms": live.lookahead_ms_for(input_rate) if input_rate else live.lookahead_ms,
             "analyzer_device_allocations_during_timed_ticks": live.analyzer.device_allocations - allocations,
             "ring_samples": live.analyzer.ring_samples,
-            **({"input_rate": input_rate, "input_ring_samples": live.analyzer.input_ring_samples} if input_rate else {})}
+            **({"input_rate": input_rate, "input_ring_samples": live.analyzer.input_ring_samples} if input_rate else {}),
+            **({"output_rate": output_rate, "output_stage_launches_ms_device": percentiles(output_ms),
+                "output_lookahead_ms": live.lookahead_ms_for(input_rate or None, output_rate) - live.lookahead_ms_for(input_rate or None),
+                "output_device_allocations_during_timed_ticks": live.output.device_allocations - out_allocations,
+                "output_ring_samples": live.output.ring_samples, "samples_per_stream_and_tick": int(next(iter(res.values())).size)}
+               if output_rate else {})}
 
 
 def main():
@@ -139,6 +153,9 @@ def main():
     ap.add_argument("--synthesis-only", action="store_true")
     ap.add_argument("--input-rate", type=int, default=0, metavar="R",
                     help="also run the live leg with every stream opened at R Hz (resampled on the device)")
+    ap.add_argument("--output-rate", type=int, default=0, metavar="R",
+                    help="also run the live leg with every stream opened with output_rate=R (resampled on the device on the way "
+                         "out)")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="checkout to import mbexwn_vocoder_amd from (default: this one)")
     ap.add_argument("--label", default="")
@@ -157,6 +174,9 @@ def main():
         out["live"] = live_leg(torch, inv, args.streams, args.warm_seconds, args.ticks)
         if args.input_rate and args.input_rate != int(inv.srate):
             out["live_resampled"] = live_leg(torch, inv, args.streams, args.warm_seconds, args.ticks, args.input_rate)
+        if args.output_rate and args.output_rate != int(inv.srate):
+            out["live_output"] = live_leg(torch, inv, args.streams, args.warm_seconds, args.ticks, args.input_rate or None,
+                                          args.output_rate)
     print(json.dumps(out))
 
 

@@ -37,7 +37,7 @@ __device__ __forceinline__ float wn_gate_act(int kind, float zt, float zs) {
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// conv1d as an implicit GEMM on the fp32 matrix cores (conv_mfma.hip)
+// conv1d as an implicit GEMM on the fp32 matrix cores (conv_mfma.hip; the mel-rate sub-nets: conv_mel.hip)
 // ---------------------------------------------------------------------------------------------
 enum ConvEpilogue {
     EPI_LINEAR = 0,   // y = acc + bias, optional PReLU / leaky slope
@@ -101,7 +101,7 @@ struct ConvArgs {
     int h_planes_only;        // wn_resskip_f16_kernel: the planes ARE the hidden state -- old values are read from them (hi + 2^-11 lo'),
                               // the float32 tensor h is neither read nor written (every consumer of h takes the planes)
     int tune_split;           // wave-tiled res/skip kernel: 1..3 pins its column split (mbx_config.tune_resskip_split; same bits), 0: by launch size
-    // EPI_LINEAR, the F0-net (conv1d_f64_tile): contraction on v_mfma_f64_16x16x4_f64
+    // EPI_LINEAR, the F0-net (conv_mel.hip: conv1d_f64_tile / conv1d_f64_tile32): contraction on v_mfma_f64_16x16x4_f64
     int precise;              // 1: float64 accumulation; with only this set x, w and out are the float32 ones above (one rounding per output)
     const double *x64;        // input as float64 (same strides, counted in elements) instead of x; needs w64
     const double *w64;        // weights (ks*cin, cout) as float64 instead of w
@@ -109,8 +109,11 @@ struct ConvArgs {
 };
 
 void launch_conv1d(const ConvArgs &a, int epilogue, hipStream_t stream);
-// n <= 3 independent EPI_LINEAR convolutions; the small (mel-rate, small batch) ones share one launch
+// n <= 3 independent EPI_LINEAR convolutions; the mel-rate ones share one launch (conv_mel.hip)
 void launch_conv1d_group(const ConvArgs *convs, int n, hipStream_t stream);
+// one EPI_LINEAR convolution in a launch of its own with the mel-rate tiles (conv_mel.hip); false: the shape is not theirs,
+// nothing was launched
+bool launch_conv1d_mel_single(const ConvArgs &a, hipStream_t stream);
 // Winograd F(4,3) form on v_mfma_f32_16x16x4_f32, wave tile 16 groups x 64 columns (wn_winograd4w.hip); a.w = image of
 // engine.pack_winograd4w_weights (ceil(C/32), ceil(C/8), 3072); split: 128-row blocks whose waves split the six products
 // (same bits as the 256-row blocks)

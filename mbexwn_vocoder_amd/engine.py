@@ -719,7 +719,7 @@ def tensor_table(config, raw_weights, wavetables, split_f16=False):
     out = dict(merge_channel_groups(fold_weights(raw_weights, wavenet_weight_norm=wn_norm,
                                                  wavenet_equalized_lr=dims.wn_equalized_lr), dims))
     # F0-net: the exact (float64) weight-norm fold of every layer, handed over as pairs of float32 words
-    # (mbx_config.f0_accumulate = MBX_F0_ACC_F64: csrc/conv_mfma.hip::conv1d_f64_tile reads them as doubles)
+    # (mbx_config.f0_accumulate = MBX_F0_ACC_F64: csrc/conv_mel.hip::conv1d_f64_tile reads them as doubles)
     from .weights import fold_weight_norm_f64
     for key in raw_weights:
         if key.startswith("PulsPar_Layer_") and key.endswith(".v") and key[:-2] + ".g" in raw_weights:

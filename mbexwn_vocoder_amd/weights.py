@@ -119,7 +119,7 @@ def fold_weight_norm(v, g):
 def fold_weight_norm_f64(v, g):
     """The same fold W = g v / sqrt(max(sum_{k,ci} v^2, 1e-12)) (reference conv_layers.py:149-153) evaluated in float64 on the
     float32 variables: the weights of the F0-net under mbx_config.f0_accumulate = MBX_F0_ACC_F64 ("<layer>.w64",
-    csrc/conv_mfma.hip::conv1d_f64_tile) -- the contour feeds the phase integrator, so its net runs on the exact fold."""
+    csrc/conv_mel.hip::conv1d_f64_tile) -- the contour feeds the phase integrator, so its net runs on the exact fold."""
     v = np.asarray(v, dtype=np.float64)
     sq = np.sum(v * v, axis=(0, 1), keepdims=True)
     return np.asarray(g, dtype=np.float64) * (v / np.sqrt(np.maximum(sq, 1e-12)))

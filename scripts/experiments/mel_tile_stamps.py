@@ -1,5 +1,5 @@
-"""Cycle account of a wave of conv1d_mel_tile_dma (csrc/conv_mfma.hip) from in-kernel s_memtime stamps (mkexp.py m2_stamp):
-    EXP_FILE=conv_mfma.hip python scripts/experiments/mkexp.py m2_stamp:m2_stamp
+"""Cycle account of a wave of conv1d_mel_tile_dma (csrc/conv_mel.hip) from in-kernel s_memtime stamps (mkexp.py m2_stamp):
+    EXP_FILE=conv_mel.hip python scripts/experiments/mkexp.py m2_stamp:m2_stamp
     gpurun -- 'MBX_LIB_PATH=$PWD/scripts/experiments/libs/lib_m2_stamp.so python scripts/experiments/mel_tile_stamps.py [ks cin cout]'
 One convolution of 16 x 800 rows as a launch of its own (default: PS_1, 3 x 256 -> 256)."""
 import ctypes

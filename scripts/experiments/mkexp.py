@@ -76,31 +76,6 @@ PATCHES = {
         ('            if (row < rows) *reinterpret_cast<float2 *>(dst + (long long)row * ld) = make_float2(acc[2 * pr][v], acc[2 * pr + 1][v]);',
          '            if (row < rows && acc[2 * pr][v] == 123.456f) *reinterpret_cast<float2 *>(dst + (long long)row * ld) = make_float2(acc[2 * pr][v], acc[2 * pr + 1][v]);'),
     ],
-    # conv_mfma.hip
-    'sgd2': [
-        ('    constexpr int DEPTH = RT * CT == 1 ? 6 : 3;',
-         '    constexpr int DEPTH = RT * CT == 1 ? 6 : 2;'),
-    ],
-    # conv_mfma.hip
-    'sgd4': [
-        ('    constexpr int DEPTH = RT * CT == 1 ? 6 : 3;',
-         '    constexpr int DEPTH = RT * CT == 1 ? 6 : 4;'),
-    ],
-    # conv_mfma.hip
-    'mel4': [
-        ('    constexpr int MEL_RT = 2;',
-         '    constexpr int MEL_RT = 4;'),
-    ],
-    # conv_mfma.hip
-    'mel1': [
-        ('    constexpr int MEL_RT = 2;',
-         '    constexpr int MEL_RT = 1;'),
-    ],
-    # conv_mfma.hip
-    'melb4': [
-        ('__global__ __launch_bounds__(256, RT <= 2 ? 3 : 2) void conv1d_mel_group_kernel',
-         '__global__ __launch_bounds__(256, 4) void conv1d_mel_group_kernel'),
-    ],
     # stft_filter.hip
     'sf_fast': [
         ('            const float re = (c.max_log_range > 0.f) ? c.max_log_range * tanhf(s.x) : s.x;\n            const float mag = expf(re);\n            float sn, cs;\n            sincosf(s.y, &sn, &cs);',
@@ -429,33 +404,21 @@ PATCHES = {
     'tail_unroll11': [
         ('#pragma unroll 4\n    for (int c = wave; c < nc8; c += 4) {', '#pragma unroll 11\n    for (int c = wave; c < nc8; c += 4) {'),
     ],
-    # conv_mfma.hip: twelve K groups of the small mel-rate tiles in flight instead of six (round-4 A/B)
-    'small_depth12': [
-        ('    constexpr int DEPTH = RT * CT == 1 ? 6 : 3;', '    constexpr int DEPTH = RT * CT == 1 ? 12 : 3;'),
-    ],
-    'small_depth8': [
-        ('    constexpr int DEPTH = RT * CT == 1 ? 6 : 3;', '    constexpr int DEPTH = RT * CT == 1 ? 8 : 3;'),
-    ],
-    'small_depth4': [
-        ('    constexpr int DEPTH = RT * CT == 1 ? 6 : 3;', '    constexpr int DEPTH = RT * CT == 1 ? 4 : 3;'),
-    ],
-    # conv_mfma.hip: the ablations of the register-staged large-launch tile (mt_*: rounds 4-5) and of the first LDS-DMA version
-    # (m2_nomfma / nolds / nodma / nobar / inter) went with the code they patched; their results: profiles/r05_mel_tile_ablations.txt
-    # conv_mfma.hip, conv1d_mel_tile_dma (timing only)
-    # conv_mfma.hip, conv1d_mel_tile_dma: cycles of a wave from start to "first slice requested", in wait + barrier, in request +
-    # cursor code, in the operand reads + MFMAs, in the quarter folds, and in the epilogue (scripts/experiments/mel_tile_stamps.py)
-    # conv_mfma.hip, conv1d_small_tile32: groups in flight per operand set
+    # (the ablations of the register-staged large-launch mel tile, mt_*, and of the first LDS-DMA version, m2_nomfma / nolds /
+    # nodma / nobar / inter, went with the code they patched; their results: profiles/r05_mel_tile_ablations.txt)
+    # conv_mel.hip, conv1d_small_tile32: groups in flight per operand set
     'st_depth6': [('    constexpr int DEPTH = 4;                                 // groups in flight beside the batch being multiplied',
                    '    constexpr int DEPTH = 6;                                 // groups in flight beside the batch being multiplied')],
     'st_depth8': [('    constexpr int DEPTH = 4;                                 // groups in flight beside the batch being multiplied',
                    '    constexpr int DEPTH = 8;                                 // groups in flight beside the batch being multiplied')],
     'st_depth3': [('    constexpr int DEPTH = 4;                                 // groups in flight beside the batch being multiplied',
                    '    constexpr int DEPTH = 3;                                 // groups in flight beside the batch being multiplied')],
-    # conv_mfma.hip, launch_conv1d_group: order of the members inside a shared launch (float32 members by work instead of by K)
+    # conv_mel.hip, launch_conv1d_group: order of the members inside a shared launch (float32 members by work instead of by K)
     'grp_bywork': [('        return convs[a].ks * convs[a].cin > convs[b].ks * convs[b].cin;',
                     '        return (long long)convs[a].ks * convs[a].cin * convs[a].cout > (long long)convs[b].ks * convs[b].cin * convs[b].cout;')],
     'grp_byworkasc': [('        return convs[a].ks * convs[a].cin > convs[b].ks * convs[b].cin;',
                        '        return (long long)convs[a].ks * convs[a].cin * convs[a].cout < (long long)convs[b].ks * convs[b].cin * convs[b].cout;')],
+    # conv_mel.hip, conv1d_mel_tile_dma: in-kernel time stamps of every wave (timing only; scripts/experiments/mel_tile_stamps.py)
     'm2_stamp': [      # start / end of every wave + where it ran (no stamps inside the loop)
         ('constexpr int M2_NG = 2, M2_STAGES = 4;',
          '__device__ unsigned long long g_m2_stamps[8192 * 4 * 8];\n#define M2_STAMP(var) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\\n\\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); __builtin_amdgcn_sched_barrier(0); }\nconstexpr int M2_NG = 2, M2_STAGES = 4;'),

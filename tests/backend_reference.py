@@ -257,7 +257,7 @@ def _where_float(stage, ii, flat, shape, g, ref, n_rows, dims):
     row, ch = divmod(flat, shape[-1]) if len(shape) > 1 else (flat, 0)
     w = {"stage": stage, "item": ii, "got": float(g.flat[flat]), "ref": float(ref.flat[flat])}
     if stage == "cepstrum":
-        # mel-rate convolution tiles: 128 output columns (conv_mfma.hip); frames are the rows
+        # mel-rate convolution tiles: 128 output columns (conv_mel.hip); frames are the rows
         w.update(frame=row, coefficient=ch, column_tile=ch // 128, column_in_tile=ch % 128, frame_in_64=row % 64,
                  frames_to_end=n_rows - row)
     elif stage == "subbands":

@@ -113,7 +113,7 @@ def test_conv1d(torch, cin, cout, ks, dil, mode, rows, prelu):
     (4, 16, 1, "CONSTANT", 1, False),
 ])
 def test_conv1d_f64_accumulation(torch, cin, cout, ks, mode, rows, prelu):
-    """mbx_conv1d_f64acc (csrc/conv_mfma.hip::conv1d_f64_tile, the F0-net's arithmetic): float32 operands, float64 sums on
+    """mbx_conv1d_f64acc (csrc/conv_mel.hip::conv1d_f64_tile, the F0-net's arithmetic): float32 operands, float64 sums on
     the f64 matrix cores, one rounding -- every output is the float32 nearest to the exact result (half an ulp)."""
     eng = get_engine("small", *SMALL)[0]
     rng = np.random.default_rng(cin * 1000 + cout + 7)
@@ -173,7 +173,7 @@ def test_conv1d_f64_tile_shapes_give_the_same_bits(torch):
     (1, 8, 36, "CONSTANT", 800),
 ])
 def test_mel_tile_large_launch_same_bits(torch, ks, cin, cout, mode, rows):
-    """Large launches (>= 12 288 rows) run the mel-rate convolutions as LDS-DMA tiles of 64 x 128 (csrc/conv_mfma.hip::
+    """Large launches (>= 12 288 rows) run the mel-rate convolutions as LDS-DMA tiles of 64 x 128 (csrc/conv_mel.hip::
     conv1d_mel_tile_dma), small ones as 32 x 32 tiles with K split over the waves: the same MFMA steps in the same order and
     the same fold of the K quarters, so a row's bits do not depend on the launch it ran in -- and both match the oracle."""
     eng = get_engine("small", *SMALL)[0]

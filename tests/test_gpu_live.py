@@ -132,7 +132,7 @@ def test_analyzer_equals_the_offline_analysis(case):
     # the long stream first, the 3-hop stream last and late: it takes the fifth slot while the long one is in flight
     order = [4, 0, 1, 2, 3]
     got = serve(an, [sounds[ii] for ii in order], [cuts[ii] for ii in order], join_late={4: 6})
-    assert an.ring_samples > ring0 and an._rings.shape[0] == 8
+    assert an.ring_samples > ring0 and an.rings.shape[0] == 8
     for pos, ii in enumerate(order):
         assert got[pos].shape == want[ii].shape == (sounds[ii].size // hop + 1, cfg["mel_channels"])
         assert np.array_equal(got[pos].view(np.int32), want[ii].view(np.int32)), f"stream of {sounds[ii].size} samples"
@@ -159,12 +159,12 @@ def test_analyzer_equals_the_offline_analysis(case):
         an.open(sid)
         an.push(sid, sounds[ii][:hop] if ii == 4 else sounds[ii], last=ii != 4)
     tick()
-    assert tuple(an._rings.shape) == (4, ring0) and an.streams[0].on_device == hop
+    assert tuple(an.rings.shape) == (4, ring0) and an.streams[0].on_device == hop
     an.open(4)
     an.push(4, sounds[order[4]], last=True)
     an.push(0, long_one[hop:hop + 6 * win])
     tick()
-    assert an._rings.shape[0] == 8 and an.ring_samples > ring0 and an._rings.shape[1] == an.ring_samples
+    assert an.rings.shape[0] == 8 and an.ring_samples > ring0 and an.rings.shape[1] == an.ring_samples
     an.push(0, long_one[hop + 6 * win:], last=True)
     tick()
     assert all(an.finished(sid) for sid in range(5))

@@ -241,7 +241,7 @@ def test_analyzer_equals_the_offline_tool_path():
         assert np.array_equal(bits(again[sid]), bits(want[sid])), f"grown stores, stream {sid} at {rates[sid]} Hz"
     plain = StreamingAnalyzer(TINY, ring_samples=win, slots=4)
     alone = serve(plain, [sounds[3]], [None], [cuts[3]])[0]
-    assert plain._in_rings is None and np.array_equal(bits(alone), bits(got[3]))
+    assert plain.input_rings is None and np.array_equal(bits(alone), bits(got[3]))
 
 
 def test_late_stream_reuses_both_slots():

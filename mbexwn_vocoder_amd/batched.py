@@ -136,8 +136,21 @@ class SynthBatch:
         return float(np.max(np.abs(self.audio(jj)))) if self.n_samples[jj] else 0.0
 
 
+def stage_factors(rows, device=None):
+    """Per-frame transposition factors of one micro-batch: ``rows`` (list of (T_j,) float32 arrays) -> (B, Tmax) float32 on
+    ``device``, every row continued with its last factor (the padding frames belong to no item)."""
+    import torch
+    tmax = max(int(rr.shape[0]) for rr in rows)
+    scale = np.ones((len(rows), tmax), dtype=np.float32)
+    for jj, rr in enumerate(rows):
+        if rr.shape[0]:
+            scale[jj, :rr.shape[0]] = rr
+            scale[jj, rr.shape[0]:] = rr[-1]
+    return torch.as_tensor(scale, device=device)
+
+
 def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False, host_audio=True,
-                      flac_compression="verbatim", out_rate=None):
+                      flac_compression="verbatim", out_rate=None, transpositions=None):
     """Generator over the padded micro-batches of ``mels`` (list of (T_i, C) float32 arrays) on ``engine``: each is staged
     and run (engine.forward with the items' lengths), its FLAC frames encoded (``flac``) and / or its audio copied to pinned
     host memory (``host_audio``), all enqueued on the current stream; the SynthBatch is yielded without waiting, so that a
@@ -146,20 +159,37 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
     None for a model without noise channel.  ``out_rate`` (None or the model's rate: nothing changes): the micro-batch is
     resampled on the device behind the forward (``resample.resample_device`` with the items' own lengths), and the FLAC
     frames, the host audio and ``n_samples`` of the SynthBatch are at that rate; ``SynthBatch.model_audio`` keeps the
-    model-rate audio."""
+    model-rate audio.
+
+    ``noises`` may also be a ``mel_inverter.KeyedNoise`` (a seed and one key per item): each micro-batch's draw is then filled
+    on the device by ``engine.keyed_noise``, a function of the seed, the item's key and the step alone.  ``transpositions``:
+    per item None or (T_i,) factors, one per mel frame -- the ``f0_scale`` rows of the forward; None: the forward of today."""
     import torch
+    from .mel_inverter import KeyedNoise
     dims = engine.dims
     if out_rate is not None and int(round(out_rate)) == int(round(dims.sample_rate)):
         out_rate = None
     lengths = [int(mm.shape[0]) for mm in mels]
     stream = torch.cuda.current_stream(engine.device)
     for group in plan_batches(range(len(mels)), lengths, max_batch, max_padded_frames):
+        keyed = isinstance(noises, KeyedNoise)
         mel, n_frames, noise = stage_micro_batch([mels[ii] for ii in group],
-                                                 None if noises is None else [noises[ii] for ii in group],
+                                                 None if noises is None or keyed else [noises[ii] for ii in group],
                                                  dims.wn_in_rows_per_frame, engine.device)
+        control = {}
+        if transpositions is not None:
+            for ii in group:
+                if transpositions[ii] is not None and np.shape(transpositions[ii]) != (lengths[ii],):
+                    raise ValueError(f"transpositions[{ii}] must hold one factor per mel frame ({lengths[ii]})")
+            control["f0_scale"] = stage_factors([np.ones(lengths[ii], dtype=np.float32) if transpositions[ii] is None
+                                                 else np.asarray(transpositions[ii], dtype=np.float32) for ii in group],
+                                                engine.device)
         events = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         events[0].record(stream)
-        audio = engine.forward(mel, n_frames=n_frames, noise=noise)
+        if keyed:                                           # the draw is part of the step: inside the device time
+            noise = engine.keyed_noise(noises.seed, [noises.keys[ii] for ii in group],
+                                       [lengths[ii] * dims.wn_in_rows_per_frame for ii in group])
+        audio = engine.forward(mel, n_frames=n_frames, noise=noise, **control)
         events[1].record(stream)
         n_samples = [lengths[ii] * dims.hop_size for ii in group]
         model_audio = None
@@ -193,52 +223,13 @@ class _Clock:
             self.seconds[key] = self.seconds.get(key, 0.0) + seconds
 
 
-def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threads=2, verbose=False, quiet=False,
-            flac_compression="verbatim", out_rate=None):
-    """The batched CLI on this process's GPU: ``files[mine]`` -> syn_<basename>.<fmt> in ``output_dir``.
-
-    ``frames``: the frame count after scale_mel of EVERY file of the job, in file order (the noise replay needs all of
-    them; default: read here, which needs ``mine`` = all files).  Reader pool (load_var + scale_mel; a missing or bad file
-    fails before anything runs), device (forward, FLAC frames, asynchronous copies into pinned memory), writer pool (MD5,
-    header, file write); both pools have ``threads`` threads.  ``flac_compression``: what the built-in FLAC writers emit,
-    on the device and on the host ("verbatim" or "fixed").  ``out_rate``: the files are written at that rate (resampled on
-    the device, ``run_micro_batches``); the verbose ``mel_error`` stays computed on the model-rate audio, the clipping note
-    is about what is written."""
-    t_start = time.perf_counter()
-    mine = list(range(len(files))) if mine is None else list(mine)
-    clock, log_lock = _Clock(), threading.Lock()
-
-    def log(lines):
-        with log_lock:
-            for line in lines:
-                print(line, file=sys.stderr)
-
-    def read(ii):
-        t0 = time.perf_counter()
-        if verbose:
-            log([f"load mell  from {files[ii]}"])
-        mel = inv.scale_mel(load_var(files[ii]), verbose=verbose)
-        clock.add("read", time.perf_counter() - t0)
-        return mel
-
-    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
-        scaled = dict(zip(mine, pool.map(read, mine)))
-    if frames is None:
-        if sorted(mine) != list(range(len(files))):
-            raise ValueError("run_job: the frames of every file are needed when this process writes only some of them")
-        frames = [int(scaled[ii].shape[1]) for ii in range(len(files))]
-    for ii in mine:
-        if int(scaled[ii].shape[1]) != int(frames[ii]):
-            raise RuntimeError(f"{files[ii]}: {scaled[ii].shape[1]} frames after scale_mel, the job plan says {frames[ii]}")
-    dims = inv.model.dims
-    draws = (replay_noise(frames, dims.wn_in_rows_per_frame, keep=mine, device=inv.model.device)
-             if dims.noise_sigma else None)
-    device_flac = fmt.lower() == "flac" and not have_soundfile()
-    rate = inv.srate
-    out_rate = inv._output_rate(out_rate)
-    file_rate = rate if out_rate is None else out_rate
-    from . import flac
+def _file_writer(inv, files, mine, scaled, output_dir, fmt, device_flac, file_rate, flac_compression, verbose, quiet, clock,
+                 log):
+    """The writer-pool task of run_job and run_audio_job: ``write(sb)`` waits for the micro-batch ``sb`` (whose indices
+    point into ``mine``) and writes syn_<basename>.<fmt> of each of its items, with the clipping note and, ``verbose``, the
+    mel error against ``scaled``."""
     from .mel_inverter import log_to_db
+    rate = inv.srate
 
     def write(sb):
         sb.wait()
@@ -267,12 +258,69 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
         clock.add("device_ms", sb.device_ms)
         clock.add("copy_ms", sb.copy_ms)
 
+    return write
+
+
+def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threads=2, verbose=False, quiet=False,
+            flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None):
+    """The batched CLI on this process's GPU: ``files[mine]`` -> syn_<basename>.<fmt> in ``output_dir``.
+
+    ``frames``: the frame count after scale_mel of EVERY file of the job, in file order (the noise replay needs all of
+    them; default: read here, which needs ``mine`` = all files).  Reader pool (load_var + scale_mel; a missing or bad file
+    fails before anything runs), device (forward, FLAC frames, asynchronous copies into pinned memory), writer pool (MD5,
+    header, file write); both pools have ``threads`` threads.  ``flac_compression``: what the built-in FLAC writers emit,
+    on the device and on the host ("verbatim" or "fixed").  ``out_rate``: the files are written at that rate (resampled on
+    the device, ``run_micro_batches``); the verbose ``mel_error`` stays computed on the model-rate audio, the clipping note
+    is about what is written.  ``noise_seed``: the noise channel takes the keyed noise of that seed instead of the replayed
+    draws, the key of a file being ``noise.item_key`` of its basename -- a file's audio then does not depend on the other
+    files; ``transposition``: a factor on every mel frame of every file (``f0_scale`` rows).  Both None: today's job."""
+    t_start = time.perf_counter()
+    mine = list(range(len(files))) if mine is None else list(mine)
+    clock, log_lock = _Clock(), threading.Lock()
+
+    def log(lines):
+        with log_lock:
+            for line in lines:
+                print(line, file=sys.stderr)
+
+    def read(ii):
+        t0 = time.perf_counter()
+        if verbose:
+            log([f"load mell  from {files[ii]}"])
+        mel = inv.scale_mel(load_var(files[ii]), verbose=verbose)
+        clock.add("read", time.perf_counter() - t0)
+        return mel
+
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+        scaled = dict(zip(mine, pool.map(read, mine)))
+    if frames is None:
+        if sorted(mine) != list(range(len(files))):
+            raise ValueError("run_job: the frames of every file are needed when this process writes only some of them")
+        frames = [int(scaled[ii].shape[1]) for ii in range(len(files))]
+    for ii in mine:
+        if int(scaled[ii].shape[1]) != int(frames[ii]):
+            raise RuntimeError(f"{files[ii]}: {scaled[ii].shape[1]} frames after scale_mel, the job plan says {frames[ii]}")
+    dims = inv.model.dims
+    draws = (replay_noise(frames, dims.wn_in_rows_per_frame, keep=mine, device=inv.model.device)
+             if dims.noise_sigma and noise_seed is None else None)
+    device_flac = fmt.lower() == "flac" and not have_soundfile()
+    rate = inv.srate
+    out_rate = inv._output_rate(out_rate)
+    file_rate = rate if out_rate is None else out_rate
+    write = _file_writer(inv, files, mine, scaled, output_dir, fmt, device_flac, file_rate, flac_compression, verbose, quiet,
+                         clock, log)
     mels = [scaled[ii][0] for ii in mine]
     noises = None if draws is None else [draws[ii] for ii in mine]
+    if noise_seed is not None and dims.noise_sigma:
+        from .mel_inverter import KeyedNoise
+        from .noise import item_key
+        noises = KeyedNoise(noise_seed, [item_key(files[ii]) for ii in mine])
+    rows = None if transposition is None else [np.full(int(mm.shape[0]), transposition, dtype=np.float32) for mm in mels]
     with ThreadPoolExecutor(max_workers=max(1, threads)) as writers:
         pending = [writers.submit(write, sb) for sb in run_micro_batches(inv.model, mels, noises, max(1, batch),
                                                                          flac=device_flac, host_audio=verbose or not device_flac,
-                                                                         flac_compression=flac_compression, out_rate=out_rate)]
+                                                                         flac_compression=flac_compression, out_rate=out_rate,
+                                                                         transpositions=rows)]
         for fu in pending:
             fu.result()
     if verbose:
@@ -283,6 +331,154 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
               f"real time); read+scale {sec.get('read', 0.0):.2f} s, device {sec.get('device_ms', 0.0) / 1e3:.3f} s, "
               f"encode+D2H {sec.get('copy_ms', 0.0) / 1e3:.3f} s, MD5+write {sec.get('write', 0.0):.2f} s "
               f"(pool stages summed over {max(1, threads)} threads each)", file=sys.stderr)
+
+
+def read_transposition_file(path):
+    """``--transposition-file``: lines ``basename factor`` -> {basename: factor}.  Blank lines and what follows a ``#`` are
+    ignored; a line of another shape, a factor that is not a finite positive number or a basename given twice raises
+    ValueError with the line number."""
+    table = {}
+    with open(path) as fi:
+        for number, line in enumerate(fi, 1):
+            fields = line.split("#", 1)[0].split()
+            if not fields:
+                continue
+            try:
+                if len(fields) != 2:
+                    raise ValueError("expected `basename factor`")
+                factor = float(fields[1])
+                if not (np.isfinite(factor) and factor > 0):
+                    raise ValueError("the factor must be finite and positive")
+                if os.path.basename(fields[0]) in table:
+                    raise ValueError(f"{fields[0]} is listed twice")
+            except ValueError as err:
+                raise ValueError(f"{path}:{number}: {err}") from None
+            table[os.path.basename(fields[0])] = factor
+    return table
+
+
+def file_factors(files, transposition=1.0, table=None):
+    """The transposition factor of every file: ``table[basename]`` (read_transposition_file) where it is listed, else
+    ``transposition``; every factor finite and positive, or ValueError."""
+    table = table or {}
+    factors = [float(table.get(os.path.basename(ff), transposition)) for ff in files]
+    if not all(np.isfinite(ff) and ff > 0 for ff in factors):
+        raise ValueError("transposition must be finite and positive")
+    return factors
+
+
+def read_sound(path):
+    """``audioio.read_audio`` for the file-to-file tool: (samples, rate), or ValueError for what the tool skips -- a file
+    with more than one channel, without samples or with an invalid rate."""
+    from .audioio import read_audio
+    snd, rate = read_audio(path)
+    if snd.size == 0:
+        raise ValueError(f"{path}: no samples")
+    if int(round(rate)) <= 0:
+        raise ValueError(f"{path}: invalid sample rate {rate}")
+    return snd, int(round(rate))
+
+
+def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
+                  quiet=False, flac_compression="verbatim", out_rate=None):
+    """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
+    ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
+
+    Reader pool (``read_sound``), device (``analysis.generate_mels``: resampler and mel analysis in micro-batches grouped by
+    rate), pool again (``scale_mel``, on the host: the mel then has the bits of generate_mel.py followed by resynth_mel.py),
+    device (``run_micro_batches`` with the keyed noise of ``noise_seed`` -- the key of a file is ``noise.item_key`` of its
+    basename --, ``factors[i]`` on every frame of file i, the output resampler and the FLAC frames), writer pool.  A file
+    gives frames * hop samples at the model rate before the output resampler, as a live stream of it emits.
+    ``out_rate``: a rate in Hz, ``"input"`` (every file at its own rate) or None (the model rate).  Nothing is replayed and
+    nothing depends on ``mine``: a file's audio is a function of the file, the model, the seed, its factor and the rate."""
+    from .analysis import generate_mels
+    from .mel_inverter import KeyedNoise
+    from .noise import item_key
+    t_start = time.perf_counter()
+    mine = list(range(len(files))) if mine is None else list(mine)
+    factors = [1.0] * len(files) if factors is None else list(factors)
+    clock, log_lock = _Clock(), threading.Lock()
+
+    def log(lines):
+        with log_lock:
+            for line in lines:
+                print(line, file=sys.stderr)
+
+    def read(ii):
+        t0 = time.perf_counter()
+        try:
+            return read_sound(files[ii])
+        except ValueError as err:
+            return err
+        finally:
+            clock.add("read", time.perf_counter() - t0)
+
+    def scale(dd):
+        t0 = time.perf_counter()
+        mel = inv.scale_mel(dd, verbose=verbose)
+        clock.add("scale", time.perf_counter() - t0)
+        return mel
+
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+        loaded = dict(zip(mine, pool.map(read, mine)))
+        skipped = [(files[ii], str(loaded[ii])) for ii in mine if isinstance(loaded[ii], ValueError)]
+        mine = [ii for ii in mine if not isinstance(loaded[ii], ValueError)]
+        for name, why in skipped:
+            log([f"transform_audio::error:: skipped {name}: {why}"])
+        stats = {}
+        dicts = generate_mels([loaded[ii][0] for ii in mine], [loaded[ii][1] for ii in mine], inv.preprocess_config,
+                              on_device=True, batch=max(1, batch), stats=stats) if mine else []
+        scaled = dict(zip(mine, pool.map(scale, dicts)))
+    dims = inv.model.dims
+    device_flac = fmt.lower() == "flac" and not have_soundfile()
+    # the files grouped by the rate they are written at (one group unless out_rate is "input")
+    groups = {}
+    for local, ii in enumerate(mine):
+        rate = loaded[ii][1] if out_rate == "input" else out_rate
+        groups.setdefault(inv._output_rate(rate), []).append(local)
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as writers:
+        pending = []
+        for rate, members in groups.items():
+            sub = [mine[local] for local in members]
+            write = _file_writer(inv, files, sub, scaled, output_dir, fmt, device_flac, inv.srate if rate is None else rate,
+                                 flac_compression, verbose, quiet, clock, log)
+            noises = KeyedNoise(noise_seed, [item_key(files[ii]) for ii in sub]) if dims.noise_sigma else None
+            rows = [np.full(int(scaled[ii].shape[1]), factors[ii], dtype=np.float32) for ii in sub]
+            pending += [writers.submit(write, sb) for sb in run_micro_batches(
+                inv.model, [scaled[ii][0] for ii in sub], noises, max(1, batch), flac=device_flac,
+                host_audio=verbose or not device_flac, flac_compression=flac_compression, out_rate=rate, transpositions=rows)]
+        for fu in pending:
+            fu.result()
+    if verbose:
+        wall = time.perf_counter() - t_start
+        sec = clock.seconds
+        audio_s = sum(int(scaled[ii].shape[1]) for ii in mine) * inv.hop_size / inv.srate
+        print(f"transform_audio: {len(mine)} files, {audio_s:.1f} s of audio in {wall:.2f} s wall ({audio_s / max(wall, 1e-9):.1f} "
+              f"x real time); read {sec.get('read', 0.0):.2f} s, upload {stats.get('upload', 0.0):.3f} s, resample "
+              f"{stats.get('resample', 0.0):.3f} s, analysis {stats.get('analysis', 0.0):.3f} s, mel copy-back "
+              f"{stats.get('copy_back', 0.0):.3f} s, scale_mel {sec.get('scale', 0.0):.2f} s, noise+forward "
+              f"{sec.get('device_ms', 0.0) / 1e3:.3f} s, resample+encode+D2H {sec.get('copy_ms', 0.0) / 1e3:.3f} s, MD5+write "
+              f"{sec.get('write', 0.0):.2f} s (pool stages summed over {max(1, threads)} threads each)", file=sys.stderr)
+    return skipped
+
+
+def plan_audio_ranks(files, ranks, threads=2):
+    """What the parent of a ``transform_audio.py --gpus N`` job decides before it starts its ranks, without importing torch:
+    the visible GPUs, the files it skips -- (file, reason) pairs, ``read_sound`` -- and the LPT partition of the others by
+    duration.  ``files`` in the plan are the ones the ranks share out."""
+    def seconds_of(path):
+        try:
+            snd, rate = read_sound(path)
+            return snd.size / rate
+        except ValueError as err:
+            return err
+
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+        seconds = list(pool.map(seconds_of, files))
+    good = [ii for ii, ss in enumerate(seconds) if not isinstance(ss, ValueError)]
+    cost = [int(np.ceil(seconds[ii] * 1000)) for ii in good]
+    return {"devices": visible_gpu_count(), "files": [files[ii] for ii in good], "shards": lpt_partition(cost, ranks),
+            "skipped": [[files[ii], str(ss)] for ii, ss in enumerate(seconds) if isinstance(ss, ValueError)]}
 
 
 def plan_ranks(model_id_or_path, files, ranks, threads=2):
@@ -300,16 +496,17 @@ def plan_ranks(model_id_or_path, files, ranks, threads=2):
     return {"devices": visible_gpu_count(), "frames": frames, "shards": lpt_partition(frames, ranks)}
 
 
-def run_ranks(script, child_argv, model_id_or_path, files, ranks, threads=2, quiet=False, poll_s=0.05):
+def run_ranks(script, child_argv, model_id_or_path, files, ranks, threads=2, quiet=False, poll_s=0.05, plan=None,
+              tool="resynth_mel"):
     """``resynth_mel.py --gpus N``: plan the job (:func:`plan_ranks`), start N fresh child processes ``script child_argv
     --rank r --job <plan>`` (rank r on visible device r % count), poll them; when one fails, end the others.  Returns the
-    exit status of the job."""
-    plan = plan_ranks(model_id_or_path, files, ranks, threads)
+    exit status of the job.  ``plan``: a plan made by the caller (``plan_audio_ranks``) instead; ``tool`` names the messages."""
+    plan = plan_ranks(model_id_or_path, files, ranks, threads) if plan is None else plan
     if plan["devices"] < 1:
-        print("resynth_mel::error:: no GPU visible", file=sys.stderr)
+        print(f"{tool}::error:: no GPU visible", file=sys.stderr)
         return 1
     if ranks > plan["devices"] and not quiet:
-        print(f"resynth_mel::note:: {ranks} ranks on {plan['devices']} visible GPU(s): rank r runs on device r % "
+        print(f"{tool}::note:: {ranks} ranks on {plan['devices']} visible GPU(s): rank r runs on device r % "
               f"{plan['devices']}, ranks share a GPU", file=sys.stderr)
     with tempfile.TemporaryDirectory() as tmp:
         job = os.path.join(tmp, "job.json")

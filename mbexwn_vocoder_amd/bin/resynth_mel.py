@@ -10,6 +10,7 @@ Deviations (documented in INTEGRATION.md):
     wav: float32 through scipy; the reference uses pysndfile, default format flac)
   * additionally ``--batch N`` (padded micro-batches, FLAC frames encoded on the GPU, reader / writer pools of -nt
     threads), ``--gpus N`` (the files sharded over N child processes by frames) and ``--batch-invariant``
+  * additionally ``--noise-seed S`` (keyed noise, include/mbexwn_noise.h) and ``--transposition F``
   * additionally ``--out-rate R``: the files are written at R Hz, resampled on the GPU from the model rate with the
     reference's resampler (mbexwn_vocoder_amd/resample.py)
 """
@@ -31,7 +32,7 @@ from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
          num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None,
-         flac_compression="verbatim", out_rate=None):
+         flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None):
     format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
     if flac_compression != "verbatim" and rank is None and not quiet:
         from mbexwn_vocoder_amd.batched import have_soundfile
@@ -45,6 +46,8 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
                 "--calibrate", str(calibrate), "--conv-form", conv_form, "--flac-compression", flac_compression]
         argv += ["-o", output_dir] if output_dir else []
         argv += ["--out-rate", str(out_rate)] if out_rate else []
+        argv += ["--noise-seed", str(noise_seed)] if noise_seed is not None else []
+        argv += ["--transposition", repr(transposition)] if transposition is not None else []
         argv += [flag for flag, on in (("-g", use_gpu), ("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant))
                  if on]
         sys.exit(run_ranks(os.path.abspath(__file__), argv, model_id, input_mell_files, gpus, threads=num_threads,
@@ -89,7 +92,7 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         from mbexwn_vocoder_amd.batched import run_job
         run_job(MelInv, input_mell_files, output_dir, format, frames=plan["frames"] if plan else None,
                 mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose, quiet=quiet,
-                flac_compression=flac_compression, out_rate=out_rate)
+                flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed, transposition=transposition)
         return
     out_rate = MelInv._output_rate(out_rate)
 
@@ -103,7 +106,13 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         log_mel_spectrogram = MelInv.scale_mel(dd, verbose=verbose)
 
         start_time = time.time()
-        syn_audio = MelInv.synth_from_mel(log_mel_spectrogram)
+        control = {}
+        if noise_seed is not None:                   # keyed noise: a function of the seed, the file's basename and the step
+            from mbexwn_vocoder_amd.noise import item_key
+            control.update(noise_seed=noise_seed, noise_key=item_key(mell_file))
+        if transposition is not None:                # the factor on every mel frame, as run_job applies it
+            control.update(transposition=np.full(log_mel_spectrogram.shape[1], transposition, dtype=np.float32))
+        syn_audio = MelInv.synth_from_mel(log_mel_spectrogram, **control)
         end_time = time.time()
 
         if verbose:                                  # reference :90-96
@@ -120,6 +129,18 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         if verbose:
             print(f"    save audio under {outfile}", file=sys.stderr)
         write_audio(outfile, syn_audio, MelInv.srate if out_rate is None else out_rate, format, flac_compression)
+
+
+def positive_factor(text):
+    """argparse type of --transposition: a finite positive factor."""
+    from argparse import ArgumentTypeError
+    try:
+        factor = float(text)
+    except ValueError:
+        factor = float("nan")
+    if not (np.isfinite(factor) and factor > 0):
+        raise ArgumentTypeError(f"a finite positive factor is expected, got {text!r}")
+    return factor
 
 
 def positive_rate(text):
@@ -172,6 +193,12 @@ if __name__ == "__main__":
                         help="write the files at R Hz: the audio is resampled on the GPU from the model rate with the "
                              "reference's resampler; with -v, mel_error stays computed on the model-rate audio, the clipping "
                              "note is about what is written (Def: the model rate)")
+    parser.add_argument("--noise-seed", dest="noise_seed", default=None, type=int, metavar="S",
+                        help="draw the noise channel keyed by (S, the .mell file's basename, the step): a file's audio then "
+                             "does not depend on the other files of the job or their order (Def: the draws of the "
+                             "one-at-a-time loop)")
+    parser.add_argument("--transposition", default=None, type=positive_factor, metavar="F",
+                        help="factor on the pitch, applied to every mel frame (Def: none)")
     parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
     parser.add_argument("--job", default=None, help=SUPPRESS)
     args = parser.parse_args()

@@ -27,14 +27,16 @@ from mbexwn_vocoder_amd.config import read_config  # noqa: E402
 from mbexwn_vocoder_amd.live import check_rate  # noqa: E402
 
 
-def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0, sample_rate=None, output_rate=None):
+def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0, sample_rate=None, output_rate=None,
+                noise_fn=None):
     """Push `samples` in pieces of tick_samples, one tick per push, until the stream is finished; returns its audio.
     ``sample_rate``: the rate of `samples` when it is not the model's (the stream resamples); ``output_rate``: the rate the
-    audio comes back at when it is not the model's (a rate in Hz, or "input")."""
+    audio comes back at when it is not the model's (a rate in Hz, or "input"); ``noise_fn``: the stream's noise instead of the
+    generator seeded with ``seed`` (``live.keyed_noise_fn``)."""
     rates = {} if sample_rate is None else {"sample_rate": sample_rate}
     if output_rate is not None:
         rates["output_rate"] = output_rate
-    live.open(stream_id, seed=seed, **rates)
+    live.open(stream_id, seed=seed, noise_fn=noise_fn, **rates)
     out = []
     for start in range(0, samples.size, tick_samples):
         end = min(start + tick_samples, samples.size)
@@ -50,7 +52,7 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0,
 
 
 def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tick_ms=80.0, seed=0, quiet=False,
-         resample=False, output_rate=None):
+         resample=False, output_rate=None, noise_seed=None):
     preprocess_config = read_config(config_file=get_config_file(model_id_or_path=model_id))['preprocess_config']
     if not os.path.isfile(input_audio_file):
         print(f"stream_transpose::error:: no such file: {input_audio_file}", file=sys.stderr)
@@ -77,14 +79,17 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
         print("stream_transpose::error:: no GPU available; this build has no CPU path", file=sys.stderr)
         sys.exit(1)
     from mbexwn_vocoder_amd.batched import write_audio
-    from mbexwn_vocoder_amd.live import LiveResynthesizer
+    from mbexwn_vocoder_amd.live import LiveResynthesizer, keyed_noise_fn
     from mbexwn_vocoder_amd.mel_inverter import MELInverter
     live = LiveResynthesizer(MELInverter(model_id_or_path=model_id))
     tick_samples = max(1, int(round(tick_ms * 1e-3 * rate)))
     own_rate = int(round(rate)) if int(round(rate)) != model_rate else None
     out_rate = (own_rate or model_rate) if output_rate == "input" else int(output_rate or model_rate)
+    # --noise-seed: the keyed noise of the file (its basename is the key), what transform_audio.py draws for it
+    keyed = {} if noise_seed is None else {"noise_fn": keyed_noise_fn(live.mel_inverter.model, noise_seed),
+                                           "stream_id": os.path.basename(input_audio_file)}
     audio = stream_file(live, samples, tick_samples, transposition, seed=seed, sample_rate=own_rate,
-                        output_rate=out_rate if out_rate != model_rate else None)
+                        output_rate=out_rate if out_rate != model_rate else None, **keyed)
     out_dir = os.path.dirname(os.path.abspath(output_file))
     os.makedirs(out_dir, exist_ok=True)
     ext = os.path.splitext(output_file)[1].lower().lstrip(".") or "wav"
@@ -131,6 +136,10 @@ if __name__ == "__main__":
                         help="write the output at R Hz, resampled on the device by the stream; input = the file's own rate, "
                              "which needs --resample when that is not the model's (Def: the model rate)")
     parser.add_argument("--seed", default=0, type=int, help="seed of the stream's noise generator (Def: %(default)s)")
+    parser.add_argument("--noise-seed", dest="noise_seed", default=None, type=int, metavar="S",
+                        help="draw the stream's noise keyed by (S, the file's basename) and the absolute step, as "
+                             "transform_audio.py --noise-seed S does for the file; --seed is then unused (Def: the generator "
+                             "seeded with --seed)")
     parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")
     args = parser.parse_args()
 

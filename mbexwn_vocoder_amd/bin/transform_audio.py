@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""Transpose sound files in batches: sound files in, transposed sound files out, on the MI355X HIP path.
+
+    transform_audio.py FILES... -o DIR --model_id VOICE [--transposition F | --transposition-file LIST] [--noise-seed S]
+                       [--batch N] [--gpus N] [--out-rate R|input] [--format flac] [--flac-compression fixed]
+
+Joins the stages of generate_mel.py and resynth_mel.py in one process (mbexwn_vocoder_amd/batched.py::run_audio_job): the
+device resampler and mel analysis, scale_mel on the host, the synthesis in padded micro-batches with the factor on every mel
+frame, the output resampler and the FLAC frames on the device.  The outputs are named syn_<basename>.<format>.
+
+The noise channel takes keyed noise (include/mbexwn_noise.h): a function of (--noise-seed, the file's basename, the step).
+With --batch-invariant or a pinned --conv-form a file's samples therefore do not depend on the batch size, the order of the
+arguments, the number of ranks or the other files of the job, and on an f23 engine they are what stream_transpose.py
+--noise-seed S streams for the file.
+
+A file gives frames * hop samples at the model rate before the output resampler (frames = resampled length // hop + 1), as
+the live path emits: the output is not trimmed to the input's length.  A file without samples or with more than one channel
+is reported and skipped; the others are written and the exit status is 1.
+"""
+import json
+import os
+import sys
+
+test_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'mbexwn_vocoder_amd')
+if os.path.exists(test_path):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
+
+from mbexwn_vocoder_amd import list_models  # noqa: E402
+from mbexwn_vocoder_amd.batched import file_factors, read_transposition_file  # noqa: E402
+
+
+def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, transposition_file=None, noise_seed=0, batch=16,
+         gpus=1, num_threads=2, out_rate=None, format="flac", flac_compression="verbatim", conv_form="auto",
+         batch_invariant=False, verbose=False, quiet=False, rank=None, job=None):
+    try:
+        table = read_transposition_file(transposition_file) if transposition_file else None
+        factors = file_factors(input_audio_files, transposition, table)
+    except (OSError, ValueError) as err:
+        print(f"transform_audio::error:: {err}", file=sys.stderr)
+        sys.exit(1)
+    missing = [ff for ff in input_audio_files if not os.path.isfile(ff)]
+    if missing:
+        print(f"transform_audio::error:: no such file: {', '.join(missing)}", file=sys.stderr)
+        sys.exit(1)
+    names = [os.path.basename(ff) for ff in input_audio_files]
+    if len(set(names)) != len(names):
+        print("transform_audio::error:: two input files share a basename: they would share an output file and a noise key",
+              file=sys.stderr)
+        sys.exit(1)
+    if gpus > 1 and rank is None:
+        # --gpus N: this parent never initialises HIP; N fresh child processes write their share of the files each
+        from mbexwn_vocoder_amd.batched import plan_audio_ranks, run_ranks
+        plan = plan_audio_ranks(input_audio_files, gpus, threads=num_threads)
+        for name, why in plan["skipped"]:
+            print(f"transform_audio::error:: skipped {name}: {why}", file=sys.stderr)
+        argv = [*plan["files"], "-o", output_dir, "--model_id", model_id, "--transposition", repr(float(transposition)),
+                "--noise-seed", str(noise_seed), "--batch", str(batch), "-nt", str(num_threads), "--format", format,
+                "--flac-compression", flac_compression, "--conv-form", conv_form]
+        argv += ["--transposition-file", transposition_file] if transposition_file else []
+        argv += ["--out-rate", str(out_rate)] if out_rate else []
+        argv += [flag for flag, on in (("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant)) if on]
+        status = run_ranks(os.path.abspath(__file__), argv, model_id, plan["files"], gpus, threads=num_threads, quiet=quiet,
+                           plan=plan, tool="transform_audio") if plan["files"] else 0
+        sys.exit(1 if status or plan["skipped"] else 0)
+    import torch
+    if not torch.cuda.is_available():
+        print("transform_audio::error:: no GPU available; this build has no CPU path", file=sys.stderr)
+        sys.exit(1)
+    plan = None
+    if job is not None:                                       # a rank of a --gpus job: its device and its files
+        with open(job) as fo:
+            plan = json.load(fo)
+        torch.cuda.set_device(rank % plan["devices"])
+    if num_threads:
+        torch.set_num_threads(max(1, int(num_threads)))
+    from mbexwn_vocoder_amd.batched import run_audio_job
+    from mbexwn_vocoder_amd.mel_inverter import MELInverter
+    inv = MELInverter(model_id_or_path=model_id, verbose=verbose, batch_invariant=True if batch_invariant else None,
+                      conv_form=None if conv_form == "auto" else conv_form)
+    os.makedirs(output_dir, exist_ok=True)
+    skipped = run_audio_job(inv, input_audio_files, output_dir, format, factors=factors, noise_seed=noise_seed,
+                            mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose,
+                            quiet=quiet, flac_compression=flac_compression, out_rate=out_rate)
+    if skipped:
+        sys.exit(1)
+
+
+def factor_arg(text):
+    """argparse type of --transposition: a finite positive factor."""
+    from argparse import ArgumentTypeError
+    try:
+        file_factors(["x"], float(text))
+    except ValueError:
+        raise ArgumentTypeError(f"a finite positive factor is expected, got {text!r}") from None
+    return float(text)
+
+
+def out_rate_arg(text):
+    """argparse type of --out-rate: "input", or a positive whole number of Hz."""
+    from argparse import ArgumentTypeError
+    if text == "input":
+        return text
+    try:
+        rate = int(text)
+    except ValueError:
+        raise ArgumentTypeError(f"a sample rate in Hz or 'input' is expected, got {text!r}") from None
+    if rate <= 0:
+        raise ArgumentTypeError(f"a sample rate must be positive, got {rate}")
+    return rate
+
+
+def make_parser():
+    from argparse import SUPPRESS, ArgumentParser
+    parser = ArgumentParser(description="transpose sound files with an MBExWN model: analysis, pitch control and synthesis in "
+                                        "batches (MI355X HIP path)")
+    parser.add_argument("input_audio_files", nargs="+", help="mono sound files, at any sample rate")
+    parser.add_argument("-o", "--output_dir", required=True, help="output directory where the transposed sounds will be stored")
+    parser.add_argument("--model_id", default="VOICE", nargs="?", const="",
+                        help="model identifier or path to a model directory. Given without a value the script lists all known "
+                             "models. (Def: %(default)s)")
+    parser.add_argument("--transposition", default=1.0, type=factor_arg, metavar="F", help="factor on the pitch (Def: %(default)s)")
+    parser.add_argument("--transposition-file", dest="transposition_file", default=None, metavar="LIST",
+                        help="text file with lines `basename factor`: the factor of the files it lists, instead of "
+                             "--transposition")
+    parser.add_argument("--noise-seed", dest="noise_seed", default=0, type=int, metavar="S",
+                        help="seed of the keyed noise: a file's noise is a function of (S, its basename, the step) "
+                             "(Def: %(default)s)")
+    parser.add_argument("--batch", default=16, type=int, metavar="N",
+                        help="analyse and synthesise up to N files per launch in padded micro-batches (Def: %(default)s)")
+    parser.add_argument("--gpus", default=1, type=int, metavar="N",
+                        help="shard the files by duration over N child processes, rank r on visible GPU r %% count, each "
+                             "writing its own files (Def: %(default)s)")
+    parser.add_argument("-nt", "--num_threads", default=2, type=int, help="reader and writer threads (Def: %(default)s)")
+    parser.add_argument("--out-rate", dest="out_rate", default=None, type=out_rate_arg, metavar="R|input",
+                        help="write the files at R Hz, resampled on the GPU from the model rate; input = every file at its "
+                             "own rate (Def: the model rate)")
+    parser.add_argument("--format", default="flac", help="file format for generated audio files (Def: %(default)s)")
+    parser.add_argument("--flac-compression", default="verbatim", choices=["verbatim", "fixed"],
+                        help="what the built-in FLAC writer emits, on the GPU: verbatim = uncompressed sub-frames; fixed = fixed "
+                             "predictors with Rice codes; ignored when soundfile writes the files (Def: %(default)s)")
+    parser.add_argument("--conv-form", default="auto", choices=["auto", "direct", "f23", "f43"],
+                        help="form of the WaveNet's dilated convolution; pinned, a file's samples do not depend on the batch "
+                             "(f23: they equal what stream_transpose.py --noise-seed streams) (Def: %(default)s)")
+    parser.add_argument("--batch-invariant", action="store_true",
+                        help="pin the engine's kernels so that a file's audio does not depend on the batch it ran in")
+    parser.add_argument("-v", "--verbose", action="store_true", help="display verbose progress info and the time per stage")
+    parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")
+    parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
+    parser.add_argument("--job", default=None, help=SUPPRESS)
+    return parser
+
+
+if __name__ == "__main__":
+    args = make_parser().parse_args()
+    if not args.model_id:
+        print("Please select one of the following models.\nYou don't need to select with a full ID. "
+              "The first model containing the model_id you provide will be selected.")
+        for kk, ll in list_models().items():
+            for md in ll:
+                print(f" - {kk}/{md}")
+    else:
+        main(**vars(args))

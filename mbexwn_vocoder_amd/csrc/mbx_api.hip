@@ -9,7 +9,9 @@
 #include "../../include/mbexwn_live_resample.h"
 #include "../../include/mbexwn_live_out.h"
 #include "../../include/mbexwn_flac.h"
+#include "../../include/mbexwn_noise.h"
 
+static_assert(MBXN_FILL_TILE == mbx::NOISE_TILE, "mbexwn_noise.h states the tile of noise_keyed.hip");
 static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
 
 using namespace mbx_host;
@@ -497,6 +499,24 @@ mbx_status mbxf_encode_flac16_fixed(const float *audio, int64_t stride, int32_t 
     HIP_TRY(hipMemsetAsync(max_abs, 0, (size_t)batch * sizeof(float), stream));
     mbx::launch_flac_fixed(audio, stride, batch, n_samples, sample_rate, crc_tables, out, frame_bytes, workspace, pcm_out,
                            max_abs, stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxn_fill_normal(float *out, int64_t stride, int32_t batch, const uint64_t *keys, const int64_t *first_step,
+                            const int32_t *counts, int32_t max_count, void *hip_stream) {
+    mbx::NoiseArgs a{};
+    a.out = out;
+    a.stride = stride;
+    a.batch = batch;
+    a.keys = keys;
+    a.first_step = first_step;
+    a.counts = counts;
+    a.max_count = max_count;
+    if (const char *why = mbx::check_fill_normal(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("fill normal: ") + why);
+    if (batch == 0 || max_count == 0) return MBX_OK;
+    mbx::launch_fill_normal(a, static_cast<hipStream_t>(hip_stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

@@ -447,6 +447,23 @@ void launch_flac_fixed(const float *audio, long long stride, int batch, const in
                        const uint16_t *crc_tables, uint8_t *out, int32_t *frame_bytes, int64_t *workspace, int16_t *pcm_out,
                        float *max_abs, hipStream_t stream);
 
+// keyed N(0,1) noise (noise_keyed.hip; include/mbexwn_noise.h: mbxn_fill_normal): Philox4x32-10 quads keyed by (seed, item
+// key), counted by the absolute step, Box-Muller in float32
+constexpr int NOISE_TILE = 4096;                // values per block
+struct NoiseArgs {
+    float *out;                  // (batch, stride)
+    long long stride;
+    int batch;
+    const uint64_t *keys;        // (batch, 2): seed, item key
+    const int64_t *first_step;   // (batch) or null = 0
+    const int32_t *counts;       // (batch)
+    int max_count;
+    int tiles;                   // set by the launcher
+};
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_fill_normal(const NoiseArgs &a);
+void launch_fill_normal(const NoiseArgs &a, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // optional RMS normalisation of the mel input / de-normalisation of the audio (norm_mel.hip)
 // ---------------------------------------------------------------------------------------------

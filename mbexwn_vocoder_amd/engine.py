@@ -227,6 +227,9 @@ def load_library():
     # include/mbexwn_flac.h (FLAC_SYMBOLS)
     lib.mbxf_encode_flac16_fixed.restype = i32
     lib.mbxf_encode_flac16_fixed.argtypes = [fp, ctypes.c_int64, i32, i64p, i32, vp, vp, ctypes.c_int64, vp, vp, vp, fp, vp]
+    # include/mbexwn_noise.h (NOISE_SYMBOLS)
+    lib.mbxn_fill_normal.restype = i32
+    lib.mbxn_fill_normal.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, vp]
     _lib = lib
     return lib
 
@@ -251,6 +254,9 @@ FLAC_SYMBOLS = ["mbxf_encode_flac16_fixed"]
 
 # include/mbexwn_live_out.h: the streaming output resampler (prefix mbxo_; the five lists above stay as they are)
 LIVE_OUT_SYMBOLS = ["mbxo_resample_emit"]
+
+# include/mbexwn_noise.h: the keyed normal noise (prefix mbxn_; the six lists above stay as they are)
+NOISE_SYMBOLS = ["mbxn_fill_normal"]
 
 
 def _check(status):
@@ -1114,6 +1120,46 @@ class MBExWNEngine:
             event.record(torch.cuda.current_stream(self.device))
         res = EncodedFlac(host, offsets, host_max, counts, rate, event)
         return res.wait() if wait else res
+
+    def keyed_noise(self, seeds, item_keys, counts, first_step=None, out=None):
+        """Keyed N(0,1) noise (include/mbexwn_noise.h, ``mbxn_fill_normal``): row b holds the values ``first_step[b] ..
+        first_step[b] + counts[b]`` of the item ``(seeds[b], item_keys[b])``, zeros behind them.  ``seeds`` / ``item_keys``:
+        integers (taken mod 2^64), one per item, or one seed for all; ``counts`` / ``first_step``: host integers.  Returns a
+        float32 device tensor (B, max(counts)); ``out``: a zeroed float32 device tensor (B, stride >= max(counts)) to fill
+        instead.  A value depends on its seed, key and step alone: not on the batch, the row or the window it is asked
+        in."""
+        torch = self._torch
+        counts = [int(nn) for nn in counts]
+        B = len(counts)
+        keys = [int(kk) for kk in item_keys]
+        seeds = [int(seeds)] * B if np.ndim(seeds) == 0 else [int(ss) for ss in seeds]
+        first = [0] * B if first_step is None else [int(ff) for ff in first_step]
+        if not (len(keys) == len(seeds) == len(first) == B):
+            raise ValueError(f"keyed_noise: one seed, item key and first step per count ({B})")
+        if any(nn < 0 for nn in counts) or any(ff < 0 for ff in first):
+            raise ValueError("keyed_noise: counts and first_step must not be negative")
+        top = max(counts, default=0)
+        if out is None:
+            out = torch.zeros((B, top), dtype=torch.float32, device=self.device)
+        elif (out.dim() != 2 or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous()
+              or int(out.shape[0]) != B or int(out.shape[1]) < top):
+            raise ValueError(f"keyed_noise: out must be a contiguous float32 tensor ({B}, >= {top}) on the engine's device")
+        if B == 0 or top == 0:
+            return out
+        mask = (1 << 64) - 1
+        table = np.empty((B, 4), dtype=np.uint64)            # one upload: seed, item key, first step, count
+        table[:, 0] = [ss & mask for ss in seeds]
+        table[:, 1] = [kk & mask for kk in keys]
+        table[:, 2] = first
+        table[:, 3] = counts
+        dev = torch.as_tensor(table.view(np.int64)).to(self.device)
+        keys_dev = dev[:, :2].contiguous()
+        first_dev = dev[:, 2].contiguous()
+        counts_dev = dev[:, 3].to(torch.int32)
+        with torch.cuda.device(self.device):
+            _check(self._lib.mbxn_fill_normal(out.data_ptr(), int(out.shape[1]), B, keys_dev.data_ptr(), first_dev.data_ptr(),
+                                              counts_dev.data_ptr(), top, self._stream()))
+        return out
 
     def _encode_flac16_fixed(self, audio, counts, counts_c, rate, out, capacity, max_abs, wait):
         """The compressed half of :meth:`encode_flac16`: frames packed densely, so the lengths are copied back first and

@@ -606,3 +606,21 @@ class LiveResynthesizer:
         if st.out_rate is not None:
             return self.output.finished(stream_id)
         return st.flushed and self.synthesizer.finished(stream_id)
+
+
+def keyed_noise_fn(engine, seed):
+    """A ``noise_fn(stream_id, a, b)`` for :meth:`LiveResynthesizer.open`: the keyed noise (include/mbexwn_noise.h,
+    ``engine.keyed_noise``) of the frames [a, b) of the item ``stream_id`` -- an integer key, or a name whose key is
+    ``noise.item_key(name)`` -- under ``seed``, counted from step ``a * steps_per_frame``, copied back to the host.  The
+    stream then takes the values ``MELInverter.synth_from_mel(..., noise_seed=seed, noise_key=key)`` takes for the whole
+    item, bit for bit, whatever its ticks are."""
+    from .noise import item_key
+    spf = int(engine.dims.steps_per_frame)
+
+    def noise_fn(stream_id, first, end):
+        count = (int(end) - int(first)) * spf
+        if count <= 0:
+            return np.zeros(0, dtype=np.float32)
+        return engine.keyed_noise(seed, [item_key(stream_id)], [count], first_step=[int(first) * spf])[0].cpu().numpy()
+
+    return noise_fn

@@ -145,7 +145,18 @@ class MELInverter(object):
         from .resample import resample_device
         return resample_device(audio.contiguous(), None, int(round(self.srate)), out_rate)[0]
 
-    def synth_from_mel(self, scaled_mell, noise=None, f0=None, transposition=None, out_rate=None):
+    def _keyed_noise(self, noise, noise_seed, keys, frames):
+        """The keyed draw of items of ``frames`` frames (engine.keyed_noise: a function of the seed, the item's key and the
+        step alone), or None for a model without noise channel; ``noise`` together with ``noise_seed`` is refused."""
+        if noise is not None:
+            raise ValueError("noise= and noise_seed= exclude each other: the keyed draw replaces the injected one")
+        dims = self.model.dims
+        if not dims.noise_sigma:
+            return None
+        return self.model.keyed_noise(int(noise_seed), keys, [int(tt) * dims.wn_in_rows_per_frame for tt in frames])
+
+    def synth_from_mel(self, scaled_mell, noise=None, f0=None, transposition=None, out_rate=None, noise_seed=None,
+                       noise_key=0):
         """(1, T, mel_channels) log-mel -> float32 audio of T*hop_size samples
         (reference mel_inverter.py:151-154; like there, a batch is flattened by ``ravel``).
 
@@ -159,8 +170,17 @@ class MELInverter(object):
 
         ``out_rate`` (this build): the audio comes back at that rate, ceil(T * hop_size * up / down) samples --
         ``resample.resample_device`` (the reference's resampler, model rate -> ``out_rate``) on the device audio before it
-        is copied back.  None or the model's rate: the audio as the model makes it."""
+        is copied back.  None or the model's rate: the audio as the model makes it.
+
+        ``noise_seed`` (this build): the noise channel takes the keyed draw of the item ``noise_key`` (an integer, e.g.
+        ``noise.item_key(file name)``; one per row of a batch, or one for all) under that seed -- ``engine.keyed_noise``,
+        handed to the forward as ``noise`` is.  The audio is then a function of (mel, seed, key) and does not depend on what
+        was synthesised before.  Not together with ``noise``."""
         out_rate = self._output_rate(out_rate)
+        if noise_seed is not None:
+            shape = np.shape(scaled_mell)
+            keys = [int(kk) for kk in np.broadcast_to(np.asarray(noise_key, dtype=object), (int(shape[0]),))]
+            noise = self._keyed_noise(noise, noise_seed, keys, [int(shape[1])] * int(shape[0]))
         self._calibrate_if_pending(scaled_mell)
         if f0 is not None or transposition is not None:
             return self._synth_with_pitch(scaled_mell, noise, f0, transposition, out_rate)
@@ -218,7 +238,7 @@ class MELInverter(object):
                               f"chosen at creation ({self.model.conv_form_info()['form']})", RuntimeWarning)
 
     def synth_from_mels(self, scaled_mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False,
-                        flac_compression="verbatim", out_rate=None):
+                        flac_compression="verbatim", out_rate=None, noise_seed=None, noise_keys=None, transpositions=None):
         """Batched :meth:`synth_from_mel` (this build): a list of ``scale_mel`` outputs (1, T_i, mel_channels) -> a list of
         float32 audio (T_i * hop_size,), or with ``flac=True`` of complete FLAC files (bytes; frames encoded on the device).
 
@@ -230,16 +250,30 @@ class MELInverter(object):
         ``out_rate``: every item comes back at that rate (audio, or FLAC files whose header, frames and MD5 are at that
         rate and length): the micro-batch is resampled on the device (``resample.resample_device`` with the items' own
         lengths, so each tail is clipped at its item's end), and item b equals ``resample_device`` of its own model-rate
-        audio alone.  None or the model's rate: today's path."""
+        audio alone.  None or the model's rate: today's path.
+
+        ``noise_seed``: item i takes the keyed draw of ``noise_keys[i]`` (default: its index) under that seed, as
+        :meth:`synth_from_mel` with ``noise_seed`` / ``noise_key`` does -- nothing is replayed, and an item's draw does not
+        depend on the list it is in.  Not together with ``noises``.  ``transpositions``: per item None, or (T_i,) factors,
+        one per mel frame (``f0_scale`` rows of the forward)."""
         import torch
         from .batched import replay_noise, run_micro_batches
+        if noise_seed is not None and noises is not None:
+            raise ValueError("noises= and noise_seed= exclude each other: the keyed draw replaces the injected one")
+        if noise_seed is None and noise_keys is not None:
+            raise ValueError("synth_from_mels: noise_keys needs noise_seed")
         out_rate = self._output_rate(out_rate)
         rate = self.srate if out_rate is None else out_rate
         if len(scaled_mels):
             self._calibrate_if_pending(scaled_mels[0])
         mels =[np.asarray(mm, dtype=np.float32).reshape(-1, mm.shape[-2], mm.shape[-1])[0] for mm in scaled_mels]
         dims = self.model.dims
-        if not dims.noise_sigma:
+        if noise_seed is not None:
+            keys = list(range(len(mels))) if noise_keys is None else [int(kk) for kk in noise_keys]
+            if len(keys) != len(mels):
+                raise ValueError("synth_from_mels: one noise key per mel")
+            noises = None if not dims.noise_sigma else KeyedNoise(int(noise_seed), keys)
+        elif not dims.noise_sigma:
             noises = None
         elif noises is None:
             noises = replay_noise([mm.shape[0] for mm in mels], dims.wn_in_rows_per_frame, device=self.model.device)
@@ -248,7 +282,7 @@ class MELInverter(object):
                       .reshape(-1) for zz in noises]
         out = [None] * len(mels)
         for batch in run_micro_batches(self.model, mels, noises, max_batch, max_padded_frames, flac=flac, host_audio=not flac,
-                                       flac_compression=flac_compression, out_rate=out_rate):
+                                       flac_compression=flac_compression, out_rate=out_rate, transpositions=transpositions):
             batch.wait()
             for jj, ii in enumerate(batch.indices):
                 if not flac:
@@ -259,6 +293,29 @@ class MELInverter(object):
                     from . import flac as flac_writer
                     out[ii] = flac_writer.encode(batch.audio(jj), rate, flac_compression)
         return out
+
+    def transform_audio(self, sounds, rates, names, transposition=1.0, noise_seed=0, out_rate=None, max_batch=16,
+                        max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim"):
+        """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
+        keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
+        factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
+        on the host, then :meth:`synth_from_mels` with the keyed noise of ``noise_seed``, the factor on every frame, and
+        ``out_rate`` / ``flac`` as there.  Item i has ``frames_i * hop_size`` samples at the model rate before the output
+        resampler (frames_i = resampled length // hop_size + 1), as a live stream of it emits: not trimmed to its input.
+
+        An item's audio is a function of (sound, rate, name, factor, seed, out_rate): with a ``batch_invariant`` engine or
+        one pinned to a convolution form it does not depend on the batch, the order or the other items."""
+        from .analysis import generate_mels
+        from .noise import item_key
+        factors = check_factors(transposition, len(sounds))
+        if not (len(sounds) == len(rates) == len(names)):
+            raise ValueError("transform_audio: one rate and one name per sound")
+        dicts = generate_mels(sounds, rates, self.preprocess_config, on_device=True, batch=max_batch)
+        scaled = [self.scale_mel(dd) for dd in dicts]
+        rows = [np.full(int(mm.shape[1]), ff, dtype=np.float32) for mm, ff in zip(scaled, factors)]
+        return self.synth_from_mels(scaled, max_batch=max_batch, max_padded_frames=max_padded_frames, flac=flac,
+                                    flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed,
+                                    noise_keys=[item_key(nn) for nn in names], transpositions=rows)
 
     def calibrate(self, scaled_mells, verbose=False, max_frames=400, seed=42):
         """Decide the form of the WaveNet's dilated convolution on REAL data (this build; C ABI mbx_calibrate).
@@ -422,6 +479,26 @@ class MELInverter(object):
         self.use_max_limit = False
         if self.preprocess_config.get("use_max_limit", False):
             self.use_max_limit = self.preprocess_config["use_max_limit"]
+
+
+class KeyedNoise:
+    """Per-item keyed noise for ``batched.run_micro_batches``: the seed and the items' keys; each micro-batch's draw is
+    filled on the device by ``engine.keyed_noise`` when the batch is staged."""
+
+    def __init__(self, seed, keys):
+        self.seed, self.keys = int(seed), [int(kk) for kk in keys]
+
+
+def check_factors(transposition, count):
+    """``transposition`` -- one factor or ``count`` of them -- as a list of ``count`` finite positive floats."""
+    factors = np.asarray(transposition, dtype=np.float64)
+    if factors.ndim == 0:
+        factors = np.full(count, float(factors))
+    if factors.shape != (count,):
+        raise ValueError(f"transposition must be one factor or one per item ({count})")
+    if not (np.all(np.isfinite(factors)) and np.all(factors > 0)):
+        raise ValueError("transposition must be finite and positive")
+    return [float(ff) for ff in factors]
 
 
 def create_synthetic_model_dir(path, voice_type="SPEECH", seed=1234, weights_format="npz", **config_overrides):

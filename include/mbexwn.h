@@ -200,8 +200,10 @@ typedef struct {
     int32_t wn_keep_start;       /* 1: keep the start convolution and the full first layer (default: folded into layer 0) */
     float calib_fraction;        /* MBX_CONV_AUTO: share of the parity budget the form's own rounding may take; 0 = 0.25 */
     /* measurement knobs, none changes what a kernel computes for a given kernel choice (scripts/experiments):
-     *   tune_gate_shape        0: by launch size, 1: 256-row F(4,3) blocks, 2: 128-row product-split blocks, 3: product-split
-     *                          blocks of half a column tile (same bits, all three)
+     *   tune_gate_shape        0: by launch size; 1: 256-row F(4,3) blocks of one column tile at every launch size; 2: 128-row
+     *                          product-split blocks, 3: product-split blocks of half a column tile (2, 3: launches below 3 072
+     *                          256-row blocks only); 4: 256-row blocks of two column tiles at every launch size,
+     *                          wherever that shape applies (d <= 16, cond_up >= 10; elsewhere as 1).  Same bits, all four
      *   tune_resskip_wave_tiles 0: default (2048); n > 0: res/skip launches of at most n 16-row tiles run the wave-tiled
      *                          kernel; -1: never
      *   tune_resskip_split     0: by launch size, 1..3: column split of the wave-tiled res/skip kernel (same bits) */
@@ -289,7 +291,9 @@ typedef struct {
 #define MBX_GATE_K_NONE 0
 #define MBX_GATE_K_DIRECT 1          /* conv1d_mfma_dma_kernel<EPI_GATE> */
 #define MBX_GATE_K_F23 2             /* wn_gate_winograd2w_kernel */
-#define MBX_GATE_K_F43 3             /* wn_gate_winograd4w_kernel, 256-row blocks */
+#define MBX_GATE_K_F43 3             /* wn_gate_winograd4w_kernel, 256-row blocks of one column tile (32 gate channels), or
+                                      * wn_gate_winograd4q_kernel, 256-row blocks of two column tiles (64): the
+                                      * block shape of large launches; mbx_kernel_report_info.gate_block_channels tells which */
 #define MBX_GATE_K_F43_PSPLIT 4      /* wn_gate_winograd4p_kernel, 128-row product-split blocks */
 #define MBX_GATE_K_F43_HSPLIT 5      /* wn_gate_winograd4h_kernel, product-split blocks of half a column tile */
 #define MBX_GATE_K_F43_STRIDED 6     /* F(4,3) over d / 16 interleaved sub-sequences (d > 16), 256-row blocks */
@@ -302,13 +306,17 @@ mbx_status mbx_conv_form(const mbx_handle *handle, mbx_conv_form_info *info);
 
 /* ABI 11: which residual/skip and tail kernels the most recent forward ran (the gate kernels: mbx_conv_form_info.gate_kernel). */
 typedef struct {
-    int32_t struct_size;        /* sizeof(mbx_kernel_report_info), set by the caller */
+    int32_t struct_size;        /* sizeof(mbx_kernel_report_info), set by the caller; the size up to gate_block_channels (a caller
+                                 * built before that field existed) is accepted too, and that field is then left alone */
     int32_t n_resskip_layers;   /* entries of resskip_kernel that the most recent forward filled (0 before the first one) */
     int32_t resskip_kernel[MBX_MAX_WN_LAYERS];   /* MBX_RESSKIP_K_*: what ran the residual/skip convolution of layer l; block-major
                                                   * as gate_kernel is.  MBX_RESSKIP_K_NONE: the layer has no launch of its own (the
                                                   * last layer of a handle with fold_skip: the tail kernel takes its share) */
     int32_t tail_kernel;        /* MBX_TAIL_K_*: what ran the end convolution and the post-net */
     int32_t tail_folded;        /* 1: that kernel was the folded tail (fold_skip: the last layer's gate output x "wn.tail.fold") */
+    int32_t gate_block_channels[MBX_MAX_WN_LAYERS];   /* gate channels per block of the F(4,3) kernel that ran layer l (indexed as
+                                                       * gate_kernel is): 64 (two column tiles), 32 (one), 16 (MBX_GATE_K_F43_HSPLIT);
+                                                       * 0 where no F(4,3) block ran */
 } mbx_kernel_report_info;
 #define MBX_RESSKIP_K_NONE 0
 #define MBX_RESSKIP_K_CONV1D 1       /* conv1d_mfma_kernel<EPI_RESSKIP> (launch_conv1d): no packed image, or the layer does not fit */

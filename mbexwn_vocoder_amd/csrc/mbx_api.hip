@@ -206,13 +206,18 @@ mbx_status mbx_conv_form(const mbx_handle *hd, mbx_conv_form_info *info) {
 }
 
 mbx_status mbx_kernel_report(const mbx_handle *hd, mbx_kernel_report_info *info) {
-    if (!hd || !info || info->struct_size != (int32_t)sizeof(mbx_kernel_report_info))
+    // (a caller built before gate_block_channels existed passes the size up to that field)
+    const bool whole = info && info->struct_size == (int32_t)sizeof(mbx_kernel_report_info);
+    if (!info || !(whole || info->struct_size == (int32_t)offsetof(mbx_kernel_report_info, gate_block_channels)))
         return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_kernel_report_info ABI mismatch (struct_size)");
+    if (!hd) return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_kernel_report: null handle");
     info->n_resskip_layers = hd->last_gate_layers;
     for (int l = 0; l < MBX_MAX_WN_LAYERS; ++l)
         info->resskip_kernel[l] = l < hd->last_gate_layers ? hd->last_resskip_kernel[l] : MBX_RESSKIP_K_NONE;
     info->tail_kernel = hd->last_gate_layers ? hd->last_tail_kernel : MBX_TAIL_K_NONE;
     info->tail_folded = hd->last_gate_layers ? hd->last_tail_folded : 0;
+    for (int l = 0; whole && l < MBX_MAX_WN_LAYERS; ++l)
+        info->gate_block_channels[l] = l < hd->last_gate_layers ? hd->last_gate_block_channels[l] : 0;
     return MBX_OK;
 }
 

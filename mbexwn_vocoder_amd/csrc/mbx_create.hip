@@ -240,6 +240,9 @@ mbx_status mbx_create(const mbx_config *config, const mbx_tensor *tensors, int32
     if (c.n_precond < 0 || c.n_precond > MBX_MAX_PRECOND) return fail(MBX_ERR_INVALID_ARGUMENT, "n_precond out of range");
     for (int i = 0; i < c.n_precond; ++i)
         if (c.precond_channels[i] < 1) return fail(MBX_ERR_INVALID_ARGUMENT, "precond_channels must be positive");
+    if (c.tune_gate_shape < 0 || c.tune_gate_shape > 4 || c.tune_resskip_split < 0 || c.tune_resskip_split > 3 ||
+        c.tune_resskip_wave_tiles < -1 || c.calib_fraction < 0.f || c.calib_fraction > 1.f)
+        return fail(MBX_ERR_INVALID_ARGUMENT, "tune_* / calib_fraction out of range");
 
     mbx_handle *hd = new mbx_handle();
     hd->cfg = c;
@@ -494,9 +497,6 @@ mbx_status mbx_create(const mbx_config *config, const mbx_tensor *tensors, int32
     hd->f0_full64 = f0_chain_is_full64(hd);
     if (c.wn_conv_form < MBX_CONV_AUTO || c.wn_conv_form > MBX_CONV_F43)
         return bail(fail(MBX_ERR_INVALID_ARGUMENT, "wn_conv_form must be MBX_CONV_AUTO, _DIRECT, _F23 or _F43"));
-    if (c.tune_gate_shape < 0 || c.tune_gate_shape > 3 || c.tune_resskip_split < 0 || c.tune_resskip_split > 3 ||
-        c.tune_resskip_wave_tiles < -1 || c.calib_fraction < 0.f || c.calib_fraction > 1.f)
-        return bail(fail(MBX_ERR_INVALID_ARGUMENT, "tune_* / calib_fraction out of range"));
     {
         // skip path folded into the end convolution when the host supplied the folded tensors (wn_keep_skip: keep
         // the skip tensor, e.g. to look at the "wn_skip" stage)

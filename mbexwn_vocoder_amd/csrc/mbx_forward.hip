@@ -224,9 +224,15 @@ struct ForwardCtx {
 // ---- launch-shape policy: pure functions of the handle's policy fields and the launch's size; they launch nothing ----
 
 struct GateShape {
-    int shape;      // F(4,3) block shape: 0 256-row | 1 product-split | 2 product-split, half column tiles
+    int shape;      // F(4,3) block shape: 0 256-row | 1 product-split | 2 product-split, half column tiles | 3 256-row, two column tiles
     bool f43;       // false: the direct form costs less than F(4,3) for this launch (dilations above 16 only)
 };
+
+// 256-row one-tile blocks from which a launch takes the blocks of two column tiles (gate_shape_policy).  Measured in one
+// process, pins 1 and 4 alternating (scripts/experiments/gate_shapes.py --ab 1 4, profiles/r07_gate_shapes_ab.txt; C = 320,
+// B x 800 frames, us per launch, one tile | two tiles): B = 1: 106.6 | 137.5, 2: 172.7 | 208.7, 4: 331.8 | 334.0 (no
+// difference: its spread is larger), 8: 661.9 | 639.7 (-3.4 %), 16: 1 329.0 | 1 280.1 (-3.7 %).  8 x 800 frames = 5 040 blocks.
+constexpr long long WIDE_FROM_BLOCKS = 5040;
 
 GateShape gate_shape_policy(const mbx_handle *hd, int C, int B, long long nsteps, int span_rows, int d) {
     // F(4,3) block shape: what a launch of a few blocks per CU costs is the largest number of wave tiles a SIMD gets.
@@ -252,8 +258,15 @@ GateShape gate_shape_policy(const mbx_handle *hd, int C, int B, long long nsteps
     // slices whose round trips, not whose MFMAs, set its time), so the finer shape only pays where the product-split
     // blocks leave CUs empty (<= 256 of them) and the half blocks do not (> 256): utterances around 2 s.
     int shape4 = split4 ? ((half_blocks <= 256 && 2 * half_blocks > 256) ? 2 : 1) : 0;
-    if (hd->gate_small_shape >= 0 && !hd->winograd4_always && full_blocks < 4 * 768) shape4 = hd->gate_small_shape;
-    split4 = shape4 != 0;
+    // round 7: 256-row blocks of TWO column tiles (wn_gate_winograd4q_kernel; same bits, so batch_invariant handles follow
+    // the same size rule): the input combinations and the activation staging are spent once per 96 MFMAs instead of once
+    // per 48.  WIDE_FROM_BLOCKS: see the measurements at its definition.
+    if (shape4 == 0 && full_blocks >= WIDE_FROM_BLOCKS) shape4 = 3;
+    // mbx_config.tune_gate_shape: 1 and 4 pin the two shapes of large launches at every size, 2 and 3 the shape of small ones
+    const int pin = hd->gate_small_shape;
+    if (pin == 0 || pin == 3) shape4 = pin;
+    else if (pin > 0 && !hd->winograd4_always && full_blocks < 4 * 768) shape4 = pin;
+    split4 = shape4 == 1 || shape4 == 2;
     bool f43 = true;
     if (d > 16) {
         // Dilations above 16 (the reference's default depth reaches 2048, custom_AE_layers.py:229-233): F(4,3) over the
@@ -269,7 +282,7 @@ GateShape gate_shape_policy(const mbx_handle *hd, int C, int B, long long nsteps
         const double cost_half = 0.56 * (double)((vrows + 127) / 128) * B * vs * tiles;
         const double cost_direct = 2.0 * ((double)span_rows / 256.0) * B * tiles;
         if (hd->gate_small_shape >= 0 && !hd->winograd4_always) {
-            shape4 = hd->gate_small_shape;              // mbx_config.tune_gate_shape pins the shape (and F(4,3) itself)
+            shape4 = hd->gate_small_shape == 3 ? 0 : hd->gate_small_shape;      // mbx_config.tune_gate_shape pins the shape (and F(4,3) itself); no two-tile blocks above d = 16
         } else {
             split4 = split4 || cost_half < 0.95 * cost_full;
             shape4 = split4 ? 1 : 0;
@@ -680,14 +693,14 @@ void run_excitation(ForwardCtx &cx) {
 // Gate of one layer (dilated convolution + conditioning + gate): split half precision, then F(4,3) in the shape the policy
 // prefers, then its 256-row shape, then F(2,3), then the direct form.  carry: the layer's stream state moves first
 // (null: none).  generic: the block runner -- F(4,3) in the 256-row shape at every size, or the direct form.  kernel:
-// where the MBX_GATE_K_* that ran is reported (null: not).
+// where the MBX_GATE_K_* that ran is reported (null: not), block_channels: the gate channels per F(4,3) block (0: none ran).
 mbx_status run_gate_layer(ForwardCtx &cx, const mbx::ConvArgs &g, const WnLayerTensors &t, const mbx::LayerCarryArgs *carry,
-                          bool generic, int *kernel) {
+                          bool generic, int *kernel, int *block_channels) {
     mbx_handle *hd = cx.hd;
     hipStream_t stream = cx.stream;
     const int d = g.dil, C = g.channels;
     const bool streamed = cx.streamed(), whole = g.cond_phase == 0 && g.out_rows == 0;
-    int ran_kernel = MBX_GATE_K_NONE;
+    int ran_kernel = MBX_GATE_K_NONE, ran_channels = 0;
     ScopedEvents ev(hd, PROF_GATE, stream);
     if (carry) mbx::launch_layer_carry(*carry, g.batch, stream);
     bool done = false;
@@ -716,9 +729,12 @@ mbx_status run_gate_layer(ForwardCtx &cx, const mbx::ConvArgs &g, const WnLayerT
             ran = 0;
             done = mbx::launch_wn_gate_winograd4w(gw, 0, stream);
         }
-        if (done)
+        if (done) {
+            // (the blocks of two column tiles are a block shape of MBX_GATE_K_F43: the size rule of large launches picks either)
             ran_kernel = d > 16 ? (ran ? MBX_GATE_K_F43_STRIDED_PSPLIT : MBX_GATE_K_F43_STRIDED)
                                 : (ran == 2 ? MBX_GATE_K_F43_HSPLIT : ran == 1 ? MBX_GATE_K_F43_PSPLIT : MBX_GATE_K_F43);
+            ran_channels = ran == 3 ? 64 : ran == 2 ? 16 : 32;
+        }
     }
     // F(2,3): wave-tiled kernel on v_mfma_f32_16x16x4_f32 (wn_winograd2w.hip): streams, per-layer regions, MBX_CONV_F23
     if (!done && !generic && hd->winograd && t.wino2w) {
@@ -733,6 +749,7 @@ mbx_status run_gate_layer(ForwardCtx &cx, const mbx::ConvArgs &g, const WnLayerT
         ran_kernel = MBX_GATE_K_DIRECT;
     }
     if (kernel) *kernel = ran_kernel;
+    if (block_channels) *block_channels = ran_channels;
     return MBX_OK;
 }
 
@@ -875,10 +892,11 @@ mbx_status run_wavenet(ForwardCtx &cx) {
             if (gs.cphase != 0 || !mbx::launch_wn_gate0(gate0_args(cx, g, t, gs.row0, lda0), stream))
                 return fail(MBX_ERR_INVALID_ARGUMENT, "folded first layer does not fit its kernel");
             hd->last_gate_kernel[l] = MBX_GATE_K_FOLDED_START;
+            hd->last_gate_block_channels[l] = 0;
         } else {
             const bool carry = cx.carry_layers && l >= 1;
             const mbx::LayerCarryArgs lc = carry ? layer_carry_args(cx, l) : mbx::LayerCarryArgs{};
-            const mbx_status st = run_gate_layer(cx, g, t, carry ? &lc : nullptr, false, &hd->last_gate_kernel[l]);
+            const mbx_status st = run_gate_layer(cx, g, t, carry ? &lc : nullptr, false, &hd->last_gate_kernel[l], &hd->last_gate_block_channels[l]);
             if (st != MBX_OK) return st;
         }
         mbx_status st = MBX_OK;
@@ -952,7 +970,8 @@ mbx_status run_wavenet_blocks(ForwardCtx &cx) {
             // k = 3, power-of-two dilation), the direct form otherwise
             const size_t slot = b * L + l;
             const mbx::ConvArgs g = gate_args(hd, t, C, c.wn_dilations[l], w.mb_h, w.mb_a, rows * C, sp, B, cond, (long long)T * blk.ccu * 2 * C);
-            mbx_status st = run_gate_layer(cx, g, t, nullptr, true, slot < MBX_MAX_WN_LAYERS ? &hd->last_gate_kernel[slot] : nullptr);
+            mbx_status st = run_gate_layer(cx, g, t, nullptr, true, slot < MBX_MAX_WN_LAYERS ? &hd->last_gate_kernel[slot] : nullptr,
+                                           slot < MBX_MAX_WN_LAYERS ? &hd->last_gate_block_channels[slot] : nullptr);
             if (st != MBX_OK) return st;
             st = run_resskip_layer(cx, resskip_args(hd, t, C, l, w.mb_a, w.mb_h, w.mb_skip, rows * C, sp, B), t, nullptr, false,
                                    slot < MBX_MAX_WN_LAYERS ? &hd->last_resskip_kernel[slot] : nullptr);

@@ -131,6 +131,7 @@ struct mbx_handle {
     long long subnet_buf_per_frame = 0;   // floats per frame of one ping-pong buffer
     int last_gate_kernel[MBX_MAX_WN_LAYERS] = {};   // MBX_GATE_K_* of the most recent forward (mbx_conv_form_info.gate_kernel)
     int last_gate_layers = 0;
+    int last_gate_block_channels[MBX_MAX_WN_LAYERS] = {};   // gate channels per F(4,3) block of that forward's layers, 0: no F(4,3) block (mbx_kernel_report)
     int last_resskip_kernel[MBX_MAX_WN_LAYERS] = {};   // MBX_RESSKIP_K_* per layer, indexed as last_gate_kernel (mbx_kernel_report)
     int last_tail_kernel = 0, last_tail_folded = 0;    // MBX_TAIL_K_* of the most recent forward; 1: it ran as the folded tail
     bool f0_full64 = false;               // mbx_config.f0_accumulate == MBX_F0_ACC_F64 and the F0-net has the shape (conv [prelu | leaky])* head
@@ -148,7 +149,7 @@ struct mbx_handle {
     bool fold_skip = false;      // skip path folded into the end convolution (needs the *.fold tensors)
     bool fold_start = false;     // start convolution folded into layer 0 (needs fold_skip and the *.start_fold / *.fold_start tensors)
     bool winograd4_always = false;   // mbx_config.batch_invariant with F(4,3): the large-launch kernel shapes at every size
-    int gate_small_shape = -1;       // mbx_config.tune_gate_shape: pins the F(4,3) block shape of small launches (0: 256-row | 1: product-split | 2: product-split, half column tiles; same bits)
+    int gate_small_shape = -1;       // mbx_config.tune_gate_shape: pins the F(4,3) block shape (0: 256-row and 3: 256-row blocks of two column tiles, at every launch size | 1: product-split | 2: product-split, half column tiles, small launches only; same bits)
     long long resskip_wave_tiles = 2048;   // default policy: res/skip launches of at most this many 16-row tiles run the wave-tiled kernel
     int resskip_split = 0;           // mbx_config.tune_resskip_split
     bool split_f16 = false;          // mbx_config.wn_precision == MBX_PRECISION_SPLIT_F16 and the images are there

@@ -90,6 +90,8 @@ struct ConvArgs {
                               // computed (out_rows == 0: all rows; out_row0 a multiple of 2 * dil)
     const float *zeros;       // >= 16 bytes of zeros in global memory (LDS-DMA source of padding lanes)
     int fast_dma;             // set by the launcher: 32-bit source offsets are safe (LDS-DMA with a uniform base)
+    int tile0;                // set by launch_wn_gate_winograd4w: first column tile of the launch (the 256-row blocks that finish an odd
+                              // tile count behind the blocks of two column tiles), 0 otherwise
     int vstride;              // set by launch_wn_gate_winograd4w for dilations above 16: every item is treated as vstride interleaved
                               // virtual items (rows s, s + vstride, s + 2 vstride ...) convolved with dilation dil / vstride
     // split half precision (mbx_config.wn_precision): the hidden state as fp16 planes, written by wn_resskip_f16_kernel and read
@@ -117,7 +119,8 @@ bool launch_conv1d_mel_single(const ConvArgs &a, hipStream_t stream);
 // Winograd F(4,3) form on v_mfma_f32_16x16x4_f32, wave tile 16 groups x 64 columns (wn_winograd4w.hip); a.w = image of
 // engine.pack_winograd4w_weights (ceil(C/32), ceil(C/8), 3072); split: 128-row blocks whose waves split the six products
 // (same bits as the 256-row blocks)
-// shape: 0 = 256-row blocks, 1 = 128-row product-split blocks, 2 = product-split blocks of half a column tile (same bits, all three)
+// shape: 0 = 256-row blocks, 1 = 128-row product-split blocks, 2 = product-split blocks of half a column tile, 3 = 256-row blocks
+// of TWO column tiles (d <= 16, cond_up >= 10; an odd last tile runs in 256-row blocks): same bits, all four
 bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream);
 // Winograd F(2,3) form on v_mfma_f32_16x16x4_f32 with wave-granular tiles (wn_winograd2w.hip: streams, per-layer regions,
 // MBX_CONV_F23); a.w = image of engine.pack_winograd2w_weights (ceil(C/32), ceil(C/8), 2048)

@@ -20,11 +20,15 @@
 // float2 and stores float2 (a wave instruction writes whole 128-byte rows).  The bias is the initial value of product
 // 1's accumulators (m1 enters all four outputs with coefficient 1).
 //
-// Two block shapes:
+// Block shapes:
 //   wn_gate_winograd4w_kernel  256 consecutive output rows (64 groups; wave w owns groups 16 w .. 16 w + 15) x 32 gate
 //             channels; K slices of 8 channels, two LDS stages (52.5 KB with the conditioning tile: 3 blocks per CU --
 //             a third wave per SIMD fills matrix-pipe slots the other two leave: 1.40 -> 1.35 ms at batch 16 x 10 s;
 //             a third stage at 2 blocks per CU measured the same as two).
+//             (Round 7: that loss at two blocks per CU belongs to a wave of 48 MFMAs per slice, not to the occupancy as such:)
+//   wn_gate_winograd4q_kernel  256 rows x 64 gate channels (TWO column tiles), a wave owns 16 groups x 128 columns: the
+//             combinations and the activation staging once per 96 MFMAs; two blocks per CU; launches of 5 040 one-tile
+//             blocks and more: 1.33 -> 1.28 ms at batch 16 x 10 s; same bits; described at the kernel below.
 //   wn_gate_winograd4p_kernel  128 rows x 32 gate channels, waves = 2 row halves x 2 PRODUCT halves, for launches of a
 //             few blocks per CU (one utterance); same bits; described at the kernel below.
 //   (Round 1/2 also had a 128-row shape whose waves split the input CHANNELS and summed the two halves in front of the
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(256, CR <= 28 ? 3 : 2) void wn_gate_winograd4w_kern
     const int id = blockIdx.x;
     const int l = id >> 3;
     const int g_ = (l / p.n_tiles) * 8 + (id & 7);
-    const int nt = l % p.n_tiles;
+    const int nt = p.tile0 + l % p.n_tiles;
     if (g_ >= p.m_tiles_total) return;
     const int bv = g_ / p.m_tiles_per_item;                 // (virtual) item
     const int mt = g_ - bv * p.m_tiles_per_item;
@@ -1091,12 +1095,350 @@ __global__ __launch_bounds__(256, 4) void wn_gate_winograd4h_kernel(ConvArgs p, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// <256 rows x TWO column tiles> (round 7): a wave owns its 16 groups over the column tiles nt and nt + 1 (64 gate channels,
+// 128 weight columns): 6 products x 8 column tiles = 48 accumulator tiles (192 registers), two waves per SIMD.  The input
+// combinations, the activation reads and the activation LDS-DMA are spent once per 96 MFMAs instead of once per 48: per
+// 8-channel slice and wave 96 MFMAs beside 24 combination instructions, 6 activation reads, 24 weight reads and 9 LDS-DMA
+// requests (A 10 KB: 3 per wave as above; B 24 KB: the slices of tiles nt and nt + 1 of the unchanged wino4w image, 6 per
+// wave).  Two stages of 34 KB: a slice is requested 96 MFMAs (3 072 matrix-pipe cycles) of every wave ahead -- the lead of
+// three stages of the one-tile kernel.  The conditioning rows of both tiles (2 x 28 x 64 floats = 14 KB) do not fit beside
+// the stages at two blocks per CU: they go through the stage that the last slice frees, requested behind its barrier.
+// Every accumulator chain, the output combination and the epilogue are those of the other shapes: the SAME bits.
+// LDS: 68 KB + tables = 71 168 bytes -> 2 blocks per CU.  An odd tile count leaves its last tile to a launch of the one-tile
+// kernel (ConvArgs::tile0).
+struct WqShape {
+    static constexpr int ROWS = 256;
+    static constexpr int AROWS = ROWS + 2 * WW_HALO;
+    static constexpr int PHASE = ROWS / 4 + WW_HALO;            // 80
+    static constexpr int CELLS = 4 * PHASE;                     // 320
+    static constexpr int A_FLOATS = CELLS * WW_BK;              // 2560: 10 LDS-DMA chunks of 1 KB
+    static constexpr int B_FLOATS = 2 * WW_B_FLOATS;            // 6144: 24 chunks, tile nt then tile nt + 1
+    static constexpr int STAGE = A_FLOATS + B_FLOATS;           // 8704 floats = 34 KB
+    static constexpr int NSTAGE = 2;
+    static constexpr int THREADS = 256;
+    static constexpr int COND_ROWS = 28;                        // conditioning rows of 64 floats PER column tile, in a freed stage
+    static constexpr int COND_CHUNKS = 2 * COND_ROWS / 4;       // 14
+    static constexpr int TAB = NSTAGE * STAGE;
+    static constexpr int LERP = TAB + ROWS;
+    static constexpr int LDS_FLOATS = LERP + 128;               // 17408 + 256 + 128 = 17792 floats = 71 168 bytes
+};
+
+template <int GA>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void wn_gate_winograd4q_kernel(ConvArgs p, int log2d) {
+    using SH = WqShape;
+    constexpr int ROWS = SH::ROWS, NSTAGE = SH::NSTAGE, STAGE = SH::STAGE, A_FLOATS = SH::A_FLOATS, PHASE = SH::PHASE;
+    typedef __attribute__((address_space(3))) float lds_float;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_float *)lds);
+
+    // p.n_tiles counts PAIRS of column tiles here
+    const int id = blockIdx.x;
+    const int l = id >> 3;
+    const int g_ = (l / p.n_tiles) * 8 + (id & 7);
+    const int nt = 2 * (l % p.n_tiles);
+    if (g_ >= p.m_tiles_total) return;
+    const int b = g_ / p.m_tiles_per_item;
+    const int mt = g_ - b * p.m_tiles_per_item;
+    const int rows = item_rows(p.n_frames, b, p.rows_per_frame, p.max_rows);
+    const int m0 = mt * ROWS;
+    if (m0 >= rows) return;
+    const int C = p.channels;
+    const int n0 = nt * 32;
+    const int d = 1 << log2d;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rw = wave;                                    // row part of this wave
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int sh = p.pad_l - d;                             // CAUSAL padding: d (see wn_gate_winograd4w_kernel)
+    const int xrow0 = max(m0 - WW_HALO - sh, 0);
+    const float *xb = p.x + (long long)b * p.x_bstride + (long long)xrow0 * p.ldx;
+    const int nk8 = (p.cin + WW_BK - 1) / WW_BK;
+
+    // ---- per-lane DMA sources of the activation rows (as in wn_gate_winograd4w_kernel): chunks wave, wave + 4, 8 + (wave & 1)
+    unsigned a_voff[3];
+    unsigned a_bits = 0;
+    int a_inst[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        a_inst[i] = i < 2 ? wave + 4 * i : 8 + (wave & 1);
+        const int pos = a_inst[i] * 64 + lane;
+        const int cell = pos >> 1;
+        const int phase = cell / PHASE, sidx = cell - phase * PHASE;
+        const int m = 4 * (sidx >> log2d) + phase;
+        const int row = (m << log2d) + (sidx & (d - 1)) + WW_HALO - d;
+        const int src = m0 - WW_HALO - sh + row;
+        const int hi = (pos & 1) ^ ((cell >> 3) & 1);
+        if (row < SH::AROWS && src >= 0 && src < rows) a_bits |= 1u << i;
+        a_bits |= (unsigned)hi << (4 + i);
+        a_voff[i] = 4u * (unsigned)((min(max(src, 0), rows - 1) - xrow0) * p.ldx + 4 * hi);
+    }
+    const bool fast_rows = p.fast_dma && m0 - sh >= WW_HALO && m0 + ROWS + WW_HALO - sh <= rows;
+    const int whole_fills = p.cin / WW_BK;
+    const long long wnext = (long long)nk8 * WW_B_FLOATS;                 // floats between the images of two column tiles
+    const float *wtile = p.w + (long long)nt * wnext;
+    const unsigned b_voff = 16u * (unsigned)lane;
+    // LDS-DMA of slice st into a stage: 3 A + 6 B requests per wave (B chunk k < 12: tile nt, k >= 12: tile nt + 1)
+    auto issue = [&](int st, int stage) {
+        const int ci0 = st * WW_BK;
+        const unsigned sdst = lds_base + 4u * (unsigned)(stage * STAGE);
+        if (fast_rows && st < whole_fills) {
+            const float *abase = xb + ci0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) ww_lds_dma16_s(abase, a_voff[i], sdst + 1024u * (unsigned)a_inst[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const int ci = ci0 + 4 * (int)((a_bits >> (4 + i)) & 1u);
+                const bool ok = ((a_bits >> i) & 1u) & (ci < p.cin);
+                // (the 64-bit source address is formed here, behind an opaque copy of the offset: hoisted out of the K loop the
+                // three addresses would not fit the 256 registers)
+                unsigned voff = a_voff[i];
+                asm volatile("" : "+v"(voff));
+                const float *src = reinterpret_cast<const float *>(reinterpret_cast<const char *>(xb + ci0) + voff);
+                ww_lds_dma16(ok ? src : p.zeros, sdst + 1024u * (unsigned)a_inst[i]);
+            }
+        }
+        const float *bsrc = wtile + (long long)st * WW_B_FLOATS;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const int k = wave + 4 * i;                                   // 0 .. 23
+            const float *src = i >= 3 ? bsrc + wnext + (k - 12) * 256 : bsrc + k * 256;
+            ww_lds_dma16_s(src, b_voff, sdst + 4u * (unsigned)A_FLOATS + 1024u * (unsigned)k);
+        }
+    };
+    // conditioning rows of this block into a free stage: 28 x (32 tanh | 32 sigmoid) columns per column tile, 14 chunks
+    // (tile k / 7, rows 4 (k % 7) .. + 3), dealt round-robin
+    const int cond_up = p.cond_up;
+    const int t2base = m0 / cond_up;
+    auto issue_cond = [&](int stage) {
+        const int n2 = rows / cond_up;
+        const float *cbase = p.cond + (long long)b * p.cond_bstride;
+        // (runs once, behind the last slice: the addresses are formed here, from an opaque copy of the lane, so that they are
+        // not carried through the K loop in registers it does not have)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = wave + 4 * i;
+            if (k >= SH::COND_CHUNKS) break;
+            const int ct = k >= 7 ? 1 : 0;
+            const int pos = (k - 7 * ct) * 64 + ln;
+            const int crow = pos >> 4, cq = pos & 15;
+            const int chn = n0 + 32 * ct + 4 * (cq & 7);
+            const int t = min(t2base + crow, n2 - 1);
+            ww_lds_dma16(chn < C ? cbase + (long long)t * (2 * C) + (cq >> 3) * C + chn : p.zeros,
+                         lds_base + 4u * (unsigned)(stage * STAGE) + 1024u * (unsigned)k);
+        }
+    };
+    // ---- prologue: both stages requested (the launcher guarantees nk8 >= NSTAGE)
+#pragma unroll
+    for (int s0 = 0; s0 < NSTAGE; ++s0)
+        if (s0 < nk8) issue(s0, s0);
+
+    f32x4 acc[6][8];          // [product][4 (tile nt | nt + 1) + 2 e + (0 tanh | 1 sigmoid)]
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            // m1 enters all four outputs with coefficient 1: its accumulators start from the bias
+            const int chl = n0 + 32 * (c >> 2) + 2 * r16 + ((c >> 1) & 1);
+            const float bv = (j == 1 && p.bias && chl < C) ? p.bias[(c & 1) * C + chl] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[j][c][r] = bv;
+        }
+    if (tid < ROWS) {
+        const int row = m0 + tid;
+        const int t2 = row / cond_up;
+        const int u = row - t2 * cond_up;
+        reinterpret_cast<int *>(lds + SH::TAB)[tid] = (((t2 - t2base) * 64) << 8) | u;
+    }
+    if (tid < 64) {
+        lds[SH::LERP + tid] = tid < cond_up ? p.lerp_w0[tid] : 0.f;
+        lds[SH::LERP + 64 + tid] = tid < cond_up ? p.lerp_w1[tid] : 0.f;
+    }
+
+    const int grp = 16 * rw + r16;
+    const float *xptr[6];     // LDS addresses (stage 0) of h[t-d] .. h[t+4d]
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+        const int cell = (q & 3) * PHASE + grp + ((q >> 2) << log2d);
+        xptr[q] = lds + 8 * cell + 4 * ((kq >> 1) ^ ((cell >> 3) & 1)) + 2 * (kq & 1);
+    }
+    const float *bptr = lds + A_FLOATS + lane * 4;                       // tile nt + 1: + WW_B_FLOATS
+
+    float2 x[6];
+    float2 u[6];              // input combination of product j
+    float4 bw[2][2];          // weights of half-phase h = 2 j + (tile) in bw[h & 1][channel parity e]
+
+    auto load_x = [&](auto sc) {
+        constexpr int S = decltype(sc)::value;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) x[q] = *reinterpret_cast<const float2 *>(xptr[q] + S * STAGE);
+    };
+    auto load_b = [&](auto sc, auto hc) {
+        constexpr int S = decltype(sc)::value, H = decltype(hc)::value, J = H >> 1, T = H & 1;
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            bw[H & 1][e] = *reinterpret_cast<const float4 *>(bptr + S * STAGE + T * WW_B_FLOATS + (J * 2 + e) * 256);
+    };
+    // product J x column tile T: 2 steps x 4 column tiles
+    auto mfma8_u = [&](auto hc, const float2 uu) {
+        constexpr int H = decltype(hc)::value, J = H >> 1, T = H & 1;
+        f32x4 *ac = acc[J] + 4 * T;
+        const float4 b0 = bw[H & 1][0], b1 = bw[H & 1][1];
+        ac[0] = WW_MFMA(uu.x, b0.x, ac[0]);
+        ac[1] = WW_MFMA(uu.x, b0.z, ac[1]);
+        ac[2] = WW_MFMA(uu.x, b1.x, ac[2]);
+        ac[3] = WW_MFMA(uu.x, b1.z, ac[3]);
+        ac[0] = WW_MFMA(uu.y, b0.y, ac[0]);
+        ac[1] = WW_MFMA(uu.y, b0.w, ac[1]);
+        ac[2] = WW_MFMA(uu.y, b1.y, ac[2]);
+        ac[3] = WW_MFMA(uu.y, b1.w, ac[3]);
+    };
+    auto mfma8 = [&](auto hc) { mfma8_u(hc, u[decltype(hc)::value >> 1]); };
+    // the six input combinations of a slice (the expressions of wn_gate_winograd4w_kernel), all at once behind the barrier: 192
+    // accumulator registers leave no room to keep the six rows through the slice.  Ordered so that rows die as they go.
+    auto comb_all = [&]() {
+        u[0] = ww_fma(4.f, x[0], ww_fma(-5.f, x[2], x[4]));
+        u[5] = ww_fma(4.f, x[1], ww_fma(-5.f, x[3], x[5]));
+        const float2 ca = ww_fma(-4.f, x[2], x[4]), cb = ww_fma(-4.f, x[1], x[3]);
+        const float2 ea = ww_sub(x[4], x[2]), eb = ww_sub(x[3], x[1]);
+        u[1] = ww_add(ca, cb);
+        u[2] = ww_sub(ca, cb);
+        u[3] = ww_fma(2.f, eb, ea);
+        u[4] = ww_fma(-2.f, eb, ea);
+    };
+    // One slice = twelve half-phases of 8 MFMAs (one product x one column tile each).  While one is multiplied the weights of
+    // the next one are requested from LDS.  The barrier that publishes slice st + 1 sits in front of the last half-phase:
+    // every wave has requested all LDS operands of slice st by then, so its stage is free -- for slice st + 2, or behind the
+    // last slice for the conditioning rows.  In: u, bw[0] of the first half-phase.  Out: those of the next slice.
+    auto phase = [&](auto sc, auto hc) {
+        constexpr int H = decltype(hc)::value;
+        load_b(sc, ww_int<H + 1>());
+        WW_FENCE();
+        mfma8(hc);
+        WW_FENCE();
+    };
+    auto fill = [&](auto sc, int st) {
+        constexpr int S = decltype(sc)::value;
+        ww_int<(S + 1) % NSTAGE> ns;
+        phase(sc, ww_int<0>());
+        phase(sc, ww_int<1>());
+        phase(sc, ww_int<2>());
+        phase(sc, ww_int<3>());
+        phase(sc, ww_int<4>());
+        phase(sc, ww_int<5>());
+        phase(sc, ww_int<6>());
+        phase(sc, ww_int<7>());
+        phase(sc, ww_int<8>());
+        load_b(sc, ww_int<10>());
+        WW_FENCE();
+        mfma8(ww_int<9>());
+        WW_FENCE();
+        load_b(sc, ww_int<11>());
+        WW_FENCE();
+        // ---- the last product behind the barrier; slice st + 1 must have landed.  Its first half-phase covers the LDS round
+        // trip of the next slice's rows, the combinations are formed between the MFMAs of the second one
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (st + NSTAGE < nk8) issue(st + NSTAGE, S);
+        else if (st + 1 == nk8) issue_cond(S);
+        load_x(ns);
+        WW_FENCE();
+        mfma8(ww_int<10>());
+        WW_FENCE();
+        load_b(ns, ww_int<0>());
+        WW_FENCE();
+        const float2 u5 = u[5];
+        comb_all();
+        mfma8_u(ww_int<11>(), u5);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { WW_SG_MFMA(1); WW_SG_VALU(3); }
+        WW_FENCE();
+    };
+
+    // ---- everything requested so far has landed (the bias and table loads above count in vmcnt as well)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    load_x(ww_int<0>());
+    load_b(ww_int<0>(), ww_int<0>());
+    comb_all();
+    {
+        int st = 0;
+        for (; st + 2 <= nk8; st += 2) {
+            fill(ww_int<0>(), st);
+            fill(ww_int<1>(), st + 1);
+        }
+        if (st < nk8) fill(ww_int<0>(), st);
+    }
+
+    // ---- epilogue (as in wn_gate_winograd4w_kernel, one column tile after the other): the conditioning rows sit in the stage
+    // of the last slice
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const float *cl = lds + ((nk8 - 1) & 1) * STAGE;
+#pragma unroll
+    for (int vi = 0; vi < 4; ++vi) {
+        const int gi = 16 * rw + 4 * kq + vi;                                    // group held by this register
+        const int lr0 = ((gi >> log2d) << (log2d + 2)) + (gi & (d - 1));         // its first row, relative to m0
+        int etab[4];
+        float2 w[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) etab[o] = reinterpret_cast<const int *>(lds + SH::TAB)[lr0 + (o << log2d)];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) w[o] = make_float2(lds[SH::LERP + (etab[o] & 255)], lds[SH::LERP + 64 + (etab[o] & 255)]);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            const int n0c = n0 + 32 * ct;
+            const bool ch_ok = n0c + 2 * r16 < C;        // C is even: both channels of the lane exist or neither
+            float *obase = p.out + (long long)b * p.out_bstride + n0c + 2 * r16;
+            const float *clane = cl + ct * (SH::COND_ROWS * 64) + 2 * r16;
+            float2 ct0[4], ct1[4], cs0[4], cs1[4];
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                const float *c0 = clane + (etab[o] >> 8);
+                ct0[o] = *reinterpret_cast<const float2 *>(c0);
+                ct1[o] = *reinterpret_cast<const float2 *>(c0 + 64);
+                cs0[o] = *reinterpret_cast<const float2 *>(c0 + 32);
+                cs1[o] = *reinterpret_cast<const float2 *>(c0 + 96);
+            }
+            float y[4][4];                                                       // [column tile][output]
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int cc = 4 * ct + c;
+                const float s12 = acc[1][cc][vi] + acc[2][cc][vi], d12 = acc[1][cc][vi] - acc[2][cc][vi];
+                const float s34 = acc[3][cc][vi] + acc[4][cc][vi], d34 = acc[3][cc][vi] - acc[4][cc][vi];
+                y[c][0] = (acc[0][cc][vi] + s12) + s34;
+                y[c][1] = fmaf(2.f, d34, d12);
+                y[c][2] = fmaf(4.f, s34, s12);
+                y[c][3] = fmaf(8.f, d34, d12) + acc[5][cc][vi];
+            }
+            float2 res[4];
+            const int kind = GA < 0 ? p.gate_act : GA;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                res[o].x = wn_gate_act(kind, y[0][o] + fmaf(ct0[o].x, w[o].x, ct1[o].x * w[o].y), y[1][o] + fmaf(cs0[o].x, w[o].x, cs1[o].x * w[o].y));
+                res[o].y = wn_gate_act(kind, y[2][o] + fmaf(ct0[o].y, w[o].x, ct1[o].y * w[o].y), y[3][o] + fmaf(cs0[o].y, w[o].x, cs1[o].y * w[o].y));
+                asm volatile("" : "+v"(res[o].x), "+v"(res[o].y));
+            }
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                const int row = m0 + lr0 + (o << log2d);
+                if (ch_ok && row < rows) *reinterpret_cast<float2 *>(obase + (long long)row * p.ldo) = res[o];
+            }
+        }
+    }
+}
+
 // a.w must point at the host-packed F(4,3) weights (ceil(C/32), ceil(C/8), 3072) of engine.pack_winograd4w_weights;
 // split = the 128-row shape whose waves split the six products (same bits as the 256-row shape).  Returns false if the
 // layer does not fit.
-// shape: 0 = 256-row blocks, 1 = 128-row product-split blocks, 2 = product-split blocks of half a column tile
+// shape: 0 = 256-row blocks, 1 = 128-row product-split blocks, 2 = product-split blocks of half a column tile, 3 = 256-row blocks
+// of two column tiles (false where that shape does not apply: d > 16, cond_up < 10, one column tile, or
+// the device refuses its LDS size; the caller falls back to shape 0)
 bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream) {
-    const bool split = shape != 0;
+    const bool split = shape == 1 || shape == 2;
     // dilations above the halo: d = 16 s runs as s interleaved virtual items per item at dilation 16 (kernels' VS variants)
     const int vs = a.dil > WW_HALO ? a.dil / WW_HALO : 1;
     const int dil_v = vs > 1 ? WW_HALO : a.dil;
@@ -1117,7 +1459,47 @@ bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream)
     ConvArgs r = a;
     r.fast_dma = 1;                 // byte offsets are relative to the block's window (< 2^32 for any item length)
     r.vstride = vs;
+    r.tile0 = 0;
     r.n_tiles = (a.channels + 31) / 32;
+    const bool gtu = a.gate_act == 0;
+    if (shape == 3) {
+        // the CR = 28 geometry only (cond_up >= 10), here and in the one-tile blocks of an odd last tile
+        if (vs > 1 || cond_rows > WqShape::COND_ROWS || r.n_tiles < 2) return false;
+        // the LDS size is an attribute of the (function, device) pair (as in launch_wn_gate_f16)
+        static unsigned long long attr_devices = 0, attr_failed = 0;
+        int dev = -1;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+        if (!((attr_devices >> dev) & 1ull)) {
+            const int bytes = WqShape::LDS_FLOATS * (int)sizeof(float);
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_winograd4q_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
+                hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_winograd4q_kernel<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                attr_failed |= 1ull << dev;
+            }
+            attr_devices |= 1ull << dev;
+        }
+        if ((attr_failed >> dev) & 1ull) return false;
+        const int tiles = r.n_tiles;
+        ConvArgs q = r;
+        q.n_tiles = tiles / 2;                            // pairs of column tiles
+        q.m_tiles_per_item = (a.max_rows + WqShape::ROWS - 1) / WqShape::ROWS;
+        q.m_tiles_total = q.m_tiles_per_item * a.batch;
+        const dim3 gridq((unsigned)(8LL * ((q.m_tiles_total + 7) / 8) * q.n_tiles)), blkq(WqShape::THREADS);
+        const size_t ldsq = WqShape::LDS_FLOATS * sizeof(float);
+        if (gtu) hipLaunchKernelGGL(wn_gate_winograd4q_kernel<0>, gridq, blkq, ldsq, stream, q, log2d);
+        else hipLaunchKernelGGL(wn_gate_winograd4q_kernel<-1>, gridq, blkq, ldsq, stream, q, log2d);
+        if (tiles & 1) {
+            // an odd tile count: the last tile in 256 x 32 blocks (no padded tile's MFMAs)
+            r.tile0 = tiles - 1;
+            r.n_tiles = 1;
+            r.m_tiles_per_item = (a.max_rows + 255) / 256;
+            r.m_tiles_total = r.m_tiles_per_item * a.batch;
+            const dim3 grid1((unsigned)(8LL * ((r.m_tiles_total + 7) / 8)));
+            if (gtu) hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, 0>), grid1, dim3(256), 0, stream, r, log2d);
+            else hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, -1>), grid1, dim3(256), 0, stream, r, log2d);
+        }
+        return true;
+    }
     const int vrows = (a.max_rows + vs - 1) / vs;         // rows of the longest virtual item
     r.m_tiles_per_item = (vrows + rows_blk - 1) / rows_blk;
     r.m_tiles_total = r.m_tiles_per_item * a.batch * vs;
@@ -1126,7 +1508,6 @@ bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream)
     if (two) r.m_tiles_total = a.batch * (vs / 2);
     const long long blocks = 8LL * ((r.m_tiles_total + 7) / 8) * r.n_tiles;
     const dim3 blk(256);
-    const bool gtu = a.gate_act == 0;
     if (shape == 2) {
         r.n_tiles *= 2;                                   // half column tiles
         const dim3 grid2((unsigned)(8LL * ((r.m_tiles_total + 7) / 8) * r.n_tiles));

@@ -95,7 +95,7 @@ GATE_KERNEL_NAMES = {0: "none", 1: "direct", 2: "f23", 3: "f43", 4: "f43_psplit"
 class mbx_kernel_report_info(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int32), ("n_resskip_layers", ctypes.c_int32),
                 ("resskip_kernel", ctypes.c_int32 * MBX_MAX_WN_LAYERS), ("tail_kernel", ctypes.c_int32),
-                ("tail_folded", ctypes.c_int32)]
+                ("tail_folded", ctypes.c_int32), ("gate_block_channels", ctypes.c_int32 * MBX_MAX_WN_LAYERS)]
 
 
 # MBX_RESSKIP_K_* / MBX_TAIL_K_* of include/mbexwn.h (mbx_kernel_report)
@@ -360,8 +360,9 @@ def make_config(config, wavetables, conv_form=None, batch_invariant=None, keep_s
                 calib_fraction=None, tune=None, precision="f32", f0_accumulate="f64"):
     """mbx_config of a model.  Policy arguments (None = default, or the experiment variable if one is set):
     conv_form "auto" | "direct" | "f23" | "f43" (mbx_config.wn_conv_form), batch_invariant, keep_skip, keep_start,
-    calib_fraction, tune = {"gate_shape": 0|1|2|3, "resskip_wave_tiles": n, "resskip_split": 0..3}.  gate_shape 0 keeps the
-    launch-size rule; 1 | 2 | 3 pin the F(4,3) block shape (256-row | product-split | product-split of half a column tile) of
+    calib_fraction, tune = {"gate_shape": 0|1|2|3|4, "resskip_wave_tiles": n, "resskip_split": 0..3}.  gate_shape 0 keeps the
+    launch-size rule; 1 | 4 pin the F(4,3) block shape of large launches (256-row blocks of one column tile | 256-row
+    blocks of two) at every launch size, 2 | 3 that of small ones (product-split | product-split of half a column tile) for
     launches of fewer than 4 * 768 256-row blocks (csrc/mbx_forward.hip, gate_shape_policy).  resskip_wave_tiles -1: never the wave-tiled res/skip
     kernel."""
     dims = ModelDims(config)
@@ -1295,7 +1296,9 @@ class MBExWNEngine:
         gate kernel of every layer of the last forward, block-major (block b, layer l at b * n_layers + l) on a model with
         several WaveNet blocks.  From mbx_kernel_report: ``resskip_kernels``, one entry (RESSKIP_KERNEL_NAMES) per layer whose
         res/skip launch ran, in the same order (the last layer of a handle with ``fold_skip`` has none: the tail takes its
-        share), ``tail_kernel`` (TAIL_KERNEL_NAMES) and ``tail_folded``."""
+        share), ``tail_kernel`` (TAIL_KERNEL_NAMES), ``tail_folded`` and ``gate_block_channels``: per entry of ``gate_kernels``
+        the gate channels of one F(4,3) block (64: blocks of two column tiles, 32: of one, 16: of half a tile; 0: no F(4,3)
+        block ran the layer)."""
         info = mbx_conv_form_info()
         info.struct_size = ctypes.sizeof(mbx_conv_form_info)
         _check(self._lib.mbx_conv_form(self._handle, ctypes.byref(info)))
@@ -1315,7 +1318,14 @@ class MBExWNEngine:
                 "split_rejected": bool(info.split_rejected), "f0_float64_chain": bool(info.f0_float64_chain),
                 "gate_kernels": [GATE_KERNEL_NAMES[info.gate_kernel[ll]] for ll in range(info.n_gate_layers)],
                 "resskip_kernels": [kk for kk in resskip if kk != "none"],
-                "tail_kernel": TAIL_KERNEL_NAMES[rep.tail_kernel], "tail_folded": bool(rep.tail_folded)}
+                "tail_kernel": TAIL_KERNEL_NAMES[rep.tail_kernel], "tail_folded": bool(rep.tail_folded),
+                "gate_block_channels": [int(rep.gate_block_channels[ll]) for ll in range(info.n_gate_layers)]}
+
+    def kernel_report(self):
+        """What the most recent forward ran, per layer: ``gate_kernels``, ``gate_block_channels``, ``resskip_kernels``,
+        ``tail_kernel`` and ``tail_folded`` of :meth:`conv_form_info`."""
+        info = self.conv_form_info()
+        return {kk: info[kk] for kk in ("gate_kernels", "gate_block_channels", "resskip_kernels", "tail_kernel", "tail_folded")}
 
     def calibrate(self, mel, n_frames=None, noise=None):
         """mbx_calibrate: repeat the form calibration on the caller's own mel batch (device tensors as for
@@ -1350,8 +1360,10 @@ class MBExWNEngine:
         half_blocks = ((rows + 127) // 128) * batch * tiles
         if info["batch_invariant"]:
             return "winograd_f43"
+        if self._tune_gate_shape in (1, 4):        # the two shapes of large launches (one | two column tiles per block), at every size
+            return "winograd_f43"
         if self._tune_gate_shape and full_blocks < 4 * 768:
-            return {1: "winograd_f43", 2: "winograd_f43_psplit", 3: "winograd_f43_hsplit"}[self._tune_gate_shape]
+            return {2: "winograd_f43_psplit", 3: "winograd_f43_hsplit"}[self._tune_gate_shape]
         load_full, load_half = (full_blocks + 255) // 256, 0.5 * ((half_blocks + 255) // 256)
         if full_blocks <= 1024 and load_half <= load_full:
             return "winograd_f43_hsplit" if half_blocks <= 256 < 2 * half_blocks else "winograd_f43_psplit"

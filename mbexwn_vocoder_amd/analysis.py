@@ -94,6 +94,31 @@ def compute_log_mel(sound, preprocess_config, dtype=np.float32):
     return mell, preprocess_config["sample_rate"] / preprocess_config["hop_size"]
 
 
+def compute_log_mel_at(sound, centres, preprocess_config, dtype=np.float32):
+    """:func:`compute_log_mel` with the frames centred where ``centres`` says (timemap.py): the host
+    definition of ``mbxw_mel_frames_at``.  ``sound``: (time,) or (batch, time); ``centres``: (K,) for all items or
+    (batch, K), integers, clipped to [0, time].  Frame k of an item holds the ``win`` samples of the reflect-padded sound
+    from ``c - win // 2`` on and goes through the numpy steps of :func:`stft_magnitude` and :func:`compute_log_mel`:
+    centres ``k * hop`` therefore give ``compute_log_mel``'s bits.  Returns (batch, K, mel_channels) and the frame rate."""
+    cfg = preprocess_config
+    sound = np.atleast_2d(np.asarray(sound))
+    win_len, fft_size = int(cfg.get("win_size", cfg["fft_size"])), int(cfg["fft_size"])
+    cc = np.asarray(centres)
+    if cc.dtype.kind not in "iu" or cc.ndim not in (1, 2):
+        raise ValueError("compute_log_mel_at: centres must be an integer array (K,) or (batch, K)")
+    cc = np.clip(np.broadcast_to(np.atleast_2d(cc).astype(np.int64), (sound.shape[0], cc.shape[-1])), 0, sound.shape[-1])
+    win = hann_symmetric(win_len).astype(dtype)
+    xp = np.pad(sound.astype(dtype, copy=False), ((0, 0), (win_len // 2, win_len)), mode="reflect")
+    spec = np.empty((sound.shape[0], cc.shape[1], fft_size // 2 + 1), dtype=dtype)
+    for ii in range(cc.shape[1]):
+        seg = xp[np.arange(sound.shape[0])[:, None], cc[:, ii, None] + np.arange(win_len)[None, :]]
+        spec[:, ii] = np.abs(np.fft.rfft(win * seg, fft_size))
+    basis = mel_basis_slaney(cfg["sample_rate"], fft_size, cfg["mel_channels"], cfg["fmin"], cfg["fmax"], dtype=dtype)
+    mel = np.dot(spec, basis.T)
+    mell = np.log(np.fmax(mel, np.finfo(mel.dtype).eps))
+    return mell, cfg["sample_rate"] / cfg["hop_size"]
+
+
 def mel_analysis_tables(preprocess_config):
     """The tables :func:`compute_log_mel_device` uploads, as numpy arrays: the float32 analysis window (win,), the twiddles
     exp(-2 pi i m / fft_size) as (fft_size / 2, 2) float32, the float32 mel basis (mel_channels, fft_size / 2 + 1) and the
@@ -145,6 +170,42 @@ def compute_log_mel_device(sound, preprocess_config, n_samples=None):
     return out, cfg["sample_rate"] / hop
 
 
+def compute_log_mel_device_at(sound, n_samples, centres, n_frames, preprocess_config):
+    """:func:`compute_log_mel_at` on the GPU (csrc/mel_warp.hip through ``mbxw_mel_frames_at``, include/mbexwn_warp.h):
+    ``sound`` float32 cuda (batch, stride), ``n_samples`` int32 cuda (batch,), ``centres`` int64 cuda (batch, max_frames),
+    ``n_frames`` int32 cuda (batch,).  Returns a cuda tensor (batch, max_frames, mel_channels) -- rows of item b from
+    ``n_frames[b]`` on are not written (they stay zero) -- and the mel frame rate.  A row carries the bits of the row
+    :func:`compute_log_mel_device` computes for a frame with the same samples in front of it."""
+    import ctypes
+    import torch
+    from .engine import _check, load_library
+    if sound.dim() != 2 or sound.dtype != torch.float32 or not sound.is_cuda:
+        raise ValueError("sound must be a float32 cuda tensor of shape (batch, time)")
+    cfg = preprocess_config
+    win_len = int(cfg.get("win_size", cfg["fft_size"]))
+    fft_size, n_mels = int(cfg["fft_size"]), int(cfg["mel_channels"])
+    dev = sound.device
+    sound = sound.contiguous()
+    B, N = int(sound.shape[0]), int(sound.shape[1])
+    for name, tt in (("n_samples", n_samples), ("n_frames", n_frames)):
+        if tt.dtype != torch.int32 or tuple(tt.shape) != (B,) or tt.device != dev:
+            raise ValueError(f"{name} must be an int32 tensor of shape (batch,) on the device of sound")
+    if centres.dtype != torch.int64 or centres.dim() != 2 or int(centres.shape[0]) != B or centres.device != dev:
+        raise ValueError("centres must be an int64 tensor of shape (batch, max_frames) on the device of sound")
+    n_samples, n_frames, centres = n_samples.contiguous(), n_frames.contiguous(), centres.contiguous()
+    frames = int(centres.shape[1])
+    tables = [torch.as_tensor(np.ascontiguousarray(tt), device=dev) for tt in mel_analysis_tables(cfg)]
+    out = torch.zeros((B, frames, n_mels), dtype=torch.float32, device=dev)
+    # no handle, hence no device of its own: the launch goes to the CURRENT device, which must be the buffers' device
+    with torch.cuda.device(dev):
+        _check(load_library().mbxw_mel_frames_at(sound.data_ptr(), N, B, n_samples.data_ptr(), centres.data_ptr(),
+                                                 n_frames.data_ptr(), frames, win_len, fft_size, n_mels, tables[0].data_ptr(),
+                                                 tables[1].data_ptr(), tables[2].data_ptr(), tables[3].data_ptr(),
+                                                 tables[4].data_ptr(), ctypes.c_float(float(np.finfo(np.float32).eps)),
+                                                 out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return out, cfg["sample_rate"] / int(cfg["hop_size"])
+
+
 def mell_header(preprocess_config):
     """The entries of a ``.mell`` dictionary apart from ``mell`` itself (reference bin/generate_mel.py:41-52)."""
     cfg = preprocess_config
@@ -167,7 +228,14 @@ def _add(stats, key, seconds):
         stats[key] = stats.get(key, 0.0) + seconds
 
 
-def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None):
+def resampled_length(n, rate, target):
+    """Samples of an n-sample sound at ``rate`` once it is at ``target``: ceil(n * up / down), as both resamplers give."""
+    from math import gcd
+    gg = gcd(int(rate), int(target))
+    return -(-int(n) * (int(target) // gg) // (int(rate) // gg))
+
+
+def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None, time_maps=None, rows_per_frame=1):
     """Sounds -> ``.mell`` dictionaries (reference bin/generate_mel.py:54-64 for a list of files): ``sounds`` is a list of 1-D
     float32 arrays, ``rates`` their sample rates.  A sound that is not at the model rate goes through the reference's resampler
     (resample.py); one already at it skips that step.  Needs the ``preprocess_config`` alone: no engine, no weights.
@@ -176,9 +244,15 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     ``resample_device`` straight into ``compute_log_mel_device`` (the lengths stay on the device), with one copy back per
     micro-batch; an item's bits do not depend on the batch it ran in.  Otherwise numpy, one item at a time (``resample_host``,
     ``compute_log_mel``).  ``stats``: a dict that collects seconds per step (resample, analysis, upload, copy_back); on the
-    device that costs one wait per micro-batch."""
+    device that costs one wait per micro-batch.
+
+    ``time_maps``: per sound None, a factor or a breakpoint array (timemap.py): the item's frames lie
+    on ``timemap.centres`` of its length at the model rate (``resampled_length``, which the host knows), K of them, and the
+    ``.mell`` has K columns.  A micro-batch with such an item goes through ``compute_log_mel_device_at`` (on the host:
+    ``compute_log_mel_at``), its other items on their regular centres, which gives them the regular analysis's bits; a
+    call without maps makes the launches it made before there were any.  ``rows_per_frame``: ``timemap.centres``' limit."""
     import time
-    from . import resample
+    from . import resample, timemap
     cfg = preprocess_config
     target, hop = int(cfg["sample_rate"]), int(cfg["hop_size"])
     win_len = int(cfg.get("win_size", cfg["fft_size"]))
@@ -190,13 +264,20 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
         if ss.ndim != 1 or ss.size == 0:
             raise ValueError(f"generate_mels: sound {ii} must be a non-empty 1-D array, got shape {ss.shape}")
     out = [None] * len(sounds)
+    maps = timemap.per_item(list(time_maps) if time_maps is not None else None, len(sounds), "generate_mels: time_maps")
+    # every map is checked, and its centres are made, before anything runs
+    warped = {ii: timemap.centres(resampled_length(sounds[ii].size, rates[ii], target), hop, target, mm, rows_per_frame)
+              for ii, mm in enumerate(maps) if mm is not None}
     if not on_device:
         for ii, (ss, rr) in enumerate(zip(sounds, rates)):
             t0 = time.perf_counter()
             if rr != target:
                 ss = resample.resample_host(ss, rr, target)
             t1 = time.perf_counter()
-            mel, _ = compute_log_mel(ss[np.newaxis], cfg, dtype=np.float32)
+            if ii in warped:
+                mel, _ = compute_log_mel_at(ss[np.newaxis], warped[ii], cfg, dtype=np.float32)
+            else:
+                mel, _ = compute_log_mel(ss[np.newaxis], cfg, dtype=np.float32)
             _add(stats, "resample", t1 - t0)
             _add(stats, "analysis", time.perf_counter() - t1)
             out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[0].T))
@@ -231,7 +312,17 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
                 snd = torch.nn.functional.pad(snd, (0, win_len // 2 + 1 - snd.shape[1]))
             if marks:
                 marks[2].record()
-            mel_dev, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
+            if any(ii in warped for ii in group):
+                cents = [warped[ii] if ii in warped else timemap.centres(nn, hop, target, None) for ii, nn in zip(group, lengths)]
+                table = np.zeros((len(group), max(cc.size for cc in cents)), dtype=np.int64)
+                for bb, cc in enumerate(cents):
+                    table[bb, :cc.size] = cc
+                counts = [int(cc.size) for cc in cents]
+                mel_dev, _ = compute_log_mel_device_at(snd, n_dev, torch.as_tensor(table).to(dev),
+                                                       torch.as_tensor(np.asarray(counts, dtype=np.int32)).to(dev), cfg)
+            else:
+                counts = [nn // hop + 1 for nn in lengths]
+                mel_dev, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
             if marks:
                 marks[3].record()
                 marks[3].synchronize()
@@ -242,5 +333,5 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
                 for key, first in (("upload", 0), ("resample", 1), ("analysis", 2)):
                     _add(stats, key, marks[first].elapsed_time(marks[first + 1]) * 1e-3)
             for bb, ii in enumerate(group):
-                out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[bb, :lengths[bb] // hop + 1].T))
+                out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[bb, :counts[bb]].T))
     return out

@@ -367,6 +367,17 @@ def file_factors(files, transposition=1.0, table=None):
     return factors
 
 
+def file_stretches(files, stretch=1.0, table=None):
+    """The time-stretch factor of every file: ``table[basename]`` (read_transposition_file: ``--time-stretch-file`` has the
+    format of ``--transposition-file``) where it is listed, else ``stretch``; every factor finite and positive, or
+    ValueError."""
+    table = table or {}
+    factors = [float(table.get(os.path.basename(ff), stretch)) for ff in files]
+    if not all(np.isfinite(ff) and ff > 0 for ff in factors):
+        raise ValueError("time stretch must be finite and positive")
+    return factors
+
+
 def read_sound(path):
     """``audioio.read_audio`` for the file-to-file tool: (samples, rate), or ValueError for what the tool skips -- a file
     with more than one channel, without samples or with an invalid rate."""
@@ -380,7 +391,7 @@ def read_sound(path):
 
 
 def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
-                  quiet=False, flac_compression="verbatim", out_rate=None):
+                  quiet=False, flac_compression="verbatim", out_rate=None, stretches=None):
     """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
     ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
 
@@ -390,8 +401,14 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     basename --, ``factors[i]`` on every frame of file i, the output resampler and the FLAC frames), writer pool.  A file
     gives frames * hop samples at the model rate before the output resampler, as a live stream of it emits.
     ``out_rate``: a rate in Hz, ``"input"`` (every file at its own rate) or None (the model rate).  Nothing is replayed and
-    nothing depends on ``mine``: a file's audio is a function of the file, the model, the seed, its factor and the rate."""
-    from .analysis import generate_mels
+    nothing depends on ``mine``: a file's audio is a function of the file, the model, the seed, its factor and the rate.
+
+    ``stretches``: a time-stretch factor per file (timemap.py), None = 1 for all.  File i is analysed
+    at the centres of ``timemap.centres`` for ``stretches[i]`` and gives K_i * hop samples, ``stretches[i]`` times as long
+    at the same pitch.  With every factor 1 the job makes the launches and writes the bytes it does without the argument.  A
+    file whose stretched length exceeds the engine's limit is reported and skipped like the unreadable ones."""
+    from . import timemap
+    from .analysis import generate_mels, resampled_length
     from .mel_inverter import KeyedNoise
     from .noise import item_key
     t_start = time.perf_counter()
@@ -423,11 +440,22 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
         loaded = dict(zip(mine, pool.map(read, mine)))
         skipped = [(files[ii], str(loaded[ii])) for ii in mine if isinstance(loaded[ii], ValueError)]
         mine = [ii for ii in mine if not isinstance(loaded[ii], ValueError)]
+        # a factor of exactly 1 is the regular analysis; every other one is checked against the engine's limit here
+        maps = {ii: None if stretches is None or float(stretches[ii]) == 1.0 else float(stretches[ii]) for ii in mine}
+        for ii in [ii for ii in mine if maps[ii] is not None]:
+            try:
+                timemap.frame_count(resampled_length(loaded[ii][0].size, loaded[ii][1], inv.srate), inv.hop_size, inv.srate,
+                                    maps[ii], inv.model.dims.steps_per_frame)
+            except ValueError as err:
+                skipped.append((files[ii], str(err)))
+                mine.remove(ii)
         for name, why in skipped:
             log([f"transform_audio::error:: skipped {name}: {why}"])
         stats = {}
         dicts = generate_mels([loaded[ii][0] for ii in mine], [loaded[ii][1] for ii in mine], inv.preprocess_config,
-                              on_device=True, batch=max(1, batch), stats=stats) if mine else []
+                              on_device=True, batch=max(1, batch), stats=stats,
+                              time_maps=None if all(maps[ii] is None for ii in mine) else [maps[ii] for ii in mine],
+                              rows_per_frame=inv.model.dims.steps_per_frame) if mine else []
         scaled = dict(zip(mine, pool.map(scale, dicts)))
     dims = inv.model.dims
     device_flac = fmt.lower() == "flac" and not have_soundfile()
@@ -453,7 +481,9 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
         wall = time.perf_counter() - t_start
         sec = clock.seconds
         audio_s = sum(int(scaled[ii].shape[1]) for ii in mine) * inv.hop_size / inv.srate
-        print(f"transform_audio: {len(mine)} files, {audio_s:.1f} s of audio in {wall:.2f} s wall ({audio_s / max(wall, 1e-9):.1f} "
+        in_s = sum(loaded[ii][0].size / loaded[ii][1] for ii in mine)
+        stretched = "" if all(maps[ii] is None for ii in mine) else f" (time-stretched from {in_s:.1f} s of input)"
+        print(f"transform_audio: {len(mine)} files, {audio_s:.1f} s of audio{stretched} in {wall:.2f} s wall ({audio_s / max(wall, 1e-9):.1f} "
               f"x real time); read {sec.get('read', 0.0):.2f} s, upload {stats.get('upload', 0.0):.3f} s, resample "
               f"{stats.get('resample', 0.0):.3f} s, analysis {stats.get('analysis', 0.0):.3f} s, mel copy-back "
               f"{stats.get('copy_back', 0.0):.3f} s, scale_mel {sec.get('scale', 0.0):.2f} s, noise+forward "
@@ -462,21 +492,31 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     return skipped
 
 
-def plan_audio_ranks(files, ranks, threads=2):
+def plan_audio_ranks(files, ranks, threads=2, stretches=None, frame_limit=None):
     """What the parent of a ``transform_audio.py --gpus N`` job decides before it starts its ranks, without importing torch:
     the visible GPUs, the files it skips -- (file, reason) pairs, ``read_sound`` -- and the LPT partition of the others by
-    duration.  ``files`` in the plan are the ones the ranks share out."""
-    def seconds_of(path):
+    duration times ``stretches[i]`` (the seconds the file comes out with; None = 1 for all).  ``files`` in the plan are the
+    ones the ranks share out.  ``frame_limit``: (hop, model rate, sub-band rows per frame) -- a file whose stretched length
+    exceeds the engine's limit (``timemap.frame_count``) is skipped here, as ``run_audio_job`` would skip it."""
+    from . import timemap
+    from .analysis import resampled_length
+
+    def seconds_of(item):
+        path, factor = item
         try:
             snd, rate = read_sound(path)
+            if frame_limit is not None and factor != 1.0:
+                hop, target, rows = frame_limit
+                timemap.frame_count(resampled_length(snd.size, rate, target), hop, target, factor, rows)
             return snd.size / rate
         except ValueError as err:
             return err
 
+    factors = [1.0] * len(files) if stretches is None else [float(ff) for ff in stretches]
     with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
-        seconds = list(pool.map(seconds_of, files))
+        seconds = list(pool.map(seconds_of, zip(files, factors)))
     good = [ii for ii, ss in enumerate(seconds) if not isinstance(ss, ValueError)]
-    cost = [int(np.ceil(seconds[ii] * 1000)) for ii in good]
+    cost = [int(np.ceil(seconds[ii] * factors[ii] * 1000)) for ii in good]
     return {"devices": visible_gpu_count(), "files": [files[ii] for ii in good], "shards": lpt_partition(cost, ranks),
             "skipped": [[files[ii], str(ss)] for ii, ss in enumerate(seconds) if isinstance(ss, ValueError)]}
 

@@ -9,6 +9,9 @@ Deviations (documented in INTEGRATION.md):
   * a file with more than one channel is refused by name (the reference raises there too)
   * additionally ``--batch N`` (padded micro-batches per input rate through the device resampler and the device analysis),
     ``-nt`` (reader / writer threads), ``--host`` (numpy analysis and host resampler, no GPU needed), ``-v``, ``-q``
+  * additionally ``--time-stretch F``: the frames lie at the positions of a sound F times as long (timemap.py, DESIGN.md
+    section 6f), the file has the reference's dictionary with K columns, and resynth_mel.py synthesises it F times as long at
+    the same pitch; with ``--host`` too
   * without ``--host`` and without a GPU the script fails loudly; there is no ``--gpus``
 """
 import os
@@ -23,13 +26,23 @@ if os.path.exists(test_path):
 from mbexwn_vocoder_amd import get_config_file, list_models  # noqa: E402
 from mbexwn_vocoder_amd.analysis import generate_mels  # noqa: E402
 from mbexwn_vocoder_amd.audioio import read_audio  # noqa: E402
-from mbexwn_vocoder_amd.config import read_config  # noqa: E402
+from mbexwn_vocoder_amd.config import ModelDims, read_config  # noqa: E402
 from mbexwn_vocoder_amd.fileio import save_var  # noqa: E402
+from mbexwn_vocoder_amd.timemap import check_factor  # noqa: E402
 
 
-def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2, host=False, verbose=False, quiet=False):
+def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2, host=False, verbose=False, quiet=False,
+         time_stretch=1.0):
     config_file = get_config_file(model_id_or_path=model_id)
-    preprocess_config = read_config(config_file=config_file)['preprocess_config']
+    config = read_config(config_file=config_file)
+    preprocess_config = config['preprocess_config']
+    try:
+        time_stretch = check_factor(time_stretch, "--time-stretch")
+        # a stretched file is made for resynth_mel.py: held to the limit of the model's engine (sub-band rows per frame)
+        rows_per_frame = ModelDims(config).steps_per_frame if time_stretch != 1.0 else 1
+    except ValueError as err:
+        print(f"generate_mel::error:: {err}", file=sys.stderr)
+        sys.exit(1)
     missing = [ff for ff in input_audio_files if not os.path.isfile(ff)]
     if missing:
         print(f"generate_mel::error:: no such file: {', '.join(missing)}", file=sys.stderr)
@@ -71,8 +84,13 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
             if not quiet:
                 for ff in files:
                     print(f"process {ff}", file=sys.stderr)
-            mells = generate_mels([ll[0] for ll in loaded], [ll[1] for ll in loaded], preprocess_config, on_device=not host,
-                                  batch=batch, stats=stats)
+            try:
+                mells = generate_mels([ll[0] for ll in loaded], [ll[1] for ll in loaded], preprocess_config, on_device=not host,
+                                      batch=batch, stats=stats, rows_per_frame=rows_per_frame,
+                                      time_maps=None if time_stretch == 1.0 else [time_stretch] * len(loaded))
+            except ValueError as err:
+                print(f"generate_mel::error:: {err}", file=sys.stderr)
+                sys.exit(1)
             for ff, ll, dd in zip(files, loaded, mells):
                 outfile = os.path.join(output_dir, os.path.splitext(os.path.basename(ff))[0] + ".mell")
                 samples += ll[0].size / ll[1]
@@ -105,6 +123,8 @@ if __name__ == "__main__":
                         help="analyse up to N files per launch, grouped by input rate, in padded micro-batches "
                              "(Def: %(default)s = one file at a time)")
     parser.add_argument("-nt", "--num_threads", default=2, type=int, help="reader and writer threads (Def: %(default)s)")
+    parser.add_argument("--time-stretch", dest="time_stretch", default=1.0, type=float, metavar="F",
+                        help="place the frames for a sound F times as long at the same pitch (Def: %(default)s)")
     parser.add_argument("--host", action="store_true", help="numpy analysis and host resampler; needs no GPU")
     parser.add_argument("-v", "--verbose", action="store_true", help="display verbose progress info")
     parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")

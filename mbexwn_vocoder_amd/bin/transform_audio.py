@@ -2,7 +2,8 @@
 """Transpose sound files in batches: sound files in, transposed sound files out, on the MI355X HIP path.
 
     transform_audio.py FILES... -o DIR --model_id VOICE [--transposition F | --transposition-file LIST] [--noise-seed S]
-                       [--batch N] [--gpus N] [--out-rate R|input] [--format flac] [--flac-compression fixed]
+                       [--time-stretch F | --time-stretch-file LIST] [--batch N] [--gpus N] [--out-rate R|input]
+                       [--format flac] [--flac-compression fixed]
 
 Joins the stages of generate_mel.py and resynth_mel.py in one process (mbexwn_vocoder_amd/batched.py::run_audio_job): the
 device resampler and mel analysis, scale_mel on the host, the synthesis in padded micro-batches with the factor on every mel
@@ -16,6 +17,11 @@ arguments, the number of ranks or the other files of the job, and on an f23 engi
 A file gives frames * hop samples at the model rate before the output resampler (frames = resampled length // hop + 1), as
 the live path emits: the output is not trimmed to the input's length.  A file without samples or with more than one channel
 is reported and skipped; the others are written and the exit status is 1.
+
+--time-stretch F makes a file F times as long at the same pitch (mbexwn_vocoder_amd/timemap.py): the
+analysis places its frames at the warped positions of the sound (include/mbexwn_warp.h) and the file gives K * hop samples
+for the K frames of the time map.  A factor of 1 is the regular analysis.  A file whose stretched length exceeds the engine's
+limit is reported and skipped like the others.
 """
 import json
 import os
@@ -26,15 +32,17 @@ if os.path.exists(test_path):
     sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
 
 from mbexwn_vocoder_amd import list_models  # noqa: E402
-from mbexwn_vocoder_amd.batched import file_factors, read_transposition_file  # noqa: E402
+from mbexwn_vocoder_amd.batched import file_factors, file_stretches, read_transposition_file  # noqa: E402
 
 
 def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, transposition_file=None, noise_seed=0, batch=16,
          gpus=1, num_threads=2, out_rate=None, format="flac", flac_compression="verbatim", conv_form="auto",
-         batch_invariant=False, verbose=False, quiet=False, rank=None, job=None):
+         batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None):
     try:
         table = read_transposition_file(transposition_file) if transposition_file else None
         factors = file_factors(input_audio_files, transposition, table)
+        stretches = file_stretches(input_audio_files, time_stretch,
+                                   read_transposition_file(time_stretch_file) if time_stretch_file else None)
     except (OSError, ValueError) as err:
         print(f"transform_audio::error:: {err}", file=sys.stderr)
         sys.exit(1)
@@ -50,13 +58,19 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
     if gpus > 1 and rank is None:
         # --gpus N: this parent never initialises HIP; N fresh child processes write their share of the files each
         from mbexwn_vocoder_amd.batched import plan_audio_ranks, run_ranks
-        plan = plan_audio_ranks(input_audio_files, gpus, threads=num_threads)
+        from mbexwn_vocoder_amd import get_config_file
+        from mbexwn_vocoder_amd.config import ModelDims, read_config
+        dims = ModelDims(read_config(config_file=get_config_file(model_id_or_path=model_id)))
+        plan = plan_audio_ranks(input_audio_files, gpus, threads=num_threads, stretches=stretches,
+                                frame_limit=(dims.hop_size, dims.sample_rate, dims.steps_per_frame))
         for name, why in plan["skipped"]:
             print(f"transform_audio::error:: skipped {name}: {why}", file=sys.stderr)
         argv = [*plan["files"], "-o", output_dir, "--model_id", model_id, "--transposition", repr(float(transposition)),
                 "--noise-seed", str(noise_seed), "--batch", str(batch), "-nt", str(num_threads), "--format", format,
                 "--flac-compression", flac_compression, "--conv-form", conv_form]
         argv += ["--transposition-file", transposition_file] if transposition_file else []
+        argv += ["--time-stretch", repr(float(time_stretch))] if time_stretch != 1.0 else []
+        argv += ["--time-stretch-file", time_stretch_file] if time_stretch_file else []
         argv += ["--out-rate", str(out_rate)] if out_rate else []
         argv += [flag for flag, on in (("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant)) if on]
         status = run_ranks(os.path.abspath(__file__), argv, model_id, plan["files"], gpus, threads=num_threads, quiet=quiet,
@@ -80,7 +94,8 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
     os.makedirs(output_dir, exist_ok=True)
     skipped = run_audio_job(inv, input_audio_files, output_dir, format, factors=factors, noise_seed=noise_seed,
                             mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose,
-                            quiet=quiet, flac_compression=flac_compression, out_rate=out_rate)
+                            quiet=quiet, flac_compression=flac_compression, out_rate=out_rate,
+                            stretches=None if all(ss == 1.0 for ss in stretches) else stretches)
     if skipped:
         sys.exit(1)
 
@@ -90,6 +105,16 @@ def factor_arg(text):
     from argparse import ArgumentTypeError
     try:
         file_factors(["x"], float(text))
+    except ValueError:
+        raise ArgumentTypeError(f"a finite positive factor is expected, got {text!r}") from None
+    return float(text)
+
+
+def stretch_arg(text):
+    """argparse type of --time-stretch: a finite positive factor."""
+    from argparse import ArgumentTypeError
+    try:
+        file_stretches(["x"], float(text))
     except ValueError:
         raise ArgumentTypeError(f"a finite positive factor is expected, got {text!r}") from None
     return float(text)
@@ -122,6 +147,11 @@ def make_parser():
     parser.add_argument("--transposition-file", dest="transposition_file", default=None, metavar="LIST",
                         help="text file with lines `basename factor`: the factor of the files it lists, instead of "
                              "--transposition")
+    parser.add_argument("--time-stretch", dest="time_stretch", default=1.0, type=stretch_arg, metavar="F",
+                        help="factor on the duration at the same pitch: the output lasts F times as long (Def: %(default)s)")
+    parser.add_argument("--time-stretch-file", dest="time_stretch_file", default=None, metavar="LIST",
+                        help="text file with lines `basename factor`: the time-stretch factor of the files it lists, instead "
+                             "of --time-stretch")
     parser.add_argument("--noise-seed", dest="noise_seed", default=0, type=int, metavar="S",
                         help="seed of the keyed noise: a file's noise is a function of (S, its basename, the step) "
                              "(Def: %(default)s)")

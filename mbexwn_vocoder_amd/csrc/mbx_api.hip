@@ -10,6 +10,7 @@
 #include "../../include/mbexwn_live_out.h"
 #include "../../include/mbexwn_flac.h"
 #include "../../include/mbexwn_noise.h"
+#include "../../include/mbexwn_warp.h"
 
 static_assert(MBXN_FILL_TILE == mbx::NOISE_TILE, "mbexwn_noise.h states the tile of noise_keyed.hip");
 static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
@@ -522,6 +523,36 @@ mbx_status mbxn_fill_normal(float *out, int64_t stride, int32_t batch, const uin
     if (const char *why = mbx::check_fill_normal(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("fill normal: ") + why);
     if (batch == 0 || max_count == 0) return MBX_OK;
     mbx::launch_fill_normal(a, static_cast<hipStream_t>(hip_stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxw_mel_frames_at(const float *audio, int64_t stride, int32_t batch, const int32_t *n_samples,
+                              const int64_t *centres, const int32_t *n_frames, int32_t max_frames, int32_t win,
+                              int32_t fft_size, int32_t n_mels, const float *window, const float *twiddle, const float *basis,
+                              const int32_t *bin_lo, const int32_t *bin_hi, float eps, float *out, void *hip_stream) {
+    mbx::MelWarpArgs a{};
+    a.audio = audio;
+    a.stride = stride;
+    a.batch = batch;
+    a.n_samples = n_samples;
+    a.centres = centres;
+    a.n_frames = n_frames;
+    a.max_frames = max_frames;
+    a.win = win;
+    a.fft_size = fft_size;
+    a.n_mels = n_mels;
+    a.window = window;
+    a.twiddle = twiddle;
+    a.basis = basis;
+    a.bin_lo = bin_lo;
+    a.bin_hi = bin_hi;
+    a.eps = eps;
+    a.out = out;
+    if (const char *why = mbx::check_mel_warp(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("mel frames at: ") + why);
+    if (batch == 0) return MBX_OK;
+    mbx::launch_mel_warp(a, static_cast<hipStream_t>(hip_stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

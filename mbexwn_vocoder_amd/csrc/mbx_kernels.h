@@ -467,6 +467,27 @@ struct NoiseArgs {
 const char *check_fill_normal(const NoiseArgs &a);
 void launch_fill_normal(const NoiseArgs &a, hipStream_t stream);
 
+// log-mel frames at arbitrary centre samples (mel_warp.hip; include/mbexwn_warp.h: mbxw_mel_frames_at): mel_analysis.hip's
+// frame with its position read from a table; tables from the host module analysis.py
+struct MelWarpArgs {
+    const float *audio;          // (batch, stride)
+    long long stride;
+    int batch;
+    const int32_t *n_samples;    // (batch), clamped in the kernel to [0, stride]
+    const int64_t *centres;      // (batch, max_frames), clamped in the kernel to [0, n_samples[b]]
+    const int32_t *n_frames;     // (batch): rows k >= n_frames[b] are not written
+    int max_frames;
+    int win, fft_size, n_mels;
+    const float *window, *twiddle, *basis;
+    const int *bin_lo, *bin_hi;
+    float eps;
+    float log_eps;               // float32 nearest to log(eps); launch_mel_warp fills it in
+    float *out;                  // (batch, max_frames, n_mels)
+};
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_mel_warp(const MelWarpArgs &a);
+void launch_mel_warp(const MelWarpArgs &a, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // optional RMS normalisation of the mel input / de-normalisation of the audio (norm_mel.hip)
 // ---------------------------------------------------------------------------------------------

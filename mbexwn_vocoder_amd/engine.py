@@ -230,6 +230,9 @@ def load_library():
     # include/mbexwn_noise.h (NOISE_SYMBOLS)
     lib.mbxn_fill_normal.restype = i32
     lib.mbxn_fill_normal.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, vp]
+    # include/mbexwn_warp.h (WARP_SYMBOLS)
+    lib.mbxw_mel_frames_at.restype = i32
+    lib.mbxw_mel_frames_at.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, i32, i32, i32, fp, fp, fp, vp, vp, ctypes.c_float, fp, vp]
     _lib = lib
     return lib
 
@@ -257,6 +260,9 @@ LIVE_OUT_SYMBOLS = ["mbxo_resample_emit"]
 
 # include/mbexwn_noise.h: the keyed normal noise (prefix mbxn_; the six lists above stay as they are)
 NOISE_SYMBOLS = ["mbxn_fill_normal"]
+
+# include/mbexwn_warp.h: the mel analysis at arbitrary frame positions (prefix mbxw_; the seven lists above stay as they are)
+WARP_SYMBOLS = ["mbxw_mel_frames_at"]
 
 
 def _check(status):

@@ -295,7 +295,7 @@ class MELInverter(object):
         return out
 
     def transform_audio(self, sounds, rates, names, transposition=1.0, noise_seed=0, out_rate=None, max_batch=16,
-                        max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim"):
+                        max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None):
         """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
         keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
         factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
@@ -303,14 +303,24 @@ class MELInverter(object):
         ``out_rate`` / ``flac`` as there.  Item i has ``frames_i * hop_size`` samples at the model rate before the output
         resampler (frames_i = resampled length // hop_size + 1), as a live stream of it emits: not trimmed to its input.
 
-        An item's audio is a function of (sound, rate, name, factor, seed, out_rate): with a ``batch_invariant`` engine or
-        one pinned to a convolution form it does not depend on the batch, the order or the other items."""
+        ``time_stretch``: a change of duration at the same pitch (timemap.py) -- None, one factor or
+        one breakpoint array for all items, or a list with one of these per item.  The analysis then places item i's frames
+        on ``timemap.centres`` of its resampled length, K_i of them, and the item has ``K_i * hop_size`` samples at the model
+        rate before the output resampler; the transposition rows, the keyed noise (counted by output step), ``out_rate``
+        and ``flac`` work on those frames as on any others.
+
+        An item's audio is a function of (sound, rate, name, factor, stretch, seed, out_rate): with a ``batch_invariant``
+        engine or one pinned to a convolution form it does not depend on the batch, the order or the other items."""
+        from . import timemap
         from .analysis import generate_mels
         from .noise import item_key
         factors = check_factors(transposition, len(sounds))
         if not (len(sounds) == len(rates) == len(names)):
             raise ValueError("transform_audio: one rate and one name per sound")
-        dicts = generate_mels(sounds, rates, self.preprocess_config, on_device=True, batch=max_batch)
+        maps = timemap.per_item(time_stretch, len(sounds), "transform_audio: time_stretch")
+        dicts = generate_mels(sounds, rates, self.preprocess_config, on_device=True, batch=max_batch,
+                              time_maps=None if all(mm is None for mm in maps) else maps,
+                              rows_per_frame=self.model.dims.steps_per_frame)
         scaled = [self.scale_mel(dd) for dd in dicts]
         rows = [np.full(int(mm.shape[1]), ff, dtype=np.float32) for mm, ff in zip(scaled, factors)]
         return self.synth_from_mels(scaled, max_batch=max_batch, max_padded_frames=max_padded_frames, flac=flac,

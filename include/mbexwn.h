@@ -340,6 +340,28 @@ typedef struct {
 #define MBX_TAIL_K_TAIL 7            /* wn_tail_kernel: C < 16 or C > 352 */
 mbx_status mbx_kernel_report(const mbx_handle *handle, mbx_kernel_report_info *info);
 
+/* Which kernels a whole-item mbx_forward of (batch, max_frames) would run, without launching anything (an extension inside
+ * ABI 11: a new symbol, no struct of an existing call changes).  The library decides the kernel of every WaveNet launch on
+ * the host in front of the first launch, from the handle's policy and the launch's size alone; this call returns that plan.
+ * After such a forward, mbx_conv_form_info.gate_kernel and mbx_kernel_report_info hold the same codes.  A size the forward
+ * would refuse because a layer fits no kernel is refused here with the same status and message.  Streaming calls and calls
+ * with an active region (mbx_forward_stream, mbx_forward_ex) plan from their own windows and are not described by this. */
+typedef struct {
+    int32_t struct_size;        /* sizeof(mbx_plan_info), set by the caller */
+    int32_t n_layers;           /* entries in use, indexed as mbx_conv_form_info.gate_kernel (block-major on several blocks) */
+    int32_t gate_kernel[MBX_MAX_WN_LAYERS];          /* MBX_GATE_K_* */
+    int32_t gate_kernel_f32[MBX_MAX_WN_LAYERS];      /* the float32 kernel the layer takes where the split half precision does
+                                                      * not run it (equal to gate_kernel on a float32 handle) */
+    int32_t gate_block_channels[MBX_MAX_WN_LAYERS];  /* as mbx_kernel_report_info.gate_block_channels */
+    int32_t resskip_kernel[MBX_MAX_WN_LAYERS];       /* MBX_RESSKIP_K_* */
+    int32_t tail_kernel;        /* MBX_TAIL_K_* */
+    int32_t tail_folded;
+    int32_t planes_only;        /* 1: split half precision with the fp16 planes as the hidden state -- every consumer of the
+                                 * hidden state runs a kernel that takes them, the float32 hidden state is not written and the
+                                 * stage is "wn_hidden_planes" instead of "wn_hidden" (mbx_stage) */
+} mbx_plan_info;
+mbx_status mbx_plan(const mbx_handle *handle, int32_t batch, int32_t max_frames, mbx_plan_info *info);
+
 /* Re-runs the calibration of MBX_CONV_AUTO on the caller's own input (same argument meaning as mbx_forward) and adopts
  * its decision for the forwards that follow -- for a handle created with any wn_conv_form (a pinned form becomes the
  * calibrated one).  Synchronises the stream, allocates and frees scratch memory: a set-up call, not part of the
@@ -530,13 +552,16 @@ mbx_status mbx_emit_rows(mbx_handle *handle, const float *audio, int64_t row_flo
                          int64_t count, float *host_out, void *hip_stream);
 
 /* Intermediate tensors of the most recent mbx_forward (pointers into its workspace), for stage parity
- * tests.  Names: "f0" "pulse" "cond" "wn_hidden" "wn_skip" "wn_out" "subbands" "excitation" "cepstrum"
+ * tests.  Names: "f0" "pulse" "cond" "wn_hidden" (or "wn_hidden_planes") "wn_skip" "wn_out" "subbands" "excitation" "cepstrum"
  * "ceps_index" "frames".  `count` = floats (int32 for ceps_index) per batch item, `stride` = item stride.
  * "wn_skip" (the C-wide skip sum) only exists when the skip path is not folded into the end convolution
  * (mbx_config.wn_keep_skip, or a handle created without the *.fold tensors).  A forward in split half precision whose
  * every consumer of the hidden state takes it as fp16 planes does not write the float32 hidden state: there "wn_hidden"
- * is unknown and "wn_hidden_planes" holds it instead, per row ceil(C/8)*8 hi halves then as many lo' halves (h = hi +
- * 2^-11 lo'; count and stride in float32 words).
+ * is unknown and "wn_hidden_planes" holds it instead (mbx_plan_info.planes_only tells in advance which of the two a
+ * forward of a given size leaves).  Layout of "wn_hidden_planes": per item max_frames * steps_per_frame rows, per row
+ * C8 = ceil(C/8)*8 IEEE half-precision values hi[0 .. C8) followed by C8 values lo'[0 .. C8) -- 4 * C8 bytes, i.e. C8
+ * float32 words, which is the unit of count and stride; channel c of a row is h = hi[c] + 2^-11 lo'[c] (evaluated in
+ * float32), the padding channels c >= C are zero.
  * Several WaveNet blocks (mbx_config.n_wn_blocks >= 1): "wn_hidden" and "wn_skip" are the LAST block's hidden state and
  * skip sum, max_frames * rows_per_frame * C floats per item at that block's own rate and channels; "cond" is block 0's
  * conditioning rows and "cond1" .. "cond3" those of blocks 1 .. 3, laid out like "cond" (max_frames * cond rows per frame

@@ -37,8 +37,8 @@ static mbx_status calibrate_run(mbx_handle *hd, const float *mel, const int32_t 
     const int form_before = current_form(hd);
     // the opt-in split precision is measured like a form: every reference and form run below is float32; the handle's
     // configuration in split precision is then held to the same threshold against the float32 direct form
-    const bool split_req = hd->split_f16, split_gate_req = hd->split_f16_gate;
-    hd->split_f16 = hd->split_f16_gate = false;
+    const bool split_req = hd->pol.split_f16, split_gate_req = hd->pol.split_f16_gate;
+    hd->pol.split_f16 = hd->pol.split_f16_gate = false;
     auto run = [&](int form, std::vector<float> &host) -> mbx_status {
         set_form(hd, form);
         mbx_status st = forward_impl(hd, mel, n_frames, B, T, noise, audio_dev, workspace, workspace_bytes, stream);
@@ -54,11 +54,11 @@ static mbx_status calibrate_run(mbx_handle *hd, const float *mel, const int32_t 
         // the calibration forwards filled the stage table with pointers into their own (temporary, or by now overwritten)
         // workspace and strides of the calibration batch: mbx_stage answers "unknown stage" until the caller's next forward
         hd->stages.clear();
-        hd->last_gate_layers = 0;
+        hd->last_plan = mbx::WnPlan();
         if (st != MBX_OK) {
             set_form(hd, form_before);
-            hd->split_f16 = split_req;
-            hd->split_f16_gate = split_gate_req;
+            hd->pol.split_f16 = split_req;
+            hd->pol.split_f16_gate = split_gate_req;
         }
         return st;
     };
@@ -98,8 +98,8 @@ static mbx_status calibrate_run(mbx_handle *hd, const float *mel, const int32_t 
     hd->calib_threshold = threshold;
     if (split_req) {
         // the handle as it will run (its form, split precision on) against the float32 direct form
-        hd->split_f16 = true;
-        hd->split_f16_gate = split_gate_req;
+        hd->pol.split_f16 = true;
+        hd->pol.split_f16_gate = split_gate_req;
         st = run(form, got);
         if (st != MBX_OK) return done(st);
         float e = 0.f;
@@ -110,7 +110,7 @@ static mbx_status calibrate_run(mbx_handle *hd, const float *mel, const int32_t 
         hd->calib_err_split = e;
         // (the split precision rides on the form's own error: its budget is what the threshold leaves)
         hd->split_rejected = !(finite && e <= threshold);
-        if (hd->split_rejected) hd->split_f16 = hd->split_f16_gate = false;
+        if (hd->split_rejected) hd->pol.split_f16 = hd->pol.split_f16_gate = false;
     }
     return done(MBX_OK);
 }
@@ -185,15 +185,15 @@ mbx_status mbx_conv_form(const mbx_handle *hd, mbx_conv_form_info *info) {
         return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_conv_form_info ABI mismatch (struct_size)");
     info->requested = hd->cfg.wn_conv_form;
     info->form = current_form(hd);
-    info->stream_form = hd->winograd != 0 && form_available(hd, MBX_CONV_F23) ? MBX_CONV_F23 : MBX_CONV_DIRECT;
+    info->stream_form = hd->pol.winograd != 0 && form_available(hd, MBX_CONV_F23) ? MBX_CONV_F23 : MBX_CONV_DIRECT;
     info->calibrated = hd->calibrated;
-    info->batch_invariant = (hd->winograd != 4 || hd->winograd4_always) ? 1 : 0;
-    info->fold_skip = hd->fold_skip;
-    info->fold_start = hd->fold_start;
+    info->batch_invariant = (hd->pol.winograd != 4 || hd->pol.winograd4_always) ? 1 : 0;
+    info->fold_skip = hd->pol.fold_skip;
+    info->fold_start = hd->pol.fold_start;
     info->split_f16_layers = 0;
-    for (int l = 0; hd->split_f16 && l + 1 < hd->cfg.wn_layers; ++l)
+    for (int l = 0; hd->pol.split_f16 && l + 1 < hd->cfg.wn_layers; ++l)
         info->split_f16_layers += hd->wn[0].layer[l].run.f16 != nullptr;
-    info->split_f16_gate_layers = hd->split_f16_gate ? std::max(0, hd->cfg.wn_layers - 1) : 0;
+    info->split_f16_gate_layers = hd->pol.split_f16_gate ? std::max(0, hd->cfg.wn_layers - 1) : 0;
     info->err_split = hd->calib_err_split;
     info->split_rejected = hd->split_rejected;
     info->err_f43 = hd->calib_err43;
@@ -201,8 +201,9 @@ mbx_status mbx_conv_form(const mbx_handle *hd, mbx_conv_form_info *info) {
     info->ref_max = hd->calib_ref;
     info->threshold = hd->calib_threshold;
     info->f0_float64_chain = hd->f0_full64 ? 1 : 0;
-    info->n_gate_layers = hd->last_gate_layers;
-    for (int l = 0; l < MBX_MAX_WN_LAYERS; ++l) info->gate_kernel[l] = l < hd->last_gate_layers ? hd->last_gate_kernel[l] : MBX_GATE_K_NONE;
+    const mbx::WnPlan &plan = hd->last_plan;
+    info->n_gate_layers = plan.n_layers;
+    for (int l = 0; l < MBX_MAX_WN_LAYERS; ++l) info->gate_kernel[l] = l < plan.n_layers ? plan.gate[l].kernel : MBX_GATE_K_NONE;
     return MBX_OK;
 }
 
@@ -212,13 +213,35 @@ mbx_status mbx_kernel_report(const mbx_handle *hd, mbx_kernel_report_info *info)
     if (!info || !(whole || info->struct_size == (int32_t)offsetof(mbx_kernel_report_info, gate_block_channels)))
         return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_kernel_report_info ABI mismatch (struct_size)");
     if (!hd) return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_kernel_report: null handle");
-    info->n_resskip_layers = hd->last_gate_layers;
-    for (int l = 0; l < MBX_MAX_WN_LAYERS; ++l)
-        info->resskip_kernel[l] = l < hd->last_gate_layers ? hd->last_resskip_kernel[l] : MBX_RESSKIP_K_NONE;
-    info->tail_kernel = hd->last_gate_layers ? hd->last_tail_kernel : MBX_TAIL_K_NONE;
-    info->tail_folded = hd->last_gate_layers ? hd->last_tail_folded : 0;
+    const mbx::WnPlan &plan = hd->last_plan;
+    info->n_resskip_layers = plan.n_layers;
+    for (int l = 0; l < MBX_MAX_WN_LAYERS; ++l) info->resskip_kernel[l] = l < plan.n_layers ? plan.resskip[l] : MBX_RESSKIP_K_NONE;
+    info->tail_kernel = plan.n_layers ? plan.tail : MBX_TAIL_K_NONE;
+    info->tail_folded = plan.n_layers ? plan.tail_folded : 0;
     for (int l = 0; whole && l < MBX_MAX_WN_LAYERS; ++l)
-        info->gate_block_channels[l] = l < hd->last_gate_layers ? hd->last_gate_block_channels[l] : 0;
+        info->gate_block_channels[l] = l < plan.n_layers ? plan.gate[l].block_channels : 0;
+    return MBX_OK;
+}
+
+mbx_status mbx_plan(const mbx_handle *hd, int32_t batch, int32_t max_frames, mbx_plan_info *info) {
+    if (!info || info->struct_size != (int32_t)sizeof(mbx_plan_info)) return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_plan_info ABI mismatch (struct_size)");
+    if (!hd) return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_plan: null handle");
+    if (batch <= 0 || max_frames <= 0) return fail(MBX_ERR_INVALID_ARGUMENT, "batch and max_frames must be positive");
+    if ((long long)max_frames * hd->cfg.steps_per_frame >= (1LL << 24))
+        return fail(MBX_ERR_UNSUPPORTED, "an item may have at most 2^24 - 1 sub-band rows (split longer recordings)");
+    const mbx::WnPlan plan = plan_whole_items(hd, batch, max_frames);
+    if (plan.status != MBX_OK) return fail(plan.status, plan.error);
+    info->n_layers = plan.n_layers;
+    for (int l = 0; l < MBX_MAX_WN_LAYERS; ++l) {
+        const bool in = l < plan.n_layers;
+        info->gate_kernel[l] = in ? plan.gate[l].kernel : MBX_GATE_K_NONE;
+        info->gate_kernel_f32[l] = in ? plan.gate_f32[l] : MBX_GATE_K_NONE;
+        info->gate_block_channels[l] = in ? plan.gate[l].block_channels : 0;
+        info->resskip_kernel[l] = in ? plan.resskip[l] : MBX_RESSKIP_K_NONE;
+    }
+    info->tail_kernel = plan.tail;
+    info->tail_folded = plan.tail_folded;
+    info->planes_only = plan.planes_only ? 1 : 0;
     return MBX_OK;
 }
 

@@ -178,18 +178,18 @@ bool form_available(const mbx_handle *hd, int form) {
             if (!images(bt, 0)) return false;
         return true;
     }
-    return images(hd->wn[0], hd->fold_start ? 1 : 0);
+    return images(hd->wn[0], hd->pol.fold_start ? 1 : 0);
 }
 
 void set_form(mbx_handle *hd, int form) {
-    hd->winograd = form == MBX_CONV_F43 ? 4 : form == MBX_CONV_F23 ? 2 : 0;
+    hd->pol.winograd = form == MBX_CONV_F43 ? 4 : form == MBX_CONV_F23 ? 2 : 0;
     // causal padding without a pinned Winograd form, or in the block runner: the direct form (generic kernel)
-    if (hd->cfg.wn_causal && !form_available(hd, form)) hd->winograd = 0;
-    hd->winograd4_always = hd->winograd == 4 && hd->cfg.batch_invariant != 0;
+    if (hd->cfg.wn_causal && !form_available(hd, form)) hd->pol.winograd = 0;
+    hd->pol.winograd4_always = hd->pol.winograd == 4 && hd->cfg.batch_invariant != 0;
 }
 
 int current_form(const mbx_handle *hd) {
-    return hd->winograd == 4 ? MBX_CONV_F43 : hd->winograd == 2 ? MBX_CONV_F23 : MBX_CONV_DIRECT;
+    return hd->pol.winograd == 4 ? MBX_CONV_F43 : hd->pol.winograd == 2 ? MBX_CONV_F23 : MBX_CONV_DIRECT;
 }
 
 }  // namespace mbx_host
@@ -508,13 +508,13 @@ mbx_status mbx_create(const mbx_config *config, const mbx_tensor *tensors, int32
         // causal padding folds the start only under a pinned Winograd form: MBX_CONV_AUTO keeps the kernels it always ran
         const bool pinned = c.wn_conv_form == MBX_CONV_F23 || c.wn_conv_form == MBX_CONV_F43;
         const bool fold_pad = !c.wn_causal || pinned;
-        hd->fold_skip = have;
+        hd->pol.fold_skip = have;
         // start convolution folded into layer 0 (wn_gate0.hip); wn_keep_start keeps the h0 tensor and the full layer
         bool have0 = have && fold_pad && !c.wn_keep_start && c.wn_kernel_size == 3 &&
                      mbx::wn_gate0_fits(C, c.pulse_channels * (1 + c.wt_subharm_channels), c.wn_dilations[0], c.cond_lin_upsampling) &&
                      lt[0].start_fold;
         if (have0 && c.wn_layers > 1) have0 = lt[0].start.fold != nullptr;
-        hd->fold_start = have0;
+        hd->pol.fold_start = have0;
         if (have0) lt[0].run = lt[0].start;
     }
     if (c.wn_precision != MBX_PRECISION_F32 && c.wn_precision != MBX_PRECISION_SPLIT_F16)
@@ -523,20 +523,38 @@ mbx_status mbx_create(const mbx_config *config, const mbx_tensor *tensors, int32
         // opt-in experiment: folded res/skip layers 1 .. L-2 on the 16-bit matrix pipe (wn_resskip_f16.hip)
         if (c.wn_gate_activation == MBX_GATE_GLU)
             return bail(fail(MBX_ERR_UNSUPPORTED, "wn_precision = split f16 needs a bounded gate (not glu)"));
-        bool have16 = hd->fold_skip && c.wn_layers >= 3 && C + c.wn_out_channels <= 384;
+        bool have16 = hd->pol.fold_skip && c.wn_layers >= 3 && C + c.wn_out_channels <= 384;
         for (int l = 1; l + 1 < c.wn_layers && have16; ++l) have16 = hd->wn[0].layer[l].plain.f16 != nullptr;
         if (!have16)
             return bail(fail(MBX_ERR_INVALID_ARGUMENT, "wn_precision = split f16 needs the folded skip path, >= 3 layers, C + n_out <= 384 "
                                                         "and the wn.res_skip_<l>.fold_f16 images"));
-        hd->split_f16 = true;
+        hd->pol.split_f16 = true;
         // ... and the gate layers behind the folded first one (wn_gate_f16.hip), where the host supplied their images
-        hd->split_f16_gate = hd->fold_start && !c.wn_causal && c.wn_kernel_size == 3;
-        for (int l = 1; l < c.wn_layers && hd->split_f16_gate; ++l) hd->split_f16_gate = hd->wn[0].layer[l].gate_f16 != nullptr;
+        hd->pol.split_f16_gate = hd->pol.fold_start && !c.wn_causal && c.wn_kernel_size == 3;
+        for (int l = 1; l < c.wn_layers && hd->pol.split_f16_gate; ++l) hd->pol.split_f16_gate = hd->wn[0].layer[l].gate_f16 != nullptr;
     }
     {
-        hd->gate_small_shape = c.tune_gate_shape - 1;
-        if (c.tune_resskip_wave_tiles) hd->resskip_wave_tiles = std::max(0, c.tune_resskip_wave_tiles);
-        hd->resskip_split = c.tune_resskip_split;
+        // what kernel selection depends on besides the form (wn_plan.h): the single block's shape, the images the host supplied
+        // for its layers, and the dynamic-LDS sizes this device grants (asked for once, here, under the device guard)
+        mbx::WnPolicy &p = hd->pol;
+        p.C = C;
+        p.n_out = c.wn_out_channels;
+        p.M = M;
+        p.L = c.wn_layers;
+        p.cond_up = c.cond_lin_upsampling;
+        p.ks = c.wn_kernel_size;
+        p.causal = c.wn_causal;
+        p.gate_act = c.wn_gate_activation;
+        p.pulse_channels = c.pulse_channels * (1 + c.wt_subharm_channels);
+        for (int l = 0; l < c.wn_layers; ++l) {
+            p.dil[l] = c.wn_dilations[l];
+            p.img[l] = (unsigned char)layer_images(hd->wn[0].layer[l]);
+        }
+        p.end_packed = hd->wn[0].end_packed != nullptr;
+        p.lds_ok = mbx::wn_gate_f16_lds_opt_in() | mbx::wn_gate_winograd4q_lds_opt_in();
+        hd->pol.gate_small_shape = c.tune_gate_shape - 1;
+        if (c.tune_resskip_wave_tiles) hd->pol.resskip_wave_tiles = std::max(0, c.tune_resskip_wave_tiles);
+        hd->pol.resskip_split = c.tune_resskip_split;
         // form of the dilated convolution: a Winograd form needs its weight images (for every layer that runs the gate
         // kernels), SAME padding and kernel size 3; a handle without them runs the direct form whatever was asked for
         const bool can43 = form_available(hd, MBX_CONV_F43), can23 = form_available(hd, MBX_CONV_F23);
@@ -546,7 +564,7 @@ mbx_status mbx_create(const mbx_config *config, const mbx_tensor *tensors, int32
         if (form == MBX_CONV_F43 && !can43) form = can23 ? MBX_CONV_F23 : MBX_CONV_DIRECT;
         if (form == MBX_CONV_F23 && !can23) form = MBX_CONV_DIRECT;
         set_form(hd, form);
-        if ((autoform && form != MBX_CONV_DIRECT) || hd->split_f16) {
+        if ((autoform && form != MBX_CONV_DIRECT) || hd->pol.split_f16) {
             // MBX_CONV_AUTO: the Winograd forms must earn their place on this handle's own weights -- and so must the opt-in
             // split precision, whatever the form (an overflow of fp16's range by the hidden state shows here as well)
             st = calibrate_on_synthetic_mel(hd, autoform && form != MBX_CONV_DIRECT);

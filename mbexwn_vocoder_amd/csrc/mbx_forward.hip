@@ -210,8 +210,7 @@ struct ForwardCtx {
     // left by the stages
     const float *nm_gain_src = nullptr;        // run_norm_mel: the gain run_backend multiplies onto the audio
     const float *pulse_wn = nullptr;           // run_excitation: the excitation rows the WaveNet reads
-    bool planes_only = false;                  // run_wavenet: split precision ran with the fp16 planes as the hidden state
-    bool planes_valid = false;                 // ... the last res/skip launch also wrote h as fp16 planes (w.h16)
+    mbx::WnPlan plan;                          // check_forward_args: the kernel of every WaveNet launch (wn_plan.h)
 
     ForwardCtx(mbx_handle *hd_, const ForwardExtras &ex_, const float *mel_, const int32_t *n_frames_, int B_, int T_,
                const float *noise_, float *audio_, void *hip_stream)
@@ -221,151 +220,49 @@ struct ForwardCtx {
     bool streamed() const { return ex.st_in || ex.st_out; }
 };
 
-// ---- launch-shape policy: pure functions of the handle's policy fields and the launch's size; they launch nothing ----
-
-struct GateShape {
-    int shape;      // F(4,3) block shape: 0 256-row | 1 product-split | 2 product-split, half column tiles | 3 256-row, two column tiles
-    bool f43;       // false: the direct form costs less than F(4,3) for this launch (dilations above 16 only)
-};
-
-// 256-row one-tile blocks from which a launch takes the blocks of two column tiles (gate_shape_policy).  Measured in one
-// process, pins 1 and 4 alternating (scripts/experiments/gate_shapes.py --ab 1 4, profiles/r07_gate_shapes_ab.txt; C = 320,
-// B x 800 frames, us per launch, one tile | two tiles): B = 1: 106.6 | 137.5, 2: 172.7 | 208.7, 4: 331.8 | 334.0 (no
-// difference: its spread is larger), 8: 661.9 | 639.7 (-3.4 %), 16: 1 329.0 | 1 280.1 (-3.7 %).  8 x 800 frames = 5 040 blocks.
-constexpr long long WIDE_FROM_BLOCKS = 5040;
-
-GateShape gate_shape_policy(const mbx_handle *hd, int C, int B, long long nsteps, int span_rows, int d) {
-    // F(4,3) block shape: what a launch of a few blocks per CU costs is the largest number of wave tiles a SIMD gets.
-    // 256-row blocks put one whole tile (16 groups x 64 columns x 6 products) on every SIMD of their CU, the 128-row
-    // product-split blocks half a tile: the finer shape runs when its worst SIMD gets clearly less work (a 10 s
-    // utterance: 630 blocks = 2.46 per CU -> 3 tiles, against 1250 = 4.88 -> 5 halves).  Both give the same bits.
-    // Streams run F(2,3): a window is bit-identical to an offline result only if both use one form with one group
-    // alignment (streaming.py), and F(2,3) needs the shorter alignment; MBX_CONV_F23 makes offline runs use it too.
-    const long long full_blocks = ((nsteps + 255) / 256) * B * ((C + 31) / 32);
-    const long long half_blocks = ((nsteps + 127) / 128) * B * ((C + 31) / 32);
-    const double load_full = (double)((full_blocks + 255) / 256), load_half = 0.5 * (double)((half_blocks + 255) / 256);
-    // measured (scripts/experiments/gate_shapes.py, one item of 3 / 5 / 10 / 15 s: 51 / 65 / 102 / 155 us against 53 / 80 /
-    // 110 / 167 us; two items of 10 s: 194 against 176 us): the finer shape wins up to about one resident round of
-    // 256-row blocks and loses behind it, where both shapes divide evenly and the 128-row block's extra LDS-DMA traffic
-    // per MFMA (the weight slice serves half the rows) and shorter slices tell
-    bool split4 = !hd->winograd4_always && full_blocks <= 1024 && load_half <= load_full;
-    // round 5: product-split blocks of HALF a column tile (one channel parity: twice the blocks of half the work; same bits
-    // as the other shapes).  The idea: a 3 s utterance is 380 product-split blocks on 256 CUs, the worst CU works two
-    // while the average is 1.5; 760 half blocks give every CU three.
-    // Measured (scripts/experiments/gate_shapes.py, profiles/r05_gate_shapes.txt; one item of 1 / 2 / 3 / 4 / 5 / 10 s):
-    // 32.4 / 43.8 / 54.0 / 65.9 / 70.4 / 131.8 us against 32.1 / 48.5 / 48.8 / 64.3 / 63.5 / 100.7 us for the product-split
-    // blocks -- the estimate above was wrong: a block of half the matrix work lasts almost as long (40 barrier-separated
-    // slices whose round trips, not whose MFMAs, set its time), so the finer shape only pays where the product-split
-    // blocks leave CUs empty (<= 256 of them) and the half blocks do not (> 256): utterances around 2 s.
-    int shape4 = split4 ? ((half_blocks <= 256 && 2 * half_blocks > 256) ? 2 : 1) : 0;
-    // round 7: 256-row blocks of TWO column tiles (wn_gate_winograd4q_kernel; same bits, so batch_invariant handles follow
-    // the same size rule): the input combinations and the activation staging are spent once per 96 MFMAs instead of once
-    // per 48.  WIDE_FROM_BLOCKS: see the measurements at its definition.
-    if (shape4 == 0 && full_blocks >= WIDE_FROM_BLOCKS) shape4 = 3;
-    // mbx_config.tune_gate_shape: 1 and 4 pin the two shapes of large launches at every size, 2 and 3 the shape of small ones
-    const int pin = hd->gate_small_shape;
-    if (pin == 0 || pin == 3) shape4 = pin;
-    else if (pin > 0 && !hd->winograd4_always && full_blocks < 4 * 768) shape4 = pin;
-    split4 = shape4 == 1 || shape4 == 2;
-    bool f43 = true;
-    if (d > 16) {
-        // Dilations above 16 (the reference's default depth reaches 2048, custom_AE_layers.py:229-233): F(4,3) over the
-        // d / 16 interleaved sub-sequences of every item (wn_winograd4w.hip, VS kernels).  A block covers 256 (128) rows
-        // of ONE sub-sequence, so short items pad: cost in 256-row block units, the product-split block 0.56 of one
-        // (half the products, ~12 % slower per product), the direct form twice the multiplies of the unpadded rows.
-        // Both block shapes give the same bits; whether F(4,3) or the direct form runs depends on the launch only
-        // under the default policy (batch_invariant: always F(4,3)).
-        const int vs = d / 16;
-        const long long vrows = ((long long)span_rows + vs - 1) / vs, tiles = (C + 31) / 32;
-        // (sub-sequences of at most 128 rows: a 256-row block takes two of them)
-        const double cost_full = (vrows <= 128 ? 0.5 : (double)((vrows + 255) / 256)) * B * vs * tiles;
-        const double cost_half = 0.56 * (double)((vrows + 127) / 128) * B * vs * tiles;
-        const double cost_direct = 2.0 * ((double)span_rows / 256.0) * B * tiles;
-        if (hd->gate_small_shape >= 0 && !hd->winograd4_always) {
-            shape4 = hd->gate_small_shape == 3 ? 0 : hd->gate_small_shape;      // mbx_config.tune_gate_shape pins the shape (and F(4,3) itself); no two-tile blocks above d = 16
-        } else {
-            split4 = split4 || cost_half < 0.95 * cost_full;
-            shape4 = split4 ? 1 : 0;
-            if (!hd->winograd4_always && std::min(cost_full, cost_half) > 0.9 * cost_direct) f43 = false;
-        }
-    }
-    return GateShape{shape4, f43};
-}
-
-struct ResSkipShape { bool wide, wave; };     // the folded res/skip kernels a launch may take, in the order they are tried
-
-ResSkipShape resskip_shape_policy(const mbx_handle *hd, int B, long long nsteps, int span_rows, bool streamed) {
-    // large launches (>= two rounds of the 512 resident 128-row blocks): one block owns all columns of its rows.
-    // Like the gate kernels' block shape this follows the launch size only under the default policy: a pinned
-    // form (MBX_CONV_DIRECT, MBX_CONV_F23, batch_invariant, streams) pins the kernel, so results do not depend on the batch they ran in.
-    const long long wide_blocks = ((nsteps + 127) / 128) * B;
-    const bool wide = hd->winograd4_always || (hd->winograd == 4 && !streamed && wide_blocks >= 2 * 512);
-    // small launches: wave-granular tiles (wn_resskip_wave.hip).  The form pinned by the streams and by
-    // MBX_CONV_F23 (F(2,3) gate) runs this kernel at every size: an output's arithmetic does not depend on
-    // its cut, so windows, per-layer regions and whole utterances agree bit for bit.
-    const long long wave_tiles = ((long long)span_rows + 15) / 16 * B;
-    const bool pinned23 = hd->winograd == 2 || (hd->winograd != 0 && streamed);
-    const bool wave = pinned23 || (hd->winograd == 4 && !hd->winograd4_always && wave_tiles <= hd->resskip_wave_tiles);
-    return ResSkipShape{wide, wave};
-}
-
 // ---- argument builders ------------------------------------------------------------------------------------------------
 
-int gate_pad(const mbx_config &c, int d) { return c.wn_causal ? d * (c.wn_kernel_size - 1) : d * (c.wn_kernel_size - 1) / 2; }
+mbx::WnSpan wn_span(const Span &sp) { return mbx::WnSpan{sp.max_rows, sp.cphase, sp.out0, sp.out_rows}; }
 
 // Gate layer of a block with C channels on the span sp: h, a are (B, rows, C) with the batch stride bstride, cond the
-// block's conditioning rows (B, rows / cond_up, 2 C)
+// block's conditioning rows (B, rows / cond_up, 2 C).  Dimensions and strides: wn_gate_dims, which the plan was made from
 mbx::ConvArgs gate_args(mbx_handle *hd, const WnLayerTensors &t, int C, int d, const float *h, float *a, long long bstride,
                         const Span &sp, int B, const float *cond, long long cond_bstride) {
     const mbx_config &c = hd->cfg;
-    mbx::ConvArgs g = conv_args(h + sp.row0 * C, bstride, C, sp.nf, sp.rpf, sp.max_rows, B, t.w, t.b, c.wn_kernel_size, C, 2 * C,
-                                d, gate_pad(c, d), MBX_PAD_ZERO, a + sp.row0 * C, bstride, C);
+    mbx::ConvArgs g = mbx::wn_gate_dims(hd->pol, C, d, bstride, wn_span(sp), B, cond_bstride);
+    g.x = h + sp.row0 * C;
+    g.n_frames = sp.nf;
+    g.rows_per_frame = sp.rpf;
+    g.w = t.w->ptr;
+    g.bias = t.b ? t.b->ptr : nullptr;
+    g.out = a + sp.row0 * C;
     const auto &lerp = hd->lerp[c.cond_lin_upsampling];
     g.cond = cond + (sp.row0 / c.cond_lin_upsampling) * (2 * C);
-    g.cond_bstride = cond_bstride;
-    g.cond_up = c.cond_lin_upsampling;
-    g.cond_phase = sp.cphase;
-    g.out_row0 = sp.out0;
-    g.out_rows = sp.out_rows;
     g.lerp_w0 = lerp.first;
     g.lerp_w1 = lerp.second;
-    g.channels = C;
-    g.gate_act = c.wn_gate_activation;
     g.zeros = hd->zeros;
     return g;
 }
 
 // Layer 0 with the start convolution folded in (wn_gate0.hip): rows, conditioning and bias of the gate's ConvArgs, the
 // excitation instead of the hidden state, rows of ldo floats out
-mbx::Gate0Args gate0_args(const ForwardCtx &cx, const mbx::ConvArgs &g, const WnLayerTensors &t, long long row0, int ldo) {
+mbx::Gate0Args gate0_args(const ForwardCtx &cx, const mbx::ConvArgs &g, const WnLayerTensors &t, long long row0) {
     const mbx_config &c = cx.c;
     const int nsub1 = 1 + c.wt_subharm_channels;              // floats per excitation sample (pulse + sub-harmonic sinusoids)
-    mbx::Gate0Args g0{};
+    mbx::Gate0Args g0 = mbx::wn_gate0_dims(cx.hd->pol, g, cx.nsteps);
     g0.pulse = cx.pulse_wn + row0 * (c.pulse_per_frame / c.steps_per_frame * nsub1);
     g0.pulse_bstride = cx.npulse * nsub1;
     g0.noise = c.noise_sigma != 0.f ? cx.noise + row0 : nullptr;
     g0.noise_bstride = cx.nsteps;
     g0.sigma = c.noise_sigma;
-    g0.pulse_channels = c.pulse_channels * nsub1;
     g0.n_frames = g.n_frames;
     g0.rows_per_frame = g.rows_per_frame;
-    g0.max_rows = g.max_rows;
-    g0.batch = g.batch;
     g0.w = t.start_fold->ptr;
     g0.bias = g.bias;
-    g0.channels = g.channels;
-    g0.gate_act = g.gate_act;
-    g0.dil = g.dil;
-    g0.causal = c.wn_causal;
     g0.cond = g.cond;
-    g0.cond_bstride = g.cond_bstride;
-    g0.cond_up = g.cond_up;
     g0.lerp_w0 = g.lerp_w0;
     g0.lerp_w1 = g.lerp_w1;
-    g0.out = cx.w.a + row0 * ldo;
-    g0.out_bstride = cx.nsteps * ldo;
-    g0.ldo = ldo;
-    g0.write_inputs = c.wn_layers > 1;
+    g0.out = cx.w.a + row0 * g0.ldo;
     return g0;
 }
 
@@ -396,22 +293,39 @@ mbx::LayerCarryArgs layer_carry_args(const ForwardCtx &cx, int l) {
 // res/skip layer with a skip tensor (un-folded single block, block runner): a, h, skip are (B, rows, C)
 mbx::ConvArgs resskip_args(mbx_handle *hd, const WnLayerTensors &t, int C, int l, const float *a, float *h, float *skip,
                            long long bstride, const Span &sp, int B) {
-    const bool last = l == hd->cfg.wn_layers - 1;
-    mbx::ConvArgs r = conv_args(a + sp.row0 * C, bstride, C, sp.nf, sp.rpf, sp.max_rows, B, t.res_w, t.res_b, 1, C,
-                                last ? C : 2 * C, 1, 0, MBX_PAD_ZERO, nullptr, 0, 0);
-    r.channels = C;
+    mbx::ConvArgs r = mbx::wn_resskip_dims(C, l == 0, l == hd->cfg.wn_layers - 1, bstride, sp.max_rows, B);
+    r.x = a + sp.row0 * C;
+    r.n_frames = sp.nf;
+    r.rows_per_frame = sp.rpf;
+    r.w = t.res_w->ptr;
+    r.bias = t.res_b ? t.res_b->ptr : nullptr;
     r.zeros = hd->zeros;
     r.h = h + sp.row0 * C;
     r.skip = skip + sp.row0 * C;
-    r.hs_bstride = bstride;
-    r.skip_init = (l == 0);
-    r.last_layer = last;
+    return r;
+}
+
+// res/skip layer l < L - 1 with the skip path folded into the end convolution (wn_resskip_fold_dims): a (B, rows, C, or C + 16
+// under ext) -> h (B, rows, C) and the n_out-wide output accumulator
+mbx::ConvArgs resskip_fold_args(const ForwardCtx &cx, const WnLayerTensors &t, int l, bool ext, const Span &sp) {
+    const int C = cx.c.wn_channels, n_out = cx.c.wn_out_channels;
+    mbx::ConvArgs r = mbx::wn_resskip_fold_dims(cx.hd->pol, l == 0, ext, cx.nsteps, sp.max_rows, cx.B);
+    r.x = cx.w.a + sp.row0 * r.cin;
+    r.n_frames = sp.nf;
+    r.rows_per_frame = sp.rpf;
+    r.w = t.run.fold->ptr;
+    r.bias = t.fold_b ? t.fold_b->ptr : nullptr;
+    r.zeros = cx.hd->zeros;
+    r.h = cx.w.h + sp.row0 * C;
+    r.skip = cx.w.wn_out + sp.row0 * n_out;
     return r;
 }
 
 // ---- stages -----------------------------------------------------------------------------------------------------------
 
 mbx_status plan_layer_spans(ForwardCtx &cx);
+mbx::WnGeometry wn_geometry(const ForwardCtx &cx);
+mbx::WnPlan plan_blocks(const mbx_handle *hd, int B, int T);
 
 // Every check that needs no launch, in front of the first launch; carves the workspace and derives the regions.
 mbx_status check_forward_args(ForwardCtx &cx, void *workspace, size_t workspace_bytes) {
@@ -470,10 +384,14 @@ mbx_status check_forward_args(ForwardCtx &cx, void *workspace, size_t workspace_
     if (hd->blocks.empty()) {
         const mbx_status st = plan_layer_spans(cx);
         if (st != MBX_OK) return st;
+        // the kernel of every WaveNet launch, and "does not fit" in front of the first launch
+        cx.plan = mbx::wn_plan(hd->pol, wn_geometry(cx));
+        if (cx.plan.status != MBX_OK) return fail(cx.plan.status, cx.plan.error);
         if (c.pulse_per_frame % c.steps_per_frame != 0)
             return fail(MBX_ERR_INVALID_ARGUMENT, "pulse_per_frame must be a multiple of steps_per_frame");
     }
     if (c.ps_subband_gain && windowed) return fail(MBX_ERR_UNSUPPORTED, "ps_use_stft: false models run whole items only");
+    if (!hd->blocks.empty()) cx.plan = plan_blocks(hd, cx.B, T);
     return MBX_OK;
 }
 
@@ -690,130 +608,148 @@ void run_excitation(ForwardCtx &cx) {
     }
 }
 
-// Gate of one layer (dilated convolution + conditioning + gate): split half precision, then F(4,3) in the shape the policy
-// prefers, then its 256-row shape, then F(2,3), then the direct form.  carry: the layer's stream state moves first
-// (null: none).  generic: the block runner -- F(4,3) in the 256-row shape at every size, or the direct form.  kernel:
-// where the MBX_GATE_K_* that ran is reported (null: not), block_channels: the gate channels per F(4,3) block (0: none ran).
-mbx_status run_gate_layer(ForwardCtx &cx, const mbx::ConvArgs &g, const WnLayerTensors &t, const mbx::LayerCarryArgs *carry,
-                          bool generic, int *kernel, int *block_channels) {
-    mbx_handle *hd = cx.hd;
-    hipStream_t stream = cx.stream;
-    const int d = g.dil, C = g.channels;
-    const bool streamed = cx.streamed(), whole = g.cond_phase == 0 && g.out_rows == 0;
-    int ran_kernel = MBX_GATE_K_NONE, ran_channels = 0;
-    ScopedEvents ev(hd, PROF_GATE, stream);
-    if (carry) mbx::launch_layer_carry(*carry, g.batch, stream);
-    bool done = false;
-    // opt-in split half precision: whole-item forwards of the layers behind the folded first one
-    if (hd->split_f16_gate && !streamed && whole) {
-        mbx::ConvArgs gh = g;
-        gh.w = t.gate_f16->ptr;
-        if (cx.planes_valid) {                                  // the res/skip layer in front left h as fp16 planes
-            gh.h_split = cx.w.h16;
-            gh.h_split_ld = (C + 7) / 8 * 8;
-            gh.h_split_bstride = cx.nsteps * (long long)gh.h_split_ld;
-        }
-        ran_kernel = mbx::launch_wn_gate_f16(gh, stream);       // which of the three split kernels ran (0: the layer does not fit)
-        done = ran_kernel != MBX_GATE_K_NONE;
-        if (cx.planes_only && !(done && cx.planes_valid))
-            return fail(MBX_ERR_INVALID_ARGUMENT, "split precision: a gate layer did not take the plane-only hidden state");
+// The launch geometry the single block's plan is made from (wn_plan.h): the spans of plan_layer_spans and the kind of call
+mbx::WnGeometry wn_geometry(const ForwardCtx &cx) {
+    mbx::WnGeometry geo;
+    geo.B = cx.B;
+    geo.nsteps = cx.nsteps;
+    geo.cond_bstride = (long long)cx.T * cx.cond_cout;
+    geo.streamed = cx.streamed();
+    geo.active = cx.ex.active_frames != nullptr;
+    geo.layer_state = cx.ex.lay != nullptr;
+    for (int l = 0; l < cx.c.wn_layers; ++l) {
+        geo.gate[l] = wn_span(cx.gate_sp[l]);
+        geo.res_rows[l] = cx.res_sp[l].max_rows;
     }
-    const GateShape pol = generic ? GateShape{0, true} : gate_shape_policy(hd, C, g.batch, cx.nsteps, g.max_rows, d);
-    if (!done && hd->winograd == 4 && !streamed && pol.f43 && t.wino4w && g.cond_phase == 0) {
-        mbx::ConvArgs gw = g;
-        gw.w = t.wino4w->ptr;
-        // (the product-split shape holds 16 conditioning rows: cond_up >= 10; the 256-row shape takes cond_up >= 5)
-        int ran = pol.shape;
-        done = mbx::launch_wn_gate_winograd4w(gw, pol.shape, stream);
-        if (!done && pol.shape != 0) {
-            ran = 0;
-            done = mbx::launch_wn_gate_winograd4w(gw, 0, stream);
-        }
-        if (done) {
-            // (the blocks of two column tiles are a block shape of MBX_GATE_K_F43: the size rule of large launches picks either)
-            ran_kernel = d > 16 ? (ran ? MBX_GATE_K_F43_STRIDED_PSPLIT : MBX_GATE_K_F43_STRIDED)
-                                : (ran == 2 ? MBX_GATE_K_F43_HSPLIT : ran == 1 ? MBX_GATE_K_F43_PSPLIT : MBX_GATE_K_F43);
-            ran_channels = ran == 3 ? 64 : ran == 2 ? 16 : 32;
-        }
-    }
-    // F(2,3): wave-tiled kernel on v_mfma_f32_16x16x4_f32 (wn_winograd2w.hip): streams, per-layer regions, MBX_CONV_F23
-    if (!done && !generic && hd->winograd && t.wino2w) {
-        mbx::ConvArgs gw = g;
-        gw.w = t.wino2w->ptr;
-        done = mbx::launch_wn_gate_winograd2w(gw, stream);
-        if (done) ran_kernel = MBX_GATE_K_F23;
-    }
-    if (!done && !whole) return fail(MBX_ERR_UNSUPPORTED, "per-layer regions need the Winograd F(2,3) gate kernel");
-    if (!done) {
-        mbx::launch_conv1d(g, mbx::EPI_GATE, stream);
-        ran_kernel = MBX_GATE_K_DIRECT;
-    }
-    if (kernel) *kernel = ran_kernel;
-    if (block_channels) *block_channels = ran_channels;
-    return MBX_OK;
+    return geo;
 }
 
-// res/skip of one layer: split half precision, then the wide, then the wave-tiled kernel (folded layers: im is the layer's
-// image set, rows of C + 16 channels under ext), then the packed LDS-DMA kernel, then the generic one (layers with a skip
-// tensor only: im null, r.w the plain weights).  kernel: where the MBX_RESSKIP_K_* that ran is reported (null: not).
-mbx_status run_resskip_layer(ForwardCtx &cx, const mbx::ConvArgs &r, const WnLayerTensors &t, const FoldImages *im, bool ext, int *kernel) {
+// Layer l of block b of the block runner, whole items of T frames: F(4,3) in the 256-row shape at every size where the
+// host supplied the block's weight image and the layer fits (SAME padding, k = 3, power-of-two dilation), the direct form
+// otherwise; the packed res/skip kernel or the generic one
+struct BlockLayerPlan { mbx::GateChoice gate; int resskip; };
+BlockLayerPlan plan_block_layer(const mbx_handle *hd, size_t b, int l, int B, int T) {
+    const auto &blk = hd->blocks[b];
+    const int C = blk.C, L = hd->cfg.wn_layers;
+    const long long rows = (long long)T * blk.spf;
+    const unsigned img = layer_images(hd->wn[b].layer[l]);
+    const mbx::ConvArgs g = mbx::wn_gate_dims(hd->pol, C, hd->cfg.wn_dilations[l], rows * C, mbx::WnSpan{(int)rows, 0, 0, 0}, B,
+                                              (long long)T * blk.ccu * 2 * C);
+    BlockLayerPlan lp;
+    lp.gate = mbx::wn_plan_gate(hd->pol, img, g, (long long)T * hd->cfg.steps_per_frame, false, true, false, nullptr);
+    bool planes;
+    lp.resskip = mbx::wn_plan_resskip(hd->pol, img, mbx::wn_resskip_dims(C, l == 0, l == L - 1, rows * C, (int)rows, B),
+                                      (long long)T * hd->cfg.steps_per_frame, false, false, false, &planes);
+    return lp;
+}
+
+// The report of a model with several blocks (mbx_conv_form_info.gate_kernel, mbx_kernel_report_info): block-major, entry
+// b * L + l, as many as MBX_MAX_WN_LAYERS holds; every block's end convolution and the post-net are generic convolutions
+mbx::WnPlan plan_blocks(const mbx_handle *hd, int B, int T) {
+    mbx::WnPlan plan;
+    const int L = hd->cfg.wn_layers;
+    plan.n_layers = std::min<int>((int)hd->blocks.size() * L, MBX_MAX_WN_LAYERS);
+    for (int slot = 0; slot < plan.n_layers; ++slot) {
+        const BlockLayerPlan lp = plan_block_layer(hd, slot / L, slot % L, B, T);
+        plan.gate[slot] = lp.gate;
+        plan.gate_f32[slot] = lp.gate.kernel;
+        plan.resskip[slot] = lp.resskip;
+    }
+    plan.tail = MBX_TAIL_K_UNFUSED;
+    return plan;
+}
+
+// Gate of one layer (dilated convolution + conditioning + gate) with the kernel the plan chose.  carry: the layer's stream
+// state moves first (null: none)
+mbx_status run_gate_layer(ForwardCtx &cx, const mbx::ConvArgs &g, const WnLayerTensors &t, const mbx::GateChoice &k,
+                          const mbx::LayerCarryArgs *carry) {
     mbx_handle *hd = cx.hd;
     hipStream_t stream = cx.stream;
-    const int C = r.channels;
-    ScopedEvents ev(hd, (hd->split_f16 && (!ext || im->f16)) ? PROF_RES_SKIP_F16 : PROF_RES_SKIP, stream);
-    int done = MBX_RESSKIP_K_NONE;
-    if (im) {
-        // opt-in split half precision (mbx_config.wn_precision): every launch size, every layer whose split image the
-        // host supplied (layer 0 with the folded start convolution too: its rows [a0 | x'] have the image *.fold_start_f16)
-        if (hd->split_f16 && im->f16) {
-            mbx::ConvArgs rh = r;
-            rh.w = im->f16->ptr;
-            rh.gate_act = cx.c.wn_gate_activation;
-            if (hd->split_f16_gate && !cx.ex.active_frames) {      // the next layer's gate reads the new hidden state as fp16 planes
-                rh.h_split = cx.w.h16;
-                rh.h_split_ld = (C + 7) / 8 * 8;
-                rh.h_split_bstride = cx.nsteps * (long long)rh.h_split_ld;
-                rh.h_planes_only = cx.planes_only ? 1 : 0;
-            }
-            done = mbx::launch_wn_resskip_f16(rh, stream);
-            cx.planes_valid = done != MBX_RESSKIP_K_NONE && rh.h_split != nullptr;
-            if (cx.planes_only && !cx.planes_valid)
-                return fail(MBX_ERR_INVALID_ARGUMENT, "split precision: a res/skip layer did not take the plane-only hidden state");
-        } else {
-            cx.planes_valid = false;
-            if (cx.planes_only) return fail(MBX_ERR_INVALID_ARGUMENT, "split precision: a res/skip image is missing behind a plane-only layer");
-        }
-        const ResSkipShape pol = resskip_shape_policy(hd, r.batch, cx.nsteps, r.max_rows, cx.streamed());
-        if (!done && im->wide && pol.wide) {
-            mbx::ConvArgs rw = r;
-            rw.w = im->wide->ptr;
-            done = mbx::launch_wn_resskip_wide(rw, stream);
-        }
-        if (!done && im->wave && pol.wave) {
-            mbx::ConvArgs rw = r;
-            rw.w = im->wave->ptr;
-            rw.tune_split = hd->resskip_split;
-            done = mbx::launch_wn_resskip_wave(rw, stream);
-        }
+    ScopedEvents ev(hd, PROF_GATE, stream);
+    if (carry) mbx::launch_layer_carry(*carry, g.batch, stream);
+    mbx::ConvArgs a = g;
+    const char *err = nullptr;
+    switch (k.kernel) {
+    case MBX_GATE_K_SPLIT_F16:
+    case MBX_GATE_K_SPLIT_F16_WIDE:                 // the res/skip layer in front left h as fp16 planes
+        a.h_split = cx.w.h16;
+        mbx::wn_planes_dims(a, g.channels, cx.nsteps);
+        [[fallthrough]];
+    case MBX_GATE_K_SPLIT_F16_F32H:
+        a.w = t.gate_f16->ptr;
+        err = mbx::launch_wn_gate_f16(a, k.kernel, stream);
+        break;
+    case MBX_GATE_K_F43:
+    case MBX_GATE_K_F43_PSPLIT:
+    case MBX_GATE_K_F43_HSPLIT:
+    case MBX_GATE_K_F43_STRIDED:
+    case MBX_GATE_K_F43_STRIDED_PSPLIT:
+        a.w = t.wino4w->ptr;
+        err = mbx::launch_wn_gate_winograd4w(a, k, stream);
+        break;
+    case MBX_GATE_K_F23:
+        a.w = t.wino2w->ptr;
+        err = mbx::launch_wn_gate_winograd2w(a, stream);
+        break;
+    case MBX_GATE_K_DIRECT:
+        mbx::launch_conv1d(g, mbx::EPI_GATE, stream);
+        break;
+    default:
+        err = "gate layer without a planned kernel";
     }
-    // LDS-DMA kernel with host-packed weights (folded layers: the image r was built with)
-    const DevTensor *pk = im ? im->fold : t.packed;
-    if (!done && pk) {
-        mbx::ConvArgs rp = r;
-        rp.w = pk->ptr;
-        done = mbx::launch_wn_resskip(rp, stream);
-    }
-    if (!done && im) return fail(MBX_ERR_INVALID_ARGUMENT, "folded res/skip layer does not fit its kernel");
-    if (!done) {
+    return err ? fail(MBX_ERR_INVALID_ARGUMENT, err) : MBX_OK;
+}
+
+// res/skip of one layer with the kernel the plan chose (folded layers: im is the layer's image set, rows of C + 16 channels
+// under ext; layers with a skip tensor: im null, r.w the plain weights).  planes_out: a split launch also writes h as fp16 planes
+mbx_status run_resskip_layer(ForwardCtx &cx, const mbx::ConvArgs &r, const WnLayerTensors &t, const FoldImages *im, bool ext,
+                             int kernel, bool planes_out) {
+    mbx_handle *hd = cx.hd;
+    hipStream_t stream = cx.stream;
+    ScopedEvents ev(hd, (hd->pol.split_f16 && (!ext || im->f16)) ? PROF_RES_SKIP_F16 : PROF_RES_SKIP, stream);
+    mbx::ConvArgs a = r;
+    const char *err = nullptr;
+    switch (kernel) {
+    case MBX_RESSKIP_K_SPLIT_F16:
+        a.w = im->f16->ptr;
+        a.gate_act = cx.c.wn_gate_activation;
+        if (planes_out) {                           // the next layer's gate reads the new hidden state as fp16 planes
+            a.h_split = cx.w.h16;
+            mbx::wn_planes_dims(a, r.channels, cx.nsteps);
+            a.h_planes_only = cx.plan.planes_only ? 1 : 0;
+        }
+        err = mbx::launch_wn_resskip_f16(a, stream);
+        break;
+    case MBX_RESSKIP_K_WIDE11_RES10:
+    case MBX_RESSKIP_K_WIDE11:
+    case MBX_RESSKIP_K_WIDE6X2:
+        a.w = im->wide->ptr;
+        err = mbx::launch_wn_resskip_wide(a, kernel, stream);
+        break;
+    case MBX_RESSKIP_K_WAVE11:
+    case MBX_RESSKIP_K_WAVE12:
+    case MBX_RESSKIP_K_WAVE6X2:
+    case MBX_RESSKIP_K_WAVE4X3:
+        a.w = im->wave->ptr;
+        a.tune_split = hd->pol.resskip_split;
+        err = mbx::launch_wn_resskip_wave(a, kernel, stream);
+        break;
+    case MBX_RESSKIP_K_PACKED64:
+    case MBX_RESSKIP_K_PACKED128:                   // host-packed weights (folded layers: the image r was built with)
+        a.w = (im ? im->fold : t.packed)->ptr;
+        err = mbx::launch_wn_resskip(a, kernel, stream);
+        break;
+    case MBX_RESSKIP_K_CONV1D:
         mbx::launch_conv1d(r, mbx::EPI_RESSKIP, stream);
-        done = MBX_RESSKIP_K_CONV1D;
+        break;
+    default:
+        err = "res/skip layer without a planned kernel";
     }
-    if (kernel) *kernel = done;
-    return MBX_OK;
+    return err ? fail(MBX_ERR_INVALID_ARGUMENT, err) : MBX_OK;
 }
 
 // End of the single block: the last layer's share of the folded skip path, or the end convolution on the skip tensor; then
-// the post-net 1x1 into the sub-band rows (one kernel where the images are there)
+// the post-net 1x1 into the sub-band rows (one kernel where the plan found the images and the shapes fit)
 mbx_status run_tail(ForwardCtx &cx) {
     mbx_handle *hd = cx.hd;
     const mbx_config &c = cx.c;
@@ -826,20 +762,8 @@ mbx_status run_tail(ForwardCtx &cx) {
     const DevTensor *wpn = hd->tab.post_w, *bpn = hd->tab.post_b, *be = bt.end_b;
     const Span &ts = cx.tail_sp;
     float *acc_t = w.wn_out + ts.row0 * n_out, *sub_t = w.sub + ts.row0 * M, *skip_t = w.skip + ts.row0 * C;
-    int ran = MBX_TAIL_K_NONE;
-    if (hd->fold_skip) {
-        ran = mbx::launch_wn_tail(w.a + ts.row0 * C, nsteps * C, ts.nf, ts.rpf, ts.max_rows, B, C, bt.tail_fold->ptr, bt.tail_fold_b->ptr,
-                                  n_out, wpn->ptr, bpn ? bpn->ptr : nullptr, M, L > 1 ? acc_t : nullptr,
-                                  acc_t, nsteps * n_out, sub_t, nsteps * M, stream);
-        if (!ran) return fail(MBX_ERR_INVALID_ARGUMENT, "folded WaveNet tail does not fit its kernel");
-    }
-    if (!hd->fold_skip && bt.end_packed)
-        ran = mbx::launch_wn_tail(skip_t, nsteps * C, ts.nf, ts.rpf, ts.max_rows, B, C, bt.end_packed->ptr,
-                                  be ? be->ptr : nullptr, n_out, wpn->ptr, bpn ? bpn->ptr : nullptr, M, nullptr,
-                                  acc_t, nsteps * n_out, sub_t, nsteps * M, stream);
-    hd->last_tail_kernel = ran ? ran : MBX_TAIL_K_UNFUSED;
-    hd->last_tail_folded = hd->fold_skip ? 1 : 0;
-    if (!ran) {
+    const char *err = nullptr;
+    if (cx.plan.tail == MBX_TAIL_K_UNFUSED) {
         mbx::ConvArgs a = conv_args(skip_t, nsteps * C, C, ts.nf, ts.rpf, ts.max_rows, B, bt.end_w, be, 1, C,
                                     n_out, 1, 0, MBX_PAD_ZERO, acc_t, nsteps * n_out, n_out);
         mbx::launch_conv1d(a, mbx::EPI_LINEAR, stream);
@@ -847,21 +771,31 @@ mbx_status run_tail(ForwardCtx &cx) {
         mbx::ConvArgs pn = conv_args(acc_t, nsteps * n_out, n_out, ts.nf, ts.rpf, ts.max_rows, B, wpn, bpn, 1, n_out, M, 1, 0,
                                      MBX_PAD_ZERO, sub_t, nsteps * M, M);
         mbx::launch_conv1d(pn, mbx::EPI_LINEAR, stream);
+    } else if (hd->pol.fold_skip) {
+        err = mbx::launch_wn_tail(cx.plan.tail, w.a + ts.row0 * C, nsteps * C, ts.nf, ts.rpf, ts.max_rows, B, C, bt.tail_fold->ptr,
+                                  bt.tail_fold_b->ptr, n_out, wpn->ptr, bpn ? bpn->ptr : nullptr, M, L > 1 ? acc_t : nullptr,
+                                  acc_t, nsteps * n_out, sub_t, nsteps * M, stream);
+    } else {
+        err = mbx::launch_wn_tail(cx.plan.tail, skip_t, nsteps * C, ts.nf, ts.rpf, ts.max_rows, B, C, bt.end_packed->ptr,
+                                  be ? be->ptr : nullptr, n_out, wpn->ptr, bpn ? bpn->ptr : nullptr, M, nullptr,
+                                  acc_t, nsteps * n_out, sub_t, nsteps * M, stream);
     }
-    return MBX_OK;
+    return err ? fail(MBX_ERR_INVALID_ARGUMENT, err) : MBX_OK;
 }
 
-// ---- WaveNet (reference custom_AE_layers.py:273-346), one block: the measured path
+// ---- WaveNet (reference custom_AE_layers.py:273-346), one block: the measured path.  Which kernel runs every layer was
+// planned in check_forward_args (cx.plan); this only builds the arguments and launches.
 mbx_status run_wavenet(ForwardCtx &cx) {
     mbx_handle *hd = cx.hd;
     const mbx_config &c = cx.c;
     const Workspace &w = cx.w;
     const WnBlockTensors &bt = hd->wn[0];
-    const bool fold_start = hd->fold_start, fold = hd->fold_skip;
-    const int B = cx.B, C = c.wn_channels, L = c.wn_layers, n_out = c.wn_out_channels;
+    const mbx::WnPlan &plan = cx.plan;
+    const bool fold_start = hd->pol.fold_start, fold = hd->pol.fold_skip;
+    const int B = cx.B, C = c.wn_channels, L = c.wn_layers;
     const long long nsteps = cx.nsteps;
-    const int lda0 = (fold_start && L > 1) ? C + 16 : C;      // row stride of layer 0's output
     hipStream_t stream = cx.stream;
+    hd->last_plan = plan;
     if (!fold_start) {
         ScopedEvents ev(hd, PROF_START, stream);
         const Span &sp = cx.gate_sp[0];                       // (the region: a handle that carries layer state folds the start)
@@ -871,59 +805,26 @@ mbx_status run_wavenet(ForwardCtx &cx) {
                              sp.nf, sp.rpf, sp.max_rows, B, c.pulse_channels * nsub1, bt.start_w->ptr,
                              bt.start_b->ptr, C, w.h + sp.row0 * C, nsteps * C, stream);
     }
-    // split half precision, round 6: where every consumer of the hidden state takes the planes -- the split gate of every layer
-    // behind the first one (dilation <= 16: wn_gate_f16.hip) and the split res/skip layer of every layer in front of the last
-    // one, layer 0's with the folded start convolution included -- the planes ARE the hidden state: hi + 2^-11 lo' keeps 22-23 of
-    // float32's 24 bits, and the float32 tensor h (328 MB written and read again per layer at 16 x 10 s) is not touched
-    bool planes_only = hd->split_f16 && hd->split_f16_gate && fold && fold_start && !cx.streamed() && !cx.ex.active_frames && !cx.ex.lay && L >= 2 &&
-                       bt.layer[0].start.f16 != nullptr;
-    for (int l = 1; l < L && planes_only; ++l) planes_only = c.wn_dilations[l] <= 16;
-    for (int l = 1; l + 1 < L && planes_only; ++l) planes_only = bt.layer[l].plain.f16 != nullptr;
-    cx.planes_only = planes_only;
-    cx.planes_valid = false;
-    hd->last_gate_layers = L;
     for (int l = 0; l < L; ++l) {
         const WnLayerTensors &t = bt.layer[l];
         const Span &gs = cx.gate_sp[l], &rs = cx.res_sp[l];
         const mbx::ConvArgs g = gate_args(hd, t, C, c.wn_dilations[l], w.h, w.a, nsteps * C, gs, B, w.cond, (long long)cx.T * cx.cond_cout);
-        if (l == 0 && fold_start) {
+        mbx_status st = MBX_OK;
+        if (plan.gate[l].kernel == MBX_GATE_K_FOLDED_START) {
             // start convolution folded into the layer: a K = 24 contraction of the excitation (wn_gate0.hip)
             ScopedEvents ev(hd, PROF_GATE0, stream);
-            if (gs.cphase != 0 || !mbx::launch_wn_gate0(gate0_args(cx, g, t, gs.row0, lda0), stream))
-                return fail(MBX_ERR_INVALID_ARGUMENT, "folded first layer does not fit its kernel");
-            hd->last_gate_kernel[l] = MBX_GATE_K_FOLDED_START;
-            hd->last_gate_block_channels[l] = 0;
+            if (const char *err = mbx::launch_wn_gate0(gate0_args(cx, g, t, gs.row0), stream)) st = fail(MBX_ERR_INVALID_ARGUMENT, err);
         } else {
             const bool carry = cx.carry_layers && l >= 1;
             const mbx::LayerCarryArgs lc = carry ? layer_carry_args(cx, l) : mbx::LayerCarryArgs{};
-            const mbx_status st = run_gate_layer(cx, g, t, carry ? &lc : nullptr, false, &hd->last_gate_kernel[l], &hd->last_gate_block_channels[l]);
-            if (st != MBX_OK) return st;
+            st = run_gate_layer(cx, g, t, plan.gate[l], carry ? &lc : nullptr);
         }
-        mbx_status st = MBX_OK;
-        if (!fold) {
-            st = run_resskip_layer(cx, resskip_args(hd, t, C, l, w.a, w.h, w.skip, nsteps * C, rs, B), t, nullptr, false,
-                                   &hd->last_resskip_kernel[l]);
-        } else if (l < L - 1) {
-            // skip path folded into the end convolution: layers 0..L-2 update h and add a W_skip W_end to the n_out-wide
-            // output accumulator; the last layer's contribution is added by the tail kernel.
-            // Layer 0 with the start convolution folded in: rows [a0 | x'] (C + 16 channels) x [Wr ; Ws'], h starts from the bias
-            const bool ext = l == 0 && fold_start;
-            const int cin_l = ext ? C + 16 : C;
-            mbx::ConvArgs r = conv_args(w.a + rs.row0 * cin_l, nsteps * cin_l, cin_l, rs.nf, rs.rpf, rs.max_rows, B, t.run.fold, t.fold_b, 1,
-                                        cin_l, C + n_out, 1, 0, MBX_PAD_ZERO, nullptr, 0, 0);
-            r.h_init = ext;
-            r.channels = C;
-            r.zeros = hd->zeros;
-            r.h = w.h + rs.row0 * C;
-            r.skip = w.wn_out + rs.row0 * n_out;
-            r.skip_ld = n_out;
-            r.skip_bstride = nsteps * n_out;
-            r.hs_bstride = nsteps * C;
-            r.skip_init = (l == 0);
-            st = run_resskip_layer(cx, r, t, &t.run, ext, &hd->last_resskip_kernel[l]);
-        } else {
-            hd->last_resskip_kernel[l] = MBX_RESSKIP_K_NONE;       // the tail kernel adds the last layer's share
-        }
+        if (st != MBX_OK) return st;
+        if (!fold)
+            st = run_resskip_layer(cx, resskip_args(hd, t, C, l, w.a, w.h, w.skip, nsteps * C, rs, B), t, nullptr, false, plan.resskip[l], false);
+        else if (l < L - 1)                                   // (the tail kernel adds the last layer's share)
+            st = run_resskip_layer(cx, resskip_fold_args(cx, t, l, l == 0 && fold_start, rs), t, &t.run, l == 0 && fold_start, plan.resskip[l],
+                                   plan.planes_out[l]);
         if (st != MBX_OK) return st;
     }
     return run_tail(cx);
@@ -944,9 +845,7 @@ mbx_status run_wavenet_blocks(ForwardCtx &cx) {
     const int L = c.wn_layers, n_out = c.wn_out_channels, M = c.subbands;
     const int nsub1 = 1 + c.wt_subharm_channels;
     const float *x_in = nullptr;                 // output of the previous block (B, rows, n_out)
-    // mbx_conv_form_info.gate_kernel and mbx_kernel_report_info.resskip_kernel: block-major, entry b * L + l (as many as
-    // MBX_MAX_WN_LAYERS holds)
-    hd->last_gate_layers = std::min<int>((int)hd->blocks.size() * L, MBX_MAX_WN_LAYERS);
+    hd->last_plan = cx.plan;                     // (plan_blocks: the report of as many layers as MBX_MAX_WN_LAYERS holds)
     for (size_t b = 0; b < hd->blocks.size(); ++b) {
         const auto &blk = hd->blocks[b];
         const WnBlockTensors &bt = hd->wn[b];
@@ -966,15 +865,11 @@ mbx_status run_wavenet_blocks(ForwardCtx &cx) {
         }
         for (int l = 0; l < L; ++l) {
             const WnLayerTensors &t = bt.layer[l];
-            // the Winograd F(4,3) form when the host supplied the block's weight image and the layer fits (SAME padding,
-            // k = 3, power-of-two dilation), the direct form otherwise
-            const size_t slot = b * L + l;
+            const BlockLayerPlan lp = plan_block_layer(hd, b, l, B, T);
             const mbx::ConvArgs g = gate_args(hd, t, C, c.wn_dilations[l], w.mb_h, w.mb_a, rows * C, sp, B, cond, (long long)T * blk.ccu * 2 * C);
-            mbx_status st = run_gate_layer(cx, g, t, nullptr, true, slot < MBX_MAX_WN_LAYERS ? &hd->last_gate_kernel[slot] : nullptr,
-                                           slot < MBX_MAX_WN_LAYERS ? &hd->last_gate_block_channels[slot] : nullptr);
+            mbx_status st = run_gate_layer(cx, g, t, lp.gate, nullptr);
             if (st != MBX_OK) return st;
-            st = run_resskip_layer(cx, resskip_args(hd, t, C, l, w.mb_a, w.mb_h, w.mb_skip, rows * C, sp, B), t, nullptr, false,
-                                   slot < MBX_MAX_WN_LAYERS ? &hd->last_resskip_kernel[slot] : nullptr);
+            st = run_resskip_layer(cx, resskip_args(hd, t, C, l, w.mb_a, w.mb_h, w.mb_skip, rows * C, sp, B), t, nullptr, false, lp.resskip, false);
             if (st != MBX_OK) return st;
         }
         // end convolution (reference custom_AE_layers.py:337-340); the last block's output is the stage "wn_out" unless an
@@ -999,8 +894,6 @@ mbx_status run_wavenet_blocks(ForwardCtx &cx) {
     mbx::ConvArgs pn = conv_args(x_in, cx.nsteps * n_out, n_out, n_frames, c.steps_per_frame, (int)cx.nsteps, B, hd->tab.post_w,
                                  hd->tab.post_b, 1, n_out, M, 1, 0, MBX_PAD_ZERO, w.sub, cx.nsteps * M, M);
     mbx::launch_conv1d(pn, mbx::EPI_LINEAR, stream);
-    hd->last_tail_kernel = MBX_TAIL_K_UNFUSED;      // every block's end convolution and the post-net are generic convolutions
-    hd->last_tail_folded = 0;
     return MBX_OK;
 }
 
@@ -1090,7 +983,7 @@ void publish_stages(ForwardCtx &cx) {
     sg["f0"] = {w.f0, npulse, npulse};
     sg["pulse"] = {w.pulse, npulse * (1 + c.wt_subharm_channels), npulse * (1 + c.wt_subharm_channels)};
     sg["cond"] = {w.cond, (long long)T * cx.cond_cout, (long long)T * cx.cond_cout};
-    if (cx.planes_only) {
+    if (cx.plan.planes_only) {
         // split precision with the planes as the hidden state: the float32 tensor was not written; per row [C8 hi halves | C8 lo'
         // halves] = C8 float32 words (engine.py::stage rebuilds hi + 2^-11 lo' from it)
         sg.erase("wn_hidden");
@@ -1099,7 +992,7 @@ void publish_stages(ForwardCtx &cx) {
         sg.erase("wn_hidden_planes");
         sg["wn_hidden"] = {w.h, nsteps * C, nsteps * C};
     }
-    if (!hd->fold_skip) sg["wn_skip"] = {w.skip, nsteps * C, nsteps * C};
+    if (!hd->pol.fold_skip) sg["wn_skip"] = {w.skip, nsteps * C, nsteps * C};
     else sg.erase("wn_skip");
     if (!hd->blocks.empty()) {
         // several blocks (run_wavenet_blocks): the hidden state and the skip sum of the last block, at its own rate
@@ -1139,7 +1032,7 @@ LayerGeom layer_geom(const mbx_handle *hd) {
     const int L = c.wn_layers, C = c.wn_channels;
     // needs the folded graph (no separate start / skip tensors to carry) and the F(2,3) gate kernel (per-layer regions
     // start between conditioning rows: ConvArgs::cond_phase)
-    if (!hd->fold_skip || !hd->fold_start || !hd->winograd || c.wn_kernel_size != 3 || L < 2) return g;
+    if (!hd->pol.fold_skip || !hd->pol.fold_start || !hd->pol.winograd || c.wn_kernel_size != 3 || L < 2) return g;
     for (int l = 1; l < L; ++l) {
         const int d = c.wn_dilations[l];
         if (!hd->wn[0].layer[l].wino2w || d > 16 || (d & (d - 1)) != 0) return g;
@@ -1166,6 +1059,21 @@ LayerGeom layer_geom(const mbx_handle *hd) {
     }
     g.floats = (int)off;
     return g;
+}
+
+// What a whole-item mbx_forward of (batch, max_frames) would run (mbx_plan): check_forward_args' planning without a workspace
+mbx::WnPlan plan_whole_items(const mbx_handle *hd, int batch, int max_frames) {
+    if (!hd->blocks.empty()) return plan_blocks(hd, batch, max_frames);
+    const mbx_config &c = hd->cfg;
+    mbx::WnGeometry geo;
+    geo.B = batch;
+    geo.nsteps = (long long)max_frames * c.steps_per_frame;
+    geo.cond_bstride = (long long)max_frames * 2 * c.wn_channels * c.cond_conv_upsampling;
+    for (int l = 0; l < c.wn_layers; ++l) {
+        geo.gate[l] = mbx::WnSpan{(int)geo.nsteps, 0, 0, 0};
+        geo.res_rows[l] = (int)geo.nsteps;
+    }
+    return mbx::wn_plan(hd->pol, geo);
 }
 
 // One forward pass, in the order of DESIGN.md section 1.  Only enqueues kernels on the caller's stream.

@@ -89,6 +89,13 @@ struct WnLayerTensors {
     FoldImages run;                   // the set the layer runs with: start for layer 0 under mbx_handle::fold_start, else plain
 };
 
+// the WN_IMG_* bits of a layer (wn_plan.h): which of its weight images are there, the fold set being the one it runs with
+inline unsigned layer_images(const WnLayerTensors &t) {
+    return (t.wino4w ? mbx::WN_IMG_WINO4W : 0) | (t.wino2w ? mbx::WN_IMG_WINO2W : 0) | (t.run.fold ? mbx::WN_IMG_FOLD : 0) |
+           (t.run.wide ? mbx::WN_IMG_WIDE : 0) | (t.run.wave ? mbx::WN_IMG_WAVE : 0) | (t.run.f16 ? mbx::WN_IMG_F16 : 0) |
+           (t.packed ? mbx::WN_IMG_PACKED : 0);
+}
+
 struct WnBlockTensors {
     const DevTensor *start_w = nullptr, *start_b = nullptr, *end_w = nullptr, *end_b = nullptr, *end_packed = nullptr;
     const DevTensor *tail_fold = nullptr, *tail_fold_b = nullptr;
@@ -129,11 +136,8 @@ struct mbx_handle {
     // derived
     int f0_time_factor = 1, vtf_time_factor = 1;
     long long subnet_buf_per_frame = 0;   // floats per frame of one ping-pong buffer
-    int last_gate_kernel[MBX_MAX_WN_LAYERS] = {};   // MBX_GATE_K_* of the most recent forward (mbx_conv_form_info.gate_kernel)
-    int last_gate_layers = 0;
-    int last_gate_block_channels[MBX_MAX_WN_LAYERS] = {};   // gate channels per F(4,3) block of that forward's layers, 0: no F(4,3) block (mbx_kernel_report)
-    int last_resskip_kernel[MBX_MAX_WN_LAYERS] = {};   // MBX_RESSKIP_K_* per layer, indexed as last_gate_kernel (mbx_kernel_report)
-    int last_tail_kernel = 0, last_tail_folded = 0;    // MBX_TAIL_K_* of the most recent forward; 1: it ran as the folded tail
+    mbx::WnPolicy pol;                    // what kernel selection depends on (wn_plan.h): the form, the tuning pins, split precision, folds, images
+    mbx::WnPlan last_plan;                // the plan of the most recent forward (mbx_conv_form, mbx_kernel_report); n_layers == 0: none yet
     bool f0_full64 = false;               // mbx_config.f0_accumulate == MBX_F0_ACC_F64 and the F0-net has the shape (conv [prelu | leaky])* head
                                           // with its "<layer>.w64" tensors: float64 weights and hidden layers (f0_chain_is_full64)
     std::vector<mbx_subnet_op> cond_ops;  // pre-conditioning convolutions + the conditioning layer (empty: conditioning disabled)
@@ -146,17 +150,8 @@ struct mbx_handle {
     };
     std::vector<WnBlock> blocks;
     long long mb_hc_per_frame = 0;                 // max over the blocks of rows per frame x channels
-    bool fold_skip = false;      // skip path folded into the end convolution (needs the *.fold tensors)
-    bool fold_start = false;     // start convolution folded into layer 0 (needs fold_skip and the *.start_fold / *.fold_start tensors)
-    bool winograd4_always = false;   // mbx_config.batch_invariant with F(4,3): the large-launch kernel shapes at every size
-    int gate_small_shape = -1;       // mbx_config.tune_gate_shape: pins the F(4,3) block shape (0: 256-row and 3: 256-row blocks of two column tiles, at every launch size | 1: product-split | 2: product-split, half column tiles, small launches only; same bits)
-    long long resskip_wave_tiles = 2048;   // default policy: res/skip launches of at most this many 16-row tiles run the wave-tiled kernel
-    int resskip_split = 0;           // mbx_config.tune_resskip_split
-    bool split_f16 = false;          // mbx_config.wn_precision == MBX_PRECISION_SPLIT_F16 and the images are there
-    bool split_f16_gate = false;     // ... for the gate layers too (wn_gate_f16.hip)
     float calib_err_split = -1.f;    // max |audio(split precision) - audio(float32 direct form)| of the calibration run
     int split_rejected = 0;          // the calibration switched the split precision off (error above the threshold, or not finite)
-    int winograd = 0;            // gate layer form in effect: 0 direct, 2 Winograd F(2,3), 4 Winograd F(4,3) (needs the packed weights)
     // what mbx_conv_form reports
     int calibrated = 0;
     float calib_err43 = -1.f, calib_err23 = -1.f, calib_ref = 0.f, calib_threshold = 0.f;
@@ -215,7 +210,7 @@ inline Workspace carve(const mbx_handle *hd, char *base, int B, int T) {
     w.h = take(B * nsteps * c.wn_channels);
     w.a = take(B * nsteps * (c.wn_channels + 16));   // layer 0 appends the excitation channels to its rows (wn_gate0.hip)
     w.skip = take(B * nsteps * c.wn_channels);
-    w.h16 = take(hd->split_f16_gate ? B * nsteps * (size_t)((c.wn_channels + 7) / 8 * 8) : 0);
+    w.h16 = take(hd->pol.split_f16_gate ? B * nsteps * (size_t)((c.wn_channels + 7) / 8 * 8) : 0);
     w.wn_out = take(B * nsteps * c.wn_out_channels);
     w.sub = take(B * nsteps * c.subbands);
     w.exc = take(BT * c.hop_size);
@@ -407,6 +402,7 @@ int current_form(const mbx_handle *hd);
 mbx_status calibrate_on_synthetic_mel(mbx_handle *hd, bool forms);
 // mbx_forward.hip
 LayerGeom layer_geom(const mbx_handle *hd);
+mbx::WnPlan plan_whole_items(const mbx_handle *hd, int batch, int max_frames);
 mbx_status forward_impl(mbx_handle *hd, const float *mel, const int32_t *n_frames, int32_t batch, int32_t max_frames,
                         const float *noise, float *audio, void *workspace, size_t workspace_bytes, void *hip_stream,
                         const ForwardExtras &ex = ForwardExtras());

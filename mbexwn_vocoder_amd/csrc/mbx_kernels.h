@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mbexwn.h"   // MBX_RESSKIP_K_* / MBX_TAIL_K_*: what the res/skip and tail launchers return
+#include "wn_plan.h"   // ConvArgs / Gate0Args (mbx_args.h), the WaveNet kernels' selectors and shape constants
 
 namespace mbx {
 
@@ -39,76 +40,6 @@ __device__ __forceinline__ float wn_gate_act(int kind, float zt, float zs) {
 // ---------------------------------------------------------------------------------------------
 // conv1d as an implicit GEMM on the fp32 matrix cores (conv_mfma.hip; the mel-rate sub-nets: conv_mel.hip)
 // ---------------------------------------------------------------------------------------------
-enum ConvEpilogue {
-    EPI_LINEAR = 0,   // y = acc + bias, optional PReLU / leaky slope
-    EPI_GATE = 1,     // a = tanh(acc_t + bias_t + cond_t) * sigmoid(acc_s + bias_s + cond_s)
-    EPI_RESSKIP = 2   // h += r[:, :C] ; skip (+)= r[:, C:]   (last layer: skip += r)
-};
-
-struct ConvArgs {
-    // input (batch, rows, cin) channels-last
-    const float *x;
-    long long x_bstride;      // floats between batch items
-    int ldx;                  // floats between rows
-    // rows per item: n_frames ? n_frames[b] * rows_per_frame : max_rows
-    const int *n_frames;
-    int rows_per_frame;
-    int max_rows;
-    int batch;
-    // weights (ks*cin, cout) row-major, bias (cout) or null
-    const float *w;
-    const float *bias;
-    int cin, cout, ks, dil, pad_l, pad_mode;
-    // output
-    float *out;
-    long long out_bstride;
-    int ldo;
-    // EPI_LINEAR extras
-    const float *alpha;       // PReLU slopes (cout) or null
-    float leaky;              // slope when use_leaky
-    int use_leaky;
-    // EPI_GATE extras: conditioning (batch, rows/cond_up, 2*C), interpolated on the fly
-    const float *cond;
-    long long cond_bstride;
-    int cond_up;
-    int cond_phase;           // item row r sits at conditioning-rate position r + cond_phase (0 <= cond_phase < cond_up; F(2,3) gate kernel only)
-    const float *lerp_w0, *lerp_w1;   // (cond_up) float32 interpolation weights
-    int channels;             // C (gate: cout == 2C, out has C columns; res/skip: split point)
-    int gate_act;             // EPI_GATE and the gate kernels: 0 gtu, 1 gfu, 2 gsu, 3 glu (wn_gate_act)
-    // EPI_RESSKIP extras
-    float *h;                 // (batch, rows, C) updated in place
-    float *skip;              // (batch, rows, skip_ld)
-    int skip_ld;              // floats between rows of skip (0: C)
-    long long skip_bstride;   // floats between batch items of skip (0: max_rows * skip_ld, or hs_bstride when skip_ld == 0)
-    long long hs_bstride;
-    int skip_init;            // 1: skip = s (first layer)  0: skip += s
-    int h_init;               // 1: h = r (first layer with the start convolution folded in: x carries [a | x'], cin > C)
-    int last_layer;           // 1: cout == C, everything goes to skip
-    int acc_preloaded;        // set by the launcher: accumulators start from bias + old value, epilogue only stores
-    int remap, n_tiles, m_tiles_per_item, m_tiles_total;   // XCD-aware 1-D grid (set by the launcher)
-    int out_row0, out_rows;   // wave-tiled F(2,3) gate kernel: only the rows [out_row0, out_row0 + out_rows) of every item are
-                              // computed (out_rows == 0: all rows; out_row0 a multiple of 2 * dil)
-    const float *zeros;       // >= 16 bytes of zeros in global memory (LDS-DMA source of padding lanes)
-    int fast_dma;             // set by the launcher: 32-bit source offsets are safe (LDS-DMA with a uniform base)
-    int tile0;                // set by launch_wn_gate_winograd4w: first column tile of the launch (the 256-row blocks that finish an odd
-                              // tile count behind the blocks of two column tiles), 0 otherwise
-    int vstride;              // set by launch_wn_gate_winograd4w for dilations above 16: every item is treated as vstride interleaved
-                              // virtual items (rows s, s + vstride, s + 2 vstride ...) convolved with dilation dil / vstride
-    // split half precision (mbx_config.wn_precision): the hidden state as fp16 planes, written by wn_resskip_f16_kernel and read
-    // by wn_gate_f16_kernel -- row r: [hi: h_split_ld halves][lo': h_split_ld halves] (h_split_ld = channels rounded up to 8,
-    // the padding zero), i.e. h_split_ld float32 words per row
-    float *h_split;
-    long long h_split_bstride;   // float32 words between batch items
-    int h_split_ld;
-    int h_planes_only;        // wn_resskip_f16_kernel: the planes ARE the hidden state -- old values are read from them (hi + 2^-11 lo'),
-                              // the float32 tensor h is neither read nor written (every consumer of h takes the planes)
-    int tune_split;           // wave-tiled res/skip kernel: 1..3 pins its column split (mbx_config.tune_resskip_split; same bits), 0: by launch size
-    // EPI_LINEAR, the F0-net (conv_mel.hip: conv1d_f64_tile / conv1d_f64_tile32): contraction on v_mfma_f64_16x16x4_f64
-    int precise;              // 1: float64 accumulation; with only this set x, w and out are the float32 ones above (one rounding per output)
-    const double *x64;        // input as float64 (same strides, counted in elements) instead of x; needs w64
-    const double *w64;        // weights (ks*cin, cout) as float64 instead of w
-    double *out64;            // output as float64 (same strides) instead of out
-};
 
 void launch_conv1d(const ConvArgs &a, int epilogue, hipStream_t stream);
 // n <= 3 independent EPI_LINEAR convolutions; the mel-rate ones share one launch (conv_mel.hip)
@@ -116,63 +47,50 @@ void launch_conv1d_group(const ConvArgs *convs, int n, hipStream_t stream);
 // one EPI_LINEAR convolution in a launch of its own with the mel-rate tiles (conv_mel.hip); false: the shape is not theirs,
 // nothing was launched
 bool launch_conv1d_mel_single(const ConvArgs &a, hipStream_t stream);
+// ---- WaveNet layers.  Which kernel runs a layer, and whether the layer fits it, is decided on the host by the selectors of
+// wn_plan.h; a launcher is told the instantiation, checks what the caller guarantees (non-null, aligned pointers), computes the
+// grid and launches.  Return value: nullptr, or what is wrong with the pointers (nothing was launched).
 // Winograd F(4,3) form on v_mfma_f32_16x16x4_f32, wave tile 16 groups x 64 columns (wn_winograd4w.hip); a.w = image of
-// engine.pack_winograd4w_weights (ceil(C/32), ceil(C/8), 3072); split: 128-row blocks whose waves split the six products
-// (same bits as the 256-row blocks)
-// shape: 0 = 256-row blocks, 1 = 128-row product-split blocks, 2 = product-split blocks of half a column tile, 3 = 256-row blocks
-// of TWO column tiles (d <= 16, cond_up >= 10; an odd last tile runs in 256-row blocks): same bits, all four
-bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream);
+// engine.pack_winograd4w_weights (ceil(C/32), ceil(C/8), 3072); k.shape: 0 = 256-row blocks, 1 = 128-row blocks whose waves
+// split the six products, 2 = product-split blocks of half a column tile, 3 = 256-row blocks of TWO column tiles (d <= 16,
+// cond_up >= 10; an odd last tile runs in 256-row blocks): same bits, all four
+const char *launch_wn_gate_winograd4w(const ConvArgs &a, const GateChoice &k, hipStream_t stream);
 // Winograd F(2,3) form on v_mfma_f32_16x16x4_f32 with wave-granular tiles (wn_winograd2w.hip: streams, per-layer regions,
 // MBX_CONV_F23); a.w = image of engine.pack_winograd2w_weights (ceil(C/32), ceil(C/8), 2048)
-bool launch_wn_gate_winograd2w(const ConvArgs &a, hipStream_t stream);
+const char *launch_wn_gate_winograd2w(const ConvArgs &a, hipStream_t stream);
 // the dilated convolution + gate in split half precision, direct form (wn_gate_f16.hip; opt-in, mbx_config.wn_precision);
-// a.w = image of engine.pack_gate_f16_weights (ceil(C/32), ceil(C/32), 6144)
-int launch_wn_gate_f16(const ConvArgs &a, hipStream_t stream);   // MBX_GATE_K_SPLIT_F16* of the kernel launched, 0: does not fit
+// a.w = image of engine.pack_gate_f16_weights (ceil(C/32), ceil(C/32), 6144); kernel: MBX_GATE_K_SPLIT_F16*
+const char *launch_wn_gate_f16(const ConvArgs &a, int kernel, hipStream_t stream);
 // First WaveNet layer with the start convolution folded into it (wn_gate0.hip)
-struct Gate0Args {
-    const float *pulse;       // (batch, rows * pulse_channels): the excitation, folded to pulse_channels per row
-    long long pulse_bstride;
-    const float *noise;       // (batch, rows) or null
-    long long noise_bstride;
-    float sigma;
-    int pulse_channels;
-    const int *n_frames;
-    int rows_per_frame, max_rows, batch;
-    const float *w;           // image of engine.fold_start_weights (ceil(C/32), 3, 2, 64, 4)
-    const float *bias;        // (2C) gate bias or null
-    int channels, dil;
-    int causal;               // 0: SAME (taps t - d, t, t + d), 1: CAUSAL (taps t - 2d, t - d, t)
-    const float *cond;        // (batch, rows/cond_up, 2C)
-    long long cond_bstride;
-    int cond_up;
-    const float *lerp_w0, *lerp_w1;
-    int gate_act;             // 0 gtu, 1 gfu, 2 gsu, 3 glu (wn_gate_act)
-    float *out;               // (batch, rows, ldo): C gate channels, then x' padded to 16 channels if write_inputs
-    long long out_bstride;
-    int ldo, write_inputs;
-    int n_tiles, m_tiles_per_item;   // set by the launcher
-};
-bool launch_wn_gate0(const Gate0Args &a, hipStream_t stream);
-bool wn_gate0_fits(int channels, int pulse_channels, int dil, int cond_up);
-// The res/skip launchers return the MBX_RESSKIP_K_* of the instantiation they launched, MBX_RESSKIP_K_NONE (0): the layer does
-// not fit, nothing was launched.
-// WaveNet residual/skip layer for large row counts (wn_resskip.hip); a.w = host-packed weights (ceil(cout/128), ceil(C/16), 2048)
-int launch_wn_resskip(const ConvArgs &a, hipStream_t stream);
+const char *launch_wn_gate0(const Gate0Args &a, hipStream_t stream);
+// the dynamic-LDS opt-ins of the kernels above, once per handle with its device current (mbx_create): WN_LDS_* bits granted
+unsigned wn_gate_f16_lds_opt_in();
+unsigned wn_gate_winograd4q_lds_opt_in();
+// WaveNet residual/skip layer for large row counts (wn_resskip.hip); a.w = host-packed weights (ceil(cout/128), ceil(C/16), 2048);
+// kernel: MBX_RESSKIP_K_PACKED64 | _PACKED128
+const char *launch_wn_resskip(const ConvArgs &a, int kernel, hipStream_t stream);
 // the same layer for large launches, one block owning all columns of its rows (wn_resskip_wide.hip); a.w = image of
-// engine.pack_resskip_wide_weights (ceil(cin/8), ceil(cout/32), 256)
-int launch_wn_resskip_wide(const ConvArgs &a, hipStream_t stream);
+// engine.pack_resskip_wide_weights (ceil(cin/8), ceil(cout/32), 256); kernel: MBX_RESSKIP_K_WIDE*
+const char *launch_wn_resskip_wide(const ConvArgs &a, int kernel, hipStream_t stream);
 // the same layer for small launches (one utterance, streaming ticks), tiled at wave granularity (wn_resskip_wave.hip);
-// a.w = image of engine.pack_resskip_wave_weights (ceil(cin/16), 12, 512)
-int launch_wn_resskip_wave(const ConvArgs &a, hipStream_t stream);
+// a.w = image of engine.pack_resskip_wave_weights (ceil(cin/16), 12, 512); kernel: MBX_RESSKIP_K_WAVE*
+const char *launch_wn_resskip_wave(const ConvArgs &a, int kernel, hipStream_t stream);
 // the same layer in split half precision (wn_resskip_f16.hip; opt-in, mbx_config.wn_precision); a.w = image of
 // engine.pack_resskip_f16_weights (ceil(cin/32), 12, 1024); a.gate_act must be set (glu is refused)
-int launch_wn_resskip_f16(const ConvArgs &a, hipStream_t stream);
+const char *launch_wn_resskip_f16(const ConvArgs &a, hipStream_t stream);
+// the pointers of a folded res/skip launch (wide, wave-tiled, split half precision): the workspace is carved in 256-byte
+// pieces and tensors come from the device allocator, so a failure here is a bug of the caller
+inline const char *wn_resskip_folded_pointers(const ConvArgs &a) {
+    const bool ok = (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && (uintptr_t)a.h % 8 == 0 && (uintptr_t)a.skip % 8 == 0 &&
+                    (!a.bias || (uintptr_t)a.bias % 8 == 0) && a.zeros && a.h && a.skip;
+    return ok ? nullptr : "folded res/skip layer: a pointer is null or not aligned";
+}
 // WaveNet end convolution + post-net in one pass over the skip tensor (wn_tail.hip); w_end_packed = host-packed
-// weights (ceil(C/8), 2, 32, 4); returns the MBX_TAIL_K_* of the kernel it chose, MBX_TAIL_K_NONE (0): shapes do not fit
-int launch_wn_tail(const float *skip, long long skip_bstride, const int *n_frames, int rows_per_frame, int max_rows,
-                   int batch, int C, const float *w_end_packed, const float *b_end, int n_out, const float *w_post,
-                   const float *b_post, int M, const float *y_acc, float *y, long long y_bstride, float *sub,
-                   long long sub_bstride, hipStream_t stream);
+// weights (ceil(C/8), 2, 32, 4); kind: MBX_TAIL_K_TAIL2_* | MBX_TAIL_K_TAIL
+const char *launch_wn_tail(int kind, const float *skip, long long skip_bstride, const int *n_frames, int rows_per_frame, int max_rows,
+                           int batch, int C, const float *w_end_packed, const float *b_end, int n_out, const float *w_post,
+                           const float *b_post, int M, const float *y_acc, float *y, long long y_bstride, float *sub,
+                           long long sub_bstride, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // element-wise / bandwidth-type stages (elementwise.hip)

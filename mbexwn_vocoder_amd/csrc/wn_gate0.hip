@@ -37,11 +37,9 @@ namespace mbx {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int G0_ROWS = 256;
+// (G0_ROWS = 256, G0_MAX_DIL = 16, G0_COND_ROWS = 32: wn_plan.h, the selector reads them)
 
-constexpr int G0_MAX_DIL = 16;
 constexpr int G0_XROWS = G0_ROWS + 2 * G0_MAX_DIL;      // staged rows of x'
-constexpr int G0_COND_ROWS = 32;
 constexpr int G0_CS = 68;                               // floats between conditioning rows in LDS (16-byte reads of rows t2, t2 + 1)
 
 template <int KIND>
@@ -257,22 +255,12 @@ __global__ __launch_bounds__(256) void wn_gate0_kernel(Gate0Args p) {
     }
 }
 
-// geometry the kernel is built for (mbx_create keeps the un-folded first layer otherwise)
-bool wn_gate0_fits(int channels, int pulse_channels, int dil, int cond_up) {
-    return pulse_channels >= 1 && pulse_channels + 2 <= 8 && channels % 4 == 0 && cond_up >= 1 && dil >= 1 &&
-           dil <= G0_MAX_DIL && (G0_ROWS + cond_up - 2) / cond_up + 2 <= G0_COND_ROWS;
-}
-
-// a.w: image of engine.fold_start_weights (ceil(C/32), 3, 2, 64, 4); false: the layer does not fit
-bool launch_wn_gate0(const Gate0Args &a, hipStream_t stream) {
-    const bool ok = a.pulse_channels >= 1 && a.pulse_channels + 2 <= 8 && a.channels % 4 == 0 && a.ldo % 4 == 0 &&
-                    a.out_bstride % 4 == 0 && (uintptr_t)a.out % 16 == 0 && (uintptr_t)a.w % 16 == 0 && a.cond &&
-                    (uintptr_t)a.cond % 8 == 0 && a.cond_bstride % 2 == 0 && a.cond_up >= 1 && a.lerp_w0 && a.lerp_w1 &&
-                    a.dil >= 1 && a.dil <= G0_MAX_DIL && (G0_ROWS + a.cond_up - 2) / a.cond_up + 2 <= G0_COND_ROWS &&
-                    (uintptr_t)a.cond % 16 == 0 && a.cond_bstride % 4 == 0 && (!a.write_inputs || a.ldo >= a.channels + 16) &&
-                    (uintptr_t)a.bias % 16 == 0;
-    if (!ok) return false;
-    if (a.max_rows <= 0 || a.batch <= 0) return true;
+// a.w: image of engine.fold_start_weights (ceil(C/32), 3, 2, 64, 4); the layer fits (wn_gate0_select)
+const char *launch_wn_gate0(const Gate0Args &a, hipStream_t stream) {
+    if ((uintptr_t)a.out % 16 != 0 || (uintptr_t)a.w % 16 != 0 || !a.cond || (uintptr_t)a.cond % 16 != 0 || !a.lerp_w0 || !a.lerp_w1 ||
+        (uintptr_t)a.bias % 16 != 0)
+        return "folded first layer: a pointer is null or not 16-byte aligned";
+    if (a.max_rows <= 0 || a.batch <= 0) return nullptr;
     Gate0Args r = a;
     r.n_tiles = (a.channels + 31) / 32;
     r.m_tiles_per_item = (a.max_rows + G0_ROWS - 1) / G0_ROWS;
@@ -281,7 +269,7 @@ bool launch_wn_gate0(const Gate0Args &a, hipStream_t stream) {
     else if (a.gate_act == 1) hipLaunchKernelGGL(wn_gate0_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, stream, r);
     else if (a.gate_act == 2) hipLaunchKernelGGL(wn_gate0_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, stream, r);
     else hipLaunchKernelGGL(wn_gate0_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, stream, r);
-    return true;
+    return nullptr;
 }
 
 }  // namespace mbx

@@ -35,16 +35,13 @@ namespace mbx {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int GH_ROWS = 256;
-constexpr int GH_HALO = 16;
+// (GH_ROWS = 256, GH_HALO = 16, GH_BK = 32, GH_COND_ROWS = 28 conditioning rows of 64 floats: wn_plan.h, the selector reads them)
 constexpr int GH_AROWS = GH_ROWS + 2 * GH_HALO;            // 288 staged rows
-constexpr int GH_BK = 32;
 constexpr int GH_A_FLOATS = GH_AROWS * GH_BK;              // 9216 floats = 36 KB
 constexpr int GH_B_FLOATS = 3 * 4 * 2 * 256;               // 3 taps x 4 tiles x 2 images x 1 KB = 24 KB
 constexpr int GH_X = 0;                                    // float32 landing tile
 constexpr int GH_Y = GH_A_FLOATS;                          // operand tile (hi / lo' halves), same size
 constexpr int GH_B = 2 * GH_A_FLOATS;                      // two weight stages
-constexpr int GH_COND_ROWS = 28;                           // conditioning rows of 64 floats (cond_up >= 10)
 constexpr int GH_COND = GH_B + 2 * GH_B_FLOATS;
 constexpr int GH_TAB = GH_COND + GH_COND_ROWS * 64;
 constexpr int GH_LERP = GH_TAB + GH_ROWS;
@@ -507,59 +504,45 @@ __global__ __launch_bounds__(512, 1) void wn_gate_f16w_kernel(ConvArgs p, int lo
     }
 }
 
+// The dynamic-LDS sizes of the three kernels are attributes of the (function, device) pair: mbx_create asks for them once,
+// with the handle's device current; returns the WN_LDS_* bits of the groups the device granted.
+unsigned wn_gate_f16_lds_opt_in() {
+    unsigned bits = 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_f16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            GH_LDS_FLOATS * (int)sizeof(float)) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_f16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            GH_LDS_FLOATS * (int)sizeof(float)) == hipSuccess)
+        bits |= WN_LDS_GATE_F16;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_f16w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            GW_LDS_FLOATS * (int)sizeof(float)) == hipSuccess)
+        bits |= WN_LDS_GATE_F16W;
+    (void)hipGetLastError();
+    return bits;
+}
+
 // a.w must point at the image of engine.pack_gate_f16_weights (ceil(C/32) column tiles, ceil(C/32) steps, 6144 floats);
-// returns the MBX_GATE_K_* of the instantiation it launched -- MBX_GATE_K_SPLIT_F16_WIDE: wn_gate_f16w_kernel, MBX_GATE_K_SPLIT_F16:
-// wn_gate_f16_kernel<true>, MBX_GATE_K_SPLIT_F16_F32H: wn_gate_f16_kernel<false> -- or MBX_GATE_K_NONE (0) if the layer does not
-// fit (the caller then runs the float32 kernels).  wn_gate_f16_kernel<false> reads the float32 hidden state: it runs where the
-// res/skip layer in front left no planes, which a legal tensor table reaches -- one without wn.res_skip_0.fold_start_f16 runs
-// layer 0's res/skip in float32 and layer 1's gate here (tests/test_gpu_wavenet_stages.py: speech-split-f32h).
-int launch_wn_gate_f16(const ConvArgs &a, hipStream_t stream) {
-    int log2d = 0;
-    while ((1 << log2d) < a.dil) ++log2d;
-    const bool ok = a.ks == 3 && (1 << log2d) == a.dil && a.dil <= GH_HALO && a.pad_l == a.dil && a.pad_mode == 0 &&
-                    a.cin % 4 == 0 && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 && a.channels % 4 == 0 && a.cin == a.channels &&
-                    a.cout == 2 * a.channels && (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && a.zeros && a.cond &&
-                    (uintptr_t)a.cond % 16 == 0 && a.cond_bstride % 4 == 0 && a.cond_up >= 1 && a.cond_up <= 64 &&
-                    (GH_ROWS + a.cond_up - 2) / a.cond_up + 2 <= GH_COND_ROWS && a.lerp_w0 && a.lerp_w1 &&
-                    a.cond_phase == 0 && a.out_rows == 0 && a.max_rows < (1 << 24) &&
-                    (!a.h_split || (a.h_split_ld % 8 == 0 && a.h_split_ld >= a.channels && a.h_split_bstride % 4 == 0 &&
-                                    (uintptr_t)a.h_split % 16 == 0));
-    if (!ok) return MBX_GATE_K_NONE;
-    // the attribute belongs to the (function, device) pair: a process may hold handles on several devices
-    static unsigned long long attr_devices = 0;       // bit d: set for device d (devices >= 64: set at every launch)
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return MBX_GATE_K_NONE;
-    const bool attr_set = dev >= 0 && dev < 64 && ((attr_devices >> dev) & 1ull);
-    static bool gw_ok = false;
-    if (!attr_set) {
-        gw_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_f16w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    GW_LDS_FLOATS * (int)sizeof(float)) == hipSuccess;
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_f16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GH_LDS_FLOATS * (int)sizeof(float)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_f16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GH_LDS_FLOATS * (int)sizeof(float)) != hipSuccess)
-            return MBX_GATE_K_NONE;
-        if (dev >= 0 && dev < 64) attr_devices |= 1ull << dev;
-    }
+// kernel: the MBX_GATE_K_SPLIT_F16* that wn_gate_f16_select chose for these arguments (a.h_split set for the two planes kernels)
+const char *launch_wn_gate_f16(const ConvArgs &a, int kernel, hipStream_t stream) {
+    const bool planes = kernel != MBX_GATE_K_SPLIT_F16_F32H;
+    if ((uintptr_t)a.x % 16 != 0 || (uintptr_t)a.w % 16 != 0 || !a.zeros || !a.cond || (uintptr_t)a.cond % 16 != 0 || !a.lerp_w0 ||
+        !a.lerp_w1 || planes != (a.h_split != nullptr) || (uintptr_t)a.h_split % 16 != 0)
+        return "split gate layer: a pointer is null or not 16-byte aligned";
+    const int log2d = wn_log2_ceil(a.dil);
     ConvArgs r = a;
     r.n_tiles = (a.channels + 31) / 32;
     r.m_tiles_per_item = (a.max_rows + GH_ROWS - 1) / GH_ROWS;
     r.m_tiles_total = r.m_tiles_per_item * a.batch;
     const long long blocks = 8LL * ((r.m_tiles_total + 7) / 8) * r.n_tiles;
-    // 256 x 128 tiles (pairs of column tiles) for launches of several rounds of blocks: 0.83 against 0.93 ms at 16 x 10 s; one
-    // utterance of 10 s is 315 such blocks on 256 CUs and keeps the 256 x 64 tiles (72.5 against 78.7 us).  Same bits.
-    const long long blocks2 = 8LL * ((r.m_tiles_total + 7) / 8) * ((r.n_tiles + 1) / 2);
-    if (a.h_split && gw_ok && (a.cin + GH_BK - 1) / GH_BK >= 2 && blocks2 >= 4 * 256) {
-        r.n_tiles = (r.n_tiles + 1) / 2;
+    if (kernel == MBX_GATE_K_SPLIT_F16_WIDE) {
+        r.n_tiles = (r.n_tiles + 1) / 2;                  // pairs of column tiles
+        const long long blocks2 = 8LL * ((r.m_tiles_total + 7) / 8) * r.n_tiles;
         hipLaunchKernelGGL(wn_gate_f16w_kernel, dim3((unsigned)blocks2), dim3(512), GW_LDS_FLOATS * sizeof(float), stream, r, log2d);
-        return MBX_GATE_K_SPLIT_F16_WIDE;
-    }
-    if (a.h_split) {
+    } else if (planes) {
         hipLaunchKernelGGL(wn_gate_f16_kernel<true>, dim3((unsigned)blocks), dim3(512), GH_LDS_FLOATS * sizeof(float), stream, r, log2d);
-        return MBX_GATE_K_SPLIT_F16;
+    } else {
+        hipLaunchKernelGGL(wn_gate_f16_kernel<false>, dim3((unsigned)blocks), dim3(512), GH_LDS_FLOATS * sizeof(float), stream, r, log2d);
     }
-    hipLaunchKernelGGL(wn_gate_f16_kernel<false>, dim3((unsigned)blocks), dim3(512), GH_LDS_FLOATS * sizeof(float), stream, r, log2d);
-    return MBX_GATE_K_SPLIT_F16_F32H;
+    return nullptr;
 }
 
 }  // namespace mbx

@@ -237,19 +237,14 @@ __global__ __launch_bounds__(256, MT == 2 ? 3 : 4) void wn_resskip_kernel(ConvAr
     }
 }
 
-// a.w must point at the host-packed weights (ceil(cout/128), ceil(C/16), 2048); returns MBX_RESSKIP_K_NONE if the layer does not fit
-int launch_wn_resskip(const ConvArgs &a, hipStream_t stream) {
-    const bool ok = a.ks == 1 && (a.h_init ? a.cin >= a.channels && !a.last_layer : a.cin == a.channels) && a.cin % 4 == 0 && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 &&
-                    (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && a.zeros && a.h && a.skip && a.cout > 0 &&
-                    (long long)a.max_rows * a.channels < (1LL << 31) &&
-                    (a.skip_ld ? a.cout <= a.channels + a.skip_ld : a.cout == (a.last_layer ? a.channels : 2 * a.channels));
-    if (!ok) return MBX_RESSKIP_K_NONE;
+// a.w must point at the host-packed weights (ceil(cout/128), ceil(C/16), 2048); kernel: MBX_RESSKIP_K_PACKED64 (64-row blocks) or
+// _PACKED128, as wn_resskip_select chose for these arguments
+const char *launch_wn_resskip(const ConvArgs &a, int kernel, hipStream_t stream) {
+    if ((uintptr_t)a.x % 16 != 0 || (uintptr_t)a.w % 16 != 0 || !a.zeros || !a.h || !a.skip) return "res/skip layer: a pointer is null or not 16-byte aligned";
     ConvArgs r = a;
     r.fast_dma = 1;                 // byte offsets are relative to the block's first row
     r.n_tiles = (a.cout + 127) / 128;
-    // 64-row blocks while the 128-row grid is less than three rounds of the 768 resident blocks (3 per CU x 256 CUs)
-    const long long big_blocks = (long long)((a.max_rows + 127) / 128) * a.batch * r.n_tiles;
-    const bool small = big_blocks < 3 * 768;
+    const bool small = kernel == MBX_RESSKIP_K_PACKED64;
     const int tile_rows = small ? 64 : 128;
     r.m_tiles_per_item = (a.max_rows + tile_rows - 1) / tile_rows;
     r.m_tiles_total = r.m_tiles_per_item * a.batch;
@@ -257,7 +252,7 @@ int launch_wn_resskip(const ConvArgs &a, hipStream_t stream) {
     // stages: three for the large shape (measured -4 % at batch 16), two for the small one (no difference at batch 1)
     if (small) hipLaunchKernelGGL((wn_resskip_kernel<1, 2>), dim3((unsigned)blocks), dim3(256), 0, stream, r);
     else hipLaunchKernelGGL((wn_resskip_kernel<2, 3>), dim3((unsigned)blocks), dim3(256), 0, stream, r);
-    return small ? MBX_RESSKIP_K_PACKED64 : MBX_RESSKIP_K_PACKED128;
+    return nullptr;
 }
 
 }  // namespace mbx

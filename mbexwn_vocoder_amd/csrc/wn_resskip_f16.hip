@@ -239,23 +239,16 @@ __global__ __launch_bounds__(512, 4) void wn_resskip_f16_kernel(ConvArgs p) {
     }
 }
 
-// a.w must point at the image of engine.pack_resskip_f16_weights (ceil(cin/32), 12, 1024 floats); returns MBX_RESSKIP_K_NONE if the
-// layer does not fit (the caller then runs the float32 kernels)
-int launch_wn_resskip_f16(const ConvArgs &a, hipStream_t stream) {
-    const bool ok = a.ks == 1 && (a.h_init ? a.cin >= a.channels : a.cin == a.channels) && !a.last_layer && a.skip_ld > 0 && a.cout <= 384 &&
-                    (!a.h_split || (a.h_split_ld % 8 == 0 && a.h_split_ld >= a.channels && a.h_split_ld <= a.cout + 32 && a.h_split_bstride % 4 == 0)) &&
-                    a.gate_act != 3 &&          // glu: the layer's input is not bounded by 1
-                    a.cin % 4 == 0 && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 && a.channels % 2 == 0 && a.skip_ld % 2 == 0 &&
-                    a.cout % 2 == 0 && a.cout <= a.channels + a.skip_ld && (uintptr_t)a.x % 16 == 0 &&
-                    (uintptr_t)a.w % 16 == 0 && (uintptr_t)a.h % 8 == 0 && (uintptr_t)a.skip % 8 == 0 &&
-                    (!a.bias || (uintptr_t)a.bias % 8 == 0) && a.hs_bstride % 2 == 0 && a.h && a.skip && a.zeros;
-    if (!ok) return MBX_RESSKIP_K_NONE;
+// a.w must point at the image of engine.pack_resskip_f16_weights (ceil(cin/32), 12, 1024 floats); the layer fits
+// (wn_resskip_f16_select)
+const char *launch_wn_resskip_f16(const ConvArgs &a, hipStream_t stream) {
+    if (const char *e = wn_resskip_folded_pointers(a)) return e;
     ConvArgs r = a;
     r.m_tiles_per_item = (a.max_rows + RH_ROWS - 1) / RH_ROWS;
     r.m_tiles_total = r.m_tiles_per_item * a.batch;
     const long long blocks = 16LL * ((r.m_tiles_total + 7) / 8);
     hipLaunchKernelGGL(wn_resskip_f16_kernel, dim3((unsigned)blocks), dim3(512), 0, stream, r);
-    return MBX_RESSKIP_K_SPLIT_F16;
+    return nullptr;
 }
 
 }  // namespace mbx

@@ -31,7 +31,7 @@ namespace mbx {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int RV_BK = 16;
+// (RV_BK = 16: wn_plan.h, the selector reads it)
 constexpr int RV_A_FLOATS = 16 * RV_BK;           // one wave tile of one slice: 256 floats = 1 KB
 constexpr int RV_PAIRS = 12;                      // pairs of the weight image (zero padded)
 
@@ -293,48 +293,21 @@ __global__ __launch_bounds__(256, (RvShape<NPW, NSTAGE>::WAVES_PER_SIMD)) void w
     }
 }
 
-// a.w must point at the image of engine.pack_resskip_wave_weights (ceil(cin/16), 12, 512); returns MBX_RESSKIP_K_NONE if the layer
-// does not fit (the caller then uses launch_wn_resskip).  The cut (pairs per wave) follows the number of wave tiles:
-// all columns per wave while the tiles alone give every SIMD about one wave, column splits below that.
-int launch_wn_resskip_wave(const ConvArgs &a, hipStream_t stream) {
-    const int np = (a.cout + 31) / 32;
-    const int nk = (a.cin + RV_BK - 1) / RV_BK;
-    const bool ok = a.ks == 1 && (a.h_init ? a.cin >= a.channels : a.cin == a.channels) && !a.last_layer && a.skip_ld > 0 &&
-                    (np == 11 || np == 12) && a.cin % 4 == 0 && nk >= 4 && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 &&
-                    a.channels % 2 == 0 && a.skip_ld % 2 == 0 && a.cout % 2 == 0 && a.cout <= a.channels + a.skip_ld &&
-                    (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && (uintptr_t)a.h % 8 == 0 &&
-                    (uintptr_t)a.skip % 8 == 0 && (!a.bias || (uintptr_t)a.bias % 8 == 0) && a.hs_bstride % 2 == 0 && a.zeros &&
-                    a.h && a.skip;
-    if (!ok) return MBX_RESSKIP_K_NONE;
+// a.w must point at the image of engine.pack_resskip_wave_weights (ceil(cin/16), 12, 512); kernel: the MBX_RESSKIP_K_WAVE* (the
+// cut: pairs per wave) that wn_resskip_wave_select chose for these arguments
+const char *launch_wn_resskip_wave(const ConvArgs &a, int kernel, hipStream_t stream) {
+    if (const char *e = wn_resskip_folded_pointers(a)) return e;
     ConvArgs r = a;
     r.fast_dma = 1;                 // byte offsets are relative to the tile's first row
     r.m_tiles_per_item = (a.max_rows + 15) / 16;
     r.m_tiles_total = r.m_tiles_per_item * a.batch;
     const unsigned groups = (unsigned)((r.m_tiles_total + 3) / 4);
-    // waves per SIMD with s column splits = tiles * s / 1024: take the cut whose last round is fullest
-    int split = a.tune_split;
-    if (split != 1 && split != 2 && split != 3) {
-        double best = -1.0;
-        for (int s = 1; s <= 3; ++s) {
-            const double per_simd = (double)r.m_tiles_total * s / 1024.0;
-            const double fill = per_simd / std::ceil(per_simd);
-            const double score = fill - 0.02 * (s - 1);            // prefer fewer splits (less re-reading of the rows)
-            if (score > best) {
-                best = score;
-                split = s;
-            }
-        }
-    }
     // (stages: 2, 3 and 4 measured the same for the all-columns cut: 41.5 / 41.9 / 42.1 us for a 10 s utterance)
-    if (split == 1) {
-        if (np == 11) hipLaunchKernelGGL((wn_resskip_wave_kernel<11, 3>), dim3(groups, 1), dim3(256), 0, stream, r);
-        else hipLaunchKernelGGL((wn_resskip_wave_kernel<12, 3>), dim3(groups, 1), dim3(256), 0, stream, r);
-    } else if (split == 2) {
-        hipLaunchKernelGGL((wn_resskip_wave_kernel<6, 4>), dim3(groups, 2), dim3(256), 0, stream, r);
-    } else {
-        hipLaunchKernelGGL((wn_resskip_wave_kernel<4, 4>), dim3(groups, 3), dim3(256), 0, stream, r);
-    }
-    return split == 1 ? (np == 11 ? MBX_RESSKIP_K_WAVE11 : MBX_RESSKIP_K_WAVE12) : split == 2 ? MBX_RESSKIP_K_WAVE6X2 : MBX_RESSKIP_K_WAVE4X3;
+    if (kernel == MBX_RESSKIP_K_WAVE11) hipLaunchKernelGGL((wn_resskip_wave_kernel<11, 3>), dim3(groups, 1), dim3(256), 0, stream, r);
+    else if (kernel == MBX_RESSKIP_K_WAVE12) hipLaunchKernelGGL((wn_resskip_wave_kernel<12, 3>), dim3(groups, 1), dim3(256), 0, stream, r);
+    else if (kernel == MBX_RESSKIP_K_WAVE6X2) hipLaunchKernelGGL((wn_resskip_wave_kernel<6, 4>), dim3(groups, 2), dim3(256), 0, stream, r);
+    else hipLaunchKernelGGL((wn_resskip_wave_kernel<4, 4>), dim3(groups, 3), dim3(256), 0, stream, r);
+    return nullptr;
 }
 
 }  // namespace mbx

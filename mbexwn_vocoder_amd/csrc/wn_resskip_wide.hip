@@ -29,7 +29,7 @@ namespace mbx {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RW_ROWS = 128;
-constexpr int RW_BK = 8;
+// (RW_BK = 8: wn_plan.h, the selector reads it)
 constexpr int RW_A_FLOATS = RW_ROWS * RW_BK;      // 1024 floats = 4 KB
 
 __device__ __forceinline__ void rw_lds_dma16(const float *src, unsigned lds_byte_addr) {
@@ -294,27 +294,17 @@ __global__ __launch_bounds__(512, 4) void wn_resskip_wide_kernel(ConvArgs p) {
 }
 
 // a.w must point at the image of engine.pack_resskip_wide_weights (ceil(cin/8), np, 256) with np = ceil(cout/32) in
-// {11, 12}; returns MBX_RESSKIP_K_NONE if the layer does not fit (the caller then uses launch_wn_resskip)
-int launch_wn_resskip_wide(const ConvArgs &a, hipStream_t stream) {
-    const int np = (a.cout + 31) / 32;
-    const bool ok = a.ks == 1 && (a.h_init ? a.cin >= a.channels : a.cin == a.channels) && !a.last_layer && a.skip_ld > 0 &&
-                    (np == 11 || np == 12) && a.cin % 4 == 0 && a.cin >= 3 * RW_BK && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 &&
-                    a.channels % 2 == 0 && a.skip_ld % 2 == 0 && a.cout % 2 == 0 && a.cout <= a.channels + a.skip_ld &&
-                    (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && (uintptr_t)a.h % 8 == 0 &&
-                    (uintptr_t)a.skip % 8 == 0 && (!a.bias || (uintptr_t)a.bias % 8 == 0) && a.hs_bstride % 2 == 0 && a.zeros &&
-                    a.h && a.skip;
-    if (!ok) return MBX_RESSKIP_K_NONE;
+// {11, 12}; kernel: the MBX_RESSKIP_K_WIDE* that wn_resskip_wide_select chose for these arguments
+const char *launch_wn_resskip_wide(const ConvArgs &a, int kernel, hipStream_t stream) {
+    if (const char *e = wn_resskip_folded_pointers(a)) return e;
     ConvArgs r = a;
     r.fast_dma = 1;                 // byte offsets are relative to the block's first row
     r.m_tiles_per_item = (a.max_rows + RW_ROWS - 1) / RW_ROWS;
     const long long blocks = (long long)r.m_tiles_per_item * a.batch;
-    // 11 pairs (C = 320): one block owns all columns of its rows.  12 pairs (C = 340) would need 96 accumulator registers
-    // per wave, which leaves one 8-wave block per CU (162 VGPRs; measured 0.53 of the peak): two blocks per row tile own
-    // six pairs each instead and read the rows of `a` twice (the second read is an L2 hit)
-    if (np == 11 && a.channels >= 320) hipLaunchKernelGGL((wn_resskip_wide_kernel<11, 1, 10>), dim3((unsigned)blocks), dim3(512), 0, stream, r);
-    else if (np == 11) hipLaunchKernelGGL((wn_resskip_wide_kernel<11, 1, 0>), dim3((unsigned)blocks), dim3(512), 0, stream, r);
+    if (kernel == MBX_RESSKIP_K_WIDE11_RES10) hipLaunchKernelGGL((wn_resskip_wide_kernel<11, 1, 10>), dim3((unsigned)blocks), dim3(512), 0, stream, r);
+    else if (kernel == MBX_RESSKIP_K_WIDE11) hipLaunchKernelGGL((wn_resskip_wide_kernel<11, 1, 0>), dim3((unsigned)blocks), dim3(512), 0, stream, r);
     else hipLaunchKernelGGL((wn_resskip_wide_kernel<6, 2, 0>), dim3((unsigned)(2 * blocks)), dim3(512), 0, stream, r);
-    return np == 12 ? MBX_RESSKIP_K_WIDE6X2 : a.channels >= 320 ? MBX_RESSKIP_K_WIDE11_RES10 : MBX_RESSKIP_K_WIDE11;
+    return nullptr;
 }
 
 }  // namespace mbx

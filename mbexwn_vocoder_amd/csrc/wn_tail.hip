@@ -258,35 +258,27 @@ __global__ __launch_bounds__(256) void wn_tail2_kernel(const float *skip, long l
     }
 }
 
-// returns the MBX_TAIL_K_* of the kernel the shapes take (an empty launch included), MBX_TAIL_K_NONE if they do not fit (caller
-// falls back to two generic convolutions)
-int launch_wn_tail(const float *skip, long long skip_bstride, const int *n_frames, int rows_per_frame, int max_rows,
-                   int batch, int C, const float *w_end_packed, const float *b_end, int n_out, const float *w_post,
-                   const float *b_post, int M, const float *y_acc, float *y, long long y_bstride, float *sub,
-                   long long sub_bstride, hipStream_t stream) {
-    if (n_out > 32 || M > 16 || C % 4 != 0 || skip_bstride % 4 != 0 || (uintptr_t)skip % 16 != 0 ||
-        (uintptr_t)w_end_packed % 16 != 0)
-        return MBX_TAIL_K_NONE;
-    // rows owned by waves (wn_tail2_kernel): up to 352 channels (22 blocks of 16 in a lane's registers)
-    const int nc8 = (C + 7) / 8, nj = (8 * nc8 + 15) / 16;
-    const int kind = !(nj <= 22 && C >= 16) ? MBX_TAIL_K_TAIL : nj <= 4 ? MBX_TAIL_K_TAIL2_NJ4 : nj <= 8 ? MBX_TAIL_K_TAIL2_NJ8 :
-                     nj <= 12 ? MBX_TAIL_K_TAIL2_NJ12 : nj <= 20 ? MBX_TAIL_K_TAIL2_NJ20 : MBX_TAIL_K_TAIL2_NJ22;
-    if (max_rows <= 0 || batch <= 0) return kind;
+// kind: the MBX_TAIL_K_* that wn_tail_select chose for these shapes
+const char *launch_wn_tail(int kind, const float *skip, long long skip_bstride, const int *n_frames, int rows_per_frame, int max_rows,
+                           int batch, int C, const float *w_end_packed, const float *b_end, int n_out, const float *w_post,
+                           const float *b_post, int M, const float *y_acc, float *y, long long y_bstride, float *sub,
+                           long long sub_bstride, hipStream_t stream) {
+    if ((uintptr_t)skip % 16 != 0 || (uintptr_t)w_end_packed % 16 != 0) return "WaveNet tail: a pointer is not 16-byte aligned";
+    if (max_rows <= 0 || batch <= 0) return nullptr;
+    const int nc8 = (C + 7) / 8;
     const size_t lds2 = std::max((size_t)nc8 * 256, (size_t)(4 * T2_YT + 32 * 16 + 16)) * sizeof(float);
-    if (nj <= 22 && C >= 16) {
-        // the smallest instantiation that holds the row: a lane issues NJ loads and keeps 4 NJ registers whatever C is
-        // (same arithmetic in the same order for every NJ >= nj; ADVICE round 5: C = 64 used to issue 20 loads for 4)
-        auto kern = nj <= 4 ? wn_tail2_kernel<4> : nj <= 8 ? wn_tail2_kernel<8> : nj <= 12 ? wn_tail2_kernel<12> :
-                    nj <= 20 ? wn_tail2_kernel<20> : wn_tail2_kernel<22>;
+    if (kind != MBX_TAIL_K_TAIL) {
+        auto kern = kind == MBX_TAIL_K_TAIL2_NJ4 ? wn_tail2_kernel<4> : kind == MBX_TAIL_K_TAIL2_NJ8 ? wn_tail2_kernel<8> :
+                    kind == MBX_TAIL_K_TAIL2_NJ12 ? wn_tail2_kernel<12> : kind == MBX_TAIL_K_TAIL2_NJ20 ? wn_tail2_kernel<20> : wn_tail2_kernel<22>;
         hipLaunchKernelGGL(kern, dim3((max_rows + T2_ROWS - 1) / T2_ROWS, batch), dim3(256), lds2, stream, skip, skip_bstride,
                            n_frames, rows_per_frame, max_rows, C, w_end_packed, b_end, n_out, w_post, b_post, M, y_acc, y,
                            y_bstride, sub, sub_bstride);
-        return kind;
+        return nullptr;
     }
     hipLaunchKernelGGL(wn_tail_kernel, dim3((max_rows + 31) / 32, batch), dim3(256), 0, stream, skip, skip_bstride,
                        n_frames, rows_per_frame, max_rows, C, w_end_packed, b_end, n_out, w_post, b_post, M, y_acc, y,
                        y_bstride, sub, sub_bstride);
-    return kind;
+    return nullptr;
 }
 
 }  // namespace mbx

@@ -44,14 +44,12 @@ namespace mbx {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int W2_HALO = 16;                            // largest dilation
-constexpr int W2_BK = 8;
-constexpr int W2_TROWS = 32;                           // output rows of a wave tile
+// (W2_HALO = 16, the largest dilation, W2_BK = 8, W2_TROWS = 32 output rows of a wave tile, W2_COND_ROWS = 8 conditioning rows
+// of a wave tile: wn_plan.h, the selector reads them)
 constexpr int W2_PHASE = W2_TROWS / 2 + W2_HALO;       // cells per phase (m & 1)
 constexpr int W2_A_FLOATS = 2 * W2_PHASE * W2_BK;      // 512: one wave's rows of one slice
 constexpr int W2_B_FLOATS = 4 * W2_BK * 64;            // 2048: packed weights of one slice
 constexpr int W2_STAGE = 4 * W2_A_FLOATS + W2_B_FLOATS;   // 4096 floats = 16 KB
-constexpr int W2_COND_ROWS = 8;                        // conditioning rows of a wave tile (64 floats each)
 
 constexpr int W2_NSTAGE = 2;                           // (three stages at 3 blocks per CU: 0.834 against 0.811 ms per 64-stream tick)
 constexpr int W2_COND = W2_NSTAGE * W2_STAGE;
@@ -369,35 +367,25 @@ __global__ __launch_bounds__(256, 4) void wn_gate_winograd2w_kernel(ConvArgs p, 
     }
 }
 
-// a.w must point at the host-packed F(2,3) weights (ceil(C/32), ceil(C/8), 2048) of engine.pack_winograd2w_weights;
-// a.out_row0 / a.out_rows: the rows of every item that are computed (out_rows == 0: all of them; out_row0 a multiple of
-// 2 * dilation, so that the output pairs are those of a whole-item run).  Returns false if the layer does not fit.
-bool launch_wn_gate_winograd2w(const ConvArgs &a, hipStream_t stream) {
-    int log2d = 0;
-    while ((1 << log2d) < a.dil) ++log2d;
-    const int nk8 = (a.cin + W2_BK - 1) / W2_BK;
-    const bool ok = a.ks == 3 && (1 << log2d) == a.dil && a.dil <= W2_HALO && nk8 >= 3 && a.pad_mode == 0 &&
-                    (a.pad_l == a.dil || a.pad_l == 2 * a.dil) &&
-                    a.cin % 4 == 0 && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 && a.channels % 4 == 0 &&
-                    a.cout == 2 * a.channels && (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && a.zeros &&
-                    a.cond && (uintptr_t)a.cond % 16 == 0 && a.cond_bstride % 4 == 0 && a.cond_up >= 1 &&
-                    (W2_TROWS + a.cond_up - 2) / a.cond_up + 2 <= W2_COND_ROWS && a.lerp_w0 && a.lerp_w1 &&
-                    a.max_rows < (1 << 24) && a.cond_phase >= 0 && a.cond_phase < a.cond_up && a.out_row0 >= 0 &&
-                    a.out_rows >= 0 && a.out_row0 % (2 * a.dil) == 0 && a.ldo % 2 == 0 && a.out_bstride % 2 == 0 &&
-                    (uintptr_t)a.out % 8 == 0;
-    if (!ok) return false;
+// a.w must point at the host-packed F(2,3) weights (ceil(C/32), ceil(C/8), 2048) of engine.pack_winograd2w_weights; the layer
+// fits (wn_gate_winograd2w_fits).  a.out_row0 / a.out_rows: the rows of every item that are computed.
+const char *launch_wn_gate_winograd2w(const ConvArgs &a, hipStream_t stream) {
+    if ((uintptr_t)a.x % 16 != 0 || (uintptr_t)a.w % 16 != 0 || !a.zeros || !a.cond || (uintptr_t)a.cond % 16 != 0 || !a.lerp_w0 ||
+        !a.lerp_w1 || (uintptr_t)a.out % 8 != 0)
+        return "F(2,3) gate layer: a pointer is null or not aligned";
+    const int log2d = wn_log2_ceil(a.dil);
     ConvArgs r = a;
     r.fast_dma = 1;                 // byte offsets are relative to the tile's window
     r.n_tiles = (a.channels + 31) / 32;
     const int span = a.out_rows > 0 ? std::min(a.out_rows, a.max_rows - a.out_row0) : a.max_rows - a.out_row0;
-    if (span <= 0) return true;
+    if (span <= 0) return nullptr;
     r.m_tiles_per_item = (span + W2_TROWS - 1) / W2_TROWS;               // wave tiles per item
     r.m_tiles_total = r.m_tiles_per_item * a.batch;
     const long long groups = (r.m_tiles_total + 3) / 4;
     const long long blocks = 8LL * ((groups + 7) / 8) * r.n_tiles;
     if (a.gate_act == 0) hipLaunchKernelGGL(wn_gate_winograd2w_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, stream, r, log2d);
     else hipLaunchKernelGGL(wn_gate_winograd2w_kernel<-1>, dim3((unsigned)blocks), dim3(256), 0, stream, r, log2d);
-    return true;
+    return nullptr;
 }
 
 }  // namespace mbx

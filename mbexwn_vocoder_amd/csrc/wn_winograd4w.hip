@@ -58,8 +58,7 @@ namespace mbx {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int WW_HALO = 16;
-constexpr int WW_BK = 8;
+// (WW_HALO = 16, WW_BK = 8: wn_plan.h, the selector reads them)
 constexpr int WW_B_FLOATS = 6 * WW_BK * 64;            // 3072: packed weights of one 8-channel slice
 
 // CR = conditioning rows the block's tile holds: 28 for cond_up >= 10 (the canonical models: 3 blocks per CU), 56 for
@@ -820,7 +819,7 @@ __global__ __launch_bounds__(256, 3) void wn_gate_winograd4p_kernel(ConvArgs p, 
 // products, same sums in the same order as the other two shapes: the SAME bits.  LDS 29.5 KB, 4+ blocks per CU.
 // Measured (profiles/r05_gate_shapes.txt): 54.0 against 48.8 us at 3 s -- a block of half the matrix work lasts almost as long
 // (its 40 barrier-separated slices set its time, not its MFMAs) -- and 43.8 against 48.5 us at 2 s, where the product-split
-// blocks leave CUs empty: the launcher takes this shape there only (mbx_forward.hip, gate_shape_policy).
+// blocks leave CUs empty: the plan takes this shape there only (wn_plan.h, gate_shape_policy).
 struct WhShape {
     static constexpr int ROWS = 128;
     static constexpr int PHASE = ROWS / 4 + WW_HALO;            // 48
@@ -1431,31 +1430,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
+static_assert(WqShape::COND_ROWS == WQ_COND_ROWS, "wn_gate_winograd4w_select knows the conditioning rows of the two-tile blocks");
+
+// The LDS size of the blocks of two column tiles is an attribute of the (function, device) pair: mbx_create asks for it once,
+// with the handle's device current; returns WN_LDS_F43Q if the device granted it.
+unsigned wn_gate_winograd4q_lds_opt_in() {
+    const int bytes = WqShape::LDS_FLOATS * (int)sizeof(float);
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_winograd4q_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_winograd4q_kernel<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess)
+        return WN_LDS_F43Q;
+    (void)hipGetLastError();
+    return 0;
+}
+
 // a.w must point at the host-packed F(4,3) weights (ceil(C/32), ceil(C/8), 3072) of engine.pack_winograd4w_weights;
-// split = the 128-row shape whose waves split the six products (same bits as the 256-row shape).  Returns false if the
-// layer does not fit.
-// shape: 0 = 256-row blocks, 1 = 128-row product-split blocks, 2 = product-split blocks of half a column tile, 3 = 256-row blocks
-// of two column tiles (false where that shape does not apply: d > 16, cond_up < 10, one column tile, or
-// the device refuses its LDS size; the caller falls back to shape 0)
-bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream) {
+// k: what wn_gate_winograd4w_select chose for these arguments.  k.shape: 0 = 256-row blocks, 1 = 128-row product-split blocks
+// (same bits as the 256-row shape), 2 = product-split blocks of half a column tile, 3 = 256-row blocks of two column tiles
+const char *launch_wn_gate_winograd4w(const ConvArgs &a, const GateChoice &k, hipStream_t stream) {
+    if ((uintptr_t)a.x % 16 != 0 || (uintptr_t)a.w % 16 != 0 || !a.zeros || !a.cond || (uintptr_t)a.cond % 16 != 0 || !a.lerp_w0 || !a.lerp_w1)
+        return "F(4,3) gate layer: a pointer is null or not 16-byte aligned";
+    const int shape = k.shape;
     const bool split = shape == 1 || shape == 2;
     // dilations above the halo: d = 16 s runs as s interleaved virtual items per item at dilation 16 (kernels' VS variants)
     const int vs = a.dil > WW_HALO ? a.dil / WW_HALO : 1;
-    const int dil_v = vs > 1 ? WW_HALO : a.dil;
-    int log2d = 0;
-    while ((1 << log2d) < dil_v) ++log2d;
+    const int log2d = wn_log2_ceil(vs > 1 ? WW_HALO : a.dil);
     const int rows_blk = split ? 128 : 256;
-    const int nk8 = (a.cin + WW_BK - 1) / WW_BK;
-    const int cond_rows = vs > 1 ? 1 : a.cond_up >= 1 ? (rows_blk + a.cond_up - 2) / a.cond_up + 2 : 1 << 30;   // conditioning rows a block's tile holds
-    const bool ok = a.ks == 3 && (1 << log2d) == dil_v && dil_v * vs == a.dil && nk8 >= 4 && a.pad_mode == 0 &&
-                    (a.pad_l == a.dil || (vs == 1 && a.pad_l == 2 * a.dil)) &&
-                    a.cin % 4 == 0 && a.ldx % 4 == 0 && a.x_bstride % 4 == 0 && a.channels % 4 == 0 &&
-                    a.cout == 2 * a.channels && (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && a.zeros &&
-                    a.cond && (uintptr_t)a.cond % 16 == 0 && a.cond_bstride % 4 == 0 && a.cond_up >= 1 &&
-                    a.cond_up <= 64 && cond_rows <= (split ? 16 : 56) && a.lerp_w0 && a.lerp_w1 && a.max_rows < (1 << 24) &&
-                    (vs == 1 || (shape != 2 && a.max_rows >= a.cond_up &&
-                                 (long long)(rows_blk + 2 * WW_HALO) * vs * a.ldx * 4 < (1LL << 32)));
-    if (!ok) return false;
     ConvArgs r = a;
     r.fast_dma = 1;                 // byte offsets are relative to the block's window (< 2^32 for any item length)
     r.vstride = vs;
@@ -1463,22 +1462,6 @@ bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream)
     r.n_tiles = (a.channels + 31) / 32;
     const bool gtu = a.gate_act == 0;
     if (shape == 3) {
-        // the CR = 28 geometry only (cond_up >= 10), here and in the one-tile blocks of an odd last tile
-        if (vs > 1 || cond_rows > WqShape::COND_ROWS || r.n_tiles < 2) return false;
-        // the LDS size is an attribute of the (function, device) pair (as in launch_wn_gate_f16)
-        static unsigned long long attr_devices = 0, attr_failed = 0;
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-        if (!((attr_devices >> dev) & 1ull)) {
-            const int bytes = WqShape::LDS_FLOATS * (int)sizeof(float);
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_winograd4q_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void *>(wn_gate_winograd4q_kernel<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                attr_failed |= 1ull << dev;
-            }
-            attr_devices |= 1ull << dev;
-        }
-        if ((attr_failed >> dev) & 1ull) return false;
         const int tiles = r.n_tiles;
         ConvArgs q = r;
         q.n_tiles = tiles / 2;                            // pairs of column tiles
@@ -1498,13 +1481,12 @@ bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream)
             if (gtu) hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, 0>), grid1, dim3(256), 0, stream, r, log2d);
             else hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, -1>), grid1, dim3(256), 0, stream, r, log2d);
         }
-        return true;
+        return nullptr;
     }
     const int vrows = (a.max_rows + vs - 1) / vs;         // rows of the longest virtual item
     r.m_tiles_per_item = (vrows + rows_blk - 1) / rows_blk;
     r.m_tiles_total = r.m_tiles_per_item * a.batch * vs;
-    // sub-sequences of at most 128 rows: a 256-row block takes two of them (VS == 2)
-    const bool two = vs > 1 && !split && vrows <= 128 && vs % 2 == 0 && log2d == 4;
+    const bool two = k.vs_arg == 2;                       // a 256-row block takes two sub-sequences (VS == 2)
     if (two) r.m_tiles_total = a.batch * (vs / 2);
     const long long blocks = 8LL * ((r.m_tiles_total + 7) / 8) * r.n_tiles;
     const dim3 blk(256);
@@ -1513,7 +1495,7 @@ bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream)
         const dim3 grid2((unsigned)(8LL * ((r.m_tiles_total + 7) / 8) * r.n_tiles));
         if (gtu) hipLaunchKernelGGL(wn_gate_winograd4h_kernel<0>, grid2, blk, 0, stream, r, log2d);
         else hipLaunchKernelGGL(wn_gate_winograd4h_kernel<-1>, grid2, blk, 0, stream, r, log2d);
-        return true;
+        return nullptr;
     }
     const dim3 grid((unsigned)blocks);
     if (vs > 1) {
@@ -1523,15 +1505,15 @@ bool launch_wn_gate_winograd4w(const ConvArgs &a, int shape, hipStream_t stream)
         else if (two) hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, -1, 2>), grid, blk, 0, stream, r, log2d);
         else if (gtu) hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, 0, 1>), grid, blk, 0, stream, r, log2d);
         else hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, -1, 1>), grid, blk, 0, stream, r, log2d);
-        return true;
+        return nullptr;
     }
     if (split && gtu) hipLaunchKernelGGL(wn_gate_winograd4p_kernel<0>, grid, blk, 0, stream, r, log2d);
     else if (split) hipLaunchKernelGGL(wn_gate_winograd4p_kernel<-1>, grid, blk, 0, stream, r, log2d);
-    else if (cond_rows <= 28 && gtu) hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, 0>), grid, blk, 0, stream, r, log2d);
-    else if (cond_rows <= 28) hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, -1>), grid, blk, 0, stream, r, log2d);
+    else if (k.cr == 28 && gtu) hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, 0>), grid, blk, 0, stream, r, log2d);
+    else if (k.cr == 28) hipLaunchKernelGGL((wn_gate_winograd4w_kernel<28, -1>), grid, blk, 0, stream, r, log2d);
     else if (gtu) hipLaunchKernelGGL((wn_gate_winograd4w_kernel<56, 0>), grid, blk, 0, stream, r, log2d);
     else hipLaunchKernelGGL((wn_gate_winograd4w_kernel<56, -1>), grid, blk, 0, stream, r, log2d);
-    return true;
+    return nullptr;
 }
 
 }  // namespace mbx

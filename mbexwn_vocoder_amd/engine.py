@@ -98,6 +98,13 @@ class mbx_kernel_report_info(ctypes.Structure):
                 ("tail_folded", ctypes.c_int32), ("gate_block_channels", ctypes.c_int32 * MBX_MAX_WN_LAYERS)]
 
 
+class mbx_plan_info(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("n_layers", ctypes.c_int32),
+                ("gate_kernel", ctypes.c_int32 * MBX_MAX_WN_LAYERS), ("gate_kernel_f32", ctypes.c_int32 * MBX_MAX_WN_LAYERS),
+                ("gate_block_channels", ctypes.c_int32 * MBX_MAX_WN_LAYERS), ("resskip_kernel", ctypes.c_int32 * MBX_MAX_WN_LAYERS),
+                ("tail_kernel", ctypes.c_int32), ("tail_folded", ctypes.c_int32), ("planes_only", ctypes.c_int32)]
+
+
 # MBX_RESSKIP_K_* / MBX_TAIL_K_* of include/mbexwn.h (mbx_kernel_report)
 RESSKIP_KERNEL_NAMES = {0: "none", 1: "conv1d", 2: "packed64", 3: "packed128", 4: "wide11_res10", 5: "wide11", 6: "wide6x2",
                         7: "wave11", 8: "wave12", 9: "wave6x2", 10: "wave4x3", 11: "split_f16"}
@@ -163,6 +170,8 @@ def load_library():
     lib.mbx_conv_form.argtypes = [vp, ctypes.POINTER(mbx_conv_form_info)]
     lib.mbx_kernel_report.restype = i32
     lib.mbx_kernel_report.argtypes = [vp, ctypes.POINTER(mbx_kernel_report_info)]
+    lib.mbx_plan.restype = i32
+    lib.mbx_plan.argtypes = [vp, i32, i32, ctypes.POINTER(mbx_plan_info)]
     lib.mbx_calibrate.restype = i32
     lib.mbx_calibrate.argtypes = [vp, fp, vp, i32, i32, fp, vp, ctypes.c_size_t, vp]
     lib.mbx_workspace_size.restype = ctypes.c_size_t
@@ -237,7 +246,7 @@ def load_library():
     return lib
 
 
-EXPORTED_SYMBOLS = ["mbx_last_error", "mbx_create", "mbx_destroy", "mbx_conv_form", "mbx_kernel_report", "mbx_calibrate", "mbx_workspace_size", "mbx_forward",
+EXPORTED_SYMBOLS = ["mbx_last_error", "mbx_create", "mbx_destroy", "mbx_conv_form", "mbx_kernel_report", "mbx_plan", "mbx_calibrate", "mbx_workspace_size", "mbx_forward",
                     "mbx_forward_stream", "mbx_forward_ex", "mbx_layer_state_info", "mbx_window_advance", "mbx_window_update", "mbx_emit_rows", "mbx_stage",
                     "mbx_profile_enable", "mbx_profile_read", "mbx_profile_read_launches", "mbx_clock_probe", "mbx_pqmf_synthesis", "mbx_conv1d", "mbx_conv1d_f64acc", "mbx_lin_interp", "mbx_wavetable", "mbx_stft_filter", "mbx_norm_mel", "mbx_mel_analysis",
                     "mbx_encode_flac16"]
@@ -369,7 +378,7 @@ def make_config(config, wavetables, conv_form=None, batch_invariant=None, keep_s
     calib_fraction, tune = {"gate_shape": 0|1|2|3|4, "resskip_wave_tiles": n, "resskip_split": 0..3}.  gate_shape 0 keeps the
     launch-size rule; 1 | 4 pin the F(4,3) block shape of large launches (256-row blocks of one column tile | 256-row
     blocks of two) at every launch size, 2 | 3 that of small ones (product-split | product-split of half a column tile) for
-    launches of fewer than 4 * 768 256-row blocks (csrc/mbx_forward.hip, gate_shape_policy).  resskip_wave_tiles -1: never the wave-tiled res/skip
+    launches of fewer than 4 * 768 256-row blocks (csrc/wn_plan.h, gate_shape_policy).  resskip_wave_tiles -1: never the wave-tiled res/skip
     kernel."""
     dims = ModelDims(config)
     mb = config["mbexwn_config"]
@@ -833,7 +842,6 @@ class MBExWNEngine:
         cconf, self.dims = make_config(config, wavetables, conv_form=conv_form, batch_invariant=batch_invariant,
                                        keep_skip=keep_skip, keep_start=keep_start, calib_fraction=calib_fraction, tune=tune,
                                        precision=precision, f0_accumulate=f0_accumulate)
-        self._tune_gate_shape = cconf.tune_gate_shape
         self.normalizes_rms = cconf.nm_iters > 0            # row A14: done on the device inside mbx_forward
         self._tensors = tensor_table(config, raw_weights, wavetables, split_f16=precision == "split_f16")   # keep the host arrays alive
         if not weight_images:
@@ -1349,31 +1357,36 @@ class MBExWNEngine:
                                        self._stream()))
         return self.conv_form_info()
 
+    def _plan_info(self, batch, max_frames):
+        info = mbx_plan_info()
+        info.struct_size = ctypes.sizeof(mbx_plan_info)
+        _check(self._lib.mbx_plan(self._handle, int(batch), int(max_frames), ctypes.byref(info)))
+        return info
+
+    def plan(self, batch, max_frames):
+        """What a whole-item :meth:`forward` of this size would run, without launching (mbx_plan): the dict of
+        :meth:`kernel_report`, which equals it after such a forward."""
+        info = self._plan_info(batch, max_frames)
+        resskip = [RESSKIP_KERNEL_NAMES[info.resskip_kernel[ll]] for ll in range(info.n_layers)]
+        return {"gate_kernels": [GATE_KERNEL_NAMES[info.gate_kernel[ll]] for ll in range(info.n_layers)],
+                "gate_block_channels": [int(info.gate_block_channels[ll]) for ll in range(info.n_layers)],
+                "resskip_kernels": [kk for kk in resskip if kk != "none"],
+                "tail_kernel": TAIL_KERNEL_NAMES[info.tail_kernel], "tail_folded": bool(info.tail_folded)}
+
     def gate_form(self, batch, max_frames):
-        """Which implementation of the dilated convolution a forward of this size runs: the handle's form
-        (mbx_conv_form) and, for F(4,3), the block shape the library's launch-size rule picks (csrc/mbx_forward.hip, gate_shape_policy: 256-row
-        blocks, or 128-row blocks whose waves split the six products where those spread the work clearly more evenly over
-        the SIMDs, or product-split blocks of half a column tile where even those load the CUs unevenly; all three give the same
-        bits): "direct", "winograd_f23", "winograd_f43", "winograd_f43_psplit" or "winograd_f43_hsplit"."""
-        info = self.conv_form_info()
-        if info["form"] == "direct":
-            return "direct"
-        if info["form"] == "f23":
-            return "winograd_f23"
-        rows = max_frames * self.dims.steps_per_frame
-        tiles = (self.dims.wn_channels + 31) // 32
-        full_blocks = ((rows + 255) // 256) * batch * tiles
-        half_blocks = ((rows + 127) // 128) * batch * tiles
-        if info["batch_invariant"]:
-            return "winograd_f43"
-        if self._tune_gate_shape in (1, 4):        # the two shapes of large launches (one | two column tiles per block), at every size
-            return "winograd_f43"
-        if self._tune_gate_shape and full_blocks < 4 * 768:
-            return {2: "winograd_f43_psplit", 3: "winograd_f43_hsplit"}[self._tune_gate_shape]
-        load_full, load_half = (full_blocks + 255) // 256, 0.5 * ((half_blocks + 255) // 256)
-        if full_blocks <= 1024 and load_half <= load_full:
-            return "winograd_f43_hsplit" if half_blocks <= 256 < 2 * half_blocks else "winograd_f43_psplit"
-        return "winograd_f43"
+        """Which float32 implementation of the dilated convolution a forward of this size runs, as the library plans it
+        (mbx_plan; csrc/wn_plan.h): the kernel of the first layer behind a folded first layer -- the handle's form and, for
+        F(4,3), the block shape of the launch-size rule (256-row blocks, or 128-row blocks whose waves split the six products
+        where those spread the work clearly more evenly over the SIMDs, or product-split blocks of half a column tile where even
+        those load the CUs unevenly; all give the same bits): "direct", "winograd_f23", "winograd_f43", "winograd_f43_psplit" or
+        "winograd_f43_hsplit"."""
+        info = self._plan_info(batch, max_frames)
+        first = 1 if info.n_layers > 1 and info.gate_kernel[0] == 8 else 0        # MBX_GATE_K_FOLDED_START
+        kernel = GATE_KERNEL_NAMES[info.gate_kernel_f32[first]]
+        if kernel == "folded_start":              # a one-layer model: no layer runs a gate kernel of the form
+            kernel = self.conv_form_info()["form"]
+        return {"direct": "direct", "f23": "winograd_f23", "f43": "winograd_f43", "f43_strided": "winograd_f43",
+                "f43_psplit": "winograd_f43_psplit", "f43_strided_psplit": "winograd_f43_psplit", "f43_hsplit": "winograd_f43_hsplit"}[kernel]
 
     @property
     def folds_start(self):

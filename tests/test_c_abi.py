@@ -34,12 +34,13 @@ def test_library_exports_every_declared_symbol():
 def test_struct_layout_matches_c(tmp_path):
     src = tmp_path / "sizes.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mbexwn.h"\n'
-                   'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mbx_config), sizeof(mbx_subnet_op),'
+                   'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mbx_config), sizeof(mbx_subnet_op),'
                    ' sizeof(mbx_tensor), offsetof(mbx_config, n_f0_ops), offsetof(mbx_config, vtf_ops),'
                    ' offsetof(mbx_config, wt_nominal_f0), sizeof(mbx_forward_options), offsetof(mbx_forward_options, wn_frames),'
                    ' offsetof(mbx_forward_options, sub_carry), offsetof(mbx_forward_options, layer_rows),'
                    ' offsetof(mbx_config, wn_conv_form), offsetof(mbx_config, tune_resskip_split), sizeof(mbx_conv_form_info),'
-                   ' offsetof(mbx_conv_form_info, err_f23), sizeof(mbx_kernel_report_info), offsetof(mbx_kernel_report_info, tail_kernel));'
+                   ' offsetof(mbx_conv_form_info, err_f23), sizeof(mbx_kernel_report_info), offsetof(mbx_kernel_report_info, tail_kernel),'
+                   ' sizeof(mbx_plan_info), offsetof(mbx_plan_info, resskip_kernel), offsetof(mbx_plan_info, planes_only));'
                    ' return 0;}\n')
     exe = tmp_path / "sizes"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
@@ -52,7 +53,8 @@ def test_struct_layout_matches_c(tmp_path):
                    engine.mbx_forward_options.sub_carry.offset, engine.mbx_forward_options.layer_rows.offset,
                    cc.wn_conv_form.offset, cc.tune_resskip_split.offset, ctypes.sizeof(engine.mbx_conv_form_info),
                    engine.mbx_conv_form_info.err_f23.offset, ctypes.sizeof(engine.mbx_kernel_report_info),
-                   engine.mbx_kernel_report_info.tail_kernel.offset]
+                   engine.mbx_kernel_report_info.tail_kernel.offset, ctypes.sizeof(engine.mbx_plan_info),
+                   engine.mbx_plan_info.resskip_kernel.offset, engine.mbx_plan_info.planes_only.offset]
 
 
 def test_policy_fields_and_experiment_variables(monkeypatch, capsys):

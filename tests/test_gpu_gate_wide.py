@@ -13,7 +13,7 @@ from helpers import build_case, synthetic_inputs
 E2E_TOL = 1e-4          # the bar of test_gpu_parity.test_f43_block_shapes_give_the_same_bits
 LENGTHS = [240, 133, 7]  # 4 800 rows; 2 660 rows: ends inside a block; 140 rows: shorter than one block
 _WN = "mbexwn_config:pp_mod_subnet:"
-# launch-size rule of csrc/mbx_forward.hip (gate_shape_policy, WIDE_FROM_BLOCKS): 256-row blocks of one column tile a launch
+# launch-size rule of csrc/wn_plan.h (gate_shape_policy, WIDE_FROM_BLOCKS): 256-row blocks of one column tile a launch
 # must have to take the blocks of two -- (batch, frames) of the smallest SPEECH launch of 800-frame items above it, one below
 WIDE_FROM_BLOCKS = 5040
 ABOVE, BELOW = (8, 800), (8, 787)      # 63 x 8 x 10 = 5 040 blocks | 62 x 8 x 10 = 4 960

@@ -161,6 +161,7 @@ EXEMPT = {
     "mbx_create": "writes a host handle pointer only",
     "mbx_conv_form": "fills a host struct",
     "mbx_kernel_report": "fills a host struct",
+    "mbx_plan": "fills a host struct, launches nothing",
     "mbx_layer_state_info": "writes three host integers",
     "mbx_stage": "hands out pointers into the workspace of the last forward, writes no device memory",
     "mbx_profile_read": "host scalars",

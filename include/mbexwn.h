@@ -566,7 +566,10 @@ mbx_status mbx_emit_rows(mbx_handle *handle, const float *audio, int64_t row_flo
  * skip sum, max_frames * rows_per_frame * C floats per item at that block's own rate and channels; "cond" is block 0's
  * conditioning rows and "cond1" .. "cond3" those of blocks 1 .. 3, laid out like "cond" (max_frames * cond rows per frame
  * * 2 C of the block; zeros with disable_conditioning).  "pulse_ana" (pulse_pqmf_taps > 0 only): the PQMF analysis of
- * "pulse", the rows the WaveNet reads (max_frames * pulse_per_frame floats per item, pulse_channels per row). */
+ * "pulse", the rows the WaveNet reads (max_frames * pulse_per_frame floats per item, pulse_channels per row).
+ * "mel_env" (after mbxe_forward of mbexwn_envelope.h with a formant shift only, unknown otherwise): the warped mel rows the VTF
+ * and conditioning chains read, max_frames * mel_channels floats per item -- a pointer into the caller's env_mel, not into the
+ * workspace. */
 mbx_status mbx_stage(const mbx_handle *handle, const char *name, const void **device_ptr, int64_t *count,
                      int64_t *stride);
 

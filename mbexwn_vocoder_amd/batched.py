@@ -150,7 +150,7 @@ def stage_factors(rows, device=None):
 
 
 def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False, host_audio=True,
-                      flac_compression="verbatim", out_rate=None, transpositions=None):
+                      flac_compression="verbatim", out_rate=None, transpositions=None, formants=None):
     """Generator over the padded micro-batches of ``mels`` (list of (T_i, C) float32 arrays) on ``engine``: each is staged
     and run (engine.forward with the items' lengths), its FLAC frames encoded (``flac``) and / or its audio copied to pinned
     host memory (``host_audio``), all enqueued on the current stream; the SynthBatch is yielded without waiting, so that a
@@ -163,7 +163,9 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
 
     ``noises`` may also be a ``mel_inverter.KeyedNoise`` (a seed and one key per item): each micro-batch's draw is then filled
     on the device by ``engine.keyed_noise``, a function of the seed, the item's key and the step alone.  ``transpositions``:
-    per item None or (T_i,) factors, one per mel frame -- the ``f0_scale`` rows of the forward; None: the forward of today."""
+    per item None or (T_i,) factors, one per mel frame -- the ``f0_scale`` rows of the forward; None: the forward of today.
+    ``formants``: the same for the formant shift (the ``formant`` rows of the forward).  A micro-batch
+    whose factors are all exactly 1 runs the forward without them: a factor of 1 copies the row, so the bits are the same."""
     import torch
     from .mel_inverter import KeyedNoise
     dims = engine.dims
@@ -184,6 +186,14 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
             control["f0_scale"] = stage_factors([np.ones(lengths[ii], dtype=np.float32) if transpositions[ii] is None
                                                  else np.asarray(transpositions[ii], dtype=np.float32) for ii in group],
                                                 engine.device)
+        if formants is not None:
+            for ii in group:
+                if formants[ii] is not None and np.shape(formants[ii]) != (lengths[ii],):
+                    raise ValueError(f"formants[{ii}] must hold one factor per mel frame ({lengths[ii]})")
+            rows = [np.ones(lengths[ii], dtype=np.float32) if formants[ii] is None else np.asarray(formants[ii], dtype=np.float32)
+                    for ii in group]
+            if any(np.any(rr != 1.0) for rr in rows):
+                control["formant"] = stage_factors(rows, engine.device)
         events = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         events[0].record(stream)
         if keyed:                                           # the draw is part of the step: inside the device time
@@ -262,7 +272,7 @@ def _file_writer(inv, files, mine, scaled, output_dir, fmt, device_flac, file_ra
 
 
 def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threads=2, verbose=False, quiet=False,
-            flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None):
+            flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant=None):
     """The batched CLI on this process's GPU: ``files[mine]`` -> syn_<basename>.<fmt> in ``output_dir``.
 
     ``frames``: the frame count after scale_mel of EVERY file of the job, in file order (the noise replay needs all of
@@ -273,7 +283,8 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
     the device, ``run_micro_batches``); the verbose ``mel_error`` stays computed on the model-rate audio, the clipping note
     is about what is written.  ``noise_seed``: the noise channel takes the keyed noise of that seed instead of the replayed
     draws, the key of a file being ``noise.item_key`` of its basename -- a file's audio then does not depend on the other
-    files; ``transposition``: a factor on every mel frame of every file (``f0_scale`` rows).  Both None: today's job."""
+    files; ``transposition``: a factor on every mel frame of every file (``f0_scale`` rows); ``formant``: a formant-shift
+    factor on every mel frame of every file (``formant`` rows).  All None: today's job."""
     t_start = time.perf_counter()
     mine = list(range(len(files))) if mine is None else list(mine)
     clock, log_lock = _Clock(), threading.Lock()
@@ -316,11 +327,12 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
         from .noise import item_key
         noises = KeyedNoise(noise_seed, [item_key(files[ii]) for ii in mine])
     rows = None if transposition is None else [np.full(int(mm.shape[0]), transposition, dtype=np.float32) for mm in mels]
+    shifts = None if formant is None else [np.full(int(mm.shape[0]), formant, dtype=np.float32) for mm in mels]
     with ThreadPoolExecutor(max_workers=max(1, threads)) as writers:
         pending = [writers.submit(write, sb) for sb in run_micro_batches(inv.model, mels, noises, max(1, batch),
                                                                          flac=device_flac, host_audio=verbose or not device_flac,
                                                                          flac_compression=flac_compression, out_rate=out_rate,
-                                                                         transpositions=rows)]
+                                                                         transpositions=rows, formants=shifts)]
         for fu in pending:
             fu.result()
     if verbose:
@@ -357,13 +369,14 @@ def read_transposition_file(path):
     return table
 
 
-def file_factors(files, transposition=1.0, table=None):
+def file_factors(files, transposition=1.0, table=None, what="transposition"):
     """The transposition factor of every file: ``table[basename]`` (read_transposition_file) where it is listed, else
-    ``transposition``; every factor finite and positive, or ValueError."""
+    ``transposition``; every factor finite and positive, or ValueError.  ``what`` names the factor in the message
+    (``--formant-shift-file`` has the format and the reader of ``--transposition-file``)."""
     table = table or {}
     factors = [float(table.get(os.path.basename(ff), transposition)) for ff in files]
     if not all(np.isfinite(ff) and ff > 0 for ff in factors):
-        raise ValueError("transposition must be finite and positive")
+        raise ValueError(f"{what} must be finite and positive")
     return factors
 
 
@@ -391,7 +404,7 @@ def read_sound(path):
 
 
 def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
-                  quiet=False, flac_compression="verbatim", out_rate=None, stretches=None):
+                  quiet=False, flac_compression="verbatim", out_rate=None, stretches=None, formants=None):
     """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
     ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
 
@@ -406,7 +419,10 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     ``stretches``: a time-stretch factor per file (timemap.py), None = 1 for all.  File i is analysed
     at the centres of ``timemap.centres`` for ``stretches[i]`` and gives K_i * hop samples, ``stretches[i]`` times as long
     at the same pitch.  With every factor 1 the job makes the launches and writes the bytes it does without the argument.  A
-    file whose stretched length exceeds the engine's limit is reported and skipped like the unreadable ones."""
+    file whose stretched length exceeds the engine's limit is reported and skipped like the unreadable ones.
+
+    ``formants``: a formant-shift factor per file, None = 1 for all: ``formants[i]`` on every frame of
+    file i, pitch and duration kept.  With every factor 1 the job makes the launches and writes the bytes it does without."""
     from . import timemap
     from .analysis import generate_mels, resampled_length
     from .mel_inverter import KeyedNoise
@@ -472,9 +488,11 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
                                  flac_compression, verbose, quiet, clock, log)
             noises = KeyedNoise(noise_seed, [item_key(files[ii]) for ii in sub]) if dims.noise_sigma else None
             rows = [np.full(int(scaled[ii].shape[1]), factors[ii], dtype=np.float32) for ii in sub]
+            shifts = None if formants is None else [np.full(int(scaled[ii].shape[1]), formants[ii], dtype=np.float32) for ii in sub]
             pending += [writers.submit(write, sb) for sb in run_micro_batches(
                 inv.model, [scaled[ii][0] for ii in sub], noises, max(1, batch), flac=device_flac,
-                host_audio=verbose or not device_flac, flac_compression=flac_compression, out_rate=rate, transpositions=rows)]
+                host_audio=verbose or not device_flac, flac_compression=flac_compression, out_rate=rate, transpositions=rows,
+                formants=shifts)]
         for fu in pending:
             fu.result()
     if verbose:

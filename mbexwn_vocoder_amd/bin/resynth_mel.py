@@ -32,7 +32,7 @@ from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
          num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None,
-         flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None):
+         flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant_shift=None):
     format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
     if flac_compression != "verbatim" and rank is None and not quiet:
         from mbexwn_vocoder_amd.batched import have_soundfile
@@ -48,6 +48,7 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         argv += ["--out-rate", str(out_rate)] if out_rate else []
         argv += ["--noise-seed", str(noise_seed)] if noise_seed is not None else []
         argv += ["--transposition", repr(transposition)] if transposition is not None else []
+        argv += ["--formant-shift", repr(formant_shift)] if formant_shift is not None else []
         argv += [flag for flag, on in (("-g", use_gpu), ("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant))
                  if on]
         sys.exit(run_ranks(os.path.abspath(__file__), argv, model_id, input_mell_files, gpus, threads=num_threads,
@@ -92,7 +93,8 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         from mbexwn_vocoder_amd.batched import run_job
         run_job(MelInv, input_mell_files, output_dir, format, frames=plan["frames"] if plan else None,
                 mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose, quiet=quiet,
-                flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed, transposition=transposition)
+                flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed, transposition=transposition,
+                formant=formant_shift)
         return
     out_rate = MelInv._output_rate(out_rate)
 
@@ -112,6 +114,8 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
             control.update(noise_seed=noise_seed, noise_key=item_key(mell_file))
         if transposition is not None:                # the factor on every mel frame, as run_job applies it
             control.update(transposition=np.full(log_mel_spectrogram.shape[1], transposition, dtype=np.float32))
+        if formant_shift is not None and formant_shift != 1.0:       # (a factor of 1: the call without it, as run_job makes it)
+            control.update(formant=formant_shift)
         syn_audio = MelInv.synth_from_mel(log_mel_spectrogram, **control)
         end_time = time.time()
 
@@ -132,7 +136,7 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
 
 
 def positive_factor(text):
-    """argparse type of --transposition: a finite positive factor."""
+    """argparse type of --transposition and --formant-shift: a finite positive factor."""
     from argparse import ArgumentTypeError
     try:
         factor = float(text)
@@ -199,6 +203,9 @@ if __name__ == "__main__":
                              "one-at-a-time loop)")
     parser.add_argument("--transposition", default=None, type=positive_factor, metavar="F",
                         help="factor on the pitch, applied to every mel frame (Def: none)")
+    parser.add_argument("--formant-shift", dest="formant_shift", default=None, type=positive_factor, metavar="F",
+                        help="factor on the formant frequencies at the same pitch, applied to every mel frame: F > 1 moves "
+                             "them up (Def: none)")
     parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
     parser.add_argument("--job", default=None, help=SUPPRESS)
     args = parser.parse_args()

@@ -2,8 +2,8 @@
 """Transpose a running voice: feeds a sound file through a ``LiveResynthesizer`` (mbexwn_vocoder_amd/live.py) in tick-sized
 pushes, as a live source would deliver it, and writes what the stream gives back.
 
-    stream_transpose.py in.wav -o out.wav --model_id VOICE --transposition 1.5 [--tick-ms 80] [--resample]
-                        [--output-rate R|input]
+    stream_transpose.py in.wav -o out.wav --model_id VOICE --transposition 1.5 [--formant-shift F] [--tick-ms 80]
+                        [--resample] [--output-rate R|input]
 
 The demonstration of the live path (streaming mel analysis -> scale_mel -> streaming synthesis with per-frame pitch control).
 The input must be at the model's sample rate, unless ``--resample`` is given: then a file at another rate streams at its own
@@ -28,11 +28,11 @@ from mbexwn_vocoder_amd.live import check_rate  # noqa: E402
 
 
 def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0, sample_rate=None, output_rate=None,
-                noise_fn=None):
+                noise_fn=None, formant=None):
     """Push `samples` in pieces of tick_samples, one tick per push, until the stream is finished; returns its audio.
     ``sample_rate``: the rate of `samples` when it is not the model's (the stream resamples); ``output_rate``: the rate the
     audio comes back at when it is not the model's (a rate in Hz, or "input"); ``noise_fn``: the stream's noise instead of the
-    generator seeded with ``seed`` (``live.keyed_noise_fn``)."""
+    generator seeded with ``seed`` (``live.keyed_noise_fn``); ``formant``: a formant-shift factor given with every push."""
     rates = {} if sample_rate is None else {"sample_rate": sample_rate}
     if output_rate is not None:
         rates["output_rate"] = output_rate
@@ -40,7 +40,8 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0,
     out = []
     for start in range(0, samples.size, tick_samples):
         end = min(start + tick_samples, samples.size)
-        live.push_audio(stream_id, samples[start:end], last=end == samples.size, transposition=transposition)
+        live.push_audio(stream_id, samples[start:end], last=end == samples.size, transposition=transposition,
+                        **({} if formant is None else {"formant": formant}))
         out += [audio for audio in [live.tick().get(stream_id)] if audio is not None]
     while not live.finished(stream_id):
         audio = live.tick().get(stream_id)
@@ -52,7 +53,7 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0,
 
 
 def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tick_ms=80.0, seed=0, quiet=False,
-         resample=False, output_rate=None, noise_seed=None):
+         resample=False, output_rate=None, noise_seed=None, formant_shift=1.0):
     preprocess_config = read_config(config_file=get_config_file(model_id_or_path=model_id))['preprocess_config']
     if not os.path.isfile(input_audio_file):
         print(f"stream_transpose::error:: no such file: {input_audio_file}", file=sys.stderr)
@@ -71,6 +72,8 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
             raise ValueError(f"{input_audio_file}: no samples")
         if not (np.isfinite(transposition) and transposition > 0):
             raise ValueError("--transposition must be finite and positive")
+        if not (np.isfinite(formant_shift) and formant_shift > 0):
+            raise ValueError("--formant-shift must be finite and positive")
     except ValueError as err:
         print(f"stream_transpose::error:: {err}", file=sys.stderr)
         sys.exit(1)
@@ -89,7 +92,8 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
     keyed = {} if noise_seed is None else {"noise_fn": keyed_noise_fn(live.mel_inverter.model, noise_seed),
                                            "stream_id": os.path.basename(input_audio_file)}
     audio = stream_file(live, samples, tick_samples, transposition, seed=seed, sample_rate=own_rate,
-                        output_rate=out_rate if out_rate != model_rate else None, **keyed)
+                        output_rate=out_rate if out_rate != model_rate else None,
+                        formant=None if formant_shift == 1.0 else formant_shift, **keyed)
     out_dir = os.path.dirname(os.path.abspath(output_file))
     os.makedirs(out_dir, exist_ok=True)
     ext = os.path.splitext(output_file)[1].lower().lstrip(".") or "wav"
@@ -127,6 +131,8 @@ if __name__ == "__main__":
                         help="model identifier or path to a model directory. Given without a value the script lists all known "
                              "models. (Def: %(default)s)")
     parser.add_argument("--transposition", default=1.0, type=float, metavar="F", help="factor on the pitch (Def: %(default)s)")
+    parser.add_argument("--formant-shift", dest="formant_shift", default=1.0, type=float, metavar="F",
+                        help="factor on the formant frequencies at the same pitch: F > 1 moves them up (Def: %(default)s)")
     parser.add_argument("--tick-ms", dest="tick_ms", default=80.0, type=float,
                         help="milliseconds of audio per push and tick (Def: %(default)s)")
     parser.add_argument("--resample", action="store_true",

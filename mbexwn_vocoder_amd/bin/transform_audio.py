@@ -2,7 +2,8 @@
 """Transpose sound files in batches: sound files in, transposed sound files out, on the MI355X HIP path.
 
     transform_audio.py FILES... -o DIR --model_id VOICE [--transposition F | --transposition-file LIST] [--noise-seed S]
-                       [--time-stretch F | --time-stretch-file LIST] [--batch N] [--gpus N] [--out-rate R|input]
+                       [--time-stretch F | --time-stretch-file LIST] [--formant-shift F | --formant-shift-file LIST]
+                       [--batch N] [--gpus N] [--out-rate R|input]
                        [--format flac] [--flac-compression fixed]
 
 Joins the stages of generate_mel.py and resynth_mel.py in one process (mbexwn_vocoder_amd/batched.py::run_audio_job): the
@@ -22,6 +23,11 @@ is reported and skipped; the others are written and the exit status is 1.
 analysis places its frames at the warped positions of the sound (include/mbexwn_warp.h) and the file gives K * hop samples
 for the K frames of the time map.  A factor of 1 is the regular analysis.  A file whose stretched length exceeds the engine's
 limit is reported and skipped like the others.
+
+--formant-shift F moves the formants of a file by the factor F (F > 1: up) at the same pitch and duration (DESIGN.md section
+6g; include/mbexwn_envelope.h): the VTF-net and the WaveNet conditioning read every mel row at f / F, the F0-net reads it as
+it is.  A factor of 1 is the job without the flag, launch by launch.  The level is not compensated.  The three controls
+combine freely.
 """
 import json
 import os
@@ -37,12 +43,15 @@ from mbexwn_vocoder_amd.batched import file_factors, file_stretches, read_transp
 
 def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, transposition_file=None, noise_seed=0, batch=16,
          gpus=1, num_threads=2, out_rate=None, format="flac", flac_compression="verbatim", conv_form="auto",
-         batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None):
+         batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None,
+         formant_shift=1.0, formant_shift_file=None):
     try:
         table = read_transposition_file(transposition_file) if transposition_file else None
         factors = file_factors(input_audio_files, transposition, table)
         stretches = file_stretches(input_audio_files, time_stretch,
                                    read_transposition_file(time_stretch_file) if time_stretch_file else None)
+        formants = file_factors(input_audio_files, formant_shift,
+                                read_transposition_file(formant_shift_file) if formant_shift_file else None, what="formant shift")
     except (OSError, ValueError) as err:
         print(f"transform_audio::error:: {err}", file=sys.stderr)
         sys.exit(1)
@@ -71,6 +80,8 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
         argv += ["--transposition-file", transposition_file] if transposition_file else []
         argv += ["--time-stretch", repr(float(time_stretch))] if time_stretch != 1.0 else []
         argv += ["--time-stretch-file", time_stretch_file] if time_stretch_file else []
+        argv += ["--formant-shift", repr(float(formant_shift))] if formant_shift != 1.0 else []
+        argv += ["--formant-shift-file", formant_shift_file] if formant_shift_file else []
         argv += ["--out-rate", str(out_rate)] if out_rate else []
         argv += [flag for flag, on in (("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant)) if on]
         status = run_ranks(os.path.abspath(__file__), argv, model_id, plan["files"], gpus, threads=num_threads, quiet=quiet,
@@ -95,13 +106,14 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
     skipped = run_audio_job(inv, input_audio_files, output_dir, format, factors=factors, noise_seed=noise_seed,
                             mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose,
                             quiet=quiet, flac_compression=flac_compression, out_rate=out_rate,
-                            stretches=None if all(ss == 1.0 for ss in stretches) else stretches)
+                            stretches=None if all(ss == 1.0 for ss in stretches) else stretches,
+                            formants=None if all(ff == 1.0 for ff in formants) else formants)
     if skipped:
         sys.exit(1)
 
 
 def factor_arg(text):
-    """argparse type of --transposition: a finite positive factor."""
+    """argparse type of --transposition and --formant-shift: a finite positive factor."""
     from argparse import ArgumentTypeError
     try:
         file_factors(["x"], float(text))
@@ -152,6 +164,12 @@ def make_parser():
     parser.add_argument("--time-stretch-file", dest="time_stretch_file", default=None, metavar="LIST",
                         help="text file with lines `basename factor`: the time-stretch factor of the files it lists, instead "
                              "of --time-stretch")
+    parser.add_argument("--formant-shift", dest="formant_shift", default=1.0, type=factor_arg, metavar="F",
+                        help="factor on the formant frequencies at the same pitch and duration: F > 1 moves them up "
+                             "(Def: %(default)s)")
+    parser.add_argument("--formant-shift-file", dest="formant_shift_file", default=None, metavar="LIST",
+                        help="text file with lines `basename factor`: the formant-shift factor of the files it lists, instead "
+                             "of --formant-shift")
     parser.add_argument("--noise-seed", dest="noise_seed", default=0, type=int, metavar="S",
                         help="seed of the keyed noise: a file's noise is a function of (S, its basename, the step) "
                              "(Def: %(default)s)")

@@ -11,6 +11,7 @@
 #include "../../include/mbexwn_flac.h"
 #include "../../include/mbexwn_noise.h"
 #include "../../include/mbexwn_warp.h"
+#include "../../include/mbexwn_envelope.h"
 
 static_assert(MBXN_FILL_TILE == mbx::NOISE_TILE, "mbexwn_noise.h states the tile of noise_keyed.hip");
 static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
@@ -262,13 +263,22 @@ mbx_status mbx_forward_stream(mbx_handle *hd, const float *mel, const int32_t *n
     return forward_impl(hd, mel, n_frames, batch, max_frames, noise, audio, workspace, workspace_bytes, hip_stream, ex);
 }
 
-mbx_status mbx_forward_ex(mbx_handle *hd, const float *mel, const int32_t *n_frames, int32_t batch, int32_t max_frames,
-                          const float *noise, float *audio, void *workspace, size_t workspace_bytes,
-                          const mbx_forward_options *options, void *hip_stream) {
+// mbx_forward_ex and mbxe_forward (include/mbexwn_envelope.h): the options (null: none) and the formant shift (all three or none)
+static mbx_status forward_with_options(mbx_handle *hd, const float *mel, const int32_t *n_frames, int32_t batch, int32_t max_frames,
+                                       const float *noise, float *audio, void *workspace, size_t workspace_bytes,
+                                       const mbx_forward_options *options, const float *env_factor, const float *env_centres,
+                                       float *env_mel, void *hip_stream) {
+    if ((env_factor != nullptr) != (env_centres != nullptr) || (env_factor != nullptr) != (env_mel != nullptr))
+        return fail(MBX_ERR_INVALID_ARGUMENT, "env_factor, env_centres and env_mel go together (all three or none)");
+    ForwardExtras ex;
+    ex.env_factor = env_factor;
+    ex.env_centres = env_centres;
+    ex.env_mel = env_mel;
+    if (!options) return forward_impl(hd, mel, n_frames, batch, max_frames, noise, audio, workspace, workspace_bytes, hip_stream, ex);
     // two sizes: the whole struct, or the struct as it was before the per-frame pitch control (f0_frames, f0_scale,
     // f0_item_mask are then not read: all NULL)
-    const bool has_control = options && options->struct_size == (int32_t)sizeof(mbx_forward_options);
-    if (!options || (!has_control && options->struct_size != (int32_t)offsetof(mbx_forward_options, f0_frames)))
+    const bool has_control = options->struct_size == (int32_t)sizeof(mbx_forward_options);
+    if (!has_control && options->struct_size != (int32_t)offsetof(mbx_forward_options, f0_frames))
         return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_forward_options ABI mismatch (struct_size)");
     if (!(options->transposition > 0.f)) return fail(MBX_ERR_INVALID_ARGUMENT, "transposition must be positive");
     const float *f0_frames = has_control ? options->f0_frames : nullptr, *f0_scale = has_control ? options->f0_scale : nullptr;
@@ -281,7 +291,6 @@ mbx_status mbx_forward_ex(mbx_handle *hd, const float *mel, const int32_t *n_fra
     if ((!options->layer_carry && options->layer_rows != 0) || options->layer_rows < 0)
         return fail(MBX_ERR_INVALID_ARGUMENT, "layer_rows must be >= 0 and needs layer_carry");
     const LayerOpts lay{options->layer_store, options->layer_store_floats, options->layer_carry, options->layer_rows};
-    ForwardExtras ex;
     ex.st_in = reinterpret_cast<const mbx::StreamState *>(options->state_in);
     ex.st_out = reinterpret_cast<mbx::StreamState *>(options->state_out);
     ex.f0_in = options->f0;
@@ -306,6 +315,22 @@ mbx_status mbx_forward_ex(mbx_handle *hd, const float *mel, const int32_t *n_fra
     ex.fe_margin_frames = options->fe_margin_frames;
     ex.fe_end_frames = options->fe_end_frames;
     return forward_impl(hd, mel, n_frames, batch, max_frames, noise, audio, workspace, workspace_bytes, hip_stream, ex);
+}
+
+mbx_status mbx_forward_ex(mbx_handle *hd, const float *mel, const int32_t *n_frames, int32_t batch, int32_t max_frames,
+                          const float *noise, float *audio, void *workspace, size_t workspace_bytes,
+                          const mbx_forward_options *options, void *hip_stream) {
+    if (!options) return fail(MBX_ERR_INVALID_ARGUMENT, "mbx_forward_options ABI mismatch (struct_size)");
+    return forward_with_options(hd, mel, n_frames, batch, max_frames, noise, audio, workspace, workspace_bytes, options, nullptr,
+                                nullptr, nullptr, hip_stream);
+}
+
+mbx_status mbxe_forward(mbx_handle *hd, const float *mel, const int32_t *n_frames, int32_t batch, int32_t max_frames,
+                        const float *noise, float *audio, void *workspace, size_t workspace_bytes,
+                        const mbx_forward_options *options, const float *env_factor, const float *env_centres, float *env_mel,
+                        void *hip_stream) {
+    return forward_with_options(hd, mel, n_frames, batch, max_frames, noise, audio, workspace, workspace_bytes, options, env_factor,
+                                env_centres, env_mel, hip_stream);
 }
 
 mbx_status mbx_window_advance(mbx_handle *hd, float *mel_window, const float *mel_new, float *noise_window,
@@ -576,6 +601,27 @@ mbx_status mbxw_mel_frames_at(const float *audio, int64_t stride, int32_t batch,
     if (const char *why = mbx::check_mel_warp(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("mel frames at: ") + why);
     if (batch == 0) return MBX_OK;
     mbx::launch_mel_warp(a, static_cast<hipStream_t>(hip_stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxe_warp_envelope(const float *mel, int64_t row_stride_items, int32_t batch, const int32_t *n_frames,
+                              int32_t max_frames, int32_t n_mels, const float *centres, const float *factors, float *out,
+                              void *hip_stream) {
+    mbx::EnvelopeArgs a{};
+    a.mel = mel;
+    a.bstride = row_stride_items;
+    a.batch = batch;
+    a.n_frames = n_frames;
+    a.max_frames = max_frames;
+    a.n_mels = n_mels;
+    a.centres = centres;
+    a.factors = factors;
+    a.out = out;
+    if (const char *why = mbx::check_envelope(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("warp envelope: ") + why);
+    if (batch == 0) return MBX_OK;
+    mbx::launch_envelope(a, static_cast<hipStream_t>(hip_stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

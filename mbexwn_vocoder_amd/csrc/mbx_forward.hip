@@ -189,6 +189,7 @@ struct ForwardCtx {
     int B, T;
     hipStream_t stream;
     const float *mel;              // (run_norm_mel: the normalised / the aligned copy from there on)
+    const float *mel_env = nullptr; // run_envelope: the rows the VTF and conditioning chains read (mel itself without a formant shift)
     const int32_t *n_frames;
     const float *noise;
     float *audio;
@@ -327,6 +328,21 @@ mbx_status plan_layer_spans(ForwardCtx &cx);
 mbx::WnGeometry wn_geometry(const ForwardCtx &cx);
 mbx::WnPlan plan_blocks(const mbx_handle *hd, int B, int T);
 
+// The formant shift of the call (mbxe_forward: env_factor): the whole window of the mel the chains read -> env_mel
+mbx::EnvelopeArgs envelope_args(const ForwardCtx &cx) {
+    mbx::EnvelopeArgs a{};
+    a.mel = cx.mel;
+    a.bstride = (long long)cx.T * cx.c.mel_channels;
+    a.batch = cx.B;
+    a.n_frames = cx.n_frames;
+    a.max_frames = cx.T;
+    a.n_mels = cx.c.mel_channels;
+    a.centres = cx.ex.env_centres;
+    a.factors = cx.ex.env_factor;
+    a.out = cx.ex.env_mel;
+    return a;
+}
+
 // Every check that needs no launch, in front of the first launch; carves the workspace and derives the regions.
 mbx_status check_forward_args(ForwardCtx &cx, void *workspace, size_t workspace_bytes) {
     mbx_handle *hd = cx.hd;
@@ -364,6 +380,9 @@ mbx_status check_forward_args(ForwardCtx &cx, void *workspace, size_t workspace_
         return fail(MBX_ERR_INVALID_ARGUMENT, "wn_frames needs active_frames and wn_begin inside the active region");
     if ((ex.sub_store != nullptr) != (ex.sub_carry != nullptr) || (ex.sub_store && ex.sub_store_rows <= 0))
         return fail(MBX_ERR_INVALID_ARGUMENT, "sub_store, sub_store_rows and sub_carry go together");
+    if (ex.env_factor)
+        if (const char *why = mbx::check_envelope(envelope_args(cx)))
+            return fail(MBX_ERR_INVALID_ARGUMENT, std::string("formant shift (env_factor / env_centres / env_mel): ") + why);
     cx.w = carve(hd, static_cast<char *>(workspace), cx.B, T);
     if (cx.w.total > workspace_bytes) return fail(MBX_ERR_WORKSPACE, "workspace too small, see mbx_workspace_size");
 
@@ -469,6 +488,16 @@ mbx_status run_norm_mel(ForwardCtx &cx) {
     return MBX_OK;
 }
 
+// ---- formant shift (no counterpart in the reference): the chains that describe the spectral envelope
+// read the mel rows warped along the frequency axis, the F0 chain keeps cx.mel
+void run_envelope(ForwardCtx &cx) {
+    cx.mel_env = cx.mel;
+    if (!cx.ex.env_factor) return;
+    ScopedEvents ev(cx.hd, PROF_FRONTEND, cx.stream);
+    mbx::launch_envelope(envelope_args(cx), cx.stream);
+    cx.mel_env = cx.ex.env_mel;
+}
+
 // ---- conditioning conv (reference custom_AE_layers.py:214-227,287), VTF-net -> cepstrum (reference
 // custom_pulsed_generator.py:793-800) and F0-net (reference :773-791) are independent chains on the mel input:
 // the n-th convolution of each goes into one launch (launch_conv1d_group; matters at small batch, where the
@@ -492,15 +521,16 @@ mbx_status run_frontend(ForwardCtx &cx) {
         const int Tf = fe_frames ? fe_frames : T;
         const long long f_off = fe_frames ? fe_end - Tf : 0;
         const int32_t *nf_fe = fe_frames ? nullptr : cx.n_frames;
-        const float *mel_fe = mel + f_off * c.mel_channels;
-        SubnetRun cond(hd, hd->cond_ops.data(), hd->wn[0].cond.data(), (int)hd->cond_ops.size(), mel_fe, c.mel_channels, nf_fe, B, Tf,
+        const float *mel_fe = mel + f_off * c.mel_channels;                 // the F0 chain's rows
+        const float *env_fe = cx.mel_env + f_off * c.mel_channels;          // the VTF and conditioning chains' rows
+        SubnetRun cond(hd, hd->cond_ops.data(), hd->wn[0].cond.data(), (int)hd->cond_ops.size(), env_fe, c.mel_channels, nf_fe, B, Tf,
                        w.sub4, w.sub5, w.cond + f_off * cond_cout, false, 1.f, 0.f, stream);
         if (hd->cond_ops.empty()) {   // disable_conditioning: cond_layers = zeros (reference custom_AE_layers.py:293-294)
             cond.finished = true;
             if (hipMemsetAsync(w.cond, 0, (size_t)B * T * cond_cout * sizeof(float), stream) != hipSuccess)
                 return fail(MBX_ERR_HIP, "hipMemsetAsync of the conditioning rows failed");
         }
-        SubnetRun vtf(hd, c.vtf_ops, hd->tab.vtf.data(), c.n_vtf_ops, mel_fe, c.mel_channels, nf_fe, B, Tf, w.sub2, w.sub3,
+        SubnetRun vtf(hd, c.vtf_ops, hd->tab.vtf.data(), c.n_vtf_ops, env_fe, c.mel_channels, nf_fe, B, Tf, w.sub2, w.sub3,
                       w.ceps + f_off * c.n_ceps, false, 1.f, 0.f, stream);
         const bool f0_wide = hd->f0_time_factor > c.pulse_per_frame;
         SubnetRun f0(hd, c.f0_ops, hd->tab.f0.data(), c.n_f0_ops, mel_fe, c.mel_channels, nf_fe, B, Tf, w.sub0, w.sub1,
@@ -539,7 +569,7 @@ mbx_status run_frontend(ForwardCtx &cx) {
                     return fail(MBX_ERR_HIP, "hipMemsetAsync of the conditioning rows failed");
                 continue;
             }
-            SubnetRun cb(hd, blk.cond_ops.data(), hd->wn[bk].cond.data(), (int)blk.cond_ops.size(), mel, c.mel_channels, cx.n_frames, B, T,
+            SubnetRun cb(hd, blk.cond_ops.data(), hd->wn[bk].cond.data(), (int)blk.cond_ops.size(), cx.mel_env, c.mel_channels, cx.n_frames, B, T,
                          w.sub4, w.sub5, w.mb_cond[bk], false, 1.f, 0.f, stream);
             mbx::ConvArgs one;
             while (cb.next_conv(one)) mbx::launch_conv1d_group(&one, 1, stream);
@@ -980,6 +1010,8 @@ void publish_stages(ForwardCtx &cx) {
     auto &sg = hd->stages;
     if (cx.nm_gain_src) sg["mel_norm"] = {w.mel_norm, (long long)T * c.mel_channels, (long long)T * c.mel_channels};
     else sg.erase("mel_norm");
+    if (cx.ex.env_factor) sg["mel_env"] = {cx.ex.env_mel, (long long)T * c.mel_channels, (long long)T * c.mel_channels};
+    else sg.erase("mel_env");
     sg["f0"] = {w.f0, npulse, npulse};
     sg["pulse"] = {w.pulse, npulse * (1 + c.wt_subharm_channels), npulse * (1 + c.wt_subharm_channels)};
     sg["cond"] = {w.cond, (long long)T * cx.cond_cout, (long long)T * cx.cond_cout};
@@ -1084,7 +1116,10 @@ mbx_status forward_impl(mbx_handle *hd, const float *mel, const int32_t *n_frame
     ForwardCtx cx(hd, ex, mel, n_frames, batch, max_frames, noise, audio, hip_stream);
     mbx_status st = check_forward_args(cx, workspace, workspace_bytes);
     if (st == MBX_OK) st = run_norm_mel(cx);
-    if (st == MBX_OK) st = run_frontend(cx);
+    if (st == MBX_OK) {
+        run_envelope(cx);
+        st = run_frontend(cx);
+    }
     if (st != MBX_OK) return st;
     run_excitation(cx);
     st = hd->blocks.empty() ? run_wavenet(cx) : run_wavenet_blocks(cx);

@@ -380,6 +380,9 @@ struct ForwardExtras {
     // per-frame pitch control (mbx_forward_options.f0_frames / f0_scale / f0_item_mask): device (batch, max_frames) rows
     const float *f0_frames = nullptr, *f0_scale = nullptr;
     const int32_t *f0_item_mask = nullptr;
+    // formant shift (mbxe_forward of include/mbexwn_envelope.h: env_factor / env_centres / env_mel): all three or none
+    const float *env_factor = nullptr, *env_centres = nullptr;
+    float *env_mel = nullptr;
     int active_begin = 0;
     const int32_t *active_frames = nullptr;
     int wn_begin = 0;

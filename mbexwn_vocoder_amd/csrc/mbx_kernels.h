@@ -406,6 +406,23 @@ struct MelWarpArgs {
 const char *check_mel_warp(const MelWarpArgs &a);
 void launch_mel_warp(const MelWarpArgs &a, hipStream_t stream);
 
+// formant shift: every mel row read at f / phi (mel_envelope.hip; include/mbexwn_envelope.h: mbxe_warp_envelope, and the
+// forward with it, mbxe_forward); the centre table from the host module envelope.py
+struct EnvelopeArgs {
+    const float *mel;            // (batch, max_frames, n_mels), items bstride floats apart
+    long long bstride;           // of mel and of out
+    int batch;
+    const int32_t *n_frames;     // (batch), clamped in the kernel to [0, max_frames]; rows behind are copied; null: max_frames
+    int max_frames, n_mels;
+    const float *centres;        // (n_mels) Hz, strictly increasing
+    const float *factors;        // (batch, max_frames)
+    float *out;                  // laid out like mel
+    int frames_per_block;        // set by the launcher
+};
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_envelope(const EnvelopeArgs &a);
+void launch_envelope(const EnvelopeArgs &a, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // optional RMS normalisation of the mel input / de-normalisation of the audio (norm_mel.hip)
 // ---------------------------------------------------------------------------------------------

@@ -242,6 +242,11 @@ def load_library():
     # include/mbexwn_warp.h (WARP_SYMBOLS)
     lib.mbxw_mel_frames_at.restype = i32
     lib.mbxw_mel_frames_at.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, i32, i32, i32, fp, fp, fp, vp, vp, ctypes.c_float, fp, vp]
+    # include/mbexwn_envelope.h (ENVELOPE_SYMBOLS)
+    lib.mbxe_warp_envelope.restype = i32
+    lib.mbxe_warp_envelope.argtypes = [fp, ctypes.c_int64, i32, vp, i32, i32, fp, fp, fp, vp]
+    lib.mbxe_forward.restype = i32
+    lib.mbxe_forward.argtypes = [vp, fp, vp, i32, i32, fp, fp, vp, ctypes.c_size_t, ctypes.POINTER(mbx_forward_options), fp, fp, fp, vp]
     _lib = lib
     return lib
 
@@ -272,6 +277,9 @@ NOISE_SYMBOLS = ["mbxn_fill_normal"]
 
 # include/mbexwn_warp.h: the mel analysis at arbitrary frame positions (prefix mbxw_; the seven lists above stay as they are)
 WARP_SYMBOLS = ["mbxw_mel_frames_at"]
+
+# include/mbexwn_envelope.h: the formant shift (prefix mbxe_; the eight lists above stay as they are)
+ENVELOPE_SYMBOLS = ["mbxe_warp_envelope", "mbxe_forward"]
 
 
 def _check(status):
@@ -804,7 +812,8 @@ def tensor_table(config, raw_weights, wavetables, split_f16=False):
 def forward_entry_point(state, active, control, f0, transposed):
     """The library entry point of a forward, from which of its arguments are present: stream_state, active, any of the
     per-frame pitch control (f0_frames / f0_scale / f0_item_mask), an f0 contour, a transposition other than 1.  The plain
-    entry points serve the calls that need no mbx_forward_options."""
+    entry points serve the calls that need no mbx_forward_options.  (A formant shift takes mbxe_forward of mbexwn_envelope.h
+    instead, with the options the call would have without it, or none.)"""
     if state:
         return "mbx_forward_ex" if active or control else "mbx_forward_stream"
     return "mbx_forward_ex" if f0 or transposed or control else "mbx_forward"
@@ -861,6 +870,8 @@ class MBExWNEngine:
         self._workspace = None
         self._last_shape = None
         self._flac_tables = None
+        self._env_centres = None                            # formant shift: the device centre table and the scratch (forward)
+        self._env_mel = None
 
     def close(self):
         if getattr(self, "_handle", None):
@@ -907,7 +918,7 @@ class MBExWNEngine:
 
     def forward(self, mel, n_frames=None, noise=None, out=None, stream_state=None, active=None, wavenet=None, carry=None,
                 layers=None, state_out=None, frontend=None, f0=None, transposition=1.0, f0_frames=None, f0_scale=None,
-                f0_item_mask=None):
+                f0_item_mask=None, formant=None):
         """mel (B,T,80) float32 cuda tensor; n_frames int32 cuda tensor (B,) or None;
         noise (B, T*steps_per_frame) float32 cuda tensor (N(0,1) draw) -> audio (B, T*hop) cuda tensor.
 
@@ -920,6 +931,11 @@ class MBExWNEngine:
         f0_scale``); f0_item_mask: optional int32 cuda tensor (B,), 1 = the item takes f0_frames, 0 = it keeps the F0-net
         (None: every item takes them).  Legal with and without stream_state and the window arguments; not together with f0 /
         a transposition other than 1.
+
+        formant: optional formant shift, float32 cuda tensor (B, T): one factor per mel frame, > 1 moves the formants up
+        (``mbxe_forward`` of include/mbexwn_envelope.h: ``env_factor``).  The VTF-net and the conditioning chains read the mel rows
+        warped along the frequency axis (envelope.warp_envelope_host gives their bits, ``stage("mel_env")`` returns them), the
+        F0-net reads the rows as they are: the pitch contour keeps its bits.  Legal with every other argument.
 
         stream_state: optional int32 cuda tensor (B, 6) holding one ``mbx_stream_state`` per item (see
         streaming.pack_state); the call then returns (audio, state_out) with the carried phase state.
@@ -954,6 +970,9 @@ class MBExWNEngine:
             if n_frames.dtype != torch.int32 or tuple(n_frames.shape) != (B,) or n_frames.device != self.device:
                 raise ValueError("n_frames must be an int32 tensor of shape (batch,) on the engine's device")
             n_frames = n_frames.contiguous()
+        if formant is not None and (not torch.is_tensor(formant) or formant.dtype != torch.float32 or
+                                    tuple(formant.shape) != (B, T) or formant.device != self.device):
+            raise ValueError(f"formant must be a float32 tensor of shape ({B}, {T}) on the engine's device")
         if out is None:
             out = torch.empty((B, T * self.dims.hop_size), dtype=torch.float32, device=self.device)
         ws, need = self._get_workspace(B, T)
@@ -963,7 +982,17 @@ class MBExWNEngine:
             f0_item_mask)
         common = (self._handle, mel.data_ptr(), n_frames.data_ptr() if n_frames is not None else None, B, T,
                   noise.data_ptr() if noise is not None else None, out.data_ptr(), ws.data_ptr(), need)
-        if entry == "mbx_forward":
+        if formant is not None:
+            # (mbxe_forward takes the options of the call without the shift: none where that is mbx_forward)
+            if entry == "mbx_forward_stream":
+                opt = mbx_forward_options()
+                opt.struct_size, opt.transposition = ctypes.sizeof(mbx_forward_options), 1.0
+                opt.state_in, opt.state_out = stream_state.data_ptr(), state_out.data_ptr()
+            formant = formant.contiguous()
+            scratch = self._envelope_scratch(B * T * self.dims.mel_channels)
+            _check(self._lib.mbxe_forward(*common, ctypes.byref(opt) if opt is not None else None, formant.data_ptr(),
+                                          self._envelope_centres().data_ptr(), scratch.data_ptr(), self._stream()))
+        elif entry == "mbx_forward":
             _check(self._lib.mbx_forward(*common, self._stream()))
         elif entry == "mbx_forward_stream":
             _check(self._lib.mbx_forward_stream(*common, stream_state.data_ptr(), state_out.data_ptr(), self._stream()))
@@ -1093,6 +1122,47 @@ class MBExWNEngine:
                                          tuple(f0_item_mask.shape) != (B,) or f0_item_mask.device != self.device):
             raise ValueError(f"f0_item_mask must be an int32 tensor of shape ({B},) on the engine's device")
         return tuple(None if cc is None else cc.contiguous() for cc in (f0_frames, f0_scale, f0_item_mask))
+
+    def _envelope_centres(self):
+        """The device table of the mel channels' centre frequencies (envelope.channel_centres of the model's analysis)."""
+        if self._env_centres is None:
+            from .envelope import channel_centres
+            self._env_centres = self._torch.as_tensor(channel_centres(self.config["preprocess_config"]), device=self.device)
+        return self._env_centres
+
+    def _envelope_scratch(self, floats):
+        """The warped mel rows of a forward with ``formant`` (env_mel of mbxe_forward; the stage "mel_env"): the engine's,
+        grown as needed -- like the workspace, one forward at a time uses it."""
+        if self._env_mel is None or self._env_mel.numel() < floats:
+            self._env_mel = self._torch.empty(floats, dtype=self._torch.float32, device=self.device)
+        return self._env_mel
+
+    def warp_envelope(self, mel, factors, n_frames=None):
+        """The formant shift on its own (``mbxe_warp_envelope``, include/mbexwn_envelope.h): mel float32 cuda (B, T,
+        mel_channels) -- a view with a batch stride of its own is passed as it is --, factors float32 cuda (B, T), n_frames
+        optional int32 cuda (B,) -> the warped rows (B, T, mel_channels), bit-equal to envelope.warp_envelope_host."""
+        torch = self._torch
+        n = self.dims.mel_channels
+        if (not torch.is_tensor(mel) or mel.dim() != 3 or mel.shape[2] != n or mel.dtype != torch.float32 or
+                mel.device != self.device):
+            raise ValueError(f"mel must be a float32 tensor (batch, frames, {n}) on the engine's device")
+        B, T = int(mel.shape[0]), int(mel.shape[1])
+        if not torch.is_tensor(factors) or factors.dtype != torch.float32 or tuple(factors.shape) != (B, T) or factors.device != self.device:
+            raise ValueError(f"factors must be a float32 tensor of shape ({B}, {T}) on the engine's device")
+        if n_frames is not None and (n_frames.dtype != torch.int32 or tuple(n_frames.shape) != (B,) or n_frames.device != self.device):
+            raise ValueError("n_frames must be an int32 tensor of shape (batch,) on the engine's device")
+        out = torch.empty((B, T, n), dtype=torch.float32, device=self.device)
+        if B == 0 or T == 0:
+            return out
+        if mel.stride(2) != 1 or mel.stride(1) != n or (B > 1 and mel.stride(0) < T * n):
+            mel = mel.contiguous()
+        factors = factors.contiguous()
+        stride = int(mel.stride(0)) if B > 1 else T * n
+        with torch.cuda.device(self.device):
+            _check(self._lib.mbxe_warp_envelope(mel.data_ptr(), stride, B, n_frames.contiguous().data_ptr() if n_frames is not None else None,
+                                                T, n, self._envelope_centres().data_ptr(), factors.data_ptr(), out.data_ptr(),
+                                                self._stream()))
+        return out
 
     def encode_flac16(self, audio, n_samples, sample_rate=None, wait=True, compression="verbatim"):
         """The FLAC frames (``flac.encode`` of the item without its 42-byte header) and max |x| of every item
@@ -1410,7 +1480,7 @@ class MBExWNEngine:
         _check(status)
         B = self._last_shape[0]
         dtype = torch.int32 if name == "ceps_index" else torch.float32
-        ws = self._workspace
+        ws = self._env_mel.view(torch.uint8) if name == "mel_env" else self._workspace      # (the caller's scratch: ours)
         offset = ptr.value - ws.data_ptr()
         flat = ws[offset: offset + B * stride.value * 4].view(dtype)
         return flat.view(B, stride.value)[:, :cnt.value].clone()

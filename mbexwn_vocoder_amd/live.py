@@ -463,6 +463,8 @@ class StreamingOutputResampler(_Stage):
 class _LStream:
     def __init__(self, hop, rng, noise_fn, up=1, down=1):
         self.factors = FrameFactors(hop, up, down)
+        self.formants = None          # FrameFactors of the formant shift, from the first push that gives one
+        self._rates = (hop, up, down)
         self.frames = 0               # mel frames handed to the synthesizer
         self.rng, self.noise_fn = rng, noise_fn
         self.flushed = False          # the synthesizer has been told that the stream is over
@@ -476,7 +478,7 @@ class LiveResynthesizer:
     Transposition rule: a ``transposition`` factor given with ``push_audio`` applies to the mel frames whose centre sample
     t * hop lies in that push's sample range (``FrameFactors``); a push without one has factor 1.  For a stream opened at a
     ``sample_rate`` of its own (resampled on the device, see ``StreamingAnalyzer``) the centre of frame t is input sample
-    (t * hop * down) // up.
+    (t * hop * down) // up.  A ``formant`` factor (formant shift, DESIGN.md section 6g) follows the same rule.
 
     Noise: the N(0,1) draw of the frames [a, b) of a stream is ``noise_fn(stream_id, a, b)`` ((b - a) * steps_per_frame
     float32 values); by default consecutive draws of a per-stream ``numpy.random.Generator`` seeded with ``seed``.
@@ -544,9 +546,15 @@ class LiveResynthesizer:
             self.output.close(stream_id)
             self._out_streams -= 1
 
-    def push_audio(self, stream_id, samples, last=False, transposition=None, sample_rate=None):
+    def push_audio(self, stream_id, samples, last=False, transposition=None, sample_rate=None, formant=None):
         """Append samples at the stream's rate (the model's, unless it was opened at another); ``transposition``: one finite
-        positive factor for the frames centred in this push (see the class docstring)."""
+        positive factor for the frames centred in this push (see the class docstring); ``formant``: one finite positive
+        formant-shift factor for the same frames -- the stream then equals ``MELInverter.transform_audio(formant=)`` of the
+        sound under the same noise."""
+        if formant is not None:
+            formant = float(formant)
+            if not (np.isfinite(formant) and formant > 0):
+                raise ValueError("formant must be finite and positive")
         if transposition is not None:
             transposition = float(transposition)
             if not (np.isfinite(transposition) and transposition > 0):
@@ -554,9 +562,18 @@ class LiveResynthesizer:
         st = self.streams[stream_id]
         before = self.analyzer.streams[stream_id].in_have
         self.analyzer.push(stream_id, samples, last=last, sample_rate=sample_rate)
-        st.factors.add(self.analyzer.streams[stream_id].in_have - before, transposition)
+        count = self.analyzer.streams[stream_id].in_have - before
+        if formant is not None and st.formants is None:
+            # the first formant factor of the stream: the samples pushed so far had factor 1
+            st.formants = FrameFactors(*st._rates)
+            st.formants.add(st.factors.samples)
+        st.factors.add(count, transposition)
+        if st.formants is not None:
+            st.formants.add(count, formant)
         if last:
             st.factors.close()
+            if st.formants is not None:
+                st.formants.close()
 
     def _noise(self, stream_id, st, first, end):
         spf = self.dims.steps_per_frame
@@ -582,7 +599,8 @@ class LiveResynthesizer:
             else:
                 scaled = np.zeros((0, self.dims.mel_channels), dtype=np.float32)
             noise = self._noise(sid, st, first, end) if self.dims.noise_sigma else None
-            self.synthesizer.push(sid, scaled, noise, last=done, transposition=st.factors.take(first, end))
+            shift = {} if st.formants is None else {"formant": st.formants.take(first, end)}
+            self.synthesizer.push(sid, scaled, noise, last=done, transposition=st.factors.take(first, end), **shift)
             st.frames, st.flushed = end, done
         audio = self.synthesizer.tick()
         if not self._out_streams:

@@ -156,7 +156,7 @@ class MELInverter(object):
         return self.model.keyed_noise(int(noise_seed), keys, [int(tt) * dims.wn_in_rows_per_frame for tt in frames])
 
     def synth_from_mel(self, scaled_mell, noise=None, f0=None, transposition=None, out_rate=None, noise_seed=None,
-                       noise_key=0):
+                       noise_key=0, formant=None):
         """(1, T, mel_channels) log-mel -> float32 audio of T*hop_size samples
         (reference mel_inverter.py:151-154; like there, a batch is flattened by ``ravel``).
 
@@ -175,22 +175,30 @@ class MELInverter(object):
         ``noise_seed`` (this build): the noise channel takes the keyed draw of the item ``noise_key`` (an integer, e.g.
         ``noise.item_key(file name)``; one per row of a batch, or one for all) under that seed -- ``engine.keyed_noise``,
         handed to the forward as ``noise`` is.  The audio is then a function of (mel, seed, key) and does not depend on what
-        was synthesised before.  Not together with ``noise``."""
+        was synthesised before.  Not together with ``noise``.
+
+        ``formant`` (this build): a formant shift -- one factor or one per mel frame, finite and positive
+        (:func:`check_factors`), > 1 moves the formants up.  The spectral envelope of every frame is read at ``f / factor``
+        (``envelope.warp_envelope_host`` is the definition) by the VTF-net and the WaveNet conditioning,
+        while the F0-net reads the mel as it is: pitch and timing stay.  The level is not compensated.  It combines freely
+        with ``f0`` / ``transposition``."""
         out_rate = self._output_rate(out_rate)
         if noise_seed is not None:
             shape = np.shape(scaled_mell)
             keys = [int(kk) for kk in np.broadcast_to(np.asarray(noise_key, dtype=object), (int(shape[0]),))]
             noise = self._keyed_noise(noise, noise_seed, keys, [int(shape[1])] * int(shape[0]))
         self._calibrate_if_pending(scaled_mell)
-        if f0 is not None or transposition is not None:
-            return self._synth_with_pitch(scaled_mell, noise, f0, transposition, out_rate)
+        if formant is not None:
+            formant = np.asarray(check_factors(formant, int(np.shape(scaled_mell)[1]), "formant"), dtype=np.float32)
+        if f0 is not None or transposition is not None or formant is not None:
+            return self._synth_with_pitch(scaled_mell, noise, f0, transposition, out_rate, formant)
         syn_audio = self.model.infer(scaled_mell, sigma=None, synth_length=scaled_mell.shape[1] * self.hop_size,
                                      noise=noise)
         if out_rate is not None:
             return self._to_rate(syn_audio.tensor, out_rate).cpu().numpy().ravel()
         return syn_audio.numpy().ravel()
 
-    def _synth_with_pitch(self, scaled_mell, noise, f0, transposition, out_rate=None):
+    def _synth_with_pitch(self, scaled_mell, noise, f0, transposition, out_rate=None, formant=None):
         import torch
         model = self.model
         n_frames = int(scaled_mell.shape[1])
@@ -212,13 +220,15 @@ class MELInverter(object):
         if f0_rows is not None and not torch.is_tensor(f0_rows):
             raise ValueError(f"f0 must hold one value per mel frame ({T})")
         scale = None if transposition is None else rows(transposition, "transposition")
+        # (a mel shorter than the synthesis was continued by one frame in _prepare: that frame repeats the last factor)
+        shift = {} if formant is None else {"formant": rows(np.concatenate((formant, formant[-1:]))[:T], "formant")}
         if scale is None or torch.is_tensor(scale):
-            audio = model.forward(mel, noise=noise, f0_frames=f0_rows, f0_scale=scale)
+            audio = model.forward(mel, noise=noise, f0_frames=f0_rows, f0_scale=scale, **shift)
         elif f0_rows is None:                                # a scalar: the whole-item option, as infer_components applies it
-            audio = model.forward(mel, noise=noise, transposition=float(scale))
+            audio = model.forward(mel, noise=noise, transposition=float(scale), **shift)
         else:
             audio = model.forward(mel, noise=noise, f0_frames=f0_rows,
-                                  f0_scale=torch.full((B, T), float(scale), dtype=torch.float32, device=model.device))
+                                  f0_scale=torch.full((B, T), float(scale), dtype=torch.float32, device=model.device), **shift)
         if out_rate is not None:
             return self._to_rate(audio[:, :n_frames * self.hop_size], out_rate).cpu().numpy().ravel()
         return audio[:, :n_frames * self.hop_size].cpu().numpy().ravel()
@@ -238,7 +248,8 @@ class MELInverter(object):
                               f"chosen at creation ({self.model.conv_form_info()['form']})", RuntimeWarning)
 
     def synth_from_mels(self, scaled_mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False,
-                        flac_compression="verbatim", out_rate=None, noise_seed=None, noise_keys=None, transpositions=None):
+                        flac_compression="verbatim", out_rate=None, noise_seed=None, noise_keys=None, transpositions=None,
+                        formants=None):
         """Batched :meth:`synth_from_mel` (this build): a list of ``scale_mel`` outputs (1, T_i, mel_channels) -> a list of
         float32 audio (T_i * hop_size,), or with ``flac=True`` of complete FLAC files (bytes; frames encoded on the device).
 
@@ -255,7 +266,8 @@ class MELInverter(object):
         ``noise_seed``: item i takes the keyed draw of ``noise_keys[i]`` (default: its index) under that seed, as
         :meth:`synth_from_mel` with ``noise_seed`` / ``noise_key`` does -- nothing is replayed, and an item's draw does not
         depend on the list it is in.  Not together with ``noises``.  ``transpositions``: per item None, or (T_i,) factors,
-        one per mel frame (``f0_scale`` rows of the forward)."""
+        one per mel frame (``f0_scale`` rows of the forward).  ``formants``: per item None, one formant-shift factor, or
+        (T_i,) of them (:meth:`synth_from_mel` ``formant``; the ``formant`` rows of the forward)."""
         import torch
         from .batched import replay_noise, run_micro_batches
         if noise_seed is not None and noises is not None:
@@ -267,6 +279,11 @@ class MELInverter(object):
         if len(scaled_mels):
             self._calibrate_if_pending(scaled_mels[0])
         mels =[np.asarray(mm, dtype=np.float32).reshape(-1, mm.shape[-2], mm.shape[-1])[0] for mm in scaled_mels]
+        if formants is not None:
+            if len(formants) != len(mels):
+                raise ValueError("synth_from_mels: one formants entry per mel")
+            formants = [None if ff is None else np.asarray(check_factors(ff, int(mm.shape[0]), "formant"), dtype=np.float32)
+                        for ff, mm in zip(formants, mels)]
         dims = self.model.dims
         if noise_seed is not None:
             keys = list(range(len(mels))) if noise_keys is None else [int(kk) for kk in noise_keys]
@@ -282,7 +299,8 @@ class MELInverter(object):
                       .reshape(-1) for zz in noises]
         out = [None] * len(mels)
         for batch in run_micro_batches(self.model, mels, noises, max_batch, max_padded_frames, flac=flac, host_audio=not flac,
-                                       flac_compression=flac_compression, out_rate=out_rate, transpositions=transpositions):
+                                       flac_compression=flac_compression, out_rate=out_rate, transpositions=transpositions,
+                                       formants=formants):
             batch.wait()
             for jj, ii in enumerate(batch.indices):
                 if not flac:
@@ -295,7 +313,7 @@ class MELInverter(object):
         return out
 
     def transform_audio(self, sounds, rates, names, transposition=1.0, noise_seed=0, out_rate=None, max_batch=16,
-                        max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None):
+                        max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None, formant=None):
         """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
         keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
         factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
@@ -309,7 +327,11 @@ class MELInverter(object):
         rate before the output resampler; the transposition rows, the keyed noise (counted by output step), ``out_rate``
         and ``flac`` work on those frames as on any others.
 
-        An item's audio is a function of (sound, rate, name, factor, stretch, seed, out_rate): with a ``batch_invariant``
+        ``formant``: a formant shift at the same pitch and duration -- None, or a list with one entry
+        per item, each a factor or one factor per mel frame of the item (:meth:`synth_from_mels` ``formants``).  It combines
+        freely with ``transposition`` and ``time_stretch``.
+
+        An item's audio is a function of (sound, rate, name, factor, stretch, formant, seed, out_rate): with a ``batch_invariant``
         engine or one pinned to a convolution form it does not depend on the batch, the order or the other items."""
         from . import timemap
         from .analysis import generate_mels
@@ -317,6 +339,8 @@ class MELInverter(object):
         factors = check_factors(transposition, len(sounds))
         if not (len(sounds) == len(rates) == len(names)):
             raise ValueError("transform_audio: one rate and one name per sound")
+        if formant is not None and (not isinstance(formant, (list, tuple)) or len(formant) != len(sounds)):
+            raise ValueError("transform_audio: formant takes one entry per sound")
         maps = timemap.per_item(time_stretch, len(sounds), "transform_audio: time_stretch")
         dicts = generate_mels(sounds, rates, self.preprocess_config, on_device=True, batch=max_batch,
                               time_maps=None if all(mm is None for mm in maps) else maps,
@@ -325,7 +349,7 @@ class MELInverter(object):
         rows = [np.full(int(mm.shape[1]), ff, dtype=np.float32) for mm, ff in zip(scaled, factors)]
         return self.synth_from_mels(scaled, max_batch=max_batch, max_padded_frames=max_padded_frames, flac=flac,
                                     flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed,
-                                    noise_keys=[item_key(nn) for nn in names], transpositions=rows)
+                                    noise_keys=[item_key(nn) for nn in names], transpositions=rows, formants=formant)
 
     def calibrate(self, scaled_mells, verbose=False, max_frames=400, seed=42):
         """Decide the form of the WaveNet's dilated convolution on REAL data (this build; C ABI mbx_calibrate).
@@ -499,15 +523,16 @@ class KeyedNoise:
         self.seed, self.keys = int(seed), [int(kk) for kk in keys]
 
 
-def check_factors(transposition, count):
-    """``transposition`` -- one factor or ``count`` of them -- as a list of ``count`` finite positive floats."""
+def check_factors(transposition, count, what="transposition"):
+    """``transposition`` -- one factor or ``count`` of them -- as a list of ``count`` finite positive floats.  ``what`` names
+    the factor in the messages (the formant shift is checked here too: one factor, or one per mel frame)."""
     factors = np.asarray(transposition, dtype=np.float64)
     if factors.ndim == 0:
         factors = np.full(count, float(factors))
     if factors.shape != (count,):
-        raise ValueError(f"transposition must be one factor or one per item ({count})")
+        raise ValueError(f"{what} must be one factor or one per item ({count})")
     if not (np.all(np.isfinite(factors)) and np.all(factors > 0)):
-        raise ValueError("transposition must be finite and positive")
+        raise ValueError(f"{what} must be finite and positive")
     return [float(ff) for ff in factors]
 
 

@@ -166,20 +166,21 @@ class _Stream:
 class _InputRows:
     """Input frames of every stream, one row per slot (shared so that a tick gathers its frames with one indexed copy): mel
     and noise, and next to them the per-frame pitch control -- F0 in Hz ("frames" streams; 1 where none was given, never
-    read there) and the transposition factor (1 where none was given)."""
+    read there) and the transposition factor (1 where none was given) -- and the formant-shift factor (1 where none was given)."""
 
     def __init__(self, mel_channels, steps_per_frame, cap=256):
         self._widths = (mel_channels, steps_per_frame)
         self.cap = cap            # frames per row (grows on demand)
-        self.mel, self.noise, self.f0, self.scale = self._alloc(0, cap)
+        self.mel, self.noise, self.f0, self.scale, self.formant = self._alloc(0, cap)
 
     def _alloc(self, slots, cap):
         return (np.zeros((slots, cap, self._widths[0]), dtype=np.float32),
                 np.zeros((slots, cap, self._widths[1]), dtype=np.float32),
-                np.ones((slots, cap), dtype=np.float32), np.ones((slots, cap), dtype=np.float32))
+                np.ones((slots, cap), dtype=np.float32), np.ones((slots, cap), dtype=np.float32),
+                np.ones((slots, cap), dtype=np.float32))
 
     def _arrays(self):
-        return self.mel, self.noise, self.f0, self.scale
+        return self.mel, self.noise, self.f0, self.scale, self.formant
 
     @property
     def slots(self):
@@ -190,7 +191,7 @@ class _InputRows:
         if slots <= self.slots and cap <= self.cap:
             return
         old = self._arrays()
-        self.mel, self.noise, self.f0, self.scale = self._alloc(max(slots, self.slots), max(cap, self.cap))
+        self.mel, self.noise, self.f0, self.scale, self.formant = self._alloc(max(slots, self.slots), max(cap, self.cap))
         for new, was in zip(self._arrays(), old):
             new[:was.shape[0], :was.shape[1]] = was
         self.cap = self.mel.shape[1]
@@ -200,16 +201,17 @@ class _InputRows:
         for arr in self._arrays():
             arr[slot, :live] = arr[slot, n:n + live]
 
-    def append(self, slot, col, mel, noise=None, f0=None, scale=None):
+    def append(self, slot, col, mel, noise=None, f0=None, scale=None, formant=None):
         n = mel.shape[0]
         self.mel[slot, col:col + n] = mel
         if noise is not None:
             self.noise[slot, col:col + n] = noise
         self.f0[slot, col:col + n] = 1.0 if f0 is None else f0
         self.scale[slot, col:col + n] = 1.0 if scale is None else scale
+        self.formant[slot, col:col + n] = 1.0 if formant is None else formant
 
     def window(self, slot, lo, hi):
-        """(mel, noise, f0, scale) of the columns [lo, hi) of a row (views)."""
+        """(mel, noise, f0, scale, formant) of the columns [lo, hi) of a row (views)."""
         return tuple(arr[slot, lo:hi] for arr in self._arrays())
 
     def gather(self, slots, cols, **into):
@@ -245,12 +247,14 @@ class _Layout:
         return out
 
 
-def _stage_layout(B, chunk, tpad, mel_channels, spf, use_noise, control):
+def _stage_layout(B, chunk, tpad, mel_channels, spf, use_noise, control, formant=False):
     """The (float32) stage buffer of a replayed tick: new mel frames, new noise, phase states, ring positions and -- once
-    the synthesizer has seen pitch control -- the control rows of the whole windows (what a tick does not upload is empty)."""
+    the synthesizer has seen pitch control / a formant shift -- the control rows / the formant factors of the whole windows
+    (what a tick does not upload is empty)."""
     return _Layout([("mel", (B, chunk, mel_channels), "float32"), ("noise", (B, chunk * spf * use_noise), "float32"),
                     ("states", (B, 6), "int32"), ("fpos", (B,), "int32"),
-                    ("f0_frames", (B, tpad * control), "float32"), ("f0_scale", (B, tpad * control), "float32")])
+                    ("f0_frames", (B, tpad * control), "float32"), ("f0_scale", (B, tpad * control), "float32"),
+                    ("formant", (B, tpad * formant), "float32")])
 
 
 @dataclass
@@ -259,10 +263,11 @@ class _TickInputs:
     mel: object
     noise: object
     tpad: int
-    args: object              # device views: states, desc, ldesc, nfr, act, wn, fpos, f0_item_mask, f0_frames, f0_scale
+    args: object              # device views: states, desc, ldesc, nfr, act, wn, fpos, f0_item_mask, f0_frames, f0_scale, formant
     use_fe: bool
     control: bool
     f0_mask: object           # host copy of f0_item_mask, or None without control
+    formant: bool = False     # the call carries the formant factors of the whole windows
 
 
 @dataclass
@@ -290,6 +295,7 @@ class _Phase:
     wavenet_frames: int
     control: bool
     f0_mask: object
+    formant: bool = False
 
     def same_geometry(self, other):
         for ff in fields(self):
@@ -402,6 +408,9 @@ class StreamingSynthesizer:
         # unchanged); from then on every tick passes the control rows of its whole windows -- factor 1 and mask 0 for the
         # streams without control, which changes no bit of theirs (the interpolated factor is exactly 1).
         self._control = False
+        # The same for the formant shift: set by the first factor other than 1; from then on every tick passes the factors of
+        # its whole windows -- 1 for the streams without, whose rows are then copied bit for bit.
+        self._formant = False
         # The Winograd form of the dilated convolution pairs outputs t and t+d inside blocks of 2d steps counted from
         # the first row of the item; a window that starts on a multiple of 2*d_max steps pairs exactly like the offline
         # run, which keeps the streamed audio bit-identical (any other start is equal up to float32 rounding only).
@@ -506,13 +515,15 @@ class StreamingSynthesizer:
         st = self.streams.pop(stream_id)
         self._free_slots.append(st.slot)
 
-    def push(self, stream_id, mel_frames, noise=None, last=False, f0=None, transposition=None):
+    def push(self, stream_id, mel_frames, noise=None, last=False, f0=None, transposition=None, formant=None):
         """Append mel frames (n, mel_channels) and the matching N(0,1) draw (n*steps_per_frame,) to a stream.
 
         ``f0``: (n,) Hz, one value per pushed frame -- required for a stream opened with ``f0="frames"``, refused for any
         other.  ``transposition``: factor on the stream's contour, a scalar or (n,) values (default 1).  Both are brought to
         the pulse rate by the model's linear interpolator, towards the next frame's value; they must be finite and
-        positive."""
+        positive.  ``formant``: formant-shift factor, a scalar or (n,) values, finite and positive (default 1): a frame's
+        factor travels with the frame and warps that frame's envelope only, so the streamed audio
+        equals the offline ``forward(formant=)`` of the whole utterance."""
         st = self.streams[stream_id]
         mel_frames = np.asarray(mel_frames, dtype=np.float32).reshape(-1, self.dims.mel_channels)
         n = mel_frames.shape[0]
@@ -533,6 +544,14 @@ class StreamingSynthesizer:
                     raise ValueError("transposition must be a scalar or hold one value per pushed mel frame")
             if not (np.all(np.isfinite(transposition)) and np.all(transposition > 0)):
                 raise ValueError("transposition must be finite and positive")
+        if formant is not None:
+            formant = np.asarray(formant, dtype=np.float32)
+            if formant.ndim > 0:
+                formant = formant.reshape(-1)
+                if formant.shape[0] != n:
+                    raise ValueError("formant must be a scalar or hold one value per pushed mel frame")
+            if not (np.all(np.isfinite(formant)) and np.all(formant > 0)):
+                raise ValueError("formant must be finite and positive")
         if self.dims.noise_sigma:
             if noise is None:
                 raise ValueError("noise is required (explicit input of the path)")
@@ -549,7 +568,11 @@ class StreamingSynthesizer:
                 st.base = keep_from
             if st.have - st.base + n > rows.cap:
                 rows.grow(rows.slots, max(2 * rows.cap, st.have - st.base + n))
-        rows.append(st.slot, st.have - st.base, mel_frames, noise if self.dims.noise_sigma else None, f0, transposition)
+        rows.append(st.slot, st.have - st.base, mel_frames, noise if self.dims.noise_sigma else None, f0, transposition,
+                    formant)
+        if not self._formant and formant is not None and np.any(formant != 1.0):
+            self._leave_steady()                  # (as for the first pitch control below)
+            self._formant = True
         if not self._control and transposition is not None and np.any(transposition != 1.0):
             # the first control this synthesizer sees: a steady run recorded without the control arguments is left and
             # captured anew
@@ -603,6 +626,8 @@ class StreamingSynthesizer:
         pitch = {}
         if up.control:
             pitch = {"f0_item_mask": args.f0_item_mask, "f0_frames": args.f0_frames, "f0_scale": args.f0_scale}
+        if up.formant:
+            pitch["formant"] = args.formant
         audio, state_out = self.engine.forward(
             up.mel, n_frames=args.nfr, noise=up.noise, stream_state=args.states,
             active=(plan.a0, args.act, int(plan.act.max())),
@@ -629,34 +654,39 @@ class StreamingSynthesizer:
 
     def _upload(self, plan, streams):
         """The windows of a plan, gathered from the shared input rows, and every int32 argument of the call in one upload
-        (with the control rows, floats bit-cast, once the synthesizer has seen pitch control)."""
+        (with the control rows / the formant factors, floats bit-cast, once the synthesizer has seen pitch control / a formant
+        shift)."""
         import torch
-        B, spf, control = len(streams), self.dims.steps_per_frame, self._control
+        B, spf, control, formant = len(streams), self.dims.steps_per_frame, self._control, self._formant
         tpad = max(plan.tmax, self._tcap)         # periodic schedules keep one window size for all phases (n_frames masks)
         mel = np.zeros((B, tpad, self.dims.mel_channels), dtype=np.float32)
         noise = np.zeros((B, tpad * spf), dtype=np.float32)
         # the control rows of the whole windows (the frames behind an item's end are not read)
         f0_rows = np.ones((B, tpad * control), dtype=np.float32)
         scale_rows = np.ones((B, tpad * control), dtype=np.float32)
+        formant_rows = np.ones((B, tpad * formant), dtype=np.float32)
         for item, (st, (first, end)) in enumerate(zip(streams, plan.windows)):
-            w_mel, w_noise, w_f0, w_scale = self._rows.window(st.slot, first - st.base, end - st.base)
+            w_mel, w_noise, w_f0, w_scale, w_formant = self._rows.window(st.slot, first - st.base, end - st.base)
             mel[item, :end - first] = w_mel
             if self.dims.noise_sigma:
                 noise[item, :(end - first) * spf] = w_noise.reshape(-1)
             if control:
                 f0_rows[item, :end - first], scale_rows[item, :end - first] = w_f0, w_scale
+            if formant:
+                formant_rows[item, :end - first] = w_formant
         f0_mask = np.asarray([st.f0_mode == "frames" for st in streams], dtype=np.int32) if control else None
         parts = [("states", plan.states, "int32"), ("desc", plan.desc, "int32"), ("ldesc", plan.ldesc, "int32"),
                  ("nfr", plan.nfr, "int32"), ("act", plan.act, "int32"),
                  ("wn", plan.wn if plan.wn is not None else plan.act, "int32"), ("fpos", plan.fpos, "int32"),
                  ("f0_item_mask", f0_mask if control else np.zeros(0, np.int32), "int32"),
-                 ("f0_frames", f0_rows, "float32"), ("f0_scale", scale_rows, "float32")]
+                 ("f0_frames", f0_rows, "float32"), ("f0_scale", scale_rows, "float32"), ("formant", formant_rows, "float32")]
         dev = self.engine.device
         flat = np.concatenate([arr.ravel().view(np.int32) for _, arr, _ in parts])
         args = _Layout([(name, arr.shape, dtype) for name, arr, dtype in parts]).views(torch.as_tensor(flat, device=dev))
         return _TickInputs(mel=torch.as_tensor(mel, device=dev),
                            noise=torch.as_tensor(noise, device=dev) if self.dims.noise_sigma else None, tpad=tpad, args=args,
-                           use_fe=self.fe_carry and self.carry and tpad <= self._fe_ring, control=control, f0_mask=f0_mask)
+                           use_fe=self.fe_carry and self.carry and tpad <= self._fe_ring, control=control, f0_mask=f0_mask,
+                           formant=formant)
 
     def _commit(self, plan, todo, audio, lo, state_out):
         """Cut every stream's chunk out of the audio (whose column 0 is sample `lo` of the windows) and move the streams on
@@ -697,7 +727,7 @@ class StreamingSynthesizer:
             layer_rows=plan.layer_rows, act=plan.act.copy(), wn=plan.wn.copy(), nfr=plan.nfr.copy(), desc=plan.desc.copy(),
             ldesc=plan.ldesc.copy(), state_consts=plan.states[:, 3:5].copy(), rel0=plan.rel[0], use_fe=up.use_fe,
             frames=self.last_tick_frames, active_frames=self.last_tick_active_frames,
-            wavenet_frames=self.last_tick_wavenet_frames, control=up.control, f0_mask=up.f0_mask)
+            wavenet_frames=self.last_tick_wavenet_frames, control=up.control, f0_mask=up.f0_mask, formant=up.formant)
         sids = [sid for sid, _, _ in todo]
         run = self._steady
         if run is None or run.sids != sids or run.tpad != up.tpad:
@@ -802,7 +832,7 @@ class StreamingSynthesizer:
         # ring positions and -- once the synthesizer has seen pitch control -- the control rows of the whole windows
         # (B, tpad) each: small next to the mel frames, and the window they belong to is known to the host anyway, so they
         # need no device-resident window and no second move launch
-        layout = _stage_layout(B, chunk, tpad, dims.mel_channels, spf, use_noise, rec.control)
+        layout = _stage_layout(B, chunk, tpad, dims.mel_channels, spf, use_noise, rec.control, rec.formant)
         stage_host = torch.ones(layout.size, dtype=torch.float32).pin_memory()
         stage_dev = torch.empty_like(stage_host, device=dev)
         new = layout.views(stage_dev)
@@ -810,6 +840,8 @@ class StreamingSynthesizer:
         if rec.control:
             pitch = {"f0_frames": new.f0_frames, "f0_scale": new.f0_scale,
                      "f0_item_mask": torch.as_tensor(rec.f0_mask, device=dev)}
+        if rec.formant:
+            pitch["formant"] = new.formant
         # front end: the window gained `chunk` frames and the last fe_right frames of the window before were inexact: the
         # sub-nets run on the last chunk + fe_right (+ their reach) frames in front of the window's end (frame rec.T of the
         # buffer: fe_end_frames), everything in front of that comes from the ring
@@ -840,7 +872,9 @@ class StreamingSynthesizer:
         return _CapturedTick(graph=graph, stage_host=stage_host, host=layout.views(stage_host.numpy()),
                              arange=np.arange(chunk, dtype=np.int64), arange_win=np.arange(rec.T, dtype=np.int64),
                              audio_host=audio_host, state_host=state_host, shift=shift, keep=keep,
-                             keep_alive=(stage_dev, ints, pitch))
+                             # (the engine's scratch of the warped rows, sized by this phase's recorded tick: a later,
+                             # larger forward gives the engine a new one, the graph keeps writing this one)
+                             keep_alive=(stage_dev, ints, pitch, getattr(eng, "_env_mel", None) if rec.formant else None))
 
     def _graph_tick(self):
         """A steady tick as one graph launch: gather and upload the new frames and the phase states, replay, read the
@@ -885,6 +919,9 @@ class StreamingSynthesizer:
             # the control rows of the whole windows [emitted - rel0, + T): one gather per row
             wcols = (emitted - rec.rel0 - base)[:, None] + cap.arange_win
             self._rows.gather(slots, wcols, f0=host.f0_frames[:, :rec.T], scale=host.f0_scale[:, :rec.T])
+        if host.formant is not None:
+            wcols = (emitted - rec.rel0 - base)[:, None] + cap.arange_win
+            self._rows.gather(slots, wcols, formant=host.formant[:, :rec.T])
         host.states[:, :3] = run.state_v[:, :3]
         host.states[:, 3:5] = rec.state_consts
         host.states[:, 5] = 0

@@ -50,7 +50,9 @@ WN_IDS = ["c12-f43", "c36-f43", "speech-direct", "speech-f23", "speech-f43", "sp
           "speech-split-f32h",
           "voice-f43", "deep12-f43", "deep12-f43-invariant", "deep12-split", "large-f43", "large-split",
           # C + n_out one column pair past a multiple of 32: a last pair of two valid columns under the wide and the wave kernel
-          "c292-invariant", "c324-rs-split2"]
+          "c292-invariant", "c324-rs-split2",
+          # the F(4,3) blocks of two column tiles: a partial tile inside a pair, a pair beside an odd one-tile launch, one pair
+          "c292-two-tile", "c68-two-tile", "c36-two-tile"]
 # every multi-block geometry once (the mb_* regions are the last ones carved, next to the end of the workspace), the handle
 # without weight images (res/skip through conv1d), and the pulse-PQMF and sub-harmonic inputs
 BLOCK_IDS = ["blocks-f43", "blocks-noimages", "up2-f43", "three-precond-gfu", "nocond", "c64-f43", "deep6-f43", "lin2-f43",

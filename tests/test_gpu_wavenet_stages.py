@@ -23,6 +23,15 @@ are ragged (C % 32 != 0 under an odd tile count, C % 8 == 4: plane padding, C + 
 the mixed mode under float32 gates, and hold it to the same bar; what the mode's arithmetic alone costs is in
 test_split_reference.py.
 
+The F(4,3) blocks of two column tiles (wn_gate_winograd4q_kernel, the gate of the large launches) promise the bits of the
+one-tile blocks.  The "*-two-tile" cases pin them on the ragged batch (tune gate_shape 4 holds at every launch size) at the
+channel counts where THEIR tiles are ragged (TWO_TILE_C: a partial tile inside a pair, one pair only, an odd last tile in the
+one-tile kernel, the shortest K loop, both parities of the stage the conditioning rows land in) and on the model variants,
+hold them to the oracle, and compare their stages bit for bit with a run pinned to the one-tile blocks.  Which instantiation
+of the F(4,3) kernels a case launches follows from its plan row (kernel, block shape, conditioning rows, sub-sequences per
+block) and the gate activation; test_wn_stage_plan_host.py derives it on the host for every case here and holds the union to
+the launcher's list, and every case asserts that the plan is what ran.
+
 The padding contract of include/mbexwn.h ("every boundary op honours the item's own length") is held bit for bit: the same
 ragged batch with its padding frames of mel and noise at 0, 1e30 and NaN."""
 import contextlib
@@ -81,6 +90,10 @@ GEOMETRIES = {
     # the channel counts of the res/skip and tail instantiations, 3 layers each
     **{f"c{C}": ("SPEECH", {_WN + "n_channels": C, _WN + "n_layers": 3})
        for C in (64, 68, 128, 132, 192, 196, 292, 300, 316, 324, 340, 352, 356, 512)},
+    # gfu at C = 64 (the oracle is about 25 times cheaper than at C = 320): cond_up = 5 takes the 256-row blocks of 56
+    # conditioning rows; nine layers reach d = 256, whose 16 sub-sequences of a 52-frame item have 65 rows
+    "lin5-c64-gfu": ("SPEECH", {_WN + "n_channels": 64, _WN + "n_layers": 3, _WN + "cond_lin_upsampling": 5, _WN + "activation": "gfu"}),
+    "deep9-c64-gfu": ("SPEECH", {_WN + "n_channels": 64, _WN + "n_layers": 9, _WN + "activation": "gfu"}),
 }
 
 F43 = {"conv_form": "f43"}
@@ -88,6 +101,15 @@ INVARIANT = {"conv_form": "f43", "batch_invariant": True}
 FS, PS, HS = "folded_start", "f43_psplit", "f43_hsplit"
 SP, SPW, SPF = "split_f16", "split_f16_wide", "split_f16_f32h"
 SPLIT = dict(F43, precision="split_f16")
+# the F(4,3) blocks of two column tiles (wn_gate_winograd4q_kernel), pinned: gate_shape_policy honours the pin at every launch
+# size for d <= 16
+TWO = dict(F43, tune={"gate_shape": 4})
+# channel counts of the 3-layer two-tile cases: {C: column tiles}.  36: one pair, its second tile holds 4 channels, nk8 = 5
+# with a partial last slice; 64: one full pair, nk8 even; 68: one pair, then an odd partial tile in the one-tile kernel,
+# nk8 = 9; 132: two pairs, then an odd partial tile; 292: a partial tile (4 channels) inside the last pair, nk8 = 37; 324: an
+# odd partial tile; 352: an odd full tile, nk8 = 44; 356: a partial tile inside the last pair, nk8 = 45
+TWO_TILE_C = {36: 2, 64: 2, 68: 3, 132: 5, 292: 10, 324: 11, 352: 11, 356: 12}
+TWO_TILE_VARIANTS = ("speech", "voice", "gfu", "gsu", "glu", "groups2", "lin20", "causal")
 
 
 def _split(ss):
@@ -178,7 +200,26 @@ CASES = [
     ("c132-f43", "c132", "ragged", F43, {FS, PS}),
     ("c192-f43", "c192", "ragged", F43, {FS, PS}),
     ("c196-f43", "c196", "ragged", F43, {FS, PS}),
+    # ---- the blocks of two column tiles at the stages: channel edges (3 layers) and model variants ----
+    *[(f"c{C}-two-tile", f"c{C}", "ragged", TWO, {FS, "f43"}) for C in TWO_TILE_C],
+    # causal padding under a pinned form folds the start convolution; the gate layers pad 2 d (sh = d in the kernel)
+    *[(f"{gg}-two-tile", gg, "ragged", TWO, {FS, "f43"}) for gg in TWO_TILE_VARIANTS],
+    # a kept start convolution: layer 0 runs the gate kernel at d = 1
+    ("speech-keep-start-two-tile", "speech", "ragged", dict(TWO, keep_start=True), {"f43"}),
+    # cond_up = 5 needs 53 conditioning rows, the two-tile blocks hold 28: wn_gate_winograd4w_select refuses the shape and the
+    # plan falls back to the one-tile 256-row blocks with CR = 56 (layer 0 is not folded: wn_gate0 holds 32 rows)
+    ("lin5-two-tile-refused", "lin5", "ragged", TWO, {"f43"}),
+    # ---- the <-1> instantiations (gfu, gsu, glu) of the other F(4,3) kernels ----
+    ("gfu-f43-256row", "gfu", "ragged", dict(F43, tune={"gate_shape": 1}), {FS, "f43"}),            # 4w<28,-1>
+    ("gfu-f43-hsplit", "gfu", "ragged", dict(F43, tune={"gate_shape": 3}), {FS, HS}),               # 4h<-1>
+    ("lin5-c64-gfu-f43", "lin5-c64-gfu", "ragged", F43, {"f43"}),                                   # 4w<56,-1>
+    # d = 32, 64: 4p<-1,1> under both policies; d = 128, 256: the direct form under the default policy (F(4,3) costs 144
+    # block units against 0.9 x 146.25) and, batch_invariant, 4w<28,-1,1> (130 rows per sub-sequence) and 4w<28,-1,2> (65)
+    ("deep9-c64-gfu-f43", "deep9-c64-gfu", "ragged", F43, {FS, HS, "f43_strided_psplit", "direct"}),
+    ("deep9-c64-gfu-invariant", "deep9-c64-gfu", "ragged", INVARIANT, {FS, "f43", "f43_strided_psplit", "f43_strided"}),
 ]
+# the cases that run the blocks of two column tiles: each is run once more pinned to the one-tile 256-row blocks, for the bits
+TWO_TILE = [f"c{C}-two-tile" for C in TWO_TILE_C] + [f"{gg}-two-tile" for gg in TWO_TILE_VARIANTS] + ["speech-keep-start-two-tile"]
 PLANES_ONLY = {"speech-split", "l3-split", "large-split", "voice-split", "gfu-split", "gsu-split", "groups2-split", "lin20-split",
                "large6-c340-split", "large6-c324-split", "large6-speech-split", "large8-c68-split",
                *(f"c{C}-split" for C in (340, 324, 292, 352, 68, 132, 36))}
@@ -222,6 +263,25 @@ KERNELS = {
     "c64-f43": ({P64}, NJ4), "c128-f43": ({P64}, NJ8), "c356-f43": ({P64}, "tail"), "c512-f43": ({P64}, "tail"),
     "large6-c512-f43": ({"packed128"}, "tail"),
     "c68-f43": ({P64}, NJ8), "c132-f43": ({P64}, NJ12), "c192-f43": ({P64}, NJ12), "c196-f43": ({P64}, NJ20),
+    # the gate's block shape does not enter the res/skip and tail selection: np = ceil((C + 30) / 32) of 11 or 12 takes the
+    # wave-tiled kernel (585 tiles: three column splits), every other one the packed kernel; nj = ceil(8 ceil(C / 8) / 16)
+    "c36-two-tile": ({P64}, NJ4), "c64-two-tile": ({P64}, NJ4), "c68-two-tile": ({P64}, NJ8), "c132-two-tile": ({P64}, NJ12),
+    "c292-two-tile": ({W43}, NJ20), "c324-two-tile": ({W43}, NJ22), "c352-two-tile": ({W43}, NJ22), "c356-two-tile": ({P64}, "tail"),
+    "speech-two-tile": ({W43}, NJ20), "voice-two-tile": ({W43}, NJ22), "gfu-two-tile": ({W43}, NJ20), "gsu-two-tile": ({W43}, NJ20),
+    "glu-two-tile": ({W43}, NJ20), "groups2-two-tile": ({W43}, NJ20), "lin20-two-tile": ({W43}, NJ20), "causal-two-tile": ({W43}, NJ20),
+    "speech-keep-start-two-tile": ({W43}, NJ20), "lin5-two-tile-refused": ({W43}, NJ20),
+    "gfu-f43-256row": ({W43}, NJ20), "gfu-f43-hsplit": ({W43}, NJ20), "lin5-c64-gfu-f43": ({P64}, NJ4),
+    "deep9-c64-gfu-f43": ({P64}, NJ4), "deep9-c64-gfu-invariant": ({P64}, NJ4),
+}
+# {case id: gate channels per F(4,3) block and layer} (kernel_report()["gate_block_channels"]; wn_gate_winograd4w_select: 64 two
+# column tiles, 32 one, 16 half a tile, 0 no F(4,3) block: the folded layer 0, the direct form)
+BLOCK_CHANNELS = {
+    "large-f43": [0, 64, 64, 64, 64],          # 55 row tiles x 16 items x 10 column tiles = 8 800 blocks >= WIDE_FROM_BLOCKS
+    **{f"c{C}-two-tile": [0, 64, 64] for C in TWO_TILE_C},
+    **{f"{gg}-two-tile": [0, 64, 64, 64, 64] for gg in TWO_TILE_VARIANTS},
+    "speech-keep-start-two-tile": [64] * 5, "lin5-two-tile-refused": [32] * 5,
+    "gfu-f43-256row": [0, 32, 32, 32, 32], "gfu-f43-hsplit": [0, 16, 16, 16, 16], "lin5-c64-gfu-f43": [32, 32, 32],
+    "deep9-c64-gfu-f43": [0, 16, 16, 16, 16, 32, 32, 0, 0], "deep9-c64-gfu-invariant": [0] + [32] * 8,
 }
 # the cases whose skip path is not folded (a skip tensor is kept): every layer launches a res/skip convolution, the tail reads
 # the skip tensor
@@ -320,12 +380,57 @@ def test_gpu_split_cases_cover_the_channel_edges_and_launch_sizes():
     assert not PLANES_ONLY & (set(F32_LAYER0) | {"causal-f43-split", "deep12-split"})
 
 
+def test_gpu_two_tile_cases_cover_the_channel_edges_and_variants():
+    """(CPU) The cases pinned to the blocks of two column tiles stand at the channel counts where wn_gate_winograd4q_kernel
+    and its launcher take another branch, and on every model variant that changes a path through the blocks."""
+    two = {case[0]: case for case in CASES if case[3].get("tune", {}).get("gate_shape") == 4}
+    assert set(TWO_TILE) == set(two) - {"lin5-two-tile-refused"} and len(set(TWO_TILE)) == len(TWO_TILE)
+    assert all(64 in BLOCK_CHANNELS[cid] and set(BLOCK_CHANNELS[cid]) <= {0, 64} for cid in TWO_TILE)
+    assert set(BLOCK_CHANNELS["lin5-two-tile-refused"]) == {32} and set(BLOCK_CHANNELS) <= {case[0] for case in CASES}
+    chans = {int(case[1][1:]) for case in two.values() if case[1][1:].isdigit()}
+    tiles, nk8 = (lambda C: (C + 31) // 32), (lambda C: (C + 7) // 8)
+    assert chans == set(TWO_TILE_C) and all(tiles(C) == TWO_TILE_C[C] for C in chans)
+    # a partial tile INSIDE a pair (an even tile count with C % 32 != 0): the zero page of issue_cond, the bias guard and ch_ok
+    assert {C for C in chans if tiles(C) % 2 == 0 and C % 32} >= {36, 292, 356}
+    # one pair only (q.n_tiles == 1), with and without an odd tile behind it; several pairs
+    assert {C for C in chans if tiles(C) // 2 == 1} >= {36, 64, 68} and {C for C in chans if tiles(C) // 2 > 1} >= {132, 292}
+    # the odd last tile in the one-tile kernel (ConvArgs::tile0), partial and full
+    assert {C for C in chans if tiles(C) % 2 and C % 32} >= {68, 132, 324} and {C for C in chans if tiles(C) % 2 and C % 32 == 0} >= {352}
+    # the K loop: the conditioning rows land in stage (nk8 - 1) & 1, so both parities; the smallest loop a model with two
+    # column tiles has (C = 36: nk8 = 5, against the two stages of the prologue); a partial last slice (C % 8 == 4)
+    assert {C for C in chans if nk8(C) % 2 == 0} >= {64, 352} and {C for C in chans if nk8(C) % 2} >= {36, 68, 292, 356}
+    assert min(nk8(C) for C in chans) == nk8(36) == 5 and all(nk8(C) < 5 or tiles(C) < 2 for C in range(4, 36, 4))
+    assert {C for C in chans if C % 8 == 4} >= {36, 68, 292, 356}
+    # the variants: every gate activation (<0> and <-1>), an odd tile count on a 5-layer model, channel groups, both
+    # conditioning up-samplings the shape takes, causal padding, a kept start convolution
+    acts = {GEOMETRIES[case[1]][1].get(_WN + "activation", "gtu") for case in two.values()}
+    assert acts == {"gtu", "gfu", "gsu", "glu"}
+    ups = {GEOMETRIES[case[1]][1].get(_WN + "cond_lin_upsampling", 10) for cid, case in two.items() if cid in TWO_TILE}
+    assert ups == {10, 20} and GEOMETRIES["lin5"][1][_WN + "cond_lin_upsampling"] == 5
+    assert {"voice-two-tile", "groups2-two-tile", "causal-two-tile", "speech-keep-start-two-tile"} <= set(TWO_TILE)
+    assert two["speech-keep-start-two-tile"][3].get("keep_start") and GEOMETRIES["causal"][1][_WN + "padding"] == "CAUSAL"
+    # every two-tile case runs on the ragged batch: the oracle's stages are shared with the cases of the same geometry
+    assert all(case[2] == "ragged" for case in two.values())
+    # the large launch takes the shape by the size rule (gate_shape_policy: WIDE_FROM_BLOCKS = 5040)
+    lengths = LENGTHS["large"][0]
+    assert ((max(lengths) * 20 + 255) // 256) * len(lengths) * tiles(320) == 8800 >= 5040 and BLOCK_CHANNELS["large-f43"][1:] == [64] * 4
+
+
 @pytest.fixture(scope="module")
 def torch():
     import torch as _torch
     if not _torch.cuda.is_available():
         pytest.skip("needs a GPU")
     return _torch
+
+
+@pytest.fixture(scope="module")
+def planned(tmp_path_factory):
+    """{case id: plan rows} of tests/tools/wn_plan_stage_cases.cpp for every stage case (built and run once)."""
+    import sys
+    import wn_stage_plan
+    lines, _ = wn_stage_plan.stage_case_lines(sys.modules[__name__])
+    return wn_stage_plan.run(wn_stage_plan.build(tmp_path_factory.mktemp("wn_stage_plan")), lines)
 
 
 def _inputs(lengths, seed=907):
@@ -348,8 +453,8 @@ def _reference(geom, lkey, cfg, raw, wt, mel, noise, pulse):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cid,geom,lkey,kwargs,kernels", CASES, ids=[case[0] for case in CASES])
-def test_wavenet_stages_match_the_oracle(torch, cid, geom, lkey, kwargs, kernels):
-    from mbexwn_vocoder_amd.engine import MBExWNEngine
+def test_wavenet_stages_match_the_oracle(torch, planned, cid, geom, lkey, kwargs, kernels):
+    from mbexwn_vocoder_amd.engine import GATE_KERNEL_NAMES, MBExWNEngine
     voice, over = GEOMETRIES[geom]
     cfg, raw, wt = build_case(voice, over)
     lengths, items = LENGTHS[lkey]
@@ -364,6 +469,13 @@ def test_wavenet_stages_match_the_oracle(torch, cid, geom, lkey, kwargs, kernels
     info = eng.conv_form_info()
     ran = info["gate_kernels"]
     assert len(ran) == eng.dims.wn_layers and set(ran) == kernels, f"{cid}: gate kernels {ran}, expected {sorted(kernels)}"
+    if cid in BLOCK_CHANNELS:
+        assert info["gate_block_channels"] == BLOCK_CHANNELS[cid], f"{cid}: gate block channels {info['gate_block_channels']}"
+    # the forward ran what the library plans for this size (test_gpu_plan.py), and what the stand-alone program on wn_plan.h
+    # prints for the case: the instantiations of test_wn_stage_plan_host.py are those of this run
+    assert eng.plan(B, T) == eng.kernel_report(), f"{cid}: plan {eng.plan(B, T)}, report {eng.kernel_report()}"
+    assert [GATE_KERNEL_NAMES[row[0]] for row in planned[cid]] == ran and [row[2] for row in planned[cid]] == info["gate_block_channels"], \
+        f"{cid}: the host program plans {planned[cid]}, the forward ran {ran} {info['gate_block_channels']}"
     resskip, tail = KERNELS[cid]
     ran_rs, ran_tail = info["resskip_kernels"], info["tail_kernel"]
     assert info["fold_skip"] == (cid not in UNFOLDED), f"{cid}: fold_skip {info['fold_skip']}"
@@ -402,16 +514,55 @@ def test_wavenet_stages_match_the_oracle(torch, cid, geom, lkey, kwargs, kernels
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("form", ["f43", "direct", "split_f16", "split_f16-c340", "split_f16-c340-wide"])
+@pytest.mark.parametrize("cid", TWO_TILE)
+def test_two_tile_blocks_give_the_bits_of_the_one_tile_blocks_at_the_stages(torch, cid):
+    """wn_gate_winograd4q_kernel's contract -- every accumulator chain, the output combination and the epilogue are those of the
+    other shapes -- held where it is stated: "wn_out" and "wn_hidden" of every two-tile case are bit-identical, over every
+    item's valid rows, to those of the same model pinned to the 256-row blocks of one column tile."""
+    from mbexwn_vocoder_amd.engine import MBExWNEngine
+    _, geom, lkey, kwargs, _ = next(case for case in CASES if case[0] == cid)
+    cfg, raw, wt = build_case(*GEOMETRIES[geom])
+    lengths, _ = LENGTHS[lkey]
+    B, T = len(lengths), max(lengths)
+    mel, noise = _inputs(lengths)
+    nf = torch.as_tensor(lengths, dtype=torch.int32).cuda()
+    got = {}
+    for shape in (4, 1):
+        eng = MBExWNEngine(cfg, raw, wt, **dict(kwargs, tune={"gate_shape": shape}))
+        eng.forward(torch.as_tensor(mel).cuda(), n_frames=nf, noise=torch.as_tensor(noise).cuda())
+        rep = eng.kernel_report()
+        want = [cc // 2 if shape == 1 else cc for cc in BLOCK_CHANNELS[cid]]
+        assert rep["gate_block_channels"] == want, f"{cid}: gate_shape {shape} ran {rep['gate_kernels']} {rep['gate_block_channels']}"
+        got[shape] = engine_stages(eng, ["wn_out", "wn_hidden"], B, T)
+        eng.close()
+    for name in ("wn_out", "wn_hidden"):
+        for ii, ll in enumerate(lengths):
+            a, b = got[4][name][ii, :ll * 20], got[1][name][ii, :ll * 20]
+            assert np.all(np.isfinite(b)), f"{cid}: {name} of item {ii}"
+            bad = np.argwhere(a.view(np.uint64) != b.view(np.uint64))      # (float32 values widened exactly)
+            assert bad.size == 0, f"{cid}: {name} of item {ii} ({ll} frames) differs between the blocks of two column tiles and of " \
+                                  f"one: {len(bad)} values, first at row {bad[0][0]} channel {bad[0][1]}: " \
+                                  f"{a[tuple(bad[0])]!r} against {b[tuple(bad[0])]!r}"
+
+
+# forms of the padding test on the blocks of two column tiles: {form: geometry}.  C = 292: the clamped conditioning and halo
+# sources sit beside a tile whose missing channels read the zero page; C = 68: the pair launch and the one-tile launch write the
+# same rows of `out`
+TWO_TILE_PADDING = {"f43-two-tile": "speech", "f43-two-tile-c292": "c292", "f43-two-tile-c68": "c68"}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["f43", "direct", "split_f16", "split_f16-c340", "split_f16-c340-wide", *TWO_TILE_PADDING])
 def test_padding_frames_are_never_read(torch, form):
     """The same ragged batch three times, its padding frames of mel and noise at 0, 1e30 and NaN: the audio and every WaveNet
     stage of the items' valid rows are bit-identical across the three, and the audio behind each item's end is exactly 0.
     split_f16-c340: a partial last column tile, K step and plane chunk under the planes kernel and, with the shortest batch that
     reaches it (WIDE8), under wn_gate_f16w_kernel, whose halo rows and missing twelfth column tile are clamped sources: a
-    clamped source that is not masked shows as the neighbour's NaN."""
+    clamped source that is not masked shows as the neighbour's NaN.  f43-two-tile*: the F(4,3) blocks of two column tiles
+    (TWO_TILE_PADDING)."""
     from mbexwn_vocoder_amd.engine import MBExWNEngine
-    cfg, raw, wt = build_case(*GEOMETRIES["c340" if "c340" in form else "speech"])
-    kwargs = {"conv_form": "f43", "precision": "split_f16"} if form.startswith("split_f16") else {"conv_form": form}
+    cfg, raw, wt = build_case(*GEOMETRIES[TWO_TILE_PADDING[form] if form in TWO_TILE_PADDING else "c340" if "c340" in form else "speech"])
+    kwargs = {"conv_form": "f43", "precision": "split_f16"} if form.startswith("split_f16") else TWO if form in TWO_TILE_PADDING else {"conv_form": form}
     eng = MBExWNEngine(cfg, raw, wt, **kwargs)
     lengths = WIDE8 if form.endswith("-wide") else RAGGED
     B, T = len(lengths), max(lengths)
@@ -430,6 +581,9 @@ def test_padding_frames_are_never_read(torch, form):
         if form.startswith("split_f16"):
             ran = eng.conv_form_info()["gate_kernels"]
             assert set(ran[1:]) == {SPW if form.endswith("-wide") else SP}, f"{form}: gate kernels {ran}"
+        if form in TWO_TILE_PADDING:
+            rep = eng.kernel_report()
+            assert rep["gate_block_channels"] == [0] + [64] * (eng.dims.wn_layers - 1), f"{form}: {rep}"
     eng.close()
     base_audio, base_st = runs[0.0]
     for fill in (1e30, np.nan):

@@ -235,7 +235,8 @@ def resampled_length(n, rate, target):
     return -(-int(n) * (int(target) // gg) // (int(rate) // gg))
 
 
-def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None, time_maps=None, rows_per_frame=1):
+def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None, time_maps=None, rows_per_frame=1,
+                  f0_out=None, f0_params=None):
     """Sounds -> ``.mell`` dictionaries (reference bin/generate_mel.py:54-64 for a list of files): ``sounds`` is a list of 1-D
     float32 arrays, ``rates`` their sample rates.  A sound that is not at the model rate goes through the reference's resampler
     (resample.py); one already at it skips that step.  Needs the ``preprocess_config`` alone: no engine, no weights.
@@ -250,9 +251,16 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     on ``timemap.centres`` of its length at the model rate (``resampled_length``, which the host knows), K of them, and the
     ``.mell`` has K columns.  A micro-batch with such an item goes through ``compute_log_mel_device_at`` (on the host:
     ``compute_log_mel_at``), its other items on their regular centres, which gives them the regular analysis's bits; a
-    call without maps makes the launches it made before there were any.  ``rows_per_frame``: ``timemap.centres``' limit."""
+    call without maps makes the launches it made before there were any.  ``rows_per_frame``: ``timemap.centres``' limit.
+
+    ``f0_out``: a list, or None.  Given a list, item i's ``(f0, periodicity)`` -- float32 arrays with one value per column
+    of its ``.mell``, f0 in Hz and 0 where unvoiced -- is appended to it, in the order of ``sounds``: the F0 tracker
+    (f0track.py) on the item's model-rate samples at the centres of its mel frames, warped or regular
+    (on the device ``mbxp_track_f0`` behind the analysis of the micro-batch, else ``f0track.track_f0_host``: the same
+    bits).  ``f0_params``: ``f0track.params`` of the model rate (default: its defaults).  None makes today's launches;
+    the dictionaries have the same keys either way."""
     import time
-    from . import resample, timemap
+    from . import f0track, resample, timemap
     cfg = preprocess_config
     target, hop = int(cfg["sample_rate"]), int(cfg["hop_size"])
     win_len = int(cfg.get("win_size", cfg["fft_size"]))
@@ -264,6 +272,11 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
         if ss.ndim != 1 or ss.size == 0:
             raise ValueError(f"generate_mels: sound {ii} must be a non-empty 1-D array, got shape {ss.shape}")
     out = [None] * len(sounds)
+    tracked = [None] * len(sounds)
+    if f0_out is not None:
+        f0_params = f0track.check_params(dict(f0_params)) if f0_params is not None else f0track.params(target)
+        if int(f0_params["sample_rate"]) != target:
+            raise ValueError(f"generate_mels: f0_params are for {f0_params['sample_rate']} Hz, the model rate is {target}")
     maps = timemap.per_item(list(time_maps) if time_maps is not None else None, len(sounds), "generate_mels: time_maps")
     # every map is checked, and its centres are made, before anything runs
     warped = {ii: timemap.centres(resampled_length(sounds[ii].size, rates[ii], target), hop, target, mm, rows_per_frame)
@@ -281,6 +294,13 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
             _add(stats, "resample", t1 - t0)
             _add(stats, "analysis", time.perf_counter() - t1)
             out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[0].T))
+            if f0_out is not None:
+                t2 = time.perf_counter()
+                tracked[ii] = f0track.track_f0_host(ss, warped[ii] if ii in warped else timemap.centres(ss.size, hop, target, None),
+                                                    f0_params)
+                _add(stats, "f0", time.perf_counter() - t2)
+        if f0_out is not None:
+            f0_out.extend(tracked)
         return out
     import torch
     if not torch.cuda.is_available():
@@ -297,7 +317,7 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
             host = np.zeros((len(group), max(lengths)), dtype=np.float32)
             for bb, ii in enumerate(group):
                 host[bb, :lengths[bb]] = sounds[ii]
-            marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if stats is not None else None
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if stats is not None else None
             if marks:
                 marks[0].record()
             snd = torch.as_tensor(host).to(dev)
@@ -312,26 +332,41 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
                 snd = torch.nn.functional.pad(snd, (0, win_len // 2 + 1 - snd.shape[1]))
             if marks:
                 marks[2].record()
-            if any(ii in warped for ii in group):
+            if any(ii in warped for ii in group) or f0_out is not None:
                 cents = [warped[ii] if ii in warped else timemap.centres(nn, hop, target, None) for ii, nn in zip(group, lengths)]
                 table = np.zeros((len(group), max(cc.size for cc in cents)), dtype=np.int64)
                 for bb, cc in enumerate(cents):
                     table[bb, :cc.size] = cc
                 counts = [int(cc.size) for cc in cents]
-                mel_dev, _ = compute_log_mel_device_at(snd, n_dev, torch.as_tensor(table).to(dev),
-                                                       torch.as_tensor(np.asarray(counts, dtype=np.int32)).to(dev), cfg)
+                table_dev = torch.as_tensor(table).to(dev)
+                counts_dev = torch.as_tensor(np.asarray(counts, dtype=np.int32)).to(dev)
+            if any(ii in warped for ii in group):
+                mel_dev, _ = compute_log_mel_device_at(snd, n_dev, table_dev, counts_dev, cfg)
             else:
                 counts = [nn // hop + 1 for nn in lengths]
                 mel_dev, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
             if marks:
                 marks[3].record()
-                marks[3].synchronize()
+            if f0_out is not None:                              # the regular centres are t * hop: the analysis's own frames
+                f0_dev, per_dev = f0track.track_f0_device(snd, n_dev, table_dev, counts_dev, f0_params)
+                if marks:
+                    marks[4].record()
+            if marks:
+                marks[4 if f0_out is not None else 3].synchronize()
                 t0 = time.perf_counter()
             mel = mel_dev.cpu().numpy()
+            if f0_out is not None:
+                f0_host, per_host = f0_dev.cpu().numpy(), per_dev.cpu().numpy()
+                for bb, ii in enumerate(group):
+                    tracked[ii] = (f0_host[bb, :counts[bb]].copy(), per_host[bb, :counts[bb]].copy())
             if marks:
                 _add(stats, "copy_back", time.perf_counter() - t0)
+                if f0_out is not None:
+                    _add(stats, "f0", marks[3].elapsed_time(marks[4]) * 1e-3)
                 for key, first in (("upload", 0), ("resample", 1), ("analysis", 2)):
                     _add(stats, key, marks[first].elapsed_time(marks[first + 1]) * 1e-3)
             for bb, ii in enumerate(group):
                 out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[bb, :counts[bb]].T))
+    if f0_out is not None:
+        f0_out.extend(tracked)
     return out

@@ -149,8 +149,28 @@ def stage_factors(rows, device=None):
     return torch.as_tensor(scale, device=device)
 
 
+def check_f0s(f0s, lengths):
+    """The per-item F0 contours of a job, checked before anything runs: None, or a list with, per item, None or a float32
+    array (T_i,) of positive finite Hz.  A list of Nones counts as None."""
+    if f0s is None:
+        return None
+    f0s = list(f0s)
+    if len(f0s) != len(lengths):
+        raise ValueError(f"f0s must hold one entry per item ({len(lengths)}), got {len(f0s)}")
+    out = []
+    for ii, (ff, tt) in enumerate(zip(f0s, lengths)):
+        if ff is not None:
+            ff = np.ascontiguousarray(ff, dtype=np.float32)
+            if ff.shape != (tt,):
+                raise ValueError(f"f0s[{ii}] must hold one value per mel frame ({tt}), got shape {ff.shape}")
+            if not (np.all(np.isfinite(ff)) and np.all(ff > 0)):
+                raise ValueError(f"f0s[{ii}] must be finite and positive (f0track.fill_unvoiced fills the unvoiced frames)")
+        out.append(ff)
+    return None if all(ff is None for ff in out) else out
+
+
 def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False, host_audio=True,
-                      flac_compression="verbatim", out_rate=None, transpositions=None, formants=None):
+                      flac_compression="verbatim", out_rate=None, transpositions=None, formants=None, f0s=None):
     """Generator over the padded micro-batches of ``mels`` (list of (T_i, C) float32 arrays) on ``engine``: each is staged
     and run (engine.forward with the items' lengths), its FLAC frames encoded (``flac``) and / or its audio copied to pinned
     host memory (``host_audio``), all enqueued on the current stream; the SynthBatch is yielded without waiting, so that a
@@ -165,7 +185,12 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
     on the device by ``engine.keyed_noise``, a function of the seed, the item's key and the step alone.  ``transpositions``:
     per item None or (T_i,) factors, one per mel frame -- the ``f0_scale`` rows of the forward; None: the forward of today.
     ``formants``: the same for the formant shift (the ``formant`` rows of the forward).  A micro-batch
-    whose factors are all exactly 1 runs the forward without them: a factor of 1 copies the row, so the bits are the same."""
+    whose factors are all exactly 1 runs the forward without them: a factor of 1 copies the row, so the bits are the same.
+    ``f0s``: per item None or (T_i,) Hz, one value per mel frame, positive and finite (an F0 tracker's output through
+    ``f0track.fill_unvoiced``): the ``f0_frames`` rows of the forward, with ``f0_item_mask`` 0 for the None items, which keep
+    the F0-net; every entry is checked before anything runs, and a job whose entries are all None runs the forward
+    without them."""
+    f0s = check_f0s(f0s, [int(mm.shape[0]) for mm in mels])
     import torch
     from .mel_inverter import KeyedNoise
     dims = engine.dims
@@ -194,6 +219,11 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
                     for ii in group]
             if any(np.any(rr != 1.0) for rr in rows):
                 control["formant"] = stage_factors(rows, engine.device)
+        if f0s is not None and any(f0s[ii] is not None for ii in group):
+            control["f0_frames"] = stage_factors([np.ones(lengths[ii], dtype=np.float32) if f0s[ii] is None else f0s[ii]
+                                                  for ii in group], engine.device)
+            control["f0_item_mask"] = torch.as_tensor(np.asarray([f0s[ii] is not None for ii in group], dtype=np.int32),
+                                                      device=engine.device)
         events = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         events[0].record(stream)
         if keyed:                                           # the draw is part of the step: inside the device time
@@ -271,8 +301,20 @@ def _file_writer(inv, files, mine, scaled, output_dir, fmt, device_flac, file_ra
     return write
 
 
+def f0_path(name, directory):
+    """``directory/NAME.f0`` of a sound or ``.mell`` file ``name``: where the tools write and look for its F0 contour."""
+    return os.path.join(directory or "", os.path.splitext(os.path.basename(name))[0] + ".f0")
+
+
+def load_contour(name, directory, frames):
+    """The contour ``resynth_mel.py --f0-dir`` gives the file ``name``: ``directory/NAME.f0`` (f0track.read_f0; one row per
+    mel frame, another count is refused) through ``f0track.fill_unvoiced`` -- None when no frame is voiced: the F0-net."""
+    from .f0track import fill_unvoiced, read_f0
+    return fill_unvoiced(read_f0(f0_path(name, directory), n_frames=frames)[1])
+
+
 def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threads=2, verbose=False, quiet=False,
-            flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant=None):
+            flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant=None, f0_dir=None):
     """The batched CLI on this process's GPU: ``files[mine]`` -> syn_<basename>.<fmt> in ``output_dir``.
 
     ``frames``: the frame count after scale_mel of EVERY file of the job, in file order (the noise replay needs all of
@@ -284,7 +326,9 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
     is about what is written.  ``noise_seed``: the noise channel takes the keyed noise of that seed instead of the replayed
     draws, the key of a file being ``noise.item_key`` of its basename -- a file's audio then does not depend on the other
     files; ``transposition``: a factor on every mel frame of every file (``f0_scale`` rows); ``formant``: a formant-shift
-    factor on every mel frame of every file (``formant`` rows).  All None: today's job."""
+    factor on every mel frame of every file (``formant`` rows).  ``f0_dir``: every file takes the contour of
+    ``f0_dir/NAME.f0`` (:func:`load_contour`; a missing file or a wrong row count fails before anything runs) in place of the
+    F0-net's.  All None: today's job."""
     t_start = time.perf_counter()
     mine = list(range(len(files))) if mine is None else list(mine)
     clock, log_lock = _Clock(), threading.Lock()
@@ -328,11 +372,12 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
         noises = KeyedNoise(noise_seed, [item_key(files[ii]) for ii in mine])
     rows = None if transposition is None else [np.full(int(mm.shape[0]), transposition, dtype=np.float32) for mm in mels]
     shifts = None if formant is None else [np.full(int(mm.shape[0]), formant, dtype=np.float32) for mm in mels]
+    contours = None if f0_dir is None else [load_contour(files[ii], f0_dir, int(scaled[ii].shape[1])) for ii in mine]
     with ThreadPoolExecutor(max_workers=max(1, threads)) as writers:
         pending = [writers.submit(write, sb) for sb in run_micro_batches(inv.model, mels, noises, max(1, batch),
                                                                          flac=device_flac, host_audio=verbose or not device_flac,
                                                                          flac_compression=flac_compression, out_rate=out_rate,
-                                                                         transpositions=rows, formants=shifts)]
+                                                                         transpositions=rows, formants=shifts, f0s=contours)]
         for fu in pending:
             fu.result()
     if verbose:
@@ -404,7 +449,8 @@ def read_sound(path):
 
 
 def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
-                  quiet=False, flac_compression="verbatim", out_rate=None, stretches=None, formants=None):
+                  quiet=False, flac_compression="verbatim", out_rate=None, stretches=None, formants=None, f0_source="net",
+                  f0_params=None, write_f0=False, timings=None):
     """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
     ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
 
@@ -422,8 +468,16 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     file whose stretched length exceeds the engine's limit is reported and skipped like the unreadable ones.
 
     ``formants``: a formant-shift factor per file, None = 1 for all: ``formants[i]`` on every frame of
-    file i, pitch and duration kept.  With every factor 1 the job makes the launches and writes the bytes it does without."""
-    from . import timemap
+    file i, pitch and duration kept.  With every factor 1 the job makes the launches and writes the bytes it does without.
+
+    ``f0_source``: "net", or "audio" -- the F0 tracker (f0track.py; ``f0_params``: keywords of
+    ``f0track.params``) runs behind the analysis of every micro-batch, on the frames of the mel, and a file's filled contour
+    replaces the F0-net's; ``factors`` multiply on top; a file without a voiced frame keeps the F0-net.  ``write_f0``:
+    the tracked contour (0 = unvoiced) is written as NAME.f0 into ``output_dir``, with either source.  "net" without
+    ``write_f0``: the launches and the bytes of before.  ``timings``: a dict that receives the seconds per stage the
+    verbose line reports (upload, resample, analysis, f0, copy_back from ``generate_mels``; read, scale, device, copy, write
+    from the pools and the micro-batches' events; wall)."""
+    from . import f0track, timemap
     from .analysis import generate_mels, resampled_length
     from .mel_inverter import KeyedNoise
     from .noise import item_key
@@ -467,12 +521,26 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
                 mine.remove(ii)
         for name, why in skipped:
             log([f"transform_audio::error:: skipped {name}: {why}"])
+        if f0_source not in ("net", "audio"):
+            raise ValueError(f"run_audio_job: f0_source must be 'net' or 'audio', got {f0_source!r}")
+        tracked = [] if f0_source == "audio" or write_f0 else None
         stats = {}
         dicts = generate_mels([loaded[ii][0] for ii in mine], [loaded[ii][1] for ii in mine], inv.preprocess_config,
                               on_device=True, batch=max(1, batch), stats=stats,
                               time_maps=None if all(maps[ii] is None for ii in mine) else [maps[ii] for ii in mine],
-                              rows_per_frame=inv.model.dims.steps_per_frame) if mine else []
+                              rows_per_frame=inv.model.dims.steps_per_frame, f0_out=tracked,
+                              f0_params=None if tracked is None else f0track.params(int(round(inv.srate)), **(f0_params or {}))
+                              ) if mine else []
         scaled = dict(zip(mine, pool.map(scale, dicts)))
+        contours = None
+        if tracked is not None:
+            tracked = dict(zip(mine, tracked))
+            if write_f0:
+                for ii in mine:
+                    f0track.write_f0(f0_path(files[ii], output_dir), f0track.frame_times(tracked[ii][0].size, inv.hop_size, inv.srate),
+                                     *tracked[ii])
+            if f0_source == "audio":
+                contours = {ii: f0track.fill_unvoiced(tracked[ii][0]) for ii in mine}
     dims = inv.model.dims
     device_flac = fmt.lower() == "flac" and not have_soundfile()
     # the files grouped by the rate they are written at (one group unless out_rate is "input")
@@ -492,9 +560,13 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
             pending += [writers.submit(write, sb) for sb in run_micro_batches(
                 inv.model, [scaled[ii][0] for ii in sub], noises, max(1, batch), flac=device_flac,
                 host_audio=verbose or not device_flac, flac_compression=flac_compression, out_rate=rate, transpositions=rows,
-                formants=shifts)]
+                formants=shifts, f0s=None if contours is None else [contours[ii] for ii in sub])]
         for fu in pending:
             fu.result()
+    if timings is not None:
+        timings.update(stats, read=clock.seconds.get("read", 0.0), scale=clock.seconds.get("scale", 0.0),
+                       device=clock.seconds.get("device_ms", 0.0) / 1e3, copy=clock.seconds.get("copy_ms", 0.0) / 1e3,
+                       write=clock.seconds.get("write", 0.0), wall=time.perf_counter() - t_start)
     if verbose:
         wall = time.perf_counter() - t_start
         sec = clock.seconds
@@ -503,7 +575,8 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
         stretched = "" if all(maps[ii] is None for ii in mine) else f" (time-stretched from {in_s:.1f} s of input)"
         print(f"transform_audio: {len(mine)} files, {audio_s:.1f} s of audio{stretched} in {wall:.2f} s wall ({audio_s / max(wall, 1e-9):.1f} "
               f"x real time); read {sec.get('read', 0.0):.2f} s, upload {stats.get('upload', 0.0):.3f} s, resample "
-              f"{stats.get('resample', 0.0):.3f} s, analysis {stats.get('analysis', 0.0):.3f} s, mel copy-back "
+              f"{stats.get('resample', 0.0):.3f} s, analysis {stats.get('analysis', 0.0):.3f} s, "
+              + (f"f0 tracker {stats.get('f0', 0.0):.3f} s, " if tracked is not None else "") + "mel copy-back "
               f"{stats.get('copy_back', 0.0):.3f} s, scale_mel {sec.get('scale', 0.0):.2f} s, noise+forward "
               f"{sec.get('device_ms', 0.0) / 1e3:.3f} s, resample+encode+D2H {sec.get('copy_ms', 0.0) / 1e3:.3f} s, MD5+write "
               f"{sec.get('write', 0.0):.2f} s (pool stages summed over {max(1, threads)} threads each)", file=sys.stderr)

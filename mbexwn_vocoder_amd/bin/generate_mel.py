@@ -12,6 +12,8 @@ Deviations (documented in INTEGRATION.md):
   * additionally ``--time-stretch F``: the frames lie at the positions of a sound F times as long (timemap.py, DESIGN.md
     section 6f), the file has the reference's dictionary with K columns, and resynth_mel.py synthesises it F times as long at
     the same pitch; with ``--host`` too
+  * additionally ``--write-f0`` (``--f0-min``, ``--f0-max``): the F0 tracker (f0track.py) runs on the
+    frames of the mel and NAME.f0 is written next to NAME.mell, for ``resynth_mel.py --f0-dir``; with ``--host`` too, same bits
   * without ``--host`` and without a GPU the script fails loudly; there is no ``--gpus``
 """
 import os
@@ -24,7 +26,9 @@ if os.path.exists(test_path):
     sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
 
 from mbexwn_vocoder_amd import get_config_file, list_models  # noqa: E402
+from mbexwn_vocoder_amd import f0track  # noqa: E402
 from mbexwn_vocoder_amd.analysis import generate_mels  # noqa: E402
+from mbexwn_vocoder_amd.batched import f0_path  # noqa: E402
 from mbexwn_vocoder_amd.audioio import read_audio  # noqa: E402
 from mbexwn_vocoder_amd.config import ModelDims, read_config  # noqa: E402
 from mbexwn_vocoder_amd.fileio import save_var  # noqa: E402
@@ -32,7 +36,7 @@ from mbexwn_vocoder_amd.timemap import check_factor  # noqa: E402
 
 
 def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2, host=False, verbose=False, quiet=False,
-         time_stretch=1.0):
+         time_stretch=1.0, write_f0=False, f0_min=55.0, f0_max=1000.0):
     config_file = get_config_file(model_id_or_path=model_id)
     config = read_config(config_file=config_file)
     preprocess_config = config['preprocess_config']
@@ -40,6 +44,7 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
         time_stretch = check_factor(time_stretch, "--time-stretch")
         # a stretched file is made for resynth_mel.py: held to the limit of the model's engine (sub-band rows per frame)
         rows_per_frame = ModelDims(config).steps_per_frame if time_stretch != 1.0 else 1
+        f0_params = f0track.params(int(preprocess_config["sample_rate"]), f0_min=f0_min, f0_max=f0_max) if write_f0 else None
     except ValueError as err:
         print(f"generate_mel::error:: {err}", file=sys.stderr)
         sys.exit(1)
@@ -70,6 +75,11 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
         save_var(path, data)
         return time.perf_counter() - t0
 
+    def write_contour(path, times, f0, periodicity):
+        t0 = time.perf_counter()
+        f0track.write_f0(path, times, f0, periodicity)
+        return time.perf_counter() - t0
+
     t_start = time.perf_counter()
     samples = 0
     windows = [input_audio_files[ii:ii + batch] for ii in range(0, len(input_audio_files), batch)]
@@ -85,9 +95,11 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
                 for ff in files:
                     print(f"process {ff}", file=sys.stderr)
             try:
+                tracked = [] if write_f0 else None
                 mells = generate_mels([ll[0] for ll in loaded], [ll[1] for ll in loaded], preprocess_config, on_device=not host,
                                       batch=batch, stats=stats, rows_per_frame=rows_per_frame,
-                                      time_maps=None if time_stretch == 1.0 else [time_stretch] * len(loaded))
+                                      time_maps=None if time_stretch == 1.0 else [time_stretch] * len(loaded),
+                                      f0_out=tracked, f0_params=f0_params)
             except ValueError as err:
                 print(f"generate_mel::error:: {err}", file=sys.stderr)
                 sys.exit(1)
@@ -98,6 +110,9 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
                     print(f"    {ll[0].size} samples at {ll[1]} Hz -> {dd['mell'].shape[1]} frames, save under {outfile}",
                           file=sys.stderr)
                 written.append(writers.submit(write, outfile, dd))
+            for ff, contour in zip(files, tracked or []):
+                times = f0track.frame_times(contour[0].size, preprocess_config["hop_size"], preprocess_config["sample_rate"])
+                written.append(writers.submit(write_contour, f0_path(ff, output_dir), times, *contour))
         seconds["write"] = sum(fu.result() for fu in written)
     if verbose:
         wall = time.perf_counter() - t_start
@@ -125,6 +140,13 @@ if __name__ == "__main__":
     parser.add_argument("-nt", "--num_threads", default=2, type=int, help="reader and writer threads (Def: %(default)s)")
     parser.add_argument("--time-stretch", dest="time_stretch", default=1.0, type=float, metavar="F",
                         help="place the frames for a sound F times as long at the same pitch (Def: %(default)s)")
+    parser.add_argument("--write-f0", dest="write_f0", action="store_true",
+                        help="also track the pitch of every file from its samples and write NAME.f0 next to NAME.mell: text "
+                             "rows `time_s f0_hz periodicity`, one per mel frame, 0 = unvoiced; resynth_mel.py --f0-dir reads it")
+    parser.add_argument("--f0-min", dest="f0_min", default=55.0, type=float, metavar="HZ",
+                        help="lowest pitch the F0 tracker looks for (Def: %(default)s)")
+    parser.add_argument("--f0-max", dest="f0_max", default=1000.0, type=float, metavar="HZ",
+                        help="highest pitch the F0 tracker looks for (Def: %(default)s)")
     parser.add_argument("--host", action="store_true", help="numpy analysis and host resampler; needs no GPU")
     parser.add_argument("-v", "--verbose", action="store_true", help="display verbose progress info")
     parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")

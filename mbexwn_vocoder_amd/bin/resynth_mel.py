@@ -13,6 +13,8 @@ Deviations (documented in INTEGRATION.md):
   * additionally ``--noise-seed S`` (keyed noise, include/mbexwn_noise.h) and ``--transposition F``
   * additionally ``--out-rate R``: the files are written at R Hz, resampled on the GPU from the model rate with the
     reference's resampler (mbexwn_vocoder_amd/resample.py)
+  * additionally ``--f0-dir DIR``: every file takes its pitch from ``DIR/NAME.f0`` (``generate_mel.py --write-f0``; text rows
+    ``time_s f0_hz periodicity``, one per mel frame, 0 = unvoiced and filled from its neighbours) instead of the model's own F0
 """
 import json
 import os
@@ -32,7 +34,7 @@ from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
          num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None,
-         flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant_shift=None):
+         flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant_shift=None, f0_dir=None):
     format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
     if flac_compression != "verbatim" and rank is None and not quiet:
         from mbexwn_vocoder_amd.batched import have_soundfile
@@ -49,6 +51,7 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         argv += ["--noise-seed", str(noise_seed)] if noise_seed is not None else []
         argv += ["--transposition", repr(transposition)] if transposition is not None else []
         argv += ["--formant-shift", repr(formant_shift)] if formant_shift is not None else []
+        argv += ["--f0-dir", f0_dir] if f0_dir is not None else []
         argv += [flag for flag, on in (("-g", use_gpu), ("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant))
                  if on]
         sys.exit(run_ranks(os.path.abspath(__file__), argv, model_id, input_mell_files, gpus, threads=num_threads,
@@ -94,7 +97,7 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         run_job(MelInv, input_mell_files, output_dir, format, frames=plan["frames"] if plan else None,
                 mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose, quiet=quiet,
                 flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed, transposition=transposition,
-                formant=formant_shift)
+                formant=formant_shift, f0_dir=f0_dir)
         return
     out_rate = MelInv._output_rate(out_rate)
 
@@ -116,6 +119,11 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
             control.update(transposition=np.full(log_mel_spectrogram.shape[1], transposition, dtype=np.float32))
         if formant_shift is not None and formant_shift != 1.0:       # (a factor of 1: the call without it, as run_job makes it)
             control.update(formant=formant_shift)
+        if f0_dir is not None:                       # the file's own contour in place of the F0-net's; none voiced: the F0-net
+            from mbexwn_vocoder_amd.batched import load_contour
+            contour = load_contour(mell_file, f0_dir, log_mel_spectrogram.shape[1])
+            if contour is not None:
+                control.update(f0=contour)
         syn_audio = MelInv.synth_from_mel(log_mel_spectrogram, **control)
         end_time = time.time()
 
@@ -206,6 +214,10 @@ if __name__ == "__main__":
     parser.add_argument("--formant-shift", dest="formant_shift", default=None, type=positive_factor, metavar="F",
                         help="factor on the formant frequencies at the same pitch, applied to every mel frame: F > 1 moves "
                              "them up (Def: none)")
+    parser.add_argument("--f0-dir", dest="f0_dir", default=None, metavar="DIR",
+                        help="take the pitch of every file from DIR/NAME.f0 (as generate_mel.py --write-f0 writes it: text rows "
+                             "`time_s f0_hz periodicity`, one per mel frame, 0 = unvoiced, filled from its neighbours) instead of "
+                             "the model's own F0; --transposition multiplies on top (Def: none)")
     parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
     parser.add_argument("--job", default=None, help=SUPPRESS)
     args = parser.parse_args()

@@ -28,6 +28,12 @@ limit is reported and skipped like the others.
 6g; include/mbexwn_envelope.h): the VTF-net and the WaveNet conditioning read every mel row at f / F, the F0-net reads it as
 it is.  A factor of 1 is the job without the flag, launch by launch.  The level is not compensated.  The three controls
 combine freely.
+
+--f0-source audio keeps the pitch that is in the sound instead of the pitch the model infers from the mel (DESIGN.md section
+6h; include/mbexwn_pitch.h): an F0 tracker runs on the frames of the mel analysis, between --f0-min and --f0-max Hz, its
+unvoiced frames are filled from their neighbours and the contour drives the oscillator; --transposition multiplies on top; a
+file without a voiced frame keeps the model's F0.  --write-f0 writes the tracked contour as NAME.f0 into the output directory
+(text rows `time_s f0_hz periodicity`, one per mel frame, 0 = unvoiced), with either source.
 """
 import json
 import os
@@ -44,8 +50,12 @@ from mbexwn_vocoder_amd.batched import file_factors, file_stretches, read_transp
 def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, transposition_file=None, noise_seed=0, batch=16,
          gpus=1, num_threads=2, out_rate=None, format="flac", flac_compression="verbatim", conv_form="auto",
          batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None,
-         formant_shift=1.0, formant_shift_file=None):
+         formant_shift=1.0, formant_shift_file=None, f0_source="net", f0_min=55.0, f0_max=1000.0, write_f0=False):
     try:
+        if f0_source not in ("net", "audio"):
+            raise ValueError(f"--f0-source must be net or audio, got {f0_source!r}")
+        if not 0.0 < f0_min < f0_max:
+            raise ValueError(f"--f0-min must lie below --f0-max, got {f0_min} and {f0_max}")
         table = read_transposition_file(transposition_file) if transposition_file else None
         factors = file_factors(input_audio_files, transposition, table)
         stretches = file_stretches(input_audio_files, time_stretch,
@@ -83,6 +93,9 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
         argv += ["--formant-shift", repr(float(formant_shift))] if formant_shift != 1.0 else []
         argv += ["--formant-shift-file", formant_shift_file] if formant_shift_file else []
         argv += ["--out-rate", str(out_rate)] if out_rate else []
+        argv += ["--f0-source", f0_source] if f0_source != "net" else []
+        argv += ["--f0-min", repr(float(f0_min)), "--f0-max", repr(float(f0_max))] if f0_source != "net" or write_f0 else []
+        argv += ["--write-f0"] if write_f0 else []
         argv += [flag for flag, on in (("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant)) if on]
         status = run_ranks(os.path.abspath(__file__), argv, model_id, plan["files"], gpus, threads=num_threads, quiet=quiet,
                            plan=plan, tool="transform_audio") if plan["files"] else 0
@@ -107,7 +120,8 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
                             mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose,
                             quiet=quiet, flac_compression=flac_compression, out_rate=out_rate,
                             stretches=None if all(ss == 1.0 for ss in stretches) else stretches,
-                            formants=None if all(ff == 1.0 for ff in formants) else formants)
+                            formants=None if all(ff == 1.0 for ff in formants) else formants, f0_source=f0_source,
+                            f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0)
     if skipped:
         sys.exit(1)
 
@@ -119,6 +133,16 @@ def factor_arg(text):
         file_factors(["x"], float(text))
     except ValueError:
         raise ArgumentTypeError(f"a finite positive factor is expected, got {text!r}") from None
+    return float(text)
+
+
+def hertz_arg(text):
+    """argparse type of --f0-min and --f0-max: a finite positive frequency in Hz."""
+    from argparse import ArgumentTypeError
+    try:
+        file_factors(["x"], float(text))
+    except ValueError:
+        raise ArgumentTypeError(f"a finite positive frequency in Hz is expected, got {text!r}") from None
     return float(text)
 
 
@@ -170,6 +194,17 @@ def make_parser():
     parser.add_argument("--formant-shift-file", dest="formant_shift_file", default=None, metavar="LIST",
                         help="text file with lines `basename factor`: the formant-shift factor of the files it lists, instead "
                              "of --formant-shift")
+    parser.add_argument("--f0-source", dest="f0_source", default="net", choices=["net", "audio"],
+                        help="where the pitch comes from: net = what the model infers from the mel; audio = the F0 tracker on "
+                             "the sound itself, which keeps the pitch that is in the recording; --transposition multiplies on "
+                             "top of either (Def: %(default)s)")
+    parser.add_argument("--f0-min", dest="f0_min", default=55.0, type=hertz_arg, metavar="HZ",
+                        help="lowest pitch the F0 tracker looks for (Def: %(default)s)")
+    parser.add_argument("--f0-max", dest="f0_max", default=1000.0, type=hertz_arg, metavar="HZ",
+                        help="highest pitch the F0 tracker looks for (Def: %(default)s)")
+    parser.add_argument("--write-f0", dest="write_f0", action="store_true",
+                        help="write the tracked contour of every file as NAME.f0 into the output directory: text rows `time_s "
+                             "f0_hz periodicity`, one per mel frame, 0 = unvoiced")
     parser.add_argument("--noise-seed", dest="noise_seed", default=0, type=int, metavar="S",
                         help="seed of the keyed noise: a file's noise is a function of (S, its basename, the step) "
                              "(Def: %(default)s)")

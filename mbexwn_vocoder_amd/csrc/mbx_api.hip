@@ -11,6 +11,7 @@
 #include "../../include/mbexwn_flac.h"
 #include "../../include/mbexwn_noise.h"
 #include "../../include/mbexwn_warp.h"
+#include "../../include/mbexwn_pitch.h"
 #include "../../include/mbexwn_envelope.h"
 
 static_assert(MBXN_FILL_TILE == mbx::NOISE_TILE, "mbexwn_noise.h states the tile of noise_keyed.hip");
@@ -622,6 +623,34 @@ mbx_status mbxe_warp_envelope(const float *mel, int64_t row_stride_items, int32_
     if (const char *why = mbx::check_envelope(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("warp envelope: ") + why);
     if (batch == 0) return MBX_OK;
     mbx::launch_envelope(a, static_cast<hipStream_t>(hip_stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxp_track_f0(const float *audio, int64_t stride, int32_t batch, const int32_t *n_samples,
+                         const int64_t *centres, const int32_t *n_frames, int32_t max_frames, int32_t sample_rate,
+                         int32_t window, int32_t tau_min, int32_t tau_max, float threshold, float e_min, float *f0,
+                         float *periodicity, void *hip_stream) {
+    mbx::PitchArgs a{};
+    a.audio = audio;
+    a.stride = stride;
+    a.batch = batch;
+    a.n_samples = n_samples;
+    a.centres = centres;
+    a.n_frames = n_frames;
+    a.max_frames = max_frames;
+    a.sample_rate = sample_rate;
+    a.window = window;
+    a.tau_min = tau_min;
+    a.tau_max = tau_max;
+    a.threshold = threshold;
+    a.e_min = e_min;
+    a.f0 = f0;
+    a.periodicity = periodicity;
+    if (const char *why = mbx::check_track_f0(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("track f0: ") + why);
+    if (batch == 0) return MBX_OK;
+    mbx::launch_track_f0(a, static_cast<hipStream_t>(hip_stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

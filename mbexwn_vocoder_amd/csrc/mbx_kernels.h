@@ -423,6 +423,24 @@ struct EnvelopeArgs {
 const char *check_envelope(const EnvelopeArgs &a);
 void launch_envelope(const EnvelopeArgs &a, hipStream_t stream);
 
+// F0 of every analysis frame from the audio itself (f0_track.hip; include/mbexwn_pitch.h: mbxp_track_f0): a YIN-type
+// tracker on the frame grid of the mel analysis; the host definition is f0track.py::track_f0_host
+struct PitchArgs {
+    const float *audio;          // (batch, stride)
+    long long stride;
+    int batch;
+    const int32_t *n_samples;    // (batch), clamped in the kernel to [0, stride]
+    const int64_t *centres;      // (batch, max_frames), clamped in the kernel to [0, n_samples[b]]
+    const int32_t *n_frames;     // (batch): rows k >= n_frames[b] are not written
+    int max_frames;
+    int sample_rate, window, tau_min, tau_max;
+    float threshold, e_min;
+    float *f0, *periodicity;     // (batch, max_frames) each
+};
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_track_f0(const PitchArgs &a);
+void launch_track_f0(const PitchArgs &a, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // optional RMS normalisation of the mel input / de-normalisation of the audio (norm_mel.hip)
 // ---------------------------------------------------------------------------------------------

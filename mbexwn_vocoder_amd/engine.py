@@ -247,6 +247,9 @@ def load_library():
     lib.mbxe_warp_envelope.argtypes = [fp, ctypes.c_int64, i32, vp, i32, i32, fp, fp, fp, vp]
     lib.mbxe_forward.restype = i32
     lib.mbxe_forward.argtypes = [vp, fp, vp, i32, i32, fp, fp, vp, ctypes.c_size_t, ctypes.POINTER(mbx_forward_options), fp, fp, fp, vp]
+    # include/mbexwn_pitch.h (PITCH_SYMBOLS)
+    lib.mbxp_track_f0.restype = i32
+    lib.mbxp_track_f0.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, ctypes.c_float, fp, fp, vp]
     _lib = lib
     return lib
 
@@ -280,6 +283,9 @@ WARP_SYMBOLS = ["mbxw_mel_frames_at"]
 
 # include/mbexwn_envelope.h: the formant shift (prefix mbxe_; the eight lists above stay as they are)
 ENVELOPE_SYMBOLS = ["mbxe_warp_envelope", "mbxe_forward"]
+
+# include/mbexwn_pitch.h: the F0 tracker (prefix mbxp_; the nine lists above stay as they are)
+PITCH_SYMBOLS = ["mbxp_track_f0"]
 
 
 def _check(status):
@@ -1163,6 +1169,16 @@ class MBExWNEngine:
                                                 T, n, self._envelope_centres().data_ptr(), factors.data_ptr(), out.data_ptr(),
                                                 self._stream()))
         return out
+
+    def track_f0(self, audio, n_samples, centres, n_frames, **params):
+        """F0 and periodicity of every frame from the audio itself (``mbxp_track_f0``, include/mbexwn_pitch.h) on the
+        engine's stream: ``f0track.track_f0_device`` at the model's sample rate; ``params`` are ``f0track.params``'
+        keywords (f0_min, f0_max, window, threshold, rms_floor).  Returns (f0, periodicity), cuda (batch, max_frames)."""
+        from . import f0track
+        if not self._torch.is_tensor(audio) or audio.device != self.device:
+            raise ValueError("audio must be a float32 tensor (batch, stride) on the engine's device")
+        with self._torch.cuda.device(self.device):
+            return f0track.track_f0_device(audio, n_samples, centres, n_frames, f0track.params(self.dims.sample_rate, **params))
 
     def encode_flac16(self, audio, n_samples, sample_rate=None, wait=True, compression="verbatim"):
         """The FLAC frames (``flac.encode`` of the item without its 42-byte header) and max |x| of every item

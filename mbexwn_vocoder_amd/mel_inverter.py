@@ -249,7 +249,7 @@ class MELInverter(object):
 
     def synth_from_mels(self, scaled_mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False,
                         flac_compression="verbatim", out_rate=None, noise_seed=None, noise_keys=None, transpositions=None,
-                        formants=None):
+                        formants=None, f0s=None):
         """Batched :meth:`synth_from_mel` (this build): a list of ``scale_mel`` outputs (1, T_i, mel_channels) -> a list of
         float32 audio (T_i * hop_size,), or with ``flac=True`` of complete FLAC files (bytes; frames encoded on the device).
 
@@ -267,9 +267,12 @@ class MELInverter(object):
         :meth:`synth_from_mel` with ``noise_seed`` / ``noise_key`` does -- nothing is replayed, and an item's draw does not
         depend on the list it is in.  Not together with ``noises``.  ``transpositions``: per item None, or (T_i,) factors,
         one per mel frame (``f0_scale`` rows of the forward).  ``formants``: per item None, one formant-shift factor, or
-        (T_i,) of them (:meth:`synth_from_mel` ``formant``; the ``formant`` rows of the forward)."""
+        (T_i,) of them (:meth:`synth_from_mel` ``formant``; the ``formant`` rows of the forward).  ``f0s``: per item None, or
+        (T_i,) Hz, one value per mel frame, positive and finite, in place of the F0-net's contour (:meth:`synth_from_mel`
+        ``f0``; the ``f0_frames`` rows of the forward) -- an item with None keeps the F0-net (``f0_item_mask``), the
+        transposition multiplies on top, and a wrong length or value is refused before anything runs."""
         import torch
-        from .batched import replay_noise, run_micro_batches
+        from .batched import check_f0s, replay_noise, run_micro_batches
         if noise_seed is not None and noises is not None:
             raise ValueError("noises= and noise_seed= exclude each other: the keyed draw replaces the injected one")
         if noise_seed is None and noise_keys is not None:
@@ -279,6 +282,7 @@ class MELInverter(object):
         if len(scaled_mels):
             self._calibrate_if_pending(scaled_mels[0])
         mels =[np.asarray(mm, dtype=np.float32).reshape(-1, mm.shape[-2], mm.shape[-1])[0] for mm in scaled_mels]
+        f0s = check_f0s(f0s, [int(mm.shape[0]) for mm in mels])
         if formants is not None:
             if len(formants) != len(mels):
                 raise ValueError("synth_from_mels: one formants entry per mel")
@@ -300,7 +304,7 @@ class MELInverter(object):
         out = [None] * len(mels)
         for batch in run_micro_batches(self.model, mels, noises, max_batch, max_padded_frames, flac=flac, host_audio=not flac,
                                        flac_compression=flac_compression, out_rate=out_rate, transpositions=transpositions,
-                                       formants=formants):
+                                       formants=formants, f0s=f0s):
             batch.wait()
             for jj, ii in enumerate(batch.indices):
                 if not flac:
@@ -313,7 +317,8 @@ class MELInverter(object):
         return out
 
     def transform_audio(self, sounds, rates, names, transposition=1.0, noise_seed=0, out_rate=None, max_batch=16,
-                        max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None, formant=None):
+                        max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None, formant=None,
+                        f0_source="net", f0_params=None):
         """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
         keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
         factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
@@ -331,9 +336,15 @@ class MELInverter(object):
         per item, each a factor or one factor per mel frame of the item (:meth:`synth_from_mels` ``formants``).  It combines
         freely with ``transposition`` and ``time_stretch``.
 
+        ``f0_source``: ``"net"`` -- the pitch the model infers from the mel, as before -- or ``"audio"``: the pitch that is in
+        the sound.  The F0 tracker (f0track.py; ``f0_params``: keywords of ``f0track.params``) runs on
+        the model-rate samples at the centres of the item's mel frames, warped ones included, its unvoiced frames are filled
+        (``f0track.fill_unvoiced``) and the contour replaces the F0-net's (:meth:`synth_from_mels` ``f0s``); the transposition
+        multiplies on top.  An item without a voiced frame keeps the F0-net.
+
         An item's audio is a function of (sound, rate, name, factor, stretch, formant, seed, out_rate): with a ``batch_invariant``
         engine or one pinned to a convolution form it does not depend on the batch, the order or the other items."""
-        from . import timemap
+        from . import f0track, timemap
         from .analysis import generate_mels
         from .noise import item_key
         factors = check_factors(transposition, len(sounds))
@@ -341,15 +352,40 @@ class MELInverter(object):
             raise ValueError("transform_audio: one rate and one name per sound")
         if formant is not None and (not isinstance(formant, (list, tuple)) or len(formant) != len(sounds)):
             raise ValueError("transform_audio: formant takes one entry per sound")
+        if f0_source not in F0_SOURCES:
+            raise ValueError(f"transform_audio: f0_source must be one of {F0_SOURCES}, got {f0_source!r}")
+        if f0_source == "audio":
+            f0_params = f0track.params(int(round(self.srate)), **(f0_params or {}))
         maps = timemap.per_item(time_stretch, len(sounds), "transform_audio: time_stretch")
+        tracked = [] if f0_source == "audio" else None
         dicts = generate_mels(sounds, rates, self.preprocess_config, on_device=True, batch=max_batch,
                               time_maps=None if all(mm is None for mm in maps) else maps,
-                              rows_per_frame=self.model.dims.steps_per_frame)
+                              rows_per_frame=self.model.dims.steps_per_frame, f0_out=tracked,
+                              f0_params=f0_params if tracked is not None else None)
         scaled = [self.scale_mel(dd) for dd in dicts]
+        contours = None if tracked is None else [f0track.fill_unvoiced(ff) for ff, _ in tracked]
         rows = [np.full(int(mm.shape[1]), ff, dtype=np.float32) for mm, ff in zip(scaled, factors)]
         return self.synth_from_mels(scaled, max_batch=max_batch, max_padded_frames=max_padded_frames, flac=flac,
                                     flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed,
-                                    noise_keys=[item_key(nn) for nn in names], transpositions=rows, formants=formant)
+                                    noise_keys=[item_key(nn) for nn in names], transpositions=rows, formants=formant,
+                                    f0s=contours)
+
+    def track_f0(self, snd, srate, on_device=False, **f0_params):
+        """The pitch of a single sound (this build): (times in s, f0 in Hz with 0 = unvoiced, periodicity), one value per mel
+        frame :meth:`generate_mel_from_snd` with ``resampler="reference"`` gives for it.  ``f0_params``: keywords of
+        ``f0track.params`` (f0_min, f0_max, window, threshold, rms_floor).  Host (numpy) or, ``on_device``, the HIP kernel:
+        the same bits on the same model-rate samples (a sound at another rate goes through the host or
+        the device resampler first, as in ``generate_mels``)."""
+        from . import f0track
+        from .analysis import generate_mels
+        snd = np.asarray(snd)
+        if snd.ndim == 2 and snd.shape[0] == 1:
+            snd = snd[0]
+        tracked = []
+        generate_mels([snd], [srate], self.preprocess_config, on_device=on_device, batch=1, f0_out=tracked,
+                      f0_params=f0track.params(int(round(self.srate)), **f0_params))
+        f0, periodicity = tracked[0]
+        return f0track.frame_times(f0.size, self.hop_size, self.srate), f0, periodicity
 
     def calibrate(self, scaled_mells, verbose=False, max_frames=400, seed=42):
         """Decide the form of the WaveNet's dilated convolution on REAL data (this build; C ABI mbx_calibrate).
@@ -513,6 +549,10 @@ class MELInverter(object):
         self.use_max_limit = False
         if self.preprocess_config.get("use_max_limit", False):
             self.use_max_limit = self.preprocess_config["use_max_limit"]
+
+
+# where the pitch of transform_audio comes from: the model's F0-net, or the F0 tracker on the sound itself
+F0_SOURCES = ("net", "audio")
 
 
 class KeyedNoise:

@@ -236,7 +236,7 @@ def resampled_length(n, rate, target):
 
 
 def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None, time_maps=None, rows_per_frame=1,
-                  f0_out=None, f0_params=None):
+                  f0_out=None, f0_params=None, f0_decode=None):
     """Sounds -> ``.mell`` dictionaries (reference bin/generate_mel.py:54-64 for a list of files): ``sounds`` is a list of 1-D
     float32 arrays, ``rates`` their sample rates.  A sound that is not at the model rate goes through the reference's resampler
     (resample.py); one already at it skips that step.  Needs the ``preprocess_config`` alone: no engine, no weights.
@@ -258,9 +258,14 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     (f0track.py) on the item's model-rate samples at the centres of its mel frames, warped or regular
     (on the device ``mbxp_track_f0`` behind the analysis of the micro-batch, else ``f0track.track_f0_host``: the same
     bits).  ``f0_params``: ``f0track.params`` of the model rate (default: its defaults).  None makes today's launches;
-    the dictionaries have the same keys either way."""
+    the dictionaries have the same keys either way.
+
+    ``f0_decode``: None, or a ``f0decode.decode_params`` dictionary.  Given one, every item's pair is
+    the decoded one: Viterbi over the YIN candidates of all its frames instead of the pick of every frame on its own (on
+    the device ``mbxc_f0_candidates`` and ``mbxc_decode_f0`` in place of ``mbxp_track_f0``, else
+    ``f0decode.track_f0_viterbi_host``: the same bits).  It needs ``f0_out``.  None makes exactly the launches of before."""
     import time
-    from . import f0track, resample, timemap
+    from . import f0decode, f0track, resample, timemap
     cfg = preprocess_config
     target, hop = int(cfg["sample_rate"]), int(cfg["hop_size"])
     win_len = int(cfg.get("win_size", cfg["fft_size"]))
@@ -273,6 +278,10 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
             raise ValueError(f"generate_mels: sound {ii} must be a non-empty 1-D array, got shape {ss.shape}")
     out = [None] * len(sounds)
     tracked = [None] * len(sounds)
+    if f0_decode is not None:
+        if f0_out is None:
+            raise ValueError("generate_mels: f0_decode needs f0_out, the list the contours go to")
+        f0decode.check_decode(f0_decode)
     if f0_out is not None:
         f0_params = f0track.check_params(dict(f0_params)) if f0_params is not None else f0track.params(target)
         if int(f0_params["sample_rate"]) != target:
@@ -296,8 +305,11 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
             out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[0].T))
             if f0_out is not None:
                 t2 = time.perf_counter()
-                tracked[ii] = f0track.track_f0_host(ss, warped[ii] if ii in warped else timemap.centres(ss.size, hop, target, None),
-                                                    f0_params)
+                cc = warped[ii] if ii in warped else timemap.centres(ss.size, hop, target, None)
+                if f0_decode is not None:
+                    tracked[ii] = f0decode.track_f0_viterbi_host(ss, cc, f0_params, f0_decode)
+                else:
+                    tracked[ii] = f0track.track_f0_host(ss, cc, f0_params)
                 _add(stats, "f0", time.perf_counter() - t2)
         if f0_out is not None:
             f0_out.extend(tracked)
@@ -348,7 +360,10 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
             if marks:
                 marks[3].record()
             if f0_out is not None:                              # the regular centres are t * hop: the analysis's own frames
-                f0_dev, per_dev = f0track.track_f0_device(snd, n_dev, table_dev, counts_dev, f0_params)
+                if f0_decode is not None:
+                    f0_dev, per_dev = f0decode.track_f0_viterbi_device(snd, n_dev, table_dev, counts_dev, f0_params, f0_decode)
+                else:
+                    f0_dev, per_dev = f0track.track_f0_device(snd, n_dev, table_dev, counts_dev, f0_params)
                 if marks:
                     marks[4].record()
             if marks:

@@ -450,7 +450,7 @@ def read_sound(path):
 
 def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
                   quiet=False, flac_compression="verbatim", out_rate=None, stretches=None, formants=None, f0_source="net",
-                  f0_params=None, write_f0=False, timings=None):
+                  f0_params=None, write_f0=False, timings=None, f0_decode=None):
     """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
     ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
 
@@ -474,7 +474,9 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     ``f0track.params``) runs behind the analysis of every micro-batch, on the frames of the mel, and a file's filled contour
     replaces the F0-net's; ``factors`` multiply on top; a file without a voiced frame keeps the F0-net.  ``write_f0``:
     the tracked contour (0 = unvoiced) is written as NAME.f0 into ``output_dir``, with either source.  "net" without
-    ``write_f0``: the launches and the bytes of before.  ``timings``: a dict that receives the seconds per stage the
+    ``write_f0``: the launches and the bytes of before.  ``f0_decode``: None, or a ``f0decode.decode_params`` dictionary: the
+    contour, used and written, is the Viterbi path over the YIN candidates of the file's frames (DESIGN.md section 6i);
+    it needs "audio" or ``write_f0``.  ``timings``: a dict that receives the seconds per stage the
     verbose line reports (upload, resample, analysis, f0, copy_back from ``generate_mels``; read, scale, device, copy, write
     from the pools and the micro-batches' events; wall)."""
     from . import f0track, timemap
@@ -524,13 +526,15 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
         if f0_source not in ("net", "audio"):
             raise ValueError(f"run_audio_job: f0_source must be 'net' or 'audio', got {f0_source!r}")
         tracked = [] if f0_source == "audio" or write_f0 else None
+        if f0_decode is not None and tracked is None:
+            raise ValueError("run_audio_job: f0_decode decodes the tracked contour and needs f0_source='audio' or write_f0")
         stats = {}
         dicts = generate_mels([loaded[ii][0] for ii in mine], [loaded[ii][1] for ii in mine], inv.preprocess_config,
                               on_device=True, batch=max(1, batch), stats=stats,
                               time_maps=None if all(maps[ii] is None for ii in mine) else [maps[ii] for ii in mine],
                               rows_per_frame=inv.model.dims.steps_per_frame, f0_out=tracked,
-                              f0_params=None if tracked is None else f0track.params(int(round(inv.srate)), **(f0_params or {}))
-                              ) if mine else []
+                              f0_params=None if tracked is None else f0track.params(int(round(inv.srate)), **(f0_params or {})),
+                              f0_decode=f0_decode) if mine else []
         scaled = dict(zip(mine, pool.map(scale, dicts)))
         contours = None
         if tracked is not None:

@@ -14,6 +14,8 @@ Deviations (documented in INTEGRATION.md):
     the same pitch; with ``--host`` too
   * additionally ``--write-f0`` (``--f0-min``, ``--f0-max``): the F0 tracker (f0track.py) runs on the
     frames of the mel and NAME.f0 is written next to NAME.mell, for ``resynth_mel.py --f0-dir``; with ``--host`` too, same bits
+  * additionally ``--pitch-decode viterbi`` (``--pitch-jump``, ``--pitch-switch``): the written contour is decoded over the
+    whole file (f0decode.py) instead of picked frame by frame; with ``--host`` too, same bits
   * without ``--host`` and without a GPU the script fails loudly; there is no ``--gpus``
 """
 import os
@@ -26,7 +28,7 @@ if os.path.exists(test_path):
     sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
 
 from mbexwn_vocoder_amd import get_config_file, list_models  # noqa: E402
-from mbexwn_vocoder_amd import f0track  # noqa: E402
+from mbexwn_vocoder_amd import f0decode, f0track  # noqa: E402
 from mbexwn_vocoder_amd.analysis import generate_mels  # noqa: E402
 from mbexwn_vocoder_amd.batched import f0_path  # noqa: E402
 from mbexwn_vocoder_amd.audioio import read_audio  # noqa: E402
@@ -36,7 +38,7 @@ from mbexwn_vocoder_amd.timemap import check_factor  # noqa: E402
 
 
 def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2, host=False, verbose=False, quiet=False,
-         time_stretch=1.0, write_f0=False, f0_min=55.0, f0_max=1000.0):
+         time_stretch=1.0, write_f0=False, f0_min=55.0, f0_max=1000.0, pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5):
     config_file = get_config_file(model_id_or_path=model_id)
     config = read_config(config_file=config_file)
     preprocess_config = config['preprocess_config']
@@ -45,6 +47,11 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
         # a stretched file is made for resynth_mel.py: held to the limit of the model's engine (sub-band rows per frame)
         rows_per_frame = ModelDims(config).steps_per_frame if time_stretch != 1.0 else 1
         f0_params = f0track.params(int(preprocess_config["sample_rate"]), f0_min=f0_min, f0_max=f0_max) if write_f0 else None
+        if pitch_decode not in ("greedy", "viterbi"):
+            raise ValueError(f"--pitch-decode must be greedy or viterbi, got {pitch_decode!r}")
+        f0_decode = f0decode.decode_params(w_jump=pitch_jump, w_switch=pitch_switch) if pitch_decode == "viterbi" else None
+        if f0_decode is not None and not write_f0:
+            raise ValueError("--pitch-decode viterbi decodes the contour that --write-f0 writes: it needs --write-f0")
     except ValueError as err:
         print(f"generate_mel::error:: {err}", file=sys.stderr)
         sys.exit(1)
@@ -99,7 +106,7 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
                 mells = generate_mels([ll[0] for ll in loaded], [ll[1] for ll in loaded], preprocess_config, on_device=not host,
                                       batch=batch, stats=stats, rows_per_frame=rows_per_frame,
                                       time_maps=None if time_stretch == 1.0 else [time_stretch] * len(loaded),
-                                      f0_out=tracked, f0_params=f0_params)
+                                      f0_out=tracked, f0_params=f0_params, f0_decode=f0_decode)
             except ValueError as err:
                 print(f"generate_mel::error:: {err}", file=sys.stderr)
                 sys.exit(1)
@@ -147,6 +154,13 @@ if __name__ == "__main__":
                         help="lowest pitch the F0 tracker looks for (Def: %(default)s)")
     parser.add_argument("--f0-max", dest="f0_max", default=1000.0, type=float, metavar="HZ",
                         help="highest pitch the F0 tracker looks for (Def: %(default)s)")
+    parser.add_argument("--pitch-decode", dest="pitch_decode", default="greedy", choices=["greedy", "viterbi"],
+                        help="--write-f0: greedy = every frame picks on its own; viterbi = the cheapest path over several "
+                             "candidates per frame and an unvoiced state (Def: %(default)s)")
+    parser.add_argument("--pitch-jump", dest="pitch_jump", default=4.0, type=float, metavar="W",
+                        help="viterbi: weight on the relative change of period between neighbouring frames (Def: %(default)s)")
+    parser.add_argument("--pitch-switch", dest="pitch_switch", default=0.5, type=float, metavar="W",
+                        help="viterbi: cost of a change between voiced and unvoiced (Def: %(default)s)")
     parser.add_argument("--host", action="store_true", help="numpy analysis and host resampler; needs no GPU")
     parser.add_argument("-v", "--verbose", action="store_true", help="display verbose progress info")
     parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")

@@ -34,6 +34,11 @@ combine freely.
 unvoiced frames are filled from their neighbours and the contour drives the oscillator; --transposition multiplies on top; a
 file without a voiced frame keeps the model's F0.  --write-f0 writes the tracked contour as NAME.f0 into the output directory
 (text rows `time_s f0_hz periodicity`, one per mel frame, 0 = unvoiced), with either source.
+
+--pitch-decode viterbi decodes that contour over the whole file instead of picking every frame on its own (DESIGN.md section
+6i; include/mbexwn_contour.h): every frame offers several YIN candidates and an unvoiced state, and the cheapest path wins,
+with --pitch-jump on the relative change of period between frames and --pitch-switch on a change between voiced and
+unvoiced.  A frame whose pick alone would land an octave off no longer does.  The default, greedy, is the job of before.
 """
 import json
 import os
@@ -50,12 +55,16 @@ from mbexwn_vocoder_amd.batched import file_factors, file_stretches, read_transp
 def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, transposition_file=None, noise_seed=0, batch=16,
          gpus=1, num_threads=2, out_rate=None, format="flac", flac_compression="verbatim", conv_form="auto",
          batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None,
-         formant_shift=1.0, formant_shift_file=None, f0_source="net", f0_min=55.0, f0_max=1000.0, write_f0=False):
+         formant_shift=1.0, formant_shift_file=None, f0_source="net", f0_min=55.0, f0_max=1000.0, write_f0=False,
+         pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5):
     try:
         if f0_source not in ("net", "audio"):
             raise ValueError(f"--f0-source must be net or audio, got {f0_source!r}")
         if not 0.0 < f0_min < f0_max:
             raise ValueError(f"--f0-min must lie below --f0-max, got {f0_min} and {f0_max}")
+        f0_decode = pitch_decode_params(pitch_decode, pitch_jump, pitch_switch)
+        if f0_decode is not None and f0_source != "audio" and not write_f0:
+            raise ValueError("--pitch-decode viterbi decodes the tracked contour: it needs --f0-source audio or --write-f0")
         table = read_transposition_file(transposition_file) if transposition_file else None
         factors = file_factors(input_audio_files, transposition, table)
         stretches = file_stretches(input_audio_files, time_stretch,
@@ -96,6 +105,9 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
         argv += ["--f0-source", f0_source] if f0_source != "net" else []
         argv += ["--f0-min", repr(float(f0_min)), "--f0-max", repr(float(f0_max))] if f0_source != "net" or write_f0 else []
         argv += ["--write-f0"] if write_f0 else []
+        argv += ["--pitch-decode", pitch_decode] if pitch_decode != "greedy" else []
+        argv += ["--pitch-jump", repr(float(pitch_jump))] if pitch_jump != 4.0 else []
+        argv += ["--pitch-switch", repr(float(pitch_switch))] if pitch_switch != 0.5 else []
         argv += [flag for flag, on in (("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant)) if on]
         status = run_ranks(os.path.abspath(__file__), argv, model_id, plan["files"], gpus, threads=num_threads, quiet=quiet,
                            plan=plan, tool="transform_audio") if plan["files"] else 0
@@ -121,9 +133,30 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
                             quiet=quiet, flac_compression=flac_compression, out_rate=out_rate,
                             stretches=None if all(ss == 1.0 for ss in stretches) else stretches,
                             formants=None if all(ff == 1.0 for ff in formants) else formants, f0_source=f0_source,
-                            f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0)
+                            f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0, f0_decode=f0_decode)
     if skipped:
         sys.exit(1)
+
+
+def pitch_decode_params(pitch_decode, pitch_jump, pitch_switch):
+    """None for --pitch-decode greedy, else the ``f0decode.decode_params`` dictionary of the three flags."""
+    if pitch_decode not in ("greedy", "viterbi"):
+        raise ValueError(f"--pitch-decode must be greedy or viterbi, got {pitch_decode!r}")
+    from mbexwn_vocoder_amd import f0decode
+    dec = f0decode.decode_params(w_jump=pitch_jump, w_switch=pitch_switch)               # checked with either choice
+    return dec if pitch_decode == "viterbi" else None
+
+
+def weight_arg(text):
+    """argparse type of --pitch-jump and --pitch-switch: a weight in [0, 1e6]."""
+    from argparse import ArgumentTypeError
+    try:
+        value = float(text)
+    except ValueError:
+        value = float("nan")
+    if not 0.0 <= value <= 1e6:
+        raise ArgumentTypeError(f"a weight in 0 .. 1e6 is expected, got {text!r}")
+    return value
 
 
 def factor_arg(text):
@@ -205,6 +238,14 @@ def make_parser():
     parser.add_argument("--write-f0", dest="write_f0", action="store_true",
                         help="write the tracked contour of every file as NAME.f0 into the output directory: text rows `time_s "
                              "f0_hz periodicity`, one per mel frame, 0 = unvoiced")
+    parser.add_argument("--pitch-decode", dest="pitch_decode", default="greedy", choices=["greedy", "viterbi"],
+                        help="how the tracker's contour is made: greedy = every frame picks on its own; viterbi = the cheapest "
+                             "path over several candidates per frame and an unvoiced state, which removes single-frame octave "
+                             "jumps (Def: %(default)s)")
+    parser.add_argument("--pitch-jump", dest="pitch_jump", default=4.0, type=weight_arg, metavar="W",
+                        help="viterbi: weight on the relative change of period between neighbouring frames (Def: %(default)s)")
+    parser.add_argument("--pitch-switch", dest="pitch_switch", default=0.5, type=weight_arg, metavar="W",
+                        help="viterbi: cost of a change between voiced and unvoiced (Def: %(default)s)")
     parser.add_argument("--noise-seed", dest="noise_seed", default=0, type=int, metavar="S",
                         help="seed of the keyed noise: a file's noise is a function of (S, its basename, the step) "
                              "(Def: %(default)s)")

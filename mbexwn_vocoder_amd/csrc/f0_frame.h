@@ -1,0 +1,129 @@
+// The part the F0 tracker (f0_track.hip) and the candidates kernel of the decoder (f0_decode.hip) share: one 256-thread block
+// loads a frame into LDS and leaves its cumulative-mean-normalised difference function d' there (the
+// host definition is mbexwn_vocoder_amd/f0track.py::difference_host).
+//
+//   y[i]   = x[c - L/2 + i], 0 outside the item            L = W + tau_max, c = centres[b][k] clamped to [0, n_b]
+//   d[tau] = sum_j (y[s + j] - y[s + tau + j])^2           s = (tau_max - tau) >> 1, 0 <= j < W, 1 <= tau <= tau_max
+//   d'[tau] = d[tau] tau / (d[1] + .. + d[tau])            1 where the running sum is not positive
+//
+// Host and device must give the same bits: every operation is one separately rounded IEEE float32 operation.  This header
+// sets `#pragma clang fp contract(off)` itself, and it holds for the rest of a file that includes this header.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#pragma clang fp contract(off)
+
+namespace mbx {
+
+constexpr int F0_THREADS = 256;
+constexpr int F0_WAVES = F0_THREADS / 64;
+// a sample that is not finite, or so large that the sums below could overflow, makes its frame unvoiced (f0track.SAMPLE_LIMIT)
+constexpr float F0_SAMPLE_LIMIT = 1e15f;
+
+// the definition's lane sum from 64 partial sums: after the step with m, lane l < m holds a[l] + a[l + m] (the other lanes
+// hold sums nobody reads).  All in the vector ALU: the two halves of the wave, then the rows of 16 lanes, meet through
+// gfx950's lane swaps (v_permlane32_swap, v_permlane16_swap: with both operands the same register, one result holds the lower
+// partner and the other the upper one on every lane); inside a row lane l reads lane l + m by DPP (row_shl).  The whole wave
+// must be active.
+__device__ inline float f0_lane_sum(float a) {
+    typedef unsigned f0_pair __attribute__((ext_vector_type(2)));
+    f0_pair r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(a), false, false);
+    a = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(a), false, false);
+    a = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    a = a + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(a), 0x108, 0xf, 0xf, true));   // row_shl:8
+    a = a + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(a), 0x104, 0xf, 0xf, true));   // row_shl:4
+    a = a + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(a), 0x102, 0xf, 0xf, true));   // row_shl:2
+    a = a + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(a), 0x101, 0xf, 0xf, true));   // row_shl:1
+    return a;
+}
+
+// The frame of item row `xb` (n samples) centred on c, through to d'.  The whole block calls it.  `smem` holds W + 2 TM + 1
+// floats: on return smem + W + TM is d' (TM + 1 entries, d'[0] = 1) and the W + TM floats in front of it are free; *s_energy
+// (one __shared__ float) is the energy of the W samples about the centre.  Returns, on every thread, whether the frame
+// touches a sample that is not finite or above F0_SAMPLE_LIMIT.  Ends behind a __syncthreads().
+__device__ inline int f0_frame_dprime(const float *xb, long long n, long long c, int W, int TM, float *smem, float *s_energy) {
+    const int L = W + TM;
+    float *y = smem;                                        // (L) the frame; later (TM + 1) the running sums of d
+    float *d = smem + L;                                    // (TM + 1) d, then d'
+    const long long first = c - (L >> 1);
+    int bad = 0;
+    for (int i = threadIdx.x; i < L; i += F0_THREADS) {
+        const long long s = first + i;
+        const float v = (s >= 0 && s < n) ? xb[s] : 0.f;
+        if (!(fabsf(v) <= F0_SAMPLE_LIMIT)) bad = 1;
+        y[i] = v;
+    }
+    bad = __syncthreads_or(bad);
+
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int terms = W >> 6;
+    // two lags per turn: tau_max - 2 j - 1 and tau_max - 2 j share s = j, hence the first window, which is read once for both
+    // (tau = 0, the partner of tau = 1 when tau_max is odd, is computed and dropped: its second window is the first)
+    for (int j = wave; 2 * j < TM; j += F0_WAVES) {
+        const int tau = TM - 2 * j;                         // (the highest index is j + tau + W - 1 <= TM + W - 1 = L - 1)
+        const float *u = y + j + lane, *v = u + tau;
+        float x0 = u[0];
+        float e1 = x0 - v[0], e0 = x0 - v[-1];
+        float a1 = e1 * e1, a0 = e0 * e0;
+        for (int kk = 1; kk < terms; ++kk) {
+            x0 = u[64 * kk];
+            e1 = x0 - v[64 * kk];
+            e0 = x0 - v[64 * kk - 1];
+            const float q1 = e1 * e1, q0 = e0 * e0;
+            a1 = a1 + q1;
+            a0 = a0 + q0;
+        }
+        a1 = f0_lane_sum(a1);
+        a0 = f0_lane_sum(a0);
+        if (lane == 0) {
+            d[tau] = a1;
+            if (tau > 1) d[tau - 1] = a0;
+        }
+    }
+    if (wave == F0_WAVES - 1) {                             // the energy of the W samples about the centre
+        const float *u = y + (TM >> 1) + lane;
+        float a = u[0] * u[0];
+        for (int kk = 1; kk < terms; ++kk) {
+            const float q = u[64 * kk] * u[64 * kk];
+            a = a + q;
+        }
+        a = f0_lane_sum(a);
+        if (lane == 0) *s_energy = a;
+    }
+    __syncthreads();                                        // the frame is no longer read: its space takes the running sums
+
+    float *cs = y;
+    if (threadIdx.x == 0) {
+        float run = 0.f;
+        d[0] = 1.f;
+        for (int tau = 1; tau <= TM; ++tau) {
+            run = run + d[tau];
+            cs[tau] = run;
+        }
+    }
+    __syncthreads();
+    for (int tau = 1 + threadIdx.x; tau <= TM; tau += F0_THREADS) {
+        const float ct = cs[tau];
+        const float num = d[tau] * (float)tau;
+        d[tau] = ct > 0.f ? num / ct : 1.f;
+    }
+    __syncthreads();
+    return bad;
+}
+
+// f0track.pick_host's refinement of a lag tau in [2, tau_max - 1]: float(tau) plus the vertex of the parabola through
+// d'[tau - 1 .. tau + 1], clamped to [-1, 1]
+__device__ inline float f0_refined_lag(const float *d, int tau) {
+    const float a = d[tau - 1], bb = d[tau], g = d[tau + 1];
+    const float den = (a - bb) + (g - bb);
+    float off = 0.f;
+    if (den > 0.f) {
+        off = ((a - g) / den) * 0.5f;
+        off = fminf(fmaxf(off, -1.f), 1.f);
+    }
+    return (float)tau + off;
+}
+
+}  // namespace mbx

@@ -12,6 +12,7 @@
 #include "../../include/mbexwn_noise.h"
 #include "../../include/mbexwn_warp.h"
 #include "../../include/mbexwn_pitch.h"
+#include "../../include/mbexwn_contour.h"
 #include "../../include/mbexwn_envelope.h"
 
 static_assert(MBXN_FILL_TILE == mbx::NOISE_TILE, "mbexwn_noise.h states the tile of noise_keyed.hip");
@@ -651,6 +652,61 @@ mbx_status mbxp_track_f0(const float *audio, int64_t stride, int32_t batch, cons
     if (const char *why = mbx::check_track_f0(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("track f0: ") + why);
     if (batch == 0) return MBX_OK;
     mbx::launch_track_f0(a, static_cast<hipStream_t>(hip_stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxc_f0_candidates(const float *audio, int64_t stride, int32_t batch, const int32_t *n_samples,
+                              const int64_t *centres, const int32_t *n_frames, int32_t max_frames, int32_t sample_rate,
+                              int32_t window, int32_t tau_min, int32_t tau_max, float e_min, const float *thresholds,
+                              const float *weights, int32_t n_thresholds, int32_t n_cand, float *period, float *cost,
+                              float *dprime, void *hip_stream) {
+    mbx::CandidateArgs a{};
+    a.frame.audio = audio;
+    a.frame.stride = stride;
+    a.frame.batch = batch;
+    a.frame.n_samples = n_samples;
+    a.frame.centres = centres;
+    a.frame.n_frames = n_frames;
+    a.frame.max_frames = max_frames;
+    a.frame.sample_rate = sample_rate;
+    a.frame.window = window;
+    a.frame.tau_min = tau_min;
+    a.frame.tau_max = tau_max;
+    a.frame.e_min = e_min;
+    a.n_thresholds = n_thresholds;
+    a.n_cand = n_cand;
+    a.period = period;
+    a.cost = cost;
+    a.dprime = dprime;
+    if (const char *why = mbx::fill_f0_candidates(a, thresholds, weights))
+        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("f0 candidates: ") + why);
+    if (batch == 0) return MBX_OK;
+    mbx::launch_f0_candidates(a, static_cast<hipStream_t>(hip_stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return MBX_OK;
+}
+
+mbx_status mbxc_decode_f0(const float *period, const float *cost, const float *dprime, const int32_t *n_frames,
+                          int32_t max_frames, int32_t batch, int32_t sample_rate, float w_jump, float w_switch, float *f0,
+                          float *periodicity, void *hip_stream) {
+    mbx::DecodeArgs a{};
+    a.period = period;
+    a.cost = cost;
+    a.dprime = dprime;
+    a.n_frames = n_frames;
+    a.max_frames = max_frames;
+    a.batch = batch;
+    a.sample_rate = sample_rate;
+    a.w_jump = w_jump;
+    a.w_switch = w_switch;
+    a.f0 = f0;
+    a.periodicity = periodicity;
+    if (const char *why = mbx::check_decode_f0(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("decode f0: ") + why);
+    if (batch == 0) return MBX_OK;
+    mbx::launch_decode_f0(a, static_cast<hipStream_t>(hip_stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;

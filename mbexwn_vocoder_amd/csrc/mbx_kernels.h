@@ -441,6 +441,33 @@ struct PitchArgs {
 const char *check_track_f0(const PitchArgs &a);
 void launch_track_f0(const PitchArgs &a, hipStream_t stream);
 
+// A decoded contour (f0_decode.hip; include/mbexwn_contour.h: mbxc_f0_candidates, mbxc_decode_f0): per frame up to seven
+// candidate lags and an "unvoiced" state from the tracker's d', then a Viterbi path per item; the host definition is
+// f0decode.py (candidates_host, viterbi_host)
+constexpr int F0_SLOTS = 8;
+constexpr int F0_MAX_THRESHOLDS = 16;
+constexpr int F0_DECODE_MAX_FRAMES = 16000;      // 4 bytes of back pointers per frame in 64 000 bytes of LDS
+struct CandidateArgs {
+    PitchArgs frame;             // audio .. e_min as for the tracker; threshold, f0 and periodicity are not used
+    float thresholds[F0_MAX_THRESHOLDS];         // ascending; entries from n_thresholds on are not read
+    float weights[F0_MAX_THRESHOLDS];
+    int n_thresholds, n_cand;
+    float *period, *cost, *dprime;               // (batch, max_frames, 8) each
+};
+// thresholds and weights are HOST pointers: checked and copied into the arguments here.  nullptr when valid.
+const char *fill_f0_candidates(CandidateArgs &a, const float *thresholds, const float *weights);
+void launch_f0_candidates(const CandidateArgs &a, hipStream_t stream);
+
+struct DecodeArgs {
+    const float *period, *cost, *dprime;         // (batch, max_frames, 8) each
+    const int32_t *n_frames;     // (batch), clamped in the kernel to [0, max_frames]; rows behind are not written
+    int max_frames, batch, sample_rate;
+    float w_jump, w_switch;
+    float *f0, *periodicity;     // (batch, max_frames) each
+};
+const char *check_decode_f0(const DecodeArgs &a);
+void launch_decode_f0(const DecodeArgs &a, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // optional RMS normalisation of the mel input / de-normalisation of the audio (norm_mel.hip)
 // ---------------------------------------------------------------------------------------------

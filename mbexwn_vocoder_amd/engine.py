@@ -250,6 +250,12 @@ def load_library():
     # include/mbexwn_pitch.h (PITCH_SYMBOLS)
     lib.mbxp_track_f0.restype = i32
     lib.mbxp_track_f0.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, ctypes.c_float, fp, fp, vp]
+    # include/mbexwn_contour.h (CONTOUR_SYMBOLS); thresholds and weights are host pointers
+    hfp = ctypes.POINTER(ctypes.c_float)
+    lib.mbxc_f0_candidates.restype = i32
+    lib.mbxc_f0_candidates.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, hfp, hfp, i32, i32, fp, fp, fp, vp]
+    lib.mbxc_decode_f0.restype = i32
+    lib.mbxc_decode_f0.argtypes = [fp, fp, fp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, fp, fp, vp]
     _lib = lib
     return lib
 
@@ -286,6 +292,9 @@ ENVELOPE_SYMBOLS = ["mbxe_warp_envelope", "mbxe_forward"]
 
 # include/mbexwn_pitch.h: the F0 tracker (prefix mbxp_; the nine lists above stay as they are)
 PITCH_SYMBOLS = ["mbxp_track_f0"]
+
+# include/mbexwn_contour.h: the decoded F0 contour (prefix mbxc_; the ten lists above stay as they are)
+CONTOUR_SYMBOLS = ["mbxc_f0_candidates", "mbxc_decode_f0"]
 
 
 def _check(status):

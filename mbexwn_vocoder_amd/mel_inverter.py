@@ -318,7 +318,7 @@ class MELInverter(object):
 
     def transform_audio(self, sounds, rates, names, transposition=1.0, noise_seed=0, out_rate=None, max_batch=16,
                         max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None, formant=None,
-                        f0_source="net", f0_params=None):
+                        f0_source="net", f0_params=None, f0_decode=None):
         """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
         keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
         factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
@@ -340,7 +340,9 @@ class MELInverter(object):
         the sound.  The F0 tracker (f0track.py; ``f0_params``: keywords of ``f0track.params``) runs on
         the model-rate samples at the centres of the item's mel frames, warped ones included, its unvoiced frames are filled
         (``f0track.fill_unvoiced``) and the contour replaces the F0-net's (:meth:`synth_from_mels` ``f0s``); the transposition
-        multiplies on top.  An item without a voiced frame keeps the F0-net.
+        multiplies on top.  An item without a voiced frame keeps the F0-net.  ``f0_decode``: None -- every frame's pick on its
+        own -- or a ``f0decode.decode_params`` dictionary: the contour is the Viterbi path over the YIN candidates of the
+        item's frames, which does not jump an octave for single frames.  It needs ``"audio"``.
 
         An item's audio is a function of (sound, rate, name, factor, stretch, formant, seed, out_rate): with a ``batch_invariant``
         engine or one pinned to a convolution form it does not depend on the batch, the order or the other items."""
@@ -354,6 +356,8 @@ class MELInverter(object):
             raise ValueError("transform_audio: formant takes one entry per sound")
         if f0_source not in F0_SOURCES:
             raise ValueError(f"transform_audio: f0_source must be one of {F0_SOURCES}, got {f0_source!r}")
+        if f0_decode is not None and f0_source != "audio":
+            raise ValueError("transform_audio: f0_decode decodes the tracked contour and needs f0_source='audio'")
         if f0_source == "audio":
             f0_params = f0track.params(int(round(self.srate)), **(f0_params or {}))
         maps = timemap.per_item(time_stretch, len(sounds), "transform_audio: time_stretch")
@@ -361,7 +365,7 @@ class MELInverter(object):
         dicts = generate_mels(sounds, rates, self.preprocess_config, on_device=True, batch=max_batch,
                               time_maps=None if all(mm is None for mm in maps) else maps,
                               rows_per_frame=self.model.dims.steps_per_frame, f0_out=tracked,
-                              f0_params=f0_params if tracked is not None else None)
+                              f0_params=f0_params if tracked is not None else None, f0_decode=f0_decode)
         scaled = [self.scale_mel(dd) for dd in dicts]
         contours = None if tracked is None else [f0track.fill_unvoiced(ff) for ff, _ in tracked]
         rows = [np.full(int(mm.shape[1]), ff, dtype=np.float32) for mm, ff in zip(scaled, factors)]
@@ -370,12 +374,13 @@ class MELInverter(object):
                                     noise_keys=[item_key(nn) for nn in names], transpositions=rows, formants=formant,
                                     f0s=contours)
 
-    def track_f0(self, snd, srate, on_device=False, **f0_params):
+    def track_f0(self, snd, srate, on_device=False, decode=None, **f0_params):
         """The pitch of a single sound (this build): (times in s, f0 in Hz with 0 = unvoiced, periodicity), one value per mel
         frame :meth:`generate_mel_from_snd` with ``resampler="reference"`` gives for it.  ``f0_params``: keywords of
         ``f0track.params`` (f0_min, f0_max, window, threshold, rms_floor).  Host (numpy) or, ``on_device``, the HIP kernel:
         the same bits on the same model-rate samples (a sound at another rate goes through the host or
-        the device resampler first, as in ``generate_mels``)."""
+        the device resampler first, as in ``generate_mels``).  ``decode``: None, or a ``f0decode.decode_params`` dictionary --
+        the contour is then decoded over the whole sound, on the host or on the device alike."""
         from . import f0track
         from .analysis import generate_mels
         snd = np.asarray(snd)
@@ -383,7 +388,7 @@ class MELInverter(object):
             snd = snd[0]
         tracked = []
         generate_mels([snd], [srate], self.preprocess_config, on_device=on_device, batch=1, f0_out=tracked,
-                      f0_params=f0track.params(int(round(self.srate)), **f0_params))
+                      f0_params=f0track.params(int(round(self.srate)), **f0_params), f0_decode=decode)
         f0, periodicity = tracked[0]
         return f0track.frame_times(f0.size, self.hop_size, self.srate), f0, periodicity
 

@@ -6,6 +6,9 @@ device stages between HIP events, host stages by the host clock).
 
 One process: after one untimed job per source the two sources alternate ``--rounds`` times on the same files; the line gives
 every round and the median per stage.  Prints one JSON line.
+
+``--compare decode``: both legs take the pitch from the audio, one with the greedy pick of every frame
+and one with the contour decoded over the file (``f0_decode=f0decode.decode_params()``), alternating in the same way.
 """
 import argparse
 import json
@@ -21,12 +24,15 @@ def main():
     ap.add_argument("--files", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--compare", default="source", choices=["source", "decode"],
+                    help="source: f0_source net against audio; decode: audio with the greedy pick against the decoded contour")
     args = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("f0_source_probe.py: no GPU available; a timing taken without one says nothing")
     from scipy.io import wavfile
+    from mbexwn_vocoder_amd import f0decode
     from mbexwn_vocoder_amd.batched import run_audio_job
     from mbexwn_vocoder_amd.mel_inverter import MELInverter, create_synthetic_model_dir
     rate, n = 24000, int(round(args.seconds * 24000))
@@ -40,23 +46,27 @@ def main():
             files.append(os.path.join(tmp, f"voice{ii:02d}.wav"))
             wavfile.write(files[-1], rate, snd.astype(np.float32))
 
-        def job(source, tag):
+        if args.compare == "source":
+            legs = {"net": {"f0_source": "net"}, "audio": {"f0_source": "audio"}}
+        else:
+            legs = {"greedy": {"f0_source": "audio"}, "viterbi": {"f0_source": "audio", "f0_decode": f0decode.decode_params()}}
+
+        def job(leg, tag):
             out = os.path.join(tmp, tag)
             os.makedirs(out, exist_ok=True)
             timings = {}
-            skipped = run_audio_job(inv, files, out, "flac", noise_seed=0, batch=args.files, quiet=True, f0_source=source,
-                                    timings=timings)
+            skipped = run_audio_job(inv, files, out, "flac", noise_seed=0, batch=args.files, quiet=True, timings=timings, **legs[leg])
             assert skipped == []
             return {kk: float(vv) for kk, vv in sorted(timings.items())}
 
-        for source in ("net", "audio"):
+        for source in legs:
             job(source, "warm_" + source)
-        rounds = {"net": [], "audio": []}
+        rounds = {leg: [] for leg in legs}
         for rr in range(args.rounds):
-            for source in ("net", "audio"):
+            for source in legs:
                 rounds[source].append(job(source, f"{source}_{rr}"))
     median = {source: {kk: float(np.median([rr[kk] for rr in rows])) for kk in rows[0]} for source, rows in rounds.items()}
-    print(json.dumps({"device": torch.cuda.get_device_name(0), "files": args.files, "seconds": args.seconds, "unit": "s",
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "files": args.files, "seconds": args.seconds, "unit": "s", "compare": args.compare,
                       "median": median, "rounds": rounds}))
 
 

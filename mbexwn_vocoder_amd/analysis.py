@@ -143,7 +143,7 @@ def compute_log_mel_device(sound, preprocess_config, n_samples=None):
     host path transforms in float64 and rounds: the two agree to float32 rounding of the magnitudes)."""
     import ctypes
     import torch
-    from .engine import _check, load_library
+    from .abi import _check, load_library
     if sound.dim() != 2 or sound.dtype != torch.float32 or not sound.is_cuda:
         raise ValueError("sound must be a float32 cuda tensor of shape (batch, time)")
     cfg = preprocess_config
@@ -178,7 +178,7 @@ def compute_log_mel_device_at(sound, n_samples, centres, n_frames, preprocess_co
     :func:`compute_log_mel_device` computes for a frame with the same samples in front of it."""
     import ctypes
     import torch
-    from .engine import _check, load_library
+    from .abi import _check, load_library
     if sound.dim() != 2 or sound.dtype != torch.float32 or not sound.is_cuda:
         raise ValueError("sound must be a float32 cuda tensor of shape (batch, time)")
     cfg = preprocess_config

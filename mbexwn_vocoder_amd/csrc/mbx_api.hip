@@ -1,22 +1,11 @@
-// C ABI of the mel-inversion engine (include/mbexwn.h): the extern "C" surface apart from mbx_create / mbx_destroy /
-// mbx_workspace_size (mbx_create.hip) -- the forward entry points (their launch sequence: mbx_forward.hip), the calibration
-// of the convolution form, the stage and profile readers, the stand-alone operator entry points and the window helpers.
+// C ABI of the engine handle (include/mbexwn.h): the extern "C" surface apart from mbx_create / mbx_destroy /
+// mbx_workspace_size (mbx_create.hip) and the entry points that take no handle (mbx_stages.hip) -- the forward entry points
+// (their launch sequence: mbx_forward.hip; mbxe_forward of include/mbexwn_envelope.h is one of them), the calibration of the
+// convolution form, the stage and profile readers, the stand-alone operator entry points and the window helpers.
 // Nothing in here allocates, frees or synchronises after mbx_create apart from the calibration: every call only enqueues
 // kernels on the caller's stream, so a forward pass can be captured into a hipGraph by the caller.
 #include "mbx_handle.h"
-#include "../../include/mbexwn_audio.h"
-#include "../../include/mbexwn_live.h"
-#include "../../include/mbexwn_live_resample.h"
-#include "../../include/mbexwn_live_out.h"
-#include "../../include/mbexwn_flac.h"
-#include "../../include/mbexwn_noise.h"
-#include "../../include/mbexwn_warp.h"
-#include "../../include/mbexwn_pitch.h"
-#include "../../include/mbexwn_contour.h"
 #include "../../include/mbexwn_envelope.h"
-
-static_assert(MBXN_FILL_TILE == mbx::NOISE_TILE, "mbexwn_noise.h states the tile of noise_keyed.hip");
-static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
 
 using namespace mbx_host;
 
@@ -158,6 +147,29 @@ mbx_status mbx_host::calibrate_on_synthetic_mel(mbx_handle *hd, bool forms) {
         hipMemcpy(noise_dev, noise.data(), noise.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return release(fail(MBX_ERR_HIP, "calibration: device allocation / upload failed"));
     return release(calibrate_run(hd, mel_dev, nullptr, B, T, c.noise_sigma != 0.f ? noise_dev : nullptr, ws, ws_bytes, nullptr, 1, forms));
+}
+
+// mbx_conv1d and, precise, mbx_conv1d_f64acc: the way the launch sequence issues its mel-rate convolutions (large launches
+// take the LDS-staged tile kernel)
+static mbx_status conv1d_entry(mbx_handle *hd, const float *x, int32_t batch, int32_t n_rows, int32_t cin, const float *w,
+                               const float *b, const float *alpha, int32_t ks, int32_t cout, int32_t dilation, int32_t pad_l,
+                               int32_t pad_mode, float *y, void *hip_stream, bool precise) {
+    if (!hd || !x || !w || !y || batch <= 0 || n_rows <= 0 || cin <= 0 || cout <= 0 || ks <= 0 || dilation <= 0)
+        return fail(MBX_ERR_INVALID_ARGUMENT, "bad argument");
+    if (pad_mode < MBX_PAD_ZERO || pad_mode > MBX_PAD_EDGE) return fail(MBX_ERR_INVALID_ARGUMENT, "bad pad_mode");
+    if (precise && (cin % 4 || (reinterpret_cast<uintptr_t>(x) & 15)))
+        return fail(MBX_ERR_UNSUPPORTED, "the float64-accumulating convolution needs cin % 4 == 0 and a 16-byte aligned input");
+    DeviceGuard guard(hd->device);
+    DevTensor wt, bt;
+    wt.ptr = const_cast<float *>(w);
+    bt.ptr = const_cast<float *>(b);
+    mbx::ConvArgs a = conv_args(x, (long long)n_rows * cin, cin, nullptr, 1, n_rows, batch, &wt, b ? &bt : nullptr, ks,
+                                cin, cout, dilation, pad_l, pad_mode, y, (long long)n_rows * cout, cout);
+    a.alpha = alpha;
+    a.precise = precise ? 1 : 0;
+    if (!precise) a.zeros = hd->zeros;
+    mbx::launch_conv1d_group(&a, 1, static_cast<hipStream_t>(hip_stream));
+    return launch_status();
 }
 
 extern "C" {
@@ -344,8 +356,7 @@ mbx_status mbx_window_advance(mbx_handle *hd, float *mel_window, const float *me
     if (!mbx::launch_window_advance(mel_window, mel_new, noise_window, noise_new, batch, frames, step_frames,
                                     hd->cfg.mel_channels, hd->cfg.steps_per_frame, static_cast<hipStream_t>(hip_stream)))
         return fail(MBX_ERR_INVALID_ARGUMENT, "window advance: need 0 < step_frames <= frames and a window of at most 64 KB per item");
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return launch_status();
 }
 
 mbx_status mbx_clock_probe(mbx_handle *hd, uint64_t *device_out4, int64_t real_ticks, void *hip_stream) {
@@ -355,8 +366,7 @@ mbx_status mbx_clock_probe(mbx_handle *hd, uint64_t *device_out4, int64_t real_t
     if (!guard.ok) return fail(MBX_ERR_HIP, "cannot select the handle's device");
     mbx::launch_clock_probe(reinterpret_cast<unsigned long long *>(device_out4), (unsigned long long)real_ticks,
                             static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return launch_status();
 }
 
 mbx_status mbx_window_update(mbx_handle *hd, float *mel_window, const float *mel_new, float *noise_window,
@@ -369,8 +379,7 @@ mbx_status mbx_window_update(mbx_handle *hd, float *mel_window, const float *mel
     if (!mbx::launch_window_update(mel_window, mel_new, noise_window, noise_new, batch, window_frames, shift_frames, keep_frames,
                                    new_frames, hd->cfg.mel_channels, hd->cfg.steps_per_frame, static_cast<hipStream_t>(hip_stream)))
         return fail(MBX_ERR_INVALID_ARGUMENT, "window update: need shift + keep <= window, keep + new <= window and at most 64 KB kept per item");
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return launch_status();
 }
 
 mbx_status mbx_emit_rows(mbx_handle *hd, const float *audio, int64_t row_floats, int32_t batch, int64_t first, int64_t count,
@@ -381,334 +390,6 @@ mbx_status mbx_emit_rows(mbx_handle *hd, const float *audio, int64_t row_floats,
     if (!guard.ok) return fail(MBX_ERR_HIP, "cannot select the handle's device");
     HIP_TRY(hipMemcpy2DAsync(host_out, (size_t)count * sizeof(float), audio + first, (size_t)row_floats * sizeof(float),
                              (size_t)count * sizeof(float), (size_t)batch, hipMemcpyDeviceToHost, static_cast<hipStream_t>(hip_stream)));
-    return MBX_OK;
-}
-
-mbx_status mbx_mel_analysis(const float *audio, const int32_t *n_samples, int32_t batch, int32_t max_samples,
-                            int32_t win, int32_t hop, int32_t fft_size, int32_t n_mels, const float *window,
-                            const float *twiddle, const float *basis, const int32_t *bin_lo, const int32_t *bin_hi,
-                            float eps, float *out, int32_t max_frames, void *hip_stream) {
-    mbx::MelAnalysisArgs a{};
-    a.audio = audio;
-    a.audio_bstride = max_samples;
-    a.n_samples = n_samples;
-    a.max_samples = max_samples;
-    a.batch = batch;
-    a.win = win;
-    a.hop = hop;
-    a.fft_size = fft_size;
-    a.n_mels = n_mels;
-    a.window = window;
-    a.twiddle = twiddle;
-    a.basis = basis;
-    a.bin_lo = bin_lo;
-    a.bin_hi = bin_hi;
-    a.eps = eps;
-    a.out = out;
-    a.max_frames = max_frames;
-    if (!mbx::launch_mel_analysis(a, static_cast<hipStream_t>(hip_stream)))
-        return fail(MBX_ERR_INVALID_ARGUMENT, "mel analysis: sizes do not fit the kernel (fft_size a power of two <= 2048, "
-                                              "win <= fft_size, max_samples > win/2, max_frames >= max_samples/hop + 1)");
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxa_resample_poly(const float *audio, const int32_t *n_samples, int32_t batch, int32_t max_samples, int32_t up,
-                              int32_t down, const float *taps, int32_t n_taps, float *out, int32_t max_out, void *hip_stream) {
-    mbx::ResampleArgs a{};
-    a.audio = audio;
-    a.n_samples = n_samples;
-    a.batch = batch;
-    a.max_samples = max_samples;
-    a.up = up;
-    a.down = down;
-    a.taps = taps;
-    a.n_taps = n_taps;
-    a.out = out;
-    a.max_out = max_out;
-    if (const char *why = mbx::check_resample_poly(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("resample poly: ") + why);
-    mbx::launch_resample_poly(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxl_ring_append(const float *packed, int64_t packed_samples, const int64_t *desc, int32_t n_streams,
-                            int32_t max_count, float *rings, int32_t n_slots, int32_t ring_samples, void *hip_stream) {
-    mbx::RingAppendArgs a{};
-    a.packed = packed;
-    a.packed_samples = packed_samples;
-    a.desc = reinterpret_cast<const long long *>(desc);
-    a.n_streams = n_streams;
-    a.max_count = max_count;
-    a.rings = rings;
-    a.n_slots = n_slots;
-    a.ring_samples = ring_samples;
-    if (const char *why = mbx::check_ring_append(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("ring append: ") + why);
-    mbx::launch_ring_append(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxl_mel_frames(const float *rings, int32_t n_slots, int32_t ring_samples, const int64_t *desc, int32_t n_streams,
-                           int32_t max_new_frames, int32_t win, int32_t hop, int32_t fft_size, int32_t n_mels,
-                           const float *window, const float *twiddle, const float *basis, const int32_t *bin_lo,
-                           const int32_t *bin_hi, float eps, float *out, void *hip_stream) {
-    mbx::MelStreamArgs a{};
-    a.rings = rings;
-    a.n_slots = n_slots;
-    a.ring_samples = ring_samples;
-    a.desc = reinterpret_cast<const long long *>(desc);
-    a.n_streams = n_streams;
-    a.max_new_frames = max_new_frames;
-    a.win = win;
-    a.hop = hop;
-    a.fft_size = fft_size;
-    a.n_mels = n_mels;
-    a.window = window;
-    a.twiddle = twiddle;
-    a.basis = basis;
-    a.bin_lo = bin_lo;
-    a.bin_hi = bin_hi;
-    a.eps = eps;
-    a.out = out;
-    if (const char *why = mbx::check_mel_stream(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("mel frames: ") + why);
-    mbx::launch_mel_stream(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxr_resample_rings(const float *in_rings, int32_t n_in_slots, int32_t in_ring_samples, const int64_t *desc,
-                               int32_t n_rows, int32_t max_new_out, int32_t up, int32_t down, const float *taps, int32_t n_taps,
-                               float *out_rings, int32_t n_out_slots, int32_t out_ring_samples, void *hip_stream) {
-    mbx::ResampleStreamArgs a{};
-    a.in_rings = in_rings;
-    a.n_in_slots = n_in_slots;
-    a.in_ring_samples = in_ring_samples;
-    a.desc = reinterpret_cast<const long long *>(desc);
-    a.n_rows = n_rows;
-    a.max_new_out = max_new_out;
-    a.up = up;
-    a.down = down;
-    a.taps = taps;
-    a.n_taps = n_taps;
-    a.out_rings = out_rings;
-    a.n_out_slots = n_out_slots;
-    a.out_ring_samples = out_ring_samples;
-    if (const char *why = mbx::check_resample_stream(a))
-        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("resample rings: ") + why);
-    mbx::launch_resample_stream(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxo_resample_emit(const float *in_rings, int32_t n_in_slots, int32_t in_ring_samples, const int64_t *desc,
-                              int32_t n_rows, int32_t max_new_out, int32_t up, int32_t down, const float *taps, int32_t n_taps,
-                              float *out, int64_t out_floats, void *hip_stream) {
-    mbx::ResampleEmitArgs a{};
-    a.in_rings = in_rings;
-    a.n_in_slots = n_in_slots;
-    a.in_ring_samples = in_ring_samples;
-    a.desc = reinterpret_cast<const long long *>(desc);
-    a.n_rows = n_rows;
-    a.max_new_out = max_new_out;
-    a.up = up;
-    a.down = down;
-    a.taps = taps;
-    a.n_taps = n_taps;
-    a.out = out;
-    a.out_floats = out_floats;
-    if (const char *why = mbx::check_resample_emit(a))
-        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("resample emit: ") + why);
-    mbx::launch_resample_emit(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbx_encode_flac16(const float *audio, int64_t stride, int32_t batch, const int64_t *n_samples, int32_t sample_rate,
-                             const uint16_t *crc_tables, uint8_t *out, int64_t out_bytes, float *max_abs, void *hip_stream) {
-    if (const char *why = mbx::check_flac_frames(audio, stride, batch, n_samples, sample_rate, crc_tables, out, out_bytes,
-                                                 max_abs))
-        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("encode flac16: ") + why);
-    if (batch == 0) return MBX_OK;
-    const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    HIP_TRY(hipMemsetAsync(max_abs, 0, (size_t)batch * sizeof(float), stream));
-    mbx::launch_flac_frames(audio, stride, batch, n_samples, sample_rate, crc_tables, out, max_abs, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxf_encode_flac16_fixed(const float *audio, int64_t stride, int32_t batch, const int64_t *n_samples,
-                                    int32_t sample_rate, const uint16_t *crc_tables, uint8_t *out, int64_t out_bytes,
-                                    int32_t *frame_bytes, int64_t *workspace, int16_t *pcm_out, float *max_abs, void *hip_stream) {
-    if (const char *why = mbx::check_flac_fixed(audio, stride, batch, n_samples, sample_rate, crc_tables, out, out_bytes,
-                                                frame_bytes, workspace, max_abs))
-        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("encode flac16 fixed: ") + why);
-    if (batch == 0) return MBX_OK;
-    const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    HIP_TRY(hipMemsetAsync(max_abs, 0, (size_t)batch * sizeof(float), stream));
-    mbx::launch_flac_fixed(audio, stride, batch, n_samples, sample_rate, crc_tables, out, frame_bytes, workspace, pcm_out,
-                           max_abs, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxn_fill_normal(float *out, int64_t stride, int32_t batch, const uint64_t *keys, const int64_t *first_step,
-                            const int32_t *counts, int32_t max_count, void *hip_stream) {
-    mbx::NoiseArgs a{};
-    a.out = out;
-    a.stride = stride;
-    a.batch = batch;
-    a.keys = keys;
-    a.first_step = first_step;
-    a.counts = counts;
-    a.max_count = max_count;
-    if (const char *why = mbx::check_fill_normal(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("fill normal: ") + why);
-    if (batch == 0 || max_count == 0) return MBX_OK;
-    mbx::launch_fill_normal(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxw_mel_frames_at(const float *audio, int64_t stride, int32_t batch, const int32_t *n_samples,
-                              const int64_t *centres, const int32_t *n_frames, int32_t max_frames, int32_t win,
-                              int32_t fft_size, int32_t n_mels, const float *window, const float *twiddle, const float *basis,
-                              const int32_t *bin_lo, const int32_t *bin_hi, float eps, float *out, void *hip_stream) {
-    mbx::MelWarpArgs a{};
-    a.audio = audio;
-    a.stride = stride;
-    a.batch = batch;
-    a.n_samples = n_samples;
-    a.centres = centres;
-    a.n_frames = n_frames;
-    a.max_frames = max_frames;
-    a.win = win;
-    a.fft_size = fft_size;
-    a.n_mels = n_mels;
-    a.window = window;
-    a.twiddle = twiddle;
-    a.basis = basis;
-    a.bin_lo = bin_lo;
-    a.bin_hi = bin_hi;
-    a.eps = eps;
-    a.out = out;
-    if (const char *why = mbx::check_mel_warp(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("mel frames at: ") + why);
-    if (batch == 0) return MBX_OK;
-    mbx::launch_mel_warp(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxe_warp_envelope(const float *mel, int64_t row_stride_items, int32_t batch, const int32_t *n_frames,
-                              int32_t max_frames, int32_t n_mels, const float *centres, const float *factors, float *out,
-                              void *hip_stream) {
-    mbx::EnvelopeArgs a{};
-    a.mel = mel;
-    a.bstride = row_stride_items;
-    a.batch = batch;
-    a.n_frames = n_frames;
-    a.max_frames = max_frames;
-    a.n_mels = n_mels;
-    a.centres = centres;
-    a.factors = factors;
-    a.out = out;
-    if (const char *why = mbx::check_envelope(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("warp envelope: ") + why);
-    if (batch == 0) return MBX_OK;
-    mbx::launch_envelope(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxp_track_f0(const float *audio, int64_t stride, int32_t batch, const int32_t *n_samples,
-                         const int64_t *centres, const int32_t *n_frames, int32_t max_frames, int32_t sample_rate,
-                         int32_t window, int32_t tau_min, int32_t tau_max, float threshold, float e_min, float *f0,
-                         float *periodicity, void *hip_stream) {
-    mbx::PitchArgs a{};
-    a.audio = audio;
-    a.stride = stride;
-    a.batch = batch;
-    a.n_samples = n_samples;
-    a.centres = centres;
-    a.n_frames = n_frames;
-    a.max_frames = max_frames;
-    a.sample_rate = sample_rate;
-    a.window = window;
-    a.tau_min = tau_min;
-    a.tau_max = tau_max;
-    a.threshold = threshold;
-    a.e_min = e_min;
-    a.f0 = f0;
-    a.periodicity = periodicity;
-    if (const char *why = mbx::check_track_f0(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("track f0: ") + why);
-    if (batch == 0) return MBX_OK;
-    mbx::launch_track_f0(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxc_f0_candidates(const float *audio, int64_t stride, int32_t batch, const int32_t *n_samples,
-                              const int64_t *centres, const int32_t *n_frames, int32_t max_frames, int32_t sample_rate,
-                              int32_t window, int32_t tau_min, int32_t tau_max, float e_min, const float *thresholds,
-                              const float *weights, int32_t n_thresholds, int32_t n_cand, float *period, float *cost,
-                              float *dprime, void *hip_stream) {
-    mbx::CandidateArgs a{};
-    a.frame.audio = audio;
-    a.frame.stride = stride;
-    a.frame.batch = batch;
-    a.frame.n_samples = n_samples;
-    a.frame.centres = centres;
-    a.frame.n_frames = n_frames;
-    a.frame.max_frames = max_frames;
-    a.frame.sample_rate = sample_rate;
-    a.frame.window = window;
-    a.frame.tau_min = tau_min;
-    a.frame.tau_max = tau_max;
-    a.frame.e_min = e_min;
-    a.n_thresholds = n_thresholds;
-    a.n_cand = n_cand;
-    a.period = period;
-    a.cost = cost;
-    a.dprime = dprime;
-    if (const char *why = mbx::fill_f0_candidates(a, thresholds, weights))
-        return fail(MBX_ERR_INVALID_ARGUMENT, std::string("f0 candidates: ") + why);
-    if (batch == 0) return MBX_OK;
-    mbx::launch_f0_candidates(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return MBX_OK;
-}
-
-mbx_status mbxc_decode_f0(const float *period, const float *cost, const float *dprime, const int32_t *n_frames,
-                          int32_t max_frames, int32_t batch, int32_t sample_rate, float w_jump, float w_switch, float *f0,
-                          float *periodicity, void *hip_stream) {
-    mbx::DecodeArgs a{};
-    a.period = period;
-    a.cost = cost;
-    a.dprime = dprime;
-    a.n_frames = n_frames;
-    a.max_frames = max_frames;
-    a.batch = batch;
-    a.sample_rate = sample_rate;
-    a.w_jump = w_jump;
-    a.w_switch = w_switch;
-    a.f0 = f0;
-    a.periodicity = periodicity;
-    if (const char *why = mbx::check_decode_f0(a)) return fail(MBX_ERR_INVALID_ARGUMENT, std::string("decode f0: ") + why);
-    if (batch == 0) return MBX_OK;
-    mbx::launch_decode_f0(a, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MBX_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return MBX_OK;
 }
 
@@ -776,49 +457,19 @@ mbx_status mbx_pqmf_synthesis(mbx_handle *hd, const float *x, int32_t batch, int
     const int M = hd->cfg.subbands;
     mbx::launch_pqmf(x, (long long)n_steps * M, nullptr, 1, n_steps, batch, M, hd->poly, hd->poly_t, hd->poly_ndm,
                      hd->poly_dm_min, y, (long long)n_steps * M, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return launch_status();
 }
 
 mbx_status mbx_conv1d(mbx_handle *hd, const float *x, int32_t batch, int32_t n_rows, int32_t cin, const float *w,
                       const float *b, const float *alpha, int32_t ks, int32_t cout, int32_t dilation, int32_t pad_l,
                       int32_t pad_mode, float *y, void *hip_stream) {
-    if (!hd || !x || !w || !y || batch <= 0 || n_rows <= 0 || cin <= 0 || cout <= 0 || ks <= 0 || dilation <= 0)
-        return fail(MBX_ERR_INVALID_ARGUMENT, "bad argument");
-    if (pad_mode < MBX_PAD_ZERO || pad_mode > MBX_PAD_EDGE) return fail(MBX_ERR_INVALID_ARGUMENT, "bad pad_mode");
-    DeviceGuard guard(hd->device);
-    DevTensor wt, bt;
-    wt.ptr = const_cast<float *>(w);
-    bt.ptr = const_cast<float *>(b);
-    mbx::ConvArgs a = conv_args(x, (long long)n_rows * cin, cin, nullptr, 1, n_rows, batch, &wt, b ? &bt : nullptr, ks,
-                                cin, cout, dilation, pad_l, pad_mode, y, (long long)n_rows * cout, cout);
-    a.alpha = alpha;
-    a.zeros = hd->zeros;
-    // the way the launch sequence issues its mel-rate convolutions: large launches take the LDS-staged tile kernel
-    mbx::launch_conv1d_group(&a, 1, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return conv1d_entry(hd, x, batch, n_rows, cin, w, b, alpha, ks, cout, dilation, pad_l, pad_mode, y, hip_stream, false);
 }
 
 mbx_status mbx_conv1d_f64acc(mbx_handle *hd, const float *x, int32_t batch, int32_t n_rows, int32_t cin, const float *w,
                              const float *b, const float *alpha, int32_t ks, int32_t cout, int32_t dilation, int32_t pad_l,
                              int32_t pad_mode, float *y, void *hip_stream) {
-    if (!hd || !x || !w || !y || batch <= 0 || n_rows <= 0 || cin <= 0 || cout <= 0 || ks <= 0 || dilation <= 0)
-        return fail(MBX_ERR_INVALID_ARGUMENT, "bad argument");
-    if (pad_mode < MBX_PAD_ZERO || pad_mode > MBX_PAD_EDGE) return fail(MBX_ERR_INVALID_ARGUMENT, "bad pad_mode");
-    if (cin % 4 || (reinterpret_cast<uintptr_t>(x) & 15))
-        return fail(MBX_ERR_UNSUPPORTED, "the float64-accumulating convolution needs cin % 4 == 0 and a 16-byte aligned input");
-    DeviceGuard guard(hd->device);
-    DevTensor wt, bt;
-    wt.ptr = const_cast<float *>(w);
-    bt.ptr = const_cast<float *>(b);
-    mbx::ConvArgs a = conv_args(x, (long long)n_rows * cin, cin, nullptr, 1, n_rows, batch, &wt, b ? &bt : nullptr, ks,
-                                cin, cout, dilation, pad_l, pad_mode, y, (long long)n_rows * cout, cout);
-    a.alpha = alpha;
-    a.precise = 1;
-    mbx::launch_conv1d_group(&a, 1, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return conv1d_entry(hd, x, batch, n_rows, cin, w, b, alpha, ks, cout, dilation, pad_l, pad_mode, y, hip_stream, true);
 }
 
 mbx_status mbx_lin_interp(mbx_handle *hd, const float *x, int32_t batch, int32_t n_rows, int32_t channels, int32_t up,
@@ -830,8 +481,7 @@ mbx_status mbx_lin_interp(mbx_handle *hd, const float *x, int32_t batch, int32_t
     mbx::launch_lin_interp(x, (long long)n_rows * channels, nullptr, 1, n_rows, batch, channels, up, it->second.first,
                            it->second.second, MBX_ACT_LINEAR, 1.f, 0.f, y, (long long)n_rows * up * channels,
                            static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return launch_status();
 }
 
 mbx_status mbx_wavetable(mbx_handle *hd, const float *f0, int32_t batch, int32_t n, float *pulse, float *phase,
@@ -842,8 +492,7 @@ mbx_status mbx_wavetable(mbx_handle *hd, const float *f0, int32_t batch, int32_t
     float *chunk_last = scratch + (size_t)batch * n;
     mbx::launch_wavetable(wavetable_consts(hd), f0, n, nullptr, 1, n, batch, pulse, phase, cum, chunk_last, nullptr,
                           nullptr, static_cast<hipStream_t>(hip_stream));
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return launch_status();
 }
 
 mbx_status mbx_norm_mel(mbx_handle *hd, const float *mel, const int32_t *n_frames, int32_t batch, int32_t frames,
@@ -859,8 +508,7 @@ mbx_status mbx_norm_mel(mbx_handle *hd, const float *mel, const int32_t *n_frame
                                             scratch + (size_t)batch * frames, mel_out, stream);
     if (gain)
         mbx::launch_norm_mel_gain(k, src, n_frames, frames, batch, gain, (long long)frames * c.hop_size, true, stream);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return launch_status();
 }
 
 mbx_status mbx_stft_filter(mbx_handle *hd, const float *excitation, const float *cepstrum, const int32_t *ceps_index,
@@ -875,8 +523,7 @@ mbx_status mbx_stft_filter(mbx_handle *hd, const float *excitation, const float 
                             c.n_ceps_windows ? ceps_index : nullptr, nullptr, 0, nullptr, nullptr, frames, batch, scratch,
                             stream);
     mbx::launch_overlap_add(sc, scratch, nullptr, frames, frames, batch, audio, (long long)frames * c.hop_size, stream);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, hipGetErrorString(e));
+    return launch_status();
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // The engine's handle and what mbx_create.hip, mbx_forward.hip and mbx_api.hip share: the last-error string, the uploaded
 // tensors and the records that resolve them once (mbx_create), workspace carving, the argument builders of the launch
-// sequence.  Internal: the C ABI is include/mbexwn.h.
+// sequence.  mbx_stages.hip, whose entry points take no handle, includes it for fail, launch_status and HIP_TRY alone.
+// Internal: the C ABI is include/mbexwn.h and the ten headers beside it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,6 +26,12 @@ inline thread_local std::string g_last_error;
 inline mbx_status fail(mbx_status st, const std::string &msg) {
     g_last_error = msg;
     return st;
+}
+
+// the end of an entry point that only enqueued kernels: the launch error, if there is one, behind `prefix`
+inline mbx_status launch_status(const char *prefix = "") {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MBX_OK : fail(MBX_ERR_HIP, std::string(prefix) + hipGetErrorString(e));
 }
 
 #define HIP_TRY(expr)                                                                                  \

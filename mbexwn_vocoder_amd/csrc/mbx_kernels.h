@@ -1,4 +1,4 @@
-// Internal launch interface between the C ABI (mbx_create.hip, mbx_forward.hip, mbx_api.hip) and the gfx950 kernels.
+// Internal launch interface between the C ABI (mbx_create.hip, mbx_forward.hip, mbx_api.hip, mbx_stages.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

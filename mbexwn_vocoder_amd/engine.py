@@ -1,4 +1,4 @@
-"""ctypes binding of the HIP engine (include/mbexwn.h) and its host-side driver.
+"""Host-side driver of the HIP engine (include/mbexwn.h) on top of its ctypes binding, abi.py.
 
 ``MBExWNEngine`` plays the role of the reference's Keras model object: it is what
 ``MELInverter.model`` holds and what ``model.infer(mell, synth_length=...)`` is called on
@@ -14,293 +14,24 @@ import os
 import numpy as np
 
 from . import tables as tb
-from .build import LIB_PATH
+# the binding itself (structures, constants, the function table, load_library) is abi.py; its names stay importable from here
+from .abi import (CONV_FORMS, GATE_KERNEL_NAMES, MBX_ABI_VERSION, MBX_MAX_PRECOND, MBX_MAX_SUBNET_OPS,  # noqa: F401
+                  MBX_MAX_WN_BLOCKS, MBX_MAX_WN_LAYERS, MBX_NAME_LEN, RESSKIP_KERNEL_NAMES, TAIL_KERNEL_NAMES, _check,
+                  load_library, mbx_config, mbx_conv_form_info, mbx_forward_options, mbx_kernel_report_info, mbx_plan_info,
+                  mbx_subnet_op, mbx_tensor, symbols)
+from .build import LIB_PATH  # noqa: F401
 from .config import ModelDims
 from .subnet import build_subnet
 from .weights import fold_weights, merge_channel_groups
 
-MBX_ABI_VERSION = 11
-MBX_MAX_SUBNET_OPS = 32
-MBX_MAX_WN_LAYERS = 64
-MBX_MAX_PRECOND = 8
-MBX_MAX_WN_BLOCKS = 4
-MBX_NAME_LEN = 64
+# what the build hook checks in the library: the functions of include/mbexwn.h and include/mbexwn_audio.h (abi.TABLE)
+EXPORTED_SYMBOLS = symbols("mbexwn.h")
+AUDIO_SYMBOLS = symbols("mbexwn_audio.h")
+
+_CONV_FORM_NAMES = {vv: kk for kk, vv in CONV_FORMS.items()}
 
 _OP_KIND = {"conv": 0, "lin": 1, "prelu": 2, "leaky": 3, "act": 4}
 _ACT = {"linear": 0, "soft_sigmoid": 1, "tanh": 2, "sigmoid": 3, "soft_sign": 4, "soft_sqrt": 5, "exp": 6, "relu": 7}
-
-
-class mbx_subnet_op(ctypes.Structure):
-    _fields_ = [("kind", ctypes.c_int32), ("ks", ctypes.c_int32), ("cin", ctypes.c_int32), ("cout", ctypes.c_int32),
-                ("pad_l", ctypes.c_int32), ("pad_r", ctypes.c_int32), ("pad_mode", ctypes.c_int32),
-                ("up", ctypes.c_int32), ("act", ctypes.c_int32), ("alpha", ctypes.c_float),
-                ("name", ctypes.c_char * MBX_NAME_LEN)]
-
-
-class mbx_config(ctypes.Structure):
-    _fields_ = [("struct_size", ctypes.c_int32), ("abi_version", ctypes.c_int32),
-                ("sample_rate", ctypes.c_int32), ("hop_size", ctypes.c_int32), ("mel_channels", ctypes.c_int32),
-                ("subbands", ctypes.c_int32), ("pqmf_taps", ctypes.c_int32),
-                ("pulse_channels", ctypes.c_int32), ("pulse_per_frame", ctypes.c_int32),
-                ("steps_per_frame", ctypes.c_int32),
-                ("pulse_rate", ctypes.c_float), ("noise_sigma", ctypes.c_float),
-                ("f0_min", ctypes.c_float), ("f0_max", ctypes.c_float),
-                ("wn_channels", ctypes.c_int32), ("wn_layers", ctypes.c_int32), ("wn_kernel_size", ctypes.c_int32),
-                ("wn_out_channels", ctypes.c_int32), ("wn_in_channels", ctypes.c_int32),
-                ("wn_dilations", ctypes.c_int32 * MBX_MAX_WN_LAYERS),
-                ("cond_kernel_size", ctypes.c_int32), ("cond_conv_upsampling", ctypes.c_int32),
-                ("cond_lin_upsampling", ctypes.c_int32),
-                ("stft_win", ctypes.c_int32), ("fft_size", ctypes.c_int32), ("n_ceps", ctypes.c_int32),
-                ("n_ceps_windows", ctypes.c_int32), ("filter_max_log_range", ctypes.c_float),
-                ("wt_n_period", ctypes.c_int32), ("wt_n_tables", ctypes.c_int32),
-                ("wt_nominal_f0", ctypes.c_float), ("wt_min_transposition", ctypes.c_float),
-                ("wt_max_transposition", ctypes.c_float), ("wt_grid_norm", ctypes.c_float),
-                ("phase_chunk", ctypes.c_int32),
-                ("n_f0_ops", ctypes.c_int32), ("f0_ops", mbx_subnet_op * MBX_MAX_SUBNET_OPS),
-                ("n_vtf_ops", ctypes.c_int32), ("vtf_ops", mbx_subnet_op * MBX_MAX_SUBNET_OPS),
-                ("nm_iters", ctypes.c_int32), ("nm_smooth_win", ctypes.c_int32), ("nm_use_compressor", ctypes.c_int32),
-                ("nm_use_max_limit", ctypes.c_int32), ("nm_rms_norm_fact", ctypes.c_float),
-                ("nm_rms_floor", ctypes.c_float), ("nm_compressor_exp", ctypes.c_float),
-                ("nm_lin_amp_scale", ctypes.c_float), ("nm_lin_amp_off", ctypes.c_float),
-                ("nm_mel_amp_scale", ctypes.c_float), ("wn_gate_activation", ctypes.c_int32),
-                ("wn_disable_conditioning", ctypes.c_int32), ("n_precond", ctypes.c_int32),
-                ("precond_channels", ctypes.c_int32 * MBX_MAX_PRECOND), ("spect_preserve_energy", ctypes.c_int32),
-                ("wt_subharm_channels", ctypes.c_int32), ("wt_sinusoid_as_fun", ctypes.c_int32),
-                ("ps_off", ctypes.c_int32), ("no_pqmf", ctypes.c_int32), ("n_wn_blocks", ctypes.c_int32),
-                ("wn_block_channels", ctypes.c_int32 * MBX_MAX_WN_BLOCKS), ("wn_block_ups", ctypes.c_int32 * MBX_MAX_WN_BLOCKS),
-                ("pulse_pqmf_taps", ctypes.c_int32), ("ps_subband_gain", ctypes.c_int32),
-                ("wn_causal", ctypes.c_int32),
-                ("wn_conv_form", ctypes.c_int32), ("batch_invariant", ctypes.c_int32), ("wn_keep_skip", ctypes.c_int32),
-                ("wn_keep_start", ctypes.c_int32), ("calib_fraction", ctypes.c_float), ("tune_gate_shape", ctypes.c_int32),
-                ("tune_resskip_wave_tiles", ctypes.c_int32), ("tune_resskip_split", ctypes.c_int32),
-                ("nm_use_pinv", ctypes.c_int32), ("nm_win_norm", ctypes.c_float), ("wn_precision", ctypes.c_int32),
-                ("f0_accumulate", ctypes.c_int32)]
-
-
-class mbx_conv_form_info(ctypes.Structure):
-    _fields_ = [("struct_size", ctypes.c_int32), ("requested", ctypes.c_int32), ("form", ctypes.c_int32),
-                ("stream_form", ctypes.c_int32), ("calibrated", ctypes.c_int32), ("batch_invariant", ctypes.c_int32),
-                ("fold_skip", ctypes.c_int32), ("fold_start", ctypes.c_int32), ("split_f16_layers", ctypes.c_int32),
-                ("split_f16_gate_layers", ctypes.c_int32), ("err_f43", ctypes.c_float),
-                ("err_f23", ctypes.c_float), ("ref_max", ctypes.c_float), ("threshold", ctypes.c_float),
-                ("err_split", ctypes.c_float), ("split_rejected", ctypes.c_int32), ("f0_float64_chain", ctypes.c_int32),
-                ("n_gate_layers", ctypes.c_int32), ("gate_kernel", ctypes.c_int32 * MBX_MAX_WN_LAYERS)]
-
-
-GATE_KERNEL_NAMES = {0: "none", 1: "direct", 2: "f23", 3: "f43", 4: "f43_psplit", 5: "f43_hsplit", 6: "f43_strided",
-                     7: "f43_strided_psplit", 8: "folded_start", 9: "split_f16", 10: "split_f16_wide",
-                     11: "split_f16_f32h"}
-
-
-class mbx_kernel_report_info(ctypes.Structure):
-    _fields_ = [("struct_size", ctypes.c_int32), ("n_resskip_layers", ctypes.c_int32),
-                ("resskip_kernel", ctypes.c_int32 * MBX_MAX_WN_LAYERS), ("tail_kernel", ctypes.c_int32),
-                ("tail_folded", ctypes.c_int32), ("gate_block_channels", ctypes.c_int32 * MBX_MAX_WN_LAYERS)]
-
-
-class mbx_plan_info(ctypes.Structure):
-    _fields_ = [("struct_size", ctypes.c_int32), ("n_layers", ctypes.c_int32),
-                ("gate_kernel", ctypes.c_int32 * MBX_MAX_WN_LAYERS), ("gate_kernel_f32", ctypes.c_int32 * MBX_MAX_WN_LAYERS),
-                ("gate_block_channels", ctypes.c_int32 * MBX_MAX_WN_LAYERS), ("resskip_kernel", ctypes.c_int32 * MBX_MAX_WN_LAYERS),
-                ("tail_kernel", ctypes.c_int32), ("tail_folded", ctypes.c_int32), ("planes_only", ctypes.c_int32)]
-
-
-# MBX_RESSKIP_K_* / MBX_TAIL_K_* of include/mbexwn.h (mbx_kernel_report)
-RESSKIP_KERNEL_NAMES = {0: "none", 1: "conv1d", 2: "packed64", 3: "packed128", 4: "wide11_res10", 5: "wide11", 6: "wide6x2",
-                        7: "wave11", 8: "wave12", 9: "wave6x2", 10: "wave4x3", 11: "split_f16"}
-TAIL_KERNEL_NAMES = {0: "none", 1: "unfused", 2: "tail2_nj4", 3: "tail2_nj8", 4: "tail2_nj12", 5: "tail2_nj20", 6: "tail2_nj22",
-                     7: "tail"}
-
-
-CONV_FORMS = {"auto": 0, "direct": 1, "f23": 2, "f43": 3}
-_CONV_FORM_NAMES = {vv: kk for kk, vv in CONV_FORMS.items()}
-
-
-class mbx_forward_options(ctypes.Structure):
-    _fields_ = [("struct_size", ctypes.c_int32), ("transposition", ctypes.c_float), ("f0", ctypes.c_void_p),
-                ("state_in", ctypes.c_void_p), ("state_out", ctypes.c_void_p), ("active_begin", ctypes.c_int32),
-                ("active_frames", ctypes.c_void_p), ("wn_begin", ctypes.c_int32), ("wn_frames", ctypes.c_void_p),
-                ("active_max_frames", ctypes.c_int32), ("wn_max_frames", ctypes.c_int32), ("sub_store", ctypes.c_void_p), ("sub_store_rows", ctypes.c_int32), ("sub_carry", ctypes.c_void_p),
-                ("layer_store", ctypes.c_void_p), ("layer_store_floats", ctypes.c_int32), ("layer_carry", ctypes.c_void_p),
-                ("layer_rows", ctypes.c_int32), ("fe_store", ctypes.c_void_p), ("fe_ring_frames", ctypes.c_int32),
-                ("fe_pos", ctypes.c_void_p), ("fe_new_frames", ctypes.c_int32), ("fe_margin_frames", ctypes.c_int32),
-                ("fe_end_frames", ctypes.c_int32),
-                # per-frame pitch control; struct_size may also be the offset of f0_frames (all three NULL)
-                ("f0_frames", ctypes.c_void_p), ("f0_scale", ctypes.c_void_p), ("f0_item_mask", ctypes.c_void_p)]
-
-
-class mbx_tensor(ctypes.Structure):
-    _fields_ = [("name", ctypes.c_char_p), ("data", ctypes.POINTER(ctypes.c_float)), ("ndim", ctypes.c_int32),
-                ("shape", ctypes.c_int64 * 4)]
-
-
-_STATUS_EXC = {1: ValueError, 2: RuntimeError, 3: RuntimeError, 4: NotImplementedError}
-
-_lib = None
-
-
-def load_library():
-    """Load libmbexwn_hip.so (built in-tree by mbexwn_vocoder_amd.build). Fails loudly when absent."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # PyTorch must be loaded first: the engine works on torch's device pointers and streams, so both have to
-    # live in ONE HIP runtime instance (torch bundles libamdhip64.so.7; loading ours first would give the
-    # process a second, separate runtime).
-    import torch  # noqa: F401
-    # MBX_LIB_PATH: another build of the same library (kernel experiments, scripts/experiments/, whose ablated kernels
-    # produce wrong audio on purpose) -- never a fallback; said on stderr so that a stale variable cannot go unnoticed
-    path = os.environ.get("MBX_LIB_PATH") or LIB_PATH
-    if path != LIB_PATH:
-        import sys
-        print(f"mbexwn_vocoder_amd: MBX_LIB_PATH overrides the product library: loading {path}", file=sys.stderr)
-    if not os.path.exists(path):
-        raise RuntimeError(f"HIP extension {path} is missing: run `python -m mbexwn_vocoder_amd.build` "
-                           "(there is no CPU fallback for the mel-inversion path)")
-    lib = ctypes.CDLL(path)
-    vp, i32, i64p, fp = ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p
-    lib.mbx_last_error.restype = ctypes.c_char_p
-    lib.mbx_last_error.argtypes = []
-    lib.mbx_create.restype = i32
-    lib.mbx_create.argtypes = [ctypes.POINTER(mbx_config), ctypes.POINTER(mbx_tensor), i32, i32,
-                               ctypes.POINTER(ctypes.c_void_p)]
-    lib.mbx_destroy.restype = i32
-    lib.mbx_destroy.argtypes = [vp]
-    lib.mbx_conv_form.restype = i32
-    lib.mbx_conv_form.argtypes = [vp, ctypes.POINTER(mbx_conv_form_info)]
-    lib.mbx_kernel_report.restype = i32
-    lib.mbx_kernel_report.argtypes = [vp, ctypes.POINTER(mbx_kernel_report_info)]
-    lib.mbx_plan.restype = i32
-    lib.mbx_plan.argtypes = [vp, i32, i32, ctypes.POINTER(mbx_plan_info)]
-    lib.mbx_calibrate.restype = i32
-    lib.mbx_calibrate.argtypes = [vp, fp, vp, i32, i32, fp, vp, ctypes.c_size_t, vp]
-    lib.mbx_workspace_size.restype = ctypes.c_size_t
-    lib.mbx_workspace_size.argtypes = [vp, i32, i32]
-    lib.mbx_forward.restype = i32
-    lib.mbx_forward.argtypes = [vp, fp, vp, i32, i32, fp, fp, vp, ctypes.c_size_t, vp]
-    lib.mbx_forward_stream.restype = i32
-    lib.mbx_forward_stream.argtypes = [vp, fp, vp, i32, i32, fp, fp, vp, ctypes.c_size_t, vp, vp, vp]
-    lib.mbx_forward_ex.restype = i32
-    lib.mbx_forward_ex.argtypes = [vp, fp, vp, i32, i32, fp, fp, vp, ctypes.c_size_t,
-                                   ctypes.POINTER(mbx_forward_options), vp]
-    lib.mbx_layer_state_info.restype = i32
-    lib.mbx_layer_state_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    lib.mbx_window_advance.restype = i32
-    lib.mbx_window_advance.argtypes = [vp, fp, fp, fp, fp, i32, i32, i32, vp]
-    lib.mbx_clock_probe.restype = i32
-    lib.mbx_clock_probe.argtypes = [vp, vp, ctypes.c_int64, vp]
-    lib.mbx_window_update.restype = i32
-    lib.mbx_window_update.argtypes = [vp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]
-    lib.mbx_emit_rows.restype = i32
-    lib.mbx_emit_rows.argtypes = [vp, fp, ctypes.c_int64, i32, ctypes.c_int64, ctypes.c_int64, fp, vp]
-    lib.mbx_stage.restype = i32
-    lib.mbx_stage.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), i64p, i64p]
-    lib.mbx_profile_enable.restype = i32
-    lib.mbx_profile_enable.argtypes = [vp, i32]
-    lib.mbx_profile_read.restype = i32
-    lib.mbx_profile_read.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), i64p]
-    lib.mbx_profile_read_launches.restype = i32
-    lib.mbx_profile_read_launches.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int64, i64p]
-    lib.mbx_pqmf_synthesis.restype = i32
-    lib.mbx_pqmf_synthesis.argtypes = [vp, fp, i32, i32, fp, vp]
-    lib.mbx_conv1d.restype = i32
-    lib.mbx_conv1d.argtypes = [vp, fp, i32, i32, i32, fp, fp, fp, i32, i32, i32, i32, i32, fp, vp]
-    lib.mbx_conv1d_f64acc.restype = i32
-    lib.mbx_conv1d_f64acc.argtypes = [vp, fp, i32, i32, i32, fp, fp, fp, i32, i32, i32, i32, i32, fp, vp]
-    lib.mbx_lin_interp.restype = i32
-    lib.mbx_lin_interp.argtypes = [vp, fp, i32, i32, i32, i32, fp, vp]
-    lib.mbx_wavetable.restype = i32
-    lib.mbx_wavetable.argtypes = [vp, fp, i32, i32, fp, fp, fp, vp]
-    lib.mbx_stft_filter.restype = i32
-    lib.mbx_stft_filter.argtypes = [vp, fp, fp, vp, i32, i32, fp, fp, vp]
-    lib.mbx_norm_mel.restype = i32
-    lib.mbx_norm_mel.argtypes = [vp, fp, vp, i32, i32, fp, fp, fp, vp]
-    lib.mbx_mel_analysis.restype = i32
-    lib.mbx_mel_analysis.argtypes = [fp, vp, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp, vp, ctypes.c_float, fp, i32, vp]
-    lib.mbx_encode_flac16.restype = i32
-    lib.mbx_encode_flac16.argtypes = [fp, ctypes.c_int64, i32, i64p, i32, vp, vp, ctypes.c_int64, fp, vp]
-    # include/mbexwn_audio.h (AUDIO_SYMBOLS)
-    lib.mbxa_resample_poly.restype = i32
-    lib.mbxa_resample_poly.argtypes = [fp, vp, i32, i32, i32, i32, fp, i32, fp, i32, vp]
-    # include/mbexwn_live.h (LIVE_SYMBOLS)
-    lib.mbxl_ring_append.restype = i32
-    lib.mbxl_ring_append.argtypes = [fp, ctypes.c_int64, vp, i32, i32, fp, i32, i32, vp]
-    lib.mbxl_mel_frames.restype = i32
-    lib.mbxl_mel_frames.argtypes = [fp, i32, i32, vp, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp, vp, ctypes.c_float, fp, vp]
-    # include/mbexwn_live_resample.h (LIVE_RESAMPLE_SYMBOLS)
-    lib.mbxr_resample_rings.restype = i32
-    lib.mbxr_resample_rings.argtypes = [fp, i32, i32, vp, i32, i32, i32, i32, fp, i32, fp, i32, i32, vp]
-    # include/mbexwn_live_out.h (LIVE_OUT_SYMBOLS)
-    lib.mbxo_resample_emit.restype = i32
-    lib.mbxo_resample_emit.argtypes = [fp, i32, i32, vp, i32, i32, i32, i32, fp, i32, fp, ctypes.c_int64, vp]
-    # include/mbexwn_flac.h (FLAC_SYMBOLS)
-    lib.mbxf_encode_flac16_fixed.restype = i32
-    lib.mbxf_encode_flac16_fixed.argtypes = [fp, ctypes.c_int64, i32, i64p, i32, vp, vp, ctypes.c_int64, vp, vp, vp, fp, vp]
-    # include/mbexwn_noise.h (NOISE_SYMBOLS)
-    lib.mbxn_fill_normal.restype = i32
-    lib.mbxn_fill_normal.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, vp]
-    # include/mbexwn_warp.h (WARP_SYMBOLS)
-    lib.mbxw_mel_frames_at.restype = i32
-    lib.mbxw_mel_frames_at.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, i32, i32, i32, fp, fp, fp, vp, vp, ctypes.c_float, fp, vp]
-    # include/mbexwn_envelope.h (ENVELOPE_SYMBOLS)
-    lib.mbxe_warp_envelope.restype = i32
-    lib.mbxe_warp_envelope.argtypes = [fp, ctypes.c_int64, i32, vp, i32, i32, fp, fp, fp, vp]
-    lib.mbxe_forward.restype = i32
-    lib.mbxe_forward.argtypes = [vp, fp, vp, i32, i32, fp, fp, vp, ctypes.c_size_t, ctypes.POINTER(mbx_forward_options), fp, fp, fp, vp]
-    # include/mbexwn_pitch.h (PITCH_SYMBOLS)
-    lib.mbxp_track_f0.restype = i32
-    lib.mbxp_track_f0.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, ctypes.c_float, fp, fp, vp]
-    # include/mbexwn_contour.h (CONTOUR_SYMBOLS); thresholds and weights are host pointers
-    hfp = ctypes.POINTER(ctypes.c_float)
-    lib.mbxc_f0_candidates.restype = i32
-    lib.mbxc_f0_candidates.argtypes = [fp, ctypes.c_int64, i32, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, hfp, hfp, i32, i32, fp, fp, fp, vp]
-    lib.mbxc_decode_f0.restype = i32
-    lib.mbxc_decode_f0.argtypes = [fp, fp, fp, vp, i32, i32, i32, ctypes.c_float, ctypes.c_float, fp, fp, vp]
-    _lib = lib
-    return lib
-
-
-EXPORTED_SYMBOLS = ["mbx_last_error", "mbx_create", "mbx_destroy", "mbx_conv_form", "mbx_kernel_report", "mbx_plan", "mbx_calibrate", "mbx_workspace_size", "mbx_forward",
-                    "mbx_forward_stream", "mbx_forward_ex", "mbx_layer_state_info", "mbx_window_advance", "mbx_window_update", "mbx_emit_rows", "mbx_stage",
-                    "mbx_profile_enable", "mbx_profile_read", "mbx_profile_read_launches", "mbx_clock_probe", "mbx_pqmf_synthesis", "mbx_conv1d", "mbx_conv1d_f64acc", "mbx_lin_interp", "mbx_wavetable", "mbx_stft_filter", "mbx_norm_mel", "mbx_mel_analysis",
-                    "mbx_encode_flac16"]
-
-
-# include/mbexwn_audio.h: the audio-side entry points of the same library (prefix mbxa_; mbexwn.h's list stays as it is)
-AUDIO_SYMBOLS = ["mbxa_resample_poly"]
-
-# include/mbexwn_live.h: the streaming analysis (prefix mbxl_; the two lists above stay as they are)
-LIVE_SYMBOLS = ["mbxl_ring_append", "mbxl_mel_frames"]
-
-# include/mbexwn_live_resample.h: the streaming resampler (prefix mbxr_; the three lists above stay as they are)
-LIVE_RESAMPLE_SYMBOLS = ["mbxr_resample_rings"]
-
-# include/mbexwn_flac.h: the compressing FLAC encoder (prefix mbxf_; the four lists above stay as they are)
-FLAC_SYMBOLS = ["mbxf_encode_flac16_fixed"]
-
-# include/mbexwn_live_out.h: the streaming output resampler (prefix mbxo_; the five lists above stay as they are)
-LIVE_OUT_SYMBOLS = ["mbxo_resample_emit"]
-
-# include/mbexwn_noise.h: the keyed normal noise (prefix mbxn_; the six lists above stay as they are)
-NOISE_SYMBOLS = ["mbxn_fill_normal"]
-
-# include/mbexwn_warp.h: the mel analysis at arbitrary frame positions (prefix mbxw_; the seven lists above stay as they are)
-WARP_SYMBOLS = ["mbxw_mel_frames_at"]
-
-# include/mbexwn_envelope.h: the formant shift (prefix mbxe_; the eight lists above stay as they are)
-ENVELOPE_SYMBOLS = ["mbxe_warp_envelope", "mbxe_forward"]
-
-# include/mbexwn_pitch.h: the F0 tracker (prefix mbxp_; the nine lists above stay as they are)
-PITCH_SYMBOLS = ["mbxp_track_f0"]
-
-# include/mbexwn_contour.h: the decoded F0 contour (prefix mbxc_; the ten lists above stay as they are)
-CONTOUR_SYMBOLS = ["mbxc_f0_candidates", "mbxc_decode_f0"]
-
-
-def _check(status):
-    if status != 0:
-        msg = load_library().mbx_last_error().decode("utf-8", "replace")
-        raise _STATUS_EXC.get(status, RuntimeError)(f"mbexwn_hip: {msg}")
 
 
 # ------------------------------------------------------------------------------------------------

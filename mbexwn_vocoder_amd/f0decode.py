@@ -217,7 +217,7 @@ def candidates_device(audio, n_samples, centres, n_frames, prm, dec):
     No engine: the launch goes to the current stream of the buffers' device."""
     import ctypes
     import torch
-    from .engine import _check, load_library
+    from .abi import _check, load_library
     f0track.check_params(prm)
     check_decode(dec)
     if not torch.is_tensor(audio) or audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_cuda:
@@ -257,7 +257,7 @@ def decode_device(period, cost, dprime, n_frames, sample_rate, dec):
     since the kernel gives the definition's bits."""
     import ctypes
     import torch
-    from .engine import _check, load_library
+    from .abi import _check, load_library
     check_decode(dec)
     if not torch.is_tensor(period) or period.dim() != 3 or int(period.shape[2]) != SLOTS or period.dtype != torch.float32 or not period.is_cuda:
         raise ValueError(f"period must be a float32 cuda tensor of shape (batch, max_frames, {SLOTS})")

@@ -169,7 +169,7 @@ def track_f0_device(audio, n_samples, centres, n_frames, prm):
     buffers' device."""
     import ctypes
     import torch
-    from .engine import _check, load_library
+    from .abi import _check, load_library
     check_params(prm)
     if not torch.is_tensor(audio) or audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_cuda:
         raise ValueError("audio must be a float32 cuda tensor of shape (batch, stride)")

@@ -282,7 +282,7 @@ class StreamingAnalyzer(_Stage):
         if not plan.rows:
             return {}
         import torch
-        from .engine import _check, load_library
+        from .abi import _check, load_library
         self._ensure(plan)
         lib, rings, in_rings, tabs = load_library(), self.rings, self.input_rings, self._tables
         S, R, body, used, floats = plan.S, plan.R, plan.body, plan.body + plan.samples, plan.S * plan.max_new * self.n_mels
@@ -424,7 +424,7 @@ class StreamingOutputResampler(_Stage):
         if not plan.rows:
             return {}
         import torch
-        from .engine import _check, load_library
+        from .abi import _check, load_library
         lib, dev = load_library(), self._resolve_device()
         held = ((st.slot, st.on_device) for st in self.streams.values() if st.on_device)
         self.device_allocations += self._store.ensure(dev, plan.ring_needed, held)

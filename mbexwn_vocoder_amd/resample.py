@@ -129,7 +129,7 @@ def resample_device(sound, n_samples, in_sr, out_sr):
     takes as its ``n_samples``.  The row length comes from N by integer arithmetic on the host; the lengths stay on the
     device (integer tensor arithmetic, clamped as the kernel clamps them): no device-to-host copy, no synchronisation."""
     import torch
-    from .engine import _check, load_library
+    from .abi import _check, load_library
     if sound.dim() != 2 or sound.dtype != torch.float32 or not sound.is_cuda:
         raise ValueError("sound must be a float32 cuda tensor of shape (batch, time)")
     dev = sound.device

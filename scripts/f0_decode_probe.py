@@ -39,7 +39,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("f0_decode_probe.py: no GPU available; a timing taken without one says nothing")
     from mbexwn_vocoder_amd import f0decode, f0track, timemap
-    from mbexwn_vocoder_amd.engine import _check, load_library
+    from mbexwn_vocoder_amd.abi import _check, load_library
     rate, hop = 24000, 300
     prm, dec = f0track.params(rate), f0decode.decode_params()
     dev = torch.device("cuda", torch.cuda.current_device())

@@ -41,7 +41,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("flac_probe.py: no GPU available; a timing taken without one says nothing")
     from mbexwn_vocoder_amd import flac
-    from mbexwn_vocoder_amd.engine import _check
+    from mbexwn_vocoder_amd.abi import _check
     from mbexwn_vocoder_amd.mel_inverter import MELInverter, create_synthetic_model_dir
     with tempfile.TemporaryDirectory() as tmp:
         inv = MELInverter(create_synthetic_model_dir(os.path.join(tmp, "speech"), "SPEECH"))

@@ -38,7 +38,7 @@ def main():
     from mbexwn_vocoder_amd import timemap
     from mbexwn_vocoder_amd.analysis import mel_analysis_tables
     from mbexwn_vocoder_amd.config import read_config
-    from mbexwn_vocoder_amd.engine import _check, load_library
+    from mbexwn_vocoder_amd.abi import _check, load_library
     from mbexwn_vocoder_amd.mel_inverter import create_synthetic_model_dir
     with tempfile.TemporaryDirectory() as tmp:
         cfg = read_config(config_file=os.path.join(create_synthetic_model_dir(os.path.join(tmp, "speech"), "SPEECH"),

@@ -1,60 +1,28 @@
-"""The C-ABI library loads on a CPU-only host and exports every entry point include/mbexwn.h declares;
-the ctypes mirror of the structs has the layout the C compiler gives them (no compute calls here)."""
+"""The C-ABI library builds on a CPU-only host and the binding lists what include/mbexwn.h declares; the policy fields of
+mbx_config and the kernel-code names (no compute calls here).  The exports, every parameter and the layout of every
+structure: test_abi_headers.py."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
-from mbexwn_vocoder_amd import engine
+import c_headers
+from mbexwn_vocoder_amd import abi, engine
 from mbexwn_vocoder_amd.build import LIB_PATH, build_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mbexwn.h")
 
 
-def declared_functions():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(mbx_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_library_exports_every_declared_symbol():
+    """(that the library exports each of them, and each function of the other headers: test_abi_headers.py)"""
     build_library()
     assert os.path.exists(LIB_PATH)
-    lib = engine.load_library()
-    names = declared_functions()
+    names = [name for name, _, _ in c_headers.prototypes(c_headers.read_code("mbexwn.h"))]
     assert "mbx_forward" in names and "mbx_create" in names and len(names) >= 12
-    for name in names:
-        assert hasattr(lib, name), f"{name} is declared in mbexwn.h but not exported"
-    assert sorted(engine.EXPORTED_SYMBOLS) == names
-
-
-def test_struct_layout_matches_c(tmp_path):
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mbexwn.h"\n'
-                   'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mbx_config), sizeof(mbx_subnet_op),'
-                   ' sizeof(mbx_tensor), offsetof(mbx_config, n_f0_ops), offsetof(mbx_config, vtf_ops),'
-                   ' offsetof(mbx_config, wt_nominal_f0), sizeof(mbx_forward_options), offsetof(mbx_forward_options, wn_frames),'
-                   ' offsetof(mbx_forward_options, sub_carry), offsetof(mbx_forward_options, layer_rows),'
-                   ' offsetof(mbx_config, wn_conv_form), offsetof(mbx_config, tune_resskip_split), sizeof(mbx_conv_form_info),'
-                   ' offsetof(mbx_conv_form_info, err_f23), sizeof(mbx_kernel_report_info), offsetof(mbx_kernel_report_info, tail_kernel),'
-                   ' sizeof(mbx_plan_info), offsetof(mbx_plan_info, resskip_kernel), offsetof(mbx_plan_info, planes_only));'
-                   ' return 0;}\n')
-    exe = tmp_path / "sizes"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    got = [int(vv) for vv in out]
-    cc = engine.mbx_config
-    assert got == [ctypes.sizeof(cc), ctypes.sizeof(engine.mbx_subnet_op), ctypes.sizeof(engine.mbx_tensor),
-                   cc.n_f0_ops.offset, cc.vtf_ops.offset, cc.wt_nominal_f0.offset,
-                   ctypes.sizeof(engine.mbx_forward_options), engine.mbx_forward_options.wn_frames.offset,
-                   engine.mbx_forward_options.sub_carry.offset, engine.mbx_forward_options.layer_rows.offset,
-                   cc.wn_conv_form.offset, cc.tune_resskip_split.offset, ctypes.sizeof(engine.mbx_conv_form_info),
-                   engine.mbx_conv_form_info.err_f23.offset, ctypes.sizeof(engine.mbx_kernel_report_info),
-                   engine.mbx_kernel_report_info.tail_kernel.offset, ctypes.sizeof(engine.mbx_plan_info),
-                   engine.mbx_plan_info.resskip_kernel.offset, engine.mbx_plan_info.planes_only.offset]
+    assert engine.EXPORTED_SYMBOLS == abi.symbols("mbexwn.h") == names
+    assert engine.AUDIO_SYMBOLS == abi.symbols("mbexwn_audio.h")         # the two lists the build hook reads
 
 
 def test_policy_fields_and_experiment_variables(monkeypatch, capsys):

@@ -177,11 +177,8 @@ _OUTPUT_ARGS = ("mbx_handle **", "*info", "float *audio", "float *y", "float *pu
 
 
 def _prototypes():
-    import os
-    import re
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mbexwn.h")
-    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    return {mm.group(1): " ".join(mm.group(2).split()) for mm in re.finditer(r"\b(mbx_\w+)\s*\(([^;{]*?)\)\s*;", text)}
+    import c_headers
+    return {name: plist for name, _, plist in c_headers.prototypes(c_headers.read_code("mbexwn.h"))}
 
 
 def test_cases_cover_every_kernel_branch_and_export():

@@ -23,7 +23,7 @@
  * The optional operand-order images of the weights ("*.wino2w", "*.wino4w", "*.packed", "*.fold",
  * "*.fold_wide", "*.fold_wave", "*.fold_f16", "*.start_fold", "*.fold_start", "*.fold_start_wide", "*.fold_start_wave",
  * "wn.tail.fold", "wn.end.packed";
- * engine.tensor_table builds them) select the specialised kernels; a handle created from the plain folded weights
+ * packing.tensor_table builds them) select the specialised kernels; a handle created from the plain folded weights
  * alone runs the generic ones.
  */
 #ifndef MBEXWN_H

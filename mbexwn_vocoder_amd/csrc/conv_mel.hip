@@ -26,7 +26,7 @@
 //                                  without the *.w64 tensors): one rounding to float32 per output
 //   x float32, W float64 (w64)     first layer of the full-float64 chain: reads the mel input, writes float64 (out64)
 //   x float64 (x64), W float64     hidden layers of the chain
-// The float64 weights are the exact weight-norm fold g v / |v| (host, engine.tensor_table "<layer>.w64").
+// The float64 weights are the exact weight-norm fold g v / |v| (host, packing.tensor_table "<layer>.w64").
 #include <type_traits>
 
 #include "conv_tile.h"

@@ -85,7 +85,7 @@ struct Gate0Args {
     int pulse_channels;
     const int *n_frames;
     int rows_per_frame, max_rows, batch;
-    const float *w;           // image of engine.fold_start_weights (ceil(C/32), 3, 2, 64, 4)
+    const float *w;           // image of packing.fold_start_weights (ceil(C/32), 3, 2, 64, 4)
     const float *bias;        // (2C) gate bias or null
     int channels, dil;
     int causal;               // 0: SAME (taps t - d, t, t + d), 1: CAUSAL (taps t - 2d, t - d, t)

@@ -51,15 +51,15 @@ bool launch_conv1d_mel_single(const ConvArgs &a, hipStream_t stream);
 // wn_plan.h; a launcher is told the instantiation, checks what the caller guarantees (non-null, aligned pointers), computes the
 // grid and launches.  Return value: nullptr, or what is wrong with the pointers (nothing was launched).
 // Winograd F(4,3) form on v_mfma_f32_16x16x4_f32, wave tile 16 groups x 64 columns (wn_winograd4w.hip); a.w = image of
-// engine.pack_winograd4w_weights (ceil(C/32), ceil(C/8), 3072); k.shape: 0 = 256-row blocks, 1 = 128-row blocks whose waves
+// packing.pack_winograd4w_weights (ceil(C/32), ceil(C/8), 3072); k.shape: 0 = 256-row blocks, 1 = 128-row blocks whose waves
 // split the six products, 2 = product-split blocks of half a column tile, 3 = 256-row blocks of TWO column tiles (d <= 16,
 // cond_up >= 10; an odd last tile runs in 256-row blocks): same bits, all four
 const char *launch_wn_gate_winograd4w(const ConvArgs &a, const GateChoice &k, hipStream_t stream);
 // Winograd F(2,3) form on v_mfma_f32_16x16x4_f32 with wave-granular tiles (wn_winograd2w.hip: streams, per-layer regions,
-// MBX_CONV_F23); a.w = image of engine.pack_winograd2w_weights (ceil(C/32), ceil(C/8), 2048)
+// MBX_CONV_F23); a.w = image of packing.pack_winograd2w_weights (ceil(C/32), ceil(C/8), 2048)
 const char *launch_wn_gate_winograd2w(const ConvArgs &a, hipStream_t stream);
 // the dilated convolution + gate in split half precision, direct form (wn_gate_f16.hip; opt-in, mbx_config.wn_precision);
-// a.w = image of engine.pack_gate_f16_weights (ceil(C/32), ceil(C/32), 6144); kernel: MBX_GATE_K_SPLIT_F16*
+// a.w = image of packing.pack_gate_f16_weights (ceil(C/32), ceil(C/32), 6144); kernel: MBX_GATE_K_SPLIT_F16*
 const char *launch_wn_gate_f16(const ConvArgs &a, int kernel, hipStream_t stream);
 // First WaveNet layer with the start convolution folded into it (wn_gate0.hip)
 const char *launch_wn_gate0(const Gate0Args &a, hipStream_t stream);
@@ -70,13 +70,13 @@ unsigned wn_gate_winograd4q_lds_opt_in();
 // kernel: MBX_RESSKIP_K_PACKED64 | _PACKED128
 const char *launch_wn_resskip(const ConvArgs &a, int kernel, hipStream_t stream);
 // the same layer for large launches, one block owning all columns of its rows (wn_resskip_wide.hip); a.w = image of
-// engine.pack_resskip_wide_weights (ceil(cin/8), ceil(cout/32), 256); kernel: MBX_RESSKIP_K_WIDE*
+// packing.pack_resskip_wide_weights (ceil(cin/8), ceil(cout/32), 256); kernel: MBX_RESSKIP_K_WIDE*
 const char *launch_wn_resskip_wide(const ConvArgs &a, int kernel, hipStream_t stream);
 // the same layer for small launches (one utterance, streaming ticks), tiled at wave granularity (wn_resskip_wave.hip);
-// a.w = image of engine.pack_resskip_wave_weights (ceil(cin/16), 12, 512); kernel: MBX_RESSKIP_K_WAVE*
+// a.w = image of packing.pack_resskip_wave_weights (ceil(cin/16), 12, 512); kernel: MBX_RESSKIP_K_WAVE*
 const char *launch_wn_resskip_wave(const ConvArgs &a, int kernel, hipStream_t stream);
 // the same layer in split half precision (wn_resskip_f16.hip; opt-in, mbx_config.wn_precision); a.w = image of
-// engine.pack_resskip_f16_weights (ceil(cin/32), 12, 1024); a.gate_act must be set (glu is refused)
+// packing.pack_resskip_f16_weights (ceil(cin/32), 12, 1024); a.gate_act must be set (glu is refused)
 const char *launch_wn_resskip_f16(const ConvArgs &a, hipStream_t stream);
 // the pointers of a folded res/skip launch (wide, wave-tiled, split half precision): the workspace is carved in 256-byte
 // pieces and tensors come from the device allocator, so a failure here is a bug of the caller

@@ -6,7 +6,7 @@
 //     conv0(h0)[t] = sum_tau h0[t + (tau-1) d] W0_tau = sum_tau x'[t + (tau-1) d] (Ws' W0_tau),
 // with x' = [x | 1 | 0] (8 channels; the constant channel carries the start bias) and Ws' = [Ws ; bs ; 0]: rows outside
 // the item are zero in x' exactly where the reference pads h0 with zeros, so the boundary rows are exact too.  The
-// products Ws' W0_tau (8 x 2C per tap) are formed on the host in float64 (engine.fold_start_weights).  The layer then is
+// products Ws' W0_tau (8 x 2C per tap) are formed on the host in float64 (packing.fold_start_weights).  The layer then is
 // a K = 24 contraction instead of K = 3C: its (rows, C) input tensor h0 is never written or read, and 1/L of the
 // WaveNet's dominant matrix work disappears.  The residual path gets h0 the same way: the res/skip layer of layer 0
 // contracts [a0 | x'] with [Wr ; Ws'] (wn_resskip.hip, h_init), for which this kernel appends x' (padded to 16 channels)
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void wn_gate0_kernel(Gate0Args p) {
     }
 }
 
-// a.w: image of engine.fold_start_weights (ceil(C/32), 3, 2, 64, 4); the layer fits (wn_gate0_select)
+// a.w: image of packing.fold_start_weights (ceil(C/32), 3, 2, 64, 4); the layer fits (wn_gate0_select)
 const char *launch_wn_gate0(const Gate0Args &a, hipStream_t stream) {
     if ((uintptr_t)a.out % 16 != 0 || (uintptr_t)a.w % 16 != 0 || !a.cond || (uintptr_t)a.cond % 16 != 0 || !a.lerp_w0 || !a.lerp_w1 ||
         (uintptr_t)a.bias % 16 != 0)

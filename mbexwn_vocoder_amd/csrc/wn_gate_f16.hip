@@ -19,7 +19,7 @@
 //      split in registers, once per tap and row tile -- 6 splits of 8 values per wave and step: 1.09 ms per launch, 0.83
 //      with the split removed.)  Lane (i = lane & 15, kq = lane >> 4) reads the channels 8 kq .. + 7 of its row;
 //   B: 3 taps x 4 column tiles x [hi | lo'] x 64 lanes x 8 halves, packed on the host in MFMA operand order
-//      (engine.pack_gate_f16_weights), 24 KB per step, copied verbatim by LDS-DMA into one of two stages.
+//      (packing.pack_gate_f16_weights), 24 KB per step, copied verbatim by LDS-DMA into one of two stages.
 // Per step: wait for the step's requests, barrier, convert X -> Y, barrier, request the next step (X is free, the other
 // weight stage too), multiply.  X + Y + 2 weight stages + conditioning tile + tables: 128.5 KB, one block per CU.
 // PLANES = true: the producer (wn_resskip_f16_kernel) has written the hidden state as fp16 planes already (ConvArgs::h_split:
@@ -520,7 +520,7 @@ unsigned wn_gate_f16_lds_opt_in() {
     return bits;
 }
 
-// a.w must point at the image of engine.pack_gate_f16_weights (ceil(C/32) column tiles, ceil(C/32) steps, 6144 floats);
+// a.w must point at the image of packing.pack_gate_f16_weights (ceil(C/32) column tiles, ceil(C/32) steps, 6144 floats);
 // kernel: the MBX_GATE_K_SPLIT_F16* that wn_gate_f16_select chose for these arguments (a.h_split set for the two planes kernels)
 const char *launch_wn_gate_f16(const ConvArgs &a, int kernel, hipStream_t stream) {
     const bool planes = kernel != MBX_GATE_K_SPLIT_F16_F32H;

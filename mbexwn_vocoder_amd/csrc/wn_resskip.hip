@@ -1,5 +1,5 @@
 // WaveNet residual/skip layer: r = a W + b (1x1, C -> 2C; last layer C -> C), h += r[:, :C], skip (+)= r[:, C:].
-// With the skip path folded into the end convolution (engine.fold_skip_weights) the skip half of W is the C x n_out
+// With the skip path folded into the end convolution (packing.fold_skip_weights) the skip half of W is the C x n_out
 // product W_skip W_end and "skip" is the n_out-wide WaveNet output accumulator (row stride skip_ld).
 //
 // Same layer as conv1d_mfma_kernel<EPI_RESSKIP> (reference MBExWN_NVoc/vocoder/model/custom_AE_layers.py:322-336:
@@ -9,7 +9,7 @@
 //   large launches, MT = 1 (64-row blocks, finer granularity) for small ones
 //   A: gate output rows [m0, m0+64 MT) x 16 channels per slice through LDS-DMA, chunk (row, c) at 4*row + (c ^ ((row>>2)&3))
 //   B: 16 channels x 128 columns per slice, pre-packed on the host in MFMA operand order
-//      [channel half cc][column tile jn][lane][4 k steps] (engine.pack_resskip_weights): one ds_read_b128 per lane
+//      [channel half cc][column tile jn][lane][4 k steps] (packing.pack_resskip_weights): one ds_read_b128 per lane
 //      = the weight operands of four consecutive MFMAs
 //   three (large shape) or two LDS stages of 16 / 12 KB; operand groups of 8 MFMAs, the operands of group n+1 are requested from
 //   LDS before the MFMAs of group n issue.

@@ -12,7 +12,7 @@
 // (-1, 1) -- which is why the glu gate, whose linear half is unbounded, does not get this mode -- and the excitation channels
 // that layer 0's rows carry behind it, pulse samples and the noise draw, are O(1)), the old value and the bias enter times
 // 2^11, and the epilogue multiplies by 2^-11 -- powers of two, so no rounding is added.  The weights are split on the
-// host (engine.pack_resskip_f16_weights).
+// host (packing.pack_resskip_f16_weights).
 //
 // Block = 8 waves, 128 rows x 6 pairs of 16-column tiles (two blocks per row tile: 12 pairs = 384 columns cover C + n_out
 // <= 384); wave w owns rows 16 w .. 16 w + 15 x 12 column tiles (48 accumulator registers; 2 blocks per CU).
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(512, 4) void wn_resskip_f16_kernel(ConvArgs p) {
     }
 }
 
-// a.w must point at the image of engine.pack_resskip_f16_weights (ceil(cin/32), 12, 1024 floats); the layer fits
+// a.w must point at the image of packing.pack_resskip_f16_weights (ceil(cin/32), 12, 1024 floats); the layer fits
 // (wn_resskip_f16_select)
 const char *launch_wn_resskip_f16(const ConvArgs &a, hipStream_t stream) {
     if (const char *e = wn_resskip_folded_pointers(a)) return e;

@@ -1,6 +1,6 @@
 // WaveNet residual/skip layer for SMALL launches (one utterance, the steady ticks of the streams), tiled at WAVE
 // granularity: r = a W + b (1x1), h (+)= r[:, :C], accumulator (+)= r[:, C:]  (skip path folded into the end
-// convolution, engine.fold_skip_weights: cout = C + n_out).
+// convolution, packing.fold_skip_weights: cout = C + n_out).
 //
 // Same layer and same arithmetic per output as wn_resskip_wide_kernel (wn_resskip_wide.hip; reference
 // MBExWN_NVoc/vocoder/model/custom_AE_layers.py:322-336).  What differs is how the work is cut.  The block shapes of
@@ -19,7 +19,7 @@
 //      ds_read_b128 of lane (r = lane & 15, kq = lane >> 4) -- channels 4 kq .. 4 kq + 3, contracted by MFMA steps 0..3 --
 //      is bank-conflict free
 //   B: 16 channels x 32 NPW columns in MFMA operand order [pair p][lane][even tile steps 0..3 | odd tile steps 0..3]
-//      (engine.pack_resskip_wave_weights): two ds_read_b128 per lane and pair = the weight operands of eight MFMAs
+//      (packing.pack_resskip_wave_weights): two ds_read_b128 per lane and pair = the weight operands of eight MFMAs
 // The accumulators start from old value + bias, the epilogue is a plain float2 store (as in the wide kernel).
 // h_init (layer 0 with the start convolution folded in, wn_gate0.hip): rows are [a | x'] (cin = C + 16), h starts from
 // the bias alone.
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(256, (RvShape<NPW, NSTAGE>::WAVES_PER_SIMD)) void w
     }
 }
 
-// a.w must point at the image of engine.pack_resskip_wave_weights (ceil(cin/16), 12, 512); kernel: the MBX_RESSKIP_K_WAVE* (the
+// a.w must point at the image of packing.pack_resskip_wave_weights (ceil(cin/16), 12, 512); kernel: the MBX_RESSKIP_K_WAVE* (the
 // cut: pairs per wave) that wn_resskip_wave_select chose for these arguments
 const char *launch_wn_resskip_wave(const ConvArgs &a, int kernel, hipStream_t stream) {
     if (const char *e = wn_resskip_folded_pointers(a)) return e;

@@ -2,7 +2,7 @@
 // owning ALL output columns of its rows.
 //
 // Same layer as wn_resskip_kernel (wn_resskip.hip; reference MBExWN_NVoc/vocoder/model/custom_AE_layers.py:322-336), with
-// the skip path folded into the end convolution (engine.fold_skip_weights: cout = C + n_out).  That kernel tiles the
+// the skip path folded into the end convolution (packing.fold_skip_weights: cout = C + n_out).  That kernel tiles the
 // columns in blocks of 128: C + n_out = 350 columns cost 384 (9.7 % of the matrix work is padding), the rows of `a` are
 // fetched by three blocks, and a wave requests 4 LDS-DMA kilobytes per 16 MFMAs.  Here:
 //   block = 8 waves, 128 rows x NP pairs of 16-column MFMA tiles (v_mfma_f32_16x16x4_f32).  C + n_out = 350 (C = 320):
@@ -17,7 +17,7 @@
 //   A: rows [m0, m0+128) x 8 channels, 32 bytes per row, 16-byte chunk c at 2*row + (c ^ ((row>>3)&1)); lane (r = lane & 15,
 //      kq = lane >> 4) reads the 8 bytes of channels 2 kq, 2 kq + 1: bank-conflict free; MFMA step m contracts {2 kq + m}
 //   B: 8 channels x 32 NP columns, packed on the host in MFMA operand order [pair p][lane][even tile step 0, even tile
-//      step 1, odd tile step 0, odd tile step 1] (engine.pack_resskip_wide_weights): one ds_read_b128 per lane and pair
+//      step 1, odd tile step 0, odd tile step 1] (packing.pack_resskip_wide_weights): one ds_read_b128 per lane and pair
 // h_init (layer 0 with the start convolution folded in, wn_gate0.hip): rows are [a | x'] (cin = C + 16), h starts from
 // the bias alone.
 #include <cstdlib>
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(512, 4) void wn_resskip_wide_kernel(ConvArgs p) {
     }
 }
 
-// a.w must point at the image of engine.pack_resskip_wide_weights (ceil(cin/8), np, 256) with np = ceil(cout/32) in
+// a.w must point at the image of packing.pack_resskip_wide_weights (ceil(cin/8), np, 256) with np = ceil(cout/32) in
 // {11, 12}; kernel: the MBX_RESSKIP_K_WIDE* that wn_resskip_wide_select chose for these arguments
 const char *launch_wn_resskip_wide(const ConvArgs &a, int kernel, hipStream_t stream) {
     if (const char *e = wn_resskip_folded_pointers(a)) return e;

@@ -2,7 +2,7 @@
 // (1x1, n_out -> M <= 16), one kernel, one pass over x.  Two uses:
 //   x = skip sum, W = W_end                        (end convolution after un-folded res/skip layers)
 //   x = gate output of the last layer, W = W_skip W_end, y_acc = contributions of the earlier layers
-//                                                  (skip path folded into the end convolution, engine.fold_skip_weights)
+//                                                  (skip path folded into the end convolution, packing.fold_skip_weights)
 //
 // Same arithmetic as the two EPI_LINEAR launches of conv1d_mfma_kernel it replaces (reference
 // MBExWN_NVoc/vocoder/model/custom_AE_layers.py:338-341 `end` convolution of the WaveNet,
@@ -12,7 +12,7 @@
 // Block = 32 rows, 4 waves that split the C input channels (wave w takes the 8-channel groups w, w+4, ...): the skip
 // rows go straight from global memory into the MFMA A operand (lane = row, 16 bytes = four k steps of one lane half),
 // W_end comes pre-packed from the host in the matching operand order [group][lane half][column][k step]
-// (engine.pack_end_weights, zero padded to 32 columns), one coalesced 16-byte load per lane.  The four partial 32 x 32
+// (packing.pack_end_weights, zero padded to 32 columns), one coalesced 16-byte load per lane.  The four partial 32 x 32
 // results are summed through LDS, which also puts whole rows in front of single lanes for the post-net.
 // HBM-bound: rows x C x 4 bytes.
 #include <algorithm>

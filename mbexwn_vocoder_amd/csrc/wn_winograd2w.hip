@@ -7,7 +7,7 @@
 //     m1 = (x0 - x2) W0      m2 = (x1 + x2) (W0 + W1 + W2)/2      m3 = (x2 - x1) (W0 - W1 + W2)/2      m4 = (x1 - x3) W2
 //     y[t] = m1 + m2 + m3    y[t+d] = m2 - m3 - m4
 // = 4 channel contractions per output pair instead of 6 (weight combinations formed on the host in float64,
-// engine.pack_winograd2w_weights).  F(2,3) has no numerical reach beyond the receptive field of the layer, which is why
+// packing.pack_winograd2w_weights).  F(2,3) has no numerical reach beyond the receptive field of the layer, which is why
 // the streaming windows (streaming.py) run it: a window then reproduces the offline synthesis bit for bit.
 //
 // Wave tile (as in wn_winograd4w.hip: few rows, many columns, because every vector instruction beside the fp32 MFMA
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256, 4) void wn_gate_winograd2w_kernel(ConvArgs p, 
     }
 }
 
-// a.w must point at the host-packed F(2,3) weights (ceil(C/32), ceil(C/8), 2048) of engine.pack_winograd2w_weights; the layer
+// a.w must point at the host-packed F(2,3) weights (ceil(C/32), ceil(C/8), 2048) of packing.pack_winograd2w_weights; the layer
 // fits (wn_gate_winograd2w_fits).  a.out_row0 / a.out_rows: the rows of every item that are computed.
 const char *launch_wn_gate_winograd2w(const ConvArgs &a, hipStream_t stream) {
     if ((uintptr_t)a.x % 16 != 0 || (uintptr_t)a.w % 16 != 0 || !a.zeros || !a.cond || (uintptr_t)a.cond % 16 != 0 || !a.lerp_w0 ||

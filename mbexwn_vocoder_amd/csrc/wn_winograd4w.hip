@@ -7,7 +7,7 @@
 //     m_j = v_j U_j,  U = G W  (G = [[1/4,0,0],[-1/6,-1/6,-1/6],[-1/6,1/6,-1/6],[1/24,1/12,1/6],[1/24,-1/12,1/6],[0,0,1]])
 //     y[t] = m0+m1+m2+m3+m4   y[t+d] = m1-m2+2(m3-m4)   y[t+2d] = m1+m2+4(m3+m4)   y[t+3d] = m1-m2+8(m3-m4)+m5
 // = 6 channel contractions per four outputs instead of 12.  Float32 on the exact fp32 MFMA; U is formed on the host in
-// float64 (engine.pack_winograd4w_weights).
+// float64 (packing.pack_winograd4w_weights).
 //
 // What shapes this kernel: on gfx950 the fp32 MFMA runs at the fp32 vector rate and every vector instruction a wave
 // issues takes matrix-pipe time away (measured, profiles/README.md: 3-4 cycles per v_fma, 11 per v_exp beside
@@ -1443,7 +1443,7 @@ unsigned wn_gate_winograd4q_lds_opt_in() {
     return 0;
 }
 
-// a.w must point at the host-packed F(4,3) weights (ceil(C/32), ceil(C/8), 3072) of engine.pack_winograd4w_weights;
+// a.w must point at the host-packed F(4,3) weights (ceil(C/32), ceil(C/8), 3072) of packing.pack_winograd4w_weights;
 // k: what wn_gate_winograd4w_select chose for these arguments.  k.shape: 0 = 256-row blocks, 1 = 128-row product-split blocks
 // (same bits as the 256-row shape), 2 = product-split blocks of half a column tile, 3 = 256-row blocks of two column tiles
 const char *launch_wn_gate_winograd4w(const ConvArgs &a, const GateChoice &k, hipStream_t stream) {

@@ -21,8 +21,12 @@ from .abi import (CONV_FORMS, GATE_KERNEL_NAMES, MBX_ABI_VERSION, MBX_MAX_PRECON
                   mbx_subnet_op, mbx_tensor, symbols)
 from .build import LIB_PATH  # noqa: F401
 from .config import ModelDims
+from .flac import EncodedFlac  # noqa: F401  (what encode_flac16 returns; the name stays importable from here)
+# the weight images are packing.py; its public names stay importable from here (tensor_table is what the engine itself calls)
+from .packing import (fold_skip_weights, fold_start_weights, pack_end_weights, pack_gate_f16_weights,  # noqa: F401
+                      pack_resskip_f16_weights, pack_resskip_wave_weights, pack_resskip_weights, pack_resskip_wide_weights,
+                      pack_winograd2w_weights, pack_winograd4w_weights, tensor_table)
 from .subnet import build_subnet
-from .weights import fold_weights, merge_channel_groups
 
 # what the build hook checks in the library: the functions of include/mbexwn.h and include/mbexwn_audio.h (abi.TABLE)
 EXPORTED_SYMBOLS = symbols("mbexwn.h")
@@ -225,333 +229,6 @@ def make_config(config, wavetables, conv_form=None, batch_invariant=None, keep_s
     return cc, dims
 
 
-_WINOGRAD43_G = np.array([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6],
-                          [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]], dtype=np.float64)
-
-
-def pack_winograd4w_weights(w):
-    """Winograd F(4,3) combinations U = G W of the three taps (3, C, 2C) of a dilated WaveNet convolution, packed for
-    wn_gate_winograd4w_kernel (csrc/wn_winograd4w.hip, v_mfma_f32_16x16x4_f32); formed in float64, stored float32.
-
-    Layout (ceil(C/32) column tiles, ceil(C/8) channel slices, 3072): the 12 KB image of one (tile, slice) is copied
-    verbatim into LDS, ordered [product j][channel parity e][lane = 16*kq + n][tanh step 0, tanh step 1, sigmoid step 0,
-    sigmoid step 1] with input channel 8*slice + 2*kq + step and output column (0 | C) + 32*tile + 2*n + e;
-    out-of-range entries are zero.
-    """
-    w = np.asarray(w, dtype=np.float64)
-    C = w.shape[1]
-    assert w.shape == (3, C, 2 * C)
-    u = np.einsum("ij,jcn->icn", _WINOGRAD43_G, w)
-    nt, nk = (C + 31) // 32, (C + 7) // 8
-    wp = np.zeros((6, nk * 8, 2, nt * 32))
-    wp[:, :C, 0, :C] = u[:, :, :C]
-    wp[:, :C, 1, :C] = u[:, :, C:]
-    wp = wp.reshape(6, nk, 4, 2, 2, nt, 16, 2)                    # j, slice, kq, step, tanh|sigmoid, tile, n, e
-    return np.ascontiguousarray(wp.transpose(5, 1, 0, 7, 2, 6, 4, 3).reshape(nt, nk, 3072), dtype=np.float32)
-
-
-def pack_winograd2w_weights(w):
-    """Winograd F(2,3) combinations W0, (W0+W1+W2)/2, (W0-W1+W2)/2, W2 of the three taps (3, C, 2C) of a dilated WaveNet
-    convolution, packed for wn_gate_winograd2w_kernel (csrc/wn_winograd2w.hip, v_mfma_f32_16x16x4_f32); formed in
-    float64, stored float32.
-
-    Layout (ceil(C/32) column tiles, ceil(C/8) channel slices, 2048): the 8 KB image of one (tile, slice) is copied
-    verbatim into LDS, ordered [product j][channel parity e][lane = 16*kq + n][tanh step 0, tanh step 1, sigmoid step 0,
-    sigmoid step 1] with input channel 8*slice + 2*kq + step and output column (0 | C) + 32*tile + 2*n + e;
-    out-of-range entries are zero.
-    """
-    w = np.asarray(w, dtype=np.float64)
-    C = w.shape[1]
-    assert w.shape == (3, C, 2 * C)
-    u = np.stack((w[0], (w[0] + w[1] + w[2]) / 2, (w[0] - w[1] + w[2]) / 2, w[2]))
-    nt, nk = (C + 31) // 32, (C + 7) // 8
-    wp = np.zeros((4, nk * 8, 2, nt * 32))
-    wp[:, :C, 0, :C] = u[:, :, :C]
-    wp[:, :C, 1, :C] = u[:, :, C:]
-    wp = wp.reshape(4, nk, 4, 2, 2, nt, 16, 2)                    # j, slice, kq, step, tanh|sigmoid, tile, n, e
-    return np.ascontiguousarray(wp.transpose(5, 1, 0, 7, 2, 6, 4, 3).reshape(nt, nk, 2048), dtype=np.float32)
-
-
-def pack_resskip_weights(w):
-    """Weights (1, C, cout) of a WaveNet res/skip 1x1 convolution packed for wn_resskip_kernel (csrc/wn_resskip.hip).
-
-    Layout (ceil(cout/128) column tiles, ceil(C/16) channel slices, 2048): the 8 KB image of one (tile, slice), ordered
-    [channel half cc][column sub-tile jn][lane = 32*lk + n][k step st] with input channel 16*slice + 8*cc + 4*lk + st
-    and output column 128*tile + 32*jn + n; out-of-range entries are zero.
-    """
-    w = np.asarray(w, dtype=np.float32)
-    assert w.ndim == 3 and w.shape[0] == 1
-    C, cout = w.shape[1], w.shape[2]
-    nct, nk = (cout + 127) // 128, (C + 15) // 16
-    wp = np.zeros((nk * 16, nct * 128), dtype=np.float32)
-    wp[:C, :cout] = w[0]
-    wp = wp.reshape(nk, 2, 2, 4, nct, 4, 32)                      # slice, cc, lk, st, tile, jn, n
-    return np.ascontiguousarray(wp.transpose(4, 0, 1, 5, 2, 6, 3).reshape(nct, nk, 2048))
-
-
-def pack_resskip_wide_weights(w):
-    """Weights (1, K, cout) of a WaveNet res/skip 1x1 convolution packed for wn_resskip_wide_kernel
-    (csrc/wn_resskip_wide.hip, v_mfma_f32_16x16x4_f32).
-
-    Layout (ceil(K/8) channel slices, NP = ceil(cout/32) column tile pairs, 256): [pair p][lane = 16*kq + n][even tile
-    step 0, even tile step 1, odd tile step 0, odd tile step 1] with input channel 8*slice + 2*kq + step and output
-    column 32*p + 2*n + (0 even | 1 odd); out-of-range entries are zero.
-    """
-    w = np.asarray(w, dtype=np.float32)
-    assert w.ndim == 3 and w.shape[0] == 1
-    K, cout = w.shape[1], w.shape[2]
-    nk, npair = (K + 7) // 8, (cout + 31) // 32
-    wp = np.zeros((nk * 8, npair * 32), dtype=np.float32)
-    wp[:K, :cout] = w[0]
-    wp = wp.reshape(nk, 4, 2, npair, 16, 2)                        # slice, kq, step, pair, n, parity
-    return np.ascontiguousarray(wp.transpose(0, 3, 1, 4, 5, 2).reshape(nk, npair, 256))
-
-
-def pack_resskip_wave_weights(w):
-    """Weights (1, K, cout <= 384) of a WaveNet res/skip 1x1 convolution packed for wn_resskip_wave_kernel
-    (csrc/wn_resskip_wave.hip, v_mfma_f32_16x16x4_f32, 16-channel slices).
-
-    Layout (ceil(K/16) channel slices, 12 column tile pairs, 512): [pair p][even tile | odd tile][lane = 16*kq + n][step]
-    with input channel 16*slice + 4*kq + step and output column 32*p + 2*n + (0 even | 1 odd); out-of-range entries are
-    zero (the image always has 12 pairs, so that every column split of the kernel finds its pairs).
-    """
-    w = np.asarray(w, dtype=np.float32)
-    assert w.ndim == 3 and w.shape[0] == 1 and w.shape[2] <= 384
-    K, cout = w.shape[1], w.shape[2]
-    nk = (K + 15) // 16
-    wp = np.zeros((nk * 16, 12 * 32), dtype=np.float32)
-    wp[:K, :cout] = w[0]
-    wp = wp.reshape(nk, 4, 4, 12, 16, 2)                           # slice, kq, step, pair, n, parity
-    return np.ascontiguousarray(wp.transpose(0, 3, 5, 1, 4, 2).reshape(nk, 12, 512))
-
-
-def pack_resskip_f16_weights(w):
-    """Weights (1, K, cout <= 384) of a folded WaveNet res/skip layer for wn_resskip_f16_kernel (csrc/wn_resskip_f16.hip,
-    v_mfma_f32_16x16x32_f16; opt-in split half precision): every float32 weight is split into hi = fp16(w) and
-    lo' = fp16((w - hi) * 2^11).
-
-    Layout (ceil(K/32) steps, 12 column tile pairs, 1024 float32 words = 4 images x 64 lanes x 8 halves): images [even tile
-    hi | even tile lo' | odd tile hi | odd tile lo'], lane = 16 kq + n holds the input channels 32 step + 4 kq .. + 3 and
-    32 step + 16 + 4 kq .. + 3 of output column 32 p + 2 n + (0 even | 1 odd); out-of-range entries are zero.  Returned as
-    float32 words (two halves each) because the tensor table of the C ABI is float32; the bits are what counts.
-    """
-    w = np.asarray(w, dtype=np.float32)
-    assert w.ndim == 3 and w.shape[0] == 1 and w.shape[2] <= 384
-    K, cout = w.shape[1], w.shape[2]
-    nk = (K + 31) // 32
-    wp = np.zeros((nk * 32, 384), dtype=np.float32)
-    wp[:K, :cout] = w[0]
-    if not np.all(np.abs(wp) < 65000.0):
-        raise ValueError("res/skip weights outside fp16's range: split half precision is not available for this model")
-    hi = wp.astype(np.float16)
-    lo = ((wp - hi.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)
-    both = np.stack((hi, lo))                                      # (part, channel, column)
-    both = both.reshape(2, nk, 2, 4, 4, 12, 16, 2)                 # part, step, half (0 | +16), kq, v, pair, n, parity
-    img = both.transpose(1, 5, 7, 0, 3, 6, 2, 4)                   # step, pair, parity, part, kq, n, half, v
-    img = np.ascontiguousarray(img).reshape(nk, 12, 4, 64, 8)      # image = 2 parity + part ; lane = 16 kq + n ; 8 halves
-    return np.ascontiguousarray(img).view(np.float32).reshape(nk, 12, 1024)
-
-
-def pack_gate_f16_weights(w):
-    """The three taps (3, C, 2C) of a dilated WaveNet convolution for wn_gate_f16_kernel (csrc/wn_gate_f16.hip,
-    v_mfma_f32_16x16x32_f16; opt-in split half precision): hi = fp16(w), lo' = fp16((w - hi) * 2^11).
-
-    Layout (ceil(C/32) column tiles, ceil(C/32) steps, 6144 float32 words): [tap][tile c = 2 e + (0 tanh | 1 sigmoid)]
-    [hi | lo'][lane = 16 kq + n][8 halves], input channels 32 step + 8 kq .. + 7, output column (0 | C) + 32 tile block + 2 n
-    + e; out-of-range entries are zero.  float32 words hold two halves each."""
-    w = np.asarray(w, dtype=np.float32)
-    C = w.shape[1]
-    assert w.shape == (3, C, 2 * C)
-    nt = nk = (C + 31) // 32
-    wp = np.zeros((3, nk * 32, 2, nt * 32), dtype=np.float32)          # tap, channel, tanh|sigmoid, gate channel
-    wp[:, :C, 0, :C] = w[:, :, :C]
-    wp[:, :C, 1, :C] = w[:, :, C:]
-    if not np.all(np.abs(wp) < 65000.0):
-        raise ValueError("gate weights outside fp16's range: split half precision is not available for this model")
-    hi = wp.astype(np.float16)
-    lo = ((wp - hi.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)
-    both = np.stack((hi, lo))                                          # part, tap, channel, s, gate channel
-    both = both.reshape(2, 3, nk, 4, 8, 2, nt, 16, 2)                  # part, tap, step, kq, v, s, block, n, e
-    img = both.transpose(6, 2, 1, 8, 5, 0, 3, 7, 4)                    # block, step, tap, e, s, part, kq, n, v
-    img = np.ascontiguousarray(img).reshape(nt, nk, 3 * 4 * 2 * 64 * 8)
-    return np.ascontiguousarray(img).view(np.float32).reshape(nt, nk, 6144)
-
-
-def pack_end_weights(w):
-    """Weights (1, C, n_out <= 32) of the WaveNet end convolution packed for wn_tail_kernel (csrc/wn_tail.hip):
-    (ceil(C/8), 2, 32, 4) = [channel group c][lane half lk][column n][k step st] with input channel 8c + 4lk + st,
-    zero padded to 32 columns and to a multiple of 8 channels."""
-    w = np.asarray(w, dtype=np.float32)
-    assert w.ndim == 3 and w.shape[0] == 1 and w.shape[2] <= 32
-    C, n_out = w.shape[1], w.shape[2]
-    nc8 = (C + 7) // 8
-    wp = np.zeros((nc8 * 8, 32), dtype=np.float32)
-    wp[:C, :n_out] = w[0]
-    return np.ascontiguousarray(wp.reshape(nc8, 2, 4, 32).transpose(0, 1, 3, 2))
-
-
-def fold_skip_weights(folded, n_layers, channels, split_f16=False):
-    """Fold the skip path of the WaveNet into its end convolution (both are linear, reference
-    MBExWN_NVoc/vocoder/model/custom_AE_layers.py:322-341: output += res_skip[:, C:]; ...; self.end(output)):
-
-        end(sum_l (a_l Ws_l + bs_l)) = sum_l a_l (Ws_l We) + (sum_l bs_l We + be)
-
-    so layer l < L-1 needs the C x (C + n_out) matrix [Wr_l | Ws_l We] instead of C x 2C, the last layer C x n_out
-    instead of C x C, and the (rows, C) skip tensor never exists.  Products are formed in float64.  Returns the extra
-    tensors {name: array} (packed for wn_resskip_kernel / wn_tail_kernel) or {} if the layout does not allow it.
-    """
-    we = np.asarray(folded["wn.end.w"], dtype=np.float64)
-    if we.shape[0] != 1 or we.shape[2] > 32:
-        return {}
-    C, n_out = channels, we.shape[2]
-    we = we[0]
-    const = np.asarray(folded["wn.end.b"], dtype=np.float64).copy()
-    out = {}
-    biases = []
-    for ll in range(n_layers):
-        w = np.asarray(folded[f"wn.res_skip_{ll}.w"], dtype=np.float64)
-        b = np.asarray(folded[f"wn.res_skip_{ll}.b"], dtype=np.float64)
-        if w.shape[0] != 1:
-            return {}
-        last = ll == n_layers - 1
-        ws, bs = (w[0], b) if last else (w[0][:, C:], b[C:])
-        proj = ws @ we
-        const += bs @ we
-        if last:
-            out["wn.tail.fold"] = pack_end_weights(proj[None])
-        else:
-            out[f"wn.res_skip_{ll}.fold"] = pack_resskip_weights(np.concatenate((w[0][:, :C], proj), axis=1)[None])
-            out[f"wn.res_skip_{ll}.fold_wide"] = pack_resskip_wide_weights(np.concatenate((w[0][:, :C], proj), axis=1)[None])
-            if C + n_out <= 384:
-                out[f"wn.res_skip_{ll}.fold_wave"] = pack_resskip_wave_weights(np.concatenate((w[0][:, :C], proj), axis=1)[None])
-                if ll >= 1 and split_f16:
-                    out[f"wn.res_skip_{ll}.fold_f16"] = pack_resskip_f16_weights(np.concatenate((w[0][:, :C], proj), axis=1)[None])
-            if ll == 0:
-                out["__proj_0"] = proj                 # for fold_start_weights; not a device tensor
-            biases.append(np.concatenate((b[:C], np.zeros(n_out))))
-    if biases:
-        biases[0][C:] = const                 # layer 0 initialises the accumulator
-        for ll, bb in enumerate(biases):
-            out[f"wn.res_skip_{ll}.fold_b"] = bb
-        out["wn.tail.fold_b"] = np.zeros(n_out)
-    else:
-        out["wn.tail.fold_b"] = const
-    return out
-
-
-def fold_start_weights(folded, dims, fold_skip, split_f16=False):
-    """Fold the WaveNet's start convolution (1x1, reference custom_AE_layers.py:177-182,280) into layer 0.
-
-    With x' = [x | 1 | 0] (8 channels; x = pulse channels (+ noise), the constant channel carries the start bias) and
-    Ws' = [Ws ; bs ; 0], h0 = x' Ws' and conv0(h0) = sum_tau x'[t + (tau-1) d] (Ws' W0_tau): the dilated convolution of
-    layer 0 becomes a K = 24 contraction of the excitation itself (csrc/wn_gate0.hip), and its res/skip layer obtains
-    h0 by contracting [a0 | x'] with [Wr ; Ws'] (csrc/wn_resskip.hip, h_init).  Products are formed in float64.
-    Returns {name: array}: the (ceil(C/32), 3, 2, 64, 4) image of the tap products -- [tap][channel parity e][lane =
-    16*kq + n][tanh step 0, tanh step 1, sigmoid step 0, sigmoid step 1], input channel 2*kq + step, output column
-    (0 | C) + 32*tile + 2*n + e -- and the K-extended res/skip image; {} if the layout does not allow it.
-    """
-    C, L = dims.wn_channels, dims.wn_layers
-    ws = np.asarray(folded["wn.start.w"], dtype=np.float64)
-    w0 = np.asarray(folded["wn.conv1D_0.w"], dtype=np.float64)
-    cin = dims.wn_in_channels
-    if ws.shape != (1, cin, C) or w0.shape != (3, C, 2 * C) or cin + 1 > 8 or dims.pulse_channels_eff + 2 > 8:
-        return {}
-    wsp = np.zeros((8, C))
-    wsp[:cin] = ws[0]
-    wsp[dims.pulse_channels_eff + 1] = np.asarray(folded["wn.start.b"], dtype=np.float64)   # the constant channel
-    prod = np.einsum("kc,tcn->tkn", wsp, w0)                       # (3, 8, 2C)
-    nt = (C + 31) // 32
-    wp = np.zeros((3, 8, 2, nt * 32))
-    wp[:, :, 0, :C] = prod[:, :, :C]
-    wp[:, :, 1, :C] = prod[:, :, C:]
-    wp = wp.reshape(3, 4, 2, 2, nt, 16, 2)                         # tap, kq, step, tanh|sigmoid, tile, n, e
-    out = {"wn.conv1D_0.start_fold": np.ascontiguousarray(wp.transpose(4, 0, 6, 1, 5, 3, 2).reshape(nt, 3, 512))}
-    if L > 1:
-        if not fold_skip or "wn.res_skip_0.fold" not in fold_skip:
-            return {}
-        n_out = dims.wn_out_channels
-        wr = np.asarray(folded["wn.res_skip_0.w"], dtype=np.float64)[0]
-        proj = np.asarray(fold_skip["__proj_0"], dtype=np.float64)    # Ws_0 We (C, n_out)
-        ext = np.zeros((C + 16, C + n_out))
-        ext[:C, :C] = wr[:, :C]
-        ext[:C, C:] = proj
-        ext[C:C + 8, :C] = wsp
-        out["wn.res_skip_0.fold_start"] = pack_resskip_weights(ext[None])
-        out["wn.res_skip_0.fold_start_wide"] = pack_resskip_wide_weights(ext[None])
-        if split_f16 and C + n_out <= 384:
-            out["wn.res_skip_0.fold_start_f16"] = pack_resskip_f16_weights(ext[None])
-        if C + n_out <= 384:
-            out["wn.res_skip_0.fold_start_wave"] = pack_resskip_wave_weights(ext[None])
-    return out
-
-
-def tensor_table(config, raw_weights, wavetables, split_f16=False):
-    """name -> float32 array of everything mbx_create needs: folded weights + constant tables (+ with ``split_f16`` the
-    fp16-split images of the res/skip layers for the opt-in precision mode)."""
-    dims = ModelDims(config)
-    mb = config["mbexwn_config"]
-    mbc = mb["multi_band_config"]
-    wn_norm = mb.get("pp_mod_subnet", {}).get("use_weight_norm", None)
-    out = dict(merge_channel_groups(fold_weights(raw_weights, wavenet_weight_norm=wn_norm,
-                                                 wavenet_equalized_lr=dims.wn_equalized_lr), dims))
-    # F0-net: the exact (float64) weight-norm fold of every layer, handed over as pairs of float32 words
-    # (mbx_config.f0_accumulate = MBX_F0_ACC_F64: csrc/conv_mel.hip::conv1d_f64_tile reads them as doubles)
-    from .weights import fold_weight_norm_f64
-    for key in raw_weights:
-        if key.startswith("PulsPar_Layer_") and key.endswith(".v") and key[:-2] + ".g" in raw_weights:
-            w64 = np.ascontiguousarray(fold_weight_norm_f64(raw_weights[key], raw_weights[key[:-2] + ".g"]))
-            out[key[:-2] + ".w64"] = w64.view(np.float32).reshape(w64.shape + (2,))
-    _, syn = tb.pqmf_filters(int(mbc["subbands"]), int(mbc["taps"]), float(mbc["cutoff_ratio"]), float(mbc["beta"]),
-                             mbc.get("max_band", None))
-    out["table.pqmf_syn"] = syn
-    if dims.pulse_pqmf:                                            # analysis bank in front of the WaveNet
-        pq = dims.pulse_pqmf
-        out["table.pulse_ana"] = tb.pqmf_filters(int(pq["subbands"]), int(pq["taps"]), float(pq["cutoff_ratio"]),
-                                                 float(pq["beta"]), pq.get("max_band", None))[0]
-    # (several WaveNet blocks / in-block upsampling run the library's generic kernels: no operand-order images)
-    if not dims.wn_multi and out["wn.end.w"].shape[0] == 1 and out["wn.end.w"].shape[2] <= 32:
-        out["wn.end.packed"] = pack_end_weights(out["wn.end.w"])
-        fs = fold_skip_weights(out, dims.wn_layers, dims.wn_channels, split_f16=split_f16)
-        if dims.wn_kernel_size == 3:
-            out.update(fold_start_weights(out, dims, fs, split_f16=split_f16))
-        fs.pop("__proj_0", None)
-        out.update(fs)
-    for ll in range(0 if dims.wn_multi else dims.wn_layers):
-        out[f"wn.res_skip_{ll}.packed"] = pack_resskip_weights(out[f"wn.res_skip_{ll}.w"])
-    if dims.wn_kernel_size == 3 and not dims.wn_multi:
-        for ll in range(dims.wn_layers):
-            out[f"wn.conv1D_{ll}.wino4w"] = pack_winograd4w_weights(out[f"wn.conv1D_{ll}.w"])
-            out[f"wn.conv1D_{ll}.wino2w"] = pack_winograd2w_weights(out[f"wn.conv1D_{ll}.w"])
-            if split_f16 and ll >= 1:
-                out[f"wn.conv1D_{ll}.gate_f16"] = pack_gate_f16_weights(out[f"wn.conv1D_{ll}.w"])
-    if dims.wn_multi:
-        # several blocks: the library's block runner takes the packed res/skip weights and the F(4,3) images per block
-        from .weights import block_prefix
-        for bb in range(dims.n_wn_blocks):
-            pre = block_prefix(bb)
-            for ll in range(dims.wn_layers):
-                out[f"{pre}res_skip_{ll}.packed"] = pack_resskip_weights(out[f"{pre}res_skip_{ll}.w"])
-                if dims.wn_kernel_size == 3 and dims.wn_padding == "SAME":
-                    out[f"{pre}conv1D_{ll}.wino4w"] = pack_winograd4w_weights(out[f"{pre}conv1D_{ll}.w"])
-    out["table.hann"] = tb.hann_periodic_f32(dims.stft_win)
-    out["table.inv_win"] = tb.inverse_stft_window_f32(dims.stft_win, dims.hop_size)
-    out["table.wavetables"] = np.ascontiguousarray(wavetables.tables, dtype=np.float32)
-    if dims.ps_env_order_scale and not mb.get("psns_use_cepstral_loss_constraint", False) and not dims.no_envelope:
-        logs, rows = tb.cepstral_windows(dims.ps_env_order_scale, dims.sample_rate, dims.f0_min, dims.f0_max, dims.n_ceps)
-        out["table.ceps_windows"] = rows
-        out["table.ceps_log10f0"] = logs
-        out["table.f0_smooth"] = tb.f0_smoothing_kernel(dims.hop_size)
-    if mb.get("normalize_rms_from_mell", False):
-        from .norm_mel import NormMel
-        nm = NormMel(config)
-        out["table.nm_inv_enorm"] = nm.inv_enorm
-        out["table.nm_gwin"] = nm.gwin
-        out["table.nm_smooth_win"] = nm.smooth_syn_win
-        if nm.use_pinv:
-            out["table.nm_pinv"] = nm.pinv
-    return {kk: np.ascontiguousarray(vv, dtype=np.float32) for kk, vv in out.items()}
-
-
 # ------------------------------------------------------------------------------------------------
 # the engine
 # ------------------------------------------------------------------------------------------------
@@ -563,6 +240,16 @@ def forward_entry_point(state, active, control, f0, transposed):
     if state:
         return "mbx_forward_ex" if active or control else "mbx_forward_stream"
     return "mbx_forward_ex" if f0 or transposed or control else "mbx_forward"
+
+
+def _kernel_report(gate_kernel, n_gate, rep, n_resskip):
+    """The five-key kernel report (MBExWNEngine.kernel_report) from the gate kernel codes of n_gate layers and a structure
+    with resskip_kernel[n_resskip], gate_block_channels, tail_kernel and tail_folded: mbx_kernel_report_info or mbx_plan_info."""
+    resskip = [RESSKIP_KERNEL_NAMES[rep.resskip_kernel[ll]] for ll in range(n_resskip)]
+    return {"gate_kernels": [GATE_KERNEL_NAMES[gate_kernel[ll]] for ll in range(n_gate)],
+            "gate_block_channels": [int(rep.gate_block_channels[ll]) for ll in range(n_gate)],
+            "resskip_kernels": [kk for kk in resskip if kk != "none"],
+            "tail_kernel": TAIL_KERNEL_NAMES[rep.tail_kernel], "tail_folded": bool(rep.tail_folded)}
 
 
 class MBExWNEngine:
@@ -615,9 +302,7 @@ class MBExWNEngine:
         self._handle = handle
         self._workspace = None
         self._last_shape = None
-        self._flac_tables = None
-        self._env_centres = None                            # formant shift: the device centre table and the scratch (forward)
-        self._env_mel = None
+        self._env_mel = None                                # formant shift: the scratch of the warped rows (forward)
 
     def close(self):
         if getattr(self, "_handle", None):
@@ -645,6 +330,13 @@ class MBExWNEngine:
 
     def _stream(self):
         return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _is(self, t, dtype, shape=None, contiguous=False):
+        """True when t is a tensor of that dtype on the engine's device -- of that shape if one is given (None in it: any
+        size), contiguous if that is asked for.  The one predicate of the argument checks below."""
+        return (self._torch.is_tensor(t) and t.dtype == dtype and t.device == self.device and
+                (shape is None or (t.dim() == len(shape) and all(ss is None or ss == dd for ss, dd in zip(shape, t.shape)))) and
+                (not contiguous or t.is_contiguous()))
 
     def workspace_bytes(self, batch, max_frames):
         return int(self._lib.mbx_workspace_size(self._handle, batch, max_frames))
@@ -695,7 +387,7 @@ class MBExWNEngine:
         torch = self._torch
         if mel.dim() != 3 or mel.shape[2] != self.dims.mel_channels:
             raise ValueError(f"mel must be (batch, frames, {self.dims.mel_channels})")
-        if mel.device != self.device or mel.dtype != torch.float32:
+        if not self._is(mel, torch.float32):
             raise ValueError("mel must be a float32 tensor on the engine's device")
         mel = mel.contiguous()
         B, T = int(mel.shape[0]), int(mel.shape[1])
@@ -709,15 +401,14 @@ class MBExWNEngine:
         if self.dims.noise_sigma:
             if noise is None:
                 raise ValueError("noise is required (the noise channel is an explicit input, see SURVEY.md F7)")
-            if tuple(noise.shape) != (B, steps) or noise.dtype != torch.float32 or noise.device != self.device:
+            if not self._is(noise, torch.float32, (B, steps)):
                 raise ValueError(f"noise must be float32 ({B}, {steps}) on the engine's device")
             noise = noise.contiguous()
         if n_frames is not None:
-            if n_frames.dtype != torch.int32 or tuple(n_frames.shape) != (B,) or n_frames.device != self.device:
+            if not self._is(n_frames, torch.int32, (B,)):
                 raise ValueError("n_frames must be an int32 tensor of shape (batch,) on the engine's device")
             n_frames = n_frames.contiguous()
-        if formant is not None and (not torch.is_tensor(formant) or formant.dtype != torch.float32 or
-                                    tuple(formant.shape) != (B, T) or formant.device != self.device):
+        if formant is not None and not self._is(formant, torch.float32, (B, T)):
             raise ValueError(f"formant must be a float32 tensor of shape ({B}, {T}) on the engine's device")
         if out is None:
             out = torch.empty((B, T * self.dims.hop_size), dtype=torch.float32, device=self.device)
@@ -767,13 +458,12 @@ class MBExWNEngine:
             opt.transposition = 1.0
             opt.f0_frames, opt.f0_scale, opt.f0_item_mask = (None if cc is None else cc.data_ptr() for cc in control)
         if stream_state is not None:
-            if stream_state.dtype != torch.int32 or tuple(stream_state.shape) != (B, 6) or stream_state.device != self.device:
+            if not self._is(stream_state, torch.int32, (B, 6)):
                 raise ValueError("stream_state must be an int32 tensor of shape (batch, 6) on the engine's device")
             stream_state = stream_state.contiguous()
             if state_out is None:
                 state_out = torch.empty_like(stream_state)
-            elif (state_out.dtype != torch.int32 or tuple(state_out.shape) != (B, 6) or state_out.device != self.device or
-                  not state_out.is_contiguous()):
+            elif not self._is(state_out, torch.int32, (B, 6), contiguous=True):
                 raise ValueError("state_out must be a contiguous int32 tensor of shape (batch, 6) on the engine's device")
             if active is None and (wavenet is not None or carry is not None or layers is not None or frontend is not None):
                 raise ValueError("wavenet / carry / layers describe regions inside the active one: pass active as well")
@@ -786,8 +476,7 @@ class MBExWNEngine:
                 raise ValueError("transposition must be positive")
             opt.transposition = float(transposition)
             if f0 is not None:
-                if (f0.dtype != torch.float32 or tuple(f0.shape) != (B, T * self.dims.pulse_per_frame) or
-                        f0.device != self.device):
+                if not self._is(f0, torch.float32, (B, T * self.dims.pulse_per_frame)):
                     raise ValueError(f"f0 must be a float32 tensor of shape ({B}, {T * self.dims.pulse_per_frame}) on the "
                                      "engine's device")
                 f0 = f0.contiguous()
@@ -799,7 +488,7 @@ class MBExWNEngine:
         """The streaming-window arguments of a forward, checked and written into opt (the tensors they point at: keep)."""
         torch = self._torch
         a0, act = int(active[0]), active[1]
-        if act.dtype != torch.int32 or tuple(act.shape) != (B,) or act.device != self.device or not 0 <= a0 < T:
+        if not self._is(act, torch.int32, (B,)) or not 0 <= a0 < T:
             raise ValueError("active = (begin frame inside the window, int32 tensor of shape (batch,) on the device)")
         act = act.contiguous()
         keep.append(act)
@@ -808,7 +497,7 @@ class MBExWNEngine:
             opt.active_max_frames = int(active[2])
         if wavenet is not None:
             w0, wfr = int(wavenet[0]), wavenet[1]
-            if wfr.dtype != torch.int32 or tuple(wfr.shape) != (B,) or wfr.device != self.device or not a0 <= w0 < T:
+            if not self._is(wfr, torch.int32, (B,)) or not a0 <= w0 < T:
                 raise ValueError("wavenet = (begin frame inside the active region, int32 tensor (batch,) on the device)")
             wfr = wfr.contiguous()
             keep.append(wfr)
@@ -817,20 +506,18 @@ class MBExWNEngine:
                 opt.wn_max_frames = int(wavenet[2])
         if carry is not None:
             store, desc = carry
-            if (store.dtype != torch.float32 or store.dim() != 3 or store.shape[2] != self.dims.subbands or
-                    store.device != self.device or not store.is_contiguous()):
+            if not self._is(store, torch.float32, (None, None, self.dims.subbands), contiguous=True):
                 raise ValueError("carry store must be a contiguous float32 tensor (slots, rows, subbands) on the device")
-            if desc.dtype != torch.int32 or tuple(desc.shape) != (B, 5) or desc.device != self.device:
+            if not self._is(desc, torch.int32, (B, 5)):
                 raise ValueError("carry descriptors must be an int32 tensor of shape (batch, 5) on the device")
             desc = desc.contiguous()
             keep.append(desc)
             opt.sub_store, opt.sub_store_rows, opt.sub_carry = store.data_ptr(), int(store.shape[1]), desc.data_ptr()
         if layers is not None:
             lstore, ldesc, lrows = layers
-            if (lstore.dtype != torch.float32 or lstore.dim() != 2 or lstore.device != self.device or
-                    not lstore.is_contiguous()):
+            if not self._is(lstore, torch.float32, (None, None), contiguous=True):
                 raise ValueError("layer store must be a contiguous float32 tensor (slots, floats) on the device")
-            if ldesc.dtype != torch.int32 or tuple(ldesc.shape) != (B, 3) or ldesc.device != self.device:
+            if not self._is(ldesc, torch.int32, (B, 3)):
                 raise ValueError("layer descriptors must be an int32 tensor of shape (batch, 3) on the device")
             ldesc = ldesc.contiguous()
             keep.append(ldesc)
@@ -839,11 +526,10 @@ class MBExWNEngine:
         if frontend is not None:
             ring, fpos, fnew, fmargin = frontend[:4]
             opt.fe_end_frames = int(frontend[4]) if len(frontend) > 4 else 0
-            if (ring.dtype != torch.float32 or ring.dim() != 3 or ring.device != self.device or not ring.is_contiguous() or
-                    ring.shape[2] != self.frontend_frame_floats):
+            if not self._is(ring, torch.float32, (None, None, self.frontend_frame_floats), contiguous=True):
                 raise ValueError("front-end ring must be a contiguous float32 tensor (slots, ring frames, "
                                  f"{self.frontend_frame_floats}) on the device")
-            if fpos.dtype != torch.int32 or tuple(fpos.shape) != (B,) or fpos.device != self.device or carry is None:
+            if not self._is(fpos, torch.int32, (B,)) or carry is None:
                 raise ValueError("front-end positions must be an int32 tensor (batch,) on the device; carry is required")
             fpos = fpos.contiguous()
             keep.append(fpos)
@@ -861,20 +547,16 @@ class MBExWNEngine:
         if f0_item_mask is not None and f0_frames is None:
             raise ValueError("f0_item_mask needs f0_frames")
         for name, rows in (("f0_frames", f0_frames), ("f0_scale", f0_scale)):
-            if rows is not None and (not torch.is_tensor(rows) or rows.dtype != torch.float32 or tuple(rows.shape) != (B, T) or
-                                     rows.device != self.device):
+            if rows is not None and not self._is(rows, torch.float32, (B, T)):
                 raise ValueError(f"{name} must be a float32 tensor of shape ({B}, {T}) on the engine's device")
-        if f0_item_mask is not None and (not torch.is_tensor(f0_item_mask) or f0_item_mask.dtype != torch.int32 or
-                                         tuple(f0_item_mask.shape) != (B,) or f0_item_mask.device != self.device):
+        if f0_item_mask is not None and not self._is(f0_item_mask, torch.int32, (B,)):
             raise ValueError(f"f0_item_mask must be an int32 tensor of shape ({B},) on the engine's device")
         return tuple(None if cc is None else cc.contiguous() for cc in (f0_frames, f0_scale, f0_item_mask))
 
     def _envelope_centres(self):
         """The device table of the mel channels' centre frequencies (envelope.channel_centres of the model's analysis)."""
-        if self._env_centres is None:
-            from .envelope import channel_centres
-            self._env_centres = self._torch.as_tensor(channel_centres(self.config["preprocess_config"]), device=self.device)
-        return self._env_centres
+        from .envelope import device_centres
+        return device_centres(self.config["preprocess_config"], self.device)
 
     def _envelope_scratch(self, floats):
         """The warped mel rows of a forward with ``formant`` (env_mel of mbxe_forward; the stage "mel_env"): the engine's,
@@ -885,30 +567,18 @@ class MBExWNEngine:
 
     def warp_envelope(self, mel, factors, n_frames=None):
         """The formant shift on its own (``mbxe_warp_envelope``, include/mbexwn_envelope.h): mel float32 cuda (B, T,
-        mel_channels) -- a view with a batch stride of its own is passed as it is --, factors float32 cuda (B, T), n_frames
+        mel_channels) -- a view with a batch stride of its own is passed as it is, the result then has that stride --, factors float32 cuda (B, T), n_frames
         optional int32 cuda (B,) -> the warped rows (B, T, mel_channels), bit-equal to envelope.warp_envelope_host."""
-        torch = self._torch
-        n = self.dims.mel_channels
-        if (not torch.is_tensor(mel) or mel.dim() != 3 or mel.shape[2] != n or mel.dtype != torch.float32 or
-                mel.device != self.device):
+        from .envelope import warp_envelope_device
+        torch, n = self._torch, self.dims.mel_channels
+        if not self._is(mel, torch.float32, (None, None, n)):
             raise ValueError(f"mel must be a float32 tensor (batch, frames, {n}) on the engine's device")
         B, T = int(mel.shape[0]), int(mel.shape[1])
-        if not torch.is_tensor(factors) or factors.dtype != torch.float32 or tuple(factors.shape) != (B, T) or factors.device != self.device:
+        if not self._is(factors, torch.float32, (B, T)):
             raise ValueError(f"factors must be a float32 tensor of shape ({B}, {T}) on the engine's device")
-        if n_frames is not None and (n_frames.dtype != torch.int32 or tuple(n_frames.shape) != (B,) or n_frames.device != self.device):
+        if n_frames is not None and not self._is(n_frames, torch.int32, (B,)):
             raise ValueError("n_frames must be an int32 tensor of shape (batch,) on the engine's device")
-        out = torch.empty((B, T, n), dtype=torch.float32, device=self.device)
-        if B == 0 or T == 0:
-            return out
-        if mel.stride(2) != 1 or mel.stride(1) != n or (B > 1 and mel.stride(0) < T * n):
-            mel = mel.contiguous()
-        factors = factors.contiguous()
-        stride = int(mel.stride(0)) if B > 1 else T * n
-        with torch.cuda.device(self.device):
-            _check(self._lib.mbxe_warp_envelope(mel.data_ptr(), stride, B, n_frames.contiguous().data_ptr() if n_frames is not None else None,
-                                                T, n, self._envelope_centres().data_ptr(), factors.data_ptr(), out.data_ptr(),
-                                                self._stream()))
-        return out
+        return warp_envelope_device(mel, factors, self._envelope_centres(), n_frames)
 
     def track_f0(self, audio, n_samples, centres, n_frames, **params):
         """F0 and periodicity of every frame from the audio itself (``mbxp_track_f0``, include/mbexwn_pitch.h) on the
@@ -929,38 +599,12 @@ class MBExWNEngine:
         for them), then only the bytes the frames take, and the int16 samples for the MD5.  Returns an
         :class:`EncodedFlac`; with ``wait=False`` the copies may still be in flight (``EncodedFlac.wait()`` before reading)."""
         from . import flac
-        torch = self._torch
         if compression not in flac.COMPRESSIONS:
             raise ValueError(f"compression must be one of {flac.COMPRESSIONS}, got {compression!r}")
-        if audio.dim() != 2 or audio.dtype != torch.float32 or audio.device != self.device:
+        if not self._is(audio, self._torch.float32, (None, None)):
             raise ValueError("audio must be a float32 tensor (batch, stride) on the engine's device")
-        audio = audio.contiguous()
-        B, stride = int(audio.shape[0]), int(audio.shape[1])
-        counts = [int(nn) for nn in n_samples]
-        if len(counts) != B:
-            raise ValueError(f"n_samples must hold one count per item ({B})")
-        rate = int(self.dims.sample_rate if sample_rate is None else sample_rate)
-        offsets = np.zeros(B + 1, dtype=np.int64)
-        np.cumsum([flac.frames_bytes(nn) for nn in counts], out=offsets[1:])
-        total = int(offsets[-1])
-        if self._flac_tables is None:
-            self._flac_tables = torch.as_tensor(flac.crc16_device_tables().view(np.int16)).to(self.device)
-        out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
-        max_abs = torch.empty(max(B, 1), dtype=torch.float32, device=self.device)
-        counts_c = (ctypes.c_int64 * max(B, 1))(*counts)
-        if compression == "fixed":
-            return self._encode_flac16_fixed(audio, counts, counts_c, rate, out, total, max_abs, wait)
-        with torch.cuda.device(self.device):
-            _check(self._lib.mbx_encode_flac16(audio.data_ptr(), stride, B, counts_c, rate, self._flac_tables.data_ptr(),
-                                               out.data_ptr(), total, max_abs.data_ptr(), self._stream()))
-            host = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
-            host.copy_(out, non_blocking=True)
-            host_max = torch.empty(max_abs.shape, dtype=torch.float32, pin_memory=True)
-            host_max.copy_(max_abs, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record(torch.cuda.current_stream(self.device))
-        res = EncodedFlac(host, offsets, host_max, counts, rate, event)
-        return res.wait() if wait else res
+        return flac.encode_device(audio, n_samples, self.dims.sample_rate if sample_rate is None else sample_rate,
+                                  compression=compression, wait=wait)
 
     def keyed_noise(self, seeds, item_keys, counts, first_step=None, out=None):
         """Keyed N(0,1) noise (include/mbexwn_noise.h, ``mbxn_fill_normal``): row b holds the values ``first_step[b] ..
@@ -969,76 +613,8 @@ class MBExWNEngine:
         float32 device tensor (B, max(counts)); ``out``: a zeroed float32 device tensor (B, stride >= max(counts)) to fill
         instead.  A value depends on its seed, key and step alone: not on the batch, the row or the window it is asked
         in."""
-        torch = self._torch
-        counts = [int(nn) for nn in counts]
-        B = len(counts)
-        keys = [int(kk) for kk in item_keys]
-        seeds = [int(seeds)] * B if np.ndim(seeds) == 0 else [int(ss) for ss in seeds]
-        first = [0] * B if first_step is None else [int(ff) for ff in first_step]
-        if not (len(keys) == len(seeds) == len(first) == B):
-            raise ValueError(f"keyed_noise: one seed, item key and first step per count ({B})")
-        if any(nn < 0 for nn in counts) or any(ff < 0 for ff in first):
-            raise ValueError("keyed_noise: counts and first_step must not be negative")
-        top = max(counts, default=0)
-        if out is None:
-            out = torch.zeros((B, top), dtype=torch.float32, device=self.device)
-        elif (out.dim() != 2 or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous()
-              or int(out.shape[0]) != B or int(out.shape[1]) < top):
-            raise ValueError(f"keyed_noise: out must be a contiguous float32 tensor ({B}, >= {top}) on the engine's device")
-        if B == 0 or top == 0:
-            return out
-        mask = (1 << 64) - 1
-        table = np.empty((B, 4), dtype=np.uint64)            # one upload: seed, item key, first step, count
-        table[:, 0] = [ss & mask for ss in seeds]
-        table[:, 1] = [kk & mask for kk in keys]
-        table[:, 2] = first
-        table[:, 3] = counts
-        dev = torch.as_tensor(table.view(np.int64)).to(self.device)
-        keys_dev = dev[:, :2].contiguous()
-        first_dev = dev[:, 2].contiguous()
-        counts_dev = dev[:, 3].to(torch.int32)
-        with torch.cuda.device(self.device):
-            _check(self._lib.mbxn_fill_normal(out.data_ptr(), int(out.shape[1]), B, keys_dev.data_ptr(), first_dev.data_ptr(),
-                                              counts_dev.data_ptr(), top, self._stream()))
-        return out
-
-    def _encode_flac16_fixed(self, audio, counts, counts_c, rate, out, capacity, max_abs, wait):
-        """The compressed half of :meth:`encode_flac16`: frames packed densely, so the lengths are copied back first and
-        say how many bytes of ``out`` to copy."""
-        from . import flac
-        torch = self._torch
-        B, stride = int(audio.shape[0]), int(audio.shape[1])
-        frame_counts = [-(-nn // flac.BLOCK) for nn in counts]
-        frames = sum(frame_counts)
-        frame_bytes = torch.empty(max(frames, 1), dtype=torch.int32, device=self.device)
-        workspace = torch.empty(3 * frames + 1, dtype=torch.int64, device=self.device)
-        pcm = torch.empty((max(B, 1), max(stride, 1)), dtype=torch.int16, device=self.device)
-        with torch.cuda.device(self.device):
-            _check(self._lib.mbxf_encode_flac16_fixed(audio.data_ptr(), stride, B, counts_c, rate, self._flac_tables.data_ptr(),
-                                                      out.data_ptr(), capacity, frame_bytes.data_ptr(), workspace.data_ptr(),
-                                                      pcm.data_ptr(), max_abs.data_ptr(), self._stream()))
-            host_lengths = torch.empty(frame_bytes.shape, dtype=torch.int32, pin_memory=True)
-            host_lengths.copy_(frame_bytes, non_blocking=True)
-            first = torch.cuda.Event()
-            first.record(torch.cuda.current_stream(self.device))
-            host_pcm = torch.empty(pcm.shape, dtype=torch.int16, pin_memory=True)
-            host_pcm.copy_(pcm, non_blocking=True)
-            host_max = torch.empty(max_abs.shape, dtype=torch.float32, pin_memory=True)
-            host_max.copy_(max_abs, non_blocking=True)
-            first.synchronize()                              # the lengths say how many bytes the frames take
-            lengths = host_lengths.numpy()[:frames].astype(np.int64)
-            used = int(lengths.sum())
-            if used > capacity:
-                raise RuntimeError("mbexwn_hip: the frame lengths exceed the output buffer")
-            host = torch.empty(max(used, 1), dtype=torch.uint8, pin_memory=True)
-            host.copy_(out[:max(used, 1)], non_blocking=True)
-            event = torch.cuda.Event()
-            event.record(torch.cuda.current_stream(self.device))
-        bounds = np.zeros(B + 1, dtype=np.int64)
-        np.cumsum(frame_counts, out=bounds[1:])
-        offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)[bounds]
-        res = EncodedFlac(host, offsets, host_max, counts, rate, event, frame_lengths=lengths, frame_bounds=bounds, pcm=host_pcm)
-        return res.wait() if wait else res
+        from .noise import fill_normal_device
+        return fill_normal_device(seeds, item_keys, counts, first_step=first_step, out=out, device=self.device)
 
     def window_advance(self, mel_window, mel_new, noise_window=None, noise_new=None):
         """mbx_window_advance: shift the device-resident windows (B, T, mel_channels) / (B, T*steps_per_frame) left by the
@@ -1046,7 +622,7 @@ class MBExWNEngine:
         torch = self._torch
         B, T, step = int(mel_window.shape[0]), int(mel_window.shape[1]), int(mel_new.shape[1])
         for tt in (mel_window, mel_new, noise_window, noise_new):
-            if tt is not None and (tt.dtype != torch.float32 or tt.device != self.device or not tt.is_contiguous()):
+            if tt is not None and not self._is(tt, torch.float32, contiguous=True):
                 raise ValueError("windows and new frames must be contiguous float32 tensors on the engine's device")
         if tuple(mel_new.shape) != (B, step, self.dims.mel_channels) or mel_window.shape[2] != self.dims.mel_channels:
             raise ValueError("mel_new must be (batch, step, mel_channels)")
@@ -1085,7 +661,8 @@ class MBExWNEngine:
         """mbx_emit_rows: samples [first, first + count) of every row of the device tensor `audio` (B, n) into the pinned
         host tensor host_out (B, count) as one strided copy on the engine's stream."""
         B, n = int(audio.shape[0]), int(audio.shape[1])
-        if tuple(host_out.shape) != (B, count) or not host_out.is_contiguous() or not audio.is_contiguous():
+        if (tuple(host_out.shape) != (B, count) or not host_out.is_contiguous() or
+                not self._is(audio, self._torch.float32, contiguous=True)):
             raise ValueError("emit_rows: host_out must be a contiguous (batch, count) tensor, audio contiguous")
         _check(self._lib.mbx_emit_rows(self._handle, audio.data_ptr(), n, B, int(first), int(count), host_out.data_ptr(),
                                        self._stream()))
@@ -1145,7 +722,6 @@ class MBExWNEngine:
         rep = mbx_kernel_report_info()
         rep.struct_size = ctypes.sizeof(mbx_kernel_report_info)
         _check(self._lib.mbx_kernel_report(self._handle, ctypes.byref(rep)))
-        resskip = [RESSKIP_KERNEL_NAMES[rep.resskip_kernel[ll]] for ll in range(rep.n_resskip_layers)]
         return {"requested": _CONV_FORM_NAMES[info.requested], "form": _CONV_FORM_NAMES[info.form],
                 "stream_form": _CONV_FORM_NAMES[info.stream_form], "calibrated": info.calibrated,
                 "batch_invariant": bool(info.batch_invariant), "fold_skip": bool(info.fold_skip),
@@ -1156,10 +732,7 @@ class MBExWNEngine:
                 "ref_max": float(info.ref_max), "threshold": float(info.threshold),
                 "err_split": None if info.err_split < 0 else float(info.err_split),
                 "split_rejected": bool(info.split_rejected), "f0_float64_chain": bool(info.f0_float64_chain),
-                "gate_kernels": [GATE_KERNEL_NAMES[info.gate_kernel[ll]] for ll in range(info.n_gate_layers)],
-                "resskip_kernels": [kk for kk in resskip if kk != "none"],
-                "tail_kernel": TAIL_KERNEL_NAMES[rep.tail_kernel], "tail_folded": bool(rep.tail_folded),
-                "gate_block_channels": [int(rep.gate_block_channels[ll]) for ll in range(info.n_gate_layers)]}
+                **_kernel_report(info.gate_kernel, info.n_gate_layers, rep, rep.n_resskip_layers)}
 
     def kernel_report(self):
         """What the most recent forward ran, per layer: ``gate_kernels``, ``gate_block_channels``, ``resskip_kernels``,
@@ -1193,11 +766,7 @@ class MBExWNEngine:
         """What a whole-item :meth:`forward` of this size would run, without launching (mbx_plan): the dict of
         :meth:`kernel_report`, which equals it after such a forward."""
         info = self._plan_info(batch, max_frames)
-        resskip = [RESSKIP_KERNEL_NAMES[info.resskip_kernel[ll]] for ll in range(info.n_layers)]
-        return {"gate_kernels": [GATE_KERNEL_NAMES[info.gate_kernel[ll]] for ll in range(info.n_layers)],
-                "gate_block_channels": [int(info.gate_block_channels[ll]) for ll in range(info.n_layers)],
-                "resskip_kernels": [kk for kk in resskip if kk != "none"],
-                "tail_kernel": TAIL_KERNEL_NAMES[info.tail_kernel], "tail_folded": bool(info.tail_folded)}
+        return _kernel_report(info.gate_kernel, info.n_layers, info, info.n_layers)
 
     def gate_form(self, batch, max_frames):
         """Which float32 implementation of the dilated convolution a forward of this size runs, as the library plans it
@@ -1320,7 +889,7 @@ class MBExWNEngine:
                                       "(the reference's generate_specenv has no cepstral VTF-net to run)")
         synth_length = int(synth_length) if F0 is None else int(np.asarray(F0).shape[1])
         mel, noise = self._prepare(spect, synth_length, noise)
-        hop, ppf = self.dims.hop_size, self.dims.pulse_per_frame
+        ppf = self.dims.pulse_per_frame
         B, T = int(mel.shape[0]), int(mel.shape[1])
         gain = None
         if self.normalizes_rms:                                      # 4th output: upsampled_rms (reference :539-542)
@@ -1333,17 +902,8 @@ class MBExWNEngine:
             f0_np[:, :nn] = src[:, :nn]
             f0_np[:, nn:] = src[:, -1:]
             f0_dev = torch.as_tensor(f0_np, device=self.device)
-        out = torch.empty((B, T * hop), dtype=torch.float32, device=self.device)
-        ws, need = self._get_workspace(B, T)
-        opt = mbx_forward_options()
-        opt.struct_size = ctypes.sizeof(mbx_forward_options)
-        opt.transposition = float(transposition_factor) if transposition_factor else 1.0
-        opt.f0 = f0_dev.data_ptr() if f0_dev is not None else None
-        _check(self._lib.mbx_forward_ex(self._handle, mel.data_ptr(), None, B, T,
-                                        noise.data_ptr() if noise is not None else None, out.data_ptr(), ws.data_ptr(),
-                                        need, ctypes.byref(opt), self._stream()))
-        self._last_shape = (B, T)
-        self.last_audio = out
+        self.last_audio = self.forward(mel, noise=noise, f0=f0_dev,
+                                       transposition=float(transposition_factor) if transposition_factor else 1.0)
         f0 = self.stage("f0").cpu().numpy()
         exc = self.stage("excitation").cpu().numpy()
         return f0, exc, self._envelope(B, T), gain

@@ -8,13 +8,13 @@ aligned, so a valid stream (magic, STREAMINFO with the MD5 of the samples, frame
 with numpy alone.  Any FLAC decoder reads the result; the files are the size of a wav.
 
 The layout of the frames and the headers are defined here once (frame_layout, frame_header, stream_header): ``encode``
-builds a stream from them, and the device encoder (csrc/flac_frames.hip through ``MBExWNEngine.encode_flac16``) writes the
+builds a stream from them, and the device encoder (csrc/flac_frames.hip through ``encode_device``) writes the
 same frames, in front of which ``write_frames`` / ``assemble`` put the header with the MD5 of the samples.
 
 ``compression="fixed"`` compresses: every frame takes the cheapest of FLAC's fixed predictors of orders 0-4 with
 partitioned Rice codes (``plan_fixed_frame`` makes the choices, DESIGN.md defines them), a CONSTANT sub-frame where all
 samples are equal, and stays VERBATIM where no predictor saves a bit.  The device encoder of csrc/flac_fixed.hip
-(``MBExWNEngine.encode_flac16(..., compression="fixed")``) writes the same bytes.  Frame lengths then come from the data:
+(``encode_device(..., compression="fixed")``) writes the same bytes.  Frame lengths then come from the data:
 ``stream_header`` / ``assemble`` / ``write_frames`` take them as a list.
 
 Format: https://xiph.org/flac/format.html (STREAMINFO, FRAME_HEADER, SUBFRAME_VERBATIM / _CONSTANT / _FIXED, RESIDUAL,
@@ -536,3 +536,139 @@ def write_frames(path, frames, n, rate, frame_lengths=None, pcm=None):
         fo.write(stream_header(n, rate, md5, frame_lengths=frame_lengths))
         fo.write(frames)
     return path
+
+
+# ------------------------------------------------------------------------------------------------
+# the device encoders (mbx_encode_flac16, mbxf_encode_flac16_fixed): no engine handle, only the library
+# ------------------------------------------------------------------------------------------------
+class EncodedFlac:
+    """What :func:`encode_device` (``MBExWNEngine.encode_flac16``) returns: the frames of every item in one pinned host buffer
+    (item b at ``offsets[b]:offsets[b + 1]``) and max |x| per item, behind the event of their device-to-host copies.  Compressed
+    frames (``compression="fixed"``) come with their lengths (``frame_lengths(b)``) and the int16 samples they hold (``pcm(b)``)."""
+
+    def __init__(self, host, offsets, max_abs, n_samples, rate, event, frame_lengths=None, frame_bounds=None, pcm=None):
+        self._host, self._host_max, self._event = host, max_abs, event
+        self.offsets, self.n_samples, self.rate = offsets, list(n_samples), rate
+        self._lengths, self._bounds, self._pcm = frame_lengths, frame_bounds, pcm
+        self.compression = "verbatim" if frame_lengths is None else "fixed"
+        self.max_abs = None
+
+    def wait(self):
+        if self._event is not None:
+            self._event.synchronize()
+            self._event = None
+            self.max_abs = self._host_max.numpy()[:len(self.n_samples)]
+        return self
+
+    def frames(self, b):
+        """The frames of item b (a numpy view of the pinned buffer)."""
+        self.wait()
+        return self._host.numpy()[self.offsets[b]:self.offsets[b + 1]]
+
+    def frame_lengths(self, b):
+        """The lengths of the compressed frames of item b; None for uncompressed frames (``frame_layout`` has those)."""
+        if self._lengths is None:
+            return None
+        return self._lengths[self._bounds[b]:self._bounds[b + 1]]
+
+    def pcm(self, b):
+        """The int16 samples the compressed frames of item b hold; None for uncompressed frames (they hold them as they are)."""
+        if self._pcm is None:
+            return None
+        self.wait()
+        return self._pcm.numpy()[b, :self.n_samples[b]]
+
+    def stream(self, b):
+        """The whole FLAC stream of item b (``assemble``); only for an item whose max |x| is finite -- any other goes
+        through the host writer, ``encode``."""
+        return assemble(self.frames(b), self.n_samples[b], self.rate, frame_lengths=self.frame_lengths(b), pcm=self.pcm(b))
+
+    def write(self, path, b):
+        """``stream(b)`` into a file (``write_frames``: the frames are written as they are)."""
+        return write_frames(path, self.frames(b), self.n_samples[b], self.rate, frame_lengths=self.frame_lengths(b),
+                            pcm=self.pcm(b))
+
+
+_device_tables = {}
+
+
+def device_crc_tables(device):
+    """``crc16_device_tables`` on the device (as int16 words), uploaded once per device."""
+    import torch
+    key = str(device)
+    if key not in _device_tables:
+        _device_tables[key] = torch.as_tensor(crc16_device_tables().view(np.int16)).to(device)
+    return _device_tables[key]
+
+
+def encode_device(audio, n_samples, rate, compression="verbatim", wait=True):
+    """The FLAC frames (``encode`` of the item without its 42-byte header) and max |x| of every item audio[b, :n_samples[b]]
+    of a float32 cuda batch (B, stride), encoded on the current stream of its device and copied into pinned host memory
+    asynchronously.  ``n_samples``: host integers.  ``compression="verbatim"`` is mbx_encode_flac16; ``"fixed"`` is
+    mbxf_encode_flac16_fixed (the bytes of ``encode(..., compression="fixed")``): frames packed densely, so their lengths come
+    back first (the call waits for them) and say how many bytes to copy, and the int16 samples come along for the MD5.
+    Returns an :class:`EncodedFlac`; with ``wait=False`` the copies may still be in flight."""
+    import ctypes
+    import torch
+    from .abi import _check, load_library
+    if compression not in COMPRESSIONS:
+        raise ValueError(f"compression must be one of {COMPRESSIONS}, got {compression!r}")
+    if not torch.is_tensor(audio) or audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_cuda:
+        raise ValueError("audio must be a float32 cuda tensor (batch, stride)")
+    dev = audio.device
+    audio = audio.contiguous()
+    B, stride = int(audio.shape[0]), int(audio.shape[1])
+    counts = [int(nn) for nn in n_samples]
+    if len(counts) != B:
+        raise ValueError(f"n_samples must hold one count per item ({B})")
+    rate = int(rate)
+    capacity = sum(frames_bytes(nn) for nn in counts)            # the VERBATIM frames: no compressed frame is longer
+    tables = device_crc_tables(dev)
+    out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
+    max_abs = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
+    counts_c = (ctypes.c_int64 * max(B, 1))(*counts)
+    lib = load_library()
+
+    def to_host(src):
+        host = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
+        host.copy_(src, non_blocking=True)
+        return host
+
+    def record():
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(dev))
+        return event
+
+    # no handle, hence no device of its own: the launch goes to the CURRENT device, which must be the buffers'
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if compression == "verbatim":
+            _check(lib.mbx_encode_flac16(audio.data_ptr(), stride, B, counts_c, rate, tables.data_ptr(), out.data_ptr(), capacity,
+                                         max_abs.data_ptr(), stream))
+            offsets = np.zeros(B + 1, dtype=np.int64)
+            np.cumsum([frames_bytes(nn) for nn in counts], out=offsets[1:])
+            res = EncodedFlac(to_host(out), offsets, to_host(max_abs), counts, rate, record())
+        else:
+            frame_counts = [-(-nn // BLOCK) for nn in counts]
+            frames = sum(frame_counts)
+            frame_bytes = torch.empty(max(frames, 1), dtype=torch.int32, device=dev)
+            workspace = torch.empty(3 * frames + 1, dtype=torch.int64, device=dev)
+            pcm = torch.empty((max(B, 1), max(stride, 1)), dtype=torch.int16, device=dev)
+            _check(lib.mbxf_encode_flac16_fixed(audio.data_ptr(), stride, B, counts_c, rate, tables.data_ptr(), out.data_ptr(),
+                                                capacity, frame_bytes.data_ptr(), workspace.data_ptr(), pcm.data_ptr(),
+                                                max_abs.data_ptr(), stream))
+            host_lengths = to_host(frame_bytes)
+            first = record()
+            host_pcm, host_max = to_host(pcm), to_host(max_abs)
+            first.synchronize()                              # the lengths say how many bytes the frames take
+            lengths = host_lengths.numpy()[:frames].astype(np.int64)
+            used = int(lengths.sum())
+            if used > capacity:
+                raise RuntimeError("mbexwn_hip: the frame lengths exceed the output buffer")
+            host = to_host(out[:max(used, 1)])
+            bounds = np.zeros(B + 1, dtype=np.int64)
+            np.cumsum(frame_counts, out=bounds[1:])
+            offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)[bounds]
+            res = EncodedFlac(host, offsets, host_max, counts, rate, record(), frame_lengths=lengths, frame_bounds=bounds,
+                              pcm=host_pcm)
+    return res.wait() if wait else res

@@ -1,6 +1,6 @@
 """Keyed noise: the N(0,1) draw of the model's noise channel as a function of (seed, item key, absolute step) alone.
 
-The device draws it (csrc/noise_keyed.hip through ``mbxn_fill_normal``, ``MBExWNEngine.keyed_noise``); this module is the
+The device draws it (csrc/noise_keyed.hip through ``mbxn_fill_normal``: ``fill_normal_device``); the rest of this module is the
 numpy mirror of the integer part of include/mbexwn_noise.h's definition, bit for bit, and a float64 evaluation of the float
 part for the tests.  Value ``s`` of an item (``s >= 0``) belongs to quad ``q = s >> 2``, lane ``j = s & 3``:
 
@@ -106,4 +106,47 @@ def normals_float32_port(seed, key, first, count):
     tt = TWO_PI_F32 * ub
     out = np.stack([rr * np.cos(tt), rr * np.sin(tt)], axis=-1).reshape(-1)[skip: skip + int(count)]
     assert out.dtype == np.float32
+    return out
+
+
+def fill_normal_device(seeds, item_keys, counts, first_step=None, out=None, device=None):
+    """Keyed N(0,1) noise on the GPU (include/mbexwn_noise.h, ``mbxn_fill_normal``): row b holds the values ``first_step[b] ..
+    first_step[b] + counts[b]`` of the item ``(seeds[b], item_keys[b])``, zeros behind them.  ``seeds`` / ``item_keys``:
+    integers (taken mod 2^64), one per item, or one seed for all; ``counts`` / ``first_step``: host integers.  Returns a
+    float32 tensor (B, max(counts)) on ``device`` (default: that of ``out``, else the current one); ``out``: a zeroed float32
+    tensor (B, stride >= max(counts)) there to fill instead.  Enqueued on the current stream of that device."""
+    import torch
+    from .abi import _check, load_library
+    counts = [int(nn) for nn in counts]
+    B = len(counts)
+    keys = [int(kk) for kk in item_keys]
+    seeds = [int(seeds)] * B if np.ndim(seeds) == 0 else [int(ss) for ss in seeds]
+    first = [0] * B if first_step is None else [int(ff) for ff in first_step]
+    if not (len(keys) == len(seeds) == len(first) == B):
+        raise ValueError(f"keyed_noise: one seed, item key and first step per count ({B})")
+    if any(nn < 0 for nn in counts) or any(ff < 0 for ff in first):
+        raise ValueError("keyed_noise: counts and first_step must not be negative")
+    top = max(counts, default=0)
+    if device is None:
+        device = out.device if torch.is_tensor(out) else torch.device("cuda", torch.cuda.current_device())
+    if out is None:
+        out = torch.zeros((B, top), dtype=torch.float32, device=device)
+    elif (not torch.is_tensor(out) or out.dim() != 2 or out.dtype != torch.float32 or out.device != device or not out.is_cuda
+          or not out.is_contiguous() or int(out.shape[0]) != B or int(out.shape[1]) < top):
+        raise ValueError(f"keyed_noise: out must be a contiguous float32 tensor ({B}, >= {top}) on the engine's device")
+    if B == 0 or top == 0:
+        return out
+    table = np.empty((B, 4), dtype=np.uint64)            # one upload: seed, item key, first step, count
+    table[:, 0] = [ss & MASK64 for ss in seeds]
+    table[:, 1] = [kk & MASK64 for kk in keys]
+    table[:, 2] = first
+    table[:, 3] = counts
+    dev = torch.as_tensor(table.view(np.int64)).to(device)
+    keys_dev = dev[:, :2].contiguous()
+    first_dev = dev[:, 2].contiguous()
+    counts_dev = dev[:, 3].to(torch.int32)
+    # no handle, hence no device of its own: the launch goes to the CURRENT device, which must be the buffers'
+    with torch.cuda.device(device):
+        _check(load_library().mbxn_fill_normal(out.data_ptr(), int(out.shape[1]), B, keys_dev.data_ptr(), first_dev.data_ptr(),
+                                               counts_dev.data_ptr(), top, torch.cuda.current_stream(device).cuda_stream))
     return out

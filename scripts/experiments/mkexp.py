@@ -389,8 +389,8 @@ PATCHES = {
          '            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");\n            GW_STAMP(s1_);\n            __syncthreads();                   // ... for every wave; and every wave is past tap g - 1\n            GW_STAMP(s2_);\n            if (tap == 0 && !last) issue_a(kt + 1);\n            if (g + 3 < ntap) issue_b(g + 3);\n            GW_STAMP(s3_);'),
         ('                    accx[rt][c] = GH_MFMA(al, bh[c], accx[rt][c]);\n                }\n            }\n        }\n    }\n\n    // ---- epilogue (as in wn_gate_f16_kernel): main + 2^-11 cross, conditioning, gate, store',
          '                    accx[rt][c] = GH_MFMA(al, bh[c], accx[rt][c]);\n                }\n            }\n            GW_STAMP(s4_);\n            aw_ += s1_ - s0_; ab_ += s2_ - s1_; ai_ += s3_ - s2_; ac_ += s4_ - s3_;\n        }\n    }\n    GW_STAMP(gt2_);\n\n    // ---- epilogue (as in wn_gate_f16_kernel): main + 2^-11 cross, conditioning, gate, store'),
-        ('            if (ch_ok && row < rows) *reinterpret_cast<float2 *>(obase + (long long)row * p.ldo) = res[v];\n        }\n    }\n}\n\n// a.w must point at the image of engine.pack_gate_f16_weights',
-         '            if (ch_ok && row < rows) *reinterpret_cast<float2 *>(obase + (long long)row * p.ldo) = res[v];\n        }\n    }\n    GW_STAMP(gt3_);\n    if (lane == 0 && blockIdx.x < 8192) {\n        unsigned long long *o_ = g_gw_stamps + ((long long)blockIdx.x * 8 + wave) * 8;\n        o_[0] = gt0_; o_[1] = gt1_; o_[2] = gt2_; o_[3] = gt3_; o_[4] = aw_; o_[5] = ab_; o_[6] = ai_; o_[7] = ac_;\n    }\n}\n\n// a.w must point at the image of engine.pack_gate_f16_weights'),
+        ('            if (ch_ok && row < rows) *reinterpret_cast<float2 *>(obase + (long long)row * p.ldo) = res[v];\n        }\n    }\n}\n\n// a.w must point at the image of packing.pack_gate_f16_weights',
+         '            if (ch_ok && row < rows) *reinterpret_cast<float2 *>(obase + (long long)row * p.ldo) = res[v];\n        }\n    }\n    GW_STAMP(gt3_);\n    if (lane == 0 && blockIdx.x < 8192) {\n        unsigned long long *o_ = g_gw_stamps + ((long long)blockIdx.x * 8 + wave) * 8;\n        o_[0] = gt0_; o_[1] = gt1_; o_[2] = gt2_; o_[3] = gt3_; o_[4] = aw_; o_[5] = ab_; o_[6] = ai_; o_[7] = ac_;\n    }\n}\n\n// a.w must point at the image of packing.pack_gate_f16_weights'),
         ('}  // namespace mbx\n',
          '}  // namespace mbx\n\nextern "C" int mbx_exp_stamps(void *dst, size_t bytes) {\n    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(mbx::g_gw_stamps), bytes, 0, hipMemcpyDeviceToHost);\n}\n'),
     ],

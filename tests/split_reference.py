@@ -9,7 +9,7 @@ Gate (layers >= 1): a main accumulator (bias + hi_h hi_w) and a cross accumulato
 All sums in float32 (numpy's float32 matrix product: another order than the MFMA's, the same arithmetic).  The hidden state is
 carried between layers as fp16 planes, hi + 2^-11 lo', with ceil8(C) columns, the padding zero.  Layer 0's gate (the start
 convolution folded in, float32) and the tail (the last layer's share of the end convolution, float32) are the port's / a float32
-product.  The weights are UNPACKED from the images of engine.pack_resskip_f16_weights / pack_gate_f16_weights, not split again:
+product.  The weights are UNPACKED from the images of packing.pack_resskip_f16_weights / pack_gate_f16_weights, not split again:
 the packers' lane order is part of what the emulation checks.
 
 ``defects`` plants what only this path can get wrong (test_split_reference.py):
@@ -22,7 +22,7 @@ the packers' lane order is part of what the emulation checks.
 """
 import numpy as np
 
-from mbexwn_vocoder_amd import engine
+from mbexwn_vocoder_amd import packing
 from mbexwn_vocoder_amd.config import ModelDims
 
 F32 = np.float32
@@ -39,7 +39,7 @@ def split(x):
 
 
 def unpack_resskip_f16(img):
-    """Image of engine.pack_resskip_f16_weights (steps, 12, 1024 words) -> (hi, lo') fp16 arrays (32 steps, 384): channel, column."""
+    """Image of packing.pack_resskip_f16_weights (steps, 12, 1024 words) -> (hi, lo') fp16 arrays (32 steps, 384): channel, column."""
     nk = img.shape[0]
     halves = np.ascontiguousarray(img).view(np.float16).reshape(nk, 12, 2, 2, 4, 16, 2, 4)   # step, pair, parity, part, kq, n, half, v
     both = halves.transpose(3, 0, 6, 4, 7, 1, 5, 2)                                          # part, step, half, kq, v, pair, n, parity
@@ -48,7 +48,7 @@ def unpack_resskip_f16(img):
 
 
 def unpack_gate_f16(img):
-    """Image of engine.pack_gate_f16_weights (tiles, steps, 6144 words) -> fp16 array (part: hi | lo', tap, 32 steps channels,
+    """Image of packing.pack_gate_f16_weights (tiles, steps, 6144 words) -> fp16 array (part: hi | lo', tap, 32 steps channels,
     tanh | sigmoid, column tile, 32 gate channels of the tile)."""
     nt, nk = img.shape[:2]
     halves = np.ascontiguousarray(img).view(np.float16).reshape(nt, nk, 3, 2, 2, 2, 4, 16, 8)  # block, step, tap, e, s, part, kq, n, v
@@ -57,7 +57,7 @@ def unpack_gate_f16(img):
 
 
 def unpack_end(img, C, n_out):
-    """Image of engine.pack_end_weights (ceil(C/8), 2, 32, 4) -> (C, n_out) float32."""
+    """Image of packing.pack_end_weights (ceil(C/8), 2, 32, 4) -> (C, n_out) float32."""
     img = np.asarray(img, dtype=F32)
     return np.ascontiguousarray(img.transpose(0, 1, 3, 2)).reshape(-1, 32)[:C, :n_out]
 
@@ -71,7 +71,7 @@ class SplitEmulation:
         self.C, self.L, self.n_out = dims.wn_channels, dims.wn_layers, dims.wn_out_channels
         self.C8 = (self.C + 7) // 8 * 8
         self.defects = dict(defects or {})
-        tab = engine.tensor_table(cfg, raw, wt, split_f16=True)
+        tab = packing.tensor_table(cfg, raw, wt, split_f16=True)
         C, L = self.C, self.L
         assert "wn.res_skip_0.fold_start_f16" in tab and L >= 3
         self.rs = [unpack_resskip_f16(tab["wn.res_skip_0.fold_start_f16" if ll == 0 else f"wn.res_skip_{ll}.fold_f16"])

@@ -86,7 +86,7 @@ def test_model_dims_force_causal_pads_the_wavenet_causally():
 def test_engine_tensor_table_of_a_causal_model_has_the_winograd_images():
     """A single-block force_causal model gets the F(2,3) / F(4,3) images and the folded start weights that the pinned
     causal forms run on (they do not depend on the padding)."""
-    from mbexwn_vocoder_amd.engine import tensor_table
+    from mbexwn_vocoder_amd.packing import tensor_table
     cfg, raw, wt = build_case(*CAUSAL_CASES["causal_canon"][:2])
     tab = tensor_table(cfg, raw, wt)
     for ll in range(3):

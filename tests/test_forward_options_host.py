@@ -2,6 +2,7 @@
 (engine.forward_entry_point) and which combinations are refused, against a table written out from the forward that had
 one copy of the call per branch."""
 import itertools
+import re
 
 import pytest
 import torch
@@ -111,6 +112,61 @@ def test_refused_combinations(case):
     eng = _HostEngine()
     with pytest.raises(ValueError, match=text):
         eng._forward_options(**_arguments(eng, **asked))
+
+
+def _whole_items(eng):
+    return _arguments(eng, f0=True)
+
+
+def _window(eng):
+    args = _arguments(eng, state=True, active=True, wavenet=True, carry=True, layers=True, frontend=True,
+                      control=("f0_frames", "f0_scale", "f0_item_mask"))
+    return dict(args, state_out=torch.zeros((B, 6), dtype=torch.int32))
+
+
+# every tensor argument of _forward_options: (name, the call it belongs to, key in the arguments, index in that key's tuple or
+# None, its message, whether it must be contiguous, whether a non-tensor is refused with the same message)
+TENSORS = [
+    ("stream_state", _window, "stream_state", None, "stream_state must be an int32 tensor of shape (batch, 6) on the", False, False),
+    ("state_out", _window, "state_out", None, "state_out must be a contiguous int32 tensor of shape (batch, 6) on the", True, False),
+    ("active[1]", _window, "active", 1, "active = (begin frame inside the window, int32 tensor of shape (batch,) on", False, False),
+    ("wavenet[1]", _window, "wavenet", 1, "wavenet = (begin frame inside the active region, int32 tensor (batch,) on", False, False),
+    ("carry store", _window, "carry", 0, "carry store must be a contiguous float32 tensor (slots, rows, subbands) on", True, False),
+    ("carry descriptors", _window, "carry", 1, "carry descriptors must be an int32 tensor of shape (batch, 5) on", False, False),
+    ("layer store", _window, "layers", 0, "layer store must be a contiguous float32 tensor (slots, floats) on", True, False),
+    ("layer descriptors", _window, "layers", 1, "layer descriptors must be an int32 tensor of shape (batch, 3) on", False, False),
+    ("front-end ring", _window, "frontend", 0, "front-end ring must be a contiguous float32 tensor (slots, ring frames, ", True, False),
+    ("front-end positions", _window, "frontend", 1, "front-end positions must be an int32 tensor (batch,) on", False, False),
+    ("f0", _whole_items, "f0", None, f"f0 must be a float32 tensor of shape ({B}, ", False, False),
+    ("f0_frames", _window, "f0_frames", None, f"f0_frames must be a float32 tensor of shape ({B}, {T}) on", False, True),
+    ("f0_scale", _window, "f0_scale", None, f"f0_scale must be a float32 tensor of shape ({B}, {T}) on", False, True),
+    ("f0_item_mask", _window, "f0_item_mask", None, f"f0_item_mask must be an int32 tensor of shape ({B},) on", False, True),
+]
+BAD = {
+    "dtype": lambda good: good.double(),
+    "shape": lambda good: good.unsqueeze(0),                  # one dimension more: wrong for the fixed and the open shapes alike
+    "view": lambda good: torch.zeros(tuple(good.shape[:-1]) + (2 * good.shape[-1],), dtype=good.dtype)[..., ::2],
+    "non-tensor": lambda good: good.numpy(),
+}
+TENSOR_CASES = [(row, kind) for row in TENSORS for kind in BAD
+                if kind in ("dtype", "shape") or (kind == "view" and row[5]) or (kind == "non-tensor" and row[6])]
+
+
+@pytest.mark.parametrize("row,kind", TENSOR_CASES, ids=[f"{row[0]}-{kind}" for row, kind in TENSOR_CASES])
+def test_tensor_arguments_are_refused_with_their_message(row, kind):
+    """One tensor argument at a time with a wrong dtype, a wrong shape, a non-contiguous view where contiguity is demanded,
+    a numpy array where a non-tensor is refused by name: ValueError with that argument's message; the call is fine without."""
+    _, base, key, index, text, _, _ = row
+    eng = _HostEngine()
+    args = base(eng)
+    eng._forward_options(**args)
+    good = args[key] if index is None else args[key][index]
+    bad = BAD[kind](good)
+    if kind == "view":
+        assert tuple(bad.shape) == tuple(good.shape) and bad.dtype == good.dtype and not bad.is_contiguous()
+    args[key] = bad if index is None else args[key][:index] + (bad,) + args[key][index + 1:]
+    with pytest.raises(ValueError, match=re.escape(text)):
+        eng._forward_options(**args)
 
 
 def test_window_arguments_reach_the_options():

@@ -102,6 +102,28 @@ def test_kernel_equals_the_host_restatement(n_mels):
     assert np.array_equal(bits(call.rows(call.out.view(call.torch.float32).cpu().numpy())), bits(call.want()))
 
 
+def test_warp_envelope_device_needs_no_engine():
+    """envelope.warp_envelope_device on its own (the library and a centre table, no model): a batch view with a batch stride of
+    its own -- passed as it is, the row-stride path --, the factors 0.8, 1 and 1.25, a short item: the bits of
+    warp_envelope_host."""
+    from mbexwn_vocoder_amd.envelope import device_centres, warp_envelope_device
+    batch, frames, n, counts = 2, 3, 80, (3, 1)
+    analysis = {"mel_channels": n, "fmin": TABLES[n][0], "fmax": TABLES[n][1], "sample_rate": 24000}
+    rng = np.random.default_rng(8)
+    wide = np.clip(rng.normal(-5.0, 2.0, size=(batch, frames + 2, n)), -11.5, 2.0).astype(np.float32)
+    factors = np.asarray([[0.8, 1.0, 1.25], [1.25, 0.8, 1.0]], dtype=np.float32)
+    view = _dev(wide)[:, :frames]
+    assert not view.is_contiguous() and view.stride(0) == (frames + 2) * n
+    centres = device_centres(analysis, view.device)
+    assert centres is device_centres(dict(analysis), view.device)                    # uploaded once
+    got = warp_envelope_device(view, _dev(factors), centres, _dev(np.asarray(counts, dtype=np.int32)))
+    assert got.stride() == view.stride()                       # (the call has one item stride for mel and out)
+    got = got.cpu().numpy()
+    want = warp_envelope_host(wide[:, :frames], factors, channel_centres(analysis), n_frames=counts)
+    assert got.shape == (batch, frames, n) and np.array_equal(bits(got), bits(want))
+    assert not np.array_equal(got[0, 0], wide[0, 0]) and np.array_equal(bits(got[1, 1:]), bits(wide[1, 1:frames]))
+
+
 def test_kernel_refusals_leave_the_output_untouched():
     call = Call(80, 2, 6, (6, 3), seed=3, fill="huge")
 

@@ -131,6 +131,20 @@ def test_ragged_batch_matches_the_host_writer(engine, ragged):
     assert kinds >= {("constant", None), ("verbatim", None)} | {("fixed", oo) for oo in range(5)}, kinds
 
 
+@pytest.mark.parametrize("compression", flac.COMPRESSIONS)
+def test_encode_device_needs_no_engine(compression):
+    """flac.encode_device on its own (the library, no model): a ragged batch with an empty item, one sample, a full block and
+    a block plus one sample at a stride of 4 100 -- every stream is the host writer's, byte for byte."""
+    import torch
+    lengths = (0, 1, 4096, 4097)
+    host = (0.5 * np.random.default_rng(6).uniform(-1.0, 1.0, size=(len(lengths), 4100))).astype(np.float32)
+    enc = flac.encode_device(torch.as_tensor(host).cuda(), lengths, RATE, compression=compression)
+    assert isinstance(enc, flac.EncodedFlac) and enc.compression == compression
+    for bb, nn in enumerate(lengths):
+        assert enc.stream(bb) == flac.encode(host[bb, :nn], RATE, compression=compression), f"item {bb} ({nn} samples)"
+        assert enc.max_abs[bb] == (np.max(np.abs(host[bb, :nn])) if nn else 0.0)
+
+
 def test_other_rate_and_two_byte_frame_numbers(engine):
     """A rate outside FLAC's table (code 0000: taken from STREAMINFO) and an item of 129 frames, whose last frame numbers
     take two bytes."""

@@ -140,3 +140,21 @@ def test_engine_keyed_noise(lib):
         eng.keyed_noise(3, [1, 2], [4])
     with pytest.raises(ValueError):
         eng.keyed_noise(3, [1], [4], first_step=[-1])
+
+
+def test_fill_normal_device_needs_no_engine(lib, port_error):
+    """noise.fill_normal_device on its own: counts (0, 1, 5) from the steps (0, 3, 2^32 + 1) under two seeds -- (B, max count)
+    with zeros behind each count, the bits of the direct call (as test_engine_keyed_noise asks of the method), and within the
+    bar of test_device_normals_match_the_mirror of the host mirror's float64 values."""
+    counts, first, seeds, keys = [0, 1, 5], [0, 3, 2 ** 32 + 1], [3, 4, 3], [11, 12, 13]
+    out = noise.fill_normal_device(seeds, keys, counts, first_step=first).cpu().numpy()
+    assert out.shape == (3, 5) and out.dtype == np.float32 and np.all(out[0] == 0) and np.all(out[1, 1:] == 0)
+    want = fill(lib, [[ss, kk] for ss, kk in zip(seeds, keys)], counts, first=first, stride=5)[0]
+    for bb, (ss, kk, cc, ff) in enumerate(zip(seeds, keys, counts, first)):
+        assert np.array_equal(bits(out[bb, :cc]), bits(want[bb, :cc])), bb
+        ref = noise.normals_reference(ss, kk, ff, cc)
+        assert np.all(np.abs(out[bb, :cc] - ref) <= np.maximum(8 * port_error[1], 4e-6 * np.maximum(1.0, np.abs(ref)))), bb
+    assert not np.array_equal(out[2], noise.fill_normal_device(4, keys, counts, first_step=first).cpu().numpy()[2])   # the seed counts
+    import torch
+    filled = noise.fill_normal_device(seeds, keys, counts, first_step=first, out=torch.zeros((3, 8), device="cuda")).cpu().numpy()
+    assert np.array_equal(bits(filled[:, :5]), bits(out)) and np.all(filled[:, 5:] == 0)

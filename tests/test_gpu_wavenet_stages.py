@@ -293,8 +293,8 @@ _REFS = {}
 def tensor_table_of(cid):
     """The tensor table a case's engine is created from: for the cases of NO_START_F16 the host leaves out layer 0's split
     res/skip image (a legal table: the C ABI runs that layer in float32), for every other case the engine's own."""
-    from mbexwn_vocoder_amd import engine as engine_module
-    fold_start = engine_module.fold_start_weights
+    from mbexwn_vocoder_amd import packing as packing_module
+    fold_start = packing_module.fold_start_weights
 
     def without_the_split_image(*args, **kw):
         out = fold_start(*args, **kw)
@@ -302,11 +302,11 @@ def tensor_table_of(cid):
         return out
 
     if cid in NO_START_F16:
-        engine_module.fold_start_weights = without_the_split_image
+        packing_module.fold_start_weights = without_the_split_image
     try:
         yield
     finally:
-        engine_module.fold_start_weights = fold_start
+        packing_module.fold_start_weights = fold_start
 
 
 def test_gpu_cases_cover_every_gate_kernel():

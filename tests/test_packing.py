@@ -1,10 +1,10 @@
-"""Host-side weight images consumed by the HIP kernels (engine.pack_*, engine.fold_skip_weights): every image is
+"""Host-side weight images consumed by the HIP kernels (packing.pack_*, packing.fold_skip_weights): every image is
 unpacked here with the index formula of the kernel that reads it and fed through a float64 numpy restatement of that
 kernel's arithmetic, which must reproduce the plain convolution."""
 import numpy as np
 import pytest
 
-from mbexwn_vocoder_amd import engine
+from mbexwn_vocoder_amd import packing
 
 
 def _direct_dilated(x, w, d):
@@ -15,7 +15,7 @@ def _direct_dilated(x, w, d):
 
 
 def _unpack_gate_16x16x4(packed, C, n_prod):
-    """Image of engine.pack_winograd2w_weights / pack_winograd4w_weights -> U (n_prod, C, 2C) with the lane/step map of the
+    """Image of packing.pack_winograd2w_weights / pack_winograd4w_weights -> U (n_prod, C, 2C) with the lane/step map of the
     gate kernels on v_mfma_f32_16x16x4_f32: [product j][parity e][lane = 16 kq + n][tanh step 0, 1, sigmoid step 0, 1]."""
     nt, nk, _ = packed.shape
     img = packed.reshape(nt, nk, n_prod, 2, 64, 2, 2)               # tile, slice, j, e, lane, tanh|sigmoid, step
@@ -41,7 +41,7 @@ def test_winograd_f23_image_reproduces_the_convolution(C):
     """wn_gate_winograd2w_kernel: pairs (t, t + d) inside blocks of 2 d rows counted from the first computed row."""
     rng = np.random.default_rng(C)
     w = rng.normal(size=(3, C, 2 * C))
-    packed = engine.pack_winograd2w_weights(w)
+    packed = packing.pack_winograd2w_weights(w)
     assert packed.shape == ((C + 31) // 32, (C + 7) // 8, 2048)
     U = _unpack_gate_16x16x4(packed.astype(np.float64), C, 4)
     x = rng.normal(size=(64, C))
@@ -78,7 +78,7 @@ def test_winograd2w_staging_map_covers_every_row_once():
 def test_winograd_f43_image_reproduces_the_convolution(C):
     rng = np.random.default_rng(C)
     w = rng.normal(size=(3, C, 2 * C))
-    U = _unpack_gate_16x16x4(engine.pack_winograd4w_weights(w).astype(np.float64), C, 6)
+    U = _unpack_gate_16x16x4(packing.pack_winograd4w_weights(w).astype(np.float64), C, 6)
     x = rng.normal(size=(128, C))
     for d in (1, 4, 16):
         ref = _direct_dilated(x, w, d)
@@ -122,9 +122,9 @@ def test_resskip_and_end_images_are_permutations_of_the_weights():
     rng = np.random.default_rng(3)
     C, cout = 40, 70
     w = rng.normal(size=(1, C, cout)).astype(np.float32)
-    assert np.array_equal(_unpack_resskip(engine.pack_resskip_weights(w), C, cout), w[0].astype(np.float64))
+    assert np.array_equal(_unpack_resskip(packing.pack_resskip_weights(w), C, cout), w[0].astype(np.float64))
     we = rng.normal(size=(1, 44, 30)).astype(np.float32)
-    img = engine.pack_end_weights(we)                                 # [c][lk][n][st], channel 8c + 4lk + st
+    img = packing.pack_end_weights(we)                                 # [c][lk][n][st], channel 8c + 4lk + st
     assert img.shape == (6, 2, 32, 4)
     for c in range(6):
         for lk in range(2):
@@ -157,7 +157,7 @@ def test_folded_skip_path_is_the_same_linear_map(layers):
             skip += r
     ref = skip @ folded["wn.end.w"][0] + folded["wn.end.b"]
     # folded graph as the kernels run it
-    extra = engine.fold_skip_weights(folded, layers, C)
+    extra = packing.fold_skip_weights(folded, layers, C)
     y = np.zeros((T, n_out))
     for ll in range(layers - 1):
         W = _unpack_resskip(extra[f"wn.res_skip_{ll}.fold"].astype(np.float64), C, C + n_out)
@@ -173,7 +173,7 @@ def test_folded_skip_path_is_the_same_linear_map(layers):
 
 
 def test_start_convolution_folds_into_layer_0_including_the_item_edges():
-    """engine.fold_start_weights: the K = 24 contraction of x' = [x | 1 | 0] with the tap products Ws' W0_tau equals the
+    """packing.fold_start_weights: the K = 24 contraction of x' = [x | 1 | 0] with the tap products Ws' W0_tau equals the
     dilated convolution of h0 = start(x) with zero "SAME" padding -- also in the first and last rows, where a tap falls
     outside the item (the constant channel is zero there, exactly where the reference pads h0) -- and [a0 | x'] times
     the K-extended res/skip image equals h0 + a0 Wr (+ the folded skip columns)."""
@@ -185,7 +185,7 @@ def test_start_convolution_folds_into_layer_0_including_the_item_edges():
               "wn.conv1D_0.w": rng.normal(size=(3, C, 2 * C)),
               "wn.res_skip_0.w": rng.normal(size=(1, C, 2 * C)), "wn.res_skip_0.b": rng.normal(size=2 * C)}
     proj = rng.normal(size=(C, n_out))
-    out = engine.fold_start_weights(folded, dims, {"wn.res_skip_0.fold": None, "__proj_0": proj})
+    out = packing.fold_start_weights(folded, dims, {"wn.res_skip_0.fold": None, "__proj_0": proj})
     img = out["wn.conv1D_0.start_fold"].astype(np.float64)
     nt = img.shape[0]
     img = img.reshape(nt, 3, 2, 64, 2, 2)                          # tile, tap, e, lane, tanh|sigmoid, step
@@ -217,11 +217,11 @@ def test_start_convolution_folds_into_layer_0_including_the_item_edges():
 
 
 def test_resskip_wide_image_is_a_permutation_of_the_weights():
-    """engine.pack_resskip_wide_weights unpacked with the lane/step map of wn_resskip_wide_kernel."""
+    """packing.pack_resskip_wide_weights unpacked with the lane/step map of wn_resskip_wide_kernel."""
     rng = np.random.default_rng(5)
     K, cout = 44, 70
     w = rng.normal(size=(1, K, cout)).astype(np.float32)
-    img = engine.pack_resskip_wide_weights(w)
+    img = packing.pack_resskip_wide_weights(w)
     nk, npair = (K + 7) // 8, (cout + 31) // 32
     assert img.shape == (nk, npair, 256)
     img = img.reshape(nk, npair, 64, 2, 2)                          # slice, pair, lane, parity, step
@@ -304,7 +304,7 @@ def test_resskip_wave_image_is_a_permutation_of_the_weights():
     rng = np.random.default_rng(11)
     K, cout = 40, 70
     w = rng.normal(size=(1, K, cout)).astype(np.float32)
-    img = engine.pack_resskip_wave_weights(w)
+    img = packing.pack_resskip_wave_weights(w)
     assert img.shape == ((K + 15) // 16, 12, 512)
     got = np.zeros((K, cout), dtype=np.float32)
     seen = 0
@@ -350,7 +350,7 @@ def test_split_f16_weight_images():
     """The fp16-split weight images of the opt-in precision mode (csrc/wn_resskip_f16.hip, csrc/wn_gate_f16.hip): every
     image entry sits where the kernel's MFMA operand order expects it, hi + 2^-11 lo' reproduces the float32 weight to
     2^-21 of its magnitude, and out-of-range entries are zero."""
-    from mbexwn_vocoder_amd.engine import pack_gate_f16_weights, pack_resskip_f16_weights
+    from mbexwn_vocoder_amd.packing import pack_gate_f16_weights, pack_resskip_f16_weights
     rng = np.random.default_rng(11)
     # res/skip: (1, K, cout), K = 340 (partial last step), cout = 370 (12 pairs, the last one partial)
     K, cout = 340, 370
@@ -391,3 +391,24 @@ def test_split_f16_weight_images():
     assert np.max(np.abs(back - want)) <= 2.0 ** -21 * np.max(np.abs(wg))
     with pytest.raises(ValueError, match="fp16"):
         pack_gate_f16_weights(wg * 1e6)
+
+
+def test_packing_imports_without_the_binding():
+    """``import mbexwn_vocoder_amd.packing`` in a fresh interpreter loads neither torch nor the binding (abi), and no module
+    of the package that it loads holds ctypes or anything defined there.  (numpy imports ctypes for itself, so sys.modules
+    can say so only where numpy does not.)"""
+    import subprocess
+    import sys
+    code = ("import sys, numpy\n"
+            "numpy_loads_ctypes = 'ctypes' in sys.modules\n"
+            "import mbexwn_vocoder_amd.packing\n"
+            "assert 'torch' not in sys.modules and 'mbexwn_vocoder_amd.abi' not in sys.modules\n"
+            "assert numpy_loads_ctypes or 'ctypes' not in sys.modules\n"
+            "import ctypes\n"
+            "ours = [mm for name, mm in sys.modules.items() if name.startswith('mbexwn_vocoder_amd')]\n"
+            "held = [(mm.__name__, kk) for mm in ours for kk, vv in vars(mm).items()\n"
+            "        if vv is ctypes or getattr(vv, '__module__', None) in ('ctypes', '_ctypes')]\n"
+            "assert 'mbexwn_vocoder_amd.packing' in sys.modules and not held, held\n")
+    root = __file__.rsplit("/tests/", 1)[0]
+    res = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr[-2000:]

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from helpers import build_case
-from mbexwn_vocoder_amd import engine
+from mbexwn_vocoder_amd import packing
 from oracle import mbexwn_oracle as orc
 from split_reference import SplitEmulation, unpack_gate_f16, unpack_resskip_f16
 from test_wn_reference import LENGTHS, N_OUT, _cpu_excitation, _rs_case
@@ -52,7 +52,7 @@ def test_unpacked_images_are_the_split_weights():
     zero outside the matrix (K = 340 + 16 rows: a partial last step; 370 and 2 x 68 columns: partial last pair and tile)."""
     rng = np.random.default_rng(5)
     w = (rng.normal(size=(1, 356, 370)) * 0.07).astype(np.float32)
-    hi, lo = unpack_resskip_f16(engine.pack_resskip_f16_weights(w))
+    hi, lo = unpack_resskip_f16(packing.pack_resskip_f16_weights(w))
     assert hi.shape == lo.shape == (384, 384)
     want = np.zeros((384, 384), dtype=np.float32)
     want[:356, :370] = w[0]
@@ -60,7 +60,7 @@ def test_unpacked_images_are_the_split_weights():
     assert np.array_equal(lo, ((want - want.astype(np.float16).astype(np.float32)) * np.float32(2048)).astype(np.float16))
     C = 68
     wg = (rng.normal(size=(3, C, 2 * C)) * 0.05).astype(np.float32)
-    g = unpack_gate_f16(engine.pack_gate_f16_weights(wg))
+    g = unpack_gate_f16(packing.pack_gate_f16_weights(wg))
     assert g.shape == (2, 3, 96, 2, 3, 32)
     want = np.zeros((3, 96, 2, 96), dtype=np.float32)
     want[:, :C, 0, :C], want[:, :C, 1, :C] = wg[:, :, :C], wg[:, :, C:]
@@ -132,7 +132,7 @@ def test_plane_padding_is_never_multiplied_into_a_result():
     for name in ("wn_out", "wn_hidden"):
         assert np.array_equal(got[name], clean[name], equal_nan=True), name
     assert not failures(ref.compare(got))
-    g = unpack_gate_f16(engine.tensor_table(*_case(324)[1], split_f16=True)["wn.conv1D_1.gate_f16"])
+    g = unpack_gate_f16(packing.tensor_table(*_case(324)[1], split_f16=True)["wn.conv1D_1.gate_f16"])
     assert np.all(g[:, :, 324:] == 0) and np.any(g[:, :, 323] != 0)
 
 

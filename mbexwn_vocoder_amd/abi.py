@@ -1,5 +1,5 @@
 """ctypes binding of libmbexwn_hip.so: the structures and constants of include/mbexwn.h, and ONE table of every function the
-eleven headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
+twelve headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
 
 Nothing else lives here: a tool that only resamples imports this module, not the engine's driver.  The table is declared in
 Python (the package loads without include/ beside it); tests/test_abi_headers.py holds it to the headers name by name and
@@ -159,6 +159,8 @@ TABLE = {
     "mbexwn_contour.h": [
         ("mbxc_f0_candidates", i32, _f0_frames + [f32, P(f32), P(f32), i32, i32, vp, vp, vp, vp]),
         ("mbxc_decode_f0", i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp])],
+    # rings, n_slots, ring_samples, desc, n_streams, max_new_frames, hop, sample_rate, window, tau_min, tau_max, ...
+    "mbexwn_live_pitch.h": [("mbxt_f0_frames", i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp])],
 }
 
 

@@ -450,7 +450,7 @@ def read_sound(path):
 
 def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
                   quiet=False, flac_compression="verbatim", out_rate=None, stretches=None, formants=None, f0_source="net",
-                  f0_params=None, write_f0=False, timings=None, f0_decode=None):
+                  f0_params=None, write_f0=False, timings=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0):
     """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
     ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
 
@@ -476,7 +476,9 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     the tracked contour (0 = unvoiced) is written as NAME.f0 into ``output_dir``, with either source.  "net" without
     ``write_f0``: the launches and the bytes of before.  ``f0_decode``: None, or a ``f0decode.decode_params`` dictionary: the
     contour, used and written, is the Viterbi path over the YIN candidates of the file's frames (DESIGN.md section 6i);
-    it needs "audio" or ``write_f0``.  ``timings``: a dict that receives the seconds per stage the
+    it needs "audio" or ``write_f0``.  ``f0_fill``: "interpolate", or "hold" -- the causal fill of the live streams
+    (``f0track.fill_hold`` with ``f0_initial`` Hz in front of the first voiced frame); it needs "audio".
+    ``timings``: a dict that receives the seconds per stage the
     verbose line reports (upload, resample, analysis, f0, copy_back from ``generate_mels``; read, scale, device, copy, write
     from the pools and the micro-batches' events; wall)."""
     from . import f0track, timemap
@@ -525,6 +527,7 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
             log([f"transform_audio::error:: skipped {name}: {why}"])
         if f0_source not in ("net", "audio"):
             raise ValueError(f"run_audio_job: f0_source must be 'net' or 'audio', got {f0_source!r}")
+        f0track.check_fill(f0_fill, f0_source, "run_audio_job")
         tracked = [] if f0_source == "audio" or write_f0 else None
         if f0_decode is not None and tracked is None:
             raise ValueError("run_audio_job: f0_decode decodes the tracked contour and needs f0_source='audio' or write_f0")
@@ -544,7 +547,7 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
                     f0track.write_f0(f0_path(files[ii], output_dir), f0track.frame_times(tracked[ii][0].size, inv.hop_size, inv.srate),
                                      *tracked[ii])
             if f0_source == "audio":
-                contours = {ii: f0track.fill_unvoiced(tracked[ii][0]) for ii in mine}
+                contours = {ii: f0track.fill_tracked(tracked[ii][0], f0_fill, f0_initial) for ii in mine}
     dims = inv.model.dims
     device_flac = fmt.lower() == "flac" and not have_soundfile()
     # the files grouped by the rate they are written at (one group unless out_rate is "input")

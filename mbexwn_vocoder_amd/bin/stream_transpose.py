@@ -4,6 +4,7 @@ pushes, as a live source would deliver it, and writes what the stream gives back
 
     stream_transpose.py in.wav -o out.wav --model_id VOICE --transposition 1.5 [--formant-shift F] [--tick-ms 80]
                         [--resample] [--output-rate R|input]
+                        [--f0-source audio [--f0-min HZ --f0-max HZ --f0-initial HZ] [--write-f0]]
 
 The demonstration of the live path (streaming mel analysis -> scale_mel -> streaming synthesis with per-frame pitch control).
 The input must be at the model's sample rate, unless ``--resample`` is given: then a file at another rate streams at its own
@@ -11,6 +12,12 @@ rate (``--tick-ms`` of its own samples per push), is resampled on the device by 
 model rate -- or, with ``--output-rate R``, at R Hz (``input``: the file's own rate): the stream resamples its output on the
 device too.  A ``.wav`` output holds the float32 samples as they are; any other extension goes through the writers of
 resynth_mel.py.
+
+``--f0-source audio`` keeps the pitch that is in the sound: the stream tracks its F0 on the device
+between ``--f0-min`` and ``--f0-max`` Hz and drives the oscillator with it, an unvoiced frame holding the last voiced value
+(``--f0-initial`` Hz in front of the first); ``--transposition`` multiplies on top.  The output is what ``transform_audio.py
+--f0-source audio --f0-fill hold`` writes for the file under the same ``--noise-seed``.  ``--write-f0`` writes the raw tracked
+rows as NAME.f0 beside the output (text rows `time_s f0_hz periodicity`, one per mel frame, 0 = unvoiced).
 """
 import os
 import sys
@@ -28,12 +35,23 @@ from mbexwn_vocoder_amd.live import check_rate  # noqa: E402
 
 
 def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0, sample_rate=None, output_rate=None,
-                noise_fn=None, formant=None):
+                noise_fn=None, formant=None, f0_source="net", f0_params=None, f0_initial=150.0, f0_out=None):
     """Push `samples` in pieces of tick_samples, one tick per push, until the stream is finished; returns its audio.
     ``sample_rate``: the rate of `samples` when it is not the model's (the stream resamples); ``output_rate``: the rate the
     audio comes back at when it is not the model's (a rate in Hz, or "input"); ``noise_fn``: the stream's noise instead of the
-    generator seeded with ``seed`` (``live.keyed_noise_fn``); ``formant``: a formant-shift factor given with every push."""
+    generator seeded with ``seed`` (``live.keyed_noise_fn``); ``formant``: a formant-shift factor given with every push; ``f0_source``,
+    ``f0_params``, ``f0_initial``: as for ``LiveResynthesizer.open``; ``f0_out``: a list that receives the stream's tracked
+    (f0, periodicity), one pair of arrays per tick that handed out rows."""
     rates = {} if sample_rate is None else {"sample_rate": sample_rate}
+    if f0_source != "net":
+        rates.update(f0_source=f0_source, f0_params=f0_params, f0_initial=f0_initial)
+
+    def tick():
+        audio = live.tick().get(stream_id)
+        if f0_out is not None and stream_id in live.last_f0:
+            f0_out.append(live.last_f0[stream_id])
+        return audio
+
     if output_rate is not None:
         rates["output_rate"] = output_rate
     live.open(stream_id, seed=seed, noise_fn=noise_fn, **rates)
@@ -42,9 +60,9 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0,
         end = min(start + tick_samples, samples.size)
         live.push_audio(stream_id, samples[start:end], last=end == samples.size, transposition=transposition,
                         **({} if formant is None else {"formant": formant}))
-        out += [audio for audio in [live.tick().get(stream_id)] if audio is not None]
+        out += [audio for audio in [tick()] if audio is not None]
     while not live.finished(stream_id):
-        audio = live.tick().get(stream_id)
+        audio = tick()
         if audio is None:                                     # a closed stream emits with every tick until it is finished
             raise RuntimeError("the closed stream did not advance")
         out.append(audio)
@@ -53,7 +71,8 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0,
 
 
 def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tick_ms=80.0, seed=0, quiet=False,
-         resample=False, output_rate=None, noise_seed=None, formant_shift=1.0):
+         resample=False, output_rate=None, noise_seed=None, formant_shift=1.0, f0_source="net", f0_min=55.0, f0_max=1000.0,
+         f0_initial=150.0, write_f0=False):
     preprocess_config = read_config(config_file=get_config_file(model_id_or_path=model_id))['preprocess_config']
     if not os.path.isfile(input_audio_file):
         print(f"stream_transpose::error:: no such file: {input_audio_file}", file=sys.stderr)
@@ -74,6 +93,16 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
             raise ValueError("--transposition must be finite and positive")
         if not (np.isfinite(formant_shift) and formant_shift > 0):
             raise ValueError("--formant-shift must be finite and positive")
+        if f0_source not in ("net", "audio"):
+            raise ValueError(f"--f0-source must be net or audio, got {f0_source!r}")
+        if write_f0 and f0_source != "audio":
+            raise ValueError("--write-f0 writes what the stream tracked: it needs --f0-source audio")
+        f0_params = None
+        if f0_source == "audio":
+            from mbexwn_vocoder_amd import f0track
+            f0_params = f0track.params(model_rate, f0_min=f0_min, f0_max=f0_max)
+            if not (np.isfinite(f0_initial) and f0_initial > 0):
+                raise ValueError("--f0-initial must be finite and positive")
     except ValueError as err:
         print(f"stream_transpose::error:: {err}", file=sys.stderr)
         sys.exit(1)
@@ -91,9 +120,11 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
     # --noise-seed: the keyed noise of the file (its basename is the key), what transform_audio.py draws for it
     keyed = {} if noise_seed is None else {"noise_fn": keyed_noise_fn(live.mel_inverter.model, noise_seed),
                                            "stream_id": os.path.basename(input_audio_file)}
+    tracked = [] if write_f0 else None
     audio = stream_file(live, samples, tick_samples, transposition, seed=seed, sample_rate=own_rate,
                         output_rate=out_rate if out_rate != model_rate else None,
-                        formant=None if formant_shift == 1.0 else formant_shift, **keyed)
+                        formant=None if formant_shift == 1.0 else formant_shift, f0_source=f0_source, f0_params=f0_params,
+                        f0_initial=f0_initial, f0_out=tracked, **keyed)
     out_dir = os.path.dirname(os.path.abspath(output_file))
     os.makedirs(out_dir, exist_ok=True)
     ext = os.path.splitext(output_file)[1].lower().lstrip(".") or "wav"
@@ -102,9 +133,13 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
         wavfile.write(output_file, out_rate, audio.astype(np.float32, copy=False))
     else:
         write_audio(output_file, audio, out_rate, ext)
+    if write_f0:
+        f0, periodicity = (np.concatenate([pair[kk] for pair in tracked]) if tracked else np.zeros(0, np.float32) for kk in (0, 1))
+        f0track.write_f0(os.path.splitext(output_file)[0] + ".f0",
+                         f0track.frame_times(f0.size, int(preprocess_config["hop_size"]), model_rate), f0, periodicity)
     if not quiet:
         print(f"{input_audio_file}: {samples.size} samples in pushes of {tick_samples} -> {audio.size} samples, transposed by "
-              f"{transposition}, look-ahead {live.lookahead_ms_for(own_rate, out_rate):.1f} ms, saved at {out_rate} Hz under {output_file}",
+              f"{transposition}, look-ahead {live.lookahead_ms_for(own_rate, out_rate, f0_source, f0_params):.1f} ms, saved at {out_rate} Hz under {output_file}",
               file=sys.stderr)
 
 
@@ -141,6 +176,19 @@ if __name__ == "__main__":
     parser.add_argument("--output-rate", dest="output_rate", default=None, type=output_rate_arg, metavar="R|input",
                         help="write the output at R Hz, resampled on the device by the stream; input = the file's own rate, "
                              "which needs --resample when that is not the model's (Def: the model rate)")
+    parser.add_argument("--f0-source", dest="f0_source", default="net", choices=["net", "audio"],
+                        help="where the pitch comes from: net = what the model infers from the mel; audio = the streaming F0 "
+                             "tracker on the sound itself, unvoiced frames holding the last voiced value; --transposition "
+                             "multiplies on top of either (Def: %(default)s)")
+    parser.add_argument("--f0-min", dest="f0_min", default=55.0, type=float, metavar="HZ",
+                        help="lowest pitch the F0 tracker looks for (Def: %(default)s)")
+    parser.add_argument("--f0-max", dest="f0_max", default=1000.0, type=float, metavar="HZ",
+                        help="highest pitch the F0 tracker looks for (Def: %(default)s)")
+    parser.add_argument("--f0-initial", dest="f0_initial", default=150.0, type=float, metavar="HZ",
+                        help="--f0-source audio: the pitch in front of the first voiced frame (Def: %(default)s)")
+    parser.add_argument("--write-f0", dest="write_f0", action="store_true",
+                        help="--f0-source audio: write the tracked rows as NAME.f0 beside the output: text rows `time_s f0_hz "
+                             "periodicity`, one per mel frame, 0 = unvoiced")
     parser.add_argument("--seed", default=0, type=int, help="seed of the stream's noise generator (Def: %(default)s)")
     parser.add_argument("--noise-seed", dest="noise_seed", default=None, type=int, metavar="S",
                         help="draw the stream's noise keyed by (S, the file's basename) and the absolute step, as "

@@ -32,7 +32,9 @@ combine freely.
 --f0-source audio keeps the pitch that is in the sound instead of the pitch the model infers from the mel (DESIGN.md section
 6h; include/mbexwn_pitch.h): an F0 tracker runs on the frames of the mel analysis, between --f0-min and --f0-max Hz, its
 unvoiced frames are filled from their neighbours and the contour drives the oscillator; --transposition multiplies on top; a
-file without a voiced frame keeps the model's F0.  --write-f0 writes the tracked contour as NAME.f0 into the output directory
+file without a voiced frame keeps the model's F0.  --f0-fill hold fills causally instead, as a live stream must (DESIGN.md
+section 6j): an unvoiced frame holds the last voiced value and the frames in front of the first take --f0-initial Hz; the file
+then has the samples stream_transpose.py --f0-source audio streams for it.  --write-f0 writes the tracked contour as NAME.f0 into the output directory
 (text rows `time_s f0_hz periodicity`, one per mel frame, 0 = unvoiced), with either source.
 
 --pitch-decode viterbi decodes that contour over the whole file instead of picking every frame on its own (DESIGN.md section
@@ -56,12 +58,16 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
          gpus=1, num_threads=2, out_rate=None, format="flac", flac_compression="verbatim", conv_form="auto",
          batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None,
          formant_shift=1.0, formant_shift_file=None, f0_source="net", f0_min=55.0, f0_max=1000.0, write_f0=False,
-         pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5):
+         pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5, f0_fill="interpolate", f0_initial=150.0):
     try:
         if f0_source not in ("net", "audio"):
             raise ValueError(f"--f0-source must be net or audio, got {f0_source!r}")
         if not 0.0 < f0_min < f0_max:
             raise ValueError(f"--f0-min must lie below --f0-max, got {f0_min} and {f0_max}")
+        if f0_fill not in ("interpolate", "hold"):
+            raise ValueError(f"--f0-fill must be interpolate or hold, got {f0_fill!r}")
+        if f0_fill == "hold" and f0_source != "audio":
+            raise ValueError("--f0-fill hold fills the tracked contour: it needs --f0-source audio")
         f0_decode = pitch_decode_params(pitch_decode, pitch_jump, pitch_switch)
         if f0_decode is not None and f0_source != "audio" and not write_f0:
             raise ValueError("--pitch-decode viterbi decodes the tracked contour: it needs --f0-source audio or --write-f0")
@@ -105,6 +111,7 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
         argv += ["--f0-source", f0_source] if f0_source != "net" else []
         argv += ["--f0-min", repr(float(f0_min)), "--f0-max", repr(float(f0_max))] if f0_source != "net" or write_f0 else []
         argv += ["--write-f0"] if write_f0 else []
+        argv += ["--f0-fill", f0_fill, "--f0-initial", repr(float(f0_initial))] if f0_fill != "interpolate" else []
         argv += ["--pitch-decode", pitch_decode] if pitch_decode != "greedy" else []
         argv += ["--pitch-jump", repr(float(pitch_jump))] if pitch_jump != 4.0 else []
         argv += ["--pitch-switch", repr(float(pitch_switch))] if pitch_switch != 0.5 else []
@@ -133,7 +140,8 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
                             quiet=quiet, flac_compression=flac_compression, out_rate=out_rate,
                             stretches=None if all(ss == 1.0 for ss in stretches) else stretches,
                             formants=None if all(ff == 1.0 for ff in formants) else formants, f0_source=f0_source,
-                            f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0, f0_decode=f0_decode)
+                            f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0, f0_decode=f0_decode,
+                            f0_fill=f0_fill, f0_initial=f0_initial)
     if skipped:
         sys.exit(1)
 
@@ -235,6 +243,12 @@ def make_parser():
                         help="lowest pitch the F0 tracker looks for (Def: %(default)s)")
     parser.add_argument("--f0-max", dest="f0_max", default=1000.0, type=hertz_arg, metavar="HZ",
                         help="highest pitch the F0 tracker looks for (Def: %(default)s)")
+    parser.add_argument("--f0-fill", dest="f0_fill", default="interpolate", choices=["interpolate", "hold"],
+                        help="how --f0-source audio fills unvoiced frames: interpolate = between the voiced neighbours; hold = "
+                             "the last voiced value, --f0-initial in front of the first: the causal fill of "
+                             "stream_transpose.py --f0-source audio, whose samples the file then has (Def: %(default)s)")
+    parser.add_argument("--f0-initial", dest="f0_initial", default=150.0, type=hertz_arg, metavar="HZ",
+                        help="--f0-fill hold: the pitch in front of the first voiced frame (Def: %(default)s)")
     parser.add_argument("--write-f0", dest="write_f0", action="store_true",
                         help="write the tracked contour of every file as NAME.f0 into the output directory: text rows `time_s "
                              "f0_hz periodicity`, one per mel frame, 0 = unvoiced")

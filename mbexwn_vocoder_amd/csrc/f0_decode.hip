@@ -43,7 +43,8 @@ __global__ __launch_bounds__(F0_THREADS) void f0_candidates_kernel(CandidateArgs
     // length and centre from the device arrays, clamped to the item's row: a wrong entry must not address outside the buffer
     const long long n = min(max((long long)f.n_samples[b], 0LL), f.stride);
     const long long c = min(max(f.centres[(long long)b * f.max_frames + k], 0LL), n);
-    const int bad = f0_frame_dprime(f.audio + (long long)b * f.stride, n, c, W, TM, f0_smem, &s_energy);
+    const int bad = f0_frame_load(F0RowFetch(f.audio + (long long)b * f.stride, n, c, L), L, f0_smem);
+    f0_frame_dprime(W, TM, f0_smem, &s_energy);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave != 0) return;
 

@@ -1,6 +1,7 @@
-// The part the F0 tracker (f0_track.hip) and the candidates kernel of the decoder (f0_decode.hip) share: one 256-thread block
-// loads a frame into LDS and leaves its cumulative-mean-normalised difference function d' there (the
-// host definition is mbexwn_vocoder_amd/f0track.py::difference_host).
+// The part the F0 tracker (f0_track.hip), its streaming form (f0_stream.hip) and the candidates kernel of the decoder
+// (f0_decode.hip) share: one 256-thread block loads a frame into LDS (f0_frame_load, with the kernel's own fetch) and leaves
+// its cumulative-mean-normalised difference function d' there (f0_frame_dprime; the host definition is
+// mbexwn_vocoder_amd/f0track.py::difference_host); the two trackers then share the pick (f0_frame_pick).
 //
 //   y[i]   = x[c - L/2 + i], 0 outside the item            L = W + tau_max, c = centres[b][k] clamped to [0, n_b]
 //   d[tau] = sum_j (y[s + j] - y[s + tau + j])^2           s = (tau_max - tau) >> 1, 0 <= j < W, 1 <= tau <= tau_max
@@ -9,6 +10,9 @@
 // Host and device must give the same bits: every operation is one separately rounded IEEE float32 operation.  This header
 // sets `#pragma clang fp contract(off)` itself, and it holds for the rest of a file that includes this header.
 #pragma once
+
+#include <climits>
+#include <cmath>
 
 #include <hip/hip_runtime.h>
 
@@ -39,23 +43,40 @@ __device__ inline float f0_lane_sum(float a) {
     return a;
 }
 
-// The frame of item row `xb` (n samples) centred on c, through to d'.  The whole block calls it.  `smem` holds W + 2 TM + 1
-// floats: on return smem + W + TM is d' (TM + 1 entries, d'[0] = 1) and the W + TM floats in front of it are free; *s_energy
-// (one __shared__ float) is the energy of the W samples about the centre.  Returns, on every thread, whether the frame
-// touches a sample that is not finite or above F0_SAMPLE_LIMIT.  Ends behind a __syncthreads().
-__device__ inline int f0_frame_dprime(const float *xb, long long n, long long c, int W, int TM, float *smem, float *s_energy) {
-    const int L = W + TM;
-    float *y = smem;                                        // (L) the frame; later (TM + 1) the running sums of d
-    float *d = smem + L;                                    // (TM + 1) d, then d'
-    const long long first = c - (L >> 1);
+// The load of a frame into LDS: y[i] = fetch(i) for 0 <= i < L, where fetch(i) is sample c - L/2 + i of the sound or 0 outside
+// it -- the item's row (f0_track.hip, f0_decode.hip) or a stream's ring (f0_stream.hip); only the fetch differs between
+// them.  The whole block calls it.  Returns, on every thread, whether the frame touches a sample that is not finite or above
+// F0_SAMPLE_LIMIT.  Ends behind a __syncthreads().
+template <typename Fetch>
+__device__ inline int f0_frame_load(Fetch fetch, int L, float *y) {
     int bad = 0;
     for (int i = threadIdx.x; i < L; i += F0_THREADS) {
-        const long long s = first + i;
-        const float v = (s >= 0 && s < n) ? xb[s] : 0.f;
+        const float v = fetch(i);
         if (!(fabsf(v) <= F0_SAMPLE_LIMIT)) bad = 1;
         y[i] = v;
     }
-    bad = __syncthreads_or(bad);
+    return __syncthreads_or(bad);
+}
+
+// the fetch of an item row `xb` of n samples for the frame centred on c
+struct F0RowFetch {
+    const float *xb;
+    long long n, first;
+    __device__ F0RowFetch(const float *xb_, long long n_, long long c, int L) : xb(xb_), n(n_), first(c - (L >> 1)) {}
+    __device__ float operator()(int i) const {
+        const long long s = first + i;
+        return (s >= 0 && s < n) ? xb[s] : 0.f;
+    }
+};
+
+// Everything behind the load, through to d'.  The whole block calls it, behind f0_frame_load.  `smem` holds W + 2 TM + 1
+// floats, the first L = W + TM of them the frame: on return smem + W + TM is d' (TM + 1 entries, d'[0] = 1) and the W + TM
+// floats in front of it are free; *s_energy (one __shared__ float) is the energy of the W samples about the centre.  Ends
+// behind a __syncthreads().
+__device__ inline void f0_frame_dprime(int W, int TM, float *smem, float *s_energy) {
+    const int L = W + TM;
+    float *y = smem;                                        // (L) the frame; later (TM + 1) the running sums of d
+    float *d = smem + L;                                    // (TM + 1) d, then d'
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int terms = W >> 6;
@@ -110,7 +131,6 @@ __device__ inline int f0_frame_dprime(const float *xb, long long n, long long c,
         d[tau] = ct > 0.f ? num / ct : 1.f;
     }
     __syncthreads();
-    return bad;
 }
 
 // f0track.pick_host's refinement of a lag tau in [2, tau_max - 1]: float(tau) plus the vertex of the parabola through
@@ -124,6 +144,53 @@ __device__ inline float f0_refined_lag(const float *d, int tau) {
         off = fminf(fmaxf(off, -1.f), 1.f);
     }
     return (float)tau + off;
+}
+
+// f0track.pick_host on the d' of a frame: the first lag in [max(tau_min, 2), TM - 1] below the threshold, walked on to its
+// local minimum and refined.  ONE whole wave calls it (every lane active) behind f0_frame_dprime; the results are valid on
+// lane 0.  `bad`: the frame touches a sample that is not finite -- unvoiced with periodicity 1.
+__device__ inline void f0_frame_pick(const float *d, int tau_min, int TM, float threshold, float e_min, float energy,
+                                     int sample_rate, int bad, float &f0, float &per) {
+    const int lane = threadIdx.x & 63;
+    // the first lag below the threshold, and the first lag of the minimum, over [lo, hi]: per lane, then over the wave
+    const int lo = max(tau_min, 2), hi = TM - 1;
+    int pick = INT_MAX, best = INT_MAX;
+    float best_v = INFINITY;
+    for (int tau = lo + lane; tau <= hi; tau += 64) {
+        const float v = d[tau];
+        if (v < threshold && pick == INT_MAX) pick = tau;
+        if (v < best_v) {
+            best_v = v;
+            best = tau;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        pick = min(pick, __shfl_xor(pick, m, 64));
+        const float ov = __shfl_xor(best_v, m, 64);
+        const int oi = __shfl_xor(best, m, 64);
+        if (ov < best_v || (ov == best_v && oi < best)) {
+            best_v = ov;
+            best = oi;
+        }
+    }
+    f0 = 0.f;
+    per = 1.f;
+    if (lane != 0) return;
+    if (pick == INT_MAX) {
+        per = best == INT_MAX ? d[lo] : best_v;
+    } else {
+        int tau = pick;
+        while (tau + 1 <= hi && d[tau + 1] < d[tau]) ++tau;
+        per = d[tau];
+        if (energy >= e_min) {
+            f0 = (float)sample_rate / f0_refined_lag(d, tau);
+        }
+    }
+    if (bad) {
+        f0 = 0.f;
+        per = 1.f;
+    }
 }
 
 }  // namespace mbx

@@ -6,9 +6,10 @@
 //   d'[tau] = d[tau] tau / (d[1] + .. + d[tau])            the cumulative-mean-normalised difference function
 //   pick   = first tau in [lo, hi] with d' < thr, walked down to its local minimum, refined by a parabola
 //
-// One 256-thread block per (frame, item).  Everything up to d' is f0_frame.h's f0_frame_dprime, which the candidates kernel
-// of f0_decode.hip calls too.  The frame's L samples sit in LDS; each of the four waves takes every fourth pair
-// of lags with a common s (so the first window is read once for two lags): lane l sums the W / 64 terms j = l + 64 k in
+// One 256-thread block per (frame, item).  Everything is f0_frame.h's: the load of the frame with the row's fetch, d'
+// (f0_frame_dprime, which the candidates kernel of f0_decode.hip calls too) and the pick (f0_frame_pick); the streaming
+// tracker of f0_stream.hip runs the same two functions behind a fetch from its ring.
+// The frame's L samples sit in LDS; each of the four waves takes every fourth pair of lags with a common s (so the first window is read once for two lags): lane l sums the W / 64 terms j = l + 64 k in
 // order, and the wave adds the 64 partial sums in the order of the definition's halving tree with lane swaps and DPP, not
 // through LDS (float addition commutes, so which partner is the left operand does not matter; lane 0 ends with the tree's
 // value).  The running sum of d is one thread's sequential chain (it is the definition's order); the division and the two
@@ -38,48 +39,12 @@ __global__ __launch_bounds__(F0_THREADS) void f0_track_kernel(PitchArgs p) {
     // length and centre from the device arrays, clamped to the item's row: a wrong entry must not address outside the buffer
     const long long n = min(max((long long)p.n_samples[b], 0LL), p.stride);
     const long long c = min(max(p.centres[(long long)b * p.max_frames + k], 0LL), n);
-    const int bad = f0_frame_dprime(p.audio + (long long)b * p.stride, n, c, W, TM, f0_smem, &s_energy);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (wave != 0) return;
-
-    // the first lag below the threshold, and the first lag of the minimum, over [lo, hi]: per lane, then over the wave
-    const int lo = max(p.tau_min, 2), hi = TM - 1;
-    int pick = INT_MAX, best = INT_MAX;
-    float best_v = INFINITY;
-    for (int tau = lo + lane; tau <= hi; tau += 64) {
-        const float v = d[tau];
-        if (v < p.threshold && pick == INT_MAX) pick = tau;
-        if (v < best_v) {
-            best_v = v;
-            best = tau;
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        pick = min(pick, __shfl_xor(pick, m, 64));
-        const float ov = __shfl_xor(best_v, m, 64);
-        const int oi = __shfl_xor(best, m, 64);
-        if (ov < best_v || (ov == best_v && oi < best)) {
-            best_v = ov;
-            best = oi;
-        }
-    }
-    if (lane != 0) return;
-    float f0 = 0.f, per;
-    if (pick == INT_MAX) {
-        per = best == INT_MAX ? d[lo] : best_v;
-    } else {
-        int tau = pick;
-        while (tau + 1 <= hi && d[tau + 1] < d[tau]) ++tau;
-        per = d[tau];
-        if (s_energy >= p.e_min) {
-            f0 = (float)p.sample_rate / f0_refined_lag(d, tau);
-        }
-    }
-    if (bad) {
-        f0 = 0.f;
-        per = 1.f;
-    }
+    const int bad = f0_frame_load(F0RowFetch(p.audio + (long long)b * p.stride, n, c, L), L, f0_smem);
+    f0_frame_dprime(W, TM, f0_smem, &s_energy);
+    if (threadIdx.x >= 64) return;
+    float f0, per;
+    f0_frame_pick(d, p.tau_min, TM, p.threshold, p.e_min, s_energy, p.sample_rate, bad, f0, per);
+    if (threadIdx.x != 0) return;
     const long long o = (long long)b * p.max_frames + k;
     p.f0[o] = f0;
     p.periodicity[o] = per;

@@ -1,7 +1,7 @@
 // The engine's handle and what mbx_create.hip, mbx_forward.hip and mbx_api.hip share: the last-error string, the uploaded
 // tensors and the records that resolve them once (mbx_create), workspace carving, the argument builders of the launch
 // sequence.  mbx_stages.hip, whose entry points take no handle, includes it for fail, launch_status and HIP_TRY alone.
-// Internal: the C ABI is include/mbexwn.h and the ten headers beside it.
+// Internal: the C ABI is include/mbexwn.h and the eleven headers beside it.
 #pragma once
 
 #include <hip/hip_runtime.h>

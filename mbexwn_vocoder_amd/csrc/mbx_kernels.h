@@ -441,6 +441,21 @@ struct PitchArgs {
 const char *check_track_f0(const PitchArgs &a);
 void launch_track_f0(const PitchArgs &a, hipStream_t stream);
 
+// the same tracker for sounds that are still arriving (f0_stream.hip; include/mbexwn_live_pitch.h: mbxt_f0_frames): frames
+// at t * hop from the ring store of the streaming mel analysis, on its descriptor table
+struct PitchStreamArgs {
+    const float *rings;          // (n_slots, ring_samples)
+    int n_slots, ring_samples;   // ring_samples a power of two, at least window + tau_max
+    const long long *desc;       // (n_streams, 4): slot, first_frame, n_frames, n_total (< 0: the stream is still open)
+    int n_streams, max_new_frames;
+    int hop, sample_rate, window, tau_min, tau_max;
+    float threshold, e_min;
+    float *f0, *periodicity;     // (n_streams, max_new_frames) each; rows at or behind a stream's n_frames are not written
+};
+// nullptr when the arguments describe a valid launch, else what is wrong with them
+const char *check_f0_stream(const PitchStreamArgs &a);
+void launch_f0_stream(const PitchStreamArgs &a, hipStream_t stream);
+
 // A decoded contour (f0_decode.hip; include/mbexwn_contour.h: mbxc_f0_candidates, mbxc_decode_f0): per frame up to seven
 // candidate lags and an "unvoiced" state from the tracker's d', then a Viterbi path per item; the host definition is
 // f0decode.py (candidates_host, viterbi_host)

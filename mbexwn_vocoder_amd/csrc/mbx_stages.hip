@@ -1,6 +1,7 @@
 // C ABI of the stages that take no engine handle: mbx_mel_analysis and mbx_encode_flac16 of include/mbexwn.h and the entry
-// points of the ten headers beside it (mbxa_ resampler, mbxl_ / mbxr_ / mbxo_ live rings, mbxf_ FLAC, mbxn_ noise, mbxw_ mel
-// warp, mbxe_warp_envelope, mbxp_ tracker, mbxc_ decoder; mbxe_forward takes a handle and is in mbx_api.hip).  Each one copies
+// points of the eleven headers beside it (mbxa_ resampler, mbxl_ / mbxr_ / mbxo_ live rings, mbxf_ FLAC, mbxn_ noise, mbxw_ mel
+// warp, mbxe_warp_envelope, mbxp_ tracker, mbxc_ decoder, mbxt_ streaming tracker; mbxe_forward takes a handle and is in
+// mbx_api.hip).  Each one copies
 // its arguments into the kernel's struct, lets check_* (beside the kernel) refuse them, enqueues on the caller's stream and
 // reports the launch error.  A new entry point: prototype in its header, a row in abi.py's TABLE, the body here.
 #include "mbx_handle.h"
@@ -14,6 +15,7 @@
 #include "../../include/mbexwn_pitch.h"
 #include "../../include/mbexwn_contour.h"
 #include "../../include/mbexwn_envelope.h"
+#include "../../include/mbexwn_live_pitch.h"
 
 static_assert(MBXN_FILL_TILE == mbx::NOISE_TILE, "mbexwn_noise.h states the tile of noise_keyed.hip");
 static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
@@ -321,6 +323,30 @@ mbx_status mbxc_decode_f0(const float *period, const float *cost, const float *d
     if (const char *why = mbx::check_decode_f0(a)) return refuse("decode f0", why);
     if (batch == 0) return MBX_OK;
     mbx::launch_decode_f0(a, static_cast<hipStream_t>(hip_stream));
+    return launch_status("kernel launch: ");
+}
+
+mbx_status mbxt_f0_frames(const float *rings, int32_t n_slots, int32_t ring_samples, const int64_t *desc, int32_t n_streams,
+                          int32_t max_new_frames, int32_t hop, int32_t sample_rate, int32_t window, int32_t tau_min,
+                          int32_t tau_max, float threshold, float e_min, float *f0, float *periodicity, void *hip_stream) {
+    mbx::PitchStreamArgs a{};
+    a.rings = rings;
+    a.n_slots = n_slots;
+    a.ring_samples = ring_samples;
+    a.desc = reinterpret_cast<const long long *>(desc);
+    a.n_streams = n_streams;
+    a.max_new_frames = max_new_frames;
+    a.hop = hop;
+    a.sample_rate = sample_rate;
+    a.window = window;
+    a.tau_min = tau_min;
+    a.tau_max = tau_max;
+    a.threshold = threshold;
+    a.e_min = e_min;
+    a.f0 = f0;
+    a.periodicity = periodicity;
+    if (const char *why = mbx::check_f0_stream(a)) return refuse("f0 frames", why);
+    mbx::launch_f0_stream(a, static_cast<hipStream_t>(hip_stream));
     return launch_status("kernel launch: ");
 }
 

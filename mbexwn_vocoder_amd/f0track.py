@@ -220,6 +220,45 @@ def fill_unvoiced(f0):
     return out
 
 
+F0_FILLS = ("interpolate", "hold")
+
+
+def check_fill(f0_fill, f0_source, what):
+    """Raise ValueError unless ``f0_fill`` is a fill and goes with ``f0_source``: "hold" fills a tracked contour."""
+    if f0_fill not in F0_FILLS:
+        raise ValueError(f"{what}: f0_fill must be one of {F0_FILLS}, got {f0_fill!r}")
+    if f0_fill == "hold" and f0_source != "audio":
+        raise ValueError(f"{what}: f0_fill='hold' fills the tracked contour and needs f0_source='audio'")
+
+
+def fill_tracked(f0, f0_fill="interpolate", f0_initial=150.0):
+    """The oscillator's contour from a tracked one: :func:`fill_unvoiced` (None without a voiced frame) or, "hold",
+    :func:`fill_hold`."""
+    return fill_hold(f0, f0_initial) if f0_fill == "hold" else fill_unvoiced(f0)
+
+
+def fill_hold(f0, initial=150.0):
+    """The causal fill, what a stream can do: voiced frames keep their bits, an unvoiced frame takes
+    the last voiced value in front of it, frames in front of the first voiced one take ``float32(initial)``.  Always an
+    array (float32, the shape of ``f0``).  Chunk by chunk with the last value of a chunk's result as the next chunk's
+    ``initial`` it gives what it gives on the whole contour."""
+    f0 = np.asarray(f0, dtype=f32)
+    if f0.ndim != 1:
+        raise ValueError(f"fill_hold: the contour must be 1-D, got shape {f0.shape}")
+    if not np.all(np.isfinite(f0)) or np.any(f0 < 0):
+        raise ValueError("fill_hold: the contour must be finite and not negative (0 = unvoiced)")
+    try:
+        with np.errstate(over="ignore"):
+            start = f32(initial)
+    except (TypeError, ValueError):
+        raise ValueError(f"fill_hold: initial must be a finite positive frequency in Hz, got {initial!r}") from None
+    if start.ndim != 0 or not (np.isfinite(start) and start > 0):
+        raise ValueError(f"fill_hold: initial must be a finite positive frequency in Hz, got {initial!r}")
+    # the index of the last voiced frame at or in front of every frame, -1 in front of the first
+    last = np.maximum.accumulate(np.where(f0 > 0, np.arange(f0.size), -1)) if f0.size else np.zeros(0, dtype=np.int64)
+    return np.where(last >= 0, f0[np.maximum(last, 0)], start).astype(f32)
+
+
 def frame_times(n_frames, hop, sample_rate):
     """The time in seconds of every frame on the synthesis grid: frame k drives the hop samples from ``k * hop`` on."""
     return np.arange(int(n_frames), dtype=np.float64) * (int(hop) / float(sample_rate))

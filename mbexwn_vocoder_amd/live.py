@@ -25,7 +25,8 @@ import numpy as np
 
 from .analysis import mel_analysis_tables, mell_header
 from .live_plan import (AnalysisPlan, FrameFactors, OutputPlan, _AStream, _OStream, _pow2_at_least, check_rate,  # noqa: F401
-                        frame_factors, frames_ready, frames_total, input_keep_from, outputs_ready, stream_frames_ready)
+                        f0_frames_ready, frame_factors, frames_ready, frames_total, input_keep_from, outputs_ready,
+                        stream_frames_ready)
 from .resample import _host_taps, device_taps, positive_rate
 
 
@@ -53,6 +54,12 @@ class _RingStore:
         self.ring_samples = _pow2_at_least(ring_samples)
         self.slots, self._first_slots, self._free = 0, max(1, int(first_slots)), []
         self.rings = None             # (slots, ring_samples) float32 on the device
+
+    def at_least(self, ring_samples):
+        """Rings of at least ``ring_samples`` samples from the start (before the store is on the device; later ``ensure``
+        grows it)."""
+        if self.rings is None:
+            self.ring_samples = max(self.ring_samples, _pow2_at_least(ring_samples))
 
     def take(self):
         if not self._free:
@@ -172,7 +179,16 @@ class StreamingAnalyzer(_Stage):
     final -- ``outputs_ready`` -- into the stream's model-rate ring.  Behind that ring nothing differs: the stream's
     model-rate length is the count of outputs produced, and the rows are those of ``generate_mels`` on the whole sound at R,
     bit for bit.  The input store grows as the other does; its rule is ``input_keep_from``.  A tick without resampled
-    streams is the tick described above, launch for launch."""
+    streams is the tick described above, launch for launch.
+
+    ``open(stream_id, f0_params=P)`` with P an ``f0track.params`` dictionary at the model rate gives a stream that tracks its
+    F0 (csrc/f0_stream.hip, include/mbexwn_live_pitch.h): a frame is handed out when its mel window and
+    the L = window + tau_max samples of its F0 frame have both arrived (``f0_frames_ready``), a tick with such streams adds one
+    ``mbxt_f0_frames`` launch behind ``mbxl_mel_frames`` on the same descriptor table, and the tick's values are in
+    ``last_f0`` -- {stream_id: (f0, periodicity)}, float32, one value per mel row handed out, 0 = unvoiced.  Concatenated they
+    are ``f0track.track_f0_host(sound, arange(0, n + 1, hop), P)`` bit for bit.  The tracker reads the model-rate ring, so a
+    resampled stream needs nothing special.  All tracking streams of an analyzer share one P.  A tick without tracking
+    streams makes the launches it made before and no others."""
 
     def __init__(self, preprocess_config, device=None, ring_samples=None, slots=16, input_ring_samples=None):
         cfg = preprocess_config
@@ -190,15 +206,32 @@ class StreamingAnalyzer(_Stage):
         self._in_store = _RingStore(int(input_ring_samples or 4096), slots)     # the input-rate store of the resampled streams
         self._tables = None
         self._stage_host = self._stage_dev = None     # one tick's descriptors and samples: pinned, and its device twin
+        self.f0_params = None         # the parameters of the tracking streams: set by the first one opened
+        self.last_f0 = {}             # {stream_id: (f0, periodicity)} of the last tick's rows of the tracking streams
 
     input_ring_samples = property(lambda self: self._in_store.ring_samples)
     input_rings = property(lambda self: self._in_store.rings)   # None until the first tick with a resampled stream
 
     # -- host side ----------------------------------------------------------------------------------------------------
-    def open(self, stream_id, sample_rate=None):
-        """Open a stream; ``sample_rate``: the rate its pushes will be at (None or the model's: no resampling)."""
+    def open(self, stream_id, sample_rate=None, f0_params=None, f0_decode=None):
+        """Open a stream; ``sample_rate``: the rate its pushes will be at (None or the model's: no resampling);
+        ``f0_params``: an ``f0track.params`` dictionary at the model rate -- the stream tracks its F0 (``last_f0``)."""
         if stream_id in self.streams:
             raise ValueError(f"stream {stream_id!r} is open already")
+        if f0_decode is not None:
+            raise ValueError(f"stream {stream_id!r}: f0_decode decodes the contour over the whole sound (f0decode.py), which a "
+                             "stream does not have; streams track every frame on its own")
+        f0_len = None
+        if f0_params is not None:
+            from .f0track import check_params
+            f0_params = check_params(dict(f0_params))
+            if int(f0_params["sample_rate"]) != self.model_rate:
+                raise ValueError(f"stream {stream_id!r}: f0_params are for {f0_params['sample_rate']} Hz, the tracker reads the "
+                                 f"model-rate samples at {self.model_rate} Hz")
+            if self.f0_params is not None and f0_params != self.f0_params and any(
+                    st.f0_len is not None for st in self.streams.values()):
+                raise ValueError(f"stream {stream_id!r}: the tracking streams of an analyzer share one set of f0_params")
+            f0_len = int(f0_params["window"]) + int(f0_params["tau_max"])
         rate, filt = None, None
         if sample_rate is not None:
             if not np.isfinite(sample_rate) or int(round(sample_rate)) <= 0:
@@ -207,7 +240,11 @@ class StreamingAnalyzer(_Stage):
                 rate = int(round(sample_rate))
                 filt = resampling_filter(rate, self.model_rate)
         slot = self._store.take()       # the device stores follow at the next tick (_RingStore.ensure)
-        self.streams[stream_id] = _AStream(slot) if rate is None else _AStream(slot, rate, self._in_store.take(), filt)
+        self.streams[stream_id] = (_AStream(slot, f0_len=f0_len) if rate is None else
+                                   _AStream(slot, rate, self._in_store.take(), filt, f0_len=f0_len))
+        if f0_len is not None:
+            self.f0_params = f0_params
+            self._store.at_least(f0_len)        # the tracker's frame must fit the ring
 
     def close(self, stream_id):
         """Forget a stream (its slots are reused)."""
@@ -268,24 +305,32 @@ class StreamingAnalyzer(_Stage):
             self._tables = [torch.as_tensor(np.ascontiguousarray(tt), device=dev) for tt in self._tables_host]
         # a fresh stream's slot still holds another stream's samples: nothing of it moves to a longer ring
         held = ((st.slot, st.on_device) for st in self.streams.values() if st.on_device and not st.fresh)
-        self.device_allocations += self._store.ensure(dev, plan.ring_needed, held)
+        ring_needed = max(plan.ring_needed, self._f0_len() if plan.T else 0)
+        self.device_allocations += self._store.ensure(dev, ring_needed, held)
         if plan.R:
             held = ((st.in_slot, st.in_on_device) for st in self.streams.values() if st.rate is not None and st.in_on_device)
             self.device_allocations += self._in_store.ensure(dev, plan.in_ring_needed, held)
             for rate, _, _, _ in plan.groups:
                 self._device_taps(rate)
 
+    def _f0_len(self):
+        return int(self.f0_params["window"]) + int(self.f0_params["tau_max"])
+
     def tick(self):
         """Append what was pushed to the rings and compute every frame that became ready.
-        Returns {stream_id: ndarray (n, mel_channels) float32} for the streams with new frames."""
+        Returns {stream_id: ndarray (n, mel_channels) float32} for the streams with new frames; ``last_f0`` then holds the
+        tracked (f0, periodicity) of those rows for the streams that track."""
         plan = self.plan()
+        self.last_f0 = {}
         if not plan.rows:
             return {}
         import torch
         from .abi import _check, load_library
         self._ensure(plan)
         lib, rings, in_rings, tabs = load_library(), self.rings, self.input_rings, self._tables
-        S, R, body, used, floats = plan.S, plan.R, plan.body, plan.body + plan.samples, plan.S * plan.max_new * self.n_mels
+        S, R, body, used, mel_floats = plan.S, plan.R, plan.body, plan.body + plan.samples, plan.S * plan.max_new * self.n_mels
+        plane = plan.T * plan.max_new           # the two planes of the tracker ride behind the mel rows in the one copy back
+        floats = mel_floats + 2 * plane
         self._stage_host, self._stage_dev = self._grown_pair(self._stage_host, self._stage_dev, used, torch.float32)
         self._out_host, self._out_dev = self._grown_pair(self._out_host, self._out_dev, floats, torch.float32)
         plan.pack(self._stage_host.numpy())
@@ -309,8 +354,18 @@ class StreamingAnalyzer(_Stage):
                                        tabs[1].data_ptr(), tabs[2].data_ptr(), tabs[3].data_ptr(), tabs[4].data_ptr(),
                                        ctypes.c_float(float(np.finfo(np.float32).eps)), self._out_dev.data_ptr(),
                                        stream.cuda_stream))
-            rows = self._copy_back(stream, events, floats).reshape(S, plan.max_new, self.n_mels)
+            if plane:
+                prm, out = self.f0_params, self._out_dev.data_ptr() + 4 * mel_floats
+                _check(lib.mbxt_f0_frames(rings.data_ptr(), int(rings.shape[0]), self.ring_samples, base + 32 * S, plan.T,
+                                          plan.max_new, self.hop, int(prm["sample_rate"]), int(prm["window"]),
+                                          int(prm["tau_min"]), int(prm["tau_max"]), ctypes.c_float(float(prm["threshold"])),
+                                          ctypes.c_float(float(prm["e_min"])), out, out + 4 * plane, stream.cuda_stream))
+            packed = self._copy_back(stream, events, floats)
+            rows = packed[:mel_floats].reshape(S, plan.max_new, self.n_mels)
+            tracked = packed[mel_floats:].reshape(2, plan.T, plan.max_new)
         result = {sid: rows[row, :nn].copy() for row, (sid, nn) in enumerate(plan.rows) if nn}
+        self.last_f0 = {sid: (tracked[0, row, :nn].copy(), tracked[1, row, :nn].copy())
+                        for row, (sid, nn) in enumerate(plan.rows[:plan.T]) if nn}
         self.commit(plan)
         self.ticks += 1
         return result
@@ -469,6 +524,7 @@ class _LStream:
         self.rng, self.noise_fn = rng, noise_fn
         self.flushed = False          # the synthesizer has been told that the stream is over
         self.out_rate = None          # the stream's output rate when it is not the model's: it goes through the output stage
+        self.f0_hold = None           # f0_source="audio": the last voiced F0 (float32), what an unvoiced frame takes
 
 
 class LiveResynthesizer:
@@ -485,7 +541,14 @@ class LiveResynthesizer:
 
     A stream's output then equals ``mel_inverter.synth_from_mel(scale_mel(mell dictionary of the whole sound), noise=the
     same draw, transposition=the per-frame factors)`` bit for bit, when the engine is pinned to ``conv_form="f23"`` (the
-    form the streams run) and the mel is the device analysis of the sound (``compute_log_mel_device``)."""
+    form the streams run) and the mel is the device analysis of the sound (``compute_log_mel_device``).
+
+    Pitch source: a stream opened with ``f0_source="audio"`` sings with the pitch that is in the sound:
+    the analyzer tracks its F0 on the device, every tick turns the tracked values into a positive contour by the causal
+    rule of ``f0track.fill_hold`` -- an unvoiced frame holds the last voiced value, ``f0_initial`` in front of the first --
+    and pushes it with the mel rows to a synthesizer stream opened with ``f0="frames"``.  The stream then equals
+    ``MELInverter.transform_audio(f0_source="audio", f0_fill="hold", f0_initial=...)`` of the sound under the same noise.
+    ``last_f0`` holds the raw tracked values of the last tick (0 = unvoiced)."""
 
     def __init__(self, mel_inverter, chunk_frames=(6, 6, 7, 6, 7)):
         from .streaming import StreamingSynthesizer
@@ -511,13 +574,28 @@ class LiveResynthesizer:
         frames = -(-(an.win - an.win // 2) // an.hop)
         return 1000.0 * frames * an.hop / an.sample_rate + self.synthesizer.lookahead_ms
 
-    def lookahead_ms_for(self, sample_rate=None, output_rate=None):
+    last_f0 = property(lambda self: self.analyzer.last_f0)      # {stream_id: (f0, periodicity)} of the last tick
+
+    def _f0_params(self, f0_params):
+        from .f0track import check_params, params
+        return params(self.analyzer.model_rate) if f0_params is None else check_params(dict(f0_params))
+
+    def lookahead_ms_for(self, sample_rate=None, output_rate=None, f0_source="net", f0_params=None):
         """``lookahead_ms`` of a stream opened at ``sample_rate`` and ``output_rate``: a resampled stream waits for half
         its filter as well, half / up input samples (0.92 ms at 44.1 and 48 kHz, 1.4 ms at 16 kHz for a 24 kHz model); a
         stream with an output rate waits for half the output filter, half / up model-rate samples (0.92 ms to 48 kHz,
-        0.94 ms to 44.1 kHz, 1.4 ms to 16 kHz)."""
+        0.94 ms to 44.1 kHz, 1.4 ms to 16 kHz).  With ``f0_source="audio"`` a frame waits for its F0 frame too, L = window
+        + tau_max of ``f0_params`` (None: the defaults) samples about its centre: the analysis part is
+        ceil(max(win - win // 2, L - L // 2) / hop) frames -- 3 instead of 2 with the defaults at 24 kHz."""
         model = self.analyzer.model_rate
         ms = self.lookahead_ms
+        if f0_source not in ("net", "audio"):
+            raise ValueError(f"f0_source must be 'net' or 'audio', got {f0_source!r}")
+        if f0_source == "audio":
+            an, prm = self.analyzer, self._f0_params(f0_params)
+            reach, f0_len = an.win - an.win // 2, int(prm["window"]) + int(prm["tau_max"])
+            frames = -(-max(reach, f0_len - f0_len // 2) // an.hop)
+            ms += 1000.0 * (frames - -(-reach // an.hop)) * an.hop / an.sample_rate
         if sample_rate is not None and int(round(sample_rate)) != model:
             ms += resampling_lookahead_ms(sample_rate, model)
         out_rate = resolve_output_rate(output_rate, sample_rate, model)
@@ -525,15 +603,33 @@ class LiveResynthesizer:
             ms += output_lookahead_ms(model, out_rate)
         return ms
 
-    def open(self, stream_id, seed=None, noise_fn=None, sample_rate=None, output_rate=None):
+    def open(self, stream_id, seed=None, noise_fn=None, sample_rate=None, output_rate=None, f0_source="net", f0_params=None,
+             f0_initial=150.0, f0_decode=None):
         """``output_rate``: the rate the stream's audio comes back at -- a rate in Hz, or ``"input"`` for the stream's own
-        ``sample_rate``; None or the model's rate: the model-rate audio, as the synthesizer emits it."""
+        ``sample_rate``; None or the model's rate: the model-rate audio, as the synthesizer emits it.  ``f0_source``:
+        ``"net"`` -- the F0-net's contour -- or ``"audio"``: the tracked pitch of the sound (``f0_params``: an
+        ``f0track.params`` dictionary at the model rate, None = its defaults; ``f0_initial``: Hz of the frames in front of the
+        first voiced one).  ``f0_decode`` is refused: decoding the contour needs the whole sound."""
+        if f0_source not in ("net", "audio"):
+            raise ValueError(f"f0_source must be 'net' or 'audio', got {f0_source!r}")
+        if f0_decode is not None:
+            raise ValueError(f"stream {stream_id!r}: f0_decode decodes the contour over the whole sound (f0decode.py), which a "
+                             "stream does not have; streams track every frame on its own")
+        hold = None
+        if f0_source == "audio":
+            f0_params = self._f0_params(f0_params)
+            hold = np.float32(f0_initial)
+            if not (np.isfinite(hold) and hold > 0):
+                raise ValueError(f"f0_initial must be a finite positive frequency in Hz, got {f0_initial!r}")
+        elif f0_params is not None:
+            raise ValueError("f0_params go with f0_source='audio'")
         out_rate = resolve_output_rate(output_rate, sample_rate, self.analyzer.sample_rate)
-        self.analyzer.open(stream_id, sample_rate=sample_rate)
-        self.synthesizer.open(stream_id)
+        self.analyzer.open(stream_id, sample_rate=sample_rate, f0_params=f0_params)
+        self.synthesizer.open(stream_id, f0="net" if hold is None else "frames")
         up, down = (self.analyzer.streams[stream_id].filt or (1, 1))[:2]
         st = self.streams[stream_id] = _LStream(self.analyzer.hop, None if noise_fn else np.random.default_rng(seed),
                                                 noise_fn, up, down)
+        st.f0_hold = hold
         if out_rate is not None:
             self.output.open(stream_id, out_rate)
             st.out_rate = out_rate
@@ -600,6 +696,13 @@ class LiveResynthesizer:
                 scaled = np.zeros((0, self.dims.mel_channels), dtype=np.float32)
             noise = self._noise(sid, st, first, end) if self.dims.noise_sigma else None
             shift = {} if st.formants is None else {"formant": st.formants.take(first, end)}
+            if st.f0_hold is not None:
+                # the tick's tracked values as a positive contour, causally (the flush push carries an empty one)
+                from .f0track import fill_hold
+                tracked = self.analyzer.last_f0.get(sid, (np.zeros(0, dtype=np.float32),))[0]
+                shift["f0"] = fill_hold(tracked, st.f0_hold)
+                if n:
+                    st.f0_hold = shift["f0"][-1]
             self.synthesizer.push(sid, scaled, noise, last=done, transposition=st.factors.take(first, end), **shift)
             st.frames, st.flushed = end, done
         audio = self.synthesizer.tick()

@@ -29,6 +29,16 @@ def frames_ready(have, hop, win, closed=False):
     return 0 if have < need else (have - need) // hop + 1
 
 
+def f0_frames_ready(have, hop, L, closed=False):
+    """Frames of a stream whose F0 the streaming tracker can compute once ``have`` samples have arrived: frame t reads the L =
+    window + tau_max samples from t * hop - L // 2 on, so while the stream is open it is ready when t * hop - L // 2 + L <=
+    have; a closed stream has all frames_total(have) frames (behind the end is silence, as offline)."""
+    if closed:
+        return frames_total(have, hop)
+    need = L - L // 2
+    return 0 if have < need else (have - need) // hop + 1
+
+
 def outputs_ready(have, up, down, half, closed=False):
     """Model-rate samples of a resampled stream that are final once ``have`` input samples have arrived: output k reads the
     input up to sample (k * down + half) // up, so while the stream is open it is final when k * down + half <=
@@ -114,8 +124,9 @@ def rate_groups(rates, new):
 
 
 class _AStream:
-    def __init__(self, slot, rate=None, in_slot=None, filt=None):
+    def __init__(self, slot, rate=None, in_slot=None, filt=None, f0_len=None):
         self.slot = slot
+        self.f0_len = f0_len      # None, or L = window + tau_max of the stream's F0 tracker: a frame waits for its F0 frame too
         self.rate = rate          # None: pushes at the model rate; else the stream's own input rate
         self.in_slot = in_slot    # ... its slot in the input-rate ring store
         self.filt = filt          # ... and its filter: (up, down, half, n_taps)
@@ -133,7 +144,10 @@ def stream_frames_ready(st, hop, win, hold_first=False):
     """``frames_ready`` of an analyzer's stream; ``hold_first``: frame 0 waits for sample win // 2 (StreamingAnalyzer)."""
     if hold_first and not st.closed and st.have < win // 2 + 1:
         return 0
-    return frames_ready(st.have, hop, win, st.closed)
+    ready = frames_ready(st.have, hop, win, st.closed)
+    if st.f0_len is not None:     # a tracking stream hands out a frame when its mel window AND its F0 frame are there
+        ready = min(ready, f0_frames_ready(st.have, hop, st.f0_len, st.closed))
+    return ready
 
 
 def _table(rows, width):
@@ -143,11 +157,17 @@ def _table(rows, width):
 class AnalysisPlan:
     """One tick of the analyzer, planned on the host from its ``streams`` ({id: _AStream}) alone; building one changes
     nothing.  S streams have work -- samples to append or frames that became ready --, R of them are resampled.  The tables
-    are int64, one row per stream, as include/mbexwn_live.h and include/mbexwn_live_resample.h lay them out."""
+    are int64, one row per stream, as include/mbexwn_live.h and include/mbexwn_live_resample.h lay them out.
+
+    The streams that track F0 (``_AStream.f0_len``) come first among the rows, T of them: the tracker's launch reads the
+    first T rows of ``frames``, the table of the mel launch.  Without such a stream the rows are in the order of ``streams``
+    and T = 0: the plan of an analyzer that knows no tracker, field for field."""
 
     def __init__(self, streams, hop, win, hold_first=False):
         work = [(sid, st, stream_frames_ready(st, hop, win, hold_first) - st.emitted) for sid, st in streams.items()]
         work = [(sid, st, max(0, nn)) for sid, st, nn in work if nn > 0 or st.queue or st.have > st.on_device]
+        work.sort(key=lambda item: item[1].f0_len is None)        # stable: the tracking streams in front
+        self.T = sum(st.f0_len is not None for _, st, _ in work)
         sts = [st for _, st, _ in work]
         self.rows = [(sid, nn) for sid, _, nn in work]        # (stream_id, frames to hand out), in the order of ``streams``
         # the rows of the resampled streams, by rate (stable), are the rows of the two (R, .) tables: their samples go to the
@@ -177,7 +197,9 @@ class AnalysisPlan:
         self.max_in = max((counts[row] for row in self.resampled), default=0)
         # the rings hold every sample from the first one a pending frame may read -- the start of the window of the next frame
         # to hand out, less the two samples the reflection at the end can reach in front of it -- to the newest one pushed
-        self.ring_needed = max((st.have - max(0, st.emitted * hop - win // 2 - 2) for st in sts), default=0)
+        # (a tracking stream's next F0 frame starts L // 2 in front of its centre, which may be further back)
+        self.ring_needed = max((st.have - max(0, st.emitted * hop - max(win // 2 + 2, (st.f0_len or 0) // 2)) for st in sts),
+                               default=0)
         # ... the input rings from the first one a pending output may read (never behind what is to be appended)
         self.in_ring_needed = max((st.in_have - min(input_keep_from(st.on_device, *st.filt), st.in_on_device) for st in rs),
                                   default=0)

@@ -318,7 +318,7 @@ class MELInverter(object):
 
     def transform_audio(self, sounds, rates, names, transposition=1.0, noise_seed=0, out_rate=None, max_batch=16,
                         max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None, formant=None,
-                        f0_source="net", f0_params=None, f0_decode=None):
+                        f0_source="net", f0_params=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0):
         """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
         keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
         factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
@@ -343,6 +343,10 @@ class MELInverter(object):
         multiplies on top.  An item without a voiced frame keeps the F0-net.  ``f0_decode``: None -- every frame's pick on its
         own -- or a ``f0decode.decode_params`` dictionary: the contour is the Viterbi path over the YIN candidates of the
         item's frames, which does not jump an octave for single frames.  It needs ``"audio"``.
+        ``f0_fill``: ``"interpolate"`` -- the fill described above -- or ``"hold"``, the causal fill of the live streams
+        (``f0track.fill_hold``): an unvoiced frame holds the last voiced value, the frames in front of
+        the first voiced one take ``f0_initial`` Hz, and every item takes its contour.  It needs ``"audio"`` and exists so that
+        an offline run has the bits of ``LiveResynthesizer.open(f0_source="audio")``.
 
         An item's audio is a function of (sound, rate, name, factor, stretch, formant, seed, out_rate): with a ``batch_invariant``
         engine or one pinned to a convolution form it does not depend on the batch, the order or the other items."""
@@ -358,6 +362,7 @@ class MELInverter(object):
             raise ValueError(f"transform_audio: f0_source must be one of {F0_SOURCES}, got {f0_source!r}")
         if f0_decode is not None and f0_source != "audio":
             raise ValueError("transform_audio: f0_decode decodes the tracked contour and needs f0_source='audio'")
+        f0track.check_fill(f0_fill, f0_source, "transform_audio")
         if f0_source == "audio":
             f0_params = f0track.params(int(round(self.srate)), **(f0_params or {}))
         maps = timemap.per_item(time_stretch, len(sounds), "transform_audio: time_stretch")
@@ -367,7 +372,7 @@ class MELInverter(object):
                               rows_per_frame=self.model.dims.steps_per_frame, f0_out=tracked,
                               f0_params=f0_params if tracked is not None else None, f0_decode=f0_decode)
         scaled = [self.scale_mel(dd) for dd in dicts]
-        contours = None if tracked is None else [f0track.fill_unvoiced(ff) for ff, _ in tracked]
+        contours = None if tracked is None else [f0track.fill_tracked(ff, f0_fill, f0_initial) for ff, _ in tracked]
         rows = [np.full(int(mm.shape[1]), ff, dtype=np.float32) for mm, ff in zip(scaled, factors)]
         return self.synth_from_mels(scaled, max_batch=max_batch, max_padded_frames=max_padded_frames, flac=flac,
                                     flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed,

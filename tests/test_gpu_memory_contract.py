@@ -13,7 +13,9 @@ format: survives a multiply by zero) and once with float32 1e30 (finite: survive
   three equal wrong answers cannot pass.  That is the only tolerance in this file: everything else is equality.
 
 The forward cases are those of test_gpu_wavenet_stages.py, test_gpu_wavenet_blocks.py and test_gpu_backend_stages.py,
-selected by id with their ragged length lists, plus batch shapes those tables do not have.  The one int32 region of the
+selected by id with their ragged length lists, plus batch shapes those tables do not have, plus the per-frame controls
+together (CONTROLS: the control rows are guarded inputs whose entries behind an item's length hold the fill, and env_mel of
+mbxe_forward -- scratch of the caller -- is a guarded, filled buffer of exactly its stated size).  The one int32 region of the
 workspace ("ceps_index") is filled with a valid lifter row instead of the poison (a stale read still changes bits, and
 cannot address outside the lifter table); integer inputs are never poisoned.  The stand-alone entry points are called through
 the library with raw pointers and held bit for bit to the engine's own wrappers, which the parity tests hold to the oracle.
@@ -28,15 +30,17 @@ import numpy as np
 import pytest
 
 import backend_reference as bref
+import control_reference as cref
 import test_gpu_backend_stages as tbe
 import test_gpu_parity as parity
 import test_gpu_wavenet_blocks as tblk
 import test_gpu_wavenet_stages as twn
 import wn_blocks_reference as wnb
 import wn_reference as wnr
-from guarded import FILLS, Guarded, GuardSet
+from guarded import FILLS, Guarded, GuardSet, fill_word
 from helpers import build_case, synthetic_inputs
 from mbexwn_vocoder_amd import flac
+from mbexwn_vocoder_amd.envelope import channel_centres, warp_envelope_host
 from oracle import mbexwn_oracle as orc
 
 E2E_TOL = parity.E2E_TOL
@@ -69,6 +73,19 @@ EXTRA = [
     ("last-one-frame", "speech", [52, 13, 1], F43),
     ("f0net-f32", "speech", twn.RAGGED, dict(F43, f0_accumulate="f32")),
 ]
+# The per-frame controls together (mbx_forward_options.f0_frames / f0_scale / f0_item_mask, env_factor of mbxe_forward), on the
+# small SPEECH model of the control tests (tests/test_gpu_controls.py), its RMS-normalising variant and the causal two-block
+# geometry: every control row is a guarded input of exactly its byte size whose entries at or behind an item's n_frames hold
+# the fill, and env_mel -- "scratch of the caller" -- is a guarded, filled buffer of exactly batch x max_frames x mel floats.
+_SMALL5 = {"mbexwn_config:pp_mod_subnet:n_channels": 32, "mbexwn_config:pp_mod_subnet:n_layers": 5}
+_NORM5 = dict(_SMALL5, **{"mbexwn_config:normalize_rms_from_mell": True, "mbexwn_config:normalize_rms_num_smooth_iters": 1})
+CONTROL_KEYS = ("f0_frames", "f0_scale", "f0_item_mask", "formant")
+ALL_CONTROLS = {"f0_frames": "rows", "f0_scale": "rows", "f0_item_mask": "alternate", "formant": "rows"}
+CONTROLS = [
+    ("backend-speech-controls", ("SPEECH", _SMALL5), tbe.RAGGED, {}, ALL_CONTROLS, "backend"),
+    ("backend-normmel-formant", ("SPEECH", _NORM5), tbe.RAGGED, {}, {"formant": "rows"}, "backend"),
+    ("causal-blocks-controls", tblk.GEOMETRIES["causal"], tblk.RAGGED, {}, ALL_CONTROLS, "blocks"),
+]
 
 
 def _forward_cases():
@@ -91,6 +108,8 @@ def _forward_cases():
         out.append(("backend-" + cid, tbe.GEOMETRIES[geom], lengths, tbe.LARGE_CHECK if lengths is tbe.LARGE else None, {}, fw,
                     "backend"))
     out.append(("backend-pulsepqmf", tblk.GEOMETRIES["pqmf"], tbe.RAGGED, None, {}, {}, "backend"))
+    for cid, model, lengths, kwargs, fw, cutter in CONTROLS:
+        out.append((cid, model, lengths, None, kwargs, fw, cutter))
     small = [case for case in out if case[0].replace("backend-", "") not in LARGE_IDS]
     return small + [case for case in out if case[0].replace("backend-", "") in LARGE_IDS]      # the large launches last
 
@@ -304,6 +323,14 @@ def _case_inputs(case, dims):
     fw = dict(fw)
     if fw.get("f0") == "sweep":
         fw["f0"] = tbe.sweep_contour(lengths, dims.pulse_per_frame)
+    if any(kk in fw for kk in CONTROL_KEYS):
+        rng = np.random.default_rng(908)
+        rows = {"f0_frames": rng.uniform(80.0, 400.0, size=(B, T)).astype(np.float32),
+                "f0_scale": rng.uniform(0.5, 2.0, size=(B, T)).astype(np.float32),
+                "f0_item_mask": (np.arange(B) % 2 == 0).astype(np.int32),          # mixed: the F0-net runs for the odd items
+                "formant": cref.formant_rows(rng, B, T)}
+        rows["formant"][:, 0] = np.float32(1.3)                                      # (a one-frame item is warped too)
+        fw.update({kk: rows[kk] for kk in CONTROL_KEYS if kk in fw})
     return mel, (noise if dims.noise_sigma else None), fw
 
 
@@ -342,6 +369,9 @@ def _stages(torch, eng, cfg, case):
         got = bref.engine_backend_stages(eng, B, T)
         for name, arr in got.items():
             out[name] = [arr[ii, :lengths[ii] * per_frame[name]] for ii in items]
+    if "formant" in case[5]:
+        env = eng.stage("mel_env").cpu().numpy().reshape(B, T, d.mel_channels)
+        out["mel_env"] = [env[ii, :lengths[ii]] for ii in items]
     return out
 
 
@@ -363,6 +393,18 @@ def _run_forward(torch, case, fill):
         dev["f0"] = gs.put("f0", fw["f0"]).view(torch.float32, B, T * d.pulse_per_frame)
     if "transposition" in fw:
         dev["transposition"] = fw["transposition"]
+    for key in CONTROL_KEYS:
+        if key not in fw:
+            continue
+        if key == "f0_item_mask":
+            dev[key] = gs.put(key, fw[key]).view(torch.int32)
+            continue
+        dev[key] = gs.put(key, fw[key]).view(torch.float32, B, T)
+        for ii, ll in enumerate(lengths):                 # entries at or behind an item's n_frames: the fill again
+            dev[key][ii, ll:].view(torch.int32).fill_(fill_word(fill))
+    env_before = eng._env_mel
+    if "formant" in fw:
+        eng._env_mel = gs.new("env_mel", B * T * d.mel_channels * 4).view(torch.float32)
     eng._workspace = ws.payload
     try:
         out = eng.forward(mel_g.view(torch.float32, B, T, d.mel_channels), n_frames=nf_g.view(torch.int32),
@@ -375,12 +417,32 @@ def _run_forward(torch, case, fill):
         stages = _stages(torch, eng, cfg, case)
     finally:
         eng._workspace = None
+        eng._env_mel = env_before
     return audio, stages
 
 
-def _oracle_audio(cfg, raw, wt, mel, noise, f0=None, transposition=1.0):
+def _oracle_audio(cfg, raw, wt, mel, noise, f0=None, transposition=1.0, controls=None):
     """The float64 oracle's audio of one item (1, T hop): OracleModel.forward, with the RMS normalisation of a normalising
-    model in front and its gain behind, and with the contour given or transposed as mbx_forward_options does."""
+    model in front and its gain behind, and with the contour given or transposed as mbx_forward_options does.  controls: the
+    item's per-frame rows {f0_frames, f0_scale, formant: (1, T); f0_item_mask: 0 or 1}, any subset: the contour is built on the
+    host as the header defines it -- LI(f0_frames) for an item that takes the frames, the oracle's own F0-net on the unwarped
+    rows otherwise, times LI(f0_scale) -- and the chains read the rows warped by envelope.warp_envelope_host
+    (tests/control_reference.py: controlled_oracle_audio)."""
+    if controls:
+        ppf = int(orc.OracleModel(cfg, raw, wt).pulse_per_frame)
+        scale = controls.get("f0_scale")
+        if "f0_frames" in controls and controls.get("f0_item_mask", 1):
+            contour = orc.lin_interp(controls["f0_frames"].astype(np.float64)[:, :, None], ppf)[:, :, 0]
+            if scale is not None:
+                # (one float32 multiply of the two float32 interpolations, as the header states it)
+                li = orc.lin_interp(scale.astype(np.float64)[:, :, None], ppf)[:, :, 0]
+                contour = contour.astype(np.float32) * li.astype(np.float32)
+        else:
+            contour = cref.oracle_contour(cfg, raw, wt, mel, scale)
+        env = None
+        if "formant" in controls:
+            env = warp_envelope_host(cref.chain_rows(cfg, mel)[0], controls["formant"], channel_centres(cfg["preprocess_config"]))
+        return cref.controlled_oracle_audio(cfg, raw, wt, mel, noise, contour, env_rows=env)
     om = orc.OracleModel(cfg, raw, wt)
     T = mel.shape[1]
     gain = None
@@ -437,7 +499,9 @@ def test_forward_stays_inside_its_buffers_and_ignores_stale_scratch(torch, fill,
             ll = lengths[ii]
             ref = _oracle_audio(cfg, raw, wt, mel[ii:ii + 1, :ll], None if noise is None else noise[ii:ii + 1, :ll * rpf],
                                 f0=fw["f0"][ii:ii + 1, :ll * d.pulse_per_frame] if "f0" in fw else None,
-                                transposition=fw.get("transposition", 1.0))[0]
+                                transposition=fw.get("transposition", 1.0),
+                                controls={kk: int(fw[kk][ii]) if kk == "f0_item_mask" else fw[kk][ii:ii + 1, :ll]
+                                          for kk in CONTROL_KEYS if kk in fw})[0]
             err = float(np.max(np.abs(audio[ii, :ll * hop].astype(np.float64) - ref)))
             bar = E2E_TOL * max(1.0, float(np.max(np.abs(ref))))
             print(f"\nmemory contract {cid}: item {ii} ({ll} frames) max|audio - oracle| {err:.3e} (bar {bar:.3e})")
@@ -809,7 +873,7 @@ def test_the_detector_reports_a_row_it_is_told_is_guard(torch):
 # host-side refusals: nothing is launched, nothing is written
 # ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("entry", ["mbx_forward", "mbx_forward_ex", "mbx_forward_stream", "mbx_calibrate"])
+@pytest.mark.parametrize("entry", ["mbx_forward", "mbx_forward_ex", "mbx_forward_stream", "mbx_calibrate", "mbxe_forward"])
 @pytest.mark.parametrize("fill", FILLS)
 def test_short_or_misaligned_workspace_is_refused_before_any_launch(torch, fill, entry):
     """workspace_bytes one less than mbx_workspace_size -> MBX_ERR_WORKSPACE; a workspace pointer at +128 bytes ->
@@ -827,6 +891,10 @@ def test_short_or_misaligned_workspace_is_refused_before_any_launch(torch, fill,
     mel_g, noise_g = gs.put("mel", mel), gs.put("noise", noise)
     state = gs.put("state_in", np.zeros((B, 6), dtype=np.int32))
     state_out = gs.new("state_out", B * 6 * 4)
+    # mbxe_forward with all three env arguments given: the factors, the centre table, the caller's scratch of the warped rows
+    env_factor = gs.put("env_factor", np.full((B, T), 1.25, dtype=np.float32))
+    env_mel = gs.new("env_mel", B * T * d.mel_channels * 4)
+    centres = eng._envelope_centres()
     opt = mbx_forward_options()
     opt.struct_size = ctypes.sizeof(mbx_forward_options)
     opt.transposition = 1.0
@@ -840,6 +908,9 @@ def test_short_or_misaligned_workspace_is_refused_before_any_launch(torch, fill,
         if entry == "mbx_forward_stream":
             return lib.mbx_forward_stream(eng._handle, mel_g.ptr, None, B, T, noise_g.ptr, audio.ptr, ptr, nbytes, state.ptr,
                                           state_out.ptr, eng._stream())
+        if entry == "mbxe_forward":
+            return lib.mbxe_forward(eng._handle, mel_g.ptr, None, B, T, noise_g.ptr, audio.ptr, ptr, nbytes, ctypes.byref(opt),
+                                    env_factor.ptr, centres.data_ptr(), env_mel.ptr, eng._stream())
         return lib.mbx_calibrate(eng._handle, mel_g.ptr, None, B, T, noise_g.ptr, ptr, nbytes, eng._stream())
 
     before = eng.conv_form_info()
@@ -849,18 +920,19 @@ def test_short_or_misaligned_workspace_is_refused_before_any_launch(torch, fill,
     assert "256-byte aligned" in lib.mbx_last_error().decode()
     torch.cuda.synchronize()
     gs.check()
-    assert ws.payload_untouched() and audio.payload_untouched() and state_out.payload_untouched()
+    assert ws.payload_untouched() and audio.payload_untouched() and state_out.payload_untouched() and env_mel.payload_untouched()
     assert eng.conv_form_info()["form"] == before["form"]
 
 
 # ------------------------------------------------------------------------------------------------------------------------
 # streaming: nothing is carried in the workspace between ticks
 # ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.gpu
-def test_streams_carry_nothing_in_the_workspace(torch):
+def _streams_carry_nothing(torch, controlled):
     """The 80 ms schedule (6 / 6 / 7 / 6 / 7 frames) on a handful of streams of the small streaming model, the engine's
     workspace refilled with NaN between the ticks (an ordinary memset between graph replays): bit-equal to the undisturbed
-    run.  The header names no state that lives in the workspace; what a stream carries lives in the caller's stores."""
+    run.  The header names no state that lives in the workspace; what a stream carries lives in the caller's stores.
+    controlled: stream 0 is pushed with a formant shift and a transposition, both changing from frame to frame, and the
+    engine's scratch of the warped rows (env_mel of mbxe_forward) is refilled with the workspace."""
     import test_gpu_streaming as tstream
     from mbexwn_vocoder_amd.engine import MBExWNEngine
     from mbexwn_vocoder_amd.streaming import StreamingSynthesizer
@@ -875,13 +947,19 @@ def test_streams_carry_nothing_in_the_workspace(torch):
             mel, noise = synthetic_inputs(100 + sid, 1, ll)
             pending[sid] = (mel[0], noise[0], 0)
             syn.open(sid)
+        rng = np.random.default_rng(99)
+        formant = cref.formant_rows(rng, 1, lengths[0])[0]
+        scale = rng.uniform(0.5, 2.0, size=lengths[0]).astype(np.float32)
         got = {sid: [] for sid in pending}
         for _ in range(400):
             for sid, (mel, noise, pos) in pending.items():
                 if pos < mel.shape[0]:
                     end = min(pos + 8, mel.shape[0])
-                    syn.push(sid, mel[pos:end], noise[pos * 20:end * 20], last=end == mel.shape[0])
+                    extra = {"formant": formant[pos:end], "transposition": scale[pos:end]} if controlled and sid == 0 else {}
+                    syn.push(sid, mel[pos:end], noise[pos * 20:end * 20], last=end == mel.shape[0], **extra)
                     pending[sid] = (mel, noise, end)
+            if poison and eng._env_mel is not None:
+                eng._env_mel.view(torch.uint8).fill_(0xFF)
             if poison and eng._workspace is not None:
                 eng._workspace.fill_(0xFF)
                 # the integer region of the last tick's layout (the layout of a steady tick and of every graph replay) gets a
@@ -896,6 +974,7 @@ def test_streams_carry_nothing_in_the_workspace(torch):
             if all(syn.finished(sid) for sid in pending):
                 break
         torch.cuda.synchronize()
+        assert (syn._formant, syn._control) == (controlled, controlled) and (eng._env_mel is not None) == controlled
         eng.close()
         return {sid: np.concatenate(vv) for sid, vv in got.items()}, syn.graph_ticks
 
@@ -907,3 +986,15 @@ def test_streams_carry_nothing_in_the_workspace(torch):
         assert plain[sid].shape == (ll * 300,) and np.all(np.isfinite(plain[sid]))
         where = _first_difference(poisoned[sid], plain[sid])
         assert where is None, f"stream {sid}: the audio depends on what the workspace held between ticks, first at sample {where[0]}"
+
+
+@pytest.mark.gpu
+def test_streams_carry_nothing_in_the_workspace(torch):
+    _streams_carry_nothing(torch, False)
+
+
+@pytest.mark.gpu
+def test_controlled_streams_carry_nothing_in_the_workspace(torch):
+    """The same run with one stream pushed with ``formant`` and ``transposition``: the ticks go through mbxe_forward with the
+    control rows of their whole windows, and neither the workspace nor the scratch of the warped rows carries anything."""
+    _streams_carry_nothing(torch, True)

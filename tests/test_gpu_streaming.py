@@ -414,3 +414,21 @@ def test_random_models_and_stream_sets_stay_bit_equal():
                          capture_output=True, text=True, timeout=600)
     assert res.returncode == 0 and "failures: 0" in res.stdout, res.stdout[-3000:] + res.stderr[-2000:]
     assert res.stdout.count(" OK ") == 40
+
+
+def test_random_models_and_controlled_stream_sets_stay_bit_equal():
+    """Twelve draws of tests/tools/stream_fuzz.py in its ``controls`` mode: on top of the above every stream draws no control, a
+    transposition contour, F0 frames, a formant shift or all three -- some with their first value other than 1 at a random
+    frame, which switches the stage layout of the ticks in mid-run --, and a quarter of the models are force_causal; the
+    offline synthesis gets the same rows.  The twelve draws hold a causal model and every kind of control."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, os.path.join(root, "tests", "tools", "stream_fuzz.py"), "12", "31000", "controls"],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and "failures: 0" in res.stdout, res.stdout[-3000:] + res.stderr[-2000:]
+    assert res.stdout.count(" OK ") == 12
+    assert "'force_causal': True" in res.stdout
+    for kind in ("'none'", "'transposition'", "'f0'", "'formant'", "'all'"):
+        assert kind in res.stdout, kind

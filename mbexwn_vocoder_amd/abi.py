@@ -1,5 +1,5 @@
 """ctypes binding of libmbexwn_hip.so: the structures and constants of include/mbexwn.h, and ONE table of every function the
-twelve headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
+thirteen headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
 
 Nothing else lives here: a tool that only resamples imports this module, not the engine's driver.  The table is declared in
 Python (the package loads without include/ beside it); tests/test_abi_headers.py holds it to the headers name by name and
@@ -161,6 +161,11 @@ TABLE = {
         ("mbxc_decode_f0", i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp])],
     # rings, n_slots, ring_samples, desc, n_streams, max_new_frames, hop, sample_rate, window, tau_min, tau_max, ...
     "mbexwn_live_pitch.h": [("mbxt_f0_frames", i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp])],
+    # mel_a, mel_b, n_frames_a, n_frames_b, batch, max_frames_a, max_frames_b, n_mels, band, cost, stream
+    "mbexwn_align.h": [
+        ("mbxg_local_cost", i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+        ("mbxg_align_workspace_size", size_t, [i32, i32, i32]),
+        ("mbxg_align_path", i32, [vp, vp, vp, i32, i32, i32, vp, size_t, vp, vp, vp, vp, vp])],
 }
 
 

@@ -235,8 +235,43 @@ def resampled_length(n, rate, target):
     return -(-int(n) * (int(target) // gg) // (int(rate) // gg))
 
 
+def _guide_mels_device(sounds, rates, preprocess_config, batch, dev):
+    """The regular log-mel of every sound as a device tensor (frames, mel_channels): the micro-batches of
+    :func:`generate_mels` (grouped by rate, resampled and analysed on the device), without the copy back."""
+    import torch
+    from . import resample
+    cfg = preprocess_config
+    target, hop = int(cfg["sample_rate"]), int(cfg["hop_size"])
+    win_len = int(cfg.get("win_size", cfg["fft_size"]))
+    out = [None] * len(sounds)
+    by_rate = {}
+    for ii, rr in enumerate(rates):
+        by_rate.setdefault(rr, []).append(ii)
+    for rr, members in by_rate.items():
+        members = sorted(members, key=lambda ii: -sounds[ii].size)
+        for start in range(0, len(members), max(1, int(batch))):
+            group = members[start:start + max(1, int(batch))]
+            lengths = [sounds[ii].size for ii in group]
+            host = np.zeros((len(group), max(lengths)), dtype=np.float32)
+            for bb, ii in enumerate(group):
+                host[bb, :lengths[bb]] = sounds[ii]
+            snd = torch.as_tensor(host).to(dev)
+            n_dev = torch.as_tensor(np.asarray(lengths, dtype=np.int32)).to(dev)
+            if rr != target:
+                _, up, down = resample.device_taps(rr, target, dev)
+                snd, n_dev = resample.resample_device(snd, n_dev, rr, target)
+                lengths = [-(-nn * up // down) for nn in lengths]
+            if snd.shape[1] < win_len // 2 + 1:
+                snd = torch.nn.functional.pad(snd, (0, win_len // 2 + 1 - snd.shape[1]))
+            mel_dev, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
+            for bb, ii in enumerate(group):
+                out[ii] = mel_dev[bb, :lengths[bb] // hop + 1]
+    return out
+
+
 def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None, time_maps=None, rows_per_frame=1,
-                  f0_out=None, f0_params=None, f0_decode=None):
+                  f0_out=None, f0_params=None, f0_decode=None, guides=None, guide_rates=None, align_band_s=1.0,
+                  align_out=None):
     """Sounds -> ``.mell`` dictionaries (reference bin/generate_mel.py:54-64 for a list of files): ``sounds`` is a list of 1-D
     float32 arrays, ``rates`` their sample rates.  A sound that is not at the model rate goes through the reference's resampler
     (resample.py); one already at it skips that step.  Needs the ``preprocess_config`` alone: no engine, no weights.
@@ -263,9 +298,19 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     ``f0_decode``: None, or a ``f0decode.decode_params`` dictionary.  Given one, every item's pair is
     the decoded one: Viterbi over the YIN candidates of all its frames instead of the pick of every frame on its own (on
     the device ``mbxc_f0_candidates`` and ``mbxc_decode_f0`` in place of ``mbxp_track_f0``, else
-    ``f0decode.track_f0_viterbi_host``: the same bits).  It needs ``f0_out``.  None makes exactly the launches of before."""
+    ``f0decode.track_f0_viterbi_host``: the same bits).  It needs ``f0_out``.  None makes exactly the launches of before.
+
+    ``guides``: None, or per sound None or a 1-D float32 array at ``guide_rates[i]``: the item takes the TIMING of its guide
+    (align.py).  Guide and source go through the resampler and the regular analysis; the band costs
+    and the DTW path of ``align_band_s`` seconds around the diagonal follow (on the device ``mbxg_local_cost`` and
+    ``mbxg_align_path`` on the micro-batch, one small copy bringing the nodes back; else ``align.align_host``: the same
+    bits given the same mels); ``align.centres_from_path`` makes the centres, which then are the item's time map
+    (``timemap.Centres``): its ``.mell`` has the guide's frame count.  A guided item takes no ``time_maps`` entry.  An item
+    without a guide keeps its regular bits; a call without guides makes the launches of before.  ``align_out``: a dict, or
+    None.  Given a dict, item i's ``align.path_stats`` go to ``align_out[i]``, and an item that cannot be aligned
+    (``align.AlignError``) leaves ``{"error": message}`` there and None in the result (and in ``f0_out``) instead of raising."""
     import time
-    from . import f0decode, f0track, resample, timemap
+    from . import align, f0decode, f0track, resample, timemap
     cfg = preprocess_config
     target, hop = int(cfg["sample_rate"]), int(cfg["hop_size"])
     win_len = int(cfg.get("win_size", cfg["fft_size"]))
@@ -290,12 +335,55 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     # every map is checked, and its centres are made, before anything runs
     warped = {ii: timemap.centres(resampled_length(sounds[ii].size, rates[ii], target), hop, target, mm, rows_per_frame)
               for ii, mm in enumerate(maps) if mm is not None}
+    guided, band, failed = {}, None, set()
+    if guides is not None and any(gg is not None for gg in guides):
+        if guide_rates is None or len(guides) != len(sounds) or len(guide_rates) != len(sounds):
+            raise ValueError("generate_mels: guides and guide_rates take one entry per sound")
+        band = align.band_frames(align_band_s, target, hop)
+        for ii, gg in enumerate(guides):
+            if gg is None:
+                continue
+            if maps[ii] is not None:
+                raise ValueError(f"generate_mels: sound {ii} has a guide and a time map; the guide IS its time map")
+            gg = np.ascontiguousarray(gg, dtype=np.float32)
+            if gg.ndim != 1 or gg.size == 0:
+                raise ValueError(f"generate_mels: guide {ii} must be a non-empty 1-D array, got shape {gg.shape}")
+            guided[ii] = (gg, int(round(guide_rates[ii])))
+            frames_a = resampled_length(gg.size, guided[ii][1], target) // hop + 1
+            align.check_sizes(frames_a, resampled_length(sounds[ii].size, rates[ii], target) // hop + 1, band)
+            timemap._check_frames(float(frames_a), rows_per_frame)
+
+    def aligned_centres(ii, nodes, cost, frames_a, frames_b, n_source):
+        """The centres of a guided item from its path, or None (and the note in ``align_out``) when there is none."""
+        if len(nodes) == 0:
+            err = align.cannot_align(frames_a, frames_b, band)
+            if align_out is None:
+                raise err
+            align_out[ii] = {"error": str(err)}
+            failed.add(ii)
+            return None
+        if align_out is not None:
+            align_out[ii] = align.path_stats(nodes, cost, frames_a, frames_b, hop, target)
+        return timemap.centres(n_source, hop, target, timemap.Centres(align.centres_from_path(nodes, hop, n_source)),
+                               rows_per_frame)
+
     if not on_device:
         for ii, (ss, rr) in enumerate(zip(sounds, rates)):
             t0 = time.perf_counter()
             if rr != target:
                 ss = resample.resample_host(ss, rr, target)
             t1 = time.perf_counter()
+            if ii in guided:
+                gg, gr = guided[ii]
+                if gr != target:
+                    gg = resample.resample_host(gg, gr, target)
+                mel_a = compute_log_mel(gg[np.newaxis], cfg, dtype=np.float32)[0][0]
+                mel_b = compute_log_mel(ss[np.newaxis], cfg, dtype=np.float32)[0][0]
+                nodes, cost = align.align_host(mel_a, mel_b, band)
+                cc = aligned_centres(ii, nodes, cost, mel_a.shape[0], mel_b.shape[0], ss.size)
+                if cc is None:
+                    continue
+                warped[ii] = cc
             if ii in warped:
                 mel, _ = compute_log_mel_at(ss[np.newaxis], warped[ii], cfg, dtype=np.float32)
             else:
@@ -318,6 +406,11 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     if not torch.cuda.is_available():
         raise RuntimeError("generate_mels(on_device=True): no GPU available (on_device=False is the host path)")
     dev = torch.device("cuda", torch.cuda.current_device())
+    guide_mel = {}
+    if guided:
+        order = sorted(guided)
+        guide_mel = dict(zip(order, _guide_mels_device([guided[ii][0] for ii in order], [guided[ii][1] for ii in order], cfg,
+                                                       batch, dev)))
     by_rate = {}
     for ii, rr in enumerate(rates):
         by_rate.setdefault(rr, []).append(ii)
@@ -344,6 +437,25 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
                 snd = torch.nn.functional.pad(snd, (0, win_len // 2 + 1 - snd.shape[1]))
             if marks:
                 marks[2].record()
+            rows = [bb for bb, ii in enumerate(group) if ii in guide_mel]
+            if rows:
+                # the regular analysis of the micro-batch, the two alignment kernels on its guided items, one copy back
+                regular, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
+                n_a = [int(guide_mel[group[bb]].shape[0]) for bb in rows]
+                n_b = [lengths[bb] // hop + 1 for bb in rows]
+                mel_a = torch.zeros((len(rows), max(n_a), regular.shape[2]), dtype=torch.float32, device=dev)
+                for kk, bb in enumerate(rows):
+                    mel_a[kk, :n_a[kk]] = guide_mel[group[bb]]
+                mel_b = regular[rows, :max(n_b)].contiguous()
+                found = align.align_device(mel_a, torch.as_tensor(np.asarray(n_a, dtype=np.int32)).to(dev), mel_b,
+                                           torch.as_tensor(np.asarray(n_b, dtype=np.int32)).to(dev), band)
+                packed = torch.cat([found[0], found[1], found[2][:, None], found[3][:, None]], dim=1).cpu().numpy()
+                for kk, bb in enumerate(rows):
+                    count = int(packed[kk, -2])
+                    nodes = np.stack((packed[kk, :count], packed[kk, max(n_a):max(n_a) + count]), axis=1)
+                    cc = aligned_centres(group[bb], nodes, int(packed[kk, -1]), n_a[kk], n_b[kk], lengths[bb])
+                    if cc is not None:
+                        warped[group[bb]] = cc
             if any(ii in warped for ii in group) or f0_out is not None:
                 cents = [warped[ii] if ii in warped else timemap.centres(nn, hop, target, None) for ii, nn in zip(group, lengths)]
                 table = np.zeros((len(group), max(cc.size for cc in cents)), dtype=np.int64)
@@ -382,6 +494,8 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
                     _add(stats, key, marks[first].elapsed_time(marks[first + 1]) * 1e-3)
             for bb, ii in enumerate(group):
                 out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[bb, :counts[bb]].T))
+    for ii in failed:
+        out[ii], tracked[ii] = None, None
     if f0_out is not None:
         f0_out.extend(tracked)
     return out

@@ -450,7 +450,8 @@ def read_sound(path):
 
 def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
                   quiet=False, flac_compression="verbatim", out_rate=None, stretches=None, formants=None, f0_source="net",
-                  f0_params=None, write_f0=False, timings=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0):
+                  f0_params=None, write_f0=False, timings=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0,
+                  guides=None, align_band_s=1.0):
     """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
     ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
 
@@ -478,6 +479,11 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     contour, used and written, is the Viterbi path over the YIN candidates of the file's frames (DESIGN.md section 6i);
     it needs "audio" or ``write_f0``.  ``f0_fill``: "interpolate", or "hold" -- the causal fill of the live streams
     (``f0track.fill_hold`` with ``f0_initial`` Hz in front of the first voiced frame); it needs "audio".
+    ``guides``: per file None or the path of a guide recording, None = none for all: file i comes out
+    with the TIMING of its guide -- the guide's frame count, hence its length -- through ``generate_mels(guides=)`` with a
+    band of ``align_band_s`` seconds; it takes no ``stretches`` entry other than 1.  A guide that cannot be read, and a file
+    that cannot be aligned to its guide, is reported and skipped like the unreadable ones; ``verbose`` prints the path's mean
+    cost per node and its largest offset from the diagonal.  No guide: the launches and the bytes of before.
     ``timings``: a dict that receives the seconds per stage the
     verbose line reports (upload, resample, analysis, f0, copy_back from ``generate_mels``; read, scale, device, copy, write
     from the pools and the micro-batches' events; wall)."""
@@ -510,10 +516,30 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
         clock.add("scale", time.perf_counter() - t0)
         return mel
 
+    guides = None if guides is None or all(gg is None for gg in guides) else list(guides)
+    if guides is not None and len(guides) != len(files):
+        raise ValueError(f"run_audio_job: guides takes one entry per file ({len(files)}), got {len(guides)}")
+
+    def read_guide(path):
+        try:
+            return read_sound(path)
+        except (OSError, ValueError) as err:
+            return ValueError(f"guide {path}: {err}")
+
     with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
         loaded = dict(zip(mine, pool.map(read, mine)))
         skipped = [(files[ii], str(loaded[ii])) for ii in mine if isinstance(loaded[ii], ValueError)]
         mine = [ii for ii in mine if not isinstance(loaded[ii], ValueError)]
+        guide_sounds = {}
+        if guides is not None:
+            paths = sorted({guides[ii] for ii in mine if guides[ii] is not None})
+            guide_sounds = dict(zip(paths, pool.map(read_guide, paths)))
+            for ii in [ii for ii in mine if guides[ii] is not None]:
+                if isinstance(guide_sounds[guides[ii]], ValueError):
+                    skipped.append((files[ii], str(guide_sounds[guides[ii]])))
+                    mine.remove(ii)
+                elif stretches is not None and float(stretches[ii]) != 1.0:
+                    raise ValueError(f"run_audio_job: {files[ii]} has a guide and a time stretch; the guide sets its timing")
         # a factor of exactly 1 is the regular analysis; every other one is checked against the engine's limit here
         maps = {ii: None if stretches is None or float(stretches[ii]) == 1.0 else float(stretches[ii]) for ii in mine}
         for ii in [ii for ii in mine if maps[ii] is not None]:
@@ -532,12 +558,37 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
         if f0_decode is not None and tracked is None:
             raise ValueError("run_audio_job: f0_decode decodes the tracked contour and needs f0_source='audio' or write_f0")
         stats = {}
-        dicts = generate_mels([loaded[ii][0] for ii in mine], [loaded[ii][1] for ii in mine], inv.preprocess_config,
-                              on_device=True, batch=max(1, batch), stats=stats,
-                              time_maps=None if all(maps[ii] is None for ii in mine) else [maps[ii] for ii in mine],
-                              rows_per_frame=inv.model.dims.steps_per_frame, f0_out=tracked,
-                              f0_params=None if tracked is None else f0track.params(int(round(inv.srate)), **(f0_params or {})),
-                              f0_decode=f0_decode) if mine else []
+        aligned = {}
+        have_guides = guides is not None and any(guides[ii] is not None for ii in mine)
+        try:
+            dicts = generate_mels([loaded[ii][0] for ii in mine], [loaded[ii][1] for ii in mine], inv.preprocess_config,
+                                  on_device=True, batch=max(1, batch), stats=stats,
+                                  time_maps=None if all(maps[ii] is None for ii in mine) else [maps[ii] for ii in mine],
+                                  rows_per_frame=inv.model.dims.steps_per_frame, f0_out=tracked,
+                                  f0_params=None if tracked is None else f0track.params(int(round(inv.srate)), **(f0_params or {})),
+                                  f0_decode=f0_decode,
+                                  **({"guides": [None if guides[ii] is None else guide_sounds[guides[ii]][0] for ii in mine],
+                                      "guide_rates": [None if guides[ii] is None else guide_sounds[guides[ii]][1] for ii in mine],
+                                      "align_band_s": align_band_s, "align_out": aligned} if have_guides else {})) if mine else []
+        except ValueError as err:
+            if not have_guides:
+                raise
+            raise ValueError(f"align: {err}") from None
+        if have_guides:                                       # the files without a path leave the job here
+            lines = []
+            for local, ii in enumerate(list(mine)):
+                note = aligned.get(local)
+                if note is not None and "error" in note:
+                    skipped.append((files[ii], f"{note['error']} (guide {guides[ii]})"))
+                    lines.append(f"transform_audio::error:: skipped {files[ii]}: {note['error']} (guide {guides[ii]})")
+                elif note is not None and verbose:
+                    lines.append(f"    aligned {files[ii]} to {guides[ii]}: {note['nodes']} nodes, mean cost per node "
+                                 f"{note['mean_cost']:.3f}, largest offset from the diagonal {note['max_offset_ms']:.1f} ms")
+            log(lines)
+            keep = [local for local in range(len(mine)) if dicts[local] is not None]
+            if tracked is not None:
+                tracked[:] = [tracked[local] for local in keep]
+            dicts, mine = [dicts[local] for local in keep], [mine[local] for local in keep]
         scaled = dict(zip(mine, pool.map(scale, dicts)))
         contours = None
         if tracked is not None:
@@ -580,6 +631,8 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
         audio_s = sum(int(scaled[ii].shape[1]) for ii in mine) * inv.hop_size / inv.srate
         in_s = sum(loaded[ii][0].size / loaded[ii][1] for ii in mine)
         stretched = "" if all(maps[ii] is None for ii in mine) else f" (time-stretched from {in_s:.1f} s of input)"
+        if guides is not None:
+            stretched = f" (aligned to guides, from {in_s:.1f} s of input)"
         print(f"transform_audio: {len(mine)} files, {audio_s:.1f} s of audio{stretched} in {wall:.2f} s wall ({audio_s / max(wall, 1e-9):.1f} "
               f"x real time); read {sec.get('read', 0.0):.2f} s, upload {stats.get('upload', 0.0):.3f} s, resample "
               f"{stats.get('resample', 0.0):.3f} s, analysis {stats.get('analysis', 0.0):.3f} s, "
@@ -590,19 +643,26 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     return skipped
 
 
-def plan_audio_ranks(files, ranks, threads=2, stretches=None, frame_limit=None):
+def plan_audio_ranks(files, ranks, threads=2, stretches=None, frame_limit=None, guides=None):
     """What the parent of a ``transform_audio.py --gpus N`` job decides before it starts its ranks, without importing torch:
     the visible GPUs, the files it skips -- (file, reason) pairs, ``read_sound`` -- and the LPT partition of the others by
     duration times ``stretches[i]`` (the seconds the file comes out with; None = 1 for all).  ``files`` in the plan are the
     ones the ranks share out.  ``frame_limit``: (hop, model rate, sub-band rows per frame) -- a file whose stretched length
-    exceeds the engine's limit (``timemap.frame_count``) is skipped here, as ``run_audio_job`` would skip it."""
+    exceeds the engine's limit (``timemap.frame_count``) is skipped here, as ``run_audio_job`` would skip it.  ``guides``: per
+    file None or the path of its guide (``run_audio_job``): an aligned file comes out with its guide's duration and is
+    weighed by it; a guide that cannot be read skips the file."""
     from . import timemap
     from .analysis import resampled_length
 
     def seconds_of(item):
-        path, factor = item
+        path, factor, guide = item
         try:
             snd, rate = read_sound(path)
+            if guide is not None:
+                try:
+                    snd, rate = read_sound(guide)
+                except (OSError, ValueError) as err:
+                    raise ValueError(f"guide {guide}: {err}") from None
             if frame_limit is not None and factor != 1.0:
                 hop, target, rows = frame_limit
                 timemap.frame_count(resampled_length(snd.size, rate, target), hop, target, factor, rows)
@@ -611,8 +671,9 @@ def plan_audio_ranks(files, ranks, threads=2, stretches=None, frame_limit=None):
             return err
 
     factors = [1.0] * len(files) if stretches is None else [float(ff) for ff in stretches]
+    guides = [None] * len(files) if guides is None else list(guides)
     with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
-        seconds = list(pool.map(seconds_of, zip(files, factors)))
+        seconds = list(pool.map(seconds_of, zip(files, factors, guides)))
     good = [ii for ii, ss in enumerate(seconds) if not isinstance(ss, ValueError)]
     cost = [int(np.ceil(seconds[ii] * factors[ii] * 1000)) for ii in good]
     return {"devices": visible_gpu_count(), "files": [files[ii] for ii in good], "shards": lpt_partition(cost, ranks),

@@ -16,6 +16,9 @@ Deviations (documented in INTEGRATION.md):
     frames of the mel and NAME.f0 is written next to NAME.mell, for ``resynth_mel.py --f0-dir``; with ``--host`` too, same bits
   * additionally ``--pitch-decode viterbi`` (``--pitch-jump``, ``--pitch-switch``): the written contour is decoded over the
     whole file (f0decode.py) instead of picked frame by frame; with ``--host`` too, same bits
+  * additionally ``--align-to GUIDE`` / ``--align-to-dir DIR`` (``--align-band SECONDS``): the frames lie where the guide's
+    timing puts them (align.py), the file has the guide's frame count, and resynth_mel.py synthesises
+    the sound with the guide's timing; with ``--host`` too; not combinable with ``--time-stretch``
   * without ``--host`` and without a GPU the script fails loudly; there is no ``--gpus``
 """
 import os
@@ -38,7 +41,8 @@ from mbexwn_vocoder_amd.timemap import check_factor  # noqa: E402
 
 
 def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2, host=False, verbose=False, quiet=False,
-         time_stretch=1.0, write_f0=False, f0_min=55.0, f0_max=1000.0, pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5):
+         time_stretch=1.0, write_f0=False, f0_min=55.0, f0_max=1000.0, pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5,
+         align_to=None, align_to_dir=None, align_band=1.0):
     config_file = get_config_file(model_id_or_path=model_id)
     config = read_config(config_file=config_file)
     preprocess_config = config['preprocess_config']
@@ -52,10 +56,14 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
         f0_decode = f0decode.decode_params(w_jump=pitch_jump, w_switch=pitch_switch) if pitch_decode == "viterbi" else None
         if f0_decode is not None and not write_f0:
             raise ValueError("--pitch-decode viterbi decodes the contour that --write-f0 writes: it needs --write-f0")
+        guide_of = file_guides(input_audio_files, align_to, align_to_dir, align_band, time_stretch)
+        if guide_of is not None:
+            rows_per_frame = ModelDims(config).steps_per_frame
+            guide_of = dict(zip(input_audio_files, guide_of))
     except ValueError as err:
         print(f"generate_mel::error:: {err}", file=sys.stderr)
         sys.exit(1)
-    missing = [ff for ff in input_audio_files if not os.path.isfile(ff)]
+    missing = [ff for ff in input_audio_files + sorted(set((guide_of or {}).values())) if not os.path.isfile(ff)]
     if missing:
         print(f"generate_mel::error:: no such file: {', '.join(missing)}", file=sys.stderr)
         sys.exit(1)
@@ -87,8 +95,16 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
         f0track.write_f0(path, times, f0, periodicity)
         return time.perf_counter() - t0
 
+    guide_cache = {}
+
+    def guide_sound(path):
+        if path not in guide_cache:
+            guide_cache[path] = read(path)[:2]
+        return guide_cache[path]
+
     t_start = time.perf_counter()
     samples = 0
+    unaligned = []
     windows = [input_audio_files[ii:ii + batch] for ii in range(0, len(input_audio_files), batch)]
     with ThreadPoolExecutor(max_workers=threads) as readers, ThreadPoolExecutor(max_workers=threads) as writers:
         pending = [readers.submit(read, ff) for ff in windows[0]] if windows else []
@@ -103,14 +119,28 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
                     print(f"process {ff}", file=sys.stderr)
             try:
                 tracked = [] if write_f0 else None
+                aligned = {}
+                guide_args = {}
+                if guide_of is not None:
+                    pairs = [guide_sound(guide_of[ff]) for ff in files]
+                    guide_args = {"guides": [pp[0] for pp in pairs], "guide_rates": [pp[1] for pp in pairs],
+                                  "align_band_s": align_band, "align_out": aligned}
                 mells = generate_mels([ll[0] for ll in loaded], [ll[1] for ll in loaded], preprocess_config, on_device=not host,
                                       batch=batch, stats=stats, rows_per_frame=rows_per_frame,
                                       time_maps=None if time_stretch == 1.0 else [time_stretch] * len(loaded),
-                                      f0_out=tracked, f0_params=f0_params, f0_decode=f0_decode)
+                                      f0_out=tracked, f0_params=f0_params, f0_decode=f0_decode, **guide_args)
             except ValueError as err:
                 print(f"generate_mel::error:: {err}", file=sys.stderr)
                 sys.exit(1)
-            for ff, ll, dd in zip(files, loaded, mells):
+            for local, (ff, ll, dd) in enumerate(zip(files, loaded, mells)):
+                note = aligned.get(local)
+                if dd is None:                              # cannot be aligned: reported, skipped, exit status 1
+                    print(f"generate_mel::error:: skipped {ff}: {note['error']} (guide {guide_of[ff]})", file=sys.stderr)
+                    unaligned.append(ff)
+                    continue
+                if note is not None and verbose:
+                    print(f"    aligned to {guide_of[ff]}: {note['nodes']} nodes, mean cost per node {note['mean_cost']:.3f}, "
+                          f"largest offset from the diagonal {note['max_offset_ms']:.1f} ms", file=sys.stderr)
                 outfile = os.path.join(output_dir, os.path.splitext(os.path.basename(ff))[0] + ".mell")
                 samples += ll[0].size / ll[1]
                 if verbose:
@@ -118,6 +148,8 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
                           file=sys.stderr)
                 written.append(writers.submit(write, outfile, dd))
             for ff, contour in zip(files, tracked or []):
+                if contour is None:
+                    continue
                 times = f0track.frame_times(contour[0].size, preprocess_config["hop_size"], preprocess_config["sample_rate"])
                 written.append(writers.submit(write_contour, f0_path(ff, output_dir), times, *contour))
         seconds["write"] = sum(fu.result() for fu in written)
@@ -130,11 +162,40 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
               + f"{where} resample {stats.get('resample', 0.0):.3f} s, {where} analysis {stats.get('analysis', 0.0):.3f} s, "
               + (f"copy-back {stats.get('copy_back', 0.0):.3f} s, " if not host else "")
               + f"write {seconds['write']:.2f} s (read and write summed over {threads} threads each)", file=sys.stderr)
+    if unaligned:
+        sys.exit(1)
 
 
-if __name__ == "__main__":
+def file_guides(files, align_to=None, align_to_dir=None, align_band=1.0, time_stretch=1.0):
+    """The guide of every file: ``align_to`` for all, or ``align_to_dir/<basename>``; None without either flag.  ValueError
+    for both flags, for a guide beside a time stretch, for a band that is not finite and positive."""
+    if align_to is None and align_to_dir is None:
+        return None
+    if align_to is not None and align_to_dir is not None:
+        raise ValueError("--align-to and --align-to-dir exclude each other")
+    if time_stretch != 1.0:
+        raise ValueError("--align-to / --align-to-dir set the timing of a file: not combinable with --time-stretch")
+    band = float(align_band)
+    if not (band > 0 and band != float("inf")):
+        raise ValueError(f"--align-band: a finite positive number of seconds is expected, got {align_band!r}")
+    return [align_to if align_to is not None else os.path.join(align_to_dir, os.path.basename(ff)) for ff in files]
+
+
+def make_parser():
     from argparse import ArgumentParser
-    parser = ArgumentParser(description="create mel analysis from sound files using the analysis configuration of a model")
+
+    class Parser(ArgumentParser):
+        """The align flags exclude the time stretch: refused at parse time, with exit status 2."""
+
+        def parse_args(self, args=None, namespace=None):
+            parsed = super().parse_args(args, namespace)
+            try:
+                file_guides([], parsed.align_to, parsed.align_to_dir, parsed.align_band, parsed.time_stretch)
+            except ValueError as err:
+                self.error(str(err))
+            return parsed
+
+    parser = Parser(description="create mel analysis from sound files using the analysis configuration of a model")
     parser.add_argument("input_audio_files", nargs="+", help="input files to process")
     parser.add_argument("-o", "--output_dir", required=True, help="output directory where the .mell files will be stored")
     parser.add_argument("--model_id", default="VOICE", nargs="?", const="",
@@ -147,6 +208,13 @@ if __name__ == "__main__":
     parser.add_argument("-nt", "--num_threads", default=2, type=int, help="reader and writer threads (Def: %(default)s)")
     parser.add_argument("--time-stretch", dest="time_stretch", default=1.0, type=float, metavar="F",
                         help="place the frames for a sound F times as long at the same pitch (Def: %(default)s)")
+    parser.add_argument("--align-to", dest="align_to", default=None, metavar="GUIDE",
+                        help="place the frames where the timing of the recording GUIDE puts them: the .mell has the guide's "
+                             "frame count; excludes --time-stretch")
+    parser.add_argument("--align-to-dir", dest="align_to_dir", default=None, metavar="DIR",
+                        help="as --align-to, every file taking the guide DIR/<its basename>")
+    parser.add_argument("--align-band", dest="align_band", default=1.0, type=float, metavar="SECONDS",
+                        help="how far the alignment may leave the diagonal (Def: %(default)s)")
     parser.add_argument("--write-f0", dest="write_f0", action="store_true",
                         help="also track the pitch of every file from its samples and write NAME.f0 next to NAME.mell: text "
                              "rows `time_s f0_hz periodicity`, one per mel frame, 0 = unvoiced; resynth_mel.py --f0-dir reads it")
@@ -164,7 +232,11 @@ if __name__ == "__main__":
     parser.add_argument("--host", action="store_true", help="numpy analysis and host resampler; needs no GPU")
     parser.add_argument("-v", "--verbose", action="store_true", help="display verbose progress info")
     parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")
-    args = parser.parse_args()
+    return parser
+
+
+if __name__ == "__main__":
+    args = make_parser().parse_args()
 
     if not args.model_id:
         print("Please select one of the following models.\nYou don't need to select with a full ID. "

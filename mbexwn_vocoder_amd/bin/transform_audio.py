@@ -3,6 +3,7 @@
 
     transform_audio.py FILES... -o DIR --model_id VOICE [--transposition F | --transposition-file LIST] [--noise-seed S]
                        [--time-stretch F | --time-stretch-file LIST] [--formant-shift F | --formant-shift-file LIST]
+                       [--align-to GUIDE | --align-to-dir DIR] [--align-band SECONDS]
                        [--batch N] [--gpus N] [--out-rate R|input]
                        [--format flac] [--flac-compression fixed]
 
@@ -23,6 +24,13 @@ is reported and skipped; the others are written and the exit status is 1.
 analysis places its frames at the warped positions of the sound (include/mbexwn_warp.h) and the file gives K * hop samples
 for the K frames of the time map.  A factor of 1 is the regular analysis.  A file whose stretched length exceeds the engine's
 limit is reported and skipped like the others.
+
+--align-to GUIDE gives every file the TIMING of the recording GUIDE, --align-to-dir DIR that of DIR/<the file's basename>
+(mbexwn_vocoder_amd/align.py; include/mbexwn_align.h): the mel frames of guide and file are aligned by
+dynamic time warping within --align-band seconds of the diagonal, with local slope between 1/2 and 2, the analysis places one
+frame per guide frame where the path says, and the file comes out with the guide's sample count: dubbing to a guide track,
+stacking doubles.  Both recordings must hold the same material from start to end.  A file that cannot be aligned (a length
+ratio outside about 1/2 .. 2, a band too narrow) is reported and skipped like the others.  Not combinable with --time-stretch.
 
 --formant-shift F moves the formants of a file by the factor F (F > 1: up) at the same pitch and duration (DESIGN.md section
 6g; include/mbexwn_envelope.h): the VTF-net and the WaveNet conditioning read every mel row at f / F, the F0-net reads it as
@@ -58,8 +66,10 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
          gpus=1, num_threads=2, out_rate=None, format="flac", flac_compression="verbatim", conv_form="auto",
          batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None,
          formant_shift=1.0, formant_shift_file=None, f0_source="net", f0_min=55.0, f0_max=1000.0, write_f0=False,
-         pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5, f0_fill="interpolate", f0_initial=150.0):
+         pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5, f0_fill="interpolate", f0_initial=150.0, align_to=None,
+         align_to_dir=None, align_band=1.0):
     try:
+        guides = file_guides(input_audio_files, align_to, align_to_dir, align_band, time_stretch, time_stretch_file)
         if f0_source not in ("net", "audio"):
             raise ValueError(f"--f0-source must be net or audio, got {f0_source!r}")
         if not 0.0 < f0_min < f0_max:
@@ -96,7 +106,7 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
         from mbexwn_vocoder_amd.config import ModelDims, read_config
         dims = ModelDims(read_config(config_file=get_config_file(model_id_or_path=model_id)))
         plan = plan_audio_ranks(input_audio_files, gpus, threads=num_threads, stretches=stretches,
-                                frame_limit=(dims.hop_size, dims.sample_rate, dims.steps_per_frame))
+                                frame_limit=(dims.hop_size, dims.sample_rate, dims.steps_per_frame), guides=guides)
         for name, why in plan["skipped"]:
             print(f"transform_audio::error:: skipped {name}: {why}", file=sys.stderr)
         argv = [*plan["files"], "-o", output_dir, "--model_id", model_id, "--transposition", repr(float(transposition)),
@@ -108,6 +118,9 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
         argv += ["--formant-shift", repr(float(formant_shift))] if formant_shift != 1.0 else []
         argv += ["--formant-shift-file", formant_shift_file] if formant_shift_file else []
         argv += ["--out-rate", str(out_rate)] if out_rate else []
+        argv += ["--align-to", align_to] if align_to else []
+        argv += ["--align-to-dir", align_to_dir] if align_to_dir else []
+        argv += ["--align-band", repr(float(align_band))] if guides is not None else []
         argv += ["--f0-source", f0_source] if f0_source != "net" else []
         argv += ["--f0-min", repr(float(f0_min)), "--f0-max", repr(float(f0_max))] if f0_source != "net" or write_f0 else []
         argv += ["--write-f0"] if write_f0 else []
@@ -135,15 +148,47 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
     inv = MELInverter(model_id_or_path=model_id, verbose=verbose, batch_invariant=True if batch_invariant else None,
                       conv_form=None if conv_form == "auto" else conv_form)
     os.makedirs(output_dir, exist_ok=True)
-    skipped = run_audio_job(inv, input_audio_files, output_dir, format, factors=factors, noise_seed=noise_seed,
-                            mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose,
-                            quiet=quiet, flac_compression=flac_compression, out_rate=out_rate,
-                            stretches=None if all(ss == 1.0 for ss in stretches) else stretches,
-                            formants=None if all(ff == 1.0 for ff in formants) else formants, f0_source=f0_source,
-                            f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0, f0_decode=f0_decode,
-                            f0_fill=f0_fill, f0_initial=f0_initial)
+    try:
+        skipped = run_audio_job(inv, input_audio_files, output_dir, format, factors=factors, noise_seed=noise_seed,
+                                mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose,
+                                quiet=quiet, flac_compression=flac_compression, out_rate=out_rate,
+                                stretches=None if all(ss == 1.0 for ss in stretches) else stretches,
+                                formants=None if all(ff == 1.0 for ff in formants) else formants, f0_source=f0_source,
+                                f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0, f0_decode=f0_decode,
+                                f0_fill=f0_fill, f0_initial=f0_initial, guides=guides, align_band_s=align_band)
+    except ValueError as err:
+        if guides is None:
+            raise
+        print(f"transform_audio::error:: {err}", file=sys.stderr)       # a band or a length the alignment refuses
+        sys.exit(1)
     if skipped:
         sys.exit(1)
+
+
+def file_guides(files, align_to=None, align_to_dir=None, align_band=1.0, time_stretch=1.0, time_stretch_file=None):
+    """The guide of every file: ``align_to`` for all, or ``align_to_dir/<basename>``; None without either flag.  ValueError
+    for both flags, for a guide beside a time stretch, for a band that is not finite and positive."""
+    if align_to is None and align_to_dir is None:
+        return None
+    if align_to is not None and align_to_dir is not None:
+        raise ValueError("--align-to and --align-to-dir exclude each other")
+    if time_stretch != 1.0 or time_stretch_file:
+        raise ValueError("--align-to / --align-to-dir set the timing of a file: not combinable with --time-stretch or "
+                         "--time-stretch-file")
+    band_arg(str(align_band))
+    return [align_to if align_to is not None else os.path.join(align_to_dir, os.path.basename(ff)) for ff in files]
+
+
+def band_arg(text):
+    """argparse type of --align-band: a finite positive number of seconds."""
+    from argparse import ArgumentTypeError
+    try:
+        value = float(text)
+    except ValueError:
+        value = float("nan")
+    if not (value > 0 and value != float("inf")):
+        raise ArgumentTypeError(f"a finite positive number of seconds is expected, got {text!r}")
+    return value
 
 
 def pitch_decode_params(pitch_decode, pitch_jump, pitch_switch):
@@ -212,8 +257,21 @@ def out_rate_arg(text):
 
 
 def make_parser():
-    from argparse import SUPPRESS, ArgumentParser
-    parser = ArgumentParser(description="transpose sound files with an MBExWN model: analysis, pitch control and synthesis in "
+    from argparse import SUPPRESS, ArgumentParser, ArgumentTypeError
+
+    class Parser(ArgumentParser):
+        """The align flags exclude the time stretch: refused at parse time, with exit status 2."""
+
+        def parse_args(self, args=None, namespace=None):
+            parsed = super().parse_args(args, namespace)
+            try:
+                file_guides([], parsed.align_to, parsed.align_to_dir, parsed.align_band, parsed.time_stretch,
+                            parsed.time_stretch_file)
+            except (ValueError, ArgumentTypeError) as err:
+                self.error(str(err))
+            return parsed
+
+    parser = Parser(description="transpose sound files with an MBExWN model: analysis, pitch control and synthesis in "
                                         "batches (MI355X HIP path)")
     parser.add_argument("input_audio_files", nargs="+", help="mono sound files, at any sample rate")
     parser.add_argument("-o", "--output_dir", required=True, help="output directory where the transposed sounds will be stored")
@@ -229,6 +287,13 @@ def make_parser():
     parser.add_argument("--time-stretch-file", dest="time_stretch_file", default=None, metavar="LIST",
                         help="text file with lines `basename factor`: the time-stretch factor of the files it lists, instead "
                              "of --time-stretch")
+    parser.add_argument("--align-to", dest="align_to", default=None, metavar="GUIDE",
+                        help="give every file the timing of the recording GUIDE: its mel frames are aligned to the guide's by "
+                             "dynamic time warping and it comes out with the guide's length; excludes --time-stretch")
+    parser.add_argument("--align-to-dir", dest="align_to_dir", default=None, metavar="DIR",
+                        help="as --align-to, every file taking the guide DIR/<its basename>")
+    parser.add_argument("--align-band", dest="align_band", default=1.0, type=band_arg, metavar="SECONDS",
+                        help="how far the alignment may leave the diagonal (Def: %(default)s)")
     parser.add_argument("--formant-shift", dest="formant_shift", default=1.0, type=factor_arg, metavar="F",
                         help="factor on the formant frequencies at the same pitch and duration: F > 1 moves them up "
                              "(Def: %(default)s)")

@@ -483,6 +483,33 @@ struct DecodeArgs {
 const char *check_decode_f0(const DecodeArgs &a);
 void launch_decode_f0(const DecodeArgs &a, hipStream_t stream);
 
+// Timing alignment (mel_align.hip; include/mbexwn_align.h: mbxg_local_cost, mbxg_align_path): the quantised band costs of a
+// guide's and a source's log-mel, then a DTW path per item; the host definition is align.py (local_cost_host, path_host)
+constexpr int ALIGN_MAX_FRAMES = 65535;          // nodes * 16384 < 2^31
+constexpr int ALIGN_MAX_BAND = 511;              // one thread per band cell: 2 band + 1 <= 1024
+constexpr int ALIGN_MAX_MELS = 240;              // 64 source rows of n_mels | 1 floats and the guide row in 64 KiB of LDS
+struct AlignCostArgs {
+    const float *mel_a, *mel_b;  // (batch, max_frames_a, n_mels), (batch, max_frames_b, n_mels)
+    const int32_t *n_frames_a, *n_frames_b;      // (batch) each, clamped in the kernel to [0, max_frames_*]
+    int batch, max_frames_a, max_frames_b, n_mels, band;
+    uint16_t *cost;              // (batch, max_frames_a, 2 band + 1); rows behind n_frames_a[b] are not written
+};
+const char *check_align_cost(const AlignCostArgs &a);
+void launch_align_cost(const AlignCostArgs &a, hipStream_t stream);
+
+struct AlignPathArgs {
+    const uint16_t *cost;        // (batch, max_frames_a, 2 band + 1)
+    const int32_t *n_frames_a, *n_frames_b;      // (batch) each
+    int batch, max_frames_a, band;
+    uint8_t *workspace;          // align_workspace_bytes: back pointers, then the nodes in walking order
+    size_t workspace_bytes;
+    int32_t *nodes_i, *nodes_j;  // (batch, max_frames_a) each; entries behind count[b] are not written
+    int32_t *count, *total;      // (batch) each
+};
+size_t align_workspace_bytes(long long batch, long long max_frames_a, long long band);
+const char *check_align_path(const AlignPathArgs &a);
+void launch_align_path(const AlignPathArgs &a, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------
 // optional RMS normalisation of the mel input / de-normalisation of the audio (norm_mel.hip)
 // ---------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // C ABI of the stages that take no engine handle: mbx_mel_analysis and mbx_encode_flac16 of include/mbexwn.h and the entry
-// points of the eleven headers beside it (mbxa_ resampler, mbxl_ / mbxr_ / mbxo_ live rings, mbxf_ FLAC, mbxn_ noise, mbxw_ mel
-// warp, mbxe_warp_envelope, mbxp_ tracker, mbxc_ decoder, mbxt_ streaming tracker; mbxe_forward takes a handle and is in
+// points of the twelve headers beside it (mbxa_ resampler, mbxl_ / mbxr_ / mbxo_ live rings, mbxf_ FLAC, mbxn_ noise, mbxw_ mel
+// warp, mbxe_warp_envelope, mbxp_ tracker, mbxc_ decoder, mbxt_ streaming tracker, mbxg_ alignment; mbxe_forward takes a handle and is in
 // mbx_api.hip).  Each one copies
 // its arguments into the kernel's struct, lets check_* (beside the kernel) refuse them, enqueues on the caller's stream and
 // reports the launch error.  A new entry point: prototype in its header, a row in abi.py's TABLE, the body here.
@@ -16,7 +16,10 @@
 #include "../../include/mbexwn_contour.h"
 #include "../../include/mbexwn_envelope.h"
 #include "../../include/mbexwn_live_pitch.h"
+#include "../../include/mbexwn_align.h"
 
+static_assert(MBXG_MAX_FRAMES == mbx::ALIGN_MAX_FRAMES && MBXG_MAX_BAND == mbx::ALIGN_MAX_BAND && MBXG_MAX_MELS == mbx::ALIGN_MAX_MELS,
+              "mbexwn_align.h states the limits of mel_align.hip");
 static_assert(MBXN_FILL_TILE == mbx::NOISE_TILE, "mbexwn_noise.h states the tile of noise_keyed.hip");
 static_assert(MBXA_RESAMPLE_TILE == mbx::RS_TILE, "mbexwn_audio.h states the tile of resample_poly.hip");
 
@@ -347,6 +350,55 @@ mbx_status mbxt_f0_frames(const float *rings, int32_t n_slots, int32_t ring_samp
     a.periodicity = periodicity;
     if (const char *why = mbx::check_f0_stream(a)) return refuse("f0 frames", why);
     mbx::launch_f0_stream(a, static_cast<hipStream_t>(hip_stream));
+    return launch_status("kernel launch: ");
+}
+
+mbx_status mbxg_local_cost(const float *mel_a, const float *mel_b, const int32_t *n_frames_a, const int32_t *n_frames_b,
+                           int32_t batch, int32_t max_frames_a, int32_t max_frames_b, int32_t n_mels, int32_t band,
+                           uint16_t *cost, void *hip_stream) {
+    mbx::AlignCostArgs a{};
+    a.mel_a = mel_a;
+    a.mel_b = mel_b;
+    a.n_frames_a = n_frames_a;
+    a.n_frames_b = n_frames_b;
+    a.batch = batch;
+    a.max_frames_a = max_frames_a;
+    a.max_frames_b = max_frames_b;
+    a.n_mels = n_mels;
+    a.band = band;
+    a.cost = cost;
+    if (const char *why = mbx::check_align_cost(a)) return refuse("local cost", why);
+    if (batch == 0) return MBX_OK;
+    mbx::launch_align_cost(a, static_cast<hipStream_t>(hip_stream));
+    return launch_status("kernel launch: ");
+}
+
+size_t mbxg_align_workspace_size(int32_t batch, int32_t max_frames_a, int32_t band) {
+    if (batch < 0 || batch > 65535 || max_frames_a < 1 || max_frames_a > mbx::ALIGN_MAX_FRAMES || band < 1 ||
+        band > mbx::ALIGN_MAX_BAND)
+        return 0;
+    return mbx::align_workspace_bytes(batch, max_frames_a, band);
+}
+
+mbx_status mbxg_align_path(const uint16_t *cost, const int32_t *n_frames_a, const int32_t *n_frames_b, int32_t batch,
+                           int32_t max_frames_a, int32_t band, uint8_t *workspace, size_t workspace_bytes, int32_t *nodes_i,
+                           int32_t *nodes_j, int32_t *count, int32_t *total, void *hip_stream) {
+    mbx::AlignPathArgs a{};
+    a.cost = cost;
+    a.n_frames_a = n_frames_a;
+    a.n_frames_b = n_frames_b;
+    a.batch = batch;
+    a.max_frames_a = max_frames_a;
+    a.band = band;
+    a.workspace = workspace;
+    a.workspace_bytes = workspace_bytes;
+    a.nodes_i = nodes_i;
+    a.nodes_j = nodes_j;
+    a.count = count;
+    a.total = total;
+    if (const char *why = mbx::check_align_path(a)) return refuse("align path", why);
+    if (batch == 0) return MBX_OK;
+    mbx::launch_align_path(a, static_cast<hipStream_t>(hip_stream));
     return launch_status("kernel launch: ");
 }
 

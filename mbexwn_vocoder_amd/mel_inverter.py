@@ -318,7 +318,8 @@ class MELInverter(object):
 
     def transform_audio(self, sounds, rates, names, transposition=1.0, noise_seed=0, out_rate=None, max_batch=16,
                         max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None, formant=None,
-                        f0_source="net", f0_params=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0):
+                        f0_source="net", f0_params=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0,
+                        align_to=None, align_band_s=1.0):
         """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
         keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
         factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
@@ -348,6 +349,13 @@ class MELInverter(object):
         the first voiced one take ``f0_initial`` Hz, and every item takes its contour.  It needs ``"audio"`` and exists so that
         an offline run has the bits of ``LiveResynthesizer.open(f0_source="audio")``.
 
+        ``align_to``: None, or a list with, per item, None or a ``(guide, rate)`` pair -- a 1-D float32 recording whose TIMING
+        the item takes (align.py; the ``guides`` of ``analysis.generate_mels`` and of
+        ``batched.run_audio_job``): the mel frames of guide and item are aligned by dynamic time warping within
+        ``align_band_s`` seconds of the diagonal, and the item comes out with the guide's frame count.  Such an item takes no
+        ``time_stretch``; one that cannot be aligned raises ``align.AlignError``.  Everything else works on its frames as on
+        any others.
+
         An item's audio is a function of (sound, rate, name, factor, stretch, formant, seed, out_rate): with a ``batch_invariant``
         engine or one pinned to a convolution form it does not depend on the batch, the order or the other items."""
         from . import f0track, timemap
@@ -367,10 +375,16 @@ class MELInverter(object):
             f0_params = f0track.params(int(round(self.srate)), **(f0_params or {}))
         maps = timemap.per_item(time_stretch, len(sounds), "transform_audio: time_stretch")
         tracked = [] if f0_source == "audio" else None
+        guide_args = {}
+        if align_to is not None and any(gg is not None for gg in align_to):
+            if len(align_to) != len(sounds):
+                raise ValueError("transform_audio: align_to takes one entry per sound")
+            guide_args = {"guides": [None if gg is None else gg[0] for gg in align_to],
+                          "guide_rates": [None if gg is None else gg[1] for gg in align_to], "align_band_s": align_band_s}
         dicts = generate_mels(sounds, rates, self.preprocess_config, on_device=True, batch=max_batch,
                               time_maps=None if all(mm is None for mm in maps) else maps,
                               rows_per_frame=self.model.dims.steps_per_frame, f0_out=tracked,
-                              f0_params=f0_params if tracked is not None else None, f0_decode=f0_decode)
+                              f0_params=f0_params if tracked is not None else None, f0_decode=f0_decode, **guide_args)
         scaled = [self.scale_mel(dd) for dd in dicts]
         contours = None if tracked is None else [f0track.fill_tracked(ff, f0_fill, f0_initial) for ff, _ in tracked]
         rows = [np.full(int(mm.shape[1]), ff, dtype=np.float32) for mm, ff in zip(scaled, factors)]

@@ -15,6 +15,10 @@ Breakpoints, ``(m, 2)`` float64 rows ``(t_out, t_in)`` in seconds: ``t_out`` str
 non-decreasing within ``[0, n / R]`` (equal neighbours hold a frame):
     K = int(floor(t_out[-1] * R / H)) + 1
     c[k] = clip(int(rint(np.interp(k * H / R, t_out, t_in) * R)), 0, n)
+
+Explicit centres, :class:`Centres` around an int64 array: K = its size, c = the array, which must be non-decreasing and lie
+within ``[0, n]``.  This is how a map that was computed in frames (align.py) reaches the analysis
+without a trip through float seconds, where ``floor(t_out[-1] * R / H) + 1`` could lose the last frame to rounding.
 """
 import numpy as np
 
@@ -33,9 +37,22 @@ def check_factor(factor, what="time stretch"):
     return value
 
 
+class Centres:
+    """A time map given as the centre samples themselves: a 1-D array of at least one integer (kept as int64).  Whether they
+    fit a sound -- non-decreasing, within [0, n], no more frames than the engine takes -- is checked where the sound's
+    length is known (:func:`centres`, :func:`frame_count`).  A bare 1-D list is NOT this kind of spec: wrap it."""
+
+    def __init__(self, values):
+        arr = np.asarray(values)
+        if arr.ndim != 1 or arr.size < 1 or arr.dtype.kind not in "iu":
+            raise ValueError(f"time stretch: explicit centres are a 1-D integer array with at least one entry, got "
+                             f"shape {arr.shape} of {arr.dtype}")
+        self.values = arr.astype(np.int64)
+
+
 def is_factor(spec):
-    """True for a spec that is one number (a constant factor), False for None or a breakpoint array."""
-    return spec is not None and np.ndim(spec) == 0
+    """True for a spec that is one number (a constant factor), False for None, a breakpoint array or :class:`Centres`."""
+    return spec is not None and not isinstance(spec, Centres) and np.ndim(spec) == 0
 
 
 def _check_frames(frames, rows_per_frame):
@@ -46,10 +63,18 @@ def _check_frames(frames, rows_per_frame):
 
 
 def _plan(n, hop, rate, spec, rows_per_frame):
-    """(K, factor or None, breakpoints or None) of a checked spec."""
+    """(K, factor or None, breakpoints or None) of a checked spec; for :class:`Centres` (K, None, the checked int64 array)."""
     n, hop = int(n), int(hop)
     if n < 0 or hop < 1 or not (np.isfinite(rate) and rate > 0):
         raise ValueError(f"time stretch: need n >= 0, hop >= 1 and a positive rate, got n={n}, hop={hop}, rate={rate}")
+    if isinstance(spec, Centres):
+        cc = spec.values
+        if np.any(np.diff(cc) < 0):
+            raise ValueError("time stretch: explicit centres must be non-decreasing")
+        if cc[0] < 0 or cc[-1] > n:
+            raise ValueError(f"time stretch: explicit centres must lie within [0, {n}], got {int(cc[0])} .. {int(cc[-1])}")
+        _check_frames(float(cc.size), rows_per_frame)
+        return int(cc.size), None, cc
     if spec is None or is_factor(spec):
         factor = np.float64(1.0 if spec is None else check_factor(spec))
         frames = np.floor(np.float64(n) * factor / hop) + 1
@@ -78,11 +103,13 @@ def frame_count(n, hop, rate, spec, rows_per_frame=1):
 def centres(n, hop, rate, spec, rows_per_frame=1):
     """The int64 centre samples ``c[0..K)`` of the output frames of a sound of ``n`` samples at ``rate`` with hop ``hop``.
 
-    ``spec``: None (the regular frames, factor 1), a factor, or a breakpoint array (the module's text gives both
-    definitions).  ``rows_per_frame``: the sub-band rows the engine makes of one frame (``ModelDims.steps_per_frame``); K
+    ``spec``: None (the regular frames, factor 1), a factor, a breakpoint array or :class:`Centres` (the module's text gives
+    the definitions).  ``rows_per_frame``: the sub-band rows the engine makes of one frame (``ModelDims.steps_per_frame``); K
     may not exceed ``(2^24 - 1) // rows_per_frame`` frames.  ValueError for a factor that is not finite or not positive, a
     malformed or non-monotone map, and a K above that limit (the message names the limit in frames)."""
     frames, factor, bp = _plan(n, hop, rate, spec, rows_per_frame)
+    if isinstance(spec, Centres):
+        return bp.copy()
     kk = np.arange(frames, dtype=np.int64)
     if bp is None:
         pos = np.rint((kk * int(hop)).astype(np.float64) / factor)

@@ -235,15 +235,120 @@ def resampled_length(n, rate, target):
     return -(-int(n) * (int(target) // gg) // (int(rate) // gg))
 
 
-def _guide_mels_device(sounds, rates, preprocess_config, batch, dev):
-    """The regular log-mel of every sound as a device tensor (frames, mel_channels): the micro-batches of
-    :func:`generate_mels` (grouped by rate, resampled and analysed on the device), without the copy back."""
+def _plan_mels(sounds, rates, preprocess_config, time_maps, rows_per_frame, f0_out, f0_params, f0_decode, guides, guide_rates,
+               align_band_s, align_out):
+    """What :func:`generate_mels` decides before anything runs, and every refusal of the call: a namespace of the checked
+    ``sounds`` and ``rates``, the F0 settings (``track``, ``f0_params`` resolved, ``f0_decode`` checked), ``warped`` {item:
+    centres of its time map}, ``guided`` {item: (guide, rate)} with their ``band``, and ``align_out`` / ``failed``."""
+    from types import SimpleNamespace
+    from . import align, f0decode, f0track, timemap
+    cfg = preprocess_config
+    target, hop = int(cfg["sample_rate"]), int(cfg["hop_size"])
+    sounds = [np.ascontiguousarray(ss, dtype=np.float32) for ss in sounds]
+    rates = [int(round(rr)) for rr in rates]
+    if len(sounds) != len(rates):
+        raise ValueError("generate_mels: one rate per sound")
+    for ii, ss in enumerate(sounds):
+        if ss.ndim != 1 or ss.size == 0:
+            raise ValueError(f"generate_mels: sound {ii} must be a non-empty 1-D array, got shape {ss.shape}")
+    if f0_decode is not None:
+        if f0_out is None:
+            raise ValueError("generate_mels: f0_decode needs f0_out, the list the contours go to")
+        f0decode.check_decode(f0_decode)
+    if f0_out is not None:
+        f0_params = f0track.check_params(dict(f0_params)) if f0_params is not None else f0track.params(target)
+        if int(f0_params["sample_rate"]) != target:
+            raise ValueError(f"generate_mels: f0_params are for {f0_params['sample_rate']} Hz, the model rate is {target}")
+    maps = timemap.per_item(list(time_maps) if time_maps is not None else None, len(sounds), "generate_mels: time_maps")
+    # every map is checked, and its centres are made, before anything runs
+    warped = {ii: timemap.centres(resampled_length(sounds[ii].size, rates[ii], target), hop, target, mm, rows_per_frame)
+              for ii, mm in enumerate(maps) if mm is not None}
+    guided, band = {}, None
+    if guides is not None and any(gg is not None for gg in guides):
+        if guide_rates is None or len(guides) != len(sounds) or len(guide_rates) != len(sounds):
+            raise ValueError("generate_mels: guides and guide_rates take one entry per sound")
+        band = align.band_frames(align_band_s, target, hop)
+        for ii, gg in enumerate(guides):
+            if gg is None:
+                continue
+            if maps[ii] is not None:
+                raise ValueError(f"generate_mels: sound {ii} has a guide and a time map; the guide IS its time map")
+            gg = np.ascontiguousarray(gg, dtype=np.float32)
+            if gg.ndim != 1 or gg.size == 0:
+                raise ValueError(f"generate_mels: guide {ii} must be a non-empty 1-D array, got shape {gg.shape}")
+            guided[ii] = (gg, int(round(guide_rates[ii])))
+            frames_a = resampled_length(gg.size, guided[ii][1], target) // hop + 1
+            align.check_sizes(frames_a, resampled_length(sounds[ii].size, rates[ii], target) // hop + 1, band)
+            timemap._check_frames(float(frames_a), rows_per_frame)
+    return SimpleNamespace(cfg=cfg, target=target, hop=hop, win_len=int(cfg.get("win_size", cfg["fft_size"])), sounds=sounds,
+                           rates=rates, rows_per_frame=rows_per_frame, track=f0_out is not None, f0_params=f0_params,
+                           f0_decode=f0_decode, warped=warped, guided=guided, band=band, align_out=align_out, failed=set())
+
+
+def _aligned_centres(plan, ii, nodes, cost, frames_a, frames_b, n_source):
+    """The centres of guided item ``ii`` from its path: its time map in ``plan.warped``, the path's statistics in
+    ``plan.align_out``.  No path: ``align.AlignError`` or, where notes are taken, the note, ``plan.failed`` and None."""
+    from . import align, timemap
+    if len(nodes) == 0:
+        err = align.cannot_align(frames_a, frames_b, plan.band)
+        if plan.align_out is None:
+            raise err
+        plan.align_out[ii] = {"error": str(err)}
+        plan.failed.add(ii)
+        return None
+    if plan.align_out is not None:
+        plan.align_out[ii] = align.path_stats(nodes, cost, frames_a, frames_b, plan.hop, plan.target)
+    plan.warped[ii] = timemap.centres(n_source, plan.hop, plan.target,
+                                      timemap.Centres(align.centres_from_path(nodes, plan.hop, n_source)), plan.rows_per_frame)
+    return plan.warped[ii]
+
+
+def _analyse_host(plan, ii, stats):
+    """Item ``ii`` in numpy: its mel (frames, mel_channels) and its tracked pair (None unless ``plan.track``); (None, None)
+    for a guided item without a path."""
+    import time
+    from . import align, f0decode, f0track, resample, timemap
+    cfg, ss = plan.cfg, plan.sounds[ii]
+    t0 = time.perf_counter()
+    if plan.rates[ii] != plan.target:
+        ss = resample.resample_host(ss, plan.rates[ii], plan.target)
+    t1 = time.perf_counter()
+    if ii in plan.guided:
+        gg, gr = plan.guided[ii]
+        if gr != plan.target:
+            gg = resample.resample_host(gg, gr, plan.target)
+        mel_a = compute_log_mel(gg[np.newaxis], cfg, dtype=np.float32)[0][0]
+        mel_b = compute_log_mel(ss[np.newaxis], cfg, dtype=np.float32)[0][0]
+        nodes, cost = align.align_host(mel_a, mel_b, plan.band)
+        if _aligned_centres(plan, ii, nodes, cost, mel_a.shape[0], mel_b.shape[0], ss.size) is None:
+            return None, None
+    if ii in plan.warped:
+        mel, _ = compute_log_mel_at(ss[np.newaxis], plan.warped[ii], cfg, dtype=np.float32)
+    else:
+        mel, _ = compute_log_mel(ss[np.newaxis], cfg, dtype=np.float32)
+    _add(stats, "resample", t1 - t0)
+    _add(stats, "analysis", time.perf_counter() - t1)
+    if not plan.track:
+        return mel[0], None
+    t2 = time.perf_counter()
+    cc = plan.warped[ii] if ii in plan.warped else timemap.centres(ss.size, plan.hop, plan.target, None)
+    if plan.f0_decode is not None:
+        pair = f0decode.track_f0_viterbi_host(ss, cc, plan.f0_params, plan.f0_decode)
+    else:
+        pair = f0track.track_f0_host(ss, cc, plan.f0_params)
+    _add(stats, "f0", time.perf_counter() - t2)
+    return mel[0], pair
+
+
+def _device_batches(sounds, rates, preprocess_config, batch, dev, timed=False):
+    """The device micro-batches of ``sounds``: grouped by rate, sorted by length (neighbours share a launch: less padding),
+    at most ``batch`` items, padded, uploaded, resampled to the model rate and padded to half a window.  Yields (group of
+    indices, device sound (B, stride), device lengths int32 (B,), host lengths, marks); ``marks``: None, or with ``timed``
+    five timing events, the first three recorded around the upload and the resampler."""
     import torch
     from . import resample
     cfg = preprocess_config
-    target, hop = int(cfg["sample_rate"]), int(cfg["hop_size"])
-    win_len = int(cfg.get("win_size", cfg["fft_size"]))
-    out = [None] * len(sounds)
+    target, win_len = int(cfg["sample_rate"]), int(cfg.get("win_size", cfg["fft_size"]))
     by_rate = {}
     for ii, rr in enumerate(rates):
         by_rate.setdefault(rr, []).append(ii)
@@ -255,18 +360,110 @@ def _guide_mels_device(sounds, rates, preprocess_config, batch, dev):
             host = np.zeros((len(group), max(lengths)), dtype=np.float32)
             for bb, ii in enumerate(group):
                 host[bb, :lengths[bb]] = sounds[ii]
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timed else None
+            if marks:
+                marks[0].record()
             snd = torch.as_tensor(host).to(dev)
             n_dev = torch.as_tensor(np.asarray(lengths, dtype=np.int32)).to(dev)
+            if marks:
+                marks[1].record()
             if rr != target:
                 _, up, down = resample.device_taps(rr, target, dev)
                 snd, n_dev = resample.resample_device(snd, n_dev, rr, target)
                 lengths = [-(-nn * up // down) for nn in lengths]
-            if snd.shape[1] < win_len // 2 + 1:
+            if snd.shape[1] < win_len // 2 + 1:                # the analysis kernel wants rows of at least half a window
                 snd = torch.nn.functional.pad(snd, (0, win_len // 2 + 1 - snd.shape[1]))
-            mel_dev, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
-            for bb, ii in enumerate(group):
-                out[ii] = mel_dev[bb, :lengths[bb] // hop + 1]
+            if marks:
+                marks[2].record()
+            yield group, snd, n_dev, lengths, marks
+
+
+def _guide_mels_device(plan, batch, dev):
+    """{guided item: the regular log-mel of its guide as a device tensor (frames, mel_channels)}: the guides go through the
+    micro-batches of the sounds, without the copy back."""
+    order = sorted(plan.guided)
+    out = {}
+    for group, snd, n_dev, lengths, _ in _device_batches([plan.guided[ii][0] for ii in order],
+                                                         [plan.guided[ii][1] for ii in order], plan.cfg, batch, dev):
+        mel_dev, _ = compute_log_mel_device(snd, plan.cfg, n_samples=n_dev)
+        for bb, kk in enumerate(group):
+            out[order[kk]] = mel_dev[bb, :lengths[bb] // plan.hop + 1]
     return out
+
+
+def _align_device(plan, group, snd, n_dev, lengths, guide_mel):
+    """The guided items of one micro-batch: its regular analysis, the two alignment kernels on those rows, one copy back
+    with the nodes, and the items' centres (:func:`_aligned_centres`)."""
+    import torch
+    from . import align
+    rows = [bb for bb, ii in enumerate(group) if ii in guide_mel]
+    if not rows:
+        return
+    dev = snd.device
+    regular, _ = compute_log_mel_device(snd, plan.cfg, n_samples=n_dev)
+    n_a = [int(guide_mel[group[bb]].shape[0]) for bb in rows]
+    n_b = [lengths[bb] // plan.hop + 1 for bb in rows]
+    mel_a = torch.zeros((len(rows), max(n_a), regular.shape[2]), dtype=torch.float32, device=dev)
+    for kk, bb in enumerate(rows):
+        mel_a[kk, :n_a[kk]] = guide_mel[group[bb]]
+    mel_b = regular[rows, :max(n_b)].contiguous()
+    found = align.align_device(mel_a, torch.as_tensor(np.asarray(n_a, dtype=np.int32)).to(dev), mel_b,
+                               torch.as_tensor(np.asarray(n_b, dtype=np.int32)).to(dev), plan.band)
+    packed = torch.cat([found[0], found[1], found[2][:, None], found[3][:, None]], dim=1).cpu().numpy()
+    for kk, bb in enumerate(rows):
+        count = int(packed[kk, -2])
+        nodes = np.stack((packed[kk, :count], packed[kk, max(n_a):max(n_a) + count]), axis=1)
+        _aligned_centres(plan, group[bb], nodes, int(packed[kk, -1]), n_a[kk], n_b[kk], lengths[bb])
+
+
+def _analyse_device(plan, micro_batch, guide_mel, stats):
+    """One micro-batch of :func:`_device_batches` on the device: per item of its group the mel (frames, mel_channels) and
+    the tracked pair (None unless ``plan.track``), after one copy back.  ``stats`` costs the one wait."""
+    import time
+    import torch
+    from . import f0decode, f0track, timemap
+    group, snd, n_dev, lengths, marks = micro_batch
+    cfg, dev = plan.cfg, snd.device
+    _align_device(plan, group, snd, n_dev, lengths, guide_mel)
+    warped = any(ii in plan.warped for ii in group)
+    if warped or plan.track:
+        cents = [plan.warped[ii] if ii in plan.warped else timemap.centres(nn, plan.hop, plan.target, None)
+                 for ii, nn in zip(group, lengths)]
+        table = np.zeros((len(group), max(cc.size for cc in cents)), dtype=np.int64)
+        for bb, cc in enumerate(cents):
+            table[bb, :cc.size] = cc
+        counts = [int(cc.size) for cc in cents]
+        table_dev = torch.as_tensor(table).to(dev)
+        counts_dev = torch.as_tensor(np.asarray(counts, dtype=np.int32)).to(dev)
+    if warped:
+        mel_dev, _ = compute_log_mel_device_at(snd, n_dev, table_dev, counts_dev, cfg)
+    else:
+        counts = [nn // plan.hop + 1 for nn in lengths]
+        mel_dev, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
+    last = 3
+    if marks:
+        marks[3].record()
+    if plan.track:                                          # the regular centres are t * hop: the analysis's own frames
+        if plan.f0_decode is not None:
+            f0_dev, per_dev = f0decode.track_f0_viterbi_device(snd, n_dev, table_dev, counts_dev, plan.f0_params, plan.f0_decode)
+        else:
+            f0_dev, per_dev = f0track.track_f0_device(snd, n_dev, table_dev, counts_dev, plan.f0_params)
+        last = 4
+        if marks:
+            marks[4].record()
+    if marks:
+        marks[last].synchronize()
+        t0 = time.perf_counter()
+    mel = mel_dev.cpu().numpy()
+    pairs = [None] * len(group)
+    if plan.track:
+        f0_host, per_host = f0_dev.cpu().numpy(), per_dev.cpu().numpy()
+        pairs = [(f0_host[bb, :counts[bb]].copy(), per_host[bb, :counts[bb]].copy()) for bb in range(len(group))]
+    if marks:
+        _add(stats, "copy_back", time.perf_counter() - t0)
+        for key, first in (("f0", 3), ("upload", 0), ("resample", 1), ("analysis", 2))[4 - last:]:
+            _add(stats, key, marks[first].elapsed_time(marks[first + 1]) * 1e-3)
+    return [(mel[bb, :counts[bb]], pairs[bb]) for bb in range(len(group))]
 
 
 def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None, time_maps=None, rows_per_frame=1,
@@ -309,193 +506,22 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     without a guide keeps its regular bits; a call without guides makes the launches of before.  ``align_out``: a dict, or
     None.  Given a dict, item i's ``align.path_stats`` go to ``align_out[i]``, and an item that cannot be aligned
     (``align.AlignError``) leaves ``{"error": message}`` there and None in the result (and in ``f0_out``) instead of raising."""
-    import time
-    from . import align, f0decode, f0track, resample, timemap
-    cfg = preprocess_config
-    target, hop = int(cfg["sample_rate"]), int(cfg["hop_size"])
-    win_len = int(cfg.get("win_size", cfg["fft_size"]))
-    sounds = [np.ascontiguousarray(ss, dtype=np.float32) for ss in sounds]
-    rates = [int(round(rr)) for rr in rates]
-    if len(sounds) != len(rates):
-        raise ValueError("generate_mels: one rate per sound")
-    for ii, ss in enumerate(sounds):
-        if ss.ndim != 1 or ss.size == 0:
-            raise ValueError(f"generate_mels: sound {ii} must be a non-empty 1-D array, got shape {ss.shape}")
-    out = [None] * len(sounds)
-    tracked = [None] * len(sounds)
-    if f0_decode is not None:
-        if f0_out is None:
-            raise ValueError("generate_mels: f0_decode needs f0_out, the list the contours go to")
-        f0decode.check_decode(f0_decode)
-    if f0_out is not None:
-        f0_params = f0track.check_params(dict(f0_params)) if f0_params is not None else f0track.params(target)
-        if int(f0_params["sample_rate"]) != target:
-            raise ValueError(f"generate_mels: f0_params are for {f0_params['sample_rate']} Hz, the model rate is {target}")
-    maps = timemap.per_item(list(time_maps) if time_maps is not None else None, len(sounds), "generate_mels: time_maps")
-    # every map is checked, and its centres are made, before anything runs
-    warped = {ii: timemap.centres(resampled_length(sounds[ii].size, rates[ii], target), hop, target, mm, rows_per_frame)
-              for ii, mm in enumerate(maps) if mm is not None}
-    guided, band, failed = {}, None, set()
-    if guides is not None and any(gg is not None for gg in guides):
-        if guide_rates is None or len(guides) != len(sounds) or len(guide_rates) != len(sounds):
-            raise ValueError("generate_mels: guides and guide_rates take one entry per sound")
-        band = align.band_frames(align_band_s, target, hop)
-        for ii, gg in enumerate(guides):
-            if gg is None:
-                continue
-            if maps[ii] is not None:
-                raise ValueError(f"generate_mels: sound {ii} has a guide and a time map; the guide IS its time map")
-            gg = np.ascontiguousarray(gg, dtype=np.float32)
-            if gg.ndim != 1 or gg.size == 0:
-                raise ValueError(f"generate_mels: guide {ii} must be a non-empty 1-D array, got shape {gg.shape}")
-            guided[ii] = (gg, int(round(guide_rates[ii])))
-            frames_a = resampled_length(gg.size, guided[ii][1], target) // hop + 1
-            align.check_sizes(frames_a, resampled_length(sounds[ii].size, rates[ii], target) // hop + 1, band)
-            timemap._check_frames(float(frames_a), rows_per_frame)
-
-    def aligned_centres(ii, nodes, cost, frames_a, frames_b, n_source):
-        """The centres of a guided item from its path, or None (and the note in ``align_out``) when there is none."""
-        if len(nodes) == 0:
-            err = align.cannot_align(frames_a, frames_b, band)
-            if align_out is None:
-                raise err
-            align_out[ii] = {"error": str(err)}
-            failed.add(ii)
-            return None
-        if align_out is not None:
-            align_out[ii] = align.path_stats(nodes, cost, frames_a, frames_b, hop, target)
-        return timemap.centres(n_source, hop, target, timemap.Centres(align.centres_from_path(nodes, hop, n_source)),
-                               rows_per_frame)
-
+    plan = _plan_mels(sounds, rates, preprocess_config, time_maps, rows_per_frame, f0_out, f0_params, f0_decode, guides,
+                      guide_rates, align_band_s, align_out)
+    results = [(None, None)] * len(plan.sounds)
     if not on_device:
-        for ii, (ss, rr) in enumerate(zip(sounds, rates)):
-            t0 = time.perf_counter()
-            if rr != target:
-                ss = resample.resample_host(ss, rr, target)
-            t1 = time.perf_counter()
-            if ii in guided:
-                gg, gr = guided[ii]
-                if gr != target:
-                    gg = resample.resample_host(gg, gr, target)
-                mel_a = compute_log_mel(gg[np.newaxis], cfg, dtype=np.float32)[0][0]
-                mel_b = compute_log_mel(ss[np.newaxis], cfg, dtype=np.float32)[0][0]
-                nodes, cost = align.align_host(mel_a, mel_b, band)
-                cc = aligned_centres(ii, nodes, cost, mel_a.shape[0], mel_b.shape[0], ss.size)
-                if cc is None:
-                    continue
-                warped[ii] = cc
-            if ii in warped:
-                mel, _ = compute_log_mel_at(ss[np.newaxis], warped[ii], cfg, dtype=np.float32)
-            else:
-                mel, _ = compute_log_mel(ss[np.newaxis], cfg, dtype=np.float32)
-            _add(stats, "resample", t1 - t0)
-            _add(stats, "analysis", time.perf_counter() - t1)
-            out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[0].T))
-            if f0_out is not None:
-                t2 = time.perf_counter()
-                cc = warped[ii] if ii in warped else timemap.centres(ss.size, hop, target, None)
-                if f0_decode is not None:
-                    tracked[ii] = f0decode.track_f0_viterbi_host(ss, cc, f0_params, f0_decode)
-                else:
-                    tracked[ii] = f0track.track_f0_host(ss, cc, f0_params)
-                _add(stats, "f0", time.perf_counter() - t2)
-        if f0_out is not None:
-            f0_out.extend(tracked)
-        return out
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("generate_mels(on_device=True): no GPU available (on_device=False is the host path)")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    guide_mel = {}
-    if guided:
-        order = sorted(guided)
-        guide_mel = dict(zip(order, _guide_mels_device([guided[ii][0] for ii in order], [guided[ii][1] for ii in order], cfg,
-                                                       batch, dev)))
-    by_rate = {}
-    for ii, rr in enumerate(rates):
-        by_rate.setdefault(rr, []).append(ii)
-    for rr, members in by_rate.items():
-        members = sorted(members, key=lambda ii: -sounds[ii].size)         # neighbours in length share a launch: less padding
-        for start in range(0, len(members), max(1, int(batch))):
-            group = members[start:start + max(1, int(batch))]
-            lengths = [sounds[ii].size for ii in group]
-            host = np.zeros((len(group), max(lengths)), dtype=np.float32)
-            for bb, ii in enumerate(group):
-                host[bb, :lengths[bb]] = sounds[ii]
-            marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if stats is not None else None
-            if marks:
-                marks[0].record()
-            snd = torch.as_tensor(host).to(dev)
-            n_dev = torch.as_tensor(np.asarray(lengths, dtype=np.int32)).to(dev)
-            if marks:
-                marks[1].record()
-            if rr != target:
-                _, up, down = resample.device_taps(rr, target, dev)
-                snd, n_dev = resample.resample_device(snd, n_dev, rr, target)
-                lengths = [-(-nn * up // down) for nn in lengths]
-            if snd.shape[1] < win_len // 2 + 1:                # the analysis kernel wants rows of at least half a window
-                snd = torch.nn.functional.pad(snd, (0, win_len // 2 + 1 - snd.shape[1]))
-            if marks:
-                marks[2].record()
-            rows = [bb for bb, ii in enumerate(group) if ii in guide_mel]
-            if rows:
-                # the regular analysis of the micro-batch, the two alignment kernels on its guided items, one copy back
-                regular, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
-                n_a = [int(guide_mel[group[bb]].shape[0]) for bb in rows]
-                n_b = [lengths[bb] // hop + 1 for bb in rows]
-                mel_a = torch.zeros((len(rows), max(n_a), regular.shape[2]), dtype=torch.float32, device=dev)
-                for kk, bb in enumerate(rows):
-                    mel_a[kk, :n_a[kk]] = guide_mel[group[bb]]
-                mel_b = regular[rows, :max(n_b)].contiguous()
-                found = align.align_device(mel_a, torch.as_tensor(np.asarray(n_a, dtype=np.int32)).to(dev), mel_b,
-                                           torch.as_tensor(np.asarray(n_b, dtype=np.int32)).to(dev), band)
-                packed = torch.cat([found[0], found[1], found[2][:, None], found[3][:, None]], dim=1).cpu().numpy()
-                for kk, bb in enumerate(rows):
-                    count = int(packed[kk, -2])
-                    nodes = np.stack((packed[kk, :count], packed[kk, max(n_a):max(n_a) + count]), axis=1)
-                    cc = aligned_centres(group[bb], nodes, int(packed[kk, -1]), n_a[kk], n_b[kk], lengths[bb])
-                    if cc is not None:
-                        warped[group[bb]] = cc
-            if any(ii in warped for ii in group) or f0_out is not None:
-                cents = [warped[ii] if ii in warped else timemap.centres(nn, hop, target, None) for ii, nn in zip(group, lengths)]
-                table = np.zeros((len(group), max(cc.size for cc in cents)), dtype=np.int64)
-                for bb, cc in enumerate(cents):
-                    table[bb, :cc.size] = cc
-                counts = [int(cc.size) for cc in cents]
-                table_dev = torch.as_tensor(table).to(dev)
-                counts_dev = torch.as_tensor(np.asarray(counts, dtype=np.int32)).to(dev)
-            if any(ii in warped for ii in group):
-                mel_dev, _ = compute_log_mel_device_at(snd, n_dev, table_dev, counts_dev, cfg)
-            else:
-                counts = [nn // hop + 1 for nn in lengths]
-                mel_dev, _ = compute_log_mel_device(snd, cfg, n_samples=n_dev)
-            if marks:
-                marks[3].record()
-            if f0_out is not None:                              # the regular centres are t * hop: the analysis's own frames
-                if f0_decode is not None:
-                    f0_dev, per_dev = f0decode.track_f0_viterbi_device(snd, n_dev, table_dev, counts_dev, f0_params, f0_decode)
-                else:
-                    f0_dev, per_dev = f0track.track_f0_device(snd, n_dev, table_dev, counts_dev, f0_params)
-                if marks:
-                    marks[4].record()
-            if marks:
-                marks[4 if f0_out is not None else 3].synchronize()
-                t0 = time.perf_counter()
-            mel = mel_dev.cpu().numpy()
-            if f0_out is not None:
-                f0_host, per_host = f0_dev.cpu().numpy(), per_dev.cpu().numpy()
-                for bb, ii in enumerate(group):
-                    tracked[ii] = (f0_host[bb, :counts[bb]].copy(), per_host[bb, :counts[bb]].copy())
-            if marks:
-                _add(stats, "copy_back", time.perf_counter() - t0)
-                if f0_out is not None:
-                    _add(stats, "f0", marks[3].elapsed_time(marks[4]) * 1e-3)
-                for key, first in (("upload", 0), ("resample", 1), ("analysis", 2)):
-                    _add(stats, key, marks[first].elapsed_time(marks[first + 1]) * 1e-3)
-            for bb, ii in enumerate(group):
-                out[ii] = dict(mell_header(cfg), mell=np.ascontiguousarray(mel[bb, :counts[bb]].T))
-    for ii in failed:
-        out[ii], tracked[ii] = None, None
+        results = [_analyse_host(plan, ii, stats) for ii in range(len(plan.sounds))]
+    else:
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("generate_mels(on_device=True): no GPU available (on_device=False is the host path)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        guide_mel = _guide_mels_device(plan, batch, dev) if plan.guided else {}
+        for micro_batch in _device_batches(plan.sounds, plan.rates, plan.cfg, batch, dev, timed=stats is not None):
+            for ii, result in zip(micro_batch[0], _analyse_device(plan, micro_batch, guide_mel, stats)):
+                results[ii] = result
+    for ii in plan.failed:
+        results[ii] = (None, None)
     if f0_out is not None:
-        f0_out.extend(tracked)
-    return out
+        f0_out.extend(pair for _, pair in results)
+    return [None if mel is None else dict(mell_header(plan.cfg), mell=np.ascontiguousarray(mel.T)) for mel, _ in results]

@@ -149,6 +149,26 @@ def stage_factors(rows, device=None):
     return torch.as_tensor(scale, device=device)
 
 
+def _control_rows(control, key, name, rows, group, lengths, device, drop_ones=False, mask_key=None):
+    """``control[key]``: the rows of the micro-batch ``group`` out of the per-item ``rows`` (run_micro_batches' argument
+    ``name``; None: ones), or nothing without the argument; a row of another length than its mel is refused by name.
+    ``drop_ones``: nothing when every value is exactly 1.  ``mask_key``: with ``control[mask_key]``, int32 (B,), 0 for the
+    items with None -- and nothing when all are."""
+    import torch
+    if rows is None or (mask_key and all(rows[ii] is None for ii in group)):
+        return
+    for ii in group:
+        if rows[ii] is not None and np.shape(rows[ii]) != (lengths[ii],):
+            raise ValueError(f"{name}[{ii}] must hold one factor per mel frame ({lengths[ii]})")
+    staged = [np.ones(lengths[ii], dtype=np.float32) if rows[ii] is None else np.asarray(rows[ii], dtype=np.float32)
+              for ii in group]
+    if drop_ones and not any(np.any(rr != 1.0) for rr in staged):
+        return
+    control[key] = stage_factors(staged, device)
+    if mask_key:
+        control[mask_key] = torch.as_tensor(np.asarray([rows[ii] is not None for ii in group], dtype=np.int32), device=device)
+
+
 def check_f0s(f0s, lengths):
     """The per-item F0 contours of a job, checked before anything runs: None, or a list with, per item, None or a float32
     array (T_i,) of positive finite Hz.  A list of Nones counts as None."""
@@ -204,26 +224,9 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
                                                  None if noises is None or keyed else [noises[ii] for ii in group],
                                                  dims.wn_in_rows_per_frame, engine.device)
         control = {}
-        if transpositions is not None:
-            for ii in group:
-                if transpositions[ii] is not None and np.shape(transpositions[ii]) != (lengths[ii],):
-                    raise ValueError(f"transpositions[{ii}] must hold one factor per mel frame ({lengths[ii]})")
-            control["f0_scale"] = stage_factors([np.ones(lengths[ii], dtype=np.float32) if transpositions[ii] is None
-                                                 else np.asarray(transpositions[ii], dtype=np.float32) for ii in group],
-                                                engine.device)
-        if formants is not None:
-            for ii in group:
-                if formants[ii] is not None and np.shape(formants[ii]) != (lengths[ii],):
-                    raise ValueError(f"formants[{ii}] must hold one factor per mel frame ({lengths[ii]})")
-            rows = [np.ones(lengths[ii], dtype=np.float32) if formants[ii] is None else np.asarray(formants[ii], dtype=np.float32)
-                    for ii in group]
-            if any(np.any(rr != 1.0) for rr in rows):
-                control["formant"] = stage_factors(rows, engine.device)
-        if f0s is not None and any(f0s[ii] is not None for ii in group):
-            control["f0_frames"] = stage_factors([np.ones(lengths[ii], dtype=np.float32) if f0s[ii] is None else f0s[ii]
-                                                  for ii in group], engine.device)
-            control["f0_item_mask"] = torch.as_tensor(np.asarray([f0s[ii] is not None for ii in group], dtype=np.int32),
-                                                      device=engine.device)
+        _control_rows(control, "f0_scale", "transpositions", transpositions, group, lengths, engine.device)
+        _control_rows(control, "formant", "formants", formants, group, lengths, engine.device, drop_ones=True)
+        _control_rows(control, "f0_frames", "f0s", f0s, group, lengths, engine.device, mask_key="f0_item_mask")
         events = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         events[0].record(stream)
         if keyed:                                           # the draw is part of the step: inside the device time
@@ -263,8 +266,46 @@ class _Clock:
             self.seconds[key] = self.seconds.get(key, 0.0) + seconds
 
 
-def _file_writer(inv, files, mine, scaled, output_dir, fmt, device_flac, file_rate, flac_compression, verbose, quiet, clock,
-                 log):
+class _Job:
+    """What run_job and run_audio_job share: the start time, the clock of the pool stages, a locked ``log``, "submit every
+    micro-batch to the writers and wait", and the verbose line around the tool's own stages."""
+
+    def __init__(self, threads):
+        self.t_start, self.threads = time.perf_counter(), max(1, threads)
+        self.clock, self._lock = _Clock(), threading.Lock()
+
+    def log(self, lines):
+        with self._lock:
+            for line in lines:
+                print(line, file=sys.stderr)
+
+    def timed(self, key, func):
+        """``func``, its seconds added to the clock under ``key``."""
+        def call(*args):
+            t0 = time.perf_counter()
+            try:
+                return func(*args)
+            finally:
+                self.clock.add(key, time.perf_counter() - t0)
+        return call
+
+    def write_all(self, work):
+        """``work`` yields (writer task, SynthBatch) as the micro-batches are enqueued: submitted at once, all waited for."""
+        with ThreadPoolExecutor(max_workers=self.threads) as writers:
+            pending = [writers.submit(write, sb) for write, sb in work]
+            for fu in pending:
+                fu.result()
+
+    def summary(self, tool, count, audio_s, stages, device, copy, note=""):
+        """The verbose line: the tool's own ``stages`` between the totals and the micro-batches' device and copy time."""
+        wall, sec = time.perf_counter() - self.t_start, self.clock.seconds
+        print(f"{tool}: {count} files, {audio_s:.1f} s of audio{note} in {wall:.2f} s wall ({audio_s / max(wall, 1e-9):.1f} x "
+              f"real time); {stages}, {device} {sec.get('device_ms', 0.0) / 1e3:.3f} s, {copy} "
+              f"{sec.get('copy_ms', 0.0) / 1e3:.3f} s, MD5+write {sec.get('write', 0.0):.2f} s (pool stages summed over "
+              f"{self.threads} threads each)", file=sys.stderr)
+
+
+def _file_writer(job, inv, files, mine, scaled, output_dir, fmt, device_flac, file_rate, flac_compression, verbose, quiet):
     """The writer-pool task of run_job and run_audio_job: ``write(sb)`` waits for the micro-batch ``sb`` (whose indices
     point into ``mine``) and writes syn_<basename>.<fmt> of each of its items, with the clipping note and, ``verbose``, the
     mel error against ``scaled``."""
@@ -293,10 +334,10 @@ def _file_writer(inv, files, mine, scaled, output_dir, fmt, device_flac, file_ra
                 sb.flac.write(outfile, jj)
             else:                                        # soundfile, wav, or an item the host writer must take
                 write_audio(outfile, audio if audio is not None else sb.audio(jj), file_rate, fmt, flac_compression)
-            log(lines)
-        clock.add("write", time.perf_counter() - t0)
-        clock.add("device_ms", sb.device_ms)
-        clock.add("copy_ms", sb.copy_ms)
+            job.log(lines)
+        job.clock.add("write", time.perf_counter() - t0)
+        job.clock.add("device_ms", sb.device_ms)
+        job.clock.add("copy_ms", sb.copy_ms)
 
     return write
 
@@ -329,25 +370,16 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
     factor on every mel frame of every file (``formant`` rows).  ``f0_dir``: every file takes the contour of
     ``f0_dir/NAME.f0`` (:func:`load_contour`; a missing file or a wrong row count fails before anything runs) in place of the
     F0-net's.  All None: today's job."""
-    t_start = time.perf_counter()
+    job = _Job(threads)
     mine = list(range(len(files))) if mine is None else list(mine)
-    clock, log_lock = _Clock(), threading.Lock()
-
-    def log(lines):
-        with log_lock:
-            for line in lines:
-                print(line, file=sys.stderr)
 
     def read(ii):
-        t0 = time.perf_counter()
         if verbose:
-            log([f"load mell  from {files[ii]}"])
-        mel = inv.scale_mel(load_var(files[ii]), verbose=verbose)
-        clock.add("read", time.perf_counter() - t0)
-        return mel
+            job.log([f"load mell  from {files[ii]}"])
+        return inv.scale_mel(load_var(files[ii]), verbose=verbose)
 
-    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
-        scaled = dict(zip(mine, pool.map(read, mine)))
+    with ThreadPoolExecutor(max_workers=job.threads) as pool:
+        scaled = dict(zip(mine, pool.map(job.timed("read", read), mine)))
     if frames is None:
         if sorted(mine) != list(range(len(files))):
             raise ValueError("run_job: the frames of every file are needed when this process writes only some of them")
@@ -361,9 +393,8 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
     device_flac = fmt.lower() == "flac" and not have_soundfile()
     rate = inv.srate
     out_rate = inv._output_rate(out_rate)
-    file_rate = rate if out_rate is None else out_rate
-    write = _file_writer(inv, files, mine, scaled, output_dir, fmt, device_flac, file_rate, flac_compression, verbose, quiet,
-                         clock, log)
+    write = _file_writer(job, inv, files, mine, scaled, output_dir, fmt, device_flac, rate if out_rate is None else out_rate,
+                         flac_compression, verbose, quiet)
     mels = [scaled[ii][0] for ii in mine]
     noises = None if draws is None else [draws[ii] for ii in mine]
     if noise_seed is not None and dims.noise_sigma:
@@ -373,21 +404,13 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
     rows = None if transposition is None else [np.full(int(mm.shape[0]), transposition, dtype=np.float32) for mm in mels]
     shifts = None if formant is None else [np.full(int(mm.shape[0]), formant, dtype=np.float32) for mm in mels]
     contours = None if f0_dir is None else [load_contour(files[ii], f0_dir, int(scaled[ii].shape[1])) for ii in mine]
-    with ThreadPoolExecutor(max_workers=max(1, threads)) as writers:
-        pending = [writers.submit(write, sb) for sb in run_micro_batches(inv.model, mels, noises, max(1, batch),
-                                                                         flac=device_flac, host_audio=verbose or not device_flac,
-                                                                         flac_compression=flac_compression, out_rate=out_rate,
-                                                                         transpositions=rows, formants=shifts, f0s=contours)]
-        for fu in pending:
-            fu.result()
+    job.write_all((write, sb) for sb in run_micro_batches(inv.model, mels, noises, max(1, batch), flac=device_flac,
+                                                          host_audio=verbose or not device_flac,
+                                                          flac_compression=flac_compression, out_rate=out_rate,
+                                                          transpositions=rows, formants=shifts, f0s=contours))
     if verbose:
-        wall = time.perf_counter() - t_start
-        sec = clock.seconds
-        audio_s = sum(int(frames[ii]) for ii in mine) * inv.hop_size / rate
-        print(f"resynth_mel: {len(mine)} files, {audio_s:.1f} s of audio in {wall:.2f} s wall ({audio_s / max(wall, 1e-9):.1f} x "
-              f"real time); read+scale {sec.get('read', 0.0):.2f} s, device {sec.get('device_ms', 0.0) / 1e3:.3f} s, "
-              f"encode+D2H {sec.get('copy_ms', 0.0) / 1e3:.3f} s, MD5+write {sec.get('write', 0.0):.2f} s "
-              f"(pool stages summed over {max(1, threads)} threads each)", file=sys.stderr)
+        job.summary("resynth_mel", len(mine), sum(int(frames[ii]) for ii in mine) * inv.hop_size / rate,
+                    f"read+scale {job.clock.seconds.get('read', 0.0):.2f} s", "device", "encode+D2H")
 
 
 def read_transposition_file(path):
@@ -429,11 +452,7 @@ def file_stretches(files, stretch=1.0, table=None):
     """The time-stretch factor of every file: ``table[basename]`` (read_transposition_file: ``--time-stretch-file`` has the
     format of ``--transposition-file``) where it is listed, else ``stretch``; every factor finite and positive, or
     ValueError."""
-    table = table or {}
-    factors = [float(table.get(os.path.basename(ff), stretch)) for ff in files]
-    if not all(np.isfinite(ff) and ff > 0 for ff in factors):
-        raise ValueError("time stretch must be finite and positive")
-    return factors
+    return file_factors(files, stretch, table, what="time stretch")
 
 
 def read_sound(path):
@@ -487,38 +506,89 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     ``timings``: a dict that receives the seconds per stage the
     verbose line reports (upload, resample, analysis, f0, copy_back from ``generate_mels``; read, scale, device, copy, write
     from the pools and the micro-batches' events; wall)."""
-    from . import f0track, timemap
-    from .analysis import generate_mels, resampled_length
-    from .mel_inverter import KeyedNoise
-    from .noise import item_key
-    t_start = time.perf_counter()
+    from . import f0track
+    job = _Job(threads)
     mine = list(range(len(files))) if mine is None else list(mine)
     factors = [1.0] * len(files) if factors is None else list(factors)
-    clock, log_lock = _Clock(), threading.Lock()
-
-    def log(lines):
-        with log_lock:
-            for line in lines:
-                print(line, file=sys.stderr)
-
-    def read(ii):
-        t0 = time.perf_counter()
-        try:
-            return read_sound(files[ii])
-        except ValueError as err:
-            return err
-        finally:
-            clock.add("read", time.perf_counter() - t0)
-
-    def scale(dd):
-        t0 = time.perf_counter()
-        mel = inv.scale_mel(dd, verbose=verbose)
-        clock.add("scale", time.perf_counter() - t0)
-        return mel
-
     guides = None if guides is None or all(gg is None for gg in guides) else list(guides)
     if guides is not None and len(guides) != len(files):
         raise ValueError(f"run_audio_job: guides takes one entry per file ({len(files)}), got {len(guides)}")
+    stats = {}
+    with ThreadPoolExecutor(max_workers=job.threads) as pool:                                   # the readers, then scale_mel
+        loaded, guide_sounds, mine, maps, skipped = _load_sounds(job, pool, inv, files, mine, guides, stretches)
+        have_guides = guides is not None and any(guides[ii] is not None for ii in mine)
+        scale = job.timed("scale", lambda dd: inv.scale_mel(dd, verbose=verbose))
+        try:
+            done = analyse_for_synthesis(
+                inv, [loaded[ii][0] for ii in mine], [loaded[ii][1] for ii in mine], time_maps=[maps[ii] for ii in mine],
+                guides=[None if guides[ii] is None else guide_sounds[guides[ii]][0] for ii in mine] if have_guides else None,
+                guide_rates=[None if guides[ii] is None else guide_sounds[guides[ii]][1] for ii in mine] if have_guides else None,
+                align_band_s=align_band_s, f0_source=f0_source, f0_params=f0_params, f0_decode=f0_decode, f0_fill=f0_fill,
+                f0_initial=f0_initial, write_f0=bool(write_f0), batch=batch, stats=stats,
+                scale_map=lambda dicts: list(pool.map(scale, dicts)), who="run_audio_job")
+        except ValueError as err:
+            if not have_guides:
+                raise
+            raise ValueError(f"align: {err}") from None
+    lines = []
+    for local, ii in enumerate(mine):                          # the files without a path leave the job here
+        note = done.notes.get(local)
+        if note is not None and "error" in note:
+            skipped.append((files[ii], f"{note['error']} (guide {guides[ii]})"))
+            lines.append(f"transform_audio::error:: skipped {files[ii]}: {note['error']} (guide {guides[ii]})")
+        elif note is not None and verbose:
+            lines.append(f"    aligned {files[ii]} to {guides[ii]}: {note['nodes']} nodes, mean cost per node "
+                         f"{note['mean_cost']:.3f}, largest offset from the diagonal {note['max_offset_ms']:.1f} ms")
+    job.log(lines)
+    keep = [local for local in range(len(mine)) if done.scaled[local] is not None]
+    scaled = {mine[local]: done.scaled[local] for local in keep}
+    contours = None if done.contours is None else {mine[local]: done.contours[local] for local in keep}
+    if write_f0:
+        for local in keep:
+            f0, periodicity = done.tracked[local]
+            f0track.write_f0(f0_path(files[mine[local]], output_dir), f0track.frame_times(f0.size, inv.hop_size, inv.srate),
+                             f0, periodicity)
+    mine = [mine[local] for local in keep]
+    rates = {ii: loaded[ii][1] if out_rate == "input" else out_rate for ii in mine}
+    _synthesise_files(job, inv, files, mine, scaled, contours, rates, output_dir, fmt, factors, formants, noise_seed, batch,
+                      flac_compression, verbose, quiet)
+    if timings is not None:
+        sec = job.clock.seconds
+        timings.update(stats, read=sec.get("read", 0.0), scale=sec.get("scale", 0.0), device=sec.get("device_ms", 0.0) / 1e3,
+                       copy=sec.get("copy_ms", 0.0) / 1e3, write=sec.get("write", 0.0), wall=time.perf_counter() - job.t_start)
+    if verbose:
+        in_s = sum(loaded[ii][0].size / loaded[ii][1] for ii in mine)
+        note = "" if all(maps[ii] is None for ii in mine) else f" (time-stretched from {in_s:.1f} s of input)"
+        if guides is not None:
+            note = f" (aligned to guides, from {in_s:.1f} s of input)"
+        sec = job.clock.seconds
+        job.summary("transform_audio", len(mine), sum(int(scaled[ii].shape[1]) for ii in mine) * inv.hop_size / inv.srate,
+                    f"read {sec.get('read', 0.0):.2f} s, upload {stats.get('upload', 0.0):.3f} s, resample "
+                    f"{stats.get('resample', 0.0):.3f} s, analysis {stats.get('analysis', 0.0):.3f} s, "
+                    + (f"f0 tracker {stats.get('f0', 0.0):.3f} s, " if done.tracked is not None else "") + "mel copy-back "
+                    f"{stats.get('copy_back', 0.0):.3f} s, scale_mel {sec.get('scale', 0.0):.2f} s", "noise+forward",
+                    "resample+encode+D2H", note)
+    return skipped
+
+
+def check_stretch(n_samples, rate, factor, hop, target, rows_per_frame):
+    """ValueError (``timemap.frame_count``) when ``n_samples`` at ``rate``, stretched by ``factor``, exceed the engine's
+    limit.  A factor of exactly 1 is the regular analysis: never refused."""
+    from . import timemap
+    from .analysis import resampled_length
+    if factor != 1.0:
+        timemap.frame_count(resampled_length(n_samples, rate, target), hop, target, factor, rows_per_frame)
+
+
+def _load_sounds(job, pool, inv, files, mine, guides, stretches):
+    """Phase one of run_audio_job, on the reader ``pool``: the sounds {index: (samples, rate)}, the guides {path: (samples,
+    rate)}, the indices that stay in the job, their time maps {index: None or a factor} and the (file, reason) pairs of
+    the others, reported here: an unreadable file or guide, a stretched length beyond the engine's limit."""
+    def read(path):
+        try:
+            return read_sound(path)
+        except ValueError as err:
+            return err
 
     def read_guide(path):
         try:
@@ -526,121 +596,103 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
         except (OSError, ValueError) as err:
             return ValueError(f"guide {path}: {err}")
 
-    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
-        loaded = dict(zip(mine, pool.map(read, mine)))
-        skipped = [(files[ii], str(loaded[ii])) for ii in mine if isinstance(loaded[ii], ValueError)]
-        mine = [ii for ii in mine if not isinstance(loaded[ii], ValueError)]
-        guide_sounds = {}
-        if guides is not None:
-            paths = sorted({guides[ii] for ii in mine if guides[ii] is not None})
-            guide_sounds = dict(zip(paths, pool.map(read_guide, paths)))
-            for ii in [ii for ii in mine if guides[ii] is not None]:
-                if isinstance(guide_sounds[guides[ii]], ValueError):
-                    skipped.append((files[ii], str(guide_sounds[guides[ii]])))
-                    mine.remove(ii)
-                elif stretches is not None and float(stretches[ii]) != 1.0:
-                    raise ValueError(f"run_audio_job: {files[ii]} has a guide and a time stretch; the guide sets its timing")
-        # a factor of exactly 1 is the regular analysis; every other one is checked against the engine's limit here
-        maps = {ii: None if stretches is None or float(stretches[ii]) == 1.0 else float(stretches[ii]) for ii in mine}
-        for ii in [ii for ii in mine if maps[ii] is not None]:
-            try:
-                timemap.frame_count(resampled_length(loaded[ii][0].size, loaded[ii][1], inv.srate), inv.hop_size, inv.srate,
-                                    maps[ii], inv.model.dims.steps_per_frame)
-            except ValueError as err:
-                skipped.append((files[ii], str(err)))
-                mine.remove(ii)
-        for name, why in skipped:
-            log([f"transform_audio::error:: skipped {name}: {why}"])
-        if f0_source not in ("net", "audio"):
-            raise ValueError(f"run_audio_job: f0_source must be 'net' or 'audio', got {f0_source!r}")
-        f0track.check_fill(f0_fill, f0_source, "run_audio_job")
-        tracked = [] if f0_source == "audio" or write_f0 else None
-        if f0_decode is not None and tracked is None:
-            raise ValueError("run_audio_job: f0_decode decodes the tracked contour and needs f0_source='audio' or write_f0")
-        stats = {}
-        aligned = {}
-        have_guides = guides is not None and any(guides[ii] is not None for ii in mine)
+    loaded = dict(zip(mine, pool.map(job.timed("read", read), [files[ii] for ii in mine])))
+    why = {ii: str(loaded[ii]) for ii in mine if isinstance(loaded[ii], ValueError)}
+    paths = sorted({guides[ii] for ii in mine if ii not in why and guides is not None and guides[ii] is not None})
+    guide_sounds = dict(zip(paths, pool.map(read_guide, paths)))
+    # a factor of exactly 1 is the regular analysis; every other one is checked against the engine's limit below
+    maps = {ii: None if stretches is None or float(stretches[ii]) == 1.0 else float(stretches[ii]) for ii in mine}
+    for ii in [ii for ii in mine if ii not in why]:
+        guide = None if guides is None or guides[ii] is None else guide_sounds[guides[ii]]
+        if isinstance(guide, ValueError):
+            why[ii] = str(guide)
+        elif guide is not None and maps[ii] is not None:
+            raise ValueError(f"run_audio_job: {files[ii]} has a guide and a time stretch; the guide sets its timing")
+    for ii in [ii for ii in mine if ii not in why and maps[ii] is not None]:
         try:
-            dicts = generate_mels([loaded[ii][0] for ii in mine], [loaded[ii][1] for ii in mine], inv.preprocess_config,
-                                  on_device=True, batch=max(1, batch), stats=stats,
-                                  time_maps=None if all(maps[ii] is None for ii in mine) else [maps[ii] for ii in mine],
-                                  rows_per_frame=inv.model.dims.steps_per_frame, f0_out=tracked,
-                                  f0_params=None if tracked is None else f0track.params(int(round(inv.srate)), **(f0_params or {})),
-                                  f0_decode=f0_decode,
-                                  **({"guides": [None if guides[ii] is None else guide_sounds[guides[ii]][0] for ii in mine],
-                                      "guide_rates": [None if guides[ii] is None else guide_sounds[guides[ii]][1] for ii in mine],
-                                      "align_band_s": align_band_s, "align_out": aligned} if have_guides else {})) if mine else []
+            check_stretch(loaded[ii][0].size, loaded[ii][1], maps[ii], inv.hop_size, inv.srate, inv.model.dims.steps_per_frame)
         except ValueError as err:
-            if not have_guides:
-                raise
-            raise ValueError(f"align: {err}") from None
-        if have_guides:                                       # the files without a path leave the job here
-            lines = []
-            for local, ii in enumerate(list(mine)):
-                note = aligned.get(local)
-                if note is not None and "error" in note:
-                    skipped.append((files[ii], f"{note['error']} (guide {guides[ii]})"))
-                    lines.append(f"transform_audio::error:: skipped {files[ii]}: {note['error']} (guide {guides[ii]})")
-                elif note is not None and verbose:
-                    lines.append(f"    aligned {files[ii]} to {guides[ii]}: {note['nodes']} nodes, mean cost per node "
-                                 f"{note['mean_cost']:.3f}, largest offset from the diagonal {note['max_offset_ms']:.1f} ms")
-            log(lines)
-            keep = [local for local in range(len(mine)) if dicts[local] is not None]
-            if tracked is not None:
-                tracked[:] = [tracked[local] for local in keep]
-            dicts, mine = [dicts[local] for local in keep], [mine[local] for local in keep]
-        scaled = dict(zip(mine, pool.map(scale, dicts)))
-        contours = None
-        if tracked is not None:
-            tracked = dict(zip(mine, tracked))
-            if write_f0:
-                for ii in mine:
-                    f0track.write_f0(f0_path(files[ii], output_dir), f0track.frame_times(tracked[ii][0].size, inv.hop_size, inv.srate),
-                                     *tracked[ii])
-            if f0_source == "audio":
-                contours = {ii: f0track.fill_tracked(tracked[ii][0], f0_fill, f0_initial) for ii in mine}
+            why[ii] = str(err)
+    skipped = [(files[ii], reason) for ii, reason in why.items()]
+    job.log([f"transform_audio::error:: skipped {name}: {reason}" for name, reason in skipped])
+    return loaded, guide_sounds, [ii for ii in mine if ii not in why], maps, skipped
+
+
+def analyse_for_synthesis(inv, sounds, rates, time_maps=None, guides=None, guide_rates=None, align_band_s=1.0, f0_source="net",
+                          f0_params=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0, write_f0=None, batch=16,
+                          stats=None, scale_map=None, on_device=True, rows_per_frame=None, who="analyse_for_synthesis"):
+    """Sounds in, what the synthesis takes out: the step between reading and ``run_micro_batches``, the same code under
+    ``MELInverter.transform_audio`` and :func:`run_audio_job`.  ``sounds`` at ``rates`` go through ``analysis.generate_mels``
+    (``time_maps``, ``guides``, ``guide_rates``, ``align_band_s``, ``batch``, ``stats``, ``on_device`` and ``rows_per_frame``
+    -- default: the engine's -- as there) and ``inv.scale_mel``; ``scale_map``: a function from the list of ``.mell``
+    dictionaries to the list of scaled mels, for a caller with a thread pool.  The pitch options are checked before anything
+    runs, ``who`` naming the caller: ``f0_source`` "net" or "audio", ``f0_params`` keywords of ``f0track.params``,
+    ``f0_decode`` None or ``f0decode.decode_params`` (it needs a tracked contour), ``f0_fill`` / ``f0_initial`` as
+    ``f0track.fill_tracked`` takes them; ``write_f0``: None for a caller without the option, else whether "net" tracks too.
+
+    Returns a namespace: ``scaled`` (1, T, mel_channels), ``contours`` (filled; an item without a voiced frame: None; not
+    "audio": None as a whole) and ``tracked`` (raw (f0, periodicity); nothing tracked: None as a whole) hold one entry per
+    sound; ``notes`` is {item: ``align.path_stats`` or {"error": message}}.  An item that cannot be aligned to its guide
+    has its note and None in all three lists."""
+    from types import SimpleNamespace
+    from . import f0track
+    from .analysis import generate_mels
+    if f0_source not in ("net", "audio"):
+        raise ValueError(f"{who}: f0_source must be 'net' or 'audio', got {f0_source!r}")
+    f0track.check_fill(f0_fill, f0_source, who)
+    tracked = [] if f0_source == "audio" or write_f0 else None
+    if f0_decode is not None and tracked is None:
+        raise ValueError(f"{who}: f0_decode decodes the tracked contour and needs f0_source='audio'"
+                         + ("" if write_f0 is None else " or write_f0"))
+    if tracked is not None:
+        f0_params = f0track.params(int(round(inv.srate)), **(f0_params or {}))
+    guided = guides is not None and any(gg is not None for gg in guides)
+    notes = {}
+    dicts = []
+    if len(sounds):
+        dicts = generate_mels(sounds, rates, inv.preprocess_config, on_device=on_device, batch=max(1, batch), stats=stats,
+                              time_maps=None if time_maps is None or all(mm is None for mm in time_maps) else list(time_maps),
+                              rows_per_frame=inv.model.dims.steps_per_frame if rows_per_frame is None else rows_per_frame,
+                              f0_out=tracked, f0_params=f0_params if tracked is not None else None, f0_decode=f0_decode,
+                              guides=guides if guided else None, guide_rates=guide_rates if guided else None,
+                              align_band_s=align_band_s, align_out=notes if guided else None)
+    keep = [ii for ii, dd in enumerate(dicts) if dd is not None]
+    scale_map = scale_map or (lambda some: [inv.scale_mel(dd) for dd in some])
+    scaled = [None] * len(dicts)
+    for ii, mel in zip(keep, scale_map([dicts[ii] for ii in keep])):
+        scaled[ii] = mel
+    contours = None
+    if f0_source == "audio":
+        contours = [None if pair is None else f0track.fill_tracked(pair[0], f0_fill, f0_initial) for pair in tracked]
+    return SimpleNamespace(scaled=scaled, contours=contours, tracked=tracked, notes=notes)
+
+
+def _synthesise_files(job, inv, files, mine, scaled, contours, rates, output_dir, fmt, factors, formants, noise_seed, batch,
+                      flac_compression, verbose, quiet):
+    """Phase three of run_audio_job: the files ``mine`` grouped by the rate they are written at (``rates``: {index: a rate
+    or None}), each group through ``run_micro_batches`` with keyed noise and per-file factors, then to the writers."""
+    from .mel_inverter import KeyedNoise
+    from .noise import item_key
     dims = inv.model.dims
     device_flac = fmt.lower() == "flac" and not have_soundfile()
-    # the files grouped by the rate they are written at (one group unless out_rate is "input")
     groups = {}
-    for local, ii in enumerate(mine):
-        rate = loaded[ii][1] if out_rate == "input" else out_rate
-        groups.setdefault(inv._output_rate(rate), []).append(local)
-    with ThreadPoolExecutor(max_workers=max(1, threads)) as writers:
-        pending = []
-        for rate, members in groups.items():
-            sub = [mine[local] for local in members]
-            write = _file_writer(inv, files, sub, scaled, output_dir, fmt, device_flac, inv.srate if rate is None else rate,
-                                 flac_compression, verbose, quiet, clock, log)
+    for ii in mine:
+        groups.setdefault(inv._output_rate(rates[ii]), []).append(ii)
+
+    def work():
+        for rate, sub in groups.items():
+            write = _file_writer(job, inv, files, sub, scaled, output_dir, fmt, device_flac, inv.srate if rate is None else rate,
+                                 flac_compression, verbose, quiet)
             noises = KeyedNoise(noise_seed, [item_key(files[ii]) for ii in sub]) if dims.noise_sigma else None
             rows = [np.full(int(scaled[ii].shape[1]), factors[ii], dtype=np.float32) for ii in sub]
             shifts = None if formants is None else [np.full(int(scaled[ii].shape[1]), formants[ii], dtype=np.float32) for ii in sub]
-            pending += [writers.submit(write, sb) for sb in run_micro_batches(
-                inv.model, [scaled[ii][0] for ii in sub], noises, max(1, batch), flac=device_flac,
-                host_audio=verbose or not device_flac, flac_compression=flac_compression, out_rate=rate, transpositions=rows,
-                formants=shifts, f0s=None if contours is None else [contours[ii] for ii in sub])]
-        for fu in pending:
-            fu.result()
-    if timings is not None:
-        timings.update(stats, read=clock.seconds.get("read", 0.0), scale=clock.seconds.get("scale", 0.0),
-                       device=clock.seconds.get("device_ms", 0.0) / 1e3, copy=clock.seconds.get("copy_ms", 0.0) / 1e3,
-                       write=clock.seconds.get("write", 0.0), wall=time.perf_counter() - t_start)
-    if verbose:
-        wall = time.perf_counter() - t_start
-        sec = clock.seconds
-        audio_s = sum(int(scaled[ii].shape[1]) for ii in mine) * inv.hop_size / inv.srate
-        in_s = sum(loaded[ii][0].size / loaded[ii][1] for ii in mine)
-        stretched = "" if all(maps[ii] is None for ii in mine) else f" (time-stretched from {in_s:.1f} s of input)"
-        if guides is not None:
-            stretched = f" (aligned to guides, from {in_s:.1f} s of input)"
-        print(f"transform_audio: {len(mine)} files, {audio_s:.1f} s of audio{stretched} in {wall:.2f} s wall ({audio_s / max(wall, 1e-9):.1f} "
-              f"x real time); read {sec.get('read', 0.0):.2f} s, upload {stats.get('upload', 0.0):.3f} s, resample "
-              f"{stats.get('resample', 0.0):.3f} s, analysis {stats.get('analysis', 0.0):.3f} s, "
-              + (f"f0 tracker {stats.get('f0', 0.0):.3f} s, " if tracked is not None else "") + "mel copy-back "
-              f"{stats.get('copy_back', 0.0):.3f} s, scale_mel {sec.get('scale', 0.0):.2f} s, noise+forward "
-              f"{sec.get('device_ms', 0.0) / 1e3:.3f} s, resample+encode+D2H {sec.get('copy_ms', 0.0) / 1e3:.3f} s, MD5+write "
-              f"{sec.get('write', 0.0):.2f} s (pool stages summed over {max(1, threads)} threads each)", file=sys.stderr)
-    return skipped
+            for sb in run_micro_batches(inv.model, [scaled[ii][0] for ii in sub], noises, max(1, batch), flac=device_flac,
+                                        host_audio=verbose or not device_flac, flac_compression=flac_compression, out_rate=rate,
+                                        transpositions=rows, formants=shifts,
+                                        f0s=None if contours is None else [contours[ii] for ii in sub]):
+                yield write, sb
+
+    job.write_all(work())
 
 
 def plan_audio_ranks(files, ranks, threads=2, stretches=None, frame_limit=None, guides=None):
@@ -651,9 +703,6 @@ def plan_audio_ranks(files, ranks, threads=2, stretches=None, frame_limit=None, 
     exceeds the engine's limit (``timemap.frame_count``) is skipped here, as ``run_audio_job`` would skip it.  ``guides``: per
     file None or the path of its guide (``run_audio_job``): an aligned file comes out with its guide's duration and is
     weighed by it; a guide that cannot be read skips the file."""
-    from . import timemap
-    from .analysis import resampled_length
-
     def seconds_of(item):
         path, factor, guide = item
         try:
@@ -663,9 +712,8 @@ def plan_audio_ranks(files, ranks, threads=2, stretches=None, frame_limit=None, 
                     snd, rate = read_sound(guide)
                 except (OSError, ValueError) as err:
                     raise ValueError(f"guide {guide}: {err}") from None
-            if frame_limit is not None and factor != 1.0:
-                hop, target, rows = frame_limit
-                timemap.frame_count(resampled_length(snd.size, rate, target), hop, target, factor, rows)
+            if frame_limit is not None:
+                check_stretch(snd.size, rate, factor, *frame_limit)
             return snd.size / rate
         except ValueError as err:
             return err

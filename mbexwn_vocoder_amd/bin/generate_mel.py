@@ -25,15 +25,16 @@ import os
 import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
+from functools import lru_cache
 
 test_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'mbexwn_vocoder_amd')
 if os.path.exists(test_path):
     sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
 
-from mbexwn_vocoder_amd import get_config_file, list_models  # noqa: E402
-from mbexwn_vocoder_amd import f0decode, f0track  # noqa: E402
+from mbexwn_vocoder_amd import cli, f0track, get_config_file  # noqa: E402
 from mbexwn_vocoder_amd.analysis import generate_mels  # noqa: E402
 from mbexwn_vocoder_amd.batched import f0_path  # noqa: E402
+from mbexwn_vocoder_amd.cli import file_guides, pitch_decode_params  # noqa: E402,F401
 from mbexwn_vocoder_amd.audioio import read_audio  # noqa: E402
 from mbexwn_vocoder_amd.config import ModelDims, read_config  # noqa: E402
 from mbexwn_vocoder_amd.fileio import save_var  # noqa: E402
@@ -43,17 +44,15 @@ from mbexwn_vocoder_amd.timemap import check_factor  # noqa: E402
 def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2, host=False, verbose=False, quiet=False,
          time_stretch=1.0, write_f0=False, f0_min=55.0, f0_max=1000.0, pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5,
          align_to=None, align_to_dir=None, align_band=1.0):
-    config_file = get_config_file(model_id_or_path=model_id)
-    config = read_config(config_file=config_file)
+    config = read_config(config_file=get_config_file(model_id_or_path=model_id))
     preprocess_config = config['preprocess_config']
     try:
         time_stretch = check_factor(time_stretch, "--time-stretch")
         # a stretched file is made for resynth_mel.py: held to the limit of the model's engine (sub-band rows per frame)
         rows_per_frame = ModelDims(config).steps_per_frame if time_stretch != 1.0 else 1
         f0_params = f0track.params(int(preprocess_config["sample_rate"]), f0_min=f0_min, f0_max=f0_max) if write_f0 else None
-        if pitch_decode not in ("greedy", "viterbi"):
-            raise ValueError(f"--pitch-decode must be greedy or viterbi, got {pitch_decode!r}")
-        f0_decode = f0decode.decode_params(w_jump=pitch_jump, w_switch=pitch_switch) if pitch_decode == "viterbi" else None
+        # (greedy: the weights are not looked at, as before there was a decoder)
+        f0_decode = None if pitch_decode == "greedy" else pitch_decode_params(pitch_decode, pitch_jump, pitch_switch)
         if f0_decode is not None and not write_f0:
             raise ValueError("--pitch-decode viterbi decodes the contour that --write-f0 writes: it needs --write-f0")
         guide_of = file_guides(input_audio_files, align_to, align_to_dir, align_band, time_stretch)
@@ -85,23 +84,12 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
             raise ValueError(f"{path}: no samples")
         return snd, rate, time.perf_counter() - t0
 
-    def write(path, data):
+    def timed(func, *args):
         t0 = time.perf_counter()
-        save_var(path, data)
+        func(*args)
         return time.perf_counter() - t0
 
-    def write_contour(path, times, f0, periodicity):
-        t0 = time.perf_counter()
-        f0track.write_f0(path, times, f0, periodicity)
-        return time.perf_counter() - t0
-
-    guide_cache = {}
-
-    def guide_sound(path):
-        if path not in guide_cache:
-            guide_cache[path] = read(path)[:2]
-        return guide_cache[path]
-
+    guide_sound = lru_cache(maxsize=None)(lambda path: read(path)[:2])           # a guide shared by many files is read once
     t_start = time.perf_counter()
     samples = 0
     unaligned = []
@@ -120,15 +108,13 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
             try:
                 tracked = [] if write_f0 else None
                 aligned = {}
-                guide_args = {}
-                if guide_of is not None:
-                    pairs = [guide_sound(guide_of[ff]) for ff in files]
-                    guide_args = {"guides": [pp[0] for pp in pairs], "guide_rates": [pp[1] for pp in pairs],
-                                  "align_band_s": align_band, "align_out": aligned}
+                pairs = [(None, None) if guide_of is None else guide_sound(guide_of[ff]) for ff in files]
                 mells = generate_mels([ll[0] for ll in loaded], [ll[1] for ll in loaded], preprocess_config, on_device=not host,
                                       batch=batch, stats=stats, rows_per_frame=rows_per_frame,
                                       time_maps=None if time_stretch == 1.0 else [time_stretch] * len(loaded),
-                                      f0_out=tracked, f0_params=f0_params, f0_decode=f0_decode, **guide_args)
+                                      f0_out=tracked, f0_params=f0_params, f0_decode=f0_decode,
+                                      guides=[pp[0] for pp in pairs], guide_rates=[pp[1] for pp in pairs],
+                                      align_band_s=align_band, align_out=aligned)
             except ValueError as err:
                 print(f"generate_mel::error:: {err}", file=sys.stderr)
                 sys.exit(1)
@@ -146,12 +132,12 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
                 if verbose:
                     print(f"    {ll[0].size} samples at {ll[1]} Hz -> {dd['mell'].shape[1]} frames, save under {outfile}",
                           file=sys.stderr)
-                written.append(writers.submit(write, outfile, dd))
+                written.append(writers.submit(timed, save_var, outfile, dd))
             for ff, contour in zip(files, tracked or []):
                 if contour is None:
                     continue
                 times = f0track.frame_times(contour[0].size, preprocess_config["hop_size"], preprocess_config["sample_rate"])
-                written.append(writers.submit(write_contour, f0_path(ff, output_dir), times, *contour))
+                written.append(writers.submit(timed, f0track.write_f0, f0_path(ff, output_dir), times, *contour))
         seconds["write"] = sum(fu.result() for fu in written)
     if verbose:
         wall = time.perf_counter() - t_start
@@ -164,21 +150,6 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
               + f"write {seconds['write']:.2f} s (read and write summed over {threads} threads each)", file=sys.stderr)
     if unaligned:
         sys.exit(1)
-
-
-def file_guides(files, align_to=None, align_to_dir=None, align_band=1.0, time_stretch=1.0):
-    """The guide of every file: ``align_to`` for all, or ``align_to_dir/<basename>``; None without either flag.  ValueError
-    for both flags, for a guide beside a time stretch, for a band that is not finite and positive."""
-    if align_to is None and align_to_dir is None:
-        return None
-    if align_to is not None and align_to_dir is not None:
-        raise ValueError("--align-to and --align-to-dir exclude each other")
-    if time_stretch != 1.0:
-        raise ValueError("--align-to / --align-to-dir set the timing of a file: not combinable with --time-stretch")
-    band = float(align_band)
-    if not (band > 0 and band != float("inf")):
-        raise ValueError(f"--align-band: a finite positive number of seconds is expected, got {align_band!r}")
-    return [align_to if align_to is not None else os.path.join(align_to_dir, os.path.basename(ff)) for ff in files]
 
 
 def make_parser():
@@ -239,10 +210,6 @@ if __name__ == "__main__":
     args = make_parser().parse_args()
 
     if not args.model_id:
-        print("Please select one of the following models.\nYou don't need to select with a full ID. "
-              "The first model containing the model_id you provide will be selected.")
-        for kk, ll in list_models().items():
-            for md in ll:
-                print(f" - {kk}/{md}")
+        cli.print_models()
     else:
         main(**vars(args))

@@ -27,14 +27,16 @@ test_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..',
 if os.path.exists(test_path):
     sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
 
-from mbexwn_vocoder_amd import list_models, mel_inverter  # noqa: E402
-from mbexwn_vocoder_amd.batched import write_audio  # noqa: E402,F401 -- the writer of the one-at-a-time loop
+from mbexwn_vocoder_amd import cli, mel_inverter  # noqa: E402
+from mbexwn_vocoder_amd.batched import load_contour, write_audio  # noqa: E402 -- the one-at-a-time loop's
+from mbexwn_vocoder_amd.noise import item_key  # noqa: E402
 from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 
 
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
          num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None,
          flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant_shift=None, f0_dir=None):
+    values = dict(locals())
     format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
     if flac_compression != "verbatim" and rank is None and not quiet:
         from mbexwn_vocoder_amd.batched import have_soundfile
@@ -43,19 +45,11 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
                   "by itself" if format.lower() == "flac" else f"the format is {format}"), file=sys.stderr)
     if gpus > 1 and rank is None:
         # --gpus N: this parent never initialises HIP; N fresh child processes write their share of the files each
-        from mbexwn_vocoder_amd.batched import run_ranks
-        argv = [model_id, "-i", *input_mell_files, "--format", format, "-nt", str(num_threads), "--batch", str(batch),
-                "--calibrate", str(calibrate), "--conv-form", conv_form, "--flac-compression", flac_compression]
-        argv += ["-o", output_dir] if output_dir else []
-        argv += ["--out-rate", str(out_rate)] if out_rate else []
-        argv += ["--noise-seed", str(noise_seed)] if noise_seed is not None else []
-        argv += ["--transposition", repr(transposition)] if transposition is not None else []
-        argv += ["--formant-shift", repr(formant_shift)] if formant_shift is not None else []
-        argv += ["--f0-dir", f0_dir] if f0_dir is not None else []
-        argv += [flag for flag, on in (("-g", use_gpu), ("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant))
-                 if on]
-        sys.exit(run_ranks(os.path.abspath(__file__), argv, model_id, input_mell_files, gpus, threads=num_threads,
-                           quiet=quiet))
+        # (the model is the positional; the files follow -i like any other option)
+        from mbexwn_vocoder_amd import batched
+        argv = cli.rank_argv(make_parser(), dict(values, format=format), [model_id])
+        sys.exit(batched.run_ranks(os.path.abspath(__file__), argv, model_id, input_mell_files, gpus, threads=num_threads,
+                                   quiet=quiet))
     import torch
     if not torch.cuda.is_available():
         print("resynth_mel::error:: no GPU available; this build has no CPU path", file=sys.stderr)
@@ -111,20 +105,13 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         log_mel_spectrogram = MelInv.scale_mel(dd, verbose=verbose)
 
         start_time = time.time()
-        control = {}
-        if noise_seed is not None:                   # keyed noise: a function of the seed, the file's basename and the step
-            from mbexwn_vocoder_amd.noise import item_key
-            control.update(noise_seed=noise_seed, noise_key=item_key(mell_file))
-        if transposition is not None:                # the factor on every mel frame, as run_job applies it
-            control.update(transposition=np.full(log_mel_spectrogram.shape[1], transposition, dtype=np.float32))
-        if formant_shift is not None and formant_shift != 1.0:       # (a factor of 1: the call without it, as run_job makes it)
-            control.update(formant=formant_shift)
-        if f0_dir is not None:                       # the file's own contour in place of the F0-net's; none voiced: the F0-net
-            from mbexwn_vocoder_amd.batched import load_contour
-            contour = load_contour(mell_file, f0_dir, log_mel_spectrogram.shape[1])
-            if contour is not None:
-                control.update(f0=contour)
-        syn_audio = MelInv.synth_from_mel(log_mel_spectrogram, **control)
+        # keyed noise: a function of the seed, the file's basename and the step; the factor on every mel frame, as run_job
+        # applies it (a formant factor of 1: the call without it); the file's own contour in place of the F0-net's (none
+        # voiced: the F0-net)
+        rows = None if transposition is None else np.full(log_mel_spectrogram.shape[1], transposition, dtype=np.float32)
+        contour = None if f0_dir is None else load_contour(mell_file, f0_dir, log_mel_spectrogram.shape[1])
+        syn_audio = MelInv.synth_from_mel(log_mel_spectrogram, noise_seed=noise_seed, noise_key=item_key(mell_file),
+                                          transposition=rows, formant=None if formant_shift == 1.0 else formant_shift, f0=contour)
         end_time = time.time()
 
         if verbose:                                  # reference :90-96
@@ -143,31 +130,11 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         write_audio(outfile, syn_audio, MelInv.srate if out_rate is None else out_rate, format, flac_compression)
 
 
-def positive_factor(text):
-    """argparse type of --transposition and --formant-shift: a finite positive factor."""
-    from argparse import ArgumentTypeError
-    try:
-        factor = float(text)
-    except ValueError:
-        factor = float("nan")
-    if not (np.isfinite(factor) and factor > 0):
-        raise ArgumentTypeError(f"a finite positive factor is expected, got {text!r}")
-    return factor
+positive_factor = cli.positive_arg("factor")
+positive_rate = cli.rate_arg()
 
 
-def positive_rate(text):
-    """argparse type of --out-rate: a positive whole number of Hz."""
-    from argparse import ArgumentTypeError
-    try:
-        rate = int(text)
-    except ValueError:
-        raise ArgumentTypeError(f"a sample rate in Hz is expected, got {text!r}") from None
-    if rate <= 0:
-        raise ArgumentTypeError(f"a sample rate must be positive, got {rate}")
-    return rate
-
-
-if __name__ == "__main__":
+def make_parser():
     from argparse import SUPPRESS, ArgumentParser
     parser = ArgumentParser(description="invert mel spectrograms into audio with an MBExWN model (MI355X HIP path)")
     parser.add_argument("model_id", default=None, nargs="?", const=None,
@@ -220,14 +187,12 @@ if __name__ == "__main__":
                              "the model's own F0; --transposition multiplies on top (Def: none)")
     parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
     parser.add_argument("--job", default=None, help=SUPPRESS)
-    args = parser.parse_args()
+    return parser
 
+
+if __name__ == "__main__":
+    args = make_parser().parse_args()
     if not args.model_id:
-        print("Please select one of the following models for mel inversion.\nYou don't need to select with a full ID. "
-              "The first model containing the model_id you provide will be selected.\nFor example just specifying SPEECH "
-              "will select the default SPEECH model.")
-        for kk, ll in list_models().items():
-            for md in ll:
-                print(f" - {kk}/{md}")
+        cli.print_models(" for mel inversion", "\nFor example just specifying SPEECH will select the default SPEECH model.")
     else:
         main(**vars(args))

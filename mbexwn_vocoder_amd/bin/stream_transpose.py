@@ -28,7 +28,7 @@ test_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..',
 if os.path.exists(test_path):
     sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
 
-from mbexwn_vocoder_amd import get_config_file, list_models  # noqa: E402
+from mbexwn_vocoder_amd import cli, get_config_file  # noqa: E402
 from mbexwn_vocoder_amd.audioio import read_audio  # noqa: E402
 from mbexwn_vocoder_amd.config import read_config  # noqa: E402
 from mbexwn_vocoder_amd.live import check_rate  # noqa: E402
@@ -143,18 +143,7 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
               file=sys.stderr)
 
 
-def output_rate_arg(text):
-    """argparse type of --output-rate: "input", or a positive whole number of Hz."""
-    from argparse import ArgumentTypeError
-    if text == "input":
-        return text
-    try:
-        rate = int(text)
-    except ValueError:
-        raise ArgumentTypeError(f"a sample rate in Hz or 'input' is expected, got {text!r}") from None
-    if rate <= 0:
-        raise ArgumentTypeError(f"a sample rate must be positive, got {rate}")
-    return rate
+output_rate_arg = cli.rate_arg(allow_input=True)
 
 
 if __name__ == "__main__":
@@ -198,10 +187,6 @@ if __name__ == "__main__":
     args = parser.parse_args()
 
     if not args.model_id:
-        print("Please select one of the following models.\nYou don't need to select with a full ID. "
-              "The first model containing the model_id you provide will be selected.")
-        for kk, ll in list_models().items():
-            for md in ll:
-                print(f" - {kk}/{md}")
+        cli.print_models()
     else:
         main(**vars(args))

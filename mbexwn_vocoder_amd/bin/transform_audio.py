@@ -53,13 +53,21 @@ unvoiced.  A frame whose pick alone would land an octave off no longer does.  Th
 import json
 import os
 import sys
+from functools import partial
 
 test_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'mbexwn_vocoder_amd')
 if os.path.exists(test_path):
     sys.path.insert(0, os.path.dirname(os.path.abspath(test_path)))
 
-from mbexwn_vocoder_amd import list_models  # noqa: E402
+from mbexwn_vocoder_amd import cli  # noqa: E402
 from mbexwn_vocoder_amd.batched import file_factors, file_stretches, read_transposition_file  # noqa: E402
+from mbexwn_vocoder_amd.cli import pitch_decode_params, weight_arg  # noqa: E402
+
+file_guides = partial(cli.file_guides, stretch_flags="--time-stretch or --time-stretch-file")
+factor_arg = stretch_arg = cli.positive_arg("factor")
+hertz_arg = cli.positive_arg("frequency in Hz")
+band_arg = cli.positive_arg("number of seconds")
+out_rate_arg = cli.rate_arg(allow_input=True)
 
 
 def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, transposition_file=None, noise_seed=0, batch=16,
@@ -68,70 +76,15 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
          formant_shift=1.0, formant_shift_file=None, f0_source="net", f0_min=55.0, f0_max=1000.0, write_f0=False,
          pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5, f0_fill="interpolate", f0_initial=150.0, align_to=None,
          align_to_dir=None, align_band=1.0):
+    values = dict(locals())
     try:
-        guides = file_guides(input_audio_files, align_to, align_to_dir, align_band, time_stretch, time_stretch_file)
-        if f0_source not in ("net", "audio"):
-            raise ValueError(f"--f0-source must be net or audio, got {f0_source!r}")
-        if not 0.0 < f0_min < f0_max:
-            raise ValueError(f"--f0-min must lie below --f0-max, got {f0_min} and {f0_max}")
-        if f0_fill not in ("interpolate", "hold"):
-            raise ValueError(f"--f0-fill must be interpolate or hold, got {f0_fill!r}")
-        if f0_fill == "hold" and f0_source != "audio":
-            raise ValueError("--f0-fill hold fills the tracked contour: it needs --f0-source audio")
-        f0_decode = pitch_decode_params(pitch_decode, pitch_jump, pitch_switch)
-        if f0_decode is not None and f0_source != "audio" and not write_f0:
-            raise ValueError("--pitch-decode viterbi decodes the tracked contour: it needs --f0-source audio or --write-f0")
-        table = read_transposition_file(transposition_file) if transposition_file else None
-        factors = file_factors(input_audio_files, transposition, table)
-        stretches = file_stretches(input_audio_files, time_stretch,
-                                   read_transposition_file(time_stretch_file) if time_stretch_file else None)
-        formants = file_factors(input_audio_files, formant_shift,
-                                read_transposition_file(formant_shift_file) if formant_shift_file else None, what="formant shift")
+        guides, f0_decode, factors, stretches, formants = file_options(values)
+        check_files(input_audio_files)
     except (OSError, ValueError) as err:
         print(f"transform_audio::error:: {err}", file=sys.stderr)
         sys.exit(1)
-    missing = [ff for ff in input_audio_files if not os.path.isfile(ff)]
-    if missing:
-        print(f"transform_audio::error:: no such file: {', '.join(missing)}", file=sys.stderr)
-        sys.exit(1)
-    names = [os.path.basename(ff) for ff in input_audio_files]
-    if len(set(names)) != len(names):
-        print("transform_audio::error:: two input files share a basename: they would share an output file and a noise key",
-              file=sys.stderr)
-        sys.exit(1)
     if gpus > 1 and rank is None:
-        # --gpus N: this parent never initialises HIP; N fresh child processes write their share of the files each
-        from mbexwn_vocoder_amd.batched import plan_audio_ranks, run_ranks
-        from mbexwn_vocoder_amd import get_config_file
-        from mbexwn_vocoder_amd.config import ModelDims, read_config
-        dims = ModelDims(read_config(config_file=get_config_file(model_id_or_path=model_id)))
-        plan = plan_audio_ranks(input_audio_files, gpus, threads=num_threads, stretches=stretches,
-                                frame_limit=(dims.hop_size, dims.sample_rate, dims.steps_per_frame), guides=guides)
-        for name, why in plan["skipped"]:
-            print(f"transform_audio::error:: skipped {name}: {why}", file=sys.stderr)
-        argv = [*plan["files"], "-o", output_dir, "--model_id", model_id, "--transposition", repr(float(transposition)),
-                "--noise-seed", str(noise_seed), "--batch", str(batch), "-nt", str(num_threads), "--format", format,
-                "--flac-compression", flac_compression, "--conv-form", conv_form]
-        argv += ["--transposition-file", transposition_file] if transposition_file else []
-        argv += ["--time-stretch", repr(float(time_stretch))] if time_stretch != 1.0 else []
-        argv += ["--time-stretch-file", time_stretch_file] if time_stretch_file else []
-        argv += ["--formant-shift", repr(float(formant_shift))] if formant_shift != 1.0 else []
-        argv += ["--formant-shift-file", formant_shift_file] if formant_shift_file else []
-        argv += ["--out-rate", str(out_rate)] if out_rate else []
-        argv += ["--align-to", align_to] if align_to else []
-        argv += ["--align-to-dir", align_to_dir] if align_to_dir else []
-        argv += ["--align-band", repr(float(align_band))] if guides is not None else []
-        argv += ["--f0-source", f0_source] if f0_source != "net" else []
-        argv += ["--f0-min", repr(float(f0_min)), "--f0-max", repr(float(f0_max))] if f0_source != "net" or write_f0 else []
-        argv += ["--write-f0"] if write_f0 else []
-        argv += ["--f0-fill", f0_fill, "--f0-initial", repr(float(f0_initial))] if f0_fill != "interpolate" else []
-        argv += ["--pitch-decode", pitch_decode] if pitch_decode != "greedy" else []
-        argv += ["--pitch-jump", repr(float(pitch_jump))] if pitch_jump != 4.0 else []
-        argv += ["--pitch-switch", repr(float(pitch_switch))] if pitch_switch != 0.5 else []
-        argv += [flag for flag, on in (("-v", verbose), ("-q", quiet), ("--batch-invariant", batch_invariant)) if on]
-        status = run_ranks(os.path.abspath(__file__), argv, model_id, plan["files"], gpus, threads=num_threads, quiet=quiet,
-                           plan=plan, tool="transform_audio") if plan["files"] else 0
-        sys.exit(1 if status or plan["skipped"] else 0)
+        sys.exit(run_parent(values, stretches, guides))
     import torch
     if not torch.cuda.is_available():
         print("transform_audio::error:: no GPU available; this build has no CPU path", file=sys.stderr)
@@ -165,95 +118,56 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
         sys.exit(1)
 
 
-def file_guides(files, align_to=None, align_to_dir=None, align_band=1.0, time_stretch=1.0, time_stretch_file=None):
-    """The guide of every file: ``align_to`` for all, or ``align_to_dir/<basename>``; None without either flag.  ValueError
-    for both flags, for a guide beside a time stretch, for a band that is not finite and positive."""
-    if align_to is None and align_to_dir is None:
-        return None
-    if align_to is not None and align_to_dir is not None:
-        raise ValueError("--align-to and --align-to-dir exclude each other")
-    if time_stretch != 1.0 or time_stretch_file:
-        raise ValueError("--align-to / --align-to-dir set the timing of a file: not combinable with --time-stretch or "
-                         "--time-stretch-file")
-    band_arg(str(align_band))
-    return [align_to if align_to is not None else os.path.join(align_to_dir, os.path.basename(ff)) for ff in files]
+def file_options(v):
+    """What ``main``'s arguments ``v`` say per file, checked: the guides (or None), the decode parameters (or None), the
+    transposition, time-stretch and formant-shift factors.  ValueError or OSError for what the tool refuses."""
+    files = v["input_audio_files"]
+    guides = file_guides(files, v["align_to"], v["align_to_dir"], v["align_band"], v["time_stretch"], v["time_stretch_file"])
+    if v["f0_source"] not in ("net", "audio"):
+        raise ValueError(f"--f0-source must be net or audio, got {v['f0_source']!r}")
+    if not 0.0 < v["f0_min"] < v["f0_max"]:
+        raise ValueError(f"--f0-min must lie below --f0-max, got {v['f0_min']} and {v['f0_max']}")
+    if v["f0_fill"] not in ("interpolate", "hold"):
+        raise ValueError(f"--f0-fill must be interpolate or hold, got {v['f0_fill']!r}")
+    if v["f0_fill"] == "hold" and v["f0_source"] != "audio":
+        raise ValueError("--f0-fill hold fills the tracked contour: it needs --f0-source audio")
+    f0_decode = pitch_decode_params(v["pitch_decode"], v["pitch_jump"], v["pitch_switch"])
+    if f0_decode is not None and v["f0_source"] != "audio" and not v["write_f0"]:
+        raise ValueError("--pitch-decode viterbi decodes the tracked contour: it needs --f0-source audio or --write-f0")
+
+    def table(path):
+        return read_transposition_file(path) if path else None
+
+    return (guides, f0_decode, file_factors(files, v["transposition"], table(v["transposition_file"])),
+            file_stretches(files, v["time_stretch"], table(v["time_stretch_file"])),
+            file_factors(files, v["formant_shift"], table(v["formant_shift_file"]), what="formant shift"))
 
 
-def band_arg(text):
-    """argparse type of --align-band: a finite positive number of seconds."""
-    from argparse import ArgumentTypeError
-    try:
-        value = float(text)
-    except ValueError:
-        value = float("nan")
-    if not (value > 0 and value != float("inf")):
-        raise ArgumentTypeError(f"a finite positive number of seconds is expected, got {text!r}")
-    return value
+def check_files(files):
+    """ValueError for a file that is not there and for two files with one basename."""
+    missing = [ff for ff in files if not os.path.isfile(ff)]
+    if missing:
+        raise ValueError(f"no such file: {', '.join(missing)}")
+    if len({os.path.basename(ff) for ff in files}) != len(files):
+        raise ValueError("two input files share a basename: they would share an output file and a noise key")
 
 
-def pitch_decode_params(pitch_decode, pitch_jump, pitch_switch):
-    """None for --pitch-decode greedy, else the ``f0decode.decode_params`` dictionary of the three flags."""
-    if pitch_decode not in ("greedy", "viterbi"):
-        raise ValueError(f"--pitch-decode must be greedy or viterbi, got {pitch_decode!r}")
-    from mbexwn_vocoder_amd import f0decode
-    dec = f0decode.decode_params(w_jump=pitch_jump, w_switch=pitch_switch)               # checked with either choice
-    return dec if pitch_decode == "viterbi" else None
-
-
-def weight_arg(text):
-    """argparse type of --pitch-jump and --pitch-switch: a weight in [0, 1e6]."""
-    from argparse import ArgumentTypeError
-    try:
-        value = float(text)
-    except ValueError:
-        value = float("nan")
-    if not 0.0 <= value <= 1e6:
-        raise ArgumentTypeError(f"a weight in 0 .. 1e6 is expected, got {text!r}")
-    return value
-
-
-def factor_arg(text):
-    """argparse type of --transposition and --formant-shift: a finite positive factor."""
-    from argparse import ArgumentTypeError
-    try:
-        file_factors(["x"], float(text))
-    except ValueError:
-        raise ArgumentTypeError(f"a finite positive factor is expected, got {text!r}") from None
-    return float(text)
-
-
-def hertz_arg(text):
-    """argparse type of --f0-min and --f0-max: a finite positive frequency in Hz."""
-    from argparse import ArgumentTypeError
-    try:
-        file_factors(["x"], float(text))
-    except ValueError:
-        raise ArgumentTypeError(f"a finite positive frequency in Hz is expected, got {text!r}") from None
-    return float(text)
-
-
-def stretch_arg(text):
-    """argparse type of --time-stretch: a finite positive factor."""
-    from argparse import ArgumentTypeError
-    try:
-        file_stretches(["x"], float(text))
-    except ValueError:
-        raise ArgumentTypeError(f"a finite positive factor is expected, got {text!r}") from None
-    return float(text)
-
-
-def out_rate_arg(text):
-    """argparse type of --out-rate: "input", or a positive whole number of Hz."""
-    from argparse import ArgumentTypeError
-    if text == "input":
-        return text
-    try:
-        rate = int(text)
-    except ValueError:
-        raise ArgumentTypeError(f"a sample rate in Hz or 'input' is expected, got {text!r}") from None
-    if rate <= 0:
-        raise ArgumentTypeError(f"a sample rate must be positive, got {rate}")
-    return rate
+def run_parent(v, stretches, guides):
+    """--gpus N: this parent never initialises HIP; N fresh child processes write their share of the files each.  Returns
+    the exit status of the job."""
+    from mbexwn_vocoder_amd import batched, get_config_file
+    from mbexwn_vocoder_amd.config import ModelDims, read_config
+    dims = ModelDims(read_config(config_file=get_config_file(model_id_or_path=v["model_id"])))
+    plan = batched.plan_audio_ranks(v["input_audio_files"], v["gpus"], threads=v["num_threads"], stretches=stretches,
+                                    frame_limit=(dims.hop_size, dims.sample_rate, dims.steps_per_frame), guides=guides)
+    for name, why in plan["skipped"]:
+        print(f"transform_audio::error:: skipped {name}: {why}", file=sys.stderr)
+    # the tracker's range travels with whatever tracks, also at its default
+    always = ("f0_min", "f0_max") if v["f0_source"] != "net" or v["write_f0"] else ()
+    argv = cli.rank_argv(make_parser(), v, plan["files"], always=always)
+    status = batched.run_ranks(os.path.abspath(__file__), argv, v["model_id"], plan["files"], v["gpus"],
+                               threads=v["num_threads"], quiet=v["quiet"], plan=plan, tool="transform_audio") if plan["files"] else 0
+    return 1 if status or plan["skipped"] else 0
 
 
 def make_parser():
@@ -356,10 +270,6 @@ def make_parser():
 if __name__ == "__main__":
     args = make_parser().parse_args()
     if not args.model_id:
-        print("Please select one of the following models.\nYou don't need to select with a full ID. "
-              "The first model containing the model_id you provide will be selected.")
-        for kk, ll in list_models().items():
-            for md in ll:
-                print(f" - {kk}/{md}")
+        cli.print_models()
     else:
         main(**vars(args))

@@ -1,0 +1,102 @@
+"""What the command-line tools under ``bin/`` share: argparse types, the guide and pitch-decode options, the model listing
+and the argv of a ``--gpus`` rank.  Plain functions; nothing here imports torch (the parent of a ``--gpus`` job never does)."""
+import os
+from argparse import ArgumentTypeError
+
+
+def _number(text):
+    try:
+        return float(text)
+    except ValueError:
+        return float("nan")
+
+
+def positive_arg(what):
+    """argparse type "a finite positive number"; ``what`` names it in the refusal: factor, frequency in Hz, number of seconds."""
+    def parse(text):
+        value = _number(text)
+        if not (value > 0 and value != float("inf")):
+            raise ArgumentTypeError(f"a finite positive {what} is expected, got {text!r}")
+        return value
+    return parse
+
+
+def rate_arg(allow_input=False):
+    """argparse type of an output rate: a positive whole number of Hz, with ``allow_input`` also the word "input"."""
+    words = "a sample rate in Hz or 'input'" if allow_input else "a sample rate in Hz"
+
+    def parse(text):
+        if allow_input and text == "input":
+            return text
+        try:
+            rate = int(text)
+        except ValueError:
+            raise ArgumentTypeError(f"{words} is expected, got {text!r}") from None
+        if rate <= 0:
+            raise ArgumentTypeError(f"a sample rate must be positive, got {rate}")
+        return rate
+    return parse
+
+
+def weight_arg(text):
+    """argparse type of --pitch-jump and --pitch-switch: a weight in [0, 1e6]."""
+    value = _number(text)
+    if not 0.0 <= value <= 1e6:
+        raise ArgumentTypeError(f"a weight in 0 .. 1e6 is expected, got {text!r}")
+    return value
+
+
+def file_guides(files, align_to=None, align_to_dir=None, align_band=1.0, time_stretch=1.0, time_stretch_file=None,
+                stretch_flags="--time-stretch"):
+    """The guide of every file: ``align_to`` for all, or ``align_to_dir/<basename>``; None without either flag.  ValueError
+    for both flags, for a guide beside a time stretch (``stretch_flags``: how the tool names what it excludes), for a band
+    that is not finite and positive."""
+    if align_to is None and align_to_dir is None:
+        return None
+    if align_to is not None and align_to_dir is not None:
+        raise ValueError("--align-to and --align-to-dir exclude each other")
+    if time_stretch != 1.0 or time_stretch_file:
+        raise ValueError(f"--align-to / --align-to-dir set the timing of a file: not combinable with {stretch_flags}")
+    band = float(align_band)
+    if not (band > 0 and band != float("inf")):
+        raise ValueError(f"--align-band: a finite positive number of seconds is expected, got {align_band!r}")
+    return [align_to if align_to is not None else os.path.join(align_to_dir, os.path.basename(ff)) for ff in files]
+
+
+def pitch_decode_params(pitch_decode, pitch_jump, pitch_switch):
+    """None for --pitch-decode greedy, else the ``f0decode.decode_params`` dictionary of the three flags."""
+    if pitch_decode not in ("greedy", "viterbi"):
+        raise ValueError(f"--pitch-decode must be greedy or viterbi, got {pitch_decode!r}")
+    from . import f0decode
+    dec = f0decode.decode_params(w_jump=pitch_jump, w_switch=pitch_switch)               # checked with either choice
+    return dec if pitch_decode == "viterbi" else None
+
+
+def print_models(purpose="", example=""):
+    """What a tool prints when ``model_id`` is given without a value: the known models."""
+    from . import list_models
+    print(f"Please select one of the following models{purpose}.\nYou don't need to select with a full ID. "
+          f"The first model containing the model_id you provide will be selected.{example}")
+    for kk, ll in list_models().items():
+        for md in ll:
+            print(f" - {kk}/{md}")
+
+
+def rank_argv(parser, values, files, drop=("gpus", "rank", "job"), always=()):
+    """The argv of a rank of a ``--gpus`` job, from the parser's own actions and ``values`` (``main``'s arguments by name): the
+    positionals are replaced by ``files``; every option whose value differs from its default -- and every one named in
+    ``always`` -- follows with its first option string, floats as ``repr(float)``, a list as one word per entry, a
+    store-true flag as the flag alone.  The options in ``drop`` are the parent's own."""
+    argv = [str(ff) for ff in files]
+    for action in parser._actions:
+        if not action.option_strings or action.dest in drop or action.dest not in values:
+            continue
+        value = values[action.dest]
+        if value == action.default and action.dest not in always:
+            continue
+        if action.nargs == 0:
+            argv += [action.option_strings[0]] if value else []
+            continue
+        words = value if isinstance(value, (list, tuple)) else [value]
+        argv += [action.option_strings[0], *(repr(float(ww)) if isinstance(ww, float) else str(ww) for ww in words)]
+    return argv

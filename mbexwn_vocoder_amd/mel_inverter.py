@@ -221,14 +221,14 @@ class MELInverter(object):
             raise ValueError(f"f0 must hold one value per mel frame ({T})")
         scale = None if transposition is None else rows(transposition, "transposition")
         # (a mel shorter than the synthesis was continued by one frame in _prepare: that frame repeats the last factor)
-        shift = {} if formant is None else {"formant": rows(np.concatenate((formant, formant[-1:]))[:T], "formant")}
+        shift = None if formant is None else rows(np.concatenate((formant, formant[-1:]))[:T], "formant")
         if scale is None or torch.is_tensor(scale):
-            audio = model.forward(mel, noise=noise, f0_frames=f0_rows, f0_scale=scale, **shift)
+            audio = model.forward(mel, noise=noise, f0_frames=f0_rows, f0_scale=scale, formant=shift)
         elif f0_rows is None:                                # a scalar: the whole-item option, as infer_components applies it
-            audio = model.forward(mel, noise=noise, transposition=float(scale), **shift)
+            audio = model.forward(mel, noise=noise, transposition=float(scale), formant=shift)
         else:
-            audio = model.forward(mel, noise=noise, f0_frames=f0_rows,
-                                  f0_scale=torch.full((B, T), float(scale), dtype=torch.float32, device=model.device), **shift)
+            audio = model.forward(mel, noise=noise, f0_frames=f0_rows, formant=shift,
+                                  f0_scale=torch.full((B, T), float(scale), dtype=torch.float32, device=model.device))
         if out_rate is not None:
             return self._to_rate(audio[:, :n_frames * self.hop_size], out_rate).cpu().numpy().ravel()
         return audio[:, :n_frames * self.hop_size].cpu().numpy().ravel()
@@ -358,40 +358,30 @@ class MELInverter(object):
 
         An item's audio is a function of (sound, rate, name, factor, stretch, formant, seed, out_rate): with a ``batch_invariant``
         engine or one pinned to a convolution form it does not depend on the batch, the order or the other items."""
-        from . import f0track, timemap
-        from .analysis import generate_mels
+        from . import align, timemap
+        from .batched import analyse_for_synthesis
         from .noise import item_key
         factors = check_factors(transposition, len(sounds))
         if not (len(sounds) == len(rates) == len(names)):
             raise ValueError("transform_audio: one rate and one name per sound")
         if formant is not None and (not isinstance(formant, (list, tuple)) or len(formant) != len(sounds)):
             raise ValueError("transform_audio: formant takes one entry per sound")
-        if f0_source not in F0_SOURCES:
-            raise ValueError(f"transform_audio: f0_source must be one of {F0_SOURCES}, got {f0_source!r}")
-        if f0_decode is not None and f0_source != "audio":
-            raise ValueError("transform_audio: f0_decode decodes the tracked contour and needs f0_source='audio'")
-        f0track.check_fill(f0_fill, f0_source, "transform_audio")
-        if f0_source == "audio":
-            f0_params = f0track.params(int(round(self.srate)), **(f0_params or {}))
-        maps = timemap.per_item(time_stretch, len(sounds), "transform_audio: time_stretch")
-        tracked = [] if f0_source == "audio" else None
-        guide_args = {}
-        if align_to is not None and any(gg is not None for gg in align_to):
-            if len(align_to) != len(sounds):
-                raise ValueError("transform_audio: align_to takes one entry per sound")
-            guide_args = {"guides": [None if gg is None else gg[0] for gg in align_to],
-                          "guide_rates": [None if gg is None else gg[1] for gg in align_to], "align_band_s": align_band_s}
-        dicts = generate_mels(sounds, rates, self.preprocess_config, on_device=True, batch=max_batch,
-                              time_maps=None if all(mm is None for mm in maps) else maps,
-                              rows_per_frame=self.model.dims.steps_per_frame, f0_out=tracked,
-                              f0_params=f0_params if tracked is not None else None, f0_decode=f0_decode, **guide_args)
-        scaled = [self.scale_mel(dd) for dd in dicts]
-        contours = None if tracked is None else [f0track.fill_tracked(ff, f0_fill, f0_initial) for ff, _ in tracked]
-        rows = [np.full(int(mm.shape[1]), ff, dtype=np.float32) for mm, ff in zip(scaled, factors)]
-        return self.synth_from_mels(scaled, max_batch=max_batch, max_padded_frames=max_padded_frames, flac=flac,
+        guided = align_to is not None and any(gg is not None for gg in align_to)
+        if guided and len(align_to) != len(sounds):
+            raise ValueError("transform_audio: align_to takes one entry per sound")
+        done = analyse_for_synthesis(self, sounds, rates, time_maps=timemap.per_item(time_stretch, len(sounds), "transform_audio: time_stretch"),
+                                     guides=[None if gg is None else gg[0] for gg in align_to] if guided else None,
+                                     guide_rates=[None if gg is None else gg[1] for gg in align_to] if guided else None,
+                                     align_band_s=align_band_s, f0_source=f0_source, f0_params=f0_params, f0_decode=f0_decode,
+                                     f0_fill=f0_fill, f0_initial=f0_initial, batch=max_batch, who="transform_audio")
+        for ii, mel in enumerate(done.scaled):
+            if mel is None:
+                raise align.AlignError(done.notes[ii]["error"])
+        rows = [np.full(int(mm.shape[1]), ff, dtype=np.float32) for mm, ff in zip(done.scaled, factors)]
+        return self.synth_from_mels(done.scaled, max_batch=max_batch, max_padded_frames=max_padded_frames, flac=flac,
                                     flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed,
                                     noise_keys=[item_key(nn) for nn in names], transpositions=rows, formants=formant,
-                                    f0s=contours)
+                                    f0s=done.contours)
 
     def track_f0(self, snd, srate, on_device=False, decode=None, **f0_params):
         """The pitch of a single sound (this build): (times in s, f0 in Hz with 0 = unvoiced, periodicity), one value per mel

@@ -244,7 +244,15 @@ def test_resynth_mel_and_stream_transpose_flags():
     params = inspect.signature(load_script("resynth_mel").main).parameters
     assert params["formant_shift"].default is None
     source = open(os.path.join(BIN, "resynth_mel.py")).read()
-    assert '"--formant-shift", repr(formant_shift)' in source and "formant=formant_shift" in source     # ranks, run_job
+    assert "formant=formant_shift" in source                                                            # run_job
+    from mbexwn_vocoder_amd import batched
+    tool, seen = load_script("resynth_mel"), []
+    with pytest.MonkeyPatch.context() as patch:                          # ranks: what the parent of a --gpus job sends
+        patch.setattr(batched, "run_ranks", lambda script, argv, *rest, **kw: seen.append(list(argv)) or 0)
+        with pytest.raises(SystemExit) as exc:
+            tool.main("model", ["a.mell"], "out", gpus=2, quiet=True, formant_shift=1.2)
+    assert exc.value.code == 0 and seen[0][seen[0].index("--formant-shift"):][:2] == ["--formant-shift", repr(1.2)]
+    assert tool.make_parser().parse_args(seen[0]).formant_shift == 1.2
     res = run_script("stream_transpose", ["--help"])
     assert res.returncode == 0 and "--formant-shift" in res.stdout
     tool = load_script("stream_transpose")

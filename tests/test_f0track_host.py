@@ -320,7 +320,15 @@ def test_resynth_mel_and_generate_mel_flags(tmp_path):
     params = inspect.signature(load_script("resynth_mel").main).parameters
     assert params["f0_dir"].default is None
     source = open(os.path.join(BIN, "resynth_mel.py")).read()
-    assert '"--f0-dir", f0_dir' in source and "f0_dir=f0_dir" in source and "load_contour(" in source       # ranks, run_job, single
+    assert "f0_dir=f0_dir" in source and "load_contour(" in source                                        # run_job, single
+    from mbexwn_vocoder_amd import batched
+    tool, seen = load_script("resynth_mel"), []
+    with pytest.MonkeyPatch.context() as patch:                          # ranks: what the parent of a --gpus job sends
+        patch.setattr(batched, "run_ranks", lambda script, argv, *rest, **kw: seen.append(list(argv)) or 0)
+        with pytest.raises(SystemExit) as exc:
+            tool.main("model", ["a.mell"], "out", gpus=2, quiet=True, f0_dir="contours")
+    assert exc.value.code == 0 and seen[0][seen[0].index("--f0-dir"):][:2] == ["--f0-dir", "contours"]
+    assert tool.make_parser().parse_args(seen[0]).f0_dir == "contours"
     res = run_script("generate_mel", ["--help"])
     assert res.returncode == 0 and all(flag in res.stdout for flag in ("--write-f0", "--f0-min", "--f0-max"))
     params = inspect.signature(load_script("generate_mel").main).parameters

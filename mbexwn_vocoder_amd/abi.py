@@ -1,5 +1,5 @@
 """ctypes binding of libmbexwn_hip.so: the structures and constants of include/mbexwn.h, and ONE table of every function the
-thirteen headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
+fourteen headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
 
 Nothing else lives here: a tool that only resamples imports this module, not the engine's driver.  The table is declared in
 Python (the package loads without include/ beside it); tests/test_abi_headers.py holds it to the headers name by name and
@@ -161,6 +161,13 @@ TABLE = {
         ("mbxc_decode_f0", i32, [vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp])],
     # rings, n_slots, ring_samples, desc, n_streams, max_new_frames, hop, sample_rate, window, tau_min, tau_max, ...
     "mbexwn_live_pitch.h": [("mbxt_f0_frames", i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp])],
+    # the streaming tracker's ring arguments, then mbxc_f0_candidates' rule (thresholds and weights are HOST pointers) and
+    # tables; tables, desc, n_streams, max_new_frames, hop, state, n_slots, lag, sample_rate, w_jump, w_switch, f0, periodicity, max_out
+    "mbexwn_live_contour.h": [
+        ("mbxv_f0_candidate_frames", i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, f32, P(f32), P(f32), i32, i32,
+                                           vp, vp, vp, vp]),
+        ("mbxv_lag_state_words", size_t, []),
+        ("mbxv_decode_f0_frames", i32, [vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, f32, vp, vp, i32, vp])],
     # mel_a, mel_b, n_frames_a, n_frames_b, batch, max_frames_a, max_frames_b, n_mels, band, cost, stream
     "mbexwn_align.h": [
         ("mbxg_local_cost", i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),

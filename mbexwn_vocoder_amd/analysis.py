@@ -236,7 +236,7 @@ def resampled_length(n, rate, target):
 
 
 def _plan_mels(sounds, rates, preprocess_config, time_maps, rows_per_frame, f0_out, f0_params, f0_decode, guides, guide_rates,
-               align_band_s, align_out):
+               align_band_s, align_out, f0_lag=None):
     """What :func:`generate_mels` decides before anything runs, and every refusal of the call: a namespace of the checked
     ``sounds`` and ``rates``, the F0 settings (``track``, ``f0_params`` resolved, ``f0_decode`` checked), ``warped`` {item:
     centres of its time map}, ``guided`` {item: (guide, rate)} with their ``band``, and ``align_out`` / ``failed``."""
@@ -255,6 +255,10 @@ def _plan_mels(sounds, rates, preprocess_config, time_maps, rows_per_frame, f0_o
         if f0_out is None:
             raise ValueError("generate_mels: f0_decode needs f0_out, the list the contours go to")
         f0decode.check_decode(f0_decode)
+    if f0_lag is not None:
+        if f0_decode is None:
+            raise ValueError("generate_mels: f0_lag is the look-ahead of the decoder and needs f0_decode")
+        f0_lag = f0decode.check_lag(f0_lag)
     if f0_out is not None:
         f0_params = f0track.check_params(dict(f0_params)) if f0_params is not None else f0track.params(target)
         if int(f0_params["sample_rate"]) != target:
@@ -282,7 +286,7 @@ def _plan_mels(sounds, rates, preprocess_config, time_maps, rows_per_frame, f0_o
             timemap._check_frames(float(frames_a), rows_per_frame)
     return SimpleNamespace(cfg=cfg, target=target, hop=hop, win_len=int(cfg.get("win_size", cfg["fft_size"])), sounds=sounds,
                            rates=rates, rows_per_frame=rows_per_frame, track=f0_out is not None, f0_params=f0_params,
-                           f0_decode=f0_decode, warped=warped, guided=guided, band=band, align_out=align_out, failed=set())
+                           f0_decode=f0_decode, f0_lag=f0_lag, warped=warped, guided=guided, band=band, align_out=align_out, failed=set())
 
 
 def _aligned_centres(plan, ii, nodes, cost, frames_a, frames_b, n_source):
@@ -332,7 +336,10 @@ def _analyse_host(plan, ii, stats):
         return mel[0], None
     t2 = time.perf_counter()
     cc = plan.warped[ii] if ii in plan.warped else timemap.centres(ss.size, plan.hop, plan.target, None)
-    if plan.f0_decode is not None:
+    if plan.f0_lag is not None:                             # what a live stream with this lag decides
+        tables = f0decode.candidates_host(*f0track.difference_host(ss, cc, plan.f0_params), plan.f0_params, plan.f0_decode)
+        pair = f0decode.viterbi_lag_host(*tables, int(plan.f0_params["sample_rate"]), plan.f0_decode, plan.f0_lag)
+    elif plan.f0_decode is not None:
         pair = f0decode.track_f0_viterbi_host(ss, cc, plan.f0_params, plan.f0_decode)
     else:
         pair = f0track.track_f0_host(ss, cc, plan.f0_params)
@@ -444,7 +451,11 @@ def _analyse_device(plan, micro_batch, guide_mel, stats):
     if marks:
         marks[3].record()
     if plan.track:                                          # the regular centres are t * hop: the analysis's own frames
-        if plan.f0_decode is not None:
+        if plan.f0_lag is not None:
+            tables = f0decode.candidates_device(snd, n_dev, table_dev, counts_dev, plan.f0_params, plan.f0_decode)
+            f0_dev, per_dev = f0decode.decode_lag_device(*tables, counts_dev, int(plan.f0_params["sample_rate"]), plan.f0_decode,
+                                                         plan.f0_lag)
+        elif plan.f0_decode is not None:
             f0_dev, per_dev = f0decode.track_f0_viterbi_device(snd, n_dev, table_dev, counts_dev, plan.f0_params, plan.f0_decode)
         else:
             f0_dev, per_dev = f0track.track_f0_device(snd, n_dev, table_dev, counts_dev, plan.f0_params)
@@ -468,7 +479,7 @@ def _analyse_device(plan, micro_batch, guide_mel, stats):
 
 def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None, time_maps=None, rows_per_frame=1,
                   f0_out=None, f0_params=None, f0_decode=None, guides=None, guide_rates=None, align_band_s=1.0,
-                  align_out=None):
+                  align_out=None, f0_lag=None):
     """Sounds -> ``.mell`` dictionaries (reference bin/generate_mel.py:54-64 for a list of files): ``sounds`` is a list of 1-D
     float32 arrays, ``rates`` their sample rates.  A sound that is not at the model rate goes through the reference's resampler
     (resample.py); one already at it skips that step.  Needs the ``preprocess_config`` alone: no engine, no weights.
@@ -496,6 +507,9 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     the decoded one: Viterbi over the YIN candidates of all its frames instead of the pick of every frame on its own (on
     the device ``mbxc_f0_candidates`` and ``mbxc_decode_f0`` in place of ``mbxp_track_f0``, else
     ``f0decode.track_f0_viterbi_host``: the same bits).  It needs ``f0_out``.  None makes exactly the launches of before.
+    ``f0_lag``: None, or a number of frames 0 .. 128: the decoder decides frame t from the frames up
+    to t + lag only, as a live stream opened with that lag does -- a file then has the stream's contour (on the device
+    ``mbxv_decode_f0_frames`` in place of ``mbxc_decode_f0``, else ``f0decode.viterbi_lag_host``).  It needs ``f0_decode``.
 
     ``guides``: None, or per sound None or a 1-D float32 array at ``guide_rates[i]``: the item takes the TIMING of its guide
     (align.py).  Guide and source go through the resampler and the regular analysis; the band costs
@@ -507,7 +521,7 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     None.  Given a dict, item i's ``align.path_stats`` go to ``align_out[i]``, and an item that cannot be aligned
     (``align.AlignError``) leaves ``{"error": message}`` there and None in the result (and in ``f0_out``) instead of raising."""
     plan = _plan_mels(sounds, rates, preprocess_config, time_maps, rows_per_frame, f0_out, f0_params, f0_decode, guides,
-                      guide_rates, align_band_s, align_out)
+                      guide_rates, align_band_s, align_out, f0_lag)
     results = [(None, None)] * len(plan.sounds)
     if not on_device:
         results = [_analyse_host(plan, ii, stats) for ii in range(len(plan.sounds))]

@@ -470,7 +470,7 @@ def read_sound(path):
 def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
                   quiet=False, flac_compression="verbatim", out_rate=None, stretches=None, formants=None, f0_source="net",
                   f0_params=None, write_f0=False, timings=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0,
-                  guides=None, align_band_s=1.0):
+                  guides=None, align_band_s=1.0, f0_lag=None):
     """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
     ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
 
@@ -496,7 +496,8 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     the tracked contour (0 = unvoiced) is written as NAME.f0 into ``output_dir``, with either source.  "net" without
     ``write_f0``: the launches and the bytes of before.  ``f0_decode``: None, or a ``f0decode.decode_params`` dictionary: the
     contour, used and written, is the Viterbi path over the YIN candidates of the file's frames (DESIGN.md section 6i);
-    it needs "audio" or ``write_f0``.  ``f0_fill``: "interpolate", or "hold" -- the causal fill of the live streams
+    it needs "audio" or ``write_f0``.  ``f0_lag``: None, or the decoder's look-ahead in frames: the
+    contour a live stream with that lag decides; it needs ``f0_decode``.  ``f0_fill``: "interpolate", or "hold" -- the causal fill of the live streams
     (``f0track.fill_hold`` with ``f0_initial`` Hz in front of the first voiced frame); it needs "audio".
     ``guides``: per file None or the path of a guide recording, None = none for all: file i comes out
     with the TIMING of its guide -- the guide's frame count, hence its length -- through ``generate_mels(guides=)`` with a
@@ -525,7 +526,7 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
                 guide_rates=[None if guides[ii] is None else guide_sounds[guides[ii]][1] for ii in mine] if have_guides else None,
                 align_band_s=align_band_s, f0_source=f0_source, f0_params=f0_params, f0_decode=f0_decode, f0_fill=f0_fill,
                 f0_initial=f0_initial, write_f0=bool(write_f0), batch=batch, stats=stats,
-                scale_map=lambda dicts: list(pool.map(scale, dicts)), who="run_audio_job")
+                scale_map=lambda dicts: list(pool.map(scale, dicts)), who="run_audio_job", f0_lag=f0_lag)
         except ValueError as err:
             if not have_guides:
                 raise
@@ -620,14 +621,16 @@ def _load_sounds(job, pool, inv, files, mine, guides, stretches):
 
 def analyse_for_synthesis(inv, sounds, rates, time_maps=None, guides=None, guide_rates=None, align_band_s=1.0, f0_source="net",
                           f0_params=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0, write_f0=None, batch=16,
-                          stats=None, scale_map=None, on_device=True, rows_per_frame=None, who="analyse_for_synthesis"):
+                          stats=None, scale_map=None, on_device=True, rows_per_frame=None, who="analyse_for_synthesis",
+                          f0_lag=None):
     """Sounds in, what the synthesis takes out: the step between reading and ``run_micro_batches``, the same code under
     ``MELInverter.transform_audio`` and :func:`run_audio_job`.  ``sounds`` at ``rates`` go through ``analysis.generate_mels``
     (``time_maps``, ``guides``, ``guide_rates``, ``align_band_s``, ``batch``, ``stats``, ``on_device`` and ``rows_per_frame``
     -- default: the engine's -- as there) and ``inv.scale_mel``; ``scale_map``: a function from the list of ``.mell``
     dictionaries to the list of scaled mels, for a caller with a thread pool.  The pitch options are checked before anything
     runs, ``who`` naming the caller: ``f0_source`` "net" or "audio", ``f0_params`` keywords of ``f0track.params``,
-    ``f0_decode`` None or ``f0decode.decode_params`` (it needs a tracked contour), ``f0_fill`` / ``f0_initial`` as
+    ``f0_decode`` None or ``f0decode.decode_params`` (it needs a tracked contour), ``f0_lag`` None or the decoder's fixed
+    lag in frames (it needs ``f0_decode``; ``analysis.generate_mels``), ``f0_fill`` / ``f0_initial`` as
     ``f0track.fill_tracked`` takes them; ``write_f0``: None for a caller without the option, else whether "net" tracks too.
 
     Returns a namespace: ``scaled`` (1, T, mel_channels), ``contours`` (filled; an item without a voiced frame: None; not
@@ -644,6 +647,8 @@ def analyse_for_synthesis(inv, sounds, rates, time_maps=None, guides=None, guide
     if f0_decode is not None and tracked is None:
         raise ValueError(f"{who}: f0_decode decodes the tracked contour and needs f0_source='audio'"
                          + ("" if write_f0 is None else " or write_f0"))
+    if f0_lag is not None and f0_decode is None:
+        raise ValueError(f"{who}: f0_lag is the look-ahead of the decoder and needs f0_decode")
     if tracked is not None:
         f0_params = f0track.params(int(round(inv.srate)), **(f0_params or {}))
     guided = guides is not None and any(gg is not None for gg in guides)
@@ -655,7 +660,7 @@ def analyse_for_synthesis(inv, sounds, rates, time_maps=None, guides=None, guide
                               rows_per_frame=inv.model.dims.steps_per_frame if rows_per_frame is None else rows_per_frame,
                               f0_out=tracked, f0_params=f0_params if tracked is not None else None, f0_decode=f0_decode,
                               guides=guides if guided else None, guide_rates=guide_rates if guided else None,
-                              align_band_s=align_band_s, align_out=notes if guided else None)
+                              align_band_s=align_band_s, align_out=notes if guided else None, f0_lag=f0_lag)
     keep = [ii for ii, dd in enumerate(dicts) if dd is not None]
     scale_map = scale_map or (lambda some: [inv.scale_mel(dd) for dd in some])
     scaled = [None] * len(dicts)

@@ -34,7 +34,7 @@ if os.path.exists(test_path):
 from mbexwn_vocoder_amd import cli, f0track, get_config_file  # noqa: E402
 from mbexwn_vocoder_amd.analysis import generate_mels  # noqa: E402
 from mbexwn_vocoder_amd.batched import f0_path  # noqa: E402
-from mbexwn_vocoder_amd.cli import file_guides, pitch_decode_params  # noqa: E402,F401
+from mbexwn_vocoder_amd.cli import file_guides, lag_arg, pitch_decode_params  # noqa: E402,F401
 from mbexwn_vocoder_amd.audioio import read_audio  # noqa: E402
 from mbexwn_vocoder_amd.config import ModelDims, read_config  # noqa: E402
 from mbexwn_vocoder_amd.fileio import save_var  # noqa: E402
@@ -43,7 +43,7 @@ from mbexwn_vocoder_amd.timemap import check_factor  # noqa: E402
 
 def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2, host=False, verbose=False, quiet=False,
          time_stretch=1.0, write_f0=False, f0_min=55.0, f0_max=1000.0, pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5,
-         align_to=None, align_to_dir=None, align_band=1.0):
+         align_to=None, align_to_dir=None, align_band=1.0, pitch_lag=None):
     config = read_config(config_file=get_config_file(model_id_or_path=model_id))
     preprocess_config = config['preprocess_config']
     try:
@@ -55,6 +55,8 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
         f0_decode = None if pitch_decode == "greedy" else pitch_decode_params(pitch_decode, pitch_jump, pitch_switch)
         if f0_decode is not None and not write_f0:
             raise ValueError("--pitch-decode viterbi decodes the contour that --write-f0 writes: it needs --write-f0")
+        if pitch_lag is not None and f0_decode is None:
+            raise ValueError("--pitch-lag is the look-ahead of the decoder: it needs --pitch-decode viterbi")
         guide_of = file_guides(input_audio_files, align_to, align_to_dir, align_band, time_stretch)
         if guide_of is not None:
             rows_per_frame = ModelDims(config).steps_per_frame
@@ -114,7 +116,7 @@ def main(input_audio_files, output_dir, model_id="VOICE", batch=1, num_threads=2
                                       time_maps=None if time_stretch == 1.0 else [time_stretch] * len(loaded),
                                       f0_out=tracked, f0_params=f0_params, f0_decode=f0_decode,
                                       guides=[pp[0] for pp in pairs], guide_rates=[pp[1] for pp in pairs],
-                                      align_band_s=align_band, align_out=aligned)
+                                      align_band_s=align_band, align_out=aligned, f0_lag=pitch_lag)
             except ValueError as err:
                 print(f"generate_mel::error:: {err}", file=sys.stderr)
                 sys.exit(1)
@@ -200,6 +202,9 @@ def make_parser():
                         help="viterbi: weight on the relative change of period between neighbouring frames (Def: %(default)s)")
     parser.add_argument("--pitch-switch", dest="pitch_switch", default=0.5, type=float, metavar="W",
                         help="viterbi: cost of a change between voiced and unvoiced (Def: %(default)s)")
+    parser.add_argument("--pitch-lag", dest="pitch_lag", default=None, type=lag_arg, metavar="N",
+                        help="--pitch-decode viterbi: decide every frame once N later frames are seen, 0 .. 128: the contour "
+                             "of a live stream with that lag (Def: the path over the whole file)")
     parser.add_argument("--host", action="store_true", help="numpy analysis and host resampler; needs no GPU")
     parser.add_argument("-v", "--verbose", action="store_true", help="display verbose progress info")
     parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")

@@ -4,7 +4,8 @@ pushes, as a live source would deliver it, and writes what the stream gives back
 
     stream_transpose.py in.wav -o out.wav --model_id VOICE --transposition 1.5 [--formant-shift F] [--tick-ms 80]
                         [--resample] [--output-rate R|input]
-                        [--f0-source audio [--f0-min HZ --f0-max HZ --f0-initial HZ] [--write-f0]]
+                        [--f0-source audio [--f0-min HZ --f0-max HZ --f0-initial HZ] [--write-f0]
+                         [--pitch-decode viterbi [--pitch-lag N --pitch-jump W --pitch-switch W]]]
 
 The demonstration of the live path (streaming mel analysis -> scale_mel -> streaming synthesis with per-frame pitch control).
 The input must be at the model's sample rate, unless ``--resample`` is given: then a file at another rate streams at its own
@@ -18,6 +19,12 @@ between ``--f0-min`` and ``--f0-max`` Hz and drives the oscillator with it, an u
 (``--f0-initial`` Hz in front of the first); ``--transposition`` multiplies on top.  The output is what ``transform_audio.py
 --f0-source audio --f0-fill hold`` writes for the file under the same ``--noise-seed``.  ``--write-f0`` writes the raw tracked
 rows as NAME.f0 beside the output (text rows `time_s f0_hz periodicity`, one per mel frame, 0 = unvoiced).
+
+``--pitch-decode viterbi`` decodes the tracked contour with a fixed lag of ``--pitch-lag`` frames (8
+frames are 100 ms at hop 300 / 24 kHz): a frame is decided, and synthesised, once that many later frames have been seen,
+which removes the octave jumps of the frame-by-frame pick at the price of that much more look-ahead.  The output -- and the
+contour ``--write-f0`` writes -- is then what ``transform_audio.py --f0-source audio --pitch-decode viterbi --pitch-lag N
+--f0-fill hold`` gives for the file under the same ``--noise-seed``.
 """
 import os
 import sys
@@ -35,16 +42,19 @@ from mbexwn_vocoder_amd.live import check_rate  # noqa: E402
 
 
 def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0, sample_rate=None, output_rate=None,
-                noise_fn=None, formant=None, f0_source="net", f0_params=None, f0_initial=150.0, f0_out=None):
+                noise_fn=None, formant=None, f0_source="net", f0_params=None, f0_initial=150.0, f0_out=None, f0_decode=None,
+                f0_lag=None):
     """Push `samples` in pieces of tick_samples, one tick per push, until the stream is finished; returns its audio.
     ``sample_rate``: the rate of `samples` when it is not the model's (the stream resamples); ``output_rate``: the rate the
     audio comes back at when it is not the model's (a rate in Hz, or "input"); ``noise_fn``: the stream's noise instead of the
     generator seeded with ``seed`` (``live.keyed_noise_fn``); ``formant``: a formant-shift factor given with every push; ``f0_source``,
-    ``f0_params``, ``f0_initial``: as for ``LiveResynthesizer.open``; ``f0_out``: a list that receives the stream's tracked
-    (f0, periodicity), one pair of arrays per tick that handed out rows."""
+    ``f0_params``, ``f0_initial``, ``f0_decode``, ``f0_lag``: as for ``LiveResynthesizer.open``; ``f0_out``: a list that
+    receives the stream's tracked (f0, periodicity), one pair of arrays per tick that handed out (with a lag: decided) rows."""
     rates = {} if sample_rate is None else {"sample_rate": sample_rate}
     if f0_source != "net":
         rates.update(f0_source=f0_source, f0_params=f0_params, f0_initial=f0_initial)
+    if f0_lag is not None:
+        rates.update(f0_decode=f0_decode, f0_lag=f0_lag)
 
     def tick():
         audio = live.tick().get(stream_id)
@@ -72,7 +82,7 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0,
 
 def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tick_ms=80.0, seed=0, quiet=False,
          resample=False, output_rate=None, noise_seed=None, formant_shift=1.0, f0_source="net", f0_min=55.0, f0_max=1000.0,
-         f0_initial=150.0, write_f0=False):
+         f0_initial=150.0, write_f0=False, pitch_decode="greedy", pitch_lag=8, pitch_jump=4.0, pitch_switch=0.5):
     preprocess_config = read_config(config_file=get_config_file(model_id_or_path=model_id))['preprocess_config']
     if not os.path.isfile(input_audio_file):
         print(f"stream_transpose::error:: no such file: {input_audio_file}", file=sys.stderr)
@@ -97,13 +107,17 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
             raise ValueError(f"--f0-source must be net or audio, got {f0_source!r}")
         if write_f0 and f0_source != "audio":
             raise ValueError("--write-f0 writes what the stream tracked: it needs --f0-source audio")
+        f0_decode = cli.pitch_decode_params(pitch_decode, pitch_jump, pitch_switch)
+        if f0_decode is not None and f0_source != "audio":
+            raise ValueError("--pitch-decode viterbi decodes what the stream tracked: it needs --f0-source audio")
+        f0_lag = None if f0_decode is None else cli.lag_arg(str(pitch_lag))
         f0_params = None
         if f0_source == "audio":
             from mbexwn_vocoder_amd import f0track
             f0_params = f0track.params(model_rate, f0_min=f0_min, f0_max=f0_max)
             if not (np.isfinite(f0_initial) and f0_initial > 0):
                 raise ValueError("--f0-initial must be finite and positive")
-    except ValueError as err:
+    except (ValueError, cli.ArgumentTypeError) as err:
         print(f"stream_transpose::error:: {err}", file=sys.stderr)
         sys.exit(1)
     import torch
@@ -124,7 +138,7 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
     audio = stream_file(live, samples, tick_samples, transposition, seed=seed, sample_rate=own_rate,
                         output_rate=out_rate if out_rate != model_rate else None,
                         formant=None if formant_shift == 1.0 else formant_shift, f0_source=f0_source, f0_params=f0_params,
-                        f0_initial=f0_initial, f0_out=tracked, **keyed)
+                        f0_initial=f0_initial, f0_out=tracked, f0_decode=f0_decode, f0_lag=f0_lag, **keyed)
     out_dir = os.path.dirname(os.path.abspath(output_file))
     os.makedirs(out_dir, exist_ok=True)
     ext = os.path.splitext(output_file)[1].lower().lstrip(".") or "wav"
@@ -139,14 +153,14 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
                          f0track.frame_times(f0.size, int(preprocess_config["hop_size"]), model_rate), f0, periodicity)
     if not quiet:
         print(f"{input_audio_file}: {samples.size} samples in pushes of {tick_samples} -> {audio.size} samples, transposed by "
-              f"{transposition}, look-ahead {live.lookahead_ms_for(own_rate, out_rate, f0_source, f0_params):.1f} ms, saved at {out_rate} Hz under {output_file}",
+              f"{transposition}, look-ahead {live.lookahead_ms_for(own_rate, out_rate, f0_source, f0_params, f0_lag):.1f} ms, saved at {out_rate} Hz under {output_file}",
               file=sys.stderr)
 
 
 output_rate_arg = cli.rate_arg(allow_input=True)
 
 
-if __name__ == "__main__":
+def make_parser():
     from argparse import ArgumentParser
     parser = ArgumentParser(description="transpose a sound file through the live path: streaming analysis and synthesis")
     parser.add_argument("input_audio_file", help="mono sound file at the model's sample rate (any rate with --resample)")
@@ -178,13 +192,26 @@ if __name__ == "__main__":
     parser.add_argument("--write-f0", dest="write_f0", action="store_true",
                         help="--f0-source audio: write the tracked rows as NAME.f0 beside the output: text rows `time_s f0_hz "
                              "periodicity`, one per mel frame, 0 = unvoiced")
+    parser.add_argument("--pitch-decode", dest="pitch_decode", default="greedy", choices=["greedy", "viterbi"],
+                        help="--f0-source audio: greedy = every frame's pick on its own; viterbi = one path over the YIN "
+                             "candidates, each frame decided --pitch-lag frames later: no octave jumps (Def: %(default)s)")
+    parser.add_argument("--pitch-lag", dest="pitch_lag", default=8, type=cli.lag_arg, metavar="N",
+                        help="--pitch-decode viterbi: frames of look-ahead of the decoder, 0 .. 128 (Def: %(default)s)")
+    parser.add_argument("--pitch-jump", dest="pitch_jump", default=4.0, type=cli.weight_arg, metavar="W",
+                        help="--pitch-decode viterbi: weight of a pitch jump between two frames (Def: %(default)s)")
+    parser.add_argument("--pitch-switch", dest="pitch_switch", default=0.5, type=cli.weight_arg, metavar="W",
+                        help="--pitch-decode viterbi: cost of a change between voiced and unvoiced (Def: %(default)s)")
     parser.add_argument("--seed", default=0, type=int, help="seed of the stream's noise generator (Def: %(default)s)")
     parser.add_argument("--noise-seed", dest="noise_seed", default=None, type=int, metavar="S",
                         help="draw the stream's noise keyed by (S, the file's basename) and the absolute step, as "
                              "transform_audio.py --noise-seed S does for the file; --seed is then unused (Def: the generator "
                              "seeded with --seed)")
     parser.add_argument("-q", "--quiet", action="store_true", help="dont display progress")
-    args = parser.parse_args()
+    return parser
+
+
+if __name__ == "__main__":
+    args = make_parser().parse_args()
 
     if not args.model_id:
         cli.print_models()

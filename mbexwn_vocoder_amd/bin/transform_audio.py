@@ -75,7 +75,7 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
          batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None,
          formant_shift=1.0, formant_shift_file=None, f0_source="net", f0_min=55.0, f0_max=1000.0, write_f0=False,
          pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5, f0_fill="interpolate", f0_initial=150.0, align_to=None,
-         align_to_dir=None, align_band=1.0):
+         align_to_dir=None, align_band=1.0, pitch_lag=None):
     values = dict(locals())
     try:
         guides, f0_decode, factors, stretches, formants = file_options(values)
@@ -108,7 +108,8 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
                                 stretches=None if all(ss == 1.0 for ss in stretches) else stretches,
                                 formants=None if all(ff == 1.0 for ff in formants) else formants, f0_source=f0_source,
                                 f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0, f0_decode=f0_decode,
-                                f0_fill=f0_fill, f0_initial=f0_initial, guides=guides, align_band_s=align_band)
+                                f0_fill=f0_fill, f0_initial=f0_initial, guides=guides, align_band_s=align_band,
+                                f0_lag=pitch_lag)
     except ValueError as err:
         if guides is None:
             raise
@@ -134,6 +135,8 @@ def file_options(v):
     f0_decode = pitch_decode_params(v["pitch_decode"], v["pitch_jump"], v["pitch_switch"])
     if f0_decode is not None and v["f0_source"] != "audio" and not v["write_f0"]:
         raise ValueError("--pitch-decode viterbi decodes the tracked contour: it needs --f0-source audio or --write-f0")
+    if v.get("pitch_lag") is not None and f0_decode is None:
+        raise ValueError("--pitch-lag is the look-ahead of the decoder: it needs --pitch-decode viterbi")
 
     def table(path):
         return read_transposition_file(path) if path else None
@@ -239,6 +242,10 @@ def make_parser():
                         help="viterbi: weight on the relative change of period between neighbouring frames (Def: %(default)s)")
     parser.add_argument("--pitch-switch", dest="pitch_switch", default=0.5, type=weight_arg, metavar="W",
                         help="viterbi: cost of a change between voiced and unvoiced (Def: %(default)s)")
+    parser.add_argument("--pitch-lag", dest="pitch_lag", default=None, type=cli.lag_arg, metavar="N",
+                        help="--pitch-decode viterbi: decide every frame once N later frames are seen, 0 .. 128, as "
+                             "stream_transpose.py --pitch-lag N does -- with --f0-fill hold the file then has the stream's "
+                             "samples (Def: the path over the whole file)")
     parser.add_argument("--noise-seed", dest="noise_seed", default=0, type=int, metavar="S",
                         help="seed of the keyed noise: a file's noise is a function of (S, its basename, the step) "
                              "(Def: %(default)s)")

@@ -1,7 +1,7 @@
 """What the command-line tools under ``bin/`` share: argparse types, the guide and pitch-decode options, the model listing
 and the argv of a ``--gpus`` rank.  Plain functions; nothing here imports torch (the parent of a ``--gpus`` job never does)."""
 import os
-from argparse import ArgumentTypeError
+from argparse import ArgumentTypeError  # noqa: F401  (the tools catch it by this name)
 
 
 def _number(text):
@@ -43,6 +43,17 @@ def weight_arg(text):
     value = _number(text)
     if not 0.0 <= value <= 1e6:
         raise ArgumentTypeError(f"a weight in 0 .. 1e6 is expected, got {text!r}")
+    return value
+
+
+def lag_arg(text):
+    """argparse type of --pitch-lag: the decoder's look-ahead, a whole number of frames in 0 .. 128."""
+    try:
+        value = int(text)
+    except ValueError:
+        value = -1
+    if not 0 <= value <= 128:
+        raise ArgumentTypeError(f"a whole number of frames in 0 .. 128 is expected, got {text!r}")
     return value
 
 

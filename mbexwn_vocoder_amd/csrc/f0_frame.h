@@ -1,7 +1,8 @@
-// The part the F0 tracker (f0_track.hip), its streaming form (f0_stream.hip) and the candidates kernel of the decoder
-// (f0_decode.hip) share: one 256-thread block loads a frame into LDS (f0_frame_load, with the kernel's own fetch) and leaves
-// its cumulative-mean-normalised difference function d' there (f0_frame_dprime; the host definition is
-// mbexwn_vocoder_amd/f0track.py::difference_host); the two trackers then share the pick (f0_frame_pick).
+// The part the F0 tracker (f0_track.hip), its streaming form (f0_stream.hip) and the candidates kernels of the decoder
+// (f0_decode.hip, and f0_lag.hip for streams) share: one 256-thread block loads a frame into LDS (f0_frame_load, with the
+// kernel's own fetch: F0RowFetch or F0RingFetch) and leaves its cumulative-mean-normalised difference function d' there
+// (f0_frame_dprime; the host definition is mbexwn_vocoder_amd/f0track.py::difference_host); the two
+// trackers then share the pick (f0_frame_pick), the two candidates kernels the candidates (f0_frame_candidates).
 //
 //   y[i]   = x[c - L/2 + i], 0 outside the item            L = W + tau_max, c = centres[b][k] clamped to [0, n_b]
 //   d[tau] = sum_j (y[s + j] - y[s + tau + j])^2           s = (tau_max - tau) >> 1, 0 <= j < W, 1 <= tau <= tau_max
@@ -15,6 +16,8 @@
 #include <cmath>
 
 #include <hip/hip_runtime.h>
+
+#include "mbx_kernels.h"
 
 #pragma clang fp contract(off)
 
@@ -44,7 +47,7 @@ __device__ inline float f0_lane_sum(float a) {
 }
 
 // The load of a frame into LDS: y[i] = fetch(i) for 0 <= i < L, where fetch(i) is sample c - L/2 + i of the sound or 0 outside
-// it -- the item's row (f0_track.hip, f0_decode.hip) or a stream's ring (f0_stream.hip); only the fetch differs between
+// it -- the item's row (f0_track.hip, f0_decode.hip) or a stream's ring (f0_stream.hip, f0_lag.hip); only the fetch differs between
 // them.  The whole block calls it.  Returns, on every thread, whether the frame touches a sample that is not finite or above
 // F0_SAMPLE_LIMIT.  Ends behind a __syncthreads().
 template <typename Fetch>
@@ -66,6 +69,20 @@ struct F0RowFetch {
     __device__ float operator()(int i) const {
         const long long s = first + i;
         return (s >= 0 && s < n) ? xb[s] : 0.f;
+    }
+};
+
+// the fetch from a stream's ring (sample s at ring[s & (ring_samples - 1)]) for the frame centred on c; n_total < 0: the
+// stream is still open and only the start is an edge.  "Outside" is decided from the index alone and never touches the ring
+struct F0RingFetch {
+    const float *ring;
+    long long mask, n_total, first;
+    __device__ F0RingFetch(const float *ring_, int ring_samples, long long n_total_, long long c, int L)
+        : ring(ring_), mask(ring_samples - 1), n_total(n_total_), first(c - (L >> 1)) {}
+    __device__ float operator()(int i) const {
+        const long long s = first + i;
+        if (s < 0 || (n_total >= 0 && s >= n_total)) return 0.f;
+        return ring[s & mask];
     }
 };
 
@@ -191,6 +208,115 @@ __device__ inline void f0_frame_pick(const float *d, int tau_min, int TM, float 
         f0 = 0.f;
         per = 1.f;
     }
+}
+
+// f0decode.py::candidates_host on the d' of a frame: per threshold the tracker's pick, the weight sums
+// per distinct lag, the n_cand heaviest lags by ascending lag in slots 0 .. 6 and "unvoiced" in slot 7, written to the three
+// tables at out .. out + 7.  ONE whole wave calls it (every lane active) behind f0_frame_dprime: every lane scans its lags
+// once and keeps, for each of the up to 16 ascending thresholds, the first lag below it; 16 first-index reductions over the
+// wave; lane n < N walks pick_n on to its local minimum; the weight sums P (per distinct lag, in ascending n) and U (no
+// pick), the ranks by counting, and lanes 0 .. 7 write the eight slots.  Thresholds from n_thresholds on are -inf.  The
+// offline kernel (f0_decode.hip) and the streaming one (f0_lag.hip) both end in it: same d', same bits.
+__device__ inline void f0_frame_candidates(const float *d, int tau_min, int TM, int bad, float energy, float e_min,
+                                           const float (&thresholds)[F0_MAX_THRESHOLDS], const float (&weights)[F0_MAX_THRESHOLDS],
+                                           int n_thresholds, int n_cand, long long out, float *period_out, float *cost_out,
+                                           float *dprime_out) {
+    const int lane = threadIdx.x & 63;
+    // per threshold the first lag below it, and the first lag of the minimum, over [lo, hi]: per lane, then over the wave
+    // (thresholds from n_thresholds on are -inf: nothing is below them)
+    const int lo = max(tau_min, 2), hi = TM - 1, N = n_thresholds;
+    int first[F0_MAX_THRESHOLDS];
+#pragma unroll
+    for (int nn = 0; nn < F0_MAX_THRESHOLDS; ++nn) first[nn] = INT_MAX;
+    int best = INT_MAX;
+    float best_v = INFINITY;
+    for (int tau = lo + lane; tau <= hi; tau += 64) {
+        const float v = d[tau];
+#pragma unroll
+        for (int nn = 0; nn < F0_MAX_THRESHOLDS; ++nn)
+            if (v < thresholds[nn] && first[nn] == INT_MAX) first[nn] = tau;
+        if (v < best_v) {
+            best_v = v;
+            best = tau;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int nn = 0; nn < F0_MAX_THRESHOLDS; ++nn) first[nn] = min(first[nn], __shfl_xor(first[nn], m, 64));
+        const float ov = __shfl_xor(best_v, m, 64);
+        const int oi = __shfl_xor(best, m, 64);
+        if (ov < best_v || (ov == best_v && oi < best)) {
+            best_v = ov;
+            best = oi;
+        }
+    }
+    // lane n < N: pick_n, walked on to its local minimum; INT_MAX is "no pick"
+    const bool usable = !bad && energy >= e_min;
+    int tau_n = INT_MAX;
+#pragma unroll
+    for (int nn = 0; nn < F0_MAX_THRESHOLDS; ++nn)
+        if (lane == nn) tau_n = first[nn];
+    if (!usable || lane >= N) tau_n = INT_MAX;
+    if (tau_n != INT_MAX)
+        while (tau_n + 1 <= hi && d[tau_n + 1] < d[tau_n]) ++tau_n;
+    // P of this lane's lag and U, both added in ascending n; the first lane with a lag leads it
+    float P = 0.f, U = 0.f;
+    int leader = tau_n != INT_MAX;
+#pragma unroll
+    for (int m = 0; m < F0_MAX_THRESHOLDS; ++m) {
+        const int tm = __shfl(tau_n, m, 64);
+        const float wm = weights[m];
+        if (m < N) {
+            if (tm == INT_MAX) {
+                U = U + wm;
+            } else if (tm == tau_n) {
+                P = P + wm;
+                if (m < lane) leader = 0;
+            }
+        }
+    }
+    // keep the n_cand leaders with the largest P (the smaller lag wins a tie), listed by ascending lag
+    int rank = 0;
+#pragma unroll
+    for (int m = 0; m < F0_MAX_THRESHOLDS; ++m) {
+        const int tm = __shfl(tau_n, m, 64), lm = __shfl(leader, m, 64);
+        const float pm = __shfl(P, m, 64);
+        if (lm && m != lane && (pm > P || (pm == P && tm < tau_n))) ++rank;
+    }
+    const int keep = leader && rank < n_cand;
+    int slot = 0;
+#pragma unroll
+    for (int m = 0; m < F0_MAX_THRESHOLDS; ++m) {
+        const int tm = __shfl(tau_n, m, 64), km = __shfl(keep, m, 64);
+        if (km && tm < tau_n) ++slot;
+    }
+    const int mine = keep ? slot : -1;
+    int w_tau = INT_MAX;
+    float w_P = 0.f;
+#pragma unroll
+    for (int m = 0; m < F0_MAX_THRESHOLDS; ++m) {
+        const int tm = __shfl(tau_n, m, 64), sm = __shfl(mine, m, 64);
+        const float pm = __shfl(P, m, 64);
+        if (sm == lane) {
+            w_tau = tm;
+            w_P = pm;
+        }
+    }
+    if (lane >= F0_SLOTS) return;
+    float period = 0.f, cost = INFINITY, dprime = 1.f;
+    if (lane == F0_SLOTS - 1) {
+        cost = fmaxf(1.f - U, 0.f);
+        if (!bad) dprime = best == INT_MAX ? d[lo] : best_v;
+    } else if (w_tau != INT_MAX) {
+        period = f0_refined_lag(d, w_tau);
+        cost = fmaxf(1.f - w_P, 0.f);
+        dprime = d[w_tau];
+    }
+    const long long o = out + lane;
+    period_out[o] = period;
+    cost_out[o] = cost;
+    dprime_out[o] = dprime;
 }
 
 }  // namespace mbx

@@ -30,17 +30,9 @@ __global__ __launch_bounds__(F0_THREADS) void f0_stream_kernel(PitchStreamArgs p
     const long long slot = dsc[0], n_total = dsc[3];
     if ((long long)blockIdx.x >= dsc[2] || slot < 0 || slot >= p.n_slots || dsc[1] < 0) return;
     const int W = p.window, TM = p.tau_max, L = W + TM;
-    const float *ring = p.rings + slot * p.ring_samples;
-    const long long mask = p.ring_samples - 1;
     long long c = (dsc[1] + blockIdx.x) * p.hop;
     if (n_total >= 0) c = min(c, n_total);
-    const long long first = c - (L >> 1);
-    auto fetch = [=](int i) {
-        const long long s = first + i;
-        if (s < 0 || (n_total >= 0 && s >= n_total)) return 0.f;        // outside the sound: never fetched
-        return ring[s & mask];
-    };
-    const int bad = f0_frame_load(fetch, L, f0_smem);
+    const int bad = f0_frame_load(F0RingFetch(p.rings + slot * p.ring_samples, p.ring_samples, n_total, c, L), L, f0_smem);
     f0_frame_dprime(W, TM, f0_smem, &s_energy);
     if (threadIdx.x >= 64) return;
     float f0, per;

@@ -483,6 +483,42 @@ struct DecodeArgs {
 const char *check_decode_f0(const DecodeArgs &a);
 void launch_decode_f0(const DecodeArgs &a, hipStream_t stream);
 
+// The decoded contour of sounds that are still arriving (f0_lag.hip; include/mbexwn_live_contour.h: mbxv_f0_candidate_frames,
+// mbxv_decode_f0_frames): the candidates of the new frames from the ring store, then the Viterbi
+// recursion continued from a state row per stream, frame t decided once frame t + lag is there; the host definition is
+// f0decode.py (viterbi_lag_host, LagDecoder)
+// the rule part of fill_f0_candidates: checks n_thresholds, n_cand and the HOST arrays, and fills th and ww (16 each)
+const char *fill_f0_rule(float *th, float *ww, int n_thresholds, int n_cand, const float *thresholds, const float *weights);
+struct CandidateStreamArgs {
+    PitchStreamArgs ring;        // rings .. e_min as for the streaming tracker; threshold, f0 and periodicity are not used
+    float thresholds[F0_MAX_THRESHOLDS];
+    float weights[F0_MAX_THRESHOLDS];
+    int n_thresholds, n_cand;
+    float *period, *cost, *dprime;               // (n_streams, max_new_frames, 8) each
+};
+const char *fill_f0_stream_candidates(CandidateStreamArgs &a, const float *thresholds, const float *weights);
+void launch_f0_stream_candidates(const CandidateStreamArgs &a, hipStream_t stream);
+
+constexpr int F0_MAX_LAG = 128;                  // f0decode.MAX_LAG
+constexpr int F0_LAG_CHUNK = 64;                 // frames of a sub-chunk: forward steps, then one decided frame per lane
+constexpr int F0_LAG_RING = 256;                 // frames of the ring, a power of two >= F0_MAX_LAG + 1 + F0_LAG_CHUNK
+// one stream's state, in 32-bit words: [0] done, [1] decided, [2 .. 9] delta, [10 .. 17] and [18 .. 25] periods and costs of
+// the last frame, [26 .. 31] zero; then per ring frame (index t & 255) the pointer word, 8 periods, 8 dprimes
+constexpr int F0_LAG_HEAD = 32;
+constexpr int F0_LAG_STATE_WORDS = F0_LAG_HEAD + F0_LAG_RING * (1 + 2 * F0_SLOTS);
+struct LagDecodeArgs {
+    const float *period, *cost, *dprime;         // (n_streams, max_new_frames, 8) each
+    const long long *desc;       // (n_streams, 4): slot, first_frame, n_frames, n_total (< 0: the stream is still open)
+    int n_streams, max_new_frames, hop;
+    unsigned *state;             // (n_slots, F0_LAG_STATE_WORDS)
+    int n_slots, lag, sample_rate;
+    float w_jump, w_switch;
+    float *f0, *periodicity;     // (n_streams, max_out) each; entries behind a stream's decided count are not written
+    int max_out;
+};
+const char *check_lag_decode(const LagDecodeArgs &a);
+void launch_lag_decode(const LagDecodeArgs &a, hipStream_t stream);
+
 // Timing alignment (mel_align.hip; include/mbexwn_align.h: mbxg_local_cost, mbxg_align_path): the quantised band costs of a
 // guide's and a source's log-mel, then a DTW path per item; the host definition is align.py (local_cost_host, path_host)
 constexpr int ALIGN_MAX_FRAMES = 65535;          // nodes * 16384 < 2^31

@@ -1,6 +1,6 @@
 // C ABI of the stages that take no engine handle: mbx_mel_analysis and mbx_encode_flac16 of include/mbexwn.h and the entry
-// points of the twelve headers beside it (mbxa_ resampler, mbxl_ / mbxr_ / mbxo_ live rings, mbxf_ FLAC, mbxn_ noise, mbxw_ mel
-// warp, mbxe_warp_envelope, mbxp_ tracker, mbxc_ decoder, mbxt_ streaming tracker, mbxg_ alignment; mbxe_forward takes a handle and is in
+// points of the thirteen headers beside it (mbxa_ resampler, mbxl_ / mbxr_ / mbxo_ live rings, mbxf_ FLAC, mbxn_ noise, mbxw_ mel
+// warp, mbxe_warp_envelope, mbxp_ tracker, mbxc_ decoder, mbxt_ streaming tracker, mbxv_ streaming decoder, mbxg_ alignment; mbxe_forward takes a handle and is in
 // mbx_api.hip).  Each one copies
 // its arguments into the kernel's struct, lets check_* (beside the kernel) refuse them, enqueues on the caller's stream and
 // reports the launch error.  A new entry point: prototype in its header, a row in abi.py's TABLE, the body here.
@@ -16,6 +16,7 @@
 #include "../../include/mbexwn_contour.h"
 #include "../../include/mbexwn_envelope.h"
 #include "../../include/mbexwn_live_pitch.h"
+#include "../../include/mbexwn_live_contour.h"
 #include "../../include/mbexwn_align.h"
 
 static_assert(MBXG_MAX_FRAMES == mbx::ALIGN_MAX_FRAMES && MBXG_MAX_BAND == mbx::ALIGN_MAX_BAND && MBXG_MAX_MELS == mbx::ALIGN_MAX_MELS,
@@ -350,6 +351,64 @@ mbx_status mbxt_f0_frames(const float *rings, int32_t n_slots, int32_t ring_samp
     a.periodicity = periodicity;
     if (const char *why = mbx::check_f0_stream(a)) return refuse("f0 frames", why);
     mbx::launch_f0_stream(a, static_cast<hipStream_t>(hip_stream));
+    return launch_status("kernel launch: ");
+}
+
+mbx_status mbxv_f0_candidate_frames(const float *rings, int32_t n_slots, int32_t ring_samples, const int64_t *desc,
+                                    int32_t n_streams, int32_t max_new_frames, int32_t hop, int32_t sample_rate, int32_t window,
+                                    int32_t tau_min, int32_t tau_max, float e_min, const float *thresholds, const float *weights,
+                                    int32_t n_thresholds, int32_t n_cand, float *period, float *cost, float *dprime,
+                                    void *hip_stream) {
+    mbx::CandidateStreamArgs a{};
+    a.ring.rings = rings;
+    a.ring.n_slots = n_slots;
+    a.ring.ring_samples = ring_samples;
+    a.ring.desc = reinterpret_cast<const long long *>(desc);
+    a.ring.n_streams = n_streams;
+    a.ring.max_new_frames = max_new_frames;
+    a.ring.hop = hop;
+    a.ring.sample_rate = sample_rate;
+    a.ring.window = window;
+    a.ring.tau_min = tau_min;
+    a.ring.tau_max = tau_max;
+    a.ring.e_min = e_min;
+    a.n_thresholds = n_thresholds;
+    a.n_cand = n_cand;
+    a.period = period;
+    a.cost = cost;
+    a.dprime = dprime;
+    if (const char *why = mbx::fill_f0_stream_candidates(a, thresholds, weights)) return refuse("f0 candidate frames", why);
+    if (n_streams == 0 || max_new_frames == 0) return MBX_OK;
+    mbx::launch_f0_stream_candidates(a, static_cast<hipStream_t>(hip_stream));
+    return launch_status("kernel launch: ");
+}
+
+size_t mbxv_lag_state_words(void) { return mbx::F0_LAG_STATE_WORDS; }
+
+mbx_status mbxv_decode_f0_frames(const float *period, const float *cost, const float *dprime, const int64_t *desc,
+                                 int32_t n_streams, int32_t max_new_frames, int32_t hop, void *state, int32_t n_slots,
+                                 int32_t lag, int32_t sample_rate, float w_jump, float w_switch, float *f0, float *periodicity,
+                                 int32_t max_out, void *hip_stream) {
+    mbx::LagDecodeArgs a{};
+    a.period = period;
+    a.cost = cost;
+    a.dprime = dprime;
+    a.desc = reinterpret_cast<const long long *>(desc);
+    a.n_streams = n_streams;
+    a.max_new_frames = max_new_frames;
+    a.hop = hop;
+    a.state = static_cast<unsigned *>(state);
+    a.n_slots = n_slots;
+    a.lag = lag;
+    a.sample_rate = sample_rate;
+    a.w_jump = w_jump;
+    a.w_switch = w_switch;
+    a.f0 = f0;
+    a.periodicity = periodicity;
+    a.max_out = max_out;
+    if (const char *why = mbx::check_lag_decode(a)) return refuse("decode f0 frames", why);
+    if (n_streams == 0) return MBX_OK;
+    mbx::launch_lag_decode(a, static_cast<hipStream_t>(hip_stream));
     return launch_status("kernel launch: ");
 }
 

@@ -150,19 +150,19 @@ def candidates_host(dp, energy, bad, prm, dec):
     return period, cost, dprime
 
 
-def viterbi_host(period, cost, dprime, sample_rate, dec, trace=None):
-    """Stage 2 (the module's docstring) on the (T, 8) tables of one item: ``(f0, periodicity)``, each (T,) float32.
-    ``trace``: a list that receives every frame's delta (8,), +inf at unavailable slots."""
-    check_decode(dec)
+def _checked_tables(name, period, cost, dprime, sample_rate):
     period, cost, dprime = (np.ascontiguousarray(aa, dtype=f32) for aa in (period, cost, dprime))
     if not (period.ndim == 2 and period.shape[1] == SLOTS and period.shape == cost.shape == dprime.shape):
-        raise ValueError(f"viterbi_host: three tables of shape (T, {SLOTS}), got {period.shape}, {cost.shape}, {dprime.shape}")
+        raise ValueError(f"{name}: three tables of shape (T, {SLOTS}), got {period.shape}, {cost.shape}, {dprime.shape}")
     if int(sample_rate) < 1:
-        raise ValueError(f"viterbi_host: sample_rate must be at least 1, got {sample_rate!r}")
+        raise ValueError(f"{name}: sample_rate must be at least 1, got {sample_rate!r}")
+    return period, cost, dprime
+
+
+def _forward(period, cost, dec, trace=None):
+    """The forward recursion of stage 2 on T >= 1 frames: the back pointers (T, 8) and every frame's best state -- the smallest
+    index of the minimum of its delta.  Frame t of both depends on the frames 0 .. t only."""
     T = period.shape[0]
-    f0, per = np.zeros(T, dtype=f32), np.zeros(T, dtype=f32)
-    if T == 0:
-        return f0, per
     w_jump, w_switch, inf = f32(dec["w_jump"]), f32(dec["w_switch"]), f32(np.inf)
     with np.errstate(all="ignore"):
         # what does not depend on the path, for all frames at once: availability, local costs, tr[t, i, j] from t - 1 to t
@@ -176,7 +176,9 @@ def viterbi_host(period, cost, dprime, sample_rate, dec, trace=None):
         tr[:, :, SLOTS - 1] = w_switch
         tr[:, SLOTS - 1, SLOTS - 1] = f32(0)
     back = np.zeros((T, SLOTS), dtype=np.int64)
+    best = np.zeros(T, dtype=np.int64)
     delta = np.where(avail[0], loc[0], inf).astype(f32)
+    best[0] = int(np.argmin(delta))
     if trace is not None:
         trace.append(delta.copy())
     with np.errstate(all="ignore"):
@@ -185,10 +187,25 @@ def viterbi_host(period, cost, dprime, sample_rate, dec, trace=None):
             back[t] = np.argmin(v, axis=0)                              # the first index of the minimum: strict <, ascending i
             new = np.where(avail[t], v.min(axis=0) + loc[t], inf).astype(f32)
             delta = new - new.min()
+            best[t] = int(np.argmin(delta))
             if trace is not None:
                 trace.append(delta.copy())
-        state = int(np.argmin(delta))
-        sr = f32(int(sample_rate))
+    return back, best
+
+
+def viterbi_host(period, cost, dprime, sample_rate, dec, trace=None):
+    """Stage 2 (the module's docstring) on the (T, 8) tables of one item: ``(f0, periodicity)``, each (T,) float32.
+    ``trace``: a list that receives every frame's delta (8,), +inf at unavailable slots."""
+    check_decode(dec)
+    period, cost, dprime = _checked_tables("viterbi_host", period, cost, dprime, sample_rate)
+    T = period.shape[0]
+    f0, per = np.zeros(T, dtype=f32), np.zeros(T, dtype=f32)
+    if T == 0:
+        return f0, per
+    back, best = _forward(period, cost, dec, trace)
+    state = best[T - 1]
+    sr = f32(int(sample_rate))
+    with np.errstate(all="ignore"):
         for t in range(T - 1, -1, -1):
             if state < SLOTS - 1:
                 f0[t] = sr / period[t, state]
@@ -202,6 +219,164 @@ def track_f0_viterbi_host(x, centres, prm, dec):
     Arguments and results as ``f0track.track_f0_host``, plus ``dec``: :func:`decode_params`."""
     dp, energy, bad = f0track.difference_host(x, centres, prm)
     return viterbi_host(*candidates_host(dp, energy, bad, prm, dec), int(prm["sample_rate"]), dec)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the fixed-lag decision (DESIGN.md section 6l): a stream decides frame t once frame t + lag has been seen
+# ------------------------------------------------------------------------------------------------------------------------
+MAX_LAG = 128                # mbxv_decode_f0_frames keeps a ring of 256 frames: lag + 1 behind a sub-chunk of 64
+
+
+def check_lag(lag):
+    """The look-ahead of the fixed-lag decoder in frames, as an int: ValueError for a bool, a non-integer or a value outside
+    0 .. 128."""
+    if isinstance(lag, (bool, np.bool_)) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= MAX_LAG:
+        raise ValueError(f"f0 decode: the lag must be an integer in 0 .. {MAX_LAG} frames, got {lag!r}")
+    return int(lag)
+
+
+def lag_frames_decided(done, lag, closed=False):
+    """Frames of a stream the fixed-lag decoder has decided once it has seen ``done`` of them: frame t waits for frame t +
+    lag while the stream is open; a closed stream has all of them (the rule beside ``live_plan.f0_frames_ready``)."""
+    return int(done) if closed else max(0, int(done) - int(lag))
+
+
+def viterbi_lag_host(period, cost, dprime, sample_rate, dec, lag):
+    """Stage 2 with a fixed lag, on the (T, 8) tables of one item: the forward recursion is :func:`viterbi_host`'s; frame t
+    takes the state the back pointers lead to from the best state of frame ``e = min(t + lag, T - 1)`` (the smallest index
+    of the minimum of delta_e), so it depends on the frames 0 .. t + lag only.  ``lag >= T - 1`` is :func:`viterbi_host`.
+    Returns ``(f0, periodicity)``, each (T,) float32."""
+    check_decode(dec)
+    lag = check_lag(lag)
+    period, cost, dprime = _checked_tables("viterbi_lag_host", period, cost, dprime, sample_rate)
+    T = period.shape[0]
+    f0, per = np.zeros(T, dtype=f32), np.zeros(T, dtype=f32)
+    if T == 0:
+        return f0, per
+    back, best = _forward(period, cost, dec)
+    sr = f32(int(sample_rate))
+    with np.errstate(all="ignore"):
+        for t in range(T):
+            e = min(t + lag, T - 1)
+            state = int(best[e])
+            for u in range(e, t, -1):
+                state = int(back[u, state])
+            if state < SLOTS - 1:
+                f0[t] = sr / period[t, state]
+            per[t] = dprime[t, state]
+    return f0, per
+
+
+class LagDecoder:
+    """:func:`viterbi_lag_host` as a state machine, and the definition of the state ``mbxv_decode_f0_frames`` keeps per
+    stream: ``done`` frames seen, ``decided`` of them handed out, ``delta`` (8) of the last frame, that frame's periods and
+    costs, and of the last ``lag + 1`` frames the pointer word (eight 3-bit back pointers and, from bit 24, the frame's best
+    state), the periods and the dprimes.  The concatenated results of ``push`` are ``viterbi_lag_host`` of the concatenated
+    tables, however they were cut."""
+
+    def __init__(self, sample_rate, dec, lag):
+        check_decode(dec)
+        if int(sample_rate) < 1:
+            raise ValueError(f"LagDecoder: sample_rate must be at least 1, got {sample_rate!r}")
+        self.lag, self.sample_rate = check_lag(lag), int(sample_rate)
+        self.w_jump, self.w_switch = f32(dec["w_jump"]), f32(dec["w_switch"])
+        self.done = self.decided = 0
+        self.delta = np.zeros(SLOTS, dtype=f32)
+        self.prev_period, self.prev_cost = np.zeros(SLOTS, dtype=f32), np.zeros(SLOTS, dtype=f32)
+        self.words, self.periods, self.dprimes = {}, {}, {}      # frame -> word, (8,), (8,): the last lag + 1 frames
+
+    @staticmethod
+    def _available(period, cost):
+        c_ok = (cost >= 0) & (cost <= LIMIT)
+        avail = c_ok & (period >= 1) & (period <= LIMIT)
+        avail[SLOTS - 1] = True
+        return avail, np.where(c_ok, cost, f32(0)).astype(f32)
+
+    def _step(self, period, cost):
+        inf = f32(np.inf)
+        avail, loc = self._available(period, cost)
+        word = 0
+        if self.done == 0:
+            delta = np.where(avail, loc, inf).astype(f32)
+        else:
+            before, _ = self._available(self.prev_period, self.prev_cost)
+            pi, pj = self.prev_period[:, None], period[None, :]
+            tr = (self.w_jump * (np.abs(pj - pi) / (pj + pi))).astype(f32)
+            tr[SLOTS - 1, :] = self.w_switch
+            tr[:, SLOTS - 1] = self.w_switch
+            tr[SLOTS - 1, SLOTS - 1] = f32(0)
+            v = np.where(before[:, None], self.delta[:, None] + np.where(before[:, None], tr, f32(0)), inf)
+            arg = np.argmin(v, axis=0)
+            new = np.where(avail, v.min(axis=0) + loc, inf).astype(f32)
+            delta = new - new.min()
+            word = sum(int(arg[j]) << (3 * j) for j in range(SLOTS) if avail[j])
+        self.delta, self.prev_period, self.prev_cost = delta, period.copy(), cost.copy()
+        return word | int(np.argmin(delta)) << 24
+
+    def push(self, period, cost, dprime, last=False):
+        """The tables (n, 8) of the next n >= 0 frames; ``last``: no frame follows.  Returns ``(f0, periodicity)`` of the
+        frames that became decided: those below ``lag_frames_decided(done, lag, last)``."""
+        period, cost, dprime = _checked_tables("LagDecoder.push", period, cost, dprime, self.sample_rate)
+        with np.errstate(all="ignore"):
+            for row in range(period.shape[0]):
+                t = self.done
+                self.words[t], self.periods[t], self.dprimes[t] = self._step(period[row], cost[row]), period[row].copy(), dprime[row].copy()
+                self.done = t + 1
+            target = max(self.decided, lag_frames_decided(self.done, self.lag, last))
+            f0, per = np.zeros(target - self.decided, dtype=f32), np.zeros(target - self.decided, dtype=f32)
+            sr = f32(self.sample_rate)
+            for t in range(self.decided, target):
+                e = min(t + self.lag, self.done - 1)
+                state = self.words[e] >> 24
+                for u in range(e, t, -1):
+                    state = (self.words[u] >> (3 * state)) & 7
+                if state < SLOTS - 1:
+                    f0[t - self.decided] = sr / self.periods[t][state]
+                per[t - self.decided] = self.dprimes[t][state]
+        self.decided = target
+        for store in (self.words, self.periods, self.dprimes):          # what no later frame reads
+            for t in [t for t in store if t < self.done - self.lag - 1]:
+                del store[t]
+        return f0, per
+
+
+def decode_lag_device(period, cost, dprime, n_frames, sample_rate, dec, lag):
+    """:func:`viterbi_lag_host` on the GPU for a ragged batch (``mbxv_decode_f0_frames``, include/mbexwn_live_contour.h, on
+    fresh zero states: every item is a stream that is pushed once and closed): tensors as for :func:`decode_device`, of any
+    length -- the kernel keeps a ring of frames, not the item.  Returns two cuda tensors (batch, max_frames), f0 and
+    periodicity; rows from ``n_frames[b]`` on stay zero.  No engine, current stream."""
+    import ctypes
+    import torch
+    from .abi import _check, load_library
+    check_decode(dec)
+    lag = check_lag(lag)
+    if not torch.is_tensor(period) or period.dim() != 3 or int(period.shape[2]) != SLOTS or period.dtype != torch.float32 or not period.is_cuda:
+        raise ValueError(f"period must be a float32 cuda tensor of shape (batch, max_frames, {SLOTS})")
+    dev = period.device
+    for name, tt in (("cost", cost), ("dprime", dprime)):
+        if not torch.is_tensor(tt) or tt.dtype != torch.float32 or tt.shape != period.shape or tt.device != dev:
+            raise ValueError(f"{name} must be a float32 tensor with the shape and device of period")
+    B, frames = int(period.shape[0]), int(period.shape[1])
+    if not torch.is_tensor(n_frames) or n_frames.dtype != torch.int32 or tuple(n_frames.shape) != (B,) or n_frames.device != dev:
+        raise ValueError("n_frames must be an int32 tensor of shape (batch,) on the device of period")
+    if int(sample_rate) < 1:
+        raise ValueError(f"decode_lag_device: sample_rate must be at least 1, got {sample_rate!r}")
+    period, cost, dprime = period.contiguous(), cost.contiguous(), dprime.contiguous()
+    f0 = torch.zeros((B, frames + lag), dtype=torch.float32, device=dev)
+    per = torch.zeros((B, frames + lag), dtype=torch.float32, device=dev)
+    if B == 0 or frames == 0:
+        return f0[:, :frames].contiguous(), per[:, :frames].contiguous()
+    lib = load_library()
+    counts = n_frames.to(torch.int64).clamp(0, frames)
+    # every item is its own stream: slot b, first frame 0, all its frames, and n_total = T - 1 with hop 1 closes it
+    desc = torch.stack([torch.arange(B, device=dev), torch.zeros_like(counts), counts, counts - 1], dim=1).contiguous()
+    state = torch.zeros((B, int(lib.mbxv_lag_state_words())), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.mbxv_decode_f0_frames(period.data_ptr(), cost.data_ptr(), dprime.data_ptr(), desc.data_ptr(), B, frames, 1,
+                                         state.data_ptr(), B, lag, int(sample_rate), ctypes.c_float(float(dec["w_jump"])),
+                                         ctypes.c_float(float(dec["w_switch"])), f0.data_ptr(), per.data_ptr(), frames + lag,
+                                         torch.cuda.current_stream(dev).cuda_stream))
+    return f0[:, :frames].contiguous(), per[:, :frames].contiguous()
 
 
 def _host_tables(dec):

@@ -188,7 +188,16 @@ class StreamingAnalyzer(_Stage):
     ``last_f0`` -- {stream_id: (f0, periodicity)}, float32, one value per mel row handed out, 0 = unvoiced.  Concatenated they
     are ``f0track.track_f0_host(sound, arange(0, n + 1, hop), P)`` bit for bit.  The tracker reads the model-rate ring, so a
     resampled stream needs nothing special.  All tracking streams of an analyzer share one P.  A tick without tracking
-    streams makes the launches it made before and no others."""
+    streams makes the launches it made before and no others.
+
+    ``open(stream_id, f0_params=P, f0_lag=N, f0_decode=D)`` gives a tracking stream whose contour is DECODED with a fixed lag
+    of N frames (csrc/f0_lag.hip, include/mbexwn_live_contour.h; D: an ``f0decode.decode_params``
+    dictionary, None: the defaults).  Mel rows and readiness are those of a tracking stream.  In place of ``mbxt_f0_frames``
+    the tick launches ``mbxv_f0_candidate_frames`` and ``mbxv_decode_f0_frames`` on the same descriptor table; the candidate
+    tables stay on the device, and so does a state row per slot.  ``last_f0[stream_id]`` holds the frames DECIDED in the tick
+    -- ``f0decode.lag_frames_decided`` of the frames seen, all of them at the stream's end; a stream with none is absent --
+    so it trails the mel rows by N frames until the closing tick.  Concatenated they are ``f0decode.viterbi_lag_host`` of
+    ``candidates_host`` on the whole sound, bit for bit.  All tracking streams of an analyzer share one (P, D, N)."""
 
     def __init__(self, preprocess_config, device=None, ring_samples=None, slots=16, input_ring_samples=None):
         cfg = preprocess_config
@@ -207,20 +216,31 @@ class StreamingAnalyzer(_Stage):
         self._tables = None
         self._stage_host = self._stage_dev = None     # one tick's descriptors and samples: pinned, and its device twin
         self.f0_params = None         # the parameters of the tracking streams: set by the first one opened
+        self.f0_decode = self.f0_lag = None           # ... and their decoder's and its lag, when they decode (section 6l)
+        self._lag_state = None        # (slots, mbxv_lag_state_words()) int32 on the device: a decoder state per ring slot
+        self._cand = None             # one tick's three candidate tables, on the device only
         self.last_f0 = {}             # {stream_id: (f0, periodicity)} of the last tick's rows of the tracking streams
 
     input_ring_samples = property(lambda self: self._in_store.ring_samples)
     input_rings = property(lambda self: self._in_store.rings)   # None until the first tick with a resampled stream
 
     # -- host side ----------------------------------------------------------------------------------------------------
-    def open(self, stream_id, sample_rate=None, f0_params=None, f0_decode=None):
+    def open(self, stream_id, sample_rate=None, f0_params=None, f0_decode=None, f0_lag=None):
         """Open a stream; ``sample_rate``: the rate its pushes will be at (None or the model's: no resampling);
-        ``f0_params``: an ``f0track.params`` dictionary at the model rate -- the stream tracks its F0 (``last_f0``)."""
+        ``f0_params``: an ``f0track.params`` dictionary at the model rate -- the stream tracks its F0 (``last_f0``);
+        ``f0_lag``: frames of look-ahead (0 .. 128) -- the stream decodes its contour with that lag, by ``f0_decode``, an
+        ``f0decode.decode_params`` dictionary (None: the defaults)."""
         if stream_id in self.streams:
             raise ValueError(f"stream {stream_id!r} is open already")
-        if f0_decode is not None:
+        if f0_decode is not None and f0_lag is None:
             raise ValueError(f"stream {stream_id!r}: f0_decode decodes the contour over the whole sound (f0decode.py), which a "
                              "stream does not have; streams track every frame on its own")
+        if f0_lag is not None:
+            from .f0decode import check_decode, check_lag, decode_params
+            if f0_params is None:
+                raise ValueError(f"stream {stream_id!r}: f0_lag is the look-ahead of a stream that tracks its F0: give f0_params")
+            f0_lag = check_lag(f0_lag)
+            f0_decode = decode_params() if f0_decode is None else check_decode(dict(f0_decode))
         f0_len = None
         if f0_params is not None:
             from .f0track import check_params
@@ -228,9 +248,12 @@ class StreamingAnalyzer(_Stage):
             if int(f0_params["sample_rate"]) != self.model_rate:
                 raise ValueError(f"stream {stream_id!r}: f0_params are for {f0_params['sample_rate']} Hz, the tracker reads the "
                                  f"model-rate samples at {self.model_rate} Hz")
-            if self.f0_params is not None and f0_params != self.f0_params and any(
-                    st.f0_len is not None for st in self.streams.values()):
-                raise ValueError(f"stream {stream_id!r}: the tracking streams of an analyzer share one set of f0_params")
+            if self.f0_params is not None and any(st.f0_len is not None for st in self.streams.values()):
+                if f0_params != self.f0_params:
+                    raise ValueError(f"stream {stream_id!r}: the tracking streams of an analyzer share one set of f0_params")
+                if f0_lag != self.f0_lag or not _same_decode(f0_decode, self.f0_decode):
+                    raise ValueError(f"stream {stream_id!r}: the tracking streams of an analyzer share one f0_decode and one "
+                                     f"f0_lag (open: lag {self.f0_lag!r})")
             f0_len = int(f0_params["window"]) + int(f0_params["tau_max"])
         rate, filt = None, None
         if sample_rate is not None:
@@ -243,7 +266,7 @@ class StreamingAnalyzer(_Stage):
         self.streams[stream_id] = (_AStream(slot, f0_len=f0_len) if rate is None else
                                    _AStream(slot, rate, self._in_store.take(), filt, f0_len=f0_len))
         if f0_len is not None:
-            self.f0_params = f0_params
+            self.f0_params, self.f0_decode, self.f0_lag = f0_params, f0_decode, f0_lag
             self._store.at_least(f0_len)        # the tracker's frame must fit the ring
 
     def close(self, stream_id):
@@ -294,6 +317,8 @@ class StreamingAnalyzer(_Stage):
         for sid, nn in plan.rows:
             st = self.streams[sid]
             st.on_device, st.in_on_device, st.queue, st.fresh = st.have, st.in_have, [], False
+            if st.f0_len is not None and self.f0_lag is not None:
+                st.f0_decided = self._decided_after(st, nn)
             st.emitted += nn
 
     # -- device side --------------------------------------------------------------------------------------------------
@@ -316,6 +341,30 @@ class StreamingAnalyzer(_Stage):
     def _f0_len(self):
         return int(self.f0_params["window"]) + int(self.f0_params["tau_max"])
 
+    def _decided_after(self, st, nn):
+        """Frames of a decoding stream that are decided behind a tick that computes its next ``nn`` frames: the rule of
+        ``mbxv_decode_f0_frames``."""
+        from .f0decode import lag_frames_decided
+        done = st.emitted + nn
+        return max(st.f0_decided, lag_frames_decided(done, self.f0_lag, st.closed and done >= frames_total(st.have, self.hop)))
+
+    def _ensure_decoder(self, plan):
+        """The decoder's state rows, one per ring slot, and room for the tick's candidate tables (``tick`` zeroes the row of a
+        fresh stream beside its ring, whether or not the tick launches the decoder)."""
+        import torch
+        from .abi import load_library
+        words, slots = int(load_library().mbxv_lag_state_words()), int(self.rings.shape[0])
+        if self._lag_state is None or self._lag_state.shape[0] < slots:
+            new = torch.zeros((slots, words), dtype=torch.int32, device=self.device)
+            if self._lag_state is not None:
+                new[:self._lag_state.shape[0]] = self._lag_state
+            self._lag_state = new
+            self.device_allocations += 1
+        need = 3 * plan.T * plan.max_new * 8
+        if self._cand is None or self._cand.numel() < need:
+            self._cand = torch.zeros(_pow2_at_least(max(need, 1024)), dtype=torch.float32, device=self.device)
+            self.device_allocations += 1
+
     def tick(self):
         """Append what was pushed to the rings and compute every frame that became ready.
         Returns {stream_id: ndarray (n, mel_channels) float32} for the streams with new frames; ``last_f0`` then holds the
@@ -327,9 +376,14 @@ class StreamingAnalyzer(_Stage):
         import torch
         from .abi import _check, load_library
         self._ensure(plan)
+        if self.f0_lag is not None:
+            self._ensure_decoder(plan)
         lib, rings, in_rings, tabs = load_library(), self.rings, self.input_rings, self._tables
         S, R, body, used, mel_floats = plan.S, plan.R, plan.body, plan.body + plan.samples, plan.S * plan.max_new * self.n_mels
-        plane = plan.T * plan.max_new           # the two planes of the tracker ride behind the mel rows in the one copy back
+        lag = self.f0_lag if plan.T else None
+        # the two planes of the tracker ride behind the mel rows in the one copy back; a decoder's are `lag` frames wider
+        width = plan.max_new + (lag or 0)
+        plane = plan.T * width
         floats = mel_floats + 2 * plane
         self._stage_host, self._stage_dev = self._grown_pair(self._stage_host, self._stage_dev, used, torch.float32)
         self._out_host, self._out_dev = self._grown_pair(self._out_host, self._out_dev, floats, torch.float32)
@@ -337,6 +391,8 @@ class StreamingAnalyzer(_Stage):
         with torch.cuda.device(self.device):
             for slot in plan.fresh:                           # a reused slot starts from silence (first tick of a stream)
                 rings[slot].zero_()
+                if self._lag_state is not None:               # ... and from a decoder that has seen no frame
+                    self._lag_state[slot].zero_()
             stream, base, events = self._upload(self._stage_host, self._stage_dev, used)
             _check(lib.mbxl_ring_append(base + 4 * body, plan.samples, base, S, plan.max_model, rings.data_ptr(),
                                         int(rings.shape[0]), self.ring_samples, stream.cuda_stream))
@@ -354,7 +410,9 @@ class StreamingAnalyzer(_Stage):
                                        tabs[1].data_ptr(), tabs[2].data_ptr(), tabs[3].data_ptr(), tabs[4].data_ptr(),
                                        ctypes.c_float(float(np.finfo(np.float32).eps)), self._out_dev.data_ptr(),
                                        stream.cuda_stream))
-            if plane:
+            if plane and lag is not None:
+                self._decode_frames(lib, plan, base + 32 * S, width, self._out_dev.data_ptr() + 4 * mel_floats, stream)
+            elif plane:
                 prm, out = self.f0_params, self._out_dev.data_ptr() + 4 * mel_floats
                 _check(lib.mbxt_f0_frames(rings.data_ptr(), int(rings.shape[0]), self.ring_samples, base + 32 * S, plan.T,
                                           plan.max_new, self.hop, int(prm["sample_rate"]), int(prm["window"]),
@@ -362,13 +420,43 @@ class StreamingAnalyzer(_Stage):
                                           ctypes.c_float(float(prm["e_min"])), out, out + 4 * plane, stream.cuda_stream))
             packed = self._copy_back(stream, events, floats)
             rows = packed[:mel_floats].reshape(S, plan.max_new, self.n_mels)
-            tracked = packed[mel_floats:].reshape(2, plan.T, plan.max_new)
+            tracked = packed[mel_floats:].reshape(2, plan.T, width)
         result = {sid: rows[row, :nn].copy() for row, (sid, nn) in enumerate(plan.rows) if nn}
-        self.last_f0 = {sid: (tracked[0, row, :nn].copy(), tracked[1, row, :nn].copy())
-                        for row, (sid, nn) in enumerate(plan.rows[:plan.T]) if nn}
+        if lag is not None:           # a decoder hands out what became decided, which is not what was computed
+            counts = [self._decided_after(self.streams[sid], nn) - self.streams[sid].f0_decided for sid, nn in plan.rows[:plan.T]]
+        else:
+            counts = [nn for _, nn in plan.rows[:plan.T]]
+        self.last_f0 = {sid: (tracked[0, row, :cc].copy(), tracked[1, row, :cc].copy())
+                        for row, ((sid, _), cc) in enumerate(zip(plan.rows[:plan.T], counts)) if cc}
         self.commit(plan)
         self.ticks += 1
         return result
+
+    def _decode_frames(self, lib, plan, desc, width, out, stream):
+        """The two launches of a tick with decoding streams, on the first T rows of the mel launch's table: the candidates of
+        the new frames into ``_cand``, then the recursion continued from ``_lag_state`` into the two (T, width) planes."""
+        from .abi import _check
+        from .f0decode import _host_tables
+        prm, dec, rings = self.f0_params, self.f0_decode, self.rings
+        th, ww = _host_tables(dec)
+        fpp = ctypes.POINTER(ctypes.c_float)
+        table = 4 * plan.T * plan.max_new * 8
+        cand = [self._cand.data_ptr() + kk * table for kk in range(3)]
+        _check(lib.mbxv_f0_candidate_frames(rings.data_ptr(), int(rings.shape[0]), self.ring_samples, desc, plan.T, plan.max_new,
+                                            self.hop, int(prm["sample_rate"]), int(prm["window"]), int(prm["tau_min"]),
+                                            int(prm["tau_max"]), ctypes.c_float(float(prm["e_min"])), th.ctypes.data_as(fpp),
+                                            ww.ctypes.data_as(fpp), int(th.size), int(dec["n_cand"]), *cand, stream.cuda_stream))
+        _check(lib.mbxv_decode_f0_frames(*cand, desc, plan.T, plan.max_new, self.hop, self._lag_state.data_ptr(),
+                                         int(self._lag_state.shape[0]), self.f0_lag, int(prm["sample_rate"]),
+                                         ctypes.c_float(float(dec["w_jump"])), ctypes.c_float(float(dec["w_switch"])), out,
+                                         out + 4 * plan.T * width, width, stream.cuda_stream))
+
+
+def _same_decode(one, other):
+    """Whether two checked ``f0decode.decode_params`` dictionaries (or None) say the same."""
+    if one is None or other is None:
+        return one is other
+    return all(np.array_equal(np.asarray(one[key], dtype=np.float32), np.asarray(other[key], dtype=np.float32)) for key in one)
 
 
 def resolve_output_rate(output_rate, sample_rate, model_rate):
@@ -525,6 +613,7 @@ class _LStream:
         self.flushed = False          # the synthesizer has been told that the stream is over
         self.out_rate = None          # the stream's output rate when it is not the model's: it goes through the output stage
         self.f0_hold = None           # f0_source="audio": the last voiced F0 (float32), what an unvoiced frame takes
+        self.pending = None           # a decoding stream (f0_lag): the scaled mel rows that still wait for their decided F0
 
 
 class LiveResynthesizer:
@@ -548,7 +637,14 @@ class LiveResynthesizer:
     rule of ``f0track.fill_hold`` -- an unvoiced frame holds the last voiced value, ``f0_initial`` in front of the first --
     and pushes it with the mel rows to a synthesizer stream opened with ``f0="frames"``.  The stream then equals
     ``MELInverter.transform_audio(f0_source="audio", f0_fill="hold", f0_initial=...)`` of the sound under the same noise.
-    ``last_f0`` holds the raw tracked values of the last tick (0 = unvoiced)."""
+    ``last_f0`` holds the raw tracked values of the last tick (0 = unvoiced).
+
+    With ``f0_lag=N`` as well the stream's contour is decoded with a fixed lag of N frames (``StreamingAnalyzer``, DESIGN.md
+    section 6l; ``f0_decode``: an ``f0decode.decode_params`` dictionary, None = the defaults).  Its scaled mel rows wait in
+    a FIFO on the host: a tick pushes as many of them to the synthesizer as frames were decided, with the contour, noise,
+    transposition and formant factors of exactly those frames; a tick that decides nothing pushes nothing, the closing tick
+    everything.  The stream then equals ``MELInverter.transform_audio(f0_source="audio", f0_decode=..., f0_lag=N,
+    f0_fill="hold")`` of the sound under the same noise, N frames later."""
 
     def __init__(self, mel_inverter, chunk_frames=(6, 6, 7, 6, 7)):
         from .streaming import StreamingSynthesizer
@@ -580,13 +676,14 @@ class LiveResynthesizer:
         from .f0track import check_params, params
         return params(self.analyzer.model_rate) if f0_params is None else check_params(dict(f0_params))
 
-    def lookahead_ms_for(self, sample_rate=None, output_rate=None, f0_source="net", f0_params=None):
+    def lookahead_ms_for(self, sample_rate=None, output_rate=None, f0_source="net", f0_params=None, f0_lag=None):
         """``lookahead_ms`` of a stream opened at ``sample_rate`` and ``output_rate``: a resampled stream waits for half
         its filter as well, half / up input samples (0.92 ms at 44.1 and 48 kHz, 1.4 ms at 16 kHz for a 24 kHz model); a
         stream with an output rate waits for half the output filter, half / up model-rate samples (0.92 ms to 48 kHz,
         0.94 ms to 44.1 kHz, 1.4 ms to 16 kHz).  With ``f0_source="audio"`` a frame waits for its F0 frame too, L = window
         + tau_max of ``f0_params`` (None: the defaults) samples about its centre: the analysis part is
-        ceil(max(win - win // 2, L - L // 2) / hop) frames -- 3 instead of 2 with the defaults at 24 kHz."""
+        ceil(max(win - win // 2, L - L // 2) / hop) frames -- 3 instead of 2 with the defaults at 24 kHz.  ``f0_lag=N`` adds
+        the decoder's N frames, 1000 N hop / sample_rate ms."""
         model = self.analyzer.model_rate
         ms = self.lookahead_ms
         if f0_source not in ("net", "audio"):
@@ -596,6 +693,9 @@ class LiveResynthesizer:
             reach, f0_len = an.win - an.win // 2, int(prm["window"]) + int(prm["tau_max"])
             frames = -(-max(reach, f0_len - f0_len // 2) // an.hop)
             ms += 1000.0 * (frames - -(-reach // an.hop)) * an.hop / an.sample_rate
+        if f0_lag is not None:
+            from .f0decode import check_lag
+            ms += 1000.0 * check_lag(f0_lag) * self.analyzer.hop / self.analyzer.sample_rate
         if sample_rate is not None and int(round(sample_rate)) != model:
             ms += resampling_lookahead_ms(sample_rate, model)
         out_rate = resolve_output_rate(output_rate, sample_rate, model)
@@ -604,17 +704,21 @@ class LiveResynthesizer:
         return ms
 
     def open(self, stream_id, seed=None, noise_fn=None, sample_rate=None, output_rate=None, f0_source="net", f0_params=None,
-             f0_initial=150.0, f0_decode=None):
+             f0_initial=150.0, f0_decode=None, f0_lag=None):
         """``output_rate``: the rate the stream's audio comes back at -- a rate in Hz, or ``"input"`` for the stream's own
         ``sample_rate``; None or the model's rate: the model-rate audio, as the synthesizer emits it.  ``f0_source``:
         ``"net"`` -- the F0-net's contour -- or ``"audio"``: the tracked pitch of the sound (``f0_params``: an
         ``f0track.params`` dictionary at the model rate, None = its defaults; ``f0_initial``: Hz of the frames in front of the
-        first voiced one).  ``f0_decode`` is refused: decoding the contour needs the whole sound."""
+        first voiced one).  ``f0_lag``: frames of look-ahead of a decoded contour (0 .. 128, with ``f0_source="audio"``), by
+        ``f0_decode`` (None: the defaults); ``f0_decode`` without a lag is refused: decoding the contour over the whole sound
+        needs the whole sound."""
         if f0_source not in ("net", "audio"):
             raise ValueError(f"f0_source must be 'net' or 'audio', got {f0_source!r}")
-        if f0_decode is not None:
+        if f0_decode is not None and f0_lag is None:
             raise ValueError(f"stream {stream_id!r}: f0_decode decodes the contour over the whole sound (f0decode.py), which a "
                              "stream does not have; streams track every frame on its own")
+        if f0_lag is not None and f0_source != "audio":
+            raise ValueError("f0_lag goes with f0_source='audio'")
         hold = None
         if f0_source == "audio":
             f0_params = self._f0_params(f0_params)
@@ -624,12 +728,13 @@ class LiveResynthesizer:
         elif f0_params is not None:
             raise ValueError("f0_params go with f0_source='audio'")
         out_rate = resolve_output_rate(output_rate, sample_rate, self.analyzer.sample_rate)
-        self.analyzer.open(stream_id, sample_rate=sample_rate, f0_params=f0_params)
+        self.analyzer.open(stream_id, sample_rate=sample_rate, f0_params=f0_params, f0_decode=f0_decode, f0_lag=f0_lag)
         self.synthesizer.open(stream_id, f0="net" if hold is None else "frames")
         up, down = (self.analyzer.streams[stream_id].filt or (1, 1))[:2]
         st = self.streams[stream_id] = _LStream(self.analyzer.hop, None if noise_fn else np.random.default_rng(seed),
                                                 noise_fn, up, down)
         st.f0_hold = hold
+        st.pending = None if f0_lag is None else np.zeros((0, self.dims.mel_channels), dtype=np.float32)
         if out_rate is not None:
             self.output.open(stream_id, out_rate)
             st.out_rate = out_rate
@@ -686,20 +791,24 @@ class LiveResynthesizer:
         for sid, st in self.streams.items():
             rows = mels.get(sid)
             done = self.analyzer.finished(sid)
+            tracked = self.analyzer.last_f0.get(sid, (np.zeros(0, dtype=np.float32),))[0]
+            scaled = np.zeros((0, self.dims.mel_channels), dtype=np.float32)
+            if rows is not None:
+                scaled = self.mel_inverter.scale_mel(dict(self._header, mell=rows.T))[0]
+            if st.pending is not None:
+                # a decoding stream: the rows wait for their F0, and as many leave as frames were decided in this tick
+                st.pending = np.concatenate((st.pending, scaled))
+                scaled, st.pending = st.pending[:tracked.size], st.pending[tracked.size:]
+                rows = scaled if tracked.size else None
             if rows is None and not (done and not st.flushed):
                 continue
             n = 0 if rows is None else rows.shape[0]
             first, end = st.frames, st.frames + n
-            if n:
-                scaled = self.mel_inverter.scale_mel(dict(self._header, mell=rows.T))[0]
-            else:
-                scaled = np.zeros((0, self.dims.mel_channels), dtype=np.float32)
             noise = self._noise(sid, st, first, end) if self.dims.noise_sigma else None
             shift = {} if st.formants is None else {"formant": st.formants.take(first, end)}
             if st.f0_hold is not None:
                 # the tick's tracked values as a positive contour, causally (the flush push carries an empty one)
                 from .f0track import fill_hold
-                tracked = self.analyzer.last_f0.get(sid, (np.zeros(0, dtype=np.float32),))[0]
                 shift["f0"] = fill_hold(tracked, st.f0_hold)
                 if n:
                     st.f0_hold = shift["f0"][-1]

@@ -135,6 +135,7 @@ class _AStream:
         self.have = 0             # model-rate samples so far: pushed, or final outputs of the resampler (outputs_ready)
         self.on_device = 0        # ... of which the ring holds [max(0, on_device - ring), on_device)
         self.emitted = 0          # frames handed out
+        self.f0_decided = 0       # ... of which a decoding stream's fixed-lag decoder has decided the F0 (live.py, section 6l)
         self.closed = False
         self.queue = []           # pushed since the last tick
         self.fresh = True         # the slot's ring still holds another stream's samples: the stream's first tick zeroes it

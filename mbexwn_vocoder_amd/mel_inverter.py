@@ -319,7 +319,7 @@ class MELInverter(object):
     def transform_audio(self, sounds, rates, names, transposition=1.0, noise_seed=0, out_rate=None, max_batch=16,
                         max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None, formant=None,
                         f0_source="net", f0_params=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0,
-                        align_to=None, align_band_s=1.0):
+                        align_to=None, align_band_s=1.0, f0_lag=None):
         """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
         keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
         factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
@@ -344,6 +344,9 @@ class MELInverter(object):
         multiplies on top.  An item without a voiced frame keeps the F0-net.  ``f0_decode``: None -- every frame's pick on its
         own -- or a ``f0decode.decode_params`` dictionary: the contour is the Viterbi path over the YIN candidates of the
         item's frames, which does not jump an octave for single frames.  It needs ``"audio"``.
+        ``f0_lag``: None -- the path over the whole item -- or the fixed lag in frames, 0 .. 128, of a live stream's decoder
+        (DESIGN.md section 6l): frame t is decided from the frames up to t + lag.  It needs ``f0_decode``, and with
+        ``f0_fill="hold"`` the run has the bits of ``LiveResynthesizer.open(f0_source="audio", f0_decode=..., f0_lag=...)``.
         ``f0_fill``: ``"interpolate"`` -- the fill described above -- or ``"hold"``, the causal fill of the live streams
         (``f0track.fill_hold``): an unvoiced frame holds the last voiced value, the frames in front of
         the first voiced one take ``f0_initial`` Hz, and every item takes its contour.  It needs ``"audio"`` and exists so that
@@ -373,7 +376,8 @@ class MELInverter(object):
                                      guides=[None if gg is None else gg[0] for gg in align_to] if guided else None,
                                      guide_rates=[None if gg is None else gg[1] for gg in align_to] if guided else None,
                                      align_band_s=align_band_s, f0_source=f0_source, f0_params=f0_params, f0_decode=f0_decode,
-                                     f0_fill=f0_fill, f0_initial=f0_initial, batch=max_batch, who="transform_audio")
+                                     f0_fill=f0_fill, f0_initial=f0_initial, batch=max_batch, who="transform_audio",
+                                     f0_lag=f0_lag)
         for ii, mel in enumerate(done.scaled):
             if mel is None:
                 raise align.AlignError(done.notes[ii]["error"])
@@ -383,13 +387,14 @@ class MELInverter(object):
                                     noise_keys=[item_key(nn) for nn in names], transpositions=rows, formants=formant,
                                     f0s=done.contours)
 
-    def track_f0(self, snd, srate, on_device=False, decode=None, **f0_params):
+    def track_f0(self, snd, srate, on_device=False, decode=None, f0_lag=None, **f0_params):
         """The pitch of a single sound (this build): (times in s, f0 in Hz with 0 = unvoiced, periodicity), one value per mel
         frame :meth:`generate_mel_from_snd` with ``resampler="reference"`` gives for it.  ``f0_params``: keywords of
         ``f0track.params`` (f0_min, f0_max, window, threshold, rms_floor).  Host (numpy) or, ``on_device``, the HIP kernel:
         the same bits on the same model-rate samples (a sound at another rate goes through the host or
         the device resampler first, as in ``generate_mels``).  ``decode``: None, or a ``f0decode.decode_params`` dictionary --
-        the contour is then decoded over the whole sound, on the host or on the device alike."""
+        the contour is then decoded over the whole sound, on the host or on the device alike; with
+        ``f0_lag`` (frames, 0 .. 128; it needs ``decode``) as a live stream with that lag decides it (section 6l)."""
         from . import f0track
         from .analysis import generate_mels
         snd = np.asarray(snd)
@@ -397,7 +402,7 @@ class MELInverter(object):
             snd = snd[0]
         tracked = []
         generate_mels([snd], [srate], self.preprocess_config, on_device=on_device, batch=1, f0_out=tracked,
-                      f0_params=f0track.params(int(round(self.srate)), **f0_params), f0_decode=decode)
+                      f0_params=f0track.params(int(round(self.srate)), **f0_params), f0_decode=decode, f0_lag=f0_lag)
         f0, periodicity = tracked[0]
         return f0track.frame_times(f0.size, self.hop_size, self.srate), f0, periodicity
 

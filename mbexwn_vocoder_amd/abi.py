@@ -1,5 +1,5 @@
 """ctypes binding of libmbexwn_hip.so: the structures and constants of include/mbexwn.h, and ONE table of every function the
-fourteen headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
+fifteen headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
 
 Nothing else lives here: a tool that only resamples imports this module, not the engine's driver.  The table is declared in
 Python (the package loads without include/ beside it); tests/test_abi_headers.py holds it to the headers name by name and
@@ -173,6 +173,11 @@ TABLE = {
         ("mbxg_local_cost", i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
         ("mbxg_align_workspace_size", size_t, [i32, i32, i32]),
         ("mbxg_align_path", i32, [vp, vp, vp, i32, i32, i32, vp, size_t, vp, vp, vp, vp, vp])],
+    # n_samples, hops, coefs and targets are HOST arrays, abs_gate and ceiling HOST pointers to one double
+    "mbexwn_level.h": [
+        ("mbxl_measure", i32, [vp, i64, i32, i64p, P(i32), P(ctypes.c_double), P(ctypes.c_double), vp, i32, vp, i32, vp, vp]),
+        ("mbxl_gains", i32, [vp, i32, P(ctypes.c_double), vp, P(ctypes.c_double), i32, vp, vp]),
+        ("mbxl_apply", i32, [vp, i64, i32, i64p, vp, vp, i64, vp])],
 }
 
 

@@ -347,11 +347,13 @@ def _analyse_host(plan, ii, stats):
     return mel[0], pair
 
 
-def _device_batches(sounds, rates, preprocess_config, batch, dev, timed=False):
+def _device_batches(sounds, rates, preprocess_config, batch, dev, timed=False, levels=None):
     """The device micro-batches of ``sounds``: grouped by rate, sorted by length (neighbours share a launch: less padding),
     at most ``batch`` items, padded, uploaded, resampled to the model rate and padded to half a window.  Yields (group of
     indices, device sound (B, stride), device lengths int32 (B,), host lengths, marks); ``marks``: None, or with ``timed``
-    five timing events, the first three recorded around the upload and the resampler."""
+    five timing events, the first three recorded around the upload and the resampler.  ``levels``: None, or a list that
+    receives (group, ``level.DeviceMeasure``) of every micro-batch as uploaded, at its own rate, in front of the resampler
+    (enqueued only)."""
     import torch
     from . import resample
     cfg = preprocess_config
@@ -372,6 +374,9 @@ def _device_batches(sounds, rates, preprocess_config, batch, dev, timed=False):
                 marks[0].record()
             snd = torch.as_tensor(host).to(dev)
             n_dev = torch.as_tensor(np.asarray(lengths, dtype=np.int32)).to(dev)
+            if levels is not None:                             # counted with the upload, not with the resampler
+                from . import level
+                levels.append((group, level.measure_device(snd, lengths, rr)))
             if marks:
                 marks[1].record()
             if rr != target:
@@ -479,7 +484,7 @@ def _analyse_device(plan, micro_batch, guide_mel, stats):
 
 def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, stats=None, time_maps=None, rows_per_frame=1,
                   f0_out=None, f0_params=None, f0_decode=None, guides=None, guide_rates=None, align_band_s=1.0,
-                  align_out=None, f0_lag=None):
+                  align_out=None, levels_out=None, f0_lag=None):
     """Sounds -> ``.mell`` dictionaries (reference bin/generate_mel.py:54-64 for a list of files): ``sounds`` is a list of 1-D
     float32 arrays, ``rates`` their sample rates.  A sound that is not at the model rate goes through the reference's resampler
     (resample.py); one already at it skips that step.  Needs the ``preprocess_config`` alone: no engine, no weights.
@@ -519,21 +524,38 @@ def generate_mels(sounds, rates, preprocess_config, on_device=True, batch=16, st
     (``timemap.Centres``): its ``.mell`` has the guide's frame count.  A guided item takes no ``time_maps`` entry.  An item
     without a guide keeps its regular bits; a call without guides makes the launches of before.  ``align_out``: a dict, or
     None.  Given a dict, item i's ``align.path_stats`` go to ``align_out[i]``, and an item that cannot be aligned
-    (``align.AlignError``) leaves ``{"error": message}`` there and None in the result (and in ``f0_out``) instead of raising."""
+    (``align.AlignError``) leaves ``{"error": message}`` there and None in the result (and in ``f0_out``) instead of raising.
+
+    ``levels_out``: a list, or None.  Given a list, (P, count) of every sound -- its BS.1770 power and the number of gated
+    blocks behind it, 0 for a sound that is not measurable (level.py) -- is appended to it in the order
+    of ``sounds``: the sound as handed in, at its own rate, measured on the device in the micro-batch that uploads it (else
+    ``level.measure_host``: the same bits).  None makes exactly the launches of before."""
     plan = _plan_mels(sounds, rates, preprocess_config, time_maps, rows_per_frame, f0_out, f0_params, f0_decode, guides,
                       guide_rates, align_band_s, align_out, f0_lag)
     results = [(None, None)] * len(plan.sounds)
+    measured = [] if levels_out is not None else None
     if not on_device:
         results = [_analyse_host(plan, ii, stats) for ii in range(len(plan.sounds))]
+        if measured is not None:
+            from . import level
+            found = [level.measure_host(ss, rr) for ss, rr in zip(plan.sounds, plan.rates)]
+            levels_out.extend((mm.power, mm.count) for mm in found)
     else:
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("generate_mels(on_device=True): no GPU available (on_device=False is the host path)")
         dev = torch.device("cuda", torch.cuda.current_device())
         guide_mel = _guide_mels_device(plan, batch, dev) if plan.guided else {}
-        for micro_batch in _device_batches(plan.sounds, plan.rates, plan.cfg, batch, dev, timed=stats is not None):
+        for micro_batch in _device_batches(plan.sounds, plan.rates, plan.cfg, batch, dev, timed=stats is not None,
+                                           levels=measured):
             for ii, result in zip(micro_batch[0], _analyse_device(plan, micro_batch, guide_mel, stats)):
                 results[ii] = result
+        if measured is not None:
+            powers = [None] * len(plan.sounds)
+            for group, measure in measured:
+                for ii, mm in zip(group, measure.host(details=False)):
+                    powers[ii] = (mm.power, mm.count)
+            levels_out.extend(powers)
     for ii in plan.failed:
         results[ii] = (None, None)
     if f0_out is not None:

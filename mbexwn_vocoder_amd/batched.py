@@ -99,9 +99,11 @@ class SynthBatch:
     and what was enqueued behind the forward -- the FLAC frames (``engine.EncodedFlac``) and / or the audio in pinned host
     memory.  :meth:`wait` before reading; ``device_ms`` / ``copy_ms`` are then the forward's and the encode + copies' time."""
 
-    def __init__(self, indices, n_samples, audio, flac, host_audio, events, model_audio=None):
+    def __init__(self, indices, n_samples, audio, flac, host_audio, events, model_audio=None, level=None):
         self.indices, self.n_samples, self.device_audio = list(indices), list(n_samples), audio
         self.flac, self.host_audio, self._events = flac, host_audio, events
+        # with a level stage: (LevelControl, the items' target powers, host records, host gains) -- see level()
+        self._level = level
         # with an output rate: (device audio at the model rate, its lengths) -- everything above is at the output rate
         self._model_audio = model_audio
         self.device_ms = self.copy_ms = 0.0
@@ -129,6 +131,26 @@ class SynthBatch:
             return self.audio(jj)
         audio, n_samples = self._model_audio
         return audio[jj, :n_samples[jj]].cpu().numpy()
+
+    def level(self, jj):
+        """What the level stage did to item jj (after :meth:`wait`; None for a batch without the stage): a dict with
+        ``loudness_in`` and ``loudness_out`` in LUFS (-inf: not measurable), ``gain`` (the float32 factor), ``gain_db``,
+        ``peak_in`` and ``peak_out`` (linear; the true peak where the stage was asked for it) and ``limited`` -- the
+        ceiling, not the target, set the gain."""
+        if self._level is None:
+            return None
+        from . import level as lv
+        control, powers, records, gains = self._level
+        self.wait()
+        power, count, _, sample_peak, true_peak = lv.DeviceMeasure.unpack(records.numpy(), jj)
+        peak = true_peak if control.true_peak else sample_peak
+        gain = float(gains.numpy()[jj])
+        _, limited = lv.gain_host(power, count, peak, powers[jj], lv.ceiling_linear(control.peak_limit))
+        loud = lv.lufs(power) if count else float("-inf")
+        with np.errstate(divide="ignore"):
+            gain_db = float(20.0 * np.log10(np.float64(gain)))
+        return {"loudness_in": loud, "loudness_out": loud + gain_db, "gain": gain, "gain_db": gain_db, "peak_in": float(peak),
+                "peak_out": float(np.float32(peak) * np.float32(gain)), "limited": bool(limited)}
 
     def max_abs(self, jj):
         if self.flac is not None:
@@ -190,7 +212,7 @@ def check_f0s(f0s, lengths):
 
 
 def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False, host_audio=True,
-                      flac_compression="verbatim", out_rate=None, transpositions=None, formants=None, f0s=None):
+                      flac_compression="verbatim", out_rate=None, transpositions=None, formants=None, f0s=None, level=None):
     """Generator over the padded micro-batches of ``mels`` (list of (T_i, C) float32 arrays) on ``engine``: each is staged
     and run (engine.forward with the items' lengths), its FLAC frames encoded (``flac``) and / or its audio copied to pinned
     host memory (``host_audio``), all enqueued on the current stream; the SynthBatch is yielded without waiting, so that a
@@ -209,7 +231,14 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
     ``f0s``: per item None or (T_i,) Hz, one value per mel frame, positive and finite (an F0 tracker's output through
     ``f0track.fill_unvoiced``): the ``f0_frames`` rows of the forward, with ``f0_item_mask`` 0 for the None items, which keep
     the F0-net; every entry is checked before anything runs, and a job whose entries are all None runs the forward
-    without them."""
+    without them.
+
+    ``level``: None, or a ``level.LevelControl``: behind the forward and the output resampler, and in
+    front of the FLAC encoder and the host copy, every item is measured at the rate it is written at (``level.measure_device``),
+    takes one gain from its target and the ceiling (``level.gains_device``) and is multiplied by it (``level.apply_device``)
+    -- all on the device, nothing waited for.  The FLAC frames, ``pcm``, MD5, ``max_abs`` and the host audio are those of the
+    gained audio; ``SynthBatch.model_audio`` keeps the ungained model-rate audio and ``SynthBatch.level`` reports.  A
+    per-item target list is indexed like ``mels``.  None: the launches of before."""
     f0s = check_f0s(f0s, [int(mm.shape[0]) for mm in mels])
     import torch
     from .mel_inverter import KeyedNoise
@@ -242,6 +271,22 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
             model_audio = (audio, n_samples)
             audio, _ = resample_device(audio, n_frames * dims.hop_size, int(round(dims.sample_rate)), int(round(out_rate)))
             n_samples = [-(-nn * up // down) for nn in n_samples]
+        report = None
+        if level is not None:
+            from . import level as lv
+            powers = level.powers(group)
+            if model_audio is None:                         # the gain goes into a copy: the forward's audio stays as it is
+                model_audio, gained = (audio, n_samples), torch.empty_like(audio.contiguous())
+            else:
+                gained = None                               # the resampler's output is this batch's own: in place
+            audio = audio.contiguous()
+            measure = lv.measure_device(audio, n_samples, dims.sample_rate if out_rate is None else out_rate, level.true_peak)
+            gains = lv.gains_device(measure, powers, ceiling=lv.ceiling_linear(level.peak_limit), true_peak=level.true_peak)
+            audio = lv.apply_device(audio, n_samples, gains, out=gained)
+            pinned = [torch.empty(tuple(tt.shape), dtype=tt.dtype, pin_memory=True) for tt in (measure.records, gains)]
+            pinned[0].copy_(measure.records, non_blocking=True)
+            pinned[1].copy_(gains, non_blocking=True)
+            report = (level, powers, pinned[0], pinned[1])
         enc = None
         if flac:
             enc = engine.encode_flac16(audio, n_samples, sample_rate=None if out_rate is None else int(round(out_rate)),
@@ -251,7 +296,7 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
             host = torch.empty(tuple(audio.shape), dtype=torch.float32, pin_memory=True)
             host.copy_(audio, non_blocking=True)
         events[2].record(stream)
-        yield SynthBatch(group, n_samples, audio, enc, host, events, model_audio)
+        yield SynthBatch(group, n_samples, audio, enc, host, events, model_audio, report)
 
 
 class _Clock:
@@ -305,10 +350,23 @@ class _Job:
               f"{self.threads} threads each)", file=sys.stderr)
 
 
+def level_line(outfile, report):
+    """The writer's line about a file that went through the level stage (``SynthBatch.level``)."""
+    def db(value):
+        return "-inf" if not value > 0 else f"{20.0 * np.log10(value):.2f}"
+
+    if np.isfinite(report["loudness_in"]):
+        loud = f"{report['loudness_in']:.2f} -> {report['loudness_out']:.2f} LUFS"
+    else:
+        loud = "loudness not measurable (under 0.4 s, or silent)"
+    why = " (the peak limit, not the loudness, set the gain)" if report["limited"] else ""
+    return f"    level of {outfile}: {loud}, gain {report['gain_db']:+.2f} dB, peak {db(report['peak_out'])} dBFS{why}"
+
+
 def _file_writer(job, inv, files, mine, scaled, output_dir, fmt, device_flac, file_rate, flac_compression, verbose, quiet):
     """The writer-pool task of run_job and run_audio_job: ``write(sb)`` waits for the micro-batch ``sb`` (whose indices
-    point into ``mine``) and writes syn_<basename>.<fmt> of each of its items, with the clipping note and, ``verbose``, the
-    mel error against ``scaled``."""
+    point into ``mine``) and writes syn_<basename>.<fmt> of each of its items, with the clipping note -- or, for a batch
+    that went through the level stage, :func:`level_line` in its place -- and, ``verbose``, the mel error against ``scaled``."""
     from .mel_inverter import log_to_db
     rate = inv.srate
 
@@ -325,8 +383,10 @@ def _file_writer(job, inv, files, mine, scaled, output_dir, fmt, device_flac, fi
                 err = log_to_db * np.mean(np.abs(scaled[ii] - resyn[:, :scaled[ii].shape[1]]))
                 lines.append(f"    synthesized audio with {audio.size} samples in a micro-batch of {len(sb.indices)} "
                              f"({sb.device_ms:.1f} ms on the device), mel_error: {err:.3f}dB")
-            peak = sb.max_abs(jj)
-            if peak > 1:
+            peak, report = sb.max_abs(jj), sb.level(jj)
+            if report is not None:
+                lines.append(level_line(outfile, report))
+            elif peak > 1:
                 lines.append(f'    to prevent clipping you would need to normalize {outfile} by {0.99 / peak:.3f}')
             if verbose:
                 lines.append(f"    save audio under {outfile}")
@@ -355,7 +415,8 @@ def load_contour(name, directory, frames):
 
 
 def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threads=2, verbose=False, quiet=False,
-            flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant=None, f0_dir=None):
+            flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant=None, f0_dir=None,
+            level=None):
     """The batched CLI on this process's GPU: ``files[mine]`` -> syn_<basename>.<fmt> in ``output_dir``.
 
     ``frames``: the frame count after scale_mel of EVERY file of the job, in file order (the noise replay needs all of
@@ -369,7 +430,8 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
     files; ``transposition``: a factor on every mel frame of every file (``f0_scale`` rows); ``formant``: a formant-shift
     factor on every mel frame of every file (``formant`` rows).  ``f0_dir``: every file takes the contour of
     ``f0_dir/NAME.f0`` (:func:`load_contour`; a missing file or a wrong row count fails before anything runs) in place of the
-    F0-net's.  All None: today's job."""
+    F0-net's.  ``level``: a ``level.LevelControl`` with a loudness in LUFS and / or a peak limit (``run_micro_batches``): the
+    files are written at that level and the writer reports it in place of the clipping note.  All None: today's job."""
     job = _Job(threads)
     mine = list(range(len(files))) if mine is None else list(mine)
 
@@ -407,7 +469,7 @@ def run_job(inv, files, output_dir, fmt, frames=None, mine=None, batch=16, threa
     job.write_all((write, sb) for sb in run_micro_batches(inv.model, mels, noises, max(1, batch), flac=device_flac,
                                                           host_audio=verbose or not device_flac,
                                                           flac_compression=flac_compression, out_rate=out_rate,
-                                                          transpositions=rows, formants=shifts, f0s=contours))
+                                                          transpositions=rows, formants=shifts, f0s=contours, level=level))
     if verbose:
         job.summary("resynth_mel", len(mine), sum(int(frames[ii]) for ii in mine) * inv.hop_size / rate,
                     f"read+scale {job.clock.seconds.get('read', 0.0):.2f} s", "device", "encode+D2H")
@@ -470,7 +532,7 @@ def read_sound(path):
 def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
                   quiet=False, flac_compression="verbatim", out_rate=None, stretches=None, formants=None, f0_source="net",
                   f0_params=None, write_f0=False, timings=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0,
-                  guides=None, align_band_s=1.0, f0_lag=None):
+                  guides=None, align_band_s=1.0, loudness=None, peak_limit=None, true_peak=False, f0_lag=None):
     """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
     ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
 
@@ -504,10 +566,16 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     band of ``align_band_s`` seconds; it takes no ``stretches`` entry other than 1.  A guide that cannot be read, and a file
     that cannot be aligned to its guide, is reported and skipped like the unreadable ones; ``verbose`` prints the path's mean
     cost per node and its largest offset from the diagonal.  No guide: the launches and the bytes of before.
+    ``loudness``: None, a number of LUFS, or ``"input"`` -- every file comes out at the loudness of its source, measured as
+    read, at its own rate, on the device in the micro-batches the analysis stages (``generate_mels(levels_out=)``); a source
+    that is not measurable leaves the loudness gain at 1.  ``peak_limit``: a ceiling in dBFS (default: -1 with a loudness, else
+    none); ``true_peak``: on the 4x true peak.  DESIGN.md section 6m.  None of them: the launches and the bytes of before.
     ``timings``: a dict that receives the seconds per stage the
     verbose line reports (upload, resample, analysis, f0, copy_back from ``generate_mels``; read, scale, device, copy, write
     from the pools and the micro-batches' events; wall)."""
     from . import f0track
+    from .level import check_options, level_control
+    loudness, peak_limit, true_peak = check_options(loudness, peak_limit, true_peak, allow_input=True)   # before anything runs
     job = _Job(threads)
     mine = list(range(len(files))) if mine is None else list(mine)
     factors = [1.0] * len(files) if factors is None else list(factors)
@@ -526,7 +594,8 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
                 guide_rates=[None if guides[ii] is None else guide_sounds[guides[ii]][1] for ii in mine] if have_guides else None,
                 align_band_s=align_band_s, f0_source=f0_source, f0_params=f0_params, f0_decode=f0_decode, f0_fill=f0_fill,
                 f0_initial=f0_initial, write_f0=bool(write_f0), batch=batch, stats=stats,
-                scale_map=lambda dicts: list(pool.map(scale, dicts)), who="run_audio_job", f0_lag=f0_lag)
+                scale_map=lambda dicts: list(pool.map(scale, dicts)), who="run_audio_job", f0_lag=f0_lag,
+                source_levels=loudness == "input")
         except ValueError as err:
             if not have_guides:
                 raise
@@ -549,10 +618,16 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
             f0, periodicity = done.tracked[local]
             f0track.write_f0(f0_path(files[mine[local]], output_dir), f0track.frame_times(f0.size, inv.hop_size, inv.srate),
                              f0, periodicity)
+    if loudness == "input":                                    # the source's P is the target of its output
+        loudness = [None] * len(files)
+        for local in keep:
+            power, count = done.levels[local]
+            loudness[mine[local]] = power if count else None
+    control = level_control(loudness, peak_limit, true_peak)
     mine = [mine[local] for local in keep]
     rates = {ii: loaded[ii][1] if out_rate == "input" else out_rate for ii in mine}
     _synthesise_files(job, inv, files, mine, scaled, contours, rates, output_dir, fmt, factors, formants, noise_seed, batch,
-                      flac_compression, verbose, quiet)
+                      flac_compression, verbose, quiet, control)
     if timings is not None:
         sec = job.clock.seconds
         timings.update(stats, read=sec.get("read", 0.0), scale=sec.get("scale", 0.0), device=sec.get("device_ms", 0.0) / 1e3,
@@ -622,7 +697,7 @@ def _load_sounds(job, pool, inv, files, mine, guides, stretches):
 def analyse_for_synthesis(inv, sounds, rates, time_maps=None, guides=None, guide_rates=None, align_band_s=1.0, f0_source="net",
                           f0_params=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0, write_f0=None, batch=16,
                           stats=None, scale_map=None, on_device=True, rows_per_frame=None, who="analyse_for_synthesis",
-                          f0_lag=None):
+                          source_levels=False, f0_lag=None):
     """Sounds in, what the synthesis takes out: the step between reading and ``run_micro_batches``, the same code under
     ``MELInverter.transform_audio`` and :func:`run_audio_job`.  ``sounds`` at ``rates`` go through ``analysis.generate_mels``
     (``time_maps``, ``guides``, ``guide_rates``, ``align_band_s``, ``batch``, ``stats``, ``on_device`` and ``rows_per_frame``
@@ -636,7 +711,8 @@ def analyse_for_synthesis(inv, sounds, rates, time_maps=None, guides=None, guide
     Returns a namespace: ``scaled`` (1, T, mel_channels), ``contours`` (filled; an item without a voiced frame: None; not
     "audio": None as a whole) and ``tracked`` (raw (f0, periodicity); nothing tracked: None as a whole) hold one entry per
     sound; ``notes`` is {item: ``align.path_stats`` or {"error": message}}.  An item that cannot be aligned to its guide
-    has its note and None in all three lists."""
+    has its note and None in all three lists.  ``source_levels``: ``levels`` holds, per sound, (P, count) of the sound as it
+    was handed in, at its own rate (``level.py``; ``generate_mels(levels_out=)``); else None."""
     from types import SimpleNamespace
     from . import f0track
     from .analysis import generate_mels
@@ -654,13 +730,15 @@ def analyse_for_synthesis(inv, sounds, rates, time_maps=None, guides=None, guide
     guided = guides is not None and any(gg is not None for gg in guides)
     notes = {}
     dicts = []
+    levels = [] if source_levels else None
     if len(sounds):
         dicts = generate_mels(sounds, rates, inv.preprocess_config, on_device=on_device, batch=max(1, batch), stats=stats,
                               time_maps=None if time_maps is None or all(mm is None for mm in time_maps) else list(time_maps),
                               rows_per_frame=inv.model.dims.steps_per_frame if rows_per_frame is None else rows_per_frame,
                               f0_out=tracked, f0_params=f0_params if tracked is not None else None, f0_decode=f0_decode,
                               guides=guides if guided else None, guide_rates=guide_rates if guided else None,
-                              align_band_s=align_band_s, align_out=notes if guided else None, f0_lag=f0_lag)
+                              align_band_s=align_band_s, align_out=notes if guided else None, f0_lag=f0_lag,
+                              levels_out=levels)
     keep = [ii for ii, dd in enumerate(dicts) if dd is not None]
     scale_map = scale_map or (lambda some: [inv.scale_mel(dd) for dd in some])
     scaled = [None] * len(dicts)
@@ -669,13 +747,15 @@ def analyse_for_synthesis(inv, sounds, rates, time_maps=None, guides=None, guide
     contours = None
     if f0_source == "audio":
         contours = [None if pair is None else f0track.fill_tracked(pair[0], f0_fill, f0_initial) for pair in tracked]
-    return SimpleNamespace(scaled=scaled, contours=contours, tracked=tracked, notes=notes)
+    return SimpleNamespace(scaled=scaled, contours=contours, tracked=tracked, notes=notes, levels=levels)
 
 
 def _synthesise_files(job, inv, files, mine, scaled, contours, rates, output_dir, fmt, factors, formants, noise_seed, batch,
-                      flac_compression, verbose, quiet):
+                      flac_compression, verbose, quiet, level=None):
     """Phase three of run_audio_job: the files ``mine`` grouped by the rate they are written at (``rates``: {index: a rate
-    or None}), each group through ``run_micro_batches`` with keyed noise and per-file factors, then to the writers."""
+    or None}), each group through ``run_micro_batches`` with keyed noise and per-file factors, then to the writers.
+    ``level``: None or the job's ``level.LevelControl``, a target list indexed like ``files``."""
+    from .level import LevelControl
     from .mel_inverter import KeyedNoise
     from .noise import item_key
     dims = inv.model.dims
@@ -691,10 +771,13 @@ def _synthesise_files(job, inv, files, mine, scaled, contours, rates, output_dir
             noises = KeyedNoise(noise_seed, [item_key(files[ii]) for ii in sub]) if dims.noise_sigma else None
             rows = [np.full(int(scaled[ii].shape[1]), factors[ii], dtype=np.float32) for ii in sub]
             shifts = None if formants is None else [np.full(int(scaled[ii].shape[1]), formants[ii], dtype=np.float32) for ii in sub]
+            part = level
+            if level is not None and isinstance(level.target, (list, tuple)):
+                part = LevelControl([level.target[ii] for ii in sub], level.peak_limit, level.true_peak)
             for sb in run_micro_batches(inv.model, [scaled[ii][0] for ii in sub], noises, max(1, batch), flac=device_flac,
                                         host_audio=verbose or not device_flac, flac_compression=flac_compression, out_rate=rate,
                                         transpositions=rows, formants=shifts,
-                                        f0s=None if contours is None else [contours[ii] for ii in sub]):
+                                        f0s=None if contours is None else [contours[ii] for ii in sub], level=part):
                 yield write, sb
 
     job.write_all(work())

@@ -15,6 +15,10 @@ Deviations (documented in INTEGRATION.md):
     reference's resampler (mbexwn_vocoder_amd/resample.py)
   * additionally ``--f0-dir DIR``: every file takes its pitch from ``DIR/NAME.f0`` (``generate_mel.py --write-f0``; text rows
     ``time_s f0_hz periodicity``, one per mel frame, 0 = unvoiced and filled from its neighbours) instead of the model's own F0
+  * additionally ``--loudness LUFS``, ``--peak-limit DBFS`` and ``--true-peak`` (mbexwn_vocoder_amd/level.py; DESIGN.md section
+    6m): every file is written at that BS.1770 loudness and / or below that peak, by one gain per file measured and applied on
+    the GPU; such a job runs through the micro-batches, of one file with ``--batch 1``, and the writer reports the level in
+    place of the clipping note
 """
 import json
 import os
@@ -29,15 +33,22 @@ if os.path.exists(test_path):
 
 from mbexwn_vocoder_amd import cli, mel_inverter  # noqa: E402
 from mbexwn_vocoder_amd.batched import load_contour, write_audio  # noqa: E402 -- the one-at-a-time loop's
+from mbexwn_vocoder_amd.level import level_control  # noqa: E402
 from mbexwn_vocoder_amd.noise import item_key  # noqa: E402
 from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 
 
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
          num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None,
-         flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant_shift=None, f0_dir=None):
+         flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant_shift=None, f0_dir=None,
+         loudness=None, peak_limit=None, true_peak=False):
     values = dict(locals())
     format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
+    try:
+        level = level_control(loudness, peak_limit, true_peak)
+    except ValueError as err:
+        print(f"resynth_mel::error:: {err}", file=sys.stderr)
+        sys.exit(1)
     if flac_compression != "verbatim" and rank is None and not quiet:
         from mbexwn_vocoder_amd.batched import have_soundfile
         if format.lower() != "flac" or have_soundfile():
@@ -86,12 +97,12 @@ def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, form
         if not quiet and not verbose:
             print(f"calibrated on {len(first)} file(s): convolution form {info['form']}", file=sys.stderr)
 
-    if batch > 1 or plan is not None:
+    if batch > 1 or plan is not None or level is not None:     # the level stage lives in the micro-batches, of one file too
         from mbexwn_vocoder_amd.batched import run_job
         run_job(MelInv, input_mell_files, output_dir, format, frames=plan["frames"] if plan else None,
                 mine=plan["shards"][rank] if plan else None, batch=batch, threads=num_threads, verbose=verbose, quiet=quiet,
                 flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed, transposition=transposition,
-                formant=formant_shift, f0_dir=f0_dir)
+                formant=formant_shift, f0_dir=f0_dir, level=level)
         return
     out_rate = MelInv._output_rate(out_rate)
 
@@ -185,6 +196,7 @@ def make_parser():
                         help="take the pitch of every file from DIR/NAME.f0 (as generate_mel.py --write-f0 writes it: text rows "
                              "`time_s f0_hz periodicity`, one per mel frame, 0 = unvoiced, filled from its neighbours) instead of "
                              "the model's own F0; --transposition multiplies on top (Def: none)")
+    cli.add_level_options(parser)                              # no source sound here: --loudness input is refused by name
     parser.add_argument("--rank", type=int, default=None, help=SUPPRESS)       # set by the parent of a --gpus job
     parser.add_argument("--job", default=None, help=SUPPRESS)
     return parser

@@ -34,8 +34,14 @@ ratio outside about 1/2 .. 2, a band too narrow) is reported and skipped like th
 
 --formant-shift F moves the formants of a file by the factor F (F > 1: up) at the same pitch and duration (DESIGN.md section
 6g; include/mbexwn_envelope.h): the VTF-net and the WaveNet conditioning read every mel row at f / F, the F0-net reads it as
-it is.  A factor of 1 is the job without the flag, launch by launch.  The level is not compensated.  The three controls
-combine freely.
+it is.  A factor of 1 is the job without the flag, launch by launch.  The level is not compensated (--loudness input does
+that).  The three controls combine freely.
+
+--loudness LUFS writes every file at that BS.1770 integrated loudness, --loudness input at the loudness of its source sound,
+measured as read (mbexwn_vocoder_amd/level.py; include/mbexwn_level.h): one static gain per file,
+measured and applied on the GPU between the output resampler and the FLAC encoder.  --peak-limit DBFS (default -1 with
+--loudness) scales a file down as a whole where it would peak above; alone it only ever scales down, so no file is written
+clipped.  --true-peak puts the limit on the 4x oversampled peak.  The writer reports loudness in -> out, gain and peak per file.
 
 --f0-source audio keeps the pitch that is in the sound instead of the pitch the model infers from the mel (DESIGN.md section
 6h; include/mbexwn_pitch.h): an F0 tracker runs on the frames of the mel analysis, between --f0-min and --f0-max Hz, its
@@ -62,6 +68,7 @@ if os.path.exists(test_path):
 from mbexwn_vocoder_amd import cli  # noqa: E402
 from mbexwn_vocoder_amd.batched import file_factors, file_stretches, read_transposition_file  # noqa: E402
 from mbexwn_vocoder_amd.cli import pitch_decode_params, weight_arg  # noqa: E402
+from mbexwn_vocoder_amd.level import check_options  # noqa: E402
 
 file_guides = partial(cli.file_guides, stretch_flags="--time-stretch or --time-stretch-file")
 factor_arg = stretch_arg = cli.positive_arg("factor")
@@ -75,9 +82,10 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
          batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None,
          formant_shift=1.0, formant_shift_file=None, f0_source="net", f0_min=55.0, f0_max=1000.0, write_f0=False,
          pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5, f0_fill="interpolate", f0_initial=150.0, align_to=None,
-         align_to_dir=None, align_band=1.0, pitch_lag=None):
+         align_to_dir=None, align_band=1.0, pitch_lag=None, loudness=None, peak_limit=None, true_peak=False):
     values = dict(locals())
     try:
+        check_options(loudness, peak_limit, true_peak, allow_input=True)
         guides, f0_decode, factors, stretches, formants = file_options(values)
         check_files(input_audio_files)
     except (OSError, ValueError) as err:
@@ -109,7 +117,7 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
                                 formants=None if all(ff == 1.0 for ff in formants) else formants, f0_source=f0_source,
                                 f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0, f0_decode=f0_decode,
                                 f0_fill=f0_fill, f0_initial=f0_initial, guides=guides, align_band_s=align_band,
-                                f0_lag=pitch_lag)
+                                f0_lag=pitch_lag, loudness=loudness, peak_limit=peak_limit, true_peak=true_peak)
     except ValueError as err:
         if guides is None:
             raise
@@ -258,6 +266,7 @@ def make_parser():
     parser.add_argument("--out-rate", dest="out_rate", default=None, type=out_rate_arg, metavar="R|input",
                         help="write the files at R Hz, resampled on the GPU from the model rate; input = every file at its "
                              "own rate (Def: the model rate)")
+    cli.add_level_options(parser, allow_input=True)
     parser.add_argument("--format", default="flac", help="file format for generated audio files (Def: %(default)s)")
     parser.add_argument("--flac-compression", default="verbatim", choices=["verbatim", "fixed"],
                         help="what the built-in FLAC writer emits, on the GPU: verbatim = uncompressed sub-frames; fixed = fixed "

@@ -1,4 +1,4 @@
-"""What the command-line tools under ``bin/`` share: argparse types, the guide and pitch-decode options, the model listing
+"""What the command-line tools under ``bin/`` share: argparse types, the guide, pitch-decode and level options, the model listing
 and the argv of a ``--gpus`` rank.  Plain functions; nothing here imports torch (the parent of a ``--gpus`` job never does)."""
 import os
 from argparse import ArgumentTypeError  # noqa: F401  (the tools catch it by this name)
@@ -55,6 +55,45 @@ def lag_arg(text):
     if not 0 <= value <= 128:
         raise ArgumentTypeError(f"a whole number of frames in 0 .. 128 is expected, got {text!r}")
     return value
+
+
+def loudness_arg(allow_input=False):
+    """argparse type of --loudness: a finite number of LUFS, with ``allow_input`` also the word "input".  A tool without a
+    source sound refuses "input" by name."""
+    def parse(text):
+        if text == "input":
+            if allow_input:
+                return text
+            raise ArgumentTypeError("'input' is the loudness of the source sound, and this tool reads none: a number of "
+                                    "LUFS is expected")
+        value = _number(text)
+        if value != value or value in (float("inf"), float("-inf")):
+            raise ArgumentTypeError("a loudness in LUFS" + (" or 'input'" if allow_input else "") + f" is expected, got {text!r}")
+        return value
+    return parse
+
+
+def decibel_arg(text):
+    """argparse type of --peak-limit: a finite number of dBFS."""
+    value = _number(text)
+    if value != value or value in (float("inf"), float("-inf")):
+        raise ArgumentTypeError(f"a peak level in dBFS is expected, got {text!r}")
+    return value
+
+
+def add_level_options(parser, allow_input=False):
+    """--loudness, --peak-limit and --true-peak (level.py), the same in every file tool; what they
+    say together -- the default of --peak-limit, --true-peak without a peak to limit -- is ``level.check_options``."""
+    parser.add_argument("--loudness", default=None, type=loudness_arg(allow_input), metavar="LUFS|input" if allow_input else "LUFS",
+                        help="write every file at this BS.1770 integrated loudness, measured and gained on the GPU"
+                             + ("; input = at the loudness of its source sound" if allow_input else "")
+                             + " (Def: the level the model gives)")
+    parser.add_argument("--peak-limit", dest="peak_limit", default=None, type=decibel_arg, metavar="DBFS",
+                        help="no file peaks above DBFS: a file that would is scaled down as a whole; usable without "
+                             "--loudness, where it only ever scales down (Def: -1.0 with --loudness, else none)")
+    parser.add_argument("--true-peak", dest="true_peak", action="store_true",
+                        help="--peak-limit is about the true peak, the maximum of the signal at four times its rate, not the "
+                             "sample peak")
 
 
 def file_guides(files, align_to=None, align_to_dir=None, align_band=1.0, time_stretch=1.0, time_stretch_file=None,

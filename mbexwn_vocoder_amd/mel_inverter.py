@@ -249,7 +249,7 @@ class MELInverter(object):
 
     def synth_from_mels(self, scaled_mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False,
                         flac_compression="verbatim", out_rate=None, noise_seed=None, noise_keys=None, transpositions=None,
-                        formants=None, f0s=None):
+                        formants=None, f0s=None, loudness=None, peak_limit=None, true_peak=False, levels_out=None):
         """Batched :meth:`synth_from_mel` (this build): a list of ``scale_mel`` outputs (1, T_i, mel_channels) -> a list of
         float32 audio (T_i * hop_size,), or with ``flac=True`` of complete FLAC files (bytes; frames encoded on the device).
 
@@ -270,9 +270,21 @@ class MELInverter(object):
         (T_i,) of them (:meth:`synth_from_mel` ``formant``; the ``formant`` rows of the forward).  ``f0s``: per item None, or
         (T_i,) Hz, one value per mel frame, positive and finite, in place of the F0-net's contour (:meth:`synth_from_mel`
         ``f0``; the ``f0_frames`` rows of the forward) -- an item with None keeps the F0-net (``f0_item_mask``), the
-        transposition multiplies on top, and a wrong length or value is refused before anything runs."""
+        transposition multiplies on top, and a wrong length or value is refused before anything runs.
+
+        Level (level.py): ``loudness`` -- None, a BS.1770 integrated loudness in LUFS every item comes
+        out at, or a list with, per item, a target POWER (``level.target_power``, or the P of another measurement) or None;
+        ``peak_limit`` -- a ceiling in dBFS on the item's peak (default: -1 with a loudness, else none; alone it only ever
+        scales down); ``true_peak`` -- the ceiling is about the 4x oversampled peak.  One static gain per item, measured and
+        applied on the device behind the forward and the output resampler: what comes back -- audio or FLAC -- is the
+        gained audio, measured at the rate it has.  ``levels_out``: a list that receives ``SynthBatch.level`` of every item,
+        in item order.  None of them: the launches of before."""
         import torch
         from .batched import check_f0s, replay_noise, run_micro_batches
+        from .level import level_control
+        control = level_control(loudness, peak_limit, true_peak)
+        if control is not None and isinstance(control.target, list) and len(control.target) != len(scaled_mels):
+            raise ValueError("synth_from_mels: a loudness list takes one entry per mel")
         if noise_seed is not None and noises is not None:
             raise ValueError("noises= and noise_seed= exclude each other: the keyed draw replaces the injected one")
         if noise_seed is None and noise_keys is not None:
@@ -301,12 +313,13 @@ class MELInverter(object):
         else:
             noises = [torch.as_tensor(np.asarray(zz) if not torch.is_tensor(zz) else zz).to(self.model.device, torch.float32)
                       .reshape(-1) for zz in noises]
-        out = [None] * len(mels)
+        out, reports = [None] * len(mels), [None] * len(mels)
         for batch in run_micro_batches(self.model, mels, noises, max_batch, max_padded_frames, flac=flac, host_audio=not flac,
                                        flac_compression=flac_compression, out_rate=out_rate, transpositions=transpositions,
-                                       formants=formants, f0s=f0s):
+                                       formants=formants, f0s=f0s, level=control):
             batch.wait()
             for jj, ii in enumerate(batch.indices):
+                reports[ii] = batch.level(jj)
                 if not flac:
                     out[ii] = batch.audio(jj)
                 elif np.isfinite(batch.flac.max_abs[jj]):
@@ -314,12 +327,25 @@ class MELInverter(object):
                 else:
                     from . import flac as flac_writer
                     out[ii] = flac_writer.encode(batch.audio(jj), rate, flac_compression)
+        if levels_out is not None:
+            levels_out.extend(reports)
         return out
+
+    def measure_loudness(self, snd, srate, true_peak=False):
+        """The BS.1770 measure of a single sound at ``srate`` (this build; level.py), on the device: a
+        ``level.Measure`` -- ``lufs`` (-inf when ``count`` is 0: under 0.4 s, or silent), ``power``, ``sample_peak`` and,
+        asked for, the 4x ``true_peak``.  ``level.measure_host`` is its definition."""
+        import torch
+        from . import level
+        snd = np.ascontiguousarray(np.asarray(snd).reshape(-1), dtype=np.float32)
+        audio = torch.as_tensor(snd[np.newaxis]).to(self.model.device)
+        return level.measure_device(audio, [snd.size], int(round(srate)), true_peak).host()[0]
 
     def transform_audio(self, sounds, rates, names, transposition=1.0, noise_seed=0, out_rate=None, max_batch=16,
                         max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None, formant=None,
                         f0_source="net", f0_params=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0,
-                        align_to=None, align_band_s=1.0, f0_lag=None):
+                        align_to=None, align_band_s=1.0, loudness=None, peak_limit=None, true_peak=False, levels_out=None,
+                        f0_lag=None):
         """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
         keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
         factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
@@ -359,16 +385,23 @@ class MELInverter(object):
         ``time_stretch``; one that cannot be aligned raises ``align.AlignError``.  Everything else works on its frames as on
         any others.
 
+        ``loudness`` / ``peak_limit`` / ``true_peak`` / ``levels_out``: the level of what comes back, as in
+        :meth:`synth_from_mels` -- and ``loudness="input"``: every item comes out at the loudness of its source, which is
+        measured as handed in, at its own rate, on the device in the micro-batches the analysis stages; a source that is not
+        measurable leaves the loudness gain at 1 (the ceiling still applies).
+
         An item's audio is a function of (sound, rate, name, factor, stretch, formant, seed, out_rate): with a ``batch_invariant``
         engine or one pinned to a convolution form it does not depend on the batch, the order or the other items."""
         from . import align, timemap
         from .batched import analyse_for_synthesis
+        from .level import check_options
         from .noise import item_key
         factors = check_factors(transposition, len(sounds))
         if not (len(sounds) == len(rates) == len(names)):
             raise ValueError("transform_audio: one rate and one name per sound")
         if formant is not None and (not isinstance(formant, (list, tuple)) or len(formant) != len(sounds)):
             raise ValueError("transform_audio: formant takes one entry per sound")
+        loudness, peak_limit, true_peak = check_options(loudness, peak_limit, true_peak, allow_input=True)   # before anything runs
         guided = align_to is not None and any(gg is not None for gg in align_to)
         if guided and len(align_to) != len(sounds):
             raise ValueError("transform_audio: align_to takes one entry per sound")
@@ -377,7 +410,9 @@ class MELInverter(object):
                                      guide_rates=[None if gg is None else gg[1] for gg in align_to] if guided else None,
                                      align_band_s=align_band_s, f0_source=f0_source, f0_params=f0_params, f0_decode=f0_decode,
                                      f0_fill=f0_fill, f0_initial=f0_initial, batch=max_batch, who="transform_audio",
-                                     f0_lag=f0_lag)
+                                     f0_lag=f0_lag, source_levels=isinstance(loudness, str))
+        if isinstance(loudness, str):
+            loudness = [power if count else None for power, count in done.levels]
         for ii, mel in enumerate(done.scaled):
             if mel is None:
                 raise align.AlignError(done.notes[ii]["error"])
@@ -385,7 +420,8 @@ class MELInverter(object):
         return self.synth_from_mels(done.scaled, max_batch=max_batch, max_padded_frames=max_padded_frames, flac=flac,
                                     flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed,
                                     noise_keys=[item_key(nn) for nn in names], transpositions=rows, formants=formant,
-                                    f0s=done.contours)
+                                    f0s=done.contours, loudness=loudness, peak_limit=peak_limit, true_peak=true_peak,
+                                    levels_out=levels_out)
 
     def track_f0(self, snd, srate, on_device=False, decode=None, f0_lag=None, **f0_params):
         """The pitch of a single sound (this build): (times in s, f0 in Hz with 0 = unvoiced, periodicity), one value per mel

@@ -1,5 +1,5 @@
 """ctypes binding of libmbexwn_hip.so: the structures and constants of include/mbexwn.h, and ONE table of every function the
-fifteen headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
+sixteen headers under include/ declare, from which ``load_library`` sets each ``restype`` / ``argtypes``.
 
 Nothing else lives here: a tool that only resamples imports this module, not the engine's driver.  The table is declared in
 Python (the package loads without include/ beside it); tests/test_abi_headers.py holds it to the headers name by name and
@@ -178,6 +178,11 @@ TABLE = {
         ("mbxl_measure", i32, [vp, i64, i32, i64p, P(i32), P(ctypes.c_double), P(ctypes.c_double), vp, i32, vp, i32, vp, vp]),
         ("mbxl_gains", i32, [vp, i32, P(ctypes.c_double), vp, P(ctypes.c_double), i32, vp, vp]),
         ("mbxl_apply", i32, [vp, i64, i32, i64p, vp, vp, i64, vp])],
+    # n_samples is a HOST array; audio, stride, batch, n_samples, gains, ceiling, h, hold, weights, taps, n_taps, out, ...
+    "mbexwn_limiter.h": [
+        ("mbxd_limit", i32, [vp, i64, i32, i64p, vp, f32, i32, i32, vp, vp, i32, vp, i64, vp, vp, i64, vp]),
+        ("mbxd_limit_workspace_floats", size_t, [i64, i32, i32, i32, i32]),
+        ("mbxd_limit_emit", i32, [vp, i32, i32, vp, i32, i32, f32, i32, i32, vp, vp, i64, vp, vp])],
 }
 
 

@@ -136,21 +136,37 @@ class SynthBatch:
         """What the level stage did to item jj (after :meth:`wait`; None for a batch without the stage): a dict with
         ``loudness_in`` and ``loudness_out`` in LUFS (-inf: not measurable), ``gain`` (the float32 factor), ``gain_db``,
         ``peak_in`` and ``peak_out`` (linear; the true peak where the stage was asked for it) and ``limited`` -- the
-        ceiling, not the target, set the gain."""
+        ceiling, not the target, set the gain.  With the limiter ``limited`` is False, the loudness and
+        the peak that came out are those of a second measurement, and ``limiter`` holds ``reduction_db`` (the deepest gain
+        reduction), ``limited`` and ``clamped`` (samples with a gain below 1, samples the clamp moved) and ``trim_db`` (the
+        ceiling-only gain behind the limiter with ``true_peak``; 0 without)."""
         if self._level is None:
             return None
         from . import level as lv
-        control, powers, records, gains = self._level
+        control, powers, records, gains = self._level[:4]
         self.wait()
         power, count, _, sample_peak, true_peak = lv.DeviceMeasure.unpack(records.numpy(), jj)
         peak = true_peak if control.true_peak else sample_peak
         gain = float(gains.numpy()[jj])
-        _, limited = lv.gain_host(power, count, peak, powers[jj], lv.ceiling_linear(control.peak_limit))
         loud = lv.lufs(power) if count else float("-inf")
         with np.errstate(divide="ignore"):
             gain_db = float(20.0 * np.log10(np.float64(gain)))
-        return {"loudness_in": loud, "loudness_out": loud + gain_db, "gain": gain, "gain_db": gain_db, "peak_in": float(peak),
-                "peak_out": float(np.float32(peak) * np.float32(gain)), "limited": bool(limited)}
+        if not control.limiter:
+            _, limited = lv.gain_host(power, count, peak, powers[jj], lv.ceiling_linear(control.peak_limit))
+            return {"loudness_in": loud, "loudness_out": loud + gain_db, "gain": gain, "gain_db": gain_db, "peak_in": float(peak),
+                    "peak_out": float(np.float32(peak) * np.float32(gain)), "limited": bool(limited)}
+        # the limiter: the loudness and the peak that came out are measured, not derived
+        from .limiter import LimitStats
+        stats = LimitStats.from_words(self._level[4].numpy()[jj])
+        power_out, count_out, _, sample_out, true_out = lv.DeviceMeasure.unpack(self._level[5].numpy(), jj)
+        trim = float(self._level[6].numpy()[jj]) if len(self._level) > 6 else 1.0
+        with np.errstate(divide="ignore"):
+            trim_db = float(20.0 * np.log10(np.float64(trim)))
+        return {"loudness_in": loud, "loudness_out": (lv.lufs(power_out) if count_out else float("-inf")) + trim_db, "gain": gain,
+                "gain_db": gain_db, "peak_in": float(peak),
+                "peak_out": float(np.float32(true_out if control.true_peak else sample_out) * np.float32(trim)),
+                "limited": False, "limiter": {"reduction_db": stats.reduction_db, "limited": stats.limited,
+                                              "clamped": stats.clamped, "trim_db": trim_db}}
 
     def max_abs(self, jj):
         if self.flac is not None:
@@ -238,13 +254,17 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
     takes one gain from its target and the ceiling (``level.gains_device``) and is multiplied by it (``level.apply_device``)
     -- all on the device, nothing waited for.  The FLAC frames, ``pcm``, MD5, ``max_abs`` and the host audio are those of the
     gained audio; ``SynthBatch.model_audio`` keeps the ungained model-rate audio and ``SynthBatch.level`` reports.  A
-    per-item target list is indexed like ``mels``.  None: the launches of before."""
+    per-item target list is indexed like ``mels``.  None: the launches of before.  With ``level.limiter`` (DESIGN.md section
+    6n) the gain comes without the ceiling, the look-ahead limiter (``limiter.limit_device``) keeps the ceiling, the result
+    is measured again, and with ``true_peak`` a ceiling-only gain follows; without it, the launches of before."""
     f0s = check_f0s(f0s, [int(mm.shape[0]) for mm in mels])
     import torch
     from .mel_inverter import KeyedNoise
     dims = engine.dims
     if out_rate is not None and int(round(out_rate)) == int(round(dims.sample_rate)):
         out_rate = None
+    if level is not None:
+        level.check_rates([dims.sample_rate if out_rate is None else out_rate])     # the limiter's window: before anything runs
     lengths = [int(mm.shape[0]) for mm in mels]
     stream = torch.cuda.current_stream(engine.device)
     for group in plan_batches(range(len(mels)), lengths, max_batch, max_padded_frames):
@@ -280,13 +300,33 @@ def run_micro_batches(engine, mels, noises=None, max_batch=16, max_padded_frames
             else:
                 gained = None                               # the resampler's output is this batch's own: in place
             audio = audio.contiguous()
-            measure = lv.measure_device(audio, n_samples, dims.sample_rate if out_rate is None else out_rate, level.true_peak)
-            gains = lv.gains_device(measure, powers, ceiling=lv.ceiling_linear(level.peak_limit), true_peak=level.true_peak)
-            audio = lv.apply_device(audio, n_samples, gains, out=gained)
-            pinned = [torch.empty(tuple(tt.shape), dtype=tt.dtype, pin_memory=True) for tt in (measure.records, gains)]
-            pinned[0].copy_(measure.records, non_blocking=True)
-            pinned[1].copy_(gains, non_blocking=True)
-            report = (level, powers, pinned[0], pinned[1])
+            rate = dims.sample_rate if out_rate is None else out_rate
+            measure = lv.measure_device(audio, n_samples, rate, level.true_peak)
+            if not level.limiter:
+                gains = lv.gains_device(measure, powers, ceiling=lv.ceiling_linear(level.peak_limit), true_peak=level.true_peak)
+                audio = lv.apply_device(audio, n_samples, gains, out=gained)
+                results = (measure.records, gains)
+            else:
+                # the loudness gain stands: no ceiling in it.  The limiter keeps the ceiling; what it wrote is measured again, and with the true peak a ceiling-only gain follows,
+                # because the gain's modulation moves the peaks between the samples a little
+                from . import limiter as lm
+                ceiling = lv.ceiling_linear(level.peak_limit)
+                h, hold = level.window(rate)
+                gains = lv.gains_device(measure, powers)
+                # the resampler's output is this batch's own: in place, as the static gain (the margins of the tiles go
+                # through a workspace of (3 h + hold) / 2048 of the audio)
+                audio, stats = lm.limit_device(audio, n_samples, gains, ceiling, h, hold, rate=rate, true_peak=level.true_peak,
+                                               out=audio if gained is None else gained)
+                after = lv.measure_device(audio, n_samples, rate, level.true_peak)
+                results = (measure.records, gains, stats, after.records)
+                if level.true_peak:
+                    trim = lv.gains_device(after, None, ceiling=lm.trim_ceiling(ceiling), true_peak=True)
+                    audio = lv.apply_device(audio, n_samples, trim)
+                    results += (trim,)
+            pinned = [torch.empty(tuple(tt.shape), dtype=tt.dtype, pin_memory=True) for tt in results]
+            for host_copy, tt in zip(pinned, results):
+                host_copy.copy_(tt, non_blocking=True)
+            report = (level, powers) + tuple(pinned)
         enc = None
         if flac:
             enc = engine.encode_flac16(audio, n_samples, sample_rate=None if out_rate is None else int(round(out_rate)),
@@ -360,6 +400,10 @@ def level_line(outfile, report):
     else:
         loud = "loudness not measurable (under 0.4 s, or silent)"
     why = " (the peak limit, not the loudness, set the gain)" if report["limited"] else ""
+    if report.get("limiter"):
+        lim = report["limiter"]
+        why = (f", limiter: {lim['reduction_db']:.2f} dB at most, {lim['limited']} samples limited, {lim['clamped']} clamped"
+               + (f", trim {lim['trim_db']:+.3f} dB" if lim["trim_db"] != 0.0 else ""))
     return f"    level of {outfile}: {loud}, gain {report['gain_db']:+.2f} dB, peak {db(report['peak_out'])} dBFS{why}"
 
 
@@ -532,7 +576,8 @@ def read_sound(path):
 def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=None, batch=16, threads=2, verbose=False,
                   quiet=False, flac_compression="verbatim", out_rate=None, stretches=None, formants=None, f0_source="net",
                   f0_params=None, write_f0=False, timings=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0,
-                  guides=None, align_band_s=1.0, loudness=None, peak_limit=None, true_peak=False, f0_lag=None):
+                  guides=None, align_band_s=1.0, loudness=None, peak_limit=None, true_peak=False, *, limiter=False,
+                  lookahead_ms=None, hold_ms=None, f0_lag=None):
     """The file-to-file tool on this process's GPU: sound files ``files[mine]`` -> transposed syn_<basename>.<fmt> in
     ``output_dir``.  Returns the (file, reason) pairs it skipped: files without samples or with more than one channel.
 
@@ -570,12 +615,19 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     read, at its own rate, on the device in the micro-batches the analysis stages (``generate_mels(levels_out=)``); a source
     that is not measurable leaves the loudness gain at 1.  ``peak_limit``: a ceiling in dBFS (default: -1 with a loudness, else
     none); ``true_peak``: on the 4x true peak.  DESIGN.md section 6m.  None of them: the launches and the bytes of before.
+    ``limiter``: the look-ahead limiter keeps the ceiling in place of the static gain (``lookahead_ms`` / ``hold_ms``: its
+    window); without it, the launches and the bytes of before.
     ``timings``: a dict that receives the seconds per stage the
     verbose line reports (upload, resample, analysis, f0, copy_back from ``generate_mels``; read, scale, device, copy, write
     from the pools and the micro-batches' events; wall)."""
     from . import f0track
     from .level import check_options, level_control
-    loudness, peak_limit, true_peak = check_options(loudness, peak_limit, true_peak, allow_input=True)   # before anything runs
+    loudness, peak_limit, true_peak = check_options(loudness, peak_limit, true_peak, allow_input=True, limiter=limiter,
+                                                    lookahead_ms=lookahead_ms, hold_ms=hold_ms)   # before anything runs
+    window_check = level_control(None if isinstance(loudness, str) else loudness, peak_limit, true_peak, limiter, lookahead_ms,
+                                 hold_ms)
+    if window_check is not None and out_rate != "input":   # the limiter's window at the rate of the files: before anything runs
+        window_check.check_rates([inv.srate if out_rate is None else out_rate])
     job = _Job(threads)
     mine = list(range(len(files))) if mine is None else list(mine)
     factors = [1.0] * len(files) if factors is None else list(factors)
@@ -585,6 +637,8 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
     stats = {}
     with ThreadPoolExecutor(max_workers=job.threads) as pool:                                   # the readers, then scale_mel
         loaded, guide_sounds, mine, maps, skipped = _load_sounds(job, pool, inv, files, mine, guides, stretches)
+        if window_check is not None and out_rate == "input":       # ... at every file's own rate: known once they are read
+            window_check.check_rates([loaded[ii][1] for ii in mine] or [inv.srate])
         have_guides = guides is not None and any(guides[ii] is not None for ii in mine)
         scale = job.timed("scale", lambda dd: inv.scale_mel(dd, verbose=verbose))
         try:
@@ -623,7 +677,7 @@ def run_audio_job(inv, files, output_dir, fmt, factors=None, noise_seed=0, mine=
         for local in keep:
             power, count = done.levels[local]
             loudness[mine[local]] = power if count else None
-    control = level_control(loudness, peak_limit, true_peak)
+    control = level_control(loudness, peak_limit, true_peak, limiter, lookahead_ms, hold_ms)
     mine = [mine[local] for local in keep]
     rates = {ii: loaded[ii][1] if out_rate == "input" else out_rate for ii in mine}
     _synthesise_files(job, inv, files, mine, scaled, contours, rates, output_dir, fmt, factors, formants, noise_seed, batch,
@@ -773,7 +827,7 @@ def _synthesise_files(job, inv, files, mine, scaled, contours, rates, output_dir
             shifts = None if formants is None else [np.full(int(scaled[ii].shape[1]), formants[ii], dtype=np.float32) for ii in sub]
             part = level
             if level is not None and isinstance(level.target, (list, tuple)):
-                part = LevelControl([level.target[ii] for ii in sub], level.peak_limit, level.true_peak)
+                part = level.sliced(sub)
             for sb in run_micro_batches(inv.model, [scaled[ii][0] for ii in sub], noises, max(1, batch), flac=device_flac,
                                         host_audio=verbose or not device_flac, flac_compression=flac_compression, out_rate=rate,
                                         transpositions=rows, formants=shifts,

@@ -41,11 +41,12 @@ from mbexwn_vocoder_amd.fileio import load_var  # noqa: E402
 def main(model_id, input_mell_files, output_dir, use_gpu=False, sigma=None, format=None, verbose=False, seed=42,
          num_threads=2, quiet=False, calibrate=0, batch=1, gpus=1, batch_invariant=False, conv_form="auto", rank=None, job=None,
          flac_compression="verbatim", out_rate=None, noise_seed=None, transposition=None, formant_shift=None, f0_dir=None,
-         loudness=None, peak_limit=None, true_peak=False):
+         loudness=None, peak_limit=None, true_peak=False, limiter=False, limiter_lookahead=None, limiter_hold=None):
     values = dict(locals())
     format = format or "flac"                                   # the reference's default (bin/resynth_mel.py:119)
     try:
-        level = level_control(loudness, peak_limit, true_peak)
+        level = level_control(loudness, peak_limit, true_peak, limiter, limiter_lookahead, limiter_hold)
+        cli.check_limiter_rate(model_id, out_rate, limiter, limiter_lookahead, limiter_hold, true_peak)
     except ValueError as err:
         print(f"resynth_mel::error:: {err}", file=sys.stderr)
         sys.exit(1)

@@ -4,6 +4,7 @@ pushes, as a live source would deliver it, and writes what the stream gives back
 
     stream_transpose.py in.wav -o out.wav --model_id VOICE --transposition 1.5 [--formant-shift F] [--tick-ms 80]
                         [--resample] [--output-rate R|input]
+                        [--peak-limit DBFS [--gain DB] [--limiter-lookahead MS] [--limiter-hold MS]]
                         [--f0-source audio [--f0-min HZ --f0-max HZ --f0-initial HZ] [--write-f0]
                          [--pitch-decode viterbi [--pitch-lag N --pitch-jump W --pitch-switch W]]]
 
@@ -25,6 +26,11 @@ frames are 100 ms at hop 300 / 24 kHz): a frame is decided, and synthesised, onc
 which removes the octave jumps of the frame-by-frame pick at the price of that much more look-ahead.  The output -- and the
 contour ``--write-f0`` writes -- is then what ``transform_audio.py --f0-source audio --pitch-decode viterbi --pitch-lag N
 --f0-fill hold`` gives for the file under the same ``--noise-seed``.
+
+``--peak-limit DBFS`` keeps the stream under that ceiling with the look-ahead peak limiter, the last
+stage of the stream, at the rate the output is written at; ``--gain DB`` is the fixed gain in front of it (a stream has no
+integrated loudness), ``--limiter-lookahead`` and ``--limiter-hold`` its window in ms.  A stream that overshoots -- a formant
+shift or a transposition does that -- is otherwise handed out over full scale.
 """
 import os
 import sys
@@ -43,13 +49,15 @@ from mbexwn_vocoder_amd.live import check_rate  # noqa: E402
 
 def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0, sample_rate=None, output_rate=None,
                 noise_fn=None, formant=None, f0_source="net", f0_params=None, f0_initial=150.0, f0_out=None, f0_decode=None,
-                f0_lag=None):
+                f0_lag=None, level=None):
     """Push `samples` in pieces of tick_samples, one tick per push, until the stream is finished; returns its audio.
     ``sample_rate``: the rate of `samples` when it is not the model's (the stream resamples); ``output_rate``: the rate the
     audio comes back at when it is not the model's (a rate in Hz, or "input"); ``noise_fn``: the stream's noise instead of the
     generator seeded with ``seed`` (``live.keyed_noise_fn``); ``formant``: a formant-shift factor given with every push; ``f0_source``,
     ``f0_params``, ``f0_initial``, ``f0_decode``, ``f0_lag``: as for ``LiveResynthesizer.open``; ``f0_out``: a list that
-    receives the stream's tracked (f0, periodicity), one pair of arrays per tick that handed out (with a lag: decided) rows."""
+    receives the stream's tracked (f0, periodicity), one pair of arrays per tick that handed out (with a lag: decided) rows;
+    ``level``: None, or the keywords ``gain_db``, ``peak_limit``, ``limiter_lookahead_ms``, ``limiter_hold_ms`` of
+    ``LiveResynthesizer.open``."""
     rates = {} if sample_rate is None else {"sample_rate": sample_rate}
     if f0_source != "net":
         rates.update(f0_source=f0_source, f0_params=f0_params, f0_initial=f0_initial)
@@ -64,6 +72,7 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0,
 
     if output_rate is not None:
         rates["output_rate"] = output_rate
+    rates.update(level or {})
     live.open(stream_id, seed=seed, noise_fn=noise_fn, **rates)
     out = []
     for start in range(0, samples.size, tick_samples):
@@ -82,7 +91,8 @@ def stream_file(live, samples, tick_samples, transposition, seed=0, stream_id=0,
 
 def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tick_ms=80.0, seed=0, quiet=False,
          resample=False, output_rate=None, noise_seed=None, formant_shift=1.0, f0_source="net", f0_min=55.0, f0_max=1000.0,
-         f0_initial=150.0, write_f0=False, pitch_decode="greedy", pitch_lag=8, pitch_jump=4.0, pitch_switch=0.5):
+         f0_initial=150.0, write_f0=False, pitch_decode="greedy", pitch_lag=8, pitch_jump=4.0, pitch_switch=0.5, gain=None,
+         peak_limit=None, limiter_lookahead=None, limiter_hold=None):
     preprocess_config = read_config(config_file=get_config_file(model_id_or_path=model_id))['preprocess_config']
     if not os.path.isfile(input_audio_file):
         print(f"stream_transpose::error:: no such file: {input_audio_file}", file=sys.stderr)
@@ -117,6 +127,16 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
             f0_params = f0track.params(model_rate, f0_min=f0_min, f0_max=f0_max)
             if not (np.isfinite(f0_initial) and f0_initial > 0):
                 raise ValueError("--f0-initial must be finite and positive")
+        level = None
+        if peak_limit is None:
+            if gain is not None or limiter_lookahead is not None or limiter_hold is not None:
+                raise ValueError("--gain, --limiter-lookahead and --limiter-hold go with --peak-limit")
+        else:
+            from mbexwn_vocoder_amd import limiter
+            level = {"gain_db": 0.0 if gain is None else gain, "peak_limit": peak_limit,
+                     "limiter_lookahead_ms": limiter_lookahead, "limiter_hold_ms": limiter_hold}
+            written_rate = model_rate if output_rate is None else int(round(rate)) if output_rate == "input" else int(output_rate)
+            limiter.check_window(*limiter.window(written_rate, level["limiter_lookahead_ms"], level["limiter_hold_ms"]))
     except (ValueError, cli.ArgumentTypeError) as err:
         print(f"stream_transpose::error:: {err}", file=sys.stderr)
         sys.exit(1)
@@ -138,7 +158,7 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
     audio = stream_file(live, samples, tick_samples, transposition, seed=seed, sample_rate=own_rate,
                         output_rate=out_rate if out_rate != model_rate else None,
                         formant=None if formant_shift == 1.0 else formant_shift, f0_source=f0_source, f0_params=f0_params,
-                        f0_initial=f0_initial, f0_out=tracked, f0_decode=f0_decode, f0_lag=f0_lag, **keyed)
+                        f0_initial=f0_initial, f0_out=tracked, f0_decode=f0_decode, f0_lag=f0_lag, level=level, **keyed)
     out_dir = os.path.dirname(os.path.abspath(output_file))
     os.makedirs(out_dir, exist_ok=True)
     ext = os.path.splitext(output_file)[1].lower().lstrip(".") or "wav"
@@ -153,7 +173,7 @@ def main(input_audio_file, output_file, model_id="VOICE", transposition=1.0, tic
                          f0track.frame_times(f0.size, int(preprocess_config["hop_size"]), model_rate), f0, periodicity)
     if not quiet:
         print(f"{input_audio_file}: {samples.size} samples in pushes of {tick_samples} -> {audio.size} samples, transposed by "
-              f"{transposition}, look-ahead {live.lookahead_ms_for(own_rate, out_rate, f0_source, f0_params, f0_lag):.1f} ms, saved at {out_rate} Hz under {output_file}",
+              f"{transposition}, look-ahead {live.lookahead_ms_for(own_rate, out_rate, f0_source, f0_params, f0_lag, peak_limit, limiter_lookahead):.1f} ms, saved at {out_rate} Hz under {output_file}",
               file=sys.stderr)
 
 
@@ -201,6 +221,15 @@ def make_parser():
                         help="--pitch-decode viterbi: weight of a pitch jump between two frames (Def: %(default)s)")
     parser.add_argument("--pitch-switch", dest="pitch_switch", default=0.5, type=cli.weight_arg, metavar="W",
                         help="--pitch-decode viterbi: cost of a change between voiced and unvoiced (Def: %(default)s)")
+    parser.add_argument("--peak-limit", dest="peak_limit", default=None, type=cli.decibel_arg, metavar="DBFS",
+                        help="keep the stream under DBFS with the look-ahead peak limiter on the device, the last stage of the "
+                             "stream (Def: no limiter)")
+    parser.add_argument("--gain", default=None, type=cli.decibel_arg, metavar="DB",
+                        help="--peak-limit: a fixed gain in front of the limiter (Def: 0)")
+    parser.add_argument("--limiter-lookahead", dest="limiter_lookahead", default=None, type=cli.positive_ms_arg, metavar="MS",
+                        help="--peak-limit: the limiter's look-ahead, which the stream's look-ahead grows by (Def: 1.5)")
+    parser.add_argument("--limiter-hold", dest="limiter_hold", default=None, type=cli.positive_ms_arg, metavar="MS",
+                        help="--peak-limit: the limiter's hold (Def: 20)")
     parser.add_argument("--seed", default=0, type=int, help="seed of the stream's noise generator (Def: %(default)s)")
     parser.add_argument("--noise-seed", dest="noise_seed", default=None, type=int, metavar="S",
                         help="draw the stream's noise keyed by (S, the file's basename) and the absolute step, as "

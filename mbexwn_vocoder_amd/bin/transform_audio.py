@@ -42,6 +42,9 @@ measured as read (mbexwn_vocoder_amd/level.py; include/mbe
 measured and applied on the GPU between the output resampler and the FLAC encoder.  --peak-limit DBFS (default -1 with
 --loudness) scales a file down as a whole where it would peak above; alone it only ever scales down, so no file is written
 clipped.  --true-peak puts the limit on the 4x oversampled peak.  The writer reports loudness in -> out, gain and peak per file.
+--limiter keeps the ceiling (-1 dBFS unless --peak-limit says otherwise) with a look-ahead peak limiter on the GPU in place of
+the one gain, so that the loudness stands although single peaks are in its way (--limiter-lookahead / --limiter-hold MS: its
+window); the writer then reports the loudness and the peak measured behind it and what it did.
 
 --f0-source audio keeps the pitch that is in the sound instead of the pitch the model infers from the mel (DESIGN.md section
 6h; include/mbexwn_pitch.h): an F0 tracker runs on the frames of the mel analysis, between --f0-min and --f0-max Hz, its
@@ -82,10 +85,13 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
          batch_invariant=False, verbose=False, quiet=False, rank=None, job=None, time_stretch=1.0, time_stretch_file=None,
          formant_shift=1.0, formant_shift_file=None, f0_source="net", f0_min=55.0, f0_max=1000.0, write_f0=False,
          pitch_decode="greedy", pitch_jump=4.0, pitch_switch=0.5, f0_fill="interpolate", f0_initial=150.0, align_to=None,
-         align_to_dir=None, align_band=1.0, pitch_lag=None, loudness=None, peak_limit=None, true_peak=False):
+         align_to_dir=None, align_band=1.0, pitch_lag=None, loudness=None, peak_limit=None, true_peak=False, limiter=False,
+         limiter_lookahead=None, limiter_hold=None):
     values = dict(locals())
     try:
-        check_options(loudness, peak_limit, true_peak, allow_input=True)
+        check_options(loudness, peak_limit, true_peak, allow_input=True, limiter=limiter, lookahead_ms=limiter_lookahead,
+                      hold_ms=limiter_hold)
+        cli.check_limiter_rate(model_id, out_rate, limiter, limiter_lookahead, limiter_hold, true_peak)
         guides, f0_decode, factors, stretches, formants = file_options(values)
         check_files(input_audio_files)
     except (OSError, ValueError) as err:
@@ -117,9 +123,10 @@ def main(input_audio_files, output_dir, model_id="VOICE", transposition=1.0, tra
                                 formants=None if all(ff == 1.0 for ff in formants) else formants, f0_source=f0_source,
                                 f0_params={"f0_min": f0_min, "f0_max": f0_max}, write_f0=write_f0, f0_decode=f0_decode,
                                 f0_fill=f0_fill, f0_initial=f0_initial, guides=guides, align_band_s=align_band,
-                                f0_lag=pitch_lag, loudness=loudness, peak_limit=peak_limit, true_peak=true_peak)
+                                f0_lag=pitch_lag, loudness=loudness, peak_limit=peak_limit, true_peak=true_peak,
+                                limiter=limiter, lookahead_ms=limiter_lookahead, hold_ms=limiter_hold)
     except ValueError as err:
-        if guides is None:
+        if guides is None and not str(err).startswith("limiter:"):
             raise
         print(f"transform_audio::error:: {err}", file=sys.stderr)       # a band or a length the alignment refuses
         sys.exit(1)

@@ -82,8 +82,9 @@ def decibel_arg(text):
 
 
 def add_level_options(parser, allow_input=False):
-    """--loudness, --peak-limit and --true-peak (level.py), the same in every file tool; what they
-    say together -- the default of --peak-limit, --true-peak without a peak to limit -- is ``level.check_options``."""
+    """--loudness, --peak-limit and --true-peak (level.py) and --limiter, --limiter-lookahead and
+    --limiter-hold (limiter.py; section 6n), the same in every file tool; what they say together -- the default of
+    --peak-limit, --true-peak without a peak to limit, a window without --limiter -- is ``level.check_options``."""
     parser.add_argument("--loudness", default=None, type=loudness_arg(allow_input), metavar="LUFS|input" if allow_input else "LUFS",
                         help="write every file at this BS.1770 integrated loudness, measured and gained on the GPU"
                              + ("; input = at the loudness of its source sound" if allow_input else "")
@@ -94,6 +95,34 @@ def add_level_options(parser, allow_input=False):
     parser.add_argument("--true-peak", dest="true_peak", action="store_true",
                         help="--peak-limit is about the true peak, the maximum of the signal at four times its rate, not the "
                              "sample peak")
+    parser.add_argument("--limiter", action="store_true",
+                        help="keep the ceiling with a look-ahead peak limiter on the GPU in place of one gain for the whole "
+                             "file, so that a --loudness stands although single peaks are in its way; brings --peak-limit -1.0 "
+                             "along, with or without --loudness")
+    parser.add_argument("--limiter-lookahead", dest="limiter_lookahead", default=None, type=positive_ms_arg, metavar="MS",
+                        help="the limiter's look-ahead, the time its gain takes to come down in front of a peak (Def: 1.5)")
+    parser.add_argument("--limiter-hold", dest="limiter_hold", default=None, type=positive_ms_arg, metavar="MS",
+                        help="the limiter's hold, the time its gain stays down behind a peak: peaks that repeat within it see "
+                             "one constant gain (Def: 20)")
+
+
+def positive_ms_arg(text):
+    """argparse type of --limiter-lookahead and --limiter-hold: a finite positive number of milliseconds."""
+    value = _number(text)
+    if not (0 < value < float("inf")):
+        raise ArgumentTypeError(f"a positive time in ms is expected, got {text!r}")
+    return value
+
+
+def check_limiter_rate(model_id, out_rate, limiter, lookahead_ms, hold_ms, true_peak):
+    """ValueError when the limiter's window is refused at the rate the files are written at, from the model's configuration
+    alone: before a model is loaded.  ``out_rate`` "input" is every file's own rate, which the job checks once they are read."""
+    if limiter and out_rate != "input":
+        from . import get_config_file
+        from .config import read_config
+        from .limiter import check_rates
+        rate = read_config(config_file=get_config_file(model_id_or_path=model_id))["preprocess_config"]["sample_rate"]
+        check_rates([rate if out_rate is None else out_rate], lookahead_ms, hold_ms, true_peak)
 
 
 def file_guides(files, align_to=None, align_to_dir=None, align_band=1.0, time_stretch=1.0, time_stretch_file=None,

@@ -209,10 +209,30 @@ def ceiling_linear(dbfs):
 class LevelControl:
     """What ``run_micro_batches(level=)`` takes.  ``target``: None, a loudness in LUFS, or a list with one entry per item of
     the job -- a target POWER (the P of a source) or None; ``peak_limit``: the ceiling in dBFS or None; ``true_peak``: the
-    ceiling and the reported peak are about the 4x true peak.  The three go through :func:`check_options`."""
+    ceiling and the reported peak are about the 4x true peak; ``limiter``: the ceiling is kept by the look-ahead limiter
+    (limiter.py) with the window ``lookahead_ms`` / ``hold_ms``, and the loudness gain stands.  All go
+    through :func:`check_options`."""
 
-    def __init__(self, target=None, peak_limit=None, true_peak=False):
-        self.target, self.peak_limit, self.true_peak = check_options(target, peak_limit, true_peak)
+    def __init__(self, target=None, peak_limit=None, true_peak=False, limiter=False, lookahead_ms=None, hold_ms=None):
+        self.target, self.peak_limit, self.true_peak = check_options(target, peak_limit, true_peak, limiter=limiter,
+                                                                     lookahead_ms=lookahead_ms, hold_ms=hold_ms)
+        self.limiter, self.lookahead_ms, self.hold_ms = bool(limiter), lookahead_ms, hold_ms       # None: limiter.window's default
+
+    def window(self, rate):
+        """(h, H) of the limiter at ``rate`` (``limiter.window``: ValueError for a hold shorter than half the look-ahead)."""
+        from .limiter import window
+        return window(rate, self.lookahead_ms, self.hold_ms)
+
+    def check_rates(self, rates):
+        """ValueError when the limiter's window is refused at one of the rates a job writes at: before anything runs."""
+        if self.limiter:
+            from .limiter import check_rates
+            check_rates(rates, self.lookahead_ms, self.hold_ms, self.true_peak)
+
+    def sliced(self, indices):
+        """The control of the items ``indices`` of the job: a per-item target list is cut, everything else is kept."""
+        target = [self.target[ii] for ii in indices] if isinstance(self.target, (list, tuple)) else self.target
+        return LevelControl(target, self.peak_limit, self.true_peak, self.limiter, self.lookahead_ms, self.hold_ms)
 
     def powers(self, indices):
         """The target power (or None) of the items ``indices``."""
@@ -223,12 +243,23 @@ class LevelControl:
         return [None if self.target[ii] is None or not self.target[ii] > 0 else float(self.target[ii]) for ii in indices]
 
 
-def check_options(loudness=None, peak_limit=None, true_peak=False, allow_input=False):
-    """THE validation of the three public options, of the tools and of the methods: ``(loudness, peak_limit, true_peak)``
+def check_options(loudness=None, peak_limit=None, true_peak=False, allow_input=False, limiter=False, lookahead_ms=None,
+                  hold_ms=None):
+    """THE validation of the public options, of the tools and of the methods: ``(loudness, peak_limit, true_peak)``
     with the default ceiling filled in -- ``DEFAULT_PEAK_LIMIT`` dBFS with a loudness, none without.  ``loudness``: None, a
     finite number of LUFS, a list of per-item target powers, or -- ``allow_input``, for a caller that has source sounds --
     the word "input".  ValueError for anything else, for a peak limit that is not finite, and for ``true_peak`` (--true-peak)
-    without a peak to limit."""
+    without a peak to limit.  ``limiter`` (--limiter) comes with the default ceiling too, with or without a loudness; its
+    window ``lookahead_ms`` / ``hold_ms`` (None: not given, ``limiter.window`` fills in 1.5 / 20) is an error without it and
+    must be finite and positive with it (the hold against the look-ahead, and the window against the device, are checked at
+    the rates of the job: ``LevelControl.check_rates``)."""
+    given = [name for name, value in (("lookahead_ms", lookahead_ms), ("hold_ms", hold_ms)) if value is not None]
+    if given and not limiter:
+        raise ValueError(f"{' and '.join(given)} shape the limiter's window: give limiter (--limiter) too")
+    if limiter:
+        for name, value in (("lookahead_ms", lookahead_ms), ("hold_ms", hold_ms)):
+            if value is not None and not (isinstance(value, (int, float)) and np.isfinite(value) and value > 0):
+                raise ValueError(f"limiter: {name} must be a finite positive number of ms, got {value!r}")
     if isinstance(loudness, str):
         if loudness != "input" or not allow_input:
             raise ValueError("loudness is a number of LUFS" + (" or 'input'" if allow_input else "") + f", got {loudness!r}")
@@ -242,17 +273,20 @@ def check_options(loudness=None, peak_limit=None, true_peak=False, allow_input=F
         peak_limit = float(peak_limit)
         if not np.isfinite(peak_limit):
             raise ValueError(f"peak_limit must be a finite number of dBFS, got {peak_limit!r}")
-    if loudness is None and peak_limit is None and true_peak:
+    if loudness is None and peak_limit is None and true_peak and not limiter:
         raise ValueError("true_peak (--true-peak) chooses the peak of a peak limit or a loudness: give one of them")
-    if loudness is not None and peak_limit is None:
+    if (loudness is not None or limiter) and peak_limit is None:
         peak_limit = DEFAULT_PEAK_LIMIT
     return loudness, peak_limit, bool(true_peak)
 
 
-def level_control(loudness=None, peak_limit=None, true_peak=False):
+def level_control(loudness=None, peak_limit=None, true_peak=False, limiter=False, lookahead_ms=None, hold_ms=None):
     """The :class:`LevelControl` of the public options (:func:`check_options`), or None when none is given."""
-    loudness, peak_limit, true_peak = check_options(loudness, peak_limit, true_peak)
-    return None if loudness is None and peak_limit is None else LevelControl(loudness, peak_limit, true_peak)
+    loudness, peak_limit, true_peak = check_options(loudness, peak_limit, true_peak, limiter=limiter,
+                                                    lookahead_ms=lookahead_ms, hold_ms=hold_ms)
+    if loudness is None and peak_limit is None:
+        return None
+    return LevelControl(loudness, peak_limit, true_peak, limiter, lookahead_ms, hold_ms)
 
 
 # ------------------------------------------------------------------------------------------------

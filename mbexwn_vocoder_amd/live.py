@@ -24,7 +24,8 @@ import ctypes
 import numpy as np
 
 from .analysis import mel_analysis_tables, mell_header
-from .live_plan import (AnalysisPlan, FrameFactors, OutputPlan, _AStream, _OStream, _pow2_at_least, check_rate,  # noqa: F401
+from .live_plan import (AnalysisPlan, FrameFactors, LimiterPlan, OutputPlan, _AStream, _DStream, _OStream,  # noqa: F401
+                        _pow2_at_least, check_rate,
                         f0_frames_ready, frame_factors, frames_ready, frames_total, input_keep_from, outputs_ready,
                         stream_frames_ready)
 from .resample import _host_taps, device_taps, positive_rate
@@ -490,7 +491,11 @@ class StreamingOutputResampler(_Stage):
     element ``offset`` -- and the tick's ``mbxl_ring_append`` reads them from there: the audio never visits the host on its
     way in.  A steady tick is one small pinned upload (the descriptor tables), one append per distinct source tensor, one
     ``mbxo_resample_emit`` per distinct output rate into one packed buffer, and one copy back; it allocates no device
-    memory (``device_allocations`` counts every (re)allocation)."""
+    memory (``device_allocations`` counts every (re)allocation).
+
+    ``last_emit_device``, like the synthesizer's: where the last tick left its outputs on the device, ``(tensor, {stream_id:
+    (flat offset, count)})``, valid until the next tick; None after a tick without output.  The streaming limiter reads
+    resampled audio from there."""
     _taps_to_model = False
 
     def __init__(self, model_rate, device=None, ring_samples=None, slots=16):
@@ -499,6 +504,7 @@ class StreamingOutputResampler(_Stage):
         # samples (48 kHz to 8 kHz) a pending output still reads
         self._store = _RingStore(int(ring_samples or 4096), slots)
         self._desc_host = self._desc_dev = None       # one tick's descriptor tables (int64): pinned, and its device twin
+        self.last_emit_device = None
 
     # -- host side ----------------------------------------------------------------------------------------------------
     def open(self, stream_id, output_rate):
@@ -564,6 +570,7 @@ class StreamingOutputResampler(_Stage):
         """Append what was pushed to the rings and resample every output that became final.
         Returns {stream_id: float32 ndarray at the stream's output rate} for the streams with new output."""
         plan = self.plan()
+        self.last_emit_device = None
         if not plan.rows:
             return {}
         import torch
@@ -598,6 +605,144 @@ class StreamingOutputResampler(_Stage):
                                               self._out_dev.data_ptr(), int(self._out_dev.numel()), stream.cuda_stream))
             packed = self._copy_back(stream, events, total)
         result = {sid: packed[at:at + n_new].copy() for (sid, _, n_new, _), at in zip(plan.rows, starts) if n_new > 0}
+        if total:
+            self.last_emit_device = (self._out_dev, {sid: (at, n_new) for (sid, _, n_new, _), at in zip(plan.rows, starts)
+                                                     if n_new > 0})
+        self.commit(plan)
+        self.ticks += 1
+        return result
+
+
+class StreamingLimiter(_Stage):
+    """The last stage of a live stream: the look-ahead peak limiter of limiter.py on audio that is
+    still being produced, a tick at a time (csrc/limiter.hip through ``mbxd_limit_emit``).
+
+    The concatenated arrays ``tick`` hands out for a stream are ``limiter.limit_device`` on the stream's whole sound, bit
+    for bit -- and so is ``stats(stream_id)`` --, however the sound was cut into pushes: with ``have`` samples appended,
+    ``limiter.ready_outputs(have, h)`` outputs are final (output i once sample i + 2 h is there), every one once the
+    stream is closed; the ring (a ``_RingStore`` at the stream's own rate) holds every sample from
+    ``limiter.keep_from(next output, h, H)`` on and grows by doubling before it would not.
+
+    A stream has a fixed gain (it has no integrated loudness), a ceiling and a window at its rate.  A push names where the
+    samples ARE on the device, as ``StreamingOutputResampler.push`` does.  A steady tick is one small pinned upload (the
+    descriptor tables), one ``mbxl_ring_append`` per distinct source tensor, one ``mbxd_limit_emit`` per distinct (window,
+    ceiling) into one packed buffer, and one copy back; it allocates no device memory."""
+
+    def __init__(self, device=None, ring_samples=None, slots=16):
+        super().__init__(None, device)
+        # 8192: two ticks of the 80 ms schedule at 48 kHz behind the 1068 samples a pending output still reads
+        self._store = _RingStore(int(ring_samples or 8192), slots)
+        self._desc_host = self._desc_dev = None       # one tick's descriptor tables (int64): pinned, and its device twin
+        self._stats = None            # int32 (slots, 4) on the device
+        self._fresh = []              # slots of streams opened since the last tick: their statistics start over
+        self._weights = {}            # h -> the weights on the device
+
+    # -- host side ----------------------------------------------------------------------------------------------------
+    @staticmethod
+    def check_open(stream_id, rate, gain_db=0.0, peak_limit=-1.0, lookahead_ms=None, hold_ms=None):
+        """What ``open`` refuses, without opening: -> (rate, h, H, gain_db, peak_limit)."""
+        from . import limiter
+        rate = positive_rate(rate, f"stream {stream_id!r}: rate")
+        gain_db, peak_limit = float(gain_db), float(peak_limit)
+        if not (np.isfinite(gain_db) and np.isfinite(peak_limit)):
+            raise ValueError(f"stream {stream_id!r}: gain_db and peak_limit must be finite, got {gain_db!r} and {peak_limit!r}")
+        h, hold = limiter.window(rate, lookahead_ms, hold_ms)
+        limiter.check_window(h, hold)
+        return rate, h, hold, gain_db, peak_limit
+
+    def open(self, stream_id, rate, gain_db=0.0, peak_limit=-1.0, lookahead_ms=None, hold_ms=None):
+        if stream_id in self.streams:
+            raise ValueError(f"stream {stream_id!r} is open already")
+        rate, h, hold, gain_db, peak_limit = self.check_open(stream_id, rate, gain_db, peak_limit, lookahead_ms, hold_ms)
+        slot = self._store.take()
+        self.streams[stream_id] = _DStream(slot, rate, h, hold, np.float32(10.0 ** (gain_db / 20.0)),
+                                           float(np.float32(10.0 ** (peak_limit / 20.0))))
+        self._fresh.append(slot)
+
+    def close(self, stream_id):
+        """Forget a stream (its slot is reused)."""
+        self._store.release(self.streams.pop(stream_id).slot)
+
+    push = StreamingOutputResampler.push
+
+    def finished(self, stream_id):
+        st = self.streams[stream_id]
+        return st.closed and st.emitted >= st.have
+
+    def plan(self):
+        """What the next tick does, from the host state alone (no device, nothing changes)."""
+        return LimiterPlan(self.streams)
+
+    commit = StreamingOutputResampler.commit
+
+    def stats(self, stream_id):
+        """``limiter.LimitStats`` of what the stream has been handed so far (a copy back; waits for the device)."""
+        from .limiter import LimitStats
+        st = self.streams[stream_id]
+        if self._stats is None or st.slot in self._fresh:
+            return LimitStats(np.float32(1.0), 0, 0)
+        return LimitStats.from_words(self._stats[st.slot].cpu().numpy())
+
+    # -- device side --------------------------------------------------------------------------------------------------
+    _append_calls = StreamingOutputResampler._append_calls
+
+    def _ensure_stats(self, dev):
+        import torch
+        from .limiter import ONE_BITS, STAT_WORDS
+        if self._stats is None or self._stats.shape[0] < self._store.slots:
+            new = torch.zeros((self._store.slots, STAT_WORDS), dtype=torch.int32, device=dev)
+            if self._stats is not None:
+                new[:self._stats.shape[0]] = self._stats
+            self._stats = new
+            self.device_allocations += 1
+        if self._fresh:
+            # the tick behind an open: a small temporary on the device, counted like every other allocation
+            self._stats[self._fresh] = torch.as_tensor([ONE_BITS, 0, 0, 0], dtype=torch.int32, device=dev)
+            self.device_allocations += 1
+            self._fresh = []
+
+    def tick(self):
+        """Append what was pushed to the rings and limit every output that became final.
+        Returns {stream_id: float32 ndarray} for the streams with new output."""
+        plan = self.plan()
+        if not plan.rows:
+            return {}
+        import torch
+        from . import limiter
+        from .abi import _check, load_library
+        lib, dev = load_library(), self._resolve_device()
+        held = ((st.slot, st.on_device) for st in self.streams.values() if st.on_device)
+        self.device_allocations += self._store.ensure(dev, plan.ring_needed, held)
+        self._ensure_stats(dev)
+        rings, ring = self._store.rings, self._store.ring_samples
+        calls = self._append_calls(plan)
+        app = [row for rows in calls.values() for row in rows]
+        n_app, S = len(app), len(plan.rows)
+        starts = [0, *np.cumsum([max(n_new, 0) for _, _, n_new, _ in plan.rows]).tolist()]    # where a row's outputs go
+        emit = [limiter.emit_row(self.streams[sid].slot, first_out, n_new, None if n_total < 0 else n_total, at,
+                                 self.streams[sid].g0) for (sid, first_out, n_new, n_total), at in zip(plan.rows, starts)]
+        used, total = 4 * n_app + 6 * S, starts[-1]
+        self._desc_host, self._desc_dev = self._grown_pair(self._desc_host, self._desc_dev, used, torch.int64)
+        self._desc_host.numpy()[:used] = [word for row in app + emit for word in row]
+        self._out_host, self._out_dev = self._grown_pair(self._out_host, self._out_dev, total, torch.float32)
+        for (h, _, _), _, _, _ in plan.groups:
+            if h not in self._weights:
+                self._weights[h] = limiter.device_weights(h, dev)
+                self.device_allocations += 1
+        with torch.cuda.device(dev):
+            stream, base, events = self._upload(self._desc_host, self._desc_dev, used)
+            first = 0
+            for (_, ptr, numel), rows in calls.items():
+                _check(lib.mbxl_ring_append(ptr, numel, base + 32 * first, len(rows), max(rr[2] for rr in rows),
+                                            rings.data_ptr(), int(rings.shape[0]), ring, stream.cuda_stream))
+                first += len(rows)
+            for (h, hold, ceiling), first, end, max_new in plan.groups:      # one launch per distinct window and ceiling
+                _check(lib.mbxd_limit_emit(rings.data_ptr(), int(rings.shape[0]), ring, base + 32 * n_app + 48 * first,
+                                           end - first, max_new, ceiling, h, hold, self._weights[h].data_ptr(),
+                                           self._out_dev.data_ptr(), int(self._out_dev.numel()), self._stats.data_ptr(),
+                                           stream.cuda_stream))
+            packed = self._copy_back(stream, events, total)
+        result = {sid: packed[at:at + n_new].copy() for (sid, _, n_new, _), at in zip(plan.rows, starts) if n_new > 0}
         self.commit(plan)
         self.ticks += 1
         return result
@@ -612,6 +757,7 @@ class _LStream:
         self.rng, self.noise_fn = rng, noise_fn
         self.flushed = False          # the synthesizer has been told that the stream is over
         self.out_rate = None          # the stream's output rate when it is not the model's: it goes through the output stage
+        self.limited = False          # the stream leaves through the limiter, the last stage
         self.f0_hold = None           # f0_source="audio": the last voiced F0 (float32), what an unvoiced frame takes
         self.pending = None           # a decoding stream (f0_lag): the scaled mel rows that still wait for their decided F0
 
@@ -662,6 +808,9 @@ class LiveResynthesizer:
         # streams with an output rate of their own leave through this stage; its store is allocated by its first tick
         self.output = StreamingOutputResampler(self.analyzer.sample_rate, device=engine.device)
         self._out_streams = 0
+        # streams with a peak limit leave through the limiter, at the rate they are handed out at; allocated by its first tick
+        self.limiter = StreamingLimiter(device=engine.device)
+        self._lim_streams = 0
 
     @property
     def lookahead_ms(self):
@@ -676,14 +825,16 @@ class LiveResynthesizer:
         from .f0track import check_params, params
         return params(self.analyzer.model_rate) if f0_params is None else check_params(dict(f0_params))
 
-    def lookahead_ms_for(self, sample_rate=None, output_rate=None, f0_source="net", f0_params=None, f0_lag=None):
+    def lookahead_ms_for(self, sample_rate=None, output_rate=None, f0_source="net", f0_params=None, f0_lag=None,
+                         peak_limit=None, limiter_lookahead_ms=None):
         """``lookahead_ms`` of a stream opened at ``sample_rate`` and ``output_rate``: a resampled stream waits for half
         its filter as well, half / up input samples (0.92 ms at 44.1 and 48 kHz, 1.4 ms at 16 kHz for a 24 kHz model); a
         stream with an output rate waits for half the output filter, half / up model-rate samples (0.92 ms to 48 kHz,
         0.94 ms to 44.1 kHz, 1.4 ms to 16 kHz).  With ``f0_source="audio"`` a frame waits for its F0 frame too, L = window
         + tau_max of ``f0_params`` (None: the defaults) samples about its centre: the analysis part is
         ceil(max(win - win // 2, L - L // 2) / hop) frames -- 3 instead of 2 with the defaults at 24 kHz.  ``f0_lag=N`` adds
-        the decoder's N frames, 1000 N hop / sample_rate ms."""
+        the decoder's N frames, 1000 N hop / sample_rate ms.  A stream with a ``peak_limit`` waits for the limiter's
+        look-ahead, 2 h samples at the rate it is handed out at (``limiter.window`` of ``limiter_lookahead_ms``)."""
         model = self.analyzer.model_rate
         ms = self.lookahead_ms
         if f0_source not in ("net", "audio"):
@@ -701,19 +852,30 @@ class LiveResynthesizer:
         out_rate = resolve_output_rate(output_rate, sample_rate, model)
         if out_rate is not None:
             ms += output_lookahead_ms(model, out_rate)
+        if peak_limit is not None:
+            from .limiter import window
+            rate = model if out_rate is None else out_rate
+            ms += 1000.0 * 2 * window(rate, limiter_lookahead_ms, 1000.0)[0] / rate
         return ms
 
     def open(self, stream_id, seed=None, noise_fn=None, sample_rate=None, output_rate=None, f0_source="net", f0_params=None,
-             f0_initial=150.0, f0_decode=None, f0_lag=None):
+             f0_initial=150.0, f0_decode=None, f0_lag=None, gain_db=0.0, peak_limit=None, limiter_lookahead_ms=None,
+             limiter_hold_ms=None):
         """``output_rate``: the rate the stream's audio comes back at -- a rate in Hz, or ``"input"`` for the stream's own
         ``sample_rate``; None or the model's rate: the model-rate audio, as the synthesizer emits it.  ``f0_source``:
         ``"net"`` -- the F0-net's contour -- or ``"audio"``: the tracked pitch of the sound (``f0_params``: an
         ``f0track.params`` dictionary at the model rate, None = its defaults; ``f0_initial``: Hz of the frames in front of the
         first voiced one).  ``f0_lag``: frames of look-ahead of a decoded contour (0 .. 128, with ``f0_source="audio"``), by
         ``f0_decode`` (None: the defaults); ``f0_decode`` without a lag is refused: decoding the contour over the whole sound
-        needs the whole sound."""
+        needs the whole sound.  ``peak_limit``: a ceiling in dBFS the stream is kept under by the look-ahead limiter
+        (``StreamingLimiter``), the last stage, at the rate the stream is handed out at, behind the fixed
+        gain ``gain_db`` -- a stream has no integrated loudness -- and with the window ``limiter_lookahead_ms`` /
+        ``limiter_hold_ms``; the stream then equals ``limiter.limit_device`` on the whole output of the same stream without
+        a peak limit.  None: the stream of before (the gain and the window go with a peak limit)."""
         if f0_source not in ("net", "audio"):
             raise ValueError(f"f0_source must be 'net' or 'audio', got {f0_source!r}")
+        if peak_limit is None and (float(gain_db) != 0.0 or limiter_lookahead_ms is not None or limiter_hold_ms is not None):
+            raise ValueError("gain_db, limiter_lookahead_ms and limiter_hold_ms go with a peak_limit")
         if f0_decode is not None and f0_lag is None:
             raise ValueError(f"stream {stream_id!r}: f0_decode decodes the contour over the whole sound (f0decode.py), which a "
                              "stream does not have; streams track every frame on its own")
@@ -728,6 +890,13 @@ class LiveResynthesizer:
         elif f0_params is not None:
             raise ValueError("f0_params go with f0_source='audio'")
         out_rate = resolve_output_rate(output_rate, sample_rate, self.analyzer.sample_rate)
+        limit = None
+        if peak_limit is not None:                          # before any stage knows the stream: a window the rate refuses
+            limit = (self.analyzer.sample_rate if out_rate is None else out_rate, gain_db, peak_limit, limiter_lookahead_ms,
+                     limiter_hold_ms)
+            self.limiter.check_open(stream_id, *limit)
+            if stream_id in self.limiter.streams:
+                raise ValueError(f"stream {stream_id!r} is open already")
         self.analyzer.open(stream_id, sample_rate=sample_rate, f0_params=f0_params, f0_decode=f0_decode, f0_lag=f0_lag)
         self.synthesizer.open(stream_id, f0="net" if hold is None else "frames")
         up, down = (self.analyzer.streams[stream_id].filt or (1, 1))[:2]
@@ -735,6 +904,10 @@ class LiveResynthesizer:
                                                 noise_fn, up, down)
         st.f0_hold = hold
         st.pending = None if f0_lag is None else np.zeros((0, self.dims.mel_channels), dtype=np.float32)
+        st.limited = limit is not None
+        if limit is not None:                               # the last stage, opened last: the checks above cannot fail it
+            self.limiter.open(stream_id, *limit)
+            self._lim_streams += 1
         if out_rate is not None:
             self.output.open(stream_id, out_rate)
             st.out_rate = out_rate
@@ -743,9 +916,13 @@ class LiveResynthesizer:
     def close(self, stream_id):
         self.analyzer.close(stream_id)
         self.synthesizer.close(stream_id)
-        if self.streams.pop(stream_id).out_rate is not None:
+        st = self.streams.pop(stream_id)
+        if st.out_rate is not None:
             self.output.close(stream_id)
             self._out_streams -= 1
+        if st.limited:
+            self.limiter.close(stream_id)
+            self._lim_streams -= 1
 
     def push_audio(self, stream_id, samples, last=False, transposition=None, sample_rate=None, formant=None):
         """Append samples at the stream's rate (the model's, unless it was opened at another); ``transposition``: one finite
@@ -815,8 +992,13 @@ class LiveResynthesizer:
             self.synthesizer.push(sid, scaled, noise, last=done, transposition=st.factors.take(first, end), **shift)
             st.frames, st.flushed = end, done
         audio = self.synthesizer.tick()
-        if not self._out_streams:
-            return audio
+        if self._out_streams:
+            audio = self._resample_out(audio)
+        if self._lim_streams:
+            audio = self._limit_out(audio)
+        return audio
+
+    def _resample_out(self, audio):
         # the streams with an output rate: their chunks go on, from where the synthesizer left them on the device, to the
         # output stage, and what that stage has final comes back in their place
         source, spans = self.synthesizer.last_emit_device or (None, {})
@@ -831,8 +1013,28 @@ class LiveResynthesizer:
         audio.update(self.output.tick())
         return audio
 
+    def _limit_out(self, audio):
+        # the streams with a peak limit: what the stage in front of the limiter left on the device in this tick -- the
+        # output resampler for a stream with an output rate, else the synthesizer -- goes on to the limiter, and what
+        # that has final comes back in its place
+        places = {False: self.synthesizer.last_emit_device or (None, {}), True: self.output.last_emit_device or (None, {})}
+        for sid, st in self.streams.items():
+            if not st.limited or self.limiter.streams[sid].closed:
+                continue
+            resampled = st.out_rate is not None
+            source, spans = places[resampled]
+            offset, count = spans.get(sid, (0, 0))
+            last = self.output.finished(sid) if resampled else st.flushed and self.synthesizer.finished(sid)
+            if count or last:
+                self.limiter.push(sid, source, offset, count, last=last)
+            audio.pop(sid, None)
+        audio.update(self.limiter.tick())
+        return audio
+
     def finished(self, stream_id):
         st = self.streams[stream_id]
+        if st.limited:
+            return self.limiter.finished(stream_id)
         if st.out_rate is not None:
             return self.output.finished(stream_id)
         return st.flushed and self.synthesizer.finished(stream_id)

@@ -240,3 +240,34 @@ class OutputPlan:
                 # from the first sample a pending output may still read (never behind what is to be appended)
                 self.ring_needed = max(self.ring_needed, st.have - min(input_keep_from(st.emitted, *st.filt), st.on_device))
         self.groups = list(rate_groups(rates, [row[2] for row in self.rows]))     # (rate, first, end, max_out) over the rows
+
+
+class _DStream:
+    def __init__(self, slot, rate, h, hold, g0, ceiling):
+        self.slot, self.rate, self.g0 = slot, rate, g0
+        self.key = (h, hold, ceiling)     # what one launch of the limiter shares: the window and the ceiling
+        self.have = 0             # samples pushed
+        self.on_device = 0        # ... of which the ring holds the newest
+        self.emitted = 0          # outputs handed out
+        self.closed = False
+        self.queue = []           # (source, offset, count) pushed since the last tick
+
+
+class LimiterPlan:
+    """One tick of the streaming limiter, planned on the host from its ``streams`` ({id: _DStream}) alone; building one
+    changes nothing.  The streams with work have samples to append or outputs that became final (``limiter.ready_outputs``:
+    output i once sample i + 2 h is there, or the stream is closed)."""
+
+    def __init__(self, streams):
+        from .limiter import keep_from, ready_outputs
+        self.rows, keys = [], []      # (stream_id, first_out, n_new, n_total or -1) per stream with work, by window and ceiling
+        self.ring_needed = 0          # the samples the longest-held stream's ring must hold
+        for sid, st in sorted(streams.items(), key=lambda kv: kv[1].key):
+            h, hold, _ = st.key
+            n_new = ready_outputs(st.have, h, st.have if st.closed else None) - st.emitted
+            if n_new > 0 or st.queue:
+                self.rows.append((sid, st.emitted, n_new, st.have if st.closed else -1))
+                keys.append(st.key)
+                # from the first sample a pending output may still read (never behind what is to be appended)
+                self.ring_needed = max(self.ring_needed, st.have - min(keep_from(st.emitted, h, hold), st.on_device))
+        self.groups = list(rate_groups(keys, [row[2] for row in self.rows]))     # (key, first, end, max_new) over the rows

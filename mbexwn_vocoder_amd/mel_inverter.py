@@ -249,7 +249,8 @@ class MELInverter(object):
 
     def synth_from_mels(self, scaled_mels, noises=None, max_batch=16, max_padded_frames=16 * 1200, flac=False,
                         flac_compression="verbatim", out_rate=None, noise_seed=None, noise_keys=None, transpositions=None,
-                        formants=None, f0s=None, loudness=None, peak_limit=None, true_peak=False, levels_out=None):
+                        formants=None, f0s=None, loudness=None, peak_limit=None, true_peak=False, levels_out=None,
+                        limiter=False, lookahead_ms=None, hold_ms=None):
         """Batched :meth:`synth_from_mel` (this build): a list of ``scale_mel`` outputs (1, T_i, mel_channels) -> a list of
         float32 audio (T_i * hop_size,), or with ``flac=True`` of complete FLAC files (bytes; frames encoded on the device).
 
@@ -278,11 +279,18 @@ class MELInverter(object):
         scales down); ``true_peak`` -- the ceiling is about the 4x oversampled peak.  One static gain per item, measured and
         applied on the device behind the forward and the output resampler: what comes back -- audio or FLAC -- is the
         gained audio, measured at the rate it has.  ``levels_out``: a list that receives ``SynthBatch.level`` of every item,
-        in item order.  None of them: the launches of before."""
+        in item order.  None of them: the launches of before.
+
+        ``limiter`` (limiter.py): the ceiling -- -1 dBFS unless ``peak_limit`` says otherwise, with or
+        without a loudness -- is kept by a look-ahead peak limiter in place of the static gain, so the loudness gain stands;
+        ``lookahead_ms`` and ``hold_ms`` shape its window (None: 1.5 and 20 ms).  The report then carries the loudness and the peak measured
+        behind the limiter and a ``limiter`` entry (``SynthBatch.level``).  False: the launches and the bytes of before."""
         import torch
         from .batched import check_f0s, replay_noise, run_micro_batches
         from .level import level_control
-        control = level_control(loudness, peak_limit, true_peak)
+        control = level_control(loudness, peak_limit, true_peak, limiter, lookahead_ms, hold_ms)
+        if control is not None:
+            control.check_rates([self.srate if out_rate is None else out_rate])   # a window the rate refuses: before anything runs
         if control is not None and isinstance(control.target, list) and len(control.target) != len(scaled_mels):
             raise ValueError("synth_from_mels: a loudness list takes one entry per mel")
         if noise_seed is not None and noises is not None:
@@ -345,7 +353,7 @@ class MELInverter(object):
                         max_padded_frames=16 * 1200, flac=False, flac_compression="verbatim", time_stretch=None, formant=None,
                         f0_source="net", f0_params=None, f0_decode=None, f0_fill="interpolate", f0_initial=150.0,
                         align_to=None, align_band_s=1.0, loudness=None, peak_limit=None, true_peak=False, levels_out=None,
-                        f0_lag=None):
+                        *, limiter=False, lookahead_ms=None, hold_ms=None, f0_lag=None):
         """Sounds in, transposed sounds out (this build): ``sounds`` -- 1-D float32 arrays at ``rates``; ``names`` -- what
         keys each item's noise (``noise.item_key``: the basename of a file name, or an integer); ``transposition`` -- one
         factor for all, or one per item.  Device resampler and mel analysis (``analysis.generate_mels``), :meth:`scale_mel`
@@ -388,7 +396,8 @@ class MELInverter(object):
         ``loudness`` / ``peak_limit`` / ``true_peak`` / ``levels_out``: the level of what comes back, as in
         :meth:`synth_from_mels` -- and ``loudness="input"``: every item comes out at the loudness of its source, which is
         measured as handed in, at its own rate, on the device in the micro-batches the analysis stages; a source that is not
-        measurable leaves the loudness gain at 1 (the ceiling still applies).
+        measurable leaves the loudness gain at 1 (the ceiling still applies).  ``limiter`` / ``lookahead_ms`` / ``hold_ms``:
+        the look-ahead limiter of :meth:`synth_from_mels`.
 
         An item's audio is a function of (sound, rate, name, factor, stretch, formant, seed, out_rate): with a ``batch_invariant``
         engine or one pinned to a convolution form it does not depend on the batch, the order or the other items."""
@@ -401,7 +410,8 @@ class MELInverter(object):
             raise ValueError("transform_audio: one rate and one name per sound")
         if formant is not None and (not isinstance(formant, (list, tuple)) or len(formant) != len(sounds)):
             raise ValueError("transform_audio: formant takes one entry per sound")
-        loudness, peak_limit, true_peak = check_options(loudness, peak_limit, true_peak, allow_input=True)   # before anything runs
+        loudness, peak_limit, true_peak = check_options(loudness, peak_limit, true_peak, allow_input=True, limiter=limiter,
+                                                        lookahead_ms=lookahead_ms, hold_ms=hold_ms)   # before anything runs
         guided = align_to is not None and any(gg is not None for gg in align_to)
         if guided and len(align_to) != len(sounds):
             raise ValueError("transform_audio: align_to takes one entry per sound")
@@ -421,7 +431,7 @@ class MELInverter(object):
                                     flac_compression=flac_compression, out_rate=out_rate, noise_seed=noise_seed,
                                     noise_keys=[item_key(nn) for nn in names], transpositions=rows, formants=formant,
                                     f0s=done.contours, loudness=loudness, peak_limit=peak_limit, true_peak=true_peak,
-                                    levels_out=levels_out)
+                                    levels_out=levels_out, limiter=limiter, lookahead_ms=lookahead_ms, hold_ms=hold_ms)
 
     def track_f0(self, snd, srate, on_device=False, decode=None, f0_lag=None, **f0_params):
         """The pitch of a single sound (this build): (times in s, f0 in Hz with 0 = unvoiced, periodicity), one value per mel

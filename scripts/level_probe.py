@@ -6,7 +6,11 @@ place), with and without the 4x true peak, next to the forward it follows -- all
 The three legs alternate, each between two HIP events on the stream it runs on; after a warm-up of all, the timed calls give
 the percentiles of the device time of a whole leg.  The level legs go through ``level.measure_device`` / ``gains_device`` /
 ``apply_device`` as the micro-batches call them (so they include their allocations; nothing is uploaded);
-``measure_only`` is mbxl_measure alone, without the true peak.  The time of each kernel comes from a run of its own under
+``measure_only`` is mbxl_measure alone, without the true peak.  ``limiter`` is the level stage with the look-ahead limiter
+ as ``run_micro_batches`` runs it -- measure, gains without a ceiling, mbxd_limit, measure again -- at
+per-item loudness targets ``--limiter-over`` dB above the one at which the static gain would touch the ceiling, and
+``limit_only`` is mbxd_limit alone on the same gains (its kernels are limit_kernel and limit_stats_kernel);
+``limit_only_heavy`` is the same 12 dB further up, where no tile takes the fast path.  The share of samples limited is reported.  The time of each kernel comes from a run of its own under
 ``rocprofv3 --kernel-trace --stats`` with ``--only level`` (the kernels are level_hops_kernel, level_peak_kernel,
 level_gate_kernel, level_gains_kernel and level_apply_kernel).
 
@@ -39,6 +43,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10, help="untimed rounds of every leg")
     ap.add_argument("--iters", type=int, default=50, help="timed rounds of every leg")
     ap.add_argument("--only", choices=["all", "level"], default="all", help="level: without the forward, for a run under a profiler")
+    ap.add_argument("--limiter-over", type=float, default=3.0,
+                    help="dB of loudness the limiter legs ask for beyond what the static ceiling allows")
     ap.add_argument("--job-batches", type=int, default=6, help="micro-batches of a job run (0: no job runs)")
     ap.add_argument("--job-runs", type=int, default=5, help="timed job runs of each kind, after one untimed")
     args = ap.parse_args()
@@ -46,7 +52,7 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("level_probe.py: no GPU available; a timing taken without one says nothing")
-    from mbexwn_vocoder_amd import level
+    from mbexwn_vocoder_amd import level, limiter
     from mbexwn_vocoder_amd.mel_inverter import MELInverter, create_synthetic_model_dir
     with tempfile.TemporaryDirectory() as tmp:
         inv = MELInverter(create_synthetic_model_dir(os.path.join(tmp, "speech"), "SPEECH"))
@@ -75,11 +81,32 @@ def main():
         level.apply_device(audio, counts, gains, out=gained)
 
     gained = torch.empty_like(audio)
+    h, hold = limiter.window(rate)
+    # per item: the loudness at which its peak touches the ceiling, and --limiter-over dB more
+    loud = [level.target_power(mm.lufs - 20.0 * np.log10(float(mm.sample_peak) / ceiling) + args.limiter_over)
+            for mm in level.measure_device(audio, counts, rate).host(details=False)]
+    loud_gains = level.gains_device(level.measure_device(audio, counts, rate), loud)
+    heavy_gains = (loud_gains * 4.0).contiguous()
+
+    def limited_stage():
+        measure = level.measure_device(audio, counts, rate)
+        gains = level.gains_device(measure, loud)
+        out, _ = limiter.limit_device(audio, counts, gains, ceiling, h, hold, out=gained)
+        level.measure_device(out, counts, rate)
+
+    item0, stats0 = limiter.limit_device(audio[:1], counts[:1], loud_gains[:1].contiguous(), ceiling, h, hold)
+    want0, want_stats = limiter.limit_host(audio[0].cpu().numpy(), loud_gains[0].item(), np.float32(ceiling), h, hold)
+    assert np.array_equal(item0.cpu().numpy()[0].view(np.int32), want0.view(np.int32)), "device limiter differs"
+    assert list(stats0.cpu().numpy()[0]) == list(want_stats.words())
     legs = [("forward", lambda: eng.forward(mel, noise=noise))] if args.only == "all" else []
     legs += [("level", lambda: stage(False)), ("level_true_peak", lambda: stage(True)),
-             ("measure_only", lambda: level.measure_device(audio, counts, rate))]
+             ("measure_only", lambda: level.measure_device(audio, counts, rate)), ("limiter", limited_stage),
+             ("limit_only", lambda: limiter.limit_device(audio, counts, loud_gains, ceiling, h, hold, out=gained)),
+             ("limit_only_heavy", lambda: limiter.limit_device(audio, counts, heavy_gains, ceiling, h, hold, out=gained))]
     result = {"device": torch.cuda.get_device_name(0), "items": B, "seconds": stride / rate, "rate": rate,
-              "hops_per_item": stride // level.hop_samples(rate), "lufs_item0": got.lufs, "warmup": args.warmup, "iters": args.iters}
+              "hops_per_item": stride // level.hop_samples(rate), "lufs_item0": got.lufs, "warmup": args.warmup, "iters": args.iters,
+              "limiter": {"over_db": args.limiter_over, "h": h, "hold": hold, "limited_share_item0": want_stats.limited / stride,
+                          "clamped_item0": want_stats.clamped, "reduction_db_item0": want_stats.reduction_db}}
     with torch.cuda.device(eng.device):
         stream = torch.cuda.current_stream(eng.device)
         times = {name: [] for name, _ in legs}
@@ -100,6 +127,7 @@ def main():
         mels = [mel[bb].cpu().numpy() for bb in range(B)] * args.job_batches
         keyed = KeyedNoise(0, list(range(len(mels)))) if dims.noise_sigma else None
         control = level.level_control(-23.0, -1.0)
+        limiting = level.level_control(loud * args.job_batches, -1.0, limiter=True)
 
         def job(ctl):
             torch.cuda.synchronize()
@@ -115,9 +143,9 @@ def main():
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) * 1e3, enqueue
 
-        runs = {"plain": [], "level": []}
+        runs = {"plain": [], "level": [], "limiter": []}
         for it in range(1 + args.job_runs):
-            for name, ctl in (("plain", None), ("level", control)):
+            for name, ctl in (("plain", None), ("level", control), ("limiter", limiting)):
                 got_ms = job(ctl)
                 if it:
                     runs[name].append(got_ms)
@@ -126,7 +154,7 @@ def main():
                          for name, vals in runs.items()}
     if "forward" in times:
         step = result["leg_ms_device"]["forward"]["p50"]
-        result["share_of_step"] = {name: result["leg_ms_device"][name]["p50"] / step for name in ("level", "level_true_peak")}
+        result["share_of_step"] = {name: result["leg_ms_device"][name]["p50"] / step for name in ("level", "level_true_peak", "limiter", "limit_only", "limit_only_heavy")}
     print(json.dumps(result))
 
 

@@ -18,7 +18,7 @@ OBJ_DIR = os.path.join(HERE, "build")
 LIB_PATH = os.path.join(HERE, "libmbexwn_hip.so")
 SOURCES = ["conv_mfma.hip", "conv_mel.hip", "wn_winograd2w.hip", "wn_winograd4w.hip", "wn_gate0.hip", "wn_resskip.hip", "wn_resskip_wide.hip", "wn_resskip_wave.hip", "wn_resskip_f16.hip", "wn_gate_f16.hip", "wn_tail.hip",
            "elementwise.hip", "wavetable.hip", "pqmf.hip", "stft_filter.hip", "mel_analysis.hip", "mel_stream.hip", "resample_poly.hip", "resample_stream.hip", "norm_mel.hip", "flac_frames.hip", "flac_fixed.hip", "noise_keyed.hip", "mel_warp.hip", "mel_envelope.hip", "f0_track.hip", "f0_decode.hip", "f0_stream.hip", "f0_lag.hip", "mel_align.hip", "level.hip", "limiter.hip", "mbx_create.hip", "mbx_forward.hip", "mbx_api.hip", "mbx_stages.hip"]
-HEADERS = ["mbx_kernels.h", "mbx_args.h", "wn_plan.h", "mbx_handle.h", "conv_tile.h", "fft_lds.h", "mel_frame.h", "resample_chain.h", "flac_frame.h", "f0_frame.h", "f0_viterbi.h", os.path.join("..", "..", "include", "mbexwn.h"),
+HEADERS = ["mbx_kernels.h", "mbx_args.h", "wn_plan.h", "mbx_handle.h", "conv_tile.h", "fft_lds.h", "mel_frame.h", "resample_chain.h", "flac_frame.h", "f0_frame.h", "f0_viterbi.h", "ring_rows.h", os.path.join("..", "..", "include", "mbexwn.h"),
            os.path.join("..", "..", "include", "mbexwn_audio.h"), os.path.join("..", "..", "include", "mbexwn_live.h"),
            os.path.join("..", "..", "include", "mbexwn_live_resample.h"), os.path.join("..", "..", "include", "mbexwn_flac.h"),
            os.path.join("..", "..", "include", "mbexwn_live_out.h"), os.path.join("..", "..", "include", "mbexwn_noise.h"),

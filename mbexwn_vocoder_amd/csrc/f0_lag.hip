@@ -40,13 +40,13 @@ __global__ __launch_bounds__(F0_THREADS) void f0_stream_candidates_kernel(Candid
     extern __shared__ __attribute__((aligned(16))) float f0_smem[];
     __shared__ float s_energy;
     const PitchStreamArgs &f = p.ring;
-    const long long *dsc = f.desc + 4LL * blockIdx.y;
-    const long long slot = dsc[0], n_total = dsc[3];
-    if ((long long)blockIdx.x >= dsc[2] || slot < 0 || slot >= f.n_slots || dsc[1] < 0) return;
+    const StreamRow row{f.desc + 4LL * blockIdx.y};
+    if (!row.has_frame(blockIdx.x, f.rings)) return;
+    const long long n_total = row.n_total();
     const int W = f.window, TM = f.tau_max, L = W + TM;
-    long long c = (dsc[1] + blockIdx.x) * f.hop;
+    long long c = (row.first() + blockIdx.x) * f.hop;
     if (n_total >= 0) c = min(c, n_total);
-    const int bad = f0_frame_load(F0RingFetch(f.rings + slot * f.ring_samples, f.ring_samples, n_total, c, L), L, f0_smem);
+    const int bad = f0_frame_load(F0RingFetch(f.rings.row(row.slot()), f.rings.ring_samples, n_total, c, L), L, f0_smem);
     f0_frame_dprime(W, TM, f0_smem, &s_energy);
     if (threadIdx.x >= 64) return;
     f0_frame_candidates(f0_smem + L, f.tau_min, TM, bad, s_energy, f.e_min, p.thresholds, p.weights, p.n_thresholds, p.n_cand,
@@ -78,12 +78,12 @@ __global__ __launch_bounds__(64) void f0_lag_decode_kernel(LagDecodeArgs p) {
     __shared__ float s_cst[F0_LAG_CHUNK * F0_SLOTS];        // the costs of a sub-chunk
     constexpr int MASK = F0_LAG_RING - 1;
     const int r = blockIdx.x, lane = threadIdx.x;
-    const long long *dsc = p.desc + 4LL * r;
-    const long long slot = dsc[0], first = dsc[1], n_total = dsc[3];
+    const StreamRow row{p.desc + 4LL * r};
+    const long long slot = row.slot(), first = row.first(), n_total = row.n_total();
     if (slot < 0 || slot >= p.n_slots || first < 0 || first > (long long)INT_MAX - p.max_new_frames) return;
     unsigned *st = p.state + slot * F0_LAG_STATE_WORDS;
     if ((long long)(int)st[0] != first) return;             // not the stream's next frame: nothing is touched
-    const int n = (int)min(max(dsc[2], 0LL), (long long)p.max_new_frames), lag = p.lag;
+    const int n = (int)min(max(row.n(), 0LL), (long long)p.max_new_frames), lag = p.lag;
     const bool closing = n_total >= 0 && first + n >= n_total / p.hop + 1;
     int done = (int)first;
     int decided = min(max((int)st[1], max(done - lag, 0)), done);
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(64) void f0_lag_decode_kernel(LagDecodeArgs p) {
 
 const char *check_lag_decode(const LagDecodeArgs &a) {
     if (!a.period || !a.cost || !a.dprime || !a.desc || !a.state || !a.f0 || !a.periodicity) return "NULL pointer";
-    if (a.n_streams < 0 || a.n_streams > 65535) return "n_streams must lie in [0, 65535]";
+    if (!row_count_fits(a.n_streams)) return "n_streams must lie in [0, 65535]";
     if (a.max_new_frames < 0) return "max_new_frames must not be negative";
     if (a.hop < 1) return "hop must be at least 1";
     if (a.n_slots < 1) return "n_slots must be at least 1";

@@ -26,13 +26,13 @@ namespace mbx {
 __global__ __launch_bounds__(F0_THREADS) void f0_stream_kernel(PitchStreamArgs p) {
     extern __shared__ __attribute__((aligned(16))) float f0_smem[];
     __shared__ float s_energy;
-    const long long *dsc = p.desc + 4LL * blockIdx.y;
-    const long long slot = dsc[0], n_total = dsc[3];
-    if ((long long)blockIdx.x >= dsc[2] || slot < 0 || slot >= p.n_slots || dsc[1] < 0) return;
+    const StreamRow row{p.desc + 4LL * blockIdx.y};
+    if (!row.has_frame(blockIdx.x, p.rings)) return;
+    const long long n_total = row.n_total();
     const int W = p.window, TM = p.tau_max, L = W + TM;
-    long long c = (dsc[1] + blockIdx.x) * p.hop;
+    long long c = (row.first() + blockIdx.x) * p.hop;
     if (n_total >= 0) c = min(c, n_total);
-    const int bad = f0_frame_load(F0RingFetch(p.rings + slot * p.ring_samples, p.ring_samples, n_total, c, L), L, f0_smem);
+    const int bad = f0_frame_load(F0RingFetch(p.rings.row(row.slot()), p.rings.ring_samples, n_total, c, L), L, f0_smem);
     f0_frame_dprime(W, TM, f0_smem, &s_energy);
     if (threadIdx.x >= 64) return;
     float f0, per;
@@ -44,13 +44,12 @@ __global__ __launch_bounds__(F0_THREADS) void f0_stream_kernel(PitchStreamArgs p
 }
 
 const char *check_f0_stream(const PitchStreamArgs &a) {
-    if (!a.rings || !a.desc || !a.f0 || !a.periodicity) return "NULL pointer";
-    if (a.n_streams < 0 || a.n_streams > 65535) return "n_streams must lie in [0, 65535]";
+    if (!a.rings.data || !a.desc || !a.f0 || !a.periodicity) return "NULL pointer";
+    if (!row_count_fits(a.n_streams)) return "n_streams must lie in [0, 65535]";
     if (a.max_new_frames < 0) return "max_new_frames must not be negative";
-    if (a.n_slots < 1) return "n_slots must be at least 1";
     if (a.hop < 1) return "hop must be at least 1";
     PitchArgs f{};                                          // the offline tracker's checks of the arguments the two share
-    f.audio = a.rings;
+    f.audio = a.rings.data;
     f.n_samples = f.n_frames = reinterpret_cast<const int32_t *>(a.desc);
     f.centres = reinterpret_cast<const int64_t *>(a.desc);
     f.f0 = a.f0;
@@ -63,9 +62,8 @@ const char *check_f0_stream(const PitchStreamArgs &a) {
     f.threshold = a.threshold;
     f.e_min = a.e_min;
     if (const char *why = check_track_f0(f)) return why;
-    if (a.ring_samples < 1 || (a.ring_samples & (a.ring_samples - 1)) != 0 || a.ring_samples < a.window + a.tau_max)
-        return "ring_samples must be a power of two, at least window + tau_max";
-    return nullptr;
+    if (ring_store_ok(a.rings, a.window + a.tau_max)) return nullptr;
+    return "n_slots must be at least 1 and ring_samples a power of two, at least window + tau_max";
 }
 
 void launch_f0_stream(const PitchStreamArgs &a, hipStream_t stream) {

@@ -17,6 +17,7 @@
 
 #include "mbx_handle.h"
 #include "resample_chain.h"
+#include "ring_rows.h"
 #include "../../include/mbexwn_limiter.h"
 
 #pragma clang fp contract(off)
@@ -219,8 +220,7 @@ __global__ __launch_bounds__(LIM_THREADS) void limit_kernel(const float *audio, 
 }
 
 struct LimitEmitArgs {
-    const float *rings;
-    int n_slots, ring_samples;
+    RingStore rings;
     const long long *desc;
     int n_rows, max_new;
     float c;
@@ -233,20 +233,19 @@ struct LimitEmitArgs {
 
 __global__ __launch_bounds__(LIM_THREADS) void limit_emit_kernel(LimitEmitArgs p) {
     extern __shared__ unsigned int limit_lds[];
-    const long long *d = p.desc + 6LL * blockIdx.y;
-    const long long slot = d[0], first = d[1], n_new = d[2], n_total = d[3], out_offset = d[4];
-    const float g0 = __uint_as_float((unsigned int)(d[5] & 0xFFFFFFFFLL));
+    const EmitRow row = EmitRow::of(p.desc + 6LL * blockIdx.y);
+    const long long first = row.first_out, n_new = row.n_new;
+    const float g0 = __uint_as_float((unsigned int)(row.word5 & 0xFFFFFFFFLL));
     // all uniform over the block
-    if (slot < 0 || slot >= p.n_slots || n_new <= 0 || first < 0 || first > (1LL << 62) - n_new) return;
-    if (out_offset < 0 || out_offset > p.out_floats || n_new > p.out_floats - out_offset) return;
+    if (!row.fits(p.rings, p.out_floats) || n_new <= 0 || first > (1LL << 62) - n_new) return;
     const long long end = first + n_new;
     // an open stream: the caller asks for outputs whose samples are there, the last of them reads sample end + 2 h - 1
-    const long long n = n_total >= 0 ? n_total : end + 2LL * p.h;
+    const long long n = row.n_total >= 0 ? row.n_total : end + 2LL * p.h;
     if (end > n) return;
-    const float *ring = p.rings + slot * p.ring_samples;
-    const long long mask = p.ring_samples - 1;
-    float *dst = p.out + out_offset;
-    int *stats = p.stats ? p.stats + MBXD_STAT_WORDS * slot : nullptr;
+    const float *ring = p.rings.row(row.slot);
+    const long long mask = p.rings.mask();
+    float *dst = p.out + row.out_offset;
+    int *stats = p.stats ? p.stats + MBXD_STAT_WORDS * row.slot : nullptr;
     for (long long t0 = first + (long long)blockIdx.x * LIM_TILE; t0 < end; t0 += (long long)gridDim.x * LIM_TILE) {
         const int cnt = (int)min((long long)LIM_TILE, end - t0);
         limit_tile<false>(limit_lds, LIM_TILE + 3 * p.h + p.H, p.weights, p.h, p.H, nullptr, 0, n, t0, cnt, g0, p.c,
@@ -356,16 +355,15 @@ size_t mbxd_limit_workspace_floats(int64_t stride, int32_t batch, int32_t h, int
 mbx_status mbxd_limit_emit(const float *rings, int32_t n_slots, int32_t ring_samples, const int64_t *desc, int32_t n_rows,
                            int32_t max_new, float ceiling, int32_t h, int32_t hold, const float *weights, float *out,
                            int64_t out_floats, int32_t *stats, void *hip_stream) {
+    const mbx::LimitEmitArgs args{{rings, n_slots, ring_samples}, reinterpret_cast<const long long *>(desc), n_rows, max_new,
+                                  ceiling, h, hold, weights, out, out_floats, stats};
     if (!rings || !desc || !out) return refuse_limit("limit emit", "NULL pointer");
-    if (n_rows < 0 || n_rows > 65535) return refuse_limit("limit emit", "n_rows must lie in [0, 65535]");
+    if (!mbx::row_count_fits(n_rows)) return refuse_limit("limit emit", "n_rows must lie in [0, 65535]");
     if (max_new < 0) return refuse_limit("limit emit", "max_new must not be negative");
-    if (n_slots < 1) return refuse_limit("limit emit", "n_slots must be at least 1");
-    if (ring_samples < 1 || (ring_samples & (ring_samples - 1))) return refuse_limit("limit emit", "ring_samples must be a power of two");
+    if (!mbx::ring_store_ok(args.rings)) return refuse_limit("limit emit", "n_slots must be at least 1 and ring_samples a power of two");
     if (out_floats < 0) return refuse_limit("limit emit", "out_floats must not be negative");
     if (const char *why = mbx::check_window(ceiling, h, hold, weights, 0)) return refuse_limit("limit emit", why);
     if (n_rows == 0 || max_new == 0) return MBX_OK;
-    const mbx::LimitEmitArgs args{rings, n_slots, ring_samples, reinterpret_cast<const long long *>(desc), n_rows, max_new,
-                                  ceiling, h, hold, weights, out, out_floats, stats};
     const long long want = ((long long)max_new + mbx::LIM_TILE - 1) / mbx::LIM_TILE;
     const dim3 grid((unsigned)std::min<long long>(want, mbx::LIM_MAX_TILES), (unsigned)n_rows);
     hipLaunchKernelGGL(mbx::limit_emit_kernel, grid, dim3(mbx::LIM_THREADS), (size_t)mbx::lds_words(h, hold, 0) * sizeof(unsigned int),

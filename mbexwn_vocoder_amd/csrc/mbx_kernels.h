@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mbexwn.h"   // MBX_RESSKIP_K_* / MBX_TAIL_K_*: what the res/skip and tail launchers return
+#include "ring_rows.h"   // RingStore: the ring stores of the live stages, and their descriptor rows
 #include "wn_plan.h"   // ConvArgs / Gate0Args (mbx_args.h), the WaveNet kernels' selectors and shape constants
 
 namespace mbx {
@@ -261,12 +262,10 @@ struct RingAppendArgs {
     long long packed_samples;
     const long long *desc;        // (n_streams, 4): slot, abs_start, count, offset into packed
     int n_streams, max_count;     // max_count sizes the grid only: a larger count is still appended whole
-    float *rings;                 // (n_slots, ring_samples)
-    int n_slots, ring_samples;    // ring_samples a power of two
+    RingStoreOut rings;
 };
 struct MelStreamArgs {
-    const float *rings;
-    int n_slots, ring_samples;
+    RingStore rings;
     const long long *desc;        // (n_streams, 4): slot, first_frame, n_frames, n_total (< 0: the stream is still open)
     int n_streams, max_new_frames;
     int win, hop, fft_size, n_mels;
@@ -301,15 +300,13 @@ void launch_resample_poly(const ResampleArgs &a, hipStream_t stream);
 // streaming resampler (resample_stream.hip; include/mbexwn_live_resample.h: mbxr_resample_rings): from a ring store at the
 // input rate into the model-rate ring store of the streaming analysis, with resample_chain.h's chain
 struct ResampleStreamArgs {
-    const float *in_rings;        // (n_in_slots, in_ring_samples)
-    int n_in_slots, in_ring_samples;
+    RingStore in_rings;
     const long long *desc;        // (n_rows, 6): in_slot, out_slot, first_out, n_out_new, n_total_in (< 0: still open), 0
     int n_rows, max_new_out;      // max_new_out sizes the grid only: a larger n_out_new is still produced whole
     int up, down;
     const float *taps;            // (n_taps), natural order, gain included
     int n_taps;
-    float *out_rings;             // (n_out_slots, out_ring_samples)
-    int n_out_slots, out_ring_samples;
+    RingStoreOut out_rings;
 };
 // nullptr when the arguments describe a valid launch, else what is wrong with them
 const char *check_resample_stream(const ResampleStreamArgs &a);
@@ -318,8 +315,7 @@ void launch_resample_stream(const ResampleStreamArgs &a, hipStream_t stream);
 // the same resampler on the way out (resample_stream.hip; include/mbexwn_live_out.h: mbxo_resample_emit): from a model-rate
 // ring store into packed rows at the output rate
 struct ResampleEmitArgs {
-    const float *in_rings;        // (n_in_slots, in_ring_samples)
-    int n_in_slots, in_ring_samples;
+    RingStore in_rings;
     const long long *desc;        // (n_rows, 6): in_slot, first_out, n_out_new, n_total_in (< 0: still open), out_offset, 0
     int n_rows, max_new_out;      // max_new_out sizes the grid only: a larger n_out_new is still produced whole
     int up, down;
@@ -444,8 +440,7 @@ void launch_track_f0(const PitchArgs &a, hipStream_t stream);
 // the same tracker for sounds that are still arriving (f0_stream.hip; include/mbexwn_live_pitch.h: mbxt_f0_frames): frames
 // at t * hop from the ring store of the streaming mel analysis, on its descriptor table
 struct PitchStreamArgs {
-    const float *rings;          // (n_slots, ring_samples)
-    int n_slots, ring_samples;   // ring_samples a power of two, at least window + tau_max
+    RingStore rings;             // ring_samples at least window + tau_max
     const long long *desc;       // (n_streams, 4): slot, first_frame, n_frames, n_total (< 0: the stream is still open)
     int n_streams, max_new_frames;
     int hop, sample_rate, window, tau_min, tau_max;

@@ -87,9 +87,7 @@ mbx_status mbxl_ring_append(const float *packed, int64_t packed_samples, const i
     a.desc = reinterpret_cast<const long long *>(desc);
     a.n_streams = n_streams;
     a.max_count = max_count;
-    a.rings = rings;
-    a.n_slots = n_slots;
-    a.ring_samples = ring_samples;
+    a.rings = {rings, n_slots, ring_samples};
     if (const char *why = mbx::check_ring_append(a)) return refuse("ring append", why);
     mbx::launch_ring_append(a, static_cast<hipStream_t>(hip_stream));
     return launch_status("kernel launch: ");
@@ -100,9 +98,7 @@ mbx_status mbxl_mel_frames(const float *rings, int32_t n_slots, int32_t ring_sam
                            const float *window, const float *twiddle, const float *basis, const int32_t *bin_lo,
                            const int32_t *bin_hi, float eps, float *out, void *hip_stream) {
     mbx::MelStreamArgs a{};
-    a.rings = rings;
-    a.n_slots = n_slots;
-    a.ring_samples = ring_samples;
+    a.rings = {rings, n_slots, ring_samples};
     a.desc = reinterpret_cast<const long long *>(desc);
     a.n_streams = n_streams;
     a.max_new_frames = max_new_frames;
@@ -126,9 +122,7 @@ mbx_status mbxr_resample_rings(const float *in_rings, int32_t n_in_slots, int32_
                                int32_t n_rows, int32_t max_new_out, int32_t up, int32_t down, const float *taps, int32_t n_taps,
                                float *out_rings, int32_t n_out_slots, int32_t out_ring_samples, void *hip_stream) {
     mbx::ResampleStreamArgs a{};
-    a.in_rings = in_rings;
-    a.n_in_slots = n_in_slots;
-    a.in_ring_samples = in_ring_samples;
+    a.in_rings = {in_rings, n_in_slots, in_ring_samples};
     a.desc = reinterpret_cast<const long long *>(desc);
     a.n_rows = n_rows;
     a.max_new_out = max_new_out;
@@ -136,9 +130,7 @@ mbx_status mbxr_resample_rings(const float *in_rings, int32_t n_in_slots, int32_
     a.down = down;
     a.taps = taps;
     a.n_taps = n_taps;
-    a.out_rings = out_rings;
-    a.n_out_slots = n_out_slots;
-    a.out_ring_samples = out_ring_samples;
+    a.out_rings = {out_rings, n_out_slots, out_ring_samples};
     if (const char *why = mbx::check_resample_stream(a)) return refuse("resample rings", why);
     mbx::launch_resample_stream(a, static_cast<hipStream_t>(hip_stream));
     return launch_status("kernel launch: ");
@@ -148,9 +140,7 @@ mbx_status mbxo_resample_emit(const float *in_rings, int32_t n_in_slots, int32_t
                               int32_t n_rows, int32_t max_new_out, int32_t up, int32_t down, const float *taps, int32_t n_taps,
                               float *out, int64_t out_floats, void *hip_stream) {
     mbx::ResampleEmitArgs a{};
-    a.in_rings = in_rings;
-    a.n_in_slots = n_in_slots;
-    a.in_ring_samples = in_ring_samples;
+    a.in_rings = {in_rings, n_in_slots, in_ring_samples};
     a.desc = reinterpret_cast<const long long *>(desc);
     a.n_rows = n_rows;
     a.max_new_out = max_new_out;
@@ -334,9 +324,7 @@ mbx_status mbxt_f0_frames(const float *rings, int32_t n_slots, int32_t ring_samp
                           int32_t max_new_frames, int32_t hop, int32_t sample_rate, int32_t window, int32_t tau_min,
                           int32_t tau_max, float threshold, float e_min, float *f0, float *periodicity, void *hip_stream) {
     mbx::PitchStreamArgs a{};
-    a.rings = rings;
-    a.n_slots = n_slots;
-    a.ring_samples = ring_samples;
+    a.rings = {rings, n_slots, ring_samples};
     a.desc = reinterpret_cast<const long long *>(desc);
     a.n_streams = n_streams;
     a.max_new_frames = max_new_frames;
@@ -360,9 +348,7 @@ mbx_status mbxv_f0_candidate_frames(const float *rings, int32_t n_slots, int32_t
                                     int32_t n_thresholds, int32_t n_cand, float *period, float *cost, float *dprime,
                                     void *hip_stream) {
     mbx::CandidateStreamArgs a{};
-    a.ring.rings = rings;
-    a.ring.n_slots = n_slots;
-    a.ring.ring_samples = ring_samples;
+    a.ring.rings = {rings, n_slots, ring_samples};
     a.ring.desc = reinterpret_cast<const long long *>(desc);
     a.ring.n_streams = n_streams;
     a.ring.max_new_frames = max_new_frames;

@@ -27,11 +27,11 @@ __global__ __launch_bounds__(RING_APPEND_THREADS) void ring_append_kernel(RingAp
     const long long *d = p.desc + 4LL * blockIdx.y;
     const long long slot = d[0], start = d[1], offset = d[3];
     // one call never writes more than the ring holds of a stream
-    const long long count = min(d[2], (long long)p.ring_samples);
-    if (count <= 0 || slot < 0 || slot >= p.n_slots || start < 0 || offset < 0 || offset > p.packed_samples - count) return;
-    float *ring = p.rings + slot * p.ring_samples;
+    const long long count = min(d[2], (long long)p.rings.ring_samples);
+    if (count <= 0 || !p.rings.has(slot) || start < 0 || offset < 0 || offset > p.packed_samples - count) return;
+    float *ring = p.rings.row(slot);
     const float *src = p.packed + offset;
-    const long long mask = p.ring_samples - 1;
+    const long long mask = p.rings.mask();
     for (long long i = (long long)blockIdx.x * RING_APPEND_THREADS + threadIdx.x; i < count;
          i += (long long)gridDim.x * RING_APPEND_THREADS)
         ring[(start + i) & mask] = src[i];
@@ -39,12 +39,11 @@ __global__ __launch_bounds__(RING_APPEND_THREADS) void ring_append_kernel(RingAp
 
 __global__ __launch_bounds__(FFT_THREADS) void mel_stream_kernel(MelStreamArgs p, float log_eps) {
     extern __shared__ float2 smem[];
-    const long long *d = p.desc + 4LL * blockIdx.y;
-    const long long slot = d[0], n_total = d[3];
-    if ((long long)blockIdx.x >= d[2] || slot < 0 || slot >= p.n_slots || d[1] < 0) return;
-    const long long t = d[1] + blockIdx.x;
-    const float *ring = p.rings + slot * p.ring_samples;
-    const long long mask = p.ring_samples - 1;
+    const StreamRow row{p.desc + 4LL * blockIdx.y};
+    if (!row.has_frame(blockIdx.x, p.rings)) return;
+    const long long t = row.first() + blockIdx.x, n_total = row.n_total();
+    const float *ring = p.rings.row(row.slot());
+    const long long mask = p.rings.mask();
     const MelFrameTables tabs{p.win, p.fft_size, p.n_mels, p.window, p.twiddle, p.basis, p.bin_lo, p.bin_hi, p.eps, log_eps};
     const long long first = t * p.hop - p.win / 2;
     auto fetch = [=](int j, float &x) {
@@ -71,35 +70,29 @@ __global__ __launch_bounds__(FFT_THREADS) void mel_stream_kernel(MelStreamArgs p
     mel_frame_body(tabs, smem, fetch, p.out + ((long long)blockIdx.y * p.max_new_frames + blockIdx.x) * p.n_mels);
 }
 
-static bool power_of_two(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
 const char *check_ring_append(const RingAppendArgs &a) {
-    if (!a.packed || !a.desc || !a.rings) return "NULL pointer";
-    if (a.n_streams < 0 || a.n_streams > 65535) return "n_streams must lie in [0, 65535]";
+    if (!a.packed || !a.desc || !a.rings.data) return "NULL pointer";
+    if (!row_count_fits(a.n_streams)) return "n_streams must lie in [0, 65535]";
     if (a.packed_samples < 0 || a.max_count < 0) return "packed_samples and max_count must not be negative";
-    if (a.n_slots < 1) return "n_slots must be at least 1";
-    if (!power_of_two(a.ring_samples)) return "ring_samples must be a power of two";
-    return nullptr;
+    return ring_store_ok(a.rings) ? nullptr : "n_slots must be at least 1 and ring_samples a power of two";
 }
 
 void launch_ring_append(const RingAppendArgs &a, hipStream_t stream) {
     if (a.n_streams == 0 || a.max_count == 0) return;
-    const long long want = ((long long)std::min(a.max_count, a.ring_samples) + RING_APPEND_THREADS - 1) / RING_APPEND_THREADS;
+    const long long want = ((long long)std::min(a.max_count, a.rings.ring_samples) + RING_APPEND_THREADS - 1) / RING_APPEND_THREADS;
     const int blocks = (int)std::min<long long>(std::max<long long>(want, 1), RING_APPEND_MAX_BLOCKS);
     hipLaunchKernelGGL(ring_append_kernel, dim3(blocks, a.n_streams), dim3(RING_APPEND_THREADS), 0, stream, a);
 }
 
 const char *check_mel_stream(const MelStreamArgs &a) {
-    if (!a.rings || !a.desc || !a.window || !a.twiddle || !a.basis || !a.bin_lo || !a.bin_hi || !a.out) return "NULL pointer";
-    if (a.n_streams < 0 || a.n_streams > 65535) return "n_streams must lie in [0, 65535]";
+    if (!a.rings.data || !a.desc || !a.window || !a.twiddle || !a.basis || !a.bin_lo || !a.bin_hi || !a.out) return "NULL pointer";
+    if (!row_count_fits(a.n_streams)) return "n_streams must lie in [0, 65535]";
     if (a.max_new_frames < 0) return "max_new_frames must not be negative";
-    if (a.n_slots < 1) return "n_slots must be at least 1";
     // the bounds of launch_mel_analysis
     if (a.fft_size < 8 || a.fft_size > 2048 || !power_of_two(a.fft_size)) return "fft_size must be a power of two in [8, 2048]";
     if (a.win < 2 || a.win > a.fft_size) return "win must lie in [2, fft_size]";
     if (a.hop < 1 || a.n_mels < 1) return "hop and n_mels must be at least 1";
-    if (!power_of_two(a.ring_samples) || a.ring_samples < a.win) return "ring_samples must be a power of two, at least win";
-    return nullptr;
+    return ring_store_ok(a.rings, a.win) ? nullptr : "n_slots must be at least 1 and ring_samples a power of two, at least win";
 }
 
 void launch_mel_stream(const MelStreamArgs &a, hipStream_t stream) {

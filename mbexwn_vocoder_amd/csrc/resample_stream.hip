@@ -65,47 +65,41 @@ template <bool T_LDS>
 __global__ __launch_bounds__(RSS_THREADS) void resample_stream_kernel(ResampleStreamArgs p) {
     const long long *d = p.desc + 6LL * blockIdx.y;
     const long long in_slot = d[0], out_slot = d[1], first_out = d[2], n_total = d[4];
-    const long long n_new = min(d[3], (long long)p.out_ring_samples);     // one call never writes more than the ring holds
-    if (out_slot < 0 || out_slot >= p.n_out_slots) return;
-    float *out = p.out_rings + out_slot * p.out_ring_samples;
-    const long long out_mask = p.out_ring_samples - 1;
-    resample_stream_row<T_LDS>(p.in_rings, p.n_in_slots, p.in_ring_samples, p.up, p.down, p.taps, p.n_taps, in_slot, first_out,
-                               n_new, n_total, [=](long long k, float v) { out[k & out_mask] = v; });
+    const long long n_new = min(d[3], (long long)p.out_rings.ring_samples);     // one call never writes more than the ring holds
+    if (!p.out_rings.has(out_slot)) return;
+    float *out = p.out_rings.row(out_slot);
+    const long long out_mask = p.out_rings.mask();
+    resample_stream_row<T_LDS>(p.in_rings.data, p.in_rings.n_slots, p.in_rings.ring_samples, p.up, p.down, p.taps, p.n_taps,
+                               in_slot, first_out, n_new, n_total, [=](long long k, float v) { out[k & out_mask] = v; });
 }
 
 // into packed rows (mbxo_resample_emit, include/mbexwn_live_out.h): output first_out + i at out[out_offset + i]
 template <bool T_LDS>
 __global__ __launch_bounds__(RSS_THREADS) void resample_emit_kernel(ResampleEmitArgs p) {
-    const long long *d = p.desc + 6LL * blockIdx.y;
-    const long long in_slot = d[0], first_out = d[1], n_new = d[2], n_total = d[3], out_offset = d[4];
-    if (out_offset < 0 || out_offset > p.out_floats || n_new > p.out_floats - out_offset) return;   // the row must fit `out`
-    float *out = p.out + out_offset;
-    resample_stream_row<T_LDS>(p.in_rings, p.n_in_slots, p.in_ring_samples, p.up, p.down, p.taps, p.n_taps, in_slot, first_out,
-                               n_new, n_total, [=](long long k, float v) { out[k - first_out] = v; });
+    const EmitRow row = EmitRow::of(p.desc + 6LL * blockIdx.y);
+    if (!row.fits(p.in_rings, p.out_floats)) return;
+    float *out = p.out + row.out_offset;
+    const long long first_out = row.first_out;
+    resample_stream_row<T_LDS>(p.in_rings.data, p.in_rings.n_slots, p.in_rings.ring_samples, p.up, p.down, p.taps, p.n_taps,
+                               row.slot, first_out, row.n_new, row.n_total, [=](long long k, float v) { out[k - first_out] = v; });
 }
 
-static bool rss_power_of_two(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
 const char *check_resample_stream(const ResampleStreamArgs &a) {
-    if (!a.in_rings || !a.desc || !a.taps || !a.out_rings) return "NULL pointer";
-    if (a.n_rows < 0 || a.n_rows > 65535) return "n_rows must lie in [0, 65535]";
+    if (!a.in_rings.data || !a.desc || !a.taps || !a.out_rings.data) return "NULL pointer";
+    if (!row_count_fits(a.n_rows)) return "n_rows must lie in [0, 65535]";
     if (a.max_new_out < 0) return "max_new_out must not be negative";
     if (a.up < 1 || a.down < 1 || a.n_taps < 1) return "up, down and n_taps must be at least 1";
-    if (a.n_in_slots < 1 || a.n_out_slots < 1) return "n_in_slots and n_out_slots must be at least 1";
-    if (!rss_power_of_two(a.in_ring_samples) || !rss_power_of_two(a.out_ring_samples))
-        return "in_ring_samples and out_ring_samples must be powers of two";
-    return nullptr;
+    if (!ring_store_ok(a.in_rings)) return "n_in_slots must be at least 1 and in_ring_samples a power of two";
+    return ring_store_ok(a.out_rings) ? nullptr : "n_out_slots must be at least 1 and out_ring_samples a power of two";
 }
 
 const char *check_resample_emit(const ResampleEmitArgs &a) {
-    if (!a.in_rings || !a.desc || !a.taps || !a.out) return "NULL pointer";
-    if (a.n_rows < 0 || a.n_rows > 65535) return "n_rows must lie in [0, 65535]";
+    if (!a.in_rings.data || !a.desc || !a.taps || !a.out) return "NULL pointer";
+    if (!row_count_fits(a.n_rows)) return "n_rows must lie in [0, 65535]";
     if (a.max_new_out < 0) return "max_new_out must not be negative";
     if (a.up < 1 || a.down < 1 || a.n_taps < 1) return "up, down and n_taps must be at least 1";
-    if (a.n_in_slots < 1) return "n_in_slots must be at least 1";
-    if (!rss_power_of_two(a.in_ring_samples)) return "in_ring_samples must be a power of two";
     if (a.out_floats < 0) return "out_floats must not be negative";
-    return nullptr;
+    return ring_store_ok(a.in_rings) ? nullptr : "n_in_slots must be at least 1 and in_ring_samples a power of two";
 }
 
 // one block per (row, tile of the longest row), at most RSS_MAX_TILES tiles; the taps in LDS when they fit
@@ -124,7 +118,7 @@ static void rss_launch(void (*taps_in_lds)(Args), void (*taps_in_global)(Args), 
 
 void launch_resample_stream(const ResampleStreamArgs &a, hipStream_t stream) {
     if (a.n_rows == 0 || a.max_new_out == 0) return;
-    rss_launch(resample_stream_kernel<true>, resample_stream_kernel<false>, a, std::min(a.max_new_out, a.out_ring_samples), stream);
+    rss_launch(resample_stream_kernel<true>, resample_stream_kernel<false>, a, std::min(a.max_new_out, a.out_rings.ring_samples), stream);
 }
 
 void launch_resample_emit(const ResampleEmitArgs &a, hipStream_t stream) {

@@ -359,7 +359,11 @@ def limit_emit_device(rings, desc, n_rows, max_new, ceiling, h, H, out, stats=No
     return out
 
 
+def gain_bits(g0):
+    """The sixth word of a descriptor row of ``mbxd_limit_emit``: the bit pattern of the float32 gain."""
+    return int(np.float32(g0).view(np.uint32))
+
+
 def emit_row(slot, first_out, count, final, out_offset, g0):
     """One descriptor row of ``mbxd_limit_emit``; ``final``: the stream's length once it is known, else None."""
-    return [int(slot), int(first_out), int(count), -1 if final is None else int(final), int(out_offset),
-            int(np.float32(g0).view(np.uint32))]
+    return [int(slot), int(first_out), int(count), -1 if final is None else int(final), int(out_offset), gain_bits(g0)]

@@ -17,15 +17,15 @@ chain from a ring of the synthesizer's model-rate samples into packed rows (incl
 ``resample.resample_device`` gives on the stream's whole synthesis.  Streams without an output rate get what they got.
 
 The readiness rules (``frames_ready``, ``outputs_ready``, ``input_keep_from``), the mapping of per-push transposition factors
-to mel frames (``FrameFactors``) and what a tick does (``AnalysisPlan``, ``OutputPlan``) are pure host logic: live_plan.py.
+to mel frames (``FrameFactors``) and what a tick does (``AnalysisPlan``, ``EmitPlan``) are pure host logic: live_plan.py.
 """
 import ctypes
 
 import numpy as np
 
 from .analysis import mel_analysis_tables, mell_header
-from .live_plan import (AnalysisPlan, FrameFactors, LimiterPlan, OutputPlan, _AStream, _DStream, _OStream,  # noqa: F401
-                        _pow2_at_least, check_rate,
+from .live_plan import (AnalysisPlan, EmitPlan, FrameFactors, LimiterPlan, OutputPlan, _AStream, _DStream,  # noqa: F401
+                        _OStream, _pow2_at_least, check_rate,
                         f0_frames_ready, frame_factors, frames_ready, frames_total, input_keep_from, outputs_ready,
                         stream_frames_ready)
 from .resample import _host_taps, device_taps, positive_rate
@@ -135,6 +135,18 @@ class _Stage:
         size = _pow2_at_least(max(size, 1024))
         self.device_allocations += 1
         return torch.zeros(size, dtype=dtype).pin_memory(), torch.zeros(size, dtype=dtype, device=self.device)
+
+    def _state_rows(self, table, slots, words):
+        """A table of int32 state rows on the device, one per ring slot: ``table`` itself when it has ``slots`` rows, else
+        a longer one that keeps its rows and starts the new ones from zero."""
+        import torch
+        if table is not None and table.shape[0] >= slots:
+            return table
+        new = torch.zeros((slots, words), dtype=torch.int32, device=self.device)
+        if table is not None:
+            new[:table.shape[0]] = table
+        self.device_allocations += 1
+        return new
 
     def _upload(self, host, dev_buf, used):
         """The tick's one upload on the current stream -> (the stream, the device address, the events around the launches)."""
@@ -354,13 +366,8 @@ class StreamingAnalyzer(_Stage):
         fresh stream beside its ring, whether or not the tick launches the decoder)."""
         import torch
         from .abi import load_library
-        words, slots = int(load_library().mbxv_lag_state_words()), int(self.rings.shape[0])
-        if self._lag_state is None or self._lag_state.shape[0] < slots:
-            new = torch.zeros((slots, words), dtype=torch.int32, device=self.device)
-            if self._lag_state is not None:
-                new[:self._lag_state.shape[0]] = self._lag_state
-            self._lag_state = new
-            self.device_allocations += 1
+        words = int(load_library().mbxv_lag_state_words())
+        self._lag_state = self._state_rows(self._lag_state, int(self.rings.shape[0]), words)
         need = 3 * plan.T * plan.max_new * 8
         if self._cand is None or self._cand.numel() < need:
             self._cand = torch.zeros(_pow2_at_least(max(need, 1024)), dtype=torch.float32, device=self.device)
@@ -476,51 +483,40 @@ def resolve_output_rate(output_rate, sample_rate, model_rate):
     return None if rate == int(round(model_rate)) else rate
 
 
-class StreamingOutputResampler(_Stage):
-    """The way out of a live stream: model-rate audio that is still being produced, resampled on the device to each
-    stream's own output rate, a tick at a time (csrc/resample_stream.hip through include/mbexwn_live_out.h).
-
-    The concatenated arrays ``tick`` hands out for a stream opened at rate R are ``resample.resample_device(the stream's
-    whole model-rate sound, None, model_rate, R)`` bit for bit, ceil(n * up / down) samples, however the sound was cut into
-    pushes.  The rules are those of the resampled input streams read in the other direction: with ``have`` model-rate
-    samples appended, ``outputs_ready(have, up, down, half, closed)`` outputs are final; the ring (a third ``_RingStore``,
-    at the model rate) holds every sample from ``input_keep_from(next output, ...)`` on and grows by doubling before it
-    would not; after ``push(..., last=True)`` the remaining outputs follow with the filter's tail clipped at the end.
+class _EmitStage(_Stage):
+    """What the stages behind the synthesizer share: model-rate or output-rate audio that is still
+    being produced goes into a ring per stream, and every output that became final leaves in packed rows.
 
     A push names where the samples ARE on the device -- ``source``, a contiguous float32 tensor, ``count`` samples from flat
     element ``offset`` -- and the tick's ``mbxl_ring_append`` reads them from there: the audio never visits the host on its
-    way in.  A steady tick is one small pinned upload (the descriptor tables), one append per distinct source tensor, one
-    ``mbxo_resample_emit`` per distinct output rate into one packed buffer, and one copy back; it allocates no device
-    memory (``device_allocations`` counts every (re)allocation).
+    way in.  A tick is planned on the host (``plan``: an ``EmitPlan``, no device); a steady one is one small pinned upload
+    (the descriptor tables), one append per distinct source tensor, one launch of the stage's kernel per distinct key among
+    the streams with work into one packed buffer, and one copy back; it allocates no device memory (``device_allocations``
+    counts every (re)allocation).  The ring store grows by doubling before a stream's pushes would overwrite samples a
+    pending output still reads.
 
     ``last_emit_device``, like the synthesizer's: where the last tick left its outputs on the device, ``(tensor, {stream_id:
-    (flat offset, count)})``, valid until the next tick; None after a tick without output.  The streaming limiter reads
-    resampled audio from there."""
-    _taps_to_model = False
+    (flat offset, count)})``, valid until the next tick; None after a tick without output.  The next stage reads from there.
 
-    def __init__(self, model_rate, device=None, ring_samples=None, slots=16):
-        super().__init__(positive_rate(model_rate, "model_rate"), device)
-        # 4096: a synthesis tick of the 80 ms schedule hands over up to 7 frames = 2100 samples at once, behind the 44 to 130
-        # samples (48 kHz to 8 kHz) a pending output still reads
-        self._store = _RingStore(int(ring_samples or 4096), slots)
+    A stage gives ``open``, the streams' records (``live_plan._EStream``: their two rules and their key) and three hooks:
+    ``_prepare`` -- what the groups of a tick need on the device before the launches --, ``_word5`` -- the sixth word of a
+    stream's descriptor row -- and ``_launch``, the one launch of a group."""
+
+    def __init__(self, model_rate, device, ring_samples, slots):
+        super().__init__(model_rate, device)
+        self._store = _RingStore(ring_samples, slots)
         self._desc_host = self._desc_dev = None       # one tick's descriptor tables (int64): pinned, and its device twin
         self.last_emit_device = None
 
     # -- host side ----------------------------------------------------------------------------------------------------
-    def open(self, stream_id, output_rate):
-        if stream_id in self.streams:
-            raise ValueError(f"stream {stream_id!r} is open already")
-        rate = positive_rate(output_rate, f"stream {stream_id!r}: output_rate")
-        self.streams[stream_id] = _OStream(self._store.take(), rate, output_filter(self.model_rate, rate))
-
     def close(self, stream_id):
         """Forget a stream (its slot is reused)."""
         self._store.release(self.streams.pop(stream_id).slot)
 
     def push(self, stream_id, source, offset, count, last=False):
-        """The stream's next ``count`` model-rate samples are the flat elements [offset, offset + count) of ``source``, a
-        contiguous float32 tensor on the stage's device that stays valid until the next ``tick``; ``last`` closes the
-        stream.  ``count`` 0 needs no source."""
+        """The stream's next ``count`` samples are the flat elements [offset, offset + count) of ``source``, a contiguous
+        float32 tensor on the stage's device that stays valid until the next ``tick``; ``last`` closes the stream.
+        ``count`` 0 needs no source."""
         st = self.streams[stream_id]
         if st.closed:
             raise ValueError(f"stream {stream_id!r} is closed")
@@ -539,11 +535,11 @@ class StreamingOutputResampler(_Stage):
 
     def finished(self, stream_id):
         st = self.streams[stream_id]
-        return st.closed and st.emitted >= outputs_ready(st.have, *st.filt[:3], closed=True)
+        return st.closed and st.emitted >= st.ready()
 
     def plan(self):
         """What the next tick does, from the host state alone (no device, nothing changes)."""
-        return OutputPlan(self.streams)
+        return EmitPlan(self.streams)
 
     def commit(self, plan):
         """Move the streams on to behind the planned tick."""
@@ -553,22 +549,12 @@ class StreamingOutputResampler(_Stage):
             st.emitted += n_new
 
     # -- device side --------------------------------------------------------------------------------------------------
-    def _append_calls(self, plan):
-        """The append rows of a tick: one call per distinct source tensor (and per place in its stream's queue: two rows of
-        one call never name the same slot) -> {(turn, address, elements): [(slot, abs_start, count, offset)]}."""
-        calls = {}
-        for sid, _, _, _ in plan.rows:
-            st, at = self.streams[sid], self.streams[sid].on_device
-            for turn, (source, offset, count) in enumerate(st.queue):
-                if source.device != self.device:
-                    raise ValueError(f"stream {sid!r}: source is on {source.device}, the stage on {self.device}")
-                calls.setdefault((turn, source.data_ptr(), source.numel()), []).append((st.slot, at, count, offset))
-                at += count
-        return calls
+    def _word5(self, st):
+        return 0
 
     def tick(self):
-        """Append what was pushed to the rings and resample every output that became final.
-        Returns {stream_id: float32 ndarray at the stream's output rate} for the streams with new output."""
+        """Append what was pushed to the rings and emit every output that became final.
+        Returns {stream_id: float32 ndarray} for the streams with new output."""
         plan = self.plan()
         self.last_emit_device = None
         if not plan.rows:
@@ -578,42 +564,70 @@ class StreamingOutputResampler(_Stage):
         lib, dev = load_library(), self._resolve_device()
         held = ((st.slot, st.on_device) for st in self.streams.values() if st.on_device)
         self.device_allocations += self._store.ensure(dev, plan.ring_needed, held)
-        rings, ring = self._store.rings, self._store.ring_samples
-        calls = self._append_calls(plan)
-        app = [row for rows in calls.values() for row in rows]
-        n_app, S = len(app), len(plan.rows)
-        starts = [0, *np.cumsum([max(n_new, 0) for _, _, n_new, _ in plan.rows]).tolist()]    # where a row's outputs go
-        emit = [(self.streams[sid].slot, first_out, n_new, n_total, at, 0)
-                for (sid, first_out, n_new, n_total), at in zip(plan.rows, starts)]
-        used, total = 4 * n_app + 6 * S, starts[-1]
+        for sid, _, _, _ in plan.rows:
+            for source, _, _ in self.streams[sid].queue:
+                if source.device != dev:
+                    raise ValueError(f"stream {sid!r}: source is on {source.device}, the stage on {dev}")
+        rings, n_app, used, total = self._store.rings, plan.n_app, plan.words, plan.starts[-1]
+        store = (rings.data_ptr(), int(rings.shape[0]), self._store.ring_samples)
         self._desc_host, self._desc_dev = self._grown_pair(self._desc_host, self._desc_dev, used, torch.int64)
-        self._desc_host.numpy()[:used] = [word for row in app + emit for word in row]
+        plan.pack(self._desc_host.numpy(), self._word5)
         self._out_host, self._out_dev = self._grown_pair(self._out_host, self._out_dev, total, torch.float32)
-        for rate, _, _, _ in plan.groups:
-            self._device_taps(rate)
+        self._prepare(plan)
         with torch.cuda.device(dev):
             stream, base, events = self._upload(self._desc_host, self._desc_dev, used)
             first = 0
-            for (_, ptr, numel), rows in calls.items():
-                _check(lib.mbxl_ring_append(ptr, numel, base + 32 * first, len(rows), max(rr[2] for rr in rows),
-                                            rings.data_ptr(), int(rings.shape[0]), ring, stream.cuda_stream))
+            for (_, ptr, numel), rows in plan.calls.items():
+                _check(lib.mbxl_ring_append(ptr, numel, base + 32 * first, len(rows), max(rr[2] for rr in rows), *store,
+                                            stream.cuda_stream))
                 first += len(rows)
-            for rate, first, end, max_out in plan.groups:     # one launch per distinct output rate
-                taps, up, down = self._taps[rate]
-                _check(lib.mbxo_resample_emit(rings.data_ptr(), int(rings.shape[0]), ring, base + 32 * n_app + 48 * first,
-                                              end - first, max_out, up, down, taps.data_ptr(), int(taps.numel()),
-                                              self._out_dev.data_ptr(), int(self._out_dev.numel()), stream.cuda_stream))
+            for key, first, end, max_new in plan.groups:      # one launch per distinct key
+                _check(self._launch(lib, key, store, base + 32 * n_app + 48 * first, end - first, max_new, stream.cuda_stream))
             packed = self._copy_back(stream, events, total)
-        result = {sid: packed[at:at + n_new].copy() for (sid, _, n_new, _), at in zip(plan.rows, starts) if n_new > 0}
+        spans = {sid: (at, n_new) for (sid, _, n_new, _), at in zip(plan.rows, plan.starts) if n_new > 0}
         if total:
-            self.last_emit_device = (self._out_dev, {sid: (at, n_new) for (sid, _, n_new, _), at in zip(plan.rows, starts)
-                                                     if n_new > 0})
+            self.last_emit_device = (self._out_dev, spans)
         self.commit(plan)
         self.ticks += 1
-        return result
+        return {sid: packed[at:at + n_new].copy() for sid, (at, n_new) in spans.items()}
 
 
-class StreamingLimiter(_Stage):
+class StreamingOutputResampler(_EmitStage):
+    """The way out of a live stream: model-rate audio that is still being produced, resampled on the device to each
+    stream's own output rate, a tick at a time (csrc/resample_stream.hip through include/mbexwn_live_out.h).
+
+    The concatenated arrays ``tick`` hands out for a stream opened at rate R are ``resample.resample_device(the stream's
+    whole model-rate sound, None, model_rate, R)`` bit for bit, ceil(n * up / down) samples, however the sound was cut into
+    pushes.  The rules are those of the resampled input streams read in the other direction: with ``have`` model-rate
+    samples appended, ``outputs_ready(have, up, down, half, closed)`` outputs are final; the ring (a third ``_RingStore``,
+    at the model rate) holds every sample from ``input_keep_from(next output, ...)`` on; after ``push(..., last=True)`` the
+    remaining outputs follow with the filter's tail clipped at the end.
+
+    An emit stage (``_EmitStage``) whose key is the output rate: one ``mbxo_resample_emit`` per distinct rate."""
+    _taps_to_model = False
+
+    def __init__(self, model_rate, device=None, ring_samples=None, slots=16):
+        # 4096: a synthesis tick of the 80 ms schedule hands over up to 7 frames = 2100 samples at once, behind the 44 to 130
+        # samples (48 kHz to 8 kHz) a pending output still reads
+        super().__init__(positive_rate(model_rate, "model_rate"), device, int(ring_samples or 4096), slots)
+
+    def open(self, stream_id, output_rate):
+        if stream_id in self.streams:
+            raise ValueError(f"stream {stream_id!r} is open already")
+        rate = positive_rate(output_rate, f"stream {stream_id!r}: output_rate")
+        self.streams[stream_id] = _OStream(self._store.take(), rate, output_filter(self.model_rate, rate))
+
+    def _prepare(self, plan):
+        for rate, _, _, _ in plan.groups:
+            self._device_taps(rate)
+
+    def _launch(self, lib, rate, store, desc, n_rows, max_new, stream):
+        taps, up, down = self._taps[rate]
+        return lib.mbxo_resample_emit(*store, desc, n_rows, max_new, up, down, taps.data_ptr(), int(taps.numel()),
+                                      self._out_dev.data_ptr(), int(self._out_dev.numel()), stream)
+
+
+class StreamingLimiter(_EmitStage):
     """The last stage of a live stream: the look-ahead peak limiter of limiter.py on audio that is
     still being produced, a tick at a time (csrc/limiter.hip through ``mbxd_limit_emit``).
 
@@ -621,23 +635,18 @@ class StreamingLimiter(_Stage):
     for bit -- and so is ``stats(stream_id)`` --, however the sound was cut into pushes: with ``have`` samples appended,
     ``limiter.ready_outputs(have, h)`` outputs are final (output i once sample i + 2 h is there), every one once the
     stream is closed; the ring (a ``_RingStore`` at the stream's own rate) holds every sample from
-    ``limiter.keep_from(next output, h, H)`` on and grows by doubling before it would not.
+    ``limiter.keep_from(next output, h, H)`` on.
 
-    A stream has a fixed gain (it has no integrated loudness), a ceiling and a window at its rate.  A push names where the
-    samples ARE on the device, as ``StreamingOutputResampler.push`` does.  A steady tick is one small pinned upload (the
-    descriptor tables), one ``mbxl_ring_append`` per distinct source tensor, one ``mbxd_limit_emit`` per distinct (window,
-    ceiling) into one packed buffer, and one copy back; it allocates no device memory."""
+    A stream has a fixed gain (it has no integrated loudness), a ceiling and a window at its rate.  An emit stage
+    (``_EmitStage``) whose key is (window, ceiling): one ``mbxd_limit_emit`` per distinct one."""
 
     def __init__(self, device=None, ring_samples=None, slots=16):
-        super().__init__(None, device)
         # 8192: two ticks of the 80 ms schedule at 48 kHz behind the 1068 samples a pending output still reads
-        self._store = _RingStore(int(ring_samples or 8192), slots)
-        self._desc_host = self._desc_dev = None       # one tick's descriptor tables (int64): pinned, and its device twin
+        super().__init__(None, device, int(ring_samples or 8192), slots)
         self._stats = None            # int32 (slots, 4) on the device
         self._fresh = []              # slots of streams opened since the last tick: their statistics start over
         self._weights = {}            # h -> the weights on the device
 
-    # -- host side ----------------------------------------------------------------------------------------------------
     @staticmethod
     def check_open(stream_id, rate, gain_db=0.0, peak_limit=-1.0, lookahead_ms=None, hold_ms=None):
         """What ``open`` refuses, without opening: -> (rate, h, H, gain_db, peak_limit)."""
@@ -659,22 +668,6 @@ class StreamingLimiter(_Stage):
                                            float(np.float32(10.0 ** (peak_limit / 20.0))))
         self._fresh.append(slot)
 
-    def close(self, stream_id):
-        """Forget a stream (its slot is reused)."""
-        self._store.release(self.streams.pop(stream_id).slot)
-
-    push = StreamingOutputResampler.push
-
-    def finished(self, stream_id):
-        st = self.streams[stream_id]
-        return st.closed and st.emitted >= st.have
-
-    def plan(self):
-        """What the next tick does, from the host state alone (no device, nothing changes)."""
-        return LimiterPlan(self.streams)
-
-    commit = StreamingOutputResampler.commit
-
     def stats(self, stream_id):
         """``limiter.LimitStats`` of what the stream has been handed so far (a copy back; waits for the device)."""
         from .limiter import LimitStats
@@ -683,69 +676,28 @@ class StreamingLimiter(_Stage):
             return LimitStats(np.float32(1.0), 0, 0)
         return LimitStats.from_words(self._stats[st.slot].cpu().numpy())
 
-    # -- device side --------------------------------------------------------------------------------------------------
-    _append_calls = StreamingOutputResampler._append_calls
-
-    def _ensure_stats(self, dev):
-        import torch
-        from .limiter import ONE_BITS, STAT_WORDS
-        if self._stats is None or self._stats.shape[0] < self._store.slots:
-            new = torch.zeros((self._store.slots, STAT_WORDS), dtype=torch.int32, device=dev)
-            if self._stats is not None:
-                new[:self._stats.shape[0]] = self._stats
-            self._stats = new
-            self.device_allocations += 1
-        if self._fresh:
-            # the tick behind an open: a small temporary on the device, counted like every other allocation
-            self._stats[self._fresh] = torch.as_tensor([ONE_BITS, 0, 0, 0], dtype=torch.int32, device=dev)
-            self.device_allocations += 1
-            self._fresh = []
-
-    def tick(self):
-        """Append what was pushed to the rings and limit every output that became final.
-        Returns {stream_id: float32 ndarray} for the streams with new output."""
-        plan = self.plan()
-        if not plan.rows:
-            return {}
+    def _prepare(self, plan):
         import torch
         from . import limiter
-        from .abi import _check, load_library
-        lib, dev = load_library(), self._resolve_device()
-        held = ((st.slot, st.on_device) for st in self.streams.values() if st.on_device)
-        self.device_allocations += self._store.ensure(dev, plan.ring_needed, held)
-        self._ensure_stats(dev)
-        rings, ring = self._store.rings, self._store.ring_samples
-        calls = self._append_calls(plan)
-        app = [row for rows in calls.values() for row in rows]
-        n_app, S = len(app), len(plan.rows)
-        starts = [0, *np.cumsum([max(n_new, 0) for _, _, n_new, _ in plan.rows]).tolist()]    # where a row's outputs go
-        emit = [limiter.emit_row(self.streams[sid].slot, first_out, n_new, None if n_total < 0 else n_total, at,
-                                 self.streams[sid].g0) for (sid, first_out, n_new, n_total), at in zip(plan.rows, starts)]
-        used, total = 4 * n_app + 6 * S, starts[-1]
-        self._desc_host, self._desc_dev = self._grown_pair(self._desc_host, self._desc_dev, used, torch.int64)
-        self._desc_host.numpy()[:used] = [word for row in app + emit for word in row]
-        self._out_host, self._out_dev = self._grown_pair(self._out_host, self._out_dev, total, torch.float32)
+        self._stats = self._state_rows(self._stats, self._store.slots, limiter.STAT_WORDS)
+        if self._fresh:
+            # the tick behind an open: a small temporary on the device, counted like every other allocation
+            self._stats[self._fresh] = torch.as_tensor([limiter.ONE_BITS, 0, 0, 0], dtype=torch.int32, device=self.device)
+            self.device_allocations += 1
+            self._fresh = []
         for (h, _, _), _, _, _ in plan.groups:
             if h not in self._weights:
-                self._weights[h] = limiter.device_weights(h, dev)
+                self._weights[h] = limiter.device_weights(h, self.device)
                 self.device_allocations += 1
-        with torch.cuda.device(dev):
-            stream, base, events = self._upload(self._desc_host, self._desc_dev, used)
-            first = 0
-            for (_, ptr, numel), rows in calls.items():
-                _check(lib.mbxl_ring_append(ptr, numel, base + 32 * first, len(rows), max(rr[2] for rr in rows),
-                                            rings.data_ptr(), int(rings.shape[0]), ring, stream.cuda_stream))
-                first += len(rows)
-            for (h, hold, ceiling), first, end, max_new in plan.groups:      # one launch per distinct window and ceiling
-                _check(lib.mbxd_limit_emit(rings.data_ptr(), int(rings.shape[0]), ring, base + 32 * n_app + 48 * first,
-                                           end - first, max_new, ceiling, h, hold, self._weights[h].data_ptr(),
-                                           self._out_dev.data_ptr(), int(self._out_dev.numel()), self._stats.data_ptr(),
-                                           stream.cuda_stream))
-            packed = self._copy_back(stream, events, total)
-        result = {sid: packed[at:at + n_new].copy() for (sid, _, n_new, _), at in zip(plan.rows, starts) if n_new > 0}
-        self.commit(plan)
-        self.ticks += 1
-        return result
+
+    def _word5(self, st):
+        from .limiter import gain_bits
+        return gain_bits(st.g0)
+
+    def _launch(self, lib, key, store, desc, n_rows, max_new, stream):
+        h, hold, ceiling = key
+        return lib.mbxd_limit_emit(*store, desc, n_rows, max_new, ceiling, h, hold, self._weights[h].data_ptr(),
+                                   self._out_dev.data_ptr(), int(self._out_dev.numel()), self._stats.data_ptr(), stream)
 
 
 class _LStream:
@@ -807,10 +759,8 @@ class LiveResynthesizer:
         self.streams = {}
         # streams with an output rate of their own leave through this stage; its store is allocated by its first tick
         self.output = StreamingOutputResampler(self.analyzer.sample_rate, device=engine.device)
-        self._out_streams = 0
         # streams with a peak limit leave through the limiter, at the rate they are handed out at; allocated by its first tick
         self.limiter = StreamingLimiter(device=engine.device)
-        self._lim_streams = 0
 
     @property
     def lookahead_ms(self):
@@ -907,11 +857,9 @@ class LiveResynthesizer:
         st.limited = limit is not None
         if limit is not None:                               # the last stage, opened last: the checks above cannot fail it
             self.limiter.open(stream_id, *limit)
-            self._lim_streams += 1
         if out_rate is not None:
             self.output.open(stream_id, out_rate)
             st.out_rate = out_rate
-            self._out_streams += 1
 
     def close(self, stream_id):
         self.analyzer.close(stream_id)
@@ -919,10 +867,8 @@ class LiveResynthesizer:
         st = self.streams.pop(stream_id)
         if st.out_rate is not None:
             self.output.close(stream_id)
-            self._out_streams -= 1
         if st.limited:
             self.limiter.close(stream_id)
-            self._lim_streams -= 1
 
     def push_audio(self, stream_id, samples, last=False, transposition=None, sample_rate=None, formant=None):
         """Append samples at the stream's rate (the model's, unless it was opened at another); ``transposition``: one finite
@@ -992,43 +938,28 @@ class LiveResynthesizer:
             self.synthesizer.push(sid, scaled, noise, last=done, transposition=st.factors.take(first, end), **shift)
             st.frames, st.flushed = end, done
         audio = self.synthesizer.tick()
-        if self._out_streams:
-            audio = self._resample_out(audio)
-        if self._lim_streams:
-            audio = self._limit_out(audio)
+        for stage in (self.output, self.limiter):
+            if stage.streams:
+                audio = self._hand_on(stage, audio)
         return audio
 
-    def _resample_out(self, audio):
-        # the streams with an output rate: their chunks go on, from where the synthesizer left them on the device, to the
-        # output stage, and what that stage has final comes back in their place
-        source, spans = self.synthesizer.last_emit_device or (None, {})
+    def _hand_on(self, stage, audio):
+        # the streams of an emit stage: what the stage in front of it left on the device in this tick -- the output resampler
+        # for a limited stream with an output rate, else the synthesizer -- goes on to the stage, and what that has final
+        # comes back in its place
+        fronts = (self.synthesizer, self.output)
+        places = [front.last_emit_device or (None, {}) for front in fronts]      # asked once: the synthesizer makes its own
         for sid, st in self.streams.items():
-            if st.out_rate is None or self.output.streams[sid].closed:
+            if sid not in stage.streams or stage.streams[sid].closed:
                 continue
+            resampled = stage is self.limiter and st.out_rate is not None
+            front, (source, spans) = fronts[resampled], places[resampled]
             offset, count = spans.get(sid, (0, 0))
-            last = st.flushed and self.synthesizer.finished(sid)
+            last = (front is self.output or st.flushed) and front.finished(sid)
             if count or last:
-                self.output.push(sid, source, offset, count, last=last)
+                stage.push(sid, source, offset, count, last=last)
             audio.pop(sid, None)
-        audio.update(self.output.tick())
-        return audio
-
-    def _limit_out(self, audio):
-        # the streams with a peak limit: what the stage in front of the limiter left on the device in this tick -- the
-        # output resampler for a stream with an output rate, else the synthesizer -- goes on to the limiter, and what
-        # that has final comes back in its place
-        places = {False: self.synthesizer.last_emit_device or (None, {}), True: self.output.last_emit_device or (None, {})}
-        for sid, st in self.streams.items():
-            if not st.limited or self.limiter.streams[sid].closed:
-                continue
-            resampled = st.out_rate is not None
-            source, spans = places[resampled]
-            offset, count = spans.get(sid, (0, 0))
-            last = self.output.finished(sid) if resampled else st.flushed and self.synthesizer.finished(sid)
-            if count or last:
-                self.limiter.push(sid, source, offset, count, last=last)
-            audio.pop(sid, None)
-        audio.update(self.limiter.tick())
+        audio.update(stage.tick())
         return audio
 
     def finished(self, stream_id):

@@ -1,6 +1,6 @@
 """The host side of the live streams (live.py) as pure arithmetic: the readiness rules (``frames_ready``, ``outputs_ready``,
 ``input_keep_from``), the mapping of per-push transposition factors to mel frames (``FrameFactors``), the counters of a
-stream, and what one tick of the analyzer and of the output stage does (``AnalysisPlan``, ``OutputPlan``).  numpy only -- no
+stream, and what one tick of the analyzer and of an emit stage does (``AnalysisPlan``, ``EmitPlan``).  numpy only -- no
 torch, no engine -- so it runs and is tested without a device; live.py packs and uploads what a plan holds, launches, commits."""
 from itertools import accumulate
 
@@ -215,37 +215,14 @@ class AnalysisPlan:
             np.concatenate([part for queue in self.queues for part in queue], out=stage[self.body:self.body + self.samples])
 
 
-class _OStream:
-    def __init__(self, slot, rate, filt):
-        self.slot, self.rate, self.filt = slot, rate, filt     # filt: (up, down, half, n_taps), model rate -> rate
-        self.have = 0             # model-rate samples pushed
-        self.on_device = 0        # ... of which the ring holds the newest
-        self.emitted = 0          # outputs handed out
-        self.closed = False
-        self.queue = []           # (source, offset, count) pushed since the last tick
+class _EStream:
+    """A stream of an emit stage (live.py: ``_EmitStage``): samples that are named on the device go into its ring, the outputs
+    that became final leave in packed rows.  A subclass gives the two rules: ``ready()``, how many outputs are final, and
+    ``keep_from()``, the first sample a pending output still reads."""
 
-
-class OutputPlan:
-    """One tick of the output stage, planned on the host from its ``streams`` ({id: _OStream}) alone; building one changes
-    nothing.  The streams with work have samples to append or outputs that became final."""
-
-    def __init__(self, streams):
-        self.rows, rates = [], []     # (stream_id, first_out, n_out_new, n_total_in or -1) per stream with work, by output rate
-        self.ring_needed = 0          # the samples the longest-held stream's ring must hold
-        for sid, st in sorted(streams.items(), key=lambda kv: kv[1].rate):
-            n_new = outputs_ready(st.have, *st.filt[:3], closed=st.closed) - st.emitted
-            if n_new > 0 or st.queue:
-                self.rows.append((sid, st.emitted, n_new, st.have if st.closed else -1))
-                rates.append(st.rate)
-                # from the first sample a pending output may still read (never behind what is to be appended)
-                self.ring_needed = max(self.ring_needed, st.have - min(input_keep_from(st.emitted, *st.filt), st.on_device))
-        self.groups = list(rate_groups(rates, [row[2] for row in self.rows]))     # (rate, first, end, max_out) over the rows
-
-
-class _DStream:
-    def __init__(self, slot, rate, h, hold, g0, ceiling):
-        self.slot, self.rate, self.g0 = slot, rate, g0
-        self.key = (h, hold, ceiling)     # what one launch of the limiter shares: the window and the ceiling
+    def __init__(self, slot, rate, key):
+        self.slot, self.rate = slot, rate
+        self.key = key            # what one launch of the stage shares: the streams of a tick are grouped by it
         self.have = 0             # samples pushed
         self.on_device = 0        # ... of which the ring holds the newest
         self.emitted = 0          # outputs handed out
@@ -253,21 +230,82 @@ class _DStream:
         self.queue = []           # (source, offset, count) pushed since the last tick
 
 
-class LimiterPlan:
-    """One tick of the streaming limiter, planned on the host from its ``streams`` ({id: _DStream}) alone; building one
-    changes nothing.  The streams with work have samples to append or outputs that became final (``limiter.ready_outputs``:
-    output i once sample i + 2 h is there, or the stream is closed)."""
+class _OStream(_EStream):
+    def __init__(self, slot, rate, filt):
+        super().__init__(slot, rate, rate)
+        self.filt = filt          # (up, down, half, n_taps), model rate -> rate
+
+    def ready(self):
+        return outputs_ready(self.have, *self.filt[:3], closed=self.closed)
+
+    def keep_from(self):
+        return input_keep_from(self.emitted, *self.filt)
+
+
+class _DStream(_EStream):
+    def __init__(self, slot, rate, h, hold, g0, ceiling):
+        super().__init__(slot, rate, (h, hold, ceiling))      # one launch of the limiter shares the window and the ceiling
+        self.g0 = g0
+
+    def ready(self):
+        """``limiter.ready_outputs``: output i once sample i + 2 h is there, or the stream is closed."""
+        from .limiter import ready_outputs
+        return ready_outputs(self.have, self.key[0], self.have if self.closed else None)
+
+    def keep_from(self):
+        from .limiter import keep_from
+        return keep_from(self.emitted, *self.key[:2])
+
+
+class EmitPlan:
+    """One tick of an emit stage, planned on the host from its ``streams`` ({id: _EStream}) alone; building one changes
+    nothing.  The streams with work have samples to append or outputs that became final.  The descriptor tables are int64
+    as include/mbexwn_live.h (append rows), include/mbexwn_live_out.h and include/mbexwn_limiter.h (emit rows) lay them
+    out; a source is anything with ``data_ptr()`` and ``numel()``, and is asked only when the tables are."""
 
     def __init__(self, streams):
-        from .limiter import keep_from, ready_outputs
-        self.rows, keys = [], []      # (stream_id, first_out, n_new, n_total or -1) per stream with work, by window and ceiling
-        self.ring_needed = 0          # the samples the longest-held stream's ring must hold
+        self.rows, self._streams = [], []     # (stream_id, first_out, n_new, n_total or -1) per stream with work, by key (stable)
+        self.ring_needed = 0                  # the samples the longest-held stream's ring must hold
         for sid, st in sorted(streams.items(), key=lambda kv: kv[1].key):
-            h, hold, _ = st.key
-            n_new = ready_outputs(st.have, h, st.have if st.closed else None) - st.emitted
+            n_new = st.ready() - st.emitted
             if n_new > 0 or st.queue:
                 self.rows.append((sid, st.emitted, n_new, st.have if st.closed else -1))
-                keys.append(st.key)
+                self._streams.append(st)
                 # from the first sample a pending output may still read (never behind what is to be appended)
-                self.ring_needed = max(self.ring_needed, st.have - min(keep_from(st.emitted, h, hold), st.on_device))
-        self.groups = list(rate_groups(keys, [row[2] for row in self.rows]))     # (key, first, end, max_new) over the rows
+                self.ring_needed = max(self.ring_needed, st.have - min(st.keep_from(), st.on_device))
+        new = [row[2] for row in self.rows]
+        self.groups = list(rate_groups([st.key for st in self._streams], new))      # (key, first, end, max_new) over the rows
+        self.starts = list(accumulate((max(nn, 0) for nn in new), initial=0))       # where a row's outputs go; [-1]: their sum
+        self._calls = None
+
+    @property
+    def calls(self):
+        """The append rows of the tick: one call per distinct source tensor (and per place in its stream's queue: two rows of
+        one call never name the same slot) -> {(turn, address, elements): [(slot, abs_start, count, offset)]}."""
+        if self._calls is None:
+            self._calls = calls = {}
+            for st in self._streams:
+                at = st.on_device
+                for turn, (source, offset, count) in enumerate(st.queue):
+                    calls.setdefault((turn, source.data_ptr(), source.numel()), []).append((st.slot, at, count, offset))
+                    at += count
+        return self._calls
+
+    @property
+    def n_app(self):
+        return sum(len(rows) for rows in self.calls.values())
+
+    @property
+    def words(self):
+        """int64 words of the tick's upload: the (n_app, 4) append rows, call by call, then the (S, 6) emit rows."""
+        return 4 * self.n_app + 6 * len(self.rows)
+
+    def pack(self, desc, word5_of):
+        """The tick's upload into ``desc`` (int64, ``words`` or more); ``word5_of(stream)``: the sixth word of its emit row."""
+        app = [row for rows in self.calls.values() for row in rows]
+        emit = [(st.slot, first_out, n_new, n_total, at, word5_of(st))
+                for st, (_, first_out, n_new, n_total), at in zip(self._streams, self.rows, self.starts)]
+        desc[:self.words] = [word for row in app + emit for word in row]
+
+
+OutputPlan = LimiterPlan = EmitPlan       # the names the two emit stages' plans had when they were two classes

@@ -17,6 +17,10 @@ With ``--output-rate R`` a further leg follows: the live leg with every stream o
 of ``--input-rate``, when given), so that the device time of the output stage's launches -- mbxl_ring_append from the
 synthesizer's buffer, mbxo_resample_emit -- and the host-inclusive live tick stand next to the tick without an output rate.
 
+With ``--limiter`` a last leg follows: that leg again (with the output rate, when given) with every stream opened with
+``peak_limit=-1.0``, so that the device time of the limiter's launches -- mbxl_ring_append from the buffer of the stage in
+front of it, mbxd_limit_emit -- and the host-inclusive live tick stand next to the tick without a limiter.
+
 Prints one JSON line.  ``--synthesis-only`` runs the first leg alone; with ``--root DIR`` the package is imported from another
 checkout (the parent commit, for the comparison of the synthesis tick), which needs nothing of the live path.
 """
@@ -85,13 +89,15 @@ def synthesis_leg(torch, inv, streams, warm_seconds, ticks):
             "graph_ticks": int(syn.graph_ticks)}
 
 
-def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None, output_rate=None):
+def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None, output_rate=None, limiter=False):
     from mbexwn_vocoder_amd.live import LiveResynthesizer
     live = LiveResynthesizer(inv, chunk_frames=SCHEDULE)
     live.analyzer.time_device = True
     live.synthesizer.time_device = True
     if output_rate:
         live.output.time_device = True
+    if limiter:
+        live.limiter.time_device = True
     rate = int(input_rate or inv.srate)
     per_tick = int(round(0.080 * rate))
     rng = np.random.default_rng(99)
@@ -101,10 +107,12 @@ def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None, output_r
     rates = {"sample_rate": input_rate} if input_rate else {}
     if output_rate:
         rates["output_rate"] = output_rate
+    if limiter:
+        rates["peak_limit"] = -1.0
     for sid in range(streams):
         live.open(sid, seed=sid, **rates)
-    allocations = out_allocations = None
-    tick_ms, push_ms, analysis_ms, syn_dev_ms, output_ms, replayed, pos, warm_ticks = [], [], [], [], [], 0, 0, 0
+    allocations = out_allocations = lim_allocations = None
+    tick_ms, push_ms, analysis_ms, syn_dev_ms, output_ms, limiter_ms, replayed, pos, warm_ticks = [], [], [], [], [], [], 0, 0, 0
     t_start = time.perf_counter()
     while len(tick_ms) < ticks:
         t0 = time.perf_counter()
@@ -121,8 +129,11 @@ def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None, output_r
             if allocations is None:
                 allocations = live.analyzer.device_allocations
                 out_allocations = live.output.device_allocations if output_rate else 0
+                lim_allocations = live.limiter.device_allocations if limiter else 0
             if output_rate:
                 output_ms.append(live.output.last_tick_device_ms)
+            if limiter:
+                limiter_ms.append(live.limiter.last_tick_device_ms)
             tick_ms.append((t2 - t1) * 1e3)
             push_ms.append((t1 - t0) * 1e3)
             analysis_ms.append(live.analyzer.last_tick_device_ms)
@@ -142,7 +153,10 @@ def live_leg(torch, inv, streams, warm_seconds, ticks, input_rate=None, output_r
                 "output_lookahead_ms": live.lookahead_ms_for(input_rate or None, output_rate) - live.lookahead_ms_for(input_rate or None),
                 "output_device_allocations_during_timed_ticks": live.output.device_allocations - out_allocations,
                 "output_ring_samples": live.output.ring_samples, "samples_per_stream_and_tick": int(next(iter(res.values())).size)}
-               if output_rate else {})}
+               if output_rate else {}),
+            **({"peak_limit": -1.0, "limiter_launches_ms_device": percentiles(limiter_ms),
+                "limiter_device_allocations_during_timed_ticks": live.limiter.device_allocations - lim_allocations,
+                "limiter_ring_samples": live.limiter.ring_samples} if limiter else {})}
 
 
 def main():
@@ -156,6 +170,8 @@ def main():
     ap.add_argument("--output-rate", type=int, default=0, metavar="R",
                     help="also run the live leg with every stream opened with output_rate=R (resampled on the device on the way "
                          "out)")
+    ap.add_argument("--limiter", action="store_true",
+                    help="also run the live leg (with the output rate, when given) with every stream opened with peak_limit=-1.0")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="checkout to import mbexwn_vocoder_amd from (default: this one)")
     ap.add_argument("--label", default="")
@@ -177,6 +193,10 @@ def main():
         if args.output_rate and args.output_rate != int(inv.srate):
             out["live_output"] = live_leg(torch, inv, args.streams, args.warm_seconds, args.ticks, args.input_rate or None,
                                           args.output_rate)
+        if args.limiter:
+            out_rate = args.output_rate if args.output_rate != int(inv.srate) else 0
+            out["live_limited"] = live_leg(torch, inv, args.streams, args.warm_seconds, args.ticks, args.input_rate or None,
+                                           out_rate or None, limiter=True)
     print(json.dumps(out))
 
 

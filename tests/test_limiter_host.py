@@ -234,3 +234,54 @@ def test_the_file_tools_refuse_a_window_before_a_model_is_loaded(tmp_path):
                              timeout=120)
         assert res.returncode == 1 and f"{tool[:-3]}::error:: limiter:" in res.stderr and word in res.stderr, res.stderr[-2000:]
         assert "Traceback" not in res.stderr
+
+
+def test_a_worked_tick_packs_the_descriptor_words_of_the_headers():
+    """Four streams, one tick, every word by hand from the row layouts of mbexwn_live.h (append: slot, abs_start, count,
+    offset) and mbexwn_limiter.h (emit: slot, first_out, n_new, n_total or -1, out_offset, the bits of g0).  Output i is
+    final once sample i + 2 h is there: h = 18 at 24 kHz, 6 at 8 kHz."""
+    import math
+    import torch
+    from mbexwn_vocoder_amd import live
+    one, two = torch.zeros(1200, dtype=torch.float32), torch.zeros(64, dtype=torch.float32)
+    stage = live.StreamingLimiter()
+    double = 20.0 * math.log10(2.0)                      # 10 ** (double / 20) rounds to the float32 2.0
+    for sid, rate, gain_db in (("a", 24000, double), ("b", 8000, 0.0), ("c", 24000, -double), ("d", 24000, 0.0)):    # slots 0 .. 3
+        stage.open(sid, rate, gain_db=gain_db)
+    ceiling = float(np.float32(10.0 ** (-1.0 / 20.0)))
+    wide, narrow = (18, 480, ceiling), (6, 160, ceiling)
+    assert [st.key for st in stage.streams.values()] == [wide, narrow, wide, wide]
+    stage.push("a", one, 0, 100)                         # an earlier tick: outputs 0 .. 63
+    first = stage.plan()
+    assert first.rows == [("a", 0, 64, -1)] and first.starts == [0, 64]
+    stage.commit(first)
+    stage.push("a", one, 100, 500)                       # two pushes from one tensor: two turns
+    stage.push("a", one, 600, 400)                       # ... 1000 samples: outputs 64 .. 963
+    stage.push("b", two, 5, 50)                          # a second tensor, another window: 50 - 12 = 38 outputs
+    stage.push("c", one, 1000, 20, last=True)            # closed at 20 samples: every output
+    stage.push("d", one, 1100, 30)                       # 30 <= 2 h: appended, nothing final
+    plan = stage.plan()
+    assert plan.rows == [("b", 0, 38, -1), ("a", 64, 900, -1), ("c", 0, 20, 20), ("d", 0, 0, -1)]       # by window, stable
+    assert plan.groups == [((6, 160, ceiling), 0, 1, 38), ((18, 480, ceiling), 1, 4, 900)]
+    assert plan.starts == [0, 38, 938, 958, 958] and plan.ring_needed == 1000    # output 64 still reads sample 0: 64 - 18 - 480 < 0
+    # one call per (turn, tensor), no slot twice in a call: the second tensor, the first turn of the first, its second turn
+    assert plan.calls == {(0, two.data_ptr(), 64): [(1, 0, 50, 5)],
+                          (0, one.data_ptr(), 1200): [(0, 100, 500, 100), (2, 0, 20, 1000), (3, 0, 30, 1100)],
+                          (1, one.data_ptr(), 1200): [(0, 600, 400, 600)]}
+    assert list(plan.calls) == [(0, two.data_ptr(), 64), (0, one.data_ptr(), 1200), (1, one.data_ptr(), 1200)]
+    assert (plan.n_app, plan.words) == (5, 4 * 5 + 6 * 4)
+    desc = np.full(48, -7, dtype=np.int64)
+    plan.pack(desc, stage._word5)
+    assert desc.tolist() == [1, 0, 50, 5,
+                             0, 100, 500, 100, 2, 0, 20, 1000, 3, 0, 30, 1100,
+                             0, 600, 400, 600,
+                             1, 0, 38, -1, 0, 0x3F800000,
+                             0, 64, 900, -1, 38, 0x40000000,
+                             2, 0, 20, 20, 938, 0x3F000000,
+                             3, 0, 0, -1, 958, 0x3F800000,
+                             -7, -7, -7, -7]
+    stage.commit(plan)
+    assert [(st.emitted, st.on_device, st.queue) for st in stage.streams.values()] == [(964, 1000, []), (38, 50, []), (20, 20, []),
+                                                                                      (0, 30, [])]
+    assert stage.finished("c") and not stage.finished("a") and stage.plan().rows == []
+    assert stage.rings is None and stage.device_allocations == 0                 # planning and packing touch no device

@@ -222,3 +222,48 @@ def test_tool_flags_parse_and_refuse(tmp_path):
     res = run_tool("stream_transpose.py", src, "-o", dst, "--model_id", model, "--output-rate", "input")
     assert res.returncode == 1 and "--output-rate input" in res.stderr and "--resample" in res.stderr
     assert not os.path.exists(dst)
+
+
+def test_a_worked_tick_packs_the_descriptor_words_of_the_headers():
+    """Four streams, one tick, every word by hand from the row layouts of mbexwn_live.h (append: slot, abs_start, count,
+    offset) and mbexwn_live_out.h (emit: in_slot, first_out, n_out_new, n_total_in or -1, out_offset, 0).  To 48 kHz (up 2,
+    down 1, half 44) output k is final once 2 have - 45 >= k; to 16 kHz (up 2, down 3, half 66) once 2 have - 67 >= 3 k."""
+    import torch
+    one, two = torch.zeros(400, dtype=torch.float32), torch.zeros(128, dtype=torch.float32)
+    stage = live.StreamingOutputResampler(MODEL_RATE)
+    for sid, rate in (("a", 48000), ("b", 16000), ("c", 48000), ("d", 48000)):      # slots 0 .. 3
+        stage.open(sid, rate)
+    stage.push("a", one, 0, 40)                          # an earlier tick: 2 * 40 - 45 = 35, outputs 0 .. 35
+    first = stage.plan()
+    assert first.rows == [("a", 0, 36, -1)] and first.starts == [0, 36]
+    stage.commit(first)
+    stage.push("a", one, 40, 100)                        # two pushes from one tensor: two turns
+    stage.push("a", one, 140, 50)                        # ... 190 samples: 2 * 190 - 45 = 335, outputs 36 .. 335
+    stage.push("b", two, 10, 90)                         # a second tensor, another rate: 2 * 90 - 67 = 113 = 3 * 37 + 2, 38 outputs
+    stage.push("c", one, 200, 30, last=True)             # closed at 30 samples: all ceil(30 * 2 / 1) = 60 outputs
+    stage.push("d", one, 300, 20)                        # 2 * 20 - 45 < 0: appended, nothing final
+    plan = stage.plan()
+    assert plan.rows == [("b", 0, 38, -1), ("a", 36, 300, -1), ("c", 0, 60, 30), ("d", 0, 0, -1)]       # by rate, stable
+    assert plan.groups == [(16000, 0, 1, 38), (48000, 1, 4, 300)]
+    assert plan.starts == [0, 38, 338, 398, 398] and plan.ring_needed == 190     # output 36 still reads from sample 0 on
+    # one call per (turn, tensor), no slot twice in a call: the second tensor, the first turn of the first, its second turn
+    assert plan.calls == {(0, two.data_ptr(), 128): [(1, 0, 90, 10)],
+                          (0, one.data_ptr(), 400): [(0, 40, 100, 40), (2, 0, 30, 200), (3, 0, 20, 300)],
+                          (1, one.data_ptr(), 400): [(0, 140, 50, 140)]}
+    assert list(plan.calls) == [(0, two.data_ptr(), 128), (0, one.data_ptr(), 400), (1, one.data_ptr(), 400)]
+    assert (plan.n_app, plan.words) == (5, 4 * 5 + 6 * 4)
+    desc = np.full(48, -7, dtype=np.int64)
+    plan.pack(desc, stage._word5)
+    assert desc.tolist() == [1, 0, 90, 10,
+                             0, 40, 100, 40, 2, 0, 30, 200, 3, 0, 20, 300,
+                             0, 140, 50, 140,
+                             1, 0, 38, -1, 0, 0,
+                             0, 36, 300, -1, 38, 0,
+                             2, 0, 60, 30, 338, 0,
+                             3, 0, 0, -1, 398, 0,
+                             -7, -7, -7, -7]
+    stage.commit(plan)
+    assert [(st.emitted, st.on_device, st.queue) for st in stage.streams.values()] == [(336, 190, []), (38, 90, []), (60, 30, []),
+                                                                                      (0, 20, [])]
+    assert stage.finished("c") and not stage.finished("a") and stage.plan().rows == []
+    assert stage.rings is None and stage.device_allocations == 0                 # planning and packing touch no device
